@@ -21,6 +21,11 @@ so `roofline` / `roofline_kernels` carry the duration a launch has between its r
 the old figure -- HIP events around a loop of back-to-back launches of the one kernel on warm slabs -- stays as
 `ms_per_launch_loop`.  Whole phases (forward, BPTT chain + weight gradients) are bracketed with HIP events in the
 same pass (`phases_ms`).
+
+--dump-outputs DIR (e.g. bench_outputs, git-ignored): after the timed steps, before anything else runs a step, rank 0
+writes what the last timed step handed its caller as DIR/<name>.npy in float32: `loss`, every parameter after the Adam
+update (`param.<name>`) and its gradient (`grad.<name>`).  The inputs depend on the arguments alone (seeded init and
+data), so two builds can be compared array by array.
 """
 from __future__ import annotations
 
@@ -168,7 +173,37 @@ def parse_args(argv=None):
     ap.add_argument("--master-port", type=int, default=29533)
     ap.add_argument("--phase-events", type=int, default=0, help="after the timed region, bracket the phases of this many more steps with HIP events (phase_ms in the line: pack+forward, head/loss, BPTT+weight gradients, all-reduce+Adam)")
     ap.add_argument("--lib", default=None, help="load this build of the library (A/B copies made by nasa-niswan_amd/build.py --out=...) instead of the product one")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's loss, updated parameters and gradients to DIR/<name>.npy (float32)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def step_outputs(loss, model):
+    """{name: float32 array} of what one FusedTrainer.step() hands its caller: the loss and, by parameter name, the updated
+    weights and their gradients (the trainer leaves both in the model's parameters)."""
+    import numpy as np
+    out = {"loss": np.asarray([float(loss)], dtype=np.float32)}
+    for name, p in model.named_parameters():
+        out[f"param.{name}"] = p.detach().float().cpu().numpy()
+        out[f"grad.{name}"] = p.grad.detach().float().cpu().numpy()
+    return out
+
+
+def write_outputs(directory, arrays):
+    """DIR/<name>.npy for every array; refuses (before writing anything) more than DUMP_LIMIT_BYTES in all."""
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES} byte limit")
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 def spawn_ranks(args, argv):
@@ -324,6 +359,8 @@ def main():
     elapsed, loss = timed(args.steps)
     local_elapsed = timed.local
     final_loss = float(loss)
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, step_outputs(final_loss, model))
     long_elapsed = timed(args.long_steps)[0] if args.long_steps > 0 else None
 
     # ---- the gradient all-reduce by itself (N > 1 or --force-dist): HIP events around dist.all_reduce on the step's

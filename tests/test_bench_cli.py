@@ -128,3 +128,35 @@ def test_probe_pass_keeps_collectives_symmetric_across_ranks(tmp_path):
     r0, r1 = torch.load(out + ".0"), torch.load(out + ".1")
     assert r0["steps"] == r1["steps"] == 4 and r0["sum"] == 8.0          # 3 probed steps + 1 plain one, on both ranks
     assert r0["dur"] and not r1["dur"] and r0["probed"] == 1 and r1["probed"] == 0
+
+
+def test_steps_must_be_positive():
+    bench = _bench()
+    assert bench.parse_args(["--steps", "7"]).steps == 7
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+
+
+def test_dump_outputs_writes_loss_parameters_and_gradients(tmp_path):
+    """--dump-outputs: the loss, every updated parameter and its gradient as float32 .npy files named after the parameter."""
+    import torch
+    bench = _bench()
+    assert bench.parse_args([]).dump_outputs is None and bench.parse_args(["--dump-outputs", "d"]).dump_outputs == "d"
+    net = torch.nn.Conv2d(3, 4, 3)
+    for p in net.parameters():
+        p.grad = torch.full_like(p, 0.5)
+    arrays = bench.step_outputs(torch.tensor(1.25), net)
+    assert sorted(arrays) == ["grad.bias", "grad.weight", "loss", "param.bias", "param.weight"]
+    bench.write_outputs(str(tmp_path / "out"), arrays)
+    assert np.load(tmp_path / "out" / "loss.npy").tolist() == [1.25]
+    w = np.load(tmp_path / "out" / "param.weight.npy")
+    assert w.dtype == np.float32 and np.array_equal(w, net.weight.detach().numpy())
+    assert np.array_equal(np.load(tmp_path / "out" / "grad.bias.npy"), np.full(4, 0.5, dtype=np.float32))
+
+
+def test_dump_outputs_refuses_more_than_the_limit(tmp_path):
+    bench = _bench()
+    big = {"x": np.zeros(bench.DUMP_LIMIT_BYTES // 4 + 1, dtype=np.float32)}
+    with pytest.raises(SystemExit):
+        bench.write_outputs(str(tmp_path / "out"), big)
+    assert not (tmp_path / "out").exists()

@@ -366,6 +366,31 @@ def test_timing_probes_bracket_every_launch_and_change_nothing(pkg, hidden):
     assert len(d[(1, 0)]) == 1 and len(d[(7, 3)]) == T - 2 and len(d[(7, 2)]) == 2 and all(us > 0 for _, us in d[(7, 3)]) and len(d[(5, 0)]) == 1
 
 
+def test_bench_dump_outputs_is_the_last_timed_step_and_reproducible(pkg, tmp_path):
+    """bench.py --dump-outputs: the loss file is the line's final_loss, every parameter and gradient is there, and a second
+    run with the same arguments writes the same arrays (seeded inputs, deterministic step)."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    runs = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "1",
+               "--no-cpu-baseline", "--no-kernel-rooflines", "--long-steps", "0", "--dump-outputs", str(d)]
+        out = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+        line = json.loads([l for l in out.stdout.splitlines() if l.startswith('{"metric"')][-1])
+        assert line["steps"] == 2 and line["ms_per_step"] > 0
+        arrays = {p.name[:-4]: np.load(p) for p in d.glob("*.npy")}
+        assert abs(float(arrays["loss"][0]) - line["final_loss"]) <= 1e-5          # (the line rounds to 5 decimals)
+        runs.append(arrays)
+    names = set(runs[0])
+    assert {"param.conv.weight", "grad.conv.weight", "param.layers.0.conv.weight", "grad.layers.2.conv.bias"} <= names
+    assert names == set(runs[1]) and all(runs[0][k].dtype == np.float32 for k in names)
+    for k in names:
+        assert np.array_equal(runs[0][k], runs[1][k]), k
+
+
 def test_bench_starts_its_own_ranks(pkg):
     """`python bench.py --gpus 1 --force-dist` is what the driver runs for N = 1; for N > 1 the same form must start N
     ranks by itself.  On this one-GPU box: the parent decides from argv, the torchrun child runs the single rank."""
