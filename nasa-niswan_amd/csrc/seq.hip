@@ -120,6 +120,7 @@ static Probe make_probe(const nint_seq* s, bool bwd, void* stream) {
 static int seq_check(const nint_seq* s) {
   if (!s || s->L < 1 || s->L > NINT_MAX_LAYERS || s->B < 1 || s->T < 1) return NINT_E_ARG;
   if (s->dtype != NINT_F32 && s->dtype != NINT_BF16) return NINT_E_ARG;
+  if (s->wave < 0 || s->wave > 5) return NINT_E_ARG;          // the modes of nint_seq.wave (nint.h); no other value is a mode
   if (!s->xs) return NINT_E_ARG;
   for (int l = 0; l < s->L; ++l) {
     if (!s->h[l] || !s->c[l]) return NINT_E_ARG;

@@ -14,18 +14,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import nasa_niswan_amd as pkg  # noqa: E402
 from nasa_niswan_amd import engine  # noqa: E402
 from oracle import convlstm_oracle as O  # noqa: E402
-
-
-def stored_dG(eng, ws, l):
-    """ws.dG[l] (ET halo slab [T*B][Hh][Wh][4*Ch16], column (cblock*4+gate)*16+col) -> f32 (T*B, 4*Ch, H, W) in the reference's
-    out-channel order [i,f,g,o]: the summands the weight-gradient kernel reduced (layout only, no arithmetic)."""
-    g, cfg = ws.g, eng.cfgs[l]
-    Ch16 = (cfg.Ch + 15) // 16 * 16
-    N = ws.T * ws.B
-    t = ws.dG[l].view(torch.bfloat16 if eng.es == 2 else torch.float32).view(N, g.Hh, g.Wh, 4 * Ch16)
-    t = t[:, g.P:g.P + ws.H, g.P:g.P + ws.W, :].float()
-    t = t.reshape(N, ws.H, ws.W, Ch16 // 16, 4, 16).permute(0, 4, 3, 5, 1, 2).reshape(N, 4, Ch16, ws.H, ws.W)
-    return t[:, :, :cfg.Ch].reshape(N, 4 * cfg.Ch, ws.H, ws.W)
+from oracle.stored_audit import stored_dG  # noqa: E402
 
 
 def check_bias_grad(tag, name, db, dbo, dG_stored, dG_oracle, dtype):
