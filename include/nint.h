@@ -313,7 +313,19 @@ int nint_adam_flat(float* p, const float* g, float* m, float* v, size_t n, doubl
  *                              (image t*B+b, ET = dtype, channels-last, channel padding zeroed) on the padded
  *                              grid g->H x g->W = Hp x Wp: the f32 NCHW tensor of dataset.py:538 and the
  *                              nint_pack_btchw pass never exist.  Values are the f32 result rounded once to ET.
- * t0: host array of B non-negative window starts. */
+ * t0: host array of B non-negative window starts.
+ *
+ * nint_preproc_fuse_pad_static[_batch|_slab]: the same three with `nstatic` after `nsrc`: the LAST nstatic of the
+ *                              nsrc sources are time-invariant (the static attributes of dataset.py:100-122,
+ *                              concatenated after the dynamic channels before the pad, :531-533 / :622-624).  A static
+ *                              source is laid out (lev_i, H, W) f32 -- one "time step" -- and is read at that step for
+ *                              every sample and window step: t0 does not apply to it (and srcs[i] of the single-sample
+ *                              entry is its base, not a window offset).  It counts as one source of lev_i levels against
+ *                              the 16-source limit; mean / std cover all C channels, static ones included.  Static
+ *                              channels are ordinary fused channels otherwise, so in mode 0 the halo rows of channel c
+ *                              come from channel C-1-c across the whole C (the met channels' halo from the static
+ *                              channels and the other way round).  nstatic outside [0, nsrc]: NINT_E_ARG before any
+ *                              launch.  The three entries above are these with nstatic = 0. */
 #define NINT_PRE_MAX_B 64   /* samples per launch (larger batches are split internally) */
 int nint_preproc_fuse_pad(const float* const* srcs /*host*/, const int* lev /*host*/, int nsrc,
                           const float* mean, const float* std, float* out, int T, int H, int W,
@@ -325,6 +337,16 @@ int nint_preproc_fuse_pad_slab(const float* const* srcs /*host*/, const int* lev
                                const float* mean, const float* std, const int* t0 /*host*/, int B, void* xs_slab,
                                int Cxp, int xfold_k /* 0: plain slab; k: horizontally folded for kernel size k */,
                                int T, int H, int W, const nint_geom* g /*host*/, int mode, int dtype, void* stream);
+int nint_preproc_fuse_pad_static(const float* const* srcs /*host*/, const int* lev /*host*/, int nsrc, int nstatic,
+                                 const float* mean, const float* std, float* out, int T, int H, int W,
+                                 int Hp, int Wp, int mode, void* stream);
+int nint_preproc_fuse_pad_static_batch(const float* const* srcs /*host*/, const int* lev /*host*/, int nsrc, int nstatic,
+                                       const float* mean, const float* std, const int* t0 /*host*/, int B, float* out,
+                                       int T, int H, int W, int Hp, int Wp, int mode, void* stream);
+int nint_preproc_fuse_pad_static_slab(const float* const* srcs /*host*/, const int* lev /*host*/, int nsrc, int nstatic,
+                                      const float* mean, const float* std, const int* t0 /*host*/, int B, void* xs_slab,
+                                      int Cxp, int xfold_k, int T, int H, int W, const nint_geom* g /*host*/, int mode,
+                                      int dtype, void* stream);
 
 #ifdef __cplusplus
 }

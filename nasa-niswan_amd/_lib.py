@@ -79,6 +79,11 @@ SIGNATURES = {
     "nint_preproc_fuse_pad": (_I, [C.POINTER(vp), C.POINTER(_I), _I, vp, vp, vp, _I, _I, _I, _I, _I, _I, vp]),
     "nint_preproc_fuse_pad_batch": (_I, [C.POINTER(vp), C.POINTER(_I), _I, vp, vp, C.POINTER(_I), _I, vp, _I, _I, _I, _I, _I, _I, vp]),
     "nint_preproc_fuse_pad_slab": (_I, [C.POINTER(vp), C.POINTER(_I), _I, vp, vp, C.POINTER(_I), _I, vp, _I, _I, _I, _I, _I, _PG, _I, _I, vp]),
+    "nint_preproc_fuse_pad_static": (_I, [C.POINTER(vp), C.POINTER(_I), _I, _I, vp, vp, vp, _I, _I, _I, _I, _I, _I, vp]),
+    "nint_preproc_fuse_pad_static_batch": (_I, [C.POINTER(vp), C.POINTER(_I), _I, _I, vp, vp, C.POINTER(_I), _I, vp, _I, _I, _I, _I, _I,
+                                                _I, vp]),
+    "nint_preproc_fuse_pad_static_slab": (_I, [C.POINTER(vp), C.POINTER(_I), _I, _I, vp, vp, C.POINTER(_I), _I, vp, _I, _I, _I, _I, _I,
+                                               _PG, _I, _I, vp]),
 }
 
 _lib = None

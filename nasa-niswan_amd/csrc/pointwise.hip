@@ -1294,15 +1294,25 @@ extern "C" int nint_adam_flat(float* p, const float* g, float* m, float* v, size
 //   the SOURCE channel that is actually read (the reference z-scores before it pads).
 // Sources are RECORDS (n_steps, lev_i, H, W) resident in HBM; sample b of a batch reads the time steps
 // [t0[b], t0[b]+T) of every source (the sliding window of dataset.py:614-616 as a pointer offset), so one
-// launch serves the whole batch.  All index arithmetic is per row (scalar); threads only walk x.
+// launch serves the whole batch.  The trailing sources from first_static on are TIME-INVARIANT (the static
+// attributes of dataset.py:100-122, concatenated after the dynamic channels at :531-533 / :622-624): one
+// (lev_i, H, W) "time step", read at step 0 whatever t0[b] + t is.  They are ordinary fused channels otherwise,
+// so the mode-0 halo of channel c still comes from channel C-1-c across the whole C.
+// All index arithmetic is per row (scalar); threads only walk x.
 #define PRE_MAX_SRC 16
 #define PRE_MAX_B NINT_PRE_MAX_B
 struct PreArgs {
   const float* src[PRE_MAX_SRC];
   int first_c[PRE_MAX_SRC + 1];   // first fused channel of each source
   int nsrc;
+  int first_static;               // sources [first_static, nsrc) are time-invariant (nsrc: none)
   int t0[PRE_MAX_B];              // first time step of each sample's window
 };
+
+// time step of source s that sample b reads at window step t (0 for a time-invariant source)
+__device__ __forceinline__ size_t pre_step(const PreArgs& a, int s, int b, int t) {
+  return s >= a.first_static ? 0 : (size_t)(a.t0[b] + t);
+}
 
 // latitude rule: source row of padded row yp, and whether the row comes from the channel-flipped source
 __device__ __forceinline__ int pre_src_row(int yp, int H, int pt, int pb, int mode, bool* flip) {
@@ -1343,7 +1353,7 @@ __global__ __launch_bounds__(256) void preproc_nchw_kernel(PreArgs a, const floa
     const int cs = f ? C - 1 - c : c;
     int s, lev, nlev;
     pre_find(a, cs, &s, &lev, &nlev);
-    base[f] = a.src[s] + ((size_t)(a.t0[b] + t) * nlev + lev) * H * W;
+    base[f] = a.src[s] + (pre_step(a, s, b, t) * nlev + lev) * H * W;
     m[f] = mean[cs]; sd[f] = stdv[cs];
   }
   float* o = out + (((size_t)b * T + t) * C + c) * Hp * Wp;
@@ -1383,7 +1393,7 @@ __global__ __launch_bounds__(256) void preproc_slab_kernel(PreArgs a, const floa
   for (int cs = threadIdx.x; cs < C; cs += 256) {   // one descriptor per source channel: (source, level) found once per row block
     int s, lev, nlev;
     pre_find(a, cs, &s, &lev, &nlev);
-    rows[cs] = RowDesc{a.src[s] + ((size_t)(a.t0[b] + t) * nlev + lev) * H * W + (size_t)ys * W, mean[cs], stdv[cs],
+    rows[cs] = RowDesc{a.src[s] + (pre_step(a, s, b, t) * nlev + lev) * H * W + (size_t)ys * W, mean[cs], stdv[cs],
                        flip ? C - 1 - cs : cs};
   }
   __syncthreads();
@@ -1396,13 +1406,15 @@ __global__ __launch_bounds__(256) void preproc_slab_kernel(PreArgs a, const floa
   }, kf);
 }
 
-static int pre_args(PreArgs* a, const float* const* srcs, const int* lev, int nsrc, int H, int W, int Hp, int Wp, int mode) {
-  if (!srcs || !lev || nsrc <= 0 || nsrc > PRE_MAX_SRC) return NINT_E_ARG;
+static int pre_args(PreArgs* a, const float* const* srcs, const int* lev, int nsrc, int nstatic, int H, int W, int Hp, int Wp,
+                    int mode) {
+  if (!srcs || !lev || nsrc <= 0 || nsrc > PRE_MAX_SRC || nstatic < 0 || nstatic > nsrc) return NINT_E_ARG;
   if (Hp < H || Wp < W || (mode != 0 && mode != 1)) return NINT_E_ARG;
   const int pl = (Wp - W) / 2, pr = Wp - W - pl, pt = (Hp - H) / 2, pb = Hp - H - pt;
   // the reference raises AttributeError for oversize padding (dataset.py:80,98)
   if (pl > W || pr > W || pt + 1 > H || pb + 1 > H) return NINT_E_SHAPE;
   a->nsrc = nsrc;
+  a->first_static = nsrc - nstatic;
   int c = 0;
   for (int i = 0; i < nsrc; ++i) {
     if (!srcs[i] || lev[i] <= 0) return NINT_E_ARG;
@@ -1414,12 +1426,12 @@ static int pre_args(PreArgs* a, const float* const* srcs, const int* lev, int ns
   return c;
 }
 
-extern "C" int nint_preproc_fuse_pad_batch(const float* const* srcs, const int* lev, int nsrc, const float* mean,
-                                           const float* stdv, const int* t0, int B, float* out, int T, int H, int W,
-                                           int Hp, int Wp, int mode, void* stream) {
+extern "C" int nint_preproc_fuse_pad_static_batch(const float* const* srcs, const int* lev, int nsrc, int nstatic,
+                                                  const float* mean, const float* stdv, const int* t0, int B, float* out,
+                                                  int T, int H, int W, int Hp, int Wp, int mode, void* stream) {
   if (!mean || !stdv || !out || !t0 || T <= 0 || B <= 0) return NINT_E_ARG;
   PreArgs a;
-  const int C = pre_args(&a, srcs, lev, nsrc, H, W, Hp, Wp, mode);
+  const int C = pre_args(&a, srcs, lev, nsrc, nstatic, H, W, Hp, Wp, mode);
   if (C < 0) return C;
   for (int b0 = 0; b0 < B; b0 += PRE_MAX_B) {
     const int nb = B - b0 < PRE_MAX_B ? B - b0 : PRE_MAX_B;
@@ -1438,29 +1450,43 @@ extern "C" int nint_preproc_fuse_pad_batch(const float* const* srcs, const int* 
   return NINT_OK;
 }
 
+extern "C" int nint_preproc_fuse_pad_batch(const float* const* srcs, const int* lev, int nsrc, const float* mean,
+                                           const float* stdv, const int* t0, int B, float* out, int T, int H, int W,
+                                           int Hp, int Wp, int mode, void* stream) {
+  return nint_preproc_fuse_pad_static_batch(srcs, lev, nsrc, 0, mean, stdv, t0, B, out, T, H, W, Hp, Wp, mode, stream);
+}
+
+extern "C" int nint_preproc_fuse_pad_static(const float* const* srcs, const int* lev, int nsrc, int nstatic,
+                                            const float* mean, const float* stdv, float* out, int T, int H, int W, int Hp,
+                                            int Wp, int mode, void* stream) {
+  const int t0 = 0;     // srcs already point at the window's first time step (static sources: at their only step)
+  return nint_preproc_fuse_pad_static_batch(srcs, lev, nsrc, nstatic, mean, stdv, &t0, 1, out, T, H, W, Hp, Wp, mode, stream);
+}
+
 extern "C" int nint_preproc_fuse_pad(const float* const* srcs, const int* lev, int nsrc, const float* mean,
                                      const float* stdv, float* out, int T, int H, int W, int Hp, int Wp, int mode,
                                      void* stream) {
-  const int t0 = 0;     // srcs already point at the window's first time step
-  return nint_preproc_fuse_pad_batch(srcs, lev, nsrc, mean, stdv, &t0, 1, out, T, H, W, Hp, Wp, mode, stream);
+  return nint_preproc_fuse_pad_static(srcs, lev, nsrc, 0, mean, stdv, out, T, H, W, Hp, Wp, mode, stream);
 }
 
-extern "C" int nint_preproc_fuse_pad_slab(const float* const* srcs, const int* lev, int nsrc, const float* mean,
-                                          const float* stdv, const int* t0, int B, void* xs_slab, int Cxp, int xfold_k,
-                                          int T, int H, int W, const nint_geom* g, int mode, int dtype, void* stream) {
+extern "C" int nint_preproc_fuse_pad_static_slab(const float* const* srcs, const int* lev, int nsrc, int nstatic,
+                                                 const float* mean, const float* stdv, const int* t0, int B, void* xs_slab,
+                                                 int Cxp, int xfold_k, int T, int H, int W, const nint_geom* g, int mode,
+                                                 int dtype, void* stream) {
   if (!mean || !stdv || !xs_slab || !t0 || !g || T <= 0 || B <= 0) return NINT_E_ARG;
   if (xfold_k < 0 || (xfold_k > 1 && !(xfold_k & 1))) return NINT_E_ARG;
   const int kf = xfold_k > 1 ? xfold_k : 1;
   if (dtype != NINT_BF16 && dtype != NINT_F32) return NINT_E_ARG;
   const int Hp = g->H, Wp = g->W;               // the model runs on the padded grid (launcher.sh:24)
   PreArgs a;
-  const int C = pre_args(&a, srcs, lev, nsrc, H, W, Hp, Wp, mode);
+  const int C = pre_args(&a, srcs, lev, nsrc, nstatic, H, W, Hp, Wp, mode);   // C counts the static channels too
   if (C < 0) return C;
   if (Cxp < C * kf || Cxp % (dtype == NINT_BF16 ? 8 : 4)) return NINT_E_ARG;
   if ((((uintptr_t)xs_slab) & 15) != 0) return NINT_E_ALIGN;
   const size_t tile_bytes = nint_round_up(C * (int)sizeof(RowDesc), 16) + (size_t)C * (W + 1) * sizeof(float);
   if (tile_bytes > 160 * 1024) return NINT_E_LDS;
-  // widest row vector every source row's alignment allows (rows start at multiples of W floats from the record base)
+  // widest row vector every source row's alignment allows (rows start at multiples of W floats from the record base,
+  // static sources included)
   int vw = W % 4 == 0 ? 4 : (W % 2 == 0 ? 2 : 1);
   for (int i = 0; i < nsrc; ++i) {
     const uintptr_t p = (uintptr_t)srcs[i];
@@ -1489,4 +1515,11 @@ extern "C" int nint_preproc_fuse_pad_slab(const float* const* srcs, const int* l
     NINT_LAUNCH_CHECK();
   }
   return NINT_OK;
+}
+
+extern "C" int nint_preproc_fuse_pad_slab(const float* const* srcs, const int* lev, int nsrc, const float* mean,
+                                          const float* stdv, const int* t0, int B, void* xs_slab, int Cxp, int xfold_k,
+                                          int T, int H, int W, const nint_geom* g, int mode, int dtype, void* stream) {
+  return nint_preproc_fuse_pad_static_slab(srcs, lev, nsrc, 0, mean, stdv, t0, B, xs_slab, Cxp, xfold_k, T, H, W, g, mode,
+                                           dtype, stream);
 }

@@ -15,6 +15,13 @@ levels as 3L level-channels beside the two 2-D fields (C = 3L+2) and predicts th
 levels; L=1 is the reference.  An ``in_channels`` that is not 3L+2 (BASELINE configs[0]: 4 channels
 on a 32x32 grid) synthesises that many generic fields instead of the named ones.
 
+Static attributes (reference dataset.py:100-122, used at :531-533 / :622-624): S time-invariant (H, W) land-surface fields,
+z-scored over space with their own statistics, repeated over the T steps and concatenated AFTER the dynamic channels,
+before the halo pad (so they take part in the mode-0 channel-flip quirk of the pad like any other channel).  The reference
+switches them on with ``in_channels > 5``; here they are explicit -- ``static=`` (S, H, W) / ``static_channels=S`` -- because
+the level-fused extension already has C = 3L+2 > 5 without them.  C becomes 3L+2+S.  A static field with zero spatial std
+is refused (the reference would divide by zero and train on NaN).
+
 Two device paths feed the model (the whole record stays resident in HBM, a window is a pointer offset):
 ``device_batch`` materialises the reference's (B,T,C,Hp,Wp) f32 tensor (one launch per batch);
 ``slab_batch`` returns a handle that the engine asks to write the SAME values straight into its bf16/f32
@@ -51,23 +58,24 @@ class SlabBatch:
         dv = ds._device_arrays()
         B, T, Cc, Hp, Wp = self.shape
         assert (ws.B, ws.T, ws.H, ws.W) == (B, T, Hp, Wp) and Cc == eng.cfgs[0].Cx
-        ptrs, lev = ds._sources(dv)
+        ptrs, lev, nstatic = ds._sources(dv)
         H, W = ds.grid
         t0 = (C.c_int * B)(*[int(t) for t in self.t0])
         lib = _lib.load()
-        rc = lib.nint_preproc_fuse_pad_slab(ptrs, lev, len(lev), ptr(dv["mean"]), ptr(dv["std"]), t0, B, ptr(ws.xs), ws.Cxp0,
-                                            eng.cfgs[0].k if eng.cfgs[0].xfold else 0, T, H, W, C.byref(ws.g), ds.mode, eng.dt,
-                                            stream_ptr())
+        rc = lib.nint_preproc_fuse_pad_static_slab(ptrs, lev, len(lev), nstatic, ptr(dv["mean"]), ptr(dv["std"]), t0, B,
+                                                   ptr(ws.xs), ws.Cxp0, eng.cfgs[0].k if eng.cfgs[0].xfold else 0, T, H, W,
+                                                   C.byref(ws.g), ds.mode, eng.dt, stream_ptr())
         if rc == _lib.NINT_E_LDS:
             # a channel-row tile beyond the 160 KiB of LDS (hundreds of channels on a wide grid): the same values through
             # the f32 tensor and the pack kernel, whose generic path has no such limit (bit-identical by construction:
             # tests/test_gpu_train.py::test_slab_batch_is_bit_identical_to_preproc_then_pack)
             X = torch.empty(B, T, Cc, Hp, Wp, dtype=torch.float32, device=self.device)
-            check(lib.nint_preproc_fuse_pad_batch(ptrs, lev, len(lev), ptr(dv["mean"]), ptr(dv["std"]), t0, B, ptr(X),
-                                                  T, H, W, Hp, Wp, ds.mode, stream_ptr()), "nint_preproc_fuse_pad_batch")
+            check(lib.nint_preproc_fuse_pad_static_batch(ptrs, lev, len(lev), nstatic, ptr(dv["mean"]), ptr(dv["std"]), t0, B,
+                                                         ptr(X), T, H, W, Hp, Wp, ds.mode, stream_ptr()),
+                  "nint_preproc_fuse_pad_static_batch")
             eng.pack_input(ws, X)
             return
-        check(rc, "nint_preproc_fuse_pad_slab")
+        check(rc, "nint_preproc_fuse_pad_static_slab")
 
 
 def reference_split(n_steps: int) -> Tuple[int, int]:
@@ -84,7 +92,7 @@ class _ResidentRecord(torch.utils.data.Dataset):
     already in host memory: statistics over the training part, windows, period split, one upload of the record."""
 
     def _setup(self, fields, yraw, period: str, padding, in_channels: int, sequence_length: int, levels: int,
-               grid: Tuple[int, int], pad_mode: str, device, pinned: bool = False):
+               grid: Tuple[int, int], pad_mode: str, device, pinned: bool = False, static=None):
         self.period, self.padding, self.seq_len, self.levels = period, tuple(padding) if padding else None, sequence_length, levels
         self.in_channels, self.grid, self.device = in_channels, tuple(grid), torch.device(device)
         self.mode = {"reference": 0, "reflect": 1}[pad_mode]
@@ -102,6 +110,23 @@ class _ResidentRecord(torch.utils.data.Dataset):
         self.X_mean = Xs.mean(axis=(0, 2, 3)).astype(np.float32)
         self.X_std = Xs.std(axis=(0, 2, 3)).astype(np.float32)
         del Xs
+        # static attributes (dataset.py:100-122): (S, H, W), statistics over space with the reference's own expression
+        self.static, self.S_mean, self.S_std = None, None, None
+        if static is not None:
+            S = np.ascontiguousarray(np.asarray(static, dtype=np.float32))
+            if S.ndim != 3 or S.shape[0] < 1 or S.shape[1:] != self.grid:
+                raise ValueError(f"static: expected (S, {self.grid[0]}, {self.grid[1]}) with S >= 1, got {S.shape}")
+            self.S_mean = S.mean(axis=(1, 2)).astype(np.float32)
+            self.S_std = S.std(axis=(1, 2)).astype(np.float32)
+            flat = np.flatnonzero(~(self.S_std > 0))
+            if len(flat):
+                raise ValueError(f"static channel {int(flat[0])} has zero spatial std (constant field): its z-score is "
+                                 "undefined (the reference would divide by zero and train on NaN)")
+            self.static = S
+            self.X_mean = np.concatenate([self.X_mean, self.S_mean])
+            self.X_std = np.concatenate([self.X_std, self.S_std])
+        if len(self.X_mean) != in_channels:
+            raise ValueError(f"in_channels={in_channels}, but the fields and static attributes give {len(self.X_mean)} channels")
         self.y_mean = np.float32(self.yraw[:ntrain].mean())
         self.y_std = np.float32(self.yraw[:ntrain].std())
         nseq = n_steps - sequence_length + 1
@@ -132,6 +157,8 @@ class _ResidentRecord(torch.utils.data.Dataset):
                     return t.pin_memory().to(d, non_blocking=True)
                 return t.to(d)
             self._dev = {name: up(a) for name, a in self.fields}
+            if self.static is not None:
+                self._dev["static"] = up(self.static)
             self._dev.update(y=up(self.yraw), mean=torch.from_numpy(self.X_mean).to(d),
                              std=torch.from_numpy(self.X_std).to(d),
                              ymean=torch.full((self.levels,), float(self.y_mean), device=d),
@@ -139,11 +166,15 @@ class _ResidentRecord(torch.utils.data.Dataset):
         return self._dev
 
     def _sources(self, dv):
-        """(host array of record base pointers, host array of levels per source) in fusion order (dataset.py:526)"""
-        n = len(self.fields)
-        ptrs = (C.c_void_p * n)(*[dv[name].data_ptr() for name, _ in self.fields])
-        lev = (C.c_int * n)(*[a.shape[1] if a.ndim == 4 else 1 for _, a in self.fields])
-        return ptrs, lev
+        """(host array of record base pointers, host array of levels per source, number of trailing time-invariant sources)
+        in fusion order (dataset.py:526, the static attributes last: :531-533)"""
+        srcs = [(dv[name].data_ptr(), a.shape[1] if a.ndim == 4 else 1) for name, a in self.fields]
+        if self.static is not None:
+            srcs.append((dv["static"].data_ptr(), self.static.shape[0]))
+        n = len(srcs)
+        ptrs = (C.c_void_p * n)(*[p for p, _ in srcs])
+        lev = (C.c_int * n)(*[l for _, l in srcs])
+        return ptrs, lev, int(self.static is not None)
 
     def _targets(self, dv, t0s):
         """z-scored targets (dataset.py:596,599) of a batch: the tracer at each window's LAST step, one launch"""
@@ -166,10 +197,11 @@ class _ResidentRecord(torch.utils.data.Dataset):
         t0s = [int(self.first[int(i)]) for i in indices]
         B, T = len(t0s), self.seq_len
         X = torch.empty(B, T, self.in_channels, Hp, Wp, dtype=torch.float32, device=self.device)
-        ptrs, lev = self._sources(dv)
+        ptrs, lev, nstatic = self._sources(dv)
         t0 = (C.c_int * B)(*t0s)
-        check(_lib.load().nint_preproc_fuse_pad_batch(ptrs, lev, len(lev), ptr(dv["mean"]), ptr(dv["std"]), t0, B, ptr(X),
-                                                      T, H, W, Hp, Wp, self.mode, stream_ptr()), "nint_preproc_fuse_pad_batch")
+        check(_lib.load().nint_preproc_fuse_pad_static_batch(ptrs, lev, len(lev), nstatic, ptr(dv["mean"]), ptr(dv["std"]), t0,
+                                                             B, ptr(X), T, H, W, Hp, Wp, self.mode, stream_ptr()),
+              "nint_preproc_fuse_pad_static_batch")
         return X, self._targets(dv, t0s)
 
     def slab_batch(self, indices: Sequence[int]):
@@ -184,13 +216,39 @@ class _ResidentRecord(torch.utils.data.Dataset):
         return X[0], y[0]
 
 
+def synth_static(S: int, grid: Tuple[int, int], seed: int = 0) -> np.ndarray:
+    """S smooth, seeded, non-constant (H, W) f32 fields standing in for static_attrs.nc: an offset plus a few low
+    longitudinal (cyclic) and latitudinal harmonics, each field on its own scale.  Drawn from a generator of its own, so the
+    dynamic fields of a seed do not change with S."""
+    H, W = grid
+    rng = np.random.default_rng([seed, 0x5717])
+    y = (np.arange(H, dtype=np.float64)[:, None] + 0.5) / H
+    x = np.arange(W, dtype=np.float64)[None, :] / W
+    out = np.empty((S, H, W), dtype=np.float32)
+    for s in range(S):
+        a = np.zeros((H, W))
+        for kx in range(4):
+            for ky in range(1, 4):
+                amp, px, py = rng.standard_normal(), rng.uniform(0, 2 * np.pi), rng.uniform(0, 2 * np.pi)
+                a += amp / (1 + kx + ky) * np.cos(2 * np.pi * kx * x + px) * np.cos(np.pi * ky * y + py)
+        out[s] = rng.uniform(-2, 2) + 10.0 ** rng.uniform(-1, 1) * a
+    return out
+
+
 class SyntheticE33OMA_CRNN(_ResidentRecord):
     def __init__(self, period: str, species: str = "bcb", padding: Tuple[int, int] = (100, 154), in_channels: int = 5,
                  sequence_length: int = 10, *, levels: int = 1, n_steps: int = 480, grid: Tuple[int, int] = (90, 144),
-                 pad_mode: str = "reference", device="cuda", seed: int = 0):
+                 pad_mode: str = "reference", device="cuda", seed: int = 0, static_channels: int = 0):
         super().__init__()
         assert species == "bcb", "only the BCB statistics ship with the reference"
-        self.generic = in_channels != 3 * levels + 2       # static attributes (dataset.py:100-122) are out of scope
+        S = int(static_channels)
+        if S < 0:
+            raise ValueError(f"static_channels must be >= 0, got {S}")
+        if S and in_channels != 3 * levels + 2 + S:
+            raise ValueError(f"static_channels={S} with levels={levels} needs in_channels = 3*levels+2+static_channels = "
+                             f"{3 * levels + 2 + S}, got {in_channels}")
+        # without static attributes, an in_channels that is not 3L+2 means that many generic fields
+        self.generic = S == 0 and in_channels != 3 * levels + 2
         H, W = grid
         rng = np.random.default_rng(seed)
 
@@ -214,7 +272,8 @@ class SyntheticE33OMA_CRNN(_ResidentRecord):
             self.src = field("bc_src", (n_steps, H, W), True)
             fields = [("u", self.u), ("v", self.v), ("w", self.w), ("prec", self.prec), ("src", self.src)]
         yraw = field("bc_conc", (n_steps, levels, H, W), True)
-        self._setup(fields, yraw, period, padding, in_channels, sequence_length, levels, grid, pad_mode, device)
+        static = synth_static(S, grid, seed) if S else None
+        self._setup(fields, yraw, period, padding, in_channels, sequence_length, levels, grid, pad_mode, device, static=static)
 
 
 class E33OMA90D_CRNN(_ResidentRecord):
@@ -227,7 +286,11 @@ class E33OMA90D_CRNN(_ResidentRecord):
     extension; prec, src: (n_steps, H, W).  Statistics over the first 3023 steps and the 3023 / 3455 split when the record has
     the reference's 4320 steps (dataset.py:587-612), the same 70 / 10 / 20 % otherwise; windows X[i] = steps [i, i+T), target =
     the tracer at step i+T-1 (dataset.py:598-599,614-616).  The record is uploaded ONCE (page-locked staging, asynchronous
-    copies) and stays resident in HBM; `device_batch` / `slab_batch` / `__getitem__` are those of the synthetic dataset."""
+    copies) and stays resident in HBM; `device_batch` / `slab_batch` / `__getitem__` are those of the synthetic dataset.
+
+    static: optional (S, H, W) static attributes (what the reference reads from static_attrs.nc, dataset.py:100-122; which
+    variables to keep -- the reference drops ``lai_*`` -- is the caller's choice).  They are z-scored over space and
+    appended after the five (3L+2) dynamic channels of every step: in_channels = 3L+2+S."""
 
     def __init__(self, *a, **k):
         raise TypeError("the NetCDF reader of the reference is out of scope (SURVEY.md section 2): use E33OMA90D_CRNN.from_arrays")
@@ -235,7 +298,7 @@ class E33OMA90D_CRNN(_ResidentRecord):
     @classmethod
     def from_arrays(cls, u, v, omega, prec, src, conc, *, period: str = "train", species: str = "bcb",
                     padding: Tuple[int, int] = (100, 154), sequence_length: int = 10, pad_mode: str = "reference",
-                    device="cuda", pinned: bool = True):
+                    device="cuda", pinned: bool = True, static=None):
         self = cls.__new__(cls)
         torch.utils.data.Dataset.__init__(self)
         f32 = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.float32))
@@ -251,5 +314,7 @@ class E33OMA90D_CRNN(_ResidentRecord):
                 raise ValueError(f"{name}: expected {(n, H, W)}, got {a.shape}")
         self.species, self.generic = species, False
         fields = [("u", u), ("v", v), ("w", omega), ("prec", prec), ("src", src)]          # fusion order dataset.py:584
-        self._setup(fields, conc, period, padding, 3 * L + 2, sequence_length, L, (H, W), pad_mode, device, pinned=pinned)
+        nS = np.shape(static)[0] if static is not None and np.ndim(static) else 0
+        self._setup(fields, conc, period, padding, 3 * L + 2 + nS, sequence_length, L, (H, W), pad_mode, device, pinned=pinned,
+                    static=static)
         return self

@@ -4,7 +4,8 @@ MI355X step.  Same flags, same artefacts (`configurations.json`, `logger.npy`,
 `epoch-XXX/generator.pth.tar`, per-epoch print), same schedule (Adam betas (0.5,0.999), StepLR
 stepped once per epoch before validation, checkpoint every 10 epochs); the per-batch
 `loss.item()` / sklearn R2 host syncs (train.py:113-114) are replaced by device accumulators read
-once per epoch.  Added flags: --dtype, --levels, --grid, --synthetic-steps, --pad-mode, --f32-inputs.
+once per epoch.  Added flags: --dtype, --levels, --grid, --synthetic-steps, --pad-mode, --f32-inputs,
+--static-channels.
 
 The data path is on the device too: by default every batch is written by ONE launch of the
 fuse / z-score / halo-pad kernel straight into the model's bf16 input slab (dataset.slab_batch);
@@ -61,6 +62,10 @@ def get_arguments(argv=None, MODEL='LSTM-00', SPECIES='bcb', LEARNING_RATE=1.0E-
     # extensions
     parser.add_argument("--dtype", type=str, default="bf16", choices=["bf16", "f32"])
     parser.add_argument("--levels", type=int, default=1, help="vertical levels fused as channels (C = 3L+2)")
+    parser.add_argument("--static-channels", type=int, default=0,
+                        help="time-invariant static-attribute channels appended after the dynamic ones (reference "
+                             "dataset.py:100-122; C = 3L+2+S, so the reference launcher's --in-channels 8 is S = 3); 0: none, "
+                             "and an --in-channels other than 3L+2 means that many generic fields")
     parser.add_argument("--synthetic-steps", type=int, default=480, help="length of the synthetic record")
     parser.add_argument("--pad-mode", type=str, default="reference", choices=["reference", "reflect"])
     parser.add_argument("--grid", nargs=2, type=int, default=(90, 144),
@@ -112,7 +117,7 @@ def main(args):
     halo = ((args.input_size[0] - H) // 2, (args.input_size[1] - W) // 2)                    # 5,5 in the reference (train.py:102)
     ds_kw = dict(species=args.species, padding=tuple(args.input_size), in_channels=args.in_channels,
                  sequence_length=args.sequence_length, levels=args.levels, n_steps=args.synthetic_steps,
-                 grid=(H, W), pad_mode=args.pad_mode, device=dev)
+                 grid=(H, W), pad_mode=args.pad_mode, device=dev, static_channels=args.static_channels)
     train_dataset = SyntheticE33OMA_CRNN('train', **ds_kw)                                   # train.py:63-65
     val_dataset = SyntheticE33OMA_CRNN('val', **ds_kw)
     get_batch = (lambda ds, idx: ds.device_batch(idx)) if args.f32_inputs else (lambda ds, idx: ds.slab_batch(idx))
