@@ -227,9 +227,9 @@ def _to_bytes(t: torch.Tensor) -> torch.Tensor:
 
 
 def write_halo(geo: Geo, v: torch.Tensor, Cp: int) -> torch.Tensor:
-    """(N, C, H, W) values -> halo slab bytes (ET, zero ring / slack / channel padding)"""
+    """(N, C, H, W) values -> halo slab bytes (ET, zero ring / slack / channel padding), on v's device"""
     N, C = v.shape[:2]
-    s = torch.zeros(N, geo.Hh, geo.Wh, Cp, dtype=geo.et)
+    s = torch.zeros(N, geo.Hh, geo.Wh, Cp, dtype=geo.et, device=v.device)
     s[:, geo.P:geo.P + geo.H, geo.P:geo.P + geo.W, :C] = v.permute(0, 2, 3, 1).to(geo.et)
     return _to_bytes(s)
 
@@ -261,14 +261,14 @@ def _gate_slab(geo: Geo, l: int, v: torch.Tensor, halo: bool, pad_vals) -> torch
     ly = geo.layers[l]
     N = v.shape[0]
     Gc = 4 * ly.Ch16
-    s = torch.zeros(N, geo.H, geo.W, Gc, dtype=geo.et)
+    s = torch.zeros(N, geo.H, geo.W, Gc, dtype=geo.et, device=v.device)
     for gate in range(4):
         for ch in range(ly.Ch, ly.Ch16):
             s[..., ((ch // 16) * 4 + gate) * 16 + ch % 16] = pad_vals[gate]
-    s[..., _gate_cols(ly.Ch16, ly.Ch)] = v.permute(0, 2, 3, 1).to(geo.et)
+    s[..., _gate_cols(ly.Ch16, ly.Ch).to(v.device)] = v.permute(0, 2, 3, 1).to(geo.et)
     if not halo:
         return _to_bytes(s)
-    h = torch.zeros(N, geo.Hh, geo.Wh, Gc, dtype=geo.et)
+    h = torch.zeros(N, geo.Hh, geo.Wh, Gc, dtype=geo.et, device=v.device)
     h[:, geo.P:geo.P + geo.H, geo.P:geo.P + geo.W] = s
     return _to_bytes(h)
 

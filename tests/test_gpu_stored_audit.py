@@ -2,7 +2,13 @@
 values it read out of the workspace (oracle/stored_audit.py: reference and error bound per element), and the padding of
 every slab checked after the pass.  A local mistake -- one tile, one dropped tap of one channel chunk, one stale pixel, a
 stray write into the halo -- shows here as err / bound > 1 where the end-to-end rel-L2 gates of the other files cannot see
-it.  Each case prints its worst err / bound per tensor kind."""
+it.  Each case prints its worst err / bound per tensor kind.
+
+Every layer's weight and bias gradient (the dW / db engine.backward returns) is checked against oracle/wgrad_audit.py's
+gamma_{n+1} sum |dG||cat| bound, built from the stored dG[l], the stored x source (xs, or h[l-1] slots 1..T) and h[l] slots
+0..T-1 (slot 0 skipped from the zero state): the wiring of layers >= 1 (a source one time step off, the wrong layer's slab,
+a wrong skip, another layer's fold-table entry) shows here; the summation itself is checked bit for bit on integer data in
+tests/test_gpu_exact_reductions.py."""
 import time
 
 import pytest
@@ -10,10 +16,11 @@ import torch
 
 from oracle import convlstm_oracle as O
 from oracle import stored_audit as SA
+from oracle import wgrad_audit as WA
 
 pytestmark = pytest.mark.gpu
 
-KINDS = ("gates", "c", "h", "dG", "dx", "dh_init", "dc_init", "zacc")
+KINDS = ("gates", "c", "h", "dG", "dx", "dh_init", "dc_init", "zacc", "dW", "db")
 
 
 @pytest.fixture(scope="module")
@@ -63,7 +70,7 @@ def run_audit(C, hidden, ks, B, T, H, W, dtype, wave=None, rows=0, fuse=None, ha
         if zero:              # zero_state_grads: dc of every layer and dh of every layer but the top one start from zero
             dh_T = [None] * (L - 1) + [dh_T[-1]]
             dc_T = [None] * L
-        _, _, dx = eng.backward(ws, need_dx=True, zero_state_grads=range(L) if zero else ())
+        dWs, dbs, dx = eng.backward(ws, need_dx=True, zero_state_grads=range(L) if zero else ())
         wave_ran = int(ws.seq.wave)
         torch.cuda.synchronize()
         st = SA.read_workspace(eng, ws, dx)
@@ -74,16 +81,30 @@ def run_audit(C, hidden, ks, B, T, H, W, dtype, wave=None, rows=0, fuse=None, ha
     bad = SA.check_padding(geo, st["raw"])
     assert bad == [], (tag, bad)
     worst = SA.audit(geo, Ws, bs, st, dh_T, dc_T, has_init, fwd_ts=fwd_ts, t_min=t_min)
+    for l in range(L):      # the weight / bias gradient of every layer from the slabs it reduced, reference in f64 on the GPU
+        x_src = st["x"] if l == 0 else st["h"][l - 1][B:]
+        rW, rb = WA.wgrad_bound(st["dG"][l].cuda(), x_src.cuda(), st["h"][l].cuda(), ks[l], geo.es, has_init=has_init,
+                                B=B, n_cu=eng.n_cu)
+        worst["dW"] = max(worst.get("dW", 0.0), WA.bound_ratio(dWs[l], rW))
+        worst["db"] = max(worst.get("db", 0.0), WA.bound_ratio(dbs[l], rb))
     print(f"  {tag} {dtype} wave={wave_ran} rows={rows} fuse={fuse if fuse is None else hex(fuse)}: max err/bound  "
-          + "  ".join(f"{k} {worst[k]:.3f}" for k in KINDS if k in worst), flush=True)
+          + "  ".join(f"{k} {worst[k]:.3f}" if k not in ("dW", "db") else f"{k} {worst[k]:.1e}" for k in KINDS if k in worst), flush=True)
     assert max(worst.values()) <= 1.0, (tag, dtype, wave, rows, fuse, worst)
-    assert {"gates", "c", "h", "dG", "dx"} <= set(worst)
+    assert {"gates", "c", "h", "dG", "dx", "dW", "db"} <= set(worst)
+    st["dW"], st["db"] = dWs, dbs
     return worst, eng, st
 
 
 @pytest.mark.parametrize("dtype,wave", [("bf16", 0), ("bf16", 4), ("bf16", 5), ("bf16", None), ("f32", 4)])
 def test_bench_geometry(pkg, dtype, wave):
-    run_audit(62, [64, 32, 16], [5, 3, 3], 2, 3, 100, 154, dtype, wave=wave, tag="bench 62->[64,32,16] 100x154 B=2 T=3")
+    _, eng, st = run_audit(62, [64, 32, 16], [5, 3, 3], 2, 3, 100, 154, dtype, wave=wave, tag="bench 62->[64,32,16] 100x154 B=2 T=3")
+    # the dW bound's margin against a source one time step off: layer 1's x source read from h[0] slots 0..T-1 instead of 1..T
+    B = 2
+    rW, _ = WA.wgrad_bound(st["dG"][1].cuda(), st["h"][0][:-B].cuda(), st["h"][1].cuda(), 3, st["geo"].es, has_init=False, B=B,
+                           n_cu=eng.n_cu)
+    r = WA.bound_ratio(st["dW"][1], rW)
+    print(f"  layer 1 dW against the reference of an x source one step early: err/bound {r:.1f}")
+    assert r > 1.0, r
 
 
 @pytest.mark.parametrize("dtype", ["bf16", "f32"])

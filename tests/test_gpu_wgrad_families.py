@@ -6,8 +6,10 @@
 group of channel tiles per workgroup) wherever it is instantiated.  Both reduce the SAME bf16 slabs, so both are compared
 with an f64 reference computed from exactly those slab values (torch.nn.grad.conv2d_weight on the unpacked slabs): only
 the f32 summation order separates them -- tolerance 2e-5 of the gradient's max (measured: see the printed lines).  Shapes:
-ragged grids (rows not a multiple of 4, columns not a multiple of 32), 62 -> 64 padded input channels, h parts that skip
-the zero-state time step, several split-K workgroups per column, reductions that leave some splits one tile short.
+ragged grids (rows not a multiple of 4, columns not a multiple of 32), 62 -> 64 padded input channels, several split-K
+workgroups per column, reductions that leave some splits one tile short.  (nint_conv_wgrad reduces the h source from its
+first image: the h part that skips the zero-state time step runs inside nint_seq_bwd and is checked bit for bit in
+tests/test_gpu_exact_reductions.py.)
 """
 import ctypes as C
 
@@ -16,7 +18,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-# (Cx, Ch, k, N images, H, W, h_skip via has_init=False and B)
+# (Cx, Ch, k, N images, H, W)
 SHAPES = {
     "cfg3-like-62-128": (62, 128, 3, 4, 30, 70),
     "64-64-ragged": (64, 64, 3, 6, 21, 45),
@@ -39,7 +41,7 @@ def lib():
     return p.load_library()
 
 
-def _run(lib, eng, ws, l, wide, N, skip):
+def _run(lib, eng, ws, l, wide, N):
     from nasa_niswan_amd import _lib
     ly, cfg = eng.layers[l], eng.cfgs[l]
     ly.wide = wide
@@ -89,7 +91,7 @@ def test_both_weight_gradient_families_reduce_the_same_slabs_to_the_f64_sum(lib,
     ref_db = dGr.sum(dim=(0, 2, 3)).cpu()
     out = {}
     for wide in (1, 2):
-        dW, db = _run(lib, eng, ws, 0, wide, N, 0)
+        dW, db = _run(lib, eng, ws, 0, wide, N)
         assert bool(torch.isfinite(dW).all()) and bool(torch.isfinite(db).all()), (name, wide, "unwritten gradient elements")
         eW = float((dW.cpu().double() - ref_dW).abs().max() / ref_dW.abs().max())
         eb = float((db.cpu().double() - ref_db).abs().max() / ref_db.abs().max())
@@ -97,7 +99,7 @@ def test_both_weight_gradient_families_reduce_the_same_slabs_to_the_f64_sum(lib,
         assert eW <= 2e-5 and eb <= 2e-5, (name, wide, eW, eb)
         out[wide] = (dW, db)
         # bitwise reproducible (fixed fold order, no float atomics)
-        dW2, db2 = _run(lib, eng, ws, 0, wide, N, 0)
+        dW2, db2 = _run(lib, eng, ws, 0, wide, N)
         assert torch.equal(dW, dW2) and torch.equal(db, db2), (name, wide, "not reproducible")
     eng.layers[0].wide = 0
     eng.release(ws)
