@@ -3,6 +3,7 @@
 grids at seq_len=12 (BASELINE.json metric / configs[1]).
 
     python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full   # + long window, all-reduce, kernel rooflines, CPU baseline
     python bench.py --gpus 8 [--scaling strong]        # starts its own 8 ranks (torch.distributed.run as a child process)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
@@ -10,12 +11,17 @@ A "step" is one pass of the hot path over one batch resident in HBM: pack -> Con
 (12 steps x 3 layers) -> 1x1 head -> crop+MSE+L1 -> BPTT (pointwise, dgrad, wgrad) -> [RCCL
 all-reduce of the flat gradient bucket] -> Adam.  Rank 0 prints ONE JSON line.
 
+A plain run does only what the headline needs: set up, warm up, time --steps steps, write --dump-outputs, print the
+line.  Everything else it can measure takes runs of its own and comes with --full (see extras()): the long window
+(`value_200steps`), the gradient all-reduce by itself (N > 1 or --force-dist), the kernel rooflines below and the CPU
+baseline.  Without --full those keys of the line are null.
+
 Workload (config.workload = "cfg1-20level"): ConvLSTM(62, (64,32,16), (5,3,3)), head out 20,
 X (B,12,62,100,154) = 3 met fields x 20 levels + precipitation + emission on the 90x144 GISS grid
 with the reference's 5-cell halo (launcher.sh:24), y (B,20,90,144); bf16 storage, f32 accumulate,
 f32 master weights; B = 8 per GPU (launcher.sh:25), weak scaling across GPUs (--scaling strong: global batch 8).
 
-Kernel rooflines are priced INSIDE the step: after the timed region a few more steps run with the library's timing
+Kernel rooflines (--full) are priced INSIDE the step: after the timed region a few more steps run with the library's timing
 probes on (nint_seq.probe: one-thread stamp launches around every priced launch, calibrated by a back-to-back pair),
 so `roofline` / `roofline_kernels` carry the duration a launch has between its real neighbours (`ms_per_launch`);
 the old figure -- HIP events around a loop of back-to-back launches of the one kernel on warm slabs -- stays as
@@ -159,9 +165,11 @@ def parse_args(argv=None):
                     help="weak: --batch samples per GPU; strong: --batch samples in all, --batch / N per GPU (SURVEY 8d cfg 2)")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
     ap.add_argument("--workload", default="cfg1-20level", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-rooflines", action="store_true", help="skip the probe pass and the per-kernel loops")
-    ap.add_argument("--long-steps", type=int, default=200, help="steps of the extra long window (value_200steps); 0 = skip")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the long window, the all-reduce by itself, the kernel rooflines and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-kernel-rooflines", action="store_true", help="with --full: skip the probe pass and the per-kernel loops")
+    ap.add_argument("--long-steps", type=int, default=200, help="with --full: steps of the extra long window (value_200steps); 0 = skip")
     ap.add_argument("--fuse-bwd", type=lambda v: int(v, 0), default=0,
                     help="nint_seq.fuse_bwd (BPTT schedule; 0 = the library's per-layer choice, 0x40000000|masks = explicit, see nint.h)")
     ap.add_argument("--wide", type=int, default=0, help="nint_layer.wide of every layer: weight-gradient kernel family (0 = the library's choice, 1 = 4-wave 64-column kernel, 2 = 8-wave 128-column kernel where instantiated)")
@@ -179,6 +187,17 @@ def parse_args(argv=None):
     if args.steps < 1:
         ap.error("--steps must be at least 1")
     return args
+
+
+def extras(args, world):
+    """What a run measures beyond its headline figure; all of it needs --full.  long_steps: steps of the long window (0 =
+    none); allreduce: the gradient all-reduce timed by itself; rooflines: the probe pass and the per-kernel warm loops;
+    cpu_baseline: the CPU oracle's train steps (one rank only)."""
+    full = args.full
+    return {"long_steps": args.long_steps if full else 0,
+            "allreduce": full and (world > 1 or args.force_dist),
+            "rooflines": full and not args.no_kernel_rooflines,
+            "cpu_baseline": full and not args.no_cpu_baseline and world == 1}
 
 
 DUMP_LIMIT_BYTES = 64 << 20
@@ -300,6 +319,7 @@ def main():
     dev = torch.device("cuda", local_rank)
     import torch.distributed as dist
     use_dist = world > 1 or args.force_dist
+    ex = extras(args, world)
     json_fd = None
     if use_dist:
         # RCCL writes its version banner (five lines: "RCCL version : ...", "HIP version", ...) to STDOUT when the process group is
@@ -361,12 +381,12 @@ def main():
     final_loss = float(loss)
     if args.dump_outputs and rank == 0:
         write_outputs(args.dump_outputs, step_outputs(final_loss, model))
-    long_elapsed = timed(args.long_steps)[0] if args.long_steps > 0 else None
+    long_elapsed = timed(ex["long_steps"])[0] if ex["long_steps"] > 0 else None
 
-    # ---- the gradient all-reduce by itself (N > 1 or --force-dist): HIP events around dist.all_reduce on the step's
-    # stream, the flat bucket exactly as trainer.step() reduces it
+    # ---- the gradient all-reduce by itself (--full, N > 1 or --force-dist): HIP events around dist.all_reduce on the
+    # step's stream, the flat bucket exactly as trainer.step() reduces it
     ar_ms = bus_bw = None
-    if use_dist:
+    if ex["allreduce"]:
         st = torch.cuda.current_stream()
         buf = trainer.flat.grad
         for _ in range(3):
@@ -419,7 +439,7 @@ def main():
             wave_on = int(ws_.seq.wave)             # the launch schedule of the timed steps (nint_seq.wave: 0 / 1 / 2 / 4)
     PSTEPS, SLOTS = 5, 2048
     dur = step_ms = None
-    if not args.no_kernel_rooflines:
+    if ex["rooflines"]:
         # probe pass: PSTEPS more steps with stamps around the layer-0 gate / dgrad / pointwise launches, every layer's
         # weight-gradient block and the fold.  EVERY rank runs the steps (each ends in the all-reduce); rank 0 alone stamps.
         pbuf = torch.zeros(2 * SLOTS, dtype=torch.int64, device=dev) if rank == 0 else None
@@ -615,10 +635,7 @@ def main():
             "roofline_kernels": roof_all,
             "phases": phases,
         }
-        if not args.no_cpu_baseline and world == 1:
-            line["cpu_baseline"] = cpu_baseline(args.workload)
-        else:
-            line["cpu_baseline"] = None
+        line["cpu_baseline"] = cpu_baseline(args.workload) if ex["cpu_baseline"] else None
         if json_fd is not None:
             os.write(json_fd, (json.dumps(line) + "\n").encode())
         else:

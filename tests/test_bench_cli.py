@@ -130,6 +130,24 @@ def test_probe_pass_keeps_collectives_symmetric_across_ranks(tmp_path):
     assert r0["dur"] and not r1["dur"] and r0["probed"] == 1 and r1["probed"] == 0
 
 
+def test_extra_measurements_need_full():
+    """A plain run measures the headline alone; --full adds the long window, the all-reduce by itself (under a process group),
+    the kernel rooflines and the CPU baseline (one rank), each of which its own --no-* / --long-steps 0 still turns off."""
+    bench = _bench()
+    off = {"long_steps": 0, "allreduce": False, "rooflines": False, "cpu_baseline": False}
+    plain = ["--gpus", "1", "--steps", "20", "--warmup", "5"]
+    assert bench.parse_args(plain).full is False
+    assert bench.extras(bench.parse_args(plain), 1) == off
+    assert bench.extras(bench.parse_args(plain + ["--force-dist", "--phase-events", "3"]), 1) == off
+    assert bench.extras(bench.parse_args(["--gpus", "2"]), 2) == off
+    assert bench.extras(bench.parse_args(plain + ["--full"]), 1) == {"long_steps": 200, "allreduce": False, "rooflines": True,
+                                                                     "cpu_baseline": True}
+    assert bench.extras(bench.parse_args(plain + ["--full", "--force-dist"]), 1)["allreduce"] is True
+    assert bench.extras(bench.parse_args(["--gpus", "2", "--full"]), 2) == {"long_steps": 200, "allreduce": True, "rooflines": True,
+                                                                            "cpu_baseline": False}
+    assert bench.extras(bench.parse_args(plain + ["--full", "--no-cpu-baseline", "--no-kernel-rooflines", "--long-steps", "0"]), 1) == off
+
+
 def test_steps_must_be_positive():
     bench = _bench()
     assert bench.parse_args(["--steps", "7"]).steps == 7

@@ -291,7 +291,7 @@ def test_bench_under_torchrun_with_rccl_group(pkg):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", "29577", os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-           "--batch", "2", "--force-dist", "--no-cpu-baseline", "--long-steps", "4"]
+           "--batch", "2", "--force-dist", "--full", "--no-cpu-baseline", "--long-steps", "4"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
@@ -391,6 +391,23 @@ def test_bench_dump_outputs_is_the_last_timed_step_and_reproducible(pkg, tmp_pat
         assert np.array_equal(runs[0][k], runs[1][k]), k
 
 
+def test_plain_bench_run_measures_only_the_headline(pkg):
+    """`bench.py --gpus 1 --steps N --warmup W` without --full: the headline line, and none of the extra measurements."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "1"]
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1 and lines[0].startswith('{"metric"'), out.stdout[:1500]
+    d = json.loads(lines[0])
+    assert d["unit"] == "samples/s" and d["higher_is_better"] is True and d["dtype"] == "bf16" and d["steps"] == 2
+    assert d["value"] > 0 and abs(d["value"] - 1 / (d["ms_per_step"] * 1e-3)) <= 0.01 * d["value"]   # B = 1, one rank
+    assert d["value_200steps"] is None and d["long_window"] is None and d["allreduce_ms"] is None
+    assert d["roofline"] is None and d["roofline_kernels"] is None and d["phases"] is None and d["cpu_baseline"] is None
+
+
 def test_bench_starts_its_own_ranks(pkg):
     """`python bench.py --gpus 1 --force-dist` is what the driver runs for N = 1; for N > 1 the same form must start N
     ranks by itself.  On this one-GPU box: the parent decides from argv, the torchrun child runs the single rank."""
@@ -400,7 +417,7 @@ def test_bench_starts_its_own_ranks(pkg):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     sys.path.insert(0, root)
     import bench
-    argv = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "1", "--force-dist", "--no-cpu-baseline",
+    argv = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "1", "--force-dist", "--full", "--no-cpu-baseline",
             "--no-kernel-rooflines", "--long-steps", "0", "--master-port", "29579"]
     args = bench.parse_args(argv)
     code = ("import sys; sys.path.insert(0, %r); import bench; a = %r; "

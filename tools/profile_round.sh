@@ -1,6 +1,6 @@
 #!/bin/bash
 # One round's profile set on the GPU box (writes under gpurun_out/<tag>/; copy what is to be judged into profiles/):
-#   <tag>/bench_line.json            python bench.py --steps 20 --warmup 5 (un-profiled, with the CPU baseline)
+#   <tag>/bench_line.json            python bench.py --full --steps 20 --warmup 5 (un-profiled, with rooflines and the CPU baseline)
 #   <tag>/stats/...kernel_stats.csv  rocprofv3 --kernel-trace --stats of `python3 bench.py --steps 10 --warmup 3`
 #   <tag>/pmc_summary.txt            tools/pmc.sh passes over tools/kbench.py (SQ_*, FETCH_SIZE, WRITE_SIZE in separate passes)
 #   <tag>/sweep.jsonl                tools/sweep.sh
@@ -9,7 +9,7 @@ TAG=${1:-prof}
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG
 mkdir -p "$OUT"
 cd "$GRAFT_REPO_ROOT"
-python bench.py --steps 20 --warmup 5 2>/dev/null | tail -1 > "$OUT/bench_line.json"
+python bench.py --full --steps 20 --warmup 5 2>/dev/null | tail -1 > "$OUT/bench_line.json"
 ( cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -- python3 "$GRAFT_REPO_ROOT/bench.py" --steps 10 --warmup 3 --no-cpu-baseline --no-kernel-rooflines --long-steps 0 > "$OUT/stats.log" 2>&1 )
 find "$OUT/stats" -name "*kernel_stats.csv" -exec cp {} "$OUT/bench_steps10_kernel_stats.csv" \;
 TR=$(find "$OUT/stats" -name "*kernel_trace.csv" | head -1)

@@ -3,7 +3,7 @@
 # usage: tools/sweep.sh <out.jsonl>     (on the GPU box; ~2 minutes)
 OUT=${1:-gpurun_out/sweep.jsonl}
 : > "$OUT"
-run() { python bench.py --steps 20 --warmup 5 --no-cpu-baseline --long-steps 0 "$@" 2>/dev/null | tail -1 >> "$OUT"; }
+run() { python bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --long-steps 0 "$@" 2>/dev/null | tail -1 >> "$OUT"; }
 run --batch 1
 run --batch 2
 run --batch 4
