@@ -589,19 +589,24 @@ def bwd_chain(geo: Geo, Ws: Sequence[torch.Tensor], dG: Sequence[torch.Tensor], 
 # --------------------------------------------------------------------------- whole pass
 def read_workspace(eng, ws, dx: Optional[torch.Tensor] = None) -> Dict[str, object]:
     """Every slab of a workspace after forward + backward, decoded on the CPU (f32: exact for every stored value) (plus the raw bytes for check_padding).
-    dx: engine.backward's (B, T, C, H, W) f32 result (the unfolded input gradient)."""
+    dx: engine.backward's (B, T, C, H, W) f32 result (the unfolded input gradient).
+    An inference workspace (train=False) has no stash, dG, dh or dc: those entries are None and the audit checks h, c and the
+    padding only."""
     geo = geo_of(eng, ws)
     L = len(geo.layers)
+    train = bool(ws.train)
     st = {"geo": geo, "x": read_xs(geo, ws.xs),
           "h": [read_h(geo, l, ws.h[l]) for l in range(L)], "c": [read_c(geo, l, ws.c[l]) for l in range(L)],
-          "gates": [read_gates(geo, l, ws.gates[l]) for l in range(L)], "dG": [read_dG(geo, l, ws.dG[l]) for l in range(L)],
-          "dh_fin": [read_compact(geo, ws.dh[l], geo.B, geo.layers[l].Ch, geo.layers[l].Chp, geo.et) for l in range(L)],
-          "dc_fin": [read_compact(geo, ws.dc[l], geo.B, geo.layers[l].Ch, geo.layers[l].Chp, torch.float32) for l in range(L)],
+          "gates": [read_gates(geo, l, ws.gates[l]) for l in range(L)] if train else None,
+          "dG": [read_dG(geo, l, ws.dG[l]) for l in range(L)] if train else None,
+          "dh_fin": [read_compact(geo, ws.dh[l], geo.B, geo.layers[l].Ch, geo.layers[l].Chp, geo.et) for l in range(L)] if train else None,
+          "dc_fin": [read_compact(geo, ws.dc[l], geo.B, geo.layers[l].Ch, geo.layers[l].Chp, torch.float32) for l in range(L)] if train else None,
           "dx": None if dx is None else dx.detach().cpu().float().transpose(0, 1).reshape(geo.T * geo.B, *dx.shape[2:])}
     raw = {"xs": ws.xs.cpu()}
     for l in range(L):
-        raw.update({f"h{l}": ws.h[l].cpu(), f"dG{l}": ws.dG[l].cpu(), f"gates{l}": ws.gates[l].cpu(), f"c{l}": ws.c[l].cpu(),
-                    f"dh{l}": ws.dh[l].cpu(), f"dc{l}": ws.dc[l].cpu()})
+        raw.update({f"h{l}": ws.h[l].cpu(), f"c{l}": ws.c[l].cpu()})
+        if train:
+            raw.update({f"dG{l}": ws.dG[l].cpu(), f"gates{l}": ws.gates[l].cpu(), f"dh{l}": ws.dh[l].cpu(), f"dc{l}": ws.dc[l].cpu()})
     st["raw"] = raw
     return st
 
@@ -625,7 +630,8 @@ def audit(geo: Geo, Ws: Sequence[torch.Tensor], bs: Sequence[Optional[torch.Tens
     """max(|stored - ref| / bound) per tensor kind ('gates', 'c', 'h', 'dG', 'dx', 'dh_init', 'dc_init'; with f32 storage also
     'zacc', the gate pre-activation's accumulation measured through the stash: _z_from_stash) over the forward
     launches of the time steps fwd_ts (None: all) and the backward launches of t_min .. T-1.  dh_T / dc_T: the state
-    gradients stored before the backward (None: zero, as zero_state_grads)."""
+    gradients stored before the backward (None: zero, as zero_state_grads).  st from an inference workspace (st['gates'] and
+    st['dG'] None): the forward's c and h only."""
     B, T, L = geo.B, geo.T, len(geo.layers)
     sl = lambda t: slice(t * B, (t + 1) * B)
     worst: Dict[str, float] = {}
@@ -640,11 +646,14 @@ def audit(geo: Geo, Ws: Sequence[torch.Tensor], bs: Sequence[Optional[torch.Tens
             zero = t == 0 and not has_init
             res = fwd_launch(geo, l, x_in, None if zero else st["h"][l][sl(t)].double(), None if zero else st["c"][l][sl(t)].double(),
                              Ws[l], bs[l])
-            note("gates", st["gates"][l][sl(t)], *res["gates"])
+            if st["gates"] is not None:
+                note("gates", st["gates"][l][sl(t)], *res["gates"])
             note("c", st["c"][l][sl(t + 1)], *res["c"])
             note("h", st["h"][l][sl(t + 1)], *res["h"])
-            if geo.u_et == 0.0:
+            if geo.u_et == 0.0 and st["gates"] is not None:
                 note("zacc", *_z_from_stash(st["gates"][l][sl(t)].double(), *res["zg"]))
+    if st["dG"] is None:                     # an inference workspace: no stash, no BPTT
+        return worst
     for name, key, ref, bound in bwd_chain(geo, Ws, st["dG"], st["gates"], st["c"], dh_T, dc_T, t_min=t_min,
                                            has_init=has_init, need_dx=st.get("dx") is not None):
         if name == "dG":
