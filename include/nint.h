@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define NINT_VERSION 111
+#define NINT_VERSION 112
 
 enum { NINT_F32 = 0, NINT_BF16 = 1 };
 
@@ -259,6 +259,30 @@ int nint_conv_wgrad(const nint_layer* ly, const nint_geom* g, int dtype, int N,
 /* ---- whole-sequence drivers (model.py:253-274 and its BPTT), all launches from C++ ---------- */
 int nint_seq_fwd(const nint_seq* s /*host*/, void* stream);
 int nint_seq_bwd(const nint_seq* s /*host*/, void* stream);
+
+/* The launch plan of a pass, for tests and tools (host only: nothing is enqueued, no pointer is dereferenced).  Both drivers
+ * first PLAN a pass into an ordered list of launches and then enqueue that list; this entry runs the same argument checks and
+ * the same planner as nint_seq_fwd (bwd = 0) / nint_seq_bwd (bwd = 1: the BPTT chain, without the weight-gradient
+ * reductions behind it) and writes one record per conv / pointwise problem in enqueue order into out[0 .. cap).  Returns the
+ * number of problems of the pass (which may exceed cap) or a negative NINT_E_* code. */
+enum { NINT_K_CONV_IGEMM = 0, NINT_K_CONV_LSTM_MULTI = 1, NINT_K_CONV_LSTM_MULTI8 = 2, NINT_K_CONV_BWD_MULTI = 3,
+       NINT_K_CONV_BWD_MULTI8 = 4, NINT_K_CONV_DGRAD_MULTI8 = 5, NINT_K_STENCIL = 6, NINT_K_TINY = 7, NINT_K_POINTWISE = 8 };
+enum { NINT_OP_GATE = 0, NINT_OP_DGRAD = 1 /* conv backward-data, also with the layer below's pointwise backward on its x columns */,
+       NINT_OP_FUSED = 2 /* conv backward-data + the layer's own pointwise backward */, NINT_OP_POINTWISE = 3 };
+typedef struct nint_launch_rec {
+  int32_t index;            /* enqueue index: the problems of one merged grid share it */
+  int32_t bwd;              /* 0 = forward pass, 1 = BPTT */
+  int32_t op, layer, t;     /* NINT_OP_*; t = the time step of the launch's own data */
+  int32_t kernel;           /* NINT_K_*: the host kernel that carries the problem */
+  int32_t dtype;
+  /* the conv_igemm body (0 in all of them for the stencil, dense-K and pointwise kernels, which have none): */
+  int32_t epi, wn, wk, ntw, mt;   /* epilogue (0 gates, 1 backward-data, 2 backward-data + pointwise backward), waves along N / K,
+                                   * n-tiles per wave, tile rows */
+  int32_t strip;            /* 1: the leftover rows run as merged tiles of mt/2 rows x 32 pixels */
+  int32_t gx, gy;           /* the problem's own grid: pixel tiles x column groups */
+  int32_t nt_begin;         /* first n-tile it computes */
+} nint_launch_rec;
+int nint_debug_seq_plan(const nint_seq* s /*host*/, int bwd, nint_launch_rec* out /*host*/, int cap);
 
 /* ---- 1x1 head (model.py:251,274) ------------------------------------------------------------ */
 /* pred (N,O,H,W) f32 = w (O,Ch) . h + b  from halo-slab images [n0, n0+N) */

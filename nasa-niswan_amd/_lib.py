@@ -13,7 +13,7 @@ LIB_PATH = os.path.join(HERE, "libnint_hip.so")     # the one product library; n
 NINT_F32, NINT_BF16 = 0, 1
 NINT_OK, NINT_E_ARG, NINT_E_SHAPE, NINT_E_LDS, NINT_E_ALIGN = 0, -1, -2, -3, -4
 NINT_MAX_LAYERS = 8
-NINT_VERSION = 111     # include/nint.h NINT_VERSION: the library this binding was written against
+NINT_VERSION = 112     # include/nint.h NINT_VERSION: the library this binding was written against
 NINT_LOSS_SCRATCH_FLOATS = 8194
 NINT_LOSS_STATS = 8
 
@@ -40,6 +40,12 @@ class NintSeq(C.Structure):
                 ("wg_partial", vp), ("wg_partial_bytes", C.c_size_t), ("fuse_bwd", C.c_int32),
                 ("probe_mask", C.c_int32), ("probe", vp), ("probe_slots", C.c_int32),
                 ("wave", C.c_int32), ("bwd_parts", C.c_int32)]
+
+
+class NintLaunchRec(C.Structure):
+    """nint_launch_rec: one conv / pointwise problem of a planned pass (nint_debug_seq_plan)"""
+    _fields_ = [(n, C.c_int32) for n in ("index", "bwd", "op", "layer", "t", "kernel", "dtype", "epi", "wn", "wk", "ntw", "mt",
+                                         "strip", "gx", "gy", "nt_begin")]
 
 
 # every symbol include/nint.h declares: name -> (restype, argtypes)
@@ -71,6 +77,7 @@ SIGNATURES = {
     "nint_conv_wgrad": (_I, [_PL, _PG, _I, _I, vp, vp, vp, vp, vp, vp, _SZ, _I, vp]),
     "nint_seq_fwd": (_I, [_PS, vp]),
     "nint_seq_bwd": (_I, [_PS, vp]),
+    "nint_debug_seq_plan": (_I, [_PS, _I, C.POINTER(NintLaunchRec), _I]),
     "nint_head_fwd": (_I, [vp, _I, _I, _I, _I, _I, vp, vp, vp, _PG, _I, vp]),
     "nint_head_bwd": (_I, [vp, _I, _I, _I, _I, _I, vp, vp, vp, vp, vp, _PG, _I, vp, _SZ, vp]),
     "nint_loss_mse_l1_crop": (_I, [vp, vp, vp, vp, vp, _I, _I, _I, _I, _I, _I, _I, _I, vp]),

@@ -693,17 +693,7 @@ __global__ __launch_bounds__(256, MT >= 8 ? 2 : (xchg_rounds(EPI, WK, NTW, MT) =
 // problem's tile -> XCD mapping is the one of its own launch); every problem runs the body of the 4-row-tile shape its own
 // launch would have taken (ConvPlan::variant): same instructions on the same data, bit-identical results.  Registers / LDS
 // are those of the widest variant in the kernel.
-struct ConvMulti {
-  ConvArgs a[NINT_MULTI_MAX];
-  int n;
-  int begin[NINT_MULTI_MAX + 1];     // first workgroup of each problem (multiples of 8); begin[n] = grid size
-  int nbx[NINT_MULTI_MAX];           // pixel-tile workgroups of each problem (its launch's gridDim.x); column group = (b - begin) / nbx
-  int nwg[NINT_MULTI_MAX];           // nbx * column groups: workgroups past it are padding
-  int variant[NINT_MULTI_MAX];
-  PwArgs pw;                         // conv_bwd_multi_kernel only: workgroups [begin[n], begin[n] + pw_blocks) run a pointwise LSTM backward pass
-  int pw_blocks;
-};
-constexpr int conv_variant(int EPI, int WN, int WK, int NTW, int MT) { return EPI * 10000 + WN * 1000 + WK * 100 + NTW * 10 + MT / 4; }
+// (ConvMulti, the argument block, and conv_variant: nint_common.h)
 #define NINT_MULTI_PROLOGUE                                                                                     \
   extern __shared__ __attribute__((aligned(16))) char smem[];                                                   \
   int i = 0;                                                                                                    \
@@ -799,10 +789,10 @@ static bool multi_holds(int variant) {
 }
 
 // ------------------------------------------------------------------------------ host side
-// (ConvPlan, nint_common.h: a launch that is planned but not enqueued; the sequence drivers collect independent ones and
-// enqueue them as one grid)
+// Every conv launch is PLANNED (ConvPlan, nint_common.h: arguments, grid, LDS, kernel handle) and enqueued from its plan, by
+// itself (nint_internal_conv_enqueue) or with other independent ones as one grid (nint_internal_multi_plan / _enqueue).
 template <int DT, int EPI, int WN, int WK, int NTW, int MT>
-static int launch_cfg(ConvArgs& a, int N, int ngroups_y, hipStream_t st, ConvPlan* plan = nullptr) {
+static int launch_cfg(ConvArgs& a, int N, int ngroups_y, ConvPlan* plan) {
   const int NHP = (MT + 2 * a.p) * (16 + 2 * a.p);
   a.nhp_pad = nint_round_up(NHP, 16);
   a.magic_nhpp = (unsigned)(((1ull << 32) + a.nhp_pad - 1) / a.nhp_pad);
@@ -838,26 +828,35 @@ static int launch_cfg(ConvArgs& a, int N, int ngroups_y, hipStream_t st, ConvPla
   size_t lds = (size_t)a.a_bytes;
   if ((size_t)red_bytes > lds) lds = red_bytes;
   if (lds > 160 * 1024) return NINT_E_LDS;
-  if (plan) {
-    plan->a = a; plan->gx = a.n_full + N * a.tiles_x2; plan->gy = ngroups_y; plan->lds = lds;
-    plan->variant = conv_variant(EPI, WN, WK, NTW, MT);
-    return NINT_OK;
-  }
-  auto kern = conv_igemm_kernel<DT, EPI, WN, WK, NTW, MT>;
-  if (lds > 64 * 1024)
-    NINT_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  dim3 grid(a.n_full + N * a.tiles_x2, ngroups_y), block(256);
-  hipLaunchKernelGGL(kern, grid, block, lds, st, a);
+  plan->a = a; plan->gx = a.n_full + N * a.tiles_x2; plan->gy = ngroups_y; plan->lds = lds;
+  plan->variant = conv_variant(EPI, WN, WK, NTW, MT);
+  plan->kern = (const void*)conv_igemm_kernel<DT, EPI, WN, WK, NTW, MT>;
+  return NINT_OK;
+}
+
+int nint_internal_conv_enqueue(const ConvPlan* pl, void* stream) {
+  if (pl->gx <= 0) return NINT_OK;
+  if (pl->lds > 64 * 1024)
+    NINT_CHECK_HIP(hipFuncSetAttribute(pl->kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl->lds));
+  void* args[] = {(void*)&pl->a};
+  (void)hipLaunchKernel(pl->kern, dim3(pl->gx, pl->gy), dim3(256), args, pl->lds, (hipStream_t)stream);
   NINT_LAUNCH_CHECK();
   return NINT_OK;
+}
+
+int nint_internal_n_cu() {
+  int n_cu = 256, dev = 0;
+  if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev);
+  return n_cu;
 }
 
 #ifndef NINT_SPLIT_NUM
 #define NINT_SPLIT_NUM 3        // small batches: split the columns while workgroups < NINT_SPLIT_NUM / 2 per CU
 #endif
 template <int DT, int EPI>
-static int launch_conv(ConvArgs& a, int N, int ntiles, hipStream_t st, ConvPlan* plan = nullptr) {
-  if (ntiles <= 0) return NINT_OK;             // (a plan keeps gx == 0)
+static int launch_conv(ConvArgs& a, int N, int ntiles, int n_cu, ConvPlan* plan) {
+  plan->gx = 0; plan->carrier = NINT_K_CONV_IGEMM;
+  if (ntiles <= 0) return NINT_OK;             // (nothing to launch: gx == 0)
   // short-K launches (narrow layers) take 4-row tiles; nint_layer.tile_rows = 4 | 8 overrides (tests run both
   // heights on every shape)
   const int ksteps = a.nchunk0 * a.k * a.kx0 + a.nchunk1 * a.taps;
@@ -865,8 +864,7 @@ static int launch_conv(ConvArgs& a, int N, int ntiles, hipStream_t st, ConvPlan*
   // 8-row tiles against 104.0; dgrad layer 1 -- 36 steps -- 40.2 against 41.5; the 18-27-step launches prefer 4 rows)
   bool mt4 = a.tile_rows ? a.tile_rows == 4
                          : (EPI != EPI_LSTM ? ksteps <= 32 : (ksteps <= 48 || ntiles <= 4));
-  int n_cu = 256;
-  { int dev = 0; if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev); }
+  if (n_cu <= 0) n_cu = nint_internal_n_cu();   // (the single-launch entry points; the sequence drivers look it up once per pass)
   // few images (B = 1 or 2 per GPU): 8-row tiles would leave CUs without a workgroup; 4-row tiles double the count
   if (!a.tile_rows && 2 * N * nint_cdiv(a.W, 16) * nint_cdiv(a.H, 8) < 3 * n_cu) mt4 = true;
   if constexpr (EPI == EPI_LSTM) {
@@ -879,23 +877,23 @@ static int launch_conv(ConvArgs& a, int N, int ntiles, hipStream_t st, ConvPlan*
     // (an explicit nint_layer.tile_rows pins the launch shape: no split)
     const bool few4 = !a.tile_rows && 2 * ptiles * (cbs / 4 > 0 ? cbs / 4 : 1) < NINT_SPLIT_NUM * n_cu;       // with 4 column blocks per workgroup
     const bool few2 = !a.tile_rows && 2 * ptiles * (cbs / 2 > 0 ? cbs / 2 : 1) < NINT_SPLIT_NUM * n_cu;       // with 2
-    if (cbs % 4 == 0 && !few4) return mt4 ? launch_cfg<DT, EPI, 4, 1, 4, 4>(a, N, cbs / 4, st, plan) : launch_cfg<DT, EPI, 4, 1, 4, 8>(a, N, cbs / 4, st, plan);
-    if (cbs % 2 == 0 && !few2) return mt4 ? launch_cfg<DT, EPI, 2, 2, 4, 4>(a, N, cbs / 2, st, plan) : launch_cfg<DT, EPI, 2, 2, 4, 8>(a, N, cbs / 2, st, plan);
-    return mt4 ? launch_cfg<DT, EPI, 1, 4, 4, 4>(a, N, cbs, st, plan) : launch_cfg<DT, EPI, 1, 4, 4, 8>(a, N, cbs, st, plan);
+    if (cbs % 4 == 0 && !few4) return mt4 ? launch_cfg<DT, EPI, 4, 1, 4, 4>(a, N, cbs / 4, plan) : launch_cfg<DT, EPI, 4, 1, 4, 8>(a, N, cbs / 4, plan);
+    if (cbs % 2 == 0 && !few2) return mt4 ? launch_cfg<DT, EPI, 2, 2, 4, 4>(a, N, cbs / 2, plan) : launch_cfg<DT, EPI, 2, 2, 4, 8>(a, N, cbs / 2, plan);
+    return mt4 ? launch_cfg<DT, EPI, 1, 4, 4, 4>(a, N, cbs, plan) : launch_cfg<DT, EPI, 1, 4, 4, 8>(a, N, cbs, plan);
   } else {
     // (WN, NTW) with WN*NTW dividing the tile count, widest first; leftover waves split K.  Small batches: a shape whose
     // launch would leave CUs without a workgroup is passed over for the next narrower one (more column groups on
     // blockIdx.y; the same rule as the gate launches above)
     const int ptiles = N * nint_cdiv(a.W, 16) * nint_cdiv(a.H, mt4 ? 4 : 8);
     auto few = [&](int cols) { return !a.tile_rows && EPI == EPI_DGRAD && 2 * ptiles * (ntiles / cols) < NINT_SPLIT_NUM * n_cu; };
-    if (ntiles % 16 == 0 && !few(16)) return mt4 ? launch_cfg<DT, EPI, 4, 1, 4, 4>(a, N, ntiles / 16, st, plan) : launch_cfg<DT, EPI, 4, 1, 4, 8>(a, N, ntiles / 16, st, plan);
-    if (ntiles % 12 == 0 && !few(12)) return mt4 ? launch_cfg<DT, EPI, 4, 1, 3, 4>(a, N, ntiles / 12, st, plan) : launch_cfg<DT, EPI, 4, 1, 3, 8>(a, N, ntiles / 12, st, plan);
-    if (ntiles % 8 == 0 && !few(8)) return mt4 ? launch_cfg<DT, EPI, 2, 2, 4, 4>(a, N, ntiles / 8, st, plan) : launch_cfg<DT, EPI, 2, 2, 4, 8>(a, N, ntiles / 8, st, plan);
-    if (ntiles % 6 == 0 && !few(6)) return mt4 ? launch_cfg<DT, EPI, 2, 2, 3, 4>(a, N, ntiles / 6, st, plan) : launch_cfg<DT, EPI, 2, 2, 3, 8>(a, N, ntiles / 6, st, plan);
-    if (ntiles % 4 == 0 && !few(4)) return mt4 ? launch_cfg<DT, EPI, 1, 4, 4, 4>(a, N, ntiles / 4, st, plan) : launch_cfg<DT, EPI, 1, 4, 4, 8>(a, N, ntiles / 4, st, plan);
-    if (ntiles % 3 == 0 && !few(3)) return mt4 ? launch_cfg<DT, EPI, 1, 4, 3, 4>(a, N, ntiles / 3, st, plan) : launch_cfg<DT, EPI, 1, 4, 3, 8>(a, N, ntiles / 3, st, plan);
-    if (ntiles % 2 == 0 && !few(2)) return mt4 ? launch_cfg<DT, EPI, 1, 4, 2, 4>(a, N, ntiles / 2, st, plan) : launch_cfg<DT, EPI, 1, 4, 2, 8>(a, N, ntiles / 2, st, plan);
-    return mt4 ? launch_cfg<DT, EPI, 1, 4, 1, 4>(a, N, ntiles, st, plan) : launch_cfg<DT, EPI, 1, 4, 1, 8>(a, N, ntiles, st, plan);
+    if (ntiles % 16 == 0 && !few(16)) return mt4 ? launch_cfg<DT, EPI, 4, 1, 4, 4>(a, N, ntiles / 16, plan) : launch_cfg<DT, EPI, 4, 1, 4, 8>(a, N, ntiles / 16, plan);
+    if (ntiles % 12 == 0 && !few(12)) return mt4 ? launch_cfg<DT, EPI, 4, 1, 3, 4>(a, N, ntiles / 12, plan) : launch_cfg<DT, EPI, 4, 1, 3, 8>(a, N, ntiles / 12, plan);
+    if (ntiles % 8 == 0 && !few(8)) return mt4 ? launch_cfg<DT, EPI, 2, 2, 4, 4>(a, N, ntiles / 8, plan) : launch_cfg<DT, EPI, 2, 2, 4, 8>(a, N, ntiles / 8, plan);
+    if (ntiles % 6 == 0 && !few(6)) return mt4 ? launch_cfg<DT, EPI, 2, 2, 3, 4>(a, N, ntiles / 6, plan) : launch_cfg<DT, EPI, 2, 2, 3, 8>(a, N, ntiles / 6, plan);
+    if (ntiles % 4 == 0 && !few(4)) return mt4 ? launch_cfg<DT, EPI, 1, 4, 4, 4>(a, N, ntiles / 4, plan) : launch_cfg<DT, EPI, 1, 4, 4, 8>(a, N, ntiles / 4, plan);
+    if (ntiles % 3 == 0 && !few(3)) return mt4 ? launch_cfg<DT, EPI, 1, 4, 3, 4>(a, N, ntiles / 3, plan) : launch_cfg<DT, EPI, 1, 4, 3, 8>(a, N, ntiles / 3, plan);
+    if (ntiles % 2 == 0 && !few(2)) return mt4 ? launch_cfg<DT, EPI, 1, 4, 2, 4>(a, N, ntiles / 2, plan) : launch_cfg<DT, EPI, 1, 4, 2, 8>(a, N, ntiles / 2, plan);
+    return mt4 ? launch_cfg<DT, EPI, 1, 4, 1, 4>(a, N, ntiles, plan) : launch_cfg<DT, EPI, 1, 4, 1, 8>(a, N, ntiles, plan);
   }
 }
 
@@ -903,7 +901,8 @@ static inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0;
 
 static int cell_fwd(const nint_layer* ly, const nint_geom* g, int dtype, int N,
                     const void* x_slab, const void* h_prev, const float* c_prev,
-                    void* h_out, float* c_out, void* gates_out, void* stream, ConvPlan* plan) {
+                    void* h_out, float* c_out, void* gates_out, void* stream, int n_cu, ConvPlan* plan) {
+  // plan != nullptr: nothing is enqueued, *plan describes the launch
   if (!ly || !g || !x_slab || !h_out || !c_out || N <= 0) return NINT_E_ARG;
   if (dtype != NINT_F32 && dtype != NINT_BF16) return NINT_E_ARG;
   if (!(ly->k & 1) || ly->k / 2 > g->P) return NINT_E_ARG;
@@ -931,44 +930,46 @@ static int cell_fwd(const nint_layer* ly, const nint_geom* g, int dtype, int N,
   a.c_prev = c_prev; a.c_out = c_out; a.h_out = (char*)h_out; a.gates_out = (char*)gates_out;
   a.Chp = ly->Chp; a.Ch16 = ly->Ch16;
   a.tile_rows = ly->tile_rows <= 2 ? 0 : ly->tile_rows;
-  hipStream_t st = (hipStream_t)stream;
   if (ly->wide < 0 || ly->wide > 2) return NINT_E_ARG;   // (the weight-gradient family switch: nothing to do with this launch)
   // tiny hidden widths (4*Ch <= 32 gate columns: no dense contraction): the VALU stencil kernel (csrc/stencil.hip) -- on request
   // (nint_layer.tile_rows == 1: "one pixel per lane"), or where it measured faster than the padded MFMA tiles (NINT_STENCIL_AUTO).
-  // A planned launch (merged grids) has no stencil form: the caller then enqueues it by itself.
+  // These two have no planned form: NINT_E_SHAPE, and the caller runs the step through nint_cell_fwd.
   if (nint_internal_stencil_holds(ly) && (ly->tile_rows == 1 || (ly->tile_rows == 0 && NINT_STENCIL_AUTO(dtype)))) {
-    if (plan) return NINT_E_SHAPE;
+    if (plan) { plan->gx = 0; plan->carrier = NINT_K_STENCIL; return NINT_E_SHAPE; }
     return nint_internal_stencil_lstm(ly, g, dtype, N, x_slab, h_prev, c_prev, h_out, c_out, gates_out, stream);
   }
   // ... and the library's own choice for such layers: the matrix pipe with a DENSE K (csrc/tiny_gemm.hip)
   if ((ly->tile_rows == 2 || (ly->tile_rows == 0 && NINT_TINY_AUTO(dtype))) && nint_tiny_shape(ly->Cx, ly->Ch, ly->k, ly->xfold, dtype)) {
-    if (plan) return NINT_E_SHAPE;
+    if (plan) { plan->gx = 0; plan->carrier = NINT_K_TINY; return NINT_E_SHAPE; }
     return nint_internal_tiny_lstm(ly, g, dtype, N, x_slab, h_prev, c_prev, h_out, c_out, gates_out, stream);
   }
-  return dtype == NINT_BF16 ? launch_conv<NINT_BF16, EPI_LSTM>(a, N, a.NTt, st, plan)
-                            : launch_conv<NINT_F32, EPI_LSTM>(a, N, a.NTt, st, plan);
+  ConvPlan own;
+  ConvPlan* pl = plan ? plan : &own;
+  const int rc = dtype == NINT_BF16 ? launch_conv<NINT_BF16, EPI_LSTM>(a, N, a.NTt, n_cu, pl)
+                                    : launch_conv<NINT_F32, EPI_LSTM>(a, N, a.NTt, n_cu, pl);
+  return rc != NINT_OK || plan ? rc : nint_internal_conv_enqueue(pl, stream);
 }
 
 extern "C" int nint_cell_fwd(const nint_layer* ly, const nint_geom* g, int dtype, int N,
                              const void* x_slab, const void* h_prev, const float* c_prev,
                              void* h_out, float* c_out, void* gates_out, void* stream) {
-  return cell_fwd(ly, g, dtype, N, x_slab, h_prev, c_prev, h_out, c_out, gates_out, stream, nullptr);
+  return cell_fwd(ly, g, dtype, N, x_slab, h_prev, c_prev, h_out, c_out, gates_out, stream, 0, nullptr);
 }
 
-int nint_internal_cell_fwd_plan(const CellFwdJob* j, const nint_geom* g, int dtype, int N, ConvPlan* plan) {
-  return cell_fwd(j->ly, g, dtype, N, j->x_slab, j->h_prev, j->c_prev, j->h_out, j->c_out, j->gates_out, nullptr, plan);
+int nint_internal_cell_fwd_plan(const CellFwdJob* j, const nint_geom* g, int dtype, int N, int n_cu, ConvPlan* plan) {
+  return cell_fwd(j->ly, g, dtype, N, j->x_slab, j->h_prev, j->c_prev, j->h_out, j->c_out, j->gates_out, nullptr, n_cu, plan);
 }
 
-// Up to NINT_MULTI_MAX planned launches that do not depend on each other, as ONE grid.  NINT_E_SHAPE (nothing enqueued): one
-// of them has a shape the merged kernels do not hold, or they are of both kinds -- the caller then enqueues them one by one.
-int nint_internal_conv_multi(const ConvPlan* plans, int n, int dtype, void* stream, const PwArgs* pw, bool dry_run) {
+// Up to NINT_MULTI_MAX planned launches that do not depend on each other, as ONE grid: which kernel, with what arguments (pure).
+int nint_internal_multi_plan(const ConvPlan* plans, int n, const PwArgs* pw, MultiPlan* out) {
   if (!plans || n < 1 || n > NINT_MULTI_MAX) return NINT_E_SHAPE;
-  ConvMulti m = {};
+  ConvMulti& m = out->m;
+  m = ConvMulti{};
   size_t lds = 0;
   int b = 0, nfwd = 0;
   for (int i = 0; i < n; ++i) {
     const ConvPlan& pl = plans[i];
-    if (!multi_holds(pl.variant)) return NINT_E_SHAPE;
+    if (pl.gx <= 0 || !multi_holds(pl.variant)) return NINT_E_SHAPE;
     nfwd += pl.variant / 10000 == EPI_LSTM ? 1 : 0;
     m.a[i] = pl.a; m.variant[i] = pl.variant; m.nbx[i] = pl.gx; m.nwg[i] = pl.gx * pl.gy;
     m.begin[i] = b;
@@ -979,11 +980,6 @@ int nint_internal_conv_multi(const ConvPlan* plans, int n, int dtype, void* stre
   if (pw && nfwd) return NINT_E_SHAPE;
   m.n = n;
   for (int i = n; i <= NINT_MULTI_MAX; ++i) m.begin[i] = b;
-  hipStream_t st = (hipStream_t)stream;
-#define NINT_MULTI_LAUNCH(KERN_)                                                                                                      \
-  { auto kern = KERN_;                                                                                                                \
-    if (lds > 64 * 1024) NINT_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-    hipLaunchKernelGGL(kern, dim3(b), dim3(256), lds, st, m); }
   bool rows8 = false, dpair = false;
   for (int i = 0; i < n; ++i) rows8 = rows8 || plans[i].variant % 10 == 2;
   for (int i = 0; i < n; ++i) dpair = dpair || plans[i].variant == conv_variant(EPI_DGRAD, 2, 2, 3, 8);
@@ -1002,26 +998,48 @@ int nint_internal_conv_multi(const ConvPlan* plans, int n, int dtype, void* stre
     m.pw = *pw; m.pw_blocks = (int)pb;
     b += (int)pb;
   }
-  if (dry_run) return NINT_OK;     // (the caller only asked whether these launches go into one grid)
-  if (dpair) { if (dtype == NINT_BF16) NINT_MULTI_LAUNCH(conv_dgrad_multi8_kernel<NINT_BF16>) else NINT_MULTI_LAUNCH(conv_dgrad_multi8_kernel<NINT_F32>) }
-  else if (nfwd && rows8) { if (dtype == NINT_BF16) NINT_MULTI_LAUNCH(conv_lstm_multi8_kernel<NINT_BF16>) else NINT_MULTI_LAUNCH(conv_lstm_multi8_kernel<NINT_F32>) }
-  else if (nfwd) { if (dtype == NINT_BF16) NINT_MULTI_LAUNCH(conv_lstm_multi_kernel<NINT_BF16>) else NINT_MULTI_LAUNCH(conv_lstm_multi_kernel<NINT_F32>) }
-  else if (rows8) { if (dtype == NINT_BF16) NINT_MULTI_LAUNCH(conv_bwd_multi8_kernel<NINT_BF16>) else NINT_MULTI_LAUNCH(conv_bwd_multi8_kernel<NINT_F32>) }
-  else { if (dtype == NINT_BF16) NINT_MULTI_LAUNCH(conv_bwd_multi_kernel<NINT_BF16>) else NINT_MULTI_LAUNCH(conv_bwd_multi_kernel<NINT_F32>) }
-#undef NINT_MULTI_LAUNCH
+  out->grid = b; out->lds = lds;
+  out->carrier = dpair ? NINT_K_CONV_DGRAD_MULTI8
+                       : nfwd ? (rows8 ? NINT_K_CONV_LSTM_MULTI8 : NINT_K_CONV_LSTM_MULTI) : (rows8 ? NINT_K_CONV_BWD_MULTI8 : NINT_K_CONV_BWD_MULTI);
+  return NINT_OK;
+}
+
+template <int DT>
+static const void* multi_kernel(int carrier) {
+  switch (carrier) {
+    case NINT_K_CONV_DGRAD_MULTI8: return (const void*)conv_dgrad_multi8_kernel<DT>;
+    case NINT_K_CONV_LSTM_MULTI8: return (const void*)conv_lstm_multi8_kernel<DT>;
+    case NINT_K_CONV_LSTM_MULTI: return (const void*)conv_lstm_multi_kernel<DT>;
+    case NINT_K_CONV_BWD_MULTI8: return (const void*)conv_bwd_multi8_kernel<DT>;
+    default: return (const void*)conv_bwd_multi_kernel<DT>;
+  }
+}
+int nint_internal_multi_enqueue(const MultiPlan* mp, int dtype, void* stream) {
+  const void* kern = dtype == NINT_BF16 ? multi_kernel<NINT_BF16>(mp->carrier) : multi_kernel<NINT_F32>(mp->carrier);
+  if (mp->lds > 64 * 1024) NINT_CHECK_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mp->lds));
+  void* args[] = {(void*)&mp->m};
+  (void)hipLaunchKernel(kern, dim3(mp->grid), dim3(256), args, mp->lds, (hipStream_t)stream);
   NINT_LAUNCH_CHECK();
   return NINT_OK;
 }
 
-extern "C" int nint_conv_dgrad(const nint_layer* ly, const nint_geom* g, int dtype, int N,
-                               const void* dG, void* dx_accum, void* dh_prev, void* stream) {
-  return nint_internal_conv_dgrad(ly, g, dtype, N, dG, dx_accum, dh_prev, false, nullptr, stream);
+// the single-launch entry points: planned with a CU lookup of their own, enqueued at once
+static int dgrad_now(const nint_layer* ly, const nint_geom* g, int dtype, int N, const void* dG, void* dx_accum, void* dh_prev,
+                     bool overwrite_dx, const DgradPw* pw, void* stream) {
+  ConvPlan pl;
+  const int rc = nint_internal_conv_dgrad(ly, g, dtype, N, dG, dx_accum, dh_prev, overwrite_dx, pw, 0, &pl);
+  return rc != NINT_OK ? rc : nint_internal_conv_enqueue(&pl, stream);
 }
 
-// plan != nullptr: nothing is enqueued, *plan describes the launch (plan->gx == 0: there is nothing to launch)
+extern "C" int nint_conv_dgrad(const nint_layer* ly, const nint_geom* g, int dtype, int N,
+                               const void* dG, void* dx_accum, void* dh_prev, void* stream) {
+  return dgrad_now(ly, g, dtype, N, dG, dx_accum, dh_prev, false, nullptr, stream);
+}
+
+// *plan describes the launch (plan->gx == 0: there is nothing to launch); nothing is enqueued
 int nint_internal_conv_dgrad(const nint_layer* ly, const nint_geom* g, int dtype, int N, const void* dG, void* dx_accum,
-                             void* dh_prev, bool overwrite_dx, const DgradPw* pw, void* stream, ConvPlan* plan) {
-  if (plan) plan->gx = 0;
+                             void* dh_prev, bool overwrite_dx, const DgradPw* pw, int n_cu, ConvPlan* plan) {
+  plan->gx = 0; plan->carrier = NINT_K_CONV_IGEMM;
   if (!ly || !g || !dG || N <= 0) return NINT_E_ARG;
   if (dtype != NINT_F32 && dtype != NINT_BF16) return NINT_E_ARG;
   // fused forms: pw->gates set = this layer's pointwise backward on the h columns (dh_prev is then not stored);
@@ -1054,7 +1072,6 @@ int nint_internal_conv_dgrad(const nint_layer* ly, const nint_geom* g, int dtype
   const int nt_x = ly->Cxp / 16, nt_h = (pw && pw->gates) ? ly->Ch16 / 16 : ly->Chp / 16;
   a.nt_begin = dx_accum ? 0 : nt_x;
   const int ntiles = (dx_accum ? nt_x : 0) + ((dh_prev || (pw && pw->gates)) ? nt_h : 0);
-  hipStream_t st = (hipStream_t)stream;
   if (pw) {
     a.pw_gates = (const char*)pw->gates; a.pw_c_prev = pw->c_prev; a.pw_c_new = pw->c_new; a.pw_dc = pw->dc;
     a.pw_old = (const char*)pw->old; a.pw_dG = (char*)pw->dG_out;
@@ -1064,11 +1081,11 @@ int nint_internal_conv_dgrad(const nint_layer* ly, const nint_geom* g, int dtype
       a.lo_dG = (char*)pw->lo_dG_out; a.lo_Ch16 = pw->lo_Ch16; a.lo_dc_zero = pw->lo_dc_zero ? 1 : 0;
     }
     if (pw->tile_rows) a.tile_rows = pw->tile_rows;
-    return dtype == NINT_BF16 ? launch_conv<NINT_BF16, EPI_DGRAD_PW>(a, N, ntiles, st, plan)
-                              : launch_conv<NINT_F32, EPI_DGRAD_PW>(a, N, ntiles, st, plan);
+    return dtype == NINT_BF16 ? launch_conv<NINT_BF16, EPI_DGRAD_PW>(a, N, ntiles, n_cu, plan)
+                              : launch_conv<NINT_F32, EPI_DGRAD_PW>(a, N, ntiles, n_cu, plan);
   }
-  return dtype == NINT_BF16 ? launch_conv<NINT_BF16, EPI_DGRAD>(a, N, ntiles, st, plan)
-                            : launch_conv<NINT_F32, EPI_DGRAD>(a, N, ntiles, st, plan);
+  return dtype == NINT_BF16 ? launch_conv<NINT_BF16, EPI_DGRAD>(a, N, ntiles, n_cu, plan)
+                            : launch_conv<NINT_F32, EPI_DGRAD>(a, N, ntiles, n_cu, plan);
 }
 
 extern "C" int nint_cell_bwd_fused(const nint_layer* ly, const nint_geom* g, int dtype, int N, const void* dG_next, void* dx,
@@ -1076,5 +1093,5 @@ extern "C" int nint_cell_bwd_fused(const nint_layer* ly, const nint_geom* g, int
                                    float* dc, void* dG, void* stream) {
   DgradPw pw = {};
   pw.gates = gates; pw.c_prev = c_prev; pw.c_new = c_new; pw.dc = dc; pw.old = dh_above; pw.dG_out = dG;
-  return nint_internal_conv_dgrad(ly, g, dtype, N, dG_next, dx, nullptr, true, &pw, stream);
+  return dgrad_now(ly, g, dtype, N, dG_next, dx, nullptr, true, &pw, stream);
 }

@@ -234,10 +234,11 @@ struct Probe {
 };
 
 // internal entry points shared between translation units (not part of the C ABI)
-int nint_internal_cell_bwd_pointwise(const nint_layer* ly, const nint_geom* g, int dtype, int N, const void* gates,
-                                     const float* c_prev, const float* c_new, const void* dh, float* dc, void* dG,
-                                     bool dc_zero, void* stream, const void* dh2 = nullptr,    // dh2: a second piece of d/dh, added
-                                     PwArgs* plan = nullptr);                                  // plan: nothing enqueued, *plan describes the launch
+// (planned, then enqueued: the first checks the arguments and fills *plan, the second launches lstm_bwd_pointwise_kernel)
+int nint_internal_pointwise_plan(const nint_layer* ly, const nint_geom* g, int dtype, int N, const void* gates,
+                                 const float* c_prev, const float* c_new, const void* dh, float* dc, void* dG,
+                                 bool dc_zero, const void* dh2, PwArgs* plan);                 // dh2: a second piece of d/dh, added (or nullptr)
+int nint_internal_pointwise_enqueue(const PwArgs* plan, int dtype, void* stream);
 struct WgJob {           // one layer's weight / bias gradient
   const nint_layer* ly; int N;
   const void* dG; const void* x_slab; const void* h_slab;
@@ -285,19 +286,41 @@ int nint_internal_stencil_lstm(const nint_layer* ly, const nint_geom* g, int dty
 struct CellFwdJob {      // one gate launch (nint_cell_fwd's arguments)
   const nint_layer* ly; const void* x_slab; const void* h_prev; const float* c_prev; void* h_out; float* c_out; void* gates_out;
 };
-// A conv_igemm launch that is planned but not enqueued: the sequence drivers collect independent ones and enqueue them as ONE
-// grid (nint_internal_conv_multi; NINT_E_SHAPE = not possible for these shapes, nothing enqueued).
+// A conv_igemm launch, planned: every conv launch is planned first (cell_fwd / nint_internal_conv_dgrad) and enqueued from its
+// plan (nint_internal_conv_enqueue), by itself or with other independent ones as ONE grid (nint_internal_multi_*).
 struct ConvPlan {
-  ConvArgs a; int gx, gy; size_t lds; int variant;   // grid, dynamic LDS, kernel shape (EPI, WN, WK, NTW, MT)
+  ConvArgs a; int gx, gy; size_t lds; int variant;   // grid (gx == 0: nothing to launch), dynamic LDS, kernel shape (conv_variant)
+  const void* kern;                                  // host handle of the conv_igemm_kernel<...> instantiation
+  int carrier;                                       // NINT_K_CONV_IGEMM; NINT_K_STENCIL / NINT_K_TINY with NINT_E_SHAPE: no planned form
 };
-int nint_internal_cell_fwd_plan(const CellFwdJob* j, const nint_geom* g, int dtype, int N, ConvPlan* plan);
-int nint_internal_conv_multi(const ConvPlan* plans, int n, int dtype, void* stream, const PwArgs* pw = nullptr,    // pw: one more problem, a pointwise backward pass
-                             bool dry_run = false);                                                          // dry_run: NINT_OK / NINT_E_SHAPE, nothing enqueued
+constexpr int conv_variant(int EPI, int WN, int WK, int NTW, int MT) { return EPI * 10000 + WN * 1000 + WK * 100 + NTW * 10 + MT / 4; }
+int nint_internal_n_cu();                            // CUs of the current device; 256 where the lookup fails
+// n_cu: the CU count the launch-shape rules use (<= 0: looked up here)
+int nint_internal_cell_fwd_plan(const CellFwdJob* j, const nint_geom* g, int dtype, int N, int n_cu, ConvPlan* plan);
+int nint_internal_conv_enqueue(const ConvPlan* plan, void* stream);
+// Independent planned launches in ONE grid: the argument block of conv_lstm_multi[8]_kernel / conv_bwd_multi[8]_kernel /
+// conv_dgrad_multi8_kernel (csrc/conv_igemm.hip).
+struct ConvMulti {
+  ConvArgs a[NINT_MULTI_MAX];
+  int n;
+  int begin[NINT_MULTI_MAX + 1];     // first workgroup of each problem (multiples of 8); begin[n] = grid size
+  int nbx[NINT_MULTI_MAX];           // pixel-tile workgroups of each problem (its launch's gridDim.x); column group = (b - begin) / nbx
+  int nwg[NINT_MULTI_MAX];           // nbx * column groups: workgroups past it are padding
+  int variant[NINT_MULTI_MAX];
+  PwArgs pw;                         // conv_bwd_multi_kernel only: workgroups [begin[n], begin[n] + pw_blocks) run a pointwise LSTM backward pass
+  int pw_blocks;
+};
+struct MultiPlan { ConvMulti m; int carrier, grid; size_t lds; };     // carrier: NINT_K_CONV_LSTM_MULTI ... NINT_K_CONV_DGRAD_MULTI8
+// pure: the merged kernel that holds plans[0..n) (pw: plus one pointwise backward pass), its argument block, grid and LDS -- or
+// NINT_E_SHAPE: one of them has a shape the merged kernels do not hold, or they are of both kinds (the caller enqueues them one by one)
+int nint_internal_multi_plan(const ConvPlan* plans, int n, const PwArgs* pw, MultiPlan* out);
+int nint_internal_multi_enqueue(const MultiPlan* mp, int dtype, void* stream);
 struct DgradPw {         // fused pointwise backward of the previous time step (EPI_DGRAD_PW)
   const void* gates; const float* c_prev; const float* c_new; float* dc; const void* old; void* dG_out;
   // optional: the layer below's pointwise backward of THIS time step, run on the x columns (the layer's dh buffer is only read)
   const void* lo_gates; const float* lo_c_prev; const float* lo_c_new; float* lo_dc; void* lo_dG_out; int lo_Ch16; bool lo_dc_zero;
   int tile_rows;          // 0 = the layer's choice, 4 / 8 = this launch's tile height
 };
+// *plan describes the launch (plan->gx == 0: there is nothing to launch); nothing is enqueued
 int nint_internal_conv_dgrad(const nint_layer* ly, const nint_geom* g, int dtype, int N, const void* dG, void* dx_accum,
-                             void* dh_prev, bool overwrite_dx, const DgradPw* pw, void* stream, ConvPlan* plan = nullptr);
+                             void* dh_prev, bool overwrite_dx, const DgradPw* pw, int n_cu, ConvPlan* plan);

@@ -559,18 +559,21 @@ __global__ __launch_bounds__(256) void lstm_bwd_pointwise_kernel(PwArgs a) {
   lstm_bwd_pointwise_body<DT>(a, blockIdx.x, gridDim.x);       // (nint_common.h: the body is also a problem of conv_bwd_multi_kernel)
 }
 
-int nint_internal_cell_bwd_pointwise(const nint_layer* ly, const nint_geom* g, int dtype, int N, const void* gates,
-                                     const float* c_prev, const float* c_new, const void* dh, float* dc, void* dG,
-                                     bool dc_zero, void* stream, const void* dh2, PwArgs* plan) {
+int nint_internal_pointwise_plan(const nint_layer* ly, const nint_geom* g, int dtype, int N, const void* gates,
+                                 const float* c_prev, const float* c_new, const void* dh, float* dc, void* dG,
+                                 bool dc_zero, const void* dh2, PwArgs* plan) {
   if (!ly || !g || !gates || !c_new || !dh || !dc || !dG || N <= 0) return NINT_E_ARG;
   if (dtype != NINT_F32 && dtype != NINT_BF16) return NINT_E_ARG;
-  const PwArgs a = {gates, c_prev, c_new, dh, dh2, dc, dG, N, g->H, g->W, g->P, g->Hh, g->Wh, ly->Ch16, ly->Chp, dc_zero ? 1 : 0};
-  if (plan) { *plan = a; return NINT_OK; }
-  const size_t total = (size_t)N * g->H * g->W * (ly->Ch16 / 4);
+  *plan = PwArgs{gates, c_prev, c_new, dh, dh2, dc, dG, N, g->H, g->W, g->P, g->Hh, g->Wh, ly->Ch16, ly->Chp, dc_zero ? 1 : 0};
+  return NINT_OK;
+}
+
+int nint_internal_pointwise_enqueue(const PwArgs* a, int dtype, void* stream) {
+  const size_t total = (size_t)a->N * a->H * a->W * (a->Ch16 / 4);
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid = grid1d(total);
-  if (dtype == NINT_BF16) hipLaunchKernelGGL((lstm_bwd_pointwise_kernel<NINT_BF16>), grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL((lstm_bwd_pointwise_kernel<NINT_F32>), grid, dim3(256), 0, st, a);
+  if (dtype == NINT_BF16) hipLaunchKernelGGL((lstm_bwd_pointwise_kernel<NINT_BF16>), grid, dim3(256), 0, st, *a);
+  else hipLaunchKernelGGL((lstm_bwd_pointwise_kernel<NINT_F32>), grid, dim3(256), 0, st, *a);
   NINT_LAUNCH_CHECK();
   return NINT_OK;
 }
@@ -578,7 +581,9 @@ int nint_internal_cell_bwd_pointwise(const nint_layer* ly, const nint_geom* g, i
 extern "C" int nint_cell_bwd_pointwise(const nint_layer* ly, const nint_geom* g, int dtype, int N, const void* gates,
                                        const float* c_prev, const float* c_new, const void* dh, float* dc, void* dG,
                                        void* stream) {
-  return nint_internal_cell_bwd_pointwise(ly, g, dtype, N, gates, c_prev, c_new, dh, dc, dG, false, stream, nullptr, nullptr);
+  PwArgs a;
+  const int rc = nint_internal_pointwise_plan(ly, g, dtype, N, gates, c_prev, c_new, dh, dc, dG, false, nullptr, &a);
+  return rc != NINT_OK ? rc : nint_internal_pointwise_enqueue(&a, dtype, stream);
 }
 
 // ------------------------------------------------------------------------------ 1x1 head

@@ -3,6 +3,7 @@
 // ConvLSTM forward (model.py:253-274) or its BPTT from C++ on one HIP stream, so the Python
 // side pays one ctypes call per pass instead of one per kernel.
 #include <string.h>
+#include <vector>
 #include "nint_common.h"
 
 extern "C" int nint_version(void) { return NINT_VERSION; }
@@ -89,11 +90,10 @@ extern "C" int nint_selftest(float* out, void* stream) {
 }
 
 // ------------------------------------------------------------------------------ sequence drivers
-// Every launch of a pass is enqueued from C++ on the CALLER's stream, in dependency order.  The library owns no
-// streams, events or other state.  At the bench's batch size a (t, layer) wavefront on side streams and weight-gradient
-// reductions overlapped with the BPTT chain were both at or below this order (co-resident
-// MFMA-bound kernels evict each other's LDS / register budget; every cross-stream edge is a marker on the first layer's
-// chain).  For small batches the forward wavefront runs as ONE grid per step instead (nint_seq.wave, conv_lstm_multi_kernel).
+// Every launch of a pass is enqueued from C++ on the CALLER's stream, in dependency order.  The library owns no streams, events
+// or other state.  A (t, layer) wavefront on side streams and weight-gradient reductions overlapped with the BPTT chain were both at
+// or below this order (co-resident MFMA-bound kernels evict each other's LDS / register budget); independent
+// launches go out as ONE grid instead (nint_seq.wave; conv_lstm_multi_kernel and its kin).
 static inline size_t esize(int dtype) { return dtype == NINT_BF16 ? 2 : 4; }
 
 __global__ void probe_stamp_kernel(unsigned long long* slot, unsigned long long tag) {
@@ -129,362 +129,362 @@ static int seq_check(const nint_seq* s) {
   return NINT_OK;
 }
 
-extern "C" int nint_seq_fwd(const nint_seq* s, void* stream) {
-  int rc = seq_check(s);
-  if (rc != NINT_OK) return rc;
-  const nint_geom* g = &s->g;
-  const size_t es = esize(s->dtype);
-  const size_t halo_px = (size_t)g->Hh * g->Wh, comp_px = (size_t)g->H * g->W;
-  const int B = s->B, L = s->L;
-  Probe probe = make_probe(s, false, stream);
-  auto job = [&](int l, int t) {
-    const nint_layer* ly = &s->layer[l];
-    const char* x_slab = (l == 0)
-        ? (const char*)s->xs + (size_t)t * B * halo_px * ly->Cxp * es            // x[:, t]  (model.py:266)
-        : (const char*)s->h[l - 1] + (size_t)(t + 1) * B * halo_px * ly->Cxp * es;  // h of the layer below (model.py:271)
-    const size_t hs = (size_t)B * halo_px * ly->Chp * es;
-    const size_t cs = (size_t)B * comp_px * ly->Chp;
-    const bool zero_state = (t == 0 && !s->has_init_state);     // model.py:259-262: zeros -> skip the h half of K
-    CellFwdJob j;
-    j.ly = ly; j.x_slab = x_slab;
-    j.h_prev = zero_state ? nullptr : (const char*)s->h[l] + (size_t)t * hs;
-    j.c_prev = zero_state ? nullptr : s->c[l] + (size_t)t * cs;
-    j.h_out = (char*)s->h[l] + (size_t)(t + 1) * hs;
-    j.c_out = s->c[l] + (size_t)(t + 1) * cs;
-    j.gates_out = s->gates[l] ? (char*)s->gates[l] + (size_t)t * B * comp_px * 4 * ly->Ch16 * es : nullptr;
-    return j;
-  };
-  // wave = 2 / 3: every gate launch of the pass on 8-row tiles (the merged grids AND the lone launches at the ends of the
-  // wavefront, so that the pass equals the time-major order with tile_rows pinned to 8 bit for bit)
-  const bool rows8 = (s->wave == 2 || s->wave == 3 || s->wave == 4) && L > 1 && L <= NINT_MULTI_MAX;
-  auto launch = [&](int l, int t) {
-    CellFwdJob j = job(l, t);
-    nint_layer l8;
-    if (rows8 && j.ly->tile_rows == 0) { l8 = *j.ly; l8.tile_rows = 8; j.ly = &l8; }
-    probe.stamp(NINT_PROBE_GATE, l, t, 0);
-    const int r = nint_cell_fwd(j.ly, g, s->dtype, B, j.x_slab, j.h_prev, j.c_prev, j.h_out, j.c_out, j.gates_out, stream);
-    probe.stamp(NINT_PROBE_GATE, l, t, 1);
-    return r;
-  };
-  if (s->wave && L > 1 && L <= NINT_MULTI_MAX) {
-    // (t, layer) WAVEFRONT: step w runs gate(l, w - l) of every layer -- each needs gate(l-1, w-l) and gate(l, w-l-1), both
-    // of step w-1 -- as ONE grid (conv_lstm_multi_kernel).  T + L - 1 launches instead of T * L; the same workgroups
-    // on the same data, so the results are those of the time-major order bit for bit.
-    for (int w = 0; w < s->T + L - 1; ++w) {
-      ConvPlan plans[NINT_MULTI_MAX];
-      int lt[NINT_MULTI_MAX][2], n = 0;
-      for (int l = 0; l < L; ++l) {
-        const int t = w - l;
-        if (t < 0 || t >= s->T) continue;
-        lt[n][0] = l; lt[n][1] = t; ++n;
-      }
-      rc = n > 1 ? NINT_OK : NINT_E_SHAPE;
-      nint_layer ly8[NINT_MULTI_MAX];
-      for (int q = 0; q < n && rc == NINT_OK; ++q) {
-        CellFwdJob j = job(lt[q][0], lt[q][1]);
-        if (rows8 && j.ly->tile_rows == 0) {
-          // mid-size batches: the first layer's 8-row tiles make the merged grid a 256-register kernel at two workgroups per CU,
-          // where the narrow layers' 4-row tiles lose what they were chosen for (a third and fourth workgroup per CU): every
-          // problem of the grid takes 8-row tiles (half the weight bytes per MFMA).  Measured at B = 8, three fresh-process
-          // pairs: forward 2.84-2.86 -> 2.71-2.72 ms, step 1018-1024 -> 1037-1042 samples/s (profiles/r04_d_wave_rows8.txt).
-          // = the time-major order with tile_rows pinned to 8, bit for bit; against the default order (4-row narrow tiles) the
-          // four K-slice partials of a pixel are summed in another order: f32 rounding.
-          ly8[q] = *j.ly; ly8[q].tile_rows = 8; j.ly = &ly8[q];
-        }
-        rc = nint_internal_cell_fwd_plan(&j, g, s->dtype, B, &plans[q]);
-      }
-      if (rc == NINT_OK) {
-        probe.stamp(NINT_PROBE_WAVE, n, w, 0);
-        rc = nint_internal_conv_multi(plans, n, s->dtype, stream);
-        probe.stamp(NINT_PROBE_WAVE, n, w, 1);         // (a shape the merged grid does not hold: an empty bracket, then the launches one by one)
-      }
-      if (rc == NINT_E_SHAPE) {                // a shape the merged grid does not hold (or a single launch): one by one
-        for (int q = 0; q < n; ++q) {
-          rc = launch(lt[q][0], lt[q][1]);
-          if (rc != NINT_OK) return rc;
-        }
-      } else if (rc != NINT_OK) {
-        return rc;
-      }
+// A pass is first PLANNED into an ordered list of steps -- host arithmetic only: nothing is enqueued, no stream is touched, no
+// buffer is read -- and then the list is enqueued (run_steps).  nint_debug_seq_plan shows the same list to tests and tools.
+enum { STEP_CONV, STEP_MULTI, STEP_PW, STEP_GATE };
+struct SeqProb { int op, layer, t; };              // one conv / pointwise problem (NINT_OP_*)
+struct GateCall { CellFwdJob job; nint_layer ly; int carrier; };
+struct SeqStep {
+  int kind;        // a planned conv launch | a merged grid | a pointwise backward | a direct nint_cell_fwd call (stencil / dense-K: no planned form)
+  int probe, tag_layer, tag_t;       // the NINT_PROBE_* kind and tag it is bracketed with
+  int n; SeqProb prob[NINT_MULTI_MAX + 1];         // its problems, in grid order
+  union { ConvPlan conv; MultiPlan multi; PwArgs pw; GateCall gate; };
+};
+typedef std::vector<SeqStep> Steps;
+
+static SeqStep& push(Steps& out, int kind, int probe, int tag_layer, int tag_t) {
+  SeqStep& st = out.emplace_back();
+  st.kind = kind; st.probe = probe; st.tag_layer = tag_layer; st.tag_t = tag_t;
+  return st;
+}
+static void push_conv(Steps& out, const ConvPlan& pl, int probe, int op, int l, int t) {
+  if (pl.gx <= 0) return;            // (e.g. time 0 of the bottom layer from a zero state without an input gradient: nothing to launch, nothing to bracket)
+  SeqStep& st = push(out, STEP_CONV, probe, l, t);
+  st.prob[st.n++] = SeqProb{op, l, t}; st.conv = pl;
+}
+static void push_pw(Steps& out, const PwArgs& pa, int l, int t) {
+  SeqStep& st = push(out, STEP_PW, NINT_PROBE_POINTWISE, l, t);
+  st.prob[st.n++] = SeqProb{NINT_OP_POINTWISE, l, t}; st.pw = pa;
+}
+// plans[0..n) (pw: and a pointwise backward) as ONE grid with the problems prob[0..np) -- where a merged kernel holds them; asked
+// once, here, and the answer (kernel, argument block, grid) stays in the step.  false: nothing pushed, the caller plans them one by one
+static bool push_grid(Steps& out, const ConvPlan* plans, int n, const PwArgs* pw, int probe, int tag_layer, int tag_t, const SeqProb* prob, int np) {
+  SeqStep& st = push(out, STEP_MULTI, probe, tag_layer, tag_t);
+  if (nint_internal_multi_plan(plans, n, pw, &st.multi) != NINT_OK) { out.pop_back(); return false; }
+  for (; st.n < np; ++st.n) st.prob[st.n] = prob[st.n];
+  return true;
+}
+
+static int run_steps(const nint_seq* s, const Steps& steps, Probe& probe, void* stream) {
+  for (const SeqStep& st : steps) {
+    probe.stamp(st.probe, st.tag_layer, st.tag_t, 0);
+    int rc = NINT_E_ARG;
+    switch (st.kind) {
+      case STEP_CONV: rc = nint_internal_conv_enqueue(&st.conv, stream); break;
+      case STEP_MULTI: rc = nint_internal_multi_enqueue(&st.multi, s->dtype, stream); break;
+      case STEP_PW: rc = nint_internal_pointwise_enqueue(&st.pw, s->dtype, stream); break;
+      case STEP_GATE: rc = nint_cell_fwd(&st.gate.ly, &s->g, s->dtype, s->B, st.gate.job.x_slab, st.gate.job.h_prev, st.gate.job.c_prev,
+                                         st.gate.job.h_out, st.gate.job.c_out, st.gate.job.gates_out, stream); break;
     }
-    return NINT_OK;
+    probe.stamp(st.probe, st.tag_layer, st.tag_t, 1);
+    if (rc != NINT_OK) return rc;
   }
-  for (int t = 0; t < s->T; ++t) {                               // model.py:265
-    for (int l = 0; l < L; ++l) {                                // model.py:267
-      rc = launch(l, t);
-      if (rc != NINT_OK) return rc;
+  return NINT_OK;
+}
+
+// gate(l, t): NINT_OK = *pl is its conv launch; NINT_E_SHAPE = no planned form (pl->gx == 0), *gc is the direct call
+static int plan_gate(const nint_seq* s, int n_cu, bool rows8, int l, int t, GateCall* gc, ConvPlan* pl) {
+  const nint_geom* g = &s->g;
+  const size_t es = esize(s->dtype), halo_px = (size_t)g->Hh * g->Wh, comp_px = (size_t)g->H * g->W, B = s->B;
+  gc->ly = s->layer[l];
+  const nint_layer* ly = &gc->ly;
+  // wave = 2 / 3 / 4: every gate launch of the pass on 8-row tiles -- the merged grids AND the lone launches at the ends of the
+  // wavefront: the time-major order with tile_rows pinned to 8, bit for bit.  The first layer's 8-row tiles make the merged grid a
+  // 256-register kernel at two workgroups per CU anyway, where the narrow layers' 4-row tiles lose what they were chosen for; 8-row
+  // tiles halve their weight bytes per MFMA (B = 8: forward 2.85 -> 2.71 ms, profiles/r04_d_wave_rows8.txt).
+  if (rows8 && ly->tile_rows == 0) gc->ly.tile_rows = 8;
+  const size_t hs = (size_t)B * halo_px * ly->Chp * es, cs = (size_t)B * comp_px * ly->Chp;
+  const bool zero_state = (t == 0 && !s->has_init_state);     // model.py:259-262: zeros -> skip the h half of K
+  CellFwdJob& j = gc->job; j.ly = ly;
+  j.x_slab = (l == 0) ? (const char*)s->xs + (size_t)t * B * halo_px * ly->Cxp * es                // x[:, t]  (model.py:266)
+                      : (const char*)s->h[l - 1] + (size_t)(t + 1) * B * halo_px * ly->Cxp * es;   // h of the layer below (model.py:271)
+  j.h_prev = zero_state ? nullptr : (const char*)s->h[l] + (size_t)t * hs; j.c_prev = zero_state ? nullptr : s->c[l] + (size_t)t * cs;
+  j.h_out = (char*)s->h[l] + (size_t)(t + 1) * hs; j.c_out = s->c[l] + (size_t)(t + 1) * cs;
+  j.gates_out = s->gates[l] ? (char*)s->gates[l] + (size_t)t * B * comp_px * 4 * ly->Ch16 * es : nullptr;
+  const int rc = nint_internal_cell_fwd_plan(&j, g, s->dtype, s->B, n_cu, pl);
+  gc->carrier = pl->carrier;
+  return rc;
+}
+
+static int plan_fwd(const nint_seq* s, int n_cu, Steps& out) {
+  const int L = s->L, T = s->T;
+  // (t, layer) WAVEFRONT: step w runs gate(l, w - l) of every layer -- each needs gate(l-1, w-l) and gate(l, w-l-1), both of
+  // step w-1 -- as ONE grid (conv_lstm_multi[8]_kernel).  T + L - 1 launches instead of T * L; the same workgroups on the same
+  // data, so the results are those of the time-major order bit for bit.  Else: for t, for layer (model.py:265-267).
+  const bool wavefront = s->wave && L > 1 && L <= NINT_MULTI_MAX;
+  const bool rows8 = wavefront && (s->wave == 2 || s->wave == 3 || s->wave == 4);
+  out.reserve((size_t)T * L);
+  for (int w = 0; w < (wavefront ? T + L - 1 : T * L); ++w) {
+    GateCall gc[NINT_MULTI_MAX]; ConvPlan pl[NINT_MULTI_MAX]; SeqProb pr[NINT_MULTI_MAX];
+    int n = 0; bool planned = true;
+    for (int l = wavefront ? 0 : w % L; l < (wavefront ? L : w % L + 1); ++l) {
+      const int t = wavefront ? w - l : w / L;
+      if (t < 0 || t >= T) continue;
+      const int rc = plan_gate(s, n_cu, rows8, l, t, &gc[n], &pl[n]);
+      if (rc != NINT_OK && rc != NINT_E_SHAPE) return rc;
+      planned = planned && rc == NINT_OK;
+      pr[n++] = SeqProb{NINT_OP_GATE, l, t};
+    }
+    if (n > 1 && planned && push_grid(out, pl, n, nullptr, NINT_PROBE_WAVE, n, w, pr, n)) continue;
+    for (int q = 0; q < n; ++q) {    // (a single launch, or a shape the merged grid does not hold: one by one)
+      if (pl[q].gx > 0) { push_conv(out, pl[q], NINT_PROBE_GATE, NINT_OP_GATE, pr[q].layer, pr[q].t); continue; }
+      SeqStep& st = push(out, STEP_GATE, NINT_PROBE_GATE, pr[q].layer, pr[q].t);
+      st.prob[st.n++] = pr[q]; st.gate = gc[q]; st.gate.job.ly = nullptr;      // (run_steps passes the step's own copy)
     }
   }
   return NINT_OK;
 }
 
-// default of the "lower layer's pointwise backward on the fused layer's x columns" option: on (measured inside the bench
-// step, five alternations on one device: 962.2 -> 963.6 samples/s, every pair positive; profiles/HISTORY.md)
+
+// default of the "lower layer's pointwise backward on the fused layer's x columns" option: on (962.2 -> 963.6 samples/s, profiles/HISTORY.md)
 #ifndef NINT_AUTO_LO
 #define NINT_AUTO_LO true
 #endif
 
-extern "C" int nint_seq_bwd(const nint_seq* s, void* stream) {
-  int rc = seq_check(s);
+static int bwd_check(const nint_seq* s) {
+  const int rc = seq_check(s);
   if (rc != NINT_OK) return rc;
-  const nint_geom* g = &s->g;
-  const size_t es = esize(s->dtype);
-  const size_t halo_px = (size_t)g->Hh * g->Wh, comp_px = (size_t)g->H * g->W;
-  const int B = s->B, L = s->L;
-  for (int l = 0; l < L; ++l)
+  for (int l = 0; l < s->L; ++l)
     if (!s->gates[l] || !s->dG[l] || !s->dh[l] || !s->dc[l] || !s->dW[l] || !s->db[l]) return NINT_E_ARG;
-  if (s->need_dx && !s->dx) return NINT_E_ARG;
-  if (!s->wg_partial) return NINT_E_ARG;
-  if (s->fuse_bwd < 0 || (s->fuse_bwd > 2 && !(s->fuse_bwd & 0x40000000))) return NINT_E_ARG;
-  if (s->bwd_parts < 0 || s->bwd_parts > 2) return NINT_E_ARG;
+  if ((s->need_dx && !s->dx) || !s->wg_partial) return NINT_E_ARG;
+  if (s->fuse_bwd < 0 || (s->fuse_bwd > 2 && !(s->fuse_bwd & 0x40000000)) || s->bwd_parts < 0 || s->bwd_parts > 2) return NINT_E_ARG;
+  return NINT_OK;
+}
 
-  // BPTT.  A layer runs either the CLASSIC step (pointwise backward of time u, then conv backward-data of time u) or the
-  // FUSED step X[u] = conv backward-data of time u with the pointwise backward of time u-1 in its epilogue
-  // (nint_cell_bwd_fused: d/dh_{u-1} never goes to memory).  Chosen per layer by the K-steps of its dgrad launch:
-  // measured inside the bench step on two devices (bench.py --fuse-bwd 0x40000000|masks), fusing the 18-step top layer alone gives
-  // +0.7 ... +1.0 %, the 36-step layer -0.9 %, the 200-step layer -1.7 % (its workgroups run their phases in lockstep, so
-  // the heavier epilogue adds its full HBM time instead of hiding behind the other workgroup's matrix work).
-  // A fused layer consumes the x columns that the layer above produced for time u-1, so it runs ONE time step behind the
-  // layer above: at outer step s layer l works on time u_l = s + off_l, off_l = number of fused layers among l..L-1.
-  // Fused layer: u = T -> pointwise backward of T-1 alone (d/dh_{T-1} comes from the head / the caller),
-  // 1 <= u <= T-1 -> X[u], u = 0 -> plain conv backward-data of time 0.
-  // A fused layer above a classic one can ALSO run that layer's pointwise backward, on its x columns (they are the last
-  // contribution to the lower layer's d/dh of the same time step): lo[l] -- the lower layer then only launches its dgrad.
-  bool fused[NINT_MAX_LAYERS], lo[NINT_MAX_LAYERS], loc[NINT_MAX_LAYERS];
+// BPTT.  A layer runs either the CLASSIC step (pointwise backward of time u, then conv backward-data of time u) or the
+// FUSED step X[u] = conv backward-data of time u with the pointwise backward of time u-1 in its epilogue
+// (nint_cell_bwd_fused: d/dh_{u-1} never goes to memory).  Chosen per layer by the K-steps of its dgrad launch: inside the bench
+// step fusing the 18-step top layer alone gives +0.7 ... +1.0 %, the 36-step layer -0.9 %, the 200-step layer -1.7 %.
+// A fused layer consumes the x columns that the layer above produced for time u-1, so it runs ONE time step behind the
+// layer above: at outer step so layer l works on time u_l = so + off_l, off_l = number of fused layers among l..L-1.
+// Fused layer: u = T -> pointwise backward of T-1 alone (d/dh_{T-1} comes from the head / the caller),
+// 1 <= u <= T-1 -> X[u], u = 0 -> plain conv backward-data of time 0.
+struct BwdPlanner {
+  const nint_seq* s; int n_cu; Steps& out;
+  int L, T; size_t B, es, halo_px, comp_px;
+  // ---- the schedule facts, computed once (the constructor)
+  bool fused[NINT_MAX_LAYERS];
+  // lo: the fused layer l also runs the pointwise backward of the classic layer below, on its x columns (the last contribution to
+  // that layer's d/dh of the same time step): the layer below only launches its dgrad.  loc: a CLASSIC layer does the same for the
+  // classic layer below it (its dgrad then runs the fused kernel with the h columns stored, on 4-row tiles)
+  bool lo[NINT_MAX_LAYERS], loc[NINT_MAX_LAYERS];
   int off[NINT_MAX_LAYERS], pw_done[NINT_MAX_LAYERS];
-  const bool explicit_mask = (s->fuse_bwd & 0x40000000) != 0;
-  for (int l = L - 1; l >= 0; --l) {
-    const nint_layer* ly = &s->layer[l];
-    const int ksteps = (4 * ly->Ch16 / (s->dtype == NINT_BF16 ? 32 : 16)) * ly->k * ly->k;   // K-steps of the layer's dgrad launch
-    fused[l] = explicit_mask ? ((s->fuse_bwd >> l) & 1) != 0 : (s->fuse_bwd == 2 || (s->fuse_bwd == 0 && ksteps <= 24));
-    off[l] = (l == L - 1 ? 0 : off[l + 1]) + (fused[l] ? 1 : 0);
-    pw_done[l] = -1;
-  }
-  for (int l = 0; l < L; ++l) {
-    lo[l] = fused[l] && l > 0 && !fused[l - 1] && (explicit_mask ? ((s->fuse_bwd >> (8 + l)) & 1) != 0 : NINT_AUTO_LO);
-    // ... and a CLASSIC layer can do the same for the classic layer below it (its dgrad then runs the fused kernel with the
-    // h columns stored; 4-row tiles, whose many small workgroups overlap the added HBM traffic)
-    loc[l] = !fused[l] && l > 0 && !fused[l - 1] && explicit_mask && ((s->fuse_bwd >> (16 + l)) & 1) != 0;
-  }
-  const int T = s->T;
-  Probe probe = make_probe(s, true, stream);
-  // Small batches (nint_seq.wave): the bottom layer's dgrad of one outer step and the top layer's fused step of the next are
-  // ADJACENT launches that share no buffer when the stack has three or more layers (the top layer's step touches its own
-  // state and layer L-2's; the bottom dgrad reads dG[0] and writes dh[0] / dx): they go out as ONE grid
-  // (nint_internal_conv_multi).  The bottom dgrad is held back (`pend`) until the next launch is known.
-  const int wv = s->wave;
-  const bool merge = (wv == 1 || wv == 3) && L >= 3 && fused[L - 1] && !fused[0] && !loc[0];   // (wave == 2: the forward wavefront only)
-  // Mid-size batches (wave = 4): the bottom layer's dgrad of time u+1 waits for the dgrad of the layer above of time u instead and
-  // the two go out as one grid, the wide one first (the narrow layer's workgroups fill its last round: the forward wavefront's
-  // effect).  Both produce a piece of the bottom layer's d/dh of time u, so each stores its own -- the layer above into dh[0],
-  // the bottom layer into the head of the split-K scratch, which is idle until the weight gradients -- and the bottom layer's
-  // pointwise backward adds the two (f32: the same sum as the read-modify-write of the time-major order, bit for bit; bf16: each
-  // piece is rounded to bf16 before the f32 add instead of the running sum after it).
-  const size_t dh0_bytes = (size_t)B * comp_px * s->layer[0].Chp * es;
-  const bool merge_d = (wv == 4 || wv == 5) && L >= 2 && !fused[0] && !fused[1] && !loc[0] && !loc[1] && s->wg_partial_bytes >= dh0_bytes;
-  void* const dh0_own = merge_d ? s->wg_partial : s->dh[0];
-  struct { bool on; ConvPlan plan; const void* dG; void* dx; void* dh_prev; bool ow; int u; } pend = {};
-  auto flush = [&]() {                           // the held-back dgrad as a launch of its own
-    if (!pend.on) return (int)NINT_OK;
-    pend.on = false;
-    probe.stamp(NINT_PROBE_DGRAD, 0, pend.u, 0);
-    const int r = nint_internal_conv_dgrad(&s->layer[0], g, s->dtype, B, pend.dG, pend.dx, pend.dh_prev, pend.ow, nullptr, stream);
-    probe.stamp(NINT_PROBE_DGRAD, 0, pend.u, 1);
-    return r;
-  };
-  // ... and the bottom layer's pointwise backward of time u waits for the top layer's fused step of time u-1, the next launch in
-  // this order and independent of it (it touches layers >= 1 only): one grid, the fused step's workgroups first (conv_bwd_multi_kernel
-  // with a pointwise problem; the same arithmetic: bit-identical).  B = 2 / 4 / 8: another +1.3 / +0.6 / +0.25 % (profiles/r04_f_wave4.txt).
-  const bool merge_p = merge_d && L >= 3 && fused[L - 1];
-  struct { bool on; int t; } pend_pw = {};
-  auto p0_launch = [&](int t, PwArgs* plan) {
-    const nint_layer* l0 = &s->layer[0];
-    const size_t cs0 = (size_t)B * comp_px * l0->Chp, Gc0 = 4 * (size_t)l0->Ch16;
-    return nint_internal_cell_bwd_pointwise(l0, g, s->dtype, B, (const char*)s->gates[0] + (size_t)t * B * comp_px * Gc0 * es, s->c[0] + (size_t)t * cs0,
-                                            s->c[0] + (size_t)(t + 1) * cs0, s->dh[0], s->dc[0], (char*)s->dG[0] + (size_t)t * B * halo_px * Gc0 * es,
-                                            t == T - 1 && (s->zero_dstate & 1), stream, merge_d && t < T - 1 ? dh0_own : nullptr, plan);
-  };
-  auto flush_pw = [&]() {
-    if (!pend_pw.on) return (int)NINT_OK;
-    pend_pw.on = false;
-    probe.stamp(NINT_PROBE_POINTWISE, 0, pend_pw.t, 0);
-    const int r = p0_launch(pend_pw.t, nullptr);
-    probe.stamp(NINT_PROBE_POINTWISE, 0, pend_pw.t, 1);
-    return r;
-  };
-  for (int so = T - 1; so >= -off[0] && s->bwd_parts != 2; --so) {      // (part 2: the chain ran in the part-1 call)
+  // (nint_seq.wave, include/nint.h)  merge, wave 1 / 3: the bottom layer's dgrad of one outer step and the top layer's fused step of
+  // the next are ADJACENT launches that share no buffer in a stack of three or more layers: ONE grid; the bottom dgrad is held back
+  // until the next launch is known.  merge_d, wave 4 / 5: it waits for the dgrad of layer 1 of the next time step instead, the wide
+  // launch first.  Both produce a piece of the bottom layer's d/dh, so each stores its own -- layer 1 into dh[0], the bottom layer
+  // into the head of the split-K scratch, idle until the weight gradients (dh0_own) -- and the bottom layer's pointwise backward
+  // adds the two (f32: the sum of the time-major order bit for bit; bf16: each piece is rounded before the f32 add).  merge_p: ... and
+  // that pointwise backward of time u waits for the top layer's fused step of time u-1, the next launch and independent of it
+  // (layers >= 1 only): one grid, the fused step's workgroups first (the same arithmetic; profiles/r04_f_wave4.txt).
+  bool merge, merge_d, merge_p;
+  void* dh0_own;
+  // ---- the two hold-back slots: a launch waits here until its partner, or a launch that conflicts with it, is planned
+  bool has_d, has_p;
+  ConvPlan held_d; int held_u;       // the bottom layer's dgrad of time held_u
+  PwArgs held_p; int held_t;         // the bottom layer's pointwise backward of time held_t
+
+  BwdPlanner(const nint_seq* s_, int n_cu_, Steps& out_) : s(s_), n_cu(n_cu_), out(out_), L(s_->L), T(s_->T), B(s_->B), has_d(false), has_p(false), held_u(0), held_t(0) {
+    es = esize(s->dtype); halo_px = (size_t)s->g.Hh * s->g.Wh; comp_px = (size_t)s->g.H * s->g.W;
+    const bool explicit_mask = (s->fuse_bwd & 0x40000000) != 0;
     for (int l = L - 1; l >= 0; --l) {
-      const int u = so + off[l];
-      if (u < 0 || u > (fused[l] ? T : T - 1)) continue;
-      if (pend_pw.on && !(l == L - 1 && u >= 1 && u < T)) {     // (anything but the fused step it waits for)
-        rc = flush_pw();
+      const nint_layer* ly = &s->layer[l];
+      const int ksteps = (4 * ly->Ch16 / (s->dtype == NINT_BF16 ? 32 : 16)) * ly->k * ly->k;   // K-steps of the layer's dgrad launch
+      fused[l] = explicit_mask ? ((s->fuse_bwd >> l) & 1) != 0 : (s->fuse_bwd == 2 || (s->fuse_bwd == 0 && ksteps <= 24));
+      off[l] = (l == L - 1 ? 0 : off[l + 1]) + (fused[l] ? 1 : 0);
+      pw_done[l] = -1;
+    }
+    for (int l = 0; l < L; ++l) {
+      lo[l] = fused[l] && l > 0 && !fused[l - 1] && (explicit_mask ? ((s->fuse_bwd >> (8 + l)) & 1) != 0 : NINT_AUTO_LO);
+      loc[l] = !fused[l] && l > 0 && !fused[l - 1] && explicit_mask && ((s->fuse_bwd >> (16 + l)) & 1) != 0;
+    }
+    merge = (s->wave == 1 || s->wave == 3) && L >= 3 && fused[L - 1] && !fused[0] && !loc[0];   // (wave == 2: the forward wavefront only)
+    const size_t dh0_bytes = (size_t)B * comp_px * s->layer[0].Chp * es;
+    merge_d = (s->wave == 4 || s->wave == 5) && L >= 2 && !fused[0] && !fused[1] && !loc[0] && !loc[1] && s->wg_partial_bytes >= dh0_bytes;
+    merge_p = merge_d && L >= 3 && fused[L - 1];
+    dh0_own = merge_d ? (void*)s->wg_partial : s->dh[0];
+  }
+
+  void flush_d() { if (has_d) push_conv(out, held_d, NINT_PROBE_DGRAD, NINT_OP_DGRAD, 0, held_u); has_d = false; }
+  void flush_p() { if (has_p) push_pw(out, held_p, 0, held_t); has_p = false; }
+
+  // the pointwise backward of layer l: consumes dh[l] / dc[l] of time t (first BPTT step: not a dc flagged all-zero), writes dG of time t
+  int pointwise(int l, int t, int so) {
+    if (!merge_d || l == 0) flush_d();                         // (wave = 4 / 5: the held-back dgrad touches layer 0 only)
+    const nint_layer* ly = &s->layer[l];
+    const size_t cs = (size_t)B * comp_px * ly->Chp, Gc = 4 * (size_t)ly->Ch16;
+    PwArgs pa;
+    const int rc = nint_internal_pointwise_plan(ly, &s->g, s->dtype, B, (const char*)s->gates[l] + (size_t)t * B * comp_px * Gc * es,
+                                                s->c[l] + (size_t)t * cs, s->c[l] + (size_t)(t + 1) * cs, s->dh[l], s->dc[l],
+                                                (char*)s->dG[l] + (size_t)t * B * halo_px * Gc * es, t == T - 1 && ((s->zero_dstate >> (2 * l)) & 1),
+                                                merge_d && l == 0 && t < T - 1 ? dh0_own : nullptr, &pa);
+    if (rc != NINT_OK) return rc;
+    if (merge_p && l == 0 && so + off[L - 1] >= 2) { has_p = true; held_p = pa; held_t = t; }    // the next outer step opens with a fused step of the top layer
+    else push_pw(out, pa, l, t);
+    return NINT_OK;
+  }
+
+  // the pointwise backward of layer l - 1 at time u as a rider on layer l's launch
+  void ride_lo(DgradPw& pw, int l, int u) {
+    const nint_layer* lb = &s->layer[l - 1];
+    const size_t cs_b = (size_t)B * comp_px * lb->Chp, Gc_b = 4 * (size_t)lb->Ch16;
+    pw.lo_gates = (const char*)s->gates[l - 1] + (size_t)u * B * comp_px * Gc_b * es;
+    pw.lo_c_prev = s->c[l - 1] + (size_t)u * cs_b; pw.lo_c_new = s->c[l - 1] + (size_t)(u + 1) * cs_b;
+    pw.lo_dc = s->dc[l - 1]; pw.lo_dG_out = (char*)s->dG[l - 1] + (size_t)u * B * halo_px * Gc_b * es;
+    pw.lo_Ch16 = lb->Ch16; pw.lo_dc_zero = u == T - 1 && ((s->zero_dstate >> (2 * (l - 1))) & 1);
+    pw_done[l - 1] = u;
+  }
+
+  // layer l's conv backward-data of time u (pw: with a pointwise backward in its epilogue)
+  int dgrad(int l, int u, const DgradPw* pw, ConvPlan* pl) {
+    const nint_layer* ly = &s->layer[l];
+    void* dx_dst = (l > 0) ? s->dh[l - 1] : (s->need_dx ? (void*)((char*)s->dx + (size_t)u * B * comp_px * ly->Cxp * es) : nullptr);
+    // the x columns go to the layer below's dh or this time step's dx slab: STORED where nothing else is there (dx; a dh flagged zero at the
+    // first step; a FUSED layer below, whose dh buffer only ever carries them), else accumulated onto the h columns a classic layer below stored
+    const bool ow = l == 0 ? true : (u == T - 1 ? (((s->zero_dstate >> (2 * (l - 1) + 1)) & 1) != 0) : (fused[l - 1] || (merge_d && l == 1)));
+    // at time 0 with a zero initial state nobody consumes d/dh_{-1}; a fused step keeps the h columns in registers
+    void* dh_prev = (u == 0 && !s->has_init_state) || (pw && pw->gates) ? nullptr
+                  : (l == 0 && u > 0 ? dh0_own : s->dh[l]);    // (time 0: the caller reads d/dh_{-1} from dh[0])
+    return nint_internal_conv_dgrad(ly, &s->g, s->dtype, B, (const char*)s->dG[l] + (size_t)u * B * halo_px * 4 * ly->Ch16 * es, dx_dst, dh_prev,
+                                    ow, pw, n_cu, pl);
+  }
+
+  // the held-back bottom dgrad and `second` (layer l, time u) as one grid, where a merged kernel holds the two shapes
+  bool pair(const ConvPlan& second, int op, int l, int u) {
+    const ConvPlan pl[2] = {held_d, second};
+    const SeqProb pr[2] = {{NINT_OP_DGRAD, 0, held_u}, {op, l, u}};
+    if (!push_grid(out, pl, 2, nullptr, NINT_PROBE_BWD_PAIR, l, u, pr, 2)) return false;
+    has_d = false;
+    return true;
+  }
+
+  int classic(int l, int u, int so) {
+    int rc = pw_done[l] != u ? pointwise(l, u, so) : (int)NINT_OK;    // (else: the layer above already ran this pointwise backward)
+    if (rc != NINT_OK) return rc;
+    DgradPw pw = {};
+    if (loc[l]) { ride_lo(pw, l, u); pw.tile_rows = 4; }
+    ConvPlan pl;
+    rc = dgrad(l, u, loc[l] ? &pw : nullptr, &pl);
+    if (rc != NINT_OK) return rc;
+    if (merge_d && l == 1 && has_d && pair(pl, NINT_OP_DGRAD, l, u)) return NINT_OK;   // the bottom layer's dgrad of the step before + this one
+    if (!merge_d || l <= 1) flush_d();
+    // (held unless it is the very last launch: there is a step of a layer above to pair it with)
+    if ((merge || merge_d) && l == 0 && so > -off[0]) { has_d = pl.gx > 0; held_d = pl; held_u = u; }
+    else push_conv(out, pl, NINT_PROBE_DGRAD, NINT_OP_DGRAD, l, u);
+    return NINT_OK;
+  }
+
+  int fused_step(int l, int u) {                               // X[u], 1 <= u <= T - 1
+    const nint_layer* ly = &s->layer[l];
+    const size_t cs = (size_t)B * comp_px * ly->Chp, Gc = 4 * (size_t)ly->Ch16;
+    DgradPw pw = {};
+    pw.gates = (const char*)s->gates[l] + (size_t)(u - 1) * B * comp_px * Gc * es; pw.c_prev = s->c[l] + (size_t)(u - 1) * cs;
+    pw.c_new = s->c[l] + (size_t)u * cs; pw.dc = s->dc[l]; pw.old = l < L - 1 ? s->dh[l] : nullptr;
+    pw.dG_out = (char*)s->dG[l] + (size_t)(u - 1) * B * halo_px * Gc * es;
+    if (lo[l]) ride_lo(pw, l, u);
+    const bool top_pair = merge && has_d && l == L - 1;        // the top layer's step right behind the held-back bottom dgrad
+    if (top_pair && s->wave == 3) pw.tile_rows = 8;            // (experiment: the fused step on 8-row tiles inside the two-workgroups-per-CU grid)
+    ConvPlan pl;
+    const int rc = dgrad(l, u, &pw, &pl);
+    if (rc != NINT_OK) return rc;
+    if (top_pair && pair(pl, NINT_OP_FUSED, l, u)) return NINT_OK;
+    if (!merge_d) flush_d();
+    const SeqProb pr[2] = {{NINT_OP_FUSED, l, u}, {NINT_OP_POINTWISE, 0, held_t}};
+    // this step and the bottom layer's pointwise backward of the step before: one grid
+    if (has_p && push_grid(out, &pl, 1, &held_p, NINT_PROBE_BWD_PW, l, u, pr, 2)) { has_p = false; return NINT_OK; }
+    flush_p();
+    push_conv(out, pl, NINT_PROBE_FUSED, NINT_OP_FUSED, l, u);
+    return NINT_OK;
+  }
+
+  int plan() {
+    out.reserve((size_t)(T + L) * L * 2);
+    for (int so = T - 1; so >= -off[0] && s->bwd_parts != 2; --so) {      // (part 2: the chain ran in the part-1 call)
+      for (int l = L - 1; l >= 0; --l) {
+        const int u = so + off[l];
+        if (u < 0 || u > (fused[l] ? T : T - 1)) continue;
+        if (!(l == L - 1 && u >= 1 && u < T)) flush_p();       // (anything but the fused step it waits for)
+        int rc = NINT_OK;
+        if (!fused[l]) rc = classic(l, u, so);
+        else if (u == T) rc = pointwise(l, T - 1, so);
+        else if (u >= 1) rc = fused_step(l, u);
+        else {                                                 // a fused layer's time 0: plain conv backward-data
+          if (!merge_d) flush_d();
+          ConvPlan pl;
+          if ((rc = dgrad(l, 0, nullptr, &pl)) == NINT_OK) push_conv(out, pl, NINT_PROBE_DGRAD, NINT_OP_DGRAD, l, 0);
+        }
         if (rc != NINT_OK) return rc;
       }
-      const nint_layer* ly = &s->layer[l];
-      const size_t cs = (size_t)B * comp_px * ly->Chp;
-      const size_t Gc = 4 * (size_t)ly->Ch16;
-      const size_t gs = (size_t)B * comp_px * Gc * es, dgs = (size_t)B * halo_px * Gc * es;
-      // c[l][0] is the (zero or given) initial state, so c_prev is always a valid pointer
-      auto pointwise = [&](int t) {      // consumes dh[l] / dc[l] of time t, writes dG of time t
-        // first BPTT step: state gradients flagged all-zero are neither read (dc) nor accumulated into (dh below)
-        if (!merge_d || l == 0) { const int rf = flush(); if (rf != NINT_OK) return rf; }    // (wave = 4: the held-back launch touches layer 0 only)
-        if (merge_p && l == 0 && so + off[L - 1] >= 2) {     // the next outer step opens with a fused step of the top layer
-          pend_pw.on = true; pend_pw.t = t;
-          return (int)NINT_OK;
-        }
-        probe.stamp(NINT_PROBE_POINTWISE, l, t, 0);
-        const int r = nint_internal_cell_bwd_pointwise(ly, g, s->dtype, B, (const char*)s->gates[l] + (size_t)t * gs, s->c[l] + (size_t)t * cs,
-                                                       s->c[l] + (size_t)(t + 1) * cs, s->dh[l], s->dc[l], (char*)s->dG[l] + (size_t)t * dgs,
-                                                       t == T - 1 && ((s->zero_dstate >> (2 * l)) & 1), stream,
-                                                       merge_d && l == 0 && t < T - 1 ? dh0_own : nullptr);
-        probe.stamp(NINT_PROBE_POINTWISE, l, t, 1);
-        return r;
-      };
-      // destination of the x columns of time t: the layer below's dh, or this time step's dx slab (written once)
-      void* dx_dst = (l > 0) ? s->dh[l - 1]
-                             : (s->need_dx ? (void*)((char*)s->dx + (size_t)u * B * comp_px * ly->Cxp * es) : nullptr);
-      // ... stored where nothing else is there: dx; a dh flagged zero at the first step; a FUSED layer below (its dh
-      // buffer only ever carries these columns).  Accumulated onto the h columns a classic layer below stored.
-      const bool ow = l == 0 ? true : (u == T - 1 ? (((s->zero_dstate >> (2 * (l - 1) + 1)) & 1) != 0) : (fused[l - 1] || (merge_d && l == 1)));
-      // at time 0 with a zero initial state nobody consumes d/dh_{-1}
-      void* dh_prev = (u == 0 && !s->has_init_state) ? nullptr : (l == 0 && u > 0 ? dh0_own : s->dh[l]);   // (time 0: the caller reads d/dh_{-1} from dh[0])
-      if (!fused[l]) {
-        if (pw_done[l] != u) {                 // (else: the fused layer above already ran this pointwise backward)
-          rc = pointwise(u);
-          if (rc != NINT_OK) return rc;
-        }
-        DgradPw pw = {};
-        if (loc[l]) {
-          const nint_layer* lb = &s->layer[l - 1];
-          const size_t cs_b = (size_t)B * comp_px * lb->Chp, Gc_b = 4 * (size_t)lb->Ch16;
-          pw.lo_gates = (const char*)s->gates[l - 1] + (size_t)u * B * comp_px * Gc_b * es;
-          pw.lo_c_prev = s->c[l - 1] + (size_t)u * cs_b; pw.lo_c_new = s->c[l - 1] + (size_t)(u + 1) * cs_b;
-          pw.lo_dc = s->dc[l - 1]; pw.lo_dG_out = (char*)s->dG[l - 1] + (size_t)u * B * halo_px * Gc_b * es;
-          pw.lo_Ch16 = lb->Ch16;
-          pw.lo_dc_zero = u == T - 1 && ((s->zero_dstate >> (2 * (l - 1))) & 1);
-          pw.tile_rows = 4;
-          pw_done[l - 1] = u;
-        }
-        if (merge_d && l == 1 && pend.on) {       // the bottom layer's dgrad of the step before + this one: one grid
-          ConvPlan pl[2];
-          pl[0] = pend.plan;
-          rc = nint_internal_conv_dgrad(ly, g, s->dtype, B, (const char*)s->dG[l] + (size_t)u * dgs, dx_dst, dh_prev, ow, nullptr, stream, &pl[1]);
-          if (rc != NINT_OK) return rc;
-          rc = pl[1].gx > 0 ? nint_internal_conv_multi(pl, 2, s->dtype, stream, nullptr, true) : NINT_E_SHAPE;     // (dry run: is there such a grid?)
-          if (rc == NINT_OK) {
-            probe.stamp(NINT_PROBE_BWD_PAIR, l, u, 0);
-            rc = nint_internal_conv_multi(pl, 2, s->dtype, stream);
-            probe.stamp(NINT_PROBE_BWD_PAIR, l, u, 1);
-          }
-          if (rc == NINT_OK) { pend.on = false; continue; }
-          if (rc != NINT_E_SHAPE) return rc;
-        }
-        if (!merge_d || l <= 1) {
-          rc = flush();
-          if (rc != NINT_OK) return rc;
-        }
-        if ((merge || merge_d) && l == 0 && so > -off[0]) {  // (not the very last launch: there is a top-layer step to pair it with)
-          pend.dG = (const char*)s->dG[l] + (size_t)u * dgs; pend.dx = dx_dst; pend.dh_prev = dh_prev; pend.ow = ow; pend.u = u;
-          rc = nint_internal_conv_dgrad(ly, g, s->dtype, B, pend.dG, pend.dx, pend.dh_prev, pend.ow, nullptr, stream, &pend.plan);
-          if (rc != NINT_OK) return rc;
-          pend.on = pend.plan.gx > 0;
-          continue;
-        }
-        // (time 0 of the bottom layer from a zero state without an input gradient: nothing to launch -- and nothing to bracket: rounds
-        // 3-4 stamped this empty call, one zero among the 12 layer-0 dgrad durations of a step)
-        const bool nop = !dx_dst && !dh_prev && !loc[l];
-        if (!nop) probe.stamp(NINT_PROBE_DGRAD, l, u, 0);
-        rc = nint_internal_conv_dgrad(ly, g, s->dtype, B, (const char*)s->dG[l] + (size_t)u * dgs, dx_dst, dh_prev, ow, loc[l] ? &pw : nullptr, stream);
-        if (!nop) probe.stamp(NINT_PROBE_DGRAD, l, u, 1);
-      } else if (u == T) {
-        rc = pointwise(T - 1);
-      } else if (u >= 1) {
-        DgradPw pw = {};
-        pw.gates = (const char*)s->gates[l] + (size_t)(u - 1) * gs; pw.c_prev = s->c[l] + (size_t)(u - 1) * cs;
-        pw.c_new = s->c[l] + (size_t)u * cs; pw.dc = s->dc[l]; pw.old = l < L - 1 ? s->dh[l] : nullptr;
-        pw.dG_out = (char*)s->dG[l] + (size_t)(u - 1) * dgs;
-        if (lo[l]) {                           // the classic layer below: its pointwise backward of time u rides on the x columns
-          const nint_layer* lb = &s->layer[l - 1];
-          const size_t cs_b = (size_t)B * comp_px * lb->Chp, Gc_b = 4 * (size_t)lb->Ch16;
-          pw.lo_gates = (const char*)s->gates[l - 1] + (size_t)u * B * comp_px * Gc_b * es;
-          pw.lo_c_prev = s->c[l - 1] + (size_t)u * cs_b; pw.lo_c_new = s->c[l - 1] + (size_t)(u + 1) * cs_b;
-          pw.lo_dc = s->dc[l - 1]; pw.lo_dG_out = (char*)s->dG[l - 1] + (size_t)u * B * halo_px * Gc_b * es;
-          pw.lo_Ch16 = lb->Ch16;
-          pw.lo_dc_zero = u == T - 1 && ((s->zero_dstate >> (2 * (l - 1))) & 1);
-          pw_done[l - 1] = u;
-        }
-        if (merge && pend.on && l == L - 1) {    // the top layer's step right behind the held-back bottom dgrad: one grid
-          ConvPlan pl[2];
-          pl[0] = pend.plan;
-          if (s->wave == 3) pw.tile_rows = 8;    // (experiment: the fused step on 8-row tiles inside the two-workgroups-per-CU grid)
-          rc = nint_internal_conv_dgrad(ly, g, s->dtype, B, (const char*)s->dG[l] + (size_t)u * dgs, dx_dst, nullptr, ow, &pw, stream, &pl[1]);
-          if (rc != NINT_OK) return rc;
-          rc = pl[1].gx > 0 ? nint_internal_conv_multi(pl, 2, s->dtype, stream, nullptr, true) : NINT_E_SHAPE;     // (dry run: is there such a grid?)
-          if (rc == NINT_OK) {
-            probe.stamp(NINT_PROBE_BWD_PAIR, l, u, 0);
-            rc = nint_internal_conv_multi(pl, 2, s->dtype, stream);
-            probe.stamp(NINT_PROBE_BWD_PAIR, l, u, 1);
-          }
-          if (rc == NINT_OK) { pend.on = false; continue; }
-          if (rc != NINT_E_SHAPE) return rc;
-        }
-        if (!merge_d) {
-          rc = flush();
-          if (rc != NINT_OK) return rc;
-        }
-        if (pend_pw.on) {                        // this fused step and the bottom layer's pointwise backward of the step before: one grid
-          ConvPlan pl;
-          PwArgs pa;
-          rc = nint_internal_conv_dgrad(ly, g, s->dtype, B, (const char*)s->dG[l] + (size_t)u * dgs, dx_dst, nullptr, ow, &pw, stream, &pl);
-          if (rc == NINT_OK) rc = p0_launch(pend_pw.t, &pa);
-          if (rc != NINT_OK) return rc;
-          rc = pl.gx > 0 ? nint_internal_conv_multi(&pl, 1, s->dtype, stream, &pa, true) : NINT_E_SHAPE;
-          if (rc == NINT_OK) {
-            probe.stamp(NINT_PROBE_BWD_PW, l, u, 0);
-            rc = nint_internal_conv_multi(&pl, 1, s->dtype, stream, &pa);
-            probe.stamp(NINT_PROBE_BWD_PW, l, u, 1);
-          }
-          if (rc == NINT_OK) { pend_pw.on = false; continue; }
-          if (rc != NINT_E_SHAPE) return rc;
-          rc = flush_pw();
-          if (rc != NINT_OK) return rc;
-        }
-        probe.stamp(NINT_PROBE_FUSED, l, u, 0);
-        rc = nint_internal_conv_dgrad(ly, g, s->dtype, B, (const char*)s->dG[l] + (size_t)u * dgs, dx_dst, nullptr, ow, &pw, stream);
-        probe.stamp(NINT_PROBE_FUSED, l, u, 1);
-      } else {
-        if (!merge_d) {
-          rc = flush();
-          if (rc != NINT_OK) return rc;
-        }
-        const bool nop = !dx_dst && !dh_prev;
-        if (!nop) probe.stamp(NINT_PROBE_DGRAD, l, 0, 0);
-        rc = nint_internal_conv_dgrad(ly, g, s->dtype, B, (const char*)s->dG[l], dx_dst, dh_prev, ow, nullptr, stream);
-        if (!nop) probe.stamp(NINT_PROBE_DGRAD, l, 0, 1);
-      }
-      if (rc != NINT_OK) return rc;
     }
+    flush_p(); flush_d();
+    return NINT_OK;
   }
-  rc = flush_pw();
+};
+
+// check, plan (the CU count the launch-shape rules read is looked up once per pass), then the callers execute
+static int plan_pass(const nint_seq* s, bool bwd, Steps& steps) {
+  const int rc = bwd ? bwd_check(s) : seq_check(s);
   if (rc != NINT_OK) return rc;
-  rc = flush();
+  const int n_cu = nint_internal_n_cu();
+  return bwd ? BwdPlanner(s, n_cu, steps).plan() : plan_fwd(s, n_cu, steps);
+}
+
+extern "C" int nint_seq_fwd(const nint_seq* s, void* stream) {
+  Steps steps;
+  const int rc = plan_pass(s, false, steps);
+  if (rc != NINT_OK) return rc;
+  Probe probe = make_probe(s, false, stream);
+  return run_steps(s, steps, probe, stream);
+}
+
+extern "C" int nint_seq_bwd(const nint_seq* s, void* stream) {
+  Steps steps;
+  int rc = plan_pass(s, true, steps);
+  if (rc != NINT_OK) return rc;
+  Probe probe = make_probe(s, true, stream);
+  rc = run_steps(s, steps, probe, stream);
   if (rc != NINT_OK) return rc;
   // weight / bias gradients: ONE reduction over all T time steps per layer and source, all layers' folds merged
+  const nint_geom* g = &s->g; const int B = s->B, L = s->L;
   WgJob jobs[NINT_MAX_LAYERS];
   for (int l = 0; l < L; ++l) {
     const nint_layer* ly = &s->layer[l];
-    const char* x_all = (l == 0) ? (const char*)s->xs
-                                 : (const char*)s->h[l - 1] + (size_t)B * halo_px * ly->Cxp * es;  // h^{l-1}_t = slab t+1
+    const char* x_all = (l == 0) ? (const char*)s->xs : (const char*)s->h[l - 1] + (size_t)B * g->Hh * g->Wh * ly->Cxp * esize(s->dtype);  // h^{l-1}_t = slab t+1
     // h_{-1} = 0 for a sequence from the zero state: the h part of the reduction skips time step 0
-    jobs[l] = WgJob{ly, s->T * B, s->dG[l], x_all, s->h[l] /* h_{t-1} = slab t */, s->dW[l], s->db[l],
-                    s->has_init_state ? 0 : B};
+    jobs[l] = WgJob{ly, s->T * B, s->dG[l], x_all, s->h[l] /* h_{t-1} = slab t */, s->dW[l], s->db[l], s->has_init_state ? 0 : B};
   }
   // (bwd_parts: layers >= 1 in the first call, layer 0 in the second; each call folds what it reduced)
   const int j0 = s->bwd_parts == 1 ? 1 : 0, j1 = s->bwd_parts == 2 ? 1 : L;
-  if (j1 > j0) {
-    rc = nint_internal_conv_wgrad_multi(jobs + j0, j1 - j0, g, s->dtype, s->wg_partial, s->wg_partial_bytes, s->n_cu, stream,
+  if (j1 <= j0) return NINT_OK;
+  return nint_internal_conv_wgrad_multi(jobs + j0, j1 - j0, g, s->dtype, s->wg_partial, s->wg_partial_bytes, s->n_cu, stream,
                                         probe.buf ? &probe : nullptr);
-    if (rc != NINT_OK) return rc;
+}
+
+// ------------------------------------------------------------------------------ the plan, for tests and tools
+extern "C" int nint_debug_seq_plan(const nint_seq* s, int bwd, nint_launch_rec* out, int cap) {
+  Steps steps;
+  const int rc = plan_pass(s, bwd != 0, steps);
+  if (rc != NINT_OK) return rc;
+  if (cap > 0 && !out) return NINT_E_ARG;
+  int n = 0;
+  for (size_t i = 0; i < steps.size(); ++i) {
+    const SeqStep& st = steps[i];
+    for (int q = 0; q < st.n; ++q, ++n) {
+      if (n >= cap) continue;
+      nint_launch_rec r = {};
+      r.index = (int)i; r.bwd = bwd ? 1 : 0; r.op = st.prob[q].op; r.layer = st.prob[q].layer; r.t = st.prob[q].t; r.dtype = s->dtype;
+      r.kernel = st.kind == STEP_CONV ? (int)NINT_K_CONV_IGEMM : st.kind == STEP_MULTI ? st.multi.carrier
+               : st.kind == STEP_PW ? (int)NINT_K_POINTWISE : st.gate.carrier;
+      const bool in_grid = st.kind == STEP_MULTI && q < st.multi.m.n;      // (else a merged grid's pointwise problem: no body)
+      if (st.kind == STEP_CONV || in_grid) {
+        const ConvArgs& a = in_grid ? st.multi.m.a[q] : st.conv.a;
+        const int v = in_grid ? st.multi.m.variant[q] : st.conv.variant;
+        r.epi = v / 10000; r.wn = v / 1000 % 10; r.wk = v / 100 % 10; r.ntw = v / 10 % 10; r.mt = 4 * (v % 10);    // (conv_variant)
+        r.strip = a.tiles_x2 > 0; r.nt_begin = a.nt_begin;
+        r.gx = in_grid ? st.multi.m.nbx[q] : st.conv.gx; r.gy = in_grid ? st.multi.m.nwg[q] / st.multi.m.nbx[q] : st.conv.gy;
+      }
+      out[n] = r;
+    }
   }
-  return NINT_OK;
+  return n;
 }

@@ -22,6 +22,11 @@ pass, the operation, the layer and time step, the host kernel that carries it (`
 the merged strip exists and the grid.  ``n_cu`` is an argument (256 on the MI355X), as are the engine's choices that the
 library reads from the workspace (``wave``, ``fuse_bwd``, ``tile_rows``, ``need_dx``); ``default_wave`` restates
 ``SeqEngine._set_wave``.
+
+The schedule half (``plan_fwd``, ``plan_bwd``, ``bwd_facts``, ``multi_kernel`` and the launch arithmetic they call) is checked against
+the library: ``nint_debug_seq_plan`` runs the drivers' own planner on the host, and
+``tests/test_launch_plan_cpu.py::test_ledger_equals_the_library_planner`` requires the two to agree record for record.  The two
+stay independent statements of the same thing: this module calls nothing in the library.
 """
 from __future__ import annotations
 

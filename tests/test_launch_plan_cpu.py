@@ -2,7 +2,12 @@
 launch_cfg, nint_internal_conv_dgrad, nint_internal_conv_multi) and csrc/seq.hip (nint_seq_fwd, nint_seq_bwd); the sweep of
 every layer shape the engine accepts, with a reason for each instantiated body it never selects; and the coverage of the GPU
 audit: the cases of tests/test_gpu_stored_audit.py and tests/test_gpu_launch_audit.py (their module-level tables, read without
-a GPU) together run every reachable body, every 8-row body also with the merged leftover strip, and every host kernel."""
+a GPU) together run every reachable body, every 8-row body also with the merged leftover strip, and every host kernel.
+
+The schedule half of the ledger (plan_fwd, plan_bwd, bwd_facts, multi_kernel and everything they call) is also checked against
+the library itself: nint_debug_seq_plan runs the drivers' own planner without a GPU, and its records must equal the ledger's,
+launch for launch, for every audit case and for the bench stack."""
+import ctypes as C
 import time
 
 import pytest
@@ -176,3 +181,84 @@ def test_bench_cases_reach_the_bench_kernels():
         assert any(x.kernel == "conv_dgrad_multi8" for x in ls)
         assert any(x.body[5] == 8 and x.strip for x in ls if x.op == "dgrad")
         assert all(x.body[5] == 8 and x.strip for x in ls if x.op == "gate")
+
+
+# ------------------------------------------------------------------------------ the ledger against the library's own planner
+EPIS = ("LSTM", "DGRAD", "DGRAD_PW")              # nint_launch_rec.epi
+OPS = ("gate", "dgrad", "fused", "pointwise")     # NINT_OP_*
+
+
+def _seq_of(C_, hidden, ks, B, T, H, W, dtype, wave=None, rows=0, fuse=None, has_init=False, zero=False, need_dx=True, train=True,
+            **_):
+    """nint_seq as SeqEngine fills it for one run_audit case, with made-up 4096-aligned addresses (the planner reads none)"""
+    from nasa_niswan_amd import _lib
+    lib = _lib.load()
+    lys = LP.layers_of(C_, hidden, ks, dtype)
+    L = len(lys)
+    s = _lib.NintSeq()
+    s.dtype, s.B, s.T, s.L = (_lib.NINT_BF16 if dtype == "bf16" else _lib.NINT_F32), B, T, L
+    s.need_dx, s.has_init_state, s.n_cu = int(need_dx), int(has_init), LP.N_CU
+    s.zero_dstate = (1 << (2 * L)) - 1 if zero else 0
+    assert lib.nint_geom_make(C.byref(s.g), H, W, max(k // 2 for k in ks)) == 0
+    addr = iter(range(1 << 20, 1 << 30, 1 << 20))
+    for l, ly in enumerate(lys):
+        n = s.layer[l]
+        n.Cx, n.Cxp, n.Ch, n.Ch16, n.Chp, n.k, n.xfold, n.tile_rows = ly.Cx, ly.Cxp, ly.Ch, ly.Ch16, ly.Chp, ly.k, int(ly.xfold), rows
+        n.Wf, n.Wd, n.bias_p = next(addr), next(addr), next(addr)
+        s.h[l], s.c[l] = next(addr), next(addr)
+        if train:
+            s.gates[l], s.dG[l], s.dh[l], s.dc[l], s.dW[l], s.db[l] = (next(addr) for _ in range(6))
+    s.xs, s.dx, s.wg_partial = next(addr), next(addr), next(addr)
+    s.wg_partial_bytes = 1 << 30                                    # room for the bottom layer's d/dh (merge_d)
+    s.fuse_bwd = 0 if fuse is None else fuse
+    wave = LP.default_wave(B, H, W, L) if wave is None else wave
+    s.wave = wave if L > 1 else 0
+    return s
+
+
+def _library_plan(s, train):
+    from nasa_niswan_amd import _lib
+    lib = _lib.load()
+    dt = "bf16" if s.dtype == _lib.NINT_BF16 else "f32"
+    out = []
+    for bwd in ((0, 1) if train else (0,)):
+        cap = 4 * (s.T + s.L + 1) * s.L
+        recs = (_lib.NintLaunchRec * cap)()
+        n = lib.nint_debug_seq_plan(C.byref(s), bwd, recs, cap)
+        assert 0 <= n <= cap, n
+        for r in recs[:n]:
+            assert r.bwd == bwd and r.dtype == s.dtype
+            body = (dt, EPIS[r.epi], r.wn, r.wk, r.ntw, r.mt) if r.mt else None
+            out.append((r.index, LP.Launch("bwd" if bwd else "fwd", OPS[r.op], r.layer, r.t, LP.CARRIERS[r.kernel], body, bool(r.strip),
+                                           (r.gx, r.gy) if body else None, r.nt_begin)))
+    return out
+
+
+def _conformance_cases():
+    cases = [(f"launch audit: {k}", v) for k, v in LA.CASES.items()]
+    cases += [(f"stored audit {i}: {sorted(c.items())}", c) for i, c in enumerate(SAT.ledger_cases())]
+    cases += [(f"bench B={B} need_dx={dx} {d}", dict(BENCH, B=B, dtype=d, need_dx=dx))
+              for B in (8, 2, 1) for dx in (False, True) for d in ("bf16", "f32")]
+    return cases
+
+
+@pytest.mark.parametrize("name,case", _conformance_cases(), ids=[n for n, _ in _conformance_cases()])
+def test_ledger_equals_the_library_planner(name, case):
+    kw = dict(case)
+    kw["C_"] = kw.pop("C")
+    s = _seq_of(**kw)
+    train = case.get("train", True)
+    got = _library_plan(s, train)
+    want = LP.plan(case["C"], case["hidden"], case["ks"], case["B"], case["T"], case["H"], case["W"], case["dtype"],
+                   wave=case.get("wave"), tile_rows=case.get("rows", 0), fuse_bwd=case.get("fuse") or 0,
+                   need_dx=case.get("need_dx", True), train=train, has_init=case.get("has_init", False))
+    assert len(got) == len(want), (len(got), len(want))
+    for i, ((_, g), w) in enumerate(zip(got, want)):
+        assert g == w, (i, g, w)
+    # problems share an enqueue index exactly where the ledger names a merged kernel for them
+    groups = {}
+    for idx, g in got:
+        groups.setdefault((g.pass_, idx), []).append(g)
+    for (pass_, idx), ps in groups.items():
+        merged = ps[0].kernel not in ("conv_igemm", "stencil", "tiny", "pointwise")
+        assert (len(ps) > 1) == merged and len({p.kernel for p in ps}) == 1, (pass_, idx, ps)
