@@ -310,7 +310,7 @@ int nint_loss_mse_l1_crop(const float* pred, const float* y, float* dpred, float
 /* Training fast path: head forward + crop + loss + d loss/d pred + head backward-data in ONE pass over the pixels
  * (train.py:96-109 around model.py:274); the same arithmetic in the same order as nint_head_fwd ->
  * nint_loss_mse_l1_crop -> nint_head_bwd(dh).  pred is not materialised; dpred (N,O,H,W) is written for
- * nint_head_bwd(dh = NULL) to form dw / db.  Chp <= 64, else NINT_E_SHAPE (use the three separate entries). */
+ * nint_head_bwd(dh = NULL) to form dw / db.  Chp <= 128, else NINT_E_SHAPE (use the three separate entries). */
 int nint_head_loss_fused(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w, const float* b,
                          const float* y, float* dpred, void* dh, float* loss_out, double* stats, const nint_geom* g,
                          int oy, int ox, int Hc, int Wc, int dtype, void* stream);
