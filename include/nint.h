@@ -151,6 +151,13 @@ typedef struct nint_seq {
    * but layer 0's slice of the gradient bucket, which then runs under layer 0's weight gradient -- the largest launches of the
    * step -- instead of after them.  Same launches, same order inside each layer: bit-identical gradients. */
   int32_t bwd_parts;
+  const void* dh_seq;   /* ET compact [T*B][H][W][Chp of layer L-1], image t*B+b: dL/dh_t of the TOP layer that does not come
+                         * through the recurrence (the per-step head outputs: nint_head_bwd_seq / nint_head_loss_seq_fused);
+                         * NULL = none (many-to-one: the only such term is dL/dh_{T-1}, in dh[L-1]).  Non-NULL: at every t the
+                         * top layer's d/dh_t is its recurrent part plus block t; at t = T-1 block T-1 is the only source and
+                         * dh[L-1] is not read on entry.  The addend enters through pointers the BPTT bodies already have (the
+                         * second d/dh piece of the pointwise backward, the `old` columns of the fused step), so the launch
+                         * plan is the one without it, merged grids included.  16-byte aligned, else NINT_E_ALIGN. */
 } nint_seq;
 
 /* launch kinds for nint_seq.probe_mask / the probe tags */
@@ -294,6 +301,20 @@ int nint_head_bwd(const void* h_slab, int n0, int N, int Ch, int Chp, int O, con
                   float* scratch, size_t scratch_bytes, void* stream);
 /* scratch (may be NULL): >= 256*O*(Ch+1) floats enables the tiled two-stage weight-gradient path. */
 
+/* The head over the WHOLE sequence (model.py:264,272,274 commented code, test.ipynb:273): the top layer's h slab holds h_t in
+ * slot t+1, image (t+1)*B + b; seq / dseq are (B, T*O, H, W) f32 contiguous with channel t*O + o (torch.cat of the per-step
+ * head outputs on the channel axis).  The (b, t) <-> image index math is done inside the kernels.
+ * nint_head_fwd_seq: one launch; per element the arithmetic of nint_head_fwd in the same order (= T calls of it, bit for bit). */
+int nint_head_fwd_seq(const void* h_slab, int B, int T, int Ch, int Chp, int O, const float* w, const float* b,
+                      float* seq, const nint_geom* g, int dtype, void* stream);
+/* dseq (B, T*O, H, W) and dpred_last (B, O, H, W: the cotangent of pred = head(h_{T-1}), added to step T-1 inside the
+ * kernels); either may be NULL, not both.  dh_seq: compact ET [T*B][H][W][Chp], image t*B+b, padding channels zero
+ * (nint_seq.dh_seq; may be NULL: not written); dw (O,Ch), db (O): summed over all T*B images in a fixed order (overwritten;
+ * both NULL: not computed).  scratch as in nint_head_bwd. */
+int nint_head_bwd_seq(const void* h_slab, int B, int T, int Ch, int Chp, int O, const float* w, const float* dseq,
+                      const float* dpred_last, void* dh_seq, float* dw, float* db, const nint_geom* g, int dtype,
+                      float* scratch, size_t scratch_bytes, void* stream);
+
 /* ---- loss (train.py:102,105) ------------------------------------------------------------------ */
 /* pred (N,O,H,W) f32, y (N,O,Hc,Wc) f32; crop window [oy,oy+Hc) x [ox,ox+Wc).
  * loss_out: NINT_LOSS_SCRATCH_FLOATS floats, 8-byte aligned; [0] = mean((y-p)^2) + mean(|y-p|), the
@@ -314,6 +335,15 @@ int nint_loss_mse_l1_crop(const float* pred, const float* y, float* dpred, float
 int nint_head_loss_fused(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w, const float* b,
                          const float* y, float* dpred, void* dh, float* loss_out, double* stats, const nint_geom* g,
                          int oy, int ox, int Hc, int Wc, int dtype, void* stream);
+
+/* The same over every time step: y (B, T, O, Hc, Wc) f32 (the index convention of seq, on the crop); the loss is
+ * mean((y-p)^2) + mean(|y-p|) over all B*T*O*Hc*Wc elements (= nint_loss_mse_l1_crop(seq, y, N = B, O' = T*O)), stats
+ * accumulate over all elements of the call.  dh_seq: compact ET [T*B][H][W][Chp], image t*B+b (nint_seq.dh_seq); dpred
+ * (T*B, O, H, W) f32, image t*B+b: what nint_head_bwd(h_slab, n0 = B, N = T*B, dh = NULL) reduces to dw / db.  Same limits
+ * as nint_head_loss_fused (NINT_E_SHAPE beyond: nint_head_fwd_seq + nint_loss_mse_l1_crop + nint_head_bwd_seq). */
+int nint_head_loss_seq_fused(const void* h_slab, int B, int T, int Ch, int Chp, int O, const float* w, const float* b,
+                             const float* y, float* dpred, void* dh_seq, float* loss_out, double* stats, const nint_geom* g,
+                             int oy, int ox, int Hc, int Wc, int dtype, void* stream);
 
 /* ---- optimiser (train.py:71,110) ---------------------------------------------------------------- */
 /* torch.optim.Adam (eps 1e-8, no weight decay / amsgrad) on one flat f32 buffer.

@@ -602,12 +602,19 @@ __device__ __forceinline__ void head_stage_weights(float* w_s, const float* __re
   __syncthreads();
 }
 
-template <int DT, int CHV>
-__global__ __launch_bounds__(256) void head_fwd_kernel(const void* __restrict__ h, int n0, int N, int Ch, int Chp, int O,
-                                                       const float* __restrict__ w, const float* __restrict__ b,
-                                                       float* __restrict__ pred, int H, int W, int P, int Hh, int Wh) {
-  extern __shared__ __attribute__((aligned(16))) char smem_hf[];
-  float* w_s = (float*)smem_hf;
+// The sequence entries (nint_head_fwd_seq and its kin) run the same bodies over all T*B images of the top layer's slab; only the
+// plane index of the (B, T*O, H, W) tensors differs: image n = t*B + b (time-major, as everywhere inside the library) owns the
+// O planes from (b*T + t)*O.  SEQ = false (Bs unused): plane block n, the (N, O, H, W) tensors of the one-step entries.
+template <bool SEQ>
+__device__ __forceinline__ size_t head_image(size_t n, int Bs, int T) {
+  if constexpr (SEQ) return (n % (size_t)Bs) * T + n / (size_t)Bs;
+  else return n;
+}
+
+template <int DT, int CHV, bool SEQ>
+__device__ __forceinline__ void head_fwd_body(float* w_s, const void* __restrict__ h, int n0, int N, int Ch, int Chp, int O,
+                                              const float* __restrict__ w, const float* __restrict__ b,
+                                              float* __restrict__ pred, int H, int W, int P, int Hh, int Wh, int Bs) {
   head_stage_weights<CHV>(w_s, w, O, Ch);
   const size_t npix = (size_t)N * H * W;
   const size_t pix = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
@@ -623,7 +630,7 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(const void* __restrict__ 
     const f32x4_t v = (c < Chp) ? load_vec4<DT>(h, hb + c) : (f32x4_t){0.f, 0.f, 0.f, 0.f};
     hv[c] = v[0]; hv[c + 1] = v[1]; hv[c + 2] = v[2]; hv[c + 3] = v[3];
   }
-  float* out = pred + ((size_t)n * O * H + y) * W + x;
+  float* out = pred + (head_image<SEQ>(n, Bs, N / (SEQ ? Bs : 1)) * O * H + y) * W + x;
   for (int o = 0; o < O; ++o) {
     float acc = b ? b[o] : 0.f;
     const f32x4_t* wr = (const f32x4_t*)(w_s + o * CHV);
@@ -636,11 +643,27 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(const void* __restrict__ 
   }
 }
 
+template <int DT, int CHV>
+__global__ __launch_bounds__(256) void head_fwd_kernel(const void* __restrict__ h, int n0, int N, int Ch, int Chp, int O,
+                                                       const float* __restrict__ w, const float* __restrict__ b,
+                                                       float* __restrict__ pred, int H, int W, int P, int Hh, int Wh) {
+  extern __shared__ __attribute__((aligned(16))) char smem_hf[];
+  head_fwd_body<DT, CHV, false>((float*)smem_hf, h, n0, N, Ch, Chp, O, w, b, pred, H, W, P, Hh, Wh, 0);
+}
+
+template <int DT, int CHV>
+__global__ __launch_bounds__(256) void head_fwd_seq_kernel(const void* __restrict__ h, int n0, int N, int Ch, int Chp, int O,
+                                                           const float* __restrict__ w, const float* __restrict__ b,
+                                                           float* __restrict__ seq, int H, int W, int P, int Hh, int Wh, int Bs) {
+  extern __shared__ __attribute__((aligned(16))) char smem_hfs[];
+  head_fwd_body<DT, CHV, true>((float*)smem_hfs, h, n0, N, Ch, Chp, O, w, b, seq, H, W, P, Hh, Wh, Bs);
+}
+
 // generic widths: one thread per output element
-template <int DT>
-__global__ void head_fwd_wide_kernel(const void* __restrict__ h, int n0, int N, int Ch, int Chp, int O,
-                                     const float* __restrict__ w, const float* __restrict__ b, float* __restrict__ pred,
-                                     int H, int W, int P, int Hh, int Wh) {
+template <int DT, bool SEQ>
+__device__ __forceinline__ void head_fwd_wide_body(const void* __restrict__ h, int n0, int N, int Ch, int Chp, int O,
+                                                   const float* __restrict__ w, const float* __restrict__ b, float* __restrict__ pred,
+                                                   int H, int W, int P, int Hh, int Wh, int Bs) {
   const size_t total = (size_t)N * O * H * W;
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
     const int x = i % W;
@@ -651,17 +674,47 @@ __global__ void head_fwd_wide_kernel(const void* __restrict__ h, int n0, int N, 
     const size_t hb = ((((size_t)(n0 + n)) * Hh + (y + P)) * Wh + (x + P)) * Chp;
     float acc = b ? b[o] : 0.f;
     for (int c = 0; c < Ch; ++c) acc += w[o * Ch + c] * load_elem<DT>(h, hb + c);
-    pred[i] = acc;
+    if constexpr (SEQ) pred[((head_image<true>(n, Bs, N / Bs) * O + o) * H + y) * W + x] = acc;
+    else pred[i] = acc;
   }
 }
 
+template <int DT>
+__global__ void head_fwd_wide_kernel(const void* __restrict__ h, int n0, int N, int Ch, int Chp, int O,
+                                     const float* __restrict__ w, const float* __restrict__ b, float* __restrict__ pred,
+                                     int H, int W, int P, int Hh, int Wh) {
+  head_fwd_wide_body<DT, false>(h, n0, N, Ch, Chp, O, w, b, pred, H, W, P, Hh, Wh, 0);
+}
+
+template <int DT>
+__global__ void head_fwd_wide_seq_kernel(const void* __restrict__ h, int n0, int N, int Ch, int Chp, int O,
+                                         const float* __restrict__ w, const float* __restrict__ b, float* __restrict__ seq,
+                                         int H, int W, int P, int Hh, int Wh, int Bs) {
+  head_fwd_wide_body<DT, true>(h, n0, N, Ch, Chp, O, w, b, seq, H, W, P, Hh, Wh, Bs);
+}
+
+// d loss / d (head output) of image n (time-major), output o, pixel yx, for the backward kernels below.  DpPlain: the (N, O, H, W)
+// tensor of the one-step entries.  DpSeq: dseq (B, T*O, H, W) and / or the cotangent of pred = head(h_{T-1}) (B, O, H, W), which
+// joins step T-1 here; either may be nullptr.
+struct DpPlain {
+  const float* __restrict__ p; int O; size_t HW;
+  __device__ __forceinline__ float operator()(size_t n, int o, size_t yx) const { return p[(n * O + o) * HW + yx]; }
+};
+struct DpSeq {
+  const float* __restrict__ dseq; const float* __restrict__ dlast; int O, B, T; size_t HW;
+  __device__ __forceinline__ float operator()(size_t n, int o, size_t yx) const {
+    const size_t t = n / (size_t)B, b = n - t * B;
+    float d = dseq ? dseq[((b * T + t) * O + o) * HW + yx] : 0.f;
+    if (dlast && t == (size_t)(T - 1)) d += dlast[(b * O + o) * HW + yx];
+    return d;
+  }
+};
+
 // dh[n][y][x][c] = sum_o w[o][c] * dpred[n][o][y][x].  One thread per pixel (dpred planes read coalesced
 // along x, weights wave-uniform), the padded channel vector is written with 16-byte stores.
-template <int DT, int CHV>
-__global__ __launch_bounds__(256) void head_bwd_dh_kernel(const float* __restrict__ w, const float* __restrict__ dpred,
-                                                          void* __restrict__ dh, int N, int Ch, int Chp, int O, int H, int W) {
-  extern __shared__ __attribute__((aligned(16))) char smem_hd[];
-  float* w_s = (float*)smem_hd;
+template <int DT, int CHV, class Dp>
+__device__ __forceinline__ void head_bwd_dh_body(float* w_s, const float* __restrict__ w, const Dp dpred,
+                                                 void* __restrict__ dh, int N, int Ch, int Chp, int O, int H, int W) {
   head_stage_weights<CHV>(w_s, w, O, Ch);
   const size_t npix = (size_t)N * H * W;
   const size_t pix = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
@@ -671,9 +724,8 @@ __global__ __launch_bounds__(256) void head_bwd_dh_kernel(const float* __restric
   float acc[CHV];
 #pragma unroll
   for (int c = 0; c < CHV; ++c) acc[c] = 0.f;
-  const float* dp = dpred + n * O * (size_t)H * W + yx;
   for (int o = 0; o < O; ++o) {
-    const float d = dp[(size_t)o * H * W];
+    const float d = dpred(n, o, yx);
     const f32x4_t* wr = (const f32x4_t*)(w_s + o * CHV);
 #pragma unroll
     for (int c = 0; c < CHV; c += 4) {
@@ -686,9 +738,23 @@ __global__ __launch_bounds__(256) void head_bwd_dh_kernel(const float* __restric
     if (c < Chp) store_vec4<DT>(dh, pix * Chp + c, (f32x4_t){acc[c], acc[c + 1], acc[c + 2], acc[c + 3]});
 }
 
-template <int DT>
-__global__ void head_bwd_dh_wide_kernel(const float* __restrict__ w, const float* __restrict__ dpred, void* __restrict__ dh,
-                                        int N, int Ch, int Chp, int O, int H, int W) {
+template <int DT, int CHV>
+__global__ __launch_bounds__(256) void head_bwd_dh_kernel(const float* __restrict__ w, const float* __restrict__ dpred,
+                                                          void* __restrict__ dh, int N, int Ch, int Chp, int O, int H, int W) {
+  extern __shared__ __attribute__((aligned(16))) char smem_hd[];
+  head_bwd_dh_body<DT, CHV>((float*)smem_hd, w, DpPlain{dpred, O, (size_t)H * W}, dh, N, Ch, Chp, O, H, W);
+}
+
+template <int DT, int CHV>
+__global__ __launch_bounds__(256) void head_bwd_dh_seq_kernel(const float* __restrict__ w, DpSeq dpred, void* __restrict__ dh,
+                                                              int N, int Ch, int Chp, int O, int H, int W) {
+  extern __shared__ __attribute__((aligned(16))) char smem_hds[];
+  head_bwd_dh_body<DT, CHV>((float*)smem_hds, w, dpred, dh, N, Ch, Chp, O, H, W);
+}
+
+template <int DT, class Dp>
+__device__ __forceinline__ void head_bwd_dh_wide_body(const float* __restrict__ w, const Dp dpred, void* __restrict__ dh,
+                                                      int N, int Ch, int Chp, int O, int H, int W) {
   const size_t total = (size_t)N * H * W * Chp;
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
     const int c = i % Chp;
@@ -697,18 +763,30 @@ __global__ void head_bwd_dh_wide_kernel(const float* __restrict__ w, const float
     const int n = pix / ((size_t)H * W);
     float acc = 0.f;
     if (c < Ch)
-      for (int o = 0; o < O; ++o) acc += w[o * Ch + c] * dpred[((size_t)n * O + o) * H * W + yx];
+      for (int o = 0; o < O; ++o) acc += w[o * Ch + c] * dpred((size_t)n, o, yx);
     store_elem<DT>(dh, i, acc);
   }
 }
 
+template <int DT>
+__global__ void head_bwd_dh_wide_kernel(const float* __restrict__ w, const float* __restrict__ dpred, void* __restrict__ dh,
+                                        int N, int Ch, int Chp, int O, int H, int W) {
+  head_bwd_dh_wide_body<DT>(w, DpPlain{dpred, O, (size_t)H * W}, dh, N, Ch, Chp, O, H, W);
+}
+
+template <int DT>
+__global__ void head_bwd_dh_wide_seq_kernel(const float* __restrict__ w, DpSeq dpred, void* __restrict__ dh,
+                                            int N, int Ch, int Chp, int O, int H, int W) {
+  head_bwd_dh_wide_body<DT>(w, dpred, dh, N, Ch, Chp, O, H, W);
+}
+
 // dw[o][c] = sum_pixels dpred*h ; db[o] = sum dpred.  One workgroup per (o, c-or-bias) output,
 // fixed-order tree reduction -> bitwise reproducible.
-template <int DT>
-__global__ __launch_bounds__(256) void head_bwd_dw_kernel(const void* __restrict__ h, int n0, int N, int Ch, int Chp,
-                                                          int O, const float* __restrict__ dpred,
-                                                          float* __restrict__ dw, float* __restrict__ db, int H, int W,
-                                                          int P, int Hh, int Wh) {
+template <int DT, class Dp>
+__device__ __forceinline__ void head_bwd_dw_body(const void* __restrict__ h, int n0, int N, int Ch, int Chp,
+                                                 int O, const Dp dpred,
+                                                 float* __restrict__ dw, float* __restrict__ db, int H, int W,
+                                                 int P, int Hh, int Wh) {
   const int o = blockIdx.x / (Ch + 1);
   const int c = blockIdx.x % (Ch + 1);   // c == Ch -> bias
   const size_t npix = (size_t)N * H * W;
@@ -718,7 +796,7 @@ __global__ __launch_bounds__(256) void head_bwd_dw_kernel(const void* __restrict
     size_t r = i / W;
     const int y = r % H;
     const int n = r / H;
-    const float d = dpred[(((size_t)n * O + o) * H + y) * W + x];
+    const float d = dpred((size_t)n, o, (size_t)y * W + x);
     if (c < Ch) {
       const size_t hb = ((((size_t)(n0 + n)) * Hh + (y + P)) * Wh + (x + P)) * Chp + c;
       acc += d * load_elem<DT>(h, hb);
@@ -739,6 +817,21 @@ __global__ __launch_bounds__(256) void head_bwd_dw_kernel(const void* __restrict
   }
 }
 
+template <int DT>
+__global__ __launch_bounds__(256) void head_bwd_dw_kernel(const void* __restrict__ h, int n0, int N, int Ch, int Chp,
+                                                          int O, const float* __restrict__ dpred,
+                                                          float* __restrict__ dw, float* __restrict__ db, int H, int W,
+                                                          int P, int Hh, int Wh) {
+  head_bwd_dw_body<DT>(h, n0, N, Ch, Chp, O, DpPlain{dpred, O, (size_t)H * W}, dw, db, H, W, P, Hh, Wh);
+}
+
+template <int DT>
+__global__ __launch_bounds__(256) void head_bwd_dw_seq_kernel(const void* __restrict__ h, int n0, int N, int Ch, int Chp,
+                                                              int O, DpSeq dpred, float* __restrict__ dw, float* __restrict__ db,
+                                                              int H, int W, int P, int Hh, int Wh) {
+  head_bwd_dw_body<DT>(h, n0, N, Ch, Chp, O, dpred, dw, db, H, W, P, Hh, Wh);
+}
+
 // Tiled path (O*(Ch+1) <= HEAD_DW_NK*512 outputs): every workgroup owns a pixel range, stages `stage` pixels of dpred and
 // h in LDS at a time (ONE HBM round trip per stage: the launch is latency-bound, 14 MB in all for the bench's head), thread
 // i accumulates the outputs i, i+512, ... over the range; per-workgroup partials are folded in fixed order by
@@ -748,12 +841,11 @@ __global__ __launch_bounds__(256) void head_bwd_dw_kernel(const void* __restrict
 #define HEAD_DW_PIX 240
 #define HEAD_DW_NK 8
 #define HEAD_DW_LDS_FLOATS (15 * 1024)
-template <int DT>
-__global__ __launch_bounds__(512) void head_bwd_dw_tiled_kernel(const void* __restrict__ h, int n0, int N, int Ch, int Chp,
-                                                              int O, const float* __restrict__ dpred,
-                                                              float* __restrict__ partial, int H, int W, int P, int Hh,
-                                                              int Wh, int stage) {
-  extern __shared__ __attribute__((aligned(16))) float smem_dw[];
+template <int DT, class Dp>
+__device__ __forceinline__ void head_bwd_dw_tiled_body(float* smem_dw, const void* __restrict__ h, int n0, int N, int Ch, int Chp,
+                                                       int O, const Dp dpred,
+                                                       float* __restrict__ partial, int H, int W, int P, int Hh,
+                                                       int Wh, int stage) {
   const int SO = O | 1, SC = (Ch + 1) | 1;     // odd row strides: the staging writes walk pixels without bank conflicts
   float* sd = smem_dw;                         // [pixel][o]
   float* sh = smem_dw + stage * SO;            // [pixel][c] + a constant 1 for the bias column
@@ -778,7 +870,7 @@ __global__ __launch_bounds__(512) void head_bwd_dw_tiled_kernel(const void* __re
       const size_t pix = base + pp;
       const size_t yx = pix % ((size_t)H * W);
       const size_t n = pix / ((size_t)H * W);
-      sd[pp * SO + oo] = dpred[(n * O + oo) * (size_t)H * W + yx];
+      sd[pp * SO + oo] = dpred(n, oo, yx);
     }
     for (int i = threadIdx.x; i < cnt * nq; i += 512) {       // h: one 4-channel vector per thread
       const int pp = i / nq, q = i - pp * nq;
@@ -812,17 +904,33 @@ __global__ __launch_bounds__(512) void head_bwd_dw_tiled_kernel(const void* __re
     if ((int)threadIdx.x + 512 * k < nout) partial[(size_t)blockIdx.x * nout + threadIdx.x + 512 * k] = acc[k];
 }
 
+template <int DT>
+__global__ __launch_bounds__(512) void head_bwd_dw_tiled_kernel(const void* __restrict__ h, int n0, int N, int Ch, int Chp,
+                                                              int O, const float* __restrict__ dpred,
+                                                              float* __restrict__ partial, int H, int W, int P, int Hh,
+                                                              int Wh, int stage) {
+  extern __shared__ __attribute__((aligned(16))) float smem_dw[];
+  head_bwd_dw_tiled_body<DT>(smem_dw, h, n0, N, Ch, Chp, O, DpPlain{dpred, O, (size_t)H * W}, partial, H, W, P, Hh, Wh, stage);
+}
+
+template <int DT>
+__global__ __launch_bounds__(512) void head_bwd_dw_tiled_seq_kernel(const void* __restrict__ h, int n0, int N, int Ch, int Chp,
+                                                                  int O, DpSeq dpred, float* __restrict__ partial, int H, int W,
+                                                                  int P, int Hh, int Wh, int stage) {
+  extern __shared__ __attribute__((aligned(16))) float smem_dw[];
+  head_bwd_dw_tiled_body<DT>(smem_dw, h, n0, N, Ch, Chp, O, dpred, partial, H, W, P, Hh, Wh, stage);
+}
+
 // Larger heads (more than 512 outputs, and the smaller of O and Ch + 1 at most 32 -- 200 outputs x 16 channels, or 20 x
 // 128): REGISTER-tiled.  The smaller dimension ("R") lives in registers, a thread owns one index of the larger one ("T")
 // and NH = 512 / T pixel strides: per staged pixel it reads its own T value once and the R values as broadcast 16-byte reads
 // -- 1 + R/4 LDS instructions per R FMAs instead of 2 per FMA.  The NH partial sums of an output are folded through LDS in
 // fixed order; the slab layout is head_bwd_dw_tiled_kernel's.
-template <int DT>
-__global__ __launch_bounds__(512) void head_bwd_dw_rtile_kernel(const void* __restrict__ h, int n0, int N, int Ch, int Chp,
-                                                              int O, const float* __restrict__ dpred,
-                                                              float* __restrict__ partial, int H, int W, int P, int Hh,
-                                                              int Wh, int stage) {
-  extern __shared__ __attribute__((aligned(16))) float smem_dw[];
+template <int DT, class Dp>
+__device__ __forceinline__ void head_bwd_dw_rtile_body(float* smem_dw, const void* __restrict__ h, int n0, int N, int Ch, int Chp,
+                                                       int O, const Dp dpred,
+                                                       float* __restrict__ partial, int H, int W, int P, int Hh,
+                                                       int Wh, int stage) {
   const int C1 = Ch + 1;
   const bool r_is_c = C1 <= O;                 // registers over the channels (+ bias), threads over the outputs -- or the other way round
   const int R = r_is_c ? C1 : O, T = r_is_c ? O : C1;
@@ -851,7 +959,7 @@ __global__ __launch_bounds__(512) void head_bwd_dw_rtile_kernel(const void* __re
       const size_t pix = base + pp;
       const size_t yx = pix % ((size_t)H * W);
       const size_t n = pix / ((size_t)H * W);
-      sd[pp * SD + oo] = dpred[(n * O + oo) * (size_t)H * W + yx];
+      sd[pp * SD + oo] = dpred(n, oo, yx);
     }
     for (int i = threadIdx.x; i < cnt * nq; i += 512) {       // h: one 4-channel vector per thread
       const int pp = i / nq, q = i - pp * nq;
@@ -901,6 +1009,23 @@ __global__ __launch_bounds__(512) void head_bwd_dw_rtile_kernel(const void* __re
   }
 }
 
+template <int DT>
+__global__ __launch_bounds__(512) void head_bwd_dw_rtile_kernel(const void* __restrict__ h, int n0, int N, int Ch, int Chp,
+                                                              int O, const float* __restrict__ dpred,
+                                                              float* __restrict__ partial, int H, int W, int P, int Hh,
+                                                              int Wh, int stage) {
+  extern __shared__ __attribute__((aligned(16))) float smem_dw[];
+  head_bwd_dw_rtile_body<DT>(smem_dw, h, n0, N, Ch, Chp, O, DpPlain{dpred, O, (size_t)H * W}, partial, H, W, P, Hh, Wh, stage);
+}
+
+template <int DT>
+__global__ __launch_bounds__(512) void head_bwd_dw_rtile_seq_kernel(const void* __restrict__ h, int n0, int N, int Ch, int Chp,
+                                                                  int O, DpSeq dpred, float* __restrict__ partial, int H, int W,
+                                                                  int P, int Hh, int Wh, int stage) {
+  extern __shared__ __attribute__((aligned(16))) float smem_dw[];
+  head_bwd_dw_rtile_body<DT>(smem_dw, h, n0, N, Ch, Chp, O, dpred, partial, H, W, P, Hh, Wh, stage);
+}
+
 // block = 64 outputs x blockDim/64 lanes over the per-workgroup partials; fixed order
 __global__ void head_bwd_dw_final_kernel(const float* __restrict__ partial, int nblocks, int Ch, int O,
                                          float* __restrict__ dw, float* __restrict__ db) {
@@ -921,59 +1046,90 @@ __global__ void head_bwd_dw_final_kernel(const float* __restrict__ partial, int 
   else db[o] = s;
 }
 
-extern "C" int nint_head_fwd(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w,
-                             const float* b, float* pred, const nint_geom* g, int dtype, void* stream) {
-  if (!h_slab || !w || !pred || !g || N <= 0 || O <= 0 || Ch <= 0) return NINT_E_ARG;
-  if (dtype != NINT_BF16 && dtype != NINT_F32) return NINT_E_ARG;
+// sq != nullptr: the sequence entry (n0 = B, N = T*B, plane blocks b*T + t)
+static int head_fwd_impl(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w, const float* b, float* pred,
+                         const nint_geom* g, int dtype, int Bs, void* stream) {
   const size_t total = (size_t)N * O * g->H * g->W, npix = (size_t)N * g->H * g->W;
   hipStream_t st = (hipStream_t)stream;
   const dim3 gp((unsigned)((npix + 255) / 256));
   const size_t w_lds = (size_t)O * (Chp <= 32 ? 32 : (Chp <= 64 ? 64 : 128)) * sizeof(float);      // staged weights [O][CHV]
   if (Chp <= 128 && Chp % 4 == 0 && w_lds <= 64 * 1024) {
-#define NINT_HF(DT_, CHV_) hipLaunchKernelGGL((head_fwd_kernel<DT_, CHV_>), gp, dim3(256), w_lds, st, h_slab, n0, N, Ch, Chp, O, w, b, pred, g->H, g->W, g->P, g->Hh, g->Wh)
-    if (dtype == NINT_BF16) { if (Chp <= 32) NINT_HF(NINT_BF16, 32); else if (Chp <= 64) NINT_HF(NINT_BF16, 64); else NINT_HF(NINT_BF16, 128); }
-    else { if (Chp <= 32) NINT_HF(NINT_F32, 32); else if (Chp <= 64) NINT_HF(NINT_F32, 64); else NINT_HF(NINT_F32, 128); }
+#define NINT_HF(DT_, CHV_) { if (Bs) hipLaunchKernelGGL((head_fwd_seq_kernel<DT_, CHV_>), gp, dim3(256), w_lds, st, h_slab, n0, N, Ch, Chp, O, w, b, pred, g->H, g->W, g->P, g->Hh, g->Wh, Bs); \
+                             else hipLaunchKernelGGL((head_fwd_kernel<DT_, CHV_>), gp, dim3(256), w_lds, st, h_slab, n0, N, Ch, Chp, O, w, b, pred, g->H, g->W, g->P, g->Hh, g->Wh); }
+    if (dtype == NINT_BF16) { if (Chp <= 32) NINT_HF(NINT_BF16, 32) else if (Chp <= 64) NINT_HF(NINT_BF16, 64) else NINT_HF(NINT_BF16, 128) }
+    else { if (Chp <= 32) NINT_HF(NINT_F32, 32) else if (Chp <= 64) NINT_HF(NINT_F32, 64) else NINT_HF(NINT_F32, 128) }
 #undef NINT_HF
   } else if (dtype == NINT_BF16) {
-    hipLaunchKernelGGL(head_fwd_wide_kernel<NINT_BF16>, grid1d(total), dim3(256), 0, st, h_slab, n0, N, Ch, Chp, O, w, b, pred, g->H, g->W, g->P, g->Hh, g->Wh);
+    if (Bs) hipLaunchKernelGGL(head_fwd_wide_seq_kernel<NINT_BF16>, grid1d(total), dim3(256), 0, st, h_slab, n0, N, Ch, Chp, O, w, b, pred, g->H, g->W, g->P, g->Hh, g->Wh, Bs);
+    else hipLaunchKernelGGL(head_fwd_wide_kernel<NINT_BF16>, grid1d(total), dim3(256), 0, st, h_slab, n0, N, Ch, Chp, O, w, b, pred, g->H, g->W, g->P, g->Hh, g->Wh);
   } else {
-    hipLaunchKernelGGL(head_fwd_wide_kernel<NINT_F32>, grid1d(total), dim3(256), 0, st, h_slab, n0, N, Ch, Chp, O, w, b, pred, g->H, g->W, g->P, g->Hh, g->Wh);
+    if (Bs) hipLaunchKernelGGL(head_fwd_wide_seq_kernel<NINT_F32>, grid1d(total), dim3(256), 0, st, h_slab, n0, N, Ch, Chp, O, w, b, pred, g->H, g->W, g->P, g->Hh, g->Wh, Bs);
+    else hipLaunchKernelGGL(head_fwd_wide_kernel<NINT_F32>, grid1d(total), dim3(256), 0, st, h_slab, n0, N, Ch, Chp, O, w, b, pred, g->H, g->W, g->P, g->Hh, g->Wh);
   }
   NINT_LAUNCH_CHECK();
   return NINT_OK;
 }
 
-extern "C" int nint_head_bwd(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w,
-                             const float* dpred, void* dh, float* dw, float* db, const nint_geom* g, int dtype,
-                             float* scratch, size_t scratch_bytes, void* stream) {
-  if (!h_slab || !w || !dpred || !g || N <= 0 || O <= 0 || Ch <= 0) return NINT_E_ARG;
+extern "C" int nint_head_fwd(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w,
+                             const float* b, float* pred, const nint_geom* g, int dtype, void* stream) {
+  if (!h_slab || !w || !pred || !g || N <= 0 || O <= 0 || Ch <= 0) return NINT_E_ARG;
   if (dtype != NINT_BF16 && dtype != NINT_F32) return NINT_E_ARG;
+  return head_fwd_impl(h_slab, n0, N, Ch, Chp, O, w, b, pred, g, dtype, 0, stream);
+}
+
+// channel padding of a slab the head reads: KC of the storage type (nint.h), so every 16-byte channel vector stays inside
+static bool head_seq_args_ok(const void* h_slab, int B, int T, int Ch, int Chp, int O, const float* w, const nint_geom* g, int dtype) {
+  if (!h_slab || !w || !g || B <= 0 || T <= 0 || O <= 0 || Ch <= 0 || Chp < Ch) return false;
+  if (dtype != NINT_BF16 && dtype != NINT_F32) return false;
+  if (g->H <= 0 || g->W <= 0 || g->P < 0 || g->Hh < g->H + 2 * g->P || g->Wh < g->W + 2 * g->P) return false;
+  return Chp % (dtype == NINT_BF16 ? 32 : 16) == 0;
+}
+
+extern "C" int nint_head_fwd_seq(const void* h_slab, int B, int T, int Ch, int Chp, int O, const float* w, const float* b,
+                                 float* seq, const nint_geom* g, int dtype, void* stream) {
+  if (!seq || !head_seq_args_ok(h_slab, B, T, Ch, Chp, O, w, g, dtype)) return NINT_E_ARG;
+  if ((((uintptr_t)h_slab) & 15) != 0) return NINT_E_ALIGN;
+  return head_fwd_impl(h_slab, B, T * B, Ch, Chp, O, w, b, seq, g, dtype, B, stream);     // h_t = slot t + 1: images from B
+}
+
+// sq != nullptr: d loss / d (head output) comes from the sequence tensors (DpSeq) instead of dpred
+static int head_bwd_impl(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w,
+                         const float* dpred, const DpSeq* sq, void* dh, float* dw, float* db, const nint_geom* g, int dtype,
+                         float* scratch, size_t scratch_bytes, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   const size_t npix = (size_t)N * g->H * g->W;
+  const bool b16 = dtype == NINT_BF16;
   if (dh) {
     const dim3 gp((unsigned)((npix + 255) / 256));
-    const bool b16 = dtype == NINT_BF16;
     const size_t w_lds = (size_t)O * (Chp <= 32 ? 32 : (Chp <= 64 ? 64 : 128)) * sizeof(float);    // staged weights [O][CHV]
-#define NINT_HD(DT_, CHV_) hipLaunchKernelGGL((head_bwd_dh_kernel<DT_, CHV_>), gp, dim3(256), w_lds, st, w, dpred, dh, N, Ch, Chp, O, g->H, g->W)
+#define NINT_HD(DT_, CHV_) { if (sq) hipLaunchKernelGGL((head_bwd_dh_seq_kernel<DT_, CHV_>), gp, dim3(256), w_lds, st, w, *sq, dh, N, Ch, Chp, O, g->H, g->W); \
+                             else hipLaunchKernelGGL((head_bwd_dh_kernel<DT_, CHV_>), gp, dim3(256), w_lds, st, w, dpred, dh, N, Ch, Chp, O, g->H, g->W); }
+#define NINT_HDW(DT_) { if (sq) hipLaunchKernelGGL(head_bwd_dh_wide_seq_kernel<DT_>, grid1d(npix * Chp), dim3(256), 0, st, w, *sq, dh, N, Ch, Chp, O, g->H, g->W); \
+                        else hipLaunchKernelGGL(head_bwd_dh_wide_kernel<DT_>, grid1d(npix * Chp), dim3(256), 0, st, w, dpred, dh, N, Ch, Chp, O, g->H, g->W); }
     if (w_lds > 64 * 1024) {
-      if (b16) hipLaunchKernelGGL(head_bwd_dh_wide_kernel<NINT_BF16>, grid1d(npix * Chp), dim3(256), 0, st, w, dpred, dh, N, Ch, Chp, O, g->H, g->W);
-      else hipLaunchKernelGGL(head_bwd_dh_wide_kernel<NINT_F32>, grid1d(npix * Chp), dim3(256), 0, st, w, dpred, dh, N, Ch, Chp, O, g->H, g->W);
+      if (b16) NINT_HDW(NINT_BF16) else NINT_HDW(NINT_F32)
     } else if (Chp <= 32 && Chp % 4 == 0) {
-      if (b16) NINT_HD(NINT_BF16, 32); else NINT_HD(NINT_F32, 32);
+      if (b16) NINT_HD(NINT_BF16, 32) else NINT_HD(NINT_F32, 32)
     } else if (Chp <= 64 && Chp % 4 == 0) {
-      if (b16) NINT_HD(NINT_BF16, 64); else NINT_HD(NINT_F32, 64);
+      if (b16) NINT_HD(NINT_BF16, 64) else NINT_HD(NINT_F32, 64)
     } else if (Chp <= 128 && Chp % 4 == 0) {
-      if (b16) NINT_HD(NINT_BF16, 128); else NINT_HD(NINT_F32, 128);
-#undef NINT_HD
+      if (b16) NINT_HD(NINT_BF16, 128) else NINT_HD(NINT_F32, 128)
     } else {
-      if (b16) hipLaunchKernelGGL(head_bwd_dh_wide_kernel<NINT_BF16>, grid1d(npix * Chp), dim3(256), 0, st, w, dpred, dh, N, Ch, Chp, O, g->H, g->W);
-      else hipLaunchKernelGGL(head_bwd_dh_wide_kernel<NINT_F32>, grid1d(npix * Chp), dim3(256), 0, st, w, dpred, dh, N, Ch, Chp, O, g->H, g->W);
+      if (b16) NINT_HDW(NINT_BF16) else NINT_HDW(NINT_F32)
     }
+#undef NINT_HD
+#undef NINT_HDW
     NINT_LAUNCH_CHECK();
   }
   const int nout = O * (Ch + 1);
   const int row_floats = (O | 1) + ((Ch + 1) | 1);
   const int Rd = O < Ch + 1 ? O : Ch + 1, Td = O < Ch + 1 ? Ch + 1 : O;      // register / thread dimension of the register-tiled kernel
+  // the two-stage kernels: KERN_ for the one-step entry, KERN_##seq for the sequence one
+#define NINT_DW2(PLAIN_, SEQ_, NBLK_, LDS_, STAGE_) {                                                                                            \
+    if (sq) { if (b16) hipLaunchKernelGGL(SEQ_<NINT_BF16>, dim3(NBLK_), dim3(512), LDS_, st, h_slab, n0, N, Ch, Chp, O, *sq, scratch, g->H, g->W, g->P, g->Hh, g->Wh, STAGE_);  \
+              else hipLaunchKernelGGL(SEQ_<NINT_F32>, dim3(NBLK_), dim3(512), LDS_, st, h_slab, n0, N, Ch, Chp, O, *sq, scratch, g->H, g->W, g->P, g->Hh, g->Wh, STAGE_); }      \
+    else { if (b16) hipLaunchKernelGGL(PLAIN_<NINT_BF16>, dim3(NBLK_), dim3(512), LDS_, st, h_slab, n0, N, Ch, Chp, O, dpred, scratch, g->H, g->W, g->P, g->Hh, g->Wh, STAGE_); \
+           else hipLaunchKernelGGL(PLAIN_<NINT_F32>, dim3(NBLK_), dim3(512), LDS_, st, h_slab, n0, N, Ch, Chp, O, dpred, scratch, g->H, g->W, g->P, g->Hh, g->Wh, STAGE_); } }
   if (dw && db && scratch && nout > 512 && Rd <= 32 && Td <= 512 && scratch_bytes >= (size_t)256 * nout * sizeof(float)) {
     const int SR = (Rd + 3) & ~3, ST = Td | 1, NH = 512 / Td < 8 ? 512 / Td : 8;
     int stage = HEAD_DW_LDS_FLOATS / (SR + ST);
@@ -985,10 +1141,7 @@ extern "C" int nint_head_bwd(const void* h_slab, int n0, int N, int Ch, int Chp,
       const size_t cap = scratch_bytes / ((size_t)nout * sizeof(float));
       const size_t want = (npix + HEAD_DW_PIX - 1) / HEAD_DW_PIX;
       const int nblk = (int)(want < cap ? want : cap);
-      if (dtype == NINT_BF16)
-        hipLaunchKernelGGL(head_bwd_dw_rtile_kernel<NINT_BF16>, dim3(nblk), dim3(512), lds, st, h_slab, n0, N, Ch, Chp, O, dpred, scratch, g->H, g->W, g->P, g->Hh, g->Wh, stage);
-      else
-        hipLaunchKernelGGL(head_bwd_dw_rtile_kernel<NINT_F32>, dim3(nblk), dim3(512), lds, st, h_slab, n0, N, Ch, Chp, O, dpred, scratch, g->H, g->W, g->P, g->Hh, g->Wh, stage);
+      NINT_DW2(head_bwd_dw_rtile_kernel, head_bwd_dw_rtile_seq_kernel, nblk, lds, stage)
       NINT_LAUNCH_CHECK();
       hipLaunchKernelGGL(head_bwd_dw_final_kernel, dim3(nint_cdiv(nout, 64)), dim3(1024), 0, st, scratch, nblk, Ch, O, dw, db);
       NINT_LAUNCH_CHECK();
@@ -1003,23 +1156,41 @@ extern "C" int nint_head_bwd(const void* h_slab, int n0, int N, int Ch, int Chp,
     const size_t cap = scratch_bytes / ((size_t)nout * sizeof(float));
     const size_t want = (npix + HEAD_DW_PIX - 1) / HEAD_DW_PIX;
     const int nblk = (int)(want < cap ? want : cap);
-    if (dtype == NINT_BF16)
-      hipLaunchKernelGGL(head_bwd_dw_tiled_kernel<NINT_BF16>, dim3(nblk), dim3(512), lds, st, h_slab, n0, N, Ch, Chp, O, dpred, scratch, g->H, g->W, g->P, g->Hh, g->Wh, stage);
-    else
-      hipLaunchKernelGGL(head_bwd_dw_tiled_kernel<NINT_F32>, dim3(nblk), dim3(512), lds, st, h_slab, n0, N, Ch, Chp, O, dpred, scratch, g->H, g->W, g->P, g->Hh, g->Wh, stage);
+    NINT_DW2(head_bwd_dw_tiled_kernel, head_bwd_dw_tiled_seq_kernel, nblk, lds, stage)
     NINT_LAUNCH_CHECK();
     hipLaunchKernelGGL(head_bwd_dw_final_kernel, dim3(nint_cdiv(nout, 64)), dim3(1024), 0, st, scratch, nblk, Ch, O, dw, db);
     NINT_LAUNCH_CHECK();
   } else if (dw && db) {
-    if (dtype == NINT_BF16)
+    if (sq) {
+      if (b16) hipLaunchKernelGGL(head_bwd_dw_seq_kernel<NINT_BF16>, dim3(O * (Ch + 1)), dim3(256), 0, st, h_slab, n0, N, Ch, Chp, O, *sq, dw, db, g->H, g->W, g->P, g->Hh, g->Wh);
+      else hipLaunchKernelGGL(head_bwd_dw_seq_kernel<NINT_F32>, dim3(O * (Ch + 1)), dim3(256), 0, st, h_slab, n0, N, Ch, Chp, O, *sq, dw, db, g->H, g->W, g->P, g->Hh, g->Wh);
+    } else if (b16) {
       hipLaunchKernelGGL(head_bwd_dw_kernel<NINT_BF16>, dim3(O * (Ch + 1)), dim3(256), 0, st, h_slab, n0, N, Ch, Chp, O, dpred, dw, db, g->H, g->W, g->P, g->Hh, g->Wh);
-    else if (dtype == NINT_F32)
+    } else {
       hipLaunchKernelGGL(head_bwd_dw_kernel<NINT_F32>, dim3(O * (Ch + 1)), dim3(256), 0, st, h_slab, n0, N, Ch, Chp, O, dpred, dw, db, g->H, g->W, g->P, g->Hh, g->Wh);
-    else
-      return NINT_E_ARG;
+    }
     NINT_LAUNCH_CHECK();
   }
+#undef NINT_DW2
   return NINT_OK;
+}
+
+extern "C" int nint_head_bwd(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w,
+                             const float* dpred, void* dh, float* dw, float* db, const nint_geom* g, int dtype,
+                             float* scratch, size_t scratch_bytes, void* stream) {
+  if (!h_slab || !w || !dpred || !g || N <= 0 || O <= 0 || Ch <= 0) return NINT_E_ARG;
+  if (dtype != NINT_BF16 && dtype != NINT_F32) return NINT_E_ARG;
+  return head_bwd_impl(h_slab, n0, N, Ch, Chp, O, w, dpred, nullptr, dh, dw, db, g, dtype, scratch, scratch_bytes, stream);
+}
+
+extern "C" int nint_head_bwd_seq(const void* h_slab, int B, int T, int Ch, int Chp, int O, const float* w, const float* dseq,
+                                 const float* dpred_last, void* dh_seq, float* dw, float* db, const nint_geom* g, int dtype,
+                                 float* scratch, size_t scratch_bytes, void* stream) {
+  if (!head_seq_args_ok(h_slab, B, T, Ch, Chp, O, w, g, dtype)) return NINT_E_ARG;
+  if ((!dseq && !dpred_last) || (!dw) != (!db) || (!dh_seq && !dw)) return NINT_E_ARG;
+  if (((((uintptr_t)h_slab) | ((uintptr_t)dh_seq)) & 15) != 0) return NINT_E_ALIGN;
+  const DpSeq sq = {dseq, dpred_last, O, B, T, (size_t)g->H * g->W};
+  return head_bwd_impl(h_slab, B, T * B, Ch, Chp, O, w, nullptr, &sq, dh_seq, dw, db, g, dtype, scratch, scratch_bytes, stream);
 }
 
 // ------------------------------------------------------------------------------ loss
@@ -1115,17 +1286,18 @@ extern "C" int nint_loss_mse_l1_crop(const float* pred, const float* y, float* d
 // the channel vector is read once, pred never goes to memory, dpred is written for the head's weight gradient.
 // Same arithmetic, in the same order, as head_fwd_kernel -> loss_partial_kernel -> head_bwd_dh_kernel.
 #define HEAD_OCH 64
-template <int DT, int CHV>
-__global__ __launch_bounds__(256) void head_loss_fused_kernel(const void* __restrict__ h, int n0, int N, int Ch, int Chp, int O,
-                                                              const float* __restrict__ w, const float* __restrict__ b,
-                                                              const float* __restrict__ y, float* __restrict__ dpred,
-                                                              void* __restrict__ dh, double* __restrict__ partial, int H, int W,
-                                                              int P, int Hh, int Wh, int oy, int ox, int Hc, int Wc) {
+// SEQ (nint_head_loss_seq_fused): the images are all T*B steps of the slab, image n = t*B + b; the targets are (B, T, O, Hc, Wc),
+// plane block b*T + t (head_image); dpred and dh stay in image order, which is what the weight-gradient stage and BPTT read.
+template <int DT, int CHV, bool SEQ>
+__device__ __forceinline__ void head_loss_fused_body(char* smem_hl, const void* __restrict__ h, int n0, int N, int Ch, int Chp, int O,
+                                                     const float* __restrict__ w, const float* __restrict__ b,
+                                                     const float* __restrict__ y, float* __restrict__ dpred,
+                                                     void* __restrict__ dh, double* __restrict__ partial, int H, int W,
+                                                     int P, int Hh, int Wh, int oy, int ox, int Hc, int Wc, int Bs) {
   // A workgroup takes 64 pixels per pass (grid-stride).  Phase 1: wave q runs the outputs [q*OG, (q+1)*OG) of every pixel
   // (lane = pixel): pred, loss terms, d loss / d pred -> dpred and, through LDS, to phase 2: wave q accumulates the
   // channels [q*CHV/4, (q+1)*CHV/4) of dL/dh over ALL outputs in output order.  (One thread per pixel for all outputs --
   // the first version -- is a chain of O dependent round trips on 1/4 of the threads: 50 us at B = 8, 44 us at B = 1.)
-  extern __shared__ __attribute__((aligned(16))) char smem_hl[];
   float* w_s = (float*)smem_hl;                  // [O][CHV], zero padded (head_stage_weights)
   float* gq_s = w_s + O * CHV;                   // [min(O, HEAD_OCH)][64]
   head_stage_weights<CHV>(w_s, w, O, Ch);
@@ -1153,7 +1325,7 @@ __global__ __launch_bounds__(256) void head_loss_fused_kernel(const void* __rest
     const int cy = yy - oy, cx = x - ox;
     const bool in = live && cy >= 0 && cy < Hc && cx >= 0 && cx < Wc;
     float* dp = dpred + ((size_t)n * O * H + yy) * W + x;
-    const float* yp = y + ((size_t)n * O * Hc + cy) * Wc + cx;
+    const float* yp = y + (head_image<SEQ>(n, Bs, N / (SEQ ? Bs : 1)) * O * Hc + cy) * Wc + cx;
     float acc[CQ];
 #pragma unroll
     for (int c = 0; c < CQ; ++c) acc[c] = 0.f;
@@ -1224,6 +1396,30 @@ __global__ __launch_bounds__(256) void head_loss_fused_kernel(const void* __rest
   if (threadIdx.x < 4) partial[blockIdx.x * 4 + threadIdx.x] = red[threadIdx.x][0];
 }
 
+template <int DT, int CHV>
+__global__ __launch_bounds__(256) void head_loss_fused_kernel(const void* __restrict__ h, int n0, int N, int Ch, int Chp, int O,
+                                                              const float* __restrict__ w, const float* __restrict__ b,
+                                                              const float* __restrict__ y, float* __restrict__ dpred,
+                                                              void* __restrict__ dh, double* __restrict__ partial, int H, int W,
+                                                              int P, int Hh, int Wh, int oy, int ox, int Hc, int Wc) {
+  extern __shared__ __attribute__((aligned(16))) char smem_hl[];
+  head_loss_fused_body<DT, CHV, false>(smem_hl, h, n0, N, Ch, Chp, O, w, b, y, dpred, dh, partial, H, W, P, Hh, Wh, oy, ox, Hc, Wc, 0);
+}
+
+template <int DT, int CHV>
+__global__ __launch_bounds__(256) void head_loss_seq_fused_kernel(const void* __restrict__ h, int n0, int N, int Ch, int Chp, int O,
+                                                                  const float* __restrict__ w, const float* __restrict__ b,
+                                                                  const float* __restrict__ y, float* __restrict__ dpred,
+                                                                  void* __restrict__ dh, double* __restrict__ partial, int H, int W,
+                                                                  int P, int Hh, int Wh, int oy, int ox, int Hc, int Wc, int Bs) {
+  extern __shared__ __attribute__((aligned(16))) char smem_hls[];
+  head_loss_fused_body<DT, CHV, true>(smem_hls, h, n0, N, Ch, Chp, O, w, b, y, dpred, dh, partial, H, W, P, Hh, Wh, oy, ox, Hc, Wc, Bs);
+}
+
+static int head_loss_fused_impl(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w, const float* b,
+                                const float* y, float* dpred, void* dh, float* loss_out, double* stats, const nint_geom* g,
+                                int oy, int ox, int Hc, int Wc, int dtype, int Bs, void* stream);
+
 extern "C" int nint_head_loss_fused(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w, const float* b,
                                     const float* y, float* dpred, void* dh, float* loss_out, double* stats, const nint_geom* g,
                                     int oy, int ox, int Hc, int Wc, int dtype, void* stream) {
@@ -1232,6 +1428,23 @@ extern "C" int nint_head_loss_fused(const void* h_slab, int n0, int N, int Ch, i
   if (dtype != NINT_BF16 && dtype != NINT_F32) return NINT_E_ARG;
   if (Chp > 128 || Chp % 4) return NINT_E_SHAPE;   // wider heads: nint_head_fwd + nint_loss_mse_l1_crop + nint_head_bwd
   if ((((uintptr_t)loss_out) & 7) != 0) return NINT_E_ALIGN;
+  return head_loss_fused_impl(h_slab, n0, N, Ch, Chp, O, w, b, y, dpred, dh, loss_out, stats, g, oy, ox, Hc, Wc, dtype, 0, stream);
+}
+
+extern "C" int nint_head_loss_seq_fused(const void* h_slab, int B, int T, int Ch, int Chp, int O, const float* w, const float* b,
+                                        const float* y, float* dpred, void* dh_seq, float* loss_out, double* stats,
+                                        const nint_geom* g, int oy, int ox, int Hc, int Wc, int dtype, void* stream) {
+  if (!y || !dpred || !dh_seq || !loss_out || !head_seq_args_ok(h_slab, B, T, Ch, Chp, O, w, g, dtype)) return NINT_E_ARG;
+  if (oy < 0 || ox < 0 || Hc <= 0 || Wc <= 0 || oy + Hc > g->H || ox + Wc > g->W) return NINT_E_ARG;
+  if (Chp > 128) return NINT_E_SHAPE;              // wider heads: nint_head_fwd_seq + nint_loss_mse_l1_crop + nint_head_bwd_seq
+  if ((((uintptr_t)loss_out) & 7) != 0 || ((((uintptr_t)h_slab) | ((uintptr_t)dh_seq)) & 15) != 0) return NINT_E_ALIGN;
+  return head_loss_fused_impl(h_slab, B, T * B, Ch, Chp, O, w, b, y, dpred, dh_seq, loss_out, stats, g, oy, ox, Hc, Wc, dtype, B, stream);
+}
+
+// Bs != 0: the sequence entry (n0 = B, N = T*B)
+static int head_loss_fused_impl(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w, const float* b,
+                                const float* y, float* dpred, void* dh, float* loss_out, double* stats, const nint_geom* g,
+                                int oy, int ox, int Hc, int Wc, int dtype, int Bs, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   double* partial = (double*)(loss_out + 2);   // loss_out: [0]=loss, [1]=pad, [2..] = up to LOSS_BLOCKS_MAX*4 doubles
   // 64 pixels per workgroup and pass: up to LOSS_BLOCKS_MAX workgroups
@@ -1241,10 +1454,14 @@ extern "C" int nint_head_loss_fused(const void* h_slab, int n0, int N, int Ch, i
   const int chv = Chp <= 32 ? 32 : (Chp <= 64 ? 64 : 128);
   const size_t lds = ((size_t)O * chv + (size_t)(O < HEAD_OCH ? O : HEAD_OCH) * 64) * sizeof(float);   // weights [O][CHV] + d loss / d pred of 64 pixels, one output chunk
   if (lds + 8192 > 160 * 1024) return NINT_E_SHAPE;
-#define NINT_HL(DT_, CHV_) { auto kern = head_loss_fused_kernel<DT_, CHV_>;                                                                   \
-                             if (lds + 8192 > 64 * 1024) NINT_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-                             hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, h_slab, n0, N, Ch, Chp, O, w, b,                                \
-                                                y, dpred, dh, partial, g->H, g->W, g->P, g->Hh, g->Wh, oy, ox, Hc, Wc); }
+#define NINT_HL(DT_, CHV_) { if (Bs) { auto kern = head_loss_seq_fused_kernel<DT_, CHV_>;                                                       \
+                               if (lds + 8192 > 64 * 1024) NINT_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
+                               hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, h_slab, n0, N, Ch, Chp, O, w, b,                              \
+                                                  y, dpred, dh, partial, g->H, g->W, g->P, g->Hh, g->Wh, oy, ox, Hc, Wc, Bs); }                 \
+                             else { auto kern = head_loss_fused_kernel<DT_, CHV_>;                                                            \
+                               if (lds + 8192 > 64 * 1024) NINT_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
+                               hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, h_slab, n0, N, Ch, Chp, O, w, b,                              \
+                                                  y, dpred, dh, partial, g->H, g->W, g->P, g->Hh, g->Wh, oy, ox, Hc, Wc); } }
   if (dtype == NINT_BF16) { if (Chp <= 32) NINT_HL(NINT_BF16, 32) else if (Chp <= 64) NINT_HL(NINT_BF16, 64) else NINT_HL(NINT_BF16, 128) }
   else { if (Chp <= 32) NINT_HL(NINT_F32, 32) else if (Chp <= 64) NINT_HL(NINT_F32, 64) else NINT_HL(NINT_F32, 128) }
 #undef NINT_HL

@@ -248,6 +248,7 @@ static int bwd_check(const nint_seq* s) {
     if (!s->gates[l] || !s->dG[l] || !s->dh[l] || !s->dc[l] || !s->dW[l] || !s->db[l]) return NINT_E_ARG;
   if ((s->need_dx && !s->dx) || !s->wg_partial) return NINT_E_ARG;
   if (s->fuse_bwd < 0 || (s->fuse_bwd > 2 && !(s->fuse_bwd & 0x40000000)) || s->bwd_parts < 0 || s->bwd_parts > 2) return NINT_E_ARG;
+  if ((((uintptr_t)s->dh_seq) & 15) != 0) return NINT_E_ALIGN;
   return NINT_OK;
 }
 
@@ -308,16 +309,27 @@ struct BwdPlanner {
   void flush_d() { if (has_d) push_conv(out, held_d, NINT_PROBE_DGRAD, NINT_OP_DGRAD, 0, held_u); has_d = false; }
   void flush_p() { if (has_p) push_pw(out, held_p, 0, held_t); has_p = false; }
 
+  // nint_seq.dh_seq: the top layer's d/dh_t that does not come through the recurrence (the per-step head outputs), block t; nullptr: none
+  const void* seq_block(int l, int t) const {
+    return s->dh_seq && l == L - 1 ? (const char*)s->dh_seq + (size_t)t * B * comp_px * s->layer[l].Chp * es : nullptr;
+  }
+
   // the pointwise backward of layer l: consumes dh[l] / dc[l] of time t (first BPTT step: not a dc flagged all-zero), writes dG of time t
   int pointwise(int l, int t, int so) {
     if (!merge_d || l == 0) flush_d();                         // (wave = 4 / 5: the held-back dgrad touches layer 0 only)
     const nint_layer* ly = &s->layer[l];
     const size_t cs = (size_t)B * comp_px * ly->Chp, Gc = 4 * (size_t)ly->Ch16;
     PwArgs pa;
+    // d/dh_t: the recurrent part in dh[l], and a second piece -- the bottom layer's own h columns under merge_d (L >= 2), or the
+    // top layer's block of dh_seq (never both: the bottom layer is the top one in a single-layer stack only).  At T-1 there is
+    // no recurrent part: the block IS d/dh_{T-1}
+    const void* blk = seq_block(l, t);
+    const void* dh = blk && t == T - 1 ? blk : s->dh[l];
+    const void* dh2 = merge_d && l == 0 && t < T - 1 ? dh0_own : (blk && t < T - 1 ? blk : nullptr);
     const int rc = nint_internal_pointwise_plan(ly, &s->g, s->dtype, B, (const char*)s->gates[l] + (size_t)t * B * comp_px * Gc * es,
-                                                s->c[l] + (size_t)t * cs, s->c[l] + (size_t)(t + 1) * cs, s->dh[l], s->dc[l],
+                                                s->c[l] + (size_t)t * cs, s->c[l] + (size_t)(t + 1) * cs, dh, s->dc[l],
                                                 (char*)s->dG[l] + (size_t)t * B * halo_px * Gc * es, t == T - 1 && ((s->zero_dstate >> (2 * l)) & 1),
-                                                merge_d && l == 0 && t < T - 1 ? dh0_own : nullptr, &pa);
+                                                dh2, &pa);
     if (rc != NINT_OK) return rc;
     if (merge_p && l == 0 && so + off[L - 1] >= 2) { has_p = true; held_p = pa; held_t = t; }    // the next outer step opens with a fused step of the top layer
     else push_pw(out, pa, l, t);
@@ -379,7 +391,7 @@ struct BwdPlanner {
     const size_t cs = (size_t)B * comp_px * ly->Chp, Gc = 4 * (size_t)ly->Ch16;
     DgradPw pw = {};
     pw.gates = (const char*)s->gates[l] + (size_t)(u - 1) * B * comp_px * Gc * es; pw.c_prev = s->c[l] + (size_t)(u - 1) * cs;
-    pw.c_new = s->c[l] + (size_t)u * cs; pw.dc = s->dc[l]; pw.old = l < L - 1 ? s->dh[l] : nullptr;
+    pw.c_new = s->c[l] + (size_t)u * cs; pw.dc = s->dc[l]; pw.old = l < L - 1 ? s->dh[l] : seq_block(l, u - 1);
     pw.dG_out = (char*)s->dG[l] + (size_t)(u - 1) * B * halo_px * Gc * es;
     if (lo[l]) ride_lo(pw, l, u);
     const bool top_pair = merge && has_d && l == L - 1;        // the top layer's step right behind the held-back bottom dgrad

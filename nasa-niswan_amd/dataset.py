@@ -92,7 +92,9 @@ class _ResidentRecord(torch.utils.data.Dataset):
     already in host memory: statistics over the training part, windows, period split, one upload of the record."""
 
     def _setup(self, fields, yraw, period: str, padding, in_channels: int, sequence_length: int, levels: int,
-               grid: Tuple[int, int], pad_mode: str, device, pinned: bool = False, static=None):
+               grid: Tuple[int, int], pad_mode: str, device, pinned: bool = False, static=None, sequence_targets: bool = False):
+        # sequence_targets: the target is the tracer at EVERY step of the window, (T, [L,] H, W) per sample, not the last step's
+        self.sequence_targets = bool(sequence_targets)
         self.period, self.padding, self.seq_len, self.levels = period, tuple(padding) if padding else None, sequence_length, levels
         self.in_channels, self.grid, self.device = in_channels, tuple(grid), torch.device(device)
         self.mode = {"reference": 0, "reflect": 1}[pad_mode]
@@ -142,7 +144,7 @@ class _ResidentRecord(torch.utils.data.Dataset):
         """raw (un-normalised, un-padded) window and target of sample `index` (dataset.py:614-616,599)."""
         t0 = int(self.first[index])
         sl = slice(t0, t0 + self.seq_len)
-        return tuple(a[sl] for _, a in self.fields), self.yraw[t0 + self.seq_len - 1]
+        return tuple(a[sl] for _, a in self.fields), (self.yraw[sl] if self.sequence_targets else self.yraw[t0 + self.seq_len - 1])
 
     # ---- device-side pieces
     def _device_arrays(self):
@@ -177,9 +179,19 @@ class _ResidentRecord(torch.utils.data.Dataset):
         return ptrs, lev, int(self.static is not None)
 
     def _targets(self, dv, t0s):
-        """z-scored targets (dataset.py:596,599) of a batch: the tracer at each window's LAST step, one launch"""
+        """z-scored targets (dataset.py:596,599) of a batch: the tracer at each window's LAST step -- or, with sequence_targets,
+        at every step of the window (B, T, [L,] H, W): the same kernel with T = seq_len from the window start -- one launch"""
         H, W = self.grid
         B, L = len(t0s), self.levels
+        if self.sequence_targets:
+            T = self.seq_len
+            y = torch.empty(B, T, L, H, W, dtype=torch.float32, device=self.device)
+            yptr = (C.c_void_p * 1)(dv["y"].data_ptr())
+            ylev = (C.c_int * 1)(L)
+            tl = (C.c_int * B)(*[int(t) for t in t0s])
+            check(_lib.load().nint_preproc_fuse_pad_batch(yptr, ylev, 1, ptr(dv["ymean"]), ptr(dv["ystd"]), tl, B, ptr(y),
+                                                          T, H, W, H, W, 1, stream_ptr()), "target z-score")
+            return y[:, :, 0] if L == 1 else y
         y = torch.empty(B, L, H, W, dtype=torch.float32, device=self.device)
         yptr = (C.c_void_p * 1)(dv["y"].data_ptr())
         ylev = (C.c_int * 1)(L)
@@ -189,8 +201,8 @@ class _ResidentRecord(torch.utils.data.Dataset):
         return y[:, 0] if L == 1 else y
 
     def device_batch(self, indices: Sequence[int]):
-        """(X (B,T,C,Hp,Wp) f32, y (B,[L,]H,W) f32) on the GPU: the reference's tensors (dataset.py:538-539),
-        one launch of the fuse/z-score/halo-pad kernel for the whole batch."""
+        """(X (B,T,C,Hp,Wp) f32, y (B,[L,]H,W) f32 -- (B,T,[L,]H,W) with sequence_targets) on the GPU: the reference's tensors
+        (dataset.py:538-539), one launch of the fuse/z-score/halo-pad kernel for the whole batch."""
         dv = self._device_arrays()
         H, W = self.grid
         Hp, Wp = self.padding if self.padding else (H, W)
@@ -238,7 +250,8 @@ def synth_static(S: int, grid: Tuple[int, int], seed: int = 0) -> np.ndarray:
 class SyntheticE33OMA_CRNN(_ResidentRecord):
     def __init__(self, period: str, species: str = "bcb", padding: Tuple[int, int] = (100, 154), in_channels: int = 5,
                  sequence_length: int = 10, *, levels: int = 1, n_steps: int = 480, grid: Tuple[int, int] = (90, 144),
-                 pad_mode: str = "reference", device="cuda", seed: int = 0, static_channels: int = 0):
+                 pad_mode: str = "reference", device="cuda", seed: int = 0, static_channels: int = 0,
+                 sequence_targets: bool = False):
         super().__init__()
         assert species == "bcb", "only the BCB statistics ship with the reference"
         S = int(static_channels)
@@ -273,7 +286,8 @@ class SyntheticE33OMA_CRNN(_ResidentRecord):
             fields = [("u", self.u), ("v", self.v), ("w", self.w), ("prec", self.prec), ("src", self.src)]
         yraw = field("bc_conc", (n_steps, levels, H, W), True)
         static = synth_static(S, grid, seed) if S else None
-        self._setup(fields, yraw, period, padding, in_channels, sequence_length, levels, grid, pad_mode, device, static=static)
+        self._setup(fields, yraw, period, padding, in_channels, sequence_length, levels, grid, pad_mode, device, static=static,
+                    sequence_targets=sequence_targets)
 
 
 class E33OMA90D_CRNN(_ResidentRecord):
@@ -298,7 +312,7 @@ class E33OMA90D_CRNN(_ResidentRecord):
     @classmethod
     def from_arrays(cls, u, v, omega, prec, src, conc, *, period: str = "train", species: str = "bcb",
                     padding: Tuple[int, int] = (100, 154), sequence_length: int = 10, pad_mode: str = "reference",
-                    device="cuda", pinned: bool = True, static=None):
+                    device="cuda", pinned: bool = True, static=None, sequence_targets: bool = False):
         self = cls.__new__(cls)
         torch.utils.data.Dataset.__init__(self)
         f32 = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.float32))
@@ -316,5 +330,5 @@ class E33OMA90D_CRNN(_ResidentRecord):
         fields = [("u", u), ("v", v), ("w", omega), ("prec", prec), ("src", src)]          # fusion order dataset.py:584
         nS = np.shape(static)[0] if static is not None and np.ndim(static) else 0
         self._setup(fields, conc, period, padding, 3 * L + 2 + nS, sequence_length, L, (H, W), pad_mode, device, pinned=pinned,
-                    static=static)
+                    static=static, sequence_targets=sequence_targets)
         return self

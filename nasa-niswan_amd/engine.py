@@ -82,6 +82,7 @@ class Workspace:
                 self.dh.append(torch.zeros(B * comp_px * Chp * es, **u8))      # ET: transient gradient, read once per step
                 self.dc.append(torch.zeros(B * comp_px * Chp, **f32))
         self.dx = None
+        self._dh_seq = None
         self.Cxp0 = Cxp0
         self.seq = NintSeq()
         s = self.seq
@@ -101,6 +102,14 @@ class Workspace:
         if train:
             s.wg_partial = eng.wg_partial.data_ptr()
             s.wg_partial_bytes = eng.wg_partial.numel() * 4
+
+    def dh_seq_slab(self, eng) -> torch.Tensor:
+        """ET compact [T*B][H][W][Chp of the top layer]: the per-step head gradients (nint_seq.dh_seq).  Allocated when
+        sequence gradients are first asked for on this workspace: the many-to-one path never pays for it."""
+        if self._dh_seq is None:
+            Chp = eng.cfgs[-1].padded(eng.kc)[2]
+            self._dh_seq = torch.empty(self.T * self.B * self.H * self.W * Chp * eng.es, dtype=torch.uint8, device=eng.device)
+        return self._dh_seq
 
     # byte offsets of slab (t) inside the per-layer stacks
     def h_view(self, eng, l: int, slot: int) -> int:
@@ -320,6 +329,49 @@ class SeqEngine:
                                      C.byref(ws.g), self.dt, stream_ptr()), "nint_head_fwd")
         return pred
 
+    def _head_args(self, w: torch.Tensor, b: Optional[torch.Tensor]):
+        cfg = self.cfgs[-1]
+        w2 = w.detach().float().contiguous()
+        b2 = None if b is None else b.detach().float().contiguous()
+        return cfg.Ch, cfg.padded(self.kc)[2], w.shape[0], w2, b2
+
+    def head_forward_seq(self, ws: Workspace, w: torch.Tensor, b: Optional[torch.Tensor]) -> torch.Tensor:
+        """The head on the top layer's hidden state of EVERY step in one launch (nint_head_fwd_seq): (B, T*O, H, W), channel
+        t*O + o -- torch.cat of the per-step outputs (model.py:264,272,274 commented code)."""
+        Ch, Chp, O, w2, b2 = self._head_args(w, b)
+        seq = torch.empty(ws.B, ws.T * O, ws.H, ws.W, dtype=torch.float32, device=self.device)
+        check(self.lib.nint_head_fwd_seq(ptr(ws.h[-1]), ws.B, ws.T, Ch, Chp, O, ptr(w2), ptr(b2), ptr(seq), C.byref(ws.g),
+                                         self.dt, stream_ptr()), "nint_head_fwd_seq")
+        return seq
+
+    def head_backward_seq(self, ws: Workspace, w: torch.Tensor, dseq: Optional[torch.Tensor], dpred: Optional[torch.Tensor] = None,
+                          dw_out=None, db_out=None, write_dh: bool = True):
+        """Head backward over every step (nint_head_bwd_seq): dseq (B, T*O, H, W) and / or dpred (B, O, H, W), the cotangent
+        of pred = head(h_{T-1}), which joins step T-1.  Writes the per-step dL/dh into ws.dh_seq_slab() (unless `write_dh` is
+        False) for backward(..., seq_grads=True); returns (dw_head, db_head)."""
+        Ch, Chp, O, w2, _ = self._head_args(w, None)
+        ds = None if dseq is None else dseq.detach().float().contiguous()
+        dp = None if dpred is None else dpred.detach().float().contiguous()
+        dw = dw_out if dw_out is not None else torch.empty(O, Ch, dtype=torch.float32, device=self.device)
+        db = db_out if db_out is not None else torch.empty(O, dtype=torch.float32, device=self.device)
+        check(self.lib.nint_head_bwd_seq(ptr(ws.h[-1]), ws.B, ws.T, Ch, Chp, O, ptr(w2), ptr(ds), ptr(dp),
+                                         ptr(ws.dh_seq_slab(self)) if write_dh else None, ptr(dw), ptr(db), C.byref(ws.g), self.dt,
+                                         ptr(self.wg_partial), self.wg_partial.numel() * 4, stream_ptr()), "nint_head_bwd_seq")
+        return dw.view(O, Ch, 1, 1), db
+
+    def head_loss_seq_fused(self, ws: Workspace, w: torch.Tensor, b: Optional[torch.Tensor], y: torch.Tensor, dpred: torch.Tensor,
+                            scratch: torch.Tensor, stats: torch.Tensor, halo, Hc: int, Wc: int) -> bool:
+        """head_loss_fused over every step (nint_head_loss_seq_fused): y (B, T, O, Hc, Wc); dpred (T*B, O, H, W) in image
+        order t*B + b; the per-step dL/dh goes into ws.dh_seq_slab().  False beyond the fused kernel's limit."""
+        Ch, Chp, O, w2, b2 = self._head_args(w, b)
+        chv = 32 if Chp <= 32 else (64 if Chp <= 64 else 128)
+        if Chp > 128 or (O * chv + min(O, 64) * 64) * 4 + 8192 > 160 * 1024:
+            return False
+        check(self.lib.nint_head_loss_seq_fused(ptr(ws.h[-1]), ws.B, ws.T, Ch, Chp, O, ptr(w2), ptr(b2), ptr(y), ptr(dpred),
+                                                ptr(ws.dh_seq_slab(self)), ptr(scratch), ptr(stats), C.byref(ws.g), halo[0], halo[1],
+                                                Hc, Wc, self.dt, stream_ptr()), "nint_head_loss_seq_fused")
+        return True
+
     def head_loss_fused(self, ws: Workspace, w: torch.Tensor, b: Optional[torch.Tensor], y: torch.Tensor, dpred: torch.Tensor,
                         scratch: torch.Tensor, stats: torch.Tensor, halo, Hc: int, Wc: int) -> bool:
         """Training fast path (nint_head_loss_fused): head forward, crop, MSE+L1 sums, d loss / d pred and dL/dh_{T-1}
@@ -339,9 +391,13 @@ class SeqEngine:
                                             self.dt, stream_ptr()), "nint_head_loss_fused")
         return True
 
-    def head_backward(self, ws: Workspace, w: torch.Tensor, dpred: torch.Tensor, dw_out=None, db_out=None, write_dh: bool = True):
+    def head_backward(self, ws: Workspace, w: torch.Tensor, dpred: torch.Tensor, dw_out=None, db_out=None, write_dh: bool = True,
+                      images: Optional[Tuple[int, int]] = None):
         """Writes dL/dh_{T-1} of the last layer into ws.dh[-1] (unless `write_dh` is False: the fused head/loss pass
-        already did); returns (dw_head, db_head)."""
+        already did); returns (dw_head, db_head).  `images` = (first image, count) of the h slab that `dpred` (count, O, H, W)
+        belongs to: default the last step's B; (B, T*B) reduces every step's (the fused sequence pass, write_dh False)."""
+        n0, N = images if images is not None else (ws.T * ws.B, ws.B)
+        assert images is None or not write_dh
         l = len(self.cfgs) - 1
         cfg = self.cfgs[l]
         Chp = cfg.padded(self.kc)[2]
@@ -350,20 +406,23 @@ class SeqEngine:
         dp = dpred.detach().float().contiguous()
         dw = dw_out if dw_out is not None else torch.empty(O, cfg.Ch, dtype=torch.float32, device=self.device)
         db = db_out if db_out is not None else torch.empty(O, dtype=torch.float32, device=self.device)
-        check(self.lib.nint_head_bwd(ptr(ws.h[l]), ws.T * ws.B, ws.B, cfg.Ch, Chp, O, ptr(w2), ptr(dp),
+        check(self.lib.nint_head_bwd(ptr(ws.h[l]), n0, N, cfg.Ch, Chp, O, ptr(w2), ptr(dp),
                                      ptr(ws.dh[l]) if write_dh else None,
                                      ptr(dw), ptr(db), C.byref(ws.g), self.dt, ptr(self.wg_partial),
                                      self.wg_partial.numel() * 4, stream_ptr()), "nint_head_bwd")
         return dw.view(O, cfg.Ch, 1, 1), db
 
     def backward(self, ws: Workspace, need_dx: bool, zero_state_grads: Sequence[int] = (),
-                 dW_out: Optional[Sequence[torch.Tensor]] = None, db_out: Optional[Sequence[torch.Tensor]] = None, parts: int = 0):
+                 dW_out: Optional[Sequence[torch.Tensor]] = None, db_out: Optional[Sequence[torch.Tensor]] = None, parts: int = 0,
+                 seq_grads: bool = False):
         """BPTT of model.py:253-271.  Precondition: ws.dh[l], ws.dc[l] hold dL/dh_{T-1}, dL/dc_{T-1}
         (layers listed in ``zero_state_grads`` start from zero state gradients instead).  Returns ([dW_l], [db_l], dx or None).
         ``dW_out`` / ``db_out``: f32 contiguous destinations (e.g. views of a flat gradient bucket).
         ``parts`` (nint_seq.bwd_parts): 0 = everything; 1 = the BPTT chain + the gradients of layers >= 1; 2 = layer 0's weight /
         bias gradient only, after a parts = 1 call on the same workspace (the trainer starts the all-reduce of the rest of the
-        bucket in between)."""
+        bucket in between).
+        ``seq_grads`` (nint_seq.dh_seq): the top layer's dL/dh_t of every step is in ws.dh_seq_slab() (head_backward_seq /
+        head_loss_seq_fused) and joins the recurrence at each t; ws.dh[-1] is then not read on entry."""
         assert ws.train
         # layers in ``zero_state_grads`` start BPTT from zero dL/dh, dL/dc: flagged, not filled (the first BPTT step
         # then neither reads dc nor accumulates into dh).  The top layer's dh always holds the head's gradient.
@@ -392,10 +451,12 @@ class SeqEngine:
             s.dx = dx.data_ptr()
         s.need_dx = int(need_dx)
         s.bwd_parts = int(parts)
+        s.dh_seq = ws.dh_seq_slab(self).data_ptr() if seq_grads else None
         try:
             check(self.lib.nint_seq_bwd(C.byref(s), stream_ptr()), "nint_seq_bwd")
         finally:
             s.bwd_parts = 0
+            s.dh_seq = None
         s.dx = None
         dx_out = None
         if need_dx:

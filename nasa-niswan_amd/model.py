@@ -10,7 +10,8 @@ Extensions are keyword-only with reference-preserving defaults (SURVEY.md sectio
     compute_dtype   "f32" (exact-parity mode) or "bf16" (bf16 storage, f32 accumulate)
     out_channels    head width (1 in the reference, L*n_tracers for the level-fused variants)
     return_sequence also return the per-step head outputs (the variant the analysis notebook
-                    was run with: model.py:264,272,274 commented code, test.ipynb:273)
+                    was run with: model.py:264,272,274 commented code, test.ipynb:273); differentiable:
+                    gradients flow through ``seq`` as through ``pred``
 """
 from __future__ import annotations
 
@@ -58,10 +59,11 @@ class _ConvLSTMFn(torch.autograd.Function):
         pred = eng.head_forward(ws, head_w, head_b)
         outs = [pred]
         if module.return_sequence:
-            if train:
-                raise RuntimeError("return_sequence=True is an inference-only extension (test.ipynb:273)")
-            outs.append(torch.cat([eng.head_forward(ws, head_w, head_b, slot=t + 1) for t in range(T)], dim=1))
+            outs.append(eng.head_forward_seq(ws, head_w, head_b))       # every step in one launch
+        ctx.return_sequence = module.return_sequence
         if train:
+            if module.return_sequence:
+                ctx.set_materialize_grads(False)                        # an unused output's cotangent stays None: passed as NULL
             ctx.eng, ctx.ws, ctx.rel = eng, ws, _Releaser(ws)
             ctx.save_for_backward(head_w)
             ctx.x_needs_grad = ctx.needs_input_grad[2]
@@ -71,12 +73,20 @@ class _ConvLSTMFn(torch.autograd.Function):
         return tuple(outs) if len(outs) > 1 else pred
 
     @staticmethod
-    def backward(ctx, dpred, *unused):
+    def backward(ctx, dpred, dseq=None):
         eng, ws = ctx.eng, ctx.ws
         (head_w,) = ctx.saved_tensors
         L = len(eng.cfgs)
-        dw_head, db_head = eng.head_backward(ws, head_w, dpred)
-        dWs, dbs, dx = eng.backward(ws, ctx.x_needs_grad, zero_state_grads=range(L))
+        if ctx.return_sequence:
+            if dpred is None and dseq is None:
+                ctx.rel.release()
+                return (None,) * (5 + ctx.nwb)
+            # per-step head gradients (pred's cotangent joins step T-1), then BPTT with one block of them per time step
+            dw_head, db_head = eng.head_backward_seq(ws, head_w, dseq, dpred)
+            dWs, dbs, dx = eng.backward(ws, ctx.x_needs_grad, zero_state_grads=range(L), seq_grads=True)
+        else:
+            dw_head, db_head = eng.head_backward(ws, head_w, dpred)
+            dWs, dbs, dx = eng.backward(ws, ctx.x_needs_grad, zero_state_grads=range(L))
         ctx.rel.release()
         grads = []
         for l in range(L):

@@ -5,7 +5,7 @@ MI355X step.  Same flags, same artefacts (`configurations.json`, `logger.npy`,
 stepped once per epoch before validation, checkpoint every 10 epochs); the per-batch
 `loss.item()` / sklearn R2 host syncs (train.py:113-114) are replaced by device accumulators read
 once per epoch.  Added flags: --dtype, --levels, --grid, --synthetic-steps, --pad-mode, --f32-inputs,
---static-channels.
+--static-channels, --sequence-loss.
 
 The data path is on the device too: by default every batch is written by ONE launch of the
 fuse / z-score / halo-pad kernel straight into the model's bf16 input slab (dataset.slab_batch);
@@ -73,6 +73,9 @@ def get_arguments(argv=None, MODEL='LSTM-00', SPECIES='bcb', LEARNING_RATE=1.0E-
                              "(the reference hard-codes 90x144 and halo 5, train.py:102)")
     parser.add_argument("--f32-inputs", action="store_true",
                         help="materialise X as the reference's f32 (B,T,C,Hp,Wp) tensor instead of writing the input slab directly")
+    parser.add_argument("--sequence-loss", action="store_true",
+                        help="sequence-to-sequence supervision: the target is the tracer at every step of the window and the loss "
+                             "(training and validation) runs over the head's output at every step, not the last one alone")
     args = parser.parse_args(argv)
     rank = int(os.environ.get("RANK", "0"))
     if rank == 0:
@@ -117,12 +120,14 @@ def main(args):
     halo = ((args.input_size[0] - H) // 2, (args.input_size[1] - W) // 2)                    # 5,5 in the reference (train.py:102)
     ds_kw = dict(species=args.species, padding=tuple(args.input_size), in_channels=args.in_channels,
                  sequence_length=args.sequence_length, levels=args.levels, n_steps=args.synthetic_steps,
-                 grid=(H, W), pad_mode=args.pad_mode, device=dev, static_channels=args.static_channels)
+                 grid=(H, W), pad_mode=args.pad_mode, device=dev, static_channels=args.static_channels,
+                 sequence_targets=args.sequence_loss)
     train_dataset = SyntheticE33OMA_CRNN('train', **ds_kw)                                   # train.py:63-65
     val_dataset = SyntheticE33OMA_CRNN('val', **ds_kw)
     get_batch = (lambda ds, idx: ds.device_batch(idx)) if args.f32_inputs else (lambda ds, idx: ds.slab_batch(idx))
 
-    trainer = FusedTrainer(generator, lr=args.learning_rate, betas=tuple(args.betas), halo=halo)        # train.py:71
+    trainer = FusedTrainer(generator, lr=args.learning_rate, betas=tuple(args.betas), halo=halo,        # train.py:71
+                           sequence_loss=args.sequence_loss)
     optimizer = trainer.optimizer
     scheduler = optim.lr_scheduler.StepLR(optimizer, step_size=int(args.scheduler_config[0]),
                                           gamma=args.scheduler_config[1])                   # train.py:72

@@ -26,7 +26,7 @@ from .optim import FlatParams, FusedAdam
 class FusedTrainer:
     def __init__(self, model: ConvLSTM, lr: float = 1e-3, betas=(0.5, 0.999), eps: float = 1e-8,
                  halo: Tuple[int, int] = (5, 5), process_group=None, distributed: Optional[bool] = None,
-                 overlap_allreduce: bool = False):
+                 overlap_allreduce: bool = False, sequence_loss: bool = False):
         dev = next(model.parameters()).device
         if dev.type != "cuda":
             raise _lib.NintError("FusedTrainer needs the model on the MI355X (cuda)")
@@ -53,6 +53,9 @@ class FusedTrainer:
         # the one all-reduce at its end ~5 % of it): the bucket without layer 0's slice is reduced UNDER layer 0's weight gradient
         # (nint_seq.bwd_parts), layer 0's slice after it.  Two all-reduces of disjoint slices: the same sums.
         self.overlap_allreduce = bool(overlap_allreduce)
+        # Sequence-to-sequence supervision: y is (B, T, [O,] Hc, Wc), a target at every step of the window, and the loss is
+        # MSE + L1 over the per-step head outputs (model.py:264,272,274 commented code) instead of the last one alone
+        self.sequence_loss = bool(sequence_loss)
         L = model.num_layers
         self._dW = [self.flat.grad_view(2 * l) for l in range(L)]
         self._db = [self.flat.grad_view(2 * l + 1) for l in range(L)]
@@ -78,11 +81,17 @@ class FusedTrainer:
         wb_b = [c.conv.bias for c in m.layers]
         eng.pack_weights(wb_w, wb_b)
         eng.forward(ws, X)
-        pred = eng.head_forward(ws, m.conv.weight, m.conv.bias)
-        O = pred.shape[1]
+        O = m.conv.weight.shape[0]
         Hc, Wc = y.shape[-2], y.shape[-1]
         yv = y.detach().float().contiguous()
-        assert yv.numel() == B * O * Hc * Wc, "target must be (B,[O,]Hc,Wc)"
+        if self.sequence_loss:
+            # the (B, T*O, H, W) sequence against (B, T, O, Hc, Wc) targets: the loss kernel's own index math with O' = T*O
+            assert yv.numel() == B * T * O * Hc * Wc, "target must be (B,T,[O,]Hc,Wc)"
+            pred = eng.head_forward_seq(ws, m.conv.weight, m.conv.bias)
+            O = T * O
+        else:
+            assert yv.numel() == B * O * Hc * Wc, "target must be (B,[O,]Hc,Wc)"
+            pred = eng.head_forward(ws, m.conv.weight, m.conv.bias)
         dpred = None
         if train:
             if self._dpred is None or self._dpred.shape != pred.shape:
@@ -95,7 +104,7 @@ class FusedTrainer:
 
     def step(self, X: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
         """One optimisation step; returns the loss as a 0-dim DEVICE tensor (no sync).  X: (B,T,C,Hp,Wp) f32 or a
-        dataset.SlabBatch."""
+        dataset.SlabBatch.  y: (B,[O,]Hc,Wc), or (B,T,[O,]Hc,Wc) with ``sequence_loss``."""
         m = self.model
         eng = m._engine(self.device)
         B, T, _, H, W = X.shape
@@ -112,24 +121,38 @@ class FusedTrainer:
         O = m.conv.weight.shape[0]
         Hc, Wc = y.shape[-2], y.shape[-1]
         yv = y.detach().float().contiguous()
-        assert yv.numel() == B * O * Hc * Wc, "target must be (B,[O,]Hc,Wc)"
-        if self._dpred is None or self._dpred.shape != (B, O, H, W):
-            self._dpred = torch.empty(B, O, H, W, dtype=torch.float32, device=self.device)
+        sq = self.sequence_loss
+        assert yv.numel() == B * (T if sq else 1) * O * Hc * Wc, "target must be (B,T,[O,]Hc,Wc)" if sq else "target must be (B,[O,]Hc,Wc)"
+        if self._dpred is None or self._dpred.numel() != B * (T if sq else 1) * O * H * W:
+            self._dpred = torch.empty(B * (T if sq else 1), O, H, W, dtype=torch.float32, device=self.device)
         dpred = self._dpred
-        # head forward + crop + loss + dpred + dL/dh in one pass; the prediction itself is never materialised
-        fused = eng.head_loss_fused(ws, m.conv.weight, m.conv.bias, yv, dpred, self.scratch, self.stats, self.halo, Hc, Wc)
-        if not fused:
-            pred = eng.head_forward(ws, m.conv.weight, m.conv.bias)
-            check(self.lib.nint_loss_mse_l1_crop(ptr(pred), ptr(yv), ptr(dpred), ptr(self.scratch), ptr(self.stats),
-                                                 B, O, H, W, self.halo[0], self.halo[1], Hc, Wc, stream_ptr()),
-                  "nint_loss_mse_l1_crop")
-        eng.head_backward(ws, m.conv.weight, dpred, dw_out=self._dw_head, db_out=self._db_head, write_dh=not fused)
+        if sq:
+            # the same over every step: one pass writes the loss, d loss / d pred (image order t*B + b, which the head's
+            # weight-gradient kernels reduce as T*B images) and the per-step dL/dh that BPTT adds at each t
+            fused = eng.head_loss_seq_fused(ws, m.conv.weight, m.conv.bias, yv, dpred, self.scratch, self.stats, self.halo, Hc, Wc)
+            if fused:
+                eng.head_backward(ws, m.conv.weight, dpred, dw_out=self._dw_head, db_out=self._db_head, write_dh=False, images=(B, T * B))
+            else:
+                seq = eng.head_forward_seq(ws, m.conv.weight, m.conv.bias)
+                check(self.lib.nint_loss_mse_l1_crop(ptr(seq), ptr(yv), ptr(dpred), ptr(self.scratch), ptr(self.stats),
+                                                     B, T * O, H, W, self.halo[0], self.halo[1], Hc, Wc, stream_ptr()),
+                      "nint_loss_mse_l1_crop")
+                eng.head_backward_seq(ws, m.conv.weight, dpred.view(B, T * O, H, W), None, dw_out=self._dw_head, db_out=self._db_head)
+        else:
+            # head forward + crop + loss + dpred + dL/dh in one pass; the prediction itself is never materialised
+            fused = eng.head_loss_fused(ws, m.conv.weight, m.conv.bias, yv, dpred, self.scratch, self.stats, self.halo, Hc, Wc)
+            if not fused:
+                pred = eng.head_forward(ws, m.conv.weight, m.conv.bias)
+                check(self.lib.nint_loss_mse_l1_crop(ptr(pred), ptr(yv), ptr(dpred), ptr(self.scratch), ptr(self.stats),
+                                                     B, O, H, W, self.halo[0], self.halo[1], Hc, Wc, stream_ptr()),
+                      "nint_loss_mse_l1_crop")
+            eng.head_backward(ws, m.conv.weight, dpred, dw_out=self._dw_head, db_out=self._db_head, write_dh=not fused)
         mark()
         if self.distributed and self.overlap_allreduce and L > 1 and pb is None:
             n0 = self.flat.offsets[2]              # layers.0.conv.weight + .bias lead the bucket (module parameter order)
-            eng.backward(ws, False, zero_state_grads=range(L), dW_out=self._dW, db_out=self._db, parts=1)
+            eng.backward(ws, False, zero_state_grads=range(L), dW_out=self._dW, db_out=self._db, parts=1, seq_grads=sq)
             work = self.dist.all_reduce(self.flat.grad[n0:], op=self.dist.ReduceOp.SUM, group=self.pg, async_op=True)
-            eng.backward(ws, False, zero_state_grads=range(L), dW_out=self._dW, db_out=self._db, parts=2)
+            eng.backward(ws, False, zero_state_grads=range(L), dW_out=self._dW, db_out=self._db, parts=2, seq_grads=sq)
             mark()
             eng.release(ws)
             self.dist.all_reduce(self.flat.grad[:n0], op=self.dist.ReduceOp.SUM, group=self.pg)
@@ -137,7 +160,7 @@ class FusedTrainer:
             self.optimizer.step(grad_scale=1.0 / self.world)
             mark()
             return self.scratch[0]
-        eng.backward(ws, False, zero_state_grads=range(L), dW_out=self._dW, db_out=self._db)
+        eng.backward(ws, False, zero_state_grads=range(L), dW_out=self._dW, db_out=self._db, seq_grads=sq)
         mark()
         eng.release(ws)
         if self.distributed:
@@ -155,7 +178,8 @@ class FusedTrainer:
 
     @torch.no_grad()
     def evaluate(self, X: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
-        """Forward + loss only (val_loop, utils.py:52-75); accumulates the R2 statistics."""
+        """Forward + loss only (val_loop, utils.py:52-75); accumulates the R2 statistics.  With ``sequence_loss`` the loss runs
+        over every step and the (B, T*O, H, W) sequence is returned."""
         eng, ws, pred, _ = self.forward_loss(X, y, False)
         eng.release(ws)
         return pred
