@@ -1,0 +1,817 @@
+// head.hip -- the 1x1 head on the top layer's hidden state (forward, d/dh, weight / bias gradient), the crop + MSE + L1
+// loss, and the two fused into one pass over the pixels; each for one step's images or for every step of a sequence.
+// They share head_stage_weights, LOSS_BLOCKS_MAX and loss_final_kernel.  Every kernel body is a __forceinline__ device
+// function under ONE __global__ wrapper templated on SEQ: the register allocation depends on that function boundary.
+#include "nint_common.h"
+
+// ------------------------------------------------------------------------------ 1x1 head
+// pred[n][o][y][x] = b[o] + sum_c w[o][c] * h[n][y][x][c]     (model.py:251,274)
+// One thread per pixel: the channel vector is read once (16-byte loads), the weights are wave-uniform
+// (scalar loads), and every output plane is written coalesced along x.  CHV = channels held in registers.
+// The weights are staged once per workgroup in LDS, zero-padded to [O][CHV]: the inner loop is then broadcast LDS reads and
+// FMAs with no bounds test (a predicate on the run-time channel count made every FMA a branch and a scalar load with its
+// own wait: 176 s_load_dword / 364 branches in the 32-channel instance).  The padding terms add +0.
+template <int CHV>
+__device__ __forceinline__ void head_stage_weights(float* w_s, const float* __restrict__ w, int O, int Ch) {
+  for (int i = threadIdx.x; i < O * CHV; i += blockDim.x) {
+    const int o = i / CHV, c = i - o * CHV;
+    w_s[i] = c < Ch ? w[o * Ch + c] : 0.f;
+  }
+  __syncthreads();
+}
+
+// CHV of a padded channel count (<= 128), and the host's pick of that instance: f(std::integral_constant<int, CHV>)
+static inline int head_chv(int Chp) { return Chp <= 32 ? 32 : (Chp <= 64 ? 64 : 128); }
+template <class F> static inline auto head_by_chv(int Chp, F&& f) {
+  if (Chp <= 32) return f(std::integral_constant<int, 32>{});
+  if (Chp <= 64) return f(std::integral_constant<int, 64>{});
+  return f(std::integral_constant<int, 128>{});
+}
+
+// The sequence entries (nint_head_fwd_seq and its kin) run the same bodies over all T*B images of the top layer's slab; only the
+// plane index of the (B, T*O, H, W) tensors differs: image n = t*B + b (time-major, as everywhere inside the library) owns the
+// O planes from (b*T + t)*O.  SEQ = false: plane block n, the (N, O, H, W) tensors of the one-step entries, whose kernel
+// instances receive the sequence arguments (Bs, dlast, T) without reading them.
+template <bool SEQ>
+__device__ __forceinline__ size_t head_image(size_t n, int Bs, int T) {
+  if constexpr (SEQ) return (n % (size_t)Bs) * T + n / (size_t)Bs;
+  else return n;
+}
+
+template <int DT, int CHV, bool SEQ>
+__device__ __forceinline__ void head_fwd_body(float* w_s, const void* __restrict__ h, int n0, int N, int Ch, int Chp, int O,
+                                              const float* __restrict__ w, const float* __restrict__ b,
+                                              float* __restrict__ pred, int H, int W, int P, int Hh, int Wh, int Bs) {
+  head_stage_weights<CHV>(w_s, w, O, Ch);
+  const size_t npix = (size_t)N * H * W;
+  const size_t pix = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+  if (pix >= npix) return;
+  const int x = pix % W;
+  size_t r = pix / W;
+  const int y = r % H;
+  const int n = r / H;
+  const size_t hb = ((((size_t)(n0 + n)) * Hh + (y + P)) * Wh + (x + P)) * Chp;
+  float hv[CHV];
+#pragma unroll
+  for (int c = 0; c < CHV; c += 4) {
+    const f32x4_t v = (c < Chp) ? load_vec4<DT>(h, hb + c) : (f32x4_t){0.f, 0.f, 0.f, 0.f};
+    hv[c] = v[0]; hv[c + 1] = v[1]; hv[c + 2] = v[2]; hv[c + 3] = v[3];
+  }
+  float* out = pred + (head_image<SEQ>(n, Bs, N / (SEQ ? Bs : 1)) * O * H + y) * W + x;
+  for (int o = 0; o < O; ++o) {
+    float acc = b ? b[o] : 0.f;
+    const f32x4_t* wr = (const f32x4_t*)(w_s + o * CHV);
+#pragma unroll
+    for (int c = 0; c < CHV; c += 4) {
+      const f32x4_t wv = wr[c / 4];
+      acc += wv[0] * hv[c]; acc += wv[1] * hv[c + 1]; acc += wv[2] * hv[c + 2]; acc += wv[3] * hv[c + 3];
+    }
+    out[(size_t)o * H * W] = acc;
+  }
+}
+
+template <int DT, int CHV, bool SEQ>
+__global__ __launch_bounds__(256) void head_fwd_kernel(const void* __restrict__ h, int n0, int N, int Ch, int Chp, int O,
+                                                       const float* __restrict__ w, const float* __restrict__ b,
+                                                       float* __restrict__ pred, int H, int W, int P, int Hh, int Wh, int Bs) {
+  extern __shared__ __attribute__((aligned(16))) char smem_hf[];
+  head_fwd_body<DT, CHV, SEQ>((float*)smem_hf, h, n0, N, Ch, Chp, O, w, b, pred, H, W, P, Hh, Wh, Bs);
+}
+
+// generic widths: one thread per output element
+template <int DT, bool SEQ>
+__device__ __forceinline__ void head_fwd_wide_body(const void* __restrict__ h, int n0, int N, int Ch, int Chp, int O,
+                                                   const float* __restrict__ w, const float* __restrict__ b, float* __restrict__ pred,
+                                                   int H, int W, int P, int Hh, int Wh, int Bs) {
+  const size_t total = (size_t)N * O * H * W;
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int x = i % W;
+    size_t r = i / W;
+    const int y = r % H; r /= H;
+    const int o = r % O;
+    const int n = r / O;
+    const size_t hb = ((((size_t)(n0 + n)) * Hh + (y + P)) * Wh + (x + P)) * Chp;
+    float acc = b ? b[o] : 0.f;
+    for (int c = 0; c < Ch; ++c) acc += w[o * Ch + c] * load_elem<DT>(h, hb + c);
+    if constexpr (SEQ) pred[((head_image<true>(n, Bs, N / Bs) * O + o) * H + y) * W + x] = acc;
+    else pred[i] = acc;
+  }
+}
+
+template <int DT, bool SEQ>
+__global__ void head_fwd_wide_kernel(const void* __restrict__ h, int n0, int N, int Ch, int Chp, int O,
+                                     const float* __restrict__ w, const float* __restrict__ b, float* __restrict__ pred,
+                                     int H, int W, int P, int Hh, int Wh, int Bs) {
+  head_fwd_wide_body<DT, SEQ>(h, n0, N, Ch, Chp, O, w, b, pred, H, W, P, Hh, Wh, Bs);
+}
+
+// d loss / d (head output) of image n (time-major), output o, pixel yx, for the backward kernels below.  DpPlain: the (N, O, H, W)
+// tensor of the one-step entries.  DpSeq: dseq (B, T*O, H, W) and / or the cotangent of pred = head(h_{T-1}) (B, O, H, W), which
+// joins step T-1 here; either may be nullptr.
+struct DpPlain {
+  const float* __restrict__ p; int O; size_t HW;
+  __device__ __forceinline__ float operator()(size_t n, int o, size_t yx) const { return p[(n * O + o) * HW + yx]; }
+};
+struct DpSeq {
+  const float* __restrict__ dseq; const float* __restrict__ dlast; int O, B, T; size_t HW;
+  __device__ __forceinline__ float operator()(size_t n, int o, size_t yx) const {
+    const size_t t = n / (size_t)B, b = n - t * B;
+    float d = dseq ? dseq[((b * T + t) * O + o) * HW + yx] : 0.f;
+    if (dlast && t == (size_t)(T - 1)) d += dlast[(b * O + o) * HW + yx];
+    return d;
+  }
+};
+// the functor of a backward kernel instance, built inside the kernel from its __restrict__ pointer arguments
+template <bool SEQ>
+__device__ __forceinline__ auto head_dp(const float* __restrict__ dpred, const float* __restrict__ dlast, int O, int Bs, int T, size_t HW) {
+  if constexpr (SEQ) return DpSeq{dpred, dlast, O, Bs, T, HW};
+  else return DpPlain{dpred, O, HW};
+}
+
+// dh[n][y][x][c] = sum_o w[o][c] * dpred[n][o][y][x].  One thread per pixel (dpred planes read coalesced
+// along x, weights wave-uniform), the padded channel vector is written with 16-byte stores.
+template <int DT, int CHV, class Dp>
+__device__ __forceinline__ void head_bwd_dh_body(float* w_s, const float* __restrict__ w, const Dp dpred,
+                                                 void* __restrict__ dh, int N, int Ch, int Chp, int O, int H, int W) {
+  head_stage_weights<CHV>(w_s, w, O, Ch);
+  const size_t npix = (size_t)N * H * W;
+  const size_t pix = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+  if (pix >= npix) return;
+  const size_t yx = pix % ((size_t)H * W);
+  const size_t n = pix / ((size_t)H * W);
+  float acc[CHV];
+#pragma unroll
+  for (int c = 0; c < CHV; ++c) acc[c] = 0.f;
+  for (int o = 0; o < O; ++o) {
+    const float d = dpred(n, o, yx);
+    const f32x4_t* wr = (const f32x4_t*)(w_s + o * CHV);
+#pragma unroll
+    for (int c = 0; c < CHV; c += 4) {
+      const f32x4_t wv = wr[c / 4];
+      acc[c] += wv[0] * d; acc[c + 1] += wv[1] * d; acc[c + 2] += wv[2] * d; acc[c + 3] += wv[3] * d;
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < CHV; c += 4)
+    if (c < Chp) store_vec4<DT>(dh, pix * Chp + c, (f32x4_t){acc[c], acc[c + 1], acc[c + 2], acc[c + 3]});
+}
+
+template <int DT, int CHV, bool SEQ>
+__global__ __launch_bounds__(256) void head_bwd_dh_kernel(const float* __restrict__ w, const float* __restrict__ dpred,
+                                                          const float* __restrict__ dlast, int Bs, int T,
+                                                          void* __restrict__ dh, int N, int Ch, int Chp, int O, int H, int W) {
+  extern __shared__ __attribute__((aligned(16))) char smem_hd[];
+  head_bwd_dh_body<DT, CHV>((float*)smem_hd, w, head_dp<SEQ>(dpred, dlast, O, Bs, T, (size_t)H * W), dh, N, Ch, Chp, O, H, W);
+}
+
+template <int DT, class Dp>
+__device__ __forceinline__ void head_bwd_dh_wide_body(const float* __restrict__ w, const Dp dpred, void* __restrict__ dh,
+                                                      int N, int Ch, int Chp, int O, int H, int W) {
+  const size_t total = (size_t)N * H * W * Chp;
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int c = i % Chp;
+    const size_t pix = i / Chp;
+    const size_t yx = pix % ((size_t)H * W);
+    const int n = pix / ((size_t)H * W);
+    float acc = 0.f;
+    if (c < Ch)
+      for (int o = 0; o < O; ++o) acc += w[o * Ch + c] * dpred((size_t)n, o, yx);
+    store_elem<DT>(dh, i, acc);
+  }
+}
+
+template <int DT, bool SEQ>
+__global__ void head_bwd_dh_wide_kernel(const float* __restrict__ w, const float* __restrict__ dpred,
+                                        const float* __restrict__ dlast, int Bs, int T, void* __restrict__ dh,
+                                        int N, int Ch, int Chp, int O, int H, int W) {
+  head_bwd_dh_wide_body<DT>(w, head_dp<SEQ>(dpred, dlast, O, Bs, T, (size_t)H * W), dh, N, Ch, Chp, O, H, W);
+}
+
+// dw[o][c] = sum_pixels dpred*h ; db[o] = sum dpred.  One workgroup per (o, c-or-bias) output,
+// fixed-order tree reduction -> bitwise reproducible.
+template <int DT, class Dp>
+__device__ __forceinline__ void head_bwd_dw_body(const void* __restrict__ h, int n0, int N, int Ch, int Chp,
+                                                 int O, const Dp dpred,
+                                                 float* __restrict__ dw, float* __restrict__ db, int H, int W,
+                                                 int P, int Hh, int Wh) {
+  const int o = blockIdx.x / (Ch + 1);
+  const int c = blockIdx.x % (Ch + 1);   // c == Ch -> bias
+  const size_t npix = (size_t)N * H * W;
+  float acc = 0.f;
+  for (size_t i = threadIdx.x; i < npix; i += blockDim.x) {
+    const int x = i % W;
+    size_t r = i / W;
+    const int y = r % H;
+    const int n = r / H;
+    const float d = dpred((size_t)n, o, (size_t)y * W + x);
+    if (c < Ch) {
+      const size_t hb = ((((size_t)(n0 + n)) * Hh + (y + P)) * Wh + (x + P)) * Chp + c;
+      acc += d * load_elem<DT>(h, hb);
+    } else {
+      acc += d;
+    }
+  }
+  __shared__ float red[256];
+  red[threadIdx.x] = acc;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    if (c < Ch) dw[o * Ch + c] = red[0];
+    else db[o] = red[0];
+  }
+}
+
+template <int DT, bool SEQ>
+__global__ __launch_bounds__(256) void head_bwd_dw_kernel(const void* __restrict__ h, int n0, int N, int Ch, int Chp,
+                                                          int O, const float* __restrict__ dpred,
+                                                          const float* __restrict__ dlast, int Bs, int T,
+                                                          float* __restrict__ dw, float* __restrict__ db, int H, int W,
+                                                          int P, int Hh, int Wh) {
+  head_bwd_dw_body<DT>(h, n0, N, Ch, Chp, O, head_dp<SEQ>(dpred, dlast, O, Bs, T, (size_t)H * W), dw, db, H, W, P, Hh, Wh);
+}
+
+// Tiled path (O*(Ch+1) <= HEAD_DW_NK*512 outputs): every workgroup owns a pixel range, stages `stage` pixels of dpred and
+// h in LDS at a time (ONE HBM round trip per stage: the launch is latency-bound, 14 MB in all for the bench's head), thread
+// i accumulates the outputs i, i+512, ... over the range; per-workgroup partials are folded in fixed order by
+// head_bwd_dw_final_kernel.  The grid is one workgroup per HEAD_DW_PIX pixels, as far as the caller's scratch goes.
+// (Wide heads -- 128 hidden channels, or 200 outputs -- used to fall to head_bwd_dw_kernel: one workgroup per output walking
+// every pixel with a 4-byte strided read, 2.5 ms per step for configs[3].)
+#define HEAD_DW_PIX 240
+#define HEAD_DW_NK 8
+#define HEAD_DW_LDS_FLOATS (15 * 1024)
+template <int DT, class Dp>
+__device__ __forceinline__ void head_bwd_dw_tiled_body(float* smem_dw, const void* __restrict__ h, int n0, int N, int Ch, int Chp,
+                                                       int O, const Dp dpred,
+                                                       float* __restrict__ partial, int H, int W, int P, int Hh,
+                                                       int Wh, int stage) {
+  const int SO = O | 1, SC = (Ch + 1) | 1;     // odd row strides: the staging writes walk pixels without bank conflicts
+  float* sd = smem_dw;                         // [pixel][o]
+  float* sh = smem_dw + stage * SO;            // [pixel][c] + a constant 1 for the bias column
+  const int nout = O * (Ch + 1);
+  int oo_[HEAD_DW_NK], cc_[HEAD_DW_NK];
+  float acc[HEAD_DW_NK];
+#pragma unroll
+  for (int k = 0; k < HEAD_DW_NK; ++k) {
+    const int i = min((int)threadIdx.x + 512 * k, nout - 1);
+    oo_[k] = i / (Ch + 1); cc_[k] = i % (Ch + 1); acc[k] = 0.f;
+  }
+  const int nk = (nout + 511) / 512;
+  const size_t npix = (size_t)N * H * W;
+  const size_t per = (npix + gridDim.x - 1) / gridDim.x;
+  const size_t p0 = blockIdx.x * per, p1 = min(npix, p0 + per);
+  const int nq = (Ch + 3) / 4;                 // channel quads of a pixel (Chp is a multiple of 16: the vector load stays inside)
+  for (size_t base = p0; base < p1; base += stage) {
+    const int cnt = (int)min((size_t)stage, p1 - base);
+    __syncthreads();
+    for (int i = threadIdx.x; i < cnt * O; i += 512) {        // dpred planes: consecutive threads walk consecutive pixels
+      const int oo = i / cnt, pp = i - oo * cnt;
+      const size_t pix = base + pp;
+      const size_t yx = pix % ((size_t)H * W);
+      const size_t n = pix / ((size_t)H * W);
+      sd[pp * SO + oo] = dpred(n, oo, yx);
+    }
+    for (int i = threadIdx.x; i < cnt * nq; i += 512) {       // h: one 4-channel vector per thread
+      const int pp = i / nq, q = i - pp * nq;
+      const size_t pix = base + pp;
+      const int x = pix % W;
+      size_t r = pix / W;
+      const int y = r % H;
+      const int n = r / H;
+      const f32x4_t v = load_vec4<DT>(h, ((((size_t)(n0 + n)) * Hh + (y + P)) * Wh + (x + P)) * Chp + 4 * q);
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (4 * q + e < Ch) sh[pp * SC + 4 * q + e] = v[e];
+      if (q == 0) sh[pp * SC + Ch] = 1.f;
+    }
+    __syncthreads();
+    if (nk == 1) {
+      if ((int)threadIdx.x < nout) {
+#pragma unroll 8
+        for (int pp = 0; pp < cnt; ++pp) acc[0] += sd[pp * SO + oo_[0]] * sh[pp * SC + cc_[0]];
+      }
+    } else {
+      for (int pp = 0; pp < cnt; ++pp) {
+#pragma unroll
+        for (int k = 0; k < HEAD_DW_NK; ++k)
+          if (k < nk) acc[k] += sd[pp * SO + oo_[k]] * sh[pp * SC + cc_[k]];
+      }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < HEAD_DW_NK; ++k)
+    if ((int)threadIdx.x + 512 * k < nout) partial[(size_t)blockIdx.x * nout + threadIdx.x + 512 * k] = acc[k];
+}
+
+template <int DT, bool SEQ>
+__global__ __launch_bounds__(512) void head_bwd_dw_tiled_kernel(const void* __restrict__ h, int n0, int N, int Ch, int Chp,
+                                                              int O, const float* __restrict__ dpred,
+                                                              const float* __restrict__ dlast, int Bs, int T,
+                                                              float* __restrict__ partial, int H, int W, int P, int Hh,
+                                                              int Wh, int stage) {
+  extern __shared__ __attribute__((aligned(16))) float smem_dw[];
+  head_bwd_dw_tiled_body<DT>(smem_dw, h, n0, N, Ch, Chp, O, head_dp<SEQ>(dpred, dlast, O, Bs, T, (size_t)H * W), partial, H, W, P, Hh, Wh, stage);
+}
+
+// Larger heads (more than 512 outputs, and the smaller of O and Ch + 1 at most 32 -- 200 outputs x 16 channels, or 20 x
+// 128): REGISTER-tiled.  The smaller dimension ("R") lives in registers, a thread owns one index of the larger one ("T")
+// and NH = 512 / T pixel strides: per staged pixel it reads its own T value once and the R values as broadcast 16-byte reads
+// -- 1 + R/4 LDS instructions per R FMAs instead of 2 per FMA.  The NH partial sums of an output are folded through LDS in
+// fixed order; the slab layout is head_bwd_dw_tiled_kernel's.
+template <int DT, class Dp>
+__device__ __forceinline__ void head_bwd_dw_rtile_body(float* smem_dw, const void* __restrict__ h, int n0, int N, int Ch, int Chp,
+                                                       int O, const Dp dpred,
+                                                       float* __restrict__ partial, int H, int W, int P, int Hh,
+                                                       int Wh, int stage) {
+  const int C1 = Ch + 1;
+  const bool r_is_c = C1 <= O;                 // registers over the channels (+ bias), threads over the outputs -- or the other way round
+  const int R = r_is_c ? C1 : O, T = r_is_c ? O : C1;
+  const int SR = (R + 3) & ~3, ST = T | 1;     // row strides: 16-byte rows for the broadcast reads, odd for the per-thread ones
+  float* sr = smem_dw;                         // [pixel][R]
+  float* st = smem_dw + stage * SR;            // [pixel][T]
+  float* sd = r_is_c ? st : sr;                // dpred [pixel][o]
+  float* sh = r_is_c ? sr : st;                // h     [pixel][c] + 1
+  const int SD = r_is_c ? ST : SR, SH = r_is_c ? SR : ST;
+  const int nout = O * C1;
+  const int NH = min(8, 512 / T);
+  const int ti = threadIdx.x % T, hf = threadIdx.x / T;
+  const bool act = hf < NH;
+  float acc[32];
+#pragma unroll
+  for (int r = 0; r < 32; ++r) acc[r] = 0.f;
+  const size_t npix = (size_t)N * H * W;
+  const size_t per = (npix + gridDim.x - 1) / gridDim.x;
+  const size_t p0 = blockIdx.x * per, p1 = min(npix, p0 + per);
+  const int nq = (Ch + 3) / 4;
+  for (size_t base = p0; base < p1; base += stage) {
+    const int cnt = (int)min((size_t)stage, p1 - base);
+    __syncthreads();
+    for (int i = threadIdx.x; i < cnt * O; i += 512) {        // dpred planes: consecutive threads walk consecutive pixels
+      const int oo = i / cnt, pp = i - oo * cnt;
+      const size_t pix = base + pp;
+      const size_t yx = pix % ((size_t)H * W);
+      const size_t n = pix / ((size_t)H * W);
+      sd[pp * SD + oo] = dpred(n, oo, yx);
+    }
+    for (int i = threadIdx.x; i < cnt * nq; i += 512) {       // h: one 4-channel vector per thread
+      const int pp = i / nq, q = i - pp * nq;
+      const size_t pix = base + pp;
+      const int x = pix % W;
+      size_t r = pix / W;
+      const int y = r % H;
+      const int n = r / H;
+      const f32x4_t v = load_vec4<DT>(h, ((((size_t)(n0 + n)) * Hh + (y + P)) * Wh + (x + P)) * Chp + 4 * q);
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (4 * q + e < Ch) sh[pp * SH + 4 * q + e] = v[e];
+      if (q == 0) sh[pp * SH + Ch] = 1.f;
+    }
+    if (SR > R) for (int i = threadIdx.x; i < cnt; i += 512)   // the tail of the 16-byte rows feeds accumulators that are never stored: keep it finite
+      for (int r = R; r < SR; ++r) sr[i * SR + r] = 0.f;
+    __syncthreads();
+    if (act) {
+      for (int pp = hf; pp < cnt; pp += NH) {
+        const float tv = st[pp * ST + ti];
+        const f32x4_t* rr = (const f32x4_t*)(sr + pp * SR);
+#pragma unroll
+        for (int r4 = 0; r4 < 8; ++r4) {
+          if (4 * r4 < SR) {
+            const f32x4_t rv = rr[r4];
+            acc[4 * r4] += tv * rv[0]; acc[4 * r4 + 1] += tv * rv[1]; acc[4 * r4 + 2] += tv * rv[2]; acc[4 * r4 + 3] += tv * rv[3];
+          }
+        }
+      }
+    }
+  }
+  // fold the NH pixel strides of every output (fixed order) through LDS: red[hf][ti][r]
+  __syncthreads();
+  float* red = smem_dw;                        // NH * T * SR floats (the launch reserves the larger of this and the staging buffers)
+  if (act) {
+#pragma unroll
+    for (int r = 0; r < 32; ++r)
+      if (r < R) red[((size_t)hf * T + ti) * SR + r] = acc[r];
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < nout; i += 512) {
+    const int o = i / C1, c = i - o * C1;
+    const int t2 = r_is_c ? o : c, r2 = r_is_c ? c : o;
+    float s = 0.f;
+    for (int q = 0; q < NH; ++q) s += red[((size_t)q * T + t2) * SR + r2];
+    partial[(size_t)blockIdx.x * nout + i] = s;
+  }
+}
+
+template <int DT, bool SEQ>
+__global__ __launch_bounds__(512) void head_bwd_dw_rtile_kernel(const void* __restrict__ h, int n0, int N, int Ch, int Chp,
+                                                              int O, const float* __restrict__ dpred,
+                                                              const float* __restrict__ dlast, int Bs, int T,
+                                                              float* __restrict__ partial, int H, int W, int P, int Hh,
+                                                              int Wh, int stage) {
+  extern __shared__ __attribute__((aligned(16))) float smem_dw[];
+  head_bwd_dw_rtile_body<DT>(smem_dw, h, n0, N, Ch, Chp, O, head_dp<SEQ>(dpred, dlast, O, Bs, T, (size_t)H * W), partial, H, W, P, Hh, Wh, stage);
+}
+
+// block = 64 outputs x blockDim/64 lanes over the per-workgroup partials; fixed order
+__global__ void head_bwd_dw_final_kernel(const float* __restrict__ partial, int nblocks, int Ch, int O,
+                                         float* __restrict__ dw, float* __restrict__ db) {
+  __shared__ float red[1024];
+  const int i = blockIdx.x * 64 + (threadIdx.x & 63), sub = threadIdx.x >> 6, G = blockDim.x >> 6;
+  const int nout = O * (Ch + 1);
+  float s = 0.f;
+  if (i < nout) {
+#pragma unroll 4
+    for (int b = sub; b < nblocks; b += G) s += partial[(size_t)b * nout + i];
+  }
+  red[threadIdx.x] = s;
+  __syncthreads();
+  if (sub != 0 || i >= nout) return;
+  for (int q = 1; q < G; ++q) s += red[q * 64 + (threadIdx.x & 63)];
+  const int o = i / (Ch + 1), c = i % (Ch + 1);
+  if (c < Ch) dw[o * Ch + c] = s;
+  else db[o] = s;
+}
+
+// SEQ: the sequence entry (n0 = Bs = B, N = T*B, plane blocks b*T + t)
+template <bool SEQ>
+static int head_fwd_impl(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w, const float* b, float* pred,
+                         const nint_geom* g, int dtype, int Bs, void* stream) {
+  const size_t total = (size_t)N * O * g->H * g->W, npix = (size_t)N * g->H * g->W;
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 gp((unsigned)((npix + 255) / 256));
+  const size_t w_lds = (size_t)O * head_chv(Chp) * sizeof(float);      // staged weights [O][CHV]
+  nint_by_dtype(dtype, [&](auto dt) {
+    constexpr int DT = decltype(dt)::value;
+    if (Chp <= 128 && Chp % 4 == 0 && w_lds <= 64 * 1024)
+      head_by_chv(Chp, [&](auto chv) {
+        hipLaunchKernelGGL((head_fwd_kernel<DT, decltype(chv)::value, SEQ>), gp, dim3(256), w_lds, st, h_slab, n0, N, Ch, Chp, O, w, b, pred, g->H, g->W, g->P, g->Hh, g->Wh, Bs);
+      });
+    else
+      hipLaunchKernelGGL((head_fwd_wide_kernel<DT, SEQ>), grid1d(total), dim3(256), 0, st, h_slab, n0, N, Ch, Chp, O, w, b, pred, g->H, g->W, g->P, g->Hh, g->Wh, Bs);
+  });
+  NINT_LAUNCH_CHECK();
+  return NINT_OK;
+}
+
+extern "C" int nint_head_fwd(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w,
+                             const float* b, float* pred, const nint_geom* g, int dtype, void* stream) {
+  if (!h_slab || !w || !pred || !g || N <= 0 || O <= 0 || Ch <= 0) return NINT_E_ARG;
+  if (dtype != NINT_BF16 && dtype != NINT_F32) return NINT_E_ARG;
+  return head_fwd_impl<false>(h_slab, n0, N, Ch, Chp, O, w, b, pred, g, dtype, 0, stream);
+}
+
+// channel padding of a slab the head reads: KC of the storage type (nint.h), so every 16-byte channel vector stays inside
+static bool head_seq_args_ok(const void* h_slab, int B, int T, int Ch, int Chp, int O, const float* w, const nint_geom* g, int dtype) {
+  if (!h_slab || !w || !g || B <= 0 || T <= 0 || O <= 0 || Ch <= 0 || Chp < Ch) return false;
+  if (dtype != NINT_BF16 && dtype != NINT_F32) return false;
+  if (g->H <= 0 || g->W <= 0 || g->P < 0 || g->Hh < g->H + 2 * g->P || g->Wh < g->W + 2 * g->P) return false;
+  return Chp % (dtype == NINT_BF16 ? 32 : 16) == 0;
+}
+
+extern "C" int nint_head_fwd_seq(const void* h_slab, int B, int T, int Ch, int Chp, int O, const float* w, const float* b,
+                                 float* seq, const nint_geom* g, int dtype, void* stream) {
+  if (!seq || !head_seq_args_ok(h_slab, B, T, Ch, Chp, O, w, g, dtype)) return NINT_E_ARG;
+  if ((((uintptr_t)h_slab) & 15) != 0) return NINT_E_ALIGN;
+  return head_fwd_impl<true>(h_slab, B, T * B, Ch, Chp, O, w, b, seq, g, dtype, B, stream);     // h_t = slot t + 1: images from B
+}
+
+// SEQ: d loss / d (head output) comes from the sequence tensors (DpSeq: dpred = dseq, dlast, Bs = B, T) instead of dpred alone
+template <bool SEQ>
+static int head_bwd_impl(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w, const float* dpred,
+                         const float* dlast, int Bs, int T, void* dh, float* dw, float* db, const nint_geom* g, int dtype,
+                         float* scratch, size_t scratch_bytes, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  const size_t npix = (size_t)N * g->H * g->W;
+  if (dh) {
+    const dim3 gp((unsigned)((npix + 255) / 256));
+    const size_t w_lds = (size_t)O * head_chv(Chp) * sizeof(float);    // staged weights [O][CHV]
+    nint_by_dtype(dtype, [&](auto dt) {
+      constexpr int DT = decltype(dt)::value;
+      if (w_lds > 64 * 1024 || Chp > 128 || Chp % 4 != 0)
+        hipLaunchKernelGGL((head_bwd_dh_wide_kernel<DT, SEQ>), grid1d(npix * Chp), dim3(256), 0, st, w, dpred, dlast, Bs, T, dh, N, Ch, Chp, O, g->H, g->W);
+      else
+        head_by_chv(Chp, [&](auto chv) {
+          hipLaunchKernelGGL((head_bwd_dh_kernel<DT, decltype(chv)::value, SEQ>), gp, dim3(256), w_lds, st, w, dpred, dlast, Bs, T, dh, N, Ch, Chp, O, g->H, g->W);
+        });
+    });
+    NINT_LAUNCH_CHECK();
+  }
+  if (!dw || !db) return NINT_OK;
+  const int nout = O * (Ch + 1);
+  const int row_floats = (O | 1) + ((Ch + 1) | 1);
+  const int Rd = O < Ch + 1 ? O : Ch + 1, Td = O < Ch + 1 ? Ch + 1 : O;      // register / thread dimension of the register-tiled kernel
+  // the two-stage paths: per-workgroup partials in the caller's scratch (stage = pixels staged in LDS at a time), then the fold
+  int stage = 0;
+  size_t lds = 0;
+  bool rtile = false;
+  if (scratch && nout > 512 && Rd <= 32 && Td <= 512 && scratch_bytes >= (size_t)256 * nout * sizeof(float)) {
+    const int SR = (Rd + 3) & ~3, ST = Td | 1, NH = 512 / Td < 8 ? 512 / Td : 8;
+    stage = HEAD_DW_LDS_FLOATS / (SR + ST);
+    if (stage > HEAD_DW_PIX) stage = HEAD_DW_PIX;
+    size_t lds_f = (size_t)stage * (SR + ST);
+    if ((size_t)NH * Td * SR > lds_f) lds_f = (size_t)NH * Td * SR;            // the closing fold's buffer
+    lds = lds_f * sizeof(float);
+    rtile = stage >= 8 && lds <= 64 * 1024;
+  }
+  const bool tiled = !rtile && scratch && nout <= HEAD_DW_NK * 512 && 8 * row_floats <= HEAD_DW_LDS_FLOATS &&
+                     scratch_bytes >= (size_t)256 * nout * sizeof(float);
+  if (tiled) {
+    stage = HEAD_DW_LDS_FLOATS / row_floats;                   // pixels staged at a time (60 KiB of LDS)
+    if (stage > HEAD_DW_PIX) stage = HEAD_DW_PIX;
+    lds = (size_t)stage * row_floats * sizeof(float);
+  }
+  if (rtile || tiled) {
+    const size_t cap = scratch_bytes / ((size_t)nout * sizeof(float));
+    const size_t want = (npix + HEAD_DW_PIX - 1) / HEAD_DW_PIX;
+    const int nblk = (int)(want < cap ? want : cap);
+    nint_by_dtype(dtype, [&](auto dt) {
+      constexpr int DT = decltype(dt)::value;
+      auto kern = rtile ? head_bwd_dw_rtile_kernel<DT, SEQ> : head_bwd_dw_tiled_kernel<DT, SEQ>;
+      hipLaunchKernelGGL(kern, dim3(nblk), dim3(512), lds, st, h_slab, n0, N, Ch, Chp, O, dpred, dlast, Bs, T, scratch, g->H, g->W, g->P, g->Hh, g->Wh, stage);
+    });
+    NINT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(head_bwd_dw_final_kernel, dim3(nint_cdiv(nout, 64)), dim3(1024), 0, st, scratch, nblk, Ch, O, dw, db);
+  } else {
+    nint_by_dtype(dtype, [&](auto dt) {
+      hipLaunchKernelGGL((head_bwd_dw_kernel<decltype(dt)::value, SEQ>), dim3(O * (Ch + 1)), dim3(256), 0, st, h_slab, n0, N, Ch, Chp, O, dpred, dlast, Bs, T, dw, db, g->H, g->W, g->P, g->Hh, g->Wh);
+    });
+  }
+  NINT_LAUNCH_CHECK();
+  return NINT_OK;
+}
+
+extern "C" int nint_head_bwd(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w,
+                             const float* dpred, void* dh, float* dw, float* db, const nint_geom* g, int dtype,
+                             float* scratch, size_t scratch_bytes, void* stream) {
+  if (!h_slab || !w || !dpred || !g || N <= 0 || O <= 0 || Ch <= 0) return NINT_E_ARG;
+  if (dtype != NINT_BF16 && dtype != NINT_F32) return NINT_E_ARG;
+  return head_bwd_impl<false>(h_slab, n0, N, Ch, Chp, O, w, dpred, nullptr, 0, 0, dh, dw, db, g, dtype, scratch, scratch_bytes, stream);
+}
+
+extern "C" int nint_head_bwd_seq(const void* h_slab, int B, int T, int Ch, int Chp, int O, const float* w, const float* dseq,
+                                 const float* dpred_last, void* dh_seq, float* dw, float* db, const nint_geom* g, int dtype,
+                                 float* scratch, size_t scratch_bytes, void* stream) {
+  if (!head_seq_args_ok(h_slab, B, T, Ch, Chp, O, w, g, dtype)) return NINT_E_ARG;
+  if ((!dseq && !dpred_last) || (!dw) != (!db) || (!dh_seq && !dw)) return NINT_E_ARG;
+  if (((((uintptr_t)h_slab) | ((uintptr_t)dh_seq)) & 15) != 0) return NINT_E_ALIGN;
+  return head_bwd_impl<true>(h_slab, B, T * B, Ch, Chp, O, w, dseq, dpred_last, B, T, dh_seq, dw, db, g, dtype, scratch, scratch_bytes, stream);
+}
+
+// ------------------------------------------------------------------------------ loss
+// train.py:102,105: crop, MSELoss + L1Loss (mean).  Two launches on the same stream:
+//  (1) per-block partial sums in double (fixed order), (2) one block folds them, writes
+//  the loss and adds to the 5 running statistics.  dpred = (2(p-y) + sign(p-y)) / n on the crop.
+__global__ __launch_bounds__(1024) void loss_partial_kernel(const float* __restrict__ pred, const float* __restrict__ y,
+                                                           float* __restrict__ dpred, double* __restrict__ partial,
+                                                           int N, int O, int H, int W, int oy, int ox, int Hc, int Wc) {
+  const size_t total = (size_t)N * O * H * W;
+  const double inv_n = 1.0 / ((double)N * O * Hc * Wc);
+  double s2 = 0, s1 = 0, sy = 0, syy = 0;
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int x = i % W;
+    size_t r = i / W;
+    const int yy = r % H;
+    const size_t no = r / H;
+    const int cy = yy - oy, cx = x - ox;
+    float g = 0.f;
+    if (cy >= 0 && cy < Hc && cx >= 0 && cx < Wc) {
+      const float t = y[(no * Hc + cy) * Wc + cx];
+      const float d = pred[i] - t;
+      s2 += (double)d * d;
+      s1 += fabs((double)d);
+      sy += t;
+      syy += (double)t * t;
+      g = (float)((2.0 * d + (d > 0.f ? 1.0 : (d < 0.f ? -1.0 : 0.0))) * inv_n);
+    }
+    if (dpred) dpred[i] = g;
+  }
+  __shared__ double red[4][1024];
+  red[0][threadIdx.x] = s2; red[1][threadIdx.x] = s1; red[2][threadIdx.x] = sy; red[3][threadIdx.x] = syy;
+  __syncthreads();
+  for (int s = blockDim.x >> 1; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s)
+      for (int q = 0; q < 4; ++q) red[q][threadIdx.x] += red[q][threadIdx.x + s];
+    __syncthreads();
+  }
+  if (threadIdx.x < 4) partial[blockIdx.x * 4 + threadIdx.x] = red[threadIdx.x][0];
+}
+
+__global__ __launch_bounds__(256) void loss_final_kernel(const double* __restrict__ partial, int nblocks, float* __restrict__ loss_out,
+                                                         double* __restrict__ stats, double count) {
+  // thread (b, q) = one partial; fixed-order tree over the blocks
+  __shared__ double red[4][256];
+  for (int q = 0; q < 4; ++q) {
+    double s = 0;
+    for (int b = threadIdx.x; b < nblocks; b += blockDim.x) s += partial[b * 4 + q];
+    red[q][threadIdx.x] = s;
+  }
+  __syncthreads();
+  for (int st = 128; st > 0; st >>= 1) {
+    if ((int)threadIdx.x < st)
+      for (int q = 0; q < 4; ++q) red[q][threadIdx.x] += red[q][threadIdx.x + st];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const double s0 = red[0][0], s1 = red[1][0], s2 = red[2][0], s3 = red[3][0];
+    const double loss = s0 / count + s1 / count;
+    if (loss_out) loss_out[0] = (float)loss;
+    if (stats) {
+      stats[0] += s0; stats[1] += s1; stats[2] += s2; stats[3] += s3; stats[4] += count;
+      // the reference's per-batch statistics (train.py:113-117, utils.py:73-75): it sums loss.item() and
+      // sklearn r2_score(y, pred) of every batch and divides by the number of batches
+      const double ss_tot = s3 - s2 * s2 / count;
+      const double r2 = ss_tot > 0.0 ? 1.0 - s0 / ss_tot : (s0 == 0.0 ? 1.0 : 0.0);   // sklearn's constant-target convention
+      stats[5] += loss; stats[6] += r2; stats[7] += 1.0;
+    }
+  }
+}
+
+// partial sums live in a small static device buffer per call site: the caller passes it as the
+// tail of `stats` would complicate the ABI, so the kernel pair uses dpred-independent scratch
+// carved from loss_out[1..]: loss_out must have room for 1 + 2*LOSS_BLOCKS*4 floats.
+#define LOSS_BLOCKS 256
+#define LOSS_BLOCKS_MAX ((NINT_LOSS_SCRATCH_FLOATS - 2) / 8)     // what the caller's scratch holds: 4 doubles per workgroup
+extern "C" int nint_loss_mse_l1_crop(const float* pred, const float* y, float* dpred, float* loss_out, double* stats,
+                                     int N, int O, int H, int W, int oy, int ox, int Hc, int Wc, void* stream) {
+  if (!pred || !y || !loss_out || N <= 0 || O <= 0 || oy < 0 || ox < 0 || oy + Hc > H || ox + Wc > W) return NINT_E_ARG;
+  if ((((uintptr_t)loss_out) & 7) != 0) return NINT_E_ALIGN;
+  hipStream_t st = (hipStream_t)stream;
+  double* partial = (double*)(loss_out + 2);   // loss_out: [0]=loss, [1]=pad, [2..] = 256*4 doubles
+  hipLaunchKernelGGL(loss_partial_kernel, dim3(LOSS_BLOCKS), dim3(1024), 0, st, pred, y, dpred, partial, N, O, H, W, oy, ox, Hc, Wc);
+  NINT_LAUNCH_CHECK();
+  hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(256), 0, st, partial, LOSS_BLOCKS, loss_out, stats, (double)N * O * Hc * Wc);
+  NINT_LAUNCH_CHECK();
+  return NINT_OK;
+}
+
+// ------------------------------------------------------------------------------ head + loss, fused (training)
+// train.py:96-109 around the 1x1 head in ONE pass over the pixels: pred = w . h + b (model.py:274), crop, the MSE+L1
+// partial sums (train.py:102,105), d loss / d pred, and dL/dh = w^T . dpred.  One thread per pixel (grid-stride):
+// the channel vector is read once, pred never goes to memory, dpred is written for the head's weight gradient.
+// Same arithmetic, in the same order, as head_fwd_kernel -> loss_partial_kernel -> head_bwd_dh_kernel.
+#define HEAD_OCH 64
+// SEQ (nint_head_loss_seq_fused): the images are all T*B steps of the slab, image n = t*B + b; the targets are (B, T, O, Hc, Wc),
+// plane block b*T + t (head_image); dpred and dh stay in image order, which is what the weight-gradient stage and BPTT read.
+template <int DT, int CHV, bool SEQ>
+__device__ __forceinline__ void head_loss_fused_body(char* smem_hl, const void* __restrict__ h, int n0, int N, int Ch, int Chp, int O,
+                                                     const float* __restrict__ w, const float* __restrict__ b,
+                                                     const float* __restrict__ y, float* __restrict__ dpred,
+                                                     void* __restrict__ dh, double* __restrict__ partial, int H, int W,
+                                                     int P, int Hh, int Wh, int oy, int ox, int Hc, int Wc, int Bs) {
+  // A workgroup takes 64 pixels per pass (grid-stride).  Phase 1: wave q runs the outputs [q*OG, (q+1)*OG) of every pixel
+  // (lane = pixel): pred, loss terms, d loss / d pred -> dpred and, through LDS, to phase 2: wave q accumulates the
+  // channels [q*CHV/4, (q+1)*CHV/4) of dL/dh over ALL outputs in output order.  (One thread per pixel for all outputs --
+  // the first version -- is a chain of O dependent round trips on 1/4 of the threads: 50 us at B = 8, 44 us at B = 1.)
+  float* w_s = (float*)smem_hl;                  // [O][CHV], zero padded (head_stage_weights)
+  float* gq_s = w_s + O * CHV;                   // [min(O, HEAD_OCH)][64]
+  head_stage_weights<CHV>(w_s, w, O, Ch);
+  const int lane = threadIdx.x & 63;
+  const int q = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // (scalar: the weight reads below stay scalar loads)
+  const size_t npix = (size_t)N * H * W;
+  const double inv_n = 1.0 / ((double)N * O * Hc * Wc);
+  constexpr int CQ = CHV / 4;                    // channels per wave in phase 2
+  double s2 = 0, s1 = 0, sy = 0, syy = 0;
+  for (size_t p0 = (size_t)blockIdx.x * 64; p0 < npix; p0 += (size_t)gridDim.x * 64) {
+    const size_t pix = p0 + lane;
+    const bool live = pix < npix;
+    const size_t pc = live ? pix : npix - 1;
+    const int x = pc % W;
+    size_t r = pc / W;
+    const int yy = r % H;
+    const int n = r / H;
+    const size_t hb = ((((size_t)(n0 + n)) * Hh + (yy + P)) * Wh + (x + P)) * Chp;
+    float hv[CHV];
+#pragma unroll
+    for (int c = 0; c < CHV; c += 4) {
+      const f32x4_t v = (c < Chp) ? load_vec4<DT>(h, hb + c) : (f32x4_t){0.f, 0.f, 0.f, 0.f};
+      hv[c] = v[0]; hv[c + 1] = v[1]; hv[c + 2] = v[2]; hv[c + 3] = v[3];
+    }
+    const int cy = yy - oy, cx = x - ox;
+    const bool in = live && cy >= 0 && cy < Hc && cx >= 0 && cx < Wc;
+    float* dp = dpred + ((size_t)n * O * H + yy) * W + x;
+    const float* yp = y + (head_image<SEQ>(n, Bs, N / (SEQ ? Bs : 1)) * O * Hc + cy) * Wc + cx;
+    float acc[CQ];
+#pragma unroll
+    for (int c = 0; c < CQ; ++c) acc[c] = 0.f;
+    const int c0 = q * CQ;
+    // the outputs in chunks of HEAD_OCH (d loss / d pred of one chunk in LDS at a time: 200 outputs would otherwise pin the
+    // workgroup count per CU at one); phase 2 keeps accumulating in output order across the chunks
+    for (int oc = 0; oc < O; oc += HEAD_OCH) {
+      const int on = min(HEAD_OCH, O - oc);
+      const int OG = (on + 3) / 4, ob = oc + q * OG, oe = min(oc + on, ob + OG);
+      if (oc > 0) __syncthreads();               // the previous chunk is consumed
+      constexpr int OU = 5;                      // targets fetched ahead of their use: one HBM round trip per OU outputs
+      for (int o0 = ob; o0 < oe; o0 += OU) {
+        float tq[OU];
+#pragma unroll
+        for (int u = 0; u < OU; ++u) tq[u] = (in && o0 + u < oe) ? yp[(size_t)(o0 + u) * Hc * Wc] : 0.f;
+#pragma unroll
+        for (int u = 0; u < OU; ++u) {
+          const int o = o0 + u;
+          if (o >= oe) break;
+          float p = b ? b[o] : 0.f;
+          const f32x4_t* wr = (const f32x4_t*)(w_s + o * CHV);
+#pragma unroll
+          for (int c = 0; c < CHV; c += 4) {
+            const f32x4_t wv = wr[c / 4];
+            p += wv[0] * hv[c]; p += wv[1] * hv[c + 1]; p += wv[2] * hv[c + 2]; p += wv[3] * hv[c + 3];
+          }
+          float gq = 0.f;
+          if (in) {
+            const float t = tq[u];
+            const float d = p - t;
+            s2 += (double)d * d;
+            s1 += fabs((double)d);
+            sy += t;
+            syy += (double)t * t;
+            gq = (float)((2.0 * d + (d > 0.f ? 1.0 : (d < 0.f ? -1.0 : 0.0))) * inv_n);
+          }
+          if (live) dp[(size_t)o * H * W] = gq;
+          gq_s[(o - oc) * 64 + lane] = gq;
+        }
+      }
+      __syncthreads();
+      // phase 2: dL/dh[c] = sum_o w[o][c] * gq[o], in output order (the order of head_bwd_dh_kernel)
+      for (int o = oc; o < oc + on; ++o) {
+        const float gq = gq_s[(o - oc) * 64 + lane];
+        const f32x4_t* wr = (const f32x4_t*)(w_s + o * CHV + c0);
+#pragma unroll
+        for (int c = 0; c < CQ; c += 4) {
+          const f32x4_t wv = wr[c / 4];
+          acc[c] += wv[0] * gq; acc[c + 1] += wv[1] * gq; acc[c + 2] += wv[2] * gq; acc[c + 3] += wv[3] * gq;
+        }
+      }
+    }
+    if (live) {
+#pragma unroll
+      for (int c = 0; c < CQ; c += 4)
+        if (c0 + c < Chp) store_vec4<DT>(dh, pix * Chp + c0 + c, (f32x4_t){acc[c], acc[c + 1], acc[c + 2], acc[c + 3]});
+    }
+    __syncthreads();                             // gq_s is rewritten by the next pass
+  }
+  __shared__ double red[4][256];
+  red[0][threadIdx.x] = s2; red[1][threadIdx.x] = s1; red[2][threadIdx.x] = sy; red[3][threadIdx.x] = syy;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s)
+      for (int q2 = 0; q2 < 4; ++q2) red[q2][threadIdx.x] += red[q2][threadIdx.x + s];
+    __syncthreads();
+  }
+  if (threadIdx.x < 4) partial[blockIdx.x * 4 + threadIdx.x] = red[threadIdx.x][0];
+}
+
+template <int DT, int CHV, bool SEQ>
+__global__ __launch_bounds__(256) void head_loss_fused_kernel(const void* __restrict__ h, int n0, int N, int Ch, int Chp, int O,
+                                                              const float* __restrict__ w, const float* __restrict__ b,
+                                                              const float* __restrict__ y, float* __restrict__ dpred,
+                                                              void* __restrict__ dh, double* __restrict__ partial, int H, int W,
+                                                              int P, int Hh, int Wh, int oy, int ox, int Hc, int Wc, int Bs) {
+  extern __shared__ __attribute__((aligned(16))) char smem_hl[];
+  head_loss_fused_body<DT, CHV, SEQ>(smem_hl, h, n0, N, Ch, Chp, O, w, b, y, dpred, dh, partial, H, W, P, Hh, Wh, oy, ox, Hc, Wc, Bs);
+}
+
+// SEQ: the sequence entry (n0 = Bs = B, N = T*B)
+template <bool SEQ>
+static int head_loss_fused_impl(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w, const float* b,
+                                const float* y, float* dpred, void* dh, float* loss_out, double* stats, const nint_geom* g,
+                                int oy, int ox, int Hc, int Wc, int dtype, int Bs, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  double* partial = (double*)(loss_out + 2);   // loss_out: [0]=loss, [1]=pad, [2..] = up to LOSS_BLOCKS_MAX*4 doubles
+  // 64 pixels per workgroup and pass: up to LOSS_BLOCKS_MAX workgroups
+  const size_t npix = (size_t)N * g->H * g->W;
+  const int nblk = (int)((npix + 63) / 64 < LOSS_BLOCKS_MAX ? (npix + 63) / 64 : LOSS_BLOCKS_MAX);
+  const size_t lds = ((size_t)O * head_chv(Chp) + (size_t)(O < HEAD_OCH ? O : HEAD_OCH) * 64) * sizeof(float);   // weights [O][CHV] + d loss / d pred of 64 pixels, one output chunk
+  if (lds + 8192 > 160 * 1024) return NINT_E_SHAPE;
+  const int rc = nint_by_dtype(dtype, [&](auto dt) { return head_by_chv(Chp, [&](auto chv) -> int {
+    auto kern = head_loss_fused_kernel<decltype(dt)::value, decltype(chv)::value, SEQ>;
+    if (lds + 8192 > 64 * 1024) NINT_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kern, dim3(nblk), dim3(256), lds, st, h_slab, n0, N, Ch, Chp, O, w, b, y, dpred, dh, partial, g->H, g->W, g->P, g->Hh, g->Wh, oy, ox, Hc, Wc, Bs);
+    return NINT_OK; }); });
+  if (rc != NINT_OK) return rc;
+  NINT_LAUNCH_CHECK();
+  hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(256), 0, st, partial, nblk, loss_out, stats, (double)N * O * Hc * Wc);
+  NINT_LAUNCH_CHECK();
+  return NINT_OK;
+}
+
+extern "C" int nint_head_loss_fused(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w, const float* b,
+                                    const float* y, float* dpred, void* dh, float* loss_out, double* stats, const nint_geom* g,
+                                    int oy, int ox, int Hc, int Wc, int dtype, void* stream) {
+  if (!h_slab || !w || !y || !dpred || !dh || !loss_out || !g || N <= 0 || O <= 0 || Ch <= 0) return NINT_E_ARG;
+  if (oy < 0 || ox < 0 || oy + Hc > g->H || ox + Wc > g->W) return NINT_E_ARG;
+  if (dtype != NINT_BF16 && dtype != NINT_F32) return NINT_E_ARG;
+  if (Chp > 128 || Chp % 4) return NINT_E_SHAPE;   // wider heads: nint_head_fwd + nint_loss_mse_l1_crop + nint_head_bwd
+  if ((((uintptr_t)loss_out) & 7) != 0) return NINT_E_ALIGN;
+  return head_loss_fused_impl<false>(h_slab, n0, N, Ch, Chp, O, w, b, y, dpred, dh, loss_out, stats, g, oy, ox, Hc, Wc, dtype, 0, stream);
+}
+
+extern "C" int nint_head_loss_seq_fused(const void* h_slab, int B, int T, int Ch, int Chp, int O, const float* w, const float* b,
+                                        const float* y, float* dpred, void* dh_seq, float* loss_out, double* stats,
+                                        const nint_geom* g, int oy, int ox, int Hc, int Wc, int dtype, void* stream) {
+  if (!y || !dpred || !dh_seq || !loss_out || !head_seq_args_ok(h_slab, B, T, Ch, Chp, O, w, g, dtype)) return NINT_E_ARG;
+  if (oy < 0 || ox < 0 || Hc <= 0 || Wc <= 0 || oy + Hc > g->H || ox + Wc > g->W) return NINT_E_ARG;
+  if (Chp > 128) return NINT_E_SHAPE;              // wider heads: nint_head_fwd_seq + nint_loss_mse_l1_crop + nint_head_bwd_seq
+  if ((((uintptr_t)loss_out) & 7) != 0 || ((((uintptr_t)h_slab) | ((uintptr_t)dh_seq)) & 15) != 0) return NINT_E_ALIGN;
+  return head_loss_fused_impl<true>(h_slab, B, T * B, Ch, Chp, O, w, b, y, dpred, dh_seq, loss_out, stats, g, oy, ox, Hc, Wc, dtype, B, stream);
+}

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 #include "nint.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
@@ -41,6 +42,21 @@ template <> struct Elem<NINT_BF16> {
 
 __host__ __device__ inline int nint_round_up(int a, int b) { return (a + b - 1) / b * b; }
 __host__ __device__ inline int nint_cdiv(int a, int b) { return (a + b - 1) / b; }
+
+// Host side: pick a kernel's DT instance.  f is a generic lambda called with std::integral_constant<int, NINT_BF16 | NINT_F32>
+// (decltype(dt)::value is the template argument); the caller has checked dtype.
+template <class F> static inline auto nint_by_dtype(int dtype, F&& f) {
+  if (dtype == NINT_BF16) return f(std::integral_constant<int, NINT_BF16>{});
+  return f(std::integral_constant<int, NINT_F32>{});
+}
+
+// grid of a grid-stride kernel over n items
+static inline dim3 grid1d(size_t n, int block = 256) {
+  size_t g = (n + block - 1) / block;
+  if (g > 256 * 32) g = 256 * 32;   // grid-stride the rest (256 CUs x 32)
+  if (g < 1) g = 1;
+  return dim3((unsigned)g);
+}
 
 // float -> bf16 round-to-nearest-even; the plain cast lowers to v_cvt_pk_bf16_f32 on gfx950
 // and keeps NaN a NaN (MI355X_MICROARCH.md, correctness boundaries).

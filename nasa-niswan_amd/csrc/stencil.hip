@@ -39,7 +39,7 @@ struct StencilArgs {
 
 constexpr int ST_ROWS = 8, ST_COLS = 32, ST_HW = ST_COLS + 2, ST_HH = ST_ROWS + 2;
 
-// rows of the stencil weight image (shared with the packer in pointwise.hip through nint_common.h)
+// rows of the stencil weight image (shared with the packer in pack_weights.hip through nint_common.h)
 template <int DT>
 __global__ __launch_bounds__(256) void stencil_lstm_kernel(StencilArgs a_) {
   const StencilArgs& a0 = a_;

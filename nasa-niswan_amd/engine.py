@@ -317,15 +317,10 @@ class SeqEngine:
 
     def head_forward(self, ws: Workspace, w: torch.Tensor, b: Optional[torch.Tensor], slot: Optional[int] = None):
         """model.py:274: 1x1 conv on the last layer's hidden state of time step ``slot-1``."""
-        l = len(self.cfgs) - 1
-        cfg = self.cfgs[l]
-        Chp = cfg.padded(self.kc)[2]
-        O = w.shape[0]
+        Ch, Chp, O, w2, b2 = self._head_args(w, b)
         slot = ws.T if slot is None else slot
         pred = torch.empty(ws.B, O, ws.H, ws.W, dtype=torch.float32, device=self.device)
-        w2 = w.detach().float().contiguous()
-        b2 = None if b is None else b.detach().float().contiguous()
-        check(self.lib.nint_head_fwd(ptr(ws.h[l]), slot * ws.B, ws.B, cfg.Ch, Chp, O, ptr(w2), ptr(b2), ptr(pred),
+        check(self.lib.nint_head_fwd(ptr(ws.h[-1]), slot * ws.B, ws.B, Ch, Chp, O, ptr(w2), ptr(b2), ptr(pred),
                                      C.byref(ws.g), self.dt, stream_ptr()), "nint_head_fwd")
         return pred
 
@@ -334,6 +329,13 @@ class SeqEngine:
         w2 = w.detach().float().contiguous()
         b2 = None if b is None else b.detach().float().contiguous()
         return cfg.Ch, cfg.padded(self.kc)[2], w.shape[0], w2, b2
+
+    @staticmethod
+    def _beyond_fused_head(Chp: int, O: int) -> bool:
+        """The fused head/loss kernels' limit: more than 128 padded channels, or the weights [O][CHV] plus one output chunk's
+        d loss / d pred of 64 pixels (and 8 KiB of static LDS) beyond the 160 KiB of a CU."""
+        chv = 32 if Chp <= 32 else (64 if Chp <= 64 else 128)
+        return Chp > 128 or (O * chv + min(O, 64) * 64) * 4 + 8192 > 160 * 1024
 
     def head_forward_seq(self, ws: Workspace, w: torch.Tensor, b: Optional[torch.Tensor]) -> torch.Tensor:
         """The head on the top layer's hidden state of EVERY step in one launch (nint_head_fwd_seq): (B, T*O, H, W), channel
@@ -364,8 +366,7 @@ class SeqEngine:
         """head_loss_fused over every step (nint_head_loss_seq_fused): y (B, T, O, Hc, Wc); dpred (T*B, O, H, W) in image
         order t*B + b; the per-step dL/dh goes into ws.dh_seq_slab().  False beyond the fused kernel's limit."""
         Ch, Chp, O, w2, b2 = self._head_args(w, b)
-        chv = 32 if Chp <= 32 else (64 if Chp <= 64 else 128)
-        if Chp > 128 or (O * chv + min(O, 64) * 64) * 4 + 8192 > 160 * 1024:
+        if self._beyond_fused_head(Chp, O):
             return False
         check(self.lib.nint_head_loss_seq_fused(ptr(ws.h[-1]), ws.B, ws.T, Ch, Chp, O, ptr(w2), ptr(b2), ptr(y), ptr(dpred),
                                                 ptr(ws.dh_seq_slab(self)), ptr(scratch), ptr(stats), C.byref(ws.g), halo[0], halo[1],
@@ -377,17 +378,11 @@ class SeqEngine:
         """Training fast path (nint_head_loss_fused): head forward, crop, MSE+L1 sums, d loss / d pred and dL/dh_{T-1}
         (into ws.dh[-1]) in one pass; `scratch[0]` = loss, `stats` accumulated.  False when the head is wider than the
         fused kernel holds (more than 128 padded channels, or weights + one pixel group's d loss / d pred beyond the LDS) (the caller then takes the three separate launches)."""
-        l = len(self.cfgs) - 1
-        cfg = self.cfgs[l]
-        Chp = cfg.padded(self.kc)[2]
-        O = w.shape[0]
-        chv = 32 if Chp <= 32 else (64 if Chp <= 64 else 128)
-        if Chp > 128 or (O * chv + min(O, 64) * 64) * 4 + 8192 > 160 * 1024:
+        Ch, Chp, O, w2, b2 = self._head_args(w, b)
+        if self._beyond_fused_head(Chp, O):
             return False
-        w2 = w.detach().float().contiguous()
-        b2 = None if b is None else b.detach().float().contiguous()
-        check(self.lib.nint_head_loss_fused(ptr(ws.h[l]), ws.T * ws.B, ws.B, cfg.Ch, Chp, O, ptr(w2), ptr(b2), ptr(y), ptr(dpred),
-                                            ptr(ws.dh[l]), ptr(scratch), ptr(stats), C.byref(ws.g), halo[0], halo[1], Hc, Wc,
+        check(self.lib.nint_head_loss_fused(ptr(ws.h[-1]), ws.T * ws.B, ws.B, Ch, Chp, O, ptr(w2), ptr(b2), ptr(y), ptr(dpred),
+                                            ptr(ws.dh[-1]), ptr(scratch), ptr(stats), C.byref(ws.g), halo[0], halo[1], Hc, Wc,
                                             self.dt, stream_ptr()), "nint_head_loss_fused")
         return True
 
@@ -398,19 +393,15 @@ class SeqEngine:
         belongs to: default the last step's B; (B, T*B) reduces every step's (the fused sequence pass, write_dh False)."""
         n0, N = images if images is not None else (ws.T * ws.B, ws.B)
         assert images is None or not write_dh
-        l = len(self.cfgs) - 1
-        cfg = self.cfgs[l]
-        Chp = cfg.padded(self.kc)[2]
-        O = w.shape[0]
-        w2 = w.detach().float().contiguous()
+        Ch, Chp, O, w2, _ = self._head_args(w, None)
         dp = dpred.detach().float().contiguous()
-        dw = dw_out if dw_out is not None else torch.empty(O, cfg.Ch, dtype=torch.float32, device=self.device)
+        dw = dw_out if dw_out is not None else torch.empty(O, Ch, dtype=torch.float32, device=self.device)
         db = db_out if db_out is not None else torch.empty(O, dtype=torch.float32, device=self.device)
-        check(self.lib.nint_head_bwd(ptr(ws.h[l]), n0, N, cfg.Ch, Chp, O, ptr(w2), ptr(dp),
-                                     ptr(ws.dh[l]) if write_dh else None,
+        check(self.lib.nint_head_bwd(ptr(ws.h[-1]), n0, N, Ch, Chp, O, ptr(w2), ptr(dp),
+                                     ptr(ws.dh[-1]) if write_dh else None,
                                      ptr(dw), ptr(db), C.byref(ws.g), self.dt, ptr(self.wg_partial),
                                      self.wg_partial.numel() * 4, stream_ptr()), "nint_head_bwd")
-        return dw.view(O, cfg.Ch, 1, 1), db
+        return dw.view(O, Ch, 1, 1), db
 
     def backward(self, ws: Workspace, need_dx: bool, zero_state_grads: Sequence[int] = (),
                  dW_out: Optional[Sequence[torch.Tensor]] = None, db_out: Optional[Sequence[torch.Tensor]] = None, parts: int = 0,

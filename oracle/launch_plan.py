@@ -83,7 +83,7 @@ class Layer:
 
 
 def xfold_pays(Cx: int, k: int, dt: str) -> bool:
-    """nint_xfold_pays (csrc/pointwise.hip)"""
+    """nint_xfold_pays (csrc/pack_weights.hip)"""
     kc = kc_of(dt)
     return Cx > 0 and k > 1 and k % 2 == 1 and cdiv(k * Cx, kc) < cdiv(Cx, kc) * k
 

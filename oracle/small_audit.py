@@ -1,4 +1,4 @@
-"""f64 references and derived error bounds for the kernels of ``csrc/pointwise.hip`` around the gate GEMMs: the 1x1
+"""f64 references and derived error bounds for the kernels of ``csrc/pointwise.hip``, ``csrc/head.hip`` and ``csrc/pack.hip`` around the gate GEMMs: the 1x1
 head, the crop + MSE + L1 loss, their fused form, flat Adam, the layout packers and the preproc (TEST INFRASTRUCTURE
 ONLY; numpy / torch-CPU, no GPU).
 

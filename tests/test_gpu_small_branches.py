@@ -1,9 +1,9 @@
-"""The kernels of csrc/pointwise.hip around the gate GEMMs -- Adam, the loss, the 1x1 head and its fused form, the layout
+"""The kernels of csrc/pointwise.hip, csrc/head.hip and csrc/pack.hip around the gate GEMMs -- Adam, the loss, the 1x1 head and its fused form, the layout
 packers and the preproc -- at every branch of their host dispatch, called through the C ABI and checked element by
 element with the f64 references and derived bounds of oracle/small_audit.py (no tolerance here comes from a run).
 
 Every case names the branch it is meant to reach and asserts, in Python, the dispatch condition copied from the host code
-(csrc/pointwise.hip): a case whose shape drifts out of its branch fails before it launches anything.  Every buffer is sized
+(csrc/head.hip, csrc/pack.hip): a case whose shape drifts out of its branch fails before it launches anything.  Every buffer is sized
 exactly for its call."""
 import ctypes as C
 
@@ -216,7 +216,7 @@ def test_head_fwd_and_dh_elementwise_at_every_dispatch_branch(lib, dt, Ch, O, ke
     print(f"head {kernel} dt={dt}: worst ratio pred {r:.3f}, dh {r2:.3f}")
 
 
-LOSS_BLOCKS_MAX = (8194 - 2) // 8     # csrc/pointwise.hip: what the caller's scratch holds, 4 doubles per workgroup
+LOSS_BLOCKS_MAX = (8194 - 2) // 8     # csrc/head.hip: what the caller's scratch holds, 4 doubles per workgroup
 
 FUSED_CASES = [
     # (dt, Ch, O, N, n0, H, W, oy, ox, Hc, Wc, CHV of the instantiation, what else the case is there for)
