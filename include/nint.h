@@ -345,6 +345,42 @@ int nint_head_loss_seq_fused(const void* h_slab, int B, int T, int Ch, int Chp, 
                              const float* y, float* dpred, void* dh_seq, float* loss_out, double* stats, const nint_geom* g,
                              int oy, int ox, int Hc, int Wc, int dtype, void* stream);
 
+/* ---- evaluation: skill sums (test.ipynb:377-385, :462-485, :605, :630, :684-693, :796-803) ------------ */
+/* Everything the analysis notebook derives from the gathered test-period predictions -- one R2 per window, one R2 per grid
+ * cell over time, time-mean maps, cos-latitude weighted means -- follows from running f64 sums, formed on the device in one
+ * pass and read once (inference.skill_from_sums turns them into the report).  Evaluation runs in z-score units.
+ *   pix     [nslots][NINT_SKILL_PIX][O][Hc][Wc] f64, ACCUMULATED (the caller zeroes it once).  slot[n] (host) picks the
+ *           accumulator set of sample n: the slots partition the samples (by month, say), a union is the sum of its slots'
+ *           planes; slot[n] = -1 leaves sample n out of the maps (its `sample` row is still written).  slot == NULL: all 0.
+ *   sample  [N][O][NINT_SKILL_SAMPLE] f64, OVERWRITTEN: the sums of each (sample, output) over the crop; row_w (device,
+ *           [Hc] f64, NULL = 1) weights the rows of the last two (cos latitude, test.ipynb:796).  (f64: weights rounded
+ *           to f32 would put the weighted means 5e-9 relative from the notebook's f64 expression.)
+ *   scratch nint_skill_scratch_bytes(N, O, Hc, Wc) bytes, 8-byte aligned: the per-wave partial rows of `sample`.
+ * d = (double)p - (double)y, products and sums in f64.  No atomics: one thread owns a (slot, o, cy, cx) cell for the whole
+ * call and adds the call's samples in order n = 0, 1, ..., so pix is bit-identical run to run and under any split of the
+ * same samples into consecutive calls; a sample's row is reduced by a tree that depends on (O, Hc, Wc) only, so it does not
+ * depend on N or on the sample's position in the call either.  N beyond NINT_SKILL_MAX_N is split internally.
+ * NINT_E_ARG: a NULL pix / sample / y / scratch, a scratch that is too small, nslots < 1, a slot outside [-1, nslots), a
+ * crop outside the grid, a bad dtype; NINT_E_ALIGN: pix / sample / scratch not 8-byte, h_slab not 16-byte aligned --
+ * all before any launch. */
+#define NINT_SKILL_PIX 5      /* f64 planes per slot: sum y, sum p, sum y^2, sum p^2, sum (y-p)^2 */
+#define NINT_SKILL_SAMPLE 8   /* f64 per (sample, output): sum (y-p)^2, sum |y-p|, sum y, sum y^2, sum p, sum p^2,
+                                 sum row_w*y, sum row_w*p */
+#define NINT_SKILL_MAX_N 64   /* samples per launch; larger N is split internally, as NINT_PRE_MAX_B is */
+size_t nint_skill_scratch_bytes(int N, int O, int Hc, int Wc);            /* host arithmetic only */
+/* pred (N,O,H,W) f32 already in memory; y (N,O,Hc,Wc) f32 and the crop window as in nint_loss_mse_l1_crop */
+int nint_skill_accum(const float* pred, const float* y, const int32_t* slot /*host, N entries, or NULL = all 0*/,
+                     int nslots, const double* row_w /*device [Hc] or NULL = 1*/, double* pix, double* sample,
+                     double* scratch, size_t scratch_bytes, int N, int O, int H, int W, int oy, int ox, int Hc, int Wc,
+                     void* stream);
+/* fast path: the 1x1 head on halo-slab images [n0, n0+N) + crop + the same accumulation in one pass; pred never goes to
+ * memory unless pred_out (N,O,Hc,Wc) is given (= the crop of nint_head_fwd bit for bit).  pix and sample equal nint_head_fwd
+ * followed by nint_skill_accum bit for bit.  Same limits as nint_head_loss_fused, NINT_E_SHAPE beyond. */
+int nint_head_skill_accum(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w, const float* b,
+                          const float* y, const int32_t* slot /*host*/, int nslots, const double* row_w, double* pix,
+                          double* sample, float* pred_out, double* scratch, size_t scratch_bytes, const nint_geom* g,
+                          int oy, int ox, int Hc, int Wc, int dtype, void* stream);
+
 /* ---- optimiser (train.py:71,110) ---------------------------------------------------------------- */
 /* torch.optim.Adam (eps 1e-8, no weight decay / amsgrad) on one flat f32 buffer.
  * grad_scale multiplies g first (1/world_size after the RCCL all-reduce). step is 1-based. */

@@ -3,5 +3,7 @@ train.py batch step).  Import as ``nasa_niswan_amd`` (the directory name carries
 ``nasa_niswan_amd/`` at the repository root is the importable alias of this package)."""
 from ._lib import NintError, load as load_library  # noqa: F401
 from .model import ConvLSTM, ConvLSTMCell  # noqa: F401
+from .inference import SkillAccumulator, SkillReport, evaluate_skill, skill_from_sums  # noqa: F401
 
-__all__ = ["ConvLSTM", "ConvLSTMCell", "load_library", "NintError"]
+__all__ = ["ConvLSTM", "ConvLSTMCell", "load_library", "NintError", "SkillAccumulator", "SkillReport", "evaluate_skill",
+           "skill_from_sums"]

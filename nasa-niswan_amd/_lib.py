@@ -16,6 +16,7 @@ NINT_MAX_LAYERS = 8
 NINT_VERSION = 112     # include/nint.h NINT_VERSION: the library this binding was written against
 NINT_LOSS_SCRATCH_FLOATS = 8194
 NINT_LOSS_STATS = 8
+NINT_SKILL_PIX, NINT_SKILL_SAMPLE, NINT_SKILL_MAX_N = 5, 8, 64
 
 vp = C.c_void_p
 
@@ -85,6 +86,10 @@ SIGNATURES = {
     "nint_loss_mse_l1_crop": (_I, [vp, vp, vp, vp, vp, _I, _I, _I, _I, _I, _I, _I, _I, vp]),
     "nint_head_loss_fused": (_I, [vp, _I, _I, _I, _I, _I, vp, vp, vp, vp, vp, vp, vp, _PG, _I, _I, _I, _I, _I, vp]),
     "nint_head_loss_seq_fused": (_I, [vp, _I, _I, _I, _I, _I, vp, vp, vp, vp, vp, vp, vp, _PG, _I, _I, _I, _I, _I, vp]),
+    "nint_skill_scratch_bytes": (_SZ, [_I, _I, _I, _I]),
+    "nint_skill_accum": (_I, [vp, vp, C.POINTER(C.c_int32), _I, vp, vp, vp, vp, _SZ, _I, _I, _I, _I, _I, _I, _I, _I, vp]),
+    "nint_head_skill_accum": (_I, [vp, _I, _I, _I, _I, _I, vp, vp, vp, C.POINTER(C.c_int32), _I, vp, vp, vp, vp, vp, _SZ, _PG,
+                                   _I, _I, _I, _I, _I, vp]),
     "nint_adam_flat": (_I, [vp, vp, vp, vp, _SZ, C.c_double, C.c_double, C.c_double, C.c_double, _I, _F, vp]),
     "nint_preproc_fuse_pad": (_I, [C.POINTER(vp), C.POINTER(_I), _I, vp, vp, vp, _I, _I, _I, _I, _I, _I, vp]),
     "nint_preproc_fuse_pad_batch": (_I, [C.POINTER(vp), C.POINTER(_I), _I, vp, vp, C.POINTER(_I), _I, vp, _I, _I, _I, _I, _I, _I, vp]),

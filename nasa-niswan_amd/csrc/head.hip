@@ -3,6 +3,8 @@
 // They share head_stage_weights, LOSS_BLOCKS_MAX and loss_final_kernel.  Every kernel body is a __forceinline__ device
 // function under ONE __global__ wrapper templated on SEQ: the register allocation depends on that function boundary.
 #include "nint_common.h"
+#include <algorithm>
+#include <climits>
 
 // ------------------------------------------------------------------------------ 1x1 head
 // pred[n][o][y][x] = b[o] + sum_c w[o][c] * h[n][y][x][c]     (model.py:251,274)
@@ -814,4 +816,272 @@ extern "C" int nint_head_loss_seq_fused(const void* h_slab, int B, int T, int Ch
   if (Chp > 128) return NINT_E_SHAPE;              // wider heads: nint_head_fwd_seq + nint_loss_mse_l1_crop + nint_head_bwd_seq
   if ((((uintptr_t)loss_out) & 7) != 0 || ((((uintptr_t)h_slab) | ((uintptr_t)dh_seq)) & 15) != 0) return NINT_E_ALIGN;
   return head_loss_fused_impl<true>(h_slab, B, T * B, Ch, Chp, O, w, b, y, dpred, dh_seq, loss_out, stats, g, oy, ox, Hc, Wc, dtype, B, stream);
+}
+
+// ------------------------------------------------------------------------------ evaluation: skill sums (test.ipynb)
+// What the analysis notebook computes from the gathered predictions -- r_squared_temporal (:377-385), r_squared_spatial
+// (:462-485), the time-mean maps (:605,:630) and the cos-latitude weighted means (:684-693,:796-803) -- follows from running
+// f64 sums: five per map cell and accumulator set ("slot": sum y, sum p, sum y^2, sum p^2, sum (y-p)^2) and eight per
+// (sample, output) over the crop.  One pass forms them from the prediction (nint_skill_accum) or straight from the top
+// layer's hidden state (nint_head_skill_accum: the head of head_fwd_body, pred never in memory).
+//
+// Mapping: grid = (256-pixel blocks of the crop, groups of SKILL_OG outputs); a thread owns ONE crop pixel and SKILL_OG
+// outputs for the whole call -- the (slot, o, cy, cx) cells of every slot.  The host orders the call's samples by slot
+// (stable: n ascending inside a slot, slot -1 last), so a slot's five sums of a cell are loaded once, grow in registers in
+// sample order and are stored once: bit-identical run to run and under any split of the samples into consecutive calls (a
+// store and reload of an f64 changes nothing).  No atomics.  The per-sample sums are reduced per wave by a fixed exchange
+// tree (skill_wave_fold), one partial row per (sample, output, wave), and folded in a fixed order by skill_fold_kernel:
+// block mapping and fold order depend on (O, Hc, Wc) only, never on N or on the sample's position in the call.
+// Arithmetic: d = (double)p - (double)y, every product and every sum a separate f64 operation (contraction is off in the
+// shared body, so both entries and every instance round alike).
+#define SKILL_OG 4
+struct SkillPlan { int32_t slot[NINT_SKILL_MAX_N]; uint8_t idx[NINT_SKILL_MAX_N]; };   // the call's samples in slot order
+
+// Sum of v[k] over the wave's 64 lanes for k = 0..7 at once: three halving exchanges (each lane keeps half of its values and
+// takes the partner's for them), then three plain ones.  Lane 8*k ends with the total of v[k] (every lane of 8k..8k+7 does).
+__device__ __forceinline__ double skill_wave_fold(const double (&v)[8], int lane) {
+  const bool b5 = lane & 32, b4 = lane & 16, b3 = lane & 8;
+  double a[4], c[2];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) a[j] = (b5 ? v[j + 4] : v[j]) + __shfl_xor(b5 ? v[j] : v[j + 4], 32);
+#pragma unroll
+  for (int j = 0; j < 2; ++j) c[j] = (b4 ? a[j + 2] : a[j]) + __shfl_xor(b4 ? a[j] : a[j + 2], 16);
+  double s = (b3 ? c[1] : c[0]) + __shfl_xor(b3 ? c[0] : c[1], 8);   // the value k = lane >> 3 over the 8 lanes that share lane & 7
+  s += __shfl_xor(s, 4);
+  s += __shfl_xor(s, 2);
+  s += __shfl_xor(s, 1);
+  return s;
+}
+
+// the prediction of (sample n, output o0 + u) at the thread's pixel, from memory ...
+struct SkillPredPlain {
+  const float* __restrict__ pred; int O, o0; size_t HW, off;
+  __device__ __forceinline__ void sample(int) {}
+  __device__ __forceinline__ float operator()(int n, int u) const { return pred[((size_t)n * O + o0 + u) * HW + off]; }
+};
+// ... or from the hidden state: head_fwd_body's arithmetic (zero-padded weight rows in LDS, the same channel order).  The
+// outputs of a sample run as head_fwd_body's own loop -- one output per turn, not unrolled, the result stored (here to the
+// thread's LDS column) -- so that the compiler forms each dot product as it does there: it fuses most multiply-adds of the
+// chain and leaves some as a packed multiply and an add, and pred_out has to match nint_head_fwd bit for bit.
+template <int DT, int CHV>
+struct SkillPredHead {
+  const void* __restrict__ h; const float* w_s; float* p_s; const float* __restrict__ b; int n0, Chp, o0, on; size_t img, off;
+  __device__ __forceinline__ void sample(int n) {
+    // (the weight rows stay in LDS: without this fence their reads are hoisted out of the sample loop into registers)
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    const size_t hb = (size_t)(n0 + n) * img + off;
+    float hv[CHV];
+#pragma unroll
+    for (int c = 0; c < CHV; c += 4) {
+      const f32x4_t v = (c < Chp) ? load_vec4<DT>(h, hb + c) : (f32x4_t){0.f, 0.f, 0.f, 0.f};
+      hv[c] = v[0]; hv[c + 1] = v[1]; hv[c + 2] = v[2]; hv[c + 3] = v[3];
+    }
+    float* out = p_s + threadIdx.x;
+#pragma unroll 1
+    for (int u = 0; u < on; ++u) {
+      float acc = b ? b[o0 + u] : 0.f;
+      const f32x4_t* wr = (const f32x4_t*)(w_s + u * CHV);
+#pragma unroll
+      for (int c = 0; c < CHV; c += 4) {
+        const f32x4_t wv = wr[c / 4];
+        acc += wv[0] * hv[c]; acc += wv[1] * hv[c + 1]; acc += wv[2] * hv[c + 2]; acc += wv[3] * hv[c + 3];
+      }
+      out[u * 256] = acc;
+    }
+  }
+  __device__ __forceinline__ float operator()(int, int u) const { return p_s[u * 256 + threadIdx.x]; }
+};
+
+// the accumulation both entries share.  q = the thread's crop pixel (clamped; live = inside the crop), o0 / on = its outputs
+template <class Src>
+__device__ __forceinline__ void skill_accum_body(Src& src, const float* __restrict__ y, double rw, double* __restrict__ pix,
+                                                 double* __restrict__ part, float* __restrict__ pred_out, const SkillPlan& plan,
+                                                 int N, int O, size_t HWc, size_t q, bool live, int o0, int on) {
+#pragma clang fp contract(off)
+  const int lane = threadIdx.x & 63;
+  const size_t NP = (size_t)gridDim.x * 4;                            // partial rows per (sample, output): one per wave
+  const size_t prow = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const size_t plane = (size_t)O * HWc;                               // one of a slot's NINT_SKILL_PIX planes
+  double acc[SKILL_OG][NINT_SKILL_PIX];
+#pragma unroll
+  for (int u = 0; u < SKILL_OG; ++u)
+#pragma unroll
+    for (int k = 0; k < NINT_SKILL_PIX; ++k) acc[u][k] = 0.0;
+  int cur = -1;                                                       // the slot whose sums are in acc
+  for (int i = 0; i < N; ++i) {
+    const int n = plan.idx[i], s = plan.slot[i];
+    if (s != cur) {
+      if (live) {
+#pragma unroll
+        for (int u = 0; u < SKILL_OG; ++u)
+#pragma unroll
+          for (int k = 0; k < NINT_SKILL_PIX; ++k) {
+            if (u >= on) continue;
+            if (cur >= 0) pix[((size_t)cur * NINT_SKILL_PIX + k) * plane + (size_t)(o0 + u) * HWc + q] = acc[u][k];
+            if (s >= 0) acc[u][k] = pix[((size_t)s * NINT_SKILL_PIX + k) * plane + (size_t)(o0 + u) * HWc + q];
+          }
+      }
+      cur = s;
+    }
+    src.sample(n);
+    float tq[SKILL_OG];
+#pragma unroll
+    for (int u = 0; u < SKILL_OG; ++u) tq[u] = u < on ? y[((size_t)n * O + o0 + u) * HWc + q] : 0.f;
+#pragma unroll
+    for (int u = 0; u < SKILL_OG; ++u) {
+      if (u >= on) continue;                                          // (block-uniform)
+      const float pf = src(n, u);
+      if (pred_out && live) pred_out[((size_t)n * O + o0 + u) * HWc + q] = pf;
+      const double p = live ? (double)pf : 0.0, t = live ? (double)tq[u] : 0.0;   // lanes past the crop add zeros
+      const double d = p - t;
+      const double dd = d * d, tt = t * t, pp = p * p;
+      if (s >= 0) {
+        acc[u][0] += t; acc[u][1] += p; acc[u][2] += tt; acc[u][3] += pp; acc[u][4] += dd;
+      }
+      const double v[NINT_SKILL_SAMPLE] = {dd, fabs(d), t, tt, p, pp, rw * t, rw * p};
+      const double tot = skill_wave_fold(v, lane);
+      if ((lane & 7) == 0) part[(((size_t)n * O + o0 + u) * NP + prow) * NINT_SKILL_SAMPLE + (lane >> 3)] = tot;
+    }
+  }
+  if (cur >= 0 && live) {
+#pragma unroll
+    for (int u = 0; u < SKILL_OG; ++u)
+#pragma unroll
+      for (int k = 0; k < NINT_SKILL_PIX; ++k)
+        if (u < on) pix[((size_t)cur * NINT_SKILL_PIX + k) * plane + (size_t)(o0 + u) * HWc + q] = acc[u][k];
+  }
+}
+
+__global__ __launch_bounds__(256) void skill_accum_kernel(const float* __restrict__ pred, const float* __restrict__ y,
+                                                          const double* __restrict__ row_w, double* __restrict__ pix,
+                                                          double* __restrict__ part, const SkillPlan plan, int N, int O, int H,
+                                                          int W, int oy, int ox, int Hc, int Wc) {
+  const size_t HWc = (size_t)Hc * Wc, q0 = (size_t)blockIdx.x * 256 + threadIdx.x;
+  const bool live = q0 < HWc;
+  const size_t q = live ? q0 : HWc - 1;
+  const int cy = (int)(q / Wc), cx = (int)(q - (size_t)cy * Wc);
+  const int o0 = blockIdx.y * SKILL_OG, on = min(SKILL_OG, O - o0);
+  SkillPredPlain src{pred, O, o0, (size_t)H * W, (size_t)(cy + oy) * W + (cx + ox)};
+  skill_accum_body(src, y, row_w ? row_w[cy] : 1.0, pix, part, nullptr, plan, N, O, HWc, q, live, o0, on);
+}
+
+template <int DT, int CHV>
+__global__ __launch_bounds__(256) void head_skill_accum_kernel(const void* __restrict__ h, int n0, int Ch, int Chp,
+                                                               const float* __restrict__ w, const float* __restrict__ b,
+                                                               const float* __restrict__ y, const double* __restrict__ row_w,
+                                                               double* __restrict__ pix, double* __restrict__ part,
+                                                               float* __restrict__ pred_out, const SkillPlan plan, int N, int O,
+                                                               int P, int Hh, int Wh, int oy, int ox, int Hc, int Wc) {
+  __shared__ __attribute__((aligned(16))) float w_s[SKILL_OG * CHV];
+  __shared__ float p_s[SKILL_OG * 256];                                // the thread's predictions of one sample
+  const int o0 = blockIdx.y * SKILL_OG, on = min(SKILL_OG, O - o0);
+  head_stage_weights<CHV>(w_s, w + (size_t)o0 * Ch, on, Ch);           // the group's rows of [O][CHV]
+  const size_t HWc = (size_t)Hc * Wc, q0 = (size_t)blockIdx.x * 256 + threadIdx.x;
+  const bool live = q0 < HWc;
+  const size_t q = live ? q0 : HWc - 1;
+  const int cy = (int)(q / Wc), cx = (int)(q - (size_t)cy * Wc);
+  SkillPredHead<DT, CHV> src;
+  src.h = h; src.w_s = w_s; src.p_s = p_s; src.b = b; src.n0 = n0; src.Chp = Chp; src.o0 = o0; src.on = on;
+  src.img = (size_t)Hh * Wh * Chp;
+  src.off = ((size_t)(cy + oy + P) * Wh + (cx + ox + P)) * Chp;
+  skill_accum_body(src, y, row_w ? row_w[cy] : 1.0, pix, part, pred_out, plan, N, O, HWc, q, live, o0, on);
+}
+
+// sample[pair][k] = the NP partial rows of pair = (sample, output) in a fixed order: one wave per pair, lane = (j, k) adds the
+// rows j, j + 8, ..., then the eight j in order
+__global__ __launch_bounds__(256) void skill_fold_kernel(const double* __restrict__ part, double* __restrict__ sample, int npair, int NP) {
+  const int lane = threadIdx.x & 63, pair = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (pair >= npair) return;                                           // (a whole wave)
+  const int k = lane & 7, j = lane >> 3;
+  const double* p = part + (size_t)pair * NP * NINT_SKILL_SAMPLE;
+  double s = 0.0;
+#pragma unroll 4
+  for (int i = j; i < NP; i += 8) s += p[(size_t)i * NINT_SKILL_SAMPLE + k];
+  double t = __shfl(s, k);
+  for (int jj = 1; jj < 8; ++jj) t += __shfl(s, jj * 8 + k);
+  if (j == 0) sample[(size_t)pair * NINT_SKILL_SAMPLE + k] = t;
+}
+
+static inline size_t skill_pix_blocks(int Hc, int Wc) { return ((size_t)Hc * Wc + 255) / 256; }
+
+extern "C" size_t nint_skill_scratch_bytes(int N, int O, int Hc, int Wc) {
+  if (N <= 0 || O <= 0 || Hc <= 0 || Wc <= 0) return 0;
+  const size_t nc = N < NINT_SKILL_MAX_N ? N : NINT_SKILL_MAX_N;       // larger calls run in pieces that reuse the scratch
+  return nc * O * skill_pix_blocks(Hc, Wc) * 4 * NINT_SKILL_SAMPLE * sizeof(double);
+}
+
+// the checks both entries share (H x W: the grid the crop window lies in)
+static int skill_args_check(const float* y, const int32_t* slot, int nslots, const double* pix, const double* sample,
+                            const double* scratch, size_t scratch_bytes, int N, int O, int H, int W, int oy, int ox, int Hc, int Wc) {
+  if (!y || !pix || !sample || !scratch || N <= 0 || O <= 0 || Hc <= 0 || Wc <= 0 || nslots < 1) return NINT_E_ARG;
+  if (oy < 0 || ox < 0 || oy + Hc > H || ox + Wc > W) return NINT_E_ARG;
+  if (slot)
+    for (int n = 0; n < N; ++n)
+      if (slot[n] < -1 || slot[n] >= nslots) return NINT_E_ARG;
+  if (scratch_bytes < nint_skill_scratch_bytes(N, O, Hc, Wc)) return NINT_E_ARG;
+  return NINT_OK;
+}
+
+// pieces of at most NINT_SKILL_MAX_N samples: launch(first sample, count, plan), then the fold of that piece's partial rows
+template <class L>
+static int skill_run(const int32_t* slot, double* sample, double* scratch, int N, int O, int Hc, int Wc, hipStream_t st, L&& launch) {
+  const int NP = (int)skill_pix_blocks(Hc, Wc) * 4;
+  for (int c0 = 0; c0 < N; c0 += NINT_SKILL_MAX_N) {
+    const int nc = N - c0 < NINT_SKILL_MAX_N ? N - c0 : NINT_SKILL_MAX_N;
+    int order[NINT_SKILL_MAX_N];
+    for (int i = 0; i < nc; ++i) order[i] = i;
+    auto key = [&](int i) { const int s = slot ? slot[c0 + i] : 0; return s < 0 ? INT_MAX : s; };
+    std::stable_sort(order, order + nc, [&](int a, int b) { return key(a) < key(b); });
+    SkillPlan plan = {};
+    for (int i = 0; i < nc; ++i) {
+      plan.idx[i] = (uint8_t)order[i];
+      plan.slot[i] = slot ? slot[c0 + order[i]] : 0;
+    }
+    launch(c0, nc, plan);
+    NINT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(skill_fold_kernel, dim3(nint_cdiv(nc * O, 4)), dim3(256), 0, st, scratch,
+                       sample + (size_t)c0 * O * NINT_SKILL_SAMPLE, nc * O, NP);
+    NINT_LAUNCH_CHECK();
+  }
+  return NINT_OK;
+}
+
+extern "C" int nint_skill_accum(const float* pred, const float* y, const int32_t* slot, int nslots, const double* row_w,
+                                double* pix, double* sample, double* scratch, size_t scratch_bytes, int N, int O, int H, int W,
+                                int oy, int ox, int Hc, int Wc, void* stream) {
+  if (!pred) return NINT_E_ARG;
+  const int rc = skill_args_check(y, slot, nslots, pix, sample, scratch, scratch_bytes, N, O, H, W, oy, ox, Hc, Wc);
+  if (rc != NINT_OK) return rc;
+  if (((((uintptr_t)pix) | ((uintptr_t)sample) | ((uintptr_t)scratch) | ((uintptr_t)row_w)) & 7) != 0) return NINT_E_ALIGN;
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid((unsigned)skill_pix_blocks(Hc, Wc), (unsigned)nint_cdiv(O, SKILL_OG));
+  const size_t HWc = (size_t)Hc * Wc;
+  return skill_run(slot, sample, scratch, N, O, Hc, Wc, st, [&](int c0, int nc, const SkillPlan& plan) {
+    hipLaunchKernelGGL(skill_accum_kernel, grid, dim3(256), 0, st, pred + (size_t)c0 * O * H * W, y + (size_t)c0 * O * HWc, row_w,
+                       pix, scratch, plan, nc, O, H, W, oy, ox, Hc, Wc);
+  });
+}
+
+extern "C" int nint_head_skill_accum(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w, const float* b,
+                                     const float* y, const int32_t* slot, int nslots, const double* row_w, double* pix,
+                                     double* sample, float* pred_out, double* scratch, size_t scratch_bytes, const nint_geom* g,
+                                     int oy, int ox, int Hc, int Wc, int dtype, void* stream) {
+  if (!h_slab || !w || !g || Ch <= 0 || Chp < Ch || n0 < 0) return NINT_E_ARG;
+  if (dtype != NINT_BF16 && dtype != NINT_F32) return NINT_E_ARG;
+  const int rc = skill_args_check(y, slot, nslots, pix, sample, scratch, scratch_bytes, N, O, g->H, g->W, oy, ox, Hc, Wc);
+  if (rc != NINT_OK) return rc;
+  // nint_head_loss_fused's limits (one rule for both fused head passes: SeqEngine._beyond_fused_head)
+  if (Chp > 128 || Chp % 4) return NINT_E_SHAPE;
+  if (((size_t)O * head_chv(Chp) + (size_t)(O < HEAD_OCH ? O : HEAD_OCH) * 64) * sizeof(float) + 8192 > 160 * 1024) return NINT_E_SHAPE;
+  if (((((uintptr_t)pix) | ((uintptr_t)sample) | ((uintptr_t)scratch) | ((uintptr_t)row_w)) & 7) != 0 || (((uintptr_t)h_slab) & 15) != 0) return NINT_E_ALIGN;
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid((unsigned)skill_pix_blocks(Hc, Wc), (unsigned)nint_cdiv(O, SKILL_OG));
+  const size_t HWc = (size_t)Hc * Wc;
+  return skill_run(slot, sample, scratch, N, O, Hc, Wc, st, [&](int c0, int nc, const SkillPlan& plan) {
+    nint_by_dtype(dtype, [&](auto dt) { head_by_chv(Chp, [&](auto chv) {
+      hipLaunchKernelGGL((head_skill_accum_kernel<decltype(dt)::value, decltype(chv)::value>), grid, dim3(256), 0, st, h_slab, n0 + c0,
+                         Ch, Chp, w, b, y + (size_t)c0 * O * HWc, row_w, pix, scratch,
+                         pred_out ? pred_out + (size_t)c0 * O * HWc : (float*)nullptr, plan, nc, O, g->P, g->Hh, g->Wh, oy, ox, Hc, Wc);
+    }); });
+  });
 }

@@ -386,6 +386,36 @@ class SeqEngine:
                                             self.dt, stream_ptr()), "nint_head_loss_fused")
         return True
 
+    def head_skill(self, ws: Workspace, w: torch.Tensor, b: Optional[torch.Tensor], y: torch.Tensor, slots, acc,
+                   pred_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Evaluation fast path (nint_head_skill_accum): the head on the last step's images, the crop and the f64 skill sums
+        in one pass -- `acc` (an inference.SkillAccumulator: pix, scratch, row weights, crop offset) gains the batch's terms
+        in the slots `slots` (a host sequence of ws.B ints, -1 = out of the maps; None = all 0); the prediction goes to memory
+        only when `pred_out` (B, O, Hc, Wc) f32 is given.  Returns the batch's (B, O, NINT_SKILL_SAMPLE) f64 sample rows.
+        A head beyond the fused kernels' limit (_beyond_fused_head) runs as head_forward + nint_skill_accum: the same sums."""
+        Ch, Chp, O, w2, b2 = self._head_args(w, b)
+        B, Hc, Wc = ws.B, acc.Hc, acc.Wc
+        oy, ox = acc.halo if acc.halo is not None else ((ws.H - Hc) // 2, (ws.W - Wc) // 2)
+        yv = y.detach().float().contiguous()
+        assert O == acc.O and yv.numel() == B * O * Hc * Wc, "target must be (B,[O,]Hc,Wc)"
+        assert pred_out is None or (pred_out.dtype == torch.float32 and pred_out.is_contiguous() and pred_out.numel() == yv.numel())
+        sl = None if slots is None else (C.c_int32 * B)(*[int(v) for v in slots])
+        sample = torch.empty(B, O, _lib.NINT_SKILL_SAMPLE, dtype=torch.float64, device=self.device)
+        scratch = acc.scratch_for(B)
+        if self._beyond_fused_head(Chp, O):
+            pred = self.head_forward(ws, w, b)
+            check(self.lib.nint_skill_accum(ptr(pred), ptr(yv), sl, acc.nslots, ptr(acc.row_w), ptr(acc.pix), ptr(sample),
+                                            ptr(scratch), scratch.numel() * 8, B, O, ws.H, ws.W, oy, ox, Hc, Wc, stream_ptr()),
+                  "nint_skill_accum")
+            if pred_out is not None:
+                pred_out.view(B, O, Hc, Wc).copy_(pred[:, :, oy:oy + Hc, ox:ox + Wc])
+            return sample
+        check(self.lib.nint_head_skill_accum(ptr(ws.h[-1]), ws.T * B, B, Ch, Chp, O, ptr(w2), ptr(b2), ptr(yv), sl, acc.nslots,
+                                             ptr(acc.row_w), ptr(acc.pix), ptr(sample), ptr(pred_out), ptr(scratch),
+                                             scratch.numel() * 8, C.byref(ws.g), oy, ox, Hc, Wc, self.dt, stream_ptr()),
+              "nint_head_skill_accum")
+        return sample
+
     def head_backward(self, ws: Workspace, w: torch.Tensor, dpred: torch.Tensor, dw_out=None, db_out=None, write_dh: bool = True,
                       images: Optional[Tuple[int, int]] = None):
         """Writes dL/dh_{T-1} of the last layer into ws.dh[-1] (unless `write_dh` is False: the fused head/loss pass

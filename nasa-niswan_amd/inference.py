@@ -1,12 +1,19 @@
 """Inference helpers around the HIP forward path, mirroring the reference's analysis notebook:
-test-set prediction with de-normalisation (test.ipynb cell 8, :257-300) and the one-at-a-time
-(OAT) input-perturbation sweep (test.ipynb cell 56, :2433-2461).  Forward only, `torch.no_grad()`."""
+test-set prediction with de-normalisation (test.ipynb cell 8, :257-300), the one-at-a-time
+(OAT) input-perturbation sweep (test.ipynb cell 56, :2433-2461) and the evaluation cells -- R2 per
+window and per grid cell, time-mean maps, cos-latitude weighted means (:377-385, :462-485, :605, :630,
+:684-693, :796-803) -- from f64 sums kept on the device (`evaluate_skill`, `SkillAccumulator`,
+`skill_from_sums`).  Forward only, `torch.no_grad()`."""
 from __future__ import annotations
 
-from typing import Sequence, Tuple
+import ctypes as C
+from dataclasses import dataclass, fields
+from typing import Callable, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
+
+NINT_SKILL_PIX, NINT_SKILL_SAMPLE = 5, 8      # include/nint.h
 
 
 @torch.no_grad()
@@ -50,3 +57,228 @@ def oat_sensitivity(net, dataset, num_ftrs: int = 5, perturbed_values: float = 0
             pds.append(p.cpu().numpy() * dataset.y_std + dataset.y_mean)
         outs.append(np.concatenate(pds))
     return np.stack(outs)
+
+
+# ------------------------------------------------------------------------------ test-period skill from device-side sums
+@dataclass
+class SkillReport:
+    """What the notebook's evaluation cells compute, in physical units.  Maps are (O, Hc, Wc) over the chosen slots' samples;
+    per-sample series are in evaluation order."""
+    r2_spatial: np.ndarray               # R2 per grid cell over time (test.ipynb:462-485)
+    rmse: np.ndarray
+    bias: np.ndarray                     # mean of p - y
+    pearson: np.ndarray                  # nan where the target or the prediction is constant over time (as np.corrcoef)
+    mean_gt: np.ndarray                  # time-mean maps (:605, :630)
+    mean_pd: np.ndarray
+    r2_temporal: np.ndarray              # (N): R2 per window, outputs pooled (:377-385, the notebook's flatten())
+    r2_temporal_per_output: np.ndarray   # (N, O)
+    loss: np.ndarray                     # (N): MSE + L1 in z-score units (train.py:102,105)
+    global_mean_gt: np.ndarray           # (N, O): row-weighted (cos latitude) mean over the grid (:796-803)
+    global_mean_pd: np.ndarray
+    r2: float                            # pooled over every sample, output and grid cell
+    count: float                         # samples behind the maps
+
+    def arrays(self) -> dict:
+        return {f.name: np.asarray(getattr(self, f.name)) for f in fields(self)}
+
+
+def _two_prod(a, b):
+    """a * b = p + e exactly (Dekker's product with Veltkamp's split): the rounded product and its rounding error"""
+    p = a * b
+    ca, cb = 134217729.0 * a, 134217729.0 * b
+    ah, bh = ca - (ca - a), cb - (cb - b)
+    al, bl = a - ah, b - bh
+    return p, ((ah * bh - p) + ah * bl + al * bh) + al * bl
+
+
+def _centred(sqq, sq, n):
+    """sum (q - mean q)^2 = sum q^2 - (sum q)^2 / n from f64 sums of n terms.  (sum q)^2 / n is formed in double-double
+    arithmetic: where the target barely varies (a tracer that is zero in six of a group's seven windows) the difference is 1e-5 of
+    sum q^2 and R2 is -1e4 ... -1e5, so the two roundings of the plain f64 expression alone would move R2 by 1e-7; the sums
+    themselves are exact or nearly so there (few f32 values and their squares add without rounding in f64).
+    A result below the rounding error that the n additions behind each sum may have left, (n + 4) eps sum q^2, is taken as exactly
+    0: a constant q then counts as constant for any n; in exact arithmetic only values that agree to about 1e-7 relative fall
+    under it."""
+    sqq, sq = np.asarray(sqq, dtype=np.float64), np.asarray(sq, dtype=np.float64)
+    n = float(n)
+    p, e = _two_prod(sq, sq)
+    hi = p / n
+    ph, pe = _two_prod(hi, np.float64(n))
+    lo = (((p - ph) - pe) + e) / n                      # (sum q)^2 / n = hi + lo to ~1e-32 relative
+    tot = (sqq - hi) - lo
+    return np.where(tot > (n + 4.0) * np.finfo(np.float64).eps * sqq, tot, 0.0)
+
+
+def _r2(ss_res, ss_tot):
+    """1 - ss_res / ss_tot with sklearn's constant-target convention: ss_tot == 0 gives 1.0 when ss_res == 0, else 0.0"""
+    ss_res, ss_tot = np.asarray(ss_res, dtype=np.float64), np.asarray(ss_tot, dtype=np.float64)
+    ok = ss_tot > 0
+    return np.where(ok, 1.0 - ss_res / np.where(ok, ss_tot, 1.0), np.where(ss_res == 0, 1.0, 0.0))
+
+
+def skill_from_sums(pix, counts, sample, row_w=None, y_mean: float = 0.0, y_std: float = 1.0,
+                    slots: Optional[Sequence[int]] = None) -> SkillReport:
+    """The f64 sums of nint_skill_accum / nint_head_skill_accum (z-score units) -> a SkillReport in physical units
+    (value * y_std + y_mean).  Pure numpy f64; needs no GPU.
+
+    pix (nslots, 5, O, Hc, Wc): per slot and grid cell sum y, sum p, sum y^2, sum p^2, sum (y-p)^2; counts (nslots): samples
+    per slot; sample (N, O, 8): per sample and output sum (y-p)^2, sum |y-p|, sum y, sum y^2, sum p, sum p^2, sum row_w*y,
+    sum row_w*p over the grid; row_w (Hc) the row weights the last two were formed with (None: 1).  `slots`: the union of
+    slots behind the maps (None: all) -- the slots partition the samples, so a union is the sum of its slots' planes.
+
+    The statistics are formed in z-score units and de-normalised analytically: R2 and r do not change under the affine map,
+    means shift and scale, rmse and bias scale -- which keeps sum y^2 - (sum y)^2 / n free of the cancellation that physical
+    units (mean >> spread) would bring.
+
+    R2 follows sklearn's constant-target convention everywhere (as loss_final_kernel does): ss_tot == 0 gives 1.0 when
+    ss_res == 0, else 0.0; an ss_tot below the rounding error of its own computation counts as 0 (_centred).  The notebook's vectorised r_squared_spatial (test.ipynb:480-485) yields nan / -inf there; its
+    r2_score loop (:462-470) yields these values."""
+    pix = np.asarray(pix, dtype=np.float64)
+    counts = np.asarray(counts, dtype=np.float64)
+    sample = np.asarray(sample, dtype=np.float64)
+    nslots, npl, O, Hc, Wc = pix.shape
+    assert npl == NINT_SKILL_PIX and counts.shape == (nslots,) and sample.shape[1:] == (O, NINT_SKILL_SAMPLE)
+    sel = list(range(nslots)) if slots is None else [int(v) for v in slots]
+    sy, sp, syy, spp, sdd = pix[sel].sum(axis=0)
+    n = float(counts[sel].sum())
+    sig, mu = float(y_std), float(y_mean)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        inv = 1.0 / n if n > 0 else np.nan
+        tot_y, tot_p = (_centred(syy, sy, n), _centred(spp, sp, n)) if n > 0 else (syy * np.nan, spp * np.nan)
+        cov = 0.5 * (syy + spp - sdd) - sy * sp * inv                     # sum y p from (y-p)^2 = y^2 + p^2 - 2 y p
+        pearson = np.where((tot_y > 0) & (tot_p > 0), cov / np.sqrt(np.where(tot_y > 0, tot_y, 1.0) * np.where(tot_p > 0, tot_p, 1.0)), np.nan)
+        rep = dict(r2_spatial=_r2(sdd, tot_y), rmse=sig * np.sqrt(sdd * inv), bias=sig * (sp - sy) * inv, pearson=pearson,
+                   mean_gt=mu + sig * sy * inv, mean_pd=mu + sig * sp * inv)
+    # per sample, over the grid
+    npx = float(Hc * Wc)
+    d2, d1, ty, tyy = sample[..., 0], sample[..., 1], sample[..., 2], sample[..., 3]
+    rep["r2_temporal_per_output"] = _r2(d2, _centred(tyy, ty, npx))
+    rep["r2_temporal"] = _r2(d2.sum(axis=1), _centred(tyy.sum(axis=1), ty.sum(axis=1), O * npx))
+    rep["loss"] = d2.sum(axis=1) / (O * npx) + d1.sum(axis=1) / (O * npx)
+    wsum = Wc * (float(Hc) if row_w is None else float(np.asarray(row_w, dtype=np.float64).sum()))
+    rep["global_mean_gt"] = mu + sig * sample[..., 6] / wsum
+    rep["global_mean_pd"] = mu + sig * sample[..., 7] / wsum
+    nall = sample.shape[0] * O * npx
+    rep["r2"] = float(_r2(d2.sum(), _centred(tyy.sum(), ty.sum(), nall))) if nall else float("nan")
+    return SkillReport(count=n, **rep)
+
+
+class SkillAccumulator:
+    """Device-side accumulators of one evaluation: `pix` (nslots, 5, O, Hc, Wc) f64, the per-sample sums of every batch seen
+    (a growing (n_samples, O, 8) table) and the kernels' scratch.  `lat`: Hc latitudes in degrees, row_w = cos(deg2rad(lat))
+    (test.ipynb:796); None = uniform weights.  `halo`: (oy, ox) of the crop inside the model grid; None = centred.
+    The slots of a sample are host knowledge, so the per-slot sample counts are counted on the host; `counts` hands them out
+    as an f64 device tensor (what a data-parallel reduction would add up with `pix`)."""
+
+    def __init__(self, O: int, Hc: int, Wc: int, nslots: int = 1, lat=None, device="cuda", halo: Optional[Tuple[int, int]] = None):
+        from . import _lib
+        self.lib = _lib.load()
+        self.O, self.Hc, self.Wc, self.nslots = int(O), int(Hc), int(Wc), int(nslots)
+        if self.nslots < 1:
+            raise ValueError("nslots must be >= 1")
+        self.device = torch.device(device)
+        self.halo = None if halo is None else (int(halo[0]), int(halo[1]))
+        self.row_w_host = None
+        self.row_w = None
+        if lat is not None:
+            lat = np.asarray(lat, dtype=np.float64)
+            if lat.shape != (self.Hc,):
+                raise ValueError(f"lat: expected {self.Hc} latitudes, got {lat.shape}")
+            self.row_w_host = np.cos(np.deg2rad(lat))
+            self.row_w = torch.from_numpy(self.row_w_host).to(self.device)   # f64 on the device too
+        self.pix = torch.zeros(self.nslots, NINT_SKILL_PIX, self.O, self.Hc, self.Wc, dtype=torch.float64, device=self.device)
+        self._counts = np.zeros(self.nslots, dtype=np.float64)
+        self._rows = []
+        self._scratch = None
+
+    @property
+    def counts(self) -> torch.Tensor:
+        return torch.from_numpy(self._counts.copy()).to(self.device)
+
+    @property
+    def n_samples(self) -> int:
+        return sum(int(r.shape[0]) for r in self._rows)
+
+    def scratch_for(self, N: int) -> torch.Tensor:
+        need = self.lib.nint_skill_scratch_bytes(int(N), self.O, self.Hc, self.Wc) // 8
+        if self._scratch is None or self._scratch.numel() < need:
+            self._scratch = torch.empty(need, dtype=torch.float64, device=self.device)
+        return self._scratch
+
+    def _slots(self, slots, N: int):
+        sl = [0] * N if slots is None else [int(v) for v in slots]
+        if len(sl) != N or any(v < -1 or v >= self.nslots for v in sl):
+            raise ValueError(f"slots: {N} values in [-1, {self.nslots}) expected")
+        return sl
+
+    def _count(self, sl):
+        for v in sl:
+            if v >= 0:
+                self._counts[v] += 1.0
+
+    def update(self, eng, ws, w, b, y, slots=None, pred_out=None):
+        """One batch through the fused pass (SeqEngine.head_skill) after eng.forward(ws, X)."""
+        sl = self._slots(slots, ws.B)
+        self._rows.append(eng.head_skill(ws, w, b, y, sl, self, pred_out=pred_out))
+        self._count(sl)
+
+    def update_from_pred(self, pred: torch.Tensor, y: torch.Tensor, halo: Tuple[int, int], slots=None):
+        """One batch from a prediction (N, O, H, W) that is already in memory (nint_skill_accum)."""
+        from ._lib import check, ptr, stream_ptr
+        pv = pred.detach().float().contiguous()
+        N, O, H, W = pv.shape
+        yv = y.detach().float().contiguous()
+        assert O == self.O and yv.numel() == N * O * self.Hc * self.Wc, "target must be (N,[O,]Hc,Wc)"
+        sl = self._slots(slots, N)
+        sample = torch.empty(N, O, NINT_SKILL_SAMPLE, dtype=torch.float64, device=self.device)
+        scratch = self.scratch_for(N)
+        check(self.lib.nint_skill_accum(ptr(pv), ptr(yv), (C.c_int32 * N)(*sl), self.nslots, ptr(self.row_w), ptr(self.pix),
+                                        ptr(sample), ptr(scratch), scratch.numel() * 8, N, O, H, W, int(halo[0]), int(halo[1]),
+                                        self.Hc, self.Wc, stream_ptr()), "nint_skill_accum")
+        self._rows.append(sample)
+        self._count(sl)
+
+    def sums(self):
+        """(pix, counts, sample) as numpy f64: ONE device-to-host read"""
+        rows = torch.cat(self._rows) if self._rows else torch.empty(0, self.O, NINT_SKILL_SAMPLE, dtype=torch.float64, device=self.device)
+        flat = torch.cat([self.pix.reshape(-1), rows.reshape(-1)]).cpu().numpy()
+        return (flat[:self.pix.numel()].reshape(tuple(self.pix.shape)), self._counts.copy(),
+                flat[self.pix.numel():].reshape(-1, self.O, NINT_SKILL_SAMPLE))
+
+    def report(self, y_mean: float = 0.0, y_std: float = 1.0, slots: Optional[Sequence[int]] = None) -> SkillReport:
+        pix, counts, sample = self.sums()
+        return skill_from_sums(pix, counts, sample, self.row_w_host, y_mean, y_std, slots)
+
+
+@torch.no_grad()
+def evaluate_skill(net, dataset, batch_size: int = 8, halo: Tuple[int, int] = (5, 5), indices: Sequence[int] = None,
+                   groups: Union[None, Sequence[int], Callable[[int], int]] = None, lat=None, return_predictions: bool = False):
+    """Test-period skill without gathering the predictions: per batch forward + ONE pass that applies the head to the last
+    hidden state and folds the result into f64 sums on the device (no host synchronisation in the loop, one read at the end).
+    Returns the SkillAccumulator -- `.report(dataset.y_mean, dataset.y_std[, slots])` gives the notebook's quantities for all
+    samples or a union of groups -- and, with `return_predictions`, the z-score-unit crop (N, O, Hc, Wc) as a device tensor.
+
+    `groups`: the slot of each dataset index (an int array indexed by dataset index, or a callable), e.g. the month of the
+    window's target step; -1 keeps a sample out of the maps.  None: one slot.
+    The last step's prediction only: the sums are additive, so per-step (`return_sequence`) skill and a data-parallel
+    reduction can be added on top."""
+    net.eval()
+    dev = next(net.parameters()).device
+    eng = net._engine(dev)
+    idx = list(range(len(dataset))) if indices is None else [int(i) for i in indices]
+    slot_of = (lambda i: 0) if groups is None else (groups if callable(groups) else (lambda i: int(groups[i])))
+    slots_all = [int(slot_of(i)) for i in idx]
+    nslots = max([v for v in slots_all if v >= 0], default=0) + 1
+    Hc, Wc = dataset.grid
+    O = net.conv.weight.shape[0]
+    acc = SkillAccumulator(O, Hc, Wc, nslots=nslots, lat=lat, device=dev, halo=halo)
+    preds = torch.empty(len(idx), O, Hc, Wc, dtype=torch.float32, device=dev) if return_predictions else None
+    for s in range(0, len(idx), batch_size):
+        X, y = dataset.slab_batch(idx[s:s + batch_size])
+        B, T, _, H, W = X.shape
+        ws = eng.acquire(B, T, H, W, False, False)
+        eng.pack_weights([c.conv.weight for c in net.layers], [c.conv.bias for c in net.layers])
+        eng.forward(ws, X)
+        acc.update(eng, ws, net.conv.weight, net.conv.bias, y, slots_all[s:s + B], pred_out=None if preds is None else preds[s:s + B])
+        eng.release(ws)
+    return (acc, preds) if return_predictions else acc

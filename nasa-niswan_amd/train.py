@@ -5,7 +5,7 @@ MI355X step.  Same flags, same artefacts (`configurations.json`, `logger.npy`,
 stepped once per epoch before validation, checkpoint every 10 epochs); the per-batch
 `loss.item()` / sklearn R2 host syncs (train.py:113-114) are replaced by device accumulators read
 once per epoch.  Added flags: --dtype, --levels, --grid, --synthetic-steps, --pad-mode, --f32-inputs,
---static-channels, --sequence-loss.
+--static-channels, --sequence-loss, --test-skill.
 
 The data path is on the device too: by default every batch is written by ONE launch of the
 fuse / z-score / halo-pad kernel straight into the model's bf16 input slab (dataset.slab_batch);
@@ -76,6 +76,10 @@ def get_arguments(argv=None, MODEL='LSTM-00', SPECIES='bcb', LEARNING_RATE=1.0E-
     parser.add_argument("--sequence-loss", action="store_true",
                         help="sequence-to-sequence supervision: the target is the tracer at every step of the window and the loss "
                              "(training and validation) runs over the head's output at every step, not the last one alone")
+    parser.add_argument("--test-skill", action="store_true",
+                        help="after the last epoch rank 0 evaluates the 'test' period on the device (inference.evaluate_skill: R2 per "
+                             "window and per grid cell, rmse, bias, time means, cos-latitude weighted means; test.ipynb's evaluation "
+                             "cells) and writes the report's arrays to skill.npz in --snapshot-dir")
     args = parser.parse_args(argv)
     rank = int(os.environ.get("RANK", "0"))
     if rank == 0:
@@ -170,6 +174,17 @@ def main(args):
             np.save(f, np.array(logger['MSELoss']))
             np.save(f, np.array(logger['r2_score']))
             np.save(f, np.array(logger['r2_score_val']))
+        if args.test_skill:
+            # the evaluation cells of test.ipynb on the 'test' period: the last step's prediction, sums kept on the device
+            from nasa_niswan_amd.inference import evaluate_skill
+            test_dataset = SyntheticE33OMA_CRNN('test', **dict(ds_kw, sequence_targets=False))
+            lat = -90.0 + (np.arange(H) + 0.5) * (180.0 / H)                                 # cell centres of the H-row global grid
+            report = evaluate_skill(generator, test_dataset, batch_size=args.batch_size, halo=halo, lat=lat).report(
+                test_dataset.y_mean, test_dataset.y_std)
+            np.savez(os.path.join(args.snapshot_dir, "skill.npz"), **report.arrays())
+            logger['skill'] = report
+            print(f"Test period ({len(test_dataset)} windows): mean R2 per window {np.mean(report.r2_temporal):.5f}, "
+                  f"mean R2 per grid cell {np.mean(report.r2_spatial):.5f}")
         time_elapsed = time.time() - since
         print(f'Training complete in {time_elapsed // 60:.0f}m {time_elapsed % 60:.0f}s')
     if world > 1:

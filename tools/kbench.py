@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-kernel micro-benchmark at the bench workload's shapes (HIP events on the launch stream).
-    python tools/kbench.py [--dtype bf16] [--batch 8] [--iters 20] [--only fwd0,dgrad0,...]
+    python tools/kbench.py [--dtype bf16] [--batch 8] [--iters 20] [--only fwd0,dgrad0,head_skill,...]
 Prints one line per kernel: average ms, algorithmic TFLOP/s (or GB/s)."""
 import argparse
 import ctypes as C
@@ -31,6 +31,7 @@ def main():
     ap.add_argument("--T", type=int, default=12)
     ap.add_argument("--C", type=int, default=62)
     ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--O", type=int, default=20, help="head outputs of the evaluation rows (head_fwd, head_skill, skill_plain)")
     ap.add_argument("--only", default="")
     ap.add_argument("--H", type=int, default=100)
     ap.add_argument("--W", type=int, default=154)
@@ -149,7 +150,39 @@ def main():
         alg = B * T * args.C * H * W
         run("preproc_slab", lambda: sb.fill_slab(eng, ws), None, alg * (4 + es))     # 4 B in + ET out per element
         run("preproc_nchw", lambda: ds.device_batch(idx), None, alg * 8)
-    tot = sum(ms * (T if not n.startswith(("wgrad", "pack", "preproc")) else 1) for n, ms in rows if n != "preproc_nchw")
+    if not only or only & {"head_skill", "skill_plain", "head_fwd"}:
+        # evaluation: the head on the last step's images + crop + the f64 skill sums in one pass (nint_head_skill_accum), and the
+        # same sums from a prediction in memory (nint_skill_accum), one slot, cos-latitude row weights
+        O, oy, ox = args.O, 5, 5
+        Hc, Wc = H - 2 * oy, W - 2 * ox
+        ly = eng.layers[-1]
+        hw = torch.randn(O, ly.Ch, device="cuda") * 0.3
+        hb = torch.randn(O, device="cuda")
+        y = torch.randn(B, O, Hc, Wc, device="cuda")
+        pix = torch.zeros(1, 5, O, Hc, Wc, dtype=torch.float64, device="cuda")
+        smp = torch.empty(B, O, 8, dtype=torch.float64, device="cuda")
+        nb = lib.nint_skill_scratch_bytes(B, O, Hc, Wc)
+        scr = torch.empty(nb // 8, dtype=torch.float64, device="cuda")
+        rw = torch.cos(torch.deg2rad(torch.linspace(-89, 89, Hc, dtype=torch.float64, device="cuda")))
+        pred = torch.randn(B, O, H, W, device="cuda")
+        P = lambda t: C.c_void_p(t.data_ptr())
+
+        def head_fwd():
+            assert lib.nint_head_fwd(P(ws.h[-1]), T * B, B, ly.Ch, ly.Chp, O, P(hw), P(hb), P(pred), g, eng.dt, st) == 0
+
+        def head_skill():
+            assert lib.nint_head_skill_accum(P(ws.h[-1]), T * B, B, ly.Ch, ly.Chp, O, P(hw), P(hb), P(y), None, 1, P(rw), P(pix), P(smp),
+                                             None, P(scr), nb, g, oy, ox, Hc, Wc, eng.dt, st) == 0
+
+        def skill_plain():
+            assert lib.nint_skill_accum(P(pred), P(y), None, 1, P(rw), P(pix), P(smp), P(scr), nb, B, O, H, W, oy, ox, Hc, Wc, st) == 0
+        part = 2 * nb                                             # the per-wave partial rows, written and read back
+        maps = 2 * pix.numel() * 8 + y.numel() * 4 + part         # pix read + written once per call, the targets
+        run("head_fwd", head_fwd, None, B * comp_px * (ly.Chp * es + O * 4))
+        run("head_skill", head_skill, None, B * Hc * Wc * ly.Chp * es + maps)
+        run("skill_plain", skill_plain, None, B * O * Hc * Wc * 4 + maps)
+    tot = sum(ms * (T if not n.startswith(("wgrad", "pack", "preproc")) else 1) for n, ms in rows
+              if n != "preproc_nchw" and not n.startswith(("head_", "skill_")))      # (the evaluation rows are no part of a training step)
     print(f"sum over a step (T x per-step kernels + wgrad + pack): {tot:.2f} ms")
 
 
