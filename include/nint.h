@@ -345,6 +345,37 @@ int nint_head_loss_seq_fused(const void* h_slab, int B, int T, int Ch, int Chp, 
                              const float* y, float* dpred, void* dh_seq, float* loss_out, double* stats, const nint_geom* g,
                              int oy, int ox, int Hc, int Wc, int dtype, void* stream);
 
+/* ---- the same loss with a weight per crop cell: cos-latitude area weights, masks, or their product ---------- */
+/* wgt: f32 [Hc][Wc] on the device, 4-byte aligned, shared by every sample, output and time step of the call; every value
+ * finite and >= 0, at least one > 0 (the caller validates the values: the library reads them on the device only).  A mask is
+ * a map of 0 / 1; cos-latitude weights are cos(deg2rad(lat[cy])) along row cy.  wsum: the f64 sum of the map AS STORED in
+ * f32, formed on the host by the caller; cnt = N * O * wsum (T * B * O * wsum for the sequence entry) stands where the
+ * unweighted entries have N * O * Hc * Wc.
+ *   per crop cell, w = wgt[cy][cx], d = p - y in f32 (as in the unweighted entries):
+ *   loss   = (sum w d^2) / cnt + (sum w |d|) / cnt, the sums in f64 with (double)w, the same two-stage fixed-order
+ *            reduction as the unweighted entries
+ *   dpred  = (float)(((2.0 * d + sgn(d)) * (1.0 / cnt)) * (double)w), evaluated left to right in f64, rounded once;
+ *            +0 outside the crop
+ *   w == 0 : the cell is skipped -- target and prediction enter no sum, dpred = +0; a NaN target under a zero weight is
+ *            harmless (this is how missing data is masked)
+ *   stats  : [0..4] += sum w d^2, sum w |d|, sum w y, sum w y^2, cnt; [5] += loss; [6] += the weighted R2
+ *            1 - S0 / (S3 - S2^2 / cnt) = sklearn r2_score(y, p, sample_weight = w), the constant-target convention of
+ *            the unweighted entries applied to the weighted ss_tot; [7] += 1
+ * wgt = 1 everywhere and wsum = Hc * Wc give the unweighted entries' results bit for bit.
+ * Each entry mirrors its twin above (arguments, limits, checks before any launch, the fused entries bit-identical to
+ * nint_head_fwd[_seq] -> nint_loss_mse_l1_crop_weighted -> nint_head_bwd[_seq]); in addition wgt == NULL, !(wsum > 0) or a
+ * non-finite wsum: NINT_E_ARG; wgt not 4-byte aligned: NINT_E_ALIGN.  The map is read from global memory: no LDS on top. */
+int nint_loss_mse_l1_crop_weighted(const float* pred, const float* y, const float* wgt, double wsum, float* dpred,
+                                   float* loss_out, double* stats, int N, int O, int H, int W, int oy, int ox, int Hc, int Wc,
+                                   void* stream);
+int nint_head_loss_fused_weighted(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w, const float* b,
+                                  const float* y, const float* wgt, double wsum, float* dpred, void* dh, float* loss_out,
+                                  double* stats, const nint_geom* g, int oy, int ox, int Hc, int Wc, int dtype, void* stream);
+int nint_head_loss_seq_fused_weighted(const void* h_slab, int B, int T, int Ch, int Chp, int O, const float* w, const float* b,
+                                      const float* y, const float* wgt, double wsum, float* dpred, void* dh_seq,
+                                      float* loss_out, double* stats, const nint_geom* g, int oy, int ox, int Hc, int Wc,
+                                      int dtype, void* stream);
+
 /* ---- evaluation: skill sums (test.ipynb:377-385, :462-485, :605, :630, :684-693, :796-803) ------------ */
 /* Everything the analysis notebook derives from the gathered test-period predictions -- one R2 per window, one R2 per grid
  * cell over time, time-mean maps, cos-latitude weighted means -- follows from running f64 sums, formed on the device in one

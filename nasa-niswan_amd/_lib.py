@@ -50,7 +50,7 @@ class NintLaunchRec(C.Structure):
 
 
 # every symbol include/nint.h declares: name -> (restype, argtypes)
-_I, _SZ, _F = C.c_int, C.c_size_t, C.c_float
+_I, _SZ, _F, _D = C.c_int, C.c_size_t, C.c_float, C.c_double
 _PG, _PL, _PS = C.POINTER(NintGeom), C.POINTER(NintLayer), C.POINTER(NintSeq)
 SIGNATURES = {
     "nint_version": (_I, []),
@@ -86,6 +86,9 @@ SIGNATURES = {
     "nint_loss_mse_l1_crop": (_I, [vp, vp, vp, vp, vp, _I, _I, _I, _I, _I, _I, _I, _I, vp]),
     "nint_head_loss_fused": (_I, [vp, _I, _I, _I, _I, _I, vp, vp, vp, vp, vp, vp, vp, _PG, _I, _I, _I, _I, _I, vp]),
     "nint_head_loss_seq_fused": (_I, [vp, _I, _I, _I, _I, _I, vp, vp, vp, vp, vp, vp, vp, _PG, _I, _I, _I, _I, _I, vp]),
+    "nint_loss_mse_l1_crop_weighted": (_I, [vp, vp, vp, _D, vp, vp, vp, _I, _I, _I, _I, _I, _I, _I, _I, vp]),
+    "nint_head_loss_fused_weighted": (_I, [vp, _I, _I, _I, _I, _I, vp, vp, vp, vp, _D, vp, vp, vp, vp, _PG, _I, _I, _I, _I, _I, vp]),
+    "nint_head_loss_seq_fused_weighted": (_I, [vp, _I, _I, _I, _I, _I, vp, vp, vp, vp, _D, vp, vp, vp, vp, _PG, _I, _I, _I, _I, _I, vp]),
     "nint_skill_scratch_bytes": (_SZ, [_I, _I, _I, _I]),
     "nint_skill_accum": (_I, [vp, vp, C.POINTER(C.c_int32), _I, vp, vp, vp, vp, _SZ, _I, _I, _I, _I, _I, _I, _I, _I, vp]),
     "nint_head_skill_accum": (_I, [vp, _I, _I, _I, _I, _I, vp, vp, vp, C.POINTER(C.c_int32), _I, vp, vp, vp, vp, vp, _SZ, _PG,

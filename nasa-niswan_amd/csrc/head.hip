@@ -4,6 +4,7 @@
 // function under ONE __global__ wrapper templated on SEQ: the register allocation depends on that function boundary.
 #include "nint_common.h"
 #include <algorithm>
+#include <cfloat>
 #include <climits>
 
 // ------------------------------------------------------------------------------ 1x1 head
@@ -564,11 +565,16 @@ extern "C" int nint_head_bwd_seq(const void* h_slab, int B, int T, int Ch, int C
 // train.py:102,105: crop, MSELoss + L1Loss (mean).  Two launches on the same stream:
 //  (1) per-block partial sums in double (fixed order), (2) one block folds them, writes
 //  the loss and adds to the 5 running statistics.  dpred = (2(p-y) + sign(p-y)) / n on the crop.
+// WGT (the _weighted entries; nint.h has the arithmetic): every term of a crop cell carries the cell's weight wgt[cy][cx] as
+// a double factor, n becomes cnt = N * O * sum(wgt), and a cell of weight 0 is skipped -- its target is not read.  The
+// unweighted instances receive (wgt, cnt) without reading them; with wgt = 1 the weighted ones give the same bits.
+template <bool WGT>
 __global__ __launch_bounds__(1024) void loss_partial_kernel(const float* __restrict__ pred, const float* __restrict__ y,
                                                            float* __restrict__ dpred, double* __restrict__ partial,
-                                                           int N, int O, int H, int W, int oy, int ox, int Hc, int Wc) {
+                                                           int N, int O, int H, int W, int oy, int ox, int Hc, int Wc,
+                                                           const float* __restrict__ wgt, double cnt) {
   const size_t total = (size_t)N * O * H * W;
-  const double inv_n = 1.0 / ((double)N * O * Hc * Wc);
+  const double inv_n = 1.0 / (WGT ? cnt : (double)N * O * Hc * Wc);
   double s2 = 0, s1 = 0, sy = 0, syy = 0;
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
     const int x = i % W;
@@ -578,13 +584,27 @@ __global__ __launch_bounds__(1024) void loss_partial_kernel(const float* __restr
     const int cy = yy - oy, cx = x - ox;
     float g = 0.f;
     if (cy >= 0 && cy < Hc && cx >= 0 && cx < Wc) {
-      const float t = y[(no * Hc + cy) * Wc + cx];
-      const float d = pred[i] - t;
-      s2 += (double)d * d;
-      s1 += fabs((double)d);
-      sy += t;
-      syy += (double)t * t;
-      g = (float)((2.0 * d + (d > 0.f ? 1.0 : (d < 0.f ? -1.0 : 0.0))) * inv_n);
+      if constexpr (WGT) {
+        const float wf = wgt[(size_t)cy * Wc + cx];
+        if (wf != 0.f) {
+          const double wd = wf;
+          const float t = y[(no * Hc + cy) * Wc + cx];
+          const float d = pred[i] - t;
+          s2 += wd * ((double)d * d);
+          s1 += wd * fabs((double)d);
+          sy += wd * t;
+          syy += wd * ((double)t * t);
+          g = (float)(((2.0 * d + (d > 0.f ? 1.0 : (d < 0.f ? -1.0 : 0.0))) * inv_n) * wd);
+        }
+      } else {
+        const float t = y[(no * Hc + cy) * Wc + cx];
+        const float d = pred[i] - t;
+        s2 += (double)d * d;
+        s1 += fabs((double)d);
+        sy += t;
+        syy += (double)t * t;
+        g = (float)((2.0 * d + (d > 0.f ? 1.0 : (d < 0.f ? -1.0 : 0.0))) * inv_n);
+      }
     }
     if (dpred) dpred[i] = g;
   }
@@ -634,17 +654,36 @@ __global__ __launch_bounds__(256) void loss_final_kernel(const double* __restric
 // carved from loss_out[1..]: loss_out must have room for 1 + 2*LOSS_BLOCKS*4 floats.
 #define LOSS_BLOCKS 256
 #define LOSS_BLOCKS_MAX ((NINT_LOSS_SCRATCH_FLOATS - 2) / 8)     // what the caller's scratch holds: 4 doubles per workgroup
+// WGT: cnt = N * O * wsum of the weighted entry (the unweighted kernels form N * O * Hc * Wc themselves)
+template <bool WGT>
+static int loss_impl(const float* pred, const float* y, const float* wgt, double cnt, float* dpred, float* loss_out, double* stats,
+                     int N, int O, int H, int W, int oy, int ox, int Hc, int Wc, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  double* partial = (double*)(loss_out + 2);   // loss_out: [0]=loss, [1]=pad, [2..] = 256*4 doubles
+  hipLaunchKernelGGL(loss_partial_kernel<WGT>, dim3(LOSS_BLOCKS), dim3(1024), 0, st, pred, y, dpred, partial, N, O, H, W, oy, ox, Hc, Wc, wgt, cnt);
+  NINT_LAUNCH_CHECK();
+  hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(256), 0, st, partial, LOSS_BLOCKS, loss_out, stats, WGT ? cnt : (double)N * O * Hc * Wc);
+  NINT_LAUNCH_CHECK();
+  return NINT_OK;
+}
+
 extern "C" int nint_loss_mse_l1_crop(const float* pred, const float* y, float* dpred, float* loss_out, double* stats,
                                      int N, int O, int H, int W, int oy, int ox, int Hc, int Wc, void* stream) {
   if (!pred || !y || !loss_out || N <= 0 || O <= 0 || oy < 0 || ox < 0 || oy + Hc > H || ox + Wc > W) return NINT_E_ARG;
   if ((((uintptr_t)loss_out) & 7) != 0) return NINT_E_ALIGN;
-  hipStream_t st = (hipStream_t)stream;
-  double* partial = (double*)(loss_out + 2);   // loss_out: [0]=loss, [1]=pad, [2..] = 256*4 doubles
-  hipLaunchKernelGGL(loss_partial_kernel, dim3(LOSS_BLOCKS), dim3(1024), 0, st, pred, y, dpred, partial, N, O, H, W, oy, ox, Hc, Wc);
-  NINT_LAUNCH_CHECK();
-  hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(256), 0, st, partial, LOSS_BLOCKS, loss_out, stats, (double)N * O * Hc * Wc);
-  NINT_LAUNCH_CHECK();
-  return NINT_OK;
+  return loss_impl<false>(pred, y, nullptr, 0.0, dpred, loss_out, stats, N, O, H, W, oy, ox, Hc, Wc, stream);
+}
+
+// the weight map of the _weighted entries: present, and a total that is positive and finite (!(wsum > 0) also catches NaN)
+static inline bool loss_weights_ok(const float* wgt, double wsum) { return wgt && wsum > 0.0 && wsum <= DBL_MAX; }
+
+extern "C" int nint_loss_mse_l1_crop_weighted(const float* pred, const float* y, const float* wgt, double wsum, float* dpred,
+                                              float* loss_out, double* stats, int N, int O, int H, int W, int oy, int ox,
+                                              int Hc, int Wc, void* stream) {
+  if (!pred || !y || !loss_out || N <= 0 || O <= 0 || oy < 0 || ox < 0 || oy + Hc > H || ox + Wc > W) return NINT_E_ARG;
+  if (Hc <= 0 || Wc <= 0 || !loss_weights_ok(wgt, wsum)) return NINT_E_ARG;
+  if ((((uintptr_t)loss_out) & 7) != 0 || (((uintptr_t)wgt) & 3) != 0) return NINT_E_ALIGN;
+  return loss_impl<true>(pred, y, wgt, (double)N * O * wsum, dpred, loss_out, stats, N, O, H, W, oy, ox, Hc, Wc, stream);
 }
 
 // ------------------------------------------------------------------------------ head + loss, fused (training)
@@ -655,12 +694,15 @@ extern "C" int nint_loss_mse_l1_crop(const float* pred, const float* y, float* d
 #define HEAD_OCH 64
 // SEQ (nint_head_loss_seq_fused): the images are all T*B steps of the slab, image n = t*B + b; the targets are (B, T, O, Hc, Wc),
 // plane block b*T + t (head_image); dpred and dh stay in image order, which is what the weight-gradient stage and BPTT read.
-template <int DT, int CHV, bool SEQ>
+// WGT (the _weighted entries): loss_partial_kernel<true>'s terms; the pixel's weight is read once per pass, next to the crop
+// test, and a cell of weight 0 leaves the crop: neither its targets nor its prediction enter anything.
+template <int DT, int CHV, bool SEQ, bool WGT>
 __device__ __forceinline__ void head_loss_fused_body(char* smem_hl, const void* __restrict__ h, int n0, int N, int Ch, int Chp, int O,
                                                      const float* __restrict__ w, const float* __restrict__ b,
                                                      const float* __restrict__ y, float* __restrict__ dpred,
                                                      void* __restrict__ dh, double* __restrict__ partial, int H, int W,
-                                                     int P, int Hh, int Wh, int oy, int ox, int Hc, int Wc, int Bs) {
+                                                     int P, int Hh, int Wh, int oy, int ox, int Hc, int Wc, int Bs,
+                                                     const float* __restrict__ wgt, double cnt) {
   // A workgroup takes 64 pixels per pass (grid-stride).  Phase 1: wave q runs the outputs [q*OG, (q+1)*OG) of every pixel
   // (lane = pixel): pred, loss terms, d loss / d pred -> dpred and, through LDS, to phase 2: wave q accumulates the
   // channels [q*CHV/4, (q+1)*CHV/4) of dL/dh over ALL outputs in output order.  (One thread per pixel for all outputs --
@@ -671,7 +713,7 @@ __device__ __forceinline__ void head_loss_fused_body(char* smem_hl, const void* 
   const int lane = threadIdx.x & 63;
   const int q = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // (scalar: the weight reads below stay scalar loads)
   const size_t npix = (size_t)N * H * W;
-  const double inv_n = 1.0 / ((double)N * O * Hc * Wc);
+  const double inv_n = 1.0 / (WGT ? cnt : (double)N * O * Hc * Wc);
   constexpr int CQ = CHV / 4;                    // channels per wave in phase 2
   double s2 = 0, s1 = 0, sy = 0, syy = 0;
   for (size_t p0 = (size_t)blockIdx.x * 64; p0 < npix; p0 += (size_t)gridDim.x * 64) {
@@ -690,7 +732,13 @@ __device__ __forceinline__ void head_loss_fused_body(char* smem_hl, const void* 
       hv[c] = v[0]; hv[c + 1] = v[1]; hv[c + 2] = v[2]; hv[c + 3] = v[3];
     }
     const int cy = yy - oy, cx = x - ox;
-    const bool in = live && cy >= 0 && cy < Hc && cx >= 0 && cx < Wc;
+    bool in = live && cy >= 0 && cy < Hc && cx >= 0 && cx < Wc;
+    double wd = 1.0;
+    if constexpr (WGT) {
+      const float wf = in ? wgt[(size_t)cy * Wc + cx] : 0.f;
+      in = in && wf != 0.f;
+      wd = wf;
+    }
     float* dp = dpred + ((size_t)n * O * H + yy) * W + x;
     const float* yp = y + (head_image<SEQ>(n, Bs, N / (SEQ ? Bs : 1)) * O * Hc + cy) * Wc + cx;
     float acc[CQ];
@@ -723,11 +771,19 @@ __device__ __forceinline__ void head_loss_fused_body(char* smem_hl, const void* 
           if (in) {
             const float t = tq[u];
             const float d = p - t;
-            s2 += (double)d * d;
-            s1 += fabs((double)d);
-            sy += t;
-            syy += (double)t * t;
-            gq = (float)((2.0 * d + (d > 0.f ? 1.0 : (d < 0.f ? -1.0 : 0.0))) * inv_n);
+            if constexpr (WGT) {
+              s2 += wd * ((double)d * d);
+              s1 += wd * fabs((double)d);
+              sy += wd * t;
+              syy += wd * ((double)t * t);
+              gq = (float)(((2.0 * d + (d > 0.f ? 1.0 : (d < 0.f ? -1.0 : 0.0))) * inv_n) * wd);
+            } else {
+              s2 += (double)d * d;
+              s1 += fabs((double)d);
+              sy += t;
+              syy += (double)t * t;
+              gq = (float)((2.0 * d + (d > 0.f ? 1.0 : (d < 0.f ? -1.0 : 0.0))) * inv_n);
+            }
           }
           if (live) dp[(size_t)o * H * W] = gq;
           gq_s[(o - oc) * 64 + lane] = gq;
@@ -763,21 +819,22 @@ __device__ __forceinline__ void head_loss_fused_body(char* smem_hl, const void* 
   if (threadIdx.x < 4) partial[blockIdx.x * 4 + threadIdx.x] = red[threadIdx.x][0];
 }
 
-template <int DT, int CHV, bool SEQ>
+template <int DT, int CHV, bool SEQ, bool WGT>
 __global__ __launch_bounds__(256) void head_loss_fused_kernel(const void* __restrict__ h, int n0, int N, int Ch, int Chp, int O,
                                                               const float* __restrict__ w, const float* __restrict__ b,
                                                               const float* __restrict__ y, float* __restrict__ dpred,
                                                               void* __restrict__ dh, double* __restrict__ partial, int H, int W,
-                                                              int P, int Hh, int Wh, int oy, int ox, int Hc, int Wc, int Bs) {
+                                                              int P, int Hh, int Wh, int oy, int ox, int Hc, int Wc, int Bs,
+                                                              const float* __restrict__ wgt, double cnt) {
   extern __shared__ __attribute__((aligned(16))) char smem_hl[];
-  head_loss_fused_body<DT, CHV, SEQ>(smem_hl, h, n0, N, Ch, Chp, O, w, b, y, dpred, dh, partial, H, W, P, Hh, Wh, oy, ox, Hc, Wc, Bs);
+  head_loss_fused_body<DT, CHV, SEQ, WGT>(smem_hl, h, n0, N, Ch, Chp, O, w, b, y, dpred, dh, partial, H, W, P, Hh, Wh, oy, ox, Hc, Wc, Bs, wgt, cnt);
 }
 
-// SEQ: the sequence entry (n0 = Bs = B, N = T*B)
-template <bool SEQ>
+// SEQ: the sequence entry (n0 = Bs = B, N = T*B).  WGT: the weighted entries, cnt = N * O * wsum
+template <bool SEQ, bool WGT>
 static int head_loss_fused_impl(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w, const float* b,
-                                const float* y, float* dpred, void* dh, float* loss_out, double* stats, const nint_geom* g,
-                                int oy, int ox, int Hc, int Wc, int dtype, int Bs, void* stream) {
+                                const float* y, const float* wgt, double cnt, float* dpred, void* dh, float* loss_out,
+                                double* stats, const nint_geom* g, int oy, int ox, int Hc, int Wc, int dtype, int Bs, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   double* partial = (double*)(loss_out + 2);   // loss_out: [0]=loss, [1]=pad, [2..] = up to LOSS_BLOCKS_MAX*4 doubles
   // 64 pixels per workgroup and pass: up to LOSS_BLOCKS_MAX workgroups
@@ -786,13 +843,13 @@ static int head_loss_fused_impl(const void* h_slab, int n0, int N, int Ch, int C
   const size_t lds = ((size_t)O * head_chv(Chp) + (size_t)(O < HEAD_OCH ? O : HEAD_OCH) * 64) * sizeof(float);   // weights [O][CHV] + d loss / d pred of 64 pixels, one output chunk
   if (lds + 8192 > 160 * 1024) return NINT_E_SHAPE;
   const int rc = nint_by_dtype(dtype, [&](auto dt) { return head_by_chv(Chp, [&](auto chv) -> int {
-    auto kern = head_loss_fused_kernel<decltype(dt)::value, decltype(chv)::value, SEQ>;
+    auto kern = head_loss_fused_kernel<decltype(dt)::value, decltype(chv)::value, SEQ, WGT>;
     if (lds + 8192 > 64 * 1024) NINT_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3(nblk), dim3(256), lds, st, h_slab, n0, N, Ch, Chp, O, w, b, y, dpred, dh, partial, g->H, g->W, g->P, g->Hh, g->Wh, oy, ox, Hc, Wc, Bs);
+    hipLaunchKernelGGL(kern, dim3(nblk), dim3(256), lds, st, h_slab, n0, N, Ch, Chp, O, w, b, y, dpred, dh, partial, g->H, g->W, g->P, g->Hh, g->Wh, oy, ox, Hc, Wc, Bs, wgt, cnt);
     return NINT_OK; }); });
   if (rc != NINT_OK) return rc;
   NINT_LAUNCH_CHECK();
-  hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(256), 0, st, partial, nblk, loss_out, stats, (double)N * O * Hc * Wc);
+  hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(256), 0, st, partial, nblk, loss_out, stats, WGT ? cnt : (double)N * O * Hc * Wc);
   NINT_LAUNCH_CHECK();
   return NINT_OK;
 }
@@ -805,7 +862,19 @@ extern "C" int nint_head_loss_fused(const void* h_slab, int n0, int N, int Ch, i
   if (dtype != NINT_BF16 && dtype != NINT_F32) return NINT_E_ARG;
   if (Chp > 128 || Chp % 4) return NINT_E_SHAPE;   // wider heads: nint_head_fwd + nint_loss_mse_l1_crop + nint_head_bwd
   if ((((uintptr_t)loss_out) & 7) != 0) return NINT_E_ALIGN;
-  return head_loss_fused_impl<false>(h_slab, n0, N, Ch, Chp, O, w, b, y, dpred, dh, loss_out, stats, g, oy, ox, Hc, Wc, dtype, 0, stream);
+  return head_loss_fused_impl<false, false>(h_slab, n0, N, Ch, Chp, O, w, b, y, nullptr, 0.0, dpred, dh, loss_out, stats, g, oy, ox, Hc, Wc, dtype, 0, stream);
+}
+
+extern "C" int nint_head_loss_fused_weighted(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w, const float* b,
+                                             const float* y, const float* wgt, double wsum, float* dpred, void* dh, float* loss_out,
+                                             double* stats, const nint_geom* g, int oy, int ox, int Hc, int Wc, int dtype, void* stream) {
+  if (!h_slab || !w || !y || !dpred || !dh || !loss_out || !g || N <= 0 || O <= 0 || Ch <= 0) return NINT_E_ARG;
+  if (oy < 0 || ox < 0 || Hc <= 0 || Wc <= 0 || oy + Hc > g->H || ox + Wc > g->W) return NINT_E_ARG;
+  if (dtype != NINT_BF16 && dtype != NINT_F32) return NINT_E_ARG;
+  if (!loss_weights_ok(wgt, wsum)) return NINT_E_ARG;
+  if (Chp > 128 || Chp % 4) return NINT_E_SHAPE;   // wider heads: nint_head_fwd + nint_loss_mse_l1_crop_weighted + nint_head_bwd
+  if ((((uintptr_t)loss_out) & 7) != 0 || (((uintptr_t)wgt) & 3) != 0) return NINT_E_ALIGN;
+  return head_loss_fused_impl<false, true>(h_slab, n0, N, Ch, Chp, O, w, b, y, wgt, (double)N * O * wsum, dpred, dh, loss_out, stats, g, oy, ox, Hc, Wc, dtype, 0, stream);
 }
 
 extern "C" int nint_head_loss_seq_fused(const void* h_slab, int B, int T, int Ch, int Chp, int O, const float* w, const float* b,
@@ -815,7 +884,19 @@ extern "C" int nint_head_loss_seq_fused(const void* h_slab, int B, int T, int Ch
   if (oy < 0 || ox < 0 || Hc <= 0 || Wc <= 0 || oy + Hc > g->H || ox + Wc > g->W) return NINT_E_ARG;
   if (Chp > 128) return NINT_E_SHAPE;              // wider heads: nint_head_fwd_seq + nint_loss_mse_l1_crop + nint_head_bwd_seq
   if ((((uintptr_t)loss_out) & 7) != 0 || ((((uintptr_t)h_slab) | ((uintptr_t)dh_seq)) & 15) != 0) return NINT_E_ALIGN;
-  return head_loss_fused_impl<true>(h_slab, B, T * B, Ch, Chp, O, w, b, y, dpred, dh_seq, loss_out, stats, g, oy, ox, Hc, Wc, dtype, B, stream);
+  return head_loss_fused_impl<true, false>(h_slab, B, T * B, Ch, Chp, O, w, b, y, nullptr, 0.0, dpred, dh_seq, loss_out, stats, g, oy, ox, Hc, Wc, dtype, B, stream);
+}
+
+extern "C" int nint_head_loss_seq_fused_weighted(const void* h_slab, int B, int T, int Ch, int Chp, int O, const float* w, const float* b,
+                                                 const float* y, const float* wgt, double wsum, float* dpred, void* dh_seq,
+                                                 float* loss_out, double* stats, const nint_geom* g, int oy, int ox, int Hc,
+                                                 int Wc, int dtype, void* stream) {
+  if (!y || !dpred || !dh_seq || !loss_out || !head_seq_args_ok(h_slab, B, T, Ch, Chp, O, w, g, dtype)) return NINT_E_ARG;
+  if (oy < 0 || ox < 0 || Hc <= 0 || Wc <= 0 || oy + Hc > g->H || ox + Wc > g->W) return NINT_E_ARG;
+  if (!loss_weights_ok(wgt, wsum)) return NINT_E_ARG;
+  if (Chp > 128) return NINT_E_SHAPE;              // wider heads: nint_head_fwd_seq + nint_loss_mse_l1_crop_weighted + nint_head_bwd_seq
+  if ((((uintptr_t)loss_out) & 7) != 0 || ((((uintptr_t)h_slab) | ((uintptr_t)dh_seq)) & 15) != 0 || (((uintptr_t)wgt) & 3) != 0) return NINT_E_ALIGN;
+  return head_loss_fused_impl<true, true>(h_slab, B, T * B, Ch, Chp, O, w, b, y, wgt, (double)(T * B) * O * wsum, dpred, dh_seq, loss_out, stats, g, oy, ox, Hc, Wc, dtype, B, stream);
 }
 
 // ------------------------------------------------------------------------------ evaluation: skill sums (test.ipynb)

@@ -1,0 +1,136 @@
+"""The training loss as a per-cell weighted mean: cos-latitude area weights, masks, or their product.
+
+The fit loop minimises ``mean((y-p)^2) + mean(|y-p|)`` over the crop (reference train.py:102,105).  On a regular lat-lon
+grid that gives a polar row the weight of an equatorial row with many times its area, and it cannot leave out cells
+without valid data.  With a weight map ``w`` (f32, ``(Hc, Wc)``, non-negative, shared by every sample, output and time
+step) the loss is
+
+    loss = sum(w * d^2) / cnt + sum(w * |d|) / cnt,    d = p - y,    cnt = N * O * sum(w)
+
+and a cell of weight 0 is skipped: its target may be NaN.  ``include/nint.h`` (the ``_weighted`` entries) carries the exact
+arithmetic.  Three ways in: ``FusedTrainer(loss_weights=...)`` (the fused step), ``CropMSEL1Loss`` (an ``nn.Module`` for a
+torch training loop) and ``train.py --lat-weighted-loss / --loss-weights``.
+
+Under data parallelism the map is NOT broadcast: every rank has to be given the same one (``train.py`` builds it
+deterministically on every rank)."""
+from __future__ import annotations
+
+from typing import Optional, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import NINT_LOSS_SCRATCH_FLOATS, check, ptr, stream_ptr
+
+__all__ = ["grid_latitudes", "cos_latitude_weights", "validate_loss_weights", "CropMSEL1Loss"]
+
+
+def grid_latitudes(H: int) -> np.ndarray:
+    """Cell-centre latitudes in degrees of the ``H`` rows of a global grid, south to north (f64)."""
+    return -90.0 + (np.arange(H) + 0.5) * (180.0 / H)
+
+
+def cos_latitude_weights(lat_degrees, Wc: Optional[int] = None) -> np.ndarray:
+    """``cos(deg2rad(lat))`` as f32: the ``(Hc,)`` row weights, or with ``Wc`` the ``(Hc, Wc)`` map (rows broadcast)."""
+    row = np.cos(np.deg2rad(np.asarray(lat_degrees, np.float64))).astype(np.float32)
+    if row.ndim != 1:
+        raise ValueError("lat_degrees must be a vector of row latitudes")
+    return row if Wc is None else np.ascontiguousarray(np.broadcast_to(row[:, None], (row.shape[0], int(Wc))))
+
+
+def validate_loss_weights(weights, crop: Optional[Tuple[int, int]] = None) -> Tuple[np.ndarray, Optional[float]]:
+    """Host-side check of a weight map.  ``weights``: ``(Hc, Wc)`` array or tensor, or a ``(Hc,)`` vector of row weights.
+    Returns ``(w, wsum)``: the f32 array -- a vector stays a vector until ``crop = (Hc, Wc)`` is known and is then expanded
+    to rows -- and the f64 sum of the f32 map (None while it is still a vector).  ValueError for a negative, NaN or inf
+    value, an all-zero map, more than two dimensions or a shape that does not match ``crop``."""
+    if isinstance(weights, torch.Tensor):
+        weights = weights.detach().cpu().numpy()
+    w64 = np.asarray(weights, np.float64)
+    if w64.ndim not in (1, 2) or w64.size == 0:
+        raise ValueError(f"loss weights must be (Hc, Wc) or (Hc,), got shape {w64.shape}")
+    if not np.isfinite(w64).all():
+        raise ValueError("loss weights must be finite (mask a cell with weight 0, not NaN)")
+    if (w64 < 0).any():
+        raise ValueError("loss weights must be non-negative")
+    with np.errstate(over="ignore"):
+        w = w64.astype(np.float32)
+    if not np.isfinite(w).all():
+        raise ValueError("loss weights overflow f32")
+    if not (w > 0).any():
+        raise ValueError("loss weights are all zero: nothing to fit")
+    if crop is not None:
+        Hc, Wc = int(crop[0]), int(crop[1])
+        if w.ndim == 1:
+            if w.shape[0] != Hc:
+                raise ValueError(f"{w.shape[0]} row weights for a crop of {Hc} rows")
+            w = np.broadcast_to(w[:, None], (Hc, Wc))
+        elif w.shape != (Hc, Wc):
+            raise ValueError(f"loss weights {w.shape} do not match the target's crop {(Hc, Wc)}")
+    w = np.ascontiguousarray(w)
+    return w, (float(w.astype(np.float64).sum()) if w.ndim == 2 else None)
+
+
+class DeviceWeights:
+    """A validated map on its way to the device: the f32 ``(Hc, Wc)`` tensor and the f64 ``wsum``, formed at the first call
+    that knows the crop and the device (a ``(Hc,)`` vector is expanded there)."""
+
+    def __init__(self, weights):
+        self.host, _ = validate_loss_weights(weights)
+        self.map: Optional[torch.Tensor] = None
+        self.wsum: Optional[float] = None
+
+    def on(self, device, Hc: int, Wc: int) -> Tuple[torch.Tensor, float]:
+        if self.map is None or self.map.device != device or tuple(self.map.shape) != (Hc, Wc):
+            w, wsum = validate_loss_weights(self.host, (Hc, Wc))
+            self.map = torch.from_numpy(w).to(device)
+            self.wsum = wsum
+        return self.map, self.wsum
+
+
+class _CropMSEL1(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, y, wgt, wsum, oy, ox):
+        lib = _lib.load()
+        N, O, H, W = pred.shape
+        Hc, Wc = y.shape[-2], y.shape[-1]
+        p = pred.detach().float().contiguous()
+        yv = y.detach().float().contiguous()
+        if yv.numel() != N * O * Hc * Wc:
+            raise ValueError(f"target {tuple(y.shape)} does not match the prediction {tuple(pred.shape)}")
+        scratch = torch.empty(NINT_LOSS_SCRATCH_FLOATS, dtype=torch.float32, device=p.device)
+        dpred = torch.empty_like(p) if ctx.needs_input_grad[0] else None
+        if wgt is None:
+            check(lib.nint_loss_mse_l1_crop(ptr(p), ptr(yv), ptr(dpred), ptr(scratch), None, N, O, H, W, oy, ox, Hc, Wc,
+                                            stream_ptr()), "nint_loss_mse_l1_crop")
+        else:
+            check(lib.nint_loss_mse_l1_crop_weighted(ptr(p), ptr(yv), ptr(wgt), wsum, ptr(dpred), ptr(scratch), None, N, O, H, W,
+                                                     oy, ox, Hc, Wc, stream_ptr()), "nint_loss_mse_l1_crop_weighted")
+        ctx.dpred = dpred
+        ctx.dtype = pred.dtype
+        return scratch[0].clone()
+
+    @staticmethod
+    def backward(ctx, upstream):
+        g = None if ctx.dpred is None else (ctx.dpred * upstream).to(ctx.dtype)
+        return g, None, None, None, None, None
+
+
+class CropMSEL1Loss(torch.nn.Module):
+    """``MSELoss + L1Loss`` of the reference fit loop (train.py:102,105) with the crop inside and an optional weight map, for
+    users who keep a torch training loop: ``loss = criterion(y, pred)`` -- the reference's argument order -- with the
+    UNCROPPED ``pred (B, O, H, W)`` on the device and ``y (B, [O,] Hc, Wc)``.  The crop window starts at ``halo = (oy, ox)``.
+    The forward is one loss launch (``nint_loss_mse_l1_crop_weighted`` with a map, ``nint_loss_mse_l1_crop`` without), which
+    also writes d loss / d pred; backward returns that times the upstream gradient.  ``y`` receives NO gradient.
+    ``weights``: see ``validate_loss_weights``; every data-parallel rank must be given the same map."""
+
+    def __init__(self, halo: Tuple[int, int] = (5, 5), weights=None):
+        super().__init__()
+        self.halo = (int(halo[0]), int(halo[1]))
+        self._weights = None if weights is None else DeviceWeights(weights)
+
+    def forward(self, y: torch.Tensor, pred: torch.Tensor) -> torch.Tensor:
+        if pred.dim() != 4 or pred.device.type != "cuda":
+            raise _lib.NintError("CropMSEL1Loss needs the uncropped prediction (B, O, H, W) on the MI355X (cuda)")
+        wgt, wsum = (None, 0.0) if self._weights is None else self._weights.on(pred.device, y.shape[-2], y.shape[-1])
+        return _CropMSEL1.apply(pred, y, wgt, wsum, self.halo[0], self.halo[1])

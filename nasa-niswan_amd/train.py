@@ -5,7 +5,7 @@ MI355X step.  Same flags, same artefacts (`configurations.json`, `logger.npy`,
 stepped once per epoch before validation, checkpoint every 10 epochs); the per-batch
 `loss.item()` / sklearn R2 host syncs (train.py:113-114) are replaced by device accumulators read
 once per epoch.  Added flags: --dtype, --levels, --grid, --synthetic-steps, --pad-mode, --f32-inputs,
---static-channels, --sequence-loss, --test-skill.
+--static-channels, --sequence-loss, --test-skill, --lat-weighted-loss, --loss-weights.
 
 The data path is on the device too: by default every batch is written by ONE launch of the
 fuse / z-score / halo-pad kernel straight into the model's bf16 input slab (dataset.slab_batch);
@@ -80,6 +80,12 @@ def get_arguments(argv=None, MODEL='LSTM-00', SPECIES='bcb', LEARNING_RATE=1.0E-
                         help="after the last epoch rank 0 evaluates the 'test' period on the device (inference.evaluate_skill: R2 per "
                              "window and per grid cell, rmse, bias, time means, cos-latitude weighted means; test.ipynb's evaluation "
                              "cells) and writes the report's arrays to skill.npz in --snapshot-dir")
+    parser.add_argument("--lat-weighted-loss", action="store_true",
+                        help="weight the loss (training, and the validation R2V) by cos(latitude) of the --grid rows, the area of a "
+                             "cell on the lat-lon grid -- what --test-skill's weighted means report")
+    parser.add_argument("--loss-weights", type=str, default=None, metavar="FILE.npy",
+                        help="a --grid shaped (H, W) map of non-negative loss weights, 0 = leave the cell out (missing data, other "
+                             "regions); with --lat-weighted-loss the two are multiplied")
     args = parser.parse_args(argv)
     rank = int(os.environ.get("RANK", "0"))
     if rank == 0:
@@ -96,6 +102,7 @@ def main(args):
     import torch.optim as optim
     import nasa_niswan_amd as pkg
     from nasa_niswan_amd.dataset import SyntheticE33OMA_CRNN
+    from nasa_niswan_amd.loss import cos_latitude_weights, grid_latitudes
     from nasa_niswan_amd.trainer import FusedTrainer
     from nasa_niswan_amd.utils import load_checkpoint, save_checkpoint, seed, shard_indices
 
@@ -130,8 +137,17 @@ def main(args):
     val_dataset = SyntheticE33OMA_CRNN('val', **ds_kw)
     get_batch = (lambda ds, idx: ds.device_batch(idx)) if args.f32_inputs else (lambda ds, idx: ds.slab_batch(idx))
 
+    # the loss weights, built the same way on every rank (they are not broadcast)
+    loss_weights = None
+    if args.lat_weighted_loss:
+        loss_weights = cos_latitude_weights(grid_latitudes(H), W)
+    if args.loss_weights:
+        m = np.load(args.loss_weights)
+        if m.shape != (H, W):
+            raise SystemExit(f"--loss-weights {args.loss_weights}: shape {m.shape}, expected the --grid {(H, W)}")
+        loss_weights = m if loss_weights is None else (loss_weights.astype(np.float64) * m).astype(np.float32)
     trainer = FusedTrainer(generator, lr=args.learning_rate, betas=tuple(args.betas), halo=halo,        # train.py:71
-                           sequence_loss=args.sequence_loss)
+                           sequence_loss=args.sequence_loss, loss_weights=loss_weights)
     optimizer = trainer.optimizer
     scheduler = optim.lr_scheduler.StepLR(optimizer, step_size=int(args.scheduler_config[0]),
                                           gamma=args.scheduler_config[1])                   # train.py:72
@@ -178,7 +194,7 @@ def main(args):
             # the evaluation cells of test.ipynb on the 'test' period: the last step's prediction, sums kept on the device
             from nasa_niswan_amd.inference import evaluate_skill
             test_dataset = SyntheticE33OMA_CRNN('test', **dict(ds_kw, sequence_targets=False))
-            lat = -90.0 + (np.arange(H) + 0.5) * (180.0 / H)                                 # cell centres of the H-row global grid
+            lat = grid_latitudes(H)                                                          # cell centres of the H-row global grid
             report = evaluate_skill(generator, test_dataset, batch_size=args.batch_size, halo=halo, lat=lat).report(
                 test_dataset.y_mean, test_dataset.y_std)
             np.savez(os.path.join(args.snapshot_dir, "skill.npz"), **report.arrays())

@@ -3,7 +3,8 @@
     X.cuda(), y.cuda()                      -> inputs already on device
     pred = generator(X)                     -> nint_pack_btchw + nint_seq_fwd + nint_head_fwd
     pred[:, :, 5:95, 5:149].squeeze()       -> crop folded into the loss kernel (index math)
-    MSELoss(y,pred) + L1Loss(y,pred)        -> nint_loss_mse_l1_crop (also emits d loss/d pred)
+    MSELoss(y,pred) + L1Loss(y,pred)        -> nint_loss_mse_l1_crop (also emits d loss/d pred); with ``loss_weights`` the
+                                               per-cell weighted means of loss.py (the _weighted entries)
     zero_grad; loss.backward()              -> nint_head_bwd + nint_seq_bwd (grads overwrite the bucket)
     [DDP]                                   -> ONE RCCL all-reduce of the flat gradient bucket
     optimizer.step()                        -> nint_adam_flat (1/world folded in)
@@ -20,13 +21,14 @@ import torch
 from . import _lib
 from ._lib import NINT_LOSS_SCRATCH_FLOATS, NINT_LOSS_STATS, check, ptr, stream_ptr
 from .model import ConvLSTM
+from .loss import DeviceWeights
 from .optim import FlatParams, FusedAdam
 
 
 class FusedTrainer:
     def __init__(self, model: ConvLSTM, lr: float = 1e-3, betas=(0.5, 0.999), eps: float = 1e-8,
                  halo: Tuple[int, int] = (5, 5), process_group=None, distributed: Optional[bool] = None,
-                 overlap_allreduce: bool = False, sequence_loss: bool = False):
+                 overlap_allreduce: bool = False, sequence_loss: bool = False, loss_weights=None):
         dev = next(model.parameters()).device
         if dev.type != "cuda":
             raise _lib.NintError("FusedTrainer needs the model on the MI355X (cuda)")
@@ -56,6 +58,9 @@ class FusedTrainer:
         # Sequence-to-sequence supervision: y is (B, T, [O,] Hc, Wc), a target at every step of the window, and the loss is
         # MSE + L1 over the per-step head outputs (model.py:264,272,274 commented code) instead of the last one alone
         self.sequence_loss = bool(sequence_loss)
+        # Per-cell loss weights (loss.py): an (Hc, Wc) map or (Hc,) row weights -- cos latitude, a mask, their product -- used by
+        # step, evaluate and forward_loss in every branch.  Every data-parallel rank must be given the same map.
+        self.set_loss_weights(loss_weights)
         L = model.num_layers
         self._dW = [self.flat.grad_view(2 * l) for l in range(L)]
         self._db = [self.flat.grad_view(2 * l + 1) for l in range(L)]
@@ -71,11 +76,33 @@ class FusedTrainer:
         None switches them off.  Diagnostic: bench.py prices the kernels INSIDE the step with it."""
         self._probe = (buf, int(mask) if buf is not None else 0)
 
+    def set_loss_weights(self, weights):
+        """Switch the loss weights (between epochs, say): an (Hc, Wc) array or tensor, an (Hc,) vector of row weights, or None
+        for the unweighted loss.  Values are validated here (ValueError for a negative, NaN or inf value or an all-zero
+        map), the shape against the target's crop at the next step / evaluate.  Not broadcast between ranks."""
+        self._weights = None if weights is None else DeviceWeights(weights)
+
+    def _loss_weights(self, Hc: int, Wc: int):
+        """(wgt, wsum) for the engine's head/loss calls, or None"""
+        return None if self._weights is None else self._weights.on(self.device, Hc, Wc)
+
+    def _loss(self, pred, yv, dpred, N, O, H, W, Hc, Wc, wts):
+        """the stand-alone loss launch of the three-launch paths"""
+        if wts is None:
+            check(self.lib.nint_loss_mse_l1_crop(ptr(pred), ptr(yv), ptr(dpred), ptr(self.scratch), ptr(self.stats),
+                                                 N, O, H, W, self.halo[0], self.halo[1], Hc, Wc, stream_ptr()),
+                  "nint_loss_mse_l1_crop")
+        else:
+            check(self.lib.nint_loss_mse_l1_crop_weighted(ptr(pred), ptr(yv), ptr(wts[0]), wts[1], ptr(dpred), ptr(self.scratch),
+                                                          ptr(self.stats), N, O, H, W, self.halo[0], self.halo[1], Hc, Wc,
+                                                          stream_ptr()), "nint_loss_mse_l1_crop_weighted")
+
     # ------------------------------------------------------------------ pieces
     def forward_loss(self, X: torch.Tensor, y: torch.Tensor, train: bool = True):
         m = self.model
         eng = m._engine(self.device)
         B, T, _, H, W = X.shape
+        wts = self._loss_weights(y.shape[-2], y.shape[-1])      # (validates the map's shape before anything is acquired)
         ws = eng.acquire(B, T, H, W, train, False)
         wb_w = [c.conv.weight for c in m.layers]
         wb_b = [c.conv.bias for c in m.layers]
@@ -97,9 +124,7 @@ class FusedTrainer:
             if self._dpred is None or self._dpred.shape != pred.shape:
                 self._dpred = torch.empty_like(pred)
             dpred = self._dpred
-        check(self.lib.nint_loss_mse_l1_crop(ptr(pred), ptr(yv), ptr(dpred), ptr(self.scratch), ptr(self.stats),
-                                             B, O, H, W, self.halo[0], self.halo[1], Hc, Wc, stream_ptr()),
-              "nint_loss_mse_l1_crop")
+        self._loss(pred, yv, dpred, B, O, H, W, Hc, Wc, wts)
         return eng, ws, pred, dpred
 
     def step(self, X: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
@@ -109,6 +134,7 @@ class FusedTrainer:
         eng = m._engine(self.device)
         B, T, _, H, W = X.shape
         L = m.num_layers
+        wts = self._loss_weights(y.shape[-2], y.shape[-1])      # (validates the map's shape before anything is acquired)
         ws = eng.acquire(B, T, H, W, True, False)
         pb, pm = self._probe
         ws.seq.probe = pb.data_ptr() if pb is not None else None
@@ -129,23 +155,19 @@ class FusedTrainer:
         if sq:
             # the same over every step: one pass writes the loss, d loss / d pred (image order t*B + b, which the head's
             # weight-gradient kernels reduce as T*B images) and the per-step dL/dh that BPTT adds at each t
-            fused = eng.head_loss_seq_fused(ws, m.conv.weight, m.conv.bias, yv, dpred, self.scratch, self.stats, self.halo, Hc, Wc)
+            fused = eng.head_loss_seq_fused(ws, m.conv.weight, m.conv.bias, yv, dpred, self.scratch, self.stats, self.halo, Hc, Wc, wts)
             if fused:
                 eng.head_backward(ws, m.conv.weight, dpred, dw_out=self._dw_head, db_out=self._db_head, write_dh=False, images=(B, T * B))
             else:
                 seq = eng.head_forward_seq(ws, m.conv.weight, m.conv.bias)
-                check(self.lib.nint_loss_mse_l1_crop(ptr(seq), ptr(yv), ptr(dpred), ptr(self.scratch), ptr(self.stats),
-                                                     B, T * O, H, W, self.halo[0], self.halo[1], Hc, Wc, stream_ptr()),
-                      "nint_loss_mse_l1_crop")
+                self._loss(seq, yv, dpred, B, T * O, H, W, Hc, Wc, wts)
                 eng.head_backward_seq(ws, m.conv.weight, dpred.view(B, T * O, H, W), None, dw_out=self._dw_head, db_out=self._db_head)
         else:
             # head forward + crop + loss + dpred + dL/dh in one pass; the prediction itself is never materialised
-            fused = eng.head_loss_fused(ws, m.conv.weight, m.conv.bias, yv, dpred, self.scratch, self.stats, self.halo, Hc, Wc)
+            fused = eng.head_loss_fused(ws, m.conv.weight, m.conv.bias, yv, dpred, self.scratch, self.stats, self.halo, Hc, Wc, wts)
             if not fused:
                 pred = eng.head_forward(ws, m.conv.weight, m.conv.bias)
-                check(self.lib.nint_loss_mse_l1_crop(ptr(pred), ptr(yv), ptr(dpred), ptr(self.scratch), ptr(self.stats),
-                                                     B, O, H, W, self.halo[0], self.halo[1], Hc, Wc, stream_ptr()),
-                      "nint_loss_mse_l1_crop")
+                self._loss(pred, yv, dpred, B, O, H, W, Hc, Wc, wts)
             eng.head_backward(ws, m.conv.weight, dpred, dw_out=self._dw_head, db_out=self._db_head, write_dh=not fused)
         mark()
         if self.distributed and self.overlap_allreduce and L > 1 and pb is None:
