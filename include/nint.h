@@ -418,6 +418,46 @@ int nint_head_skill_accum(const void* h_slab, int n0, int N, int Ch, int Chp, in
 int nint_adam_flat(float* p, const float* g, float* m, float* v, size_t n, double lr, double beta1,
                    double beta2, double eps, int step, float grad_scale, void* stream);
 
+/* Global L2 norm of the flat gradient bucket, on the caller's stream, no host read: S = sum (double)g[i]^2 in f64,
+ * out[0] = S, out[1] = (double)grad_scale * sqrt(S) (the norm of the SCALED gradient).  Two launches: a fixed number of
+ * workgroups (NINT_GRAD_NORM_BLOCKS, whatever the device) each reduce a grid-stride share in a fixed order, one workgroup
+ * folds their partials; no atomics, so S depends on (g, n) only -- bit-identical run to run and on every rank that holds
+ * the same bucket.  g needs 4-byte alignment only (dword loads).  scratch: nint_grad_norm_scratch_bytes() bytes, 8-byte
+ * aligned.  n == 0: S = 0.  NINT_E_ARG: NULL g / out / scratch, a scratch that is too small; NINT_E_ALIGN: out or scratch
+ * not 8-byte aligned -- both before any launch. */
+#define NINT_GRAD_NORM_BLOCKS 256
+size_t nint_grad_norm_scratch_bytes(void);
+int nint_grad_norm_flat(const float* g, size_t n, float grad_scale, double* out, double* scratch, size_t scratch_bytes,
+                        void* stream);
+
+/* nint_adam_flat behind a gradient-norm guard decided on the device: torch.nn.utils.clip_grad_norm_(max_norm) and,
+ * optionally, dropping a step whose gradient is not finite.  Three launches: the norm partials above, a one-workgroup
+ * control kernel that folds them and writes the step's scalars into `state`, and the Adam body, which reads them there.
+ *   gs        = grad_scale (1/world_size after the all-reduce: every rank decides from the same bits)
+ *   norm      = (double)gs * sqrt(S)
+ *   coef      = max_norm > 0 ? min(1, max_norm / (norm + 1e-6)) : 1       (clip_grad_norm_'s formula; 1 for a NaN norm)
+ *   s         = (float)((double)gs * coef)       rounded once; the body's gradient is g[i] * s.  coef == 1: s == gs exactly
+ *   apply     = isfinite(S) || !skip_nonfinite
+ *   step      = applied + 1;  bc1 = 1 - pow(beta1, step);  bc2 = 1 - pow(beta2, step)
+ *   step_size = (float)(lr / bc1);  sqrt_bc2 = (float)sqrt(bc2)            (nint_adam_flat's host expressions, in f64)
+ * apply == 0: no thread stores to p, m or v and `applied` stays, so the bias correction counts applied steps only.
+ * With coef == 1 the body is nint_adam_flat(step = applied + 1) bit for bit.  max_norm == 0: no clipping.
+ * state: NINT_OPT_STATE doubles, 8-byte aligned; the caller zeroes it once (or sets [NINT_OPT_APPLIED] on resume):
+ *   [0] applied steps   [1] skipped steps   [2] clipped steps (finite norm, coef < 1)   [3] calls
+ *   [4] sum of norm over the calls with a finite S   [5] number of those calls   [6] max of norm over them
+ *   this call: [7] S   [8] norm   [9] coef   [10] s   [11] step_size   [12] sqrt_bc2   [13] apply (0 / 1)   [14..15] 0
+ *   ([10..12] are f32 values held in doubles; [11..12] belong to step applied + 1 whether or not it is applied.)
+ * n == 0 is a call with S = 0 (it counts, and applies).  NINT_E_ARG: a NULL p / g / m / v / state / scratch, a negative or
+ * NaN max_norm, a scratch smaller than nint_grad_norm_scratch_bytes(); NINT_E_ALIGN: state or scratch not 8-byte aligned --
+ * both before any launch. */
+#define NINT_OPT_STATE 16
+enum { NINT_OPT_APPLIED = 0, NINT_OPT_SKIPPED = 1, NINT_OPT_CLIPPED = 2, NINT_OPT_CALLS = 3, NINT_OPT_SUM_NORM = 4,
+       NINT_OPT_FINITE = 5, NINT_OPT_MAX_NORM = 6, NINT_OPT_S = 7, NINT_OPT_NORM = 8, NINT_OPT_COEF = 9, NINT_OPT_SCALE = 10,
+       NINT_OPT_STEP_SIZE = 11, NINT_OPT_SQRT_BC2 = 12, NINT_OPT_APPLY = 13 };
+int nint_adam_flat_guarded(float* p, const float* g, float* m, float* v, size_t n, double lr, double beta1, double beta2,
+                           double eps, float grad_scale, double max_norm, int skip_nonfinite, double* state,
+                           double* scratch, size_t scratch_bytes, void* stream);
+
 /* ---- preproc (dataset.py:520-536, 61-98) --------------------------------------------------------- */
 /* Fuse on the channel axis, z-score with mean/std (C = sum lev floats, device), cyclic-lon + lat halo pad.
  * mode 0 = the committed reference behaviour (np.fliplr on the channel axis, dataset.py:96),

@@ -17,6 +17,11 @@ NINT_VERSION = 112     # include/nint.h NINT_VERSION: the library this binding w
 NINT_LOSS_SCRATCH_FLOATS = 8194
 NINT_LOSS_STATS = 8
 NINT_SKILL_PIX, NINT_SKILL_SAMPLE, NINT_SKILL_MAX_N = 5, 8, 64
+NINT_GRAD_NORM_BLOCKS = 256
+NINT_OPT_STATE = 16
+# nint_adam_flat_guarded's state (include/nint.h): counters, running norm figures, then this call's scalars
+(NINT_OPT_APPLIED, NINT_OPT_SKIPPED, NINT_OPT_CLIPPED, NINT_OPT_CALLS, NINT_OPT_SUM_NORM, NINT_OPT_FINITE, NINT_OPT_MAX_NORM,
+ NINT_OPT_S, NINT_OPT_NORM, NINT_OPT_COEF, NINT_OPT_SCALE, NINT_OPT_STEP_SIZE, NINT_OPT_SQRT_BC2, NINT_OPT_APPLY) = range(14)
 
 vp = C.c_void_p
 
@@ -94,6 +99,9 @@ SIGNATURES = {
     "nint_head_skill_accum": (_I, [vp, _I, _I, _I, _I, _I, vp, vp, vp, C.POINTER(C.c_int32), _I, vp, vp, vp, vp, vp, _SZ, _PG,
                                    _I, _I, _I, _I, _I, vp]),
     "nint_adam_flat": (_I, [vp, vp, vp, vp, _SZ, C.c_double, C.c_double, C.c_double, C.c_double, _I, _F, vp]),
+    "nint_grad_norm_scratch_bytes": (_SZ, []),
+    "nint_grad_norm_flat": (_I, [vp, _SZ, _F, vp, vp, _SZ, vp]),
+    "nint_adam_flat_guarded": (_I, [vp, vp, vp, vp, _SZ, _D, _D, _D, _D, _F, _D, _I, vp, vp, _SZ, vp]),
     "nint_preproc_fuse_pad": (_I, [C.POINTER(vp), C.POINTER(_I), _I, vp, vp, vp, _I, _I, _I, _I, _I, _I, vp]),
     "nint_preproc_fuse_pad_batch": (_I, [C.POINTER(vp), C.POINTER(_I), _I, vp, vp, C.POINTER(_I), _I, vp, _I, _I, _I, _I, _I, _I, vp]),
     "nint_preproc_fuse_pad_slab": (_I, [C.POINTER(vp), C.POINTER(_I), _I, vp, vp, C.POINTER(_I), _I, vp, _I, _I, _I, _I, _I, _PG, _I, _I, vp]),

@@ -1,5 +1,6 @@
 // pointwise.hip -- the elementwise kernels: the LSTM pointwise backward (planned, then enqueued, like the conv launches)
-// and flat Adam.  One-read/one-write streaming over flat index ranges.
+// and flat Adam, with the gradient-norm guard in front of it (norm reduction, clip coefficient, skipped steps).  One-read/one-write
+// streaming over flat index ranges.
 #include "nint_common.h"
 
 // ------------------------------------------------------------------------------ LSTM pointwise backward
@@ -46,21 +47,27 @@ extern "C" int nint_cell_bwd_pointwise(const nint_layer* ly, const nint_geom* g,
 // ------------------------------------------------------------------------------ Adam
 // torch.optim.Adam single-tensor update order (train.py:71,110):
 //   m = lerp(m, g, 1-b1) ; v = b2*v + (1-b2)*g*g ; p -= (lr/bc1) * m / (sqrt(v)/sqrt(bc2) + eps)
+// (one element update for the plain and the guarded kernel: the same operations in the same order, so the same roundings)
+__device__ __forceinline__ void adam_flat_update(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                 float* __restrict__ v, size_t i, float step_size, float w1, float b2, float w2,
+                                                 float eps, float inv_sqrt_bc2_denom, float grad_scale) {
+  const float gr = g[i] * grad_scale;
+  float mi = m[i], vi = v[i];
+  // torch lerp: a + w*(b-a) for w < 0.5, else b - (b-a)*(1-w)
+  mi = (w1 < 0.5f) ? __fadd_rn(mi, __fmul_rn(w1, __fsub_rn(gr, mi)))
+                   : __fsub_rn(gr, __fmul_rn(__fsub_rn(gr, mi), 1.f - w1));
+  vi = __fadd_rn(__fmul_rn(vi, b2), __fmul_rn(__fmul_rn(w2, gr), gr));   // addcmul: (value*t1)*t2
+  const float denom = __fadd_rn(__fdiv_rn(__fsqrt_rn(vi), inv_sqrt_bc2_denom), eps);
+  p[i] = __fadd_rn(p[i], __fdiv_rn(__fmul_rn(-step_size, mi), denom));          // addcdiv: (value*t1)/t2
+  m[i] = mi;
+  v[i] = vi;
+}
+
 __global__ void adam_flat_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                  float* __restrict__ v, size_t n, float step_size, float w1, float b2, float w2,
                                  float eps, float inv_sqrt_bc2_denom, float grad_scale) {
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    const float gr = g[i] * grad_scale;
-    float mi = m[i], vi = v[i];
-    // torch lerp: a + w*(b-a) for w < 0.5, else b - (b-a)*(1-w)
-    mi = (w1 < 0.5f) ? __fadd_rn(mi, __fmul_rn(w1, __fsub_rn(gr, mi)))
-                     : __fsub_rn(gr, __fmul_rn(__fsub_rn(gr, mi), 1.f - w1));
-    vi = __fadd_rn(__fmul_rn(vi, b2), __fmul_rn(__fmul_rn(w2, gr), gr));   // addcmul: (value*t1)*t2
-    const float denom = __fadd_rn(__fdiv_rn(__fsqrt_rn(vi), inv_sqrt_bc2_denom), eps);
-    p[i] = __fadd_rn(p[i], __fdiv_rn(__fmul_rn(-step_size, mi), denom));          // addcdiv: (value*t1)/t2
-    m[i] = mi;
-    v[i] = vi;
-  }
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+    adam_flat_update(p, g, m, v, i, step_size, w1, b2, w2, eps, inv_sqrt_bc2_denom, grad_scale);
 }
 
 extern "C" int nint_adam_flat(float* p, const float* g, float* m, float* v, size_t n, double lr, double beta1,
@@ -74,6 +81,151 @@ extern "C" int nint_adam_flat(float* p, const float* g, float* m, float* v, size
   const float sqrt_bc2 = (float)sqrt(bc2);
   hipLaunchKernelGGL(adam_flat_kernel, grid1d(n), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, step_size,
                      (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, sqrt_bc2, grad_scale);
+  NINT_LAUNCH_CHECK();
+  return NINT_OK;
+}
+
+// ------------------------------------------------------------------------------ gradient norm, clipping, skipped steps
+// The guard of the training step, decided on the device (nint.h has the arithmetic): S = sum g[i]^2 in f64 by the loss
+// kernels' two-stage fixed-order reduction -- NINT_GRAD_NORM_BLOCKS workgroups whatever the device, each thread a fixed
+// strided share of g, a tree in LDS, one workgroup folding the partials; no atomics, so S depends on (g, n) only.
+// Dword loads: g needs no more than its natural alignment, and the share of a thread does not depend on the pointer.
+#define GN_THREADS 1024
+__global__ __launch_bounds__(GN_THREADS) void grad_norm_partial_kernel(const float* __restrict__ g, size_t n,
+                                                                       double* __restrict__ partial) {
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+  double a0 = 0, a1 = 0, a2 = 0, a3 = 0;
+  for (; i + 3 * stride < n; i += 4 * stride) {               // four independent loads in flight per thread
+    const double x0 = g[i], x1 = g[i + stride], x2 = g[i + 2 * stride], x3 = g[i + 3 * stride];
+    a0 += x0 * x0; a1 += x1 * x1; a2 += x2 * x2; a3 += x3 * x3;
+  }
+  for (; i < n; i += stride) {
+    const double x = g[i];
+    a0 += x * x;
+  }
+  __shared__ double red[GN_THREADS];
+  red[threadIdx.x] = (a0 + a1) + (a2 + a3);
+  __syncthreads();
+  for (int s = GN_THREADS >> 1; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
+}
+
+// one workgroup of NINT_GRAD_NORM_BLOCKS threads: the fixed-order tree over the partials; every thread returns S
+__device__ __forceinline__ double grad_norm_fold(const double* __restrict__ partial, int nblocks) {
+  __shared__ double red[NINT_GRAD_NORM_BLOCKS];
+  red[threadIdx.x] = (int)threadIdx.x < nblocks ? partial[threadIdx.x] : 0.0;
+  __syncthreads();
+  for (int s = NINT_GRAD_NORM_BLOCKS >> 1; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+    __syncthreads();
+  }
+  return red[0];
+}
+
+__global__ __launch_bounds__(NINT_GRAD_NORM_BLOCKS) void grad_norm_final_kernel(const double* __restrict__ partial, int nblocks,
+                                                                                float grad_scale, double* __restrict__ out) {
+  const double S = grad_norm_fold(partial, nblocks);
+  if (threadIdx.x == 0) {
+    out[0] = S;
+    out[1] = (double)grad_scale * sqrt(S);
+  }
+}
+
+// the control kernel of nint_adam_flat_guarded: folds the partials, takes the step's decisions, keeps the counters
+__global__ __launch_bounds__(NINT_GRAD_NORM_BLOCKS) void adam_guard_kernel(const double* __restrict__ partial, int nblocks,
+                                                                           float grad_scale, double max_norm, int skip_nonfinite,
+                                                                           double lr, double beta1, double beta2,
+                                                                           double* __restrict__ state) {
+  const double S = grad_norm_fold(partial, nblocks);
+  if (threadIdx.x != 0) return;
+  const double gs = (double)grad_scale;
+  const double norm = gs * sqrt(S);
+  const bool finite = isfinite(S);
+  double coef = 1.0;
+  if (max_norm > 0.0) {
+    const double c = max_norm / (norm + 1e-6);
+    coef = c < 1.0 ? c : 1.0;                                 // (a NaN norm: 1)
+  }
+  const bool apply = finite || !skip_nonfinite;
+  const double step = state[NINT_OPT_APPLIED] + 1.0;
+  const double bc1 = 1.0 - pow(beta1, step);
+  const double bc2 = 1.0 - pow(beta2, step);
+  state[NINT_OPT_APPLIED] += apply ? 1.0 : 0.0;
+  state[NINT_OPT_SKIPPED] += apply ? 0.0 : 1.0;
+  state[NINT_OPT_CLIPPED] += (finite && coef < 1.0) ? 1.0 : 0.0;
+  state[NINT_OPT_CALLS] += 1.0;
+  if (finite) {
+    state[NINT_OPT_SUM_NORM] += norm;
+    state[NINT_OPT_FINITE] += 1.0;
+    if (norm > state[NINT_OPT_MAX_NORM]) state[NINT_OPT_MAX_NORM] = norm;
+  }
+  state[NINT_OPT_S] = S;
+  state[NINT_OPT_NORM] = norm;
+  state[NINT_OPT_COEF] = coef;
+  state[NINT_OPT_SCALE] = (double)(float)(gs * coef);
+  state[NINT_OPT_STEP_SIZE] = (double)(float)(lr / bc1);
+  state[NINT_OPT_SQRT_BC2] = (double)(float)sqrt(bc2);
+  state[NINT_OPT_APPLY] = apply ? 1.0 : 0.0;
+  state[14] = 0.0;
+  state[15] = 0.0;
+}
+
+// adam_flat_kernel with its step scalars read from `state` (f32 values held in doubles: the casts are exact)
+__global__ void adam_flat_guarded_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                         float* __restrict__ v, size_t n, const double* __restrict__ state, float w1, float b2,
+                                         float w2, float eps) {
+  if (state[NINT_OPT_APPLY] == 0.0) return;                   // a skipped step: nothing is stored
+  const float step_size = (float)state[NINT_OPT_STEP_SIZE], sqrt_bc2 = (float)state[NINT_OPT_SQRT_BC2];
+  const float grad_scale = (float)state[NINT_OPT_SCALE];
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+    adam_flat_update(p, g, m, v, i, step_size, w1, b2, w2, eps, sqrt_bc2, grad_scale);
+}
+
+extern "C" size_t nint_grad_norm_scratch_bytes(void) { return NINT_GRAD_NORM_BLOCKS * sizeof(double); }
+
+// the partial-sum launch; *nblocks = the number of partials written (0 for n == 0: the fold then gives S = 0)
+static int grad_norm_partials(const float* g, size_t n, double* scratch, hipStream_t st, int* nblocks) {
+  *nblocks = 0;
+  if (n == 0) return NINT_OK;
+  hipLaunchKernelGGL(grad_norm_partial_kernel, dim3(NINT_GRAD_NORM_BLOCKS), dim3(GN_THREADS), 0, st, g, n, scratch);
+  NINT_LAUNCH_CHECK();
+  *nblocks = NINT_GRAD_NORM_BLOCKS;
+  return NINT_OK;
+}
+
+extern "C" int nint_grad_norm_flat(const float* g, size_t n, float grad_scale, double* out, double* scratch,
+                                   size_t scratch_bytes, void* stream) {
+  if (!g || !out || !scratch || scratch_bytes < nint_grad_norm_scratch_bytes()) return NINT_E_ARG;
+  if (((((uintptr_t)out) | ((uintptr_t)scratch)) & 7) != 0) return NINT_E_ALIGN;
+  int nblocks;
+  const int rc = grad_norm_partials(g, n, scratch, (hipStream_t)stream, &nblocks);
+  if (rc != NINT_OK) return rc;
+  hipLaunchKernelGGL(grad_norm_final_kernel, dim3(1), dim3(NINT_GRAD_NORM_BLOCKS), 0, (hipStream_t)stream, scratch, nblocks,
+                     grad_scale, out);
+  NINT_LAUNCH_CHECK();
+  return NINT_OK;
+}
+
+extern "C" int nint_adam_flat_guarded(float* p, const float* g, float* m, float* v, size_t n, double lr, double beta1,
+                                      double beta2, double eps, float grad_scale, double max_norm, int skip_nonfinite,
+                                      double* state, double* scratch, size_t scratch_bytes, void* stream) {
+  if (!p || !g || !m || !v || !state || !scratch || scratch_bytes < nint_grad_norm_scratch_bytes()) return NINT_E_ARG;
+  if (!(max_norm >= 0.0)) return NINT_E_ARG;                  // negative or NaN
+  if (((((uintptr_t)state) | ((uintptr_t)scratch)) & 7) != 0) return NINT_E_ALIGN;
+  hipStream_t st = (hipStream_t)stream;
+  int nblocks;
+  const int rc = grad_norm_partials(g, n, scratch, st, &nblocks);
+  if (rc != NINT_OK) return rc;
+  hipLaunchKernelGGL(adam_guard_kernel, dim3(1), dim3(NINT_GRAD_NORM_BLOCKS), 0, st, scratch, nblocks, grad_scale, max_norm,
+                     skip_nonfinite ? 1 : 0, lr, beta1, beta2, state);
+  NINT_LAUNCH_CHECK();
+  if (n == 0) return NINT_OK;
+  hipLaunchKernelGGL(adam_flat_guarded_kernel, grid1d(n), dim3(256), 0, st, p, g, m, v, n, state, (float)(1.0 - beta1),
+                     (float)beta2, (float)(1.0 - beta2), (float)eps);
   NINT_LAUNCH_CHECK();
   return NINT_OK;
 }

@@ -8,10 +8,15 @@ is nothing to overlap bucket-by-bucket.
 
 ``FusedAdam`` subclasses ``torch.optim.Optimizer`` so that ``StepLR`` (train.py:72) drives it
 unchanged and ``state_dict()`` is the torch Adam format (``state[i] = {step, exp_avg,
-exp_avg_sq}``, ``param_groups``) -- reference checkpoints (utils.py:23-50) interchange."""
+exp_avg_sq}``, ``param_groups``) -- reference checkpoints (utils.py:23-50) interchange.
+
+With ``max_grad_norm`` and / or ``skip_nonfinite`` the step is ``nint_adam_flat_guarded``: the global L2 norm of the bucket,
+``torch.nn.utils.clip_grad_norm_``'s coefficient and the decision to drop a non-finite step are all taken on the device, on
+the caller's stream, with no host read (include/nint.h has the arithmetic)."""
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import Iterable, List
 
 import torch
@@ -51,16 +56,30 @@ class FlatParams:
 
 
 class FusedAdam(torch.optim.Optimizer):
-    """torch.optim.Adam semantics (eps 1e-8, no weight decay, no amsgrad) in one HIP launch."""
+    """torch.optim.Adam semantics (eps 1e-8, no weight decay, no amsgrad) in one HIP launch.
 
-    def __init__(self, flat: FlatParams, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
+    ``max_grad_norm`` (a finite number >= 0; 0 = measure the norm, never clip) and ``skip_nonfinite`` switch the guarded step
+    on: three launches, the step's scalars and the applied-step count live in a small device buffer, and ``grad_stats()``
+    reports what happened.  Both off (the default): the plain step, unchanged."""
+
+    def __init__(self, flat: FlatParams, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=None, skip_nonfinite=False):
+        if max_grad_norm is not None:
+            max_grad_norm = float(max_grad_norm)
+            if not math.isfinite(max_grad_norm) or max_grad_norm < 0:
+                raise ValueError(f"max_grad_norm must be a finite number >= 0 (or None), got {max_grad_norm!r}")
         self.flat = flat
+        self.max_grad_norm = max_grad_norm
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.guarded = max_grad_norm is not None or self.skip_nonfinite
         defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=0, amsgrad=False, maximize=False,
                         foreach=None, capturable=False, differentiable=False, fused=None)
         super().__init__(flat.params, defaults)
         self.exp_avg = torch.zeros_like(flat.data)
         self.exp_avg_sq = torch.zeros_like(flat.data)
-        self._step = 0
+        self._step = 0          # guarded: the count as of the last state_dict() / load_state_dict(); the live one is on the device
+        if self.guarded:
+            self._opt_state = torch.zeros(_lib.NINT_OPT_STATE, dtype=torch.float64, device=flat.data.device)
+            self._norm_scratch = torch.empty(_lib.NINT_GRAD_NORM_BLOCKS, dtype=torch.float64, device=flat.data.device)
         self._bind_state()
 
     def _bind_state(self):
@@ -80,14 +99,46 @@ class FusedAdam(torch.optim.Optimizer):
         if not self.flat.is_intact():
             raise RuntimeError("a parameter was re-allocated after FlatParams was built; rebuild the optimizer")
         g = self.param_groups[0]
-        self._step += 1
         b1, b2 = g["betas"]
+        if self.guarded:
+            # the step number is state[NINT_OPT_APPLIED] + 1 on the device: a skipped step does not advance it
+            check(_lib.load().nint_adam_flat_guarded(
+                ptr(self.flat.data), ptr(self.flat.grad), ptr(self.exp_avg), ptr(self.exp_avg_sq), self.flat.numel,
+                float(g["lr"]), float(b1), float(b2), float(g["eps"]), float(grad_scale), self.max_grad_norm or 0.0,
+                int(self.skip_nonfinite), ptr(self._opt_state), ptr(self._norm_scratch), 8 * self._norm_scratch.numel(),
+                stream_ptr()), "nint_adam_flat_guarded")
+            return None
+        self._step += 1
         check(_lib.load().nint_adam_flat(ptr(self.flat.data), ptr(self.flat.grad), ptr(self.exp_avg), ptr(self.exp_avg_sq),
                                          self.flat.numel, float(g["lr"]), float(b1), float(b2), float(g["eps"]),
                                          self._step, float(grad_scale), stream_ptr()), "nint_adam_flat")
         for p in self.flat.params:
             self.state[p]["step"] = torch.tensor(float(self._step))
         return None
+
+    def grad_stats(self, reset: bool = False) -> dict:
+        """What the guarded steps did, in one device read: ``applied`` (Adam steps taken, the bias-correction count; never
+        reset), ``skipped`` (non-finite gradients dropped), ``clipped`` (steps with a coefficient below 1), ``calls``,
+        ``mean_norm`` / ``max_norm`` of the scaled gradient over the calls with a finite norm, and the last call's
+        ``last_norm`` / ``last_coef``.  ``reset=True`` zeroes everything but ``applied`` afterwards (per-epoch figures)."""
+        if not self.guarded:
+            raise RuntimeError("grad_stats() needs the guarded step: construct with max_grad_norm and / or skip_nonfinite")
+        s = self._opt_state.cpu().tolist()
+        if reset:
+            self._opt_state[_lib.NINT_OPT_SKIPPED:_lib.NINT_OPT_MAX_NORM + 1].zero_()
+        finite = s[_lib.NINT_OPT_FINITE]
+        return {"applied": int(s[_lib.NINT_OPT_APPLIED]), "skipped": int(s[_lib.NINT_OPT_SKIPPED]),
+                "clipped": int(s[_lib.NINT_OPT_CLIPPED]), "calls": int(s[_lib.NINT_OPT_CALLS]),
+                "mean_norm": s[_lib.NINT_OPT_SUM_NORM] / finite if finite else float("nan"),
+                "max_norm": s[_lib.NINT_OPT_MAX_NORM], "last_norm": s[_lib.NINT_OPT_NORM], "last_coef": s[_lib.NINT_OPT_COEF]}
+
+    def state_dict(self):
+        if self.guarded:
+            # the one host read of the guarded path, at checkpoint time: `step` of every parameter = applied steps
+            self._step = int(self._opt_state[_lib.NINT_OPT_APPLIED].item())
+            for p in self.flat.params:
+                self.state[p]["step"] = torch.tensor(float(self._step))
+        return super().state_dict()
 
     def load_state_dict(self, state_dict):
         super().load_state_dict(state_dict)      # torch-format dict (reference utils.py:42)
@@ -100,4 +151,6 @@ class FusedAdam(torch.optim.Optimizer):
                 self.exp_avg_sq[off:off + k].copy_(st["exp_avg_sq"].reshape(-1))
                 steps.append(int(float(st["step"])))
         self._step = max(steps) if steps else 0
+        if self.guarded:
+            self._opt_state[_lib.NINT_OPT_APPLIED] = float(self._step)
         self._bind_state()

@@ -5,7 +5,8 @@ MI355X step.  Same flags, same artefacts (`configurations.json`, `logger.npy`,
 stepped once per epoch before validation, checkpoint every 10 epochs); the per-batch
 `loss.item()` / sklearn R2 host syncs (train.py:113-114) are replaced by device accumulators read
 once per epoch.  Added flags: --dtype, --levels, --grid, --synthetic-steps, --pad-mode, --f32-inputs,
---static-channels, --sequence-loss, --test-skill, --lat-weighted-loss, --loss-weights.
+--static-channels, --sequence-loss, --test-skill, --lat-weighted-loss, --loss-weights, --clip-grad-norm,
+--skip-nonfinite-steps.
 
 The data path is on the device too: by default every batch is written by ONE launch of the
 fuse / z-score / halo-pad kernel straight into the model's bf16 input slab (dataset.slab_batch);
@@ -86,6 +87,11 @@ def get_arguments(argv=None, MODEL='LSTM-00', SPECIES='bcb', LEARNING_RATE=1.0E-
     parser.add_argument("--loss-weights", type=str, default=None, metavar="FILE.npy",
                         help="a --grid shaped (H, W) map of non-negative loss weights, 0 = leave the cell out (missing data, other "
                              "regions); with --lat-weighted-loss the two are multiplied")
+    parser.add_argument("--clip-grad-norm", type=float, default=None, metavar="X",
+                        help="clip the global L2 norm of the gradient to X before the Adam step (torch.nn.utils.clip_grad_norm_), "
+                             "on the device; under DDP the norm of the all-reduced mean gradient")
+    parser.add_argument("--skip-nonfinite-steps", action="store_true",
+                        help="drop an optimizer step whose gradient holds a NaN or inf (weights, moments and step count untouched)")
     args = parser.parse_args(argv)
     rank = int(os.environ.get("RANK", "0"))
     if rank == 0:
@@ -147,7 +153,9 @@ def main(args):
             raise SystemExit(f"--loss-weights {args.loss_weights}: shape {m.shape}, expected the --grid {(H, W)}")
         loss_weights = m if loss_weights is None else (loss_weights.astype(np.float64) * m).astype(np.float32)
     trainer = FusedTrainer(generator, lr=args.learning_rate, betas=tuple(args.betas), halo=halo,        # train.py:71
-                           sequence_loss=args.sequence_loss, loss_weights=loss_weights)
+                           sequence_loss=args.sequence_loss, loss_weights=loss_weights,
+                           max_grad_norm=args.clip_grad_norm, skip_nonfinite=args.skip_nonfinite_steps)
+    guarded = args.clip_grad_norm is not None or args.skip_nonfinite_steps
     optimizer = trainer.optimizer
     scheduler = optim.lr_scheduler.StepLR(optimizer, step_size=int(args.scheduler_config[0]),
                                           gamma=args.scheduler_config[1])                   # train.py:72
@@ -167,6 +175,7 @@ def main(args):
             if logger['first_step_loss'] is None:
                 logger['first_step_loss'] = float(loss)
         loss_e, r2_e = trainer.epoch_stats()                                                 # one host read per epoch (syncs)
+        gstats = trainer.grad_stats(reset=True) if guarded else None                         # (and one more with the guard on)
         logger['train_samples_per_s'].append(world * n_epoch / max(time.time() - t_epoch, 1e-9))   # data path included
         logger['MSELoss'].append(loss_e)                                                     # (MSE+L1, as in train.py:116)
         logger['r2_score'].append(r2_e)
@@ -179,6 +188,9 @@ def main(args):
         if rank == 0:
             print(f"Epoch: {epoch}, Loss: {logger['MSELoss'][-1]:.5f}, R2T: {logger['r2_score'][-1]:.5f}, "
                   f"R2V: {logger['r2_score_val'][-1]:.5f}")                                  # train.py:124
+            if guarded:
+                print(f"  grad norm: mean {gstats['mean_norm']:.5f}, max {gstats['max_norm']:.5f}, "
+                      f"clipped {gstats['clipped']}, skipped {gstats['skipped']} of {gstats['calls']} steps")
             print(f"  train loop incl. device preproc: {logger['train_samples_per_s'][-1]:.1f} samples/s")
             if epoch % 10 == 0:                                                              # train.py:126-136
                 d = os.path.join(args.snapshot_dir, f'epoch-{epoch:003d}')

@@ -7,7 +7,8 @@
                                                per-cell weighted means of loss.py (the _weighted entries)
     zero_grad; loss.backward()              -> nint_head_bwd + nint_seq_bwd (grads overwrite the bucket)
     [DDP]                                   -> ONE RCCL all-reduce of the flat gradient bucket
-    optimizer.step()                        -> nint_adam_flat (1/world folded in)
+    optimizer.step()                        -> nint_adam_flat (1/world folded in); with ``max_grad_norm`` / ``skip_nonfinite``
+                                               nint_adam_flat_guarded: norm, clipping and the skip decided on the device
     loss.item(); r2_score(...cpu())         -> device-side accumulators, read once per epoch
 
 No autograd graph, no per-kernel Python, no host synchronisation inside the step."""
@@ -28,14 +29,19 @@ from .optim import FlatParams, FusedAdam
 class FusedTrainer:
     def __init__(self, model: ConvLSTM, lr: float = 1e-3, betas=(0.5, 0.999), eps: float = 1e-8,
                  halo: Tuple[int, int] = (5, 5), process_group=None, distributed: Optional[bool] = None,
-                 overlap_allreduce: bool = False, sequence_loss: bool = False, loss_weights=None):
+                 overlap_allreduce: bool = False, sequence_loss: bool = False, loss_weights=None,
+                 max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False):
         dev = next(model.parameters()).device
         if dev.type != "cuda":
             raise _lib.NintError("FusedTrainer needs the model on the MI355X (cuda)")
         self.model = model
         self.device = dev
         self.flat = FlatParams(model)
-        self.optimizer = FusedAdam(self.flat, lr=lr, betas=betas, eps=eps)
+        # Gradient-norm clipping and dropping of non-finite steps (optim.FusedAdam): the norm is taken of the bucket the optimizer
+        # steps on -- under data parallelism the all-reduced sum with grad_scale = 1/world, so every rank takes the same decision
+        # from the same bits and nothing more is exchanged
+        self.optimizer = FusedAdam(self.flat, lr=lr, betas=betas, eps=eps, max_grad_norm=max_grad_norm,
+                                   skip_nonfinite=skip_nonfinite)
         self.halo = tuple(halo)
         self.lib = _lib.load()
         self.scratch = torch.zeros(NINT_LOSS_SCRATCH_FLOATS, dtype=torch.float32, device=dev)
@@ -209,6 +215,11 @@ class FusedTrainer:
     # ------------------------------------------------------------------ epoch statistics
     def reset_stats(self):
         self.stats.zero_()
+
+    def grad_stats(self, reset: bool = False) -> dict:
+        """The guarded optimizer's figures (FusedAdam.grad_stats): applied / skipped / clipped steps, calls, mean / max / last
+        gradient norm and the last clip coefficient.  One device read; identical on every rank."""
+        return self.optimizer.grad_stats(reset)
 
     def epoch_stats(self, pooled: bool = False):
         """One device->host read per epoch.  Returns what the reference logs over everything accumulated since
