@@ -292,6 +292,16 @@ typedef struct nint_launch_rec {
 int nint_debug_seq_plan(const nint_seq* s /*host*/, int bwd, nint_launch_rec* out /*host*/, int cap);
 
 /* ---- 1x1 head (model.py:251,274) ------------------------------------------------------------ */
+/* ONE rule decides which arithmetic every head entry below runs.  The "staged" bodies (weights zero-padded to [O][CHV] in
+ * LDS, CHV = 32 / 64 / 128 by Chp, the channels of a pixel in registers) hold a head with
+ *     Chp <= 128,  Chp % 4 == 0  and  (O * CHV + min(O, 64) * 64) * 4 + 8192 <= 160 KiB
+ * -- the weight image, one 64-output chunk of d loss / d pred of 64 pixels and 8 KiB of static LDS: what the fused passes
+ * keep in a CU's LDS (above 64 KiB with the dynamic-LDS opt-in).  nint_head_fwd[_seq] and the dh pass of nint_head_bwd[_seq]
+ * run their staged kernels under exactly this condition, although they keep the weights alone, and generic one-thread-per-
+ * element kernels (a plain chain over c < Ch: other roundings) beyond it; the fused entries (nint_head_loss_fused,
+ * nint_head_loss_seq_fused, their _weighted twins, nint_head_skill_accum) return NINT_E_SHAPE beyond it.  So wherever a fused
+ * entry runs, its separate launches run the same bodies, and "bit for bit" below holds for every shape a fused entry accepts
+ * (O = 200 on 128 channels included: a 100 KiB weight image). */
 /* pred (N,O,H,W) f32 = w (O,Ch) . h + b  from halo-slab images [n0, n0+N) */
 int nint_head_fwd(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w, const float* b,
                   float* pred, const nint_geom* g, int dtype, void* stream);
@@ -331,7 +341,8 @@ int nint_loss_mse_l1_crop(const float* pred, const float* y, float* dpred, float
 /* Training fast path: head forward + crop + loss + d loss/d pred + head backward-data in ONE pass over the pixels
  * (train.py:96-109 around model.py:274); the same arithmetic in the same order as nint_head_fwd ->
  * nint_loss_mse_l1_crop -> nint_head_bwd(dh).  pred is not materialised; dpred (N,O,H,W) is written for
- * nint_head_bwd(dh = NULL) to form dw / db.  Chp <= 128, else NINT_E_SHAPE (use the three separate entries). */
+ * nint_head_bwd(dh = NULL) to form dw / db.  Beyond the staged bodies' limit (the rule above the head entries: Chp > 128, or
+ * the weight image beyond the LDS) NINT_E_SHAPE: use the three separate entries. */
 int nint_head_loss_fused(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w, const float* b,
                          const float* y, float* dpred, void* dh, float* loss_out, double* stats, const nint_geom* g,
                          int oy, int ox, int Hc, int Wc, int dtype, void* stream);

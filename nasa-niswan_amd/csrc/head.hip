@@ -30,6 +30,16 @@ template <class F> static inline auto head_by_chv(int Chp, F&& f) {
   if (Chp <= 64) return f(std::integral_constant<int, 64>{});
   return f(std::integral_constant<int, 128>{});
 }
+// The ONE limit of the staged head arithmetic, for every entry that runs it: at most 128 padded channels in 4-channel vectors,
+// and the weight image [O][CHV] plus what the fused passes keep beside it -- one chunk of HEAD_OCH outputs' d loss / d pred of
+// 64 pixels, 8 KiB of static LDS -- within the 160 KiB of a CU.  nint_head_fwd[_seq] and the dh pass of nint_head_bwd[_seq]
+// keep nothing beside the weights, but take the same rule: wherever a fused pass runs, its separate launches run the SAME
+// bodies and give the same bits (the trainer and the skill path switch between the two silently).  Beyond it: the wide kernels.
+#define HEAD_OCH 64
+static inline bool head_staged_holds(int Chp, int O) {
+  if (Chp > 128 || Chp % 4 != 0) return false;
+  return ((size_t)O * head_chv(Chp) + (size_t)(O < HEAD_OCH ? O : HEAD_OCH) * 64) * sizeof(float) + 8192 <= 160 * 1024;
+}
 
 // The sequence entries (nint_head_fwd_seq and its kin) run the same bodies over all T*B images of the top layer's slab; only the
 // plane index of the (B, T*O, H, W) tensors differs: image n = t*B + b (time-major, as everywhere inside the library) owns the
@@ -444,15 +454,19 @@ static int head_fwd_impl(const void* h_slab, int n0, int N, int Ch, int Chp, int
   hipStream_t st = (hipStream_t)stream;
   const dim3 gp((unsigned)((npix + 255) / 256));
   const size_t w_lds = (size_t)O * head_chv(Chp) * sizeof(float);      // staged weights [O][CHV]
-  nint_by_dtype(dtype, [&](auto dt) {
+  const int rc = nint_by_dtype(dtype, [&](auto dt) -> int {
     constexpr int DT = decltype(dt)::value;
-    if (Chp <= 128 && Chp % 4 == 0 && w_lds <= 64 * 1024)
-      head_by_chv(Chp, [&](auto chv) {
-        hipLaunchKernelGGL((head_fwd_kernel<DT, decltype(chv)::value, SEQ>), gp, dim3(256), w_lds, st, h_slab, n0, N, Ch, Chp, O, w, b, pred, g->H, g->W, g->P, g->Hh, g->Wh, Bs);
+    if (head_staged_holds(Chp, O))
+      return head_by_chv(Chp, [&](auto chv) -> int {
+        auto kern = head_fwd_kernel<DT, decltype(chv)::value, SEQ>;
+        if (w_lds > 64 * 1024) NINT_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)w_lds));
+        hipLaunchKernelGGL(kern, gp, dim3(256), w_lds, st, h_slab, n0, N, Ch, Chp, O, w, b, pred, g->H, g->W, g->P, g->Hh, g->Wh, Bs);
+        return NINT_OK;
       });
-    else
-      hipLaunchKernelGGL((head_fwd_wide_kernel<DT, SEQ>), grid1d(total), dim3(256), 0, st, h_slab, n0, N, Ch, Chp, O, w, b, pred, g->H, g->W, g->P, g->Hh, g->Wh, Bs);
+    hipLaunchKernelGGL((head_fwd_wide_kernel<DT, SEQ>), grid1d(total), dim3(256), 0, st, h_slab, n0, N, Ch, Chp, O, w, b, pred, g->H, g->W, g->P, g->Hh, g->Wh, Bs);
+    return NINT_OK;
   });
+  if (rc != NINT_OK) return rc;
   NINT_LAUNCH_CHECK();
   return NINT_OK;
 }
@@ -489,15 +503,20 @@ static int head_bwd_impl(const void* h_slab, int n0, int N, int Ch, int Chp, int
   if (dh) {
     const dim3 gp((unsigned)((npix + 255) / 256));
     const size_t w_lds = (size_t)O * head_chv(Chp) * sizeof(float);    // staged weights [O][CHV]
-    nint_by_dtype(dtype, [&](auto dt) {
+    const int rc = nint_by_dtype(dtype, [&](auto dt) -> int {
       constexpr int DT = decltype(dt)::value;
-      if (w_lds > 64 * 1024 || Chp > 128 || Chp % 4 != 0)
+      if (!head_staged_holds(Chp, O)) {
         hipLaunchKernelGGL((head_bwd_dh_wide_kernel<DT, SEQ>), grid1d(npix * Chp), dim3(256), 0, st, w, dpred, dlast, Bs, T, dh, N, Ch, Chp, O, g->H, g->W);
-      else
-        head_by_chv(Chp, [&](auto chv) {
-          hipLaunchKernelGGL((head_bwd_dh_kernel<DT, decltype(chv)::value, SEQ>), gp, dim3(256), w_lds, st, w, dpred, dlast, Bs, T, dh, N, Ch, Chp, O, g->H, g->W);
-        });
+        return NINT_OK;
+      }
+      return head_by_chv(Chp, [&](auto chv) -> int {
+        auto kern = head_bwd_dh_kernel<DT, decltype(chv)::value, SEQ>;
+        if (w_lds > 64 * 1024) NINT_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)w_lds));
+        hipLaunchKernelGGL(kern, gp, dim3(256), w_lds, st, w, dpred, dlast, Bs, T, dh, N, Ch, Chp, O, g->H, g->W);
+        return NINT_OK;
+      });
     });
+    if (rc != NINT_OK) return rc;
     NINT_LAUNCH_CHECK();
   }
   if (!dw || !db) return NINT_OK;
@@ -691,7 +710,7 @@ extern "C" int nint_loss_mse_l1_crop_weighted(const float* pred, const float* y,
 // partial sums (train.py:102,105), d loss / d pred, and dL/dh = w^T . dpred.  One thread per pixel (grid-stride):
 // the channel vector is read once, pred never goes to memory, dpred is written for the head's weight gradient.
 // Same arithmetic, in the same order, as head_fwd_kernel -> loss_partial_kernel -> head_bwd_dh_kernel.
-#define HEAD_OCH 64
+// (HEAD_OCH outputs per chunk: head_staged_holds)
 // SEQ (nint_head_loss_seq_fused): the images are all T*B steps of the slab, image n = t*B + b; the targets are (B, T, O, Hc, Wc),
 // plane block b*T + t (head_image); dpred and dh stay in image order, which is what the weight-gradient stage and BPTT read.
 // WGT (the _weighted entries): loss_partial_kernel<true>'s terms; the pixel's weight is read once per pass, next to the crop

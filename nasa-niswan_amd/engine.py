@@ -333,7 +333,9 @@ class SeqEngine:
     @staticmethod
     def _beyond_fused_head(Chp: int, O: int) -> bool:
         """The fused head/loss kernels' limit: more than 128 padded channels, or the weights [O][CHV] plus one output chunk's
-        d loss / d pred of 64 pixels (and 8 KiB of static LDS) beyond the 160 KiB of a CU."""
+        d loss / d pred of 64 pixels (and 8 KiB of static LDS) beyond the 160 KiB of a CU.  The same rule (head_staged_holds in
+        csrc/head.hip) keeps nint_head_fwd / nint_head_bwd on their staged kernels, so the fallback of a shape the fused
+        kernels hold would give the same bits."""
         chv = 32 if Chp <= 32 else (64 if Chp <= 64 else 128)
         return Chp > 128 or (O * chv + min(O, 64) * 64) * 4 + 8192 > 160 * 1024
 

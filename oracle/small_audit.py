@@ -1,6 +1,6 @@
 """f64 references and derived error bounds for the kernels of ``csrc/pointwise.hip``, ``csrc/head.hip`` and ``csrc/pack.hip`` around the gate GEMMs: the 1x1
-head, the crop + MSE + L1 loss, their fused form, flat Adam, the layout packers and the preproc (TEST INFRASTRUCTURE
-ONLY; numpy / torch-CPU, no GPU).
+head, the crop + MSE + L1 loss, their fused form, flat Adam, the layout packers, the preproc and the evaluation skill sums
+(TEST INFRASTRUCTURE ONLY; numpy / torch-CPU, no GPU).
 
 Every reference is computed from the values the kernel READS as they are stored (bf16 inputs upcast exactly, like
 ``oracle/stored_audit.py``), and every comparator looks at every element: nothing is skipped, masked or budgeted.  A
@@ -17,16 +17,19 @@ from __future__ import annotations
 
 import numpy as np
 
-__all__ = ["U", "halfulp_bf16", "gamma", "AuditError", "ratio", "check_equal", "bf16_round", "decode_bf16",
+__all__ = ["U", "U64", "halfulp_bf16", "gamma", "AuditError", "ratio", "check_equal", "bf16_round", "decode_bf16",
            "head_fwd", "head_bwd_dh", "loss", "check_loss_scalar", "check_stats", "head_loss_fused", "adam",
-           "pack_btchw", "unpack_halo", "pack_compact", "unpack_compact", "unfold_dx", "preproc", "make_geom"]
+           "pack_btchw", "unpack_halo", "pack_compact", "unpack_compact", "unfold_dx", "preproc", "make_geom",
+           "SKILL_PIX", "SKILL_SAMPLE", "skill_terms", "skill_sums", "skill_head_pred", "skill_audit", "skill_int_data",
+           "skill_head_int_data", "skill_slots"]
 
 U = 2.0 ** -24
+U64 = 2.0 ** -53      # the f64 unit roundoff (the skill sums)
 SUM_RTOL = 1e-12      # double-precision sums of at most a few 1e5 terms (the tolerance tests/test_gpu_small_kernels.py uses)
 
 
-def gamma(k: int) -> float:
-    return k * U / (1.0 - k * U)
+def gamma(k: int, u: float = U) -> float:
+    return k * u / (1.0 - k * u)
 
 
 class AuditError(AssertionError):
@@ -429,3 +432,158 @@ def preproc(srcs, nstatic: int, mean, std, t0, T: int, Hp: int, Wp: int, mode: i
                 row = z[cflip, ys[yp]] if flip[yp] else z[:, ys[yp]]
                 out[b, t, :, yp, :] = row[:, xs]
     return out
+
+
+# --------------------------------------------------------------------------- evaluation: skill sums
+SKILL_PIX, SKILL_SAMPLE = 5, 8     # include/nint.h NINT_SKILL_PIX / NINT_SKILL_SAMPLE
+
+
+def skill_terms(pred, y, oy: int, ox: int, row_w=None):
+    """The f64 terms of nint_skill_accum, each formed as csrc/head.hip documents it: ``p = (double)pred`` on the crop,
+    ``t = (double)y``, ``d = p - t`` (one f64 subtraction), every product one f64 multiplication of its own.  pred
+    (N, O, H, W) f32, y (N, O, Hc, Wc) f32, row_w (Hc) f64 or None (= 1).  Returns the map terms (SKILL_PIX, N, O, Hc, Wc)
+    in the order of a slot's planes [t, p, t^2, p^2, d^2] and the sample terms (SKILL_SAMPLE, N, O, Hc, Wc) in the order
+    of a sample row [d^2, |d|, t, t^2, p, p^2, rw t, rw p]."""
+    pred, y = np.asarray(pred, np.float32), np.asarray(y, np.float32)
+    Hc, Wc = y.shape[-2:]
+    p = pred[:, :, oy:oy + Hc, ox:ox + Wc].astype(np.float64)
+    t = y.astype(np.float64)
+    if p.shape != t.shape:
+        raise ValueError(f"crop {p.shape} against targets {t.shape}")
+    rw = np.ones(Hc) if row_w is None else np.asarray(row_w, np.float64)
+    rw = rw[None, None, :, None]
+    d = p - t
+    dd, tt, pp = d * d, t * t, p * p
+    return np.stack([t, p, tt, pp, dd]), np.stack([dd, np.abs(d), t, tt, p, pp, rw * t, rw * p])
+
+
+def _slots(slot, N: int):
+    return np.zeros(N, np.int64) if slot is None else np.asarray(slot, np.int64)
+
+
+def skill_sums(pred, y, oy: int, ox: int, slot, nslots: int, row_w, pix_before):
+    """nint_skill_accum in f64 numpy.  slot: N ints in [-1, nslots) or None (all 0); pix_before (S, SKILL_PIX, O, Hc, Wc)
+    f64 with S >= nslots (further slots are carried through untouched).  A map cell grows in the kernel's documented
+    order -- the stored value, then the slot's samples n ascending, one f64 addition each -- so ``pix`` is what the kernel
+    must return bit for bit on ANY data as long as every term is a single f64 operation; a sample row is numpy's sum
+    over the crop (another order than the kernel's tree: equal only where the sums are exact).  Returns a dict:
+    pix, sample (N, O, SKILL_SAMPLE); pix_abs, sample_abs = the sums of the addends' magnitudes (the stored value
+    included); pix_n, sample_n = the number of addends (a stored value of exactly 0 adds no rounding and is not
+    counted)."""
+    mt, st = skill_terms(pred, y, oy, ox, row_w)
+    N = mt.shape[1]
+    sl = _slots(slot, N)
+    if sl.shape != (N,) or sl.min() < -1 or sl.max() >= nslots:
+        raise ValueError("slot")
+    pix = np.array(pix_before, np.float64, copy=True)
+    mag = np.abs(pix)
+    cnt = (pix != 0).astype(np.int64)
+    for n in range(N):
+        if sl[n] >= 0:
+            pix[sl[n]] = pix[sl[n]] + mt[:, n]
+            mag[sl[n]] += np.abs(mt[:, n])
+            cnt[sl[n]] += 1
+    sample = st.sum(axis=(3, 4)).transpose(1, 2, 0)
+    return {"pix": pix, "sample": np.ascontiguousarray(sample), "pix_abs": mag,
+            "sample_abs": np.ascontiguousarray(np.abs(st).sum(axis=(3, 4)).transpose(1, 2, 0)), "pix_n": cnt,
+            "sample_n": st.shape[3] * st.shape[4]}
+
+
+def skill_head_pred(h, w, b) -> np.ndarray:
+    """The prediction nint_head_skill_accum forms from h (N, Hc, Wc, Ch) -- the stored values on the crop -- w (O, Ch) and
+    b (O) or None, for data on which every partial sum of the head is exact in f32 (skill_head_int_data): the f64 result
+    IS the f32 one, whatever the order and whether or not a product is fused into its add.  Raises where that does not
+    hold.  Returns (N, O, Hc, Wc) f32."""
+    pred, _ = head_fwd(h, w, b)
+    p32 = pred.astype(np.float32)
+    mag = np.einsum("nyxc,oc->noyx", np.abs(np.asarray(h, np.float64)), np.abs(np.asarray(w, np.float64)))
+    mag = mag + (0.0 if b is None else np.abs(np.asarray(b, np.float64))[None, :, None, None])
+    # h integers and w, b multiples of 1/4: every product and every partial sum, in any order, is a multiple of 1/4 of
+    # magnitude at most mag; below 2^24 / 4 all of them are f32 numbers, and a fused multiply-add rounds nothing either
+    h64, w4 = np.asarray(h, np.float64), 4.0 * np.asarray(w, np.float64)
+    b4 = np.zeros(1) if b is None else 4.0 * np.asarray(b, np.float64)
+    if not (np.array_equal(h64, np.rint(h64)) and np.array_equal(w4, np.rint(w4)) and np.array_equal(b4, np.rint(b4))
+            and 4.0 * float(mag.max()) < 2.0 ** 24):
+        raise ValueError("the head's partial sums are not exact in f32 on this data")
+    assert np.array_equal(p32.astype(np.float64), pred)
+    return p32
+
+
+def skill_audit(pred, y, oy: int, ox: int, slot, nslots: int, row_w, pix_before, pix_got, sample_got, what: str = "skill"):
+    """Any-order audit of nint_skill_accum's results on arbitrary f32 data.  The error of every map cell and every sample
+    row is taken against the EXACT sum of its f64 addends: ``math.fsum(addends + [-got])`` is the correctly rounded value of
+    ``sum - got``, so the reference carries no rounding of its own.  Bound: ``gamma(n - 1, U64) * sum |addends|`` with n
+    the number of addends -- a cell's non-zero stored value and the slot's samples, Hc * Wc for a sample row -- which holds
+    for every summation order (Higham 4.4), tree, chain or split into calls alike; n <= 1 leaves no freedom: equality.
+    Raises AuditError naming the worst element; returns (worst map ratio, worst row ratio)."""
+    import math
+    mt, st = skill_terms(pred, y, oy, ox, row_w)
+    N, O = mt.shape[1:3]
+    sl = _slots(slot, N)
+    before = np.asarray(pix_before, np.float64)
+    pix_got, sample_got = np.asarray(pix_got, np.float64), np.asarray(sample_got, np.float64)
+    if pix_got.shape != before.shape or sample_got.shape != (N, O, SKILL_SAMPLE):
+        raise AuditError(f"{what}: shapes {pix_got.shape} / {sample_got.shape}")
+    worst = [0.0, 0.0]
+
+    def one(addends, got, idx, k):
+        n = len(addends)
+        err = abs(math.fsum(addends + [-got])) if math.isfinite(got) else math.inf
+        bound = gamma(max(n - 1, 0), U64) * math.fsum(abs(a) for a in addends)
+        if err > bound:
+            raise AuditError(f"{what}: {'map cell' if k == 0 else 'sample row'} {idx}: got {got!r}, exact sum "
+                             f"{math.fsum(addends)!r}, |error| {err:.3e} over the bound {bound:.3e} of {n} addends")
+        if err > 0:
+            worst[k] = max(worst[k], err / bound)
+
+    for s in range(before.shape[0]):
+        members = [n for n in range(N) if sl[n] == s]
+        if not members:
+            check_equal(pix_got[s], before[s], f"{what}: slot {s} has no sample in the call")
+            continue
+        cols = mt[:, members].transpose(0, 2, 3, 4, 1).reshape(before[s].size, len(members)).tolist()
+        b0, g0 = before[s].reshape(-1).tolist(), pix_got[s].reshape(-1).tolist()
+        for i, (c, b, g) in enumerate(zip(cols, b0, g0)):
+            one(([b] if b != 0 else []) + c, g, (s,) + tuple(int(j) for j in np.unravel_index(i, before.shape[1:])), 0)
+    rows = st.transpose(1, 2, 0, 3, 4).reshape(N, O, SKILL_SAMPLE, -1)
+    for n in range(N):
+        for o in range(O):
+            for k in range(SKILL_SAMPLE):
+                one(rows[n, o, k].tolist(), float(sample_got[n, o, k]), (n, o, k), 1)
+    return worst[0], worst[1]
+
+
+def skill_slots(N: int) -> list:
+    """slot[n] = (7 n mod 13) - 1: twelve slots in non-monotone order, and -1 (out of the maps) at n = 0, 13, ..."""
+    return [(7 * n) % 13 - 1 for n in range(N)]
+
+
+def skill_int_data(rng, N: int, O: int, H: int, W: int, oy: int, ox: int, Hc: int, Wc: int, S: int):
+    """Data on which every skill sum is exact in ANY order: pred and y integer-valued f32 in [-8, 8] (pred NaN outside the
+    crop window: never to be read), row_w = k / 8 with k in 1..16, pix_before integer-valued in [-1000, 1000].  Every
+    addend is then a multiple of 1/8 and the magnitudes of a cell or row sum far below 2^53 / 8, so every partial sum is
+    representable.  Returns (pred, y, row_w, pix_before (S, SKILL_PIX, O, Hc, Wc))."""
+    pred = np.full((N, O, H, W), np.nan, np.float32)
+    pred[:, :, oy:oy + Hc, ox:ox + Wc] = rng.integers(-8, 9, (N, O, Hc, Wc))
+    y = rng.integers(-8, 9, (N, O, Hc, Wc)).astype(np.float32)
+    row_w = rng.integers(1, 17, Hc).astype(np.float64) / 8.0
+    before = rng.integers(-1000, 1001, (S, SKILL_PIX, O, Hc, Wc)).astype(np.float64)
+    return pred, y, row_w, before
+
+
+def skill_head_int_data(rng, n0: int, N: int, Ch: int, Chp: int, O: int, geom, oy: int, ox: int, Hc: int, Wc: int, bias=True):
+    """A hidden-state slab and head on which nint_head_skill_accum is exact in any order, with or without FMA: h
+    integer-valued in [-4, 4] (exact in bf16) on the crop window of images [n0, n0 + N), w = k / 4 with |k| <= 8, b an
+    integer in [-8, 8]: every head partial sum is a multiple of 1/4 below 2^11.  Everything the kernel must not read is
+    NaN -- the images below n0, the halo ring, the slack, the interior outside the crop window -- except the channel
+    padding [Ch, Chp) of the crop's pixels, which is zero as every producer of a slab leaves it.  Returns (slab
+    (n0 + N, Hh, Wh, Chp) f32 values, h (N, Hc, Wc, Ch) of the crop, w, b or None)."""
+    H, W, P, Hh, Wh = geom
+    slab = np.full((n0 + N, Hh, Wh, Chp), np.nan, np.float32)
+    h = rng.integers(-4, 5, (N, Hc, Wc, Ch)).astype(np.float32)
+    win = slab[n0:, P + oy:P + oy + Hc, P + ox:P + ox + Wc]
+    win[..., :Ch] = h
+    win[..., Ch:] = 0
+    w = (rng.integers(-8, 9, (O, Ch)) / 4.0).astype(np.float32)
+    b = rng.integers(-8, 9, O).astype(np.float32) if bias else None
+    return slab, h, w, b

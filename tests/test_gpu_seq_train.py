@@ -188,10 +188,11 @@ HEAD_GRID = [(Ch, O) for Ch in (8, 40, 72, 136) for O in (1, 3)]
 
 
 @pytest.mark.parametrize("dtype", ["f32", "bf16"])
-@pytest.mark.parametrize("Ch,O", HEAD_GRID)
+@pytest.mark.parametrize("Ch,O", HEAD_GRID + [(72, 200), (136, 200)])
 def test_head_fwd_seq_equals_the_per_step_launches_bit_for_bit(pkg, Ch, O, dtype):
     """Ch 8 / 40 / 72 / 136: the 32-, 64-, 128-channel register bodies and the generic wide body (f32 pads 40 to 48 and 72 to 80,
-    bf16 to 64 and 96; 136 pads beyond 128 in both)."""
+    bf16 to 64 and 96; 136 pads beyond 128 in both).  200 outputs at 72 channels: a weight image [O][128] of 100 KiB, the staged
+    body with the dynamic-LDS opt-in; at 136 channels the wide body at a large O."""
     hc = HeadCase(pkg, Ch, O, dtype)
     seq, ref = hc.fwd_seq(), hc.fwd_steps()
     assert torch.isfinite(seq).all() and torch.equal(seq, ref)

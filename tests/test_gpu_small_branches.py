@@ -143,23 +143,23 @@ def test_fused_adam_optimizer_default_betas_take_the_first_lerp_formula(lib):
 
 
 # =========================================================================== 1x1 head
+def head_fused_holds(Chp, O):
+    """The ONE limit of the staged head arithmetic (csrc/head.hip head_staged_holds, engine._beyond_fused_head): at most 128
+    padded channels in 4-channel vectors, and the weight image [O][CHV] plus one 64-output chunk of d loss / d pred of 64
+    pixels plus 8 KiB of static LDS within the 160 KiB of a CU"""
+    chv = 32 if Chp <= 32 else (64 if Chp <= 64 else 128)
+    return Chp <= 128 and Chp % 4 == 0 and (O * chv + min(O, 64) * 64) * 4 + 8192 <= 160 * KIB
+
+
 def head_dispatch(dt, Ch, O):
-    """nint_head_fwd / nint_head_bwd: which kernel runs (the conditions of the host code, in its order)"""
+    """nint_head_fwd / nint_head_bwd: which kernel runs (the condition of the host code): the staged kernels wherever the
+    fused head passes hold the shape -- with the dynamic-LDS opt-in once the weight image exceeds 64 KiB -- so that fused and
+    unfused entries run the same arithmetic; the wide kernels beyond"""
     kc = 32 if dt else 16
     Chp = (Ch + kc - 1) // kc * kc
     chv = 32 if Chp <= 32 else (64 if Chp <= 64 else 128)
     w_lds = O * chv * 4
-    fwd = f"staged{chv}" if (Chp <= 128 and Chp % 4 == 0 and w_lds <= 64 * KIB) else "wide"
-    if w_lds > 64 * KIB:
-        bwd = "wide"
-    elif Chp <= 32 and Chp % 4 == 0:
-        bwd = "staged32"
-    elif Chp <= 64 and Chp % 4 == 0:
-        bwd = "staged64"
-    elif Chp <= 128 and Chp % 4 == 0:
-        bwd = "staged128"
-    else:
-        bwd = "wide"
+    fwd = bwd = f"staged{chv}" if head_fused_holds(Chp, O) else "wide"
     return Chp, chv, w_lds, fwd, bwd
 
 
@@ -189,8 +189,11 @@ HEAD_CASES = [
     pytest.param(1, 128, 20, "staged128", False, 1, id="staged128-bf16-Chp128-no-bias-n0=1"),
     pytest.param(0, 160, 4, "wide", True, 1, id="wide[Chp>128]-f32-Ch160-n0=1"),
     pytest.param(1, 160, 4, "wide", False, 0, id="wide[Chp>128]-bf16-Ch160-no-bias"),
-    pytest.param(0, 16, 600, "wide", True, 0, id="wide[weights>64KiB]-f32-O600-Ch16"),
-    pytest.param(1, 16, 600, "wide", True, 1, id="wide[weights>64KiB]-bf16-O600-Ch16-n0=1"),
+    pytest.param(0, 16, 600, "staged32", True, 0, id="staged32-LDS-opt-in[weights>64KiB]-f32-O600-Ch16"),
+    pytest.param(1, 128, 200, "staged128", True, 1, id="staged128-LDS-opt-in[weights>64KiB]-bf16-O200-Ch128-n0=1"),
+    pytest.param(1, 16, 1088, "staged32", False, 0, id="staged32-LDS-opt-in[last O the rule admits]-bf16-O1088-Ch16-no-bias"),
+    pytest.param(0, 16, 1200, "wide", True, 0, id="wide[weights beyond the LDS rule]-f32-O1200-Ch16"),
+    pytest.param(1, 16, 1200, "wide", True, 1, id="wide[weights beyond the LDS rule]-bf16-O1200-Ch16-n0=1"),
 ]
 
 
@@ -198,8 +201,11 @@ HEAD_CASES = [
 def test_head_fwd_and_dh_elementwise_at_every_dispatch_branch(lib, dt, Ch, O, kernel, bias, n0):
     Chp, chv, w_lds, fwd, bwd = head_dispatch(dt, Ch, O)
     assert fwd == kernel and bwd == kernel
-    if O == 600:
-        assert O * chv * 4 > 64 * KIB
+    assert (kernel != "wide" and w_lds > 64 * KIB) == (O in (200, 600, 1088))                  # the hipFuncSetAttribute branch
+    if O == 1200:
+        assert Chp <= 128 and not head_fused_holds(Chp, O)
+    if O == 1088:
+        assert head_fused_holds(Chp, O) and not head_fused_holds(Chp, O + 1)
     N, H, W, Pd = 2, 9, 13, 2
     g, Chp, hsl, h, w, b, rng = head_inputs(lib, dt, Ch, O, N, n0, H, W, Pd, 30 + Ch + O, bias)
     wd, bd = dev(w), (dev(b) if bias else None)
@@ -229,15 +235,25 @@ FUSED_CASES = [
     pytest.param(0, 128, 128, 1, 1, 6, 11, 1, 2, 4, 7, 128, ("optin",), id="fused128-f32-LDS-opt-in[lds+8KiB>64KiB]-O128-n0=1"),
     pytest.param(0, 16, 1, 2, 0, 150, 220, 5, 4, 140, 212, 32, ("many",), id="fused32-f32-grid-stride[npix/64>LOSS_BLOCKS_MAX]"),
     pytest.param(1, 16, 2, 2, 0, 150, 220, 5, 4, 140, 212, 32, ("many",), id="fused32-bf16-grid-stride[npix/64>LOSS_BLOCKS_MAX]"),
+    # "window": the weight image alone is beyond 64 KiB while the fused LDS rule still holds.  The unfused entries must run
+    # their staged kernels there too (with the LDS opt-in), or "fused = the three launches bit for bit" fails
+    pytest.param(1, 128, 200, 1, 0, 9, 13, 2, 2, 5, 9, 128, ("window", "optin"), id="fused128-bf16-window[weights>64KiB]-Ch128-O200"),
+    pytest.param(0, 48, 300, 1, 1, 9, 13, 2, 1, 5, 11, 64, ("window", "optin"), id="fused64-f32-window[weights>64KiB]-Ch48-O300-n0=1"),
+    pytest.param(0, 16, 600, 2, 0, 9, 13, 2, 3, 4, 5, 32, ("window", "optin"), id="fused32-f32-window[weights>64KiB]-Ch16-O600"),
+    pytest.param(1, 16, 1088, 1, 0, 9, 13, 2, 2, 5, 9, 32, ("window", "optin"), id="fused32-bf16-window[last O the LDS rule admits]-Ch16-O1088"),
 ]
 
 
 @pytest.mark.parametrize("dt,Ch,O,N,n0,H,W,oy,ox,Hc,Wc,want_chv,tags", FUSED_CASES)
 def test_head_loss_fused_elementwise(lib, dt, Ch, O, N, n0, H, W, oy, ox, Hc, Wc, want_chv, tags):
-    Chp, chv, _, _, _ = head_dispatch(dt, Ch, O)
+    Chp, chv, w_lds, fwd, bwd = head_dispatch(dt, Ch, O)
     assert Chp <= 128 and Chp % 4 == 0 and chv == want_chv      # nint_head_loss_fused: Chp > 128 -> NINT_E_SHAPE; CHV by Chp
     lds = (O * chv + min(O, 64) * 64) * 4                         # nint_head_loss_fused: weights [O][CHV] + one output chunk of dpred
-    assert lds + 8192 <= 160 * KIB
+    assert lds + 8192 <= 160 * KIB and head_fused_holds(Chp, O)
+    assert ("window" in tags) == (w_lds > 64 * KIB)
+    assert fwd == bwd == f"staged{chv}"                           # the unfused pair runs the same staged arithmetic
+    if O == 1088:
+        assert not head_fused_holds(Chp, O + 1)
     npix = N * H * W
     assert ("optin" in tags) == (lds + 8192 > 64 * KIB)           # hipFuncSetAttribute branch
     assert ("many" in tags) == ((npix + 63) // 64 > LOSS_BLOCKS_MAX)

@@ -10,10 +10,18 @@ kernel's; the order of the sums is varied) must pass its comparator, and each pl
   head     bias added twice / not at all; channel Ch-1 dropped; outputs o and o+1 swapped; a non-zero pad channel in dh
   layout   the b0 offset of the second preproc chunk dropped; the mode-0 flip taking mean and std from channel c instead
            of C-1-c; pt and pb swapped on an odd pad; fold tap kx mirrored
+  skill    a sample of slot -1 added to a map; a sample dropped from its slot; a map cell or a sample row a few ulps off;
+           a partial row left out of a sample row; a slot without samples touched
+
+The skill sums' exact model (skill_sums, skill_head_pred) is also PROVED order-free on the integer data sets of
+tests/skill_exact_cases.py: evaluated again in Python integers / fractions.Fraction it gives the same numbers exactly.
 """
+import fractions
+
 import numpy as np
 import pytest
 
+import skill_exact_cases as SX
 from oracle import preproc_oracle as PO
 from oracle import small_audit as SM
 
@@ -447,3 +455,153 @@ def test_preproc_mutations_fail():
     slab = SM.pack_btchw(ref[:2], 16, geom, 3, True)
     SM.check_equal(pack_elementwise(ref[:2], 16, geom, 3, True), slab)
     fails(lambda: SM.check_equal(pack_elementwise(ref[:2], 16, geom, 3, True, "kx_mirrored"), slab))
+
+
+# --------------------------------------------------------------------------- evaluation: skill sums
+def _exact_int_sums(mt, st, slots, before, scale):
+    """the model's sums again, in int64 arithmetic on the terms times `scale` (every term must be an integer then)"""
+    mi, si = np.rint(mt * scale).astype(np.int64), np.rint(st * scale).astype(np.int64)
+    assert np.array_equal(mi.astype(np.float64), mt * scale) and np.array_equal(si.astype(np.float64), st * scale)
+    named = before[:SX.NSLOTS - 1]
+    pix = np.rint(named * scale).astype(np.int64)
+    assert np.array_equal(pix.astype(np.float64), named * scale)
+    for n, s_ in enumerate(slots):
+        if s_ >= 0:
+            pix[s_] += mi[:, n]
+    return pix, si.sum(axis=(3, 4)).transpose(1, 2, 0)
+
+
+def _assert_order_free(mt, st, slots, before, ref, scale):
+    pix_i, smp_i = _exact_int_sums(mt, st, slots, before, scale)
+    # every partial sum, in any order, is a multiple of 1 / scale of magnitude at most the sum of the magnitudes: below
+    # 2^53 / scale each one is an f64 number, so no addition of the kernel or of the model rounds
+    assert scale * float(ref["pix_abs"][:SX.NSLOTS - 1].max()) < 2.0 ** 53 and scale * float(ref["sample_abs"].max()) < 2.0 ** 53
+    assert np.array_equal(ref["pix"][:SX.NSLOTS - 1] * scale, pix_i.astype(np.float64))
+    assert np.array_equal(ref["sample"] * scale, smp_i.astype(np.float64))
+    SM.check_equal(ref["pix"][SX.NSLOTS - 1], before[SX.NSLOTS - 1], "sentinel slot")
+
+
+@pytest.mark.parametrize("name", list(SX.PLAIN_CASES))
+def test_skill_model_is_exact_and_order_free_on_the_plain_integer_data(name):
+    c = SX.PLAIN_CASES[name]
+    pred, y, row_w, before, slots = SX.plain_data(name)
+    assert np.isnan(pred).sum() == c.N * c.O * (c.H * c.W - c.Hc * c.Wc)         # NaN exactly outside the crop window
+    ref = SM.skill_sums(pred, y, c.oy, c.ox, slots, SX.NSLOTS, row_w, before)
+    mt, st = SM.skill_terms(pred, y, c.oy, c.ox, row_w)
+    assert np.isfinite(mt).all() and np.isfinite(st).all()
+    sl = [0] * c.N if slots is None else slots
+    _assert_order_free(mt, st, sl, before, ref, 8)
+    # the samples in reverse order, the crop summed column by column: the same bits
+    pix = before.copy()
+    for n in reversed(range(c.N)):
+        if sl[n] >= 0:
+            pix[sl[n]] = mt[:, n] + pix[sl[n]]
+    SM.check_equal(pix, ref["pix"], "reversed sample order")
+    SM.check_equal(np.ascontiguousarray(st.sum(axis=3).sum(axis=3).transpose(1, 2, 0)), ref["sample"], "columns first")
+    assert ref["sample_n"] == c.Hc * c.Wc
+    if slots is not None and c.slots == "none":
+        SM.check_equal(ref["pix"], before, "every slot -1")
+
+
+def test_skill_model_against_fractions():
+    """one case evaluated with fractions.Fraction from the stored f32 / f64 values, nothing scaled"""
+    name = "1x257-N5-O7"
+    c = SX.PLAIN_CASES[name]
+    pred, y, row_w, before, slots = SX.plain_data(name)
+    ref = SM.skill_sums(pred, y, c.oy, c.ox, slots, SX.NSLOTS, row_w, before)
+    F = fractions.Fraction
+    for n in range(c.N):
+        for o in range(0, c.O, 3):
+            rows = [F(0)] * 8
+            for cx in range(c.Wc):
+                p, t, rw = F(float(pred[n, o, c.oy, c.ox + cx])), F(float(y[n, o, 0, cx])), F(float(row_w[0]))
+                d = p - t
+                for k, v in enumerate((d * d, abs(d), t, t * t, p, p * p, rw * t, rw * p)):
+                    rows[k] += v
+            assert [F(float(v)) for v in ref["sample"][n, o]] == rows
+    for s_ in range(SX.NSLOTS - 1):
+        want = F(float(before[s_, 4, 2, 0, 100]))
+        for n in range(c.N):
+            if slots[n] == s_:
+                want += (F(float(pred[n, 2, c.oy, c.ox + 100])) - F(float(y[n, 2, 0, 100]))) ** 2
+        assert F(float(ref["pix"][s_, 4, 2, 0, 100])) == want
+
+
+@pytest.mark.parametrize("name", list(SX.FUSED_CASES))
+def test_skill_head_model_is_exact_and_order_free_on_the_fused_integer_data(name):
+    c = SX.FUSED_CASES[name]
+    slab, h, w, b, y, row_w, before, slots, gt = SX.fused_data(name)
+    Chp = SX.chp_of(c.dt, c.Ch)
+    assert Chp <= 128 and Chp % 4 == 0 and ("Chp" not in name or Chp > c.Ch) and (b is None) == (not c.bias)
+    SM.check_equal(SM.bf16_round(np.nan_to_num(slab)), np.nan_to_num(slab), "the slab is exact in bf16")
+    # NaN wherever the kernel must not read; zeros in the crop's channel padding
+    live = np.zeros(slab.shape, bool)
+    live[c.n0:, c.P + c.oy:c.P + c.oy + c.Hc, c.P + c.ox:c.P + c.ox + c.Wc] = True
+    assert np.isnan(slab[~live]).all() and np.isfinite(slab[live]).all()
+    assert not slab[c.n0:, c.P + c.oy:c.P + c.oy + c.Hc, c.P + c.ox:c.P + c.ox + c.Wc, c.Ch:].any()
+    pred = SM.skill_head_pred(h, w, b)
+    # the head in f32, channel by channel from either end, rounding each product and each add: the same bits
+    for order in (range(c.Ch), reversed(range(c.Ch))):
+        acc = np.zeros(pred.shape, f32) if b is None else np.broadcast_to(b[None, :, None, None], pred.shape).astype(f32)
+        for ch in order:
+            acc = acc + (w[None, :, None, None, ch] * h[:, None, :, :, ch]).astype(f32)
+        SM.check_equal(acc, pred, "f32 chain")
+    assert float(np.abs(pred).max()) < 2.0 ** 11
+    ref = SM.skill_sums(pred, y, 0, 0, slots, SX.NSLOTS, row_w, before)
+    mt, st = SM.skill_terms(pred, y, 0, 0, row_w)
+    _assert_order_free(mt, st, slots, before, ref, 32)
+
+
+def test_skill_head_pred_refuses_data_that_is_not_exact():
+    rng = np.random.default_rng(5)
+    h, w = rng.integers(-4, 5, (1, 2, 3, 8)).astype(f32), (rng.integers(-8, 9, (2, 8)) / 4.0).astype(f32)
+    SM.skill_head_pred(h, w, None)
+    with pytest.raises(ValueError):
+        SM.skill_head_pred(h + f32(0.1), w, None)
+    with pytest.raises(ValueError):
+        SM.skill_head_pred(h, w, np.array([0.3, 1.0], f32))
+
+
+def test_gamma_takes_the_unit_roundoff_of_the_format():
+    assert SM.gamma(3) == 3 * SM.U / (1 - 3 * SM.U) and SM.gamma(0, SM.U64) == 0.0
+    assert abs(SM.gamma(12959, SM.U64) - 1.4388e-12) < 1e-16      # the product crop's sample rows
+
+
+def test_skill_audit_passes_other_orders_and_has_teeth():
+    rng = np.random.default_rng(9)
+    N, O, H, W, oy, ox, Hc, Wc, S = 9, 2, 8, 11, 1, 2, 5, 7, 3
+    pred, y = rng.standard_normal((N, O, H, W)).astype(f32), rng.standard_normal((N, O, Hc, Wc)).astype(f32)
+    row_w = 0.25 + rng.random(Hc)
+    slot = [0, 1, -1, 0, 0, 1, 0, -1, 0]                           # slot 2: no sample
+    before = rng.standard_normal((S, 5, O, Hc, Wc))
+    before[0] = 0
+    ref = SM.skill_sums(pred, y, oy, ox, slot, S, row_w, before)
+    args = (pred, y, oy, ox, slot, S, row_w, before)
+    r = SM.skill_audit(*args, ref["pix"], ref["sample"])
+    assert 0.0 <= r[0] <= 1.0 and 0.0 <= r[1] <= 1.0
+    mt, st = SM.skill_terms(pred, y, oy, ox, row_w)
+    # another order: samples descending, the crop as a chain from the last pixel
+    pix = before.copy()
+    for n in reversed(range(N)):
+        if slot[n] >= 0:
+            pix[slot[n]] = pix[slot[n]] + mt[:, n]
+    rows = np.zeros((N, O, 8))
+    for v in st.reshape(8, N, O, -1).transpose(3, 1, 2, 0)[::-1]:
+        rows = rows + v
+    assert not np.array_equal(rows, ref["sample"])
+    SM.skill_audit(*args, pix, rows)
+
+    def moved(a, idx, by):
+        a = a.copy()
+        a[idx] += by
+        return a
+    cell = (0, 2, 1, 2, 3)                                         # sum of t^2 over the five samples of slot 0
+    assert ref["pix_n"][cell] == 5 and ref["pix_n"][(1,) + cell[1:]] == 3
+    fails(lambda: SM.skill_audit(*args, moved(ref["pix"], cell, 8 * np.spacing(ref["pix"][cell])), ref["sample"]))
+    fails(lambda: SM.skill_audit(*args, moved(ref["pix"], cell, mt[(2, 2) + cell[2:]]), ref["sample"]))      # the slot -1 sample
+    fails(lambda: SM.skill_audit(*args, moved(ref["pix"], cell, -mt[(2, 3) + cell[2:]]), ref["sample"]))     # sample 3 dropped
+    fails(lambda: SM.skill_audit(*args, moved(ref["pix"], (2,) + cell[1:], np.spacing(ref["pix"][(2,) + cell[1:]])), ref["sample"]))   # an idle slot touched
+    row = (4, 1, 3)
+    fails(lambda: SM.skill_audit(*args, ref["pix"], moved(ref["sample"], row, 64 * np.spacing(ref["sample"][row]))))
+    fails(lambda: SM.skill_audit(*args, ref["pix"], moved(ref["sample"], row, -st[3, 4, 1, 4, 6])))          # one pixel left out
+    fails(lambda: SM.skill_audit(*args, ref["pix"], moved(ref["sample"], (2, 0, 0), np.nan)))
