@@ -241,15 +241,8 @@ struct ConvArgs {
   int lo_Ch16, lo_dc_zero;
 };
 
-// In-step timing probe (nint_seq.probe): a one-thread launch that writes {tag, s_memrealtime} into the caller's buffer.
-// Bracketing a launch with two of them costs two ordinary kernel boundaries (no event / barrier packets, which measured
-// +8-10 us per bracketed launch); the back-to-back calibration pair at the start of each pass prices those boundaries.
-struct Probe {
-  unsigned long long* buf; int cap; int n; unsigned mask; hipStream_t st;
-  void stamp(unsigned kind, int layer, int t, int end);                    // no-op unless bit `kind` of mask is set (kind 0: always)
-};
-
-// internal entry points shared between translation units (not part of the C ABI)
+// internal entry points shared between translation units (not part of the C ABI).  Every launch of a sequence pass has a PLANNED
+// form: a pure function checks the arguments and fills the record (host arithmetic only), an enqueue function does nothing but launch
 // (planned, then enqueued: the first checks the arguments and fills *plan, the second launches lstm_bwd_pointwise_kernel)
 int nint_internal_pointwise_plan(const nint_layer* ly, const nint_geom* g, int dtype, int N, const void* gates,
                                  const float* c_prev, const float* c_new, const void* dh, float* dc, void* dG,
@@ -261,8 +254,46 @@ struct WgJob {           // one layer's weight / bias gradient
   float* dW; float* db;
   int h_skip;                                // leading images whose h source is identically zero
 };
-int nint_internal_conv_wgrad_multi(const WgJob* jobs, int njobs, const nint_geom* g, int dtype, float* partial,
-                                   size_t partial_bytes, int n_cu, void* stream, Probe* probe = nullptr);
+// wgrad.hip: the argument blocks of wgrad_kernel / wgrad_wide_kernel (WgradArgs) and of wgrad_reduce_kernel (ReduceTable)
+struct WgSrc {           // one source (x or h) of a launch
+  const char* dG;        // first image of this source's reduction (the h source may skip the zero-state time step)
+  const char* src; long src_img_stride; int src_pix_stride;
+  float* partial;
+  int CB, JG;            // channel blocks; columns per block slab (the x source's slabs carry the bias-gradient column)
+  int nblk;              // workgroup columns of this source: NB * CB * TG
+  int ntiles, tiles_per_split;
+  int want_db;           // 1: the slab's last column (JG-1) carries the bias gradient (column sums of dG; wgrad.hip)
+};
+struct WgradArgs {
+  long dG_img_stride; int dG_pix_stride;
+  WgSrc s[2];
+  int nparts;            // 1, or 2: BOTH sources in one launch (same kernel shape), their workgroups interleaved per gate block so
+                         // that the x and h workgroups of a pixel range run together and share the dG tiles in L2
+  int NTC, J;            // channel tiles per block, (tap, channel-tile) columns in all
+  int TG;                // column groups of 4*JW columns (49 taps of a 7x7 kernel: 2)
+  int k, p, taps;
+  int P, Wh;
+  int tiles_x, tiles_y;
+};
+struct ReduceEntry {
+  const float* part; float* dW;
+  int Cx, Ch, Ch16, k, NB, CB, NTC, J, splits, is_h, xfold;
+  int TG, JG;                               // column groups per block column, columns per block slab (incl. the db column)
+  float* db;                                // non-NULL: slab column JG-1 of (channel block 0, last group) is the bias gradient
+  int waves;                                // waves that share the splits of one 64-element line (the others exit)
+  unsigned blk_begin;                       // first workgroup of this (layer, source) in the merged launch
+};
+struct ReduceTable { ReduceEntry e[2 * NINT_MAX_LAYERS]; int n; };
+// The weight / bias gradients of jobs[0..n), planned: per job ONE launch (both sources merged) or two (x, then h) into consecutive
+// regions of `partial`, and one fold of every split-K slab of every job into its dW and db.
+struct WgLaunch { const void* kern; int gx, gy, block; size_t lds; WgradArgs a; };   // kern: host handle of the wgrad[_wide]_kernel<...> instantiation
+struct WgJobPlan { WgLaunch launch[2]; int n; };
+struct WgFoldPlan { ReduceTable t; unsigned grid; int block; };
+// pure: every check (job pointers, h_skip, shape, LDS, workspace room) is made here; nothing is enqueued
+int nint_internal_wgrad_plan(const WgJob* jobs, int njobs, const nint_geom* g, int dtype, float* partial, size_t partial_bytes,
+                             int n_cu, WgJobPlan* plans, WgFoldPlan* fold);
+int nint_internal_wgrad_enqueue(const WgJobPlan* plan, void* stream);
+int nint_internal_wgrad_fold_enqueue(const WgFoldPlan* fold, void* stream);
 // stencil.hip: the gate step of tiny hidden widths (Ch <= 8, 3x3) on the vector ALU.  Its weight image -- one row of 32 f32 per
 // (tap, channel) in the kernel's iteration order -- sits behind the MFMA images in the Wf buffer (nint_pack_weights).
 __host__ __device__ inline bool nint_stencil_shape(int Cx, int Ch, int k, int xfold) {

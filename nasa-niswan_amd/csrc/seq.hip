@@ -1,7 +1,8 @@
 // seq.hip -- library entry points that are not kernels themselves: version / device info,
-// the hardware self-test, and the whole-sequence drivers that enqueue every launch of a
-// ConvLSTM forward (model.py:253-274) or its BPTT from C++ on one HIP stream, so the Python
-// side pays one ctypes call per pass instead of one per kernel.
+// the hardware self-test, and the whole-sequence drivers that plan every launch of a
+// ConvLSTM forward (model.py:253-274) or of its backward pass -- the BPTT chain, then the layers'
+// weight-gradient reductions and their fold -- as one list of steps and enqueue it from C++ on
+// one HIP stream, so the Python side pays one ctypes call per pass instead of one per kernel.
 #include <string.h>
 #include <vector>
 #include "nint_common.h"
@@ -96,6 +97,13 @@ extern "C" int nint_selftest(float* out, void* stream) {
 // launches go out as ONE grid instead (nint_seq.wave; conv_lstm_multi_kernel and its kin).
 static inline size_t esize(int dtype) { return dtype == NINT_BF16 ? 2 : 4; }
 
+// In-step timing probe (nint_seq.probe): a one-thread launch that writes {tag, s_memrealtime} into the caller's buffer.
+// Bracketing a launch with two of them costs two ordinary kernel boundaries (no event / barrier packets, which measured
+// +8-10 us per bracketed launch); the back-to-back calibration pair at the start of each pass prices those boundaries.
+struct Probe {
+  unsigned long long* buf; int cap; int n; unsigned mask; hipStream_t st;
+  void stamp(unsigned kind, int layer, int t, int end);                    // no-op unless bit `kind` of mask is set (kind 0: always)
+};
 __global__ void probe_stamp_kernel(unsigned long long* slot, unsigned long long tag) {
   if (threadIdx.x == 0) { slot[0] = tag; slot[1] = __builtin_amdgcn_s_memrealtime(); }
 }
@@ -131,14 +139,15 @@ static int seq_check(const nint_seq* s) {
 
 // A pass is first PLANNED into an ordered list of steps -- host arithmetic only: nothing is enqueued, no stream is touched, no
 // buffer is read -- and then the list is enqueued (run_steps).  nint_debug_seq_plan shows the same list to tests and tools.
-enum { STEP_CONV, STEP_MULTI, STEP_PW, STEP_GATE };
+enum { STEP_CONV, STEP_MULTI, STEP_PW, STEP_GATE, STEP_WGRAD, STEP_FOLD };
 struct SeqProb { int op, layer, t; };              // one conv / pointwise problem (NINT_OP_*)
 struct GateCall { CellFwdJob job; nint_layer ly; int carrier; };
 struct SeqStep {
   int kind;        // a planned conv launch | a merged grid | a pointwise backward | a direct nint_cell_fwd call (stencil / dense-K: no planned form)
+                   // | one layer's weight-gradient reduction | the fold of a pass's reductions
   int probe, tag_layer, tag_t;       // the NINT_PROBE_* kind and tag it is bracketed with
-  int n; SeqProb prob[NINT_MULTI_MAX + 1];         // its problems, in grid order
-  union { ConvPlan conv; MultiPlan multi; PwArgs pw; GateCall gate; };
+  int n; SeqProb prob[NINT_MULTI_MAX + 1];         // its problems, in grid order (a reduction / the fold: none, n = 0)
+  union { ConvPlan conv; MultiPlan multi; PwArgs pw; GateCall gate; WgJobPlan wg; WgFoldPlan fold; };
 };
 typedef std::vector<SeqStep> Steps;
 
@@ -175,6 +184,8 @@ static int run_steps(const nint_seq* s, const Steps& steps, Probe& probe, void* 
       case STEP_PW: rc = nint_internal_pointwise_enqueue(&st.pw, s->dtype, stream); break;
       case STEP_GATE: rc = nint_cell_fwd(&st.gate.ly, &s->g, s->dtype, s->B, st.gate.job.x_slab, st.gate.job.h_prev, st.gate.job.c_prev,
                                          st.gate.job.h_out, st.gate.job.c_out, st.gate.job.gates_out, stream); break;
+      case STEP_WGRAD: rc = nint_internal_wgrad_enqueue(&st.wg, stream); break;
+      case STEP_FOLD: rc = nint_internal_wgrad_fold_enqueue(&st.fold, stream); break;
     }
     probe.stamp(st.probe, st.tag_layer, st.tag_t, 1);
     if (rc != NINT_OK) return rc;
@@ -409,8 +420,29 @@ struct BwdPlanner {
     return NINT_OK;
   }
 
+  // weight / bias gradients: ONE reduction over all T time steps per layer and source (bracketed with q, its index among the
+  // reductions of this call), all layers' folds merged
+  int wgrads() {
+    WgJob jobs[NINT_MAX_LAYERS];
+    for (int l = 0; l < L; ++l) {
+      const nint_layer* ly = &s->layer[l];
+      const char* x_all = (l == 0) ? (const char*)s->xs : (const char*)s->h[l - 1] + B * halo_px * ly->Cxp * es;  // h^{l-1}_t = slab t+1
+      // h_{-1} = 0 for a sequence from the zero state: the h part of the reduction skips time step 0
+      jobs[l] = WgJob{ly, T * (int)B, s->dG[l], x_all, s->h[l] /* h_{t-1} = slab t */, s->dW[l], s->db[l], s->has_init_state ? 0 : (int)B};
+    }
+    // (bwd_parts: layers >= 1 in the first call, layer 0 in the second; each call folds what it reduced)
+    const int j0 = s->bwd_parts == 1 ? 1 : 0, j1 = s->bwd_parts == 2 ? 1 : L;
+    if (j1 <= j0) return NINT_OK;
+    WgJobPlan jp[NINT_MAX_LAYERS]; WgFoldPlan fold;
+    const int rc = nint_internal_wgrad_plan(jobs + j0, j1 - j0, &s->g, s->dtype, s->wg_partial, s->wg_partial_bytes, s->n_cu, jp, &fold);
+    if (rc != NINT_OK) return rc;
+    for (int q = 0; q < j1 - j0; ++q) push(out, STEP_WGRAD, NINT_PROBE_WGRAD, q, 0).wg = jp[q];
+    push(out, STEP_FOLD, NINT_PROBE_FOLD, 0, 0).fold = fold;
+    return NINT_OK;
+  }
+
   int plan() {
-    out.reserve((size_t)(T + L) * L * 2);
+    out.reserve((size_t)(T + L) * L * 2 + L + 1);
     for (int so = T - 1; so >= -off[0] && s->bwd_parts != 2; --so) {      // (part 2: the chain ran in the part-1 call)
       for (int l = L - 1; l >= 0; --l) {
         const int u = so + off[l];
@@ -429,7 +461,7 @@ struct BwdPlanner {
       }
     }
     flush_p(); flush_d();
-    return NINT_OK;
+    return wgrads();
   }
 };
 
@@ -451,25 +483,10 @@ extern "C" int nint_seq_fwd(const nint_seq* s, void* stream) {
 
 extern "C" int nint_seq_bwd(const nint_seq* s, void* stream) {
   Steps steps;
-  int rc = plan_pass(s, true, steps);
+  const int rc = plan_pass(s, true, steps);
   if (rc != NINT_OK) return rc;
   Probe probe = make_probe(s, true, stream);
-  rc = run_steps(s, steps, probe, stream);
-  if (rc != NINT_OK) return rc;
-  // weight / bias gradients: ONE reduction over all T time steps per layer and source, all layers' folds merged
-  const nint_geom* g = &s->g; const int B = s->B, L = s->L;
-  WgJob jobs[NINT_MAX_LAYERS];
-  for (int l = 0; l < L; ++l) {
-    const nint_layer* ly = &s->layer[l];
-    const char* x_all = (l == 0) ? (const char*)s->xs : (const char*)s->h[l - 1] + (size_t)B * g->Hh * g->Wh * ly->Cxp * esize(s->dtype);  // h^{l-1}_t = slab t+1
-    // h_{-1} = 0 for a sequence from the zero state: the h part of the reduction skips time step 0
-    jobs[l] = WgJob{ly, s->T * B, s->dG[l], x_all, s->h[l] /* h_{t-1} = slab t */, s->dW[l], s->db[l], s->has_init_state ? 0 : B};
-  }
-  // (bwd_parts: layers >= 1 in the first call, layer 0 in the second; each call folds what it reduced)
-  const int j0 = s->bwd_parts == 1 ? 1 : 0, j1 = s->bwd_parts == 2 ? 1 : L;
-  if (j1 <= j0) return NINT_OK;
-  return nint_internal_conv_wgrad_multi(jobs + j0, j1 - j0, g, s->dtype, s->wg_partial, s->wg_partial_bytes, s->n_cu, stream,
-                                        probe.buf ? &probe : nullptr);
+  return run_steps(s, steps, probe, stream);
 }
 
 // ------------------------------------------------------------------------------ the plan, for tests and tools

@@ -23,27 +23,6 @@
 #include <type_traits>
 #include "nint_common.h"
 
-struct WgSrc {           // one source (x or h) of a launch
-  const char* dG;        // first image of this source's reduction (the h source may skip the zero-state time step)
-  const char* src; long src_img_stride; int src_pix_stride;
-  float* partial;
-  int CB, JG;            // channel blocks; columns per block slab (the x source's slabs carry the bias-gradient column)
-  int nblk;              // workgroup columns of this source: NB * CB * TG
-  int ntiles, tiles_per_split;
-  int want_db;           // 1: the slab's last column (JG-1) carries the bias gradient (column sums of dG), see below
-};
-struct WgradArgs {
-  long dG_img_stride; int dG_pix_stride;
-  WgSrc s[2];
-  int nparts;            // 1, or 2: BOTH sources in one launch (same kernel shape), their workgroups interleaved per gate block so
-                         // that the x and h workgroups of a pixel range run together and share the dG tiles in L2
-  int NTC, J;            // channel tiles per block, (tap, channel-tile) columns in all
-  int TG;                // column groups of 4*JW columns (49 taps of a 7x7 kernel: 2)
-  int k, p, taps;
-  int P, Wh;
-  int tiles_x, tiles_y;
-};
-
 template <int DT> struct WgTile;
 template <> struct WgTile<NINT_BF16> { static constexpr int PR = 4, RA = 160; static constexpr int rb(int ntc) { return ntc == 1 ? 32 : 96; } };
 template <> struct WgTile<NINT_F32> { static constexpr int PR = 2, RA = 320; static constexpr int rb(int ntc) { return ntc == 1 ? 64 : 192; } };
@@ -562,16 +541,6 @@ __global__ __launch_bounds__(512, 2) void wgrad_wide_kernel(WgradArgs a) {
 // elements of the slab layout [block][j][n'loc 64][c 16] (one 256-byte line per split, fully coalesced) and
 // spreads the splits over its blockDim/64 waves; the per-wave sums are folded through LDS.  The order is a
 // fixed function of the launch shape (bitwise reproducible); only the single write per weight is scattered.
-struct ReduceEntry {
-  const float* part; float* dW;
-  int Cx, Ch, Ch16, k, NB, CB, NTC, J, splits, is_h, xfold;
-  int TG, JG;                               // column groups per block column, columns per block slab (incl. the db column)
-  float* db;                                // non-NULL: slab column JG-1 of (channel block 0, last group) is the bias gradient
-  int waves;                                // waves that share the splits of one 64-element line (the others exit)
-  unsigned blk_begin;                       // first workgroup of this (layer, source) in the merged launch
-};
-struct ReduceTable { ReduceEntry e[2 * NINT_MAX_LAYERS]; int n; };
-
 __global__ void wgrad_reduce_kernel(ReduceTable t) {
   __shared__ f32x4_t red[1024];
   int ei = 0;
@@ -702,9 +671,6 @@ static int wg_plan(const nint_layer* ly, int dtype, int n_cu, int N, const nint_
     // accumulator flush (J KiB-tiles per workgroup) must stay small against the K work.  (32 until round 3; at B = 1-2
     // per GPU that left the narrow layers' launches at 92-276 workgroups: 8 measured +2.9 % on the B = 1 step, +0.9 % at
     // B = 2, nothing at B >= 4 where the workgroup cap binds first; 4 and 2 equal 8.)
-#ifndef NINT_WG_MIN_TILES
-#define NINT_WG_MIN_TILES 8
-#endif
     int s = nint_cdiv(2 * n_cu, pl->NB * w.CB * w.TG);
     if (s > pl->ntiles / NINT_WG_MIN_TILES) s = pl->ntiles / NINT_WG_MIN_TILES;
     if (s < 1) s = 1;
@@ -742,8 +708,9 @@ extern "C" size_t nint_wgrad_workspace_bytes(const nint_layer* ly, int dtype, in
   return pl.total_floats * sizeof(float);
 }
 
+// A launch is PLANNED the way launch_cfg (conv_igemm.hip) plans a conv launch: fill the record, or return the error
 template <int DT, int JW, int KS, int NTCT, int KX>
-static int launch_wgrad(WgradArgs& a, int splits, int nblk, hipStream_t st) {
+static int launch_wgrad(const WgradArgs& a, int splits, int nblk, WgLaunch* out) {
   typedef WgTile<DT> TT;
   const int p = a.p;
   const int a_bytes = TT::PR * 32 * TT::RA;
@@ -751,61 +718,54 @@ static int launch_wgrad(WgradArgs& a, int splits, int nblk, hipStream_t st) {
   const size_t lds = 2 * (size_t)(a_bytes + b_bytes);
   if (lds > 160 * 1024) return NINT_E_LDS;
   if (a.k != KS || a.NTC != NTCT || a.J != KS * KX * NTCT) return NINT_E_ARG;
-  auto kern = wgrad_kernel<DT, JW, 1, KS, NTCT, KX>;
-  if (lds > 64 * 1024)
-    NINT_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(kern, dim3(splits, nblk), dim3(256), lds, st, a);
-  NINT_LAUNCH_CHECK();
+  *out = WgLaunch{(const void*)wgrad_kernel<DT, JW, 1, KS, NTCT, KX>, splits, nblk, 256, lds, a};
   return NINT_OK;
 }
 
 template <int KS, int NCT>
-static int launch_wgrad_wide(WgradArgs& a, int splits, int cols, hipStream_t st) {
-  typedef WgWide<KS, NCT> G;
-  const size_t lds = 2 * (size_t)G::buf_bytes;
+static int launch_wgrad_wide(const WgradArgs& a, int splits, int cols, WgLaunch* out) {
+  const size_t lds = 2 * (size_t)WgWide<KS, NCT>::buf_bytes;
   if (lds > 160 * 1024) return NINT_E_LDS;
-  auto kern = wgrad_wide_kernel<KS, NCT>;
-  NINT_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(kern, dim3(splits, cols), dim3(512), lds, st, a);
-  NINT_LAUNCH_CHECK();
+  *out = WgLaunch{(const void*)wgrad_wide_kernel<KS, NCT>, splits, cols, 512, lds, a};
   return NINT_OK;
 }
 
 // instantiated (kernel size, channel tiles, columns per wave, horizontal taps) combinations
 template <int DT>
-static int dispatch_wgrad(WgradArgs& a, const WgPart& w, int nblk, hipStream_t st) {
+static int dispatch_wgrad(const WgradArgs& a, const WgPart& w, int nblk, WgLaunch* out) {
   const int key = a.k * 1000 + w.NTC * 100 + w.JW * 10 + w.KX;
   switch (key) {
-    case 5 * 1000 + 1 * 100 + 7 * 10 + 5: return launch_wgrad<DT, 7, 5, 1, 5>(a, w.splits, nblk, st);
-    case 3 * 1000 + 2 * 100 + 5 * 10 + 3: return launch_wgrad<DT, 5, 3, 2, 3>(a, w.splits, nblk, st);
-    case 3 * 1000 + 1 * 100 + 5 * 10 + 3: return launch_wgrad<DT, 5, 3, 1, 3>(a, w.splits, nblk, st);
-    case 1 * 1000 + 2 * 100 + 5 * 10 + 1: return launch_wgrad<DT, 5, 1, 2, 1>(a, w.splits, nblk, st);
-    case 1 * 1000 + 1 * 100 + 5 * 10 + 1: return launch_wgrad<DT, 5, 1, 1, 1>(a, w.splits, nblk, st);
+    case 5 * 1000 + 1 * 100 + 7 * 10 + 5: return launch_wgrad<DT, 7, 5, 1, 5>(a, w.splits, nblk, out);
+    case 3 * 1000 + 2 * 100 + 5 * 10 + 3: return launch_wgrad<DT, 5, 3, 2, 3>(a, w.splits, nblk, out);
+    case 3 * 1000 + 1 * 100 + 5 * 10 + 3: return launch_wgrad<DT, 5, 3, 1, 3>(a, w.splits, nblk, out);
+    case 1 * 1000 + 2 * 100 + 5 * 10 + 1: return launch_wgrad<DT, 5, 1, 2, 1>(a, w.splits, nblk, out);
+    case 1 * 1000 + 1 * 100 + 5 * 10 + 1: return launch_wgrad<DT, 5, 1, 1, 1>(a, w.splits, nblk, out);
     // horizontally folded x source (thin first-layer inputs)
-    case 5 * 1000 + 2 * 100 + 5 * 10 + 1: return launch_wgrad<DT, 5, 5, 2, 1>(a, w.splits, nblk, st);
-    case 5 * 1000 + 1 * 100 + 5 * 10 + 1: return launch_wgrad<DT, 5, 5, 1, 1>(a, w.splits, nblk, st);
-    case 3 * 1000 + 2 * 100 + 5 * 10 + 1: return launch_wgrad<DT, 5, 3, 2, 1>(a, w.splits, nblk, st);
-    case 3 * 1000 + 1 * 100 + 5 * 10 + 1: return launch_wgrad<DT, 5, 3, 1, 1>(a, w.splits, nblk, st);
+    case 5 * 1000 + 2 * 100 + 5 * 10 + 1: return launch_wgrad<DT, 5, 5, 2, 1>(a, w.splits, nblk, out);
+    case 5 * 1000 + 1 * 100 + 5 * 10 + 1: return launch_wgrad<DT, 5, 5, 1, 1>(a, w.splits, nblk, out);
+    case 3 * 1000 + 2 * 100 + 5 * 10 + 1: return launch_wgrad<DT, 5, 3, 2, 1>(a, w.splits, nblk, out);
+    case 3 * 1000 + 1 * 100 + 5 * 10 + 1: return launch_wgrad<DT, 5, 3, 1, 1>(a, w.splits, nblk, out);
     // 7x7 kernels: 49 taps in two column groups; folded thin inputs 7 or 14 columns
-    case 7 * 1000 + 1 * 100 + 7 * 10 + 7: return launch_wgrad<DT, 7, 7, 1, 7>(a, w.splits, nblk, st);
-    case 7 * 1000 + 2 * 100 + 5 * 10 + 1: return launch_wgrad<DT, 5, 7, 2, 1>(a, w.splits, nblk, st);
-    case 7 * 1000 + 1 * 100 + 5 * 10 + 1: return launch_wgrad<DT, 5, 7, 1, 1>(a, w.splits, nblk, st);
+    case 7 * 1000 + 1 * 100 + 7 * 10 + 7: return launch_wgrad<DT, 7, 7, 1, 7>(a, w.splits, nblk, out);
+    case 7 * 1000 + 2 * 100 + 5 * 10 + 1: return launch_wgrad<DT, 5, 7, 2, 1>(a, w.splits, nblk, out);
+    case 7 * 1000 + 1 * 100 + 5 * 10 + 1: return launch_wgrad<DT, 5, 7, 1, 1>(a, w.splits, nblk, out);
     default: return NINT_E_SHAPE;
   }
 }
 
 // Weight / bias gradients of several layers ("jobs") in one go: two MFMA launches per layer (x and h source) into
 // consecutive regions of ONE workspace, then ONE launch folds every split-K slab of every layer into its dW and db
-// (the x part's slabs carry the bias-gradient column).
+// (the x part's slabs carry the bias-gradient column).  Planned here into plans[0..njobs) and *fold -- host arithmetic only --
+// and enqueued from those records (below; seq.hip: the last steps of a backward pass).
 // h_skip: the first h_skip images have an identically zero h source (h_{-1} = 0 of a sequence that starts from
 // the zero state, model.py:259-262): the h part skips them -- 1/T of its work.
-int nint_internal_conv_wgrad_multi(const WgJob* jobs, int njobs, const nint_geom* g, int dtype, float* partial,
-                                   size_t partial_bytes, int n_cu, void* stream, Probe* probe) {
+int nint_internal_wgrad_plan(const WgJob* jobs, int njobs, const nint_geom* g, int dtype, float* partial, size_t partial_bytes,
+                             int n_cu, WgJobPlan* plans, WgFoldPlan* fold) {
   if (!jobs || njobs < 1 || njobs > NINT_MAX_LAYERS || !g || !partial) return NINT_E_ARG;
   if (dtype != NINT_F32 && dtype != NINT_BF16) return NINT_E_ARG;
   const int es = dtype == NINT_BF16 ? 2 : 4;
-  hipStream_t st = (hipStream_t)stream;
-  ReduceTable rt = {};
+  ReduceTable& rt = fold->t;
+  rt = ReduceTable{};
   size_t off = 0;
   unsigned blk = 0;
   int red_threads = 256;
@@ -827,7 +787,8 @@ int nint_internal_conv_wgrad_multi(const WgJob* jobs, int njobs, const nint_geom
     a.k = ly->k; a.p = ly->k / 2;
     a.P = g->P; a.Wh = g->Wh;
     a.tiles_x = pl.tiles_x; a.tiles_y = pl.tiles_y;
-    if (probe) probe->stamp(NINT_PROBE_WGRAD, q, 0, 0);
+    WgJobPlan& jp = plans[q];
+    jp.n = 0;
     for (int part = 0; part < 2; ++part) {
       const WgPart& w = pl.part[part];
       WgSrc& S = a.s[pl.merged ? part : 0];
@@ -847,13 +808,15 @@ int nint_internal_conv_wgrad_multi(const WgJob* jobs, int njobs, const nint_geom
       a.taps = ly->k * w.KX;
       if (w.wide_nct) {                        // the 8-wave 128-column kernel, one launch per source
         a.nparts = 1;
-        rc = ly->k == 3 ? launch_wgrad_wide<3, 4>(a, w.splits, w.wcols, st)
-           : (ly->k == 5 ? launch_wgrad_wide<5, 2>(a, w.splits, w.wcols, st) : launch_wgrad_wide<7, 1>(a, w.splits, w.wcols, st));
+        WgLaunch* out = &jp.launch[jp.n++];
+        rc = ly->k == 3 ? launch_wgrad_wide<3, 4>(a, w.splits, w.wcols, out)
+           : (ly->k == 5 ? launch_wgrad_wide<5, 2>(a, w.splits, w.wcols, out) : launch_wgrad_wide<7, 1>(a, w.splits, w.wcols, out));
         if (rc != NINT_OK) return rc;
       } else if (!pl.merged || part == 1) {    // separate launches per source, or both sources in one
         a.nparts = pl.merged ? 2 : 1;
         const int nblk = pl.merged ? a.s[0].nblk + a.s[1].nblk : S.nblk;
-        rc = dtype == NINT_BF16 ? dispatch_wgrad<NINT_BF16>(a, w, nblk, st) : dispatch_wgrad<NINT_F32>(a, w, nblk, st);
+        WgLaunch* out = &jp.launch[jp.n++];
+        rc = dtype == NINT_BF16 ? dispatch_wgrad<NINT_BF16>(a, w, nblk, out) : dispatch_wgrad<NINT_F32>(a, w, nblk, out);
         if (rc != NINT_OK) return rc;
       }
       ReduceEntry& E = rt.e[rt.n++];
@@ -866,12 +829,26 @@ int nint_internal_conv_wgrad_multi(const WgJob* jobs, int njobs, const nint_geom
                                                  // many-split entries made every entry's workgroup 1024 threads: 46 -> 40 us)
       if (E.waves * 64 > red_threads) red_threads = E.waves * 64;
     }
-    if (probe) probe->stamp(NINT_PROBE_WGRAD, q, 0, 1);
   }
-  if (probe) probe->stamp(NINT_PROBE_FOLD, 0, 0, 0);
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(blk), dim3(red_threads), 0, st, rt);
+  fold->grid = blk; fold->block = red_threads;
+  return NINT_OK;
+}
+
+int nint_internal_wgrad_enqueue(const WgJobPlan* jp, void* stream) {
+  for (int i = 0; i < jp->n; ++i) {
+    const WgLaunch& l = jp->launch[i];
+    if (l.lds > 64 * 1024)
+      NINT_CHECK_HIP(hipFuncSetAttribute(l.kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l.lds));
+    void* args[] = {(void*)&l.a};
+    (void)hipLaunchKernel(l.kern, dim3(l.gx, l.gy), dim3(l.block), args, l.lds, (hipStream_t)stream);
+    NINT_LAUNCH_CHECK();
+  }
+  return NINT_OK;
+}
+
+int nint_internal_wgrad_fold_enqueue(const WgFoldPlan* fp, void* stream) {
+  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(fp->grid), dim3(fp->block), 0, (hipStream_t)stream, fp->t);
   NINT_LAUNCH_CHECK();
-  if (probe) probe->stamp(NINT_PROBE_FOLD, 0, 0, 1);
   return NINT_OK;
 }
 
@@ -879,5 +856,8 @@ extern "C" int nint_conv_wgrad(const nint_layer* ly, const nint_geom* g, int dty
                                const void* x_slab, const void* h_slab, float* dW, float* db, float* partial,
                                size_t partial_bytes, int n_cu, void* stream) {
   const WgJob jb = {ly, N, dG, x_slab, h_slab, dW, db, 0};
-  return nint_internal_conv_wgrad_multi(&jb, 1, g, dtype, partial, partial_bytes, n_cu, stream);
+  WgJobPlan jp; WgFoldPlan fold;
+  int rc = nint_internal_wgrad_plan(&jb, 1, g, dtype, partial, partial_bytes, n_cu, &jp, &fold);
+  if (rc == NINT_OK) rc = nint_internal_wgrad_enqueue(&jp, stream);
+  return rc != NINT_OK ? rc : nint_internal_wgrad_fold_enqueue(&fold, stream);
 }

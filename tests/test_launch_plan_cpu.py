@@ -262,3 +262,27 @@ def test_ledger_equals_the_library_planner(name, case):
     for (pass_, idx), ps in groups.items():
         merged = ps[0].kernel not in ("conv_igemm", "stencil", "tiny", "pointwise")
         assert (len(ps) > 1) == merged and len({p.kernel for p in ps}) == 1, (pass_, idx, ps)
+
+
+def test_backward_plan_checks_the_weight_gradient_workspace():
+    """The weight-gradient reductions are steps of the planned backward pass: a split-K workspace too small for them is refused
+    by the planner (NINT_E_ARG from nint_debug_seq_plan(bwd = 1) and, before anything is enqueued, from nint_seq_bwd), the
+    forward plan does not look at it, and the engine's own sizing -- nint_wgrad_workspace_bytes of every layer, each rounded
+    up to 256 bytes -- plans what 1 GiB plans.  (wave = 4 also parks layer 0's d/dh there, B * H * W * Chp elements: where
+    the engine's sizing has no room for it the dgrad pair falls away, so the comparison then runs at wave = 2, which reads
+    no such room.)"""
+    from nasa_niswan_amd import _lib
+    lib = _lib.load()
+    s = _seq_of(C_=BENCH["C"], **{k: v for k, v in BENCH.items() if k != "C"}, B=2, dtype="bf16")
+    sized = sum((lib.nint_wgrad_workspace_bytes(C.byref(s.layer[l]), s.dtype, s.n_cu) + 255) // 256 * 256 for l in range(s.L))
+    assert 0 < sized < s.wg_partial_bytes
+    if sized < s.B * BENCH["H"] * BENCH["W"] * s.layer[0].Chp * 2:
+        s.wave = 2
+    want = _library_plan(s, True)
+    assert any(g.pass_ == "bwd" for _, g in want)
+    s.wg_partial_bytes = sized
+    assert _library_plan(s, True) == want
+    s.wg_partial_bytes = 0
+    recs = (_lib.NintLaunchRec * len(want))()
+    assert lib.nint_debug_seq_plan(C.byref(s), 1, recs, len(want)) == _lib.NINT_E_ARG
+    assert _library_plan(s, False) == [x for x in want if x[1].pass_ == "fwd"]
