@@ -61,6 +61,7 @@ class Workspace:
         self.key = (B, T, H, W, train, has_init)
         self.B, self.T, self.H, self.W, self.train = B, T, H, W, train
         self.in_use = False
+        self.gen = 0            # bumped by every SeqEngine.acquire: an autograd graph stamps it and refuses a backward after a reuse
         dev, es, kc = eng.device, eng.es, eng.kc
         lib = _lib.load()
         self.g = NintGeom()
@@ -222,6 +223,7 @@ class SeqEngine:
         for ws in self.pool.setdefault(key, []):
             if not ws.in_use:
                 ws.in_use = True
+                ws.gen += 1
                 ws.seq.probe, ws.seq.probe_mask, ws.seq.probe_slots = None, 0, 0     # (a trainer's timing probes do not outlive its step)
                 return ws
         ws = Workspace(self, B, T, H, W, train, has_init)
@@ -229,6 +231,7 @@ class SeqEngine:
             ws.seq.layer[l] = ly
         self.pool[key].append(ws)
         ws.in_use = True
+        ws.gen += 1
         return ws
 
     @staticmethod

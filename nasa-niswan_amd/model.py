@@ -15,11 +15,13 @@ Extensions are keyword-only with reference-preserving defaults (SURVEY.md sectio
 """
 from __future__ import annotations
 
+import functools
 import weakref
 from typing import List, Optional, Sequence
 
 import torch
 import torch.nn as nn
+from torch._C import _functions
 
 from .engine import LayerCfg, SeqEngine, dtype_code
 
@@ -43,6 +45,38 @@ class _Releaser:
         self._fin()
 
 
+def _once_differentiable(fn):
+    """torch's ``once_differentiable`` with one difference.  The backward kernels run outside autograd, so under
+    ``create_graph=True`` the gradients they return carry no graph; torch's decorator hangs its error node on them only when a
+    COTANGENT requires grad, and the cotangent of ``(net(x) * r).sum()`` does not -- a gradient penalty built on dx would
+    then contribute nothing and nothing would say so.  Here every returned gradient gets the error node whenever a graph is
+    being recorded: double backward is refused, never dropped."""
+
+    @functools.wraps(fn)
+    def wrapper(ctx, *args):
+        with torch.no_grad():
+            outputs = fn(ctx, *args)
+        if not torch.is_grad_enabled():
+            return outputs
+        err = _functions.DelayedError(
+            "trying to differentiate twice through ConvLSTM / ConvLSTMCell: double backward is not supported -- the backward "
+            "pass runs HIP kernels outside autograd, so a gradient taken with create_graph=True is a constant", len(outputs))
+        return err(*[None if v is None else v.detach().requires_grad_(True) for v in outputs])
+
+    return wrapper
+
+
+def _own_workspace(ctx, who: str):
+    """The workspace a graph recorded into is its own only until its backward (or death) returns it to the pool: a forward
+    that acquired it since has overwritten the activations.  Refuse instead of running BPTT over another batch's."""
+    if ctx.ws.gen != ctx.gen:
+        raise RuntimeError(f"{who}: this graph was retained (retain_graph=True) across another forward of the same shape, which "
+                           "reused its workspace after the first backward() released it -- the stored activations are gone. "
+                           "Run every backward of a retained graph before the next forward of that shape, or run the forward "
+                           "again.")
+    return ctx.eng, ctx.ws
+
+
 # ------------------------------------------------------------------------------ autograd glue
 class _ConvLSTMFn(torch.autograd.Function):
     """x, head_w, head_b, W_0, b_0, ..., W_{L-1}, b_{L-1} -> pred [, seq]"""
@@ -64,8 +98,10 @@ class _ConvLSTMFn(torch.autograd.Function):
         if train:
             if module.return_sequence:
                 ctx.set_materialize_grads(False)                        # an unused output's cotangent stays None: passed as NULL
-            ctx.eng, ctx.ws, ctx.rel = eng, ws, _Releaser(ws)
-            ctx.save_for_backward(head_w)
+            ctx.eng, ctx.ws, ctx.rel, ctx.gen = eng, ws, _Releaser(ws), ws.gen
+            # references, not copies: the dgrad reads the engine's packed image of these weights (eng.Wd), which every forward
+            # rewrites -- torch's version check on the saved tensors is what refuses a backward after an in-place update
+            ctx.save_for_backward(head_w, *wb[0::2])
             ctx.x_needs_grad = ctx.needs_input_grad[2]
             ctx.nwb = len(wb)
         else:
@@ -73,9 +109,10 @@ class _ConvLSTMFn(torch.autograd.Function):
         return tuple(outs) if len(outs) > 1 else pred
 
     @staticmethod
+    @_once_differentiable
     def backward(ctx, dpred, dseq=None):
-        eng, ws = ctx.eng, ctx.ws
-        (head_w,) = ctx.saved_tensors
+        eng, ws = _own_workspace(ctx, "ConvLSTM")
+        head_w = ctx.saved_tensors[0]           # before the first launch: raises if a weight was modified in place
         L = len(eng.cfgs)
         if ctx.return_sequence:
             if dpred is None and dseq is None:
@@ -107,7 +144,8 @@ class _CellFn(torch.autograd.Function):
         eng.forward(ws, x.unsqueeze(1), [h], [c])
         h1, c1 = eng.h_last(ws, 0), eng.c_last(ws, 0)
         if train:
-            ctx.eng, ctx.ws, ctx.rel = eng, ws, _Releaser(ws)
+            ctx.eng, ctx.ws, ctx.rel, ctx.gen = eng, ws, _Releaser(ws), ws.gen
+            ctx.save_for_backward(W)            # (a reference: see _ConvLSTMFn)
             ctx.x_needs_grad = ctx.needs_input_grad[2]
             ctx.has_bias = b is not None
         else:
@@ -115,8 +153,10 @@ class _CellFn(torch.autograd.Function):
         return h1, c1
 
     @staticmethod
+    @_once_differentiable
     def backward(ctx, dh1, dc1):
-        eng, ws = ctx.eng, ctx.ws
+        eng, ws = _own_workspace(ctx, "ConvLSTMCell")
+        ctx.saved_tensors                       # before the first launch: raises if the weight was modified in place
         eng.set_state_grads(ws, 0, dh1, dc1)
         dWs, dbs, dx = eng.backward(ws, ctx.x_needs_grad)
         dh0, dc0 = eng.state_grads(ws, 0)
