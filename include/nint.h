@@ -200,6 +200,10 @@ int nint_unpack_halo(const void* src, float* dst, int n0, int N, int C, int Cp, 
 /* (N,C,H,W) f32 <-> compact f32 slab [N][H][W][Cp] */
 int nint_pack_compact(const float* src, void* dst, int N, int C, int Cp, int H, int W, int dtype, void* stream);   /* dtype: element type of the compact slab */
 int nint_unpack_compact(const void* src, float* dst, int N, int C, int Cp, int H, int W, int dtype, void* stream);
+/* compact slab += (N,C,H,W) f32: a cotangent that arrives as a tensor joins a gradient already in slab form (the returned final
+ * hidden state's cotangent on top of the head's dL/dh_{T-1} in nint_seq.dh[L-1] / the last block of nint_seq.dh_seq).  The
+ * channel padding is not touched. */
+int nint_pack_compact_add(const float* src, void* dst, int N, int C, int Cp, int H, int W, int dtype, void* stream);
 
 /* ---- weights ----------------------------------------------------------------------------- */
 /* 1 when horizontally folding the x source of a (first) layer lowers its number of K-steps:
@@ -519,6 +523,21 @@ int nint_preproc_fuse_pad_static_slab(const float* const* srcs /*host*/, const i
                                       const float* mean, const float* std, const int* t0 /*host*/, int B, void* xs_slab,
                                       int Cxp, int xfold_k, int T, int H, int W, const nint_geom* g /*host*/, int mode,
                                       int dtype, void* stream);
+
+/* ---- recurrent state hand-off -------------------------------------------------------------- */
+/* (h, c) of every layer from one state block to another, in slab form, in ONE launch.  A state block of
+ * layer l is B images of the ET halo slab [Hh][Wh][Chp[l]] (h) and B images of the f32 compact slab [H][W][Chp[l]] (c):
+ * slot T of nint_seq.h[l] / .c[l] after a forward pass, slot 0 of a has_init_state workspace, or a stand-alone buffer.
+ * h_dst[l] / c_dst[l] / h_src[l] / c_src[l]: host arrays of L device pointers to the first image of each block.
+ * Destination sample b receives source sample lane[b]; lane[b] = -1 gives it the zero state (this lane starts a new record);
+ * lane = NULL is the identity and needs B_dst == B_src.  Halo-slab images are copied whole: the source's halo and slack are
+ * zero by the slab invariant, so the destination's are zero afterwards; a reset image is written as zeros, halo included.
+ * B_dst above NINT_PRE_MAX_B is split internally.  Before any launch: NINT_E_ARG for a NULL table or pointer, L outside
+ * 1..NINT_MAX_LAYERS, a Chp[l] that is no multiple of nint_kc(dtype), a lane value outside [-1, B_src), or source and
+ * destination blocks of a layer that overlap; NINT_E_ALIGN for a pointer that is not 16-byte aligned. */
+int nint_state_copy(void* const* h_dst /*host*/, float* const* c_dst /*host*/, const void* const* h_src /*host*/,
+                    const float* const* c_src /*host*/, const int32_t* Chp /*host, L*/, int L, int B_dst, int B_src,
+                    const int32_t* lane /*host, B_dst entries, or NULL*/, const nint_geom* g /*host*/, int dtype, void* stream);
 
 #ifdef __cplusplus
 }

@@ -68,6 +68,9 @@ SIGNATURES = {
     "nint_unpack_halo": (_I, [vp, vp, _I, _I, _I, _I, _PG, _I, vp]),
     "nint_pack_compact": (_I, [vp, vp, _I, _I, _I, _I, _I, _I, vp]),
     "nint_unpack_compact": (_I, [vp, vp, _I, _I, _I, _I, _I, _I, vp]),
+    "nint_pack_compact_add": (_I, [vp, vp, _I, _I, _I, _I, _I, _I, vp]),
+    "nint_state_copy": (_I, [C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int32), _I, _I, _I,
+                             C.POINTER(C.c_int32), _PG, _I, vp]),
     "nint_packed_weight_bytes": (_SZ, [_I, _I, _I, _I, _I]),
     "nint_xfold_pays": (_I, [_I, _I, _I]),
     "nint_pack_weights": (_I, [vp, vp, vp, vp, vp, _I, _I, _I, _I, _I, vp]),

@@ -281,6 +281,107 @@ extern "C" int nint_unpack_compact(const void* src, float* dst, int N, int C, in
   return NINT_OK;
 }
 
+// dst += src: a cotangent that arrives as an (N,C,H,W) f32 tensor joins a gradient already in slab form (the final hidden
+// state's cotangent on top of the head's dL/dh_{T-1}).  Channel padding is left as it is.
+template <int DT>
+__global__ void pack_compact_add_kernel(const float* __restrict__ src, void* __restrict__ dst, int N, int C, int Cp,
+                                        int H, int W) {
+  const size_t total = (size_t)N * H * W * Cp;
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int c = i % Cp;
+    size_t r = i / Cp;
+    const int x = r % W; r /= W;
+    const int y = r % H;
+    const int n = r / H;
+    if (c < C) store_elem<DT>(dst, i, load_elem<DT>(dst, i) + src[(((size_t)n * C + c) * H + y) * W + x]);
+  }
+}
+
+extern "C" int nint_pack_compact_add(const float* src, void* dst, int N, int C, int Cp, int H, int W, int dtype, void* stream) {
+  if (!src || !dst || N <= 0 || C <= 0 || Cp < C || H <= 0 || W <= 0 || (dtype != NINT_F32 && dtype != NINT_BF16)) return NINT_E_ARG;
+  nint_by_dtype(dtype, [&](auto dt) {
+    hipLaunchKernelGGL(pack_compact_add_kernel<decltype(dt)::value>, grid1d((size_t)N * H * W * Cp), dim3(256), 0, (hipStream_t)stream, src, dst, N, C, Cp, H, W);
+  });
+  NINT_LAUNCH_CHECK();
+  return NINT_OK;
+}
+
+// ------------------------------------------------------------------------------ recurrent state hand-off
+// (h, c) of every layer from one place to another IN SLAB FORM: slot T of a workspace's stacks -> a stand-alone state, a state
+// -> slot 0 of a workspace, a state -> a state through a lane map.  Region r = 2l is layer l's h (ET halo slab images), r = 2l + 1
+// its c (f32 compact images); an image is a whole number of 64-byte rows in both layouts, so every region moves as 16-byte
+// vectors, and halo-slab images move WHOLE: the source's halo and slack are zero (the slab invariant), so the destination's are
+// zero afterwards without a separate fill.  Destination sample b takes source sample lane[b]; lane[b] < 0: zeros (a reset).
+// One grid for all of it: z = region, y = destination sample, x strides the image.
+struct StateCopyTable {
+  const u32x4_t* src[2 * NINT_MAX_LAYERS];
+  u32x4_t* dst[2 * NINT_MAX_LAYERS];        // first image of THIS launch's samples
+  unsigned nvec[2 * NINT_MAX_LAYERS];       // 16-byte vectors per image
+  int lane[NINT_PRE_MAX_B];
+};
+
+__global__ __launch_bounds__(256) void state_copy_kernel(StateCopyTable t) {
+  const int r = blockIdx.z, b = blockIdx.y;
+  const size_t nv = t.nvec[r];
+  const int ls = t.lane[b];
+  u32x4_t* __restrict__ d = t.dst[r] + (size_t)b * nv;
+  const size_t step = (size_t)gridDim.x * 256;
+  if (ls < 0) {
+    for (size_t i = blockIdx.x * (size_t)256 + threadIdx.x; i < nv; i += step) d[i] = (u32x4_t){0u, 0u, 0u, 0u};
+    return;
+  }
+  const u32x4_t* __restrict__ s = t.src[r] + (size_t)ls * nv;
+  for (size_t i = blockIdx.x * (size_t)256 + threadIdx.x; i < nv; i += step) d[i] = s[i];
+}
+
+extern "C" int nint_state_copy(void* const* h_dst, float* const* c_dst, const void* const* h_src, const float* const* c_src,
+                               const int32_t* Chp, int L, int B_dst, int B_src, const int32_t* lane, const nint_geom* g,
+                               int dtype, void* stream) {
+  if (!h_dst || !c_dst || !h_src || !c_src || !Chp || !g || L < 1 || L > NINT_MAX_LAYERS || B_dst < 1 || B_src < 1) return NINT_E_ARG;
+  if (dtype != NINT_F32 && dtype != NINT_BF16) return NINT_E_ARG;
+  if (g->H < 1 || g->W < 1 || g->Hh < g->H || g->Wh < g->W) return NINT_E_ARG;
+  if (!lane && B_dst != B_src) return NINT_E_ARG;
+  for (int b = 0; lane && b < B_dst; ++b)
+    if (lane[b] < -1 || lane[b] >= B_src) return NINT_E_ARG;
+  const size_t es = dtype == NINT_BF16 ? 2 : 4;
+  const int kc = dtype == NINT_BF16 ? 32 : 16;
+  StateCopyTable t = {};
+  size_t img[2 * NINT_MAX_LAYERS], max_nv = 0;
+  for (int l = 0; l < L; ++l) {
+    if (Chp[l] < 1 || Chp[l] % kc) return NINT_E_ARG;
+    if (!h_dst[l] || !c_dst[l] || !h_src[l] || !c_src[l]) return NINT_E_ARG;
+    img[2 * l] = (size_t)g->Hh * g->Wh * Chp[l] * es;
+    img[2 * l + 1] = (size_t)g->H * g->W * Chp[l] * sizeof(float);
+    t.src[2 * l] = (const u32x4_t*)h_src[l]; t.src[2 * l + 1] = (const u32x4_t*)c_src[l];
+    t.dst[2 * l] = (u32x4_t*)h_dst[l]; t.dst[2 * l + 1] = (u32x4_t*)c_dst[l];
+  }
+  for (int r = 0; r < 2 * L; ++r) {
+    if (img[r] / 16 > 0xffffffffu) return NINT_E_SHAPE;
+    t.nvec[r] = (unsigned)(img[r] / 16);
+    if (t.nvec[r] > max_nv) max_nv = t.nvec[r];
+  }
+  for (int r = 0; r < 2 * L; ++r)
+    if ((((uintptr_t)t.src[r]) | ((uintptr_t)t.dst[r])) & 15) return NINT_E_ALIGN;
+  for (int r = 0; r < 2 * L; ++r) {      // a block read while another sample's workgroups write it: refused
+    const uintptr_t s0 = (uintptr_t)t.src[r], s1 = s0 + (size_t)B_src * img[r], d0 = (uintptr_t)t.dst[r], d1 = d0 + (size_t)B_dst * img[r];
+    if (s0 < d1 && d0 < s1) return NINT_E_ARG;
+  }
+  // enough workgroups per image to keep every CU's memory pipe busy on one sample, eight vectors per thread at the most
+  unsigned gx = (unsigned)((max_nv + 256 * 8 - 1) / (256 * 8));
+  if (gx > 64) gx = 64;
+  if (gx < 1) gx = 1;
+  u32x4_t* dst0[2 * NINT_MAX_LAYERS];
+  for (int r = 0; r < 2 * L; ++r) dst0[r] = t.dst[r];
+  for (int b0 = 0; b0 < B_dst; b0 += NINT_PRE_MAX_B) {
+    const int nb = B_dst - b0 < NINT_PRE_MAX_B ? B_dst - b0 : NINT_PRE_MAX_B;
+    for (int i = 0; i < NINT_PRE_MAX_B; ++i) t.lane[i] = i < nb ? (lane ? lane[b0 + i] : b0 + i) : -1;
+    for (int r = 0; r < 2 * L; ++r) t.dst[r] = dst0[r] + (size_t)b0 * t.nvec[r];
+    hipLaunchKernelGGL(state_copy_kernel, dim3(gx, (unsigned)nb, (unsigned)(2 * L)), dim3(256), 0, (hipStream_t)stream, t);
+    NINT_LAUNCH_CHECK();
+  }
+  return NINT_OK;
+}
+
 // ------------------------------------------------------------------------------ preproc
 // dataset.py:526-536 through :67-98.  Output element (t, c, yp, xp):
 //   lon: cyclic, xs = (xp - pl) mod W                            (dataset.py:67-80)

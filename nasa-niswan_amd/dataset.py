@@ -78,6 +78,27 @@ class SlabBatch:
         check(rc, "nint_preproc_fuse_pad_static_slab")
 
 
+def stateful_schedule(n_windows: int, T: int, B: int) -> Tuple[np.ndarray, int]:
+    """Data order for carried state (FusedTrainer(stateful=True), train.py --stateful): the (K, B) int array of dataset indices
+    whose row k is the batch of step k, and the number of trailing windows that are dropped.
+
+    Window i of a dataset covers the record steps [first + i, first + i + T), so the n_windows sliding windows cover
+    n_windows + T - 1 steps, which hold C = (n_windows - 1) // T + 1 NON-OVERLAPPING chunks: windows 0, T, 2T, ...  Lane b walks
+    its own contiguous segment of K = C // B chunks: row k, lane b is window (b * K + k) * T, T steps after row k - 1 of the
+    same lane -- the chunk the carried state of that lane continues into.  The chunks that fill no row and the steps that
+    fill no chunk are dropped: the second return value is the size of that tail in record steps, n_windows + T - 1 - K * B * T
+    (= the number of windows that start behind the last chunk start).  More lanes than chunks: ValueError.  Pure numpy."""
+    n_windows, T, B = int(n_windows), int(T), int(B)
+    if n_windows < 1 or T < 1 or B < 1:
+        raise ValueError(f"stateful_schedule: n_windows, T, B must be positive, got {(n_windows, T, B)}")
+    chunks = (n_windows - 1) // T + 1
+    K = chunks // B
+    if K < 1:
+        raise ValueError(f"stateful_schedule: {B} lanes, but {n_windows} windows of {T} steps hold {chunks} non-overlapping chunks only")
+    idx = (np.arange(B, dtype=np.int64)[None, :] * K + np.arange(K, dtype=np.int64)[:, None]) * T
+    return idx, n_windows - 1 - int(idx.max())
+
+
 def reference_split(n_steps: int) -> Tuple[int, int]:
     """(first validation step, first test step) of a record: the reference hard-codes 3023 / 3455 for its 4320-step (90 days x
     48) file (dataset.py:589-612: 70 % / 10 % / 20 %); other record lengths get the same proportions."""

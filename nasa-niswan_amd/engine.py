@@ -122,6 +122,82 @@ class Workspace:
         return self.c[l].data_ptr() + slot * self.B * self.H * self.W * Chp * 4
 
 
+class ConvLSTMState:
+    """The recurrent state (h, c) of every layer of one engine, kept on the device IN SLAB FORM: per layer
+    an ET halo slab [B][Hh][Wh][Chp] for h and an f32 compact slab [B][H][W][Chp] for c -- the very bytes of slot T of a
+    workspace, so carrying it into the next call costs ONE launch (nint_state_copy) and no f32 NCHW round trip.
+    Detached by construction: it is not a tensor autograd knows, so a chain of calls through it is TRUNCATED BPTT --
+    gradients stop at the chunk boundary.  (Pass the (h, c) tensor pairs instead for gradients across the boundary.)
+    A state belongs to the engine that made it (layer widths, storage dtype, halo P) and to one (B, H, W)."""
+
+    def __init__(self, eng: "SeqEngine", B: int, H: int, W: int, zero: bool = True):
+        self.eng, self.B, self.H, self.W = eng, int(B), int(H), int(W)
+        if self.B < 1 or self.H < 1 or self.W < 1:
+            raise ValueError(f"ConvLSTMState: B, H, W must be positive, got {(B, H, W)}")
+        self.g = NintGeom()
+        check(eng.lib.nint_geom_make(C.byref(self.g), self.H, self.W, eng.P), "nint_geom_make")
+        new = torch.zeros if zero else torch.empty       # (a state that one whole-image copy fills at once needs no fill)
+        self.h, self.c = [], []
+        for cfg in eng.cfgs:
+            Chp = cfg.padded(eng.kc)[2]
+            self.h.append(new(self.B * self.g.Hh * self.g.Wh * Chp * eng.es, dtype=torch.uint8, device=eng.device))
+            self.c.append(new(self.B * self.H * self.W * Chp, dtype=torch.float32, device=eng.device))
+
+    @property
+    def dtype(self) -> str:
+        return "bf16" if self.eng.dt == NINT_BF16 else "f32"
+
+    @property
+    def layers(self) -> List[int]:
+        return [cfg.Ch for cfg in self.eng.cfgs]
+
+    def _ptrs(self):
+        return [t.data_ptr() for t in self.h], [t.data_ptr() for t in self.c]
+
+    def tensors(self) -> List[Tuple[torch.Tensor, torch.Tensor]]:
+        """The reference's ``hidden_states`` list: [(h, c)] per layer, (B, Ch, H, W) f32 (model.py:259-262,270)."""
+        eng, out = self.eng, []
+        st = stream_ptr()
+        for l, cfg in enumerate(eng.cfgs):
+            Chp = cfg.padded(eng.kc)[2]
+            h = torch.empty(self.B, cfg.Ch, self.H, self.W, dtype=torch.float32, device=eng.device)
+            c = torch.empty_like(h)
+            check(eng.lib.nint_unpack_halo(ptr(self.h[l]), ptr(h), 0, self.B, cfg.Ch, Chp, C.byref(self.g), eng.dt, st),
+                  "nint_unpack_halo")
+            check(eng.lib.nint_unpack_compact(ptr(self.c[l]), ptr(c), self.B, cfg.Ch, Chp, self.H, self.W, NINT_F32, st),
+                  "nint_unpack_compact")
+            out.append((h, c))
+        return out
+
+    def select(self, lanes: Sequence[int]) -> "ConvLSTMState":
+        """A new state whose sample b is this state's sample lanes[b] -- a permutation, a subset, a repetition -- or the zero
+        state where lanes[b] is -1 (that lane starts a new record).  One launch."""
+        lanes = [int(v) for v in lanes]
+        if not lanes or any(v < -1 or v >= self.B for v in lanes):
+            raise ValueError(f"ConvLSTMState.select: lanes must be a non-empty sequence of values in [-1, {self.B}), got {lanes}")
+        out = ConvLSTMState(self.eng, len(lanes), self.H, self.W, zero=False)
+        self.eng._state_copy(out._ptrs(), self._ptrs(), out.B, self.B, lanes, self.g)
+        return out
+
+    def reset(self, mask=None) -> "ConvLSTMState":
+        """Zero state for every sample (mask None) or for the samples whose mask entry is true; the others keep theirs.  The
+        object is changed in place (its buffers are replaced by the result of one launch)."""
+        if mask is None:
+            lanes = [-1] * self.B
+        else:
+            m = [bool(v) for v in (mask.tolist() if hasattr(mask, "tolist") else mask)]
+            if len(m) != self.B:
+                raise ValueError(f"ConvLSTMState.reset: mask has {len(m)} entries, the state has B = {self.B}")
+            lanes = [-1 if v else b for b, v in enumerate(m)]
+        if any(v < 0 for v in lanes):
+            new = self.select(lanes)
+            self.h, self.c = new.h, new.c
+        return self
+
+    def clone(self) -> "ConvLSTMState":
+        return self.select(range(self.B))
+
+
 class SeqEngine:
     def __init__(self, cfgs: Sequence[LayerCfg], dtype="f32", device="cuda"):
         if len(cfgs) < 1 or len(cfgs) > _lib.NINT_MAX_LAYERS:
@@ -237,6 +313,93 @@ class SeqEngine:
     @staticmethod
     def release(ws: Workspace):
         ws.in_use = False
+
+    # ------------------------------------------------------------------ carried state
+    def new_state(self, B: int, H: int, W: int) -> ConvLSTMState:
+        """the zero state of a (B, H, W) problem (model.py:259-262) in device form"""
+        return ConvLSTMState(self, B, H, W)
+
+    def state_from_tensors(self, pairs) -> ConvLSTMState:
+        """[(h, c)] per layer, (B, Ch, H, W) tensors on the engine's device -> a (detached) device state"""
+        hs, cs = self._state_tensors(pairs, None)
+        B, _, H, W = hs[0].shape
+        st = ConvLSTMState(self, B, H, W)
+        sp, g = stream_ptr(), C.byref(st.g)
+        for l, cfg in enumerate(self.cfgs):
+            Chp = cfg.padded(self.kc)[2]
+            hh = hs[l].detach().float().contiguous().view(B, 1, cfg.Ch, H, W)
+            check(self.lib.nint_pack_btchw(ptr(hh), ptr(st.h[l]), B, 1, cfg.Ch, Chp, g, self.dt, sp), "pack h")
+            cc = cs[l].detach().float().contiguous()
+            check(self.lib.nint_pack_compact(ptr(cc), ptr(st.c[l]), B, cfg.Ch, Chp, H, W, NINT_F32, sp), "pack c")
+        return st
+
+    def _state_tensors(self, pairs, BHW):
+        """validate a list of (h, c) tensor pairs against the engine (and a (B, H, W), when given): ValueError naming what differs"""
+        pairs = list(pairs)
+        if len(pairs) != len(self.cfgs):
+            raise ValueError(f"state: {len(pairs)} (h, c) pairs given, the model has {len(self.cfgs)} layers")
+        hs, cs = [], []
+        for l, (cfg, hc) in enumerate(zip(self.cfgs, pairs)):
+            if not isinstance(hc, (tuple, list)) or len(hc) != 2:
+                raise ValueError(f"state: layer {l} must be an (h, c) pair of tensors")
+            for name, t in zip("hc", hc):
+                if not isinstance(t, torch.Tensor) or t.dim() != 4:
+                    raise ValueError(f"state: {name} of layer {l} must be a (B, {cfg.Ch}, H, W) tensor")
+                if not t.is_floating_point():
+                    raise ValueError(f"state: {name} of layer {l} has dtype {t.dtype}, a floating-point tensor is expected")
+                if t.device.type != self.device.type:
+                    raise ValueError(f"state: {name} of layer {l} lives on {t.device}, the model on {self.device}")
+                ref = pairs[0][0].shape          # (without a (B, H, W): the first tensor's)
+                want = (BHW[0], cfg.Ch, BHW[1], BHW[2]) if BHW is not None else (ref[0], cfg.Ch, ref[2], ref[3])
+                if tuple(t.shape) != want:
+                    raise ValueError(f"state: {name} of layer {l} has shape {tuple(t.shape)}, expected {want} "
+                                     "(B, hidden channels of the layer, grid of the input)")
+            hs.append(hc[0]); cs.append(hc[1])
+        return hs, cs
+
+    def check_state(self, state: ConvLSTMState, B: int, H: int, W: int):
+        """a device state against this engine and a (B, H, W) problem, before any launch: ValueError naming what differs"""
+        eng = state.eng
+        if eng is not self:
+            if eng.dt != self.dt:
+                raise ValueError(f"state: dtype {state.dtype}, the model computes in {'bf16' if self.dt == NINT_BF16 else 'f32'}")
+            if [c.Ch for c in eng.cfgs] != [c.Ch for c in self.cfgs]:
+                raise ValueError(f"state: layers {[c.Ch for c in eng.cfgs]}, the model has {[c.Ch for c in self.cfgs]}")
+            if eng.P != self.P:
+                raise ValueError(f"state: made by an engine with halo P = {eng.P}, this one has P = {self.P}")
+        if state.B != B:
+            raise ValueError(f"state: batch size B = {state.B}, the input has B = {B}")
+        if (state.H, state.W) != (H, W):
+            raise ValueError(f"state: grid {(state.H, state.W)}, the input has {(H, W)}")
+
+    def _state_copy(self, dst, src, B_dst: int, B_src: int, lanes, g):
+        """ONE nint_state_copy launch: (h pointers, c pointers) of every layer, destination <- source through `lanes`"""
+        L = len(self.cfgs)
+        arr = lambda v: (C.c_void_p * L)(*v)
+        chp = (C.c_int32 * L)(*[cfg.padded(self.kc)[2] for cfg in self.cfgs])
+        ln = None if lanes is None else (C.c_int32 * B_dst)(*[int(v) for v in lanes])
+        check(self.lib.nint_state_copy(arr(dst[0]), arr(dst[1]), arr(src[0]), arr(src[1]), chp, L, B_dst, B_src, ln, C.byref(g),
+                                       self.dt, stream_ptr()), "nint_state_copy")
+
+    def _slot_ptrs(self, ws: Workspace, slot: int):
+        L = range(len(self.cfgs))
+        return [ws.h_view(self, l, slot) for l in L], [ws.c_view(self, l, slot) for l in L]
+
+    def load_state(self, ws: Workspace, state: ConvLSTMState):
+        """state -> slot 0 of a has_init workspace (the initial state nint_seq_fwd starts from): one launch"""
+        if not ws.key[5]:
+            raise ValueError("load_state needs a workspace acquired with has_init=True (others start from the zero state)")
+        self.check_state(state, ws.B, ws.H, ws.W)
+        self._state_copy(self._slot_ptrs(ws, 0), state._ptrs(), ws.B, ws.B, None, ws.g)
+
+    def save_state(self, ws: Workspace, state: Optional[ConvLSTMState] = None) -> ConvLSTMState:
+        """slot T of a workspace (h_{T-1}, c_{T-1} of every layer after forward) -> `state` (a new one if None): one launch"""
+        if state is None:
+            state = ConvLSTMState(self, ws.B, ws.H, ws.W, zero=False)
+        else:
+            self.check_state(state, ws.B, ws.H, ws.W)
+        self._state_copy(state._ptrs(), self._slot_ptrs(ws, ws.T), ws.B, ws.B, None, ws.g)
+        return state
 
     # ------------------------------------------------------------------ passes
     def forward(self, ws: Workspace, x: torch.Tensor, h0: Optional[List[torch.Tensor]] = None,
@@ -456,7 +619,7 @@ class SeqEngine:
 
     def backward(self, ws: Workspace, need_dx: bool, zero_state_grads: Sequence[int] = (),
                  dW_out: Optional[Sequence[torch.Tensor]] = None, db_out: Optional[Sequence[torch.Tensor]] = None, parts: int = 0,
-                 seq_grads: bool = False):
+                 seq_grads: bool = False, zero_mask: Optional[int] = None):
         """BPTT of model.py:253-271.  Precondition: ws.dh[l], ws.dc[l] hold dL/dh_{T-1}, dL/dc_{T-1}
         (layers listed in ``zero_state_grads`` start from zero state gradients instead).  Returns ([dW_l], [db_l], dx or None).
         ``dW_out`` / ``db_out``: f32 contiguous destinations (e.g. views of a flat gradient bucket).
@@ -474,7 +637,8 @@ class SeqEngine:
             mask |= 1 << (2 * l)
             if l < L - 1:
                 mask |= 1 << (2 * l + 1)
-        ws.seq.zero_dstate = mask
+        # ``zero_mask``: nint_seq.zero_dstate itself, where h and c of a layer differ (a returned state with one cotangent missing)
+        ws.seq.zero_dstate = mask if zero_mask is None else int(zero_mask)
         dWs, dbs = [], []
         s = ws.seq
         for l, cfg in enumerate(self.cfgs):
@@ -535,3 +699,24 @@ class SeqEngine:
             else:
                 s2 = src.detach().float().contiguous()
                 check(self.lib.nint_pack_compact(ptr(s2), ptr(dst), ws.B, cfg.Ch, Chp, ws.H, ws.W, dt, st), "pack dstate")
+
+    def set_dstate(self, ws: Workspace, l: int, which: str, t: torch.Tensor):
+        """one cotangent of a returned final state, (B, Ch, H, W), into ws.dh[l] (which = "h") or ws.dc[l] ("c")"""
+        cfg = self.cfgs[l]
+        Chp = cfg.padded(self.kc)[2]
+        dst, dt = (ws.dh[l], self.dt) if which == "h" else (ws.dc[l], NINT_F32)
+        s2 = t.detach().float().contiguous()
+        check(self.lib.nint_pack_compact(ptr(s2), ptr(dst), ws.B, cfg.Ch, Chp, ws.H, ws.W, dt, stream_ptr()), "pack dstate")
+
+    def add_top_dh(self, ws: Workspace, dh: torch.Tensor, seq_grads: bool):
+        """the top layer's returned h_{T-1} has a cotangent of its own: added to the head's dL/dh_{T-1} where BPTT reads it --
+        ws.dh[-1], or the last block of ws.dh_seq_slab() with per-step head gradients (nint_pack_compact_add)"""
+        cfg = self.cfgs[-1]
+        Chp = cfg.padded(self.kc)[2]
+        s2 = dh.detach().float().contiguous()
+        if seq_grads:
+            dst = C.c_void_p(ws.dh_seq_slab(self).data_ptr() + (ws.T - 1) * ws.B * ws.H * ws.W * Chp * self.es)
+        else:
+            dst = ptr(ws.dh[-1])
+        check(self.lib.nint_pack_compact_add(ptr(s2), dst, ws.B, cfg.Ch, Chp, ws.H, ws.W, self.dt, stream_ptr()),
+              "nint_pack_compact_add")

@@ -282,3 +282,70 @@ def evaluate_skill(net, dataset, batch_size: int = 8, halo: Tuple[int, int] = (5
         acc.update(eng, ws, net.conv.weight, net.conv.bias, y, slots_all[s:s + B], pred_out=None if preds is None else preds[s:s + B])
         eng.release(ws)
     return (acc, preds) if return_predictions else acc
+
+
+# ------------------------------------------------------------------------------ roll-forward inference with carried state
+@torch.no_grad()
+def predict_stream(net, dataset, lanes: int = 1, halo: Tuple[int, int] = (5, 5), skill: Optional[SkillAccumulator] = None):
+    """Walk the dataset's period ONCE: non-overlapping chunks of `dataset.seq_len` steps with the state carried on the device
+    (`net(X, state, return_state="device")`), the head applied at every step (head_forward_seq) -- where `predict` runs
+    every record step seq_len times, once per sliding window it falls into.
+
+    Returns (pred, steps, dropped): `pred` (N, O, Hc, Wc) f32 on the device, the cropped per-step predictions in z-score
+    units in time order; `steps` (N,) int64 numpy, the record step each belongs to; `dropped`, the number of steps at the
+    end of the period that fill no chunk (reported, not predicted).
+
+    `lanes` > 1 cuts the period into that many contiguous segments that run as one batch.  EACH SEGMENT STARTS FROM THE ZERO
+    STATE, so the first steps of every segment but the first see less history than with lanes = 1; the steps of the chunks
+    that fill no full row of lanes are dropped too.
+
+    `skill`: a SkillAccumulator (O, Hc, Wc of the dataset's grid) that every chunk's steps are folded into
+    (update_from_pred, time steps as samples, slot 0) against the tracer at the same steps."""
+    from .dataset import stateful_schedule
+    net.eval()
+    T = dataset.seq_len
+    Hc, Wc = dataset.grid
+    sched, _ = stateful_schedule(len(dataset), T, lanes)
+    K, B = sched.shape
+    n_steps = len(dataset) + T - 1                        # record steps the period's windows cover
+    dropped = n_steps - K * B * T
+    O = net.conv.weight.shape[0]
+    dev = next(net.parameters()).device
+    eng = net._engine(dev)
+    out = torch.empty(B, K * T, O, Hc, Wc, dtype=torch.float32, device=dev)
+    dv = dataset._device_arrays() if skill is not None else None
+    state = None
+    for k in range(K):
+        X, _ = dataset.slab_batch(sched[k])
+        _, _, _, H, W = X.shape
+        ws = eng.acquire(B, T, H, W, False, state is not None)
+        eng.pack_weights([c.conv.weight for c in net.layers], [c.conv.bias for c in net.layers])
+        if state is not None:
+            eng.load_state(ws, state)
+        eng.forward(ws, X)
+        state = eng.save_state(ws, state)
+        seq = eng.head_forward_seq(ws, net.conv.weight, net.conv.bias)             # (B, T*O, H, W), channel t*O + o
+        eng.release(ws)
+        out[:, k * T:(k + 1) * T] = seq.view(B, T, O, H, W)[:, :, :, halo[0]:halo[0] + Hc, halo[1]:halo[1] + Wc]
+        if skill is not None:
+            t0s = [int(dataset.first[int(i)]) for i in sched[k]]
+            y = _step_targets(dataset, dv, t0s, T)                                # (B, T, L, Hc, Wc)
+            skill.update_from_pred(seq.view(B * T, O, H, W), y.reshape(B * T, O, Hc, Wc), halo)
+    first = int(dataset.first[0])
+    steps = np.concatenate([first + int(sched[0, b]) + np.arange(K * T, dtype=np.int64) for b in range(B)])
+    return out.view(B * K * T, O, Hc, Wc), steps, dropped
+
+
+def _step_targets(dataset, dv, t0s, T):
+    """z-scored tracer at every step of the windows starting at record steps t0s: (B, T, L, H, W) on the device"""
+    from . import _lib
+    from ._lib import check, ptr, stream_ptr
+    H, W = dataset.grid
+    B, L = len(t0s), dataset.levels
+    y = torch.empty(B, T, L, H, W, dtype=torch.float32, device=dataset.device)
+    yptr = (C.c_void_p * 1)(dv["y"].data_ptr())
+    ylev = (C.c_int * 1)(L)
+    tl = (C.c_int * B)(*t0s)
+    check(_lib.load().nint_preproc_fuse_pad_batch(yptr, ylev, 1, ptr(dv["ymean"]), ptr(dv["ystd"]), tl, B, ptr(y), T, H, W, H, W, 1,
+                                                  stream_ptr()), "target z-score")
+    return y

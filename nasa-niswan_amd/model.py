@@ -12,6 +12,11 @@ Extensions are keyword-only with reference-preserving defaults (SURVEY.md sectio
     return_sequence also return the per-step head outputs (the variant the analysis notebook
                     was run with: model.py:264,272,274 commented code, test.ipynb:273); differentiable:
                     gradients flow through ``seq`` as through ``pred``
+
+Carried state (no reference code: model.py:259-262 always starts from zeros and drops the final state):
+``ConvLSTM.forward(x, state=None, *, return_state=False)`` takes ``(h0, c0)`` of every layer and returns ``(h_T, c_T)``, as
+tensors (differentiable: chaining two calls is full BPTT across the boundary) or as a ``ConvLSTMState`` that stays on the
+device in slab form (detached: truncated BPTT).  DESIGN.md 4.10.
 """
 from __future__ import annotations
 
@@ -23,9 +28,9 @@ import torch
 import torch.nn as nn
 from torch._C import _functions
 
-from .engine import LayerCfg, SeqEngine, dtype_code
+from .engine import ConvLSTMState, LayerCfg, SeqEngine, dtype_code
 
-__all__ = ["ConvLSTMCell", "ConvLSTM"]
+__all__ = ["ConvLSTMCell", "ConvLSTM", "ConvLSTMState"]
 
 
 def _require_cuda(t: torch.Tensor, who: str):
@@ -129,6 +134,112 @@ class _ConvLSTMFn(torch.autograd.Function):
         for l in range(L):
             grads += [dWs[l], dbs[l]]
         return (None, None, dx, dw_head, db_head, *grads)
+
+
+class _StateOpts:
+    """the non-tensor arguments of _ConvLSTMStateFn: the device state that comes in (or None), what goes out, and the box the
+    outgoing device state is handed back in (a Function's outputs are tensors)"""
+
+    def __init__(self, state_in, return_state):
+        self.state_in, self.return_state, self.state_out = state_in, return_state, None
+
+
+class _ConvLSTMStateFn(torch.autograd.Function):
+    """x, head_w, head_b, W_0, b_0, ..., W_{L-1}, b_{L-1} [, h0_0, c0_0, ..., h0_{L-1}, c0_{L-1}]
+    -> pred [, seq] [, hT_0, cT_0, ..., hT_{L-1}, cT_{L-1}]
+
+    The stateful twin of _ConvLSTMFn (which stays as it is: the default call launches what it always did).  Tensor states
+    are inputs and outputs of the Function: dL/dh0, dL/dc0 come from the BPTT's own d/dh_init, d/dc_init, and the cotangents
+    of the returned states enter BPTT as the incoming dh[l] / dc[l].  A ConvLSTMState in or out is not seen by autograd."""
+
+    @staticmethod
+    def forward(ctx, module, grad_mode, opts, x, head_w, head_b, *rest):
+        eng: SeqEngine = module._engine(x.device)
+        L = len(eng.cfgs)
+        wb, st = rest[:2 * L], rest[2 * L:]
+        B, T, _, H, W = x.shape
+        train = grad_mode and any(ctx.needs_input_grad)
+        has_init = opts.state_in is not None or len(st) > 0
+        ws = eng.acquire(B, T, H, W, train, has_init)
+        eng.pack_weights(wb[0::2], wb[1::2])
+        if opts.state_in is not None:
+            eng.load_state(ws, opts.state_in)
+            eng.forward(ws, x)
+        elif st:
+            eng.forward(ws, x, list(st[0::2]), list(st[1::2]))
+        else:
+            eng.forward(ws, x)
+        outs = [eng.head_forward(ws, head_w, head_b)]
+        if module.return_sequence:
+            outs.append(eng.head_forward_seq(ws, head_w, head_b))
+        if opts.return_state == "device":
+            opts.state_out = eng.save_state(ws)
+        elif opts.return_state:
+            for l in range(L):
+                outs += [eng.h_last(ws, l), eng.c_last(ws, l)]
+        ctx.return_sequence = module.return_sequence
+        if train:
+            ctx.set_materialize_grads(False)                            # a missing cotangent stays None: that state keeps its zero_dstate bit
+            ctx.eng, ctx.ws, ctx.rel, ctx.gen = eng, ws, _Releaser(ws), ws.gen
+            ctx.save_for_backward(head_w, *wb[0::2])                    # (references: see _ConvLSTMFn)
+            ctx.x_needs_grad = ctx.needs_input_grad[3]
+            ctx.nwb, ctx.nst = len(wb), len(st)
+            ctx.st_needs_grad = any(ctx.needs_input_grad[6 + len(wb):])
+        else:
+            eng.release(ws)
+        return tuple(outs) if len(outs) > 1 else outs[0]
+
+    @staticmethod
+    @_once_differentiable
+    def backward(ctx, *douts):
+        eng, ws = _own_workspace(ctx, "ConvLSTM")
+        head_w = ctx.saved_tensors[0]           # before the first launch: raises if a weight was modified in place
+        L = len(eng.cfgs)
+        nin = 6 + ctx.nwb + ctx.nst
+        n0 = 2 if ctx.return_sequence else 1
+        dpred = douts[0]
+        dseq = douts[1] if ctx.return_sequence else None
+        dst = list(douts[n0:]) + [None] * (2 * L - len(douts[n0:]))     # (hT_0, cT_0, ...): all None without tensor states out
+        if all(d is None for d in douts):
+            ctx.rel.release()
+            return (None,) * nin
+        # the top layer: the head's dL/dh_{T-1} (per step with a sequence cotangent) plus the cotangent of the returned h_{T-1}
+        seq_grads = dseq is not None
+        dh_top = dst[2 * (L - 1)]
+        dw_head = db_head = None
+        if seq_grads:
+            dw_head, db_head = eng.head_backward_seq(ws, head_w, dseq, dpred)
+        elif dpred is not None:
+            dw_head, db_head = eng.head_backward(ws, head_w, dpred)
+        if dw_head is None:                     # no head gradient at all: the state's cotangent alone (zeros if there is none)
+            if dh_top is None:
+                ws.dh[-1].zero_()
+            else:
+                eng.set_dstate(ws, L - 1, "h", dh_top)
+        elif dh_top is not None:
+            eng.add_top_dh(ws, dh_top, seq_grads)
+        mask = 0
+        for l in range(L):
+            dh, dc = dst[2 * l], dst[2 * l + 1]
+            if dc is None:
+                mask |= 1 << (2 * l)
+            else:
+                eng.set_dstate(ws, l, "c", dc)
+            if l < L - 1:
+                if dh is None:
+                    mask |= 1 << (2 * l + 1)
+                else:
+                    eng.set_dstate(ws, l, "h", dh)
+        dWs, dbs, dx = eng.backward(ws, ctx.x_needs_grad, seq_grads=seq_grads, zero_mask=mask)
+        dstate = []
+        if ctx.nst:
+            for l in range(L):
+                dstate += list(eng.state_grads(ws, l)) if ctx.st_needs_grad else [None, None]
+        ctx.rel.release()
+        grads = []
+        for l in range(L):
+            grads += [dWs[l], dbs[l]]
+        return (None, None, None, dx, dw_head, db_head, *grads, *dstate)
 
 
 class _CellFn(torch.autograd.Function):
@@ -236,10 +347,44 @@ class ConvLSTM(_EngineOwner, nn.Module):
             self._engines[key] = SeqEngine(cfgs, self.compute_dtype, device)
         return self._engines[key]
 
-    def forward(self, x):
-        # x: (batch_size, sequence_length, channels, height, width)  (model.py:254)
+    def forward(self, x, state=None, *, return_state=False):
+        """x: (batch_size, sequence_length, channels, height, width)  (model.py:254).
+
+        ``state``: None (zeros, model.py:259-262), a list of ``num_layers`` ``(h, c)`` tensor pairs (B, Ch_l, H, W) -- the
+        reference's ``hidden_states`` -- or a ``ConvLSTMState``.  ``return_state``: False = the return values of the
+        reference; True = the list of ``(h_T, c_T)`` tensor pairs follows ``pred`` (and ``seq``); "device" = a
+        ``ConvLSTMState`` follows instead, left on the device in slab form (no NCHW round trip).
+
+        Tensor states are differentiable both ways: a state that requires grad receives dL/dh0, dL/dc0, and the returned
+        tensors carry gradients back into the window, so two chained calls are full BPTT across the boundary.  A
+        ``ConvLSTMState`` in or out is DETACHED: chaining calls through it is truncated BPTT.  ``net(x)`` alone takes the
+        path it always took."""
         _require_cuda(x, "ConvLSTM")
         wb = []
         for cell in self.layers:
             wb += [cell.conv.weight, cell.conv.bias]
-        return _ConvLSTMFn.apply(self, torch.is_grad_enabled(), x, self.conv.weight, self.conv.bias, *wb)
+        if state is None and not return_state:
+            return _ConvLSTMFn.apply(self, torch.is_grad_enabled(), x, self.conv.weight, self.conv.bias, *wb)
+        if return_state not in (False, True, "device"):
+            raise ValueError(f"return_state must be False, True or 'device', got {return_state!r}")
+        if len(x.shape) != 5:
+            raise ValueError(f"ConvLSTM: x must be (B, T, C, H, W), got {tuple(x.shape)}")
+        eng = self._engine(x.device)
+        B, _, _, H, W = x.shape
+        st = []
+        if isinstance(state, ConvLSTMState):            # every mismatch is a ValueError here, before anything is launched
+            eng.check_state(state, B, H, W)
+        elif state is not None:
+            hs, cs = eng._state_tensors(state, (B, H, W))
+            for h, c in zip(hs, cs):
+                st += [h, c]
+        opts = _StateOpts(state if isinstance(state, ConvLSTMState) else None, return_state)
+        out = _ConvLSTMStateFn.apply(self, torch.is_grad_enabled(), opts, x, self.conv.weight, self.conv.bias, *wb, *st)
+        out = list(out) if isinstance(out, tuple) else [out]
+        n0 = 2 if self.return_sequence else 1
+        res = out[:n0]
+        if return_state == "device":
+            res.append(opts.state_out)
+        elif return_state:
+            res.append([(out[n0 + 2 * l], out[n0 + 2 * l + 1]) for l in range(self.num_layers)])
+        return tuple(res) if len(res) > 1 else res[0]

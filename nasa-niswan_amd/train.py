@@ -6,7 +6,7 @@ stepped once per epoch before validation, checkpoint every 10 epochs); the per-b
 `loss.item()` / sklearn R2 host syncs (train.py:113-114) are replaced by device accumulators read
 once per epoch.  Added flags: --dtype, --levels, --grid, --synthetic-steps, --pad-mode, --f32-inputs,
 --static-channels, --sequence-loss, --test-skill, --lat-weighted-loss, --loss-weights, --clip-grad-norm,
---skip-nonfinite-steps.
+--skip-nonfinite-steps, --stateful.
 
 The data path is on the device too: by default every batch is written by ONE launch of the
 fuse / z-score / halo-pad kernel straight into the model's bf16 input slab (dataset.slab_batch);
@@ -92,6 +92,11 @@ def get_arguments(argv=None, MODEL='LSTM-00', SPECIES='bcb', LEARNING_RATE=1.0E-
                              "on the device; under DDP the norm of the all-reduced mean gradient")
     parser.add_argument("--skip-nonfinite-steps", action="store_true",
                         help="drop an optimizer step whose gradient holds a NaN or inf (weights, moments and step count untouched)")
+    parser.add_argument("--stateful", action="store_true",
+                        help="truncated BPTT with carried state: every batch lane walks its own contiguous part of the training "
+                             "period in consecutive NON-overlapping chunks of --sequence-length steps (dataset.stateful_schedule, "
+                             "no shuffle), each chunk starting from the state the lane's previous chunk ended in; the state is reset "
+                             "at the start of every epoch.  A record step is then run once per epoch, not --sequence-length times")
     args = parser.parse_args(argv)
     rank = int(os.environ.get("RANK", "0"))
     if rank == 0:
@@ -107,7 +112,7 @@ def main(args):
     import torch.distributed as dist
     import torch.optim as optim
     import nasa_niswan_amd as pkg
-    from nasa_niswan_amd.dataset import SyntheticE33OMA_CRNN
+    from nasa_niswan_amd.dataset import SyntheticE33OMA_CRNN, stateful_schedule
     from nasa_niswan_amd.loss import cos_latitude_weights, grid_latitudes
     from nasa_niswan_amd.trainer import FusedTrainer
     from nasa_niswan_amd.utils import load_checkpoint, save_checkpoint, seed, shard_indices
@@ -154,7 +159,14 @@ def main(args):
         loss_weights = m if loss_weights is None else (loss_weights.astype(np.float64) * m).astype(np.float32)
     trainer = FusedTrainer(generator, lr=args.learning_rate, betas=tuple(args.betas), halo=halo,        # train.py:71
                            sequence_loss=args.sequence_loss, loss_weights=loss_weights,
-                           max_grad_norm=args.clip_grad_norm, skip_nonfinite=args.skip_nonfinite_steps)
+                           max_grad_norm=args.clip_grad_norm, skip_nonfinite=args.skip_nonfinite_steps, stateful=args.stateful)
+    if args.stateful:
+        # one schedule of world * batch lanes, the same every epoch; each rank takes its own columns and carries its own state
+        sched, dropped = stateful_schedule(len(train_dataset), args.sequence_length, world * args.batch_size)
+        sched = sched[:, rank * args.batch_size:(rank + 1) * args.batch_size]
+        if rank == 0:
+            print(f"Stateful schedule: {sched.shape[0]} steps of {world * args.batch_size} lanes x {args.sequence_length} record "
+                  f"steps per epoch, {dropped} trailing windows dropped")
     guarded = args.clip_grad_norm is not None or args.skip_nonfinite_steps
     optimizer = trainer.optimizer
     scheduler = optim.lr_scheduler.StepLR(optimizer, step_size=int(args.scheduler_config[0]),
@@ -168,7 +180,10 @@ def main(args):
         trainer.reset_stats()
         torch.cuda.synchronize()
         t_epoch, n_epoch = time.time(), 0
-        for idx in shard_indices(len(train_dataset), epoch, rank, world, args.batch_size):  # train.py:89
+        if args.stateful:
+            trainer.reset_state()                                                            # every lane starts the record anew
+        batches = sched if args.stateful else shard_indices(len(train_dataset), epoch, rank, world, args.batch_size)   # train.py:89
+        for idx in batches:
             X, y = get_batch(train_dataset, idx)                                             # preproc on device
             loss = trainer.step(X, y)                                                        # train.py:96-110
             n_epoch += len(idx)

@@ -7,6 +7,8 @@
                                                per-cell weighted means of loss.py (the _weighted entries)
     zero_grad; loss.backward()              -> nint_head_bwd + nint_seq_bwd (grads overwrite the bucket)
     [DDP]                                   -> ONE RCCL all-reduce of the flat gradient bucket
+    [stateful]                              -> nint_state_copy before the forward pass (carried state -> slot 0) and after it
+                                               (slot T -> carried state): truncated BPTT over consecutive chunks of a record
     optimizer.step()                        -> nint_adam_flat (1/world folded in); with ``max_grad_norm`` / ``skip_nonfinite``
                                                nint_adam_flat_guarded: norm, clipping and the skip decided on the device
     loss.item(); r2_score(...cpu())         -> device-side accumulators, read once per epoch
@@ -30,7 +32,7 @@ class FusedTrainer:
     def __init__(self, model: ConvLSTM, lr: float = 1e-3, betas=(0.5, 0.999), eps: float = 1e-8,
                  halo: Tuple[int, int] = (5, 5), process_group=None, distributed: Optional[bool] = None,
                  overlap_allreduce: bool = False, sequence_loss: bool = False, loss_weights=None,
-                 max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False):
+                 max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False, stateful: bool = False):
         dev = next(model.parameters()).device
         if dev.type != "cuda":
             raise _lib.NintError("FusedTrainer needs the model on the MI355X (cuda)")
@@ -67,6 +69,11 @@ class FusedTrainer:
         # Per-cell loss weights (loss.py): an (Hc, Wc) map or (Hc,) row weights -- cos latitude, a mask, their product -- used by
         # step, evaluate and forward_loss in every branch.  Every data-parallel rank must be given the same map.
         self.set_loss_weights(loss_weights)
+        # Truncated BPTT over consecutive chunks of a record (dataset.stateful_schedule): step() starts from the state the
+        # previous step() ended in, carried on the device in slab form (engine.ConvLSTMState), and gradients stop at the
+        # chunk start.  evaluate / forward_loss keep zero-state windows; under data parallelism every rank carries its own.
+        self.stateful = bool(stateful)
+        self.state = None
         L = model.num_layers
         self._dW = [self.flat.grad_view(2 * l) for l in range(L)]
         self._db = [self.flat.grad_view(2 * l + 1) for l in range(L)]
@@ -133,22 +140,43 @@ class FusedTrainer:
         self._loss(pred, yv, dpred, B, O, H, W, Hc, Wc, wts)
         return eng, ws, pred, dpred
 
-    def step(self, X: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    def reset_state(self):
+        """stateful: the next step() starts every lane from the zero state (a new epoch, a new record)"""
+        self.state = None
+
+    def _carried_state(self, eng, B, H, W, reset):
+        """the trainer's state for this step: zeros on first use or when the batch shape changed, lanes in `reset` zeroed"""
+        st = self.state
+        if st is None or st.eng is not eng or (st.B, st.H, st.W) != (B, H, W) or reset is True:
+            st = self.state = eng.new_state(B, H, W)
+        elif reset is not None and reset is not False:
+            st.reset(reset)
+        return st
+
+    def step(self, X: torch.Tensor, y: torch.Tensor, reset=None) -> torch.Tensor:
         """One optimisation step; returns the loss as a 0-dim DEVICE tensor (no sync).  X: (B,T,C,Hp,Wp) f32 or a
-        dataset.SlabBatch.  y: (B,[O,]Hc,Wc), or (B,T,[O,]Hc,Wc) with ``sequence_loss``."""
+        dataset.SlabBatch.  y: (B,[O,]Hc,Wc), or (B,T,[O,]Hc,Wc) with ``sequence_loss``.
+        ``reset`` (stateful trainers only): True, or one boolean per lane -- those lanes start this chunk from the zero state."""
         m = self.model
         eng = m._engine(self.device)
         B, T, _, H, W = X.shape
         L = m.num_layers
         wts = self._loss_weights(y.shape[-2], y.shape[-1])      # (validates the map's shape before anything is acquired)
-        ws = eng.acquire(B, T, H, W, True, False)
+        if reset is not None and not self.stateful:
+            raise ValueError("step(reset=...) needs FusedTrainer(stateful=True)")
+        carried = self._carried_state(eng, B, H, W, reset) if self.stateful else None
+        ws = eng.acquire(B, T, H, W, True, self.stateful)
         pb, pm = self._probe
         ws.seq.probe = pb.data_ptr() if pb is not None else None
         ws.seq.probe_mask, ws.seq.probe_slots = pm, (pb.numel() // 2 if pb is not None else 0)
         mark = self._mark
         mark()
         eng.pack_weights([c.conv.weight for c in m.layers], [c.conv.bias for c in m.layers])
+        if carried is not None:
+            eng.load_state(ws, carried)          # carried state -> slot 0
         eng.forward(ws, X)
+        if carried is not None:
+            eng.save_state(ws, carried)          # slot T -> carried state; BPTT below stops at the chunk start
         mark()
         O = m.conv.weight.shape[0]
         Hc, Wc = y.shape[-2], y.shape[-1]
