@@ -100,8 +100,8 @@ typedef struct nint_seq {
   void* dh[NINT_MAX_LAYERS];           /* ET compact [B][H][W][Chp] running dL/dh_t (in: dL/dh_{T-1}, out: dL/dh_init) */
   float* dc[NINT_MAX_LAYERS];          /* f32 compact [B][H][W][Chp] running dL/dc_t */
   void* dx;                            /* ET compact [T*B][H][W][Cxp0] (need_dx only) */
-  float* dW[NINT_MAX_LAYERS];          /* f32 OIHW (4Ch, Cx+Ch, k, k) gradient, overwritten */
-  float* db[NINT_MAX_LAYERS];          /* f32 (4Ch) gradient, overwritten */
+  float* dW[NINT_MAX_LAYERS];          /* f32 OIHW (4Ch, Cx+Ch, k, k) gradient, overwritten (accumulate = 1: added to) */
+  float* db[NINT_MAX_LAYERS];          /* f32 (4Ch) gradient, overwritten (accumulate = 1: added to) */
   float* wg_partial;                   /* f32 split-K slabs for wgrad: the SUM over the layers of nint_wgrad_workspace_bytes
                                         * (each rounded up to 256 bytes) -- the layers' slabs sit side by side */
   size_t wg_partial_bytes;
@@ -151,6 +151,19 @@ typedef struct nint_seq {
    * but layer 0's slice of the gradient bucket, which then runs under layer 0's weight gradient -- the largest launches of the
    * step -- instead of after them.  Same launches, same order inside each layer: bit-identical gradients. */
   int32_t bwd_parts;
+  /* nint_seq_bwd: how the weight / bias gradients of this call reach dW[l] / db[l].
+   *   0  stored: dW[i] = s (the buffers need no initialisation)
+   *   1  added:  dW[i] = dW[i] + s, one f32 add (round to nearest even) by the ONE thread that owns element i in the fold of
+   *      the split-K slabs -- s is the very f32 sum that 0 would have stored, formed in the same fixed order.  No atomics and
+   *      no second pass: the result is (float)(old + s) bit for bit, run to run, for every dW and db element the call
+   *      produces (both weight-gradient families of nint_layer.wide, the bias column, and under bwd_parts the layers of
+   *      that part only; the other layers' buffers are not touched).  dW / db then hold what the caller wants added to:
+   *      the gradients of the window's later segments (checkpointed BPTT) or of the micro-batches
+   *      before this one.
+   * The BPTT chain, the launch list and dx / dh / dc do not depend on it.  Any other value: NINT_E_ARG before any launch.
+   * (The field takes the four bytes that were padding between bwd_parts and the pointer behind it: no offset of the
+   * structure moves and its size stays, so a caller that zero-fills the structure, as every caller must, gets 0.) */
+  int32_t accumulate;
   const void* dh_seq;   /* ET compact [T*B][H][W][Chp of layer L-1], image t*B+b: dL/dh_t of the TOP layer that does not come
                          * through the recurrence (the per-step head outputs: nint_head_bwd_seq / nint_head_loss_seq_fused);
                          * NULL = none (many-to-one: the only such term is dL/dh_{T-1}, in dh[L-1]).  Non-NULL: at every t the
@@ -314,6 +327,13 @@ int nint_head_bwd(const void* h_slab, int n0, int N, int Ch, int Chp, int O, con
                   const float* dpred, void* dh, float* dw, float* db, const nint_geom* g, int dtype,
                   float* scratch, size_t scratch_bytes, void* stream);
 /* scratch (may be NULL): >= 256*O*(Ch+1) floats enables the tiled two-stage weight-gradient path. */
+/* nint_head_bwd with nint_seq.accumulate's switch for dw / db: accumulate = 0 is nint_head_bwd (which calls this entry with 0);
+ * accumulate = 1 writes dw[i] = dw[i] + s and db[o] = db[o] + s, one f32 add by the thread that owns the element in the last
+ * stage of whichever weight-gradient path the shape takes (the one-workgroup-per-output kernel or the fold of the tiled
+ * paths' partials), s being the sum that 0 stores.  dh is overwritten either way.  Any other value: NINT_E_ARG. */
+int nint_head_bwd_acc(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w,
+                      const float* dpred, void* dh, float* dw, float* db, int accumulate, const nint_geom* g, int dtype,
+                      float* scratch, size_t scratch_bytes, void* stream);
 
 /* The head over the WHOLE sequence (model.py:264,272,274 commented code, test.ipynb:273): the top layer's h slab holds h_t in
  * slot t+1, image (t+1)*B + b; seq / dseq are (B, T*O, H, W) f32 contiguous with channel t*O + o (torch.cat of the per-step
@@ -328,6 +348,10 @@ int nint_head_fwd_seq(const void* h_slab, int B, int T, int Ch, int Chp, int O, 
 int nint_head_bwd_seq(const void* h_slab, int B, int T, int Ch, int Chp, int O, const float* w, const float* dseq,
                       const float* dpred_last, void* dh_seq, float* dw, float* db, const nint_geom* g, int dtype,
                       float* scratch, size_t scratch_bytes, void* stream);
+/* nint_head_bwd_seq with the same switch (nint_head_bwd_seq calls it with 0) */
+int nint_head_bwd_seq_acc(const void* h_slab, int B, int T, int Ch, int Chp, int O, const float* w, const float* dseq,
+                          const float* dpred_last, void* dh_seq, float* dw, float* db, int accumulate, const nint_geom* g,
+                          int dtype, float* scratch, size_t scratch_bytes, void* stream);
 
 /* ---- loss (train.py:102,105) ------------------------------------------------------------------ */
 /* pred (N,O,H,W) f32, y (N,O,Hc,Wc) f32; crop window [oy,oy+Hc) x [ox,ox+Wc).

@@ -45,7 +45,7 @@ class NintSeq(C.Structure):
                 ("dc", vp * NINT_MAX_LAYERS), ("dx", vp), ("dW", vp * NINT_MAX_LAYERS), ("db", vp * NINT_MAX_LAYERS),
                 ("wg_partial", vp), ("wg_partial_bytes", C.c_size_t), ("fuse_bwd", C.c_int32),
                 ("probe_mask", C.c_int32), ("probe", vp), ("probe_slots", C.c_int32),
-                ("wave", C.c_int32), ("bwd_parts", C.c_int32), ("dh_seq", vp)]
+                ("wave", C.c_int32), ("bwd_parts", C.c_int32), ("accumulate", C.c_int32), ("dh_seq", vp)]
 
 
 class NintLaunchRec(C.Structure):
@@ -89,8 +89,10 @@ SIGNATURES = {
     "nint_debug_seq_plan": (_I, [_PS, _I, C.POINTER(NintLaunchRec), _I]),
     "nint_head_fwd": (_I, [vp, _I, _I, _I, _I, _I, vp, vp, vp, _PG, _I, vp]),
     "nint_head_bwd": (_I, [vp, _I, _I, _I, _I, _I, vp, vp, vp, vp, vp, _PG, _I, vp, _SZ, vp]),
+    "nint_head_bwd_acc": (_I, [vp, _I, _I, _I, _I, _I, vp, vp, vp, vp, vp, _I, _PG, _I, vp, _SZ, vp]),
     "nint_head_fwd_seq": (_I, [vp, _I, _I, _I, _I, _I, vp, vp, vp, _PG, _I, vp]),
     "nint_head_bwd_seq": (_I, [vp, _I, _I, _I, _I, _I, vp, vp, vp, vp, vp, vp, _PG, _I, vp, _SZ, vp]),
+    "nint_head_bwd_seq_acc": (_I, [vp, _I, _I, _I, _I, _I, vp, vp, vp, vp, vp, vp, _I, _PG, _I, vp, _SZ, vp]),
     "nint_loss_mse_l1_crop": (_I, [vp, vp, vp, vp, vp, _I, _I, _I, _I, _I, _I, _I, _I, vp]),
     "nint_head_loss_fused": (_I, [vp, _I, _I, _I, _I, _I, vp, vp, vp, vp, vp, vp, vp, _PG, _I, _I, _I, _I, _I, vp]),
     "nint_head_loss_seq_fused": (_I, [vp, _I, _I, _I, _I, _I, vp, vp, vp, vp, vp, vp, vp, _PG, _I, _I, _I, _I, _I, vp]),

@@ -206,7 +206,7 @@ template <int DT, class Dp>
 __device__ __forceinline__ void head_bwd_dw_body(const void* __restrict__ h, int n0, int N, int Ch, int Chp,
                                                  int O, const Dp dpred,
                                                  float* __restrict__ dw, float* __restrict__ db, int H, int W,
-                                                 int P, int Hh, int Wh) {
+                                                 int P, int Hh, int Wh, int acc_out) {
   const int o = blockIdx.x / (Ch + 1);
   const int c = blockIdx.x % (Ch + 1);   // c == Ch -> bias
   const size_t npix = (size_t)N * H * W;
@@ -232,8 +232,8 @@ __device__ __forceinline__ void head_bwd_dw_body(const void* __restrict__ h, int
     __syncthreads();
   }
   if (threadIdx.x == 0) {
-    if (c < Ch) dw[o * Ch + c] = red[0];
-    else db[o] = red[0];
+    float* dst = c < Ch ? dw + o * Ch + c : db + o;
+    *dst = acc_out ? *dst + red[0] : red[0];      // (nint_head_bwd_acc: stored, or added by the output's only writer)
   }
 }
 
@@ -242,8 +242,8 @@ __global__ __launch_bounds__(256) void head_bwd_dw_kernel(const void* __restrict
                                                           int O, const float* __restrict__ dpred,
                                                           const float* __restrict__ dlast, int Bs, int T,
                                                           float* __restrict__ dw, float* __restrict__ db, int H, int W,
-                                                          int P, int Hh, int Wh) {
-  head_bwd_dw_body<DT>(h, n0, N, Ch, Chp, O, head_dp<SEQ>(dpred, dlast, O, Bs, T, (size_t)H * W), dw, db, H, W, P, Hh, Wh);
+                                                          int P, int Hh, int Wh, int acc_out) {
+  head_bwd_dw_body<DT>(h, n0, N, Ch, Chp, O, head_dp<SEQ>(dpred, dlast, O, Bs, T, (size_t)H * W), dw, db, H, W, P, Hh, Wh, acc_out);
 }
 
 // Tiled path (O*(Ch+1) <= HEAD_DW_NK*512 outputs): every workgroup owns a pixel range, stages `stage` pixels of dpred and
@@ -428,7 +428,7 @@ __global__ __launch_bounds__(512) void head_bwd_dw_rtile_kernel(const void* __re
 
 // block = 64 outputs x blockDim/64 lanes over the per-workgroup partials; fixed order
 __global__ void head_bwd_dw_final_kernel(const float* __restrict__ partial, int nblocks, int Ch, int O,
-                                         float* __restrict__ dw, float* __restrict__ db) {
+                                         float* __restrict__ dw, float* __restrict__ db, int acc_out) {
   __shared__ float red[1024];
   const int i = blockIdx.x * 64 + (threadIdx.x & 63), sub = threadIdx.x >> 6, G = blockDim.x >> 6;
   const int nout = O * (Ch + 1);
@@ -442,8 +442,8 @@ __global__ void head_bwd_dw_final_kernel(const float* __restrict__ partial, int 
   if (sub != 0 || i >= nout) return;
   for (int q = 1; q < G; ++q) s += red[q * 64 + (threadIdx.x & 63)];
   const int o = i / (Ch + 1), c = i % (Ch + 1);
-  if (c < Ch) dw[o * Ch + c] = s;
-  else db[o] = s;
+  float* dst = c < Ch ? dw + o * Ch + c : db + o;
+  *dst = acc_out ? *dst + s : s;                  // (nint_head_bwd_acc: stored, or added by the output's only writer)
 }
 
 // SEQ: the sequence entry (n0 = Bs = B, N = T*B, plane blocks b*T + t)
@@ -496,7 +496,7 @@ extern "C" int nint_head_fwd_seq(const void* h_slab, int B, int T, int Ch, int C
 // SEQ: d loss / d (head output) comes from the sequence tensors (DpSeq: dpred = dseq, dlast, Bs = B, T) instead of dpred alone
 template <bool SEQ>
 static int head_bwd_impl(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w, const float* dpred,
-                         const float* dlast, int Bs, int T, void* dh, float* dw, float* db, const nint_geom* g, int dtype,
+                         const float* dlast, int Bs, int T, void* dh, float* dw, float* db, int acc, const nint_geom* g, int dtype,
                          float* scratch, size_t scratch_bytes, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   const size_t npix = (size_t)N * g->H * g->W;
@@ -553,31 +553,45 @@ static int head_bwd_impl(const void* h_slab, int n0, int N, int Ch, int Chp, int
       hipLaunchKernelGGL(kern, dim3(nblk), dim3(512), lds, st, h_slab, n0, N, Ch, Chp, O, dpred, dlast, Bs, T, scratch, g->H, g->W, g->P, g->Hh, g->Wh, stage);
     });
     NINT_LAUNCH_CHECK();
-    hipLaunchKernelGGL(head_bwd_dw_final_kernel, dim3(nint_cdiv(nout, 64)), dim3(1024), 0, st, scratch, nblk, Ch, O, dw, db);
+    hipLaunchKernelGGL(head_bwd_dw_final_kernel, dim3(nint_cdiv(nout, 64)), dim3(1024), 0, st, scratch, nblk, Ch, O, dw, db, acc);
   } else {
     nint_by_dtype(dtype, [&](auto dt) {
-      hipLaunchKernelGGL((head_bwd_dw_kernel<decltype(dt)::value, SEQ>), dim3(O * (Ch + 1)), dim3(256), 0, st, h_slab, n0, N, Ch, Chp, O, dpred, dlast, Bs, T, dw, db, g->H, g->W, g->P, g->Hh, g->Wh);
+      hipLaunchKernelGGL((head_bwd_dw_kernel<decltype(dt)::value, SEQ>), dim3(O * (Ch + 1)), dim3(256), 0, st, h_slab, n0, N, Ch, Chp, O, dpred, dlast, Bs, T, dw, db, g->H, g->W, g->P, g->Hh, g->Wh, acc);
     });
   }
   NINT_LAUNCH_CHECK();
   return NINT_OK;
 }
 
+extern "C" int nint_head_bwd_acc(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w,
+                                 const float* dpred, void* dh, float* dw, float* db, int accumulate, const nint_geom* g, int dtype,
+                                 float* scratch, size_t scratch_bytes, void* stream) {
+  if (!h_slab || !w || !dpred || !g || N <= 0 || O <= 0 || Ch <= 0) return NINT_E_ARG;
+  if (dtype != NINT_BF16 && dtype != NINT_F32) return NINT_E_ARG;
+  if (accumulate != 0 && accumulate != 1) return NINT_E_ARG;
+  return head_bwd_impl<false>(h_slab, n0, N, Ch, Chp, O, w, dpred, nullptr, 0, 0, dh, dw, db, accumulate, g, dtype, scratch, scratch_bytes, stream);
+}
+
 extern "C" int nint_head_bwd(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w,
                              const float* dpred, void* dh, float* dw, float* db, const nint_geom* g, int dtype,
                              float* scratch, size_t scratch_bytes, void* stream) {
-  if (!h_slab || !w || !dpred || !g || N <= 0 || O <= 0 || Ch <= 0) return NINT_E_ARG;
-  if (dtype != NINT_BF16 && dtype != NINT_F32) return NINT_E_ARG;
-  return head_bwd_impl<false>(h_slab, n0, N, Ch, Chp, O, w, dpred, nullptr, 0, 0, dh, dw, db, g, dtype, scratch, scratch_bytes, stream);
+  return nint_head_bwd_acc(h_slab, n0, N, Ch, Chp, O, w, dpred, dh, dw, db, 0, g, dtype, scratch, scratch_bytes, stream);
+}
+
+extern "C" int nint_head_bwd_seq_acc(const void* h_slab, int B, int T, int Ch, int Chp, int O, const float* w, const float* dseq,
+                                     const float* dpred_last, void* dh_seq, float* dw, float* db, int accumulate, const nint_geom* g,
+                                     int dtype, float* scratch, size_t scratch_bytes, void* stream) {
+  if (!head_seq_args_ok(h_slab, B, T, Ch, Chp, O, w, g, dtype)) return NINT_E_ARG;
+  if ((!dseq && !dpred_last) || (!dw) != (!db) || (!dh_seq && !dw)) return NINT_E_ARG;
+  if (accumulate != 0 && accumulate != 1) return NINT_E_ARG;
+  if (((((uintptr_t)h_slab) | ((uintptr_t)dh_seq)) & 15) != 0) return NINT_E_ALIGN;
+  return head_bwd_impl<true>(h_slab, B, T * B, Ch, Chp, O, w, dseq, dpred_last, B, T, dh_seq, dw, db, accumulate, g, dtype, scratch, scratch_bytes, stream);
 }
 
 extern "C" int nint_head_bwd_seq(const void* h_slab, int B, int T, int Ch, int Chp, int O, const float* w, const float* dseq,
                                  const float* dpred_last, void* dh_seq, float* dw, float* db, const nint_geom* g, int dtype,
                                  float* scratch, size_t scratch_bytes, void* stream) {
-  if (!head_seq_args_ok(h_slab, B, T, Ch, Chp, O, w, g, dtype)) return NINT_E_ARG;
-  if ((!dseq && !dpred_last) || (!dw) != (!db) || (!dh_seq && !dw)) return NINT_E_ARG;
-  if (((((uintptr_t)h_slab) | ((uintptr_t)dh_seq)) & 15) != 0) return NINT_E_ALIGN;
-  return head_bwd_impl<true>(h_slab, B, T * B, Ch, Chp, O, w, dseq, dpred_last, B, T, dh_seq, dw, db, g, dtype, scratch, scratch_bytes, stream);
+  return nint_head_bwd_seq_acc(h_slab, B, T, Ch, Chp, O, w, dseq, dpred_last, dh_seq, dw, db, 0, g, dtype, scratch, scratch_bytes, stream);
 }
 
 // ------------------------------------------------------------------------------ loss

@@ -283,7 +283,7 @@ struct ReduceEntry {
   int waves;                                // waves that share the splits of one 64-element line (the others exit)
   unsigned blk_begin;                       // first workgroup of this (layer, source) in the merged launch
 };
-struct ReduceTable { ReduceEntry e[2 * NINT_MAX_LAYERS]; int n; };
+struct ReduceTable { ReduceEntry e[2 * NINT_MAX_LAYERS]; int n; int acc; };   // acc (nint_seq.accumulate): 1 = dW / db += the sum
 // The weight / bias gradients of jobs[0..n), planned: per job ONE launch (both sources merged) or two (x, then h) into consecutive
 // regions of `partial`, and one fold of every split-K slab of every job into its dW and db.
 struct WgLaunch { const void* kern; int gx, gy, block; size_t lds; WgradArgs a; };   // kern: host handle of the wgrad[_wide]_kernel<...> instantiation

@@ -259,6 +259,7 @@ static int bwd_check(const nint_seq* s) {
     if (!s->gates[l] || !s->dG[l] || !s->dh[l] || !s->dc[l] || !s->dW[l] || !s->db[l]) return NINT_E_ARG;
   if ((s->need_dx && !s->dx) || !s->wg_partial) return NINT_E_ARG;
   if (s->fuse_bwd < 0 || (s->fuse_bwd > 2 && !(s->fuse_bwd & 0x40000000)) || s->bwd_parts < 0 || s->bwd_parts > 2) return NINT_E_ARG;
+  if (s->accumulate != 0 && s->accumulate != 1) return NINT_E_ARG;     // stored or added (nint.h); no other value is a mode
   if ((((uintptr_t)s->dh_seq) & 15) != 0) return NINT_E_ALIGN;
   return NINT_OK;
 }
@@ -436,6 +437,7 @@ struct BwdPlanner {
     WgJobPlan jp[NINT_MAX_LAYERS]; WgFoldPlan fold;
     const int rc = nint_internal_wgrad_plan(jobs + j0, j1 - j0, &s->g, s->dtype, s->wg_partial, s->wg_partial_bytes, s->n_cu, jp, &fold);
     if (rc != NINT_OK) return rc;
+    fold.t.acc = s->accumulate;                  // the fold's one write per element stores or adds (nint_seq.accumulate)
     for (int q = 0; q < j1 - j0; ++q) push(out, STEP_WGRAD, NINT_PROBE_WGRAD, q, 0).wg = jp[q];
     push(out, STEP_FOLD, NINT_PROBE_FOLD, 0, 0).fold = fold;
     return NINT_OK;

@@ -541,6 +541,7 @@ __global__ __launch_bounds__(512, 2) void wgrad_wide_kernel(WgradArgs a) {
 // elements of the slab layout [block][j][n'loc 64][c 16] (one 256-byte line per split, fully coalesced) and
 // spreads the splits over its blockDim/64 waves; the per-wave sums are folded through LDS.  The order is a
 // fixed function of the launch shape (bitwise reproducible); only the single write per weight is scattered.
+// t.acc (nint_seq.accumulate): that write is dW = dW + sum instead of dW = sum -- the same thread, the same sum.
 __global__ void wgrad_reduce_kernel(ReduceTable t) {
   __shared__ f32x4_t red[1024];
   int ei = 0;
@@ -576,7 +577,7 @@ __global__ void wgrad_reduce_kernel(ReduceTable t) {
   const int ch = (np >> 6) * 16 + (np & 15), gate = (np >> 4) & 3;
   const int JR = JG - (E.db ? 1 : 0);                 // real columns per group
   if (jl >= JR) {                                     // the bias-gradient column (all 16 "channels" hold the same sum)
-    if (cb == 0 && tgi == TG - 1 && c16 == 0 && ch < Ch) E.db[gate * Ch + ch] = s[0];
+    if (cb == 0 && tgi == TG - 1 && c16 == 0 && ch < Ch) E.db[gate * Ch + ch] = t.acc ? E.db[gate * Ch + ch] + s[0] : s[0];
     return;
   }
   const int j = tgi * JR + jl;
@@ -595,7 +596,8 @@ __global__ void wgrad_reduce_kernel(ReduceTable t) {
     }
     if (cc >= Csrc) continue;                         // padding columns
     const int ic = is_h ? Cx + cc : cc;
-    dW[(((size_t)(gate * Ch + ch)) * Ctot + ic) * taps + tap] = s[e];
+    float* dst = dW + (((size_t)(gate * Ch + ch)) * Ctot + ic) * taps + tap;
+    *dst = t.acc ? *dst + s[e] : s[e];                  // (nint_seq.accumulate: one f32 add by the element's only writer)
   }
 }
 

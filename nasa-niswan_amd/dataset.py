@@ -29,7 +29,7 @@ channels-last input slab -- no f32 intermediate, no pack pass."""
 from __future__ import annotations
 
 import ctypes as C
-from typing import Sequence, Tuple
+from typing import Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -47,11 +47,19 @@ class SlabBatch:
     slab with ONE launch of the fuse/z-score/halo-pad kernel.  Quacks like the (B,T,C,Hp,Wp) tensor where the
     trainer only needs the shape."""
 
-    def __init__(self, ds: "SyntheticE33OMA_CRNN", t0: np.ndarray):
+    def __init__(self, ds: "SyntheticE33OMA_CRNN", t0: np.ndarray, T: Optional[int] = None):
         self.ds, self.t0 = ds, np.asarray(t0, dtype=np.int32)
         Hp, Wp = ds.padding if ds.padding else ds.grid
-        self.shape = (len(self.t0), ds.seq_len, ds.in_channels, Hp, Wp)
+        self.shape = (len(self.t0), ds.seq_len if T is None else int(T), ds.in_channels, Hp, Wp)
         self.device = ds.device
+
+    def segment(self, t0: int, S: int) -> "SlabBatch":
+        """Steps [t0, t0 + S) of every window as a batch of its own (FusedTrainer(bptt_segments=n)): the record is resident, so
+        a sub-window is the same kernel from a later start -- its slab equals images [t0*B, (t0+S)*B) of the whole batch's."""
+        t0, S = int(t0), int(S)
+        if t0 < 0 or S < 1 or t0 + S > self.shape[1]:
+            raise ValueError(f"SlabBatch.segment: steps [{t0}, {t0 + S}) outside the window of {self.shape[1]} steps")
+        return SlabBatch(self.ds, self.t0 + t0, S)
 
     def fill_slab(self, eng, ws):
         ds = self.ds

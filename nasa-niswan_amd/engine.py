@@ -301,6 +301,7 @@ class SeqEngine:
                 ws.in_use = True
                 ws.gen += 1
                 ws.seq.probe, ws.seq.probe_mask, ws.seq.probe_slots = None, 0, 0     # (a trainer's timing probes do not outlive its step)
+                ws.seq.has_init_state = int(has_init)                                # (nor does a zero_start)
                 return ws
         ws = Workspace(self, B, T, H, W, train, has_init)
         for l, ly in enumerate(self.layers):
@@ -391,6 +392,15 @@ class SeqEngine:
             raise ValueError("load_state needs a workspace acquired with has_init=True (others start from the zero state)")
         self.check_state(state, ws.B, ws.H, ws.W)
         self._state_copy(self._slot_ptrs(ws, 0), state._ptrs(), ws.B, ws.B, None, ws.g)
+
+    def zero_start(self, ws: Workspace, on: bool):
+        """A has_init workspace whose slot 0 holds the ZERO state runs its following passes as a zero-state window (``on``) --
+        the first step skips the h half of K, BPTT writes no dL/dh_init and the weight gradient skips the zero h source: the
+        launches and the bits of a has_init=False workspace, which an explicit all-zero state does not give
+        -- or from the state in slot 0 again (off).  The segments of one window share a workspace this way (trainer.py)."""
+        if not ws.key[5]:
+            raise ValueError("zero_start needs a workspace acquired with has_init=True")
+        ws.seq.has_init_state = 0 if on else 1
 
     def save_state(self, ws: Workspace, state: Optional[ConvLSTMState] = None) -> ConvLSTMState:
         """slot T of a workspace (h_{T-1}, c_{T-1} of every layer after forward) -> `state` (a new one if None): one launch"""
@@ -515,18 +525,20 @@ class SeqEngine:
         return seq
 
     def head_backward_seq(self, ws: Workspace, w: torch.Tensor, dseq: Optional[torch.Tensor], dpred: Optional[torch.Tensor] = None,
-                          dw_out=None, db_out=None, write_dh: bool = True):
+                          dw_out=None, db_out=None, write_dh: bool = True, accumulate: bool = False):
         """Head backward over every step (nint_head_bwd_seq): dseq (B, T*O, H, W) and / or dpred (B, O, H, W), the cotangent
         of pred = head(h_{T-1}), which joins step T-1.  Writes the per-step dL/dh into ws.dh_seq_slab() (unless `write_dh` is
-        False) for backward(..., seq_grads=True); returns (dw_head, db_head)."""
+        False) for backward(..., seq_grads=True); returns (dw_head, db_head).  ``accumulate``: as in head_backward."""
+        self._check_accumulate(accumulate, dw_out, db_out)
         Ch, Chp, O, w2, _ = self._head_args(w, None)
         ds = None if dseq is None else dseq.detach().float().contiguous()
         dp = None if dpred is None else dpred.detach().float().contiguous()
         dw = dw_out if dw_out is not None else torch.empty(O, Ch, dtype=torch.float32, device=self.device)
         db = db_out if db_out is not None else torch.empty(O, dtype=torch.float32, device=self.device)
-        check(self.lib.nint_head_bwd_seq(ptr(ws.h[-1]), ws.B, ws.T, Ch, Chp, O, ptr(w2), ptr(ds), ptr(dp),
-                                         ptr(ws.dh_seq_slab(self)) if write_dh else None, ptr(dw), ptr(db), C.byref(ws.g), self.dt,
-                                         ptr(self.wg_partial), self.wg_partial.numel() * 4, stream_ptr()), "nint_head_bwd_seq")
+        check(self.lib.nint_head_bwd_seq_acc(ptr(ws.h[-1]), ws.B, ws.T, Ch, Chp, O, ptr(w2), ptr(ds), ptr(dp),
+                                             ptr(ws.dh_seq_slab(self)) if write_dh else None, ptr(dw), ptr(db), int(accumulate),
+                                             C.byref(ws.g), self.dt, ptr(self.wg_partial), self.wg_partial.numel() * 4, stream_ptr()),
+              "nint_head_bwd_seq_acc")
         return dw.view(O, Ch, 1, 1), db
 
     def head_loss_seq_fused(self, ws: Workspace, w: torch.Tensor, b: Optional[torch.Tensor], y: torch.Tensor, dpred: torch.Tensor,
@@ -600,26 +612,34 @@ class SeqEngine:
               "nint_head_skill_accum")
         return sample
 
+    @staticmethod
+    def _check_accumulate(accumulate, *outs):
+        if accumulate and any(o is None for o in outs):
+            raise ValueError("accumulate=True adds to the destinations: pass them (dW_out / db_out, dw_out / db_out)")
+
     def head_backward(self, ws: Workspace, w: torch.Tensor, dpred: torch.Tensor, dw_out=None, db_out=None, write_dh: bool = True,
-                      images: Optional[Tuple[int, int]] = None):
+                      images: Optional[Tuple[int, int]] = None, accumulate: bool = False):
         """Writes dL/dh_{T-1} of the last layer into ws.dh[-1] (unless `write_dh` is False: the fused head/loss pass
         already did); returns (dw_head, db_head).  `images` = (first image, count) of the h slab that `dpred` (count, O, H, W)
-        belongs to: default the last step's B; (B, T*B) reduces every step's (the fused sequence pass, write_dh False)."""
+        belongs to: default the last step's B; (B, T*B) reduces every step's (the fused sequence pass, write_dh False).
+        ``accumulate`` (nint_head_bwd_acc): dw_out / db_out (required then) receive old + gradient, one f32 add per element,
+        instead of being overwritten -- the micro-batches of one optimizer step sum into the bucket."""
+        self._check_accumulate(accumulate, dw_out, db_out)
         n0, N = images if images is not None else (ws.T * ws.B, ws.B)
         assert images is None or not write_dh
         Ch, Chp, O, w2, _ = self._head_args(w, None)
         dp = dpred.detach().float().contiguous()
         dw = dw_out if dw_out is not None else torch.empty(O, Ch, dtype=torch.float32, device=self.device)
         db = db_out if db_out is not None else torch.empty(O, dtype=torch.float32, device=self.device)
-        check(self.lib.nint_head_bwd(ptr(ws.h[-1]), n0, N, Ch, Chp, O, ptr(w2), ptr(dp),
-                                     ptr(ws.dh[-1]) if write_dh else None,
-                                     ptr(dw), ptr(db), C.byref(ws.g), self.dt, ptr(self.wg_partial),
-                                     self.wg_partial.numel() * 4, stream_ptr()), "nint_head_bwd")
+        check(self.lib.nint_head_bwd_acc(ptr(ws.h[-1]), n0, N, Ch, Chp, O, ptr(w2), ptr(dp),
+                                         ptr(ws.dh[-1]) if write_dh else None,
+                                         ptr(dw), ptr(db), int(accumulate), C.byref(ws.g), self.dt, ptr(self.wg_partial),
+                                         self.wg_partial.numel() * 4, stream_ptr()), "nint_head_bwd_acc")
         return dw.view(O, Ch, 1, 1), db
 
     def backward(self, ws: Workspace, need_dx: bool, zero_state_grads: Sequence[int] = (),
                  dW_out: Optional[Sequence[torch.Tensor]] = None, db_out: Optional[Sequence[torch.Tensor]] = None, parts: int = 0,
-                 seq_grads: bool = False, zero_mask: Optional[int] = None):
+                 seq_grads: bool = False, zero_mask: Optional[int] = None, accumulate: bool = False):
         """BPTT of model.py:253-271.  Precondition: ws.dh[l], ws.dc[l] hold dL/dh_{T-1}, dL/dc_{T-1}
         (layers listed in ``zero_state_grads`` start from zero state gradients instead).  Returns ([dW_l], [db_l], dx or None).
         ``dW_out`` / ``db_out``: f32 contiguous destinations (e.g. views of a flat gradient bucket).
@@ -627,8 +647,13 @@ class SeqEngine:
         bias gradient only, after a parts = 1 call on the same workspace (the trainer starts the all-reduce of the rest of the
         bucket in between).
         ``seq_grads`` (nint_seq.dh_seq): the top layer's dL/dh_t of every step is in ws.dh_seq_slab() (head_backward_seq /
-        head_loss_seq_fused) and joins the recurrence at each t; ws.dh[-1] is then not read on entry."""
+        head_loss_seq_fused) and joins the recurrence at each t; ws.dh[-1] is then not read on entry.
+        ``accumulate`` (nint_seq.accumulate): every dW / db element this call produces is written as old + gradient (one f32
+        add by the element's one writer, bitwise reproducible) into ``dW_out`` / ``db_out``, which are required then.  With
+        ``zero_state_grads=()`` on a has_init workspace, ws.dh[l] / ws.dc[l] as the previous call left them are the entry
+        gradients: a window runs as segments, last to first, through ONE workspace and sums into one bucket (trainer.py)."""
         assert ws.train
+        self._check_accumulate(accumulate, dW_out, db_out)
         # layers in ``zero_state_grads`` start BPTT from zero dL/dh, dL/dc: flagged, not filled (the first BPTT step
         # then neither reads dc nor accumulates into dh).  The top layer's dh always holds the head's gradient.
         L = len(self.cfgs)
@@ -658,11 +683,13 @@ class SeqEngine:
         s.need_dx = int(need_dx)
         s.bwd_parts = int(parts)
         s.dh_seq = ws.dh_seq_slab(self).data_ptr() if seq_grads else None
+        s.accumulate = int(bool(accumulate))
         try:
             check(self.lib.nint_seq_bwd(C.byref(s), stream_ptr()), "nint_seq_bwd")
         finally:
             s.bwd_parts = 0
             s.dh_seq = None
+            s.accumulate = 0
         s.dx = None
         dx_out = None
         if need_dx:

@@ -6,7 +6,7 @@ stepped once per epoch before validation, checkpoint every 10 epochs); the per-b
 `loss.item()` / sklearn R2 host syncs (train.py:113-114) are replaced by device accumulators read
 once per epoch.  Added flags: --dtype, --levels, --grid, --synthetic-steps, --pad-mode, --f32-inputs,
 --static-channels, --sequence-loss, --test-skill, --lat-weighted-loss, --loss-weights, --clip-grad-norm,
---skip-nonfinite-steps, --stateful.
+--skip-nonfinite-steps, --stateful, --bptt-segments, --accumulate-steps.
 
 The data path is on the device too: by default every batch is written by ONE launch of the
 fuse / z-score / halo-pad kernel straight into the model's bf16 input slab (dataset.slab_batch);
@@ -97,6 +97,14 @@ def get_arguments(argv=None, MODEL='LSTM-00', SPECIES='bcb', LEARNING_RATE=1.0E-
                              "period in consecutive NON-overlapping chunks of --sequence-length steps (dataset.stateful_schedule, "
                              "no shuffle), each chunk starting from the state the lane's previous chunk ended in; the state is reset "
                              "at the start of every epoch.  A record step is then run once per epoch, not --sequence-length times")
+    parser.add_argument("--bptt-segments", type=int, default=None, metavar="N",
+                        help="checkpointed BPTT: run every window as N equal segments of --sequence-length / N steps through one "
+                             "training workspace of that length, recomputing each segment's forward pass before its backward: the "
+                             "gradient of the whole window with 1/N of the per-step slabs resident, for (N-1)/N of a forward "
+                             "pass more.  N must divide --sequence-length; not with --sequence-loss")
+    parser.add_argument("--accumulate-steps", type=int, default=1, metavar="K",
+                        help="gradient accumulation: one optimizer step (and one all-reduce) per K batches, on their mean gradient; "
+                             "a group left unfinished at the end of an epoch goes on in the next")
     args = parser.parse_args(argv)
     rank = int(os.environ.get("RANK", "0"))
     if rank == 0:
@@ -159,7 +167,8 @@ def main(args):
         loss_weights = m if loss_weights is None else (loss_weights.astype(np.float64) * m).astype(np.float32)
     trainer = FusedTrainer(generator, lr=args.learning_rate, betas=tuple(args.betas), halo=halo,        # train.py:71
                            sequence_loss=args.sequence_loss, loss_weights=loss_weights,
-                           max_grad_norm=args.clip_grad_norm, skip_nonfinite=args.skip_nonfinite_steps, stateful=args.stateful)
+                           max_grad_norm=args.clip_grad_norm, skip_nonfinite=args.skip_nonfinite_steps, stateful=args.stateful,
+                           bptt_segments=args.bptt_segments, accumulate_steps=args.accumulate_steps)
     if args.stateful:
         # one schedule of world * batch lanes, the same every epoch; each rank takes its own columns and carries its own state
         sched, dropped = stateful_schedule(len(train_dataset), args.sequence_length, world * args.batch_size)

@@ -12,12 +12,18 @@
     optimizer.step()                        -> nint_adam_flat (1/world folded in); with ``max_grad_norm`` / ``skip_nonfinite``
                                                nint_adam_flat_guarded: norm, clipping and the skip decided on the device
     loss.item(); r2_score(...cpu())         -> device-side accumulators, read once per epoch
+    [bptt_segments = n]                     -> the window runs as n segments of S = T/n steps through ONE S-step training
+                                               workspace: a forward sweep that keeps the state at every segment start, then
+                                               per segment, last to first, recompute + nint_seq_bwd with accumulate = 1 -- the
+                                               full-window gradient at 1/n of the resident slabs
+    [accumulate_steps = k]                  -> k micro-batches add into the bucket (accumulate = 1 from the second on); the
+                                               all-reduce and ONE Adam launch with grad_scale = 1/(k world) on the k-th
 
 No autograd graph, no per-kernel Python, no host synchronisation inside the step."""
 from __future__ import annotations
 
 import ctypes as C
-from typing import Optional, Tuple
+from typing import List, Optional, Tuple
 
 import torch
 
@@ -28,14 +34,46 @@ from .loss import DeviceWeights
 from .optim import FlatParams, FusedAdam
 
 
+def segment_plan(T: int, n: int) -> List[Tuple[int, int]]:
+    """The segments of checkpointed BPTT: [(t0, S)] for a window of T steps in n equal segments of S = T / n steps, in time
+    order.  ValueError when n < 1 or n does not divide T (one workspace shape serves every segment).  Pure."""
+    T, n = int(T), int(n)
+    if n < 1:
+        raise ValueError(f"bptt_segments must be >= 1, got {n}")
+    if T < 1 or T % n:
+        raise ValueError(f"bptt_segments = {n} does not divide the window of T = {T} steps (equal segments only)")
+    S = T // n
+    return [(j * S, S) for j in range(n)]
+
+
 class FusedTrainer:
     def __init__(self, model: ConvLSTM, lr: float = 1e-3, betas=(0.5, 0.999), eps: float = 1e-8,
                  halo: Tuple[int, int] = (5, 5), process_group=None, distributed: Optional[bool] = None,
                  overlap_allreduce: bool = False, sequence_loss: bool = False, loss_weights=None,
-                 max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False, stateful: bool = False):
+                 max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False, stateful: bool = False,
+                 bptt_segments: Optional[int] = None, accumulate_steps: int = 1):
         dev = next(model.parameters()).device
         if dev.type != "cuda":
             raise _lib.NintError("FusedTrainer needs the model on the MI355X (cuda)")
+        # Checkpointed BPTT: step() runs its window as `bptt_segments` equal segments through one training workspace of
+        # T / bptt_segments steps (the full-window gradient; None or 1: the whole window resident, today's path)
+        if bptt_segments is not None:
+            bptt_segments = int(bptt_segments)
+            segment_plan(bptt_segments, bptt_segments)           # (n >= 1)
+            if bptt_segments > 1 and sequence_loss:
+                raise ValueError("bptt_segments with sequence_loss is not supported: the sequence loss's normaliser and per-call "
+                                 "statistics are per window, not per segment")
+            if bptt_segments > 1 and overlap_allreduce:
+                raise ValueError("bptt_segments with overlap_allreduce is not supported: layer 0's slice of the bucket is final "
+                                 "only after the first segment's backward, so there is nothing to overlap the exchange with")
+        self.bptt_segments = bptt_segments
+        # Gradient accumulation: the optimizer steps once per `accumulate_steps` calls of step(), on the sum of their buckets
+        # scaled by 1 / (accumulate_steps * world): the mean gradient of the group
+        self.accumulate_steps = int(accumulate_steps)
+        if self.accumulate_steps < 1:
+            raise ValueError(f"accumulate_steps must be >= 1, got {accumulate_steps}")
+        self._micro = 0         # calls of step() since the last optimizer step
+        self._zero = None       # segments: the zero state a stateless window starts from
         self.model = model
         self.device = dev
         self.flat = FlatParams(model)
@@ -87,6 +125,9 @@ class FusedTrainer:
         """In-step timing probes (nint_seq.probe, include/nint.h): `buf` = int64/uint64 device tensor of 2*slots words that
         the following step() calls fill with {tag, 100 MHz timestamp} pairs around every launch whose kind is in `mask`;
         None switches them off.  Diagnostic: bench.py prices the kernels INSIDE the step with it."""
+        if buf is not None and (self.bptt_segments or 1) > 1:
+            raise ValueError("set_probe with bptt_segments is not supported: a probe buffer holds the slots of one forward and "
+                             "one backward pass, a segmented step runs several of each")
         self._probe = (buf, int(mask) if buf is not None else 0)
 
     def set_loss_weights(self, weights):
@@ -153,10 +194,37 @@ class FusedTrainer:
             st.reset(reset)
         return st
 
+    def _head_pass(self, eng, ws, yv, B, T, O, H, W, Hc, Wc, wts, acc: bool):
+        """head forward + crop + loss + d loss / d pred + dL/dh + the head's weight gradient on the workspace's last h (every
+        h with sequence_loss); `acc`: the head's gradients are added to the bucket (a later micro-batch of a group)"""
+        m, sq = self.model, self.sequence_loss
+        if self._dpred is None or self._dpred.numel() != B * (T if sq else 1) * O * H * W:
+            self._dpred = torch.empty(B * (T if sq else 1), O, H, W, dtype=torch.float32, device=self.device)
+        dpred = self._dpred
+        hk = dict(dw_out=self._dw_head, db_out=self._db_head, accumulate=acc)
+        if sq:
+            # the same over every step: one pass writes the loss, d loss / d pred (image order t*B + b, which the head's
+            # weight-gradient kernels reduce as T*B images) and the per-step dL/dh that BPTT adds at each t
+            fused = eng.head_loss_seq_fused(ws, m.conv.weight, m.conv.bias, yv, dpred, self.scratch, self.stats, self.halo, Hc, Wc, wts)
+            if fused:
+                eng.head_backward(ws, m.conv.weight, dpred, write_dh=False, images=(B, T * B), **hk)
+            else:
+                seq = eng.head_forward_seq(ws, m.conv.weight, m.conv.bias)
+                self._loss(seq, yv, dpred, B, T * O, H, W, Hc, Wc, wts)
+                eng.head_backward_seq(ws, m.conv.weight, dpred.view(B, T * O, H, W), None, **hk)
+        else:
+            # head forward + crop + loss + dpred + dL/dh in one pass; the prediction itself is never materialised
+            fused = eng.head_loss_fused(ws, m.conv.weight, m.conv.bias, yv, dpred, self.scratch, self.stats, self.halo, Hc, Wc, wts)
+            if not fused:
+                pred = eng.head_forward(ws, m.conv.weight, m.conv.bias)
+                self._loss(pred, yv, dpred, B, O, H, W, Hc, Wc, wts)
+            eng.head_backward(ws, m.conv.weight, dpred, write_dh=not fused, **hk)
+
     def step(self, X: torch.Tensor, y: torch.Tensor, reset=None) -> torch.Tensor:
-        """One optimisation step; returns the loss as a 0-dim DEVICE tensor (no sync).  X: (B,T,C,Hp,Wp) f32 or a
+        """One call of the fit loop; returns the loss as a 0-dim DEVICE tensor (no sync).  X: (B,T,C,Hp,Wp) f32 or a
         dataset.SlabBatch.  y: (B,[O,]Hc,Wc), or (B,T,[O,]Hc,Wc) with ``sequence_loss``.
-        ``reset`` (stateful trainers only): True, or one boolean per lane -- those lanes start this chunk from the zero state."""
+        ``reset`` (stateful trainers only): True, or one boolean per lane -- those lanes start this chunk from the zero state.
+        With ``accumulate_steps = k`` the optimizer steps on every k-th call, on the mean gradient of the k calls."""
         m = self.model
         eng = m._engine(self.device)
         B, T, _, H, W = X.shape
@@ -164,12 +232,28 @@ class FusedTrainer:
         wts = self._loss_weights(y.shape[-2], y.shape[-1])      # (validates the map's shape before anything is acquired)
         if reset is not None and not self.stateful:
             raise ValueError("step(reset=...) needs FusedTrainer(stateful=True)")
+        k = self.accumulate_steps
+        acc, last = self._micro > 0, self._micro == k - 1       # add to the bucket; exchange and step after this call
+        if (self.bptt_segments or 1) > 1:
+            plan = segment_plan(T, self.bptt_segments)          # (before anything is acquired)
+        else:
+            plan = None
         carried = self._carried_state(eng, B, H, W, reset) if self.stateful else None
+        O = m.conv.weight.shape[0]
+        Hc, Wc = y.shape[-2], y.shape[-1]
+        yv = y.detach().float().contiguous()
+        sq = self.sequence_loss
+        assert yv.numel() == B * (T if sq else 1) * O * Hc * Wc, "target must be (B,T,[O,]Hc,Wc)" if sq else "target must be (B,[O,]Hc,Wc)"
+        mark = self._mark
+        if plan is not None:
+            mark()
+            eng.pack_weights([c.conv.weight for c in m.layers], [c.conv.bias for c in m.layers])
+            self._segments(eng, X, yv, plan, carried, acc, wts)
+            return self._finish(last)
         ws = eng.acquire(B, T, H, W, True, self.stateful)
         pb, pm = self._probe
         ws.seq.probe = pb.data_ptr() if pb is not None else None
         ws.seq.probe_mask, ws.seq.probe_slots = pm, (pb.numel() // 2 if pb is not None else 0)
-        mark = self._mark
         mark()
         eng.pack_weights([c.conv.weight for c in m.layers], [c.conv.bias for c in m.layers])
         if carried is not None:
@@ -178,52 +262,88 @@ class FusedTrainer:
         if carried is not None:
             eng.save_state(ws, carried)          # slot T -> carried state; BPTT below stops at the chunk start
         mark()
-        O = m.conv.weight.shape[0]
-        Hc, Wc = y.shape[-2], y.shape[-1]
-        yv = y.detach().float().contiguous()
-        sq = self.sequence_loss
-        assert yv.numel() == B * (T if sq else 1) * O * Hc * Wc, "target must be (B,T,[O,]Hc,Wc)" if sq else "target must be (B,[O,]Hc,Wc)"
-        if self._dpred is None or self._dpred.numel() != B * (T if sq else 1) * O * H * W:
-            self._dpred = torch.empty(B * (T if sq else 1), O, H, W, dtype=torch.float32, device=self.device)
-        dpred = self._dpred
-        if sq:
-            # the same over every step: one pass writes the loss, d loss / d pred (image order t*B + b, which the head's
-            # weight-gradient kernels reduce as T*B images) and the per-step dL/dh that BPTT adds at each t
-            fused = eng.head_loss_seq_fused(ws, m.conv.weight, m.conv.bias, yv, dpred, self.scratch, self.stats, self.halo, Hc, Wc, wts)
-            if fused:
-                eng.head_backward(ws, m.conv.weight, dpred, dw_out=self._dw_head, db_out=self._db_head, write_dh=False, images=(B, T * B))
-            else:
-                seq = eng.head_forward_seq(ws, m.conv.weight, m.conv.bias)
-                self._loss(seq, yv, dpred, B, T * O, H, W, Hc, Wc, wts)
-                eng.head_backward_seq(ws, m.conv.weight, dpred.view(B, T * O, H, W), None, dw_out=self._dw_head, db_out=self._db_head)
-        else:
-            # head forward + crop + loss + dpred + dL/dh in one pass; the prediction itself is never materialised
-            fused = eng.head_loss_fused(ws, m.conv.weight, m.conv.bias, yv, dpred, self.scratch, self.stats, self.halo, Hc, Wc, wts)
-            if not fused:
-                pred = eng.head_forward(ws, m.conv.weight, m.conv.bias)
-                self._loss(pred, yv, dpred, B, O, H, W, Hc, Wc, wts)
-            eng.head_backward(ws, m.conv.weight, dpred, dw_out=self._dw_head, db_out=self._db_head, write_dh=not fused)
+        self._head_pass(eng, ws, yv, B, T, O, H, W, Hc, Wc, wts, acc)
         mark()
-        if self.distributed and self.overlap_allreduce and L > 1 and pb is None:
+        bk = dict(zero_state_grads=range(L), dW_out=self._dW, db_out=self._db, seq_grads=sq, accumulate=acc)
+        if last and self.distributed and self.overlap_allreduce and L > 1 and pb is None:
             n0 = self.flat.offsets[2]              # layers.0.conv.weight + .bias lead the bucket (module parameter order)
-            eng.backward(ws, False, zero_state_grads=range(L), dW_out=self._dW, db_out=self._db, parts=1, seq_grads=sq)
+            eng.backward(ws, False, parts=1, **bk)
             work = self.dist.all_reduce(self.flat.grad[n0:], op=self.dist.ReduceOp.SUM, group=self.pg, async_op=True)
-            eng.backward(ws, False, zero_state_grads=range(L), dW_out=self._dW, db_out=self._db, parts=2, seq_grads=sq)
+            eng.backward(ws, False, parts=2, **bk)
             mark()
             eng.release(ws)
             self.dist.all_reduce(self.flat.grad[:n0], op=self.dist.ReduceOp.SUM, group=self.pg)
             work.wait()                            # (stream-level for RCCL: the step stays asynchronous to the host)
-            self.optimizer.step(grad_scale=1.0 / self.world)
+            self._micro = 0
+            self.optimizer.step(grad_scale=1.0 / (k * self.world))
             mark()
             return self.scratch[0]
-        eng.backward(ws, False, zero_state_grads=range(L), dW_out=self._dW, db_out=self._db, seq_grads=sq)
+        eng.backward(ws, False, **bk)
         mark()
         eng.release(ws)
+        return self._finish(last)
+
+    def _finish(self, last: bool) -> torch.Tensor:
+        """the end of a call: on the last one of a group the ONE all-reduce of the bucket and the optimizer step"""
+        if not last:
+            self._micro += 1
+            return self.scratch[0]
+        self._micro = 0
         if self.distributed:
             self.dist.all_reduce(self.flat.grad, op=self.dist.ReduceOp.SUM, group=self.pg)   # RCCL over xGMI
-        self.optimizer.step(grad_scale=1.0 / self.world)
-        mark()
+        self.optimizer.step(grad_scale=1.0 / (self.accumulate_steps * self.world))
+        self._mark()
         return self.scratch[0]
+
+    def _segments(self, eng, X, yv, plan, carried, acc: bool, wts):
+        """Checkpointed BPTT of one window: the gradients of the whole window into the bucket, with S = T / n
+        steps resident instead of T.
+          1. forward sweep: segments 0 .. n-2 in an S-step inference workspace (no stash, no dG), each from the state the one
+             before left; the state at the start of every segment is kept (B images of h and c per layer each)
+          2. segment n-1 in the S-step training workspace, the head / loss pass on its last h, BPTT from zero state gradients
+             (the bucket is overwritten, or added to for a later micro-batch)
+          3. segments n-2 .. 0: load the segment's start state, recompute its forward with the stash on, BPTT with
+             accumulate = 1; its entry gradients dL/dh, dL/dc are what the call before left in ws.dh / ws.dc -- no copy
+        Segment 0 starts from the zero state, or from the carried one (stateful: gradients still stop at the chunk start, and
+        the carried state becomes the one segment n-1 ended in).  A zero-state segment 0 runs as the whole window's first
+        steps do (SeqEngine.zero_start: the h half of K skipped at t = 0), so every segment's forward pass has the whole
+        window's bits and so has the loss."""
+        m, L, mark = self.model, self.model.num_layers, self._mark
+        B, T, _, H, W = X.shape
+        n, S = len(plan), plan[0][1]
+        seg = (lambda t0: X.segment(t0, S)) if hasattr(X, "segment") else (lambda t0: X[:, t0:t0 + S])
+        if carried is not None:
+            start = carried
+        else:
+            z = self._zero
+            if z is None or z.eng is not eng or (z.B, z.H, z.W) != (B, H, W):
+                z = self._zero = eng.new_state(B, H, W)
+            start = z
+        states = [start]
+        wf = eng.acquire(B, S, H, W, False, True)
+        for t0, _ in plan[:-1]:
+            eng.load_state(wf, states[-1])
+            eng.zero_start(wf, carried is None and t0 == 0)
+            eng.forward(wf, seg(t0))
+            states.append(eng.save_state(wf))        # slot S -> a new state: the start of the next segment
+        eng.release(wf)
+        ws = eng.acquire(B, S, H, W, True, True)
+        eng.load_state(ws, states[-1])
+        eng.forward(ws, seg(plan[-1][0]))
+        if carried is not None:
+            self.state = eng.save_state(ws)          # (a new object: the chunk's start state above stays what it was)
+        mark()
+        O = m.conv.weight.shape[0]
+        self._head_pass(eng, ws, yv, B, S, O, H, W, yv.shape[-2], yv.shape[-1], wts, acc)
+        mark()
+        eng.backward(ws, False, zero_state_grads=range(L), dW_out=self._dW, db_out=self._db, accumulate=acc)
+        for j in range(n - 2, -1, -1):
+            eng.load_state(ws, states[j])
+            eng.zero_start(ws, carried is None and j == 0)
+            eng.forward(ws, seg(plan[j][0]))
+            eng.backward(ws, False, zero_state_grads=(), dW_out=self._dW, db_out=self._db, accumulate=True)
+        mark()
+        eng.release(ws)
 
     def _mark(self):
         """bench.py --phase-events: one HIP event per phase boundary of a step (nothing is recorded unless asked for)"""
