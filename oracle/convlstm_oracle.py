@@ -123,8 +123,12 @@ def head_forward(h, w_head, b_head):
 
 def convlstm_forward(x, params, return_states: bool = False, return_sequence: bool = False,
                      h0: Optional[List[torch.Tensor]] = None, c0: Optional[List[torch.Tensor]] = None,
-                     preact: Optional[Dict[Tuple[int, int], torch.Tensor]] = None):
+                     preact: Optional[Dict[Tuple[int, int], torch.Tensor]] = None, top_h: Optional[list] = None):
     """reference model.py:253-274.  x (B,T,C,H,W) -> (B,out,H,W).
+
+    Returns ``pred``; with ``return_sequence`` ``(pred, seq)``; with ``return_states`` ``(pred, hs, cs)``, the final (h, c)
+    of every layer; with both ``(pred, seq, hs, cs)``.  ``top_h``: a list that receives the top layer's h of every step (what
+    the head reads: the summands of its weight gradient).
 
     ``return_sequence`` restates the commented-out variant (model.py:264,272,274) that
     the analysis notebook was run with (test.ipynb:273): per-step head outputs
@@ -148,9 +152,13 @@ def convlstm_forward(x, params, return_states: bool = False, return_sequence: bo
                 preact[(i, t)] = pa[0]
             hs[i], cs[i] = h, c                                  # model.py:270
             x_t = h                                              # model.py:271
+        if top_h is not None:
+            top_h.append(hs[-1])
         if return_sequence:
             outs.append(head_forward(hs[-1], params["conv.weight"], params["conv.bias"]))  # model.py:272
     pred = head_forward(hs[-1], params["conv.weight"], params["conv.bias"])               # model.py:274
+    if return_sequence and return_states:
+        return pred, torch.cat(outs, dim=1), hs, cs
     if return_sequence:
         return pred, torch.cat(outs, dim=1)
     if return_states:
