@@ -485,6 +485,15 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, char* smem, c
         const size_t rowpix = ((size_t)img * a.H + y) * a.W + xo;   // (a merged tile's second column: 16 pixels on)
         const f32x4_t cp = cpv[i][cb];
         f32x4_t gi, gf, gg, go, cn, hn;
+        // A channel block that reaches past Ch (Ch % 16 != 0: its last block only; a wave-uniform test, never taken where
+        // Ch is a multiple of 16) holds padding columns: zero weights, so 0 with finite data -- and inf * 0 = NaN with an inf
+        // or NaN in the receptive field, which the next step and the layer above would multiply by THEIR zero weights into
+        // every real column.  Their pre-activation is pinned to an exact 0: stash (0.5, 0.5, 0, 0.5), c = 0, h = 0.
+        if (cblock * 16 + 16 > a.Ch) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+            if (ch + r >= a.Ch) acc[i][cb * 4 + 0][r] = acc[i][cb * 4 + 1][r] = acc[i][cb * 4 + 2][r] = acc[i][cb * 4 + 3][r] = 0.f;
+        }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           gi[r] = sigmoidf_(acc[i][cb * 4 + 0][r]);      // (bias already in the accumulator)
@@ -928,7 +937,7 @@ static int cell_fwd(const nint_layer* ly, const nint_geom* g, int dtype, int N,
   a.H = g->H; a.W = g->W; a.P = g->P; a.Hh = g->Hh; a.Wh = g->Wh;
   a.bias = ly->bias_p;
   a.c_prev = c_prev; a.c_out = c_out; a.h_out = (char*)h_out; a.gates_out = (char*)gates_out;
-  a.Chp = ly->Chp; a.Ch16 = ly->Ch16;
+  a.Chp = ly->Chp; a.Ch16 = ly->Ch16; a.Ch = ly->Ch;
   a.tile_rows = ly->tile_rows <= 2 ? 0 : ly->tile_rows;
   if (ly->wide < 0 || ly->wide > 2) return NINT_E_ARG;   // (the weight-gradient family switch: nothing to do with this launch)
   // tiny hidden widths (4*Ch <= 32 gate columns: no dense contraction): the VALU stencil kernel (csrc/stencil.hip) -- on request

@@ -224,6 +224,7 @@ struct ConvArgs {
   char* h_out;           // halo slab, ET
   char* gates_out;       // stash [N][H][W][4*Ch16] ET or nullptr
   int Chp, Ch16;
+  int Ch;                // LSTM epilogue: real hidden channels; the gate columns of channels [Ch, Ch16) are padding (zero weights)
   // DGRAD epilogue
   char* out0;            // += columns [0, C0p)  (ET compact)
   char* out1;            // =  columns [C0p, C0p+C1p)  (ET compact)

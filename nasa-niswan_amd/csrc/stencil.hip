@@ -164,10 +164,12 @@ __global__ __launch_bounds__(256) void stencil_lstm_kernel(StencilArgs a_) {
     f32x4_t gi, gf, gg, go, cn, hn;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      gi[e] = sigmoidf_(acc[c4 + e]);
-      gf[e] = sigmoidf_(acc[8 + c4 + e]);
-      gg[e] = tanhf_(acc[16 + c4 + e]);
-      go[e] = sigmoidf_(acc[24 + c4 + e]);
+      // a padding channel (zero weights) has the pre-activation 0 with finite data and inf * 0 = NaN next to an inf: pinned to 0
+      const bool pad = c4 + e >= Ch;
+      gi[e] = sigmoidf_(pad ? 0.f : acc[c4 + e]);
+      gf[e] = sigmoidf_(pad ? 0.f : acc[8 + c4 + e]);
+      gg[e] = tanhf_(pad ? 0.f : acc[16 + c4 + e]);
+      go[e] = sigmoidf_(pad ? 0.f : acc[24 + c4 + e]);
       cn[e] = fmaf(cp[e], gf[e], gi[e] * gg[e]);       // model.py:228 (same association as conv_igemm.hip)
       hn[e] = go[e] * tanhf_(cn[e]);                   // model.py:229
     }

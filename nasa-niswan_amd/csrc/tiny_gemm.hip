@@ -153,10 +153,12 @@ __global__ __launch_bounds__(256) void tiny_lstm_kernel(TinyArgs a) {
     float gi[2], gf[2], gg[2], go[2], cn[2], hn[2];
 #pragma unroll
     for (int t2 = 0; t2 < 2; ++t2) {
-      gi[t2] = sigmoidf_(acc[r][t2][0]);
-      gf[t2] = sigmoidf_(acc[r][t2][1]);
-      gg[t2] = tanhf_(acc[r][t2][2]);
-      go[t2] = sigmoidf_(acc[r][t2][3]);
+      // a padding channel (zero weights) has the pre-activation 0 with finite data and inf * 0 = NaN next to an inf: pinned to 0
+      const bool pad = ch0 + t2 >= Ch;
+      gi[t2] = sigmoidf_(pad ? 0.f : acc[r][t2][0]);
+      gf[t2] = sigmoidf_(pad ? 0.f : acc[r][t2][1]);
+      gg[t2] = tanhf_(pad ? 0.f : acc[r][t2][2]);
+      go[t2] = sigmoidf_(pad ? 0.f : acc[r][t2][3]);
       cn[t2] = fmaf(t2 ? cp1 : cp0, gf[t2], gi[t2] * gg[t2]);   // model.py:228 (same association as conv_igemm.hip)
       hn[t2] = go[t2] * tanhf_(cn[t2]);                        // model.py:229
     }

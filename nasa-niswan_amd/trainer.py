@@ -8,7 +8,9 @@
     zero_grad; loss.backward()              -> nint_head_bwd + nint_seq_bwd (grads overwrite the bucket)
     [DDP]                                   -> ONE RCCL all-reduce of the flat gradient bucket
     [stateful]                              -> nint_state_copy before the forward pass (carried state -> slot 0) and after it
-                                               (slot T -> carried state): truncated BPTT over consecutive chunks of a record
+                                               (slot T -> carried state): truncated BPTT over consecutive chunks of a record;
+                                               with ``skip_nonfinite`` a lane whose saved state is non-finite is zeroed
+                                               (torch ops on the state buffers, on the device)
     optimizer.step()                        -> nint_adam_flat (1/world folded in); with ``max_grad_norm`` / ``skip_nonfinite``
                                                nint_adam_flat_guarded: norm, clipping and the skip decided on the device
     loss.item(); r2_score(...cpu())         -> device-side accumulators, read once per epoch
@@ -194,6 +196,22 @@ class FusedTrainer:
             st.reset(reset)
         return st
 
+    def _drop_nonfinite_lanes(self, st):
+        """stateful with skip_nonfinite: a lane whose state just saved holds a NaN or inf in any layer's h or c starts the next
+        chunk from the zero state, the other lanes keep their bytes.  Without this the one bad chunk whose
+        optimizer step the guard drops would poison the lane, and with it every later step, until reset_state().  Decided on
+        the device, no host read; a fill, not a product with a mask (NaN * 0 is NaN)."""
+        if not self.optimizer.skip_nonfinite:
+            return
+        et = torch.bfloat16 if st.dtype == "bf16" else torch.float32
+        views = [h.view(et).view(st.B, -1) for h in st.h] + [c.view(st.B, -1) for c in st.c]
+        bad = None
+        for v in views:
+            b = ~torch.isfinite(v).all(dim=1, keepdim=True)
+            bad = b if bad is None else bad | b
+        for v in views:
+            v.masked_fill_(bad, 0)
+
     def _head_pass(self, eng, ws, yv, B, T, O, H, W, Hc, Wc, wts, acc: bool):
         """head forward + crop + loss + d loss / d pred + dL/dh + the head's weight gradient on the workspace's last h (every
         h with sequence_loss); `acc`: the head's gradients are added to the bucket (a later micro-batch of a group)"""
@@ -261,6 +279,7 @@ class FusedTrainer:
         eng.forward(ws, X)
         if carried is not None:
             eng.save_state(ws, carried)          # slot T -> carried state; BPTT below stops at the chunk start
+            self._drop_nonfinite_lanes(carried)
         mark()
         self._head_pass(eng, ws, yv, B, T, O, H, W, Hc, Wc, wts, acc)
         mark()
@@ -332,6 +351,7 @@ class FusedTrainer:
         eng.forward(ws, seg(plan[-1][0]))
         if carried is not None:
             self.state = eng.save_state(ws)          # (a new object: the chunk's start state above stays what it was)
+            self._drop_nonfinite_lanes(self.state)
         mark()
         O = m.conv.weight.shape[0]
         self._head_pass(eng, ws, yv, B, S, O, H, W, yv.shape[-2], yv.shape[-1], wts, acc)
