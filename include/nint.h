@@ -415,6 +415,63 @@ int nint_head_loss_seq_fused_weighted(const void* h_slab, int B, int T, int Ch, 
                                       float* loss_out, double* stats, const nint_geom* g, int oy, int ox, int Hc, int Wc,
                                       int dtype, void* stream);
 
+/* ---- the configurable loss: an MSE / L1 / Huber mix with a weight per output and per step -------------------- */
+/* The twins of the three entries above and of their _weighted forms with the per-element term and weight opened up:
+ *     loss = a * mean_w(d^2) + b * mean_w(|d|) + c * mean_w(H(d)),     H = torch.nn.HuberLoss(delta = delta),
+ * a weighted mean whose weight is the product of the cell's (the map of the _weighted entries, optional) and the output's
+ * (ow, optional; in the sequence entry one weight per (step, output): spin-up steps are discounted or dropped there).
+ * nint_loss_spec is plain data read on the host at the call; ow is read on the device. */
+typedef struct nint_loss_spec {
+  double mse, l1, huber;  /* coefficients a, b, c: finite, >= 0, not all zero */
+  double delta;           /* Huber threshold: finite, > 0 when huber != 0; not read otherwise */
+  const float* ow;        /* device f32 [now], 4-byte aligned: weight per output, finite and >= 0 (the caller validates the
+                           * values); NULL = 1 */
+  int32_t now;            /* 0 with ow == NULL; else O (plain / fused entry) or T*O (sequence entry, index t*O+o) */
+  double osum;            /* f64 sum of ow AS STORED in f32, formed by the caller; not read with ow == NULL */
+} nint_loss_spec;
+/* Per crop element of sample n (sequence entry: of step t of sample b), output o, cell (cy, cx):
+ *   w  = wgt[cy][cx], or 1 without a map (wgt == NULL; wsum is then not read);  q = ow[o] (ow[t*O+o] in the sequence entry),
+ *        or 1 with ow == NULL;  Wd = (double)q * (double)w, exact in f64;  d = p - y in f32, as in the entries above
+ *   cnt    = N * osum * wsum, evaluated left to right in f64 with N as a double (sequence entry with ow: B * osum * wsum).
+ *            Without ow, O stands for osum (sequence entry: (T*B) * O * wsum); without a map, Hc * Wc (an exact integer)
+ *            for wsum: the expressions of the entries above.
+ *   H(d)   = 0.5*d*d if |d| <= delta, else delta*(|d| - 0.5*delta), in f64 from (double)d
+ *   C(d)   = d > delta ? delta : (d < -delta ? -delta : d): dH/dd, written as comparisons so that a NaN d stays NaN
+ *            (fmin / fmax would return delta)
+ *   S2 = sum Wd d^2, S1 = sum Wd |d|, SH = sum Wd H(d): f64, every term joined to its running sum by one fused multiply-add
+ *            fma(Wd, term, S) (so do the entries above), the two-stage fixed-order reduction of those entries with a fifth
+ *            partial for SH; SH is formed only when c != 0
+ *   loss   = a*(S2/cnt) + b*(S1/cnt) + c*(SH/cnt), left to right, each product and sum rounded.  A coefficient that is
+ *            exactly 0 takes its term OUT instead of multiplying it by 0: with b alone an inf prediction gives loss = +inf,
+ *            not 0 * inf = NaN, and a term nobody asked for cannot poison the loss.
+ *   dpred  = (float)(((a*(2.0*d) + b*sgn(d) + c*C(d)) * (1.0/cnt)) * Wd), f64, left to right, each operation rounded (no
+ *            fused multiply-add), terms omitted as in the loss, rounded to f32 once; sgn(0) = sgn(NaN) = 0; +0 outside the crop
+ *   Wd == 0: the element is skipped -- its target is not read (a NaN target is harmless), it enters no sum, dpred = +0
+ *   stats  : [0..4] += S2, S1, sum Wd y, sum Wd y^2, cnt, whatever the coefficients (the R2 needs them); [5] += loss;
+ *            [6] += the weighted R2 of the _weighted entries with Wd for w; [7] += 1
+ * Spec (1, 1, 0) with ow == NULL gives the bits of the unweighted entry (no map) and of the _weighted entry (with one):
+ * loss_out[0], dpred, dh and all eight stats; so does an all-ones ow with osum = O (T*O).  The spec entries always run this
+ * general body; the fused ones are bit-identical to nint_head_fwd[_seq] -> nint_loss_crop_spec -> nint_head_bwd[_seq]
+ * (sequence: N = B, O' = T*O and the same ow).
+ * loss_out: NINT_LOSS_SPEC_SCRATCH_FLOATS floats, 8-byte aligned ([0] = loss, then 5 doubles per workgroup).
+ * Checks before any launch -- NINT_E_ARG: the twin's argument checks; spec == NULL; a coefficient negative or not finite, or
+ * all three zero; huber != 0 with !(delta > 0) or a non-finite delta; ow with now != O (T*O), !(osum > 0) or a non-finite
+ * osum; now != 0 with ow == NULL; a map with !(wsum > 0) or a non-finite wsum.  NINT_E_ALIGN: the twin's alignment checks;
+ * ow not 4-byte aligned.  NINT_E_SHAPE: the fused entries, exactly where their twins return it.  ow and the map are read
+ * from global memory: no LDS on top of the twins'. */
+#define NINT_LOSS_SPEC_SCRATCH_FLOATS 10242
+int nint_loss_crop_spec(const float* pred, const float* y, const float* wgt, double wsum, const nint_loss_spec* spec,
+                        float* dpred, float* loss_out, double* stats, int N, int O, int H, int W, int oy, int ox, int Hc, int Wc,
+                        void* stream);
+int nint_head_loss_fused_spec(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w, const float* b,
+                              const float* y, const float* wgt, double wsum, const nint_loss_spec* spec, float* dpred, void* dh,
+                              float* loss_out, double* stats, const nint_geom* g, int oy, int ox, int Hc, int Wc, int dtype,
+                              void* stream);
+int nint_head_loss_seq_fused_spec(const void* h_slab, int B, int T, int Ch, int Chp, int O, const float* w, const float* b,
+                                  const float* y, const float* wgt, double wsum, const nint_loss_spec* spec, float* dpred,
+                                  void* dh_seq, float* loss_out, double* stats, const nint_geom* g, int oy, int ox, int Hc,
+                                  int Wc, int dtype, void* stream);
+
 /* ---- evaluation: skill sums (test.ipynb:377-385, :462-485, :605, :630, :684-693, :796-803) ------------ */
 /* Everything the analysis notebook derives from the gathered test-period predictions -- one R2 per window, one R2 per grid
  * cell over time, time-mean maps, cos-latitude weighted means -- follows from running f64 sums, formed on the device in one

@@ -15,6 +15,7 @@ NINT_OK, NINT_E_ARG, NINT_E_SHAPE, NINT_E_LDS, NINT_E_ALIGN = 0, -1, -2, -3, -4
 NINT_MAX_LAYERS = 8
 NINT_VERSION = 112     # include/nint.h NINT_VERSION: the library this binding was written against
 NINT_LOSS_SCRATCH_FLOATS = 8194
+NINT_LOSS_SPEC_SCRATCH_FLOATS = 10242     # the _spec loss entries: five doubles per workgroup
 NINT_LOSS_STATS = 8
 NINT_SKILL_PIX, NINT_SKILL_SAMPLE, NINT_SKILL_MAX_N = 5, 8, 64
 NINT_GRAD_NORM_BLOCKS = 256
@@ -54,9 +55,15 @@ class NintLaunchRec(C.Structure):
                                          "strip", "gx", "gy", "nt_begin")]
 
 
+class NintLossSpec(C.Structure):
+    """nint_loss_spec: the configurable loss of the _spec entries (coefficients, Huber threshold, output weights)"""
+    _fields_ = [("mse", C.c_double), ("l1", C.c_double), ("huber", C.c_double), ("delta", C.c_double), ("ow", vp),
+                ("now", C.c_int32), ("osum", C.c_double)]
+
+
 # every symbol include/nint.h declares: name -> (restype, argtypes)
 _I, _SZ, _F, _D = C.c_int, C.c_size_t, C.c_float, C.c_double
-_PG, _PL, _PS = C.POINTER(NintGeom), C.POINTER(NintLayer), C.POINTER(NintSeq)
+_PG, _PL, _PS, _PLS = C.POINTER(NintGeom), C.POINTER(NintLayer), C.POINTER(NintSeq), C.POINTER(NintLossSpec)
 SIGNATURES = {
     "nint_version": (_I, []),
     "nint_error_string": (C.c_char_p, [_I]),
@@ -99,6 +106,9 @@ SIGNATURES = {
     "nint_loss_mse_l1_crop_weighted": (_I, [vp, vp, vp, _D, vp, vp, vp, _I, _I, _I, _I, _I, _I, _I, _I, vp]),
     "nint_head_loss_fused_weighted": (_I, [vp, _I, _I, _I, _I, _I, vp, vp, vp, vp, _D, vp, vp, vp, vp, _PG, _I, _I, _I, _I, _I, vp]),
     "nint_head_loss_seq_fused_weighted": (_I, [vp, _I, _I, _I, _I, _I, vp, vp, vp, vp, _D, vp, vp, vp, vp, _PG, _I, _I, _I, _I, _I, vp]),
+    "nint_loss_crop_spec": (_I, [vp, vp, vp, _D, _PLS, vp, vp, vp, _I, _I, _I, _I, _I, _I, _I, _I, vp]),
+    "nint_head_loss_fused_spec": (_I, [vp, _I, _I, _I, _I, _I, vp, vp, vp, vp, _D, _PLS, vp, vp, vp, vp, _PG, _I, _I, _I, _I, _I, vp]),
+    "nint_head_loss_seq_fused_spec": (_I, [vp, _I, _I, _I, _I, _I, vp, vp, vp, vp, _D, _PLS, vp, vp, vp, vp, _PG, _I, _I, _I, _I, _I, vp]),
     "nint_skill_scratch_bytes": (_SZ, [_I, _I, _I, _I]),
     "nint_skill_accum": (_I, [vp, vp, C.POINTER(C.c_int32), _I, vp, vp, vp, vp, _SZ, _I, _I, _I, _I, _I, _I, _I, _I, vp]),
     "nint_head_skill_accum": (_I, [vp, _I, _I, _I, _I, _I, vp, vp, vp, C.POINTER(C.c_int32), _I, vp, vp, vp, vp, vp, _SZ, _PG,

@@ -932,6 +932,384 @@ extern "C" int nint_head_loss_seq_fused_weighted(const void* h_slab, int B, int 
   return head_loss_fused_impl<true, true>(h_slab, B, T * B, Ch, Chp, O, w, b, y, wgt, (double)(T * B) * O * wsum, dpred, dh_seq, loss_out, stats, g, oy, ox, Hc, Wc, dtype, B, stream);
 }
 
+// ------------------------------------------------------------------------------ the configurable loss (nint_loss_spec)
+// The general per-element body of the three passes above (nint.h has the arithmetic): the term is a * d^2 + b * |d| + c * H(d)
+// with coefficients known at run time, the weight the product of the cell's (optional map) and the output's (optional ow;
+// per (step, output) in the sequence entry).  New kernels beside the old ones: the instances above are what the default step
+// runs and stay as they are.  A zero coefficient takes its term out (flags, not products: 0 * inf is NaN).
+struct LossSpecK {
+  double a, b, c, delta;       // coefficients and the Huber threshold
+  const float* ow;             // weight per output (plain, fused) or per (step, output) (sequence); nullptr: 1
+};
+
+// The running sums join their terms with ONE fused multiply-add each -- what the compiler makes of the loops above
+// (s2 += wd * ((double)d * d) is v_fmac_f64 there), spelled out here so that spec (1, 1, 0) keeps those bits whatever the
+// optimiser does with this body.
+struct LossSpecSums {
+  double s2 = 0, s1 = 0, sy = 0, syy = 0, sh = 0;
+  __device__ __forceinline__ void add(double Wd, float d, float t, double hub) {
+    s2 = __builtin_fma(Wd, (double)d * d, s2);
+    s1 = __builtin_fma(Wd, fabs((double)d), s1);
+    sy = __builtin_fma(Wd, (double)t, sy);
+    syy = __builtin_fma(Wd, (double)t * t, syy);
+    sh = __builtin_fma(Wd, hub, sh);
+  }
+};
+
+// H(d) and d loss / d pred of one live element: f64, left to right, every operation rounded on its own
+__device__ __forceinline__ double loss_spec_huber(const LossSpecK& sp, float df) {
+#pragma clang fp contract(off)
+  if (sp.c == 0.0) return 0.0;
+  const double d = df, ad = fabs(d);
+  return ad <= sp.delta ? (0.5 * d) * d : sp.delta * (ad - 0.5 * sp.delta);
+}
+__device__ __forceinline__ float loss_spec_grad(const LossSpecK& sp, float df, double inv_n, double Wd) {
+#pragma clang fp contract(off)
+  const double d = df;
+  double g = 0.0;
+  bool any = false;
+  if (sp.a != 0.0) { g = sp.a * (2.0 * d); any = true; }
+  if (sp.b != 0.0) {
+    const double t = sp.b * (df > 0.f ? 1.0 : (df < 0.f ? -1.0 : 0.0));
+    g = any ? g + t : t; any = true;
+  }
+  if (sp.c != 0.0) {
+    const double t = sp.c * (d > sp.delta ? sp.delta : (d < -sp.delta ? -sp.delta : d));   // comparisons: a NaN d stays NaN
+    g = any ? g + t : t;
+  }
+  return (float)((g * inv_n) * Wd);
+}
+
+__global__ __launch_bounds__(1024) void loss_spec_partial_kernel(const float* __restrict__ pred, const float* __restrict__ y,
+                                                                float* __restrict__ dpred, double* __restrict__ partial,
+                                                                int N, int O, int H, int W, int oy, int ox, int Hc, int Wc,
+                                                                const float* __restrict__ wgt, double cnt, const LossSpecK sp) {
+  const size_t total = (size_t)N * O * H * W;
+  const double inv_n = 1.0 / cnt;
+  LossSpecSums s;
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int x = i % W;
+    size_t r = i / W;
+    const int yy = r % H;
+    const size_t no = r / H;
+    const int cy = yy - oy, cx = x - ox;
+    float g = 0.f;
+    if (cy >= 0 && cy < Hc && cx >= 0 && cx < Wc) {
+      const float wf = wgt ? wgt[(size_t)cy * Wc + cx] : 1.f;
+      const float qf = sp.ow ? sp.ow[no % (size_t)O] : 1.f;
+      const double Wd = (double)qf * (double)wf;
+      if (Wd != 0.0) {
+        const float t = y[(no * Hc + cy) * Wc + cx];
+        const float d = pred[i] - t;
+        s.add(Wd, d, t, loss_spec_huber(sp, d));
+        g = loss_spec_grad(sp, d, inv_n, Wd);
+      }
+    }
+    if (dpred) dpred[i] = g;
+  }
+  __shared__ double red[5][1024];
+  red[0][threadIdx.x] = s.s2; red[1][threadIdx.x] = s.s1; red[2][threadIdx.x] = s.sy; red[3][threadIdx.x] = s.syy;
+  red[4][threadIdx.x] = s.sh;
+  __syncthreads();
+  for (int st = blockDim.x >> 1; st > 0; st >>= 1) {
+    if ((int)threadIdx.x < st)
+      for (int q = 0; q < 5; ++q) red[q][threadIdx.x] += red[q][threadIdx.x + st];
+    __syncthreads();
+  }
+  if (threadIdx.x < 5) partial[blockIdx.x * 5 + threadIdx.x] = red[threadIdx.x][0];
+}
+
+// loss_final_kernel over five partials per workgroup (the same fold order per sum), and the loss as the configured mix
+__global__ __launch_bounds__(256) void loss_spec_final_kernel(const double* __restrict__ partial, int nblocks, float* __restrict__ loss_out,
+                                                              double* __restrict__ stats, double count, const LossSpecK sp) {
+#pragma clang fp contract(off)
+  __shared__ double red[5][256];
+  for (int q = 0; q < 5; ++q) {
+    double s = 0;
+    for (int b = threadIdx.x; b < nblocks; b += blockDim.x) s += partial[b * 5 + q];
+    red[q][threadIdx.x] = s;
+  }
+  __syncthreads();
+  for (int st = 128; st > 0; st >>= 1) {
+    if ((int)threadIdx.x < st)
+      for (int q = 0; q < 5; ++q) red[q][threadIdx.x] += red[q][threadIdx.x + st];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const double s0 = red[0][0], s1 = red[1][0], s2 = red[2][0], s3 = red[3][0], sh = red[4][0];
+    double loss = 0.0;
+    bool any = false;
+    if (sp.a != 0.0) { loss = sp.a * (s0 / count); any = true; }
+    if (sp.b != 0.0) { const double t = sp.b * (s1 / count); loss = any ? loss + t : t; any = true; }
+    if (sp.c != 0.0) { const double t = sp.c * (sh / count); loss = any ? loss + t : t; }
+    if (loss_out) loss_out[0] = (float)loss;
+    if (stats) {
+      stats[0] += s0; stats[1] += s1; stats[2] += s2; stats[3] += s3; stats[4] += count;
+      const double ss_tot = s3 - s2 * s2 / count;
+      const double r2 = ss_tot > 0.0 ? 1.0 - s0 / ss_tot : (s0 == 0.0 ? 1.0 : 0.0);   // (loss_final_kernel's convention)
+      stats[5] += loss; stats[6] += r2; stats[7] += 1.0;
+    }
+  }
+}
+
+#define LOSS_SPEC_BLOCKS_MAX ((NINT_LOSS_SPEC_SCRATCH_FLOATS - 2) / 10)   // what the caller's scratch holds: 5 doubles per workgroup
+static_assert(LOSS_SPEC_BLOCKS_MAX == LOSS_BLOCKS_MAX, "the spec passes take the grids of their twins: the same partials per sum");
+
+// The spec's own checks (nint.h).  nout: O of the plain and fused entries, T*O of the sequence entry.
+static int loss_spec_check(const nint_loss_spec* sp, int nout, const float* wgt, double wsum) {
+  if (!sp) return NINT_E_ARG;
+  const double co[3] = {sp->mse, sp->l1, sp->huber};
+  for (double v : co)
+    if (!(v >= 0.0) || v > DBL_MAX) return NINT_E_ARG;
+  if (sp->mse == 0.0 && sp->l1 == 0.0 && sp->huber == 0.0) return NINT_E_ARG;
+  if (sp->huber != 0.0 && (!(sp->delta > 0.0) || sp->delta > DBL_MAX)) return NINT_E_ARG;
+  if (sp->ow) {
+    if (sp->now != nout || !(sp->osum > 0.0) || sp->osum > DBL_MAX) return NINT_E_ARG;
+  } else if (sp->now != 0) {
+    return NINT_E_ARG;
+  }
+  if (wgt && !loss_weights_ok(wgt, wsum)) return NINT_E_ARG;
+  return NINT_OK;
+}
+static inline LossSpecK loss_spec_k(const nint_loss_spec* sp) {
+  return LossSpecK{sp->mse, sp->l1, sp->huber, sp->huber != 0.0 ? sp->delta : 1.0, sp->ow};
+}
+// cnt = images * (osum or outputs) * (wsum or Hc * Wc), left to right (nint.h).  With ow the sequence entry's weights run
+// over (step, output): `images` is then B, not T*B.
+static inline double loss_spec_cnt(const nint_loss_spec* sp, int images, int O, const float* wgt, double wsum, int Hc, int Wc) {
+  return (double)images * (sp->ow ? sp->osum : (double)O) * (wgt ? wsum : (double)Hc * Wc);
+}
+
+extern "C" int nint_loss_crop_spec(const float* pred, const float* y, const float* wgt, double wsum, const nint_loss_spec* spec,
+                                   float* dpred, float* loss_out, double* stats, int N, int O, int H, int W, int oy, int ox,
+                                   int Hc, int Wc, void* stream) {
+  if (!pred || !y || !loss_out || N <= 0 || O <= 0 || oy < 0 || ox < 0 || oy + Hc > H || ox + Wc > W) return NINT_E_ARG;
+  if (Hc <= 0 || Wc <= 0) return NINT_E_ARG;
+  const int rc = loss_spec_check(spec, O, wgt, wsum);
+  if (rc != NINT_OK) return rc;
+  if ((((uintptr_t)loss_out) & 7) != 0 || (((uintptr_t)wgt) & 3) != 0 || (((uintptr_t)spec->ow) & 3) != 0) return NINT_E_ALIGN;
+  hipStream_t st = (hipStream_t)stream;
+  const double cnt = loss_spec_cnt(spec, N, O, wgt, wsum, Hc, Wc);
+  const LossSpecK k = loss_spec_k(spec);
+  double* partial = (double*)(loss_out + 2);   // loss_out: [0]=loss, [1]=pad, [2..] = 256*5 doubles
+  hipLaunchKernelGGL(loss_spec_partial_kernel, dim3(LOSS_BLOCKS), dim3(1024), 0, st, pred, y, dpred, partial, N, O, H, W, oy, ox, Hc, Wc, wgt, cnt, k);
+  NINT_LAUNCH_CHECK();
+  hipLaunchKernelGGL(loss_spec_final_kernel, dim3(1), dim3(256), 0, st, partial, LOSS_BLOCKS, loss_out, stats, cnt, k);
+  NINT_LAUNCH_CHECK();
+  return NINT_OK;
+}
+
+// The prediction of the fused spec pass has to carry head_fwd_kernel's bits (fused = the three launches).  As compiled, that
+// kernel -- and head_loss_fused_body with it -- joins the products of all but the LAST 12 staged channels to the accumulator by
+// fused multiply-add, and rounds those last 12 products on their own before adding them in channel order (the vectoriser packs
+// them: v_pk_mul_f32 + v_add_f32).  Around the run-time branches of the body below the optimiser does not repeat that choice
+// (it fuses the whole chain), so the chain is spelled out; test_fused_spec_equals_the_three_launches_bit_for_bit holds the two
+// together at every CHV, with real data in the last channels.
+#define HEAD_FWD_UNFUSED_TAIL 12
+template <int CHV>
+__device__ __forceinline__ float head_dot_as_fwd(float p, const float* w_row, const float (&hv)[CHV]) {
+#pragma clang fp contract(off)
+  const f32x4_t* wr = (const f32x4_t*)w_row;
+#pragma unroll
+  for (int c = 0; c < CHV; c += 4) {
+    const f32x4_t wv = wr[c / 4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      if (c + e < CHV - HEAD_FWD_UNFUSED_TAIL) {
+        p = __builtin_fmaf(wv[e], hv[c + e], p);
+      } else {
+        const float m = wv[e] * hv[c + e];
+        p = m + p;
+      }
+    }
+  }
+  return p;
+}
+
+// head_loss_fused_body with the general element: the same passes, phases and order (so the prediction and dL/dh keep the
+// bits of head_fwd_kernel and head_bwd_dh_kernel); the output's weight is read with its target, and an element of weight 0
+// reads no target.  The fifth sum folds through red[0] after the other four: the static LDS stays the twins' 8 KiB, and
+// with it the limit (head_staged_holds).
+template <int DT, int CHV, bool SEQ>
+__device__ __forceinline__ void head_loss_spec_body(char* smem_hl, const void* __restrict__ h, int n0, int N, int Ch, int Chp, int O,
+                                                    const float* __restrict__ w, const float* __restrict__ b,
+                                                    const float* __restrict__ y, float* __restrict__ dpred,
+                                                    void* __restrict__ dh, double* __restrict__ partial, int H, int W,
+                                                    int P, int Hh, int Wh, int oy, int ox, int Hc, int Wc, int Bs,
+                                                    const float* __restrict__ wgt, double cnt, const LossSpecK sp) {
+  float* w_s = (float*)smem_hl;                  // [O][CHV], zero padded (head_stage_weights)
+  float* gq_s = w_s + O * CHV;                   // [min(O, HEAD_OCH)][64]
+  head_stage_weights<CHV>(w_s, w, O, Ch);
+  const int lane = threadIdx.x & 63;
+  const int q = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // (scalar: the weight reads below stay scalar loads)
+  const size_t npix = (size_t)N * H * W;
+  const double inv_n = 1.0 / cnt;
+  constexpr int CQ = CHV / 4;                    // channels per wave in phase 2
+  LossSpecSums s;
+  for (size_t p0 = (size_t)blockIdx.x * 64; p0 < npix; p0 += (size_t)gridDim.x * 64) {
+    const size_t pix = p0 + lane;
+    const bool live = pix < npix;
+    const size_t pc = live ? pix : npix - 1;
+    const int x = pc % W;
+    size_t r = pc / W;
+    const int yy = r % H;
+    const int n = r / H;
+    const size_t hb = ((((size_t)(n0 + n)) * Hh + (yy + P)) * Wh + (x + P)) * Chp;
+    float hv[CHV];
+#pragma unroll
+    for (int c = 0; c < CHV; c += 4) {
+      const f32x4_t v = (c < Chp) ? load_vec4<DT>(h, hb + c) : (f32x4_t){0.f, 0.f, 0.f, 0.f};
+      hv[c] = v[0]; hv[c + 1] = v[1]; hv[c + 2] = v[2]; hv[c + 3] = v[3];
+    }
+    const int cy = yy - oy, cx = x - ox;
+    bool in = live && cy >= 0 && cy < Hc && cx >= 0 && cx < Wc;
+    float wf = 1.f;
+    if (wgt) {
+      wf = in ? wgt[(size_t)cy * Wc + cx] : 0.f;
+      in = in && wf != 0.f;
+    }
+    const float* owp = sp.ow;                    // the O weights of the pixel's step (image n = t*B + b)
+    if constexpr (SEQ) owp = owp ? owp + (size_t)(n / Bs) * O : owp;
+    float* dp = dpred + ((size_t)n * O * H + yy) * W + x;
+    const float* yp = y + (head_image<SEQ>(n, Bs, N / (SEQ ? Bs : 1)) * O * Hc + cy) * Wc + cx;
+    float acc[CQ];
+#pragma unroll
+    for (int c = 0; c < CQ; ++c) acc[c] = 0.f;
+    const int c0 = q * CQ;
+    for (int oc = 0; oc < O; oc += HEAD_OCH) {
+      const int on = min(HEAD_OCH, O - oc);
+      const int OG = (on + 3) / 4, ob = oc + q * OG, oe = min(oc + on, ob + OG);
+      if (oc > 0) __syncthreads();               // the previous chunk is consumed
+      constexpr int OU = 5;                      // targets fetched ahead of their use: one HBM round trip per OU outputs
+      for (int o0 = ob; o0 < oe; o0 += OU) {
+        float tq[OU], qq[OU];
+#pragma unroll
+        for (int u = 0; u < OU; ++u) qq[u] = (in && o0 + u < oe) ? (owp ? owp[o0 + u] : 1.f) : 0.f;
+#pragma unroll
+        for (int u = 0; u < OU; ++u) tq[u] = qq[u] != 0.f ? yp[(size_t)(o0 + u) * Hc * Wc] : 0.f;
+#pragma unroll
+        for (int u = 0; u < OU; ++u) {
+          const int o = o0 + u;
+          if (o >= oe) break;
+          const float p = head_dot_as_fwd<CHV>(b ? b[o] : 0.f, w_s + o * CHV, hv);
+          float gq = 0.f;
+          if (qq[u] != 0.f) {                    // inside the crop, cell and output weights non-zero
+            const float t = tq[u];
+            const float d = p - t;
+            const double Wd = (double)qq[u] * (double)wf;
+            s.add(Wd, d, t, loss_spec_huber(sp, d));
+            gq = loss_spec_grad(sp, d, inv_n, Wd);
+          }
+          if (live) dp[(size_t)o * H * W] = gq;
+          gq_s[(o - oc) * 64 + lane] = gq;
+        }
+      }
+      __syncthreads();
+      // phase 2: dL/dh[c] = sum_o w[o][c] * gq[o], in output order (the order of head_bwd_dh_kernel)
+      for (int o = oc; o < oc + on; ++o) {
+        const float gq = gq_s[(o - oc) * 64 + lane];
+        const f32x4_t* wr = (const f32x4_t*)(w_s + o * CHV + c0);
+#pragma unroll
+        for (int c = 0; c < CQ; c += 4) {
+          const f32x4_t wv = wr[c / 4];
+          acc[c] += wv[0] * gq; acc[c + 1] += wv[1] * gq; acc[c + 2] += wv[2] * gq; acc[c + 3] += wv[3] * gq;
+        }
+      }
+    }
+    if (live) {
+#pragma unroll
+      for (int c = 0; c < CQ; c += 4)
+        if (c0 + c < Chp) store_vec4<DT>(dh, pix * Chp + c0 + c, (f32x4_t){acc[c], acc[c + 1], acc[c + 2], acc[c + 3]});
+    }
+    __syncthreads();                             // gq_s is rewritten by the next pass
+  }
+  __shared__ double red[4][256];
+  red[0][threadIdx.x] = s.s2; red[1][threadIdx.x] = s.s1; red[2][threadIdx.x] = s.sy; red[3][threadIdx.x] = s.syy;
+  __syncthreads();
+  for (int st = 128; st > 0; st >>= 1) {
+    if ((int)threadIdx.x < st)
+      for (int q2 = 0; q2 < 4; ++q2) red[q2][threadIdx.x] += red[q2][threadIdx.x + st];
+    __syncthreads();
+  }
+  if (threadIdx.x < 4) partial[blockIdx.x * 5 + threadIdx.x] = red[threadIdx.x][0];
+  __syncthreads();
+  red[0][threadIdx.x] = s.sh;                    // the fifth sum, by the same tree
+  __syncthreads();
+  for (int st = 128; st > 0; st >>= 1) {
+    if ((int)threadIdx.x < st) red[0][threadIdx.x] += red[0][threadIdx.x + st];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) partial[blockIdx.x * 5 + 4] = red[0][0];
+}
+
+template <int DT, int CHV, bool SEQ>
+__global__ __launch_bounds__(256) void head_loss_spec_kernel(const void* __restrict__ h, int n0, int N, int Ch, int Chp, int O,
+                                                             const float* __restrict__ w, const float* __restrict__ b,
+                                                             const float* __restrict__ y, float* __restrict__ dpred,
+                                                             void* __restrict__ dh, double* __restrict__ partial, int H, int W,
+                                                             int P, int Hh, int Wh, int oy, int ox, int Hc, int Wc, int Bs,
+                                                             const float* __restrict__ wgt, double cnt, const LossSpecK sp) {
+  extern __shared__ __attribute__((aligned(16))) char smem_hl[];
+  head_loss_spec_body<DT, CHV, SEQ>(smem_hl, h, n0, N, Ch, Chp, O, w, b, y, dpred, dh, partial, H, W, P, Hh, Wh, oy, ox, Hc, Wc, Bs, wgt, cnt, sp);
+}
+
+// SEQ: the sequence entry (n0 = Bs = B, N = T*B); head_loss_fused_impl's launch shape
+template <bool SEQ>
+static int head_loss_spec_impl(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w, const float* b,
+                               const float* y, const float* wgt, double cnt, const LossSpecK k, float* dpred, void* dh,
+                               float* loss_out, double* stats, const nint_geom* g, int oy, int ox, int Hc, int Wc, int dtype,
+                               int Bs, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  double* partial = (double*)(loss_out + 2);   // loss_out: [0]=loss, [1]=pad, [2..] = up to LOSS_SPEC_BLOCKS_MAX*5 doubles
+  const size_t npix = (size_t)N * g->H * g->W;
+  const int nblk = (int)((npix + 63) / 64 < LOSS_SPEC_BLOCKS_MAX ? (npix + 63) / 64 : LOSS_SPEC_BLOCKS_MAX);
+  const size_t lds = ((size_t)O * head_chv(Chp) + (size_t)(O < HEAD_OCH ? O : HEAD_OCH) * 64) * sizeof(float);
+  if (lds + 8192 > 160 * 1024) return NINT_E_SHAPE;
+  const int rc = nint_by_dtype(dtype, [&](auto dt) { return head_by_chv(Chp, [&](auto chv) -> int {
+    auto kern = head_loss_spec_kernel<decltype(dt)::value, decltype(chv)::value, SEQ>;
+    if (lds + 8192 > 64 * 1024) NINT_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kern, dim3(nblk), dim3(256), lds, st, h_slab, n0, N, Ch, Chp, O, w, b, y, dpred, dh, partial, g->H, g->W, g->P, g->Hh, g->Wh, oy, ox, Hc, Wc, Bs, wgt, cnt, k);
+    return NINT_OK; }); });
+  if (rc != NINT_OK) return rc;
+  NINT_LAUNCH_CHECK();
+  hipLaunchKernelGGL(loss_spec_final_kernel, dim3(1), dim3(256), 0, st, partial, nblk, loss_out, stats, cnt, k);
+  NINT_LAUNCH_CHECK();
+  return NINT_OK;
+}
+
+extern "C" int nint_head_loss_fused_spec(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w, const float* b,
+                                         const float* y, const float* wgt, double wsum, const nint_loss_spec* spec, float* dpred,
+                                         void* dh, float* loss_out, double* stats, const nint_geom* g, int oy, int ox, int Hc,
+                                         int Wc, int dtype, void* stream) {
+  if (!h_slab || !w || !y || !dpred || !dh || !loss_out || !g || N <= 0 || O <= 0 || Ch <= 0) return NINT_E_ARG;
+  if (oy < 0 || ox < 0 || Hc <= 0 || Wc <= 0 || oy + Hc > g->H || ox + Wc > g->W) return NINT_E_ARG;
+  if (dtype != NINT_BF16 && dtype != NINT_F32) return NINT_E_ARG;
+  const int rc = loss_spec_check(spec, O, wgt, wsum);
+  if (rc != NINT_OK) return rc;
+  if (Chp > 128 || Chp % 4) return NINT_E_SHAPE;   // wider heads: nint_head_fwd + nint_loss_crop_spec + nint_head_bwd
+  if ((((uintptr_t)loss_out) & 7) != 0 || (((uintptr_t)wgt) & 3) != 0 || (((uintptr_t)spec->ow) & 3) != 0) return NINT_E_ALIGN;
+  return head_loss_spec_impl<false>(h_slab, n0, N, Ch, Chp, O, w, b, y, wgt, loss_spec_cnt(spec, N, O, wgt, wsum, Hc, Wc),
+                                    loss_spec_k(spec), dpred, dh, loss_out, stats, g, oy, ox, Hc, Wc, dtype, 0, stream);
+}
+
+extern "C" int nint_head_loss_seq_fused_spec(const void* h_slab, int B, int T, int Ch, int Chp, int O, const float* w, const float* b,
+                                             const float* y, const float* wgt, double wsum, const nint_loss_spec* spec, float* dpred,
+                                             void* dh_seq, float* loss_out, double* stats, const nint_geom* g, int oy, int ox,
+                                             int Hc, int Wc, int dtype, void* stream) {
+  if (!y || !dpred || !dh_seq || !loss_out || !head_seq_args_ok(h_slab, B, T, Ch, Chp, O, w, g, dtype)) return NINT_E_ARG;
+  if (oy < 0 || ox < 0 || Hc <= 0 || Wc <= 0 || oy + Hc > g->H || ox + Wc > g->W) return NINT_E_ARG;
+  if ((long long)T * O > INT_MAX) return NINT_E_ARG;
+  const int rc = loss_spec_check(spec, T * O, wgt, wsum);
+  if (rc != NINT_OK) return rc;
+  if (Chp > 128) return NINT_E_SHAPE;              // wider heads: nint_head_fwd_seq + nint_loss_crop_spec + nint_head_bwd_seq
+  if ((((uintptr_t)loss_out) & 7) != 0 || ((((uintptr_t)h_slab) | ((uintptr_t)dh_seq)) & 15) != 0 || (((uintptr_t)wgt) & 3) != 0 ||
+      (((uintptr_t)spec->ow) & 3) != 0) return NINT_E_ALIGN;
+  // with ow the weights run over (step, output): cnt = B * osum * wsum; without, the twin's (T*B) * O * wsum
+  const double cnt = loss_spec_cnt(spec, spec->ow ? B : T * B, O, wgt, wsum, Hc, Wc);
+  return head_loss_spec_impl<true>(h_slab, B, T * B, Ch, Chp, O, w, b, y, wgt, cnt, loss_spec_k(spec), dpred, dh_seq, loss_out,
+                                   stats, g, oy, ox, Hc, Wc, dtype, B, stream);
+}
+
 // ------------------------------------------------------------------------------ evaluation: skill sums (test.ipynb)
 // What the analysis notebook computes from the gathered predictions -- r_squared_temporal (:377-385), r_squared_spatial
 // (:462-485), the time-mean maps (:605,:630) and the cos-latitude weighted means (:684-693,:796-803) -- follows from running

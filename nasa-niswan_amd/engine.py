@@ -542,13 +542,20 @@ class SeqEngine:
         return dw.view(O, Ch, 1, 1), db
 
     def head_loss_seq_fused(self, ws: Workspace, w: torch.Tensor, b: Optional[torch.Tensor], y: torch.Tensor, dpred: torch.Tensor,
-                            scratch: torch.Tensor, stats: torch.Tensor, halo, Hc: int, Wc: int, weights=None) -> bool:
+                            scratch: torch.Tensor, stats: torch.Tensor, halo, Hc: int, Wc: int, weights=None, spec=None) -> bool:
         """head_loss_fused over every step (nint_head_loss_seq_fused): y (B, T, O, Hc, Wc); dpred (T*B, O, H, W) in image
-        order t*B + b; the per-step dL/dh goes into ws.dh_seq_slab().  False beyond the fused kernel's limit.  `weights`:
-        as in head_loss_fused."""
+        order t*B + b; the per-step dL/dh goes into ws.dh_seq_slab().  False beyond the fused kernel's limit.  `weights`,
+        `spec` (its weights run over t*O + o): as in head_loss_fused."""
         Ch, Chp, O, w2, b2 = self._head_args(w, b)
         if self._beyond_fused_head(Chp, O):
             return False
+        if spec is not None:
+            wgt, wsum = weights if weights is not None else (None, 0.0)
+            check(self.lib.nint_head_loss_seq_fused_spec(ptr(ws.h[-1]), ws.B, ws.T, Ch, Chp, O, ptr(w2), ptr(b2), ptr(y), ptr(wgt), wsum,
+                                                         C.byref(spec), ptr(dpred), ptr(ws.dh_seq_slab(self)), ptr(scratch), ptr(stats),
+                                                         C.byref(ws.g), halo[0], halo[1], Hc, Wc, self.dt, stream_ptr()),
+                  "nint_head_loss_seq_fused_spec")
+            return True
         if weights is not None:
             wgt, wsum = weights
             check(self.lib.nint_head_loss_seq_fused_weighted(ptr(ws.h[-1]), ws.B, ws.T, Ch, Chp, O, ptr(w2), ptr(b2), ptr(y), ptr(wgt),
@@ -562,14 +569,23 @@ class SeqEngine:
         return True
 
     def head_loss_fused(self, ws: Workspace, w: torch.Tensor, b: Optional[torch.Tensor], y: torch.Tensor, dpred: torch.Tensor,
-                        scratch: torch.Tensor, stats: torch.Tensor, halo, Hc: int, Wc: int, weights=None) -> bool:
+                        scratch: torch.Tensor, stats: torch.Tensor, halo, Hc: int, Wc: int, weights=None, spec=None) -> bool:
         """Training fast path (nint_head_loss_fused): head forward, crop, MSE+L1 sums, d loss / d pred and dL/dh_{T-1}
         (into ws.dh[-1]) in one pass; `scratch[0]` = loss, `stats` accumulated.  False when the head is wider than the
         fused kernel holds (more than 128 padded channels, or weights + one pixel group's d loss / d pred beyond the LDS) (the caller then takes the three separate launches).
-        `weights` = (wgt, wsum): the f32 (Hc, Wc) device map and its f64 sum (nint_head_loss_fused_weighted); None: unweighted."""
+        `weights` = (wgt, wsum): the f32 (Hc, Wc) device map and its f64 sum (nint_head_loss_fused_weighted); None: unweighted.
+        `spec`: a _lib.NintLossSpec (loss.LossSpec.on) -- the configurable loss, nint_head_loss_fused_spec with or without the
+        map, `scratch` then of NINT_LOSS_SPEC_SCRATCH_FLOATS floats; None: the calls above."""
         Ch, Chp, O, w2, b2 = self._head_args(w, b)
         if self._beyond_fused_head(Chp, O):
             return False
+        if spec is not None:
+            wgt, wsum = weights if weights is not None else (None, 0.0)
+            check(self.lib.nint_head_loss_fused_spec(ptr(ws.h[-1]), ws.T * ws.B, ws.B, Ch, Chp, O, ptr(w2), ptr(b2), ptr(y), ptr(wgt), wsum,
+                                                     C.byref(spec), ptr(dpred), ptr(ws.dh[-1]), ptr(scratch), ptr(stats), C.byref(ws.g),
+                                                     halo[0], halo[1], Hc, Wc, self.dt, stream_ptr()),
+                  "nint_head_loss_fused_spec")
+            return True
         if weights is not None:
             wgt, wsum = weights
             check(self.lib.nint_head_loss_fused_weighted(ptr(ws.h[-1]), ws.T * ws.B, ws.B, Ch, Chp, O, ptr(w2), ptr(b2), ptr(y), ptr(wgt),

@@ -12,18 +12,32 @@ arithmetic.  Three ways in: ``FusedTrainer(loss_weights=...)`` (the fused step),
 torch training loop) and ``train.py --lat-weighted-loss / --loss-weights``.
 
 Under data parallelism the map is NOT broadcast: every rank has to be given the same one (``train.py`` builds it
-deterministically on every rank)."""
+deterministically on every rank).
+
+``LossSpec`` opens the other three axes of that loss -- which penalty, which output, which step:
+
+    loss = mse * mean_w(d^2) + l1 * mean_w(|d|) + huber * mean_w(HuberLoss_delta(d))
+
+a weighted mean whose weight is the product of the cell's (the map above), the output's (``output_weights``) and, with the
+sequence loss, the step's (``step_weights``: spin-up steps discounted or dropped).  A coefficient of 0 takes its term out, a
+weight of 0 its element (a NaN target is harmless there).  ``include/nint.h`` (the ``_spec`` entries) carries the exact
+arithmetic.  Ways in: ``FusedTrainer(loss=LossSpec(...))``, ``CropLoss`` and ``train.py --loss-mix / --huber-delta /
+--output-weights / --spinup-steps``.  Like the map, a spec is NOT broadcast between data-parallel ranks: every rank has to be
+given the same one (``train.py`` builds it from the command line on every rank)."""
 from __future__ import annotations
 
 from typing import Optional, Tuple
+
+import ctypes as C
+import math
 
 import numpy as np
 import torch
 
 from . import _lib
-from ._lib import NINT_LOSS_SCRATCH_FLOATS, check, ptr, stream_ptr
+from ._lib import NINT_LOSS_SCRATCH_FLOATS, NINT_LOSS_SPEC_SCRATCH_FLOATS, check, ptr, stream_ptr
 
-__all__ = ["grid_latitudes", "cos_latitude_weights", "validate_loss_weights", "CropMSEL1Loss"]
+__all__ = ["grid_latitudes", "cos_latitude_weights", "validate_loss_weights", "CropMSEL1Loss", "LossSpec", "CropLoss"]
 
 
 def grid_latitudes(H: int) -> np.ndarray:
@@ -134,3 +148,139 @@ class CropMSEL1Loss(torch.nn.Module):
             raise _lib.NintError("CropMSEL1Loss needs the uncropped prediction (B, O, H, W) on the MI355X (cuda)")
         wgt, wsum = (None, 0.0) if self._weights is None else self._weights.on(pred.device, y.shape[-2], y.shape[-1])
         return _CropMSEL1.apply(pred, y, wgt, wsum, self.halo[0], self.halo[1])
+
+
+def _weight_vector(values, what: str) -> np.ndarray:
+    """a vector of output or step weights as f32: finite, non-negative, not all zero (ValueError otherwise)"""
+    if isinstance(values, torch.Tensor):
+        values = values.detach().cpu().numpy()
+    v64 = np.asarray(values, np.float64)
+    if v64.ndim != 1 or v64.size == 0:
+        raise ValueError(f"{what} must be a vector, got shape {v64.shape}")
+    if not np.isfinite(v64).all():
+        raise ValueError(f"{what} must be finite (switch an entry off with weight 0, not NaN)")
+    if (v64 < 0).any():
+        raise ValueError(f"{what} must be non-negative")
+    with np.errstate(over="ignore"):
+        v = v64.astype(np.float32)
+    if not np.isfinite(v).all():
+        raise ValueError(f"{what} overflow f32")
+    if not (v > 0).any():
+        raise ValueError(f"{what} are all zero: nothing to fit")
+    return np.ascontiguousarray(v)
+
+
+class LossSpec:
+    """The configurable training loss (``nint_loss_spec``): ``mse * MSE + l1 * L1 + huber * HuberLoss(delta)`` as weighted
+    means over the crop, with a weight per output (``output_weights``, shape ``(O,)``) and, under the sequence loss, per step
+    (``step_weights``, shape ``(T,)``).  The default ``LossSpec()`` is the reference's ``MSELoss + L1Loss``.
+
+    Validated here on the host -- ValueError for a negative, NaN or inf coefficient, all coefficients zero, a ``delta`` that
+    is not finite and > 0 while ``huber`` is on, weights that are negative, non-finite or all zero; the lengths against ``O``
+    and ``T`` at the first call that knows them.  Both vectors are stored as f32; the device vector is
+    ``f32(step[t]) * f32(out[o])`` rounded to f32 on the host (index ``t*O + o``; the outputs alone without the sequence
+    loss), and ``osum`` the f64 sum of that stored vector.  ``step_weights`` without the sequence loss is a ValueError.
+    Not broadcast between data-parallel ranks: every rank must be given the same spec."""
+
+    def __init__(self, mse: float = 1.0, l1: float = 1.0, huber: float = 0.0, delta: float = 1.0, output_weights=None,
+                 step_weights=None):
+        self.mse, self.l1, self.huber, self.delta = float(mse), float(l1), float(huber), float(delta)
+        for name in ("mse", "l1", "huber"):
+            v = getattr(self, name)
+            if not math.isfinite(v) or v < 0:
+                raise ValueError(f"loss coefficient {name} = {v!r}: must be finite and >= 0")
+        if self.mse == 0 and self.l1 == 0 and self.huber == 0:
+            raise ValueError("all loss coefficients are zero: nothing to fit")
+        if self.huber != 0 and not (math.isfinite(self.delta) and self.delta > 0):
+            raise ValueError(f"huber delta = {self.delta!r}: must be finite and > 0")
+        self.output_weights = None if output_weights is None else _weight_vector(output_weights, "output weights")
+        self.step_weights = None if step_weights is None else _weight_vector(step_weights, "step weights")
+        self._key = None
+        self._vec: Optional[torch.Tensor] = None
+        self._c = None
+
+    def host_vector(self, O: int, T: Optional[int] = None) -> Optional[np.ndarray]:
+        """The weight vector the device reads, f32: ``(O,)`` for a last-step loss (``T`` None), ``(T*O,)`` with index
+        ``t*O + o`` for the sequence loss; None when neither kind of weight is set.  Checks the lengths."""
+        if self.step_weights is not None and T is None:
+            raise ValueError("step_weights need the sequence loss (a target at every step of the window)")
+        if self.output_weights is not None and self.output_weights.shape[0] != O:
+            raise ValueError(f"{self.output_weights.shape[0]} output weights for {O} outputs")
+        if self.step_weights is not None and self.step_weights.shape[0] != T:
+            raise ValueError(f"{self.step_weights.shape[0]} step weights for a window of {T} steps")
+        if self.output_weights is None and self.step_weights is None:
+            return None
+        out = self.output_weights if self.output_weights is not None else np.ones(O, np.float32)
+        if T is None:
+            return out
+        step = self.step_weights if self.step_weights is not None else np.ones(T, np.float32)
+        vec = np.ascontiguousarray((step[:, None] * out[None, :]).astype(np.float32).reshape(-1))   # f32 * f32, rounded to f32
+        if not np.isfinite(vec).all() or not (vec > 0).any():
+            raise ValueError("the products of step and output weights overflow f32 or are all zero")
+        return vec
+
+    def on(self, device, O: int, T: Optional[int] = None):
+        """the ``nint_loss_spec`` for a call with ``O`` outputs (and ``T`` steps under the sequence loss) on ``device``"""
+        key = (str(device), int(O), None if T is None else int(T))
+        if self._key != key:
+            vec = self.host_vector(int(O), None if T is None else int(T))
+            c = _lib.NintLossSpec()
+            c.mse, c.l1, c.huber, c.delta = self.mse, self.l1, self.huber, self.delta
+            if vec is None:
+                self._vec, c.ow, c.now, c.osum = None, None, 0, 0.0
+            else:
+                self._vec = torch.from_numpy(vec).to(device)
+                c.ow, c.now, c.osum = self._vec.data_ptr(), vec.shape[0], float(vec.astype(np.float64).sum())
+            self._c, self._key = c, key
+        return self._c
+
+    def __repr__(self):
+        return (f"LossSpec(mse={self.mse}, l1={self.l1}, huber={self.huber}, delta={self.delta}, "
+                f"output_weights={None if self.output_weights is None else self.output_weights.tolist()}, "
+                f"step_weights={None if self.step_weights is None else self.step_weights.tolist()})")
+
+
+class _CropSpec(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, y, wgt, wsum, spec, oy, ox):
+        lib = _lib.load()
+        N, O, H, W = pred.shape
+        Hc, Wc = y.shape[-2], y.shape[-1]
+        p = pred.detach().float().contiguous()
+        yv = y.detach().float().contiguous()
+        if yv.numel() != N * O * Hc * Wc:
+            raise ValueError(f"target {tuple(y.shape)} does not match the prediction {tuple(pred.shape)}")
+        scratch = torch.empty(NINT_LOSS_SPEC_SCRATCH_FLOATS, dtype=torch.float32, device=p.device)
+        dpred = torch.empty_like(p) if ctx.needs_input_grad[0] else None
+        check(lib.nint_loss_crop_spec(ptr(p), ptr(yv), ptr(wgt), wsum, C.byref(spec), ptr(dpred), ptr(scratch), None, N, O, H, W,
+                                      oy, ox, Hc, Wc, stream_ptr()), "nint_loss_crop_spec")
+        ctx.dpred = dpred
+        ctx.dtype = pred.dtype
+        return scratch[0].clone()
+
+    @staticmethod
+    def backward(ctx, upstream):
+        g = None if ctx.dpred is None else (ctx.dpred * upstream).to(ctx.dtype)
+        return g, None, None, None, None, None, None
+
+
+class CropLoss(torch.nn.Module):
+    """``CropMSEL1Loss`` with the configurable loss: ``loss = criterion(y, pred)`` with the UNCROPPED ``pred (B, O, H, W)`` on
+    the device and ``y (B, [O,] Hc, Wc)``; ``spec`` a ``LossSpec`` (None: the default mix, MSE + L1) and ``weights`` the
+    optional per-cell map.  The forward is ONE launch of ``nint_loss_crop_spec``, which also writes d loss / d pred;
+    backward returns that times the upstream gradient.  ``y`` receives NO gradient.  A spec with ``step_weights`` is refused
+    (ValueError): one prediction has no steps.  Every data-parallel rank must be given the same spec and map."""
+
+    def __init__(self, halo: Tuple[int, int] = (5, 5), spec: Optional[LossSpec] = None, weights=None):
+        super().__init__()
+        self.halo = (int(halo[0]), int(halo[1]))
+        if spec is not None and not isinstance(spec, LossSpec):
+            raise TypeError("spec must be a LossSpec or None")
+        self.spec = LossSpec() if spec is None else spec
+        self._weights = None if weights is None else DeviceWeights(weights)
+
+    def forward(self, y: torch.Tensor, pred: torch.Tensor) -> torch.Tensor:
+        if pred.dim() != 4 or pred.device.type != "cuda":
+            raise _lib.NintError("CropLoss needs the uncropped prediction (B, O, H, W) on the MI355X (cuda)")
+        wgt, wsum = (None, 0.0) if self._weights is None else self._weights.on(pred.device, y.shape[-2], y.shape[-1])
+        return _CropSpec.apply(pred, y, wgt, wsum, self.spec.on(pred.device, pred.shape[1]), self.halo[0], self.halo[1])

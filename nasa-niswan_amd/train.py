@@ -6,7 +6,8 @@ stepped once per epoch before validation, checkpoint every 10 epochs); the per-b
 `loss.item()` / sklearn R2 host syncs (train.py:113-114) are replaced by device accumulators read
 once per epoch.  Added flags: --dtype, --levels, --grid, --synthetic-steps, --pad-mode, --f32-inputs,
 --static-channels, --sequence-loss, --test-skill, --lat-weighted-loss, --loss-weights, --clip-grad-norm,
---skip-nonfinite-steps, --stateful, --bptt-segments, --accumulate-steps.
+--skip-nonfinite-steps, --stateful, --bptt-segments, --accumulate-steps, --loss-mix, --huber-delta, --output-weights,
+--spinup-steps.
 
 The data path is on the device too: by default every batch is written by ONE launch of the
 fuse / z-score / halo-pad kernel straight into the model's bf16 input slab (dataset.slab_batch);
@@ -105,7 +106,24 @@ def get_arguments(argv=None, MODEL='LSTM-00', SPECIES='bcb', LEARNING_RATE=1.0E-
     parser.add_argument("--accumulate-steps", type=int, default=1, metavar="K",
                         help="gradient accumulation: one optimizer step (and one all-reduce) per K batches, on their mean gradient; "
                              "a group left unfinished at the end of an epoch goes on in the next")
+    parser.add_argument("--loss-mix", nargs=3, type=float, default=(1.0, 1.0, 0.0), metavar=("MSE", "L1", "HUBER"),
+                        help="coefficients of the MSE, L1 and Huber terms of the loss (training and validation); a coefficient of "
+                             "0 takes its term out.  The default is the reference's MSELoss + L1Loss")
+    parser.add_argument("--huber-delta", type=float, default=1.0, metavar="D",
+                        help="threshold of the Huber term (torch.nn.HuberLoss), in the target's z-score units")
+    parser.add_argument("--output-weights", type=str, default=None, metavar="FILE.npy",
+                        help="a vector of --levels non-negative loss weights, one per output; 0 = leave the output out (its "
+                             "targets may be NaN)")
+    parser.add_argument("--spinup-steps", type=int, default=0, metavar="K",
+                        help="with --sequence-loss: the first K steps of every window (spin-up from the zero state) carry no "
+                             "loss; K < --sequence-length")
     args = parser.parse_args(argv)
+    if args.spinup_steps < 0:
+        parser.error("--spinup-steps must be >= 0")
+    if args.spinup_steps > 0 and not args.sequence_loss:
+        parser.error("--spinup-steps needs --sequence-loss: the last-step loss has no spin-up steps to drop")
+    if args.spinup_steps >= args.sequence_length:
+        parser.error(f"--spinup-steps {args.spinup_steps} leaves no step of the --sequence-length {args.sequence_length} window")
     rank = int(os.environ.get("RANK", "0"))
     if rank == 0:
         os.makedirs(args.snapshot_dir, exist_ok=True)
@@ -113,6 +131,28 @@ def get_arguments(argv=None, MODEL='LSTM-00', SPECIES='bcb', LEARNING_RATE=1.0E-
         with open(os.path.join(args.snapshot_dir, 'configurations.json'), "w") as f:     # train.py:221-225
             json.dump(vars(args), f, indent=4)
     return args
+
+
+def build_loss_spec(args):
+    """The loss.LossSpec of the loss flags, or None when none of them changes the reference's MSE + L1 (the trainer then runs
+    the entries it has always run).  Built the same way on every rank: a spec is not broadcast."""
+    mix = tuple(float(v) for v in args.loss_mix)
+    if mix == (1.0, 1.0, 0.0) and not args.output_weights and not args.spinup_steps:
+        return None
+    from nasa_niswan_amd.loss import LossSpec
+    ow = None
+    if args.output_weights:
+        ow = np.load(args.output_weights)
+        if ow.shape != (args.levels,):
+            raise SystemExit(f"--output-weights {args.output_weights}: shape {ow.shape}, expected one weight per output {(args.levels,)}")
+    sw = None
+    if args.spinup_steps:
+        sw = np.ones(args.sequence_length, np.float32)
+        sw[:args.spinup_steps] = 0.0
+    try:
+        return LossSpec(mix[0], mix[1], mix[2], args.huber_delta, output_weights=ow, step_weights=sw)
+    except ValueError as e:
+        raise SystemExit(f"loss flags: {e}")
 
 
 def main(args):
@@ -168,7 +208,7 @@ def main(args):
     trainer = FusedTrainer(generator, lr=args.learning_rate, betas=tuple(args.betas), halo=halo,        # train.py:71
                            sequence_loss=args.sequence_loss, loss_weights=loss_weights,
                            max_grad_norm=args.clip_grad_norm, skip_nonfinite=args.skip_nonfinite_steps, stateful=args.stateful,
-                           bptt_segments=args.bptt_segments, accumulate_steps=args.accumulate_steps)
+                           bptt_segments=args.bptt_segments, accumulate_steps=args.accumulate_steps, loss=build_loss_spec(args))
     if args.stateful:
         # one schedule of world * batch lanes, the same every epoch; each rank takes its own columns and carries its own state
         sched, dropped = stateful_schedule(len(train_dataset), args.sequence_length, world * args.batch_size)

@@ -4,7 +4,9 @@
     pred = generator(X)                     -> nint_pack_btchw + nint_seq_fwd + nint_head_fwd
     pred[:, :, 5:95, 5:149].squeeze()       -> crop folded into the loss kernel (index math)
     MSELoss(y,pred) + L1Loss(y,pred)        -> nint_loss_mse_l1_crop (also emits d loss/d pred); with ``loss_weights`` the
-                                               per-cell weighted means of loss.py (the _weighted entries)
+                                               per-cell weighted means of loss.py (the _weighted entries); with ``loss``
+                                               (a loss.LossSpec) the MSE / L1 / Huber mix with output and step weights
+                                               (the _spec entries)
     zero_grad; loss.backward()              -> nint_head_bwd + nint_seq_bwd (grads overwrite the bucket)
     [DDP]                                   -> ONE RCCL all-reduce of the flat gradient bucket
     [stateful]                              -> nint_state_copy before the forward pass (carried state -> slot 0) and after it
@@ -30,9 +32,9 @@ from typing import List, Optional, Tuple
 import torch
 
 from . import _lib
-from ._lib import NINT_LOSS_SCRATCH_FLOATS, NINT_LOSS_STATS, check, ptr, stream_ptr
+from ._lib import NINT_LOSS_SPEC_SCRATCH_FLOATS, NINT_LOSS_STATS, check, ptr, stream_ptr
 from .model import ConvLSTM
-from .loss import DeviceWeights
+from .loss import DeviceWeights, LossSpec
 from .optim import FlatParams, FusedAdam
 
 
@@ -53,7 +55,7 @@ class FusedTrainer:
                  halo: Tuple[int, int] = (5, 5), process_group=None, distributed: Optional[bool] = None,
                  overlap_allreduce: bool = False, sequence_loss: bool = False, loss_weights=None,
                  max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False, stateful: bool = False,
-                 bptt_segments: Optional[int] = None, accumulate_steps: int = 1):
+                 bptt_segments: Optional[int] = None, accumulate_steps: int = 1, loss: Optional[LossSpec] = None):
         dev = next(model.parameters()).device
         if dev.type != "cuda":
             raise _lib.NintError("FusedTrainer needs the model on the MI355X (cuda)")
@@ -86,7 +88,8 @@ class FusedTrainer:
                                    skip_nonfinite=skip_nonfinite)
         self.halo = tuple(halo)
         self.lib = _lib.load()
-        self.scratch = torch.zeros(NINT_LOSS_SCRATCH_FLOATS, dtype=torch.float32, device=dev)
+        # (the size the _spec entries ask for, five doubles per workgroup; the other entries use the first 8194 floats of it)
+        self.scratch = torch.zeros(NINT_LOSS_SPEC_SCRATCH_FLOATS, dtype=torch.float32, device=dev)
         # [0..4] pooled: sum d^2, sum |d|, sum y, sum y^2, n; [5..7] per call: sum loss, sum r2_score, calls
         self.stats = torch.zeros(NINT_LOSS_STATS, dtype=torch.float64, device=dev)
         self._dpred = None
@@ -109,6 +112,10 @@ class FusedTrainer:
         # Per-cell loss weights (loss.py): an (Hc, Wc) map or (Hc,) row weights -- cos latitude, a mask, their product -- used by
         # step, evaluate and forward_loss in every branch.  Every data-parallel rank must be given the same map.
         self.set_loss_weights(loss_weights)
+        # The configurable loss (loss.LossSpec): an MSE / L1 / Huber mix with a weight per output and, with sequence_loss, per
+        # step, used by step, evaluate and forward_loss in every branch, on top of the map.  None: the reference's MSE + L1
+        # through today's entries.  Not broadcast: every data-parallel rank must be given the same spec.
+        self.set_loss(loss)
         # Truncated BPTT over consecutive chunks of a record (dataset.stateful_schedule): step() starts from the state the
         # previous step() ended in, carried on the device in slab form (engine.ConvLSTMState), and gradients stop at the
         # chunk start.  evaluate / forward_loss keep zero-state windows; under data parallelism every rank carries its own.
@@ -142,9 +149,30 @@ class FusedTrainer:
         """(wgt, wsum) for the engine's head/loss calls, or None"""
         return None if self._weights is None else self._weights.on(self.device, Hc, Wc)
 
-    def _loss(self, pred, yv, dpred, N, O, H, W, Hc, Wc, wts):
+    def set_loss(self, spec: Optional[LossSpec]):
+        """Switch the loss (between epochs, say): a loss.LossSpec -- coefficients of the MSE, L1 and Huber terms, the Huber
+        threshold, output and step weights -- or None for the reference's MSE + L1 through the entries it has always run.
+        The values are validated by LossSpec, the lengths of its weights against the model's outputs and the window at the
+        next step / evaluate; step weights need ``sequence_loss``.  epoch_stats() then reports the mean of the configured
+        loss.  Under data parallelism the spec is NOT broadcast: every rank must be given the same one."""
+        if spec is not None and not isinstance(spec, LossSpec):
+            raise TypeError("loss must be a loss.LossSpec or None")
+        if spec is not None and spec.step_weights is not None and not self.sequence_loss:
+            raise ValueError("step_weights need FusedTrainer(sequence_loss=True): the last-step loss has one step")
+        self._spec = spec
+
+    def _loss_spec(self, O: int, T: int):
+        """the nint_loss_spec of this call (its weight vector over t*O + o with sequence_loss, over o without), or None"""
+        return None if self._spec is None else self._spec.on(self.device, O, T if self.sequence_loss else None)
+
+    def _loss(self, pred, yv, dpred, N, O, H, W, Hc, Wc, wts, spec=None):
         """the stand-alone loss launch of the three-launch paths"""
-        if wts is None:
+        if spec is not None:
+            wgt, wsum = wts if wts is not None else (None, 0.0)
+            check(self.lib.nint_loss_crop_spec(ptr(pred), ptr(yv), ptr(wgt), wsum, C.byref(spec), ptr(dpred), ptr(self.scratch),
+                                               ptr(self.stats), N, O, H, W, self.halo[0], self.halo[1], Hc, Wc, stream_ptr()),
+                  "nint_loss_crop_spec")
+        elif wts is None:
             check(self.lib.nint_loss_mse_l1_crop(ptr(pred), ptr(yv), ptr(dpred), ptr(self.scratch), ptr(self.stats),
                                                  N, O, H, W, self.halo[0], self.halo[1], Hc, Wc, stream_ptr()),
                   "nint_loss_mse_l1_crop")
@@ -159,6 +187,7 @@ class FusedTrainer:
         eng = m._engine(self.device)
         B, T, _, H, W = X.shape
         wts = self._loss_weights(y.shape[-2], y.shape[-1])      # (validates the map's shape before anything is acquired)
+        spec = self._loss_spec(m.conv.weight.shape[0], T)       # (and the spec's lengths)
         ws = eng.acquire(B, T, H, W, train, False)
         wb_w = [c.conv.weight for c in m.layers]
         wb_b = [c.conv.bias for c in m.layers]
@@ -180,7 +209,7 @@ class FusedTrainer:
             if self._dpred is None or self._dpred.shape != pred.shape:
                 self._dpred = torch.empty_like(pred)
             dpred = self._dpred
-        self._loss(pred, yv, dpred, B, O, H, W, Hc, Wc, wts)
+        self._loss(pred, yv, dpred, B, O, H, W, Hc, Wc, wts, spec)
         return eng, ws, pred, dpred
 
     def reset_state(self):
@@ -212,7 +241,7 @@ class FusedTrainer:
         for v in views:
             v.masked_fill_(bad, 0)
 
-    def _head_pass(self, eng, ws, yv, B, T, O, H, W, Hc, Wc, wts, acc: bool):
+    def _head_pass(self, eng, ws, yv, B, T, O, H, W, Hc, Wc, wts, acc: bool, spec=None):
         """head forward + crop + loss + d loss / d pred + dL/dh + the head's weight gradient on the workspace's last h (every
         h with sequence_loss); `acc`: the head's gradients are added to the bucket (a later micro-batch of a group)"""
         m, sq = self.model, self.sequence_loss
@@ -220,22 +249,23 @@ class FusedTrainer:
             self._dpred = torch.empty(B * (T if sq else 1), O, H, W, dtype=torch.float32, device=self.device)
         dpred = self._dpred
         hk = dict(dw_out=self._dw_head, db_out=self._db_head, accumulate=acc)
+        sk = {} if spec is None else dict(spec=spec)             # (None: today's calls, argument for argument)
         if sq:
             # the same over every step: one pass writes the loss, d loss / d pred (image order t*B + b, which the head's
             # weight-gradient kernels reduce as T*B images) and the per-step dL/dh that BPTT adds at each t
-            fused = eng.head_loss_seq_fused(ws, m.conv.weight, m.conv.bias, yv, dpred, self.scratch, self.stats, self.halo, Hc, Wc, wts)
+            fused = eng.head_loss_seq_fused(ws, m.conv.weight, m.conv.bias, yv, dpred, self.scratch, self.stats, self.halo, Hc, Wc, wts, **sk)
             if fused:
                 eng.head_backward(ws, m.conv.weight, dpred, write_dh=False, images=(B, T * B), **hk)
             else:
                 seq = eng.head_forward_seq(ws, m.conv.weight, m.conv.bias)
-                self._loss(seq, yv, dpred, B, T * O, H, W, Hc, Wc, wts)
+                self._loss(seq, yv, dpred, B, T * O, H, W, Hc, Wc, wts, spec)
                 eng.head_backward_seq(ws, m.conv.weight, dpred.view(B, T * O, H, W), None, **hk)
         else:
             # head forward + crop + loss + dpred + dL/dh in one pass; the prediction itself is never materialised
-            fused = eng.head_loss_fused(ws, m.conv.weight, m.conv.bias, yv, dpred, self.scratch, self.stats, self.halo, Hc, Wc, wts)
+            fused = eng.head_loss_fused(ws, m.conv.weight, m.conv.bias, yv, dpred, self.scratch, self.stats, self.halo, Hc, Wc, wts, **sk)
             if not fused:
                 pred = eng.head_forward(ws, m.conv.weight, m.conv.bias)
-                self._loss(pred, yv, dpred, B, O, H, W, Hc, Wc, wts)
+                self._loss(pred, yv, dpred, B, O, H, W, Hc, Wc, wts, spec)
             eng.head_backward(ws, m.conv.weight, dpred, write_dh=not fused, **hk)
 
     def step(self, X: torch.Tensor, y: torch.Tensor, reset=None) -> torch.Tensor:
@@ -248,6 +278,7 @@ class FusedTrainer:
         B, T, _, H, W = X.shape
         L = m.num_layers
         wts = self._loss_weights(y.shape[-2], y.shape[-1])      # (validates the map's shape before anything is acquired)
+        spec = self._loss_spec(m.conv.weight.shape[0], T)       # (and the spec's lengths)
         if reset is not None and not self.stateful:
             raise ValueError("step(reset=...) needs FusedTrainer(stateful=True)")
         k = self.accumulate_steps
@@ -266,7 +297,7 @@ class FusedTrainer:
         if plan is not None:
             mark()
             eng.pack_weights([c.conv.weight for c in m.layers], [c.conv.bias for c in m.layers])
-            self._segments(eng, X, yv, plan, carried, acc, wts)
+            self._segments(eng, X, yv, plan, carried, acc, wts, spec)
             return self._finish(last)
         ws = eng.acquire(B, T, H, W, True, self.stateful)
         pb, pm = self._probe
@@ -281,7 +312,7 @@ class FusedTrainer:
             eng.save_state(ws, carried)          # slot T -> carried state; BPTT below stops at the chunk start
             self._drop_nonfinite_lanes(carried)
         mark()
-        self._head_pass(eng, ws, yv, B, T, O, H, W, Hc, Wc, wts, acc)
+        self._head_pass(eng, ws, yv, B, T, O, H, W, Hc, Wc, wts, acc, spec)
         mark()
         bk = dict(zero_state_grads=range(L), dW_out=self._dW, db_out=self._db, seq_grads=sq, accumulate=acc)
         if last and self.distributed and self.overlap_allreduce and L > 1 and pb is None:
@@ -314,7 +345,7 @@ class FusedTrainer:
         self._mark()
         return self.scratch[0]
 
-    def _segments(self, eng, X, yv, plan, carried, acc: bool, wts):
+    def _segments(self, eng, X, yv, plan, carried, acc: bool, wts, spec=None):
         """Checkpointed BPTT of one window: the gradients of the whole window into the bucket, with S = T / n
         steps resident instead of T.
           1. forward sweep: segments 0 .. n-2 in an S-step inference workspace (no stash, no dG), each from the state the one
@@ -354,7 +385,7 @@ class FusedTrainer:
             self._drop_nonfinite_lanes(self.state)
         mark()
         O = m.conv.weight.shape[0]
-        self._head_pass(eng, ws, yv, B, S, O, H, W, yv.shape[-2], yv.shape[-1], wts, acc)
+        self._head_pass(eng, ws, yv, B, S, O, H, W, yv.shape[-2], yv.shape[-1], wts, acc, spec)
         mark()
         eng.backward(ws, False, zero_state_grads=range(L), dW_out=self._dW, db_out=self._db, accumulate=acc)
         for j in range(n - 2, -1, -1):
@@ -391,7 +422,7 @@ class FusedTrainer:
 
     def epoch_stats(self, pooled: bool = False):
         """One device->host read per epoch.  Returns what the reference logs over everything accumulated since
-        reset_stats(): (mean of the per-batch losses, mean of the per-batch sklearn ``r2_score``) -- train.py:113-117;
+        reset_stats(): (mean of the per-batch losses -- of the configured loss, with ``loss`` / set_loss --, mean of the per-batch sklearn ``r2_score``) -- train.py:113-117;
         for the validation loop at batch size 1 that is the mean of per-sample R2 (utils.py:73-75).  Under DDP
         the sums are all-reduced first, so the means run over every rank's batches.
         ``pooled=True`` appends the pooled R2 over all elements seen (1 - sum d^2 / sum (y - mean y)^2)."""

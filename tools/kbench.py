@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-kernel micro-benchmark at the bench workload's shapes (HIP events on the launch stream).
-    python tools/kbench.py [--dtype bf16] [--batch 8] [--iters 20] [--only fwd0,dgrad0,head_skill,...]
+    python tools/kbench.py [--dtype bf16] [--batch 8] [--iters 20] [--only fwd0,dgrad0,head_skill,head_loss,head_loss_spec,...]
 Prints one line per kernel: average ms, algorithmic TFLOP/s (or GB/s)."""
 import argparse
 import ctypes as C
@@ -150,7 +150,7 @@ def main():
         alg = B * T * args.C * H * W
         run("preproc_slab", lambda: sb.fill_slab(eng, ws), None, alg * (4 + es))     # 4 B in + ET out per element
         run("preproc_nchw", lambda: ds.device_batch(idx), None, alg * 8)
-    if not only or only & {"head_skill", "skill_plain", "head_fwd"}:
+    if not only or only & {"head_skill", "skill_plain", "head_fwd", "head_loss", "head_loss_spec", "head_loss_spec3"}:
         # evaluation: the head on the last step's images + crop + the f64 skill sums in one pass (nint_head_skill_accum), and the
         # same sums from a prediction in memory (nint_skill_accum), one slot, cos-latitude row weights
         O, oy, ox = args.O, 5, 5
@@ -176,6 +176,31 @@ def main():
 
         def skill_plain():
             assert lib.nint_skill_accum(P(pred), P(y), None, 1, P(rw), P(pix), P(smp), P(scr), nb, B, O, H, W, oy, ox, Hc, Wc, st) == 0
+        # training: head forward + crop + loss + d loss / d pred + dL/dh in one pass -- the entry the default step runs
+        # (nint_head_loss_fused), and the configurable loss's general body (nint_head_loss_fused_spec) on the same data: with
+        # spec (1, 1, 0), the same loss, and with all three terms plus output weights
+        from nasa_niswan_amd import _lib as L
+        dpl = torch.empty(B, O, H, W, device="cuda")
+        dhl = torch.empty(B * comp_px * ly.Chp * es, dtype=torch.uint8, device="cuda")
+        lsc = torch.zeros(L.NINT_LOSS_SPEC_SCRATCH_FLOATS, device="cuda")
+        lst = torch.zeros(L.NINT_LOSS_STATS, dtype=torch.float64, device="cuda")
+        owv = (0.5 + torch.rand(O, device="cuda")).float()
+        sp110, sp111 = L.NintLossSpec(), L.NintLossSpec()
+        sp110.mse, sp110.l1, sp110.huber, sp110.delta = 1.0, 1.0, 0.0, 1.0
+        sp111.mse, sp111.l1, sp111.huber, sp111.delta = 1.0, 1.0, 1.0, 0.75
+        sp111.ow, sp111.now, sp111.osum = owv.data_ptr(), O, float(owv.double().sum())
+
+        def head_loss():
+            assert lib.nint_head_loss_fused(P(ws.h[-1]), T * B, B, ly.Ch, ly.Chp, O, P(hw), P(hb), P(y), P(dpl), P(dhl), P(lsc), P(lst), g,
+                                            oy, ox, Hc, Wc, eng.dt, st) == 0
+
+        def head_loss_spec(sp=sp110):
+            assert lib.nint_head_loss_fused_spec(P(ws.h[-1]), T * B, B, ly.Ch, ly.Chp, O, P(hw), P(hb), P(y), None, 0.0, C.byref(sp),
+                                                 P(dpl), P(dhl), P(lsc), P(lst), g, oy, ox, Hc, Wc, eng.dt, st) == 0
+        hl_bytes = B * comp_px * (2 * ly.Chp * es + O * 4) + y.numel() * 4      # h in, dh out, dpred out, the targets
+        run("head_loss", head_loss, None, hl_bytes)
+        run("head_loss_spec", head_loss_spec, None, hl_bytes)
+        run("head_loss_spec3", lambda: head_loss_spec(sp111), None, hl_bytes)
         part = 2 * nb                                             # the per-wave partial rows, written and read back
         maps = 2 * pix.numel() * 8 + y.numel() * 4 + part         # pix read + written once per call, the targets
         run("head_fwd", head_fwd, None, B * comp_px * (ly.Chp * es + O * 4))
