@@ -318,7 +318,12 @@ int nint_debug_seq_plan(const nint_seq* s /*host*/, int bwd, nint_launch_rec* ou
  * element kernels (a plain chain over c < Ch: other roundings) beyond it; the fused entries (nint_head_loss_fused,
  * nint_head_loss_seq_fused, their _weighted twins, nint_head_skill_accum) return NINT_E_SHAPE beyond it.  So wherever a fused
  * entry runs, its separate launches run the same bodies, and "bit for bit" below holds for every shape a fused entry accepts
- * (O = 200 on 128 channels included: a 100 KiB weight image). */
+ * (O = 200 on 128 channels included: a 100 KiB weight image).
+ * The staged dot product (normative; every staged body -- nint_head_fwd[_seq], every fused loss entry, nint_head_skill_accum --
+ * gives these bits): in f32, the accumulator starts from b[o] (0 without a bias); the CHV staged channels (zeros past Ch) join
+ * it in channel order; each of the first CHV - 12 by one fused multiply-add, each of the last 12 as a rounded product
+ * followed by a rounded add.  (The library's source writes out the unfused tail; that the other products are fused is the
+ * compiler's contraction, held by the bit tests of tests/, which carry data in the last 12 staged channels at every CHV.) */
 /* pred (N,O,H,W) f32 = w (O,Ch) . h + b  from halo-slab images [n0, n0+N) */
 int nint_head_fwd(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w, const float* b,
                   float* pred, const nint_geom* g, int dtype, void* stream);

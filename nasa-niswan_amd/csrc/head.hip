@@ -1,7 +1,12 @@
-// head.hip -- the 1x1 head on the top layer's hidden state (forward, d/dh, weight / bias gradient), the crop + MSE + L1
-// loss, and the two fused into one pass over the pixels; each for one step's images or for every step of a sequence.
-// They share head_stage_weights, LOSS_BLOCKS_MAX and loss_final_kernel.  Every kernel body is a __forceinline__ device
-// function under ONE __global__ wrapper templated on SEQ: the register allocation depends on that function boundary.
+// head.hip -- the 1x1 head on the top layer's hidden state (forward, d/dh, weight / bias gradient), the crop loss (the
+// reference's MSE + L1, with a weight map, or the configurable mix: one kernel pair over a compile-time "loss element"), and
+// the two fused into one pass over the pixels; each for one step's images or for every step of a sequence.  They share
+// head_stage_weights, head_dot, the loss elements, LOSS_WG_FOLD, LOSS_BLOCKS_MAX and loss_final_kernel.  Every kernel body is
+// a __forceinline__ device function under ONE __global__ wrapper templated on SEQ: the register allocation depends on that
+// function boundary.  So does all compiled code on what stands behind a call before the inliner runs: the early passes see
+// the kernel without it.  Whatever the loss elements' functions hold is therefore plain arithmetic on values -- no index
+// arithmetic, no object with a constructor, sums in and out by value -- and the instances that existed before the elements
+// compile to the instruction streams they had (profiles/head_refactor_asm.txt).
 #include "nint_common.h"
 #include <algorithm>
 #include <cfloat>
@@ -23,6 +28,41 @@ __device__ __forceinline__ void head_stage_weights(float* w_s, const float* __re
   __syncthreads();
 }
 
+// THE dot product of the staged head (normative; restated in nint.h and DESIGN.md 4.14):
+//   the accumulator starts from the bias (0 without one); the CHV staged channels join it in order; the first CHV - 12 by
+//   fused multiply-add (one rounding), the last 12 as a rounded product, then a rounded add.
+// (What the compiler made of `acc += w * h` in head_fwd_kernel when the goldens pinned these bits: the vectoriser packs the
+// last products, v_pk_mul_f32 + v_add_f32.)  head_fwd_body, SkillPredHead and head_loss_body<LossSpec> call this function, so
+// they agree by construction.  The unfused tail -- the part an optimiser decided differently from one body to the next -- is
+// written out with contraction off.  The fused part is `acc += w * h` with contraction on, NOT __builtin_fmaf: the builtin
+// gives the same instructions in another schedule, which costs head_skill_accum_kernel a wave per SIMD at every CHV and
+// head_fwd_kernel up to 14 VGPRs, while this form compiles head_fwd_kernel to the instruction stream it had.  The fused
+// pass of LossPlain and LossMap still holds the plain loop (Elem::HEAD_DOT = false): either form of this function costs its
+// bf16 CHV = 32 instances -- the default step's -- a wave per SIMD (96 -> 108 VGPRs).  profiles/EXPERIMENTS.md has the
+// numbers.  So the SOURCE enforces the unfused tail only, and only where this function is called; the fused part here, and the
+// whole chain in that loop, are what the optimiser forms, held to the definition by the fused-vs-launches and skill bit tests,
+// whose tables have data in the last 12 staged channels (Ch > CHV - 12) at every CHV in f32 and bf16 (the "tail" cases of
+// tests/test_gpu_small_branches.py FUSED_CASES and the Ch = CHV cases beside them).
+#define HEAD_DOT_UNFUSED_TAIL 12
+template <int CHV>
+__device__ __forceinline__ float head_dot(float acc, const float* w_row, const float (&hv)[CHV]) {
+  const f32x4_t* wr = (const f32x4_t*)w_row;
+#pragma unroll
+  for (int c = 0; c < CHV - HEAD_DOT_UNFUSED_TAIL; c += 4) {
+#pragma clang fp contract(fast)
+    const f32x4_t wv = wr[c / 4];
+    acc += wv[0] * hv[c]; acc += wv[1] * hv[c + 1]; acc += wv[2] * hv[c + 2]; acc += wv[3] * hv[c + 3];
+  }
+#pragma unroll
+  for (int c = CHV - HEAD_DOT_UNFUSED_TAIL; c < CHV; c += 4) {
+#pragma clang fp contract(off)
+    const f32x4_t wv = wr[c / 4];
+    const float m0 = wv[0] * hv[c], m1 = wv[1] * hv[c + 1], m2 = wv[2] * hv[c + 2], m3 = wv[3] * hv[c + 3];
+    acc = m0 + acc; acc = m1 + acc; acc = m2 + acc; acc = m3 + acc;
+  }
+  return acc;
+}
+
 // CHV of a padded channel count (<= 128), and the host's pick of that instance: f(std::integral_constant<int, CHV>)
 static inline int head_chv(int Chp) { return Chp <= 32 ? 32 : (Chp <= 64 ? 64 : 128); }
 template <class F> static inline auto head_by_chv(int Chp, F&& f) {
@@ -36,9 +76,12 @@ template <class F> static inline auto head_by_chv(int Chp, F&& f) {
 // keep nothing beside the weights, but take the same rule: wherever a fused pass runs, its separate launches run the SAME
 // bodies and give the same bits (the trainer and the skill path switch between the two silently).  Beyond it: the wide kernels.
 #define HEAD_OCH 64
+static inline size_t head_loss_lds(int Chp, int O) {                  // the dynamic LDS of the fused head + loss pass
+  return ((size_t)O * head_chv(Chp) + (size_t)(O < HEAD_OCH ? O : HEAD_OCH) * 64) * sizeof(float);
+}
 static inline bool head_staged_holds(int Chp, int O) {
   if (Chp > 128 || Chp % 4 != 0) return false;
-  return ((size_t)O * head_chv(Chp) + (size_t)(O < HEAD_OCH ? O : HEAD_OCH) * 64) * sizeof(float) + 8192 <= 160 * 1024;
+  return head_loss_lds(Chp, O) + 8192 <= 160 * 1024;
 }
 
 // The sequence entries (nint_head_fwd_seq and its kin) run the same bodies over all T*B images of the top layer's slab; only the
@@ -71,16 +114,7 @@ __device__ __forceinline__ void head_fwd_body(float* w_s, const void* __restrict
     hv[c] = v[0]; hv[c + 1] = v[1]; hv[c + 2] = v[2]; hv[c + 3] = v[3];
   }
   float* out = pred + (head_image<SEQ>(n, Bs, N / (SEQ ? Bs : 1)) * O * H + y) * W + x;
-  for (int o = 0; o < O; ++o) {
-    float acc = b ? b[o] : 0.f;
-    const f32x4_t* wr = (const f32x4_t*)(w_s + o * CHV);
-#pragma unroll
-    for (int c = 0; c < CHV; c += 4) {
-      const f32x4_t wv = wr[c / 4];
-      acc += wv[0] * hv[c]; acc += wv[1] * hv[c + 1]; acc += wv[2] * hv[c + 2]; acc += wv[3] * hv[c + 3];
-    }
-    out[(size_t)o * H * W] = acc;
-  }
+  for (int o = 0; o < O; ++o) out[(size_t)o * H * W] = head_dot<CHV>(b ? b[o] : 0.f, w_s + o * CHV, hv);
 }
 
 template <int DT, int CHV, bool SEQ>
@@ -595,354 +629,88 @@ extern "C" int nint_head_bwd_seq(const void* h_slab, int B, int T, int Ch, int C
 }
 
 // ------------------------------------------------------------------------------ loss
-// train.py:102,105: crop, MSELoss + L1Loss (mean).  Two launches on the same stream:
-//  (1) per-block partial sums in double (fixed order), (2) one block folds them, writes
-//  the loss and adds to the 5 running statistics.  dpred = (2(p-y) + sign(p-y)) / n on the crop.
-// WGT (the _weighted entries; nint.h has the arithmetic): every term of a crop cell carries the cell's weight wgt[cy][cx] as
-// a double factor, n becomes cnt = N * O * sum(wgt), and a cell of weight 0 is skipped -- its target is not read.  The
-// unweighted instances receive (wgt, cnt) without reading them; with wgt = 1 the weighted ones give the same bits.
-template <bool WGT>
-__global__ __launch_bounds__(1024) void loss_partial_kernel(const float* __restrict__ pred, const float* __restrict__ y,
-                                                           float* __restrict__ dpred, double* __restrict__ partial,
-                                                           int N, int O, int H, int W, int oy, int ox, int Hc, int Wc,
-                                                           const float* __restrict__ wgt, double cnt) {
-  const size_t total = (size_t)N * O * H * W;
-  const double inv_n = 1.0 / (WGT ? cnt : (double)N * O * Hc * Wc);
-  double s2 = 0, s1 = 0, sy = 0, syy = 0;
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    const int x = i % W;
-    size_t r = i / W;
-    const int yy = r % H;
-    const size_t no = r / H;
-    const int cy = yy - oy, cx = x - ox;
-    float g = 0.f;
-    if (cy >= 0 && cy < Hc && cx >= 0 && cx < Wc) {
-      if constexpr (WGT) {
-        const float wf = wgt[(size_t)cy * Wc + cx];
-        if (wf != 0.f) {
-          const double wd = wf;
-          const float t = y[(no * Hc + cy) * Wc + cx];
-          const float d = pred[i] - t;
-          s2 += wd * ((double)d * d);
-          s1 += wd * fabs((double)d);
-          sy += wd * t;
-          syy += wd * ((double)t * t);
-          g = (float)(((2.0 * d + (d > 0.f ? 1.0 : (d < 0.f ? -1.0 : 0.0))) * inv_n) * wd);
-        }
-      } else {
-        const float t = y[(no * Hc + cy) * Wc + cx];
-        const float d = pred[i] - t;
-        s2 += (double)d * d;
-        s1 += fabs((double)d);
-        sy += t;
-        syy += (double)t * t;
-        g = (float)((2.0 * d + (d > 0.f ? 1.0 : (d < 0.f ? -1.0 : 0.0))) * inv_n);
-      }
-    }
-    if (dpred) dpred[i] = g;
+// train.py:102,105: crop, MSELoss + L1Loss (mean), and its configurable form (nint_loss_spec; nint.h has the arithmetic of
+// all three).  Two launches on the same stream: (1) per-workgroup partial sums in double (fixed order), (2) one workgroup
+// folds them, writes the loss and adds to the running statistics.  Either alone (loss_partial_kernel: pred from memory) or
+// fused with the head (head_loss_kernel below).  What differs between the entries is the LOSS ELEMENT, a compile-time policy:
+//   LossPlain  the reference's loss: term d^2 + |d|, dpred = (2 d + sgn d) / n on the crop, n = N * O * Hc * Wc.
+//   LossMap    the _weighted entries: every term of a crop cell carries the cell's weight wgt[cy][cx] as a double factor, n
+//              becomes cnt = N * O * sum(wgt).  With wgt = 1 it gives LossPlain's bits.
+//   LossSpec   term a d^2 + b |d| + c H(d) with coefficients known at run time; the weight is the product of the cell's
+//              (optional map) and the output's (optional ow; per (step, output) in the sequence entry).  A zero coefficient
+//              takes its term out (flags, not products: 0 * inf is NaN).  Spec (1, 1, 0) gives the bits of the other two.
+// A policy is built inside the kernel from the kernel's arguments (wgt, cnt[, LossSpecK]) and supplies
+//   NS, Sums, add     the running sums of a thread (sum-of-squares, sum |d|, sum y, sum y^2[, sum H]) and one element's terms
+//   inv_n             1 / n of the gradient
+//   CELL, cell        whether cells carry a weight, and the weight of crop cell cy * Wc + cx; a cell of weight 0 leaves the
+//                     crop, so its targets are not read
+//   OW, out           whether outputs carry a weight, and the weight of (step, output); weight 0 reads no target
+//   weight, grad      the element's f64 weight from the two, and d loss / d pred
+//   HEAD_DOT          whether the fused pass forms its prediction by head_dot or by the loop it had (see head_dot)
+//   Mix               what closes the fold: NS and the loss from the folded sums
+struct LossMseL1 {                               // what LossPlain and LossMap share
+  static constexpr int NS = 4;
+  static constexpr bool OW = false;
+  static constexpr bool HEAD_DOT = false;        // the fused pass keeps the loop it had: head_dot there costs the default step a wave per SIMD
+  using Mix = LossMseL1;
+  struct Sums { double s2, s1, sy, syy; };      // (an aggregate, zeroed by `= {}`: a constructor call would stand between the kernel and its early passes)
+  __device__ __forceinline__ double mix(double s0, double s1, double, double count) const { return s0 / count + s1 / count; }
+  __device__ __forceinline__ float out(size_t, int, int) const { return 1.f; }
+  __device__ __forceinline__ double weight(double wd, float) const { return wd; }
+};
+
+struct LossPlain : LossMseL1 {                   // (receives wgt and cnt without reading them)
+  static constexpr bool CELL = false;
+  __device__ __forceinline__ LossPlain(const float*, double) {}
+  __device__ __forceinline__ double inv_n(int N, int O, int Hc, int Wc) const { return 1.0 / ((double)N * O * Hc * Wc); }
+  __device__ __forceinline__ float cell(size_t) const { return 1.f; }
+  __device__ __forceinline__ Sums add(Sums s, double, float d, float t) const {
+    s.s2 += (double)d * d;
+    s.s1 += fabs((double)d);
+    s.sy += t;
+    s.syy += (double)t * t;
+    return s;
   }
-  __shared__ double red[4][1024];
-  red[0][threadIdx.x] = s2; red[1][threadIdx.x] = s1; red[2][threadIdx.x] = sy; red[3][threadIdx.x] = syy;
-  __syncthreads();
-  for (int s = blockDim.x >> 1; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s)
-      for (int q = 0; q < 4; ++q) red[q][threadIdx.x] += red[q][threadIdx.x + s];
-    __syncthreads();
+  __device__ __forceinline__ float grad(float d, double inv_n, double) const {
+    return (float)((2.0 * d + (d > 0.f ? 1.0 : (d < 0.f ? -1.0 : 0.0))) * inv_n);
   }
-  if (threadIdx.x < 4) partial[blockIdx.x * 4 + threadIdx.x] = red[threadIdx.x][0];
-}
+};
 
-__global__ __launch_bounds__(256) void loss_final_kernel(const double* __restrict__ partial, int nblocks, float* __restrict__ loss_out,
-                                                         double* __restrict__ stats, double count) {
-  // thread (b, q) = one partial; fixed-order tree over the blocks
-  __shared__ double red[4][256];
-  for (int q = 0; q < 4; ++q) {
-    double s = 0;
-    for (int b = threadIdx.x; b < nblocks; b += blockDim.x) s += partial[b * 4 + q];
-    red[q][threadIdx.x] = s;
+struct LossMap : LossMseL1 {
+  static constexpr bool CELL = true;
+  const float* wgt; double cnt;                  // cnt = N * O * wsum
+  __device__ __forceinline__ LossMap(const float* wgt_, double cnt_) : wgt(wgt_), cnt(cnt_) {}
+  __device__ __forceinline__ double inv_n(int, int, int, int) const { return 1.0 / cnt; }
+  __device__ __forceinline__ float cell(size_t cyx) const { return wgt[cyx]; }
+  __device__ __forceinline__ Sums add(Sums s, double wd, float d, float t) const {
+    s.s2 += wd * ((double)d * d);
+    s.s1 += wd * fabs((double)d);
+    s.sy += wd * t;
+    s.syy += wd * ((double)t * t);
+    return s;
   }
-  __syncthreads();
-  for (int st = 128; st > 0; st >>= 1) {
-    if ((int)threadIdx.x < st)
-      for (int q = 0; q < 4; ++q) red[q][threadIdx.x] += red[q][threadIdx.x + st];
-    __syncthreads();
+  __device__ __forceinline__ float grad(float d, double inv_n, double wd) const {
+    return (float)(((2.0 * d + (d > 0.f ? 1.0 : (d < 0.f ? -1.0 : 0.0))) * inv_n) * wd);
   }
-  if (threadIdx.x == 0) {
-    const double s0 = red[0][0], s1 = red[1][0], s2 = red[2][0], s3 = red[3][0];
-    const double loss = s0 / count + s1 / count;
-    if (loss_out) loss_out[0] = (float)loss;
-    if (stats) {
-      stats[0] += s0; stats[1] += s1; stats[2] += s2; stats[3] += s3; stats[4] += count;
-      // the reference's per-batch statistics (train.py:113-117, utils.py:73-75): it sums loss.item() and
-      // sklearn r2_score(y, pred) of every batch and divides by the number of batches
-      const double ss_tot = s3 - s2 * s2 / count;
-      const double r2 = ss_tot > 0.0 ? 1.0 - s0 / ss_tot : (s0 == 0.0 ? 1.0 : 0.0);   // sklearn's constant-target convention
-      stats[5] += loss; stats[6] += r2; stats[7] += 1.0;
-    }
-  }
-}
+};
 
-// partial sums live in a small static device buffer per call site: the caller passes it as the
-// tail of `stats` would complicate the ABI, so the kernel pair uses dpred-independent scratch
-// carved from loss_out[1..]: loss_out must have room for 1 + 2*LOSS_BLOCKS*4 floats.
-#define LOSS_BLOCKS 256
-#define LOSS_BLOCKS_MAX ((NINT_LOSS_SCRATCH_FLOATS - 2) / 8)     // what the caller's scratch holds: 4 doubles per workgroup
-// WGT: cnt = N * O * wsum of the weighted entry (the unweighted kernels form N * O * Hc * Wc themselves)
-template <bool WGT>
-static int loss_impl(const float* pred, const float* y, const float* wgt, double cnt, float* dpred, float* loss_out, double* stats,
-                     int N, int O, int H, int W, int oy, int ox, int Hc, int Wc, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  double* partial = (double*)(loss_out + 2);   // loss_out: [0]=loss, [1]=pad, [2..] = 256*4 doubles
-  hipLaunchKernelGGL(loss_partial_kernel<WGT>, dim3(LOSS_BLOCKS), dim3(1024), 0, st, pred, y, dpred, partial, N, O, H, W, oy, ox, Hc, Wc, wgt, cnt);
-  NINT_LAUNCH_CHECK();
-  hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(256), 0, st, partial, LOSS_BLOCKS, loss_out, stats, WGT ? cnt : (double)N * O * Hc * Wc);
-  NINT_LAUNCH_CHECK();
-  return NINT_OK;
-}
-
-extern "C" int nint_loss_mse_l1_crop(const float* pred, const float* y, float* dpred, float* loss_out, double* stats,
-                                     int N, int O, int H, int W, int oy, int ox, int Hc, int Wc, void* stream) {
-  if (!pred || !y || !loss_out || N <= 0 || O <= 0 || oy < 0 || ox < 0 || oy + Hc > H || ox + Wc > W) return NINT_E_ARG;
-  if ((((uintptr_t)loss_out) & 7) != 0) return NINT_E_ALIGN;
-  return loss_impl<false>(pred, y, nullptr, 0.0, dpred, loss_out, stats, N, O, H, W, oy, ox, Hc, Wc, stream);
-}
-
-// the weight map of the _weighted entries: present, and a total that is positive and finite (!(wsum > 0) also catches NaN)
-static inline bool loss_weights_ok(const float* wgt, double wsum) { return wgt && wsum > 0.0 && wsum <= DBL_MAX; }
-
-extern "C" int nint_loss_mse_l1_crop_weighted(const float* pred, const float* y, const float* wgt, double wsum, float* dpred,
-                                              float* loss_out, double* stats, int N, int O, int H, int W, int oy, int ox,
-                                              int Hc, int Wc, void* stream) {
-  if (!pred || !y || !loss_out || N <= 0 || O <= 0 || oy < 0 || ox < 0 || oy + Hc > H || ox + Wc > W) return NINT_E_ARG;
-  if (Hc <= 0 || Wc <= 0 || !loss_weights_ok(wgt, wsum)) return NINT_E_ARG;
-  if ((((uintptr_t)loss_out) & 7) != 0 || (((uintptr_t)wgt) & 3) != 0) return NINT_E_ALIGN;
-  return loss_impl<true>(pred, y, wgt, (double)N * O * wsum, dpred, loss_out, stats, N, O, H, W, oy, ox, Hc, Wc, stream);
-}
-
-// ------------------------------------------------------------------------------ head + loss, fused (training)
-// train.py:96-109 around the 1x1 head in ONE pass over the pixels: pred = w . h + b (model.py:274), crop, the MSE+L1
-// partial sums (train.py:102,105), d loss / d pred, and dL/dh = w^T . dpred.  One thread per pixel (grid-stride):
-// the channel vector is read once, pred never goes to memory, dpred is written for the head's weight gradient.
-// Same arithmetic, in the same order, as head_fwd_kernel -> loss_partial_kernel -> head_bwd_dh_kernel.
-// (HEAD_OCH outputs per chunk: head_staged_holds)
-// SEQ (nint_head_loss_seq_fused): the images are all T*B steps of the slab, image n = t*B + b; the targets are (B, T, O, Hc, Wc),
-// plane block b*T + t (head_image); dpred and dh stay in image order, which is what the weight-gradient stage and BPTT read.
-// WGT (the _weighted entries): loss_partial_kernel<true>'s terms; the pixel's weight is read once per pass, next to the crop
-// test, and a cell of weight 0 leaves the crop: neither its targets nor its prediction enter anything.
-template <int DT, int CHV, bool SEQ, bool WGT>
-__device__ __forceinline__ void head_loss_fused_body(char* smem_hl, const void* __restrict__ h, int n0, int N, int Ch, int Chp, int O,
-                                                     const float* __restrict__ w, const float* __restrict__ b,
-                                                     const float* __restrict__ y, float* __restrict__ dpred,
-                                                     void* __restrict__ dh, double* __restrict__ partial, int H, int W,
-                                                     int P, int Hh, int Wh, int oy, int ox, int Hc, int Wc, int Bs,
-                                                     const float* __restrict__ wgt, double cnt) {
-  // A workgroup takes 64 pixels per pass (grid-stride).  Phase 1: wave q runs the outputs [q*OG, (q+1)*OG) of every pixel
-  // (lane = pixel): pred, loss terms, d loss / d pred -> dpred and, through LDS, to phase 2: wave q accumulates the
-  // channels [q*CHV/4, (q+1)*CHV/4) of dL/dh over ALL outputs in output order.  (One thread per pixel for all outputs --
-  // the first version -- is a chain of O dependent round trips on 1/4 of the threads: 50 us at B = 8, 44 us at B = 1.)
-  float* w_s = (float*)smem_hl;                  // [O][CHV], zero padded (head_stage_weights)
-  float* gq_s = w_s + O * CHV;                   // [min(O, HEAD_OCH)][64]
-  head_stage_weights<CHV>(w_s, w, O, Ch);
-  const int lane = threadIdx.x & 63;
-  const int q = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // (scalar: the weight reads below stay scalar loads)
-  const size_t npix = (size_t)N * H * W;
-  const double inv_n = 1.0 / (WGT ? cnt : (double)N * O * Hc * Wc);
-  constexpr int CQ = CHV / 4;                    // channels per wave in phase 2
-  double s2 = 0, s1 = 0, sy = 0, syy = 0;
-  for (size_t p0 = (size_t)blockIdx.x * 64; p0 < npix; p0 += (size_t)gridDim.x * 64) {
-    const size_t pix = p0 + lane;
-    const bool live = pix < npix;
-    const size_t pc = live ? pix : npix - 1;
-    const int x = pc % W;
-    size_t r = pc / W;
-    const int yy = r % H;
-    const int n = r / H;
-    const size_t hb = ((((size_t)(n0 + n)) * Hh + (yy + P)) * Wh + (x + P)) * Chp;
-    float hv[CHV];
-#pragma unroll
-    for (int c = 0; c < CHV; c += 4) {
-      const f32x4_t v = (c < Chp) ? load_vec4<DT>(h, hb + c) : (f32x4_t){0.f, 0.f, 0.f, 0.f};
-      hv[c] = v[0]; hv[c + 1] = v[1]; hv[c + 2] = v[2]; hv[c + 3] = v[3];
-    }
-    const int cy = yy - oy, cx = x - ox;
-    bool in = live && cy >= 0 && cy < Hc && cx >= 0 && cx < Wc;
-    double wd = 1.0;
-    if constexpr (WGT) {
-      const float wf = in ? wgt[(size_t)cy * Wc + cx] : 0.f;
-      in = in && wf != 0.f;
-      wd = wf;
-    }
-    float* dp = dpred + ((size_t)n * O * H + yy) * W + x;
-    const float* yp = y + (head_image<SEQ>(n, Bs, N / (SEQ ? Bs : 1)) * O * Hc + cy) * Wc + cx;
-    float acc[CQ];
-#pragma unroll
-    for (int c = 0; c < CQ; ++c) acc[c] = 0.f;
-    const int c0 = q * CQ;
-    // the outputs in chunks of HEAD_OCH (d loss / d pred of one chunk in LDS at a time: 200 outputs would otherwise pin the
-    // workgroup count per CU at one); phase 2 keeps accumulating in output order across the chunks
-    for (int oc = 0; oc < O; oc += HEAD_OCH) {
-      const int on = min(HEAD_OCH, O - oc);
-      const int OG = (on + 3) / 4, ob = oc + q * OG, oe = min(oc + on, ob + OG);
-      if (oc > 0) __syncthreads();               // the previous chunk is consumed
-      constexpr int OU = 5;                      // targets fetched ahead of their use: one HBM round trip per OU outputs
-      for (int o0 = ob; o0 < oe; o0 += OU) {
-        float tq[OU];
-#pragma unroll
-        for (int u = 0; u < OU; ++u) tq[u] = (in && o0 + u < oe) ? yp[(size_t)(o0 + u) * Hc * Wc] : 0.f;
-#pragma unroll
-        for (int u = 0; u < OU; ++u) {
-          const int o = o0 + u;
-          if (o >= oe) break;
-          float p = b ? b[o] : 0.f;
-          const f32x4_t* wr = (const f32x4_t*)(w_s + o * CHV);
-#pragma unroll
-          for (int c = 0; c < CHV; c += 4) {
-            const f32x4_t wv = wr[c / 4];
-            p += wv[0] * hv[c]; p += wv[1] * hv[c + 1]; p += wv[2] * hv[c + 2]; p += wv[3] * hv[c + 3];
-          }
-          float gq = 0.f;
-          if (in) {
-            const float t = tq[u];
-            const float d = p - t;
-            if constexpr (WGT) {
-              s2 += wd * ((double)d * d);
-              s1 += wd * fabs((double)d);
-              sy += wd * t;
-              syy += wd * ((double)t * t);
-              gq = (float)(((2.0 * d + (d > 0.f ? 1.0 : (d < 0.f ? -1.0 : 0.0))) * inv_n) * wd);
-            } else {
-              s2 += (double)d * d;
-              s1 += fabs((double)d);
-              sy += t;
-              syy += (double)t * t;
-              gq = (float)((2.0 * d + (d > 0.f ? 1.0 : (d < 0.f ? -1.0 : 0.0))) * inv_n);
-            }
-          }
-          if (live) dp[(size_t)o * H * W] = gq;
-          gq_s[(o - oc) * 64 + lane] = gq;
-        }
-      }
-      __syncthreads();
-      // phase 2: dL/dh[c] = sum_o w[o][c] * gq[o], in output order (the order of head_bwd_dh_kernel)
-      for (int o = oc; o < oc + on; ++o) {
-        const float gq = gq_s[(o - oc) * 64 + lane];
-        const f32x4_t* wr = (const f32x4_t*)(w_s + o * CHV + c0);
-#pragma unroll
-        for (int c = 0; c < CQ; c += 4) {
-          const f32x4_t wv = wr[c / 4];
-          acc[c] += wv[0] * gq; acc[c + 1] += wv[1] * gq; acc[c + 2] += wv[2] * gq; acc[c + 3] += wv[3] * gq;
-        }
-      }
-    }
-    if (live) {
-#pragma unroll
-      for (int c = 0; c < CQ; c += 4)
-        if (c0 + c < Chp) store_vec4<DT>(dh, pix * Chp + c0 + c, (f32x4_t){acc[c], acc[c + 1], acc[c + 2], acc[c + 3]});
-    }
-    __syncthreads();                             // gq_s is rewritten by the next pass
-  }
-  __shared__ double red[4][256];
-  red[0][threadIdx.x] = s2; red[1][threadIdx.x] = s1; red[2][threadIdx.x] = sy; red[3][threadIdx.x] = syy;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s)
-      for (int q2 = 0; q2 < 4; ++q2) red[q2][threadIdx.x] += red[q2][threadIdx.x + s];
-    __syncthreads();
-  }
-  if (threadIdx.x < 4) partial[blockIdx.x * 4 + threadIdx.x] = red[threadIdx.x][0];
-}
-
-template <int DT, int CHV, bool SEQ, bool WGT>
-__global__ __launch_bounds__(256) void head_loss_fused_kernel(const void* __restrict__ h, int n0, int N, int Ch, int Chp, int O,
-                                                              const float* __restrict__ w, const float* __restrict__ b,
-                                                              const float* __restrict__ y, float* __restrict__ dpred,
-                                                              void* __restrict__ dh, double* __restrict__ partial, int H, int W,
-                                                              int P, int Hh, int Wh, int oy, int ox, int Hc, int Wc, int Bs,
-                                                              const float* __restrict__ wgt, double cnt) {
-  extern __shared__ __attribute__((aligned(16))) char smem_hl[];
-  head_loss_fused_body<DT, CHV, SEQ, WGT>(smem_hl, h, n0, N, Ch, Chp, O, w, b, y, dpred, dh, partial, H, W, P, Hh, Wh, oy, ox, Hc, Wc, Bs, wgt, cnt);
-}
-
-// SEQ: the sequence entry (n0 = Bs = B, N = T*B).  WGT: the weighted entries, cnt = N * O * wsum
-template <bool SEQ, bool WGT>
-static int head_loss_fused_impl(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w, const float* b,
-                                const float* y, const float* wgt, double cnt, float* dpred, void* dh, float* loss_out,
-                                double* stats, const nint_geom* g, int oy, int ox, int Hc, int Wc, int dtype, int Bs, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  double* partial = (double*)(loss_out + 2);   // loss_out: [0]=loss, [1]=pad, [2..] = up to LOSS_BLOCKS_MAX*4 doubles
-  // 64 pixels per workgroup and pass: up to LOSS_BLOCKS_MAX workgroups
-  const size_t npix = (size_t)N * g->H * g->W;
-  const int nblk = (int)((npix + 63) / 64 < LOSS_BLOCKS_MAX ? (npix + 63) / 64 : LOSS_BLOCKS_MAX);
-  const size_t lds = ((size_t)O * head_chv(Chp) + (size_t)(O < HEAD_OCH ? O : HEAD_OCH) * 64) * sizeof(float);   // weights [O][CHV] + d loss / d pred of 64 pixels, one output chunk
-  if (lds + 8192 > 160 * 1024) return NINT_E_SHAPE;
-  const int rc = nint_by_dtype(dtype, [&](auto dt) { return head_by_chv(Chp, [&](auto chv) -> int {
-    auto kern = head_loss_fused_kernel<decltype(dt)::value, decltype(chv)::value, SEQ, WGT>;
-    if (lds + 8192 > 64 * 1024) NINT_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3(nblk), dim3(256), lds, st, h_slab, n0, N, Ch, Chp, O, w, b, y, dpred, dh, partial, g->H, g->W, g->P, g->Hh, g->Wh, oy, ox, Hc, Wc, Bs, wgt, cnt);
-    return NINT_OK; }); });
-  if (rc != NINT_OK) return rc;
-  NINT_LAUNCH_CHECK();
-  hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(256), 0, st, partial, nblk, loss_out, stats, WGT ? cnt : (double)N * O * Hc * Wc);
-  NINT_LAUNCH_CHECK();
-  return NINT_OK;
-}
-
-extern "C" int nint_head_loss_fused(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w, const float* b,
-                                    const float* y, float* dpred, void* dh, float* loss_out, double* stats, const nint_geom* g,
-                                    int oy, int ox, int Hc, int Wc, int dtype, void* stream) {
-  if (!h_slab || !w || !y || !dpred || !dh || !loss_out || !g || N <= 0 || O <= 0 || Ch <= 0) return NINT_E_ARG;
-  if (oy < 0 || ox < 0 || oy + Hc > g->H || ox + Wc > g->W) return NINT_E_ARG;
-  if (dtype != NINT_BF16 && dtype != NINT_F32) return NINT_E_ARG;
-  if (Chp > 128 || Chp % 4) return NINT_E_SHAPE;   // wider heads: nint_head_fwd + nint_loss_mse_l1_crop + nint_head_bwd
-  if ((((uintptr_t)loss_out) & 7) != 0) return NINT_E_ALIGN;
-  return head_loss_fused_impl<false, false>(h_slab, n0, N, Ch, Chp, O, w, b, y, nullptr, 0.0, dpred, dh, loss_out, stats, g, oy, ox, Hc, Wc, dtype, 0, stream);
-}
-
-extern "C" int nint_head_loss_fused_weighted(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w, const float* b,
-                                             const float* y, const float* wgt, double wsum, float* dpred, void* dh, float* loss_out,
-                                             double* stats, const nint_geom* g, int oy, int ox, int Hc, int Wc, int dtype, void* stream) {
-  if (!h_slab || !w || !y || !dpred || !dh || !loss_out || !g || N <= 0 || O <= 0 || Ch <= 0) return NINT_E_ARG;
-  if (oy < 0 || ox < 0 || Hc <= 0 || Wc <= 0 || oy + Hc > g->H || ox + Wc > g->W) return NINT_E_ARG;
-  if (dtype != NINT_BF16 && dtype != NINT_F32) return NINT_E_ARG;
-  if (!loss_weights_ok(wgt, wsum)) return NINT_E_ARG;
-  if (Chp > 128 || Chp % 4) return NINT_E_SHAPE;   // wider heads: nint_head_fwd + nint_loss_mse_l1_crop_weighted + nint_head_bwd
-  if ((((uintptr_t)loss_out) & 7) != 0 || (((uintptr_t)wgt) & 3) != 0) return NINT_E_ALIGN;
-  return head_loss_fused_impl<false, true>(h_slab, n0, N, Ch, Chp, O, w, b, y, wgt, (double)N * O * wsum, dpred, dh, loss_out, stats, g, oy, ox, Hc, Wc, dtype, 0, stream);
-}
-
-extern "C" int nint_head_loss_seq_fused(const void* h_slab, int B, int T, int Ch, int Chp, int O, const float* w, const float* b,
-                                        const float* y, float* dpred, void* dh_seq, float* loss_out, double* stats,
-                                        const nint_geom* g, int oy, int ox, int Hc, int Wc, int dtype, void* stream) {
-  if (!y || !dpred || !dh_seq || !loss_out || !head_seq_args_ok(h_slab, B, T, Ch, Chp, O, w, g, dtype)) return NINT_E_ARG;
-  if (oy < 0 || ox < 0 || Hc <= 0 || Wc <= 0 || oy + Hc > g->H || ox + Wc > g->W) return NINT_E_ARG;
-  if (Chp > 128) return NINT_E_SHAPE;              // wider heads: nint_head_fwd_seq + nint_loss_mse_l1_crop + nint_head_bwd_seq
-  if ((((uintptr_t)loss_out) & 7) != 0 || ((((uintptr_t)h_slab) | ((uintptr_t)dh_seq)) & 15) != 0) return NINT_E_ALIGN;
-  return head_loss_fused_impl<true, false>(h_slab, B, T * B, Ch, Chp, O, w, b, y, nullptr, 0.0, dpred, dh_seq, loss_out, stats, g, oy, ox, Hc, Wc, dtype, B, stream);
-}
-
-extern "C" int nint_head_loss_seq_fused_weighted(const void* h_slab, int B, int T, int Ch, int Chp, int O, const float* w, const float* b,
-                                                 const float* y, const float* wgt, double wsum, float* dpred, void* dh_seq,
-                                                 float* loss_out, double* stats, const nint_geom* g, int oy, int ox, int Hc,
-                                                 int Wc, int dtype, void* stream) {
-  if (!y || !dpred || !dh_seq || !loss_out || !head_seq_args_ok(h_slab, B, T, Ch, Chp, O, w, g, dtype)) return NINT_E_ARG;
-  if (oy < 0 || ox < 0 || Hc <= 0 || Wc <= 0 || oy + Hc > g->H || ox + Wc > g->W) return NINT_E_ARG;
-  if (!loss_weights_ok(wgt, wsum)) return NINT_E_ARG;
-  if (Chp > 128) return NINT_E_SHAPE;              // wider heads: nint_head_fwd_seq + nint_loss_mse_l1_crop_weighted + nint_head_bwd_seq
-  if ((((uintptr_t)loss_out) & 7) != 0 || ((((uintptr_t)h_slab) | ((uintptr_t)dh_seq)) & 15) != 0 || (((uintptr_t)wgt) & 3) != 0) return NINT_E_ALIGN;
-  return head_loss_fused_impl<true, true>(h_slab, B, T * B, Ch, Chp, O, w, b, y, wgt, (double)(T * B) * O * wsum, dpred, dh_seq, loss_out, stats, g, oy, ox, Hc, Wc, dtype, B, stream);
-}
-
-// ------------------------------------------------------------------------------ the configurable loss (nint_loss_spec)
-// The general per-element body of the three passes above (nint.h has the arithmetic): the term is a * d^2 + b * |d| + c * H(d)
-// with coefficients known at run time, the weight the product of the cell's (optional map) and the output's (optional ow;
-// per (step, output) in the sequence entry).  New kernels beside the old ones: the instances above are what the default step
-// runs and stay as they are.  A zero coefficient takes its term out (flags, not products: 0 * inf is NaN).
+// The spec's coefficients as the kernels receive them, and the closing mix (a zero coefficient's term is not formed).
 struct LossSpecK {
   double a, b, c, delta;       // coefficients and the Huber threshold
   const float* ow;             // weight per output (plain, fused) or per (step, output) (sequence); nullptr: 1
+  static constexpr int NS = 5;
+  __device__ __forceinline__ double mix(double s0, double s1, double sh, double count) const {
+#pragma clang fp contract(off)
+    double loss = 0.0;
+    bool any = false;
+    if (a != 0.0) { loss = a * (s0 / count); any = true; }
+    if (b != 0.0) { const double t = b * (s1 / count); loss = any ? loss + t : t; any = true; }
+    if (c != 0.0) { const double t = c * (sh / count); loss = any ? loss + t : t; }
+    return loss;
+  }
 };
 
-// The running sums join their terms with ONE fused multiply-add each -- what the compiler makes of the loops above
+// The running sums join their terms with ONE fused multiply-add each -- what the compiler makes of LossMap::add
 // (s2 += wd * ((double)d * d) is v_fmac_f64 there), spelled out here so that spec (1, 1, 0) keeps those bits whatever the
 // optimiser does with this body.
 struct LossSpecSums {
@@ -980,13 +748,41 @@ __device__ __forceinline__ float loss_spec_grad(const LossSpecK& sp, float df, d
   return (float)((g * inv_n) * Wd);
 }
 
-__global__ __launch_bounds__(1024) void loss_spec_partial_kernel(const float* __restrict__ pred, const float* __restrict__ y,
-                                                                float* __restrict__ dpred, double* __restrict__ partial,
-                                                                int N, int O, int H, int W, int oy, int ox, int Hc, int Wc,
-                                                                const float* __restrict__ wgt, double cnt, const LossSpecK sp) {
+struct LossSpec {
+  static constexpr int NS = 5;
+  static constexpr bool CELL = true, OW = true, HEAD_DOT = true;
+  using Mix = LossSpecK;
+  using Sums = LossSpecSums;
+  const float* wgt; double cnt; LossSpecK k;     // wgt may be nullptr; cnt = images * (osum or O) * (wsum or Hc * Wc)
+  __device__ __forceinline__ LossSpec(const float* wgt_, double cnt_, const LossSpecK& k_) : wgt(wgt_), cnt(cnt_), k(k_) {}
+  __device__ __forceinline__ double inv_n(int, int, int, int) const { return 1.0 / cnt; }
+  __device__ __forceinline__ float cell(size_t cyx) const { return wgt ? wgt[cyx] : 1.f; }
+  __device__ __forceinline__ float out(size_t step, int O, int o) const { return k.ow ? k.ow[step * O + o] : 1.f; }
+  __device__ __forceinline__ double weight(double wd, float q) const { return (double)q * wd; }
+  __device__ __forceinline__ Sums add(Sums s, double Wd, float d, float t) const { s.add(Wd, d, t, loss_spec_huber(k, d)); return s; }
+  __device__ __forceinline__ float grad(float d, double inv_n, double Wd) const { return loss_spec_grad(k, d, inv_n, Wd); }
+};
+
+// The fold of a workgroup's NQ running sums, red[q][thread] -> red[q][0]: a fixed-order tree from `half` threads down.
+// (Text, not a function: behind a call the early passes lose the loop, and loss_final_kernel compiles differently.)
+#define LOSS_WG_FOLD(red, NQ, half) \
+  __syncthreads(); \
+  for (int st_ = (half); st_ > 0; st_ >>= 1) { \
+    if ((int)threadIdx.x < st_) \
+      for (int q_ = 0; q_ < (NQ); ++q_) red[q_][threadIdx.x] += red[q_][threadIdx.x + st_]; \
+    __syncthreads(); \
+  }
+
+// Coef: nothing, or the LossSpecK of LossSpec -- the other instances keep the argument list they had
+template <class Elem, class... Coef>
+__global__ __launch_bounds__(1024) void loss_partial_kernel(const float* __restrict__ pred, const float* __restrict__ y,
+                                                           float* __restrict__ dpred, double* __restrict__ partial,
+                                                           int N, int O, int H, int W, int oy, int ox, int Hc, int Wc,
+                                                           const float* __restrict__ wgt, double cnt, const Coef... sp) {
+  const Elem e(wgt, cnt, sp...);
   const size_t total = (size_t)N * O * H * W;
-  const double inv_n = 1.0 / cnt;
-  LossSpecSums s;
+  const double inv_n = e.inv_n(N, O, Hc, Wc);
+  typename Elem::Sums s = {};
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
     const int x = i % W;
     size_t r = i / W;
@@ -995,66 +791,83 @@ __global__ __launch_bounds__(1024) void loss_spec_partial_kernel(const float* __
     const int cy = yy - oy, cx = x - ox;
     float g = 0.f;
     if (cy >= 0 && cy < Hc && cx >= 0 && cx < Wc) {
-      const float wf = wgt ? wgt[(size_t)cy * Wc + cx] : 1.f;
-      const float qf = sp.ow ? sp.ow[no % (size_t)O] : 1.f;
-      const double Wd = (double)qf * (double)wf;
-      if (Wd != 0.0) {
+      const float cw = e.cell((size_t)cy * Wc + cx), q = e.out(0, O, (int)(no % (size_t)O));
+      if (cw != 0.f && q != 0.f) {
+        const double Wd = e.weight(cw, q);
         const float t = y[(no * Hc + cy) * Wc + cx];
         const float d = pred[i] - t;
-        s.add(Wd, d, t, loss_spec_huber(sp, d));
-        g = loss_spec_grad(sp, d, inv_n, Wd);
+        s = e.add(s, Wd, d, t);
+        g = e.grad(d, inv_n, Wd);
       }
     }
     if (dpred) dpred[i] = g;
   }
-  __shared__ double red[5][1024];
+  constexpr int NS = Elem::NS;
+  __shared__ double red[NS][1024];
   red[0][threadIdx.x] = s.s2; red[1][threadIdx.x] = s.s1; red[2][threadIdx.x] = s.sy; red[3][threadIdx.x] = s.syy;
-  red[4][threadIdx.x] = s.sh;
-  __syncthreads();
-  for (int st = blockDim.x >> 1; st > 0; st >>= 1) {
-    if ((int)threadIdx.x < st)
-      for (int q = 0; q < 5; ++q) red[q][threadIdx.x] += red[q][threadIdx.x + st];
-    __syncthreads();
-  }
-  if (threadIdx.x < 5) partial[blockIdx.x * 5 + threadIdx.x] = red[threadIdx.x][0];
+  if constexpr (NS == 5) red[4][threadIdx.x] = s.sh;
+  LOSS_WG_FOLD(red, NS, blockDim.x >> 1)
+  if (threadIdx.x < NS) partial[blockIdx.x * NS + threadIdx.x] = red[threadIdx.x][0];
 }
 
-// loss_final_kernel over five partials per workgroup (the same fold order per sum), and the loss as the configured mix
-__global__ __launch_bounds__(256) void loss_spec_final_kernel(const double* __restrict__ partial, int nblocks, float* __restrict__ loss_out,
-                                                              double* __restrict__ stats, double count, const LossSpecK sp) {
-#pragma clang fp contract(off)
-  __shared__ double red[5][256];
-  for (int q = 0; q < 5; ++q) {
+template <class Mix, class... Coef>
+__global__ __launch_bounds__(256) void loss_final_kernel(const double* __restrict__ partial, int nblocks, float* __restrict__ loss_out,
+                                                         double* __restrict__ stats, double count, const Coef... sp) {
+  // thread (b, q) = one partial; fixed-order tree over the blocks
+  constexpr int NS = Mix::NS;
+  __shared__ double red[NS][256];
+  for (int q = 0; q < NS; ++q) {
     double s = 0;
-    for (int b = threadIdx.x; b < nblocks; b += blockDim.x) s += partial[b * 5 + q];
+    for (int b = threadIdx.x; b < nblocks; b += blockDim.x) s += partial[b * NS + q];
     red[q][threadIdx.x] = s;
   }
-  __syncthreads();
-  for (int st = 128; st > 0; st >>= 1) {
-    if ((int)threadIdx.x < st)
-      for (int q = 0; q < 5; ++q) red[q][threadIdx.x] += red[q][threadIdx.x + st];
-    __syncthreads();
-  }
+  LOSS_WG_FOLD(red, NS, 128)
   if (threadIdx.x == 0) {
-    const double s0 = red[0][0], s1 = red[1][0], s2 = red[2][0], s3 = red[3][0], sh = red[4][0];
-    double loss = 0.0;
-    bool any = false;
-    if (sp.a != 0.0) { loss = sp.a * (s0 / count); any = true; }
-    if (sp.b != 0.0) { const double t = sp.b * (s1 / count); loss = any ? loss + t : t; any = true; }
-    if (sp.c != 0.0) { const double t = sp.c * (sh / count); loss = any ? loss + t : t; }
+    const double s0 = red[0][0], s1 = red[1][0], s2 = red[2][0], s3 = red[3][0];
+    const double loss = Mix{sp...}.mix(s0, s1, NS == 5 ? red[NS - 1][0] : 0.0, count);
     if (loss_out) loss_out[0] = (float)loss;
     if (stats) {
       stats[0] += s0; stats[1] += s1; stats[2] += s2; stats[3] += s3; stats[4] += count;
+      // the reference's per-batch statistics (train.py:113-117, utils.py:73-75): it sums loss.item() and
+      // sklearn r2_score(y, pred) of every batch and divides by the number of batches
       const double ss_tot = s3 - s2 * s2 / count;
-      const double r2 = ss_tot > 0.0 ? 1.0 - s0 / ss_tot : (s0 == 0.0 ? 1.0 : 0.0);   // (loss_final_kernel's convention)
+      const double r2 = ss_tot > 0.0 ? 1.0 - s0 / ss_tot : (s0 == 0.0 ? 1.0 : 0.0);   // sklearn's constant-target convention
       stats[5] += loss; stats[6] += r2; stats[7] += 1.0;
     }
   }
 }
 
-#define LOSS_SPEC_BLOCKS_MAX ((NINT_LOSS_SPEC_SCRATCH_FLOATS - 2) / 10)   // what the caller's scratch holds: 5 doubles per workgroup
-static_assert(LOSS_SPEC_BLOCKS_MAX == LOSS_BLOCKS_MAX, "the spec passes take the grids of their twins: the same partials per sum");
+// The caller's scratch, loss_out: [0] = the loss, [1] = padding, then from [2] (8-byte aligned) NS doubles per workgroup of
+// the partial-sum launch.  The plain pass runs LOSS_BLOCKS workgroups, the fused pass up to LOSS_BLOCKS_MAX -- what both
+// NINT_LOSS_SCRATCH_FLOATS (4 sums) and NINT_LOSS_SPEC_SCRATCH_FLOATS (5 sums) hold.
+#define LOSS_BLOCKS 256
+#define LOSS_BLOCKS_MAX ((NINT_LOSS_SCRATCH_FLOATS - 2) / 8)
+static_assert((NINT_LOSS_SPEC_SCRATCH_FLOATS - 2) / 10 == LOSS_BLOCKS_MAX, "the spec passes take the grids of their twins: the same partials per sum");
+static_assert(LOSS_BLOCKS <= LOSS_BLOCKS_MAX, "the plain pass fits the same scratch");
 
+// the plain pass: cnt is the n of the loss (the final kernel's count); k: the LossSpecK of LossSpec
+template <class Elem, class... Coef>
+static int loss_launch(const float* pred, const float* y, const float* wgt, double cnt, float* dpred, float* loss_out, double* stats,
+                       int N, int O, int H, int W, int oy, int ox, int Hc, int Wc, void* stream, const Coef... k) {
+  hipStream_t st = (hipStream_t)stream;
+  double* partial = (double*)(loss_out + 2);
+  hipLaunchKernelGGL((loss_partial_kernel<Elem, Coef...>), dim3(LOSS_BLOCKS), dim3(1024), 0, st, pred, y, dpred, partial, N, O, H, W, oy, ox, Hc, Wc, wgt, cnt, k...);
+  NINT_LAUNCH_CHECK();
+  hipLaunchKernelGGL((loss_final_kernel<typename Elem::Mix, Coef...>), dim3(1), dim3(256), 0, st, partial, LOSS_BLOCKS, loss_out, stats, cnt, k...);
+  NINT_LAUNCH_CHECK();
+  return NINT_OK;
+}
+
+// The checks the loss entries share.  Crop window inside H x W; `area`: the entries that take weights also refuse an empty one.
+static inline bool loss_crop_ok(int H, int W, int oy, int ox, int Hc, int Wc, bool area) {
+  return oy >= 0 && ox >= 0 && oy + Hc <= H && ox + Wc <= W && (!area || (Hc > 0 && Wc > 0));
+}
+// the weight map of the _weighted entries: present, and a total that is positive and finite (!(wsum > 0) also catches NaN)
+static inline bool loss_weights_ok(const float* wgt, double wsum) { return wgt && wsum > 0.0 && wsum <= DBL_MAX; }
+// loss_out holds doubles from [2]; the map and ow (either may be nullptr) are float arrays
+static inline bool loss_aligned(const float* loss_out, const float* wgt, const float* ow) {
+  return (((uintptr_t)loss_out) & 7) == 0 && ((((uintptr_t)wgt) | ((uintptr_t)ow)) & 3) == 0;
+}
 // The spec's own checks (nint.h).  nout: O of the plain and fused entries, T*O of the sequence entry.
 static int loss_spec_check(const nint_loss_spec* sp, int nout, const float* wgt, double wsum) {
   if (!sp) return NINT_E_ARG;
@@ -1080,72 +893,64 @@ static inline double loss_spec_cnt(const nint_loss_spec* sp, int images, int O, 
   return (double)images * (sp->ow ? sp->osum : (double)O) * (wgt ? wsum : (double)Hc * Wc);
 }
 
+extern "C" int nint_loss_mse_l1_crop(const float* pred, const float* y, float* dpred, float* loss_out, double* stats,
+                                     int N, int O, int H, int W, int oy, int ox, int Hc, int Wc, void* stream) {
+  if (!pred || !y || !loss_out || N <= 0 || O <= 0 || !loss_crop_ok(H, W, oy, ox, Hc, Wc, false)) return NINT_E_ARG;
+  if (!loss_aligned(loss_out, nullptr, nullptr)) return NINT_E_ALIGN;
+  return loss_launch<LossPlain>(pred, y, nullptr, (double)N * O * Hc * Wc, dpred, loss_out, stats, N, O, H, W, oy, ox, Hc, Wc, stream);
+}
+
+extern "C" int nint_loss_mse_l1_crop_weighted(const float* pred, const float* y, const float* wgt, double wsum, float* dpred,
+                                              float* loss_out, double* stats, int N, int O, int H, int W, int oy, int ox,
+                                              int Hc, int Wc, void* stream) {
+  if (!pred || !y || !loss_out || N <= 0 || O <= 0 || !loss_crop_ok(H, W, oy, ox, Hc, Wc, true)) return NINT_E_ARG;
+  if (!loss_weights_ok(wgt, wsum)) return NINT_E_ARG;
+  if (!loss_aligned(loss_out, wgt, nullptr)) return NINT_E_ALIGN;
+  return loss_launch<LossMap>(pred, y, wgt, (double)N * O * wsum, dpred, loss_out, stats, N, O, H, W, oy, ox, Hc, Wc, stream);
+}
+
 extern "C" int nint_loss_crop_spec(const float* pred, const float* y, const float* wgt, double wsum, const nint_loss_spec* spec,
                                    float* dpred, float* loss_out, double* stats, int N, int O, int H, int W, int oy, int ox,
                                    int Hc, int Wc, void* stream) {
-  if (!pred || !y || !loss_out || N <= 0 || O <= 0 || oy < 0 || ox < 0 || oy + Hc > H || ox + Wc > W) return NINT_E_ARG;
-  if (Hc <= 0 || Wc <= 0) return NINT_E_ARG;
+  if (!pred || !y || !loss_out || N <= 0 || O <= 0 || !loss_crop_ok(H, W, oy, ox, Hc, Wc, true)) return NINT_E_ARG;
   const int rc = loss_spec_check(spec, O, wgt, wsum);
   if (rc != NINT_OK) return rc;
-  if ((((uintptr_t)loss_out) & 7) != 0 || (((uintptr_t)wgt) & 3) != 0 || (((uintptr_t)spec->ow) & 3) != 0) return NINT_E_ALIGN;
-  hipStream_t st = (hipStream_t)stream;
-  const double cnt = loss_spec_cnt(spec, N, O, wgt, wsum, Hc, Wc);
-  const LossSpecK k = loss_spec_k(spec);
-  double* partial = (double*)(loss_out + 2);   // loss_out: [0]=loss, [1]=pad, [2..] = 256*5 doubles
-  hipLaunchKernelGGL(loss_spec_partial_kernel, dim3(LOSS_BLOCKS), dim3(1024), 0, st, pred, y, dpred, partial, N, O, H, W, oy, ox, Hc, Wc, wgt, cnt, k);
-  NINT_LAUNCH_CHECK();
-  hipLaunchKernelGGL(loss_spec_final_kernel, dim3(1), dim3(256), 0, st, partial, LOSS_BLOCKS, loss_out, stats, cnt, k);
-  NINT_LAUNCH_CHECK();
-  return NINT_OK;
+  if (!loss_aligned(loss_out, wgt, spec->ow)) return NINT_E_ALIGN;
+  return loss_launch<LossSpec>(pred, y, wgt, loss_spec_cnt(spec, N, O, wgt, wsum, Hc, Wc), dpred, loss_out, stats, N, O, H, W, oy, ox, Hc, Wc,
+                               stream, loss_spec_k(spec));
 }
 
-// The prediction of the fused spec pass has to carry head_fwd_kernel's bits (fused = the three launches).  As compiled, that
-// kernel -- and head_loss_fused_body with it -- joins the products of all but the LAST 12 staged channels to the accumulator by
-// fused multiply-add, and rounds those last 12 products on their own before adding them in channel order (the vectoriser packs
-// them: v_pk_mul_f32 + v_add_f32).  Around the run-time branches of the body below the optimiser does not repeat that choice
-// (it fuses the whole chain), so the chain is spelled out; test_fused_spec_equals_the_three_launches_bit_for_bit holds the two
-// together at every CHV, with real data in the last channels.
-#define HEAD_FWD_UNFUSED_TAIL 12
-template <int CHV>
-__device__ __forceinline__ float head_dot_as_fwd(float p, const float* w_row, const float (&hv)[CHV]) {
-#pragma clang fp contract(off)
-  const f32x4_t* wr = (const f32x4_t*)w_row;
-#pragma unroll
-  for (int c = 0; c < CHV; c += 4) {
-    const f32x4_t wv = wr[c / 4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      if (c + e < CHV - HEAD_FWD_UNFUSED_TAIL) {
-        p = __builtin_fmaf(wv[e], hv[c + e], p);
-      } else {
-        const float m = wv[e] * hv[c + e];
-        p = m + p;
-      }
-    }
-  }
-  return p;
-}
-
-// head_loss_fused_body with the general element: the same passes, phases and order (so the prediction and dL/dh keep the
-// bits of head_fwd_kernel and head_bwd_dh_kernel); the output's weight is read with its target, and an element of weight 0
-// reads no target.  The fifth sum folds through red[0] after the other four: the static LDS stays the twins' 8 KiB, and
-// with it the limit (head_staged_holds).
-template <int DT, int CHV, bool SEQ>
-__device__ __forceinline__ void head_loss_spec_body(char* smem_hl, const void* __restrict__ h, int n0, int N, int Ch, int Chp, int O,
-                                                    const float* __restrict__ w, const float* __restrict__ b,
-                                                    const float* __restrict__ y, float* __restrict__ dpred,
-                                                    void* __restrict__ dh, double* __restrict__ partial, int H, int W,
-                                                    int P, int Hh, int Wh, int oy, int ox, int Hc, int Wc, int Bs,
-                                                    const float* __restrict__ wgt, double cnt, const LossSpecK sp) {
+// ------------------------------------------------------------------------------ head + loss, fused (training)
+// train.py:96-109 around the 1x1 head in ONE pass over the pixels: pred = w . h + b (model.py:274), crop, the loss element's
+// partial sums (train.py:102,105), d loss / d pred, and dL/dh = w^T . dpred.  One thread per pixel (grid-stride):
+// the channel vector is read once, pred never goes to memory, dpred is written for the head's weight gradient.
+// Same arithmetic, in the same order, as head_fwd_kernel -> loss_partial_kernel<Elem> -> head_bwd_dh_kernel.
+// (HEAD_OCH outputs per chunk: head_staged_holds)
+// SEQ (the _seq_ entries): the images are all T*B steps of the slab, image n = t*B + b; the targets are (B, T, O, Hc, Wc),
+// plane block b*T + t (head_image); dpred and dh stay in image order, which is what the weight-gradient stage and BPTT read.
+// Elem: the pixel's weight is read once per pass, next to the crop test, and a cell of weight 0 leaves the crop: neither its
+// targets nor its prediction enter anything.  LossSpec reads the output's weight with its target.  The static LDS is the 8 KiB
+// of four sums for every policy -- a fifth sum folds through red[0] after the other four -- and with it the limit
+// (head_staged_holds).
+template <int DT, int CHV, bool SEQ, class Elem>
+__device__ __forceinline__ void head_loss_body(char* smem_hl, const void* __restrict__ h, int n0, int N, int Ch, int Chp, int O,
+                                               const float* __restrict__ w, const float* __restrict__ b,
+                                               const float* __restrict__ y, float* __restrict__ dpred,
+                                               void* __restrict__ dh, double* __restrict__ partial, int H, int W,
+                                               int P, int Hh, int Wh, int oy, int ox, int Hc, int Wc, int Bs, const Elem e) {
+  // A workgroup takes 64 pixels per pass (grid-stride).  Phase 1: wave q runs the outputs [q*OG, (q+1)*OG) of every pixel
+  // (lane = pixel): pred, loss terms, d loss / d pred -> dpred and, through LDS, to phase 2: wave q accumulates the
+  // channels [q*CHV/4, (q+1)*CHV/4) of dL/dh over ALL outputs in output order.  (One thread per pixel for all outputs --
+  // the first version -- is a chain of O dependent round trips on 1/4 of the threads: 50 us at B = 8, 44 us at B = 1.)
   float* w_s = (float*)smem_hl;                  // [O][CHV], zero padded (head_stage_weights)
   float* gq_s = w_s + O * CHV;                   // [min(O, HEAD_OCH)][64]
   head_stage_weights<CHV>(w_s, w, O, Ch);
   const int lane = threadIdx.x & 63;
   const int q = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // (scalar: the weight reads below stay scalar loads)
   const size_t npix = (size_t)N * H * W;
-  const double inv_n = 1.0 / cnt;
+  const double inv_n = e.inv_n(N, O, Hc, Wc);
   constexpr int CQ = CHV / 4;                    // channels per wave in phase 2
-  LossSpecSums s;
+  typename Elem::Sums s = {};
   for (size_t p0 = (size_t)blockIdx.x * 64; p0 < npix; p0 += (size_t)gridDim.x * 64) {
     const size_t pix = p0 + lane;
     const bool live = pix < npix;
@@ -1163,42 +968,54 @@ __device__ __forceinline__ void head_loss_spec_body(char* smem_hl, const void* _
     }
     const int cy = yy - oy, cx = x - ox;
     bool in = live && cy >= 0 && cy < Hc && cx >= 0 && cx < Wc;
-    float wf = 1.f;
-    if (wgt) {
-      wf = in ? wgt[(size_t)cy * Wc + cx] : 0.f;
+    double wd = 1.0;
+    if constexpr (Elem::CELL) {
+      const float wf = in ? e.cell((size_t)cy * Wc + cx) : 0.f;
       in = in && wf != 0.f;
+      wd = wf;
     }
-    const float* owp = sp.ow;                    // the O weights of the pixel's step (image n = t*B + b)
-    if constexpr (SEQ) owp = owp ? owp + (size_t)(n / Bs) * O : owp;
+    const size_t step = SEQ ? n / Bs : 0;        // of the pixel's image n = t*B + b: the row of the (step, output) weights
     float* dp = dpred + ((size_t)n * O * H + yy) * W + x;
     const float* yp = y + (head_image<SEQ>(n, Bs, N / (SEQ ? Bs : 1)) * O * Hc + cy) * Wc + cx;
     float acc[CQ];
 #pragma unroll
     for (int c = 0; c < CQ; ++c) acc[c] = 0.f;
     const int c0 = q * CQ;
+    // the outputs in chunks of HEAD_OCH (d loss / d pred of one chunk in LDS at a time: 200 outputs would otherwise pin the
+    // workgroup count per CU at one); phase 2 keeps accumulating in output order across the chunks
     for (int oc = 0; oc < O; oc += HEAD_OCH) {
       const int on = min(HEAD_OCH, O - oc);
       const int OG = (on + 3) / 4, ob = oc + q * OG, oe = min(oc + on, ob + OG);
       if (oc > 0) __syncthreads();               // the previous chunk is consumed
       constexpr int OU = 5;                      // targets fetched ahead of their use: one HBM round trip per OU outputs
       for (int o0 = ob; o0 < oe; o0 += OU) {
-        float tq[OU], qq[OU];
+        float tq[OU], qq[OU];                    // targets and output weights (0: outside the crop, or past the wave's outputs)
 #pragma unroll
-        for (int u = 0; u < OU; ++u) qq[u] = (in && o0 + u < oe) ? (owp ? owp[o0 + u] : 1.f) : 0.f;
+        for (int u = 0; u < OU; ++u) qq[u] = (in && o0 + u < oe) ? (Elem::OW ? e.out(step, O, o0 + u) : 1.f) : 0.f;
 #pragma unroll
-        for (int u = 0; u < OU; ++u) tq[u] = qq[u] != 0.f ? yp[(size_t)(o0 + u) * Hc * Wc] : 0.f;
+        for (int u = 0; u < OU; ++u) tq[u] = (Elem::OW ? qq[u] != 0.f : in && o0 + u < oe) ? yp[(size_t)(o0 + u) * Hc * Wc] : 0.f;
 #pragma unroll
         for (int u = 0; u < OU; ++u) {
           const int o = o0 + u;
           if (o >= oe) break;
-          const float p = head_dot_as_fwd<CHV>(b ? b[o] : 0.f, w_s + o * CHV, hv);
+          float p = b ? b[o] : 0.f;
+          if constexpr (Elem::HEAD_DOT) {
+            p = head_dot<CHV>(p, w_s + o * CHV, hv);
+          } else {                               // head_dot's chain as the optimiser forms it from this loop (see head_dot)
+            const f32x4_t* wr = (const f32x4_t*)(w_s + o * CHV);
+#pragma unroll
+            for (int c = 0; c < CHV; c += 4) {
+              const f32x4_t wv = wr[c / 4];
+              p += wv[0] * hv[c]; p += wv[1] * hv[c + 1]; p += wv[2] * hv[c + 2]; p += wv[3] * hv[c + 3];
+            }
+          }
           float gq = 0.f;
-          if (qq[u] != 0.f) {                    // inside the crop, cell and output weights non-zero
+          if (Elem::OW ? qq[u] != 0.f : in) {
             const float t = tq[u];
             const float d = p - t;
-            const double Wd = (double)qq[u] * (double)wf;
-            s.add(Wd, d, t, loss_spec_huber(sp, d));
-            gq = loss_spec_grad(sp, d, inv_n, Wd);
+            const double Wd = e.weight(wd, qq[u]);
+            s = e.add(s, Wd, d, t);
+            gq = e.grad(d, inv_n, Wd);
           }
           if (live) dp[(size_t)o * H * W] = gq;
           gq_s[(o - oc) * 64 + lane] = gq;
@@ -1223,73 +1040,122 @@ __device__ __forceinline__ void head_loss_spec_body(char* smem_hl, const void* _
     }
     __syncthreads();                             // gq_s is rewritten by the next pass
   }
+  constexpr int NS = Elem::NS;
   __shared__ double red[4][256];
   red[0][threadIdx.x] = s.s2; red[1][threadIdx.x] = s.s1; red[2][threadIdx.x] = s.sy; red[3][threadIdx.x] = s.syy;
-  __syncthreads();
-  for (int st = 128; st > 0; st >>= 1) {
-    if ((int)threadIdx.x < st)
-      for (int q2 = 0; q2 < 4; ++q2) red[q2][threadIdx.x] += red[q2][threadIdx.x + st];
+  LOSS_WG_FOLD(red, 4, 128)
+  if (threadIdx.x < 4) partial[blockIdx.x * NS + threadIdx.x] = red[threadIdx.x][0];
+  if constexpr (NS == 5) {                       // the fifth sum, by the same tree
     __syncthreads();
+    red[0][threadIdx.x] = s.sh;
+    LOSS_WG_FOLD(red, 1, 128)
+    if (threadIdx.x == 0) partial[blockIdx.x * NS + 4] = red[0][0];
   }
-  if (threadIdx.x < 4) partial[blockIdx.x * 5 + threadIdx.x] = red[threadIdx.x][0];
-  __syncthreads();
-  red[0][threadIdx.x] = s.sh;                    // the fifth sum, by the same tree
-  __syncthreads();
-  for (int st = 128; st > 0; st >>= 1) {
-    if ((int)threadIdx.x < st) red[0][threadIdx.x] += red[0][threadIdx.x + st];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) partial[blockIdx.x * 5 + 4] = red[0][0];
 }
 
-template <int DT, int CHV, bool SEQ>
-__global__ __launch_bounds__(256) void head_loss_spec_kernel(const void* __restrict__ h, int n0, int N, int Ch, int Chp, int O,
-                                                             const float* __restrict__ w, const float* __restrict__ b,
-                                                             const float* __restrict__ y, float* __restrict__ dpred,
-                                                             void* __restrict__ dh, double* __restrict__ partial, int H, int W,
-                                                             int P, int Hh, int Wh, int oy, int ox, int Hc, int Wc, int Bs,
-                                                             const float* __restrict__ wgt, double cnt, const LossSpecK sp) {
+// Coef: nothing, or the LossSpecK of LossSpec (loss_partial_kernel)
+template <int DT, int CHV, bool SEQ, class Elem, class... Coef>
+__global__ __launch_bounds__(256) void head_loss_kernel(const void* __restrict__ h, int n0, int N, int Ch, int Chp, int O,
+                                                        const float* __restrict__ w, const float* __restrict__ b,
+                                                        const float* __restrict__ y, float* __restrict__ dpred,
+                                                        void* __restrict__ dh, double* __restrict__ partial, int H, int W,
+                                                        int P, int Hh, int Wh, int oy, int ox, int Hc, int Wc, int Bs,
+                                                        const float* __restrict__ wgt, double cnt, const Coef... sp) {
   extern __shared__ __attribute__((aligned(16))) char smem_hl[];
-  head_loss_spec_body<DT, CHV, SEQ>(smem_hl, h, n0, N, Ch, Chp, O, w, b, y, dpred, dh, partial, H, W, P, Hh, Wh, oy, ox, Hc, Wc, Bs, wgt, cnt, sp);
+  head_loss_body<DT, CHV, SEQ>(smem_hl, h, n0, N, Ch, Chp, O, w, b, y, dpred, dh, partial, H, W, P, Hh, Wh, oy, ox, Hc, Wc, Bs, Elem(wgt, cnt, sp...));
 }
 
-// SEQ: the sequence entry (n0 = Bs = B, N = T*B); head_loss_fused_impl's launch shape
-template <bool SEQ>
-static int head_loss_spec_impl(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w, const float* b,
-                               const float* y, const float* wgt, double cnt, const LossSpecK k, float* dpred, void* dh,
-                               float* loss_out, double* stats, const nint_geom* g, int oy, int ox, int Hc, int Wc, int dtype,
-                               int Bs, void* stream) {
+// The fused pass.  SEQ: the sequence entry (n0 = Bs = B, N = T*B).  cnt: the n of the loss; k: the LossSpecK of LossSpec
+template <bool SEQ, class Elem, class... Coef>
+static int head_loss_launch(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w, const float* b,
+                            const float* y, const float* wgt, double cnt, float* dpred, void* dh, float* loss_out,
+                            double* stats, const nint_geom* g, int oy, int ox, int Hc, int Wc, int dtype, int Bs, void* stream,
+                            const Coef... k) {
   hipStream_t st = (hipStream_t)stream;
-  double* partial = (double*)(loss_out + 2);   // loss_out: [0]=loss, [1]=pad, [2..] = up to LOSS_SPEC_BLOCKS_MAX*5 doubles
+  double* partial = (double*)(loss_out + 2);
+  // 64 pixels per workgroup and pass: up to LOSS_BLOCKS_MAX workgroups
   const size_t npix = (size_t)N * g->H * g->W;
-  const int nblk = (int)((npix + 63) / 64 < LOSS_SPEC_BLOCKS_MAX ? (npix + 63) / 64 : LOSS_SPEC_BLOCKS_MAX);
-  const size_t lds = ((size_t)O * head_chv(Chp) + (size_t)(O < HEAD_OCH ? O : HEAD_OCH) * 64) * sizeof(float);
-  if (lds + 8192 > 160 * 1024) return NINT_E_SHAPE;
+  const int nblk = (int)((npix + 63) / 64 < LOSS_BLOCKS_MAX ? (npix + 63) / 64 : LOSS_BLOCKS_MAX);
+  if (!head_staged_holds(Chp, O)) return NINT_E_SHAPE;
+  const size_t lds = head_loss_lds(Chp, O);
   const int rc = nint_by_dtype(dtype, [&](auto dt) { return head_by_chv(Chp, [&](auto chv) -> int {
-    auto kern = head_loss_spec_kernel<decltype(dt)::value, decltype(chv)::value, SEQ>;
+    auto kern = head_loss_kernel<decltype(dt)::value, decltype(chv)::value, SEQ, Elem, Coef...>;
     if (lds + 8192 > 64 * 1024) NINT_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3(nblk), dim3(256), lds, st, h_slab, n0, N, Ch, Chp, O, w, b, y, dpred, dh, partial, g->H, g->W, g->P, g->Hh, g->Wh, oy, ox, Hc, Wc, Bs, wgt, cnt, k);
+    hipLaunchKernelGGL(kern, dim3(nblk), dim3(256), lds, st, h_slab, n0, N, Ch, Chp, O, w, b, y, dpred, dh, partial, g->H, g->W, g->P, g->Hh, g->Wh, oy, ox, Hc, Wc, Bs, wgt, cnt, k...);
     return NINT_OK; }); });
   if (rc != NINT_OK) return rc;
   NINT_LAUNCH_CHECK();
-  hipLaunchKernelGGL(loss_spec_final_kernel, dim3(1), dim3(256), 0, st, partial, nblk, loss_out, stats, cnt, k);
+  hipLaunchKernelGGL((loss_final_kernel<typename Elem::Mix, Coef...>), dim3(1), dim3(256), 0, st, partial, nblk, loss_out, stats, cnt, k...);
   NINT_LAUNCH_CHECK();
   return NINT_OK;
+}
+
+// what the one-step fused entries check first (the sequence entries: head_seq_args_ok)
+static bool head_loss_args_ok(const void* h_slab, int N, int Ch, int O, const float* w, const nint_geom* g, int dtype) {
+  return h_slab && w && g && N > 0 && O > 0 && Ch > 0 && (dtype == NINT_BF16 || dtype == NINT_F32);
+}
+// the 16-byte channel vectors of the sequence entries' slabs
+static inline bool head_seq_aligned(const void* h_slab, const void* dh_seq) { return ((((uintptr_t)h_slab) | ((uintptr_t)dh_seq)) & 15) == 0; }
+
+// Every fused entry: NINT_E_ARG, then NINT_E_SHAPE for the channel count (wider heads run nint_head_fwd[_seq] + the plain
+// loss entry of the same element + nint_head_bwd[_seq]), then NINT_E_ALIGN, then the launcher's NINT_E_SHAPE for the LDS.
+extern "C" int nint_head_loss_fused(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w, const float* b,
+                                    const float* y, float* dpred, void* dh, float* loss_out, double* stats, const nint_geom* g,
+                                    int oy, int ox, int Hc, int Wc, int dtype, void* stream) {
+  if (!y || !dpred || !dh || !loss_out || !head_loss_args_ok(h_slab, N, Ch, O, w, g, dtype)) return NINT_E_ARG;
+  if (!loss_crop_ok(g->H, g->W, oy, ox, Hc, Wc, false)) return NINT_E_ARG;
+  if (Chp > 128 || Chp % 4) return NINT_E_SHAPE;
+  if (!loss_aligned(loss_out, nullptr, nullptr)) return NINT_E_ALIGN;
+  return head_loss_launch<false, LossPlain>(h_slab, n0, N, Ch, Chp, O, w, b, y, nullptr, (double)N * O * Hc * Wc, dpred, dh, loss_out, stats, g,
+                                            oy, ox, Hc, Wc, dtype, 0, stream);
+}
+
+extern "C" int nint_head_loss_fused_weighted(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w, const float* b,
+                                             const float* y, const float* wgt, double wsum, float* dpred, void* dh, float* loss_out,
+                                             double* stats, const nint_geom* g, int oy, int ox, int Hc, int Wc, int dtype, void* stream) {
+  if (!y || !dpred || !dh || !loss_out || !head_loss_args_ok(h_slab, N, Ch, O, w, g, dtype)) return NINT_E_ARG;
+  if (!loss_crop_ok(g->H, g->W, oy, ox, Hc, Wc, true) || !loss_weights_ok(wgt, wsum)) return NINT_E_ARG;
+  if (Chp > 128 || Chp % 4) return NINT_E_SHAPE;
+  if (!loss_aligned(loss_out, wgt, nullptr)) return NINT_E_ALIGN;
+  return head_loss_launch<false, LossMap>(h_slab, n0, N, Ch, Chp, O, w, b, y, wgt, (double)N * O * wsum, dpred, dh, loss_out, stats, g,
+                                          oy, ox, Hc, Wc, dtype, 0, stream);
 }
 
 extern "C" int nint_head_loss_fused_spec(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w, const float* b,
                                          const float* y, const float* wgt, double wsum, const nint_loss_spec* spec, float* dpred,
                                          void* dh, float* loss_out, double* stats, const nint_geom* g, int oy, int ox, int Hc,
                                          int Wc, int dtype, void* stream) {
-  if (!h_slab || !w || !y || !dpred || !dh || !loss_out || !g || N <= 0 || O <= 0 || Ch <= 0) return NINT_E_ARG;
-  if (oy < 0 || ox < 0 || Hc <= 0 || Wc <= 0 || oy + Hc > g->H || ox + Wc > g->W) return NINT_E_ARG;
-  if (dtype != NINT_BF16 && dtype != NINT_F32) return NINT_E_ARG;
+  if (!y || !dpred || !dh || !loss_out || !head_loss_args_ok(h_slab, N, Ch, O, w, g, dtype)) return NINT_E_ARG;
+  if (!loss_crop_ok(g->H, g->W, oy, ox, Hc, Wc, true)) return NINT_E_ARG;
   const int rc = loss_spec_check(spec, O, wgt, wsum);
   if (rc != NINT_OK) return rc;
-  if (Chp > 128 || Chp % 4) return NINT_E_SHAPE;   // wider heads: nint_head_fwd + nint_loss_crop_spec + nint_head_bwd
-  if ((((uintptr_t)loss_out) & 7) != 0 || (((uintptr_t)wgt) & 3) != 0 || (((uintptr_t)spec->ow) & 3) != 0) return NINT_E_ALIGN;
-  return head_loss_spec_impl<false>(h_slab, n0, N, Ch, Chp, O, w, b, y, wgt, loss_spec_cnt(spec, N, O, wgt, wsum, Hc, Wc),
-                                    loss_spec_k(spec), dpred, dh, loss_out, stats, g, oy, ox, Hc, Wc, dtype, 0, stream);
+  if (Chp > 128 || Chp % 4) return NINT_E_SHAPE;
+  if (!loss_aligned(loss_out, wgt, spec->ow)) return NINT_E_ALIGN;
+  return head_loss_launch<false, LossSpec>(h_slab, n0, N, Ch, Chp, O, w, b, y, wgt, loss_spec_cnt(spec, N, O, wgt, wsum, Hc, Wc), dpred, dh,
+                                           loss_out, stats, g, oy, ox, Hc, Wc, dtype, 0, stream, loss_spec_k(spec));
+}
+
+extern "C" int nint_head_loss_seq_fused(const void* h_slab, int B, int T, int Ch, int Chp, int O, const float* w, const float* b,
+                                        const float* y, float* dpred, void* dh_seq, float* loss_out, double* stats,
+                                        const nint_geom* g, int oy, int ox, int Hc, int Wc, int dtype, void* stream) {
+  if (!y || !dpred || !dh_seq || !loss_out || !head_seq_args_ok(h_slab, B, T, Ch, Chp, O, w, g, dtype)) return NINT_E_ARG;
+  if (!loss_crop_ok(g->H, g->W, oy, ox, Hc, Wc, true)) return NINT_E_ARG;
+  if (Chp > 128) return NINT_E_SHAPE;
+  if (!loss_aligned(loss_out, nullptr, nullptr) || !head_seq_aligned(h_slab, dh_seq)) return NINT_E_ALIGN;
+  return head_loss_launch<true, LossPlain>(h_slab, B, T * B, Ch, Chp, O, w, b, y, nullptr, (double)(T * B) * O * Hc * Wc, dpred, dh_seq, loss_out,
+                                           stats, g, oy, ox, Hc, Wc, dtype, B, stream);
+}
+
+extern "C" int nint_head_loss_seq_fused_weighted(const void* h_slab, int B, int T, int Ch, int Chp, int O, const float* w, const float* b,
+                                                 const float* y, const float* wgt, double wsum, float* dpred, void* dh_seq,
+                                                 float* loss_out, double* stats, const nint_geom* g, int oy, int ox, int Hc,
+                                                 int Wc, int dtype, void* stream) {
+  if (!y || !dpred || !dh_seq || !loss_out || !head_seq_args_ok(h_slab, B, T, Ch, Chp, O, w, g, dtype)) return NINT_E_ARG;
+  if (!loss_crop_ok(g->H, g->W, oy, ox, Hc, Wc, true) || !loss_weights_ok(wgt, wsum)) return NINT_E_ARG;
+  if (Chp > 128) return NINT_E_SHAPE;
+  if (!loss_aligned(loss_out, wgt, nullptr) || !head_seq_aligned(h_slab, dh_seq)) return NINT_E_ALIGN;
+  return head_loss_launch<true, LossMap>(h_slab, B, T * B, Ch, Chp, O, w, b, y, wgt, (double)(T * B) * O * wsum, dpred, dh_seq, loss_out,
+                                         stats, g, oy, ox, Hc, Wc, dtype, B, stream);
 }
 
 extern "C" int nint_head_loss_seq_fused_spec(const void* h_slab, int B, int T, int Ch, int Chp, int O, const float* w, const float* b,
@@ -1297,17 +1163,15 @@ extern "C" int nint_head_loss_seq_fused_spec(const void* h_slab, int B, int T, i
                                              void* dh_seq, float* loss_out, double* stats, const nint_geom* g, int oy, int ox,
                                              int Hc, int Wc, int dtype, void* stream) {
   if (!y || !dpred || !dh_seq || !loss_out || !head_seq_args_ok(h_slab, B, T, Ch, Chp, O, w, g, dtype)) return NINT_E_ARG;
-  if (oy < 0 || ox < 0 || Hc <= 0 || Wc <= 0 || oy + Hc > g->H || ox + Wc > g->W) return NINT_E_ARG;
-  if ((long long)T * O > INT_MAX) return NINT_E_ARG;
+  if (!loss_crop_ok(g->H, g->W, oy, ox, Hc, Wc, true) || (long long)T * O > INT_MAX) return NINT_E_ARG;
   const int rc = loss_spec_check(spec, T * O, wgt, wsum);
   if (rc != NINT_OK) return rc;
-  if (Chp > 128) return NINT_E_SHAPE;              // wider heads: nint_head_fwd_seq + nint_loss_crop_spec + nint_head_bwd_seq
-  if ((((uintptr_t)loss_out) & 7) != 0 || ((((uintptr_t)h_slab) | ((uintptr_t)dh_seq)) & 15) != 0 || (((uintptr_t)wgt) & 3) != 0 ||
-      (((uintptr_t)spec->ow) & 3) != 0) return NINT_E_ALIGN;
+  if (Chp > 128) return NINT_E_SHAPE;
+  if (!loss_aligned(loss_out, wgt, spec->ow) || !head_seq_aligned(h_slab, dh_seq)) return NINT_E_ALIGN;
   // with ow the weights run over (step, output): cnt = B * osum * wsum; without, the twin's (T*B) * O * wsum
   const double cnt = loss_spec_cnt(spec, spec->ow ? B : T * B, O, wgt, wsum, Hc, Wc);
-  return head_loss_spec_impl<true>(h_slab, B, T * B, Ch, Chp, O, w, b, y, wgt, cnt, loss_spec_k(spec), dpred, dh_seq, loss_out,
-                                   stats, g, oy, ox, Hc, Wc, dtype, B, stream);
+  return head_loss_launch<true, LossSpec>(h_slab, B, T * B, Ch, Chp, O, w, b, y, wgt, cnt, dpred, dh_seq, loss_out, stats, g, oy, ox, Hc, Wc,
+                                          dtype, B, stream, loss_spec_k(spec));
 }
 
 // ------------------------------------------------------------------------------ evaluation: skill sums (test.ipynb)
@@ -1351,10 +1215,8 @@ struct SkillPredPlain {
   __device__ __forceinline__ void sample(int) {}
   __device__ __forceinline__ float operator()(int n, int u) const { return pred[((size_t)n * O + o0 + u) * HW + off]; }
 };
-// ... or from the hidden state: head_fwd_body's arithmetic (zero-padded weight rows in LDS, the same channel order).  The
-// outputs of a sample run as head_fwd_body's own loop -- one output per turn, not unrolled, the result stored (here to the
-// thread's LDS column) -- so that the compiler forms each dot product as it does there: it fuses most multiply-adds of the
-// chain and leaves some as a packed multiply and an add, and pred_out has to match nint_head_fwd bit for bit.
+// ... or from the hidden state: head_fwd_body's arithmetic (zero-padded weight rows in LDS, head_dot), so pred_out matches
+// nint_head_fwd bit for bit.  The sample's predictions wait in the thread's LDS column p_s for operator().
 template <int DT, int CHV>
 struct SkillPredHead {
   const void* __restrict__ h; const float* w_s; float* p_s; const float* __restrict__ b; int n0, Chp, o0, on; size_t img, off;
@@ -1368,18 +1230,8 @@ struct SkillPredHead {
       const f32x4_t v = (c < Chp) ? load_vec4<DT>(h, hb + c) : (f32x4_t){0.f, 0.f, 0.f, 0.f};
       hv[c] = v[0]; hv[c + 1] = v[1]; hv[c + 2] = v[2]; hv[c + 3] = v[3];
     }
-    float* out = p_s + threadIdx.x;
-#pragma unroll 1
-    for (int u = 0; u < on; ++u) {
-      float acc = b ? b[o0 + u] : 0.f;
-      const f32x4_t* wr = (const f32x4_t*)(w_s + u * CHV);
-#pragma unroll
-      for (int c = 0; c < CHV; c += 4) {
-        const f32x4_t wv = wr[c / 4];
-        acc += wv[0] * hv[c]; acc += wv[1] * hv[c + 1]; acc += wv[2] * hv[c + 2]; acc += wv[3] * hv[c + 3];
-      }
-      out[u * 256] = acc;
-    }
+#pragma unroll 1                                 // (one output's weight row in registers at a time)
+    for (int u = 0; u < on; ++u) p_s[u * 256 + threadIdx.x] = head_dot<CHV>(b ? b[o0 + u] : 0.f, w_s + u * CHV, hv);
   }
   __device__ __forceinline__ float operator()(int, int u) const { return p_s[u * 256 + threadIdx.x]; }
 };

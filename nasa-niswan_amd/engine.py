@@ -541,6 +541,19 @@ class SeqEngine:
               "nint_head_bwd_seq_acc")
         return dw.view(O, Ch, 1, 1), db
 
+    def _loss_entry(self, seq: bool, weights, spec):
+        """The fused head + loss entry of (one step | every step) x (plain | weight map | spec): the C function, its name
+        for `check`, and the arguments between `y` and `dpred`.  The one place that chooses among the six."""
+        stem = "nint_head_loss_seq_fused" if seq else "nint_head_loss_fused"
+        wgt, wsum = weights if weights is not None else (None, 0.0)
+        if spec is not None:
+            name, extra = stem + "_spec", (ptr(wgt), wsum, C.byref(spec))
+        elif weights is not None:
+            name, extra = stem + "_weighted", (ptr(wgt), wsum)
+        else:
+            name, extra = stem, ()
+        return getattr(self.lib, name), name, extra
+
     def head_loss_seq_fused(self, ws: Workspace, w: torch.Tensor, b: Optional[torch.Tensor], y: torch.Tensor, dpred: torch.Tensor,
                             scratch: torch.Tensor, stats: torch.Tensor, halo, Hc: int, Wc: int, weights=None, spec=None) -> bool:
         """head_loss_fused over every step (nint_head_loss_seq_fused): y (B, T, O, Hc, Wc); dpred (T*B, O, H, W) in image
@@ -549,23 +562,9 @@ class SeqEngine:
         Ch, Chp, O, w2, b2 = self._head_args(w, b)
         if self._beyond_fused_head(Chp, O):
             return False
-        if spec is not None:
-            wgt, wsum = weights if weights is not None else (None, 0.0)
-            check(self.lib.nint_head_loss_seq_fused_spec(ptr(ws.h[-1]), ws.B, ws.T, Ch, Chp, O, ptr(w2), ptr(b2), ptr(y), ptr(wgt), wsum,
-                                                         C.byref(spec), ptr(dpred), ptr(ws.dh_seq_slab(self)), ptr(scratch), ptr(stats),
-                                                         C.byref(ws.g), halo[0], halo[1], Hc, Wc, self.dt, stream_ptr()),
-                  "nint_head_loss_seq_fused_spec")
-            return True
-        if weights is not None:
-            wgt, wsum = weights
-            check(self.lib.nint_head_loss_seq_fused_weighted(ptr(ws.h[-1]), ws.B, ws.T, Ch, Chp, O, ptr(w2), ptr(b2), ptr(y), ptr(wgt),
-                                                             wsum, ptr(dpred), ptr(ws.dh_seq_slab(self)), ptr(scratch), ptr(stats),
-                                                             C.byref(ws.g), halo[0], halo[1], Hc, Wc, self.dt, stream_ptr()),
-                  "nint_head_loss_seq_fused_weighted")
-            return True
-        check(self.lib.nint_head_loss_seq_fused(ptr(ws.h[-1]), ws.B, ws.T, Ch, Chp, O, ptr(w2), ptr(b2), ptr(y), ptr(dpred),
-                                                ptr(ws.dh_seq_slab(self)), ptr(scratch), ptr(stats), C.byref(ws.g), halo[0], halo[1],
-                                                Hc, Wc, self.dt, stream_ptr()), "nint_head_loss_seq_fused")
+        fn, name, extra = self._loss_entry(True, weights, spec)
+        check(fn(ptr(ws.h[-1]), ws.B, ws.T, Ch, Chp, O, ptr(w2), ptr(b2), ptr(y), *extra, ptr(dpred), ptr(ws.dh_seq_slab(self)),
+                 ptr(scratch), ptr(stats), C.byref(ws.g), halo[0], halo[1], Hc, Wc, self.dt, stream_ptr()), name)
         return True
 
     def head_loss_fused(self, ws: Workspace, w: torch.Tensor, b: Optional[torch.Tensor], y: torch.Tensor, dpred: torch.Tensor,
@@ -579,23 +578,9 @@ class SeqEngine:
         Ch, Chp, O, w2, b2 = self._head_args(w, b)
         if self._beyond_fused_head(Chp, O):
             return False
-        if spec is not None:
-            wgt, wsum = weights if weights is not None else (None, 0.0)
-            check(self.lib.nint_head_loss_fused_spec(ptr(ws.h[-1]), ws.T * ws.B, ws.B, Ch, Chp, O, ptr(w2), ptr(b2), ptr(y), ptr(wgt), wsum,
-                                                     C.byref(spec), ptr(dpred), ptr(ws.dh[-1]), ptr(scratch), ptr(stats), C.byref(ws.g),
-                                                     halo[0], halo[1], Hc, Wc, self.dt, stream_ptr()),
-                  "nint_head_loss_fused_spec")
-            return True
-        if weights is not None:
-            wgt, wsum = weights
-            check(self.lib.nint_head_loss_fused_weighted(ptr(ws.h[-1]), ws.T * ws.B, ws.B, Ch, Chp, O, ptr(w2), ptr(b2), ptr(y), ptr(wgt),
-                                                         wsum, ptr(dpred), ptr(ws.dh[-1]), ptr(scratch), ptr(stats), C.byref(ws.g),
-                                                         halo[0], halo[1], Hc, Wc, self.dt, stream_ptr()),
-                  "nint_head_loss_fused_weighted")
-            return True
-        check(self.lib.nint_head_loss_fused(ptr(ws.h[-1]), ws.T * ws.B, ws.B, Ch, Chp, O, ptr(w2), ptr(b2), ptr(y), ptr(dpred),
-                                            ptr(ws.dh[-1]), ptr(scratch), ptr(stats), C.byref(ws.g), halo[0], halo[1], Hc, Wc,
-                                            self.dt, stream_ptr()), "nint_head_loss_fused")
+        fn, name, extra = self._loss_entry(False, weights, spec)
+        check(fn(ptr(ws.h[-1]), ws.T * ws.B, ws.B, Ch, Chp, O, ptr(w2), ptr(b2), ptr(y), *extra, ptr(dpred), ptr(ws.dh[-1]),
+                 ptr(scratch), ptr(stats), C.byref(ws.g), halo[0], halo[1], Hc, Wc, self.dt, stream_ptr()), name)
         return True
 
     def head_skill(self, ws: Workspace, w: torch.Tensor, b: Optional[torch.Tensor], y: torch.Tensor, slots, acc,

@@ -102,24 +102,37 @@ class DeviceWeights:
         return self.map, self.wsum
 
 
-class _CropMSEL1(torch.autograd.Function):
+def crop_loss_launch(pred, y, dpred, scratch, stats, N, O, H, W, oy, ox, Hc, Wc, weights=None, spec=None):
+    """The stand-alone loss launch on device tensors, and the one place that chooses its entry: ``nint_loss_crop_spec``
+    with a ``spec`` (a _lib.NintLossSpec; ``scratch`` then of NINT_LOSS_SPEC_SCRATCH_FLOATS floats), else
+    ``nint_loss_mse_l1_crop_weighted`` with ``weights = (wgt, wsum)``, else ``nint_loss_mse_l1_crop``.  ``dpred`` and
+    ``stats`` may be None."""
+    wgt, wsum = weights if weights is not None else (None, 0.0)
+    if spec is not None:
+        name, extra = "nint_loss_crop_spec", (ptr(wgt), wsum, C.byref(spec))
+    elif weights is not None:
+        name, extra = "nint_loss_mse_l1_crop_weighted", (ptr(wgt), wsum)
+    else:
+        name, extra = "nint_loss_mse_l1_crop", ()
+    check(getattr(_lib.load(), name)(ptr(pred), ptr(y), *extra, ptr(dpred), ptr(scratch), ptr(stats), N, O, H, W, oy, ox, Hc, Wc,
+                                     stream_ptr()), name)
+
+
+class _CropLoss(torch.autograd.Function):
+    """crop_loss_launch as an autograd function: ``spec`` None runs the MSE + L1 entries, with or without the map"""
+
     @staticmethod
-    def forward(ctx, pred, y, wgt, wsum, oy, ox):
-        lib = _lib.load()
+    def forward(ctx, pred, y, wgt, wsum, spec, oy, ox):
         N, O, H, W = pred.shape
         Hc, Wc = y.shape[-2], y.shape[-1]
         p = pred.detach().float().contiguous()
         yv = y.detach().float().contiguous()
         if yv.numel() != N * O * Hc * Wc:
             raise ValueError(f"target {tuple(y.shape)} does not match the prediction {tuple(pred.shape)}")
-        scratch = torch.empty(NINT_LOSS_SCRATCH_FLOATS, dtype=torch.float32, device=p.device)
+        scratch = torch.empty(NINT_LOSS_SCRATCH_FLOATS if spec is None else NINT_LOSS_SPEC_SCRATCH_FLOATS, dtype=torch.float32,
+                              device=p.device)
         dpred = torch.empty_like(p) if ctx.needs_input_grad[0] else None
-        if wgt is None:
-            check(lib.nint_loss_mse_l1_crop(ptr(p), ptr(yv), ptr(dpred), ptr(scratch), None, N, O, H, W, oy, ox, Hc, Wc,
-                                            stream_ptr()), "nint_loss_mse_l1_crop")
-        else:
-            check(lib.nint_loss_mse_l1_crop_weighted(ptr(p), ptr(yv), ptr(wgt), wsum, ptr(dpred), ptr(scratch), None, N, O, H, W,
-                                                     oy, ox, Hc, Wc, stream_ptr()), "nint_loss_mse_l1_crop_weighted")
+        crop_loss_launch(p, yv, dpred, scratch, None, N, O, H, W, oy, ox, Hc, Wc, None if wgt is None else (wgt, wsum), spec)
         ctx.dpred = dpred
         ctx.dtype = pred.dtype
         return scratch[0].clone()
@@ -127,7 +140,7 @@ class _CropMSEL1(torch.autograd.Function):
     @staticmethod
     def backward(ctx, upstream):
         g = None if ctx.dpred is None else (ctx.dpred * upstream).to(ctx.dtype)
-        return g, None, None, None, None, None
+        return g, None, None, None, None, None, None
 
 
 class CropMSEL1Loss(torch.nn.Module):
@@ -147,7 +160,7 @@ class CropMSEL1Loss(torch.nn.Module):
         if pred.dim() != 4 or pred.device.type != "cuda":
             raise _lib.NintError("CropMSEL1Loss needs the uncropped prediction (B, O, H, W) on the MI355X (cuda)")
         wgt, wsum = (None, 0.0) if self._weights is None else self._weights.on(pred.device, y.shape[-2], y.shape[-1])
-        return _CropMSEL1.apply(pred, y, wgt, wsum, self.halo[0], self.halo[1])
+        return _CropLoss.apply(pred, y, wgt, wsum, None, self.halo[0], self.halo[1])
 
 
 def _weight_vector(values, what: str) -> np.ndarray:
@@ -240,30 +253,6 @@ class LossSpec:
                 f"step_weights={None if self.step_weights is None else self.step_weights.tolist()})")
 
 
-class _CropSpec(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, pred, y, wgt, wsum, spec, oy, ox):
-        lib = _lib.load()
-        N, O, H, W = pred.shape
-        Hc, Wc = y.shape[-2], y.shape[-1]
-        p = pred.detach().float().contiguous()
-        yv = y.detach().float().contiguous()
-        if yv.numel() != N * O * Hc * Wc:
-            raise ValueError(f"target {tuple(y.shape)} does not match the prediction {tuple(pred.shape)}")
-        scratch = torch.empty(NINT_LOSS_SPEC_SCRATCH_FLOATS, dtype=torch.float32, device=p.device)
-        dpred = torch.empty_like(p) if ctx.needs_input_grad[0] else None
-        check(lib.nint_loss_crop_spec(ptr(p), ptr(yv), ptr(wgt), wsum, C.byref(spec), ptr(dpred), ptr(scratch), None, N, O, H, W,
-                                      oy, ox, Hc, Wc, stream_ptr()), "nint_loss_crop_spec")
-        ctx.dpred = dpred
-        ctx.dtype = pred.dtype
-        return scratch[0].clone()
-
-    @staticmethod
-    def backward(ctx, upstream):
-        g = None if ctx.dpred is None else (ctx.dpred * upstream).to(ctx.dtype)
-        return g, None, None, None, None, None, None
-
-
 class CropLoss(torch.nn.Module):
     """``CropMSEL1Loss`` with the configurable loss: ``loss = criterion(y, pred)`` with the UNCROPPED ``pred (B, O, H, W)`` on
     the device and ``y (B, [O,] Hc, Wc)``; ``spec`` a ``LossSpec`` (None: the default mix, MSE + L1) and ``weights`` the
@@ -283,4 +272,4 @@ class CropLoss(torch.nn.Module):
         if pred.dim() != 4 or pred.device.type != "cuda":
             raise _lib.NintError("CropLoss needs the uncropped prediction (B, O, H, W) on the MI355X (cuda)")
         wgt, wsum = (None, 0.0) if self._weights is None else self._weights.on(pred.device, y.shape[-2], y.shape[-1])
-        return _CropSpec.apply(pred, y, wgt, wsum, self.spec.on(pred.device, pred.shape[1]), self.halo[0], self.halo[1])
+        return _CropLoss.apply(pred, y, wgt, wsum, self.spec.on(pred.device, pred.shape[1]), self.halo[0], self.halo[1])

@@ -26,15 +26,14 @@
 No autograd graph, no per-kernel Python, no host synchronisation inside the step."""
 from __future__ import annotations
 
-import ctypes as C
 from typing import List, Optional, Tuple
 
 import torch
 
 from . import _lib
-from ._lib import NINT_LOSS_SPEC_SCRATCH_FLOATS, NINT_LOSS_STATS, check, ptr, stream_ptr
+from ._lib import NINT_LOSS_SPEC_SCRATCH_FLOATS, NINT_LOSS_STATS
 from .model import ConvLSTM
-from .loss import DeviceWeights, LossSpec
+from .loss import DeviceWeights, LossSpec, crop_loss_launch
 from .optim import FlatParams, FusedAdam
 
 
@@ -167,19 +166,7 @@ class FusedTrainer:
 
     def _loss(self, pred, yv, dpred, N, O, H, W, Hc, Wc, wts, spec=None):
         """the stand-alone loss launch of the three-launch paths"""
-        if spec is not None:
-            wgt, wsum = wts if wts is not None else (None, 0.0)
-            check(self.lib.nint_loss_crop_spec(ptr(pred), ptr(yv), ptr(wgt), wsum, C.byref(spec), ptr(dpred), ptr(self.scratch),
-                                               ptr(self.stats), N, O, H, W, self.halo[0], self.halo[1], Hc, Wc, stream_ptr()),
-                  "nint_loss_crop_spec")
-        elif wts is None:
-            check(self.lib.nint_loss_mse_l1_crop(ptr(pred), ptr(yv), ptr(dpred), ptr(self.scratch), ptr(self.stats),
-                                                 N, O, H, W, self.halo[0], self.halo[1], Hc, Wc, stream_ptr()),
-                  "nint_loss_mse_l1_crop")
-        else:
-            check(self.lib.nint_loss_mse_l1_crop_weighted(ptr(pred), ptr(yv), ptr(wts[0]), wts[1], ptr(dpred), ptr(self.scratch),
-                                                          ptr(self.stats), N, O, H, W, self.halo[0], self.halo[1], Hc, Wc,
-                                                          stream_ptr()), "nint_loss_mse_l1_crop_weighted")
+        crop_loss_launch(pred, yv, dpred, self.scratch, self.stats, N, O, H, W, self.halo[0], self.halo[1], Hc, Wc, wts, spec)
 
     # ------------------------------------------------------------------ pieces
     def forward_loss(self, X: torch.Tensor, y: torch.Tensor, train: bool = True):

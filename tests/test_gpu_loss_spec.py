@@ -204,7 +204,7 @@ def run_seq(hc, entry, y, wm, sp, st0=BEFORE):
 
 
 @pytest.mark.parametrize("dtype", ["f32", "bf16"])
-@pytest.mark.parametrize("Ch,O", [(8, 1), (40, 3), (72, 3)])
+@pytest.mark.parametrize("Ch,O", [(8, 1), (40, 3), (72, 3), (32, 3), (64, 3), (128, 3)])    # (the last three: Ch = CHV, data in the unfused tail)
 def test_spec_110_is_the_sequence_entries_bit_for_bit(pkg, Ch, O, dtype):
     hc, y, wm = seq_case(pkg, Ch, O, dtype)
     for m in (None, wm):
@@ -297,7 +297,8 @@ def test_fused_spec_equals_the_three_launches_bit_for_bit(lib, dt, Ch, O, N, n0,
 
 
 @pytest.mark.parametrize("dtype", ["f32", "bf16"])
-@pytest.mark.parametrize("Ch,O", [(Ch, O) for Ch in (8, 40, 72) for O in (1, 3)] + [(72, 200)])
+@pytest.mark.parametrize("Ch,O", [(Ch, O) for Ch in (8, 40, 72) for O in (1, 3)] + [(72, 200)] +
+                         [(32, 3), (64, 3), (128, 3)])    # (Ch = CHV: data in the 12 staged channels the dot product leaves unfused)
 def test_seq_fused_spec_equals_the_three_launches_bit_for_bit(pkg, Ch, O, dtype):
     """The sequence form with step weights (B = 2, T = 3; the first step dropped, the second discounted) times output weights:
     nint_head_loss_seq_fused_spec against nint_head_fwd_seq -> nint_loss_crop_spec (N = B, O' = T*O, the same ow) ->

@@ -132,8 +132,10 @@ def test_splits_of_a_call_change_no_bit(lib, small):
                    pixA.cpu().numpy(), one.cpu().numpy())          # gamma(n - 1) * sum |addends|, n <= 18 samples per cell
 
 
-# (the last three: the weight image [O][CHV] beyond 64 KiB while the fused head passes still hold the shape)
-@pytest.mark.parametrize("dt,Ch,O", [(0, 16, 20), (1, 16, 20), (1, 8, 1), (0, 48, 3), (1, 128, 20), (1, 128, 200), (0, 48, 300), (0, 16, 600)])
+# (the three before the last five: the weight image [O][CHV] beyond 64 KiB while the fused head passes still hold the shape; the last
+# five: Ch = CHV, so the 12 staged channels the head's dot product leaves unfused hold data, in both storage types)
+@pytest.mark.parametrize("dt,Ch,O", [(0, 16, 20), (1, 16, 20), (1, 8, 1), (0, 48, 3), (1, 128, 20), (1, 128, 200), (0, 48, 300), (0, 16, 600),
+                                     (0, 32, 3), (1, 32, 3), (0, 64, 3), (1, 64, 3), (0, 128, 3)])
 def test_fused_entry_equals_head_fwd_then_plain_entry(lib, dt, Ch, O):
     """nint_head_skill_accum = nint_head_fwd followed by nint_skill_accum, bit for bit: pred_out, pix and sample (the
     relation nint_head_loss_fused has to its three separate launches; the same shapes, all three CHV instances)."""

@@ -241,6 +241,12 @@ FUSED_CASES = [
     pytest.param(0, 48, 300, 1, 1, 9, 13, 2, 1, 5, 11, 64, ("window", "optin"), id="fused64-f32-window[weights>64KiB]-Ch48-O300-n0=1"),
     pytest.param(0, 16, 600, 2, 0, 9, 13, 2, 3, 4, 5, 32, ("window", "optin"), id="fused32-f32-window[weights>64KiB]-Ch16-O600"),
     pytest.param(1, 16, 1088, 1, 0, 9, 13, 2, 2, 5, 9, 32, ("window", "optin"), id="fused32-bf16-window[last O the LDS rule admits]-Ch16-O1088"),
+    # "tail": hidden values and weights in the last 12 STAGED channels (Ch > CHV - 12), the ones the head's dot product joins by a
+    # rounded product and an add instead of a fused multiply-add (include/nint.h): with zeros there both give the same bits, and no
+    # fused-vs-launches comparison sees how a body forms them.  (The bf16 64 and both 128 cases above have Ch = CHV as well.)
+    pytest.param(0, 24, 5, 2, 1, 5, 70, 1, 2, 3, 60, 32, ("tail", "ragged"), id="fused32-f32-tail-channels-Ch24-n0=1"),
+    pytest.param(1, 32, 5, 2, 0, 5, 70, 1, 2, 3, 60, 32, ("tail", "ragged"), id="fused32-bf16-tail-channels-Ch32"),
+    pytest.param(0, 56, 5, 2, 0, 5, 70, 1, 2, 3, 60, 64, ("tail", "ragged"), id="fused64-f32-tail-channels-Ch56"),
 ]
 
 
@@ -259,6 +265,8 @@ def test_head_loss_fused_elementwise(lib, dt, Ch, O, N, n0, H, W, oy, ox, Hc, Wc
     assert ("many" in tags) == ((npix + 63) // 64 > LOSS_BLOCKS_MAX)
     if "ragged" in tags:
         assert npix % 64 != 0
+    if "tail" in tags:
+        assert Ch > chv - 12 and npix > 64
     if "asym" in tags:
         assert oy != H - Hc - oy and ox != W - Wc - ox
     if "full" in tags:

@@ -132,9 +132,11 @@ def test_loss_mse_l1_crop_matches_oracle(lib):
         assert abs(r2 - O.r2_score_np(y.numpy(), pc.numpy())) < 1e-7
 
 
-# (the last three: the weight image [O][CHV] beyond 64 KiB while the fused pass still holds the shape)
+# (the three before the last five: the weight image [O][CHV] beyond 64 KiB while the fused pass still holds the shape; the last five:
+# Ch = CHV, so the 12 staged channels the head's dot product leaves unfused hold data, in both storage types)
 @pytest.mark.parametrize("dt,Ch,O", [(0, 16, 20), (1, 16, 20), (1, 8, 1), (0, 48, 3), (1, 128, 20), (0, 100, 3), (1, 16, 200),
-                                     (1, 128, 200), (0, 48, 300), (0, 16, 600)])
+                                     (1, 128, 200), (0, 48, 300), (0, 16, 600),
+                                     (0, 32, 3), (1, 32, 3), (0, 64, 3), (1, 64, 3), (0, 128, 3)])
 def test_head_loss_fused_equals_the_three_separate_launches(lib, dt, Ch, O):
     """The training fast path nint_head_loss_fused (head forward + crop + MSE/L1 sums + dpred + dL/dh in one pass) must
     be bit-identical to nint_head_fwd -> nint_loss_mse_l1_crop -> nint_head_bwd, which the oracle tests pin; the

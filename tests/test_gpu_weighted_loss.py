@@ -217,7 +217,8 @@ def run_seq_fused(hc, weighted, y, wgt, wsum, st0=None):
 
 
 @pytest.mark.parametrize("dtype", ["f32", "bf16"])
-@pytest.mark.parametrize("Ch,O", [(Ch, O) for Ch in (8, 40, 72) for O in (1, 3)] + [(72, 200)])
+@pytest.mark.parametrize("Ch,O", [(Ch, O) for Ch in (8, 40, 72) for O in (1, 3)] + [(72, 200)] +
+                         [(32, 3), (64, 3), (128, 3)])    # (Ch = CHV: data in the 12 staged channels the dot product leaves unfused)
 def test_seq_fused_weighted_equals_the_three_launches_bit_for_bit(pkg, Ch, O, dtype):
     """The sequence form (B = 2, T = 3, 12 x 20; the 32-, 64- and 128-channel bodies; 200 outputs at 72 channels: a weight image
     beyond 64 KiB that the fused pass still holds): nint_head_loss_seq_fused_weighted against
