@@ -3,6 +3,7 @@ sized for 288 GB of HBM: every time step's slabs stay resident) and drives the C
 library for one ConvLSTM forward / BPTT.  No arithmetic happens in Python or in torch ops."""
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence, Tuple
@@ -62,7 +63,7 @@ class Workspace:
         self.B, self.T, self.H, self.W, self.train = B, T, H, W, train
         self.in_use = False
         self.gen = 0            # bumped by every SeqEngine.acquire: an autograd graph stamps it and refuses a backward after a reuse
-        dev, es, kc = eng.device, eng.es, eng.kc
+        dev, es = eng.device, eng.es
         lib = _lib.load()
         self.g = NintGeom()
         check(lib.nint_geom_make(C.byref(self.g), H, W, eng.P), "nint_geom_make")
@@ -70,11 +71,11 @@ class Workspace:
         halo_px, comp_px = g.Hh * g.Wh, H * W
         u8 = dict(dtype=torch.uint8, device=dev)
         f32 = dict(dtype=torch.float32, device=dev)
-        Cxp0 = eng.cfgs[0].padded(kc)[0]
+        Cxp0 = eng.layers[0].Cxp
         self.xs = torch.zeros(T * B * halo_px * Cxp0 * es, **u8)
         self.h, self.c, self.gates, self.dG, self.dh, self.dc = [], [], [], [], [], []
-        for cfg in eng.cfgs:
-            Cxp, Ch16, Chp = cfg.padded(kc)
+        for ly in eng.layers:
+            Ch16, Chp = ly.Ch16, ly.Chp
             self.h.append(torch.zeros((T + 1) * B * halo_px * Chp * es, **u8))
             self.c.append(torch.zeros((T + 1) * B * comp_px * Chp, **f32))
             if train:
@@ -108,18 +109,15 @@ class Workspace:
         """ET compact [T*B][H][W][Chp of the top layer]: the per-step head gradients (nint_seq.dh_seq).  Allocated when
         sequence gradients are first asked for on this workspace: the many-to-one path never pays for it."""
         if self._dh_seq is None:
-            Chp = eng.cfgs[-1].padded(eng.kc)[2]
-            self._dh_seq = torch.empty(self.T * self.B * self.H * self.W * Chp * eng.es, dtype=torch.uint8, device=eng.device)
+            self._dh_seq = torch.empty(self.T * self.B * self.H * self.W * eng.layers[-1].Chp * eng.es, dtype=torch.uint8, device=eng.device)
         return self._dh_seq
 
     # byte offsets of slab (t) inside the per-layer stacks
     def h_view(self, eng, l: int, slot: int) -> int:
-        Chp = eng.cfgs[l].padded(eng.kc)[2]
-        return self.h[l].data_ptr() + slot * self.B * self.g.Hh * self.g.Wh * Chp * eng.es
+        return self.h[l].data_ptr() + slot * self.B * self.g.Hh * self.g.Wh * eng.layers[l].Chp * eng.es
 
     def c_view(self, eng, l: int, slot: int) -> int:
-        Chp = eng.cfgs[l].padded(eng.kc)[2]
-        return self.c[l].data_ptr() + slot * self.B * self.H * self.W * Chp * 4
+        return self.c[l].data_ptr() + slot * self.B * self.H * self.W * eng.layers[l].Chp * 4
 
 
 class ConvLSTMState:
@@ -138,10 +136,9 @@ class ConvLSTMState:
         check(eng.lib.nint_geom_make(C.byref(self.g), self.H, self.W, eng.P), "nint_geom_make")
         new = torch.zeros if zero else torch.empty       # (a state that one whole-image copy fills at once needs no fill)
         self.h, self.c = [], []
-        for cfg in eng.cfgs:
-            Chp = cfg.padded(eng.kc)[2]
-            self.h.append(new(self.B * self.g.Hh * self.g.Wh * Chp * eng.es, dtype=torch.uint8, device=eng.device))
-            self.c.append(new(self.B * self.H * self.W * Chp, dtype=torch.float32, device=eng.device))
+        for ly in eng.layers:
+            self.h.append(new(self.B * self.g.Hh * self.g.Wh * ly.Chp * eng.es, dtype=torch.uint8, device=eng.device))
+            self.c.append(new(self.B * self.H * self.W * ly.Chp, dtype=torch.float32, device=eng.device))
 
     @property
     def dtype(self) -> str:
@@ -156,18 +153,9 @@ class ConvLSTMState:
 
     def tensors(self) -> List[Tuple[torch.Tensor, torch.Tensor]]:
         """The reference's ``hidden_states`` list: [(h, c)] per layer, (B, Ch, H, W) f32 (model.py:259-262,270)."""
-        eng, out = self.eng, []
-        st = stream_ptr()
-        for l, cfg in enumerate(eng.cfgs):
-            Chp = cfg.padded(eng.kc)[2]
-            h = torch.empty(self.B, cfg.Ch, self.H, self.W, dtype=torch.float32, device=eng.device)
-            c = torch.empty_like(h)
-            check(eng.lib.nint_unpack_halo(ptr(self.h[l]), ptr(h), 0, self.B, cfg.Ch, Chp, C.byref(self.g), eng.dt, st),
-                  "nint_unpack_halo")
-            check(eng.lib.nint_unpack_compact(ptr(self.c[l]), ptr(c), self.B, cfg.Ch, Chp, self.H, self.W, NINT_F32, st),
-                  "nint_unpack_compact")
-            out.append((h, c))
-        return out
+        eng, B, g = self.eng, self.B, self.g
+        return [(eng._unpack_h(l, h.data_ptr(), B, g), eng._unpack_compact(l, c.data_ptr(), B, g))
+                for l, (h, c) in enumerate(zip(self.h, self.c))]
 
     def select(self, lanes: Sequence[int]) -> "ConvLSTMState":
         """A new state whose sample b is this state's sample lanes[b] -- a permutation, a subset, a repetition -- or the zero
@@ -296,17 +284,16 @@ class SeqEngine:
                                  "kernel is instantiated for kernel sizes 1, 3, 5 and 7 only (the reference accepts any odd k, "
                                  "model.py:204); forward / inference (torch.no_grad()) work for every odd k")
         key = (B, T, H, W, train, has_init)
-        for ws in self.pool.setdefault(key, []):
-            if not ws.in_use:
-                ws.in_use = True
-                ws.gen += 1
-                ws.seq.probe, ws.seq.probe_mask, ws.seq.probe_slots = None, 0, 0     # (a trainer's timing probes do not outlive its step)
-                ws.seq.has_init_state = int(has_init)                                # (nor does a zero_start)
-                return ws
-        ws = Workspace(self, B, T, H, W, train, has_init)
-        for l, ly in enumerate(self.layers):
-            ws.seq.layer[l] = ly
-        self.pool[key].append(ws)
+        pool = self.pool.setdefault(key, [])
+        ws = next((w for w in pool if not w.in_use), None)
+        if ws is None:
+            ws = Workspace(self, B, T, H, W, train, has_init)
+            for l, ly in enumerate(self.layers):
+                ws.seq.layer[l] = ly
+            pool.append(ws)
+        else:
+            ws.seq.probe, ws.seq.probe_mask, ws.seq.probe_slots = None, 0, 0     # (a trainer's timing probes do not outlive its step)
+            ws.seq.has_init_state = int(has_init)                                # (nor does a zero_start)
         ws.in_use = True
         ws.gen += 1
         return ws
@@ -314,6 +301,16 @@ class SeqEngine:
     @staticmethod
     def release(ws: Workspace):
         ws.in_use = False
+
+    @contextlib.contextmanager
+    def window(self, B, T, H, W, train: bool, has_init: bool):
+        """``with eng.window(...) as ws``: acquire, and the release whatever happens inside -- how a caller that does not
+        hand the workspace to an autograd graph runs a window (pack_weights, [load_state,] forward, ... in the body)"""
+        ws = self.acquire(B, T, H, W, train, has_init)
+        try:
+            yield ws
+        finally:
+            self.release(ws)
 
     # ------------------------------------------------------------------ carried state (DESIGN.md 4.10)
     def new_state(self, B: int, H: int, W: int) -> ConvLSTMState:
@@ -325,14 +322,48 @@ class SeqEngine:
         hs, cs = self._state_tensors(pairs, None)
         B, _, H, W = hs[0].shape
         st = ConvLSTMState(self, B, H, W)
-        sp, g = stream_ptr(), C.byref(st.g)
-        for l, cfg in enumerate(self.cfgs):
-            Chp = cfg.padded(self.kc)[2]
-            hh = hs[l].detach().float().contiguous().view(B, 1, cfg.Ch, H, W)
-            check(self.lib.nint_pack_btchw(ptr(hh), ptr(st.h[l]), B, 1, cfg.Ch, Chp, g, self.dt, sp), "pack h")
-            cc = cs[l].detach().float().contiguous()
-            check(self.lib.nint_pack_compact(ptr(cc), ptr(st.c[l]), B, cfg.Ch, Chp, H, W, NINT_F32, sp), "pack c")
+        self._write_state(hs, cs, st._ptrs(), B, st.g)
         return st
+
+    # ------------------------------------------------------------------ the NCHW <-> slab boundary
+    # The only code that knows how a (B, Ch, H, W) f32 tensor of layer l lies in a slab: h in ET halo images [B][Hh][Wh][Chp],
+    # everything else (c, dL/dh, dL/dc) in compact images [B][H][W][Chp], f32 or (`et`) the engine's element type.  Slabs are
+    # given by device address, `g` is the problem's NintGeom, `what` the name a failing call is reported under.  The packers
+    # view the normalised tensor in the shape the kernel will read: a tensor of another size is refused (RuntimeError) before
+    # the launch, never read past its end.
+    def _pack_h(self, l: int, t: torch.Tensor, dst: int, B: int, g: NintGeom, what: str = "pack h"):
+        ly = self.layers[l]
+        src = t.detach().float().contiguous().view(B, 1, ly.Ch, g.H, g.W)
+        check(self.lib.nint_pack_btchw(ptr(src), C.c_void_p(dst), B, 1, ly.Ch, ly.Chp, C.byref(g), self.dt, stream_ptr()), what)
+
+    def _pack_compact(self, l: int, t: torch.Tensor, dst: int, B: int, g: NintGeom, et: bool = False, what: str = "pack c",
+                      add: bool = False):
+        """`add`: the slab receives old + t (nint_pack_compact_add) instead of t"""
+        ly = self.layers[l]
+        fn = self.lib.nint_pack_compact_add if add else self.lib.nint_pack_compact
+        src = t.detach().float().contiguous().view(B, ly.Ch, g.H, g.W)
+        check(fn(ptr(src), C.c_void_p(dst), B, ly.Ch, ly.Chp, g.H, g.W, self.dt if et else NINT_F32, stream_ptr()), what)
+
+    def _unpack_h(self, l: int, src: int, B: int, g: NintGeom, image0: int = 0) -> torch.Tensor:
+        """images image0 .. image0 + B of the halo slab that starts at `src`"""
+        ly = self.layers[l]
+        out = torch.empty(B, ly.Ch, g.H, g.W, dtype=torch.float32, device=self.device)
+        check(self.lib.nint_unpack_halo(C.c_void_p(src), ptr(out), image0, B, ly.Ch, ly.Chp, C.byref(g), self.dt, stream_ptr()),
+              "nint_unpack_halo")
+        return out
+
+    def _unpack_compact(self, l: int, src: int, B: int, g: NintGeom, et: bool = False, what: str = "nint_unpack_compact") -> torch.Tensor:
+        ly = self.layers[l]
+        out = torch.empty(B, ly.Ch, g.H, g.W, dtype=torch.float32, device=self.device)
+        check(self.lib.nint_unpack_compact(C.c_void_p(src), ptr(out), B, ly.Ch, ly.Chp, g.H, g.W, self.dt if et else NINT_F32,
+                                           stream_ptr()), what)
+        return out
+
+    def _write_state(self, hs, cs, dst, B: int, g: NintGeom, tag: str = ""):
+        """the (h, c) tensors of every layer -> the (h pointers, c pointers) of a state or of a workspace slot"""
+        for l in range(len(self.cfgs)):
+            self._pack_h(l, hs[l], dst[0][l], B, g, "pack h" + tag)
+            self._pack_compact(l, cs[l], dst[1][l], B, g, what="pack c" + tag)
 
     def _state_tensors(self, pairs, BHW):
         """validate a list of (h, c) tensor pairs against the engine (and a (B, H, W), when given): ValueError naming what differs"""
@@ -377,7 +408,7 @@ class SeqEngine:
         """ONE nint_state_copy launch: (h pointers, c pointers) of every layer, destination <- source through `lanes`"""
         L = len(self.cfgs)
         arr = lambda v: (C.c_void_p * L)(*v)
-        chp = (C.c_int32 * L)(*[cfg.padded(self.kc)[2] for cfg in self.cfgs])
+        chp = (C.c_int32 * L)(*[ly.Chp for ly in self.layers])
         ln = None if lanes is None else (C.c_int32 * B_dst)(*[int(v) for v in lanes])
         check(self.lib.nint_state_copy(arr(dst[0]), arr(dst[1]), arr(src[0]), arr(src[1]), chp, L, B_dst, B_src, ln, C.byref(g),
                                        self.dt, stream_ptr()), "nint_state_copy")
@@ -418,20 +449,11 @@ class SeqEngine:
         (all layers, all steps)."""
         B, T, Cc, H, W = x.shape
         assert (B, T, H, W) == (ws.B, ws.T, ws.H, ws.W) and Cc == self.cfgs[0].Cx
-        st = stream_ptr()
-        g = C.byref(ws.g)
         self.pack_input(ws, x)
         if h0 is not None:
-            for l, cfg in enumerate(self.cfgs):
-                Chp = cfg.padded(self.kc)[2]
-                hh = h0[l].detach().float().contiguous().view(B, 1, cfg.Ch, H, W)
-                check(self.lib.nint_pack_btchw(ptr(hh), C.c_void_p(ws.h_view(self, l, 0)), B, 1, cfg.Ch, Chp, g, self.dt, st),
-                      "pack h0")
-                cc = c0[l].detach().float().contiguous()
-                check(self.lib.nint_pack_compact(ptr(cc), C.c_void_p(ws.c_view(self, l, 0)), B, cfg.Ch, Chp, H, W, NINT_F32, st),
-                      "pack c0")
+            self._write_state(h0, c0, self._slot_ptrs(ws, 0), B, ws.g, "0")
         self._set_wave(ws)
-        check(self.lib.nint_seq_fwd(C.byref(ws.seq), st), "nint_seq_fwd")
+        check(self.lib.nint_seq_fwd(C.byref(ws.seq), stream_ptr()), "nint_seq_fwd")
 
     def _set_wave(self, ws: Workspace):
         """nint_seq.wave: independent launches as one grid (a forward wavefront step; in BPTT the dgrad launches of layers 0 and 1
@@ -475,21 +497,10 @@ class SeqEngine:
             check(self.lib.nint_pack_btchw(ptr(x), ptr(ws.xs), B, T, Cc, ws.Cxp0, g, self.dt, st), "nint_pack_btchw")
 
     def h_last(self, ws: Workspace, l: int, slot: Optional[int] = None) -> torch.Tensor:
-        cfg = self.cfgs[l]
-        Chp = cfg.padded(self.kc)[2]
-        slot = ws.T if slot is None else slot
-        out = torch.empty(ws.B, cfg.Ch, ws.H, ws.W, dtype=torch.float32, device=self.device)
-        check(self.lib.nint_unpack_halo(ptr(ws.h[l]), ptr(out), slot * ws.B, ws.B, cfg.Ch, Chp, C.byref(ws.g), self.dt,
-                                        stream_ptr()), "nint_unpack_halo")
-        return out
+        return self._unpack_h(l, ws.h[l].data_ptr(), ws.B, ws.g, (ws.T if slot is None else slot) * ws.B)
 
     def c_last(self, ws: Workspace, l: int) -> torch.Tensor:
-        cfg = self.cfgs[l]
-        Chp = cfg.padded(self.kc)[2]
-        out = torch.empty(ws.B, cfg.Ch, ws.H, ws.W, dtype=torch.float32, device=self.device)
-        check(self.lib.nint_unpack_compact(C.c_void_p(ws.c_view(self, l, ws.T)), ptr(out), ws.B, cfg.Ch, Chp, ws.H, ws.W,
-                                           NINT_F32, stream_ptr()), "nint_unpack_compact")
-        return out
+        return self._unpack_compact(l, ws.c_view(self, l, ws.T), ws.B, ws.g)
 
     def head_forward(self, ws: Workspace, w: torch.Tensor, b: Optional[torch.Tensor], slot: Optional[int] = None):
         """model.py:274: 1x1 conv on the last layer's hidden state of time step ``slot-1``."""
@@ -504,7 +515,7 @@ class SeqEngine:
         cfg = self.cfgs[-1]
         w2 = w.detach().float().contiguous()
         b2 = None if b is None else b.detach().float().contiguous()
-        return cfg.Ch, cfg.padded(self.kc)[2], w.shape[0], w2, b2
+        return cfg.Ch, self.layers[-1].Chp, w.shape[0], w2, b2
 
     @staticmethod
     def _beyond_fused_head(Chp: int, O: int) -> bool:
@@ -529,12 +540,9 @@ class SeqEngine:
         """Head backward over every step (nint_head_bwd_seq): dseq (B, T*O, H, W) and / or dpred (B, O, H, W), the cotangent
         of pred = head(h_{T-1}), which joins step T-1.  Writes the per-step dL/dh into ws.dh_seq_slab() (unless `write_dh` is
         False) for backward(..., seq_grads=True); returns (dw_head, db_head).  ``accumulate``: as in head_backward."""
-        self._check_accumulate(accumulate, dw_out, db_out)
-        Ch, Chp, O, w2, _ = self._head_args(w, None)
+        Ch, Chp, O, w2, dw, db = self._head_bwd_args(w, dw_out, db_out, accumulate)
         ds = None if dseq is None else dseq.detach().float().contiguous()
         dp = None if dpred is None else dpred.detach().float().contiguous()
-        dw = dw_out if dw_out is not None else torch.empty(O, Ch, dtype=torch.float32, device=self.device)
-        db = db_out if db_out is not None else torch.empty(O, dtype=torch.float32, device=self.device)
         check(self.lib.nint_head_bwd_seq_acc(ptr(ws.h[-1]), ws.B, ws.T, Ch, Chp, O, ptr(w2), ptr(ds), ptr(dp),
                                              ptr(ws.dh_seq_slab(self)) if write_dh else None, ptr(dw), ptr(db), int(accumulate),
                                              C.byref(ws.g), self.dt, ptr(self.wg_partial), self.wg_partial.numel() * 4, stream_ptr()),
@@ -554,18 +562,24 @@ class SeqEngine:
             name, extra = stem, ()
         return getattr(self.lib, name), name, extra
 
+    def _head_loss(self, seq: bool, ws, w, b, y, dpred, scratch, stats, halo, Hc, Wc, weights, spec) -> bool:
+        """the body of head_loss_fused (the last step's B images, dL/dh into ws.dh[-1]) and head_loss_seq_fused (every
+        step's, dL/dh into ws.dh_seq_slab())"""
+        Ch, Chp, O, w2, b2 = self._head_args(w, b)
+        if self._beyond_fused_head(Chp, O):
+            return False
+        fn, name, extra = self._loss_entry(seq, weights, spec)
+        n0, N, dh = (ws.B, ws.T, ws.dh_seq_slab(self)) if seq else (ws.T * ws.B, ws.B, ws.dh[-1])
+        check(fn(ptr(ws.h[-1]), n0, N, Ch, Chp, O, ptr(w2), ptr(b2), ptr(y), *extra, ptr(dpred), ptr(dh),
+                 ptr(scratch), ptr(stats), C.byref(ws.g), halo[0], halo[1], Hc, Wc, self.dt, stream_ptr()), name)
+        return True
+
     def head_loss_seq_fused(self, ws: Workspace, w: torch.Tensor, b: Optional[torch.Tensor], y: torch.Tensor, dpred: torch.Tensor,
                             scratch: torch.Tensor, stats: torch.Tensor, halo, Hc: int, Wc: int, weights=None, spec=None) -> bool:
         """head_loss_fused over every step (nint_head_loss_seq_fused): y (B, T, O, Hc, Wc); dpred (T*B, O, H, W) in image
         order t*B + b; the per-step dL/dh goes into ws.dh_seq_slab().  False beyond the fused kernel's limit.  `weights`,
         `spec` (its weights run over t*O + o): as in head_loss_fused."""
-        Ch, Chp, O, w2, b2 = self._head_args(w, b)
-        if self._beyond_fused_head(Chp, O):
-            return False
-        fn, name, extra = self._loss_entry(True, weights, spec)
-        check(fn(ptr(ws.h[-1]), ws.B, ws.T, Ch, Chp, O, ptr(w2), ptr(b2), ptr(y), *extra, ptr(dpred), ptr(ws.dh_seq_slab(self)),
-                 ptr(scratch), ptr(stats), C.byref(ws.g), halo[0], halo[1], Hc, Wc, self.dt, stream_ptr()), name)
-        return True
+        return self._head_loss(True, ws, w, b, y, dpred, scratch, stats, halo, Hc, Wc, weights, spec)
 
     def head_loss_fused(self, ws: Workspace, w: torch.Tensor, b: Optional[torch.Tensor], y: torch.Tensor, dpred: torch.Tensor,
                         scratch: torch.Tensor, stats: torch.Tensor, halo, Hc: int, Wc: int, weights=None, spec=None) -> bool:
@@ -575,13 +589,7 @@ class SeqEngine:
         `weights` = (wgt, wsum): the f32 (Hc, Wc) device map and its f64 sum (nint_head_loss_fused_weighted); None: unweighted.
         `spec`: a _lib.NintLossSpec (loss.LossSpec.on) -- the configurable loss, nint_head_loss_fused_spec with or without the
         map, `scratch` then of NINT_LOSS_SPEC_SCRATCH_FLOATS floats; None: the calls above."""
-        Ch, Chp, O, w2, b2 = self._head_args(w, b)
-        if self._beyond_fused_head(Chp, O):
-            return False
-        fn, name, extra = self._loss_entry(False, weights, spec)
-        check(fn(ptr(ws.h[-1]), ws.T * ws.B, ws.B, Ch, Chp, O, ptr(w2), ptr(b2), ptr(y), *extra, ptr(dpred), ptr(ws.dh[-1]),
-                 ptr(scratch), ptr(stats), C.byref(ws.g), halo[0], halo[1], Hc, Wc, self.dt, stream_ptr()), name)
-        return True
+        return self._head_loss(False, ws, w, b, y, dpred, scratch, stats, halo, Hc, Wc, weights, spec)
 
     def head_skill(self, ws: Workspace, w: torch.Tensor, b: Optional[torch.Tensor], y: torch.Tensor, slots, acc,
                    pred_out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -618,6 +626,15 @@ class SeqEngine:
         if accumulate and any(o is None for o in outs):
             raise ValueError("accumulate=True adds to the destinations: pass them (dW_out / db_out, dw_out / db_out)")
 
+    def _head_bwd_args(self, w: torch.Tensor, dw_out, db_out, accumulate: bool):
+        """what both head backward entries start with: the accumulate check, the head's geometry and f32 weights, and the
+        gradient destinations (the caller's, or new ones)"""
+        self._check_accumulate(accumulate, dw_out, db_out)
+        Ch, Chp, O, w2, _ = self._head_args(w, None)
+        dw = dw_out if dw_out is not None else torch.empty(O, Ch, dtype=torch.float32, device=self.device)
+        db = db_out if db_out is not None else torch.empty(O, dtype=torch.float32, device=self.device)
+        return Ch, Chp, O, w2, dw, db
+
     def head_backward(self, ws: Workspace, w: torch.Tensor, dpred: torch.Tensor, dw_out=None, db_out=None, write_dh: bool = True,
                       images: Optional[Tuple[int, int]] = None, accumulate: bool = False):
         """Writes dL/dh_{T-1} of the last layer into ws.dh[-1] (unless `write_dh` is False: the fused head/loss pass
@@ -625,13 +642,10 @@ class SeqEngine:
         belongs to: default the last step's B; (B, T*B) reduces every step's (the fused sequence pass, write_dh False).
         ``accumulate`` (nint_head_bwd_acc): dw_out / db_out (required then) receive old + gradient, one f32 add per element,
         instead of being overwritten -- the micro-batches of one optimizer step sum into the bucket."""
-        self._check_accumulate(accumulate, dw_out, db_out)
+        Ch, Chp, O, w2, dw, db = self._head_bwd_args(w, dw_out, db_out, accumulate)
         n0, N = images if images is not None else (ws.T * ws.B, ws.B)
         assert images is None or not write_dh
-        Ch, Chp, O, w2, _ = self._head_args(w, None)
         dp = dpred.detach().float().contiguous()
-        dw = dw_out if dw_out is not None else torch.empty(O, Ch, dtype=torch.float32, device=self.device)
-        db = db_out if db_out is not None else torch.empty(O, dtype=torch.float32, device=self.device)
         check(self.lib.nint_head_bwd_acc(ptr(ws.h[-1]), n0, N, Ch, Chp, O, ptr(w2), ptr(dp),
                                          ptr(ws.dh[-1]) if write_dh else None,
                                          ptr(dw), ptr(db), int(accumulate), C.byref(ws.g), self.dt, ptr(self.wg_partial),
@@ -708,43 +722,27 @@ class SeqEngine:
 
     def state_grads(self, ws: Workspace, l: int):
         """dL/dh_init, dL/dc_init of layer l after backward (has_init_state workspaces)."""
-        cfg = self.cfgs[l]
-        Chp = cfg.padded(self.kc)[2]
-        dh = torch.empty(ws.B, cfg.Ch, ws.H, ws.W, dtype=torch.float32, device=self.device)
-        dc = torch.empty_like(dh)
-        st = stream_ptr()
-        check(self.lib.nint_unpack_compact(ptr(ws.dh[l]), ptr(dh), ws.B, cfg.Ch, Chp, ws.H, ws.W, self.dt, st), "unpack dh")
-        check(self.lib.nint_unpack_compact(ptr(ws.dc[l]), ptr(dc), ws.B, cfg.Ch, Chp, ws.H, ws.W, NINT_F32, st), "unpack dc")
-        return dh, dc
+        return (self._unpack_compact(l, ws.dh[l].data_ptr(), ws.B, ws.g, True, "unpack dh"),
+                self._unpack_compact(l, ws.dc[l].data_ptr(), ws.B, ws.g, False, "unpack dc"))
 
     def set_state_grads(self, ws: Workspace, l: int, dh: Optional[torch.Tensor], dc: Optional[torch.Tensor]):
-        cfg = self.cfgs[l]
-        Chp = cfg.padded(self.kc)[2]
-        st = stream_ptr()
-        for src, dst, dt in ((dh, ws.dh[l], self.dt), (dc, ws.dc[l], NINT_F32)):
-            if src is None:
-                dst.zero_()
-            else:
-                s2 = src.detach().float().contiguous()
-                check(self.lib.nint_pack_compact(ptr(s2), ptr(dst), ws.B, cfg.Ch, Chp, ws.H, ws.W, dt, st), "pack dstate")
+        self.set_dstate(ws, l, "h", dh)
+        self.set_dstate(ws, l, "c", dc)
 
-    def set_dstate(self, ws: Workspace, l: int, which: str, t: torch.Tensor):
-        """one cotangent of a returned final state, (B, Ch, H, W), into ws.dh[l] (which = "h") or ws.dc[l] ("c")"""
-        cfg = self.cfgs[l]
-        Chp = cfg.padded(self.kc)[2]
-        dst, dt = (ws.dh[l], self.dt) if which == "h" else (ws.dc[l], NINT_F32)
-        s2 = t.detach().float().contiguous()
-        check(self.lib.nint_pack_compact(ptr(s2), ptr(dst), ws.B, cfg.Ch, Chp, ws.H, ws.W, dt, stream_ptr()), "pack dstate")
+    def set_dstate(self, ws: Workspace, l: int, which: str, t: Optional[torch.Tensor]):
+        """one cotangent of a returned final state, (B, Ch, H, W), into ws.dh[l] (which = "h") or ws.dc[l] ("c"); None: a
+        zero fill of that slab"""
+        dst = ws.dh[l] if which == "h" else ws.dc[l]
+        if t is None:
+            dst.zero_()
+        else:
+            self._pack_compact(l, t, dst.data_ptr(), ws.B, ws.g, which == "h", "pack dstate")
 
     def add_top_dh(self, ws: Workspace, dh: torch.Tensor, seq_grads: bool):
         """the top layer's returned h_{T-1} has a cotangent of its own: added to the head's dL/dh_{T-1} where BPTT reads it --
         ws.dh[-1], or the last block of ws.dh_seq_slab() with per-step head gradients (nint_pack_compact_add)"""
-        cfg = self.cfgs[-1]
-        Chp = cfg.padded(self.kc)[2]
-        s2 = dh.detach().float().contiguous()
         if seq_grads:
-            dst = C.c_void_p(ws.dh_seq_slab(self).data_ptr() + (ws.T - 1) * ws.B * ws.H * ws.W * Chp * self.es)
+            dst = ws.dh_seq_slab(self).data_ptr() + (ws.T - 1) * ws.B * ws.H * ws.W * self.layers[-1].Chp * self.es
         else:
-            dst = ptr(ws.dh[-1])
-        check(self.lib.nint_pack_compact_add(ptr(s2), dst, ws.B, cfg.Ch, Chp, ws.H, ws.W, self.dt, stream_ptr()),
-              "nint_pack_compact_add")
+            dst = ws.dh[-1].data_ptr()
+        self._pack_compact(len(self.cfgs) - 1, dh, dst, ws.B, ws.g, True, "nint_pack_compact_add", add=True)

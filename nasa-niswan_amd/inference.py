@@ -13,7 +13,7 @@ from typing import Callable, Optional, Sequence, Tuple, Union
 import numpy as np
 import torch
 
-NINT_SKILL_PIX, NINT_SKILL_SAMPLE = 5, 8      # include/nint.h
+from ._lib import NINT_SKILL_PIX, NINT_SKILL_SAMPLE
 
 
 @torch.no_grad()
@@ -276,11 +276,10 @@ def evaluate_skill(net, dataset, batch_size: int = 8, halo: Tuple[int, int] = (5
     for s in range(0, len(idx), batch_size):
         X, y = dataset.slab_batch(idx[s:s + batch_size])
         B, T, _, H, W = X.shape
-        ws = eng.acquire(B, T, H, W, False, False)
-        eng.pack_weights([c.conv.weight for c in net.layers], [c.conv.bias for c in net.layers])
-        eng.forward(ws, X)
-        acc.update(eng, ws, net.conv.weight, net.conv.bias, y, slots_all[s:s + B], pred_out=None if preds is None else preds[s:s + B])
-        eng.release(ws)
+        with eng.window(B, T, H, W, False, False) as ws:
+            net._pack_weights(eng)
+            eng.forward(ws, X)
+            acc.update(eng, ws, net.conv.weight, net.conv.bias, y, slots_all[s:s + B], pred_out=None if preds is None else preds[s:s + B])
     return (acc, preds) if return_predictions else acc
 
 
@@ -318,14 +317,13 @@ def predict_stream(net, dataset, lanes: int = 1, halo: Tuple[int, int] = (5, 5),
     for k in range(K):
         X, _ = dataset.slab_batch(sched[k])
         _, _, _, H, W = X.shape
-        ws = eng.acquire(B, T, H, W, False, state is not None)
-        eng.pack_weights([c.conv.weight for c in net.layers], [c.conv.bias for c in net.layers])
-        if state is not None:
-            eng.load_state(ws, state)
-        eng.forward(ws, X)
-        state = eng.save_state(ws, state)
-        seq = eng.head_forward_seq(ws, net.conv.weight, net.conv.bias)             # (B, T*O, H, W), channel t*O + o
-        eng.release(ws)
+        with eng.window(B, T, H, W, False, state is not None) as ws:
+            net._pack_weights(eng)
+            if state is not None:
+                eng.load_state(ws, state)
+            eng.forward(ws, X)
+            state = eng.save_state(ws, state)
+            seq = eng.head_forward_seq(ws, net.conv.weight, net.conv.bias)             # (B, T*O, H, W), channel t*O + o
         out[:, k * T:(k + 1) * T] = seq.view(B, T, O, H, W)[:, :, :, halo[0]:halo[0] + Hc, halo[1]:halo[1] + Wc]
         if skill is not None:
             t0s = [int(dataset.first[int(i)]) for i in sched[k]]

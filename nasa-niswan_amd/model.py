@@ -83,74 +83,43 @@ def _own_workspace(ctx, who: str):
 
 
 # ------------------------------------------------------------------------------ autograd glue
-class _ConvLSTMFn(torch.autograd.Function):
-    """x, head_w, head_b, W_0, b_0, ..., W_{L-1}, b_{L-1} -> pred [, seq]"""
-
-    @staticmethod
-    def forward(ctx, module, grad_mode, x, head_w, head_b, *wb):
-        eng: SeqEngine = module._engine(x.device)
-        B, T, _, H, W = x.shape
-        # grad mode is always off inside Function.forward, so the caller samples it
-        train = grad_mode and any(ctx.needs_input_grad)
-        ws = eng.acquire(B, T, H, W, train, False)
-        eng.pack_weights(wb[0::2], wb[1::2])
-        eng.forward(ws, x)
-        pred = eng.head_forward(ws, head_w, head_b)
-        outs = [pred]
-        if module.return_sequence:
-            outs.append(eng.head_forward_seq(ws, head_w, head_b))       # every step in one launch
-        ctx.return_sequence = module.return_sequence
-        if train:
-            if module.return_sequence:
-                ctx.set_materialize_grads(False)                        # an unused output's cotangent stays None: passed as NULL
-            ctx.eng, ctx.ws, ctx.rel, ctx.gen = eng, ws, _Releaser(ws), ws.gen
-            # references, not copies: the dgrad reads the engine's packed image of these weights (eng.Wd), which every forward
-            # rewrites -- torch's version check on the saved tensors is what refuses a backward after an in-place update
-            ctx.save_for_backward(head_w, *wb[0::2])
-            ctx.x_needs_grad = ctx.needs_input_grad[2]
-            ctx.nwb = len(wb)
-        else:
-            eng.release(ws)
-        return tuple(outs) if len(outs) > 1 else pred
-
-    @staticmethod
-    @_once_differentiable
-    def backward(ctx, dpred, dseq=None):
-        eng, ws = _own_workspace(ctx, "ConvLSTM")
-        head_w = ctx.saved_tensors[0]           # before the first launch: raises if a weight was modified in place
-        L = len(eng.cfgs)
-        if ctx.return_sequence:
-            if dpred is None and dseq is None:
-                ctx.rel.release()
-                return (None,) * (5 + ctx.nwb)
-            # per-step head gradients (pred's cotangent joins step T-1), then BPTT with one block of them per time step
-            dw_head, db_head = eng.head_backward_seq(ws, head_w, dseq, dpred)
-            dWs, dbs, dx = eng.backward(ws, ctx.x_needs_grad, zero_state_grads=range(L), seq_grads=True)
-        else:
-            dw_head, db_head = eng.head_backward(ws, head_w, dpred)
-            dWs, dbs, dx = eng.backward(ws, ctx.x_needs_grad, zero_state_grads=range(L))
-        ctx.rel.release()
-        grads = []
-        for l in range(L):
-            grads += [dWs[l], dbs[l]]
-        return (None, None, dx, dw_head, db_head, *grads)
+def _keep_or_release(ctx, eng, ws, train: bool, *weights):
+    """The end of every Function.forward.  A graph that will run backward keeps its workspace until then (or until it dies)
+    and saves REFERENCES to the weights, not copies: the dgrad reads the engine's packed image of them (eng.Wd), which every
+    forward rewrites -- torch's version check on the saved tensors is what refuses a backward after an in-place update.
+    Anything else returns the workspace to the pool now."""
+    if train:
+        ctx.eng, ctx.ws, ctx.rel, ctx.gen = eng, ws, _Releaser(ws), ws.gen
+        ctx.save_for_backward(*weights)
+    else:
+        eng.release(ws)
 
 
-class _StateOpts:
-    """the non-tensor arguments of _ConvLSTMStateFn: the device state that comes in (or None), what goes out, and the box the
-    outgoing device state is handed back in (a Function's outputs are tensors)"""
+def _interleave(a, b):
+    """[a_0, b_0, a_1, b_1, ...]: the order the Functions take the layers' (W, b) and (h, c) in, and return their gradients in"""
+    return [v for pair in zip(a, b) for v in pair]
 
-    def __init__(self, state_in, return_state):
+
+class _CallOpts:
+    """the non-tensor arguments of _ConvLSTMFn: the device state that comes in (or None), what goes out, the box the outgoing
+    device state is handed back in (a Function's outputs are tensors), and the default route's head-backward rule"""
+
+    def __init__(self, state_in=None, return_state=False, seq_always=False):
         self.state_in, self.return_state, self.state_out = state_in, return_state, None
+        # The default call (no state in, none out) of a return_sequence module ALWAYS takes the per-step head backward
+        # (head_backward_seq + BPTT with seq_grads), also when only `pred` has a cotangent; a call with state does so only
+        # when `seq` has one.  Two launch plans and two summation orders of dw_head: kept apart, as they have always been.
+        self.seq_always = seq_always
 
 
-class _ConvLSTMStateFn(torch.autograd.Function):
+class _ConvLSTMFn(torch.autograd.Function):
     """x, head_w, head_b, W_0, b_0, ..., W_{L-1}, b_{L-1} [, h0_0, c0_0, ..., h0_{L-1}, c0_{L-1}]
     -> pred [, seq] [, hT_0, cT_0, ..., hT_{L-1}, cT_{L-1}]
 
-    The stateful twin of _ConvLSTMFn (which stays as it is: the default call launches what it always did).  Tensor states
-    are inputs and outputs of the Function: dL/dh0, dL/dc0 come from the BPTT's own d/dh_init, d/dc_init, and the cotangents
-    of the returned states enter BPTT as the incoming dh[l] / dc[l].  A ConvLSTMState in or out is not seen by autograd."""
+    The one Function of ConvLSTM: the default call is the case with no state in and none out, which launches what it
+    always did.  Tensor states are inputs and outputs of the Function: dL/dh0, dL/dc0 come from the BPTT's own d/dh_init,
+    d/dc_init, and the cotangents of the returned states enter BPTT as the incoming dh[l] / dc[l].  A ConvLSTMState in or
+    out is not seen by autograd."""
 
     @staticmethod
     def forward(ctx, module, grad_mode, opts, x, head_w, head_b, *rest):
@@ -158,35 +127,29 @@ class _ConvLSTMStateFn(torch.autograd.Function):
         L = len(eng.cfgs)
         wb, st = rest[:2 * L], rest[2 * L:]
         B, T, _, H, W = x.shape
+        # grad mode is always off inside Function.forward, so the caller samples it
         train = grad_mode and any(ctx.needs_input_grad)
         has_init = opts.state_in is not None or len(st) > 0
         ws = eng.acquire(B, T, H, W, train, has_init)
         eng.pack_weights(wb[0::2], wb[1::2])
         if opts.state_in is not None:
             eng.load_state(ws, opts.state_in)
-            eng.forward(ws, x)
-        elif st:
-            eng.forward(ws, x, list(st[0::2]), list(st[1::2]))
-        else:
-            eng.forward(ws, x)
+        h0, c0 = (list(st[0::2]), list(st[1::2])) if st else (None, None)
+        eng.forward(ws, x, h0, c0)
         outs = [eng.head_forward(ws, head_w, head_b)]
         if module.return_sequence:
-            outs.append(eng.head_forward_seq(ws, head_w, head_b))
+            outs.append(eng.head_forward_seq(ws, head_w, head_b))       # every step in one launch
         if opts.return_state == "device":
             opts.state_out = eng.save_state(ws)
         elif opts.return_state:
             for l in range(L):
                 outs += [eng.h_last(ws, l), eng.c_last(ws, l)]
-        ctx.return_sequence = module.return_sequence
-        if train:
-            ctx.set_materialize_grads(False)                            # a missing cotangent stays None: that state keeps its zero_dstate bit
-            ctx.eng, ctx.ws, ctx.rel, ctx.gen = eng, ws, _Releaser(ws), ws.gen
-            ctx.save_for_backward(head_w, *wb[0::2])                    # (references: see _ConvLSTMFn)
-            ctx.x_needs_grad = ctx.needs_input_grad[3]
-            ctx.nwb, ctx.nst = len(wb), len(st)
-            ctx.st_needs_grad = any(ctx.needs_input_grad[6 + len(wb):])
-        else:
-            eng.release(ws)
+        ctx.set_materialize_grads(False)        # a missing cotangent stays None: passed as NULL, or that state keeps its zero_dstate bit
+        _keep_or_release(ctx, eng, ws, train, head_w, *wb[0::2])
+        ctx.return_sequence, ctx.seq_always = module.return_sequence, opts.seq_always
+        ctx.x_needs_grad = ctx.needs_input_grad[3]
+        ctx.nwb, ctx.nst = len(wb), len(st)
+        ctx.st_needs_grad = any(ctx.needs_input_grad[6 + len(wb):])
         return tuple(outs) if len(outs) > 1 else outs[0]
 
     @staticmethod
@@ -204,7 +167,7 @@ class _ConvLSTMStateFn(torch.autograd.Function):
             ctx.rel.release()
             return (None,) * nin
         # the top layer: the head's dL/dh_{T-1} (per step with a sequence cotangent) plus the cotangent of the returned h_{T-1}
-        seq_grads = dseq is not None
+        seq_grads = dseq is not None or ctx.seq_always          # (the default route's rule: _CallOpts)
         dh_top = dst[2 * (L - 1)]
         dw_head = db_head = None
         if seq_grads:
@@ -212,10 +175,7 @@ class _ConvLSTMStateFn(torch.autograd.Function):
         elif dpred is not None:
             dw_head, db_head = eng.head_backward(ws, head_w, dpred)
         if dw_head is None:                     # no head gradient at all: the state's cotangent alone (zeros if there is none)
-            if dh_top is None:
-                ws.dh[-1].zero_()
-            else:
-                eng.set_dstate(ws, L - 1, "h", dh_top)
+            eng.set_dstate(ws, L - 1, "h", dh_top)
         elif dh_top is not None:
             eng.add_top_dh(ws, dh_top, seq_grads)
         mask = 0
@@ -236,10 +196,7 @@ class _ConvLSTMStateFn(torch.autograd.Function):
             for l in range(L):
                 dstate += list(eng.state_grads(ws, l)) if ctx.st_needs_grad else [None, None]
         ctx.rel.release()
-        grads = []
-        for l in range(L):
-            grads += [dWs[l], dbs[l]]
-        return (None, None, None, dx, dw_head, db_head, *grads, *dstate)
+        return (None, None, None, dx, dw_head, db_head, *_interleave(dWs, dbs), *dstate)
 
 
 class _CellFn(torch.autograd.Function):
@@ -254,13 +211,9 @@ class _CellFn(torch.autograd.Function):
         eng.pack_weights([W], [b])
         eng.forward(ws, x.unsqueeze(1), [h], [c])
         h1, c1 = eng.h_last(ws, 0), eng.c_last(ws, 0)
-        if train:
-            ctx.eng, ctx.ws, ctx.rel, ctx.gen = eng, ws, _Releaser(ws), ws.gen
-            ctx.save_for_backward(W)            # (a reference: see _ConvLSTMFn)
-            ctx.x_needs_grad = ctx.needs_input_grad[2]
-            ctx.has_bias = b is not None
-        else:
-            eng.release(ws)
+        _keep_or_release(ctx, eng, ws, train, W)
+        ctx.x_needs_grad = ctx.needs_input_grad[2]
+        ctx.has_bias = b is not None
         return h1, c1
 
     @staticmethod
@@ -274,7 +227,8 @@ class _CellFn(torch.autograd.Function):
         ctx.rel.release()
         if dx is not None:
             dx = dx[:, 0]
-        return None, None, dx, dh0, dc0, dWs[0], (dbs[0] if ctx.has_bias else None)
+        dW, db = _interleave(dWs, dbs)
+        return None, None, dx, dh0, dc0, dW, (db if ctx.has_bias else None)
 
 
 class _EngineOwner:
@@ -347,6 +301,11 @@ class ConvLSTM(_EngineOwner, nn.Module):
             self._engines[key] = SeqEngine(cfgs, self.compute_dtype, device)
         return self._engines[key]
 
+    def _pack_weights(self, eng: SeqEngine):
+        """the layers' current weights and biases into the engine's packed images (one launch): what the trainer and the
+        inference loops, which drive the engine themselves, do before a forward pass"""
+        eng.pack_weights([c.conv.weight for c in self.layers], [c.conv.bias for c in self.layers])
+
     def forward(self, x, state=None, *, return_state=False):
         """x: (batch_size, sequence_length, channels, height, width)  (model.py:254).
 
@@ -363,23 +322,23 @@ class ConvLSTM(_EngineOwner, nn.Module):
         wb = []
         for cell in self.layers:
             wb += [cell.conv.weight, cell.conv.bias]
-        if state is None and not return_state:
-            return _ConvLSTMFn.apply(self, torch.is_grad_enabled(), x, self.conv.weight, self.conv.bias, *wb)
-        if return_state not in (False, True, "device"):
-            raise ValueError(f"return_state must be False, True or 'device', got {return_state!r}")
-        if len(x.shape) != 5:
-            raise ValueError(f"ConvLSTM: x must be (B, T, C, H, W), got {tuple(x.shape)}")
-        eng = self._engine(x.device)
-        B, _, _, H, W = x.shape
         st = []
-        if isinstance(state, ConvLSTMState):            # every mismatch is a ValueError here, before anything is launched
-            eng.check_state(state, B, H, W)
-        elif state is not None:
-            hs, cs = eng._state_tensors(state, (B, H, W))
-            for h, c in zip(hs, cs):
-                st += [h, c]
-        opts = _StateOpts(state if isinstance(state, ConvLSTMState) else None, return_state)
-        out = _ConvLSTMStateFn.apply(self, torch.is_grad_enabled(), opts, x, self.conv.weight, self.conv.bias, *wb, *st)
+        if state is None and not return_state:          # the default call: nothing to validate, and its own head-backward rule
+            opts = _CallOpts(seq_always=self.return_sequence)
+        else:
+            if return_state not in (False, True, "device"):
+                raise ValueError(f"return_state must be False, True or 'device', got {return_state!r}")
+            if len(x.shape) != 5:
+                raise ValueError(f"ConvLSTM: x must be (B, T, C, H, W), got {tuple(x.shape)}")
+            eng = self._engine(x.device)
+            B, _, _, H, W = x.shape
+            if isinstance(state, ConvLSTMState):        # every mismatch is a ValueError here, before anything is launched
+                eng.check_state(state, B, H, W)
+            elif state is not None:
+                hs, cs = eng._state_tensors(state, (B, H, W))
+                st = _interleave(hs, cs)
+            opts = _CallOpts(state if isinstance(state, ConvLSTMState) else None, return_state)
+        out = _ConvLSTMFn.apply(self, torch.is_grad_enabled(), opts, x, self.conv.weight, self.conv.bias, *wb, *st)
         out = list(out) if isinstance(out, tuple) else [out]
         n0 = 2 if self.return_sequence else 1
         res = out[:n0]

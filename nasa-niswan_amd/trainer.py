@@ -169,46 +169,62 @@ class FusedTrainer:
         crop_loss_launch(pred, yv, dpred, self.scratch, self.stats, N, O, H, W, self.halo[0], self.halo[1], Hc, Wc, wts, spec)
 
     # ------------------------------------------------------------------ pieces
+    def _call_facts(self, X, y):
+        """What step() and forward_loss() know of a call before anything is acquired: the loss weights and spec (validated
+        against the target's crop, the model's outputs and the window), the shapes, and the target as f32 (asserted to hold
+        one value per output, cropped cell [and step])."""
+        B, T, _, H, W = X.shape
+        O, Hc, Wc = self.model.conv.weight.shape[0], y.shape[-2], y.shape[-1]
+        wts = self._loss_weights(Hc, Wc)
+        spec = self._loss_spec(O, T)
+        yv = y.detach().float().contiguous()
+        sq = self.sequence_loss
+        assert yv.numel() == B * (T if sq else 1) * O * Hc * Wc, "target must be (B,T,[O,]Hc,Wc)" if sq else "target must be (B,[O,]Hc,Wc)"
+        return wts, spec, B, T, H, W, O, Hc, Wc, yv
+
+    def _head_loss_unfused(self, eng, ws, yv, dpred, B, T, O, H, W, Hc, Wc, wts, spec):
+        """The three-launch path's first two: the head's output -- of every step with sequence_loss, (B, T*O, H, W), which
+        the loss kernel's own index math takes as O' = T*O outputs -- and the stand-alone loss launch on it."""
+        m = self.model
+        if self.sequence_loss:
+            out, O = eng.head_forward_seq(ws, m.conv.weight, m.conv.bias), T * O
+        else:
+            out = eng.head_forward(ws, m.conv.weight, m.conv.bias)
+        self._loss(out, yv, dpred, B, O, H, W, Hc, Wc, wts, spec)
+        return out
+
     def forward_loss(self, X: torch.Tensor, y: torch.Tensor, train: bool = True):
         m = self.model
         eng = m._engine(self.device)
-        B, T, _, H, W = X.shape
-        wts = self._loss_weights(y.shape[-2], y.shape[-1])      # (validates the map's shape before anything is acquired)
-        spec = self._loss_spec(m.conv.weight.shape[0], T)       # (and the spec's lengths)
-        ws = eng.acquire(B, T, H, W, train, False)
-        wb_w = [c.conv.weight for c in m.layers]
-        wb_b = [c.conv.bias for c in m.layers]
-        eng.pack_weights(wb_w, wb_b)
+        wts, spec, B, T, H, W, O, Hc, Wc, yv = self._call_facts(X, y)
+        ws = eng.acquire(B, T, H, W, train, False)          # (handed to the caller still acquired: no `with eng.window`)
+        m._pack_weights(eng)
         eng.forward(ws, X)
-        O = m.conv.weight.shape[0]
-        Hc, Wc = y.shape[-2], y.shape[-1]
-        yv = y.detach().float().contiguous()
-        if self.sequence_loss:
-            # the (B, T*O, H, W) sequence against (B, T, O, Hc, Wc) targets: the loss kernel's own index math with O' = T*O
-            assert yv.numel() == B * T * O * Hc * Wc, "target must be (B,T,[O,]Hc,Wc)"
-            pred = eng.head_forward_seq(ws, m.conv.weight, m.conv.bias)
-            O = T * O
-        else:
-            assert yv.numel() == B * O * Hc * Wc, "target must be (B,[O,]Hc,Wc)"
-            pred = eng.head_forward(ws, m.conv.weight, m.conv.bias)
         dpred = None
         if train:
-            if self._dpred is None or self._dpred.shape != pred.shape:
-                self._dpred = torch.empty_like(pred)
+            shape = (B, T * O if self.sequence_loss else O, H, W)
+            if self._dpred is None or self._dpred.shape != shape:
+                self._dpred = torch.empty(shape, dtype=torch.float32, device=self.device)
             dpred = self._dpred
-        self._loss(pred, yv, dpred, B, O, H, W, Hc, Wc, wts, spec)
+        pred = self._head_loss_unfused(eng, ws, yv, dpred, B, T, O, H, W, Hc, Wc, wts, spec)
         return eng, ws, pred, dpred
 
     def reset_state(self):
         """stateful: the next step() starts every lane from the zero state (a new epoch, a new record)"""
         self.state = None
 
+    @staticmethod
+    def _state_for(st, eng, B, H, W):
+        """`st` if it is a state of this engine and (B, H, W), else a new zero state"""
+        if st is None or st.eng is not eng or (st.B, st.H, st.W) != (B, H, W):
+            return eng.new_state(B, H, W)
+        return st
+
     def _carried_state(self, eng, B, H, W, reset):
         """the trainer's state for this step: zeros on first use or when the batch shape changed, lanes in `reset` zeroed"""
-        st = self.state
-        if st is None or st.eng is not eng or (st.B, st.H, st.W) != (B, H, W) or reset is True:
-            st = self.state = eng.new_state(B, H, W)
-        elif reset is not None and reset is not False:
+        old = None if reset is True else self.state
+        st = self.state = self._state_for(old, eng, B, H, W)
+        if st is old and reset is not None and reset is not False:
             st.reset(reset)
         return st
 
@@ -244,15 +260,13 @@ class FusedTrainer:
             if fused:
                 eng.head_backward(ws, m.conv.weight, dpred, write_dh=False, images=(B, T * B), **hk)
             else:
-                seq = eng.head_forward_seq(ws, m.conv.weight, m.conv.bias)
-                self._loss(seq, yv, dpred, B, T * O, H, W, Hc, Wc, wts, spec)
+                self._head_loss_unfused(eng, ws, yv, dpred, B, T, O, H, W, Hc, Wc, wts, spec)
                 eng.head_backward_seq(ws, m.conv.weight, dpred.view(B, T * O, H, W), None, **hk)
         else:
             # head forward + crop + loss + dpred + dL/dh in one pass; the prediction itself is never materialised
             fused = eng.head_loss_fused(ws, m.conv.weight, m.conv.bias, yv, dpred, self.scratch, self.stats, self.halo, Hc, Wc, wts, **sk)
             if not fused:
-                pred = eng.head_forward(ws, m.conv.weight, m.conv.bias)
-                self._loss(pred, yv, dpred, B, O, H, W, Hc, Wc, wts, spec)
+                self._head_loss_unfused(eng, ws, yv, dpred, B, T, O, H, W, Hc, Wc, wts, spec)
             eng.head_backward(ws, m.conv.weight, dpred, write_dh=not fused, **hk)
 
     def step(self, X: torch.Tensor, y: torch.Tensor, reset=None) -> torch.Tensor:
@@ -262,10 +276,8 @@ class FusedTrainer:
         With ``accumulate_steps = k`` the optimizer steps on every k-th call, on the mean gradient of the k calls."""
         m = self.model
         eng = m._engine(self.device)
-        B, T, _, H, W = X.shape
         L = m.num_layers
-        wts = self._loss_weights(y.shape[-2], y.shape[-1])      # (validates the map's shape before anything is acquired)
-        spec = self._loss_spec(m.conv.weight.shape[0], T)       # (and the spec's lengths)
+        wts, spec, B, T, H, W, O, Hc, Wc, yv = self._call_facts(X, y)
         if reset is not None and not self.stateful:
             raise ValueError("step(reset=...) needs FusedTrainer(stateful=True)")
         k = self.accumulate_steps
@@ -275,58 +287,53 @@ class FusedTrainer:
         else:
             plan = None
         carried = self._carried_state(eng, B, H, W, reset) if self.stateful else None
-        O = m.conv.weight.shape[0]
-        Hc, Wc = y.shape[-2], y.shape[-1]
-        yv = y.detach().float().contiguous()
         sq = self.sequence_loss
-        assert yv.numel() == B * (T if sq else 1) * O * Hc * Wc, "target must be (B,T,[O,]Hc,Wc)" if sq else "target must be (B,[O,]Hc,Wc)"
         mark = self._mark
         if plan is not None:
             mark()
-            eng.pack_weights([c.conv.weight for c in m.layers], [c.conv.bias for c in m.layers])
+            m._pack_weights(eng)
             self._segments(eng, X, yv, plan, carried, acc, wts, spec)
             return self._finish(last)
-        ws = eng.acquire(B, T, H, W, True, self.stateful)
-        pb, pm = self._probe
-        ws.seq.probe = pb.data_ptr() if pb is not None else None
-        ws.seq.probe_mask, ws.seq.probe_slots = pm, (pb.numel() // 2 if pb is not None else 0)
-        mark()
-        eng.pack_weights([c.conv.weight for c in m.layers], [c.conv.bias for c in m.layers])
-        if carried is not None:
-            eng.load_state(ws, carried)          # carried state -> slot 0
-        eng.forward(ws, X)
-        if carried is not None:
-            eng.save_state(ws, carried)          # slot T -> carried state; BPTT below stops at the chunk start
-            self._drop_nonfinite_lanes(carried)
-        mark()
-        self._head_pass(eng, ws, yv, B, T, O, H, W, Hc, Wc, wts, acc, spec)
-        mark()
-        bk = dict(zero_state_grads=range(L), dW_out=self._dW, db_out=self._db, seq_grads=sq, accumulate=acc)
-        if last and self.distributed and self.overlap_allreduce and L > 1 and pb is None:
-            n0 = self.flat.offsets[2]              # layers.0.conv.weight + .bias lead the bucket (module parameter order)
-            eng.backward(ws, False, parts=1, **bk)
-            work = self.dist.all_reduce(self.flat.grad[n0:], op=self.dist.ReduceOp.SUM, group=self.pg, async_op=True)
-            eng.backward(ws, False, parts=2, **bk)
+        pending, n0 = None, 0
+        with eng.window(B, T, H, W, True, self.stateful) as ws:
+            pb, pm = self._probe
+            ws.seq.probe = pb.data_ptr() if pb is not None else None
+            ws.seq.probe_mask, ws.seq.probe_slots = pm, (pb.numel() // 2 if pb is not None else 0)
             mark()
-            eng.release(ws)
-            self.dist.all_reduce(self.flat.grad[:n0], op=self.dist.ReduceOp.SUM, group=self.pg)
-            work.wait()                            # (stream-level for RCCL: the step stays asynchronous to the host)
-            self._micro = 0
-            self.optimizer.step(grad_scale=1.0 / (k * self.world))
+            m._pack_weights(eng)
+            if carried is not None:
+                eng.load_state(ws, carried)          # carried state -> slot 0
+            eng.forward(ws, X)
+            if carried is not None:
+                eng.save_state(ws, carried)          # slot T -> carried state; BPTT below stops at the chunk start
+                self._drop_nonfinite_lanes(carried)
             mark()
-            return self.scratch[0]
-        eng.backward(ws, False, **bk)
-        mark()
-        eng.release(ws)
-        return self._finish(last)
+            self._head_pass(eng, ws, yv, B, T, O, H, W, Hc, Wc, wts, acc, spec)
+            mark()
+            bk = dict(zero_state_grads=range(L), dW_out=self._dW, db_out=self._db, seq_grads=sq, accumulate=acc)
+            if last and self.distributed and self.overlap_allreduce and L > 1 and pb is None:
+                # the bucket without layer 0's slice is exchanged under layer 0's weight gradient; _finish exchanges the slice
+                n0 = self.flat.offsets[2]              # layers.0.conv.weight + .bias lead the bucket (module parameter order)
+                eng.backward(ws, False, parts=1, **bk)
+                pending = self.dist.all_reduce(self.flat.grad[n0:], op=self.dist.ReduceOp.SUM, group=self.pg, async_op=True)
+                eng.backward(ws, False, parts=2, **bk)
+            else:
+                eng.backward(ws, False, **bk)
+            mark()
+        return self._finish(last, pending, n0)
 
-    def _finish(self, last: bool) -> torch.Tensor:
-        """the end of a call: on the last one of a group the ONE all-reduce of the bucket and the optimizer step"""
+    def _finish(self, last: bool, pending=None, n0: int = 0) -> torch.Tensor:
+        """The end of every call: on the last one of a group the all-reduce of the bucket -- ONE, or with `pending` (the
+        asynchronous exchange of the bucket from element `n0` on, started under layer 0's weight gradient) that of the first
+        n0 elements -- and the optimizer step."""
         if not last:
             self._micro += 1
             return self.scratch[0]
         self._micro = 0
-        if self.distributed:
+        if pending is not None:
+            self.dist.all_reduce(self.flat.grad[:n0], op=self.dist.ReduceOp.SUM, group=self.pg)
+            pending.wait()                         # (stream-level for RCCL: the step stays asynchronous to the host)
+        elif self.distributed:
             self.dist.all_reduce(self.flat.grad, op=self.dist.ReduceOp.SUM, group=self.pg)   # RCCL over xGMI
         self.optimizer.step(grad_scale=1.0 / (self.accumulate_steps * self.world))
         self._mark()
@@ -349,39 +356,32 @@ class FusedTrainer:
         B, T, _, H, W = X.shape
         n, S = len(plan), plan[0][1]
         seg = (lambda t0: X.segment(t0, S)) if hasattr(X, "segment") else (lambda t0: X[:, t0:t0 + S])
-        if carried is not None:
-            start = carried
-        else:
-            z = self._zero
-            if z is None or z.eng is not eng or (z.B, z.H, z.W) != (B, H, W):
-                z = self._zero = eng.new_state(B, H, W)
-            start = z
-        states = [start]
-        wf = eng.acquire(B, S, H, W, False, True)
-        for t0, _ in plan[:-1]:
-            eng.load_state(wf, states[-1])
-            eng.zero_start(wf, carried is None and t0 == 0)
-            eng.forward(wf, seg(t0))
-            states.append(eng.save_state(wf))        # slot S -> a new state: the start of the next segment
-        eng.release(wf)
-        ws = eng.acquire(B, S, H, W, True, True)
-        eng.load_state(ws, states[-1])
-        eng.forward(ws, seg(plan[-1][0]))
-        if carried is not None:
-            self.state = eng.save_state(ws)          # (a new object: the chunk's start state above stays what it was)
-            self._drop_nonfinite_lanes(self.state)
-        mark()
-        O = m.conv.weight.shape[0]
-        self._head_pass(eng, ws, yv, B, S, O, H, W, yv.shape[-2], yv.shape[-1], wts, acc, spec)
-        mark()
-        eng.backward(ws, False, zero_state_grads=range(L), dW_out=self._dW, db_out=self._db, accumulate=acc)
-        for j in range(n - 2, -1, -1):
-            eng.load_state(ws, states[j])
-            eng.zero_start(ws, carried is None and j == 0)
-            eng.forward(ws, seg(plan[j][0]))
-            eng.backward(ws, False, zero_state_grads=(), dW_out=self._dW, db_out=self._db, accumulate=True)
-        mark()
-        eng.release(ws)
+        if carried is None:
+            self._zero = self._state_for(self._zero, eng, B, H, W)
+        states = [carried if carried is not None else self._zero]
+        with eng.window(B, S, H, W, False, True) as wf:
+            for t0, _ in plan[:-1]:
+                eng.load_state(wf, states[-1])
+                eng.zero_start(wf, carried is None and t0 == 0)
+                eng.forward(wf, seg(t0))
+                states.append(eng.save_state(wf))        # slot S -> a new state: the start of the next segment
+        with eng.window(B, S, H, W, True, True) as ws:
+            eng.load_state(ws, states[-1])
+            eng.forward(ws, seg(plan[-1][0]))
+            if carried is not None:
+                self.state = eng.save_state(ws)          # (a new object: the chunk's start state above stays what it was)
+                self._drop_nonfinite_lanes(self.state)
+            mark()
+            O = m.conv.weight.shape[0]
+            self._head_pass(eng, ws, yv, B, S, O, H, W, yv.shape[-2], yv.shape[-1], wts, acc, spec)
+            mark()
+            eng.backward(ws, False, zero_state_grads=range(L), dW_out=self._dW, db_out=self._db, accumulate=acc)
+            for j in range(n - 2, -1, -1):
+                eng.load_state(ws, states[j])
+                eng.zero_start(ws, carried is None and j == 0)
+                eng.forward(ws, seg(plan[j][0]))
+                eng.backward(ws, False, zero_state_grads=(), dW_out=self._dW, db_out=self._db, accumulate=True)
+            mark()
 
     def _mark(self):
         """bench.py --phase-events: one HIP event per phase boundary of a step (nothing is recorded unless asked for)"""

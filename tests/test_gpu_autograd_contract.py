@@ -1,10 +1,10 @@
 """The autograd contract of ConvLSTM / ConvLSTMCell on the device: whatever autograd allows on
 the reference's nn.Modules gives the right gradient here or is refused loudly.  The kernels are audited launch by launch
-elsewhere; this file is about the Python glue that decides which memory they read: the two autograd Functions of
-model.py, the engine's workspace pool and the releaser -- on the paths a training script takes and the one-forward /
-one-dense-backward tests do not: user-written recurrences over the cell, several live graphs, work between forward and
-backward, retained graphs, in-place weight updates, double backward, strided / expanded / f64 / bf16 inputs and cotangents,
-frozen parameters, dropped graphs, a side stream, a deepcopy twin.
+elsewhere; this file is about the Python glue that decides which memory they read: the autograd Functions of model.py
+(one for ConvLSTM, with or without state, one for the cell), the engine's workspace pool and the releaser -- on the
+paths a training script takes and the one-forward / one-dense-backward tests do not: user-written recurrences over the
+cell, several live graphs, work between forward and backward, retained graphs, in-place weight updates, double backward,
+strided / expanded / f64 / bf16 inputs and cotangents, frozen parameters, dropped graphs, a side stream, a deepcopy twin.
 
 Numbers are compared with the CPU oracle run in f64 under the bounds of tests/test_gpu_shapes.py::check; two routes that
 must launch the same kernels on the same bytes are compared bit for bit (torch.equal), one of each pair also against the
@@ -577,6 +577,18 @@ def test_cotangent_forms(pkg, shape, dtype):
     twin = run_std(net_s, X, lambda p, q: (q * DS.to(q)).sum())
     check(twin, oracle((base, "seq", "odd"), shape, X, lambda p, q: q[:, 1::2].sum(), seq=True), dtype)
     same(run_std(net_s, X, lambda p, q: q[:, 1::2].sum()), twin)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_default_route_of_a_sequence_module_always_takes_the_per_step_head_backward(pkg, dtype):
+    """net(x) of a return_sequence module with a loss on pred alone runs head_backward_seq and BPTT with per-step head
+    gradients, as it does when seq has a cotangent too (model._CallOpts.seq_always) -- not the one-step head backward a call
+    with state takes then, whose dw_head is summed in another order: the same loss plus (seq * 0).sum(), a zero cotangent
+    for seq, gives the same bits."""
+    net = make_net(pkg, "plain", dtype, seq=True)
+    X, R, _ = batch("plain", 12)
+    alone = run_std(net, X, lambda p, q: dense(R)(p))
+    same(run_std(net, X, lambda p, q: dense(R)(p) + (q * 0).sum()), alone)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
