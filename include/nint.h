@@ -91,6 +91,23 @@ typedef struct nint_seq {
   int32_t zero_dstate;      /* backward: bit 2l = dc[l] is all-zero at entry, bit 2l+1 = dh[l] is all-zero at entry -- the first
                              * BPTT step then neither reads nor needs them zero-filled (reference: zero state grads) */
   nint_geom g;
+  /* nint_seq_bwd: the first layer whose parameters are trained (fine-tuning: the layers below are frozen).
+   *   0       every layer (the pass as it has always been: same launches, same bits)
+   *   f > 0   dW / db are produced for layers f .. L-1 only, and BPTT stops above layer f-1: no pointwise backward, dgrad or
+   *           weight-gradient launch for a layer below f, and layer f's dgrad computes no x columns (as layer 0's under
+   *           need_dx = 0).  Exact, not an approximation: d/dh of a layer below f feeds only the parameters and initial
+   *           states of layers < f and the input.  The pass IS the backward pass of the stack of layers f .. L-1 whose input
+   *           slab is h[f-1] from image B on (h^{f-1}_t = slab t+1) with need_dx = 0: zero_dstate and an explicit fuse_bwd
+   *           mask shifted down by f layers, dh_seq on the top layer, the `wave` merges of that stack ("the bottom layer" of
+   *           the wave modes is layer f), wg_partial sized for layers >= f.  For l < f none of gates[l], dG[l], dh[l], dc[l],
+   *           dW[l], db[l] is read: all may be NULL (and a forward pass with gates[l] == NULL writes no stash for l).
+   *           nint_debug_seq_plan and the probe tags carry the real layer index.
+   *   L       valid: nothing is planned (the head alone is trained).
+   * NINT_E_ARG before any launch: a value outside [0, L]; f > 0 with need_dx (d/dx passes through every layer) or with
+   * bwd_parts != 0 (the two-piece exchange is defined around layer 0's slice).  nint_seq_fwd does not read the field.
+   * (The field takes the four bytes that were padding between g and the 8-byte aligned layer[]: no offset of the structure
+   * moves and its size stays, so a caller that zero-fills the structure, as every caller must, gets 0.) */
+  int32_t train_from;
   nint_layer layer[NINT_MAX_LAYERS];
   const void* xs;                      /* ET halo slab [T*B][Hh][Wh][Cxp0]: packed input sequence */
   void* h[NINT_MAX_LAYERS];            /* ET halo slab [(T+1)*B][Hh][Wh][Chp]: h[0]=initial, h[t+1]=h_t */
@@ -558,6 +575,32 @@ enum { NINT_OPT_APPLIED = 0, NINT_OPT_SKIPPED = 1, NINT_OPT_CLIPPED = 2, NINT_OP
 int nint_adam_flat_guarded(float* p, const float* g, float* m, float* v, size_t n, double lr, double beta1, double beta2,
                            double eps, float grad_scale, double max_norm, int skip_nonfinite, double* state,
                            double* scratch, size_t scratch_bytes, void* stream);
+
+/* Fine-tuning: torch.optim.AdamW (decoupled weight decay) over GROUPS of the flat buffer, each with its own learning rate
+ * and decay, in ONE launch of the Adam body.  groups: a HOST table of ngroups ranges [begin, end) of element indices, sorted
+ * and non-empty, that tile ONE contiguous range [groups[0].begin, groups[ngroups-1].end) without a gap (group k+1 begins
+ * where group k ends); it travels to the kernel by value.  Elements outside that range are FROZEN: p, g, m and v are
+ * neither read nor written there.  Per element of group k, in torch's AdamW single-tensor order:
+ *     p = p * (float)(1 - lr_k * weight_decay_k)       one f32 multiply, the multiplier formed in f64 and rounded once
+ *     then the element update of nint_adam_flat as it stands, with step_size = (float)(lr_k / bc1)
+ * With weight_decay_k == 0 the multiplier is 1.0f and the group's update is nint_adam_flat(p + begin, ..., end - begin, lr_k)
+ * bit for bit.  NINT_E_ARG before any launch: a NULL p / g / m / v / groups, ngroups outside [1, NINT_MAX_OPT_GROUPS], an
+ * empty or unsorted group, a gap or an overlap between neighbours, an lr or weight_decay that is negative or not finite,
+ * step < 1.
+ * nint_adam_flat_groups_guarded: nint_adam_flat_guarded's guard in front of it.  The norm partials and the control kernel run
+ * over the range only -- S is nint_grad_norm_flat(g + begin_0, end_last - begin_0) bit for bit, an inf outside the range
+ * is never seen -- and the control kernel writes each group's scalars into gstate (DEVICE, 2 * ngroups doubles, 8-byte
+ * aligned): gstate[2k] = step_size of group k, gstate[2k+1] = its decay multiplier, f32 values held in doubles like
+ * state[10..12].  state[0..13] keep their meaning; [11] is group 0's step size.  A skipped step stores nothing to p, m or
+ * v anywhere.  Checks: both entries' own, and gstate NULL (NINT_E_ARG) or not 8-byte aligned (NINT_E_ALIGN). */
+typedef struct nint_opt_group { uint64_t begin, end; double lr, weight_decay; } nint_opt_group;   /* host table */
+#define NINT_MAX_OPT_GROUPS (2 * NINT_MAX_LAYERS + 2)
+int nint_adam_flat_groups(float* p, const float* g, float* m, float* v, const nint_opt_group* groups /*host*/, int ngroups,
+                          double beta1, double beta2, double eps, int step, float grad_scale, void* stream);
+int nint_adam_flat_groups_guarded(float* p, const float* g, float* m, float* v, const nint_opt_group* groups /*host*/,
+                                  int ngroups, double beta1, double beta2, double eps, float grad_scale, double max_norm,
+                                  int skip_nonfinite, double* state, double* gstate, double* scratch, size_t scratch_bytes,
+                                  void* stream);
 
 /* ---- preproc (dataset.py:520-536, 61-98) --------------------------------------------------------- */
 /* Fuse on the channel axis, z-score with mean/std (C = sum lev floats, device), cyclic-lon + lat halo pad.

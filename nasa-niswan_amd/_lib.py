@@ -20,6 +20,7 @@ NINT_LOSS_STATS = 8
 NINT_SKILL_PIX, NINT_SKILL_SAMPLE, NINT_SKILL_MAX_N = 5, 8, 64
 NINT_GRAD_NORM_BLOCKS = 256
 NINT_OPT_STATE = 16
+NINT_MAX_OPT_GROUPS = 2 * NINT_MAX_LAYERS + 2
 # nint_adam_flat_guarded's state (include/nint.h): counters, running norm figures, then this call's scalars
 (NINT_OPT_APPLIED, NINT_OPT_SKIPPED, NINT_OPT_CLIPPED, NINT_OPT_CALLS, NINT_OPT_SUM_NORM, NINT_OPT_FINITE, NINT_OPT_MAX_NORM,
  NINT_OPT_S, NINT_OPT_NORM, NINT_OPT_COEF, NINT_OPT_SCALE, NINT_OPT_STEP_SIZE, NINT_OPT_SQRT_BC2, NINT_OPT_APPLY) = range(14)
@@ -40,7 +41,7 @@ class NintLayer(C.Structure):
 class NintSeq(C.Structure):
     _fields_ = [("dtype", C.c_int32), ("B", C.c_int32), ("T", C.c_int32), ("L", C.c_int32),
                 ("need_dx", C.c_int32), ("has_init_state", C.c_int32), ("n_cu", C.c_int32), ("zero_dstate", C.c_int32),
-                ("g", NintGeom), ("layer", NintLayer * NINT_MAX_LAYERS),
+                ("g", NintGeom), ("train_from", C.c_int32), ("layer", NintLayer * NINT_MAX_LAYERS),
                 ("xs", vp), ("h", vp * NINT_MAX_LAYERS), ("c", vp * NINT_MAX_LAYERS),
                 ("gates", vp * NINT_MAX_LAYERS), ("dG", vp * NINT_MAX_LAYERS), ("dh", vp * NINT_MAX_LAYERS),
                 ("dc", vp * NINT_MAX_LAYERS), ("dx", vp), ("dW", vp * NINT_MAX_LAYERS), ("db", vp * NINT_MAX_LAYERS),
@@ -55,6 +56,11 @@ class NintLaunchRec(C.Structure):
                                          "strip", "gx", "gy", "nt_begin")]
 
 
+class NintOptGroup(C.Structure):
+    """nint_opt_group: one range of the flat buffer with its learning rate and decoupled weight decay (nint_adam_flat_groups)"""
+    _fields_ = [("begin", C.c_uint64), ("end", C.c_uint64), ("lr", C.c_double), ("weight_decay", C.c_double)]
+
+
 class NintLossSpec(C.Structure):
     """nint_loss_spec: the configurable loss of the _spec entries (coefficients, Huber threshold, output weights)"""
     _fields_ = [("mse", C.c_double), ("l1", C.c_double), ("huber", C.c_double), ("delta", C.c_double), ("ow", vp),
@@ -64,6 +70,7 @@ class NintLossSpec(C.Structure):
 # every symbol include/nint.h declares: name -> (restype, argtypes)
 _I, _SZ, _F, _D = C.c_int, C.c_size_t, C.c_float, C.c_double
 _PG, _PL, _PS, _PLS = C.POINTER(NintGeom), C.POINTER(NintLayer), C.POINTER(NintSeq), C.POINTER(NintLossSpec)
+_POG = C.POINTER(NintOptGroup)
 SIGNATURES = {
     "nint_version": (_I, []),
     "nint_error_string": (C.c_char_p, [_I]),
@@ -117,6 +124,8 @@ SIGNATURES = {
     "nint_grad_norm_scratch_bytes": (_SZ, []),
     "nint_grad_norm_flat": (_I, [vp, _SZ, _F, vp, vp, _SZ, vp]),
     "nint_adam_flat_guarded": (_I, [vp, vp, vp, vp, _SZ, _D, _D, _D, _D, _F, _D, _I, vp, vp, _SZ, vp]),
+    "nint_adam_flat_groups": (_I, [vp, vp, vp, vp, _POG, _I, _D, _D, _D, _I, _F, vp]),
+    "nint_adam_flat_groups_guarded": (_I, [vp, vp, vp, vp, _POG, _I, _D, _D, _D, _F, _D, _I, vp, vp, vp, _SZ, vp]),
     "nint_preproc_fuse_pad": (_I, [C.POINTER(vp), C.POINTER(_I), _I, vp, vp, vp, _I, _I, _I, _I, _I, _I, vp]),
     "nint_preproc_fuse_pad_batch": (_I, [C.POINTER(vp), C.POINTER(_I), _I, vp, vp, C.POINTER(_I), _I, vp, _I, _I, _I, _I, _I, _I, vp]),
     "nint_preproc_fuse_pad_slab": (_I, [C.POINTER(vp), C.POINTER(_I), _I, vp, vp, C.POINTER(_I), _I, vp, _I, _I, _I, _I, _I, _PG, _I, _I, vp]),

@@ -135,13 +135,9 @@ __global__ __launch_bounds__(NINT_GRAD_NORM_BLOCKS) void grad_norm_final_kernel(
   }
 }
 
-// the control kernel of nint_adam_flat_guarded: folds the partials, takes the step's decisions, keeps the counters
-__global__ __launch_bounds__(NINT_GRAD_NORM_BLOCKS) void adam_guard_kernel(const double* __restrict__ partial, int nblocks,
-                                                                           float grad_scale, double max_norm, int skip_nonfinite,
-                                                                           double lr, double beta1, double beta2,
-                                                                           double* __restrict__ state) {
-  const double S = grad_norm_fold(partial, nblocks);
-  if (threadIdx.x != 0) return;
+// the decisions of a guarded step and its counters, by ONE thread: state[0..15] as nint.h lists them; returns bc1 of step applied + 1
+__device__ __forceinline__ double adam_guard_decide(double S, float grad_scale, double max_norm, int skip_nonfinite, double lr,
+                                                    double beta1, double beta2, double* __restrict__ state) {
   const double gs = (double)grad_scale;
   const double norm = gs * sqrt(S);
   const bool finite = isfinite(S);
@@ -172,6 +168,17 @@ __global__ __launch_bounds__(NINT_GRAD_NORM_BLOCKS) void adam_guard_kernel(const
   state[NINT_OPT_APPLY] = apply ? 1.0 : 0.0;
   state[14] = 0.0;
   state[15] = 0.0;
+  return bc1;
+}
+
+// the control kernel of nint_adam_flat_guarded: folds the partials, takes the step's decisions, keeps the counters
+__global__ __launch_bounds__(NINT_GRAD_NORM_BLOCKS) void adam_guard_kernel(const double* __restrict__ partial, int nblocks,
+                                                                           float grad_scale, double max_norm, int skip_nonfinite,
+                                                                           double lr, double beta1, double beta2,
+                                                                           double* __restrict__ state) {
+  const double S = grad_norm_fold(partial, nblocks);
+  if (threadIdx.x != 0) return;
+  adam_guard_decide(S, grad_scale, max_norm, skip_nonfinite, lr, beta1, beta2, state);
 }
 
 // adam_flat_kernel with its step scalars read from `state` (f32 values held in doubles: the casts are exact)
@@ -226,6 +233,117 @@ extern "C" int nint_adam_flat_guarded(float* p, const float* g, float* m, float*
   if (n == 0) return NINT_OK;
   hipLaunchKernelGGL(adam_flat_guarded_kernel, grid1d(n), dim3(256), 0, st, p, g, m, v, n, state, (float)(1.0 - beta1),
                      (float)beta2, (float)(1.0 - beta2), (float)eps);
+  NINT_LAUNCH_CHECK();
+  return NINT_OK;
+}
+
+// ------------------------------------------------------------------------------ grouped AdamW (fine-tuning)
+// Ranges of the flat buffer with a learning rate and a decoupled weight decay each (nint.h: nint_adam_flat_groups).  ONE launch:
+// blockIdx.y is the group, its workgroups grid-stride over the group's range; the table travels by value.  Elements outside the
+// groups' ranges are touched by no thread.
+struct AdamGroups { unsigned long long begin[NINT_MAX_OPT_GROUPS], end[NINT_MAX_OPT_GROUPS]; float step_size[NINT_MAX_OPT_GROUPS], decay[NINT_MAX_OPT_GROUPS]; };
+struct AdamGroupRates { double lr[NINT_MAX_OPT_GROUPS], wd[NINT_MAX_OPT_GROUPS]; int n; };
+
+// torch.optim.AdamW's single-tensor order: the decoupled decay (one f32 multiply; 1.0f without decay: p as it was), then Adam's update
+__device__ __forceinline__ void adamw_flat_update(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                  float* __restrict__ v, size_t i, float decay, float step_size, float w1, float b2,
+                                                  float w2, float eps, float sqrt_bc2, float grad_scale) {
+  p[i] = __fmul_rn(p[i], decay);
+  adam_flat_update(p, g, m, v, i, step_size, w1, b2, w2, eps, sqrt_bc2, grad_scale);
+}
+
+__global__ void adam_flat_groups_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                        float* __restrict__ v, AdamGroups t, float w1, float b2, float w2, float eps,
+                                        float sqrt_bc2, float grad_scale) {
+  const int k = blockIdx.y;
+  const size_t end = t.end[k];
+  const float step_size = t.step_size[k], decay = t.decay[k];
+  for (size_t i = t.begin[k] + blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < end; i += (size_t)gridDim.x * blockDim.x)
+    adamw_flat_update(p, g, m, v, i, decay, step_size, w1, b2, w2, eps, sqrt_bc2, grad_scale);
+}
+
+// nint_adam_flat_groups_guarded's control kernel: adam_guard_kernel's decisions (state[NINT_OPT_STEP_SIZE] from group 0's lr), then
+// every group's step size and decay multiplier into gstate
+__global__ __launch_bounds__(NINT_GRAD_NORM_BLOCKS) void adam_guard_groups_kernel(const double* __restrict__ partial, int nblocks,
+                                                                                  float grad_scale, double max_norm,
+                                                                                  int skip_nonfinite, AdamGroupRates r, double beta1,
+                                                                                  double beta2, double* __restrict__ state,
+                                                                                  double* __restrict__ gstate) {
+  const double S = grad_norm_fold(partial, nblocks);
+  if (threadIdx.x != 0) return;
+  const double bc1 = adam_guard_decide(S, grad_scale, max_norm, skip_nonfinite, r.lr[0], beta1, beta2, state);
+  for (int k = 0; k < r.n; ++k) {
+    gstate[2 * k] = (double)(float)(r.lr[k] / bc1);
+    gstate[2 * k + 1] = (double)(float)(1.0 - r.lr[k] * r.wd[k]);
+  }
+}
+
+__global__ void adam_flat_groups_guarded_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                float* __restrict__ v, AdamGroups t, const double* __restrict__ state,
+                                                const double* __restrict__ gstate, float w1, float b2, float w2, float eps) {
+  if (state[NINT_OPT_APPLY] == 0.0) return;                   // a skipped step: nothing is stored
+  const int k = blockIdx.y;
+  const size_t end = t.end[k];
+  const float step_size = (float)gstate[2 * k], decay = (float)gstate[2 * k + 1];
+  const float sqrt_bc2 = (float)state[NINT_OPT_SQRT_BC2], grad_scale = (float)state[NINT_OPT_SCALE];
+  for (size_t i = t.begin[k] + blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < end; i += (size_t)gridDim.x * blockDim.x)
+    adamw_flat_update(p, g, m, v, i, decay, step_size, w1, b2, w2, eps, sqrt_bc2, grad_scale);
+}
+
+// the table's checks (nint.h) and its device form; *longest = the longest group (the grid's x extent covers it)
+static int adam_groups_table(const nint_opt_group* groups, int ngroups, AdamGroups* t, AdamGroupRates* r, size_t* longest) {
+  if (!groups || ngroups < 1 || ngroups > NINT_MAX_OPT_GROUPS) return NINT_E_ARG;
+  *t = AdamGroups{}; *r = AdamGroupRates{}; *longest = 0;
+  for (int k = 0; k < ngroups; ++k) {
+    const nint_opt_group& q = groups[k];
+    if (q.end <= q.begin || (k > 0 && q.begin != groups[k - 1].end)) return NINT_E_ARG;        // empty, unsorted, a gap or an overlap
+    if (!(q.lr >= 0.0 && q.lr < HUGE_VAL) || !(q.weight_decay >= 0.0 && q.weight_decay < HUGE_VAL)) return NINT_E_ARG;   // negative, NaN or inf
+    t->begin[k] = q.begin; t->end[k] = q.end;
+    r->lr[k] = q.lr; r->wd[k] = q.weight_decay;
+    if (q.end - q.begin > *longest) *longest = (size_t)(q.end - q.begin);
+  }
+  r->n = ngroups;
+  return NINT_OK;
+}
+
+extern "C" int nint_adam_flat_groups(float* p, const float* g, float* m, float* v, const nint_opt_group* groups, int ngroups,
+                                     double beta1, double beta2, double eps, int step, float grad_scale, void* stream) {
+  if (!p || !g || !m || !v || step < 1) return NINT_E_ARG;
+  AdamGroups t; AdamGroupRates r; size_t longest;
+  const int rc = adam_groups_table(groups, ngroups, &t, &r, &longest);
+  if (rc != NINT_OK) return rc;
+  const double bc1 = 1.0 - pow(beta1, step);                  // (nint_adam_flat's host expressions)
+  const double bc2 = 1.0 - pow(beta2, step);
+  for (int k = 0; k < ngroups; ++k) {
+    t.step_size[k] = (float)(r.lr[k] / bc1);
+    t.decay[k] = (float)(1.0 - r.lr[k] * r.wd[k]);
+  }
+  hipLaunchKernelGGL(adam_flat_groups_kernel, dim3(grid1d(longest).x, ngroups), dim3(256), 0, (hipStream_t)stream, p, g, m, v, t,
+                     (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, (float)sqrt(bc2), grad_scale);
+  NINT_LAUNCH_CHECK();
+  return NINT_OK;
+}
+
+extern "C" int nint_adam_flat_groups_guarded(float* p, const float* g, float* m, float* v, const nint_opt_group* groups,
+                                             int ngroups, double beta1, double beta2, double eps, float grad_scale,
+                                             double max_norm, int skip_nonfinite, double* state, double* gstate, double* scratch,
+                                             size_t scratch_bytes, void* stream) {
+  if (!p || !g || !m || !v || !state || !gstate || !scratch || scratch_bytes < nint_grad_norm_scratch_bytes()) return NINT_E_ARG;
+  if (!(max_norm >= 0.0)) return NINT_E_ARG;                  // negative or NaN
+  AdamGroups t; AdamGroupRates r; size_t longest;
+  int rc = adam_groups_table(groups, ngroups, &t, &r, &longest);
+  if (rc != NINT_OK) return rc;
+  if (((((uintptr_t)state) | ((uintptr_t)gstate) | ((uintptr_t)scratch)) & 7) != 0) return NINT_E_ALIGN;
+  hipStream_t st = (hipStream_t)stream;
+  const size_t begin = (size_t)groups[0].begin, n = (size_t)groups[ngroups - 1].end - begin;
+  int nblocks;
+  rc = grad_norm_partials(g + begin, n, scratch, st, &nblocks);          // the norm of the trained range only
+  if (rc != NINT_OK) return rc;
+  hipLaunchKernelGGL(adam_guard_groups_kernel, dim3(1), dim3(NINT_GRAD_NORM_BLOCKS), 0, st, scratch, nblocks, grad_scale, max_norm,
+                     skip_nonfinite ? 1 : 0, r, beta1, beta2, state, gstate);
+  NINT_LAUNCH_CHECK();
+  hipLaunchKernelGGL(adam_flat_groups_guarded_kernel, dim3(grid1d(longest).x, ngroups), dim3(256), 0, st, p, g, m, v, t, state,
+                     gstate, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps);
   NINT_LAUNCH_CHECK();
   return NINT_OK;
 }

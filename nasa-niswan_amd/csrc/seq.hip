@@ -255,9 +255,11 @@ static int plan_fwd(const nint_seq* s, int n_cu, Steps& out) {
 static int bwd_check(const nint_seq* s) {
   const int rc = seq_check(s);
   if (rc != NINT_OK) return rc;
-  for (int l = 0; l < s->L; ++l)
+  const int f = s->train_from;         // (nint_seq.train_from: nothing of a layer below it is read)
+  if (f < 0 || f > s->L || (f > 0 && (s->need_dx || s->bwd_parts != 0))) return NINT_E_ARG;
+  for (int l = f; l < s->L; ++l)
     if (!s->gates[l] || !s->dG[l] || !s->dh[l] || !s->dc[l] || !s->dW[l] || !s->db[l]) return NINT_E_ARG;
-  if ((s->need_dx && !s->dx) || !s->wg_partial) return NINT_E_ARG;
+  if ((s->need_dx && !s->dx) || (f < s->L && !s->wg_partial)) return NINT_E_ARG;
   if (s->fuse_bwd < 0 || (s->fuse_bwd > 2 && !(s->fuse_bwd & 0x40000000)) || s->bwd_parts < 0 || s->bwd_parts > 2) return NINT_E_ARG;
   if (s->accumulate != 0 && s->accumulate != 1) return NINT_E_ARG;     // stored or added (nint.h); no other value is a mode
   if ((((uintptr_t)s->dh_seq) & 15) != 0) return NINT_E_ALIGN;
@@ -467,12 +469,47 @@ struct BwdPlanner {
   }
 };
 
+// nint_seq.train_from = f > 0: the backward pass of (s, f) IS the backward pass of the stack of layers f .. L-1, fed by h[f-1] from
+// image B on (h^{f-1}_t = slab t+1, as BwdPlanner::wgrads reads it), with no input gradient.  This is that stack as a nint_seq of its
+// own -- a shifted view of the caller's pointers -- which the one planner takes: its "bottom layer" (the wave merges, the x columns
+// nobody wants, the head of wg_partial) is layer f.
+static nint_seq sub_stack(const nint_seq* s, int f) {
+  nint_seq v = *s;
+  const int L = s->L - f;
+  v.train_from = 0; v.L = L; v.need_dx = 0; v.dx = nullptr;
+  v.zero_dstate = (int32_t)((uint32_t)s->zero_dstate >> (2 * f));
+  if (s->fuse_bwd & 0x40000000) {                // explicit masks: each of the three byte-wide fields moves down by f layers
+    const uint32_t m = (uint32_t)s->fuse_bwd;
+    v.fuse_bwd = (int32_t)(0x40000000u | ((m & 0xffu) >> f) | ((((m >> 8) & 0xffu) >> f) << 8) | ((((m >> 16) & 0xffu) >> f) << 16));
+  }
+  v.xs = (const char*)s->h[f - 1] + (size_t)s->B * s->g.Hh * s->g.Wh * s->layer[f].Cxp * esize(s->dtype);
+  for (int l = 0; l < NINT_MAX_LAYERS; ++l) {
+    const int q = l + f;
+    const bool in = l < L;
+    v.layer[l] = in ? s->layer[q] : nint_layer{};
+    v.h[l] = in ? s->h[q] : nullptr; v.c[l] = in ? s->c[q] : nullptr; v.gates[l] = in ? s->gates[q] : nullptr;
+    v.dG[l] = in ? s->dG[q] : nullptr; v.dh[l] = in ? s->dh[q] : nullptr; v.dc[l] = in ? s->dc[q] : nullptr;
+    v.dW[l] = in ? s->dW[q] : nullptr; v.db[l] = in ? s->db[q] : nullptr;
+  }
+  return v;
+}
+
 // check, plan (the CU count the launch-shape rules read is looked up once per pass), then the callers execute
 static int plan_pass(const nint_seq* s, bool bwd, Steps& steps) {
   const int rc = bwd ? bwd_check(s) : seq_check(s);
   if (rc != NINT_OK) return rc;
   const int n_cu = nint_internal_n_cu();
-  return bwd ? BwdPlanner(s, n_cu, steps).plan() : plan_fwd(s, n_cu, steps);
+  if (!bwd) return plan_fwd(s, n_cu, steps);
+  const int f = s->train_from;
+  if (f == 0) return BwdPlanner(s, n_cu, steps).plan();
+  if (f == s->L) return NINT_OK;                 // every layer frozen: nothing to plan
+  const nint_seq sub = sub_stack(s, f);          // (the plan keeps no pointer into it)
+  const int rc2 = BwdPlanner(&sub, n_cu, steps).plan();
+  for (SeqStep& st : steps) {                    // the records and probe tags carry the real layer index
+    for (int q = 0; q < st.n; ++q) st.prob[q].layer += f;
+    if (st.kind == STEP_CONV || st.kind == STEP_MULTI || st.kind == STEP_PW) st.tag_layer += f;
+  }
+  return rc2;
 }
 
 extern "C" int nint_seq_fwd(const nint_seq* s, void* stream) {

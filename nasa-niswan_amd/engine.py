@@ -58,9 +58,12 @@ class Workspace:
     """All slabs of one (B, T, H, W) problem.  Halo slabs are zero-initialised once; kernels only
     ever write their interior, so the zero padding of nn.Conv2d (model.py:207-211) is physical."""
 
-    def __init__(self, eng: "SeqEngine", B: int, T: int, H: int, W: int, train: bool, has_init: bool):
-        self.key = (B, T, H, W, train, has_init)
+    def __init__(self, eng: "SeqEngine", B: int, T: int, H: int, W: int, train: bool, has_init: bool, train_from: int = 0):
+        self.key = SeqEngine.pool_key(B, T, H, W, train, has_init, train_from)
         self.B, self.T, self.H, self.W, self.train = B, T, H, W, train
+        # fine-tuning (nint_seq.train_from): layers below it are frozen -- no gate stash (the forward pass then writes none), no
+        # dG, no dc and no dh; their slots hold None.  The top layer's dh stays whatever is frozen: the head pass writes it.
+        self.train_from = train_from
         self.in_use = False
         self.gen = 0            # bumped by every SeqEngine.acquire: an autograd graph stamps it and refuses a backward after a reuse
         dev, es = eng.device, eng.es
@@ -79,10 +82,12 @@ class Workspace:
             self.h.append(torch.zeros((T + 1) * B * halo_px * Chp * es, **u8))
             self.c.append(torch.zeros((T + 1) * B * comp_px * Chp, **f32))
             if train:
-                self.gates.append(torch.empty(T * B * comp_px * 4 * Ch16 * es, **u8))
-                self.dG.append(torch.zeros(T * B * halo_px * 4 * Ch16 * es, **u8))
-                self.dh.append(torch.zeros(B * comp_px * Chp * es, **u8))      # ET: transient gradient, read once per step
-                self.dc.append(torch.zeros(B * comp_px * Chp, **f32))
+                live = len(self.h) - 1 >= train_from
+                self.gates.append(torch.empty(T * B * comp_px * 4 * Ch16 * es, **u8) if live else None)
+                self.dG.append(torch.zeros(T * B * halo_px * 4 * Ch16 * es, **u8) if live else None)
+                self.dh.append(torch.zeros(B * comp_px * Chp * es, **u8)       # ET: transient gradient, read once per step
+                               if live or ly is eng.layers[-1] else None)
+                self.dc.append(torch.zeros(B * comp_px * Chp, **f32) if live else None)
         self.dx = None
         self._dh_seq = None
         self.Cxp0 = Cxp0
@@ -96,7 +101,7 @@ class Workspace:
         for l in range(len(eng.cfgs)):
             s.h[l] = self.h[l].data_ptr()
             s.c[l] = self.c[l].data_ptr()
-            if train:
+            if train and l >= train_from:
                 s.gates[l] = self.gates[l].data_ptr()
                 s.dG[l] = self.dG[l].data_ptr()
                 s.dh[l] = self.dh[l].data_ptr()
@@ -261,15 +266,18 @@ class SeqEngine:
         check(self.lib.nint_pack_weights_layers(wp, bp, lys, L, self.dt, stream_ptr()), "nint_pack_weights_layers")
 
     @staticmethod
-    def untrainable_layers(cfgs: Sequence[LayerCfg], dtype, n_cu: int = 256) -> List[str]:
+    def untrainable_layers(cfgs: Sequence[LayerCfg], dtype, n_cu: int = 256, train_from: int = 0) -> List[str]:
         """Layers whose weight gradient no kernel instantiation covers (`nint_wgrad_workspace_bytes` == 0):
-        kernel sizes other than 1, 3, 5, 7.  Pure host
+        kernel sizes other than 1, 3, 5, 7.  Only the layers from ``train_from`` on are asked about: a frozen layer needs no
+        weight gradient.  Pure host
         arithmetic -- callable without a GPU."""
         lib = _lib.load()
         dt = dtype_code(dtype)
         kc = lib.nint_kc(dt)
         bad = []
         for l, cfg in enumerate(cfgs):
+            if l < train_from:
+                continue
             ly = NintLayer()
             ly.Cx, ly.Ch, ly.k, ly.xfold = cfg.Cx, cfg.Ch, cfg.k, int(cfg.xfold)
             ly.Cxp, ly.Ch16, ly.Chp = cfg.padded(kc)
@@ -278,16 +286,24 @@ class SeqEngine:
         return bad
 
     # ------------------------------------------------------------------ workspaces
-    def acquire(self, B, T, H, W, train: bool, has_init: bool) -> Workspace:
-        if train and self.train_unsupported:
-            raise _lib.NintError("training is not supported for " + ", ".join(self.train_unsupported) + ": the weight-gradient "
+    def acquire(self, B, T, H, W, train: bool, has_init: bool, train_from: int = 0) -> Workspace:
+        """``train_from`` (training workspaces): the first layer that is trained; the layers below it get no stash and no
+        gradient slabs (Workspace), and a kernel size the weight-gradient kernel lacks is refused only from there on."""
+        train_from = int(train_from) if train else 0
+        if not 0 <= train_from <= len(self.cfgs):
+            raise ValueError(f"train_from must be in [0, {len(self.cfgs)}], got {train_from}")
+        bad = self.train_unsupported if train else []
+        if bad and train_from:
+            bad = self.untrainable_layers(self.cfgs, self.dt, self.n_cu, train_from)
+        if bad:
+            raise _lib.NintError("training is not supported for " + ", ".join(bad) + ": the weight-gradient "
                                  "kernel is instantiated for kernel sizes 1, 3, 5 and 7 only (the reference accepts any odd k, "
                                  "model.py:204); forward / inference (torch.no_grad()) work for every odd k")
-        key = (B, T, H, W, train, has_init)
+        key = self.pool_key(B, T, H, W, train, has_init, train_from)
         pool = self.pool.setdefault(key, [])
         ws = next((w for w in pool if not w.in_use), None)
         if ws is None:
-            ws = Workspace(self, B, T, H, W, train, has_init)
+            ws = Workspace(self, B, T, H, W, train, has_init, train_from)
             for l, ly in enumerate(self.layers):
                 ws.seq.layer[l] = ly
             pool.append(ws)
@@ -299,14 +315,20 @@ class SeqEngine:
         return ws
 
     @staticmethod
+    def pool_key(B, T, H, W, train: bool, has_init: bool, train_from: int = 0) -> tuple:
+        """the pool's key of a workspace: (B, T, H, W, train, has_init), with train_from behind it where layers are frozen
+        (a run that freezes nothing keeps the keys it has always had)"""
+        return (B, T, H, W, train, has_init) + ((train_from,) if train_from else ())
+
+    @staticmethod
     def release(ws: Workspace):
         ws.in_use = False
 
     @contextlib.contextmanager
-    def window(self, B, T, H, W, train: bool, has_init: bool):
+    def window(self, B, T, H, W, train: bool, has_init: bool, train_from: int = 0):
         """``with eng.window(...) as ws``: acquire, and the release whatever happens inside -- how a caller that does not
         hand the workspace to an autograd graph runs a window (pack_weights, [load_state,] forward, ... in the body)"""
-        ws = self.acquire(B, T, H, W, train, has_init)
+        ws = self.acquire(B, T, H, W, train, has_init, train_from)
         try:
             yield ws
         finally:
@@ -654,7 +676,7 @@ class SeqEngine:
 
     def backward(self, ws: Workspace, need_dx: bool, zero_state_grads: Sequence[int] = (),
                  dW_out: Optional[Sequence[torch.Tensor]] = None, db_out: Optional[Sequence[torch.Tensor]] = None, parts: int = 0,
-                 seq_grads: bool = False, zero_mask: Optional[int] = None, accumulate: bool = False):
+                 seq_grads: bool = False, zero_mask: Optional[int] = None, accumulate: bool = False, train_from: int = 0):
         """BPTT of model.py:253-271.  Precondition: ws.dh[l], ws.dc[l] hold dL/dh_{T-1}, dL/dc_{T-1}
         (layers listed in ``zero_state_grads`` start from zero state gradients instead).  Returns ([dW_l], [db_l], dx or None).
         ``dW_out`` / ``db_out``: f32 contiguous destinations (e.g. views of a flat gradient bucket).
@@ -666,12 +688,25 @@ class SeqEngine:
         ``accumulate`` (nint_seq.accumulate): every dW / db element this call produces is written as old + gradient (one f32
         add by the element's one writer, bitwise reproducible) into ``dW_out`` / ``db_out``, which are required then.  With
         ``zero_state_grads=()`` on a has_init workspace, ws.dh[l] / ws.dc[l] as the previous call left them are the entry
-        gradients: a window runs as segments, last to first, through ONE workspace and sums into one bucket (trainer.py)."""
+        gradients: a window runs as segments, last to first, through ONE workspace and sums into one bucket (trainer.py).
+        ``train_from`` (nint_seq.train_from): layers below it are frozen -- BPTT stops above them, their ``dW_out`` / ``db_out``
+        entries are not touched (they may be None) and their slots of the returned lists hold None.  The workspace must have
+        been acquired with a ``train_from`` no larger.  Not with ``need_dx`` or ``parts``; ``train_from == L``: no library call."""
         assert ws.train
+        L = len(self.cfgs)
+        train_from = int(train_from)
+        if not 0 <= train_from <= L:
+            raise ValueError(f"train_from must be in [0, {L}], got {train_from}")
+        if train_from > 0 and need_dx:
+            raise _lib.NintError("backward: need_dx with train_from > 0 is not supported (the input's gradient passes through every layer)")
+        if train_from > 0 and parts:
+            raise _lib.NintError("backward: parts with train_from > 0 is not supported (the two-piece exchange is defined around layer 0's slice)")
+        if train_from < ws.train_from:
+            raise _lib.NintError(f"backward: train_from = {train_from} on a workspace acquired with train_from = {ws.train_from}: "
+                                 f"layers {train_from} .. {ws.train_from - 1} have no stash")
         self._check_accumulate(accumulate, dW_out, db_out)
         # layers in ``zero_state_grads`` start BPTT from zero dL/dh, dL/dc: flagged, not filled (the first BPTT step
         # then neither reads dc nor accumulates into dh).  The top layer's dh always holds the head's gradient.
-        L = len(self.cfgs)
         mask = 0
         for l in zero_state_grads:
             mask |= 1 << (2 * l)
@@ -682,6 +717,11 @@ class SeqEngine:
         dWs, dbs = [], []
         s = ws.seq
         for l, cfg in enumerate(self.cfgs):
+            if l < train_from:
+                dWs.append(None)
+                dbs.append(None)
+                s.dW[l] = s.db[l] = None
+                continue
             if dW_out is not None:
                 dWs.append(dW_out[l])
                 dbs.append(db_out[l])
@@ -699,12 +739,15 @@ class SeqEngine:
         s.bwd_parts = int(parts)
         s.dh_seq = ws.dh_seq_slab(self).data_ptr() if seq_grads else None
         s.accumulate = int(bool(accumulate))
+        s.train_from = train_from
         try:
-            check(self.lib.nint_seq_bwd(C.byref(s), stream_ptr()), "nint_seq_bwd")
+            if train_from < L:
+                check(self.lib.nint_seq_bwd(C.byref(s), stream_ptr()), "nint_seq_bwd")
         finally:
             s.bwd_parts = 0
             s.dh_seq = None
             s.accumulate = 0
+            s.train_from = 0
         s.dx = None
         dx_out = None
         if need_dx:

@@ -100,6 +100,15 @@ def _interleave(a, b):
     return [v for pair in zip(a, b) for v in pair]
 
 
+def train_from_rule(x_needs: bool, layer_needs: Sequence[bool]) -> int:
+    """The first layer BPTT has to reach (nint_seq.train_from), from what needs a gradient: 0 if the input does (its gradient
+    passes through every layer); else the lowest layer l one of whose tensors -- W_l, b_l, or a tensor state h0_l / c0_l --
+    does (``layer_needs[l]``); L if none does (the head alone is trained).  Pure."""
+    if x_needs:
+        return 0
+    return next((l for l, need in enumerate(layer_needs) if need), len(layer_needs))
+
+
 class _CallOpts:
     """the non-tensor arguments of _ConvLSTMFn: the device state that comes in (or None), what goes out, the box the outgoing
     device state is handed back in (a Function's outputs are tensors), and the default route's head-backward rule"""
@@ -130,7 +139,11 @@ class _ConvLSTMFn(torch.autograd.Function):
         # grad mode is always off inside Function.forward, so the caller samples it
         train = grad_mode and any(ctx.needs_input_grad)
         has_init = opts.state_in is not None or len(st) > 0
-        ws = eng.acquire(B, T, H, W, train, has_init)
+        # requires_grad_(False) on the lower layers is fine-tuning: BPTT stops above them and they keep no stash
+        need = ctx.needs_input_grad
+        f = train_from_rule(need[3], [any(need[6 + 2 * l:8 + 2 * l]) or (len(st) > 0 and any(need[6 + 2 * L + 2 * l:8 + 2 * L + 2 * l]))
+                                      for l in range(L)]) if train else 0
+        ws = eng.acquire(B, T, H, W, train, has_init, f)
         eng.pack_weights(wb[0::2], wb[1::2])
         if opts.state_in is not None:
             eng.load_state(ws, opts.state_in)
@@ -150,6 +163,7 @@ class _ConvLSTMFn(torch.autograd.Function):
         ctx.x_needs_grad = ctx.needs_input_grad[3]
         ctx.nwb, ctx.nst = len(wb), len(st)
         ctx.st_needs_grad = any(ctx.needs_input_grad[6 + len(wb):])
+        ctx.train_from = f
         return tuple(outs) if len(outs) > 1 else outs[0]
 
     @staticmethod
@@ -178,8 +192,8 @@ class _ConvLSTMFn(torch.autograd.Function):
             eng.set_dstate(ws, L - 1, "h", dh_top)
         elif dh_top is not None:
             eng.add_top_dh(ws, dh_top, seq_grads)
-        mask = 0
-        for l in range(L):
+        mask, f = 0, ctx.train_from
+        for l in range(f, L):                   # (a frozen layer's returned state feeds nothing that wants a gradient)
             dh, dc = dst[2 * l], dst[2 * l + 1]
             if dc is None:
                 mask |= 1 << (2 * l)
@@ -190,11 +204,11 @@ class _ConvLSTMFn(torch.autograd.Function):
                     mask |= 1 << (2 * l + 1)
                 else:
                     eng.set_dstate(ws, l, "h", dh)
-        dWs, dbs, dx = eng.backward(ws, ctx.x_needs_grad, seq_grads=seq_grads, zero_mask=mask)
+        dWs, dbs, dx = eng.backward(ws, ctx.x_needs_grad, seq_grads=seq_grads, zero_mask=mask, train_from=f)
         dstate = []
         if ctx.nst:
             for l in range(L):
-                dstate += list(eng.state_grads(ws, l)) if ctx.st_needs_grad else [None, None]
+                dstate += list(eng.state_grads(ws, l)) if ctx.st_needs_grad and l >= f else [None, None]
         ctx.rel.release()
         return (None, None, None, dx, dw_head, db_head, *_interleave(dWs, dbs), *dstate)
 

@@ -117,7 +117,22 @@ def get_arguments(argv=None, MODEL='LSTM-00', SPECIES='bcb', LEARNING_RATE=1.0E-
     parser.add_argument("--spinup-steps", type=int, default=0, metavar="K",
                         help="with --sequence-loss: the first K steps of every window (spin-up from the zero state) carry no "
                              "loss; K < --sequence-length")
+    parser.add_argument("--freeze-layers", type=int, default=0, metavar="N",
+                        help="fine-tuning: the first N ConvLSTM layers keep their weights; the backward pass stops above them "
+                             "and pays nothing for them.  N = --num-layers trains the head alone")
+    parser.add_argument("--weight-decay", type=float, default=0.0, metavar="X",
+                        help="decoupled weight decay (torch.optim.AdamW) on the trained weights; biases get none")
+    parser.add_argument("--layer-lr-scale", nargs='+', type=float, default=None, metavar="S",
+                        help="one factor on --learning-rate per ConvLSTM layer, bottom first (smaller lower down); the head "
+                             "takes the last one, or one more of its own")
+    parser.add_argument("--reset-optimizer", action="store_true",
+                        help="with --use-checkpoint: load the weights of --restore-from only and start the optimizer afresh "
+                             "(the fine-tuning entry point; without it an optimizer state of other param groups is an error)")
     args = parser.parse_args(argv)
+    if not 0 <= args.freeze_layers <= args.num_layers:
+        parser.error(f"--freeze-layers must be in [0, --num-layers = {args.num_layers}]")
+    if args.layer_lr_scale is not None and len(args.layer_lr_scale) not in (args.num_layers, args.num_layers + 1):
+        parser.error(f"--layer-lr-scale takes {args.num_layers} factors (one per layer) or {args.num_layers + 1} (the head's last)")
     if args.spinup_steps < 0:
         parser.error("--spinup-steps must be >= 0")
     if args.spinup_steps > 0 and not args.sequence_loss:
@@ -208,7 +223,8 @@ def main(args):
     trainer = FusedTrainer(generator, lr=args.learning_rate, betas=tuple(args.betas), halo=halo,        # train.py:71
                            sequence_loss=args.sequence_loss, loss_weights=loss_weights,
                            max_grad_norm=args.clip_grad_norm, skip_nonfinite=args.skip_nonfinite_steps, stateful=args.stateful,
-                           bptt_segments=args.bptt_segments, accumulate_steps=args.accumulate_steps, loss=build_loss_spec(args))
+                           bptt_segments=args.bptt_segments, accumulate_steps=args.accumulate_steps, loss=build_loss_spec(args),
+                           freeze_layers=args.freeze_layers, weight_decay=args.weight_decay, layer_lr_scale=args.layer_lr_scale)
     if args.stateful:
         # one schedule of world * batch lanes, the same every epoch; each rank takes its own columns and carries its own state
         sched, dropped = stateful_schedule(len(train_dataset), args.sequence_length, world * args.batch_size)
@@ -222,7 +238,7 @@ def main(args):
                                           gamma=args.scheduler_config[1])                   # train.py:72
     if args.use_checkpoint:
         load_checkpoint(f'{args.restore_from}/generator.pth.tar', generator, optimizer, args.learning_rate,
-                        map_location=dev)                                                   # train.py:77-78
+                        map_location=dev, reset_optimizer=args.reset_optimizer)             # train.py:77-78
     logger = {'MSELoss': [], 'r2_score': [], 'r2_score_val': [], 'first_step_loss': None, 'train_samples_per_s': []}
     for epoch in range(1, args.num_epochs + 1):                                              # train.py:82
         generator.train()

@@ -20,6 +20,11 @@
                                                workspace: a forward sweep that keeps the state at every segment start, then
                                                per segment, last to first, recompute + nint_seq_bwd with accumulate = 1 -- the
                                                full-window gradient at 1/n of the resident slabs
+    [freeze_layers = f]                     -> fine-tuning: the first f ConvLSTM layers are frozen.  nint_seq.train_from = f: BPTT
+                                               stops above layer f-1, a frozen layer keeps no stash and no gradient slabs, the
+                                               exchange and the norm run over the trained tail of the bucket, and the optimizer
+                                               is AdamW over per-layer groups (nint_adam_flat_groups: ``weight_decay``,
+                                               ``layer_lr_scale``).  f = L trains the head alone: no BPTT
     [accumulate_steps = k]                  -> k micro-batches add into the bucket (accumulate = 1 from the second on); the
                                                all-reduce and ONE Adam launch with grad_scale = 1/(k world) on the k-th
 
@@ -54,7 +59,8 @@ class FusedTrainer:
                  halo: Tuple[int, int] = (5, 5), process_group=None, distributed: Optional[bool] = None,
                  overlap_allreduce: bool = False, sequence_loss: bool = False, loss_weights=None,
                  max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False, stateful: bool = False,
-                 bptt_segments: Optional[int] = None, accumulate_steps: int = 1, loss: Optional[LossSpec] = None):
+                 bptt_segments: Optional[int] = None, accumulate_steps: int = 1, loss: Optional[LossSpec] = None,
+                 freeze_layers: int = 0, weight_decay: float = 0.0, layer_lr_scale=None):
         dev = next(model.parameters()).device
         if dev.type != "cuda":
             raise _lib.NintError("FusedTrainer needs the model on the MI355X (cuda)")
@@ -70,6 +76,14 @@ class FusedTrainer:
                 raise ValueError("bptt_segments with overlap_allreduce is not supported: layer 0's slice of the bucket is final "
                                  "only after the first segment's backward, so there is nothing to overlap the exchange with")
         self.bptt_segments = bptt_segments
+        # Fine-tuning: the first `freeze_layers` ConvLSTM layers keep their weights (requires_grad False, in no optimizer group);
+        # every backward pass of the step starts BPTT's reach at that layer (nint_seq.train_from)
+        self.freeze_layers = int(freeze_layers)
+        if not 0 <= self.freeze_layers <= model.num_layers:
+            raise ValueError(f"freeze_layers must be in [0, {model.num_layers}], got {freeze_layers}")
+        if self.freeze_layers > 0 and overlap_allreduce:
+            raise ValueError("freeze_layers with overlap_allreduce is not supported: the two-piece exchange runs under layer 0's "
+                             "weight gradient, which a frozen layer 0 does not have")
         # Gradient accumulation: the optimizer steps once per `accumulate_steps` calls of step(), on the sum of their buckets
         # scaled by 1 / (accumulate_steps * world): the mean gradient of the group
         self.accumulate_steps = int(accumulate_steps)
@@ -84,7 +98,8 @@ class FusedTrainer:
         # steps on -- under data parallelism the all-reduced sum with grad_scale = 1/world, so every rank takes the same decision
         # from the same bits and nothing more is exchanged
         self.optimizer = FusedAdam(self.flat, lr=lr, betas=betas, eps=eps, max_grad_norm=max_grad_norm,
-                                   skip_nonfinite=skip_nonfinite)
+                                   skip_nonfinite=skip_nonfinite, weight_decay=weight_decay, freeze_layers=self.freeze_layers,
+                                   layer_lr_scale=layer_lr_scale)
         self.halo = tuple(halo)
         self.lib = _lib.load()
         # (the size the _spec entries ask for, five doubles per workgroup; the other entries use the first 8194 floats of it)
@@ -294,8 +309,8 @@ class FusedTrainer:
             m._pack_weights(eng)
             self._segments(eng, X, yv, plan, carried, acc, wts, spec)
             return self._finish(last)
-        pending, n0 = None, 0
-        with eng.window(B, T, H, W, True, self.stateful) as ws:
+        pending, n0, f = None, 0, self.freeze_layers
+        with eng.window(B, T, H, W, True, self.stateful, f) as ws:
             pb, pm = self._probe
             ws.seq.probe = pb.data_ptr() if pb is not None else None
             ws.seq.probe_mask, ws.seq.probe_slots = pm, (pb.numel() // 2 if pb is not None else 0)
@@ -310,7 +325,7 @@ class FusedTrainer:
             mark()
             self._head_pass(eng, ws, yv, B, T, O, H, W, Hc, Wc, wts, acc, spec)
             mark()
-            bk = dict(zero_state_grads=range(L), dW_out=self._dW, db_out=self._db, seq_grads=sq, accumulate=acc)
+            bk = dict(zero_state_grads=range(L), dW_out=self._dW, db_out=self._db, seq_grads=sq, accumulate=acc, train_from=f)
             if last and self.distributed and self.overlap_allreduce and L > 1 and pb is None:
                 # the bucket without layer 0's slice is exchanged under layer 0's weight gradient; _finish exchanges the slice
                 n0 = self.flat.offsets[2]              # layers.0.conv.weight + .bias lead the bucket (module parameter order)
@@ -334,7 +349,9 @@ class FusedTrainer:
             self.dist.all_reduce(self.flat.grad[:n0], op=self.dist.ReduceOp.SUM, group=self.pg)
             pending.wait()                         # (stream-level for RCCL: the step stays asynchronous to the host)
         elif self.distributed:
-            self.dist.all_reduce(self.flat.grad, op=self.dist.ReduceOp.SUM, group=self.pg)   # RCCL over xGMI
+            # (frozen layers lead the bucket -- module parameter order --: the trained tail alone is exchanged; all of it without)
+            g = self.flat.grad[self.optimizer.n0:] if self.optimizer.n0 else self.flat.grad
+            self.dist.all_reduce(g, op=self.dist.ReduceOp.SUM, group=self.pg)   # RCCL over xGMI
         self.optimizer.step(grad_scale=1.0 / (self.accumulate_steps * self.world))
         self._mark()
         return self.scratch[0]
@@ -354,7 +371,7 @@ class FusedTrainer:
         window's bits and so has the loss."""
         m, L, mark = self.model, self.model.num_layers, self._mark
         B, T, _, H, W = X.shape
-        n, S = len(plan), plan[0][1]
+        n, S, f = len(plan), plan[0][1], self.freeze_layers
         seg = (lambda t0: X.segment(t0, S)) if hasattr(X, "segment") else (lambda t0: X[:, t0:t0 + S])
         if carried is None:
             self._zero = self._state_for(self._zero, eng, B, H, W)
@@ -365,7 +382,7 @@ class FusedTrainer:
                 eng.zero_start(wf, carried is None and t0 == 0)
                 eng.forward(wf, seg(t0))
                 states.append(eng.save_state(wf))        # slot S -> a new state: the start of the next segment
-        with eng.window(B, S, H, W, True, True) as ws:
+        with eng.window(B, S, H, W, True, True, f) as ws:
             eng.load_state(ws, states[-1])
             eng.forward(ws, seg(plan[-1][0]))
             if carried is not None:
@@ -375,12 +392,12 @@ class FusedTrainer:
             O = m.conv.weight.shape[0]
             self._head_pass(eng, ws, yv, B, S, O, H, W, yv.shape[-2], yv.shape[-1], wts, acc, spec)
             mark()
-            eng.backward(ws, False, zero_state_grads=range(L), dW_out=self._dW, db_out=self._db, accumulate=acc)
-            for j in range(n - 2, -1, -1):
+            eng.backward(ws, False, zero_state_grads=range(L), dW_out=self._dW, db_out=self._db, accumulate=acc, train_from=f)
+            for j in range(n - 2, -1, -1) if f < L else ():      # (the head alone: its gradient is the last segment's)
                 eng.load_state(ws, states[j])
                 eng.zero_start(ws, carried is None and j == 0)
                 eng.forward(ws, seg(plan[j][0]))
-                eng.backward(ws, False, zero_state_grads=(), dW_out=self._dW, db_out=self._db, accumulate=True)
+                eng.backward(ws, False, zero_state_grads=(), dW_out=self._dW, db_out=self._db, accumulate=True, train_from=f)
             mark()
 
     def _mark(self):

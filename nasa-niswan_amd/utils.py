@@ -29,18 +29,30 @@ def save_checkpoint(model, optimizer, filename, learning_rate=None, epoch=None):
     torch.save(checkpoint, filename)
 
 
-def load_checkpoint(checkpoint_file, model, optimizer=None, lr=None, map_location=None):
+def load_checkpoint(checkpoint_file, model, optimizer=None, lr=None, map_location=None, reset_optimizer=False):
     """reference utils.py:34-50: restores weights (+ Adam moments) and overrides the LR with the CLI
-    value; epoch counter and scheduler are NOT restored (reference behaviour, Appendix A-8)."""
+    value; epoch counter and scheduler are NOT restored (reference behaviour, Appendix A-8).
+    ``reset_optimizer``: the weights only -- the optimizer keeps its fresh moments, step count and groups.  The entry point
+    of fine-tuning: the checkpoint's optimizer state belongs to another set of trained parameters.  Without it an optimizer
+    state whose param groups do not match the optimizer's is a ValueError that says so.  The LR override keeps each group's
+    factor of a ``layer_lr_scale`` optimizer (``optimizer.lr_scales``)."""
     checkpoint = torch.load(checkpoint_file, map_location=map_location, weights_only=True)
     print('Number of Epochs: ', checkpoint['epoch'])
     print('Learning Rate: ', checkpoint['learning_rate'])
     model.load_state_dict(checkpoint['model_state_dict'])
-    if optimizer is not None:
-        optimizer.load_state_dict(checkpoint['optimizer_state_dict'])
+    if optimizer is not None and not reset_optimizer:
+        try:
+            optimizer.load_state_dict(checkpoint['optimizer_state_dict'])
+        except ValueError as e:
+            saved = [len(g['params']) for g in checkpoint['optimizer_state_dict']['param_groups']]
+            have = [len(g['params']) for g in optimizer.param_groups]
+            raise ValueError(f"{checkpoint_file}: its optimizer state has param groups of {saved} parameters, the optimizer has "
+                             f"{have} (other frozen layers or another grouping: {e}); pass reset_optimizer=True (train.py "
+                             "--reset-optimizer) to load the weights alone") from e
+        scales = getattr(optimizer, 'lr_scales', None) or [1.0] * len(optimizer.param_groups)
         if lr is not None:
-            for param_group in optimizer.param_groups:
-                param_group['lr'] = lr
+            for param_group, scale in zip(optimizer.param_groups, scales):
+                param_group['lr'] = lr * scale
         elif checkpoint['learning_rate'] is not None:
             new_lr = checkpoint['learning_rate']
             if isinstance(new_lr, (list, tuple)):      # the reference stores scheduler.get_last_lr() (a list)

@@ -36,7 +36,15 @@ after the shape.
                 (``tr.flat.data``) and the carried state (``tr.state.tensors()``) are read back before chunk 2, and the oracle
                 runs chunk 2 from exactly those (reset lanes zeroed, state detached) -- Adam's sign sensitivity between the
                 chunks never enters a gate.  Loss, bucket and carried state after each chunk.
-  --self-check  (with one of the three) after the first passing case to which a fault applies, the REFERENCE is corrupted on
+  --finetune    two steps of ``FusedTrainer(freeze_layers=f, weight_decay=wd, layer_lr_scale=scales)`` with f drawn from 0 .. L
+                (nothing frozen ... the head alone), wd from {0, 1e-2, 0.1} and one scale per layer.  Each step is checked from
+                the parameters and moments the device held before it: the loss and the trained gradients against CPU autograd
+                (in bf16 the layers' weights: its biases and head sums cancel, the f32 cases gate them), the new weights against
+                ``torch.optim.AdamW`` (biases in zero-decay groups) stepping on the DEVICE's gradient at rtol 2e-6 / atol 1e-7,
+                and the frozen regions of the gradient bucket, the weights and both moments bit-unchanged.  The L1 kink
+                (below) is not treated here: a case that lands on it shows as a gradient miss in bf16.  --self-check: the
+                reference's AdamW loses its weight decay; the reference trains the frozen layers too.
+  --self-check  (with one of these modes) after the first passing case to which a fault applies, the REFERENCE is corrupted on
                 the host and the same comparison of the same device results must fail: --state: the oracle gets a zero c0
                 for the last layer; --train-opts with n >= 2: the oracle back-propagates the last segment only (truncated
                 BPTT); with accumulation: one window is left out of the sum; --stateful: the oracle ignores the reset.
@@ -79,7 +87,7 @@ pkg = engine = O = stored_dG = None          # the package and the oracle: loade
 WAVES = [None, 0, 1, 4, 2, 5, 4]            # engine.FORCE_WAVE by case number
 TILE_ROWS = [0, 0, 4, 8]                    # engine.FORCE_TILE_ROWS by case number
 OLD_MODES = ("plain", "trainer", "cell", "dataset")
-NEW_MODES = ("state", "train_opts", "stateful")
+NEW_MODES = ("state", "train_opts", "stateful", "finetune")       # (a new mode goes LAST: case_rng keys a stream by position)
 LIM = {"f32": 1e-3, "bf16": 3e-2}
 LOSS_LIM = {"f32": 2e-6, "bf16": 2e-2}
 
@@ -259,6 +267,17 @@ def draw_case(rng, it: int, mode: str = "plain", big: bool = False, wide: bool =
         case.update(out=out, B=B, T=T, n=n, S=S, reset_kind=kind, reset=reset, halo=[hy, hx], draws=draws,
                     tag=f"#{it} C={C} hidden={hidden} k={ks} out={out} B={B} T={T} {H}x{W} {dtype} wave={wave} rows={rows} "
                         f"halo=({hy},{hx}) n={n} S={S} reset={kind if reset is None or reset is True else [int(v) for v in reset]}")
+    elif mode == "finetune":
+        f = int(rng.integers(0, L + 1))                             # frozen layers: none ... all (the head alone)
+        wd = [0.0, 1e-2, 0.1][int(rng.integers(0, 3))]
+        scales = [float(rng.choice([0.1, 0.25, 0.5, 1.0])) for _ in range(L)]
+        hy, hx = _halo(rng, H, W)
+        out, B = max(out, 2), max(B, 2)
+        Hc, Wc = H - 2 * hy, W - 2 * hx
+        draws = [(f"{v}.{j}", sh) for j in range(2) for v, sh in (("X", (B, T, C, H, W)), ("y", (B, out, Hc, Wc)))]
+        case.update(out=out, B=B, f=f, wd=wd, scales=scales, halo=[hy, hx], draws=draws,
+                    tag=f"#{it} C={C} hidden={hidden} k={ks} out={out} B={B} T={T} {H}x{W} {dtype} wave={wave} rows={rows} "
+                        f"halo=({hy},{hx}) f={f} wd={wd} scales={scales}")
     else:
         raise ValueError(mode)
     return case
@@ -791,6 +810,88 @@ def stateful_run(case, d, params, self_check):
     return worst, tried
 
 
+# ---------------------------------------------------------------------------------------------------- --finetune
+def finetune_run(case, d, params, self_check, tried):
+    """Two steps of FusedTrainer(freeze_layers=f, weight_decay, layer_lr_scale), each checked from the parameters and moments
+    the device held before it: the loss and the trained gradients against CPU autograd (bf16: the layers' weights; its
+    biases and head sums cancel and are gated through the f32 cases), the frozen regions of the bucket, weights and moments
+    bit-unchanged, and the new weights against torch.optim.AdamW stepping on the DEVICE's gradient (rtol 2e-6, atol 1e-7: the
+    gate nint_adam_flat is held to).  Returns the worst gradient figure."""
+    from nasa_niswan_amd.trainer import FusedTrainer
+    L, f, wd, scales, halo, dtype, tag = case["L"], case["f"], case["wd"], case["scales"], tuple(case["halo"]), case["dtype"], case["tag"]
+    lr, sentinel = 1e-3, 4321.5
+    net = pkg.ConvLSTM(case["C"], case["hidden"], case["ks"], L, out_channels=case["out"], compute_dtype=dtype).cuda()
+    net.load_state_dict(params)
+    tr = FusedTrainer(net, lr=lr, halo=halo, freeze_layers=f, weight_decay=wd, layer_lr_scale=scales)
+    names = [k for k, _ in net.named_parameters()]
+    frozen = lambda k: k.startswith("layers.") and int(k.split(".")[1]) < f
+    n0 = tr.optimizer.n0
+    assert n0 == tr.flat.offsets[2 * f], (tag, "first trained element")
+    tr.flat.grad[:n0] = sentinel
+    start = tr.flat.data[:n0].clone()
+    worst = 0.0
+
+    def adamw(p_before, m_before, v_before, grads, step, fault=None):
+        leaf = {k: v.clone().requires_grad_(True) for k, v in p_before.items()}
+        groups = []
+        for k in names:
+            if frozen(k) and fault != "unfrozen":
+                continue
+            l = int(k.split(".")[1]) if k.startswith("layers.") else L - 1
+            decay = wd if leaf[k].dim() > 1 and fault != "no_decay" else 0.0
+            groups.append(dict(params=[leaf[k]], lr=lr * scales[l], weight_decay=decay))
+        opt = torch.optim.AdamW(groups, lr=lr, betas=(0.5, 0.999), eps=1e-8, foreach=False)
+        for g in groups:
+            (q,) = g["params"]
+            k = next(n for n in names if leaf[n] is q)
+            opt.state[q] = {"step": torch.tensor(float(step - 1)), "exp_avg": m_before[k].clone(), "exp_avg_sq": v_before[k].clone()}
+            q.grad = grads[k].clone() if not frozen(k) else torch.ones_like(q)
+        opt.step()
+        return {k: v.detach() for k, v in leaf.items()}
+
+    def close(new, want, what):
+        for k in names:
+            a, b = new[k], want[k]
+            assert torch.allclose(a, b, rtol=2e-6, atol=1e-7), (tag, what, k, float((a - b).abs().max()))
+
+    for j in range(2):
+        view = lambda buf: {k: buf[o:o + p.numel()].view(p.shape).detach().clone().cpu() for (k, p), o in zip(net.named_parameters(), tr.flat.offsets)}
+        p0, m0, v0 = view(tr.flat.data), view(tr.optimizer.exp_avg), view(tr.optimizer.exp_avg_sq)
+        X, y = d[f"X.{j}"], d[f"y.{j}"]
+        loss = float(tr.step(X.cuda(), y.cuda()))
+        torch.cuda.synchronize()
+        leaf = {k: v.clone().requires_grad_(not frozen(k)) for k, v in p0.items()}
+        lo = O.loss_mse_l1(y, O.crop_pred(O.convlstm_forward(X, leaf), halo, y.shape[-2:]))
+        lo.backward()
+        lo = float(lo.detach())
+        assert abs(loss - lo) <= LOSS_LIM[dtype] * abs(lo), (tag, f"step {j + 1} loss", loss, lo)
+        g_dev = view(tr.flat.grad)
+        for k in names:
+            if frozen(k):
+                assert bool((g_dev[k] == sentinel).all()), (tag, "a frozen region of the gradient bucket was written", k)
+                continue
+            a, b = g_dev[k].double(), leaf[k].grad.double()
+            assert torch.isfinite(a).all(), (tag, k)
+            if dtype == "bf16" and not (k.startswith("layers.") and a.dim() > 1):
+                continue
+            e = _err(dtype, a, b)
+            if case.get("verbose"):
+                print(f"     step {j + 1} grad.{k}: {e:.3e}", flush=True)
+            assert e <= LIM[dtype], (tag, f"step {j + 1}", k, e)
+            worst = max(worst, e)
+        new = view(tr.flat.data)
+        close(new, adamw(p0, m0, v0, g_dev, j + 1), f"step {j + 1}: weights against torch.optim.AdamW on the device's gradient")
+        if self_check:
+            for name, what, applies in (("no_decay", "the reference's AdamW has no weight decay", wd > 0),
+                                        ("unfrozen", "the reference trains the frozen layers too", f > 0)):
+                if applies and not tried.get(name):
+                    expect_failure(tag, what, lambda: close(new, adamw(p0, m0, v0, g_dev, j + 1, fault=name), what))
+                    tried[name] = True
+    assert torch.equal(tr.flat.data[:n0], start), (tag, "a frozen weight moved")
+    assert not tr.optimizer.exp_avg[:n0].any() and not tr.optimizer.exp_avg_sq[:n0].any(), (tag, "a frozen moment was written")
+    return worst
+
+
 def expect_failure(tag, what, fn):
     try:
         fn()
@@ -814,18 +915,19 @@ def parse(argv=None):
     ap.add_argument("--state", action="store_true", help="ConvLSTM.forward(x, state, return_state=...) with a drawn state and cotangents on every output, against oracle.convlstm_forward(h0=, c0=)")
     ap.add_argument("--train-opts", action="store_true", help="FusedTrainer.step with drawn bptt_segments, accumulate_steps, loss_weights, max_grad_norm, sequence_loss: losses and the bucket against CPU autograd over the whole window")
     ap.add_argument("--stateful", action="store_true", help="two chunks through FusedTrainer(stateful=True), the second with a drawn reset, each checked from the state and parameters the device held")
-    ap.add_argument("--self-check", action="store_true", help="with --state / --train-opts / --stateful: corrupt the reference after the first passing case and require the comparison to fail")
+    ap.add_argument("--finetune", action="store_true", help="two steps of FusedTrainer with a drawn number of frozen layers (0 ... all), weight decay and per-layer lr scales: loss and trained gradients against CPU autograd, the update against torch.optim.AdamW, the frozen regions untouched")
+    ap.add_argument("--self-check", action="store_true", help="with --state / --train-opts / --stateful / --finetune: corrupt the reference after the first passing case and require the comparison to fail")
     ap.add_argument("--list", action="store_true", help="print the drawn cases as JSON lines and exit (no GPU, the package is not imported)")
     ap.add_argument("--only", type=int, default=-1, help="replay the random stream up to this iteration and run it alone, printing every tensor's error")
     ap.add_argument("--force-wave", type=int, default=None, help="with --only: nint_seq.wave for the replayed case instead of the rotation's value")
     ap.add_argument("--force-dtype", choices=["f32", "bf16"], default=None, help="with --only: the storage type of the replayed case instead of the alternation's (is the miss the arithmetic's, or the storage type's?)")
     args = ap.parse_args(argv)
-    modes = [m for m in ("dataset", "cell", "trainer", "state", "train_opts", "stateful") if getattr(args, m)]
+    modes = [m for m in ("dataset", "cell", "trainer", "state", "train_opts", "stateful", "finetune") if getattr(args, m)]
     if len(modes) > 1 and not all(m in OLD_MODES for m in modes):
-        ap.error("one of --state / --train-opts / --stateful at a time, and none of the other modes with it")
+        ap.error("one of --state / --train-opts / --stateful / --finetune at a time, and none of the other modes with it")
     args.mode = modes[0] if modes else "plain"          # (--dataset before --cell before --trainer, as ever)
     if args.self_check and args.mode not in NEW_MODES:
-        ap.error("--self-check needs --state, --train-opts or --stateful")
+        ap.error("--self-check needs --state, --train-opts, --stateful or --finetune")
     return args
 
 
@@ -986,6 +1088,8 @@ def run_new(case, d, args, worst, tried):
         w, did = stateful_run(case, d, params, args.self_check and not tried.get("reset"))
         if did:
             tried["reset"] = True
+    elif mode == "finetune":
+        w = finetune_run(case, d, params, args.self_check, tried)
     else:
         if mode == "state":
             ref = state_oracle(case, d, params)
@@ -1053,7 +1157,7 @@ def main(argv=None):
         finally:
             engine.FORCE_WAVE, engine.FORCE_TILE_ROWS, engine.FORCE_WIDE = None, 0, 0
     if args.self_check:
-        want = {"state": ["zero_c0"], "train_opts": ["truncate", "drop"], "stateful": ["reset"]}[args.mode]
+        want = {"state": ["zero_c0"], "train_opts": ["truncate", "drop"], "stateful": ["reset"], "finetune": ["no_decay", "unfrozen"]}[args.mode]
         missing = [f for f in want if not tried.get(f)]
         if missing:
             raise SystemExit(f"SELF-CHECK INCOMPLETE: no drawn case to try {missing} on (raise --n or change the seed)")
