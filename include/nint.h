@@ -324,6 +324,11 @@ typedef struct nint_launch_rec {
   int32_t nt_begin;         /* first n-tile it computes */
 } nint_launch_rec;
 int nint_debug_seq_plan(const nint_seq* s /*host*/, int bwd, nint_launch_rec* out /*host*/, int cap);
+/* The merged-grid rule alone, for tests (host arithmetic only): the NINT_K_* kernel that would carry n independent launches of
+ * the conv_igemm bodies shapes[5 * i .. 5 * i + 5) = (epi, wn, wk, ntw, mt) as ONE grid, with_pw != 0: together with one
+ * pointwise backward pass -- or NINT_E_SHAPE where no merged kernel holds them all (also n outside [1, 4], or a tuple that is
+ * no body).  It is the planner's own choice: the drivers' plans go through the same function. */
+int nint_debug_multi_carrier(const int32_t* shapes /*host, n x 5*/, int n, int with_pw);
 
 /* ---- 1x1 head (model.py:251,274) ------------------------------------------------------------ */
 /* ONE rule decides which arithmetic every head entry below runs.  The "staged" bodies (weights zero-padded to [O][CHV] in

@@ -694,108 +694,82 @@ __global__ __launch_bounds__(256, MT >= 8 ? 2 : (xchg_rounds(EPI, WK, NTW, MT) =
   conv_igemm_body<DT, EPI, WN, WK, NTW, MT>(a, smem, blockIdx.x, blockIdx.y, gridDim.x);
 }
 
+// ------------------------------------------------------------------------------ the shape table
+// Which (EPI, WN, WK, NTW, MT) bodies exist and which kernel carries them is stated HERE and nowhere else: launch_conv walks
+// the two ladders, the merged kernels, their holds predicates, the carrier choice and the carrier -> kernel map are generated
+// from NINT_MULTI_KERNELS.  (ConvPlan::variant = conv_variant of a body, conv_shape its inverse: nint_common.h.)
+//
+// The ladders, X(cols, WN, WK, NTW), widest first: a workgroup takes cols = WN * NTW n-tiles, the waves that have no columns
+// of their own split K (WN * WK == 4).  The gate ladder is the 4-gate-tile rungs of the dgrad one (EPI_LSTM needs NTW % 4 == 0).
+#define NINT_GATE_LADDER(X) X(16, 4, 1, 4) X(8, 2, 2, 4) X(4, 1, 4, 4)
+#define NINT_DGRAD_LADDER(X) \
+  X(16, 4, 1, 4) X(12, 4, 1, 3) X(8, 2, 2, 4) X(6, 2, 2, 3) X(4, 1, 4, 4) X(3, 1, 4, 3) X(2, 1, 4, 2) X(1, 1, 4, 1)
+
 // Independent launches in ONE grid.  Forward: one wavefront step -- gate(0, t+1), gate(1, t), gate(2, t-1), ... are
 // independent (model.py:265-271); backward: the bottom layer's dgrad of time u and the top layer's fused step of time u-1
 // (adjacent in the BPTT order, and they share no buffer in a stack of three or more layers).  At small batches (the
 // strong-scaling shape) none of these fills the chip -- run back to back each pays its own fill / epilogue latency on
 // half-empty CUs.  Workgroup ranges [begin[i], begin[i+1]) belong to problem i (each range starts at a multiple of 8, so a
-// problem's tile -> XCD mapping is the one of its own launch); every problem runs the body of the 4-row-tile shape its own
-// launch would have taken (ConvPlan::variant): same instructions on the same data, bit-identical results.  Registers / LDS
-// are those of the widest variant in the kernel.
-// (ConvMulti, the argument block, and conv_variant: nint_common.h)
-#define NINT_MULTI_PROLOGUE                                                                                     \
-  extern __shared__ __attribute__((aligned(16))) char smem[];                                                   \
-  int i = 0;                                                                                                    \
-  _Pragma("unroll") for (int q = 1; q < NINT_MULTI_MAX; ++q) i += (q < m.n && (int)blockIdx.x >= m.begin[q]) ? 1 : 0; \
-  const int b = blockIdx.x - m.begin[i];                                                                        \
-  if (b >= m.nwg[i]) return;                   /* (padding up to the next multiple of 8) */                     \
-  const int nbx = m.nbx[i], by = b / nbx, bx = b - by * nbx;                                                    \
-  const ConvArgs& a = m.a[i];
-#define NINT_MULTI_CASE(EPI_, WN_, WK_, NTW_) \
-  case conv_variant(EPI_, WN_, WK_, NTW_, 4): conv_igemm_body<DT, EPI_, WN_, WK_, NTW_, 4>(a, smem, bx, by, nbx); break;
-template <int DT>
-__global__ __launch_bounds__(256, 3) void conv_lstm_multi_kernel(ConvMulti m) {
-  NINT_MULTI_PROLOGUE
-  switch (m.variant[i]) {
-    NINT_MULTI_CASE(EPI_LSTM, 4, 1, 4)
-    NINT_MULTI_CASE(EPI_LSTM, 2, 2, 4)
-    NINT_MULTI_CASE(EPI_LSTM, 1, 4, 4)
-    default: break;
-  }
-}
-// ... with the first layer on its 8-row tiles (mid-size batches; 256 registers: two workgroups per CU for every problem of
-// the grid).  B = 4 at 100 x 154: 966 -> 989 samples/s, steady; B = 8: bimodal from process to process (1021-1032 or 995-1000
-// against a steady 1022-1025), so the engine's rule stops below it.
-#define NINT_MULTI_CASE8(EPI_, WN_, WK_, NTW_) \
-  case conv_variant(EPI_, WN_, WK_, NTW_, 8): conv_igemm_body<DT, EPI_, WN_, WK_, NTW_, 8>(a, smem, bx, by, nbx); break;
-template <int DT>
-__global__ __launch_bounds__(256, 2) void conv_lstm_multi8_kernel(ConvMulti m) {
-  NINT_MULTI_PROLOGUE
-  switch (m.variant[i]) {
-    NINT_MULTI_CASE8(EPI_LSTM, 4, 1, 4)
-    NINT_MULTI_CASE8(EPI_LSTM, 2, 2, 4)
-    NINT_MULTI_CASE8(EPI_LSTM, 1, 4, 4)
-    NINT_MULTI_CASE(EPI_LSTM, 4, 1, 4)
-    NINT_MULTI_CASE(EPI_LSTM, 2, 2, 4)
-    NINT_MULTI_CASE(EPI_LSTM, 1, 4, 4)
-    default: break;
-  }
-}
-template <int DT>
-__global__ __launch_bounds__(256, 3) void conv_bwd_multi_kernel(ConvMulti m) {
-  if (m.pw_blocks && (int)blockIdx.x >= m.begin[m.n]) {      // (nint_seq.wave = 4: the bottom layer's pointwise backward behind the top layer's fused step)
+// problem's tile -> XCD mapping is the one of its own launch); every problem runs the body its own launch would have taken
+// (ConvPlan::variant): same instructions on the same data, bit-identical results.  Registers / LDS are those of the widest
+// variant in the kernel.  (ConvMulti, the argument block: nint_common.h)
+//
+// The case lists, X(EPI, WN, WK, NTW, MT) in switch order.  A list is one kernel's register allocation: adding a case can
+// change every body of that kernel (tools/asm_diff.py and tools/regs.py show it), so a new pairing that does not fit gets a
+// list -- a kernel -- of its own.  To add or drop a case, edit its list; the holds predicate and the planner follow.
+//   lstm_multi   one wavefront step on 4-row tiles.
+//   lstm_multi8  ... with the first layer on its 8-row tiles (mid-size batches; 256 registers: two workgroups per CU for every
+//                problem of the grid).  B = 4 at 100 x 154: 966 -> 989 samples/s, steady; B = 8: bimodal from process to
+//                process (1021-1032 or 995-1000 against a steady 1022-1025), so the engine's rule stops below it.
+//   bwd_multi    4-row BPTT launches; the only kernel with the pointwise tail (nint_seq.wave = 4: the bottom layer's pointwise
+//                backward behind the top layer's fused step).  The register-heavy fused shapes -- 4 column tiles per wave --
+//                would spill at 168 VGPRs.
+//   bwd_multi8   ... with 8-row tiles among them.
+//   dgrad_multi8 the dgrad launches of two neighbouring layers (nint_seq.wave = 4: the bottom layer's of time u+1 with the next
+//                layer's of time u), both on 8-row tiles.  A kernel of its own: as two more cases of bwd_multi8 the register
+//                allocation of ALL its bodies collapsed (1036 spilled registers).
+#define NINT_CASES_LSTM_MULTI(X) X(EPI_LSTM, 4, 1, 4, 4) X(EPI_LSTM, 2, 2, 4, 4) X(EPI_LSTM, 1, 4, 4, 4)
+#define NINT_CASES_LSTM_MULTI8(X) X(EPI_LSTM, 4, 1, 4, 8) X(EPI_LSTM, 2, 2, 4, 8) X(EPI_LSTM, 1, 4, 4, 8) NINT_CASES_LSTM_MULTI(X)
+#define NINT_CASES_BWD_MULTI(X) \
+  X(EPI_DGRAD, 1, 4, 4, 4) X(EPI_DGRAD, 1, 4, 2, 4) X(EPI_DGRAD, 2, 2, 3, 4) X(EPI_DGRAD, 1, 4, 3, 4) X(EPI_DGRAD_PW, 1, 4, 3, 4)
+#define NINT_CASES_BWD_MULTI8(X) \
+  X(EPI_DGRAD, 1, 4, 4, 8) X(EPI_DGRAD_PW, 1, 4, 3, 8) X(EPI_DGRAD, 1, 4, 4, 4) X(EPI_DGRAD, 1, 4, 2, 4) X(EPI_DGRAD_PW, 1, 4, 3, 4)
+#define NINT_CASES_DGRAD_MULTI8(X) X(EPI_DGRAD, 1, 4, 4, 8) X(EPI_DGRAD, 2, 2, 3, 8)
+// K(kernel, carrier, workgroups per CU, pointwise tail, case list), in the planner's first-fit order
+#define NINT_MULTI_KERNELS(K)                                                                     \
+  K(conv_lstm_multi_kernel, NINT_K_CONV_LSTM_MULTI, 3, false, NINT_CASES_LSTM_MULTI)              \
+  K(conv_lstm_multi8_kernel, NINT_K_CONV_LSTM_MULTI8, 2, false, NINT_CASES_LSTM_MULTI8)           \
+  K(conv_bwd_multi_kernel, NINT_K_CONV_BWD_MULTI, 3, true, NINT_CASES_BWD_MULTI)                  \
+  K(conv_bwd_multi8_kernel, NINT_K_CONV_BWD_MULTI8, 2, false, NINT_CASES_BWD_MULTI8)              \
+  K(conv_dgrad_multi8_kernel, NINT_K_CONV_DGRAD_MULTI8, 2, false, NINT_CASES_DGRAD_MULTI8)
+
 #ifndef NINT_PW_U
 #define NINT_PW_U 2
 #endif
-    lstm_bwd_pointwise_body<DT, NINT_PW_U>(m.pw, blockIdx.x - m.begin[m.n], m.pw_blocks);
-    return;
+#define NINT_MULTI_CASE(EPI_, WN_, WK_, NTW_, MT_) \
+  case conv_variant(EPI_, WN_, WK_, NTW_, MT_): conv_igemm_body<DT, EPI_, WN_, WK_, NTW_, MT_>(a, smem, bx, by, nbx); break;
+#define NINT_MULTI_KERNEL(NAME, CARRIER, WGS, PW, CASES)                                                          \
+  template <int DT>                                                                                               \
+  __global__ __launch_bounds__(256, WGS) void NAME(ConvMulti m) {                                                 \
+    if constexpr (PW) {                                                                                           \
+      if (m.pw_blocks && (int)blockIdx.x >= m.begin[m.n]) {                                                       \
+        lstm_bwd_pointwise_body<DT, NINT_PW_U>(m.pw, blockIdx.x - m.begin[m.n], m.pw_blocks);                     \
+        return;                                                                                                   \
+      }                                                                                                           \
+    }                                                                                                             \
+    extern __shared__ __attribute__((aligned(16))) char smem[];                                                   \
+    int i = 0;                                                                                                    \
+    _Pragma("unroll") for (int q = 1; q < NINT_MULTI_MAX; ++q) i += (q < m.n && (int)blockIdx.x >= m.begin[q]) ? 1 : 0; \
+    const int b = blockIdx.x - m.begin[i];                                                                        \
+    if (b >= m.nwg[i]) return;                   /* (padding up to the next multiple of 8) */                     \
+    const int nbx = m.nbx[i], by = b / nbx, bx = b - by * nbx;                                                    \
+    const ConvArgs& a = m.a[i];                                                                                   \
+    switch (m.variant[i]) {                                                                                       \
+      CASES(NINT_MULTI_CASE)                                                                                      \
+      default: break;                            /* (not reached: the planner places a launch by the same list) */ \
+    }                                                                                                             \
   }
-  NINT_MULTI_PROLOGUE
-  switch (m.variant[i]) {
-    NINT_MULTI_CASE(EPI_DGRAD, 1, 4, 4)
-    NINT_MULTI_CASE(EPI_DGRAD, 1, 4, 2)
-    NINT_MULTI_CASE(EPI_DGRAD, 2, 2, 3)
-    NINT_MULTI_CASE(EPI_DGRAD, 1, 4, 3)
-    NINT_MULTI_CASE(EPI_DGRAD_PW, 1, 4, 3)
-    default: break;                            // (the register-heavy fused shapes -- 4 column tiles per wave -- would spill at 168 VGPRs)
-  }
-}
-template <int DT>
-__global__ __launch_bounds__(256, 2) void conv_bwd_multi8_kernel(ConvMulti m) {
-  NINT_MULTI_PROLOGUE
-  switch (m.variant[i]) {
-    NINT_MULTI_CASE8(EPI_DGRAD, 1, 4, 4)
-    NINT_MULTI_CASE8(EPI_DGRAD_PW, 1, 4, 3)
-    NINT_MULTI_CASE(EPI_DGRAD, 1, 4, 4)
-    NINT_MULTI_CASE(EPI_DGRAD, 1, 4, 2)
-    NINT_MULTI_CASE(EPI_DGRAD_PW, 1, 4, 3)
-    default: break;
-  }
-}
-// the dgrad launches of two neighbouring layers (nint_seq.wave = 4: the bottom layer's of time u+1 with the next layer's of time
-// u), both on 8-row tiles.  A kernel of its own: as two more cases of the kernel above the register allocation of ALL its
-// bodies collapsed (1036 spilled registers).
-template <int DT>
-__global__ __launch_bounds__(256, 2) void conv_dgrad_multi8_kernel(ConvMulti m) {
-  NINT_MULTI_PROLOGUE
-  switch (m.variant[i]) {
-    NINT_MULTI_CASE8(EPI_DGRAD, 1, 4, 4)
-    NINT_MULTI_CASE8(EPI_DGRAD, 2, 2, 3)
-    default: break;
-  }
-}
-static bool multi_holds(int variant) {
-  switch (variant) {
-    case conv_variant(EPI_LSTM, 4, 1, 4, 8): case conv_variant(EPI_DGRAD, 1, 4, 4, 8):      // (the *_multi8 kernels)
-    case conv_variant(EPI_LSTM, 2, 2, 4, 8): case conv_variant(EPI_LSTM, 1, 4, 4, 8): case conv_variant(EPI_DGRAD_PW, 1, 4, 3, 8):
-    case conv_variant(EPI_LSTM, 4, 1, 4, 4): case conv_variant(EPI_LSTM, 2, 2, 4, 4): case conv_variant(EPI_LSTM, 1, 4, 4, 4):
-    case conv_variant(EPI_DGRAD, 1, 4, 4, 4): case conv_variant(EPI_DGRAD, 1, 4, 2, 4): case conv_variant(EPI_DGRAD_PW, 1, 4, 3, 4):
-    case conv_variant(EPI_DGRAD, 2, 2, 3, 8): case conv_variant(EPI_DGRAD, 2, 2, 3, 4):      // (8-row: conv_dgrad_multi8_kernel)
-    case conv_variant(EPI_DGRAD, 1, 4, 3, 4):
-      return true;
-    default: return false;
-  }
-}
+NINT_MULTI_KERNELS(NINT_MULTI_KERNEL)
 
 // ------------------------------------------------------------------------------ host side
 // Every conv launch is PLANNED (ConvPlan, nint_common.h: arguments, grid, LDS, kernel handle) and enqueued from its plan, by
@@ -862,6 +836,23 @@ int nint_internal_n_cu() {
 #ifndef NINT_SPLIT_NUM
 #define NINT_SPLIT_NUM 3        // small batches: split the columns while workgroups < NINT_SPLIT_NUM / 2 per CU
 #endif
+// One walk for all three epilogues: the first rung (WN, NTW) whose WN*NTW columns divide the tile count, widest first; leftover
+// waves split K.  Small batches (the strong-scaling shape: B = 1 per GPU is 125 8-row tiles for 256 CUs): a rung whose launch
+// would leave CUs without a workgroup is passed over for the next narrower one (more column groups on blockIdx.y: the waves
+// that no longer have columns of their own slice K instead) -- each workgroup then re-stages the halo tile, which an idle CU
+// does for free.  Not for the fused backward step, and an explicit nint_layer.tile_rows pins the launch shape: no split.
+template <int DT, int EPI, int MT>
+static int walk_ladder(ConvArgs& a, int N, int ntiles, int n_cu, ConvPlan* plan) {
+  const int ptiles = N * nint_cdiv(a.W, 16) * nint_cdiv(a.H, MT);
+  auto few = [&](int cols) { return !a.tile_rows && EPI != EPI_DGRAD_PW && 2 * ptiles * (ntiles / cols) < NINT_SPLIT_NUM * n_cu; };
+  constexpr int last = EPI == EPI_LSTM ? 4 : 1;       // (a gate launch has ntiles % 4 == 0: launch_conv)
+#define NINT_RUNG(COLS, WN, WK, NTW) \
+  if (ntiles % COLS == 0 && (COLS == last || !few(COLS))) return launch_cfg<DT, EPI, WN, WK, NTW, MT>(a, N, ntiles / COLS, plan);
+  if constexpr (EPI == EPI_LSTM) { NINT_GATE_LADDER(NINT_RUNG) } else { NINT_DGRAD_LADDER(NINT_RUNG) }
+#undef NINT_RUNG
+  return NINT_E_SHAPE;                                // (not reached: the last rung takes every count)
+}
+
 template <int DT, int EPI>
 static int launch_conv(ConvArgs& a, int N, int ntiles, int n_cu, ConvPlan* plan) {
   plan->gx = 0; plan->carrier = NINT_K_CONV_IGEMM;
@@ -876,48 +867,41 @@ static int launch_conv(ConvArgs& a, int N, int ntiles, int n_cu, ConvPlan* plan)
   if (n_cu <= 0) n_cu = nint_internal_n_cu();   // (the single-launch entry points; the sequence drivers look it up once per pass)
   // few images (B = 1 or 2 per GPU): 8-row tiles would leave CUs without a workgroup; 4-row tiles double the count
   if (!a.tile_rows && 2 * N * nint_cdiv(a.W, 16) * nint_cdiv(a.H, 8) < 3 * n_cu) mt4 = true;
-  if constexpr (EPI == EPI_LSTM) {
-    if (ntiles % 4) return NINT_E_SHAPE;
-    const int cbs = ntiles / 4;
-    // Small batches (the strong-scaling shape: B = 1 per GPU is 125 8-row tiles for 256 CUs): when the pixel tiles alone
-    // leave CUs empty, the gate columns are split over more workgroups (column groups on blockIdx.y: the waves that no
-    // longer have columns of their own slice K instead) -- each then re-stages the halo tile, which an idle CU does for free.
-    const int ptiles = N * nint_cdiv(a.W, 16) * nint_cdiv(a.H, mt4 ? 4 : 8);
-    // (an explicit nint_layer.tile_rows pins the launch shape: no split)
-    const bool few4 = !a.tile_rows && 2 * ptiles * (cbs / 4 > 0 ? cbs / 4 : 1) < NINT_SPLIT_NUM * n_cu;       // with 4 column blocks per workgroup
-    const bool few2 = !a.tile_rows && 2 * ptiles * (cbs / 2 > 0 ? cbs / 2 : 1) < NINT_SPLIT_NUM * n_cu;       // with 2
-    if (cbs % 4 == 0 && !few4) return mt4 ? launch_cfg<DT, EPI, 4, 1, 4, 4>(a, N, cbs / 4, plan) : launch_cfg<DT, EPI, 4, 1, 4, 8>(a, N, cbs / 4, plan);
-    if (cbs % 2 == 0 && !few2) return mt4 ? launch_cfg<DT, EPI, 2, 2, 4, 4>(a, N, cbs / 2, plan) : launch_cfg<DT, EPI, 2, 2, 4, 8>(a, N, cbs / 2, plan);
-    return mt4 ? launch_cfg<DT, EPI, 1, 4, 4, 4>(a, N, cbs, plan) : launch_cfg<DT, EPI, 1, 4, 4, 8>(a, N, cbs, plan);
-  } else {
-    // (WN, NTW) with WN*NTW dividing the tile count, widest first; leftover waves split K.  Small batches: a shape whose
-    // launch would leave CUs without a workgroup is passed over for the next narrower one (more column groups on
-    // blockIdx.y; the same rule as the gate launches above)
-    const int ptiles = N * nint_cdiv(a.W, 16) * nint_cdiv(a.H, mt4 ? 4 : 8);
-    auto few = [&](int cols) { return !a.tile_rows && EPI == EPI_DGRAD && 2 * ptiles * (ntiles / cols) < NINT_SPLIT_NUM * n_cu; };
-    if (ntiles % 16 == 0 && !few(16)) return mt4 ? launch_cfg<DT, EPI, 4, 1, 4, 4>(a, N, ntiles / 16, plan) : launch_cfg<DT, EPI, 4, 1, 4, 8>(a, N, ntiles / 16, plan);
-    if (ntiles % 12 == 0 && !few(12)) return mt4 ? launch_cfg<DT, EPI, 4, 1, 3, 4>(a, N, ntiles / 12, plan) : launch_cfg<DT, EPI, 4, 1, 3, 8>(a, N, ntiles / 12, plan);
-    if (ntiles % 8 == 0 && !few(8)) return mt4 ? launch_cfg<DT, EPI, 2, 2, 4, 4>(a, N, ntiles / 8, plan) : launch_cfg<DT, EPI, 2, 2, 4, 8>(a, N, ntiles / 8, plan);
-    if (ntiles % 6 == 0 && !few(6)) return mt4 ? launch_cfg<DT, EPI, 2, 2, 3, 4>(a, N, ntiles / 6, plan) : launch_cfg<DT, EPI, 2, 2, 3, 8>(a, N, ntiles / 6, plan);
-    if (ntiles % 4 == 0 && !few(4)) return mt4 ? launch_cfg<DT, EPI, 1, 4, 4, 4>(a, N, ntiles / 4, plan) : launch_cfg<DT, EPI, 1, 4, 4, 8>(a, N, ntiles / 4, plan);
-    if (ntiles % 3 == 0 && !few(3)) return mt4 ? launch_cfg<DT, EPI, 1, 4, 3, 4>(a, N, ntiles / 3, plan) : launch_cfg<DT, EPI, 1, 4, 3, 8>(a, N, ntiles / 3, plan);
-    if (ntiles % 2 == 0 && !few(2)) return mt4 ? launch_cfg<DT, EPI, 1, 4, 2, 4>(a, N, ntiles / 2, plan) : launch_cfg<DT, EPI, 1, 4, 2, 8>(a, N, ntiles / 2, plan);
-    return mt4 ? launch_cfg<DT, EPI, 1, 4, 1, 4>(a, N, ntiles, plan) : launch_cfg<DT, EPI, 1, 4, 1, 8>(a, N, ntiles, plan);
-  }
+  if (EPI == EPI_LSTM && ntiles % 4) return NINT_E_SHAPE;
+  return mt4 ? walk_ladder<DT, EPI, 4>(a, N, ntiles, n_cu, plan) : walk_ladder<DT, EPI, 8>(a, N, ntiles, n_cu, plan);
 }
 
 static inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+
+// What the gate launch (cell_fwd) and the backward-data launch (nint_internal_conv_dgrad) share.  The two checks stay where each
+// entry has always made them: their place among the other checks decides which code a doubly wrong call returns.
+static inline bool dtype_ok(int dtype) { return dtype == NINT_F32 || dtype == NINT_BF16; }
+static inline bool tile_rows_ok(const nint_layer* ly) {
+  return ly->tile_rows == 0 || ly->tile_rows == 1 || ly->tile_rows == 2 || ly->tile_rows == 4 || ly->tile_rows == 8;
+}
+struct ElemSize { int es, kc; };                 // bytes per element, elements per 64-byte channel chunk
+static inline ElemSize elem_size(int dtype) { return dtype == NINT_BF16 ? ElemSize{2, 32} : ElemSize{4, 16}; }
+static void set_geometry(ConvArgs& a, const nint_layer* ly, const nint_geom* g) {
+  a.k = ly->k; a.p = ly->k / 2; a.taps = ly->k * ly->k;
+  a.H = g->H; a.W = g->W; a.P = g->P; a.Hh = g->Hh; a.Wh = g->Wh;
+  // (1 / 2 = the stencil / dense-K GATE kernels, which cell_fwd reads from the layer itself: the backward launches take their own choice)
+  a.tile_rows = ly->tile_rows <= 2 ? 0 : ly->tile_rows;
+}
+template <int EPI>
+static int launch_conv_as(int dtype, ConvArgs& a, int N, int ntiles, int n_cu, ConvPlan* plan) {
+  return nint_by_dtype(dtype, [&](auto dt) { return launch_conv<decltype(dt)::value, EPI>(a, N, ntiles, n_cu, plan); });
+}
 
 static int cell_fwd(const nint_layer* ly, const nint_geom* g, int dtype, int N,
                     const void* x_slab, const void* h_prev, const float* c_prev,
                     void* h_out, float* c_out, void* gates_out, void* stream, int n_cu, ConvPlan* plan) {
   // plan != nullptr: nothing is enqueued, *plan describes the launch
   if (!ly || !g || !x_slab || !h_out || !c_out || N <= 0) return NINT_E_ARG;
-  if (dtype != NINT_F32 && dtype != NINT_BF16) return NINT_E_ARG;
+  if (!dtype_ok(dtype)) return NINT_E_ARG;
   if (!(ly->k & 1) || ly->k / 2 > g->P) return NINT_E_ARG;
-  if (ly->tile_rows != 0 && ly->tile_rows != 1 && ly->tile_rows != 2 && ly->tile_rows != 4 && ly->tile_rows != 8) return NINT_E_ARG;
+  if (!tile_rows_ok(ly)) return NINT_E_ARG;
   if (!aligned16(x_slab) || !aligned16(h_prev) || !aligned16(ly->Wf) || !aligned16(h_out)) return NINT_E_ALIGN;
-  const int es = dtype == NINT_BF16 ? 2 : 4, kc = dtype == NINT_BF16 ? 32 : 16;
+  const auto [es, kc] = elem_size(dtype);
   if (ly->Cxp % kc || ly->Chp % kc || ly->Ch16 % 16 || ly->Chp < ly->Ch16) return NINT_E_ARG;
   if ((ly->xfold != 0 && ly->xfold != 1) || (ly->xfold && ly->Cxp < ly->k * ly->Cx)) return NINT_E_ARG;
   ConvArgs a = {};
@@ -932,13 +916,11 @@ static int cell_fwd(const nint_layer* ly, const nint_geom* g, int dtype, int N,
   a.Bp = (const char*)ly->Wf;
   a.NTt = 4 * ly->Ch16 / 16;
   a.nt_begin = 0;
-  a.k = ly->k; a.p = ly->k / 2; a.taps = ly->k * ly->k;
+  set_geometry(a, ly, g);
   a.kx0 = ly->xfold ? 1 : ly->k;              // horizontally folded x source: vertical taps only
-  a.H = g->H; a.W = g->W; a.P = g->P; a.Hh = g->Hh; a.Wh = g->Wh;
   a.bias = ly->bias_p;
   a.c_prev = c_prev; a.c_out = c_out; a.h_out = (char*)h_out; a.gates_out = (char*)gates_out;
   a.Chp = ly->Chp; a.Ch16 = ly->Ch16; a.Ch = ly->Ch;
-  a.tile_rows = ly->tile_rows <= 2 ? 0 : ly->tile_rows;
   if (ly->wide < 0 || ly->wide > 2) return NINT_E_ARG;   // (the weight-gradient family switch: nothing to do with this launch)
   // tiny hidden widths (4*Ch <= 32 gate columns: no dense contraction): the VALU stencil kernel (csrc/stencil.hip) -- on request
   // (nint_layer.tile_rows == 1: "one pixel per lane"), or where it measured faster than the padded MFMA tiles (NINT_STENCIL_AUTO).
@@ -954,8 +936,7 @@ static int cell_fwd(const nint_layer* ly, const nint_geom* g, int dtype, int N,
   }
   ConvPlan own;
   ConvPlan* pl = plan ? plan : &own;
-  const int rc = dtype == NINT_BF16 ? launch_conv<NINT_BF16, EPI_LSTM>(a, N, a.NTt, n_cu, pl)
-                                    : launch_conv<NINT_F32, EPI_LSTM>(a, N, a.NTt, n_cu, pl);
+  const int rc = launch_conv_as<EPI_LSTM>(dtype, a, N, a.NTt, n_cu, pl);
   return rc != NINT_OK || plan ? rc : nint_internal_conv_enqueue(pl, stream);
 }
 
@@ -969,36 +950,41 @@ int nint_internal_cell_fwd_plan(const CellFwdJob* j, const nint_geom* g, int dty
   return cell_fwd(j->ly, g, dtype, N, j->x_slab, j->h_prev, j->c_prev, j->h_out, j->c_out, j->gates_out, nullptr, n_cu, plan);
 }
 
+// the merged kernels as the host sees them, in table order: carrier, pointwise tail, the two instantiations, the case list as a predicate
+#define NINT_HOLDS_CASE(EPI_, WN_, WK_, NTW_, MT_) case conv_variant(EPI_, WN_, WK_, NTW_, MT_):
+#define NINT_MULTI_ROW(NAME, CARRIER, WGS, PW, CASES)                            \
+  {CARRIER, PW, {(const void*)NAME<NINT_F32>, (const void*)NAME<NINT_BF16>},     \
+   [](int variant) { switch (variant) { CASES(NINT_HOLDS_CASE) return true; default: return false; } }},
+static const struct MultiKernel { int carrier; bool pw; const void* kern[2]; bool (*holds)(int variant); } multi_kernels[] = {
+    NINT_MULTI_KERNELS(NINT_MULTI_ROW)};
+static_assert(NINT_F32 == 0 && NINT_BF16 == 1, "MultiKernel::kern is indexed by dtype");
+
 // Up to NINT_MULTI_MAX planned launches that do not depend on each other, as ONE grid: which kernel, with what arguments (pure).
+// The carrier is the FIRST kernel of the table whose case list holds every launch (and which has the pointwise tail where pw
+// rides along); that gate and backward launches never share a grid and that no gate grid takes pw follow from the lists.
 int nint_internal_multi_plan(const ConvPlan* plans, int n, const PwArgs* pw, MultiPlan* out) {
   if (!plans || n < 1 || n > NINT_MULTI_MAX) return NINT_E_SHAPE;
+  const MultiKernel* carrier = nullptr;
+  for (const MultiKernel& k : multi_kernels) {
+    bool all = !pw || k.pw;
+    for (int i = 0; i < n && all; ++i) all = plans[i].gx > 0 && k.holds(plans[i].variant);
+    if (all) { carrier = &k; break; }
+  }
+  if (!carrier) return NINT_E_SHAPE;
   ConvMulti& m = out->m;
   m = ConvMulti{};
   size_t lds = 0;
-  int b = 0, nfwd = 0;
+  int b = 0;
   for (int i = 0; i < n; ++i) {
     const ConvPlan& pl = plans[i];
-    if (pl.gx <= 0 || !multi_holds(pl.variant)) return NINT_E_SHAPE;
-    nfwd += pl.variant / 10000 == EPI_LSTM ? 1 : 0;
     m.a[i] = pl.a; m.variant[i] = pl.variant; m.nbx[i] = pl.gx; m.nwg[i] = pl.gx * pl.gy;
     m.begin[i] = b;
     b += nint_round_up(pl.gx * pl.gy, 8);
     if (pl.lds > lds) lds = pl.lds;
   }
-  if (nfwd != 0 && nfwd != n) return NINT_E_SHAPE;
-  if (pw && nfwd) return NINT_E_SHAPE;
   m.n = n;
   for (int i = n; i <= NINT_MULTI_MAX; ++i) m.begin[i] = b;
-  bool rows8 = false, dpair = false;
-  for (int i = 0; i < n; ++i) rows8 = rows8 || plans[i].variant % 10 == 2;
-  for (int i = 0; i < n; ++i) dpair = dpair || plans[i].variant == conv_variant(EPI_DGRAD, 2, 2, 3, 8);
-  for (int i = 0; i < n; ++i)     // (the 4-row form of that shape is a case of conv_bwd_multi_kernel only, not of the 8-row kernel)
-    if (rows8 && (plans[i].variant == conv_variant(EPI_DGRAD, 2, 2, 3, 4) || plans[i].variant == conv_variant(EPI_DGRAD, 1, 4, 3, 4))) return NINT_E_SHAPE;
-  if (dpair)        // (conv_dgrad_multi8_kernel holds these two shapes only)
-    for (int i = 0; i < n; ++i)
-      if (plans[i].variant != conv_variant(EPI_DGRAD, 2, 2, 3, 8) && plans[i].variant != conv_variant(EPI_DGRAD, 1, 4, 4, 8)) return NINT_E_SHAPE;
-  if (pw) {                        // (a case of the 4-row backward kernel only)
-    if (rows8 || dpair) return NINT_E_SHAPE;
+  if (pw) {
     const size_t total = (size_t)pw->N * pw->H * pw->W * (pw->Ch16 / 4);
     size_t pb = (total + 255) / 256;
     // as many blocks as the conv problems have workgroups, within [1, 4] items per thread
@@ -1007,29 +993,38 @@ int nint_internal_multi_plan(const ConvPlan* plans, int n, const PwArgs* pw, Mul
     m.pw = *pw; m.pw_blocks = (int)pb;
     b += (int)pb;
   }
-  out->grid = b; out->lds = lds;
-  out->carrier = dpair ? NINT_K_CONV_DGRAD_MULTI8
-                       : nfwd ? (rows8 ? NINT_K_CONV_LSTM_MULTI8 : NINT_K_CONV_LSTM_MULTI) : (rows8 ? NINT_K_CONV_BWD_MULTI8 : NINT_K_CONV_BWD_MULTI);
+  out->grid = b; out->lds = lds; out->carrier = carrier->carrier;
   return NINT_OK;
 }
 
-template <int DT>
-static const void* multi_kernel(int carrier) {
-  switch (carrier) {
-    case NINT_K_CONV_DGRAD_MULTI8: return (const void*)conv_dgrad_multi8_kernel<DT>;
-    case NINT_K_CONV_LSTM_MULTI8: return (const void*)conv_lstm_multi8_kernel<DT>;
-    case NINT_K_CONV_LSTM_MULTI: return (const void*)conv_lstm_multi_kernel<DT>;
-    case NINT_K_CONV_BWD_MULTI8: return (const void*)conv_bwd_multi8_kernel<DT>;
-    default: return (const void*)conv_bwd_multi_kernel<DT>;
-  }
-}
 int nint_internal_multi_enqueue(const MultiPlan* mp, int dtype, void* stream) {
-  const void* kern = dtype == NINT_BF16 ? multi_kernel<NINT_BF16>(mp->carrier) : multi_kernel<NINT_F32>(mp->carrier);
+  const void* kern = nullptr;
+  for (const MultiKernel& k : multi_kernels)
+    if (k.carrier == mp->carrier) kern = k.kern[dtype == NINT_BF16];
+  if (!kern) return NINT_E_ARG;                  // (not a plan of nint_internal_multi_plan)
   if (mp->lds > 64 * 1024) NINT_CHECK_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mp->lds));
   void* args[] = {(void*)&mp->m};
   (void)hipLaunchKernel(kern, dim3(mp->grid), dim3(256), args, mp->lds, (hipStream_t)stream);
   NINT_LAUNCH_CHECK();
   return NINT_OK;
+}
+
+// the carrier rule alone, for tests (include/nint.h): one-workgroup plans stand in for the launches
+extern "C" int nint_debug_multi_carrier(const int32_t* shapes, int n, int with_pw) {
+  if (!shapes || n < 1 || n > NINT_MULTI_MAX) return NINT_E_SHAPE;
+  ConvPlan plans[NINT_MULTI_MAX] = {};
+  for (int i = 0; i < n; ++i) {
+    const int32_t* s = shapes + 5 * i;
+    if (s[0] < EPI_LSTM || s[0] > EPI_DGRAD_PW || (s[4] != 4 && s[4] != 8)) return NINT_E_SHAPE;
+    for (int q = 1; q <= 3; ++q)
+      if (s[q] < 0 || s[q] > 9) return NINT_E_SHAPE;          // (what conv_variant packs: one decimal digit each)
+    plans[i].gx = plans[i].gy = 1; plans[i].variant = conv_variant(s[0], s[1], s[2], s[3], s[4]);
+  }
+  PwArgs pw = {};
+  pw.N = pw.H = pw.W = 1; pw.Ch16 = 16;
+  MultiPlan mp;
+  const int rc = nint_internal_multi_plan(plans, n, with_pw ? &pw : nullptr, &mp);
+  return rc != NINT_OK ? rc : mp.carrier;
 }
 
 // the single-launch entry points: planned with a CU lookup of their own, enqueued at once
@@ -1050,15 +1045,15 @@ int nint_internal_conv_dgrad(const nint_layer* ly, const nint_geom* g, int dtype
                              void* dh_prev, bool overwrite_dx, const DgradPw* pw, int n_cu, ConvPlan* plan) {
   plan->gx = 0; plan->carrier = NINT_K_CONV_IGEMM;
   if (!ly || !g || !dG || N <= 0) return NINT_E_ARG;
-  if (dtype != NINT_F32 && dtype != NINT_BF16) return NINT_E_ARG;
+  if (!dtype_ok(dtype)) return NINT_E_ARG;
   // fused forms: pw->gates set = this layer's pointwise backward on the h columns (dh_prev is then not stored);
   // pw->gates NULL + pw->lo_gates = a classic dgrad (h columns stored) that runs the LOWER layer's pointwise backward
   if (pw && pw->gates && (!pw->c_new || !pw->dc || !pw->dG_out || dh_prev)) return NINT_E_ARG;
   if (pw && !pw->gates && !pw->lo_gates) return NINT_E_ARG;
   if (!dx_accum && !dh_prev && !pw) return NINT_OK;
   if (!aligned16(dG) || !aligned16(ly->Wd)) return NINT_E_ALIGN;
-  if (ly->tile_rows != 0 && ly->tile_rows != 1 && ly->tile_rows != 2 && ly->tile_rows != 4 && ly->tile_rows != 8) return NINT_E_ARG;
-  const int es = dtype == NINT_BF16 ? 2 : 4, kc = dtype == NINT_BF16 ? 32 : 16;
+  if (!tile_rows_ok(ly)) return NINT_E_ARG;
+  const auto [es, kc] = elem_size(dtype);
   const int Gc = 4 * ly->Ch16;
   ConvArgs a = {};
   a.src0 = (const char*)dG;
@@ -1069,14 +1064,12 @@ int nint_internal_conv_dgrad(const nint_layer* ly, const nint_geom* g, int dtype
   a.img_stride0 = (long)g->Hh * g->Wh * a.pix_stride0;
   a.Bp = (const char*)ly->Wd;
   a.NTt = (ly->Cxp + ly->Chp) / 16;
-  a.k = ly->k; a.p = ly->k / 2; a.taps = ly->k * ly->k;
+  set_geometry(a, ly, g);
   a.kx0 = ly->k;                              // the dG source always has all k x k taps (a folded x only zeroes weights)
-  a.H = g->H; a.W = g->W; a.P = g->P; a.Hh = g->Hh; a.Wh = g->Wh;
   a.out0 = (char*)dx_accum; a.out1 = (char*)dh_prev;
   a.out0_overwrite = overwrite_dx ? 1 : 0;
   a.C0p = ly->Cxp; a.C1p = ly->Chp;
   a.Chp = ly->Chp; a.Ch16 = ly->Ch16;
-  a.tile_rows = ly->tile_rows <= 2 ? 0 : ly->tile_rows;    // (1 / 2 = the stencil / dense-K GATE kernels: the backward launches take their own choice)
   // only the n-tiles whose destination exists are computed (fused: the Ch16 real hidden columns, not their padding)
   const int nt_x = ly->Cxp / 16, nt_h = (pw && pw->gates) ? ly->Ch16 / 16 : ly->Chp / 16;
   a.nt_begin = dx_accum ? 0 : nt_x;
@@ -1090,11 +1083,9 @@ int nint_internal_conv_dgrad(const nint_layer* ly, const nint_geom* g, int dtype
       a.lo_dG = (char*)pw->lo_dG_out; a.lo_Ch16 = pw->lo_Ch16; a.lo_dc_zero = pw->lo_dc_zero ? 1 : 0;
     }
     if (pw->tile_rows) a.tile_rows = pw->tile_rows;
-    return dtype == NINT_BF16 ? launch_conv<NINT_BF16, EPI_DGRAD_PW>(a, N, ntiles, n_cu, plan)
-                              : launch_conv<NINT_F32, EPI_DGRAD_PW>(a, N, ntiles, n_cu, plan);
+    return launch_conv_as<EPI_DGRAD_PW>(dtype, a, N, ntiles, n_cu, plan);
   }
-  return dtype == NINT_BF16 ? launch_conv<NINT_BF16, EPI_DGRAD>(a, N, ntiles, n_cu, plan)
-                            : launch_conv<NINT_F32, EPI_DGRAD>(a, N, ntiles, n_cu, plan);
+  return launch_conv_as<EPI_DGRAD>(dtype, a, N, ntiles, n_cu, plan);
 }
 
 extern "C" int nint_cell_bwd_fused(const nint_layer* ly, const nint_geom* g, int dtype, int N, const void* dG_next, void* dx,

@@ -330,7 +330,7 @@ bool nint_internal_stencil_holds(const nint_layer* ly);
 int nint_internal_stencil_lstm(const nint_layer* ly, const nint_geom* g, int dtype, int N, const void* x_slab,
                                const void* h_prev, const float* c_prev, void* h_out, float* c_out, void* gates_out,
                                void* stream);
-#define NINT_MULTI_MAX 4  // problems per merged grid (conv_lstm_multi_kernel / conv_bwd_multi_kernel)
+#define NINT_MULTI_MAX 4  // problems per merged grid (the kernels of NINT_MULTI_KERNELS, csrc/conv_igemm.hip)
 struct CellFwdJob {      // one gate launch (nint_cell_fwd's arguments)
   const nint_layer* ly; const void* x_slab; const void* h_prev; const float* c_prev; void* h_out; float* c_out; void* gates_out;
 };
@@ -342,6 +342,8 @@ struct ConvPlan {
   int carrier;                                       // NINT_K_CONV_IGEMM; NINT_K_STENCIL / NINT_K_TINY with NINT_E_SHAPE: no planned form
 };
 constexpr int conv_variant(int EPI, int WN, int WK, int NTW, int MT) { return EPI * 10000 + WN * 1000 + WK * 100 + NTW * 10 + MT / 4; }
+struct ConvShape { int epi, wn, wk, ntw, mt; };      // ... and its inverse (the bodies and their carriers: csrc/conv_igemm.hip, "the shape table")
+constexpr ConvShape conv_shape(int v) { return {v / 10000, v / 1000 % 10, v / 100 % 10, v / 10 % 10, 4 * (v % 10)}; }
 int nint_internal_n_cu();                            // CUs of the current device; 256 where the lookup fails
 // n_cu: the CU count the launch-shape rules use (<= 0: looked up here)
 int nint_internal_cell_fwd_plan(const CellFwdJob* j, const nint_geom* g, int dtype, int N, int n_cu, ConvPlan* plan);

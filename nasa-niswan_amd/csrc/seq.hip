@@ -547,7 +547,8 @@ extern "C" int nint_debug_seq_plan(const nint_seq* s, int bwd, nint_launch_rec* 
       if (st.kind == STEP_CONV || in_grid) {
         const ConvArgs& a = in_grid ? st.multi.m.a[q] : st.conv.a;
         const int v = in_grid ? st.multi.m.variant[q] : st.conv.variant;
-        r.epi = v / 10000; r.wn = v / 1000 % 10; r.wk = v / 100 % 10; r.ntw = v / 10 % 10; r.mt = 4 * (v % 10);    // (conv_variant)
+        const ConvShape sh = conv_shape(v);
+        r.epi = sh.epi; r.wn = sh.wn; r.wk = sh.wk; r.ntw = sh.ntw; r.mt = sh.mt;
         r.strip = a.tiles_x2 > 0; r.nt_begin = a.nt_begin;
         r.gx = in_grid ? st.multi.m.nbx[q] : st.conv.gx; r.gy = in_grid ? st.multi.m.nwg[q] / st.multi.m.nbx[q] : st.conv.gy;
       }

@@ -4,11 +4,11 @@ A plain-Python restatement of the host arithmetic that picks each launch, in the
 calls, no library calls.  It restates
 
 * ``cell_fwd`` (csrc/conv_igemm.hip): the VALU stencil kernel, the dense-K kernel (csrc/tiny_gemm.hip) or ``launch_conv``;
-* ``launch_conv``: the K-steps, the 4-row rule (``mt4``), the small-batch rule ``2*N*tiles8 < 3*n_cu``, the column-split rules
-  ``few4`` / ``few2`` / ``few(cols)`` and the ntiles divisibility ladder 16/12/8/6/4/3/2/1;
+* ``launch_conv``: the K-steps, the 4-row rule (``mt4``), the small-batch rule ``2*N*tiles8 < 3*n_cu``, the column-split rule
+  (``few4`` / ``few2`` of the gates, ``few(cols)`` of the dgrad launches) and the ntiles divisibility ladder 16/12/8/6/4/3/2/1;
 * ``launch_cfg``: the merged leftover strip (8-row tiles, 1..4 leftover rows, two or more column tiles) and the grid size;
 * ``nint_internal_conv_dgrad``: ``nt_begin`` and the n-tile count from ``need_dx`` / the fused forms;
-* ``nint_internal_conv_multi``: which merged kernel holds a set of planned launches, or none;
+* ``nint_internal_multi_plan``: which merged kernel holds a set of planned launches, or none;
 * ``nint_seq_fwd`` / ``nint_seq_bwd`` (csrc/seq.hip): the wavefront grids, ``rows8``, ``fused[l]`` (K-steps <= 24 or the
   ``fuse_bwd`` mask), ``lo`` / ``loc``, ``merge`` / ``merge_d`` / ``merge_p``, the held-back bottom dgrad and the pointwise
   pass that rides behind the top layer's fused step.
@@ -49,7 +49,7 @@ INSTANTIATED = frozenset(
     + [(dt, epi, wn, wk, ntw, mt) for dt in ("bf16", "f32") for epi in ("DGRAD", "DGRAD_PW")
        for _, (wn, wk, ntw) in DGRAD_LADDER for mt in (4, 8)])
 
-# nint_internal_conv_multi: the (EPI, WN, WK, NTW, MT) the merged kernels hold (multi_holds)
+# nint_internal_multi_plan: the (EPI, WN, WK, NTW, MT) the merged kernels hold (the union of the library's case lists, restated)
 MULTI_HOLDS = frozenset([("LSTM", 4, 1, 4, 8), ("LSTM", 2, 2, 4, 8), ("LSTM", 1, 4, 4, 8), ("LSTM", 4, 1, 4, 4),
                          ("LSTM", 2, 2, 4, 4), ("LSTM", 1, 4, 4, 4), ("DGRAD", 1, 4, 4, 8), ("DGRAD", 1, 4, 4, 4),
                          ("DGRAD", 1, 4, 2, 4), ("DGRAD", 2, 2, 3, 8), ("DGRAD", 2, 2, 3, 4), ("DGRAD", 1, 4, 3, 4),
@@ -224,8 +224,9 @@ def dgrad_launch(ly: Layer, dt: str, N: int, H: int, W: int, tile_rows: int, dx:
 
 
 def multi_kernel(convs: Sequence[Conv], pw: bool = False) -> Optional[str]:
-    """nint_internal_conv_multi: the merged kernel that holds these planned launches (pw: plus a pointwise pass), or None
-    (NINT_E_SHAPE: the caller enqueues them one by one)"""
+    """nint_internal_multi_plan: the merged kernel that holds these planned launches (pw: plus a pointwise pass), or None
+    (NINT_E_SHAPE: the caller enqueues them one by one).  The library takes the first kernel whose case list holds them all;
+    this states the same choice by its consequences, and tests/test_launch_plan_cpu.py compares the two on every list."""
     vs = [c.variant for c in convs]
     if not 1 <= len(vs) <= MULTI_MAX or any(v not in MULTI_HOLDS for v in vs):
         return None

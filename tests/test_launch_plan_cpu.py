@@ -1,5 +1,5 @@
 """oracle/launch_plan.py (the launch ledger) pinned on rows derived by hand from csrc/conv_igemm.hip (cell_fwd, launch_conv,
-launch_cfg, nint_internal_conv_dgrad, nint_internal_conv_multi) and csrc/seq.hip (nint_seq_fwd, nint_seq_bwd); the sweep of
+launch_cfg, nint_internal_conv_dgrad, nint_internal_multi_plan) and csrc/seq.hip (nint_seq_fwd, nint_seq_bwd); the sweep of
 every layer shape the engine accepts, with a reason for each instantiated body it never selects; and the coverage of the GPU
 audit: the cases of tests/test_gpu_stored_audit.py and tests/test_gpu_launch_audit.py (their module-level tables, read without
 a GPU) together run every reachable body, every 8-row body also with the merged leftover strip, and every host kernel.
@@ -262,6 +262,42 @@ def test_ledger_equals_the_library_planner(name, case):
     for (pass_, idx), ps in groups.items():
         merged = ps[0].kernel not in ("conv_igemm", "stencil", "tiny", "pointwise")
         assert (len(ps) > 1) == merged and len({p.kernel for p in ps}) == 1, (pass_, idx, ps)
+
+
+def test_multi_carrier_equals_the_ledger_on_every_list():
+    """Which merged kernel carries a set of launches, on EVERY list and not only on the ones a schedule produces: the library's
+    rule (nint_debug_multi_carrier: the first kernel whose case list holds every launch, nint_internal_multi_plan) against the
+    ledger's independent statement of it (LP.multi_kernel: rows8 / dpair / the two 4-row shapes / the rider rule).  Every
+    multiset of 1-3 of the 38 bodies launch_conv instantiates (dtype aside) and every multiset of 4 of the 14 a merged kernel
+    holds (a list with any other body has no carrier at any length), each with and without the pointwise rider."""
+    from itertools import combinations_with_replacement as multisets
+    from nasa_niswan_amd import _lib
+    lib = _lib.load()
+    variants = sorted({b[1:] for b in LP.INSTANTIATED})
+    assert len(variants) == 38 and len(LP.MULTI_HOLDS) == 14 and LP.MULTI_HOLDS <= set(variants)
+    lists = [vs for n in (1, 2, 3) for vs in multisets(variants, n)] + list(multisets(sorted(LP.MULTI_HOLDS), 4))
+
+    def carrier(vs, pw):
+        flat = [x for (epi, wn, wk, ntw, mt) in vs for x in (EPIS.index(epi), wn, wk, ntw, mt)]
+        return lib.nint_debug_multi_carrier((C.c_int32 * len(flat))(*flat), len(vs), int(pw))
+
+    checked, seen = 0, set()
+    for vs in lists:
+        convs = [LP.Conv(("bf16",) + v, False, 1, 1, 0) for v in vs]
+        for pw in (False, True):
+            want = LP.multi_kernel(convs, pw)
+            got = carrier(vs, pw)
+            assert got == (_lib.NINT_E_SHAPE if want is None else LP.CARRIERS.index(want)), (vs, pw, got, want)
+            checked += 1
+            seen.add(want)
+    assert checked == 26078
+    assert seen == {None, "conv_lstm_multi", "conv_lstm_multi8", "conv_bwd_multi", "conv_bwd_multi8", "conv_dgrad_multi8"}
+    one = ("LSTM", 1, 4, 4, 4)
+    assert carrier((), False) == _lib.NINT_E_SHAPE and carrier((one,) * 5, False) == _lib.NINT_E_SHAPE
+    assert carrier((one,) * 4, False) == LP.CARRIERS.index("conv_lstm_multi")
+    assert lib.nint_debug_multi_carrier(None, 1, 0) == _lib.NINT_E_SHAPE
+    # a tuple that is no body (conv_variant would alias it onto one): refused, not looked up
+    assert carrier((("LSTM", 1, 4, 4, 5),), False) == carrier((("LSTM", 11, 4, 4, 4),), False) == _lib.NINT_E_SHAPE
 
 
 def test_backward_plan_checks_the_weight_gradient_workspace():
