@@ -239,7 +239,10 @@ int nint_pack_compact_add(const float* src, void* dst, int N, int C, int Cp, int
 /* 1 when horizontally folding the x source of a (first) layer lowers its number of K-steps:
  * ceil(k*Cx / KC) * k < ceil(Cx / KC) * k * k  (see nint_layer.xfold); pure host arithmetic */
 int nint_xfold_pays(int Cx, int k, int dtype);
-/* bytes to reserve for EACH of the packed fwd / dgrad weight images of one layer */
+/* bytes to reserve for EACH of the packed fwd / dgrad weight images of one layer.
+ * Memory contract: a buffer of exactly this size is enough -- no kernel stores outside it, and no result
+ * depends on a byte outside it.  The size is the dgrad image's: a folded forward image ends short of it and the extra images of
+ * tiny layers leave gaps; those bytes are never written and never read (the caller zero-fills both buffers once). */
 size_t nint_packed_weight_bytes(int Cx, int Ch, int k, int dtype, int xfold);
 /* W (4Ch, Cx+Ch, k, k) f32 OIHW + bias (4Ch) as nn.Conv2d stores them (model.py:207-211)
  * -> Wf, Wd (fragment order, ET) and bias_p.  Must be re-run after every optimiser step. */
@@ -289,7 +292,10 @@ int nint_cell_bwd_fused(const nint_layer* ly, const nint_geom* g, int dtype, int
 
 /* conv backward-weight of model.py:220 over N = T*B images in ONE launch (all time steps):
  * dW[o][c][ky][kx] = sum_n,y,x dG[n,y,x,o] * cat[n,y+ky-p,x+kx-p,c] ; db[o] = sum dG.
- * partial: split-K workspace of nint_wgrad_workspace_bytes(). */
+ * partial: split-K workspace of nint_wgrad_workspace_bytes().
+ * Memory contract: a workspace of exactly this size is enough for every N and grid (the split count the
+ * query assumes is an upper bound; a smaller workspace is NINT_E_ARG before any launch) -- no kernel stores outside it, and
+ * no result depends on a byte outside it or on its prior contents. */
 size_t nint_wgrad_workspace_bytes(const nint_layer* ly, int dtype, int n_cu);
 int nint_conv_wgrad(const nint_layer* ly, const nint_geom* g, int dtype, int N,
                     const void* dG, const void* x_slab, const void* h_slab,
@@ -387,7 +393,9 @@ int nint_head_bwd_seq_acc(const void* h_slab, int B, int T, int Ch, int Chp, int
  * crop), may be NULL; stats (NINT_LOSS_STATS doubles, accumulated, caller zeroes): [0..4] pooled sums
  * sum (y-p)^2, sum |y-p|, sum y, sum y^2, count; [5..7] the reference's per-batch statistics: sum over calls
  * of the loss, sum over calls of sklearn-style r2_score(y, pred) of that call, number of calls -- the
- * device-side accumulators replacing loss.item() / r2_score(...cpu()) of train.py:113-117, utils.py:73-75. */
+ * device-side accumulators replacing loss.item() / r2_score(...cpu()) of train.py:113-117, utils.py:73-75.
+ * Memory contract: loss_out of exactly NINT_LOSS_SCRATCH_FLOATS floats is enough -- no kernel stores outside
+ * it, and no result depends on a byte outside it or on its prior contents. */
 #define NINT_LOSS_SCRATCH_FLOATS 8194
 #define NINT_LOSS_STATS 8
 int nint_loss_mse_l1_crop(const float* pred, const float* y, float* dpred, float* loss_out, double* stats,
@@ -485,7 +493,9 @@ typedef struct nint_loss_spec {
  * all three zero; huber != 0 with !(delta > 0) or a non-finite delta; ow with now != O (T*O), !(osum > 0) or a non-finite
  * osum; now != 0 with ow == NULL; a map with !(wsum > 0) or a non-finite wsum.  NINT_E_ALIGN: the twin's alignment checks;
  * ow not 4-byte aligned.  NINT_E_SHAPE: the fused entries, exactly where their twins return it.  ow and the map are read
- * from global memory: no LDS on top of the twins'. */
+ * from global memory: no LDS on top of the twins'.
+ * Memory contract: loss_out of exactly NINT_LOSS_SPEC_SCRATCH_FLOATS floats is enough -- no kernel stores
+ * outside it, and no result depends on a byte outside it or on its prior contents. */
 #define NINT_LOSS_SPEC_SCRATCH_FLOATS 10242
 int nint_loss_crop_spec(const float* pred, const float* y, const float* wgt, double wsum, const nint_loss_spec* spec,
                         float* dpred, float* loss_out, double* stats, int N, int O, int H, int W, int oy, int ox, int Hc, int Wc,
@@ -521,6 +531,8 @@ int nint_head_loss_seq_fused_spec(const void* h_slab, int B, int T, int Ch, int 
 #define NINT_SKILL_SAMPLE 8   /* f64 per (sample, output): sum (y-p)^2, sum |y-p|, sum y, sum y^2, sum p, sum p^2,
                                  sum row_w*y, sum row_w*p */
 #define NINT_SKILL_MAX_N 64   /* samples per launch; larger N is split internally, as NINT_PRE_MAX_B is */
+/* Memory contract: a scratch of exactly nint_skill_scratch_bytes is enough (N beyond NINT_SKILL_MAX_N
+ * included) -- no kernel stores outside it, and no result depends on a byte outside it or on its prior contents. */
 size_t nint_skill_scratch_bytes(int N, int O, int Hc, int Wc);            /* host arithmetic only */
 /* pred (N,O,H,W) f32 already in memory; y (N,O,Hc,Wc) f32 and the crop window as in nint_loss_mse_l1_crop */
 int nint_skill_accum(const float* pred, const float* y, const int32_t* slot /*host, N entries, or NULL = all 0*/,
@@ -547,7 +559,9 @@ int nint_adam_flat(float* p, const float* g, float* m, float* v, size_t n, doubl
  * folds their partials; no atomics, so S depends on (g, n) only -- bit-identical run to run and on every rank that holds
  * the same bucket.  g needs 4-byte alignment only (dword loads).  scratch: nint_grad_norm_scratch_bytes() bytes, 8-byte
  * aligned.  n == 0: S = 0.  NINT_E_ARG: NULL g / out / scratch, a scratch that is too small; NINT_E_ALIGN: out or scratch
- * not 8-byte aligned -- both before any launch. */
+ * not 8-byte aligned -- both before any launch.
+ * Memory contract: a scratch of exactly nint_grad_norm_scratch_bytes() is enough, here and in the guarded
+ * Adam entries -- no kernel stores outside it, and no result depends on a byte outside it or on its prior contents. */
 #define NINT_GRAD_NORM_BLOCKS 256
 size_t nint_grad_norm_scratch_bytes(void);
 int nint_grad_norm_flat(const float* g, size_t n, float grad_scale, double* out, double* scratch, size_t scratch_bytes,

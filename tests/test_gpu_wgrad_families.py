@@ -48,7 +48,7 @@ def _run(lib, eng, ws, l, wide, N):
     dW = torch.full((4 * cfg.Ch, cfg.Cx + cfg.Ch, cfg.k, cfg.k), float("nan"), device="cuda")
     db = torch.full((4 * cfg.Ch,), float("nan"), device="cuda")
     # (a workspace of its own, sized for THIS family: the engine's was sized for the library's choice)
-    part = torch.full((lib.nint_wgrad_workspace_bytes(C.byref(ly), eng.dt, eng.n_cu) // 4 + 16,), float("nan"), device="cuda")
+    part = torch.full((lib.nint_wgrad_workspace_bytes(C.byref(ly), eng.dt, eng.n_cu) // 4,), float("nan"), device="cuda")
     g = ws.g
     halo_px = g.Hh * g.Wh
     es = eng.es

@@ -71,8 +71,17 @@ weighted cell (|dpred cnt / w| >= 1), its own prediction d + y read back from it
 d loss / d pred itself is gated (``dpred.N``): device_side.  Measured: 1 cell of 356 in seed 215 --train-opts #1 takes the
 weight gradient from 3.9e-2 to 4.4e-3 rel-L2 and the head's bias gradient from 1.9e-1 to 8.2e-4.  Every adopted cell is
 printed (count, largest |d|, bound), with --only also when there is none.
-``--force-dtype`` (with --only) replays a case in the other storage type."""
+``--force-dtype`` (with --only) replays a case in the other storage type.
+
+``--guarded`` (every mode): the device side of each case runs inside ``oracle.guarded_alloc.patched(mode="poison")`` -- every
+buffer the package allocates sits between guards of at least 64 KiB and four slab rows, ``torch.empty`` payloads hold 0xFF
+(NaN), the case's inputs and the module's parameters go into arenas of their own (``_dev``, ``_net``).  The draw, the oracle
+and the comparison are unchanged (``--list`` prints the same lines); every gate fails on a NaN in the device result
+(tests/test_guarded_alloc_cpu.py), so a poisoned byte that reaches a result is a miss, and after each case every guard byte is
+compared: a damaged guard prints the allocation's call site, the byte range and the case's replay line.  With ``--self-check``
+one guard byte is flipped by a host write after the first passing case and the check has to fail."""
 import argparse
+import contextlib
 import json
 import os
 import sys
@@ -90,6 +99,81 @@ OLD_MODES = ("plain", "trainer", "cell", "dataset")
 NEW_MODES = ("state", "train_opts", "stateful", "finetune")       # (a new mode goes LAST: case_rng keys a stream by position)
 LIM = {"f32": 1e-3, "bf16": 3e-2}
 LOSS_LIM = {"f32": 2e-6, "bf16": 2e-2}
+
+
+GUARD = None        # --guarded: the oracle.guarded_alloc.GuardedTorch of the case that is running
+
+
+def _dev(t):
+    """a host tensor of the case on the device; --guarded: in a guarded arena of its own"""
+    t = t.cuda()
+    return t if GUARD is None else GUARD.guard_copy(t)
+
+
+def _net(net):
+    """the module on the device; --guarded: every parameter in a guarded arena"""
+    net = net.cuda()
+    return net if GUARD is None else GUARD.guard_module(net)
+
+
+def case_row_stride(case) -> int:
+    """an upper bound of the widest slab row Wh * Cp * es of a case (the guards are four of them, at least 64 KiB): the halo row
+    W + 2 P, rounded up generously, times the widest channel count -- the folded input k * C, or the 4 * Ch16 gate columns --
+    in f32.  Pure."""
+    if case["mode"] == "dataset":
+        W, ks, C, hidden = case["gw"] + 2 * case["px"], [case["k0"]], 3 * case["levels"] + 2, [16]
+    else:
+        W, ks, C, hidden = case["W"], case["ks"], case["C"], case["hidden"]
+    return (W + 2 * max(k // 2 for k in ks) + 32) * max(max(ks) * C + 32, 4 * (max(hidden) + 16)) * 4
+
+
+def replay_line(args, case) -> str:
+    """the command that runs this case alone"""
+    flags = "".join(f" --{m.replace('_', '-')}" for m in ("big", "wide") if getattr(args, m))
+    mode = "" if args.mode == "plain" else " --" + args.mode.replace("_", "-")
+    return (f"python tools/fuzz_shapes.py --seed {args.seed} --n {max(args.n, case['it'] + 1)}{mode}{flags}"
+            f"{' --guarded' if args.guarded else ''} --only {case['it']}")
+
+
+@contextlib.contextmanager
+def guarded_case(args, case, state):
+    """--guarded: the device side of the case allocates through a poisoning GuardedTorch (the package's `torch` is the proxy
+    for the duration, the case's own tensors go through _dev / _net); afterwards every guard byte is compared.  A damaged
+    guard prints the case's replay line.  --self-check: after the first passing case one guard byte is flipped by a
+    host-issued write and verify() has to fail (`state["guard"]`)."""
+    global GUARD
+    if not args.guarded:
+        yield
+        return
+    from oracle import guarded_alloc as GA
+    with GA.patched(mode="poison", row_stride=case_row_stride(case)) as gt:
+        GUARD = gt
+        try:
+            yield
+            torch.cuda.synchronize()
+            try:
+                n = gt.verify()
+            except GA.GuardError as e:
+                print(f"GUARD HIT {case['tag']}\n{e}\nreplay: {replay_line(args, case)}", flush=True)
+                raise SystemExit(f"guard damaged in {case['tag']}; replay: {replay_line(args, case)}")
+            state["arenas"] = state.get("arenas", 0) + n
+            if args.guard_self_check and not state.get("guard"):
+                a = next(a for a in reversed(gt.arenas) if a.nbytes)
+                pos = a.front + a.nbytes + 1
+                a.arena[pos] ^= 0x01
+
+                def must_fail():
+                    try:
+                        gt.verify()
+                    except GA.GuardError as e:
+                        raise AssertionError(str(e))
+                expect_failure(case["tag"], "one flipped byte in a back guard", must_fail)
+                a.arena[pos] ^= 0x01
+                gt.verify()
+                state["guard"] = True
+        finally:
+            GUARD = None
+            gt.release()
 
 
 def _load():
@@ -458,16 +542,17 @@ def _head_cotangents(case, d):
 def state_device(case, d, params):
     L, T, B, H, W = case["L"], case["T"], case["B"], case["H"], case["W"]
     net = pkg.ConvLSTM(case["C"], case["hidden"], case["ks"], L, out_channels=case["out"], return_sequence=case["return_sequence"],
-                       compute_dtype=case["dtype"]).cuda()
+                       compute_dtype=case["dtype"])
+    net = _net(net)
     net.load_state_dict(params)
     h0, c0 = state_inputs(case, d)
     rs, res = case["return_sequence"], {}
     if case["chain"]:
-        st = None if h0 is None else [(h.cuda(), c.cuda()) for h, c in zip(h0, c0)]
+        st = None if h0 is None else [(_dev(h), _dev(c)) for h, c in zip(h0, c0)]
         with torch.no_grad():
-            dev = net(d["X"][:, :T].cuda(), st, return_state="device")[-1]
+            dev = net(_dev(d["X"][:, :T]), st, return_state="device")[-1]
             assert isinstance(dev, pkg.ConvLSTMState)
-            o2 = net(d["X"][:, T:].cuda(), dev, return_state=True)
+            o2 = net(_dev(d["X"][:, T:]), dev, return_state=True)
         torch.cuda.synchronize()
         res["pred"] = o2[0].cpu()
         if rs:
@@ -475,18 +560,18 @@ def state_device(case, d, params):
         for l, (h, c) in enumerate(o2[-1]):
             res[f"h_T.{l}"], res[f"c_T.{l}"] = h.cpu(), c.cpu()
         return res
-    Xd = d["X"].cuda().requires_grad_(True)
+    Xd = _dev(d["X"]).requires_grad_(True)
     st = None
     if h0 is not None:
-        hd, cd = [t.cuda().requires_grad_(True) for t in h0], [t.cuda().requires_grad_(True) for t in c0]
+        hd, cd = [_dev(t).requires_grad_(True) for t in h0], [_dev(t).requires_grad_(True) for t in c0]
         st = list(zip(hd, cd))
     o = net(Xd, st, return_state=True)
     pred, states = o[0], o[-1]
-    loss = (pred * d["R"].cuda()).sum()
+    loss = (pred * _dev(d["R"])).sum()
     if rs:
-        loss = loss + (o[1] * d["RS"].cuda()).sum()
+        loss = loss + (o[1] * _dev(d["RS"])).sum()
     for l, (h, c) in enumerate(states):
-        loss = loss + (h * d[f"Rh.{l}"].cuda()).sum() + (c * d[f"Rc.{l}"].cuda()).sum()
+        loss = loss + (h * _dev(d[f"Rh.{l}"])).sum() + (c * _dev(d[f"Rc.{l}"])).sum()
     loss.backward()
     torch.cuda.synchronize()
     res["pred"] = pred.detach().cpu()
@@ -718,9 +803,9 @@ def train_opts_oracle(case, d, params, corrupt=None, dp_dev=None):
 
 def train_opts_device(case, d, params, ref):
     from nasa_niswan_amd.trainer import FusedTrainer
-    net = pkg.ConvLSTM(case["C"], case["hidden"], case["ks"], case["L"], out_channels=case["out"], compute_dtype=case["dtype"]).cuda()
+    net = _net(pkg.ConvLSTM(case["C"], case["hidden"], case["ks"], case["L"], out_channels=case["out"], compute_dtype=case["dtype"]))
     net.load_state_dict(params)
-    mg = None if case["clip"] is None else case["clip"] * ref["_norm"]
+    mg =None if case["clip"] is None else case["clip"] * ref["_norm"]
     tr = FusedTrainer(net, lr=1e-3, halo=tuple(case["halo"]), sequence_loss=case["sequence_loss"], loss_weights=weights_of(case, d),
                       max_grad_norm=mg, bptt_segments=case["n"], accumulate_steps=case["acc"])
     res = {"_dp": []}
@@ -729,7 +814,7 @@ def train_opts_device(case, d, params, ref):
     per_window = case["dtype"] == "bf16" and case["n"] == 1
     wins, before = [], None
     for j in range(case["acc"]):
-        res[f"loss.{j}"] = float(tr.step(d[f"X.{j}"].cuda(), d[f"y.{j}"].cuda()))
+        res[f"loss.{j}"] = float(tr.step(_dev(d[f"X.{j}"]), _dev(d[f"y.{j}"])))
         res["_dp"].append(tr._dpred.detach().clone().cpu())
         res[f"dpred.{j}"] = res["_dp"][-1].view(-1, case["out"], case["H"], case["W"])
         if per_window:
@@ -759,14 +844,14 @@ def stateful_run(case, d, params, self_check):
     (worst figure, True if the self-check was tried)"""
     from nasa_niswan_amd.trainer import FusedTrainer
     L, B, halo, dtype, tag = case["L"], case["B"], tuple(case["halo"]), case["dtype"], case["tag"]
-    net = pkg.ConvLSTM(case["C"], case["hidden"], case["ks"], L, out_channels=case["out"], compute_dtype=dtype).cuda()
+    net = _net(pkg.ConvLSTM(case["C"], case["hidden"], case["ks"], L, out_channels=case["out"], compute_dtype=dtype))
     net.load_state_dict(params)
     tr = FusedTrainer(net, lr=1e-3, halo=halo, stateful=True, bptt_segments=case["n"])
     worst, tried = 0.0, False
     p, h0, c0 = params, None, None
     for j in range(2):
         reset = case["reset"] if j == 1 else None
-        res = {"loss": float(tr.step(d[f"X.{j}"].cuda(), d[f"y.{j}"].cuda(), reset=reset))}
+        res = {"loss": float(tr.step(_dev(d[f"X.{j}"]), _dev(d[f"y.{j}"]), reset=reset))}
         torch.cuda.synchronize()
         res.update(_named_grads(net, tr.flat))
         dp_dev = tr._dpred.detach().clone().cpu()
@@ -820,7 +905,7 @@ def finetune_run(case, d, params, self_check, tried):
     from nasa_niswan_amd.trainer import FusedTrainer
     L, f, wd, scales, halo, dtype, tag = case["L"], case["f"], case["wd"], case["scales"], tuple(case["halo"]), case["dtype"], case["tag"]
     lr, sentinel = 1e-3, 4321.5
-    net = pkg.ConvLSTM(case["C"], case["hidden"], case["ks"], L, out_channels=case["out"], compute_dtype=dtype).cuda()
+    net = _net(pkg.ConvLSTM(case["C"], case["hidden"], case["ks"], L, out_channels=case["out"], compute_dtype=dtype))
     net.load_state_dict(params)
     tr = FusedTrainer(net, lr=lr, halo=halo, freeze_layers=f, weight_decay=wd, layer_lr_scale=scales)
     names = [k for k, _ in net.named_parameters()]
@@ -858,7 +943,7 @@ def finetune_run(case, d, params, self_check, tried):
         view = lambda buf: {k: buf[o:o + p.numel()].view(p.shape).detach().clone().cpu() for (k, p), o in zip(net.named_parameters(), tr.flat.offsets)}
         p0, m0, v0 = view(tr.flat.data), view(tr.optimizer.exp_avg), view(tr.optimizer.exp_avg_sq)
         X, y = d[f"X.{j}"], d[f"y.{j}"]
-        loss = float(tr.step(X.cuda(), y.cuda()))
+        loss = float(tr.step(_dev(X), _dev(y)))
         torch.cuda.synchronize()
         leaf = {k: v.clone().requires_grad_(not frozen(k)) for k, v in p0.items()}
         lo = O.loss_mse_l1(y, O.crop_pred(O.convlstm_forward(X, leaf), halo, y.shape[-2:]))
@@ -917,6 +1002,7 @@ def parse(argv=None):
     ap.add_argument("--stateful", action="store_true", help="two chunks through FusedTrainer(stateful=True), the second with a drawn reset, each checked from the state and parameters the device held")
     ap.add_argument("--finetune", action="store_true", help="two steps of FusedTrainer with a drawn number of frozen layers (0 ... all), weight decay and per-layer lr scales: loss and trained gradients against CPU autograd, the update against torch.optim.AdamW, the frozen regions untouched")
     ap.add_argument("--self-check", action="store_true", help="with --state / --train-opts / --stateful / --finetune: corrupt the reference after the first passing case and require the comparison to fail")
+    ap.add_argument("--guarded", action="store_true", help="every mode: the device side of each case allocates through oracle/guarded_alloc.py in poison mode (guards around every buffer, `empty` payloads 0xFF), its inputs and parameters in arenas of their own; the comparison stays what it is and every guard byte is checked after each case.  With --self-check (any mode): one guard byte is flipped after the first passing case and the check has to fail (the reference is then not corrupted)")
     ap.add_argument("--list", action="store_true", help="print the drawn cases as JSON lines and exit (no GPU, the package is not imported)")
     ap.add_argument("--only", type=int, default=-1, help="replay the random stream up to this iteration and run it alone, printing every tensor's error")
     ap.add_argument("--force-wave", type=int, default=None, help="with --only: nint_seq.wave for the replayed case instead of the rotation's value")
@@ -926,8 +1012,12 @@ def parse(argv=None):
     if len(modes) > 1 and not all(m in OLD_MODES for m in modes):
         ap.error("one of --state / --train-opts / --stateful / --finetune at a time, and none of the other modes with it")
     args.mode = modes[0] if modes else "plain"          # (--dataset before --cell before --trainer, as ever)
-    if args.self_check and args.mode not in NEW_MODES:
-        ap.error("--self-check needs --state, --train-opts, --stateful or --finetune")
+    if args.self_check and args.mode not in NEW_MODES and not args.guarded:
+        ap.error("--self-check needs --state, --train-opts, --stateful or --finetune (or --guarded)")
+    # --guarded --self-check is the guard's own self-check; the reference stays what it is
+    args.guard_self_check = args.self_check and args.guarded
+    if args.guard_self_check:
+        args.self_check = False
     return args
 
 
@@ -966,7 +1056,7 @@ def run_old(case, d, args, worst):
         return
     if args.mode == "cell":
         Ch, k, has_bias = hidden[0], ks[0], case["has_bias"]
-        cell = pkg.ConvLSTMCell(C, Ch, k, bias=has_bias, compute_dtype=dtype).cuda()
+        cell = _net(pkg.ConvLSTMCell(C, Ch, k, bias=has_bias, compute_dtype=dtype))
         Wt = d["Wt"] / np.sqrt((C + Ch) * k * k)
         bt = d["bt"] * 0.2 if has_bias else None
         with torch.no_grad():
@@ -974,9 +1064,9 @@ def run_old(case, d, args, worst):
             if has_bias:
                 cell.conv.bias.copy_(bt)
         x, h, c, gh, gc = d["x"], d["h"] * 0.5, d["c"], d["gh"], d["gc"]
-        xd, hd, cd = (t.cuda().requires_grad_(True) for t in (x, h, c))
+        xd, hd, cd = (_dev(t).requires_grad_(True) for t in (x, h, c))
         h1, c1 = cell(xd, (hd, cd))
-        ((h1 * gh.cuda()).sum() + (c1 * gc.cuda()).sum()).backward()
+        ((h1 * _dev(gh)).sum() + (c1 * _dev(gc)).sum()).backward()
         torch.cuda.synchronize()
         xo, ho, co = (t.clone().requires_grad_(True) for t in (x, h, c))
         Wo = Wt.clone().requires_grad_(True)
@@ -1010,10 +1100,10 @@ def run_old(case, d, args, worst):
         hy, hx = case["halo"]
         params = O.synth_params(C, hidden, ks, L, out_channels=out, seed=it)
         X, y = d["X"], d["y"]
-        net = pkg.ConvLSTM(C, hidden, ks, L, out_channels=out, compute_dtype=dtype).cuda()
+        net = _net(pkg.ConvLSTM(C, hidden, ks, L, out_channels=out, compute_dtype=dtype))
         net.load_state_dict(params)
         tr = FusedTrainer(net, lr=1e-3, halo=(hy, hx))
-        loss = float(tr.step(X.cuda(), y.cuda()))
+        loss = float(tr.step(_dev(X), _dev(y)))
         torch.cuda.synchronize()
         _, _, lo, _, grads = O.train_step(params, None, X, y, lr=1e-3, halo=(hy, hx))
         assert abs(loss - lo) <= LOSS_LIM[dtype] * abs(lo), (tag, "loss", loss, lo)
@@ -1031,11 +1121,11 @@ def run_old(case, d, args, worst):
         return
     params = O.synth_params(C, hidden, ks, L, out_channels=out, seed=it)
     X, wgt = d["X"], d["wgt"]
-    net = pkg.ConvLSTM(C, hidden, ks, L, out_channels=out, compute_dtype=dtype).cuda()
+    net = _net(pkg.ConvLSTM(C, hidden, ks, L, out_channels=out, compute_dtype=dtype))
     net.load_state_dict(params)
-    Xd = X.cuda().requires_grad_(True)
+    Xd = _dev(X).requires_grad_(True)
     pred = net(Xd)
-    (pred * wgt.cuda()).sum().backward()
+    (pred * _dev(wgt)).sum().backward()
     torch.cuda.synchronize()
     leaf = {k: v.clone().requires_grad_(True) for k, v in params.items()}
     Xo = X.clone().requires_grad_(True)
@@ -1150,10 +1240,11 @@ def main(argv=None):
         engine.FORCE_WAVE, engine.FORCE_TILE_ROWS, engine.FORCE_WIDE = case["wave"], case["rows"], case["wide"]
         try:
             d = draw_data(rng, case)
-            if new:
-                run_new(case, d, args, worst, tried)
-            else:
-                run_old(case, d, args, worst)
+            with guarded_case(args, case, tried):
+                if new:
+                    run_new(case, d, args, worst, tried)
+                else:
+                    run_old(case, d, args, worst)
         finally:
             engine.FORCE_WAVE, engine.FORCE_TILE_ROWS, engine.FORCE_WIDE = None, 0, 0
     if args.self_check:
@@ -1161,6 +1252,10 @@ def main(argv=None):
         missing = [f for f in want if not tried.get(f)]
         if missing:
             raise SystemExit(f"SELF-CHECK INCOMPLETE: no drawn case to try {missing} on (raise --n or change the seed)")
+    if args.guard_self_check and not tried.get("guard"):
+        raise SystemExit("SELF-CHECK INCOMPLETE: no case passed, so no guard byte was flipped")
+    if args.guarded:
+        print(f"guarded: {tried.get('arenas', 0)} allocations checked, every guard byte intact")
     print(f"wall {time.time() - t_start:.1f} s")
     print(f"{args.n} shapes ok; worst f32 max-rel {worst['f32']:.2e}, worst bf16 rel-L2 {worst['bf16']:.2e}")
 
