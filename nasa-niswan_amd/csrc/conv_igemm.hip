@@ -114,10 +114,16 @@ constexpr int xchg_rounds(int EPI, int WK, int NTW, int MT) {
 
 // The workgroup's work as a device function of (launch arguments, LDS base, workgroup coordinates): conv_igemm_kernel runs
 // it for blockIdx; conv_lstm_multi_kernel runs the gate launches of several layers (one wavefront step) in ONE grid.
-template <int DT, int EPI, int WN, int WK, int NTW, int MT>
+// FILL (template): pieces of the register-staged halo fill a wave holds at once; 0 = the LDS-DMA fill; -1 = by the body's own
+// registers.  The bodies of MT * NTW >= 32 accumulator tiles run two workgroups per CU on up to 256 registers: they stage 8
+// pieces (32 + 8 registers), 4 where the waves slice K (the compiler otherwise spills inside the K loop), and the K-sliced
+// fused step keeps the DMA for the same reason.  The others are allocated for three or four workgroups per CU and would lose
+// one (tools/regs.py, profiles/halo_fill_asm.txt).  The merged kernels of two workgroups per CU stage in every body they carry.
+template <int DT, int EPI, int WN, int WK, int NTW, int MT, int FILL = -1>
 __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, char* smem, const int bx_, const int by_, const int nbx_) {
   static_assert(WN * WK == 4, "four waves per workgroup");
   constexpr int BD = MT >= 8 ? BD_WIDE : BD_NARROW;
+  constexpr int FILL_PIECES = FILL >= 0 ? FILL : (MT * NTW < 32 ? 0 : (WK == 1 ? 8 : (EPI == EPI_DGRAD_PW ? 0 : 4)));
   static_assert(EPI != EPI_LSTM || NTW % 4 == 0, "LSTM epilogue needs the 4 gate tiles in one wave");
   constexpr int NTH = 256;
   constexpr int NTWG = WN * NTW;   // n-tiles per workgroup
@@ -249,11 +255,46 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, char* smem, c
     const int c_cnt = min(a.cpf, nchunks - c_begin);
     if (c_begin > 0) __syncthreads();          // every wave is done reading the previous image
     // ---- stage the halo tile for chunks [c_begin, c_begin+c_cnt): global -> LDS ----
+    // Two forms, the same image.  Where the body has registers to stage through (FILL_PIECES > 0) the fill goes in WHOLE
+    // 64-byte chunks: a piece is 16 consecutive halo pixels of one chunk, lanes 4j..4j+3 load the four 16-byte quarters of
+    // pixel j and write them to the four g planes: 16 cache lines per wave instruction.  The fill is bound by the lines an
+    // instruction touches, not by its bytes (tools/experiments/halo_fill_forms.hip).  A wave holds FILL_PIECES
+    // pieces in registers at a time; past the last piece it repeats its last one.  The barrier below waits for the writes.
+    // Pad pixels re-read pixel 0 in both forms (their LDS slots are never used).
+    if constexpr (FILL_PIECES > 0) {
+      constexpr int FB = FILL_PIECES;
+      const int nblk = NHPp >> 4, pieces = c_cnt * nblk;
+      for (int pb = wave; pb < pieces; pb += 4 * FB) {
+        u32x4_t fv[FB];
+        int fo[FB];
+#pragma unroll
+        for (int i = 0; i < FB; ++i) {
+          const int pc = min(pb + 4 * i, pieces - 1);                     // wave-uniform
+          // pc / nblk and hp / HWt by multiply-high with host-side magic numbers (exact for 16 * pc < 65536, divisor <= 4096):
+          // an integer division by a run-time value costs ~25 VALU instructions
+          const int cl = (int)__umulhi((unsigned)pc * 16u, magic_nhpp);
+          const int hp = (pc - cl * nblk) * 16 + (lane >> 2);
+          const int hs = hp < NHP ? hp : 0;
+          const int q = lane & 3;
+          const int hy = (int)__umulhi((unsigned)hs, magic_hwt);
+          const int hx = hs - hy * HWt;
+          const int c = c_begin + cl;
+          const char* src = (c < a.nchunk0)
+              ? base0 + ((long)hy * a.Wh + hx) * a.pix_stride0 + c * 64 + q * 16
+              : base1 + ((long)hy * a.Wh + hx) * a.pix_stride1 + (c - a.nchunk0) * 64 + q * 16;
+          // (default cache policy: neighbouring tiles re-read the halo pixels; a non-temporal fill measured -8 % on the step)
+          fv[i] = *(const u32x4_t*)src;
+          fo[i] = (cl * 4 + q) * plane + hp * 16;
+        }
+#pragma unroll
+        for (int i = 0; i < FB; ++i) *(u32x4_t*)(smem + fo[i]) = fv[i];
+      }
+    } else {
+    // Bodies without that room (the 4-row tiles, three and four workgroups per CU) keep the LDS-DMA fill: one
+    // global_load_lds_dwordx4 per wave moves 64 consecutive 16-byte units of the image, i.e. 64 pixels of one (chunk, g)
+    // plane (wave-uniform LDS base + lane*16; the SOURCE address is per lane): no VGPR round trip, the whole image in
+    // flight at once, 64 cache lines per instruction.  a_units is a multiple of 64.  The barrier below drains the DMA.
     const int a_units = c_cnt * 4 * NHPp;
-    // LDS-DMA fill: one global_load_lds_dwordx4 per wave moves 64 consecutive 16-byte units of the image
-    // (wave-uniform LDS base + lane*16; the SOURCE address is per lane), no VGPR round trip, so the whole
-    // image is in flight at once instead of FB loads per thread.  Units of the pad pixels re-read pixel 0
-    // (their LDS slots are never used); a_units is a multiple of 64.  The barrier below drains the DMA.
     for (int ub = wave * 64; ub < a_units; ub += 4 * 64) {
       const int u = ub + lane;
       // u / NHPp and hp / HWt by multiply-high with host-side magic numbers (exact for u < 65536, divisor <= 4096):
@@ -271,6 +312,7 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, char* smem, c
       __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
                                        (__attribute__((address_space(3))) void*)(smem + (size_t)ub * 16), 16, 0, 0);
     // (default cache policy: neighbouring tiles re-read the halo pixels; a non-temporal fill measured -8 % on the step)
+    }
     }
     // K-steps of this fill in two SEGMENTS: chunks of a horizontally folded source 0 (nint_layer.xfold: channel =
     // (kx, c), so only the k vertical taps of the halo tile's centre column remain: kx0 = 1) and all other chunks
@@ -747,7 +789,7 @@ __global__ __launch_bounds__(256, MT >= 8 ? 2 : (xchg_rounds(EPI, WK, NTW, MT) =
 #define NINT_PW_U 2
 #endif
 #define NINT_MULTI_CASE(EPI_, WN_, WK_, NTW_, MT_) \
-  case conv_variant(EPI_, WN_, WK_, NTW_, MT_): conv_igemm_body<DT, EPI_, WN_, WK_, NTW_, MT_>(a, smem, bx, by, nbx); break;
+  case conv_variant(EPI_, WN_, WK_, NTW_, MT_): conv_igemm_body<DT, EPI_, WN_, WK_, NTW_, MT_, fill>(a, smem, bx, by, nbx); break;
 #define NINT_MULTI_KERNEL(NAME, CARRIER, WGS, PW, CASES)                                                          \
   template <int DT>                                                                                               \
   __global__ __launch_bounds__(256, WGS) void NAME(ConvMulti m) {                                                 \
@@ -758,6 +800,7 @@ __global__ __launch_bounds__(256, MT >= 8 ? 2 : (xchg_rounds(EPI, WK, NTW, MT) =
       }                                                                                                           \
     }                                                                                                             \
     extern __shared__ __attribute__((aligned(16))) char smem[];                                                   \
+    constexpr int fill = (WGS) <= 2 ? 8 : 0;     /* (conv_igemm_body's FILL: a 256-register kernel stages in every body) */ \
     int i = 0;                                                                                                    \
     _Pragma("unroll") for (int q = 1; q < NINT_MULTI_MAX; ++q) i += (q < m.n && (int)blockIdx.x >= m.begin[q]) ? 1 : 0; \
     const int b = blockIdx.x - m.begin[i];                                                                        \
