@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define NINT_VERSION 112
+#define NINT_VERSION 113
 
 enum { NINT_F32 = 0, NINT_BF16 = 1 };
 
@@ -310,7 +310,7 @@ int nint_seq_bwd(const nint_seq* s /*host*/, void* stream);
 /* The launch plan of a pass, for tests and tools (host only: nothing is enqueued, no pointer is dereferenced).  Both drivers
  * first PLAN a pass into an ordered list of launches and then enqueue that list; this entry runs the same argument checks and
  * the same planner as nint_seq_fwd (bwd = 0) / nint_seq_bwd (bwd = 1: the BPTT chain, without the weight-gradient
- * reductions behind it) and writes one record per conv / pointwise problem in enqueue order into out[0 .. cap).  Returns the
+ * reductions behind it: nint_debug_wgrad_plan) and writes one record per conv / pointwise problem in enqueue order into out[0 .. cap).  Returns the
  * number of problems of the pass (which may exceed cap) or a negative NINT_E_* code. */
 enum { NINT_K_CONV_IGEMM = 0, NINT_K_CONV_LSTM_MULTI = 1, NINT_K_CONV_LSTM_MULTI8 = 2, NINT_K_CONV_BWD_MULTI = 3,
        NINT_K_CONV_BWD_MULTI8 = 4, NINT_K_CONV_DGRAD_MULTI8 = 5, NINT_K_STENCIL = 6, NINT_K_TINY = 7, NINT_K_POINTWISE = 8 };
@@ -335,6 +335,31 @@ int nint_debug_seq_plan(const nint_seq* s /*host*/, int bwd, nint_launch_rec* ou
  * pointwise backward pass -- or NINT_E_SHAPE where no merged kernel holds them all (also n outside [1, 4], or a tuple that is
  * no body).  It is the planner's own choice: the drivers' plans go through the same function. */
 int nint_debug_multi_carrier(const int32_t* shapes /*host, n x 5*/, int n, int with_pw);
+/* The weight-gradient plan of ONE layer, for tests and tools (host arithmetic only, like nint_debug_seq_plan): the planner of
+ * nint_conv_wgrad / nint_seq_bwd run for N images, the h source skipping the first h_skip of them, against a made-up workspace
+ * of exactly nint_wgrad_workspace_bytes.  Returns NINT_OK or the planner's own NINT_E_* code (*out is then unspecified). */
+typedef struct nint_wgrad_src_rec {       /* one source (x or h) of a launch */
+  int32_t CB, JG, TG;                     /* channel blocks, columns per block slab (incl. the db column), column groups */
+  int32_t nblk, ntiles, tiles_per_split, want_db;
+  int32_t is_h;
+  int64_t off;                            /* its split-K slabs: float offset from the workspace base */
+} nint_wgrad_src_rec;
+typedef struct nint_wgrad_launch_rec {
+  int32_t family;                         /* waves per workgroup: 4 (wgrad_kernel) or 8 (wgrad_wide_kernel) */
+  int32_t KS, NTC, JW, KX;                /* the instance: kernel size, channel tiles per block (8-wave: per workgroup),
+                                           * columns per wave (8-wave: 0), horizontal taps */
+  int32_t nparts;                         /* sources in this launch: src[0 .. nparts) */
+  int32_t gx, gy, block, lds;             /* grid (gx = splits), threads, dynamic LDS bytes */
+  nint_wgrad_src_rec src[2];
+} nint_wgrad_launch_rec;
+typedef struct nint_wgrad_plan_rec {
+  int32_t n_launch, n_fold;
+  int32_t fold_grid, fold_block;          /* the one launch that folds every slab */
+  nint_wgrad_launch_rec launch[2];
+  struct { int32_t blk_begin, splits, waves; } fold[2];
+} nint_wgrad_plan_rec;
+int nint_debug_wgrad_plan(const nint_layer* ly, const nint_geom* g, int dtype, int N, int h_skip, int n_cu,
+                          nint_wgrad_plan_rec* out /*host*/);
 
 /* ---- 1x1 head (model.py:251,274) ------------------------------------------------------------ */
 /* ONE rule decides which arithmetic every head entry below runs.  The "staged" bodies (weights zero-padded to [O][CHV] in

@@ -13,7 +13,7 @@ LIB_PATH = os.path.join(HERE, "libnint_hip.so")     # the one product library; n
 NINT_F32, NINT_BF16 = 0, 1
 NINT_OK, NINT_E_ARG, NINT_E_SHAPE, NINT_E_LDS, NINT_E_ALIGN = 0, -1, -2, -3, -4
 NINT_MAX_LAYERS = 8
-NINT_VERSION = 112     # include/nint.h NINT_VERSION: the library this binding was written against
+NINT_VERSION = 113     # include/nint.h NINT_VERSION: the library this binding was written against
 NINT_LOSS_SCRATCH_FLOATS = 8194
 NINT_LOSS_SPEC_SCRATCH_FLOATS = 10242     # the _spec loss entries: five doubles per workgroup
 NINT_LOSS_STATS = 8
@@ -54,6 +54,26 @@ class NintLaunchRec(C.Structure):
     """nint_launch_rec: one conv / pointwise problem of a planned pass (nint_debug_seq_plan)"""
     _fields_ = [(n, C.c_int32) for n in ("index", "bwd", "op", "layer", "t", "kernel", "dtype", "epi", "wn", "wk", "ntw", "mt",
                                          "strip", "gx", "gy", "nt_begin")]
+
+
+class NintWgradSrcRec(C.Structure):
+    """nint_wgrad_src_rec: one source (x or h) of a planned weight-gradient launch"""
+    _fields_ = [(n, C.c_int32) for n in ("CB", "JG", "TG", "nblk", "ntiles", "tiles_per_split", "want_db", "is_h")] + [("off", C.c_int64)]
+
+
+class NintWgradLaunchRec(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("family", "KS", "NTC", "JW", "KX", "nparts", "gx", "gy", "block", "lds")] + [
+        ("src", NintWgradSrcRec * 2)]
+
+
+class NintWgradFoldRec(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("blk_begin", "splits", "waves")]
+
+
+class NintWgradPlanRec(C.Structure):
+    """nint_wgrad_plan_rec: the weight-gradient launches and the fold of one layer (nint_debug_wgrad_plan)"""
+    _fields_ = [(n, C.c_int32) for n in ("n_launch", "n_fold", "fold_grid", "fold_block")] + [
+        ("launch", NintWgradLaunchRec * 2), ("fold", NintWgradFoldRec * 2)]
 
 
 class NintOptGroup(C.Structure):
@@ -102,6 +122,7 @@ SIGNATURES = {
     "nint_seq_bwd": (_I, [_PS, vp]),
     "nint_debug_seq_plan": (_I, [_PS, _I, C.POINTER(NintLaunchRec), _I]),
     "nint_debug_multi_carrier": (_I, [C.POINTER(C.c_int32), _I, _I]),
+    "nint_debug_wgrad_plan": (_I, [_PL, _PG, _I, _I, _I, _I, C.POINTER(NintWgradPlanRec)]),
     "nint_head_fwd": (_I, [vp, _I, _I, _I, _I, _I, vp, vp, vp, _PG, _I, vp]),
     "nint_head_bwd": (_I, [vp, _I, _I, _I, _I, _I, vp, vp, vp, vp, vp, _PG, _I, vp, _SZ, vp]),
     "nint_head_bwd_acc": (_I, [vp, _I, _I, _I, _I, _I, vp, vp, vp, vp, vp, _I, _PG, _I, vp, _SZ, vp]),

@@ -23,43 +23,82 @@
 #include <type_traits>
 #include "nint_common.h"
 
-template <int DT> struct WgTile;
-template <> struct WgTile<NINT_BF16> { static constexpr int PR = 4, RA = 160; static constexpr int rb(int ntc) { return ntc == 1 ? 32 : 96; } };
-template <> struct WgTile<NINT_F32> { static constexpr int PR = 2, RA = 320; static constexpr int rb(int ntc) { return ntc == 1 ? 64 : 192; } };
+// The two LDS images of a pixel tile (PR rows x 32 pixels of dG, the cat halo tile around them), shared by both kernel families:
+// RA bytes per dG pixel, RB per cat halo pixel (data + padding: conflict-free strides), counted in 16-byte units INCLUDING the
+// padding.  A tile is staged by LDS-DMA (global_load_lds_dwordx4: 64 consecutive units = one 1-KiB piece per wave instruction,
+// per-lane source address), no VGPR round trip, no ds_write pass; lanes that land on padding re-read the tile's first unit.
+// Kernel, launch record (WgRow.lds) and DESIGN.md 4.2 all read the sizes from here.
+template <int KS, int PR_, int RA_, int RB_> struct WgImage {
+  static constexpr int PR = PR_, RA = RA_, RB = RB_;
+  static constexpr int p = KS / 2, HWt = 32 + 2 * p, HHt = PR + 2 * p;
+  static constexpr int UA_ROW = RA / 16, NA_U = PR * 32 * UA_ROW;
+  static constexpr int UB_PIX = RB / 16, NB_U = HHt * HWt * UB_PIX, NB_U_PAD = (NB_U + 63) / 64 * 64;
+  static constexpr int a_bytes = PR * 32 * RA, b_bytes = NB_U_PAD * 16, buf_bytes = a_bytes + b_bytes;
+  static constexpr int NI_A = NA_U / 64, NI_B = NB_U_PAD / 64, NI = NI_A + NI_B;      // DMA pieces of a tile
+  static constexpr size_t lds = 2 * (size_t)buf_bytes;                                // two buffers: the next tile lands under this one's MFMAs
+  static_assert(NA_U % 64 == 0 && a_bytes % 1024 == 0, "whole DMA pieces");
+  static_assert(lds <= 160 * 1024, "two tile buffers in a CU's LDS");
+};
+// the 4-wave kernel's tile: 64 gate columns of dG (+ 32 / 64 bytes of padding), NTCT channel tiles of cat
+template <int DT, int KS, int NTCT>
+struct WgNarrow : WgImage<KS, DT == NINT_BF16 ? 4 : 2, DT == NINT_BF16 ? 160 : 320, (NTCT == 1 ? 32 : 96) * (DT == NINT_BF16 ? 1 : 2)> {
+  static constexpr int block = 256;
+  static constexpr int A_UNITS_PIX = 64 * Elem<DT>::ES / 16;         // 16-byte data units per dG pixel (64 gate columns)
+  static constexpr int B_UNITS_PIX = 16 * NTCT * Elem<DT>::ES / 16;  // data units per cat halo pixel
+  static constexpr int NI_WM = (WgNarrow::NI + 1) / 2;               // most DMA pieces one wave may take
+};
 
-// NS = gate-column groups among the 4 waves: NS=1 -> every wave owns all 4 row tiles and a quarter of
-// the (tap, channel-tile) columns; NS=2 -> (2 row tiles) x (half of the columns): 25 taps split 13+12
-// instead of 7+7+7+4, at the price of more fragment reads per MFMA.
+// ---- device pieces both kernels are made of
+// The transposed-read pair: two ds_read_b64_tr_b16, `half` bytes (16 pixels) apart, give the 8 K-slots of a 16x16x32 MFMA --
+// pixels 4*g + q and 16 + 4*g + q of the 32-pixel row segment that `ad` (per-lane base + immediate) points into.
+__device__ __forceinline__ u32x4_t wg_read_tr(const char* ad, int half) {
+  s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(ad));
+  s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(ad + half));
+  u32x2_t l2 = __builtin_bit_cast(u32x2_t, lo), h2 = __builtin_bit_cast(u32x2_t, hi);
+  return (u32x4_t){l2[0], l2[1], h2[0], h2[1]};
+}
+// One DMA piece: 64 lanes x 16 bytes from the per-lane address `src` to the 1 KiB at `dst` (wave-uniform).
+// Issued as inline asm ON PURPOSE: hipcc would count the builtin as an LDS write and wait vmcnt(0) ahead of the next ds_read (it
+// cannot tell the two buffers apart), which makes the staging synchronous; an asm DMA is invisible to its bookkeeping, so the
+// wait is ours: s_waitcnt vmcnt(0) ahead of the tile's barrier.  M0 = LDS destination base, saved and restored in the SAME
+// statement: the compiler keeps values of its own in M0 and sees none of this.
+__device__ __forceinline__ void wg_dma_piece(const char* src, char* dst) {
+  unsigned keep;
+  const unsigned lds_dst = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)dst);
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+               : "=&s"(keep) : "v"(src), "s"(lds_dst) : "memory");
+}
+// The tile cursor (tx, ty, img): coordinates of the next tile to load, set here for a split's first tile and then kept
+// incrementally (the tiles of a split are consecutive).
+__device__ __forceinline__ void wg_cursor_at(int tile, int tiles_x, int tiles_y, int& tx, int& ty, int& img) {
+  const int r = tile / tiles_x;
+  tx = tile - r * tiles_x;
+  img = r / tiles_y;
+  ty = r - img * tiles_y;
+}
+// (Two more pieces exist in both kernels and stay written out, each with a pointer to its twin: the cursor's step and the store
+// of a 16 x 16 accumulator tile into a slab column.  As functions, in every form tried, they moved instructions -- the step in
+// the one instance that calls its staging lambda out of line, the store in every instance; see profiles/wgrad_refactor_asm.txt.)
+
+// ---------------------------------------------------------------------------------------------- the 64-column kernel
+// Four waves; every wave owns all 4 row tiles (64 gate columns) and JW of the workgroup's 4 * JW (tap, channel-tile) columns
+// (25 taps: 7 + 7 + 7 + 4); a source with more columns (the 49 taps of a 7x7 kernel) takes TG column groups on extra workgroups.
 // KS (kernel size) and NTCT (channel tiles per column block) are template parameters so that every LDS
 // fragment address is `per-lane base VGPR + compile-time immediate`: the transposed reads then cost no
 // VALU instruction at all (the MFMAs leave only ~8 issue cycles each to the rest of the wave).
 // KX = horizontal taps of the source: KS, or 1 for a horizontally folded x source (nint_layer.xfold: its columns are
 // (vertical tap, folded channel tile) and every tap reads the centre column of the halo tile).
-template <int DT, int JW, int NS, int KS, int NTCT, int KX>
+template <int DT, int JW, int KS, int NTCT, int KX>
 __global__ __launch_bounds__(256, 2) void wgrad_kernel(WgradArgs a) {
   typedef Elem<DT> E;
-  typedef WgTile<DT> TT;
-  constexpr int PR = TT::PR, RA = TT::RA;
-  constexpr int NTN = 4 / NS;
-  constexpr int A_UNITS_PIX = 64 * E::ES / 16;           // 16-byte data units per dG pixel row (64 gate columns)
+  typedef WgNarrow<DT, KS, NTCT> G;
+  constexpr int PR = G::PR, RA = G::RA, RB = G::RB, HWt = G::HWt, HHt = G::HHt, p = G::p, k = KS;
+  constexpr int UA_ROW = G::UA_ROW, UB_PIX = G::UB_PIX, a_bytes = G::a_bytes, buf_bytes = G::buf_bytes;
+  constexpr int NI_A = G::NI_A, NI = G::NI, NI_WM = G::NI_WM;
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  constexpr int p = KS / 2, k = KS;
-  constexpr int HWt = 32 + 2 * p, HHt = PR + 2 * p;
-  constexpr int RB = TT::rb(NTCT);
-  constexpr int b_units_pix = 16 * NTCT * E::ES / 16;    // data units per cat halo pixel
-  // The two LDS images seen as 16-byte units INCLUDING their row padding: a tile is staged by LDS-DMA
-  // (global_load_lds_dwordx4: 64 consecutive units per wave instruction, per-lane source address), no VGPR
-  // round trip, no ds_write pass; lanes that land on padding re-read the tile's first unit.
-  constexpr int UA_ROW = RA / 16, NA_U = PR * 32 * UA_ROW;
-  constexpr int UB_PIX = RB / 16, NB_U = HHt * HWt * UB_PIX, NB_U_PAD = (NB_U + 63) / 64 * 64;
-  constexpr int a_bytes = PR * 32 * RA;
-  constexpr int b_bytes = NB_U_PAD * 16;
-  constexpr int buf_bytes = a_bytes + b_bytes;
-  static_assert(NA_U % 64 == 0 && a_bytes % 1024 == 0, "whole DMA pieces");
-  constexpr int NI_A = NA_U / 64, NI_B = NB_U_PAD / 64, NI = NI_A + NI_B;
 
   // (integer division runs on the vector ALU: readfirstlane puts the workgroup-uniform results back into scalars)
   int by = blockIdx.y, part = 0;
@@ -84,30 +123,30 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(WgradArgs a) {
   const int jb = tg * 4 * JW;                 // first column of this workgroup
   const int t_begin = blockIdx.x * S.tiles_per_split;
   const int t_end = min(S.ntiles, t_begin + S.tiles_per_split);
-  const int i0 = (wave % NS) * NTN;           // first row tile (16 gate columns each) of this wave
-  const int j0 = (wave / NS) * JW;
+  const int j0 = wave * JW;                   // first column of this wave
 
-  f32x4_t acc[NTN][JW];
+  f32x4_t acc[4][JW];
 #pragma unroll
-  for (int i = 0; i < NTN; ++i)
+  for (int i = 0; i < 4; ++i)
 #pragma unroll
     for (int j = 0; j < JW; ++j) acc[i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
 
   // bias gradient: channel block 0 / LAST column group of the source that carries it, on the last wave -- which has
-  // fewer than JW real columns there (host-checked), so its accumulator column JW-1 is free: no extra registers
-  const bool do_db = __builtin_amdgcn_readfirstlane((S.want_db && cb == 0 && tg == a.TG - 1 && wave == 3 && NS == 1) ? 1 : 0);
+  // fewer than JW real columns there (wg_narrow_row's static_assert), so its accumulator column JW-1 is free: no extra registers
+  int db_here = 0;                            // (an if, not a && chain inside ?: -- that spelling schedules every instance differently)
+  if (S.want_db && cb == 0 && tg == a.TG - 1 && wave == 3) db_here = 1;
+  const bool do_db = __builtin_amdgcn_readfirstlane(db_here);
 
   // DMA pieces of a tile are dealt to the waves in CONTIGUOUS ranges sized to even out each wave's work per tile:
   // a wave with fewer real columns (25 taps over 4 waves = 7, 7, 7, 4) has idle issue slots that the staging of the
   // next tile can use, so it takes more pieces: n_w = (L - nv_w * CM) / CD with the common level L such that the n_w
   // sum to NI (CM = matrix-pipe cycles per column and tile, CD ~ issue cost of one piece).  Wave-uniform integer math.
-  constexpr int NI_WM = (NI + 1) / 2;                    // most pieces one wave may take
   int p_begin, p_cnt;
   {
-    constexpr int CM = (DT == NINT_BF16 ? 16 : 32 * 4) * NTN * PR, CD = 100;
+    constexpr int CM = (DT == NINT_BF16 ? 16 : 32 * 4) * 4 * PR, CD = 100;
     int nv[4], n16[4], tot = 0, sum_nv = 0;
 #pragma unroll
-    for (int w = 0; w < 4; ++w) { nv[w] = min(JW, max(0, a.J - jb - (w / NS) * JW)); sum_nv += nv[w]; }
+    for (int w = 0; w < 4; ++w) { nv[w] = min(JW, max(0, a.J - jb - w * JW)); sum_nv += nv[w]; }
     const int L = (NI * CD + CM * sum_nv) / 4;
 #pragma unroll
     for (int w = 0; w < 4; ++w) { n16[w] = max(0, (L - nv[w] * CM) * 16 / CD); tot += n16[w]; }
@@ -142,23 +181,17 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(WgradArgs a) {
     if (t < NI_A) {
       const int u = t * 64 + lane;
       const int pix = u / UA_ROW, q = u - pix * UA_ROW;
-      if (q < A_UNITS_PIX) o = (unsigned)(((pix >> 5) * a.Wh + (pix & 31)) * a.dG_pix_stride + q * 16);
+      if (q < G::A_UNITS_PIX) o = (unsigned)(((pix >> 5) * a.Wh + (pix & 31)) * a.dG_pix_stride + q * 16);
     } else if (t < NI) {
       const int u = (t - NI_A) * 64 + lane;
       const int hp = u / UB_PIX, q = u - hp * UB_PIX;
       const int hy = hp / HWt, hx = hp - hy * HWt;
-      if (hp < HHt * HWt && q < b_units_pix) o = (unsigned)((hy * a.Wh + hx) * S.src_pix_stride + q * 16);
+      if (hp < HHt * HWt && q < G::B_UNITS_PIX) o = (unsigned)((hy * a.Wh + hx) * S.src_pix_stride + q * 16);
     }
     doff[i] = o;
   }
-  // tile coordinates of the next tile to load, kept incrementally (tiles of a split are consecutive)
   int ld_tx, ld_ty, ld_img;
-  {
-    const int r = t_begin / a.tiles_x;
-    ld_tx = t_begin - r * a.tiles_x;
-    ld_img = r / a.tiles_y;
-    ld_ty = r - ld_img * a.tiles_y;
-  }
+  wg_cursor_at(t_begin, a.tiles_x, a.tiles_y, ld_tx, ld_ty, ld_img);
   const char* const ga0 = S.dG + nb * 64 * E::ES;
   const char* const gb0 = S.src + cb * 16 * NTCT * E::ES;
 
@@ -170,19 +203,10 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(WgradArgs a) {
     for (int i = 0; i < NI_WM; ++i) {
       const int t = p_begin + i;               // wave-uniform
       if (i < p_cnt) {
-        const char* src = (t < NI_A ? ga : gb) + doff[i];
-        char* dst = buf + (t < NI_A ? t * 1024 : a_bytes + (t - NI_A) * 1024);
-        // issued as inline asm ON PURPOSE: hipcc would count the builtin as an LDS write and wait vmcnt(0) ahead
-        // of the next ds_read (it cannot tell the two buffers apart), which makes the staging synchronous; an asm
-        // DMA is invisible to its bookkeeping, so the wait is ours: s_waitcnt vmcnt(0) ahead of the tile's barrier.
-        // (M0 = LDS destination base; saved and restored in the same statement.)
-        unsigned keep;
-        const unsigned lds_dst = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)dst);
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(src), "s"(lds_dst) : "memory");
+        wg_dma_piece((t < NI_A ? ga : gb) + doff[i], buf + (t < NI_A ? t * 1024 : a_bytes + (t - NI_A) * 1024));
       }
     }
-    const bool wx = ld_tx + 1 == a.tiles_x;
+    const bool wx = ld_tx + 1 == a.tiles_x;      // (the cursor's step; twin: wgrad_wide_kernel's issue_dma)
     const bool wy = wx && (ld_ty + 1 == a.tiles_y);
     ld_tx = wx ? 0 : ld_tx + 1;
     ld_ty = wy ? 0 : (wx ? ld_ty + 1 : ld_ty);
@@ -201,12 +225,12 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(WgradArgs a) {
   int vB[JW];
   int vA;
   const int nvalid = __builtin_amdgcn_readfirstlane(min(JW, max(0, a.J - jb - j0)));   // real columns of this wave
-  constexpr int JT = KS * KX * NTCT;                                              // = a.J (host-checked)
+  constexpr int JT = KS * KX * NTCT;                                              // = a.J (the row's column count)
   constexpr int XO = KX == KS ? 0 : p;                                            // folded: the centre column
   constexpr int NVL = JT % JW == 0 ? JW : JT % JW;                                // columns of the last, partial group
   if constexpr (DT == NINT_BF16) {
     const int q = i16 >> 2, p8 = (i16 & 3) * 8;
-    vA = (4 * g + q) * RA + i0 * 32 + p8;             // pixel 4g+q of a 16-pixel half segment, 8 bytes of 4 channels
+    vA = (4 * g + q) * RA + p8;                      // pixel 4g+q of a 16-pixel half segment, 8 bytes of 4 channels
 #pragma unroll
     for (int jj = 0; jj < JW; ++jj) {
       const int j = min(jb + j0 + jj, a.J - 1);
@@ -215,7 +239,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(WgradArgs a) {
       vB[jj] = a_bytes + (tyy * HWt + txx + 4 * g + q) * RB + ct * 32 + p8;
     }
   } else {
-    vA = g * RA + (i0 * 16 + i16) * 4;                // MFMA m of a 16-pixel K-step takes pixel 4m+g
+    vA = g * RA + i16 * 4;                // MFMA m of a 16-pixel K-step takes pixel 4m+g
 #pragma unroll
     for (int jj = 0; jj < JW; ++jj) {
       const int j = min(jb + j0 + jj, a.J - 1);
@@ -242,26 +266,19 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(WgradArgs a) {
       if constexpr ((NV > 0 || DB) && DT == NINT_BF16) {
 #pragma unroll
         for (int pr = 0; pr < PR; ++pr) {
-          // pixel -> K-slot: read rd covers pixels rd*16 + 4*g + q of the 32-pixel row segment
-          auto read_tr = [&](const char* ad, int half) __attribute__((always_inline)) {
-            s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(ad));
-            s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(ad + half));
-            u32x2_t l2 = __builtin_bit_cast(u32x2_t, lo), h2 = __builtin_bit_cast(u32x2_t, hi);
-            return (u32x4_t){l2[0], l2[1], h2[0], h2[1]};
-          };
-          u32x4_t af[NTN], bf[NV > 0 ? NV : 1];
+          u32x4_t af[4], bf[NV > 0 ? NV : 1];
 #pragma unroll
-          for (int i = 0; i < NTN; ++i) af[i] = read_tr(Ab + pr * 32 * RA + i * 32, 16 * RA);
+          for (int i = 0; i < 4; ++i) af[i] = wg_read_tr(Ab + pr * 32 * RA + i * 32, 16 * RA);
 #pragma unroll
-          for (int jj = 0; jj < NV; ++jj) bf[jj] = read_tr(Bb[jj] + pr * HWt * RB, 16 * RB);
+          for (int jj = 0; jj < NV; ++jj) bf[jj] = wg_read_tr(Bb[jj] + pr * HWt * RB, 16 * RB);
 #pragma unroll
           for (int jj = 0; jj < NV; ++jj)
 #pragma unroll
-            for (int i = 0; i < NTN; ++i) acc[i][jj] = mma_step<NINT_BF16>(af[i], bf[jj], acc[i][jj]);
+            for (int i = 0; i < 4; ++i) acc[i][jj] = mma_step<NINT_BF16>(af[i], bf[jj], acc[i][jj]);
           if constexpr (DB) {                  // D[gate column][.] += sum over the 32 pixels of this row segment
             const u32x4_t ones = {0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u};
 #pragma unroll
-            for (int i = 0; i < NTN; ++i) acc[i][JW - 1] = mma_step<NINT_BF16>(af[i], ones, acc[i][JW - 1]);
+            for (int i = 0; i < 4; ++i) acc[i][JW - 1] = mma_step<NINT_BF16>(af[i], ones, acc[i][JW - 1]);
           }
         }
       } else if constexpr (NV > 0 || DB) {
@@ -272,20 +289,20 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(WgradArgs a) {
             // 16 pixels per K-step: MFMA m takes pixel 4*m + g of the segment as its K index g
 #pragma unroll
             for (int m = 0; m < 4; ++m) {
-              float af[NTN];
+              float af[4];
 #pragma unroll
-              for (int i = 0; i < NTN; ++i)
+              for (int i = 0; i < 4; ++i)
                 af[i] = *(const float*)(Ab + (pr * 32 + ks * 16 + 4 * m) * RA + i * 64);
 #pragma unroll
               for (int jj = 0; jj < NV; ++jj) {
                 const float bf = *(const float*)(Bb[jj] + (pr * HWt + ks * 16 + 4 * m) * RB);
 #pragma unroll
-                for (int i = 0; i < NTN; ++i)
+                for (int i = 0; i < 4; ++i)
                   acc[i][jj] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[i], bf, acc[i][jj], 0, 0, 0);
               }
               if constexpr (DB) {
 #pragma unroll
-                for (int i = 0; i < NTN; ++i) acc[i][JW - 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[i], 1.0f, acc[i][JW - 1], 0, 0, 0);
+                for (int i = 0; i < 4; ++i) acc[i][JW - 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[i], 1.0f, acc[i][JW - 1], 0, 0, 0);
               }
             }
           }
@@ -311,18 +328,18 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(WgradArgs a) {
     const int j = j0 + jj;
     if (jb + j < a.J) {
 #pragma unroll
-      for (int i = 0; i < NTN; ++i)
+      for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int r = 0; r < 4; ++r)
-          out[(size_t)j * 1024 + ((i0 + i) * 16 + 4 * g + r) * 16 + i16] = acc[i][jj][r];
+          out[(size_t)j * 1024 + (i * 16 + 4 * g + r) * 16 + i16] = acc[i][jj][r];      // (twin: wgrad_wide_kernel's flush)
     }
   }
   if (do_db) {                                            // slab column JG-1: all 16 "channel" columns hold the same sum
 #pragma unroll
-    for (int i = 0; i < NTN; ++i)
+    for (int i = 0; i < 4; ++i)
 #pragma unroll
       for (int r = 0; r < 4; ++r)
-        out[(size_t)(S.JG - 1) * 1024 + ((i0 + i) * 16 + 4 * g + r) * 16 + i16] = acc[i][JW - 1][r];
+        out[(size_t)(S.JG - 1) * 1024 + (i * 16 + 4 * g + r) * 16 + i16] = acc[i][JW - 1][r];
   }
 }
 
@@ -337,22 +354,16 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(WgradArgs a) {
 // of 0.79 / 0.9 transposed reads per MFMA.  Tap ranges are compile-time per wave role (switch on `half`), so every fragment
 // address is `per-lane base + immediate`, as above.  Partials leave in the layout of the 4-wave kernel with NTC = 1, so the
 // fold kernel and the workspace arithmetic are shared.  bf16 storage only (f32 mode is not the throughput mode).
-template <int KS, int NCT> struct WgWide {
+template <int KS, int NCT>
+struct WgWide : WgImage<KS, 4, 288, NCT == 4 ? 160 : (NCT == 2 ? 96 : 32)> {   // dG pixel: 256 + 32 bytes; cat: conflict-free strides
+  static constexpr int block = 512;
   static constexpr int taps = KS * KS;
   static constexpr int HG = KS == 3 ? 1 : (KS == 5 ? 2 : 4);         // column groups per channel tile
   static constexpr int JW = (taps + HG - 1) / HG;                   // taps per wave: 9, 13, 13
   static constexpr int NVL = taps - (HG - 1) * JW;                  // taps of the last group: 9, 12, 10
   static constexpr int JWA = JW + (NVL == JW ? 1 : 0);              // accumulator columns (the last group keeps one free for db)
   static constexpr int NW = 2 * NCT * HG;                           // waves
-  static constexpr int PR = 4, RA = 288;                            // pixel rows per tile; bytes per dG pixel row (256 + 32 pad)
-  static constexpr int RB = NCT == 4 ? 160 : (NCT == 2 ? 96 : 32);  // bytes per cat halo pixel (conflict-free strides)
-  static constexpr int p = KS / 2, HWt = 32 + 2 * p, HHt = PR + 2 * p;
-  static constexpr int UA_ROW = RA / 16, NA_U = PR * 32 * UA_ROW;
-  static constexpr int UB_PIX = RB / 16, NB_U = HHt * HWt * UB_PIX, NB_U_PAD = (NB_U + 63) / 64 * 64;
-  static constexpr int a_bytes = PR * 32 * RA, b_bytes = NB_U_PAD * 16, buf_bytes = a_bytes + b_bytes;
-  static constexpr int NI_A = NA_U / 64, NI_B = NB_U_PAD / 64, NI = NI_A + NI_B;
-  static constexpr int NI_W = (NI + NW - 1) / NW;                   // DMA pieces per wave and tile
-  static_assert(NA_U % 64 == 0, "whole DMA pieces");
+  static constexpr int NI_W = (WgWide::NI + NW - 1) / NW;           // DMA pieces per wave and tile
   static_assert(NW == 8, "eight waves: two per SIMD");
 };
 
@@ -403,12 +414,7 @@ __global__ __launch_bounds__(512, 2) void wgrad_wide_kernel(WgradArgs a) {
     return o;
   };
   int ld_tx, ld_ty, ld_img;
-  {
-    const int r = t_begin / a.tiles_x;
-    ld_tx = t_begin - r * a.tiles_x;
-    ld_img = r / a.tiles_y;
-    ld_ty = r - ld_img * a.tiles_y;
-  }
+  wg_cursor_at(t_begin, a.tiles_x, a.tiles_y, ld_tx, ld_ty, ld_img);
   const char* const ga0 = T.dG + nbw * 128 * 2;
   const char* const gb0 = T.src + cbw * 16 * NCT * 2;
   const long src_img_stride = T.src_img_stride;
@@ -420,16 +426,10 @@ __global__ __launch_bounds__(512, 2) void wgrad_wide_kernel(WgradArgs a) {
     for (int i = 0; i < NI_W; ++i) {
       const int t = wave + G::NW * i;              // wave-uniform
       if (t < NI) {
-        const char* src = (t < NI_A ? ga : gb) + piece_off(t);
-        char* dst = buf + (t < NI_A ? t * 1024 : a_bytes + (t - NI_A) * 1024);
-        // (inline asm for the reason given in wgrad_kernel: the wait is ours, ahead of the tile's barrier)
-        unsigned keep;
-        const unsigned lds_dst = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)dst);
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(src), "s"(lds_dst) : "memory");
+        wg_dma_piece((t < NI_A ? ga : gb) + piece_off(t), buf + (t < NI_A ? t * 1024 : a_bytes + (t - NI_A) * 1024));
       }
     }
-    const bool wx = ld_tx + 1 == a.tiles_x;
+    const bool wx = ld_tx + 1 == a.tiles_x;      // (the cursor's step; twin: wgrad_kernel's issue_dma)
     const bool wy = wx && (ld_ty + 1 == a.tiles_y);
     ld_tx = wx ? 0 : ld_tx + 1;
     ld_ty = wy ? 0 : (wx ? ld_ty + 1 : ld_ty);
@@ -451,17 +451,11 @@ __global__ __launch_bounds__(512, 2) void wgrad_wide_kernel(WgradArgs a) {
       if (tile + 1 < t_end) issue_dma(smem + (cur ^ 1) * buf_bytes);   // the other buffer was last read before the previous barrier
       const char* Ab = smem + cur * buf_bytes + vA;
       const char* Bb = smem + cur * buf_bytes + vB;
-      auto read_tr = [&](const char* ad, int half_off) __attribute__((always_inline)) {
-        s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(ad));
-        s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(ad + half_off));
-        u32x2_t l2 = __builtin_bit_cast(u32x2_t, lo), h2 = __builtin_bit_cast(u32x2_t, hi);
-        return (u32x4_t){l2[0], l2[1], h2[0], h2[1]};
-      };
 #pragma unroll
       for (int pr = 0; pr < PR; ++pr) {
         u32x4_t af[4];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) af[i] = read_tr(Ab + pr * 32 * RA + i * 32, 16 * RA);
+        for (int i = 0; i < 4; ++i) af[i] = wg_read_tr(Ab + pr * 32 * RA + i * 32, 16 * RA);
         auto colptr = [&](int jj) __attribute__((always_inline)) {
           const int tap = TAP0 + jj, tyy = tap / KS, txx = tap - tyy * KS;
           return Bb + (tyy * HWt + txx) * RB + pr * HWt * RB;
@@ -470,17 +464,17 @@ __global__ __launch_bounds__(512, 2) void wgrad_wide_kernel(WgradArgs a) {
           // cat fragments STREAMED: two live at a time, the next column's reads issued ahead of this column's MFMAs (the
           // compiler's own schedule hoists a whole row of them: 52 registers the 4 x 13 tile does not have)
           u32x4_t bfq[2];
-          if constexpr (NV > 0) bfq[0] = read_tr(colptr(0), 16 * RB);
+          if constexpr (NV > 0) bfq[0] = wg_read_tr(colptr(0), 16 * RB);
 #pragma unroll
           for (int jj = 0; jj < NV; ++jj) {
-            if (jj + 1 < NV) bfq[(jj + 1) & 1] = read_tr(colptr(jj + 1), 16 * RB);
+            if (jj + 1 < NV) bfq[(jj + 1) & 1] = wg_read_tr(colptr(jj + 1), 16 * RB);
 #pragma unroll
             for (int i = 0; i < 4; ++i) acc[i][jj] = mma_step<NINT_BF16>(af[i], bfq[jj & 1], acc[i][jj]);
           }
         } else {
 #pragma unroll
           for (int jj = 0; jj < NV; ++jj) {
-            const u32x4_t bf = read_tr(colptr(jj), 16 * RB);
+            const u32x4_t bf = wg_read_tr(colptr(jj), 16 * RB);
 #pragma unroll
             for (int i = 0; i < 4; ++i) acc[i][jj] = mma_step<NINT_BF16>(af[i], bf, acc[i][jj]);
           }
@@ -526,7 +520,7 @@ __global__ __launch_bounds__(512, 2) void wgrad_wide_kernel(WgradArgs a) {
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) out[(size_t)(tap0 + jj) * 1024 + (i * 16 + 4 * g + r) * 16 + i16] = acc[i][jj][r];
+        for (int r = 0; r < 4; ++r) out[(size_t)(tap0 + jj) * 1024 + (i * 16 + 4 * g + r) * 16 + i16] = acc[i][jj][r];   // (twin: wgrad_kernel's flush)
     }
   }
   if (do_db) {
@@ -602,8 +596,64 @@ __global__ void wgrad_reduce_kernel(ReduceTable t) {
 }
 
 // ------------------------------------------------------------------------------ host side
-struct WgPart { int NTC, J, JW, KX, CB, TG, JG, splits;   // one source (x or h) of the reduction
-                int wide_nct, wcols; };                     // > 0: the 8-wave 128-column kernel with this many channel tiles per workgroup (wgrad_wide_kernel); its workgroup columns
+// THE INSTANCE TABLE: every kernel instance that exists, once.  wg_plan derives a key from its rules and looks it up here -- a
+// key without a row is NINT_E_SHAPE at plan time (so nint_wgrad_workspace_bytes is 0 and SeqEngine.untrainable_layers names the
+// layer) -- and a launch record is filled from the row; nothing else names an instance.
+//   4-wave rows (KS, NTCT, JW, KX), each in both storage types: plain sources; the horizontally folded x source of thin
+//   first-layer inputs (KX = 1: vertical taps only); 7x7 (49 taps in two column groups).  The last line's rows -- one channel
+//   tile per block, five columns per wave -- want a channel count of 16 mod 32: f32 slabs (padded to 16) reach them, bf16 slabs
+//   as SeqEngine pads them (nint_kc = 32) never do (tests/test_wgrad_plan_cpu.py sweeps that through nint_debug_wgrad_plan), so
+//   their bf16 halves serve raw nint_layer callers only.
+#define WG_NARROW_ROWS(X) \
+  X(5, 1, 7, 5) X(3, 2, 5, 3) X(1, 2, 5, 1) \
+  X(5, 2, 5, 1) X(3, 2, 5, 1) X(7, 2, 5, 1) \
+  X(7, 1, 7, 7) \
+  X(3, 1, 5, 3) X(1, 1, 5, 1) X(5, 1, 5, 1) X(3, 1, 5, 1) X(7, 1, 5, 1)
+//   8-wave rows (KS, NCT), bf16 storage only (f32 mode is not the throughput mode):
+#define WG_WIDE_ROWS(X) X(3, 4) X(5, 2) X(7, 1)
+
+struct WgRow {
+  int KS, NTC, JW, KX;       // the key; JW = 0: an 8-wave row (NTC = its channel tiles per workgroup, KX = KS)
+  int block;
+  const void* kern[2];       // host handles by storage type (NINT_F32, NINT_BF16); nullptr: not instantiated
+  size_t lds[2];             // dynamic LDS bytes: the geometry struct's two tile buffers
+};
+constexpr int wg_jw(int J) { return J <= 20 ? 5 : 7; }                    // columns per wave of the 4-wave kernel
+template <int KS, int NTCT, int JW, int KX> static WgRow wg_narrow_row() {
+  constexpr int J = KS * KX * NTCT, TG = (J + 4 * JW - 1) / (4 * JW);     // columns; column groups of 4 * JW
+  static_assert(JW == wg_jw(J), "a row wg_plan's rules can derive");
+  static_assert(TG == 1 || J % JW == 0, "column groups hold whole waves of columns (the tile loop exists for JW, J % JW and 0 columns per wave)");
+  static_assert(J - (TG - 1) * 4 * JW <= 3 * JW + (JW - 1), "the db column needs wave 3's last accumulator column free");
+  typedef WgNarrow<NINT_F32, KS, NTCT> F;
+  typedef WgNarrow<NINT_BF16, KS, NTCT> B;
+  return WgRow{KS, NTCT, JW, KX, F::block, {(const void*)wgrad_kernel<NINT_F32, JW, KS, NTCT, KX>, (const void*)wgrad_kernel<NINT_BF16, JW, KS, NTCT, KX>},
+               {F::lds, B::lds}};
+}
+template <int KS, int NCT> static WgRow wg_wide_row() {
+  typedef WgWide<KS, NCT> G;
+  return WgRow{KS, NCT, 0, KS, G::block, {nullptr, (const void*)wgrad_wide_kernel<KS, NCT>}, {0, G::lds}};
+}
+static const WgRow wg_rows[] = {
+#define X(KS, NTCT, JW, KX) wg_narrow_row<KS, NTCT, JW, KX>(),
+  WG_NARROW_ROWS(X)
+#undef X
+#define X(KS, NCT) wg_wide_row<KS, NCT>(),
+  WG_WIDE_ROWS(X)
+#undef X
+};
+static const WgRow* wg_find_row(int dtype, int KS, int NTC, int JW, int KX) {      // NTC = 0: any (an 8-wave row by its KS)
+  for (const WgRow& r : wg_rows)
+    if (r.KS == KS && (!NTC || r.NTC == NTC) && r.JW == JW && r.KX == KX && r.kern[dtype == NINT_BF16]) return &r;
+  return nullptr;
+}
+
+struct WgPart {            // one source (x or h) of the reduction
+  const WgRow* row;        // its kernel instance
+  int NTC, J, KX, CB, TG, JG, splits;     // slab layout: channel tiles per block, columns, horizontal taps, ...
+  int nblk;                // blocks of a slab: NB * CB * TG, of JG KiB-columns each
+  int cols;                // workgroup columns (grid y) of a launch of its own
+  size_t slab() const { return (size_t)nblk * JG * 1024; }     // floats per split
+};
 struct WgPlan {
   WgPart part[2];
   int NB, tiles_x, tiles_y, ntiles;
@@ -615,43 +665,48 @@ struct WgPlan {
 // The 128-column kernel holds a SOURCE (x or h) of a layer when it is an unfolded bf16 slab, the gate columns come in pairs of
 // 64-column blocks and the source's channels in whole channel groups (3x3: 64 channels, 5x5: 32, 7x7: 16) -- the reference
 // stack's second layer (64 -> 32, 3x3) takes it for its x source only.  nint_layer.wide: 1 = never, 2 / 0 = wherever held.
-static int wg_wide_nct(const nint_layer* ly, int dtype, int q) {
-  if (dtype != NINT_BF16 || ly->wide == 1 || (q == 0 && ly->xfold)) return 0;
-  const int nct = ly->k == 3 ? 4 : (ly->k == 5 ? 2 : (ly->k == 7 ? 1 : 0));
-  if (!nct || (4 * ly->Ch16) % 128 || (q == 0 ? ly->Cxp : ly->Chp) % (16 * nct)) return 0;
-  return nct;
+static const WgRow* wg_wide_row_of(const nint_layer* ly, int dtype, int q) {
+  if (ly->wide == 1 || (q == 0 && ly->xfold)) return nullptr;
+  const WgRow* r = wg_find_row(dtype, ly->k, 0, 0, ly->k);
+  if (!r || (4 * ly->Ch16) % 128 || (q == 0 ? ly->Cxp : ly->Chp) % (16 * r->NTC)) return nullptr;
+  return r;
 }
 
+// THE SPLIT RULE: enough splits of the pixel tiles that `columns` workgroup columns give target_workgroups workgroups, but never
+// fewer than NINT_WG_MIN_TILES tiles per split -- the accumulator flush (J KiB-tiles per workgroup) must stay small against the
+// K work -- re-derived so that no split is empty.  whole_xcds: rounded down to a multiple of 8 -- workgroup (split, column)
+// sits on XCD (split + splits * column) % 8, so all columns of a split, which read the same dG tiles, then share one L2.
 #ifndef NINT_WG_MIN_TILES
 #define NINT_WG_MIN_TILES 8
 #endif
+static int wg_splits(int target_workgroups, int columns, int ntiles, bool whole_xcds) {
+  int s = nint_cdiv(target_workgroups, columns);
+  if (s > ntiles / NINT_WG_MIN_TILES) s = ntiles / NINT_WG_MIN_TILES;
+  if (s < 1) s = 1;
+  s = nint_cdiv(ntiles, nint_cdiv(ntiles, s));
+  if (whole_xcds && s >= 8) s -= s % 8;
+  return s;
+}
+
 static int wg_plan(const nint_layer* ly, int dtype, int n_cu, int N, const nint_geom* g, WgPlan* pl) {
-  if (ly->k != 1 && ly->k != 3 && ly->k != 5 && ly->k != 7) return NINT_E_SHAPE;
   pl->NB = 4 * ly->Ch16 / 64;
   const int PR = dtype == NINT_BF16 ? 4 : 2;
   pl->tiles_x = g ? nint_cdiv(g->W, 32) : 1;
   pl->tiles_y = g ? nint_cdiv(g->H, PR) : 1;
   pl->ntiles = g ? N * pl->tiles_x * pl->tiles_y : (1 << 30);
   if (n_cu <= 0) n_cu = 256;
-  size_t floats[2];
   for (int q = 0; q < 2; ++q) {
     WgPart& w = pl->part[q];
     const int Cp = q == 0 ? ly->Cxp : ly->Chp;
-    w.wide_nct = wg_wide_nct(ly, dtype, q);
-    w.wcols = 0;
-    if (w.wide_nct) {
-      // one 8-wave workgroup per CU; partial slabs in the 4-wave kernel's layout with one channel tile per block (NTC = 1)
-      w.KX = ly->k; w.NTC = 1; w.J = ly->k * ly->k; w.JW = 0; w.TG = 1;
+    w.row = wg_wide_row_of(ly, dtype, q);
+    if (w.row) {
+      // partial slabs in the 4-wave kernel's layout with one channel tile per block (NTC = 1)
+      w.KX = ly->k; w.NTC = 1; w.J = ly->k * ly->k; w.TG = 1;
       w.JG = w.J + (q == 0 ? 1 : 0);
       w.CB = Cp / 16;
-      w.wcols = (pl->NB / 2) * (w.CB / w.wide_nct);
-      int s = nint_cdiv(n_cu, w.wcols);
-      if (s > pl->ntiles / NINT_WG_MIN_TILES) s = pl->ntiles / NINT_WG_MIN_TILES;
-      if (s < 1) s = 1;
-      s = nint_cdiv(pl->ntiles, nint_cdiv(pl->ntiles, s));
-      if (s >= 8) s -= s % 8;             // all workgroup columns of a split on one XCD (they share its dG / cat tiles in L2)
-      w.splits = s;
-      floats[q] = (size_t)w.splits * pl->NB * w.CB * w.JG * 1024;
+      w.nblk = pl->NB * w.CB;
+      w.cols = (pl->NB / 2) * (w.CB / w.row->NTC);
+      w.splits = wg_splits(n_cu, w.cols, pl->ntiles, true);     // one 8-wave workgroup per CU
       continue;
     }
     w.KX = (q == 0 && ly->xfold) ? 1 : ly->k;           // folded x source: vertical taps only
@@ -659,46 +714,28 @@ static int wg_plan(const nint_layer* ly, int dtype, int n_cu, int N, const nint_
     w.NTC = (taps * 2 <= 20 && Cp % 32 == 0) ? 2 : 1;   // channel tiles per column block
     w.J = taps * w.NTC;
     // every wave owns all 4 row tiles (64 gate columns) and a quarter of the (tap, channel-tile) columns
-    w.JW = w.J <= 20 ? 5 : 7;
-    // more than 4*JW columns (the 49 taps of a 7x7 kernel): column groups on extra workgroups; only whole waves of
-    // columns there (the tile loop exists for JW, J % JW and 0 columns per wave)
-    w.TG = nint_cdiv(w.J, 4 * w.JW);
-    w.JG = (w.TG == 1 ? w.J : 4 * w.JW) + (q == 0 ? 1 : 0);     // the x part's slabs carry the bias-gradient column
-    if (w.TG > 1 && w.J % w.JW) return NINT_E_SHAPE;
-    if (q == 0 && w.J - (w.TG - 1) * 4 * w.JW > 3 * w.JW + (w.JW - 1)) return NINT_E_SHAPE;   // the db column needs wave 3's last accumulator column free
+    w.row = wg_find_row(dtype, ly->k, w.NTC, wg_jw(w.J), w.KX);
+    if (!w.row) return NINT_E_SHAPE;                    // no such instance: refused here, before any workspace is sized
+    const int JW = w.row->JW;
+    // more than 4*JW columns (the 49 taps of a 7x7 kernel): column groups on extra workgroups
+    w.TG = nint_cdiv(w.J, 4 * JW);
+    w.JG = (w.TG == 1 ? w.J : 4 * JW) + (q == 0 ? 1 : 0);     // the x part's slabs carry the bias-gradient column
     const int CW = 16 * w.NTC;
     if (Cp % CW) return NINT_E_SHAPE;
     w.CB = Cp / CW;
-    // two workgroups per CU in flight, but never fewer than NINT_WG_MIN_TILES pixel tiles per split: the
-    // accumulator flush (J KiB-tiles per workgroup) must stay small against the K work.  (32 until round 3; at B = 1-2
-    // per GPU that left the narrow layers' launches at 92-276 workgroups: 8 measured +2.9 % on the B = 1 step, +0.9 % at
-    // B = 2, nothing at B >= 4 where the workgroup cap binds first; 4 and 2 equal 8.)
-    int s = nint_cdiv(2 * n_cu, pl->NB * w.CB * w.TG);
-    if (s > pl->ntiles / NINT_WG_MIN_TILES) s = pl->ntiles / NINT_WG_MIN_TILES;
-    if (s < 1) s = 1;
-    // re-derive the split count so that no split is empty
-    w.splits = nint_cdiv(pl->ntiles, nint_cdiv(pl->ntiles, s));
-    floats[q] = (size_t)w.splits * pl->NB * w.CB * w.TG * w.JG * 1024;
+    w.cols = w.nblk = pl->NB * w.CB * w.TG;
+    // two workgroups per CU in flight.  (NINT_WG_MIN_TILES was 32 until round 3; at B = 1-2 per GPU that left the narrow
+    // layers' launches at 92-276 workgroups: 8 measured +2.9 % on the B = 1 step, +0.9 % at B = 2, nothing at B >= 4 where the
+    // workgroup cap binds first; 4 and 2 equal 8.)
+    w.splits = wg_splits(2 * n_cu, w.cols, pl->ntiles, false);
   }
-  // same kernel shape for both sources and few workgroup columns: one launch, one split count
-  const WgPart &wx = pl->part[0], &wh = pl->part[1];
-  pl->merged = !wx.wide_nct && !wh.wide_nct && wx.NTC == wh.NTC && wx.JW == wh.JW && wx.KX == wh.KX && wx.TG == 1 && wh.TG == 1 && pl->NB * (wx.CB + wh.CB) <= 8;
-  if (pl->merged) {
-    int s = nint_cdiv(2 * n_cu, pl->NB * (wx.CB + wh.CB));
-    if (s > pl->ntiles / NINT_WG_MIN_TILES) s = pl->ntiles / NINT_WG_MIN_TILES;
-    if (s < 1) s = 1;
-    s = nint_cdiv(pl->ntiles, nint_cdiv(pl->ntiles, s));
-    // a multiple of 8 splits: workgroup (split, column) sits on XCD (split + splits * column) % 8, so all columns of a split
-    // -- the workgroups that read the same dG tiles -- then share one L2 (86 splits for layer 1: 534 us; 80: see DESIGN.md)
-    if (s >= 8) s -= s % 8;
-    for (int q = 0; q < 2; ++q) {
-      WgPart& w = pl->part[q];
-      w.splits = s;
-      floats[q] = (size_t)w.splits * pl->NB * w.CB * w.TG * w.JG * 1024;
-    }
-  }
-  pl->off_h = floats[0];
-  pl->total_floats = floats[0] + floats[1];
+  // same kernel for both sources and few workgroup columns: one launch, one split count
+  WgPart &wx = pl->part[0], &wh = pl->part[1];
+  pl->merged = wx.row == wh.row && wx.row->JW && wx.TG == 1 && wh.TG == 1 && wx.cols + wh.cols <= 8;
+  // (whole XCDs -- 86 splits for layer 1: 534 us; 80: see DESIGN.md)
+  if (pl->merged) wx.splits = wh.splits = wg_splits(2 * n_cu, wx.cols + wh.cols, pl->ntiles, true);
+  pl->off_h = wx.splits * wx.slab();
+  pl->total_floats = pl->off_h + wh.splits * wh.slab();
   return NINT_OK;
 }
 
@@ -708,51 +745,6 @@ extern "C" size_t nint_wgrad_workspace_bytes(const nint_layer* ly, int dtype, in
   // upper bound independent of N: splits are capped by 2*n_cu / blocks
   if (wg_plan(ly, dtype, n_cu, 1, nullptr, &pl) != NINT_OK) return 0;
   return pl.total_floats * sizeof(float);
-}
-
-// A launch is PLANNED the way launch_cfg (conv_igemm.hip) plans a conv launch: fill the record, or return the error
-template <int DT, int JW, int KS, int NTCT, int KX>
-static int launch_wgrad(const WgradArgs& a, int splits, int nblk, WgLaunch* out) {
-  typedef WgTile<DT> TT;
-  const int p = a.p;
-  const int a_bytes = TT::PR * 32 * TT::RA;
-  const int b_bytes = nint_round_up((TT::PR + 2 * p) * (32 + 2 * p) * TT::rb(a.NTC), 1024);   // whole 1-KiB DMA pieces
-  const size_t lds = 2 * (size_t)(a_bytes + b_bytes);
-  if (lds > 160 * 1024) return NINT_E_LDS;
-  if (a.k != KS || a.NTC != NTCT || a.J != KS * KX * NTCT) return NINT_E_ARG;
-  *out = WgLaunch{(const void*)wgrad_kernel<DT, JW, 1, KS, NTCT, KX>, splits, nblk, 256, lds, a};
-  return NINT_OK;
-}
-
-template <int KS, int NCT>
-static int launch_wgrad_wide(const WgradArgs& a, int splits, int cols, WgLaunch* out) {
-  const size_t lds = 2 * (size_t)WgWide<KS, NCT>::buf_bytes;
-  if (lds > 160 * 1024) return NINT_E_LDS;
-  *out = WgLaunch{(const void*)wgrad_wide_kernel<KS, NCT>, splits, cols, 512, lds, a};
-  return NINT_OK;
-}
-
-// instantiated (kernel size, channel tiles, columns per wave, horizontal taps) combinations
-template <int DT>
-static int dispatch_wgrad(const WgradArgs& a, const WgPart& w, int nblk, WgLaunch* out) {
-  const int key = a.k * 1000 + w.NTC * 100 + w.JW * 10 + w.KX;
-  switch (key) {
-    case 5 * 1000 + 1 * 100 + 7 * 10 + 5: return launch_wgrad<DT, 7, 5, 1, 5>(a, w.splits, nblk, out);
-    case 3 * 1000 + 2 * 100 + 5 * 10 + 3: return launch_wgrad<DT, 5, 3, 2, 3>(a, w.splits, nblk, out);
-    case 3 * 1000 + 1 * 100 + 5 * 10 + 3: return launch_wgrad<DT, 5, 3, 1, 3>(a, w.splits, nblk, out);
-    case 1 * 1000 + 2 * 100 + 5 * 10 + 1: return launch_wgrad<DT, 5, 1, 2, 1>(a, w.splits, nblk, out);
-    case 1 * 1000 + 1 * 100 + 5 * 10 + 1: return launch_wgrad<DT, 5, 1, 1, 1>(a, w.splits, nblk, out);
-    // horizontally folded x source (thin first-layer inputs)
-    case 5 * 1000 + 2 * 100 + 5 * 10 + 1: return launch_wgrad<DT, 5, 5, 2, 1>(a, w.splits, nblk, out);
-    case 5 * 1000 + 1 * 100 + 5 * 10 + 1: return launch_wgrad<DT, 5, 5, 1, 1>(a, w.splits, nblk, out);
-    case 3 * 1000 + 2 * 100 + 5 * 10 + 1: return launch_wgrad<DT, 5, 3, 2, 1>(a, w.splits, nblk, out);
-    case 3 * 1000 + 1 * 100 + 5 * 10 + 1: return launch_wgrad<DT, 5, 3, 1, 1>(a, w.splits, nblk, out);
-    // 7x7 kernels: 49 taps in two column groups; folded thin inputs 7 or 14 columns
-    case 7 * 1000 + 1 * 100 + 7 * 10 + 7: return launch_wgrad<DT, 7, 7, 1, 7>(a, w.splits, nblk, out);
-    case 7 * 1000 + 2 * 100 + 5 * 10 + 1: return launch_wgrad<DT, 5, 7, 2, 1>(a, w.splits, nblk, out);
-    case 7 * 1000 + 1 * 100 + 5 * 10 + 1: return launch_wgrad<DT, 5, 7, 1, 1>(a, w.splits, nblk, out);
-    default: return NINT_E_SHAPE;
-  }
 }
 
 // Weight / bias gradients of several layers ("jobs") in one go: two MFMA launches per layer (x and h source) into
@@ -802,31 +794,23 @@ int nint_internal_wgrad_plan(const WgJob* jobs, int njobs, const nint_geom* g, i
       S.src = (const char*)(part == 0 ? jb.x_slab : jb.h_slab) + (size_t)skip * S.src_img_stride;
       S.partial = base + (part == 0 ? 0 : pl.off_h);
       S.CB = w.CB; S.JG = w.JG;
-      S.nblk = pl.NB * w.CB * w.TG;
+      S.nblk = w.nblk;
       S.want_db = part == 0 ? 1 : 0;           // the x part sees every image (the h part may skip the first time step)
       S.ntiles = (jb.N - skip) * pl.tiles_x * pl.tiles_y;  // empty splits flush zeros
       S.tiles_per_split = S.ntiles > 0 ? nint_cdiv(S.ntiles, w.splits) : 1;   // spread what is there evenly over the planned splits
       a.NTC = w.NTC; a.J = w.J; a.TG = w.TG;
       a.taps = ly->k * w.KX;
-      if (w.wide_nct) {                        // the 8-wave 128-column kernel, one launch per source
-        a.nparts = 1;
-        WgLaunch* out = &jp.launch[jp.n++];
-        rc = ly->k == 3 ? launch_wgrad_wide<3, 4>(a, w.splits, w.wcols, out)
-           : (ly->k == 5 ? launch_wgrad_wide<5, 2>(a, w.splits, w.wcols, out) : launch_wgrad_wide<7, 1>(a, w.splits, w.wcols, out));
-        if (rc != NINT_OK) return rc;
-      } else if (!pl.merged || part == 1) {    // separate launches per source, or both sources in one
+      if (!pl.merged || part == 1) {           // a launch per source, or both sources in one: filled from the row
         a.nparts = pl.merged ? 2 : 1;
-        const int nblk = pl.merged ? a.s[0].nblk + a.s[1].nblk : S.nblk;
-        WgLaunch* out = &jp.launch[jp.n++];
-        rc = dtype == NINT_BF16 ? dispatch_wgrad<NINT_BF16>(a, w, nblk, out) : dispatch_wgrad<NINT_F32>(a, w, nblk, out);
-        if (rc != NINT_OK) return rc;
+        const int gy = pl.merged ? pl.part[0].cols + w.cols : w.cols;
+        jp.launch[jp.n++] = WgLaunch{w.row->kern[dtype], w.splits, gy, w.row->block, w.row->lds[dtype], a};
       }
       ReduceEntry& E = rt.e[rt.n++];
       E.part = S.partial; E.dW = jb.dW; E.db = part == 0 ? jb.db : nullptr;
       E.Cx = ly->Cx; E.Ch = ly->Ch; E.Ch16 = ly->Ch16; E.k = ly->k; E.NB = pl.NB; E.CB = w.CB; E.NTC = w.NTC; E.J = w.J;
       E.splits = w.splits; E.is_h = part; E.xfold = ly->xfold; E.TG = w.TG; E.JG = w.JG;
       E.blk_begin = blk;
-      blk += (unsigned)((size_t)pl.NB * w.CB * w.TG * w.JG * 1024 / 256);
+      blk += (unsigned)(w.slab() / 256);
       E.waves = 4;                               // 4 waves share the splits of a 256-element line (16-wave workgroups for the
                                                  // many-split entries made every entry's workgroup 1024 threads: 46 -> 40 us)
       if (E.waves * 64 > red_threads) red_threads = E.waves * 64;
@@ -862,4 +846,32 @@ extern "C" int nint_conv_wgrad(const nint_layer* ly, const nint_geom* g, int dty
   int rc = nint_internal_wgrad_plan(&jb, 1, g, dtype, partial, partial_bytes, n_cu, &jp, &fold);
   if (rc == NINT_OK) rc = nint_internal_wgrad_enqueue(&jp, stream);
   return rc != NINT_OK ? rc : nint_internal_wgrad_fold_enqueue(&fold, stream);
+}
+
+// ------------------------------------------------------------------------------ the plan, for tests and tools
+extern "C" int nint_debug_wgrad_plan(const nint_layer* ly, const nint_geom* g, int dtype, int N, int h_skip, int n_cu,
+                                     nint_wgrad_plan_rec* out) {
+  if (!out) return NINT_E_ARG;
+  float* const base = (float*)(uintptr_t)4096;              // made up: the planner dereferences no job pointer
+  const WgJob jb = {ly, N, base, base, base, base, base, h_skip};
+  WgJobPlan jp; WgFoldPlan fold;
+  const int rc = nint_internal_wgrad_plan(&jb, 1, g, dtype, base, ly ? nint_wgrad_workspace_bytes(ly, dtype, n_cu) : 0, n_cu, &jp, &fold);
+  if (rc != NINT_OK) return rc;
+  *out = nint_wgrad_plan_rec{};
+  out->n_launch = jp.n; out->n_fold = fold.t.n; out->fold_grid = (int)fold.grid; out->fold_block = fold.block;
+  for (int i = 0; i < jp.n; ++i) {
+    const WgLaunch& l = jp.launch[i];
+    nint_wgrad_launch_rec& r = out->launch[i];
+    for (const WgRow& row : wg_rows)               // the instance, from the handle the launch carries
+      if (row.kern[dtype] == l.kern) { r.family = row.block / 64; r.KS = row.KS; r.NTC = row.NTC; r.JW = row.JW; r.KX = row.KX; }
+    r.nparts = l.a.nparts; r.gx = l.gx; r.gy = l.gy; r.block = l.block; r.lds = (int)l.lds;
+    for (int q = 0; q < l.a.nparts; ++q) {
+      const WgSrc& S = l.a.s[q];
+      r.src[q] = nint_wgrad_src_rec{S.CB, S.JG, l.a.TG, S.nblk, S.ntiles, S.tiles_per_split, S.want_db, jp.n == 1 ? q : i, S.partial - base};
+    }
+  }
+  for (int i = 0; i < fold.t.n; ++i) {
+    out->fold[i].blk_begin = (int)fold.t.e[i].blk_begin; out->fold[i].splits = fold.t.e[i].splits; out->fold[i].waves = fold.t.e[i].waves;
+  }
+  return NINT_OK;
 }

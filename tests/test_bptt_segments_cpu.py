@@ -84,7 +84,7 @@ def test_head_entries_are_declared_bound_and_check_their_switch():
         assert re.search(rf"\bint\s+{name}\s*\(", src), name
         assert len(_lib.SIGNATURES[name][1]) == nargs, name      # the old entries keep their signatures
         assert hasattr(lib, name)
-    assert "#define NINT_VERSION 112" in src and _lib.NINT_VERSION == 112       # additive: the version stays
+    assert "#define NINT_VERSION 113" in src and _lib.NINT_VERSION == 113       # (113: nint_debug_wgrad_plan was added)
     g = _lib.NintGeom()
     assert lib.nint_geom_make(C.byref(g), 9, 17, 2) == 0
     E_ARG, E_ALIGN = -1, -4

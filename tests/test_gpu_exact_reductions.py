@@ -7,7 +7,7 @@ split, a swapped tap, an unflushed empty split or an h skip of the wrong length 
 1.5 M-term sums cannot see it.  Every destination and the split-K partial buffer start as NaN, so an element nobody wrote
 shows too, and a second run must give identical bits (fixed fold order).
 
-(a) nint_conv_wgrad directly, one case per instantiated (k, NTC, JW, KX) key of dispatch_wgrad in both storage types, the
+(a) nint_conv_wgrad directly, one case per reachable row (k, NTC, JW, KX) of wgrad.hip's instance table in both storage types, the
     folded x source, the 8-wave kernel, on ragged grids, with N = 1, and at the real geometries.
 (b) layer 0's weight gradient as the product computes it: SeqEngine.backward(parts = 2) after a parts = 1 call, on slabs
     overwritten with integers -- the h source skipping the zero state (has_init = 0), a given initial state, T = B = 1.
@@ -87,7 +87,7 @@ def _direct(lib, Cx, Ch, k, N, H, W, dtype, xfold=False, wide=0, seed=0):
     ref_W, ref_b = WA.wgrad_ref(dG, x, h, k, xfold=xfold, has_init=True, B=1)
     outs = []
     for _ in range(2):
-        part = torch.full((nbytes // 4 + 16,), NAN, device="cuda")
+        part = torch.full((nbytes // 4,), NAN, device="cuda")
         dW = torch.full((4 * Ch, Cx + Ch, k, k), NAN, device="cuda")
         db = torch.full((4 * Ch,), NAN, device="cuda")
         _lib.check(lib.nint_conv_wgrad(C.byref(ly), C.byref(g), dt, N, C.c_void_p(dG_s.data_ptr()), C.c_void_p(xs.data_ptr()),
@@ -102,7 +102,8 @@ def _direct(lib, Cx, Ch, k, N, H, W, dtype, xfold=False, wide=0, seed=0):
     print(f"  {tag}: dW, db bit-equal to the f64 sum (max |dW| {float(ref_W.abs().max()):.0f})", flush=True)
 
 
-# (dtype, xfold, wide, Cx, Ch, k): the dispatch key (k, NTC, JW, KX) each case reaches, by wg_plan's host arithmetic
+# (dtype, xfold, wide, Cx, Ch, k), named by the instance -- 4-wave (k, NTC, JW, KX) or 8-wave <k, NCT> -- it is there for:
+# tests/test_wgrad_plan_cpu.py asks the planner that each case reaches it and that no reachable instance is left out
 KEYS = {
     "bf16 (5,1,7,5) 62->64": ("bf16", False, 1, 62, 64, 5),
     "bf16 (3,2,5,3) 64->64": ("bf16", False, 1, 64, 64, 3),

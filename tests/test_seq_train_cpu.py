@@ -34,7 +34,7 @@ def test_sequence_entries_exist_and_reject_bad_arguments_without_a_gpu():
     lib = _lib.load()
     for name in ("nint_head_fwd_seq", "nint_head_bwd_seq", "nint_head_loss_seq_fused"):
         assert name in _lib.SIGNATURES and hasattr(lib, name)
-    assert lib.nint_version() == 112
+    assert lib.nint_version() == 113
     g = _lib.NintGeom()
     assert lib.nint_geom_make(C.byref(g), 12, 20, 1) == 0
     gp = C.byref(g)

@@ -24,7 +24,7 @@ def test_binding_constants_match_the_header():
     assert (val("NINT_SKILL_PIX"), val("NINT_SKILL_SAMPLE"), val("NINT_SKILL_MAX_N")) == \
         (_lib.NINT_SKILL_PIX, _lib.NINT_SKILL_SAMPLE, _lib.NINT_SKILL_MAX_N) == (5, 8, 64)
     assert (inference.NINT_SKILL_PIX, inference.NINT_SKILL_SAMPLE) == (5, 8)
-    assert val("NINT_VERSION") == _lib.NINT_VERSION == 112
+    assert val("NINT_VERSION") == _lib.NINT_VERSION == 113
 
 
 def test_scratch_bytes_is_positive_and_monotone(lib):

@@ -48,7 +48,7 @@ def test_state_copy_is_declared_and_bound():
         assert hasattr(_lib.load(), name)
     res, args = _lib.SIGNATURES["nint_state_copy"]
     assert len(args) == 12
-    assert "#define NINT_VERSION 112" in src and _lib.NINT_VERSION == 112       # additive: the version stays
+    assert "#define NINT_VERSION 113" in src and _lib.NINT_VERSION == 113       # (113: nint_debug_wgrad_plan was added)
 
 
 def test_state_copy_rejects_bad_arguments_without_a_gpu():

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Device assembly of one csrc file in two source directories, compared kernel by kernel.
 
-usage: tools/asm_diff.py FILE.hip OLD_CSRC NEW_CSRC [-DNAME ...] [--keep=DIR]
+usage: tools/asm_diff.py FILE.hip OLD_CSRC NEW_CSRC [-DNAME ...] [--keep=DIR] [--rename=REGEX=REPL]
 
 Each side is compiled with the flags of nasa-niswan_amd/build.py plus ``--cuda-device-only -S`` (its own directory on the
 include path, so each side sees its own nint_common.h).  Per mangled kernel name two things are compared by plain equality:
@@ -9,6 +9,12 @@ include path, so each side sees its own nint_common.h).  Per mangled kernel name
 * the instruction stream: the lines from the kernel's label to the end of the function, comments and assembler directives
   dropped, the function index taken out of ``.LBB<function>_<block>`` labels (it moves when a kernel is added above);
 * the resource block: the ``.amdhsa_*`` lines of its ``.amdhsa_kernel`` descriptor.
+
+A device function that a kernel calls out of line (a lambda the compiler did not inline) is compared in the same way, by its
+instruction stream alone, and counted with the kernels.
+
+``--rename=REGEX=REPL`` (re.sub on the OLD side's mangled names, before the two sides are matched) pairs kernels whose name
+moved for a reason that cannot touch their code, such as a template parameter that only ever had one value being dropped.
 
 Printed: the kernel count on each side, the names on one side only, and the kernels that differ (instruction counts and the
 resource lines that changed).  Exit status 0 where both sides hold the same kernels and none differs, 1 otherwise.  A refactor
@@ -46,14 +52,16 @@ _LBB = re.compile(r"\.LBB\d+_(\d+)")
 
 
 def kernels(path):
-    """mangled kernel name -> (instruction lines, resource lines)"""
+    """mangled name -> (instruction lines, resource lines) of every kernel, and of every device function a kernel calls out of
+    line (no resource block of its own: an empty list)"""
     lines = open(path).read().splitlines()
     res, cur = {}, None
     for ln in lines:
         s = ln.split(";", 1)[0].strip()
-        if s.startswith(".amdhsa_kernel "):
+        if s.startswith(".type") and s.endswith(",@function"):
+            res.setdefault(s.split()[1].rsplit(",", 1)[0], [])
+        elif s.startswith(".amdhsa_kernel "):
             cur = s.split()[1]
-            res[cur] = []
         elif s == ".end_amdhsa_kernel":
             cur = None
         elif cur is not None and s.startswith(".amdhsa_"):
@@ -86,9 +94,10 @@ def demangle(names):
 
 
 def main(argv):
-    args = [a for a in argv if not a.startswith("-D") and not a.startswith("--keep")]
+    args = [a for a in argv if not a.startswith("-D") and not a.startswith("--keep") and not a.startswith("--rename")]
     defines = [a for a in argv if a.startswith("-D")]
     keep = [a.split("=", 1)[1] for a in argv if a.startswith("--keep=")]
+    renames = [a.split("=", 1)[1].rsplit("=", 1) for a in argv if a.startswith("--rename=")]
     if len(args) != 3:
         raise SystemExit(__doc__)
     name, old, new = args[0], os.path.abspath(args[1]), os.path.abspath(args[2])
@@ -100,6 +109,12 @@ def main(argv):
     with ThreadPoolExecutor(max_workers=2) as ex:
         cmds = list(ex.map(lambda p: compile_asm(B, name, p[0], p[1], defines), zip((old, new), outs)))
     ko, kn = kernels(outs[0]), kernels(outs[1])
+    for rx, repl in renames:                  # names, and the symbols that instructions refer to (a call out of line)
+        renamed = {re.sub(rx, repl, n): ([re.sub(rx.lstrip("^"), repl, ln) for ln in body], r) for n, (body, r) in ko.items()}
+        if len(renamed) != len(ko):
+            raise SystemExit(f"--rename={rx}={repl} maps two kernels of the old side onto one name")
+        print(f"# old names through re.sub({rx!r}, {repl!r}): {sum(n not in ko for n in renamed)} renamed")
+        ko = renamed
     if scratch:
         scratch.cleanup()
     flags = " ".join(a for a in cmds[0][1:-3] if not a.startswith("-I"))
