@@ -119,6 +119,10 @@ constexpr int xchg_rounds(int EPI, int WK, int NTW, int MT) {
 // pieces (32 + 8 registers), 4 where the waves slice K (the compiler otherwise spills inside the K loop), and the K-sliced
 // fused step keeps the DMA for the same reason.  The others are allocated for three or four workgroups per CU and would lose
 // one (tools/regs.py, profiles/halo_fill_asm.txt).  The merged kernels of two workgroups per CU stage in every body they carry.
+// The body is ONE function on purpose (map of its steps: DESIGN.md 4.1).  A step that touches the body's state (acc, the tap, the
+// ring pointer, the tile geometry) as a function or lambda of its own takes it by reference; the locals then stay in memory through
+// the simplification passes that run before inlining, and the K loops come out with other registers, waits and spills (each step
+// tried alone: profiles/conv_body_refactor_asm.txt).  What is shared is a pure function of values (halo_src, lstm_*_elem) or a macro.
 template <int DT, int EPI, int WN, int WK, int NTW, int MT, int FILL = -1>
 __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, char* smem, const int bx_, const int by_, const int nbx_) {
   static_assert(WN * WK == 4, "four waves per workgroup");
@@ -192,6 +196,11 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, char* smem, c
   const char* base1 = a.src1 ? a.src1 + (long)img * a.img_stride1 +
                                    ((long)(y0 + a.P - p) * a.Wh + (x0 + a.P - p)) * a.pix_stride1
                              : nullptr;
+  // halo_src: where 16-byte quarter q of chunk c of halo pixel (hy, hx) comes from -- the ONE source-address rule of both fills
+  auto halo_src = [&](int hy, int hx, int c, int q) __attribute__((always_inline)) {
+    return (c < a.nchunk0) ? base0 + ((long)hy * a.Wh + hx) * a.pix_stride0 + c * 64 + q * 16
+                           : base1 + ((long)hy * a.Wh + hx) * a.pix_stride1 + (c - a.nchunk0) * 64 + q * 16;
+  };
   const int a_lane_off = (lane >> 4) * plane + (lane & 15) * 16;
   // local accumulator row i of K-slice wk is tile row (i + wk*Q) % MT: the rows a wave owns after the
   // K-slice exchange are then always its local rows 0..Q-1 (static register indexing)
@@ -210,6 +219,7 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, char* smem, c
   // 8-row tiles have no registers to spare and fetch it at the top of the epilogue, before the first store: vmcnt
   // retires in order and counts stores too, so a load issued between the epilogue's stores would make every row wait
   // for the previous row's stores to be acknowledged (measured: 22 us of epilogue per round).
+  // (load_cprev and load_old are twins of NINT_TILE_ROW in the epilogue: the same row, with xo in the lane's column)
   constexpr bool EARLY = MT <= 4;
   f32x4_t cpv[EPI == EPI_LSTM ? Q : 1][EPI == EPI_LSTM ? NTW / 4 : 1];
   auto load_cprev = [&]() __attribute__((always_inline)) {
@@ -278,10 +288,7 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, char* smem, c
           const int q = lane & 3;
           const int hy = (int)__umulhi((unsigned)hs, magic_hwt);
           const int hx = hs - hy * HWt;
-          const int c = c_begin + cl;
-          const char* src = (c < a.nchunk0)
-              ? base0 + ((long)hy * a.Wh + hx) * a.pix_stride0 + c * 64 + q * 16
-              : base1 + ((long)hy * a.Wh + hx) * a.pix_stride1 + (c - a.nchunk0) * 64 + q * 16;
+          const char* src = halo_src(hy, hx, c_begin + cl, q);
           // (default cache policy: neighbouring tiles re-read the halo pixels; a non-temporal fill measured -8 % on the step)
           fv[i] = *(const u32x4_t*)src;
           fo[i] = (cl * 4 + q) * plane + hp * 16;
@@ -305,10 +312,7 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, char* smem, c
       const int q = cq & 3, cl = cq >> 2;
       const int hy = (int)__umulhi((unsigned)hp, magic_hwt);
       const int hx = hp - hy * HWt;
-      const int c = c_begin + cl;
-      const char* src = (c < a.nchunk0)
-          ? base0 + ((long)hy * a.Wh + hx) * a.pix_stride0 + c * 64 + q * 16
-          : base1 + ((long)hy * a.Wh + hx) * a.pix_stride1 + (c - a.nchunk0) * 64 + q * 16;
+      const char* src = halo_src(hy, hx, c_begin + cl, q);
       __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
                                        (__attribute__((address_space(3))) void*)(smem + (size_t)ub * 16), 16, 0, 0);
     // (default cache policy: neighbouring tiles re-read the halo pixels; a non-temporal fill measured -8 % on the step)
@@ -423,18 +427,21 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, char* smem, c
       }
 #undef NINT_K_STEP
     } else {
-  int s = s_lo;
+      // The ONE step body of the loop and of its remainder: the MT A fragments of tap (tyy, txx), MT x NTW MFMAs (swapped: D[channel][pixel]).
+      // (A macro: a lambda captures acc and the tap by reference, and the compiler then BRANCHES on the tap advance in every 4-row K loop.)
+#define NINT_PLAIN_STEP(BQ)                                                                                  \
+      {                                                                                                      \
+        const char* Ab = smem + (size_t)cl * chunk_bytes + (tyy * HWt + txx + xoff) * 16 + a_lane_off;       \
+        u32x4_t af[MT];                                                                                      \
+        _Pragma("unroll") for (int i = 0; i < MT; ++i) af[i] = *(const u32x4_t*)(Ab + rowoff[i]);            \
+        _Pragma("unroll") for (int i = 0; i < MT; ++i)                                                       \
+          _Pragma("unroll") for (int j = 0; j < NTW; ++j) acc[i][j] = mma_step<DT>(BQ[j], af[i], acc[i][j]); \
+      }
+      int s = s_lo;
       for (; s + BD <= s_hi; s += BD) {
 #pragma unroll
         for (int d = 0; d < BD; ++d) {
-          const char* Ab = smem + (size_t)cl * chunk_bytes + (tyy * HWt + txx + xoff) * 16 + a_lane_off;
-          u32x4_t af[MT];
-#pragma unroll
-          for (int i = 0; i < MT; ++i) af[i] = *(const u32x4_t*)(Ab + rowoff[i]);
-#pragma unroll
-          for (int i = 0; i < MT; ++i)
-#pragma unroll
-            for (int j = 0; j < NTW; ++j) acc[i][j] = mma_step<DT>(bq[d][j], af[i], acc[i][j]);   // swapped: D[channel][pixel]
+          NINT_PLAIN_STEP(bq[d])
 #pragma unroll
           for (int j = 0; j < NTW; ++j) bq[d][j] = *(const u32x4_t*)(Bn + blane + j * 1024);
           NINT_B_ADVANCE()
@@ -445,17 +452,11 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, char* smem, c
 #pragma unroll
       for (int d = 0; d < BD - 1; ++d) {
         if (s + d < s_hi) {
-          const char* Ab = smem + (size_t)cl * chunk_bytes + (tyy * HWt + txx + xoff) * 16 + a_lane_off;
-          u32x4_t af[MT];
-#pragma unroll
-          for (int i = 0; i < MT; ++i) af[i] = *(const u32x4_t*)(Ab + rowoff[i]);
-#pragma unroll
-          for (int i = 0; i < MT; ++i)
-#pragma unroll
-            for (int j = 0; j < NTW; ++j) acc[i][j] = mma_step<DT>(bq[d][j], af[i], acc[i][j]);   // swapped: D[channel][pixel]
+          NINT_PLAIN_STEP(bq[d])
           if (++txx == kx) { txx = 0; if (++tyy == k) { tyy = 0; ++cl; } }
         }
       }
+#undef NINT_PLAIN_STEP
     }
     }   // segment
   }
@@ -508,6 +509,16 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, char* smem, c
   const int px = lane & 15;
   const int c4 = 4 * (lane >> 4);
   const int x = x0 + px;
+  // The ONE row rule of the three epilogues.  Local accumulator row I of this wave is tile row rt: grid row y, column offset xo inside
+  // the tile (a merged tile's second column: 16 pixels on); OK = this lane's pixel is inside the grid; NINT_ROWPIX = the row's first
+  // pixel.  (Macros: as a lambda or a function the rule changes the register allocation of the K loops -- the body's locals are then
+  // captured by reference and stay in memory through the first simplification passes; profiles/conv_body_refactor_asm.txt.
+  // load_cprev and load_old above are its twins: the same row, with xo folded into the lane's column instead of the row base.)
+#define NINT_TILE_ROW(I, OK)                                                     \
+  const int rt = ((I) + wk * Q) % MT;          /* row tile of the workgroup */   \
+  const int y = y0 + rdy(rt), xo = rdx(rt);                                      \
+  const bool OK = y < a.H && x + xo < a.W;
+#define NINT_ROWPIX (((size_t)img * a.H + y) * a.W + xo)
   if constexpr (EPI == EPI_LSTM) {
 #pragma unroll
     for (int cb = 0; cb < NTW / 4; ++cb) {
@@ -521,10 +532,8 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, char* smem, c
       const unsigned lo_g = (unsigned)(x * Gc + cblock * 64) + (DT == NINT_BF16 ? (unsigned)(chb + (odd ? 32 : 0)) : (unsigned)c4);
 #pragma unroll
       for (int i = 0; i < Q; ++i) {
-        const int rt = (i + wk * Q) % MT;        // row tile of the workgroup
-        const int y = y0 + rdy(rt), xo = rdx(rt);
-        const bool ok = y < a.H && x + xo < a.W;   // (the lane exchange below needs every lane: no divergent block)
-        const size_t rowpix = ((size_t)img * a.H + y) * a.W + xo;   // (a merged tile's second column: 16 pixels on)
+        NINT_TILE_ROW(i, ok)                       // (the lane exchange below needs every lane: no divergent block)
+        const size_t rowpix = NINT_ROWPIX;
         const f32x4_t cp = cpv[i][cb];
         f32x4_t gi, gf, gg, go, cn, hn;
         // A channel block that reaches past Ch (Ch % 16 != 0: its last block only; a wave-uniform test, never taken where
@@ -538,12 +547,8 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, char* smem, c
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          gi[r] = sigmoidf_(acc[i][cb * 4 + 0][r]);      // (bias already in the accumulator)
-          gf[r] = sigmoidf_(acc[i][cb * 4 + 1][r]);
-          gg[r] = tanhf_(acc[i][cb * 4 + 2][r]);
-          go[r] = sigmoidf_(acc[i][cb * 4 + 3][r]);
-          cn[r] = fmaf(cp[r], gf[r], gi[r] * gg[r]);   // model.py:228 (the association is pinned: every kernel family agrees bit for bit)
-          hn[r] = go[r] * tanhf_(cn[r]);               // model.py:229
+          const LstmCell l = lstm_cell_elem(acc[i][cb * 4 + 0][r], acc[i][cb * 4 + 1][r], acc[i][cb * 4 + 2][r], acc[i][cb * 4 + 3][r], cp[r]);
+          gi[r] = l.i; gf[r] = l.f; gg[r] = l.g; go[r] = l.o; cn[r] = l.c; hn[r] = l.h;   // (bias already in the accumulator)
         }
         if (ok) {
           *(f32x4_t*)(a.c_out + rowpix * a.Chp + lo_c) = cn;
@@ -613,10 +618,8 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, char* smem, c
       f32x4_t cpq[RB][NTW], cnq[RB][NTW], dcq[RB][NTW];
 #pragma unroll
       for (int ii = 0; ii < RB; ++ii) {
-        const int rt = (ib + ii + wk * Q) % MT;
-        const int y = y0 + rdy(rt), xo = rdx(rt);
-        const bool okp = y < a.H && x + xo < a.W;
-        const size_t rowpix = ((size_t)img * a.H + y) * a.W + xo;
+        NINT_TILE_ROW(ib + ii, okp)
+        const size_t rowpix = NINT_ROWPIX;
 #pragma unroll
         for (int j = 0; j < NTW; ++j) {
           int ch0;
@@ -634,6 +637,8 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, char* smem, c
             oldv[ii][j] = PK::ld(a.pw_old, pix * a.Chp + ch0 + c4);
           }
           if (kind == 0 || kind == 3) continue;
+          // this side's operands (twin: the compute pass below selects Gc, Cp, dG and dc by the same `lo`; one struct filled once
+          // per tile moved 18 kernels out of their register allocation)
           const bool lo = kind == 2;
           const int Gc = 4 * (lo ? a.lo_Ch16 : a.Ch16), Cp = lo ? a.C0p : a.Chp;
           const char* gp = lo ? a.lo_gates : a.pw_gates;
@@ -652,16 +657,15 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, char* smem, c
 #pragma unroll
       for (int ii = 0; ii < RB; ++ii) {
         const int i = ib + ii;
-        const int rt = (i + wk * Q) % MT;
-        const int y = y0 + rdy(rt), xo = rdx(rt);
-        const bool okp = y < a.H && x + xo < a.W;
-        const size_t rowpix = ((size_t)img * a.H + y) * a.W + xo;
+        NINT_TILE_ROW(i, okp)
+        const size_t rowpix = NINT_ROWPIX;
 #pragma unroll
         for (int j = 0; j < NTW; ++j) {
           int ch0;
           const int kind = tile_kind(j, ch0);
           if (!okp || kind < 0) continue;
           const f32x4_t dhv = acc[i][j] + PK::up(oldv[ii][j]);
+          // kinds 0 and 3: the stores of the EPI_DGRAD epilogue below (twins; shared helpers cost 14 kernels their allocation)
           if (kind == 0) {
             if (a.out0) store_vec4<DT>(a.out0 + rowpix * a.C0p * Elem<DT>::ES, (unsigned)(x * a.C0p + ch0 + c4), dhv);
             continue;
@@ -677,14 +681,8 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, char* smem, c
           f32x4_t o_i, o_f, o_g, o_o, dcp;
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
-            const float tc = tanhf_(cn[e]);
-            const float dct = dcv[e] + dhv[e] * go[e] * (1.f - tc * tc);
-            const float d_o = dhv[e] * tc;
-            o_i[e] = dct * gg[e] * gi[e] * (1.f - gi[e]);
-            o_f[e] = dct * cp[e] * gf[e] * (1.f - gf[e]);
-            o_g[e] = dct * gi[e] * (1.f - gg[e] * gg[e]);
-            o_o[e] = d_o * go[e] * (1.f - go[e]);
-            dcp[e] = dct * gf[e];
+            const LstmBwd b = lstm_bwd_elem(gi[e], gf[e], gg[e], go[e], cp[e], cn[e], dhv[e], dcv[e]);
+            o_i[e] = b.d_i; o_f[e] = b.d_f; o_g[e] = b.d_g; o_o[e] = b.d_o; dcp[e] = b.dc_prev;
           }
           char* grow = (lo ? a.lo_dG : a.pw_dG) + ((((size_t)img * a.Hh) + (y + a.P)) * a.Wh + (xo + a.P)) * Gc * Elem<DT>::ES;
           const unsigned ob = (unsigned)(x * Gc + (ch0 >> 4) * 64 + c4);
@@ -704,10 +702,9 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, char* smem, c
     const bool rmw = a.out0 && !a.out0_overwrite;
 #pragma unroll
     for (int i = 0; i < Q; ++i) {
-      const int rt = (i + wk * Q) % MT;
-      const int y = y0 + rdy(rt), xo = rdx(rt);
-      if (y < a.H && x + xo < a.W) {
-        const size_t rowpix = ((size_t)img * a.H + y) * a.W + xo;
+      NINT_TILE_ROW(i, ok)
+      if (ok) {
+        const size_t rowpix = NINT_ROWPIX;
 #pragma unroll
         for (int j = 0; j < NTW; ++j) {
           const int n = (nt0 + j) * 16 + c4;
@@ -727,6 +724,8 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, char* smem, c
       }
     }
   }
+#undef NINT_TILE_ROW
+#undef NINT_ROWPIX
   NINT_STAMP_AT(3)
 }
 

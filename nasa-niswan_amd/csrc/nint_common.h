@@ -125,6 +125,35 @@ __device__ __forceinline__ float sigmoidf_(float x) { return rcpf_(1.0f + __expf
 // inf -> rcp 0 -> -1; underflow -> 0 -> rcp(1) -> 1); absolute error ~1e-7 (cancellation near 0 is absolute, not relative)
 __device__ __forceinline__ float tanhf_(float x) { return fmaf(2.0f, rcpf_(1.0f + __expf(-2.0f * x)), -1.0f); }
 
+// One element of the LSTM cell (model.py:223-229) from its four pre-activations (bias included) and c_{t-1}.  The ONE definition:
+// the MFMA epilogue (conv_igemm.hip: epi_lstm), stencil.hip and tiny_gemm.hip call it, so every kernel family agrees bit for bit
+// (oracle/stored_audit.py relies on that).  The association of c is pinned: fmaf(c_prev, f, i * g).  A padding channel's
+// `pad ? 0.f : acc` select stays at the caller.
+struct LstmCell { float i, f, g, o, c, h; };
+__device__ __forceinline__ LstmCell lstm_cell_elem(float ai, float af, float ag, float ao, float c_prev) {
+  LstmCell e;
+  e.i = sigmoidf_(ai);
+  e.f = sigmoidf_(af);
+  e.g = tanhf_(ag);
+  e.o = sigmoidf_(ao);
+  e.c = fmaf(c_prev, e.f, e.i * e.g);        // model.py:228
+  e.h = e.o * tanhf_(e.c);                   // model.py:229
+  return e;
+}
+// What the gate stash holds for a channel with zero weights and zero bias (pre-activation 0): i, f, g, o = 0.5, 0.5, 0, 0.5
+constexpr float lstm_stash_zero_w(int gate) { return gate == 2 ? 0.f : 0.5f; }
+
+// One element of the pointwise LSTM backward (autograd of model.py:222-229) from the stashed gates, c_{t-1}, c_t, d/dh_t and d/dc_t:
+//   dct = dc + dh*o*(1 - tanh(c_t)^2);  dG = (dct*g*i(1-i), dct*c_{t-1}*f(1-f), dct*i*(1-g^2), dh*tanh(c_t)*o(1-o));  dc_{t-1} = dct*f
+// Called by lstm_bwd_pointwise_body below and by the fused dgrad epilogue (conv_igemm.hip: epi_dgrad_pw).
+struct LstmBwd { float d_i, d_f, d_g, d_o, dc_prev; };
+__device__ __forceinline__ LstmBwd lstm_bwd_elem(float i, float f, float g, float o, float c_prev, float c, float dh, float dc) {
+  const float tc = tanhf_(c);
+  const float dct = dc + dh * o * (1.f - tc * tc);
+  const float d_o = dh * tc;
+  return {dct * g * i * (1.f - i), dct * c_prev * f * (1.f - f), dct * i * (1.f - g * g), d_o * o * (1.f - o), dct * f};
+}
+
 // LSTM pointwise backward (pointwise.hip: lstm_bwd_pointwise_kernel; also a problem of conv_bwd_multi_kernel, nint_seq.wave = 4):
 // block `blk` of `nblk` 256-thread blocks, grid-stride over (pixel, 4 consecutive hidden channels).
 struct PwArgs {
@@ -177,14 +206,8 @@ __device__ __forceinline__ void lstm_bwd_pointwise_body(const PwArgs& a, size_t 
       f32x4_t o_i, o_f, o_g, o_o, dcp;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        const float tc = tanhf_(cn[u][e]);
-        const float dct = dcv[u][e] + dhv[u][e] * go[u][e] * (1.f - tc * tc);
-        const float d_o = dhv[u][e] * tc;
-        o_i[e] = dct * gg[u][e] * gi[u][e] * (1.f - gi[u][e]);
-        o_f[e] = dct * cp[u][e] * gf[u][e] * (1.f - gf[u][e]);
-        o_g[e] = dct * gi[u][e] * (1.f - gg[u][e] * gg[u][e]);
-        o_o[e] = d_o * go[u][e] * (1.f - go[u][e]);
-        dcp[e] = dct * gf[u][e];
+        const LstmBwd b = lstm_bwd_elem(gi[u][e], gf[u][e], gg[u][e], go[u][e], cp[u][e], cn[u][e], dhv[u][e], dcv[u][e]);
+        o_i[e] = b.d_i; o_f[e] = b.d_f; o_g[e] = b.d_g; o_o[e] = b.d_o; dcp[e] = b.dc_prev;
       }
       store_vec4<DT>(a.dG, ob[u], o_i);
       store_vec4<DT>(a.dG, ob[u] + 16, o_f);

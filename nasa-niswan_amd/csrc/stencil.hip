@@ -166,12 +166,9 @@ __global__ __launch_bounds__(256) void stencil_lstm_kernel(StencilArgs a_) {
     for (int e = 0; e < 4; ++e) {
       // a padding channel (zero weights) has the pre-activation 0 with finite data and inf * 0 = NaN next to an inf: pinned to 0
       const bool pad = c4 + e >= Ch;
-      gi[e] = sigmoidf_(pad ? 0.f : acc[c4 + e]);
-      gf[e] = sigmoidf_(pad ? 0.f : acc[8 + c4 + e]);
-      gg[e] = tanhf_(pad ? 0.f : acc[16 + c4 + e]);
-      go[e] = sigmoidf_(pad ? 0.f : acc[24 + c4 + e]);
-      cn[e] = fmaf(cp[e], gf[e], gi[e] * gg[e]);       // model.py:228 (same association as conv_igemm.hip)
-      hn[e] = go[e] * tanhf_(cn[e]);                   // model.py:229
+      const LstmCell l = lstm_cell_elem(pad ? 0.f : acc[c4 + e], pad ? 0.f : acc[8 + c4 + e], pad ? 0.f : acc[16 + c4 + e],
+                                        pad ? 0.f : acc[24 + c4 + e], cp[e]);
+      gi[e] = l.i; gf[e] = l.f; gg[e] = l.g; go[e] = l.o; cn[e] = l.c; hn[e] = l.h;
     }
     if (c4 < Ch) {
       *(f32x4_t*)(co + c4) = cn;
@@ -184,10 +181,11 @@ __global__ __launch_bounds__(256) void stencil_lstm_kernel(StencilArgs a_) {
       store_vec4<DT>(gs, 48 + c4, go);
       // columns 8 .. 15 of every gate block: the values of a channel with zero weights, so that the backward kernels read
       // finite numbers there (the stash is not pre-initialised)
-      store_vec4<DT>(gs, 0 + 8 + c4, (f32x4_t){0.5f, 0.5f, 0.5f, 0.5f});
-      store_vec4<DT>(gs, 16 + 8 + c4, (f32x4_t){0.5f, 0.5f, 0.5f, 0.5f});
-      store_vec4<DT>(gs, 32 + 8 + c4, (f32x4_t){0.f, 0.f, 0.f, 0.f});
-      store_vec4<DT>(gs, 48 + 8 + c4, (f32x4_t){0.5f, 0.5f, 0.5f, 0.5f});
+#pragma unroll
+      for (int gate = 0; gate < 4; ++gate) {
+        const float z = lstm_stash_zero_w(gate);
+        store_vec4<DT>(gs, 16 * gate + 8 + c4, (f32x4_t){z, z, z, z});
+      }
     }
   }
 }

@@ -155,11 +155,13 @@ __global__ __launch_bounds__(256) void tiny_lstm_kernel(TinyArgs a) {
     for (int t2 = 0; t2 < 2; ++t2) {
       // a padding channel (zero weights) has the pre-activation 0 with finite data and inf * 0 = NaN next to an inf: pinned to 0
       const bool pad = ch0 + t2 >= Ch;
+      // Written out: the twin of lstm_cell_elem (nint_common.h), same operations in the same association.  Calling it here moved
+      // the pad selects through the activations' multiplies in this kernel's MFMA loop (profiles/conv_body_refactor_asm.txt).
       gi[t2] = sigmoidf_(pad ? 0.f : acc[r][t2][0]);
       gf[t2] = sigmoidf_(pad ? 0.f : acc[r][t2][1]);
       gg[t2] = tanhf_(pad ? 0.f : acc[r][t2][2]);
       go[t2] = sigmoidf_(pad ? 0.f : acc[r][t2][3]);
-      cn[t2] = fmaf(t2 ? cp1 : cp0, gf[t2], gi[t2] * gg[t2]);   // model.py:228 (same association as conv_igemm.hip)
+      cn[t2] = fmaf(t2 ? cp1 : cp0, gf[t2], gi[t2] * gg[t2]);   // model.py:228
       hn[t2] = go[t2] * tanhf_(cn[t2]);                        // model.py:229
     }
     if (ch0 < Ch) {                                            // (a half-empty pair: its padding channel is an exact zero)
@@ -174,10 +176,8 @@ __global__ __launch_bounds__(256) void tiny_lstm_kernel(TinyArgs a) {
       store_pair<DT>(gs, 32 + ch0, gg[0], gg[1]);
       store_pair<DT>(gs, 48 + ch0, go[0], go[1]);
       // columns 8 .. 15 of every gate block: the values of a channel with zero weights (the stash is not pre-initialised)
-      store_pair<DT>(gs, 0 + 8 + ch0, 0.5f, 0.5f);
-      store_pair<DT>(gs, 16 + 8 + ch0, 0.5f, 0.5f);
-      store_pair<DT>(gs, 32 + 8 + ch0, 0.f, 0.f);
-      store_pair<DT>(gs, 48 + 8 + ch0, 0.5f, 0.5f);
+#pragma unroll
+      for (int gate = 0; gate < 4; ++gate) store_pair<DT>(gs, 16 * gate + 8 + ch0, lstm_stash_zero_w(gate), lstm_stash_zero_w(gate));
     }
   }
 }

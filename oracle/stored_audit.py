@@ -21,13 +21,13 @@ f32 operation of the kernel adds ``u * (|v| + e)`` (one rounding of a result who
 an operation with inputs ``E(a, ea)``, ``E(b, eb)`` propagates ``|a| eb + |b| ea + ea eb`` (product) or ``ea + eb``
 (sum).  Terms, with the source lines they model:
 
-* Convolution sums (gate kernels ``csrc/conv_igemm.hip:170-178`` bias-initialised accumulators, ``:427-450`` K-slice
-  partial sums; dgrad ``csrc/conv_igemm.hip:650-675``): every product of two stored values is exact in f32 (bf16 x bf16,
+* Convolution sums (``conv_igemm_body`` in ``csrc/conv_igemm.hip``: the gate kernels' bias-initialised accumulators, its
+  "K-slice reduction" of partial sums, and the dgrad epilogue): every product of two stored values is exact in f32 (bf16 x bf16,
   or f32 x f32 inside the MFMA), so the only error is the f32 summation, ``gamma_n * sum |w| |a|`` with
   ``gamma_n = n u / (1 - n u)`` and n the number of roundings on the longest accumulation chain: ``R_MFMA`` per MFMA
   instruction (one per bf16 K-step of 32 channels, ``mma_step<NINT_BF16>``; four per f32 K-step of 16 channels,
-  ``mma_step<NINT_F32>``, ``csrc/nint_common.h:92-101``) plus ``N_SLICE_ADDS`` for the bias and the K-slice partial adds.
-  Layers the vector-ALU stencil kernel can run (``csrc/stencil.hip:103``: one ``fmaf`` per product) use the product
+  ``mma_step<NINT_F32>``, both in ``csrc/nint_common.h``) plus ``N_SLICE_ADDS`` for the bias and the K-slice partial adds.
+  Layers the vector-ALU stencil kernel can run (``fma_quad`` in ``csrc/stencil.hip``: one ``fmaf`` per product) use the product
   count instead.  ``R_MFMA = 1``: n is the K-step count (bf16) or the instruction count (f32), not ``K * u``, which would
   hide a dropped K-chunk.  How ``v_mfma_f32_16x16x32_bf16`` rounds inside one instruction is not documented; what is
   measured is the whole sum: with f32 storage the stash holds the g gate's f32 register, so ``atanh`` of it recovers the
@@ -35,18 +35,19 @@ an operation with inputs ``E(a, ea)``, ``E(b, eb)`` propagates ``|a| eb + |b| ea
   ``_z_from_stash``).  That share is at most 0.30 on the MI355X over every f32 case of tests/test_gpu_stored_audit.py,
   so one rounding per instruction needs no extra allowance.  In bf16 the stored values' own rounding dominates every
   ratio; the accumulation term is the same model.
-* ``sigmoidf_`` (``csrc/nint_common.h:106``): ``rcp(1 + __expf(-z))``.  ``__expf`` scales by log2(e) (one rounding of
+* ``sigmoidf_`` (``csrc/nint_common.h``): ``rcp(1 + __expf(-z))``.  ``__expf`` scales by log2(e) (one rounding of
   the product, one of the constant: relative ``2|z| u`` of the result) and ``v_exp_f32`` is 1 ulp (``2u``, taken as
   ``4u``); the ``1 +`` rounds once and ``v_rcp_f32`` is 1 ulp (``2u``):
   ``eps_sig(z) = sigma * ((1 - sigma)(2|z| + 4) + 3) u``.
-* ``tanhf_`` (``csrc/nint_common.h:109``): ``fma(2, sigmoid(2x), -1)``: ``eps_tanh(x) = 2 eps_sig(2x) + u |tanh x|``
+* ``tanhf_`` (``csrc/nint_common.h``): ``fma(2, sigmoid(2x), -1)``: ``eps_tanh(x) = 2 eps_sig(2x) + u |tanh x|``
   (about ``2.4e-7`` absolute near 0: the cancellation is absolute, not relative).
 * A derivative taken through an activation uses its largest value on ``[|z| - e, |z| + e]`` (``sigma'`` and ``tanh'``
   fall with ``|z|``), so a bound never rests on a single point of a steep curve.
-* LSTM epilogue (``csrc/conv_igemm.hip:490-495``, the same association in ``stencil.hip:167-172`` and
-  ``tiny_gemm.hip:156-161``): ``c = fma(c_prev, f, i*g)``, ``h = o * tanh(c)``; ``c_prev`` is the STORED f32 value, so
-  it is exact.
-* Pointwise backward (``csrc/nint_common.h:160-172``; the fused step's copy ``csrc/conv_igemm.hip:624-636``): the
+* LSTM epilogue (``lstm_cell_elem`` in ``csrc/nint_common.h``, called by the MFMA epilogue of ``conv_igemm_body`` and by
+  ``stencil_lstm_kernel``; ``tiny_lstm_kernel`` holds its written-out twin): ``c = fma(c_prev, f, i*g)``,
+  ``h = o * tanh(c)``; ``c_prev`` is the STORED f32 value, so it is exact.
+* Pointwise backward (``lstm_bwd_elem`` in ``csrc/nint_common.h``, called by ``lstm_bwd_pointwise_body`` and by the
+  fused step's ``EPI_DGRAD_PW`` epilogue of ``conv_igemm_body``): the
   operations in the kernel's order, gates and ``c`` being stored (exact) inputs, ``dh`` and ``dc`` carrying bounds.
 * Transient ``dh`` (``include/nint.h``, ``nint_seq.wave`` and ``nint_cell_bwd_fused``): ``dh_t`` is the sum of two
   pieces, the h columns of the layer's own dgrad of time t+1 (or the injected ``dL/dh_{T-1}``) and the x columns of the
@@ -66,8 +67,8 @@ wgrad read the ring as the convolution's zero padding).  The padded gate columns
 wgrad sums them into weight-gradient rows that are discarded, and dgrad multiplies them by zero weights, so the only
 thing a consumer needs there is a finite value; zero is what the pointwise backward produces from a zero-weight channel
 (``dh = dc = 0``).  The padded stash columns hold the activations of a zero pre-activation, ``(i, f, g, o) =
-(0.5, 0.5, 0, 0.5)`` exactly (``csrc/stencil.hip:178-184`` writes them explicitly; the MFMA kernels compute them), which
-the pointwise backward needs finite for the zero dG above.  The channel padding of ``c``, ``dh`` and ``dc`` is zero.
+(0.5, 0.5, 0, 0.5)`` exactly (``lstm_stash_zero_w`` in ``csrc/nint_common.h``: ``stencil_lstm_kernel`` and
+``tiny_lstm_kernel`` write them explicitly; the MFMA kernels compute them), which the pointwise backward needs finite for the zero dG above.  The channel padding of ``c``, ``dh`` and ``dc`` is zero.
 """
 from __future__ import annotations
 
@@ -499,7 +500,7 @@ def _dx_unfolded(geo: Geo, dG0: torch.Tensor, Wt: torch.Tensor):
 
 
 def pointwise(geo: Geo, dh: E, dc: E, gates: torch.Tensor, c_prev: Optional[torch.Tensor], c_new: torch.Tensor):
-    """pointwise backward (csrc/nint_common.h:160-172) in the kernel's operation order; gates (B, 4Ch, H, W) and c are the
+    """pointwise backward (lstm_bwd_elem, csrc/nint_common.h) in the kernel's operation order; gates (B, 4Ch, H, W) and c are the
     stored (exact) inputs.  Returns (dG (B, 4Ch, H, W) as E before the ET store, dc_prev as E)."""
     Ch = gates.shape[1] // 4
     gi, gf, gg, go = (gates[:, j * Ch:(j + 1) * Ch] for j in range(4))
