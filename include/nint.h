@@ -130,6 +130,23 @@ typedef struct nint_seq {
                                         * intermediate dh, which the fused step skips) */
   int32_t probe_mask;                  /* in-step timing probes (diagnostic; 0 = none): bit k brackets every launch of kind k
                                         * (NINT_PROBE_*) of nint_seq_fwd / nint_seq_bwd with two one-thread stamp launches */
+  /* Boundary condition in x.
+   *   0  zero padding on every side (nn.Conv2d, model.py:207-211): the pass as it has always been -- same plan, same launches,
+   *      same bits.
+   *   1  CYCLIC LONGITUDE: column 0 and column W-1 are neighbours in every convolution of the stack; rows keep their zero
+   *      padding.  The conv, dgrad and weight-gradient kernels are the same ones: they read their taps from the physical halo,
+   *      and a small copy kernel (halo_wrap_kernel, its launches steps of the plan) fills the halo COLUMNS of the interior
+   *      rows with the wrapped interior columns -- of xs (unfolded) and of a given initial h at the head of the forward
+   *      pass, of every h block right behind the launch that wrote it, of every dG block right behind its writer -- and
+   *      writes them back to zero in a dG block right behind the dgrad that read it: the weight gradient walks the slack
+   *      columns and needs dG zero there.  After nint_seq_bwd every dG image has zero halos again; xs and h stay wrapped.
+   *      A horizontally folded xs (nint_layer.xfold) must have been packed with the _cyclic entries below: it has no
+   *      horizontal taps for a halo to serve.  Needs W >= P.
+   * Any other value, or W < P with 1: NINT_E_ARG before any launch.  nint_debug_seq_plan lists conv / pointwise problems only:
+   * with 1 their `index` counts the wrap launches in between.  (A caller that zero-fills the structure, as every caller must, gets 0.
+   * The field sits behind probe_mask, in front of the 8-byte aligned `probe`: the fields behind it move by 8 bytes together and
+   * dh_seq stays the last one.) */
+  int32_t lon_cyclic;
   unsigned long long* probe;           /* device buffer of probe_slots {tag, s_memrealtime (100 MHz)} pairs, or NULL.  nint_seq_fwd
                                         * fills slots from 0, nint_seq_bwd from probe_slots / 2; each starts with two back-to-back
                                         * calibration stamps (kind 0).  tag = kind | layer << 8 | t << 16 | end << 31 */
@@ -196,8 +213,9 @@ enum { NINT_PROBE_CAL = 0, NINT_PROBE_GATE = 1, NINT_PROBE_POINTWISE = 2, NINT_P
        NINT_PROBE_WAVE = 7, /* a merged forward grid (nint_seq.wave): tag layer = number of gate launches in it, t = wavefront step */
        NINT_PROBE_BWD_PAIR = 8, /* a merged BPTT grid of two conv launches (wave = 4 / 5: the dgrad launches of layers 0 and 1; wave = 1 / 3:
                                  * the bottom dgrad with the top layer's fused step): tag layer = the second launch's layer, t = its time step */
-       NINT_PROBE_BWD_PW = 9    /* wave = 4 / 5: the top layer's fused step with the bottom layer's pointwise backward: tag layer = the
-                                 * fused layer, t = its time step */ };
+       NINT_PROBE_BWD_PW = 9,   /* wave = 4 / 5: the top layer's fused step with the bottom layer's pointwise backward: tag layer = the
+                                 * fused layer, t = its time step */
+       NINT_PROBE_WRAP = 10     /* nint_seq.lon_cyclic: a halo wrap / clear launch: tag layer = its number of jobs, t = 0 */ };
 
 /* ---- library / device ---------------------------------------------------------------- */
 int nint_version(void);
@@ -224,6 +242,11 @@ int nint_pack_btchw_xfold(const float* src, void* dst, int B, int T, int C, int 
 /* backward of that fold: compact ET slab [N][H][W][Cp] of d/d(folded x) -> d/dx (N,C,H,W) f32,
  * dx[c][x] = sum_kx dfold[x - kx + k/2][kx*C + c] */
 int nint_unfold_dx(const void* src, float* dst, int N, int C, int k, int Cp, int H, int W, int dtype, void* stream);
+/* The two above for CYCLIC LONGITUDE (nint_seq.lon_cyclic): the fold reads pixel (x + kx - k/2) mod W instead of a zero outside
+ * the image, and its adjoint sums over the source pixels taken mod W.  Same arguments; in addition W < k/2: NINT_E_ARG. */
+int nint_pack_btchw_xfold_cyclic(const float* src, void* dst, int B, int T, int C, int k, int Cp, const nint_geom* g,
+                                 int dtype, void* stream);
+int nint_unfold_dx_cyclic(const void* src, float* dst, int N, int C, int k, int Cp, int H, int W, int dtype, void* stream);
 /* halo slab images [n0, n0+N) -> (N,C,H,W) f32 */
 int nint_unpack_halo(const void* src, float* dst, int n0, int N, int C, int Cp, const nint_geom* g,
                      int dtype, void* stream);
@@ -696,6 +719,19 @@ int nint_preproc_fuse_pad_static_slab(const float* const* srcs /*host*/, const i
                                       const float* mean, const float* std, const int* t0 /*host*/, int B, void* xs_slab,
                                       int Cxp, int xfold_k, int T, int H, int W, const nint_geom* g /*host*/, int mode,
                                       int dtype, void* stream);
+
+/* The two slab entries for CYCLIC LONGITUDE (nint_seq.lon_cyclic): a horizontally folded slab (xfold_k > 1) is folded over the
+ * padded grid taken mod g->W instead of with zeros outside it -- the model's own boundary condition, so the grid must carry
+ * no longitude halo (g->W == W; else NINT_E_ARG).  A plain slab (xfold_k = 0) is written as by the entries above: its halo
+ * columns are nint_seq_fwd's. */
+int nint_preproc_fuse_pad_slab_cyclic(const float* const* srcs /*host*/, const int* lev /*host*/, int nsrc,
+                                      const float* mean, const float* std, const int* t0 /*host*/, int B, void* xs_slab,
+                                      int Cxp, int xfold_k, int T, int H, int W, const nint_geom* g /*host*/, int mode, int dtype,
+                                      void* stream);
+int nint_preproc_fuse_pad_static_slab_cyclic(const float* const* srcs /*host*/, const int* lev /*host*/, int nsrc, int nstatic,
+                                             const float* mean, const float* std, const int* t0 /*host*/, int B, void* xs_slab,
+                                             int Cxp, int xfold_k, int T, int H, int W, const nint_geom* g /*host*/, int mode,
+                                             int dtype, void* stream);
 
 /* ---- recurrent state hand-off -------------------------------------------------------------- */
 /* (h, c) of every layer from one state block to another, in slab form, in ONE launch.  A state block of

@@ -46,7 +46,7 @@ class NintSeq(C.Structure):
                 ("gates", vp * NINT_MAX_LAYERS), ("dG", vp * NINT_MAX_LAYERS), ("dh", vp * NINT_MAX_LAYERS),
                 ("dc", vp * NINT_MAX_LAYERS), ("dx", vp), ("dW", vp * NINT_MAX_LAYERS), ("db", vp * NINT_MAX_LAYERS),
                 ("wg_partial", vp), ("wg_partial_bytes", C.c_size_t), ("fuse_bwd", C.c_int32),
-                ("probe_mask", C.c_int32), ("probe", vp), ("probe_slots", C.c_int32),
+                ("probe_mask", C.c_int32), ("lon_cyclic", C.c_int32), ("probe", vp), ("probe_slots", C.c_int32),
                 ("wave", C.c_int32), ("bwd_parts", C.c_int32), ("accumulate", C.c_int32), ("dh_seq", vp)]
 
 
@@ -111,6 +111,8 @@ SIGNATURES = {
     "nint_pack_weights_layers": (_I, [C.POINTER(vp), C.POINTER(vp), C.POINTER(NintLayer), _I, _I, vp]),
     "nint_pack_btchw_xfold": (_I, [vp, vp, _I, _I, _I, _I, _I, _PG, _I, vp]),
     "nint_unfold_dx": (_I, [vp, vp, _I, _I, _I, _I, _I, _I, _I, vp]),
+    "nint_pack_btchw_xfold_cyclic": (_I, [vp, vp, _I, _I, _I, _I, _I, _PG, _I, vp]),
+    "nint_unfold_dx_cyclic": (_I, [vp, vp, _I, _I, _I, _I, _I, _I, _I, vp]),
     "nint_stencil_holds": (_I, [_PL]),
     "nint_cell_fwd": (_I, [_PL, _PG, _I, _I, vp, vp, vp, vp, vp, vp, vp]),
     "nint_cell_bwd_pointwise": (_I, [_PL, _PG, _I, _I, vp, vp, vp, vp, vp, vp, vp]),
@@ -156,6 +158,10 @@ SIGNATURES = {
                                                 _I, vp]),
     "nint_preproc_fuse_pad_static_slab": (_I, [C.POINTER(vp), C.POINTER(_I), _I, _I, vp, vp, C.POINTER(_I), _I, vp, _I, _I, _I, _I, _I,
                                                _PG, _I, _I, vp]),
+    "nint_preproc_fuse_pad_slab_cyclic": (_I, [C.POINTER(vp), C.POINTER(_I), _I, vp, vp, C.POINTER(_I), _I, vp, _I, _I, _I, _I, _I, _PG,
+                                               _I, _I, vp]),
+    "nint_preproc_fuse_pad_static_slab_cyclic": (_I, [C.POINTER(vp), C.POINTER(_I), _I, _I, vp, vp, C.POINTER(_I), _I, vp, _I, _I, _I, _I,
+                                                      _I, _PG, _I, _I, vp]),
 }
 
 _lib = None

@@ -353,6 +353,15 @@ bool nint_internal_stencil_holds(const nint_layer* ly);
 int nint_internal_stencil_lstm(const nint_layer* ly, const nint_geom* g, int dtype, int N, const void* x_slab,
                                const void* h_prev, const float* c_prev, void* h_out, float* c_out, void* gates_out,
                                void* stream);
+// pack.hip: cyclic longitude (nint_seq.lon_cyclic).  One launch of halo_wrap_kernel serves a table of jobs; a job is a block of halo
+// slab images whose halo COLUMNS, on the interior rows, receive the wrapped interior columns (WRAP) or zeros (CLEAR).
+enum { NINT_WRAP_COPY = 0, NINT_WRAP_CLEAR = 1 };
+#define NINT_WRAP_MAX_JOBS 12
+struct WrapJob { char* base; int nimg; int px_bytes; int op; };       // first image, images, bytes per pixel (a multiple of 16)
+struct WrapTable { WrapJob job[NINT_WRAP_MAX_JOBS]; int n; int H, W, P, Hh, Wh; };
+// pure: the geometry and every job are checked (W >= P, 16-byte pixels and bases) -- NINT_E_ARG / NINT_E_ALIGN, nothing enqueued
+int nint_internal_wrap_check(const WrapTable* t);
+int nint_internal_wrap_enqueue(const WrapTable* t, void* stream);
 #define NINT_MULTI_MAX 4  // problems per merged grid (the kernels of NINT_MULTI_KERNELS, csrc/conv_igemm.hip)
 struct CellFwdJob {      // one gate launch (nint_cell_fwd's arguments)
   const nint_layer* ly; const void* x_slab; const void* h_prev; const float* c_prev; void* h_out; float* c_out; void* gates_out;

@@ -10,7 +10,7 @@
 // strided by H*W floats per channel, served from L2 after the first touch of each line.
 template <int DT>
 __global__ void pack_btchw_kernel(const float* __restrict__ src, void* __restrict__ dst, int B, int T, int C,
-                                  int Cp, int H, int W, int P, int Hh, int Wh, int kf) {
+                                  int Cp, int H, int W, int P, int Hh, int Wh, int kf, int cyc) {
   const size_t total = (size_t)B * T * H * W * Cp;
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
     const int co = i % Cp;
@@ -19,8 +19,11 @@ __global__ void pack_btchw_kernel(const float* __restrict__ src, void* __restric
     const int y = r % H; r /= H;
     const int b = r % B;
     const int t = r / B;
-    // kf > 1: horizontally folded layout, slab channel kx*C + c of pixel x = channel c of pixel x + kx - kf/2 (0 outside)
-    const int kx = co / C, c = co - kx * C, xi = x + kx - (kf >> 1);
+    // kf > 1: horizontally folded layout, slab channel kx*C + c of pixel x = channel c of pixel x + kx - kf/2 (0 outside;
+    // cyc: of that pixel mod W -- cyclic longitude, kf/2 <= W)
+    const int kx = co / C, c = co - kx * C;
+    int xi = x + kx - (kf >> 1);
+    if (cyc) xi = xi < 0 ? xi + W : (xi >= W ? xi - W : xi);
     const float v = (kx < kf && xi >= 0 && xi < W) ? src[((((size_t)b * T + t) * C + c) * H + y) * W + xi] : 0.f;
     const size_t o = ((((size_t)t * B + b) * Hh + (y + P)) * Wh + (x + P)) * Cp + co;
     store_elem<DT>(dst, o, v);
@@ -82,10 +85,11 @@ __device__ __forceinline__ void stage_rows(float* __restrict__ tile, int ld, int
 
 // write one row of Wo pixels from the tile as 16-byte vectors of 8 (bf16) / 4 (f32) consecutive channels;
 // xmap(xo) = tile column of output pixel xo.  kf > 1: HORIZONTALLY FOLDED output (nint_layer.xfold): output channel
-// kx*C + c of pixel xo is input channel c of pixel xo + kx - kf/2, zero outside [0, Wo) (the conv's zero padding).
+// kx*C + c of pixel xo is input channel c of pixel xo + kx - kf/2, zero outside [0, Wo) (the conv's zero padding); cyc: that
+// pixel mod Wo instead (cyclic longitude, nint_seq.lon_cyclic; kf/2 <= Wo).
 template <int DT, class XMap>
 __device__ __forceinline__ void write_row_channels_last(const float* __restrict__ tile, int ld, int C, int Cp, int Wo, char* __restrict__ d,
-                                                        XMap xmap, int kf = 1) {
+                                                        XMap xmap, int kf = 1, int cyc = 0) {
   constexpr int V = 16 / Elem<DT>::ES;         // channels per 16-byte vector
   const int nv = Cp / V;
   const unsigned magic_c = (unsigned)(((1ull << 32) + C - 1) / C);    // co / C by multiply-high (co < 65536)
@@ -104,7 +108,8 @@ __device__ __forceinline__ void write_row_channels_last(const float* __restrict_
       for (int j = 0; j < V; ++j) {
         const int co = v * V + j;
         const int kx = C == 1 ? co : (int)__umulhi((unsigned)co, magic_c), c = co - kx * C;   // (C = 1: the magic number would be 2^32)
-        const int xi = xo + kx - (kf >> 1);
+        int xi = xo + kx - (kf >> 1);
+        if (cyc) xi = xi < 0 ? xi + Wo : (xi >= Wo ? xi - Wo : xi);
         f[j] = (kx < kf && xi >= 0 && xi < Wo) ? tile[c * ld + xmap(xi)] : 0.f;
       }
     }
@@ -126,7 +131,7 @@ __device__ __forceinline__ void write_row_channels_last(const float* __restrict_
 template <int DT, int VW>
 __global__ __launch_bounds__(256) void pack_btchw_rows_kernel(const float* __restrict__ src, void* __restrict__ dst,
                                                              int B, int T, int C, int Cp, int H, int W, int P, int Hh,
-                                                             int Wh, int kf) {
+                                                             int Wh, int kf, int cyc) {
   extern __shared__ float tile[];              // [C][W + 1]
   const int ld = W + 1;
   int r = blockIdx.x;
@@ -138,7 +143,7 @@ __global__ __launch_bounds__(256) void pack_btchw_rows_kernel(const float* __res
   stage_rows<VW, false>(tile, ld, C, W, [&](int c) { return RowDesc{s + c * HW, 0.f, 1.f, c}; });
   __syncthreads();
   char* d = (char*)dst + ((((size_t)t * B + b) * Hh + (y + P)) * Wh + P) * (size_t)Cp * Elem<DT>::ES;
-  write_row_channels_last<DT>(tile, ld, C, Cp, W, d, [](int x) { return x; }, kf);
+  write_row_channels_last<DT>(tile, ld, C, Cp, W, d, [](int x) { return x; }, kf, cyc);
 }
 
 template <int DT>
@@ -185,8 +190,9 @@ __global__ void unpack_compact_kernel(const void* __restrict__ src, float* __res
 }
 
 static int pack_btchw_impl(const float* src, void* dst, int B, int T, int C, int kf, int Cp, const nint_geom* g, int dtype,
-                           void* stream) {
+                           void* stream, int cyc = 0) {
   if (!src || !dst || !g || B <= 0 || T <= 0 || C <= 0 || Cp < C * kf) return NINT_E_ARG;
+  if (cyc && g->W < kf / 2) return NINT_E_ARG;
   const size_t total = (size_t)B * T * g->H * g->W * Cp;
   hipStream_t st = (hipStream_t)stream;
   if (dtype != NINT_BF16 && dtype != NINT_F32) return NINT_E_ARG;
@@ -199,7 +205,7 @@ static int pack_btchw_impl(const float* src, void* dst, int B, int T, int C, int
     const int rc = nint_by_dtype(dtype, [&](auto dt) { return by_row_vec(vw, [&](auto v) -> int {
       auto kern = pack_btchw_rows_kernel<decltype(dt)::value, decltype(v)::value>;
       if (tile_bytes > 64 * 1024) NINT_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tile_bytes));
-      hipLaunchKernelGGL(kern, grid, dim3(256), tile_bytes, st, src, dst, B, T, C, Cp, g->H, g->W, g->P, g->Hh, g->Wh, kf);
+      hipLaunchKernelGGL(kern, grid, dim3(256), tile_bytes, st, src, dst, B, T, C, Cp, g->H, g->W, g->P, g->Hh, g->Wh, kf, cyc);
       return NINT_OK; }); });
     if (rc != NINT_OK) return rc;
     NINT_LAUNCH_CHECK();
@@ -207,7 +213,7 @@ static int pack_btchw_impl(const float* src, void* dst, int B, int T, int C, int
   }
   // rows that do not fit the LDS tile (or an odd channel padding): one thread per slab element, plain or folded
   nint_by_dtype(dtype, [&](auto dt) {
-    hipLaunchKernelGGL(pack_btchw_kernel<decltype(dt)::value>, grid1d(total), dim3(256), 0, st, src, dst, B, T, C, Cp, g->H, g->W, g->P, g->Hh, g->Wh, kf);
+    hipLaunchKernelGGL(pack_btchw_kernel<decltype(dt)::value>, grid1d(total), dim3(256), 0, st, src, dst, B, T, C, Cp, g->H, g->W, g->P, g->Hh, g->Wh, kf, cyc);
   });
   NINT_LAUNCH_CHECK();
   return NINT_OK;
@@ -224,9 +230,17 @@ extern "C" int nint_pack_btchw_xfold(const float* src, void* dst, int B, int T, 
   return pack_btchw_impl(src, dst, B, T, C, k, Cp, g, dtype, stream);
 }
 
+extern "C" int nint_pack_btchw_xfold_cyclic(const float* src, void* dst, int B, int T, int C, int k, int Cp, const nint_geom* g,
+                                            int dtype, void* stream) {
+  if (k < 1 || !(k & 1)) return NINT_E_ARG;
+  return pack_btchw_impl(src, dst, B, T, C, k, Cp, g, dtype, stream, 1);
+}
+
 // d/dx from the gradient of a horizontally folded input: dx[n][c][y][x] = sum_kx dfold[n][y][x - kx + k/2][kx*C + c]
+// (cyc: the source pixel taken mod W, the adjoint of the cyclic fold)
 template <int DT>
-__global__ void unfold_dx_kernel(const void* __restrict__ src, float* __restrict__ dst, int N, int C, int k, int Cp, int H, int W) {
+__global__ void unfold_dx_kernel(const void* __restrict__ src, float* __restrict__ dst, int N, int C, int k, int Cp, int H, int W,
+                                 int cyc) {
   const size_t total = (size_t)N * C * H * W;
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
     const int x = i % W;
@@ -236,20 +250,30 @@ __global__ void unfold_dx_kernel(const void* __restrict__ src, float* __restrict
     const int n = r / C;
     float acc = 0.f;
     for (int kx = 0; kx < k; ++kx) {
-      const int xs = x - kx + k / 2;
+      int xs = x - kx + k / 2;
+      if (cyc) xs = xs < 0 ? xs + W : (xs >= W ? xs - W : xs);
       if (xs >= 0 && xs < W) acc += load_elem<DT>(src, (((size_t)n * H + y) * W + xs) * Cp + kx * C + c);
     }
     dst[i] = acc;
   }
 }
 
-extern "C" int nint_unfold_dx(const void* src, float* dst, int N, int C, int k, int Cp, int H, int W, int dtype, void* stream) {
+static int unfold_dx_impl(const void* src, float* dst, int N, int C, int k, int Cp, int H, int W, int dtype, void* stream, int cyc) {
   if (!src || !dst || N <= 0 || C <= 0 || k < 1 || !(k & 1) || Cp < k * C || (dtype != NINT_F32 && dtype != NINT_BF16)) return NINT_E_ARG;
+  if (cyc && W < k / 2) return NINT_E_ARG;
   nint_by_dtype(dtype, [&](auto dt) {
-    hipLaunchKernelGGL(unfold_dx_kernel<decltype(dt)::value>, grid1d((size_t)N * C * H * W), dim3(256), 0, (hipStream_t)stream, src, dst, N, C, k, Cp, H, W);
+    hipLaunchKernelGGL(unfold_dx_kernel<decltype(dt)::value>, grid1d((size_t)N * C * H * W), dim3(256), 0, (hipStream_t)stream, src, dst, N, C, k, Cp, H, W, cyc);
   });
   NINT_LAUNCH_CHECK();
   return NINT_OK;
+}
+
+extern "C" int nint_unfold_dx(const void* src, float* dst, int N, int C, int k, int Cp, int H, int W, int dtype, void* stream) {
+  return unfold_dx_impl(src, dst, N, C, k, Cp, H, W, dtype, stream, 0);
+}
+
+extern "C" int nint_unfold_dx_cyclic(const void* src, float* dst, int N, int C, int k, int Cp, int H, int W, int dtype, void* stream) {
+  return unfold_dx_impl(src, dst, N, C, k, Cp, H, W, dtype, stream, 1);
 }
 
 extern "C" int nint_unpack_halo(const void* src, float* dst, int n0, int N, int C, int Cp, const nint_geom* g,
@@ -382,6 +406,55 @@ extern "C" int nint_state_copy(void* const* h_dst, float* const* c_dst, const vo
   return NINT_OK;
 }
 
+// ------------------------------------------------------------------------------ cyclic longitude: halo columns
+// nint_seq.lon_cyclic.  For every image of a job and every INTERIOR row y in [P, P + H): slab columns [0, P)
+// take slab columns [W, W + P) (the last P interior columns) and slab columns [P + W, P + W + P) take [P, 2P) (the first P) --
+// or all 2P of them take zeros (CLEAR).  Halo ROWS are not touched: latitude keeps its zero padding.  With W >= P the columns
+// read are interior columns and the columns written are halo columns: no lane reads what another writes.  16 bytes per lane;
+// blockIdx.y = job, x strides its (image, row, halo pixel, 16-byte vector) items.
+__global__ __launch_bounds__(256) void halo_wrap_kernel(WrapTable t) {
+  const WrapJob j = t.job[blockIdx.y];
+  const size_t nv = (size_t)j.px_bytes >> 4, per_row = 2 * (size_t)t.P * nv;
+  const size_t total = (size_t)j.nimg * t.H * per_row;
+  for (size_t i = blockIdx.x * (size_t)256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+    const size_t v = i % nv, r = i / per_row;
+    const int q = (int)((i % per_row) / nv);                     // halo pixel of the row: [0, P) left, [P, 2P) right
+    const int y = (int)(r % t.H);
+    const size_t img = r / t.H;
+    const int dcol = q < t.P ? q : t.W + q, scol = q < t.P ? t.W + q : q;
+    char* row = j.base + ((img * t.Hh + (size_t)(y + t.P)) * t.Wh) * j.px_bytes;
+    u32x4_t val = {0u, 0u, 0u, 0u};
+    if (j.op == NINT_WRAP_COPY) val = *(const u32x4_t*)(row + (size_t)scol * j.px_bytes + v * 16);
+    *(u32x4_t*)(row + (size_t)dcol * j.px_bytes + v * 16) = val;
+  }
+}
+
+int nint_internal_wrap_check(const WrapTable* t) {
+  if (!t || t->n < 1 || t->n > NINT_WRAP_MAX_JOBS) return NINT_E_ARG;
+  if (t->H < 1 || t->P < 1 || t->W < t->P || t->Hh < t->H + 2 * t->P || t->Wh < t->W + 2 * t->P) return NINT_E_ARG;
+  for (int q = 0; q < t->n; ++q) {
+    const WrapJob& j = t->job[q];
+    if (!j.base || j.nimg < 1 || j.px_bytes < 16 || j.px_bytes % 16 || (j.op != NINT_WRAP_COPY && j.op != NINT_WRAP_CLEAR)) return NINT_E_ARG;
+    if (((uintptr_t)j.base) & 15) return NINT_E_ALIGN;
+  }
+  return NINT_OK;
+}
+
+int nint_internal_wrap_enqueue(const WrapTable* t, void* stream) {
+  const int rc = nint_internal_wrap_check(t);
+  if (rc != NINT_OK) return rc;
+  size_t most = 0;
+  for (int q = 0; q < t->n; ++q) {
+    const size_t items = (size_t)t->job[q].nimg * t->H * 2 * t->P * (t->job[q].px_bytes >> 4);
+    if (items > most) most = items;
+  }
+  unsigned gx = (unsigned)((most + 255) / 256);
+  if (gx > 2048) gx = 2048;                    // (the rest by the stride)
+  hipLaunchKernelGGL(halo_wrap_kernel, dim3(gx, (unsigned)t->n), dim3(256), 0, (hipStream_t)stream, *t);
+  NINT_LAUNCH_CHECK();
+  return NINT_OK;
+}
+
 // ------------------------------------------------------------------------------ preproc
 // dataset.py:526-536 through :67-98.  Output element (t, c, yp, xp):
 //   lon: cyclic, xs = (xp - pl) mod W                            (dataset.py:67-80)
@@ -476,7 +549,8 @@ __global__ __launch_bounds__(256) void preproc_nchw_kernel(PreArgs a, const floa
 template <int DT, int VW>
 __global__ __launch_bounds__(256) void preproc_slab_kernel(PreArgs a, const float* __restrict__ mean, const float* __restrict__ stdv,
                                                            void* __restrict__ dst, int B, int b0, int nb, int T, int C, int Cp,
-                                                           int H, int W, int Hp, int Wp, int mode, int P, int Hh, int Wh, int kf) {
+                                                           int H, int W, int Hp, int Wp, int mode, int P, int Hh, int Wh, int kf,
+                                                           int cyc) {
   extern __shared__ __attribute__((aligned(16))) char smem_pre[];
   RowDesc* rows = (RowDesc*)smem_pre;                                        // [C] source row of every fused channel
   float* tile = (float*)(smem_pre + nint_round_up(C * (int)sizeof(RowDesc), 16));   // [C][W + 1]
@@ -501,7 +575,7 @@ __global__ __launch_bounds__(256) void preproc_slab_kernel(PreArgs a, const floa
   write_row_channels_last<DT>(tile, ld, C, Cp, Wp, d, [&](int xp) {
     const int xs = xp - pl;                    // cyclic longitude (dataset.py:67-80)
     return xs < 0 ? xs + W : (xs >= W ? xs - W : xs);
-  }, kf);
+  }, kf, cyc);
 }
 
 static int pre_args(PreArgs* a, const float* const* srcs, const int* lev, int nsrc, int nstatic, int H, int W, int Hp, int Wp,
@@ -567,11 +641,12 @@ extern "C" int nint_preproc_fuse_pad(const float* const* srcs, const int* lev, i
   return nint_preproc_fuse_pad_static(srcs, lev, nsrc, 0, mean, stdv, out, T, H, W, Hp, Wp, mode, stream);
 }
 
-extern "C" int nint_preproc_fuse_pad_static_slab(const float* const* srcs, const int* lev, int nsrc, int nstatic,
-                                                 const float* mean, const float* stdv, const int* t0, int B, void* xs_slab,
-                                                 int Cxp, int xfold_k, int T, int H, int W, const nint_geom* g, int mode,
-                                                 int dtype, void* stream) {
+static int preproc_slab_impl(const float* const* srcs, const int* lev, int nsrc, int nstatic,
+                             const float* mean, const float* stdv, const int* t0, int B, void* xs_slab,
+                             int Cxp, int xfold_k, int T, int H, int W, const nint_geom* g, int mode,
+                             int dtype, void* stream, int cyc) {
   if (!mean || !stdv || !xs_slab || !t0 || !g || T <= 0 || B <= 0) return NINT_E_ARG;
+  if (cyc && (g->W != W || W < xfold_k / 2)) return NINT_E_ARG;      // (the model wraps at its own edge: no longitude halo in between)
   if (xfold_k < 0 || (xfold_k > 1 && !(xfold_k & 1))) return NINT_E_ARG;
   const int kf = xfold_k > 1 ? xfold_k : 1;
   if (dtype != NINT_BF16 && dtype != NINT_F32) return NINT_E_ARG;
@@ -603,12 +678,32 @@ extern "C" int nint_preproc_fuse_pad_static_slab(const float* const* srcs, const
       if (tile_bytes > 64 * 1024)
         NINT_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tile_bytes));
       hipLaunchKernelGGL(kern, grid, dim3(256), tile_bytes, st, a, mean, stdv, xs_slab, B, b0, nb, T, C, Cxp, H, W, Hp, Wp,
-                         mode, g->P, g->Hh, g->Wh, kf);
+                         mode, g->P, g->Hh, g->Wh, kf, cyc);
       return NINT_OK; }); });
     if (rc != NINT_OK) return rc;
     NINT_LAUNCH_CHECK();
   }
   return NINT_OK;
+}
+
+extern "C" int nint_preproc_fuse_pad_static_slab(const float* const* srcs, const int* lev, int nsrc, int nstatic,
+                                                 const float* mean, const float* stdv, const int* t0, int B, void* xs_slab,
+                                                 int Cxp, int xfold_k, int T, int H, int W, const nint_geom* g, int mode,
+                                                 int dtype, void* stream) {
+  return preproc_slab_impl(srcs, lev, nsrc, nstatic, mean, stdv, t0, B, xs_slab, Cxp, xfold_k, T, H, W, g, mode, dtype, stream, 0);
+}
+
+extern "C" int nint_preproc_fuse_pad_static_slab_cyclic(const float* const* srcs, const int* lev, int nsrc, int nstatic,
+                                                        const float* mean, const float* stdv, const int* t0, int B, void* xs_slab,
+                                                        int Cxp, int xfold_k, int T, int H, int W, const nint_geom* g, int mode,
+                                                        int dtype, void* stream) {
+  return preproc_slab_impl(srcs, lev, nsrc, nstatic, mean, stdv, t0, B, xs_slab, Cxp, xfold_k, T, H, W, g, mode, dtype, stream, 1);
+}
+
+extern "C" int nint_preproc_fuse_pad_slab_cyclic(const float* const* srcs, const int* lev, int nsrc, const float* mean,
+                                                 const float* stdv, const int* t0, int B, void* xs_slab, int Cxp, int xfold_k,
+                                                 int T, int H, int W, const nint_geom* g, int mode, int dtype, void* stream) {
+  return preproc_slab_impl(srcs, lev, nsrc, 0, mean, stdv, t0, B, xs_slab, Cxp, xfold_k, T, H, W, g, mode, dtype, stream, 1);
 }
 
 extern "C" int nint_preproc_fuse_pad_slab(const float* const* srcs, const int* lev, int nsrc, const float* mean,

@@ -130,6 +130,8 @@ static int seq_check(const nint_seq* s) {
   if (s->dtype != NINT_F32 && s->dtype != NINT_BF16) return NINT_E_ARG;
   if (s->wave < 0 || s->wave > 5) return NINT_E_ARG;          // the modes of nint_seq.wave (nint.h); no other value is a mode
   if (!s->xs) return NINT_E_ARG;
+  if (s->lon_cyclic != 0 && s->lon_cyclic != 1) return NINT_E_ARG;    // zero padding or cyclic longitude (nint.h); no other value is a mode
+  if (s->lon_cyclic && s->g.W < s->g.P) return NINT_E_ARG;            // (a wrapped halo column must be an interior column)
   for (int l = 0; l < s->L; ++l) {
     if (!s->h[l] || !s->c[l]) return NINT_E_ARG;
     if (l > 0 && s->layer[l].Cxp != s->layer[l - 1].Chp) return NINT_E_ARG;
@@ -139,15 +141,15 @@ static int seq_check(const nint_seq* s) {
 
 // A pass is first PLANNED into an ordered list of steps -- host arithmetic only: nothing is enqueued, no stream is touched, no
 // buffer is read -- and then the list is enqueued (run_steps).  nint_debug_seq_plan shows the same list to tests and tools.
-enum { STEP_CONV, STEP_MULTI, STEP_PW, STEP_GATE, STEP_WGRAD, STEP_FOLD };
+enum { STEP_CONV, STEP_MULTI, STEP_PW, STEP_GATE, STEP_WGRAD, STEP_FOLD, STEP_WRAP };
 struct SeqProb { int op, layer, t; };              // one conv / pointwise problem (NINT_OP_*)
 struct GateCall { CellFwdJob job; nint_layer ly; int carrier; };
 struct SeqStep {
   int kind;        // a planned conv launch | a merged grid | a pointwise backward | a direct nint_cell_fwd call (stencil / dense-K: no planned form)
-                   // | one layer's weight-gradient reduction | the fold of a pass's reductions
+                   // | one layer's weight-gradient reduction | the fold of a pass's reductions | a halo wrap / clear (cyclic longitude)
   int probe, tag_layer, tag_t;       // the NINT_PROBE_* kind and tag it is bracketed with
   int n; SeqProb prob[NINT_MULTI_MAX + 1];         // its problems, in grid order (a reduction / the fold: none, n = 0)
-  union { ConvPlan conv; MultiPlan multi; PwArgs pw; GateCall gate; WgJobPlan wg; WgFoldPlan fold; };
+  union { ConvPlan conv; MultiPlan multi; PwArgs pw; GateCall gate; WgJobPlan wg; WgFoldPlan fold; WrapTable wrap; };
 };
 typedef std::vector<SeqStep> Steps;
 
@@ -186,6 +188,7 @@ static int run_steps(const nint_seq* s, const Steps& steps, Probe& probe, void* 
                                          st.gate.job.h_out, st.gate.job.c_out, st.gate.job.gates_out, stream); break;
       case STEP_WGRAD: rc = nint_internal_wgrad_enqueue(&st.wg, stream); break;
       case STEP_FOLD: rc = nint_internal_wgrad_fold_enqueue(&st.fold, stream); break;
+      case STEP_WRAP: rc = nint_internal_wrap_enqueue(&st.wrap, stream); break;
     }
     probe.stamp(st.probe, st.tag_layer, st.tag_t, 1);
     if (rc != NINT_OK) return rc;
@@ -494,8 +497,79 @@ static nint_seq sub_stack(const nint_seq* s, int f) {
   return v;
 }
 
+// CYCLIC LONGITUDE (nint_seq.lon_cyclic): a pass over the FINISHED plan -- the planners above know nothing of it --
+// that puts halo wrap launches between its steps.  Steps go out in list order on one stream, so "right behind its writer" holds
+// for every schedule: a halo slab image is wrapped behind the step that wrote its interior and before any later step reads it.
+//   forward  head: xs (all T*B images, unless folded: the fold wraps by itself) and slot 0 of every h of a given initial state;
+//            behind every step with a gate problem (l, t): block t+1 of h[l] -- one launch for all of a step's problems.
+//   BPTT     behind the writer of a dG block -- a pointwise backward (l, t): dG[l] block t; a fused step X[u] of layer l: dG[l]
+//            block u-1; a dgrad / fused step (l, u) with the lower layer's pointwise backward as its rider: dG[l-1] block u --
+//            WRAP, where a dgrad of the plan reads that block (time 0 of a bottom layer nobody wants d/dx of has none);
+//            behind the step with the dgrad / fused step (l, u), which read dG[l] block u: CLEAR, because the weight gradient
+//            walks roundup(W, 32) columns and the right-hand wrapped columns lie in that slack: left wrapped they would be
+//            summed into dW and db a second time.  After the chain every dG image has zero halos again.
+// h and xs stay wrapped: the weight gradient reads its taps from them, and their slack pixels meet dG = 0.
+struct WrapList {
+  Steps& out; const nint_geom& g; WrapTable t;
+  WrapList(Steps& out_, const nint_geom& g_) : out(out_), g(g_) { t = WrapTable{}; }
+  void add(void* base, size_t nimg, size_t px_bytes, int op) {
+    if (t.n == NINT_WRAP_MAX_JOBS) flush();
+    t.job[t.n++] = WrapJob{(char*)base, (int)nimg, (int)px_bytes, op};
+  }
+  void flush() {
+    if (t.n == 0) return;
+    t.H = g.H; t.W = g.W; t.P = g.P; t.Hh = g.Hh; t.Wh = g.Wh;
+    push(out, STEP_WRAP, NINT_PROBE_WRAP, t.n, 0).wrap = t;
+    t = WrapTable{};
+  }
+};
+
+static int add_wrap_steps(const nint_seq* s, bool bwd, Steps& steps) {
+  if (s->g.P < 1) return NINT_OK;                // 1 x 1 kernels only: no halo, nothing to wrap
+  const size_t es = esize(s->dtype), halo_px = (size_t)s->g.Hh * s->g.Wh, B = s->B;
+  const int L = s->L, T = s->T;
+  Steps out;
+  out.reserve(2 * steps.size() + 1);
+  WrapList w(out, s->g);
+  auto h_px = [&](int l) { return (size_t)s->layer[l].Chp * es; };
+  auto dG_px = [&](int l) { return 4 * (size_t)s->layer[l].Ch16 * es; };
+  auto dG_blk = [&](int l, int t) { return (char*)s->dG[l] + (size_t)t * B * halo_px * dG_px(l); };
+  std::vector<char> read(bwd ? (size_t)L * T : 0, 0);       // dG[l] block t has a dgrad in the plan
+  if (bwd) {
+    for (const SeqStep& st : steps)
+      for (int q = 0; q < st.n; ++q)
+        if (st.prob[q].op == NINT_OP_DGRAD || st.prob[q].op == NINT_OP_FUSED) read[(size_t)st.prob[q].layer * T + st.prob[q].t] = 1;
+  } else {
+    if (!s->layer[0].xfold) w.add((void*)s->xs, (size_t)T * B, (size_t)s->layer[0].Cxp * es, NINT_WRAP_COPY);
+    for (int l = 0; l < L && s->has_init_state; ++l) w.add(s->h[l], B, h_px(l), NINT_WRAP_COPY);
+    w.flush();
+  }
+  auto wrap_dG = [&](int l, int t) { if (read[(size_t)l * T + t]) w.add(dG_blk(l, t), B, dG_px(l), NINT_WRAP_COPY); };
+  for (const SeqStep& st : steps) {
+    out.push_back(st);
+    for (int q = 0; q < st.n; ++q) {
+      const int op = st.prob[q].op, l = st.prob[q].layer, t = st.prob[q].t;
+      if (!bwd) {
+        if (op == NINT_OP_GATE) w.add((char*)s->h[l] + (size_t)(t + 1) * B * halo_px * h_px(l), B, h_px(l), NINT_WRAP_COPY);
+        continue;
+      }
+      if (op == NINT_OP_POINTWISE) { wrap_dG(l, t); continue; }
+      // a dgrad, alone or with pointwise backward passes in its epilogue: it has read its own block ...
+      const ConvArgs& a = st.kind == STEP_MULTI ? st.multi.m.a[q] : st.conv.a;
+      w.add(dG_blk(l, t), B, dG_px(l), NINT_WRAP_CLEAR);
+      if (op == NINT_OP_FUSED) wrap_dG(l, t - 1);            // ... X[u] wrote block u-1 of its layer,
+      if (a.lo_dG) wrap_dG(l - 1, t);                         // ... and its rider block u of the layer below
+    }
+    w.flush();
+  }
+  for (const SeqStep& st : out)
+    if (st.kind == STEP_WRAP) { const int rc = nint_internal_wrap_check(&st.wrap); if (rc != NINT_OK) return rc; }
+  steps.swap(out);
+  return NINT_OK;
+}
+
 // check, plan (the CU count the launch-shape rules read is looked up once per pass), then the callers execute
-static int plan_pass(const nint_seq* s, bool bwd, Steps& steps) {
+static int plan_chain(const nint_seq* s, bool bwd, Steps& steps) {
   const int rc = bwd ? bwd_check(s) : seq_check(s);
   if (rc != NINT_OK) return rc;
   const int n_cu = nint_internal_n_cu();
@@ -510,6 +584,12 @@ static int plan_pass(const nint_seq* s, bool bwd, Steps& steps) {
     if (st.kind == STEP_CONV || st.kind == STEP_MULTI || st.kind == STEP_PW) st.tag_layer += f;
   }
   return rc2;
+}
+
+// ... and, for cyclic longitude only, the wrap launches in between
+static int plan_pass(const nint_seq* s, bool bwd, Steps& steps) {
+  const int rc = plan_chain(s, bwd, steps);
+  return rc == NINT_OK && s->lon_cyclic ? add_wrap_steps(s, bwd, steps) : rc;
 }
 
 extern "C" int nint_seq_fwd(const nint_seq* s, void* stream) {

@@ -70,9 +70,11 @@ class SlabBatch:
         H, W = ds.grid
         t0 = (C.c_int * B)(*[int(t) for t in self.t0])
         lib = _lib.load()
-        rc = lib.nint_preproc_fuse_pad_static_slab(ptrs, lev, len(lev), nstatic, ptr(dv["mean"]), ptr(dv["std"]), t0, B,
-                                                   ptr(ws.xs), ws.Cxp0, eng.cfgs[0].k if eng.cfgs[0].xfold else 0, T, H, W,
-                                                   C.byref(ws.g), ds.mode, eng.dt, stream_ptr())
+        # (a cyclic-longitude engine: the fold wraps at the model's own edge, which then must be the record's -- no longitude halo)
+        name = "nint_preproc_fuse_pad_static_slab" + ("_cyclic" if getattr(eng, "lon_cyclic", False) else "")
+        rc = getattr(lib, name)(ptrs, lev, len(lev), nstatic, ptr(dv["mean"]), ptr(dv["std"]), t0, B,
+                                ptr(ws.xs), ws.Cxp0, eng.cfgs[0].k if eng.cfgs[0].xfold else 0, T, H, W,
+                                C.byref(ws.g), ds.mode, eng.dt, stream_ptr())
         if rc == _lib.NINT_E_LDS:
             # a channel-row tile beyond the 160 KiB of LDS (hundreds of channels on a wide grid): the same values through
             # the f32 tensor and the pack kernel, whose generic path has no such limit (bit-identical by construction:
@@ -83,7 +85,7 @@ class SlabBatch:
                   "nint_preproc_fuse_pad_static_batch")
             eng.pack_input(ws, X)
             return
-        check(rc, "nint_preproc_fuse_pad_static_slab")
+        check(rc, name)
 
 
 def stateful_schedule(n_windows: int, T: int, B: int) -> Tuple[np.ndarray, int]:

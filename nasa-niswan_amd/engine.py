@@ -96,6 +96,7 @@ class Workspace:
         s.dtype, s.B, s.T, s.L = eng.dt, B, T, len(eng.cfgs)
         s.need_dx, s.has_init_state, s.n_cu = 0, int(has_init), eng.n_cu
         s.fuse_bwd = FUSE_BWD
+        s.lon_cyclic = int(eng.lon_cyclic)
         s.g = g
         s.xs = self.xs.data_ptr()
         for l in range(len(eng.cfgs)):
@@ -131,7 +132,9 @@ class ConvLSTMState:
     workspace, so carrying it into the next call costs ONE launch (nint_state_copy) and no f32 NCHW round trip.
     Detached by construction: it is not a tensor autograd knows, so a chain of calls through it is TRUNCATED BPTT --
     gradients stop at the chunk boundary.  (Pass the (h, c) tensor pairs instead for gradients across the boundary.)
-    A state belongs to the engine that made it (layer widths, storage dtype, halo P) and to one (B, H, W)."""
+    A state belongs to the engine that made it (layer widths, storage dtype, halo P, boundary condition) and to one
+    (B, H, W).  A cyclic-longitude engine's h images carry wrapped halo columns: they never reach a
+    zero-padding engine."""
 
     def __init__(self, eng: "SeqEngine", B: int, H: int, W: int, zero: bool = True):
         self.eng, self.B, self.H, self.W = eng, int(B), int(H), int(W)
@@ -192,9 +195,13 @@ class ConvLSTMState:
 
 
 class SeqEngine:
-    def __init__(self, cfgs: Sequence[LayerCfg], dtype="f32", device="cuda"):
+    def __init__(self, cfgs: Sequence[LayerCfg], dtype="f32", device="cuda", lon_cyclic: bool = False):
+        """``lon_cyclic`` (nint_seq.lon_cyclic): column 0 and column W-1 are neighbours in every convolution
+        of the stack -- every workspace's plan carries the halo wrap launches, and a folded input is packed, preprocessed
+        and unfolded by the _cyclic entries.  False: zero padding, the engine as it has always been."""
         if len(cfgs) < 1 or len(cfgs) > _lib.NINT_MAX_LAYERS:
             raise ValueError("1..8 layers supported")
+        self.lon_cyclic = bool(lon_cyclic)
         self.lib = _lib.load()
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -423,6 +430,10 @@ class SeqEngine:
                 raise ValueError(f"state: layers {[c.Ch for c in eng.cfgs]}, the model has {[c.Ch for c in self.cfgs]}")
             if eng.P != self.P:
                 raise ValueError(f"state: made by an engine with halo P = {eng.P}, this one has P = {self.P}")
+            if eng.lon_cyclic != self.lon_cyclic:
+                name = lambda cyc: "cyclic longitude" if cyc else "zero padding"
+                raise ValueError(f"state: made by an engine with {name(eng.lon_cyclic)}, this one has {name(self.lon_cyclic)} "
+                                 "(the h images of the two differ in their halo columns)")
         if state.B != B:
             raise ValueError(f"state: batch size B = {state.B}, the input has B = {B}")
         if (state.H, state.W) != (H, W):
@@ -514,9 +525,9 @@ class SeqEngine:
         if x.dtype != torch.float32 or not x.is_contiguous():
             x = x.float().contiguous()
         st, g = stream_ptr(), C.byref(ws.g)
-        if self.cfgs[0].xfold:
-            check(self.lib.nint_pack_btchw_xfold(ptr(x), ptr(ws.xs), B, T, Cc, self.cfgs[0].k, ws.Cxp0, g, self.dt, st),
-                  "nint_pack_btchw_xfold")
+        if self.cfgs[0].xfold:       # (cyclic longitude: the fold wraps by itself; a plain slab's halo is nint_seq_fwd's)
+            name = "nint_pack_btchw_xfold_cyclic" if self.lon_cyclic else "nint_pack_btchw_xfold"
+            check(getattr(self.lib, name)(ptr(x), ptr(ws.xs), B, T, Cc, self.cfgs[0].k, ws.Cxp0, g, self.dt, st), name)
         else:
             check(self.lib.nint_pack_btchw(ptr(x), ptr(ws.xs), B, T, Cc, ws.Cxp0, g, self.dt, st), "nint_pack_btchw")
 
@@ -757,8 +768,9 @@ class SeqEngine:
             C0 = self.cfgs[0].Cx
             tb = torch.empty(ws.T * ws.B, C0, ws.H, ws.W, dtype=torch.float32, device=self.device)
             if self.cfgs[0].xfold:     # gradient of the folded input -> gradient of the input
-                check(self.lib.nint_unfold_dx(ptr(dx), ptr(tb), ws.T * ws.B, C0, self.cfgs[0].k, ws.Cxp0, ws.H, ws.W, self.dt,
-                                              stream_ptr()), "nint_unfold_dx")
+                name = "nint_unfold_dx_cyclic" if self.lon_cyclic else "nint_unfold_dx"
+                check(getattr(self.lib, name)(ptr(dx), ptr(tb), ws.T * ws.B, C0, self.cfgs[0].k, ws.Cxp0, ws.H, ws.W, self.dt,
+                                              stream_ptr()), name)
             else:
                 check(self.lib.nint_unpack_compact(ptr(dx), ptr(tb), ws.T * ws.B, C0, ws.Cxp0, ws.H, ws.W, self.dt, stream_ptr()),
                       "unpack dx")

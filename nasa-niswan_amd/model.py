@@ -12,6 +12,9 @@ Extensions are keyword-only with reference-preserving defaults (SURVEY.md sectio
     return_sequence also return the per-step head outputs (the variant the analysis notebook
                     was run with: model.py:264,272,274 commented code, test.ipynb:273); differentiable:
                     gradients flow through ``seq`` as through ``pred``
+    lon_cyclic      ConvLSTM only: cyclic longitude -- column 0 and column W-1 of the grid are neighbours in every
+                    convolution of the stack (rows keep the zero padding); same parameters, same ``state_dict``
+                    
 
 Carried state (no reference code: model.py:259-262 always starts from zeros and drops the final state):
 ``ConvLSTM.forward(x, state=None, *, return_state=False)`` takes ``(h0, c0)`` of every layer and returns ``(h_T, c_T)``, as
@@ -257,7 +260,8 @@ class _EngineOwner:
 
 # ------------------------------------------------------------------------------ modules
 class ConvLSTMCell(_EngineOwner, nn.Module):
-    """reference model.py:196-231"""
+    """reference model.py:196-231.  A cell called by itself always zero-pads: cyclic longitude (``ConvLSTM(lon_cyclic=True)``)
+    is a property of the whole-sequence passes, and the cells of such a net are parameter containers like any other."""
 
     def __init__(self, input_channels, hidden_channels, kernel_size, bias=True, *, compute_dtype="f32"):
         super().__init__()
@@ -293,7 +297,7 @@ class ConvLSTM(_EngineOwner, nn.Module):
     """reference model.py:234-274"""
 
     def __init__(self, input_channels, hidden_channels, kernel_size, num_layers, *, out_channels=1,
-                 return_sequence=False, compute_dtype="f32"):
+                 return_sequence=False, compute_dtype="f32", lon_cyclic=False):
         super().__init__()
         assert len(hidden_channels) == num_layers, 'The length of hidden_channels must be equal to num_layers.'
         self.num_layers = num_layers
@@ -306,13 +310,15 @@ class ConvLSTM(_EngineOwner, nn.Module):
         self.conv = nn.Conv2d(hidden_channels[-1], out_channels, kernel_size=1)
         self.return_sequence = return_sequence
         self.compute_dtype = compute_dtype
+        # cyclic longitude: not a parameter and not in the state_dict -- a trained checkpoint loads into either mode
+        self.lon_cyclic = bool(lon_cyclic)
         self._engines = {}
 
     def _engine(self, device) -> SeqEngine:
-        key = (str(device), dtype_code(self.compute_dtype))
+        key = (str(device), dtype_code(self.compute_dtype), self.lon_cyclic)
         if key not in self._engines:
             cfgs = [LayerCfg(c.input_channels, c.hidden_channels, c.kernel_size) for c in self.layers]
-            self._engines[key] = SeqEngine(cfgs, self.compute_dtype, device)
+            self._engines[key] = SeqEngine(cfgs, self.compute_dtype, device, lon_cyclic=self.lon_cyclic)
         return self._engines[key]
 
     def _pack_weights(self, eng: SeqEngine):

@@ -125,6 +125,10 @@ def get_arguments(argv=None, MODEL='LSTM-00', SPECIES='bcb', LEARNING_RATE=1.0E-
     parser.add_argument("--layer-lr-scale", nargs='+', type=float, default=None, metavar="S",
                         help="one factor on --learning-rate per ConvLSTM layer, bottom first (smaller lower down); the head "
                              "takes the last one, or one more of its own")
+    parser.add_argument("--cyclic-longitude", action="store_true",
+                        help="the model treats longitude as periodic: column 0 and column W-1 of its grid are neighbours in every "
+                             "convolution (ConvLSTM(lon_cyclic=True)), so the input needs no longitude halo and the loss no "
+                             "longitude crop.  The width of --input-size must equal the width of --grid")
     parser.add_argument("--reset-optimizer", action="store_true",
                         help="with --use-checkpoint: load the weights of --restore-from only and start the optimizer afresh "
                              "(the fine-tuning entry point; without it an optimizer state of other param groups is an error)")
@@ -133,6 +137,9 @@ def get_arguments(argv=None, MODEL='LSTM-00', SPECIES='bcb', LEARNING_RATE=1.0E-
         parser.error(f"--freeze-layers must be in [0, --num-layers = {args.num_layers}]")
     if args.layer_lr_scale is not None and len(args.layer_lr_scale) not in (args.num_layers, args.num_layers + 1):
         parser.error(f"--layer-lr-scale takes {args.num_layers} factors (one per layer) or {args.num_layers + 1} (the head's last)")
+    if args.cyclic_longitude and int(args.input_size[1]) != int(args.grid[1]):
+        parser.error(f"--cyclic-longitude: the model wraps at the edge of its own grid, so --input-size's width "
+                     f"({args.input_size[1]}) must be --grid's ({args.grid[1]}): no longitude halo")
     if args.spinup_steps < 0:
         parser.error("--spinup-steps must be >= 0")
     if args.spinup_steps > 0 and not args.sequence_loss:
@@ -197,7 +204,8 @@ def main(args):
         raise SystemExit("only the LSTM family (ConvLSTM) is in scope of this build")
     out_ch = args.levels
     generator = pkg.ConvLSTM(args.in_channels, list(args.hidden_channels), list(args.kernel_size), args.num_layers,
-                             out_channels=out_ch, compute_dtype=args.dtype).to(dev)         # train.py:48
+                             out_channels=out_ch, compute_dtype=args.dtype,
+                             lon_cyclic=args.cyclic_longitude).to(dev)                      # train.py:48
     H, W = (int(v) for v in args.grid)
     if args.input_size[0] < H or args.input_size[1] < W:
         raise SystemExit(f"--input-size {tuple(args.input_size)} is smaller than --grid {(H, W)}: the model runs on the "
