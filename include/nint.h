@@ -207,6 +207,26 @@ typedef struct nint_seq {
                          * plan is the one without it, merged grids included.  16-byte aligned, else NINT_E_ALIGN. */
 } nint_seq;
 
+/* CLOSED-LOOP FORWARD: what nint_seq_fwd_closed takes beside the nint_seq.  (A structure of its own: the
+ * layout and the size of nint_seq are pinned -- dh_seq is and stays its last field.)
+ * The last O input channels, [c0, c0 + O) with c0 = layer[0].Cx - O, are FEEDBACK channels.  With F = min(max(from, 0), T),
+ * before the gates of every step t >= F the pass stores, for every pixel of the grid,
+ *     xs[t*B + b][y][x][c0 + o] = round_ET( b[o] + sum_c w[o][c] * h[L-1] slab t [b][y][x][c] )
+ * -- the staged head's f32 value (nint_head_fwd, bit for bit) rounded once to ET (nint_head_feedback below; a folded xs
+ * receives every value in its k places).  Slab t of h[L-1] is the top layer's hidden state after step t-1, slab 0 the
+ * initial state.  SO WITH O > 0 THE PASS WRITES nint_seq.xs, which is declared const for the open-loop pass.
+ * Steps t < F read what the caller packed (spin-up) and are planned as an open-loop pass of F steps; steps t >= F go out
+ * time-major -- feedback(t), gate(0, t) ... gate(L-1, t), each its own launch, on the tile_rows the same `wave` gives the
+ * open-loop pass -- so the pass equals, bit for bit, the open-loop pass over an input that already holds those values.
+ * With lon_cyclic and an unfolded xs a halo wrap launch for xs block t follows feedback(t).
+ * O = 0 (a zero-filled structure, or a NULL pointer to one): open loop -- the plan, the launches and the bits of nint_seq_fwd. */
+typedef struct nint_feedback {
+  const float* w;       /* f32 (O, Ch of layer L-1): the head's weight */
+  const float* b;       /* f32 (O), or NULL: no bias */
+  int32_t O;            /* head outputs fed back; 0 = off */
+  int32_t from;         /* first fed step */
+} nint_feedback;
+
 /* launch kinds for nint_seq.probe_mask / the probe tags */
 enum { NINT_PROBE_CAL = 0, NINT_PROBE_GATE = 1, NINT_PROBE_POINTWISE = 2, NINT_PROBE_DGRAD = 3, NINT_PROBE_FUSED = 4,
        NINT_PROBE_WGRAD = 5, NINT_PROBE_FOLD = 6,
@@ -215,7 +235,8 @@ enum { NINT_PROBE_CAL = 0, NINT_PROBE_GATE = 1, NINT_PROBE_POINTWISE = 2, NINT_P
                                  * the bottom dgrad with the top layer's fused step): tag layer = the second launch's layer, t = its time step */
        NINT_PROBE_BWD_PW = 9,   /* wave = 4 / 5: the top layer's fused step with the bottom layer's pointwise backward: tag layer = the
                                  * fused layer, t = its time step */
-       NINT_PROBE_WRAP = 10     /* nint_seq.lon_cyclic: a halo wrap / clear launch: tag layer = its number of jobs, t = 0 */ };
+       NINT_PROBE_WRAP = 10,    /* nint_seq.lon_cyclic: a halo wrap / clear launch: tag layer = its number of jobs, t = 0 */
+       NINT_PROBE_FEEDBACK = 11 /* nint_seq_fwd_closed: the feedback launch of step t: tag layer = 0, t = the step */ };
 
 /* ---- library / device ---------------------------------------------------------------- */
 int nint_version(void);
@@ -329,6 +350,16 @@ int nint_conv_wgrad(const nint_layer* ly, const nint_geom* g, int dtype, int N,
 /* ---- whole-sequence drivers (model.py:253-274 and its BPTT), all launches from C++ ---------- */
 int nint_seq_fwd(const nint_seq* s /*host*/, void* stream);
 int nint_seq_bwd(const nint_seq* s /*host*/, void* stream);
+/* The same two passes for a CLOSED-LOOP window (struct nint_feedback above; fb == NULL or fb->O == 0: exactly the entries above).
+ * nint_seq_fwd_closed runs the forward pass with the feedback steps in its plan.  nint_seq_bwd_closed exists to refuse, in the
+ * library, what is not defined: the backward pass of a window in which something was fed back (fb->O > 0 with fb->from < T) is
+ * NINT_E_ARG before any launch -- d/dx of a fed step would have to re-enter the top layer's d/dh of the step before, which
+ * re-plans BPTT; a window in which nothing was fed back (fb->from >= T) trains as ever.
+ * NINT_E_ARG before any launch (both, and nint_debug_seq_plan_closed): fb->O < 0, fb->O > layer[0].Cx, fb->O > 0 with
+ * fb->w == NULL, fb->from < 0, fb->from == 0 without has_init_state (step 0 can only be fed from a state that was handed in).
+ * NINT_E_SHAPE before anything is enqueued: a head the feedback kernel does not hold (nint_head_feedback). */
+int nint_seq_fwd_closed(const nint_seq* s /*host*/, const nint_feedback* fb /*host*/, void* stream);
+int nint_seq_bwd_closed(const nint_seq* s /*host*/, const nint_feedback* fb /*host*/, void* stream);
 
 /* The launch plan of a pass, for tests and tools (host only: nothing is enqueued, no pointer is dereferenced).  Both drivers
  * first PLAN a pass into an ordered list of launches and then enqueue that list; this entry runs the same argument checks and
@@ -353,6 +384,10 @@ typedef struct nint_launch_rec {
   int32_t nt_begin;         /* first n-tile it computes */
 } nint_launch_rec;
 int nint_debug_seq_plan(const nint_seq* s /*host*/, int bwd, nint_launch_rec* out /*host*/, int cap);
+/* ... of a closed-loop window (nint_seq_fwd_closed / nint_seq_bwd_closed).  Conv / pointwise problems only, as above: their
+ * `index` counts the feedback launches in between, as it counts the halo wraps of cyclic longitude. */
+int nint_debug_seq_plan_closed(const nint_seq* s /*host*/, const nint_feedback* fb /*host*/, int bwd, nint_launch_rec* out /*host*/,
+                               int cap);
 /* The merged-grid rule alone, for tests (host arithmetic only): the NINT_K_* kernel that would carry n independent launches of
  * the conv_igemm bodies shapes[5 * i .. 5 * i + 5) = (epi, wn, wk, ntw, mt) as ONE grid, with_pw != 0: together with one
  * pointwise backward pass -- or NINT_E_SHAPE where no merged kernel holds them all (also n outside [1, 4], or a tuple that is
@@ -422,6 +457,28 @@ int nint_head_bwd_acc(const void* h_slab, int n0, int N, int Ch, int Chp, int O,
  * nint_head_fwd_seq: one launch; per element the arithmetic of nint_head_fwd in the same order (= T calls of it, bit for bit). */
 int nint_head_fwd_seq(const void* h_slab, int B, int T, int Ch, int Chp, int O, const float* w, const float* b,
                       float* seq, const nint_geom* g, int dtype, void* stream);
+/* The FEEDBACK step of the closed-loop forward (nint_seq_fwd_closed), by itself: the head of images [n0, n0 + N)
+ * of the top layer's halo slab, rounded once to ET (round to nearest even, as the pack entries round) and stored into channels
+ * [c0, c0 + O) of images [x_n0, x_n0 + N) of the input halo slab xs (Cx channels padded to Cxp per pixel).  The f32 value is
+ * nint_head_fwd's bit for bit: the same staged body pieces in the same order.
+ *   xfold_k = 0   plain slab: channels [c0, c0 + O) of the INTERIOR pixels are stored and nothing else -- no halo pixel, no
+ *                 slack column, no pad channel, no other channel.  (Cyclic longitude: the halo columns of these images are
+ *                 the caller's to refresh; nint_seq_fwd plans a wrap launch right behind.)  lon_cyclic is only checked.
+ *   xfold_k = k   horizontally folded slab (nint_layer.xfold): slab channel kx*Cx + c0 + o of pixel x receives the value of
+ *                 pixel x + kx - k/2 -- 0 outside the image, or that pixel mod W with lon_cyclic -- exactly what
+ *                 nint_pack_btchw_xfold[_cyclic] stores for the same f32 value.  Every other channel stays.
+ * One workgroup per image row: the row's predictions are formed once, staged in LDS, and every destination pixel gathers
+ * its own; stores go out in whole dwords wherever both halves are fed.
+ * Shapes: the staged head only.  Where the rule above (Chp <= 128, ...) does not hold, or the row's predictions (W * O f32)
+ * do not fit beside the weights in 160 KiB of LDS: NINT_E_SHAPE before any launch (nint_seq_fwd: before anything is enqueued).
+ * NINT_E_ARG before any launch: a NULL h_slab / w / xs_slab / g; N, O, Ch < 1; Chp < Ch or not a multiple of KC; c0 < 0 or
+ * c0 + O > Cx; xfold_k negative or even (1 is a plain slab); Cxp < Cx (plain) or < xfold_k * Cx (folded), or a pixel of Cxp
+ * elements that is no multiple of 16 bytes;
+ * lon_cyclic not 0 / 1, or 1 with g->W < g->P or g->W < xfold_k / 2; a bad dtype or geometry.  NINT_E_ALIGN: a slab that is
+ * not 16-byte aligned. */
+int nint_head_feedback(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w, const float* b,
+                       void* xs_slab, int x_n0, int Cx, int Cxp, int c0, int xfold_k, int lon_cyclic, const nint_geom* g,
+                       int dtype, void* stream);
 /* dseq (B, T*O, H, W) and dpred_last (B, O, H, W: the cotangent of pred = head(h_{T-1}), added to step T-1 inside the
  * kernels); either may be NULL, not both.  dh_seq: compact ET [T*B][H][W][Chp], image t*B+b, padding channels zero
  * (nint_seq.dh_seq; may be NULL: not written); dw (O,Ch), db (O): summed over all T*B images in a fixed order (overwritten;

@@ -527,6 +527,116 @@ extern "C" int nint_head_fwd_seq(const void* h_slab, int B, int T, int Ch, int C
   return head_fwd_impl<true>(h_slab, B, T * B, Ch, Chp, O, w, b, seq, g, dtype, B, stream);     // h_t = slot t + 1: images from B
 }
 
+// ------------------------------------------------------------------------------ feedback (closed-loop forward)
+// nint_seq.fb_O / nint_head_feedback (nint.h): the head of N images of the top layer's slab, rounded once to ET,
+// into the feedback channels [c0, c0 + O) of N images of the input slab.  One workgroup per image row.
+//   (1) one thread per pixel of the row forms the O dot products with the pieces head_fwd_body is made of -- head_stage_weights,
+//       the same channel loads, head_dot from the bias -- so the f32 value is nint_head_fwd's bit for bit; it is rounded to ET
+//       and kept in LDS, p_s[x][o].
+//   (2) every destination pixel gathers its own: thread items are (pixel, dword of the pixel's fed span), consecutive lanes on
+//       consecutive dwords.  Plain slab (kf = 1): the span is the O channels from c0.  Folded slab (kf = k): slab channel
+//       kx*Cx + c of pixel x is channel c of pixel x + kx - k/2 (0 outside the row; cyc: mod W), so the span runs over all k
+//       copies and a dword's elements are stored only where their channel is a fed one -- a whole dword where both are
+//       (bf16), else the one element.  Nothing else of xs is written: no halo pixel, no slack column, no other channel.
+template <int DT, int CHV>
+__global__ __launch_bounds__(256) void head_feedback_kernel(const void* __restrict__ h, const float* __restrict__ w,
+                                                            const float* __restrict__ b, void* __restrict__ xs, FbPlan a) {
+  // (the pointers as __restrict__ arguments of their own, as head_fwd_kernel has them; a is the rest of the plan)
+  extern __shared__ __attribute__((aligned(16))) char smem_fb[];
+  constexpr int ES = Elem<DT>::ES, EPD = 4 / ES;               // elements per dword
+  float* __restrict__ w_s = (float*)smem_fb;                   // [O][CHV]
+  float* __restrict__ p_s = w_s + a.O * CHV;                   // [W][O]
+  head_stage_weights<CHV>(w_s, w, a.O, a.Ch);
+  const int y = blockIdx.x % a.H, n = blockIdx.x / a.H;
+  const size_t row = ((size_t)n * a.Hh + (y + a.P)) * a.Wh + a.P;          // first interior pixel of the row, in both slabs
+  for (int x = threadIdx.x; x < a.W; x += 256) {
+    const size_t hb = (row + x) * a.Chp;
+    float hv[CHV];
+#pragma unroll
+    for (int c = 0; c < CHV; c += 4) {
+      const f32x4_t v = (c < a.Chp) ? load_vec4<DT>(h, hb + c) : (f32x4_t){0.f, 0.f, 0.f, 0.f};
+      hv[c] = v[0]; hv[c + 1] = v[1]; hv[c + 2] = v[2]; hv[c + 3] = v[3];
+    }
+    for (int o = 0; o < a.O; ++o) {
+      const float p = head_dot<CHV>(b ? b[o] : 0.f, w_s + o * CHV, hv);
+      p_s[x * a.O + o] = DT == NINT_BF16 ? bf2f(f2bf(p)) : p;
+    }
+  }
+  __syncthreads();
+  const int first = a.c0, last = (a.kf - 1) * a.Cx + a.c0 + a.O;          // the fed span of a pixel's channels
+  const int d0 = first / EPD, nd = (last + EPD - 1) / EPD - d0;
+  for (int i = threadIdx.x; i < a.W * nd; i += 256) {
+    const int x = i / nd, d = d0 + (i - x * nd);
+    float v[EPD]; bool on[EPD];
+#pragma unroll
+    for (int e = 0; e < EPD; ++e) {
+      const int ch = d * EPD + e, kx = ch / a.Cx, c = ch - kx * a.Cx;
+      on[e] = kx < a.kf && c >= a.c0 && c < a.c0 + a.O;
+      int xi = x + kx - (a.kf >> 1);
+      if (a.cyc) xi = xi < 0 ? xi + a.W : (xi >= a.W ? xi - a.W : xi);
+      v[e] = (on[e] && xi >= 0 && xi < a.W) ? p_s[xi * a.O + (c - a.c0)] : 0.f;
+    }
+    char* px = (char*)xs + (row + x) * (size_t)a.Cxp * ES;
+    if constexpr (DT == NINT_BF16) {
+      if (on[0] && on[1]) *(uint32_t*)(px + 4 * (size_t)d) = pack_bf16x2(v[0], v[1]);
+      else if (on[0]) *(uint16_t*)(px + 4 * (size_t)d) = f2bf(v[0]);
+      else if (on[1]) *(uint16_t*)(px + 4 * (size_t)d + 2) = f2bf(v[1]);
+    } else {
+      if (on[0]) *(float*)(px + 4 * (size_t)d) = v[0];
+    }
+  }
+}
+
+int nint_internal_feedback_plan(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w, const float* b,
+                                void* xs_slab, int x_n0, int Cx, int Cxp, int c0, int xfold_k, int lon_cyclic, const nint_geom* g,
+                                int dtype, FbPlan* plan) {
+  if (!h_slab || !w || !xs_slab || !g || !plan || N <= 0 || O <= 0 || Ch <= 0 || Cx <= 0 || n0 < 0 || x_n0 < 0) return NINT_E_ARG;
+  if (dtype != NINT_BF16 && dtype != NINT_F32) return NINT_E_ARG;
+  const int es = dtype == NINT_BF16 ? 2 : 4;
+  if (g->H <= 0 || g->W <= 0 || g->P < 0 || g->Hh < g->H + 2 * g->P || g->Wh < g->W + 2 * g->P) return NINT_E_ARG;
+  if (Chp < Ch || Chp % (dtype == NINT_BF16 ? 32 : 16) != 0) return NINT_E_ARG;
+  if (c0 < 0 || c0 + O > Cx) return NINT_E_ARG;
+  if (xfold_k < 0 || (xfold_k > 0 && !(xfold_k & 1))) return NINT_E_ARG;
+  const int kf = xfold_k > 1 ? xfold_k : 1;
+  if (Cxp < kf * Cx || (Cxp * es) % 16 != 0) return NINT_E_ARG;
+  if (lon_cyclic != 0 && lon_cyclic != 1) return NINT_E_ARG;
+  if (lon_cyclic && (g->W < g->P || g->W < kf / 2)) return NINT_E_ARG;
+  if (((((uintptr_t)h_slab) | ((uintptr_t)xs_slab)) & 15) != 0) return NINT_E_ALIGN;
+  if (!head_staged_holds(Chp, O)) return NINT_E_SHAPE;
+  const size_t lds = ((size_t)O * head_chv(Chp) + (size_t)g->W * O) * sizeof(float);
+  if (lds > 160 * 1024) return NINT_E_SHAPE;
+  const size_t halo_px = (size_t)g->Hh * g->Wh;
+  FbPlan p = {};
+  p.h = (const char*)h_slab + (size_t)n0 * halo_px * Chp * es; p.w = w; p.b = b;
+  p.xs = (char*)xs_slab + (size_t)x_n0 * halo_px * Cxp * es;
+  p.N = N; p.Ch = Ch; p.Chp = Chp; p.O = O; p.Cx = Cx; p.Cxp = Cxp; p.c0 = c0; p.kf = kf; p.cyc = lon_cyclic; p.dtype = dtype;
+  p.H = g->H; p.W = g->W; p.P = g->P; p.Hh = g->Hh; p.Wh = g->Wh; p.lds = lds;
+  *plan = p;
+  return NINT_OK;
+}
+
+int nint_internal_feedback_enqueue(const FbPlan* p, void* stream) {
+  const int rc = nint_by_dtype(p->dtype, [&](auto dt) -> int {
+    return head_by_chv(p->Chp, [&](auto chv) -> int {
+      auto kern = head_feedback_kernel<decltype(dt)::value, decltype(chv)::value>;
+      if (p->lds > 64 * 1024) NINT_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->lds));
+      hipLaunchKernelGGL(kern, dim3((unsigned)((size_t)p->N * p->H)), dim3(256), p->lds, (hipStream_t)stream, p->h, p->w, p->b, p->xs, *p);
+      return NINT_OK;
+    });
+  });
+  if (rc != NINT_OK) return rc;
+  NINT_LAUNCH_CHECK();
+  return NINT_OK;
+}
+
+extern "C" int nint_head_feedback(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w, const float* b,
+                                  void* xs_slab, int x_n0, int Cx, int Cxp, int c0, int xfold_k, int lon_cyclic,
+                                  const nint_geom* g, int dtype, void* stream) {
+  FbPlan p;
+  const int rc = nint_internal_feedback_plan(h_slab, n0, N, Ch, Chp, O, w, b, xs_slab, x_n0, Cx, Cxp, c0, xfold_k, lon_cyclic, g, dtype, &p);
+  return rc != NINT_OK ? rc : nint_internal_feedback_enqueue(&p, stream);
+}
+
 // SEQ: d loss / d (head output) comes from the sequence tensors (DpSeq: dpred = dseq, dlast, Bs = B, T) instead of dpred alone
 template <bool SEQ>
 static int head_bwd_impl(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w, const float* dpred,

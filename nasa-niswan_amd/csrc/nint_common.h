@@ -362,6 +362,18 @@ struct WrapTable { WrapJob job[NINT_WRAP_MAX_JOBS]; int n; int H, W, P, Hh, Wh; 
 // pure: the geometry and every job are checked (W >= P, 16-byte pixels and bases) -- NINT_E_ARG / NINT_E_ALIGN, nothing enqueued
 int nint_internal_wrap_check(const WrapTable* t);
 int nint_internal_wrap_enqueue(const WrapTable* t, void* stream);
+// head.hip: the feedback step of the closed-loop forward (nint_seq.fb_O; nint_head_feedback's arguments)
+struct FbPlan {
+  const void* h; const float* w; const float* b; void* xs;       // h, xs: the FIRST image read / written
+  int N, Ch, Chp, O, Cx, Cxp, c0, kf, cyc, dtype;                // kf: 1 = plain slab, k = folded
+  int H, W, P, Hh, Wh;
+  size_t lds;
+};
+// pure: every check of nint_head_feedback (NINT_E_ARG / NINT_E_ALIGN / NINT_E_SHAPE) is made here and *plan filled; nothing is enqueued
+int nint_internal_feedback_plan(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w, const float* b,
+                                void* xs_slab, int x_n0, int Cx, int Cxp, int c0, int xfold_k, int lon_cyclic, const nint_geom* g,
+                                int dtype, FbPlan* plan);
+int nint_internal_feedback_enqueue(const FbPlan* plan, void* stream);
 #define NINT_MULTI_MAX 4  // problems per merged grid (the kernels of NINT_MULTI_KERNELS, csrc/conv_igemm.hip)
 struct CellFwdJob {      // one gate launch (nint_cell_fwd's arguments)
   const nint_layer* ly; const void* x_slab; const void* h_prev; const float* c_prev; void* h_out; float* c_out; void* gates_out;

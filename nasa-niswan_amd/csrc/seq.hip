@@ -138,18 +138,29 @@ static int seq_check(const nint_seq* s) {
   }
   return NINT_OK;
 }
+// ... and of a closed-loop window (struct nint_feedback; fb is never NULL here: NO_FB stands for the open loop)
+static const nint_feedback NO_FB = {};
+static int seq_check(const nint_seq* s, const nint_feedback* fb) {
+  const int rc = seq_check(s);
+  if (rc != NINT_OK) return rc;
+  if (fb->O < 0 || fb->O > s->layer[0].Cx || fb->from < 0) return NINT_E_ARG;
+  // step 0 can only be fed from a state that was handed in
+  if (fb->O > 0 && (!fb->w || (fb->from == 0 && !s->has_init_state))) return NINT_E_ARG;
+  return NINT_OK;
+}
 
 // A pass is first PLANNED into an ordered list of steps -- host arithmetic only: nothing is enqueued, no stream is touched, no
 // buffer is read -- and then the list is enqueued (run_steps).  nint_debug_seq_plan shows the same list to tests and tools.
-enum { STEP_CONV, STEP_MULTI, STEP_PW, STEP_GATE, STEP_WGRAD, STEP_FOLD, STEP_WRAP };
+enum { STEP_CONV, STEP_MULTI, STEP_PW, STEP_GATE, STEP_WGRAD, STEP_FOLD, STEP_WRAP, STEP_FEEDBACK };
 struct SeqProb { int op, layer, t; };              // one conv / pointwise problem (NINT_OP_*)
 struct GateCall { CellFwdJob job; nint_layer ly; int carrier; };
 struct SeqStep {
   int kind;        // a planned conv launch | a merged grid | a pointwise backward | a direct nint_cell_fwd call (stencil / dense-K: no planned form)
                    // | one layer's weight-gradient reduction | the fold of a pass's reductions | a halo wrap / clear (cyclic longitude)
+                   // | the feedback launch of a closed-loop step (tag_t = the step; no problems, n = 0)
   int probe, tag_layer, tag_t;       // the NINT_PROBE_* kind and tag it is bracketed with
   int n; SeqProb prob[NINT_MULTI_MAX + 1];         // its problems, in grid order (a reduction / the fold: none, n = 0)
-  union { ConvPlan conv; MultiPlan multi; PwArgs pw; GateCall gate; WgJobPlan wg; WgFoldPlan fold; WrapTable wrap; };
+  union { ConvPlan conv; MultiPlan multi; PwArgs pw; GateCall gate; WgJobPlan wg; WgFoldPlan fold; WrapTable wrap; FbPlan fb; };
 };
 typedef std::vector<SeqStep> Steps;
 
@@ -189,6 +200,7 @@ static int run_steps(const nint_seq* s, const Steps& steps, Probe& probe, void* 
       case STEP_WGRAD: rc = nint_internal_wgrad_enqueue(&st.wg, stream); break;
       case STEP_FOLD: rc = nint_internal_wgrad_fold_enqueue(&st.fold, stream); break;
       case STEP_WRAP: rc = nint_internal_wrap_enqueue(&st.wrap, stream); break;
+      case STEP_FEEDBACK: rc = nint_internal_feedback_enqueue(&st.fb, stream); break;
     }
     probe.stamp(st.probe, st.tag_layer, st.tag_t, 1);
     if (rc != NINT_OK) return rc;
@@ -220,14 +232,14 @@ static int plan_gate(const nint_seq* s, int n_cu, bool rows8, int l, int t, Gate
   return rc;
 }
 
-static int plan_fwd(const nint_seq* s, int n_cu, Steps& out) {
-  const int L = s->L, T = s->T;
+// the open-loop pass over steps [0, T)
+static int plan_fwd_open(const nint_seq* s, int n_cu, int T, Steps& out) {
+  const int L = s->L;
   // (t, layer) WAVEFRONT: step w runs gate(l, w - l) of every layer -- each needs gate(l-1, w-l) and gate(l, w-l-1), both of
   // step w-1 -- as ONE grid (conv_lstm_multi[8]_kernel).  T + L - 1 launches instead of T * L; the same workgroups on the same
   // data, so the results are those of the time-major order bit for bit.  Else: for t, for layer (model.py:265-267).
   const bool wavefront = s->wave && L > 1 && L <= NINT_MULTI_MAX;
   const bool rows8 = wavefront && (s->wave == 2 || s->wave == 3 || s->wave == 4);
-  out.reserve((size_t)T * L);
   for (int w = 0; w < (wavefront ? T + L - 1 : T * L); ++w) {
     GateCall gc[NINT_MULTI_MAX]; ConvPlan pl[NINT_MULTI_MAX]; SeqProb pr[NINT_MULTI_MAX];
     int n = 0; bool planned = true;
@@ -249,14 +261,46 @@ static int plan_fwd(const nint_seq* s, int n_cu, Steps& out) {
   return NINT_OK;
 }
 
+// CLOSED LOOP (struct nint_feedback): steps below F = min(max(from, 0), T) are the open-loop pass of F steps -- same
+// merges, same rows8 pinning, same launches.  From F on gate(0, t) needs gate(L-1, t-1) through the feedback, so nothing merges:
+// feedback(t), gate(0, t) ... gate(L-1, t), each gate on the tile_rows the same `wave` gives it in the open-loop pass -- the pass
+// is then that open-loop pass, bit for bit, over an input that already holds the fed values.
+static int plan_fwd(const nint_seq* s, const nint_feedback* f, int n_cu, Steps& out) {
+  const int L = s->L, T = s->T;
+  out.reserve((size_t)T * (L + 1));
+  if (f->O <= 0) return plan_fwd_open(s, n_cu, T, out);
+  const int F = f->from < T ? f->from : T;                     // (seq_check: from >= 0)
+  int rc = plan_fwd_open(s, n_cu, F, out);
+  if (rc != NINT_OK) return rc;
+  const bool rows8 = L > 1 && L <= NINT_MULTI_MAX && (s->wave == 2 || s->wave == 3 || s->wave == 4);   // plan_fwd_open's rule
+  const nint_layer* l0 = &s->layer[0];
+  const nint_layer* top = &s->layer[L - 1];
+  for (int t = F; t < T; ++t) {
+    SeqStep& fb = push(out, STEP_FEEDBACK, NINT_PROBE_FEEDBACK, 0, t);
+    // slab t of the top layer's h -> block t of xs
+    rc = nint_internal_feedback_plan(s->h[L - 1], t * s->B, s->B, top->Ch, top->Chp, f->O, f->w, f->b, (void*)s->xs, t * s->B,
+                                     l0->Cx, l0->Cxp, l0->Cx - f->O, l0->xfold ? l0->k : 0, s->lon_cyclic, &s->g, s->dtype, &fb.fb);
+    if (rc != NINT_OK) return rc;
+    for (int l = 0; l < L; ++l) {
+      GateCall gc; ConvPlan pl;
+      rc = plan_gate(s, n_cu, rows8, l, t, &gc, &pl);
+      if (rc != NINT_OK && rc != NINT_E_SHAPE) return rc;
+      if (pl.gx > 0) { push_conv(out, pl, NINT_PROBE_GATE, NINT_OP_GATE, l, t); continue; }
+      SeqStep& st = push(out, STEP_GATE, NINT_PROBE_GATE, l, t);
+      st.prob[st.n++] = SeqProb{NINT_OP_GATE, l, t}; st.gate = gc; st.gate.job.ly = nullptr;         // (run_steps passes the step's own copy)
+    }
+  }
+  return NINT_OK;
+}
+
 
 // default of the "lower layer's pointwise backward on the fused layer's x columns" option: on (962.2 -> 963.6 samples/s, profiles/HISTORY.md)
 #ifndef NINT_AUTO_LO
 #define NINT_AUTO_LO true
 #endif
 
-static int bwd_check(const nint_seq* s) {
-  const int rc = seq_check(s);
+static int bwd_check(const nint_seq* s, const nint_feedback* fb) {
+  const int rc = seq_check(s, fb);
   if (rc != NINT_OK) return rc;
   const int f = s->train_from;         // (nint_seq.train_from: nothing of a layer below it is read)
   if (f < 0 || f > s->L || (f > 0 && (s->need_dx || s->bwd_parts != 0))) return NINT_E_ARG;
@@ -266,6 +310,9 @@ static int bwd_check(const nint_seq* s) {
   if (s->fuse_bwd < 0 || (s->fuse_bwd > 2 && !(s->fuse_bwd & 0x40000000)) || s->bwd_parts < 0 || s->bwd_parts > 2) return NINT_E_ARG;
   if (s->accumulate != 0 && s->accumulate != 1) return NINT_E_ARG;     // stored or added (nint.h); no other value is a mode
   if ((((uintptr_t)s->dh_seq) & 15) != 0) return NINT_E_ALIGN;
+  // a fed window has no backward pass yet: d/dx of a fed step would re-enter the top layer's d/dh of the step before, which
+  // re-plans BPTT.  A window in which nothing is fed back trains as ever.
+  if (fb->O > 0 && fb->from < s->T) return NINT_E_ARG;
   return NINT_OK;
 }
 
@@ -501,6 +548,7 @@ static nint_seq sub_stack(const nint_seq* s, int f) {
 // that puts halo wrap launches between its steps.  Steps go out in list order on one stream, so "right behind its writer" holds
 // for every schedule: a halo slab image is wrapped behind the step that wrote its interior and before any later step reads it.
 //   forward  head: xs (all T*B images, unless folded: the fold wraps by itself) and slot 0 of every h of a given initial state;
+//            behind the feedback launch of a closed-loop step t: block t of xs (unless folded), whose interior it wrote;
 //            behind every step with a gate problem (l, t): block t+1 of h[l] -- one launch for all of a step's problems.
 //   BPTT     behind the writer of a dG block -- a pointwise backward (l, t): dG[l] block t; a fused step X[u] of layer l: dG[l]
 //            block u-1; a dgrad / fused step (l, u) with the lower layer's pointwise backward as its rider: dG[l-1] block u --
@@ -547,6 +595,9 @@ static int add_wrap_steps(const nint_seq* s, bool bwd, Steps& steps) {
   auto wrap_dG = [&](int l, int t) { if (read[(size_t)l * T + t]) w.add(dG_blk(l, t), B, dG_px(l), NINT_WRAP_COPY); };
   for (const SeqStep& st : steps) {
     out.push_back(st);
+    // closed loop: the feedback of step t wrote the interior of xs block t (a folded xs wraps by itself)
+    if (st.kind == STEP_FEEDBACK && !s->layer[0].xfold)
+      w.add((char*)s->xs + (size_t)st.tag_t * B * halo_px * s->layer[0].Cxp * es, B, (size_t)s->layer[0].Cxp * es, NINT_WRAP_COPY);
     for (int q = 0; q < st.n; ++q) {
       const int op = st.prob[q].op, l = st.prob[q].layer, t = st.prob[q].t;
       if (!bwd) {
@@ -569,11 +620,11 @@ static int add_wrap_steps(const nint_seq* s, bool bwd, Steps& steps) {
 }
 
 // check, plan (the CU count the launch-shape rules read is looked up once per pass), then the callers execute
-static int plan_chain(const nint_seq* s, bool bwd, Steps& steps) {
-  const int rc = bwd ? bwd_check(s) : seq_check(s);
+static int plan_chain(const nint_seq* s, const nint_feedback* fb, bool bwd, Steps& steps) {
+  const int rc = bwd ? bwd_check(s, fb) : seq_check(s, fb);
   if (rc != NINT_OK) return rc;
   const int n_cu = nint_internal_n_cu();
-  if (!bwd) return plan_fwd(s, n_cu, steps);
+  if (!bwd) return plan_fwd(s, fb, n_cu, steps);
   const int f = s->train_from;
   if (f == 0) return BwdPlanner(s, n_cu, steps).plan();
   if (f == s->L) return NINT_OK;                 // every layer frozen: nothing to plan
@@ -587,31 +638,32 @@ static int plan_chain(const nint_seq* s, bool bwd, Steps& steps) {
 }
 
 // ... and, for cyclic longitude only, the wrap launches in between
-static int plan_pass(const nint_seq* s, bool bwd, Steps& steps) {
-  const int rc = plan_chain(s, bwd, steps);
+static int plan_pass(const nint_seq* s, const nint_feedback* fb, bool bwd, Steps& steps) {
+  if (!fb) fb = &NO_FB;
+  const int rc = s ? plan_chain(s, fb, bwd, steps) : (int)NINT_E_ARG;
   return rc == NINT_OK && s->lon_cyclic ? add_wrap_steps(s, bwd, steps) : rc;
 }
 
-extern "C" int nint_seq_fwd(const nint_seq* s, void* stream) {
+static int run_pass(const nint_seq* s, const nint_feedback* fb, bool bwd, void* stream) {
   Steps steps;
-  const int rc = plan_pass(s, false, steps);
+  const int rc = plan_pass(s, fb, bwd, steps);
   if (rc != NINT_OK) return rc;
-  Probe probe = make_probe(s, false, stream);
+  Probe probe = make_probe(s, bwd, stream);
   return run_steps(s, steps, probe, stream);
 }
-
-extern "C" int nint_seq_bwd(const nint_seq* s, void* stream) {
-  Steps steps;
-  const int rc = plan_pass(s, true, steps);
-  if (rc != NINT_OK) return rc;
-  Probe probe = make_probe(s, true, stream);
-  return run_steps(s, steps, probe, stream);
-}
+extern "C" int nint_seq_fwd(const nint_seq* s, void* stream) { return run_pass(s, nullptr, false, stream); }
+extern "C" int nint_seq_bwd(const nint_seq* s, void* stream) { return run_pass(s, nullptr, true, stream); }
+extern "C" int nint_seq_fwd_closed(const nint_seq* s, const nint_feedback* fb, void* stream) { return run_pass(s, fb, false, stream); }
+extern "C" int nint_seq_bwd_closed(const nint_seq* s, const nint_feedback* fb, void* stream) { return run_pass(s, fb, true, stream); }
 
 // ------------------------------------------------------------------------------ the plan, for tests and tools
 extern "C" int nint_debug_seq_plan(const nint_seq* s, int bwd, nint_launch_rec* out, int cap) {
+  return nint_debug_seq_plan_closed(s, nullptr, bwd, out, cap);
+}
+
+extern "C" int nint_debug_seq_plan_closed(const nint_seq* s, const nint_feedback* fb, int bwd, nint_launch_rec* out, int cap) {
   Steps steps;
-  const int rc = plan_pass(s, bwd != 0, steps);
+  const int rc = plan_pass(s, fb, bwd != 0, steps);
   if (rc != NINT_OK) return rc;
   if (cap > 0 && !out) return NINT_E_ARG;
   int n = 0;

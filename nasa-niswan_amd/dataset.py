@@ -22,6 +22,13 @@ switches them on with ``in_channels > 5``; here they are explicit -- ``static=``
 the level-fused extension already has C = 3L+2 > 5 without them.  C becomes 3L+2+S.  A static field with zero spatial std
 is refused (the reference would divide by zero and train on NaN).
 
+Tracer input (no reference code): ``tracer_input=True`` appends the tracer of record step t-1, z-scored with
+the TARGET statistics, as the last ``levels`` input channels of step t -- the channels a ``ConvLSTM(feedback=True)`` replaces
+with its own prediction in closed loop, so teacher-forced training sees what the roll-out will feed.  C becomes 3L+2+L.
+Windows start at record step >= 1.  On the device it is one more dynamic source of the same preproc entries whose record
+pointer sits one step back.  Only on grids without a data halo (``padding`` None or equal to the grid; the model then takes
+``lon_cyclic=True``): the reference's halo pad mixes channels c and C-1-c in mode 0, which has no closed-loop meaning.
+
 Two device paths feed the model (the whole record stays resident in HBM, a window is a pointer offset):
 ``device_batch`` materialises the reference's (B,T,C,Hp,Wp) f32 tensor (one launch per batch);
 ``slab_batch`` returns a handle that the engine asks to write the SAME values straight into its bf16/f32
@@ -123,7 +130,17 @@ class _ResidentRecord(torch.utils.data.Dataset):
     already in host memory: statistics over the training part, windows, period split, one upload of the record."""
 
     def _setup(self, fields, yraw, period: str, padding, in_channels: int, sequence_length: int, levels: int,
-               grid: Tuple[int, int], pad_mode: str, device, pinned: bool = False, static=None, sequence_targets: bool = False):
+               grid: Tuple[int, int], pad_mode: str, device, pinned: bool = False, static=None, sequence_targets: bool = False,
+               tracer_input: bool = False):
+        self.tracer_input = bool(tracer_input)
+        if self.tracer_input:
+            if padding and tuple(padding) != tuple(grid):
+                raise ValueError(f"tracer_input: the padded grid {tuple(padding)} carries a data halo around the {tuple(grid)} record, "
+                                 "where a fed-back prediction has no defined value; use padding=None (or the grid itself) and a "
+                                 "model with lon_cyclic=True")
+            if static is not None:
+                raise ValueError("tracer_input: the feedback channels must be the last input channels, and static attributes are "
+                                 "appended last too; the two are not combined")
         # sequence_targets: the target is the tracer at EVERY step of the window, (T, [L,] H, W) per sample, not the last step's
         self.sequence_targets = bool(sequence_targets)
         self.period, self.padding, self.seq_len, self.levels = period, tuple(padding) if padding else None, sequence_length, levels
@@ -158,12 +175,17 @@ class _ResidentRecord(torch.utils.data.Dataset):
             self.static = S
             self.X_mean = np.concatenate([self.X_mean, self.S_mean])
             self.X_std = np.concatenate([self.X_std, self.S_std])
-        if len(self.X_mean) != in_channels:
-            raise ValueError(f"in_channels={in_channels}, but the fields and static attributes give {len(self.X_mean)} channels")
         self.y_mean = np.float32(self.yraw[:ntrain].mean())
         self.y_std = np.float32(self.yraw[:ntrain].std())
+        if self.tracer_input:               # the tracer of the step before, with the target's statistics: `levels` more channels
+            self.X_mean = np.concatenate([self.X_mean, np.full(levels, self.y_mean, dtype=np.float32)])
+            self.X_std = np.concatenate([self.X_std, np.full(levels, self.y_std, dtype=np.float32)])
+        if len(self.X_mean) != in_channels:
+            raise ValueError(f"in_channels={in_channels}, but the fields , static attributes and tracer input give {len(self.X_mean)} channels")
         nseq = n_steps - sequence_length + 1
         lo, hi = {"train": (0, ntrain), "val": (ntrain, ntest0), "test": (ntest0, nseq)}[period]     # dataset.py:601-612
+        if self.tracer_input:
+            lo = max(lo, 1)                 # step t reads the tracer of step t-1
         self.first = np.arange(min(lo, nseq), min(hi, nseq))        # first time index of each window
         self._dev = None
 
@@ -204,6 +226,9 @@ class _ResidentRecord(torch.utils.data.Dataset):
         srcs = [(dv[name].data_ptr(), a.shape[1] if a.ndim == 4 else 1) for name, a in self.fields]
         if self.static is not None:
             srcs.append((dv["static"].data_ptr(), self.static.shape[0]))
+        if self.tracer_input:               # the tracer record from one step back: step t of a window reads record step t0 + t - 1 >= 0
+            L, (H, W) = self.levels, self.grid
+            srcs.append((dv["y"].data_ptr() - L * H * W * 4, L))
         n = len(srcs)
         ptrs = (C.c_void_p * n)(*[p for p, _ in srcs])
         lev = (C.c_int * n)(*[l for _, l in srcs])
@@ -282,7 +307,7 @@ class SyntheticE33OMA_CRNN(_ResidentRecord):
     def __init__(self, period: str, species: str = "bcb", padding: Tuple[int, int] = (100, 154), in_channels: int = 5,
                  sequence_length: int = 10, *, levels: int = 1, n_steps: int = 480, grid: Tuple[int, int] = (90, 144),
                  pad_mode: str = "reference", device="cuda", seed: int = 0, static_channels: int = 0,
-                 sequence_targets: bool = False):
+                 sequence_targets: bool = False, tracer_input: bool = False):
         super().__init__()
         assert species == "bcb", "only the BCB statistics ship with the reference"
         S = int(static_channels)
@@ -291,8 +316,12 @@ class SyntheticE33OMA_CRNN(_ResidentRecord):
         if S and in_channels != 3 * levels + 2 + S:
             raise ValueError(f"static_channels={S} with levels={levels} needs in_channels = 3*levels+2+static_channels = "
                              f"{3 * levels + 2 + S}, got {in_channels}")
-        # without static attributes, an in_channels that is not 3L+2 means that many generic fields
-        self.generic = S == 0 and in_channels != 3 * levels + 2
+        # tracer_input: the last `levels` of the in_channels are the tracer of the step before, not a field of their own
+        nfield = in_channels - (levels if tracer_input else 0)
+        if nfield < 1:
+            raise ValueError(f"tracer_input with levels={levels} needs in_channels > {levels}, got {in_channels}")
+        # without static attributes, a field count that is not 3L+2 means that many generic fields
+        self.generic = S == 0 and nfield != 3 * levels + 2
         H, W = grid
         rng = np.random.default_rng(seed)
 
@@ -306,7 +335,7 @@ class SyntheticE33OMA_CRNN(_ResidentRecord):
             return a
         if self.generic:
             # `in_channels` generic fields with the wind statistics; one source of in_channels "levels"
-            self.gen = field("u", (n_steps, in_channels, H, W))
+            self.gen = field("u", (n_steps, nfield, H, W))
             fields = [("gen", self.gen)]
         else:
             self.u = field("u", (n_steps, levels, H, W))
@@ -318,7 +347,7 @@ class SyntheticE33OMA_CRNN(_ResidentRecord):
         yraw = field("bc_conc", (n_steps, levels, H, W), True)
         static = synth_static(S, grid, seed) if S else None
         self._setup(fields, yraw, period, padding, in_channels, sequence_length, levels, grid, pad_mode, device, static=static,
-                    sequence_targets=sequence_targets)
+                    sequence_targets=sequence_targets, tracer_input=tracer_input)
 
 
 class E33OMA90D_CRNN(_ResidentRecord):
@@ -343,7 +372,8 @@ class E33OMA90D_CRNN(_ResidentRecord):
     @classmethod
     def from_arrays(cls, u, v, omega, prec, src, conc, *, period: str = "train", species: str = "bcb",
                     padding: Tuple[int, int] = (100, 154), sequence_length: int = 10, pad_mode: str = "reference",
-                    device="cuda", pinned: bool = True, static=None, sequence_targets: bool = False):
+                    device="cuda", pinned: bool = True, static=None, sequence_targets: bool = False,
+                    tracer_input: bool = False):
         self = cls.__new__(cls)
         torch.utils.data.Dataset.__init__(self)
         f32 = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.float32))
@@ -360,6 +390,6 @@ class E33OMA90D_CRNN(_ResidentRecord):
         self.species, self.generic = species, False
         fields = [("u", u), ("v", v), ("w", omega), ("prec", prec), ("src", src)]          # fusion order dataset.py:584
         nS = np.shape(static)[0] if static is not None and np.ndim(static) else 0
-        self._setup(fields, conc, period, padding, 3 * L + 2 + nS, sequence_length, L, (H, W), pad_mode, device, pinned=pinned,
-                    static=static, sequence_targets=sequence_targets)
+        self._setup(fields, conc, period, padding, 3 * L + 2 + nS + (L if tracer_input else 0), sequence_length, L, (H, W), pad_mode,
+                    device, pinned=pinned, static=static, sequence_targets=sequence_targets, tracer_input=tracer_input)
         return self

@@ -11,7 +11,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 
 from . import _lib
-from ._lib import NINT_BF16, NINT_F32, NintGeom, NintLayer, NintSeq, check, ptr, stream_ptr
+from ._lib import NINT_BF16, NINT_F32, NintFeedback, NintGeom, NintLayer, NintSeq, check, ptr, stream_ptr
 
 # 0: the library picks the gate / dgrad pixel-tile height per launch shape; 4 or 8 forces it for every layer of
 # engines built afterwards (nint_layer.tile_rows) -- how the tests run both heights on every shape
@@ -91,6 +91,9 @@ class Workspace:
         self.dx = None
         self._dh_seq = None
         self.Cxp0 = Cxp0
+        # closed loop (nint_feedback): what the last forward pass on this workspace fed back (O = 0: nothing), and the tensors
+        # its pointers name
+        self.fb, self._fb_keep = NintFeedback(), None
         self.seq = NintSeq()
         s = self.seq
         s.dtype, s.B, s.T, s.L = eng.dt, B, T, len(eng.cfgs)
@@ -479,16 +482,41 @@ class SeqEngine:
 
     # ------------------------------------------------------------------ passes
     def forward(self, ws: Workspace, x: torch.Tensor, h0: Optional[List[torch.Tensor]] = None,
-                c0: Optional[List[torch.Tensor]] = None):
+                c0: Optional[List[torch.Tensor]] = None, feedback=None):
         """x (B,T,C,H,W) f32 on the engine's device, or a dataset.SlabBatch of that shape.  Runs model.py:253-271
-        (all layers, all steps)."""
+        (all layers, all steps).
+
+        ``feedback = (w, b, from_step)``: CLOSED LOOP (nint_seq_fwd_closed) -- the head ``w`` (O, Ch_top), ``b`` (O)
+        or None, of the top layer's hidden state is rounded to the storage type and written into the last O input channels
+        before every step ``t >= from_step``; earlier steps see what ``x`` holds.  The input slab is filled from ``x`` first
+        (tensor or SlabBatch), then the pass writes into it.  from_step = 0 needs a has_init workspace."""
         B, T, Cc, H, W = x.shape
         assert (B, T, H, W) == (ws.B, ws.T, ws.H, ws.W) and Cc == self.cfgs[0].Cx
+        s, fb = ws.seq, ws.fb
+        # ws.fb stays as this pass sets it: a backward pass on a fed window is refused by the library (nint_seq_bwd_closed)
+        fb.w, fb.b, fb.O, fb.from_step, ws._fb_keep = None, None, 0, 0, None
+        if feedback is not None:
+            w, b, from_step = feedback
+            _, _, O, w2, b2 = self._head_args(w, b)
+            from_step = int(from_step)
+            if w2.numel() != O * self.cfgs[-1].Ch or not 1 <= O <= Cc:      # (O, Ch) or the 1x1 conv's (O, Ch, 1, 1)
+                raise ValueError(f"feedback: head weight {tuple(w.shape)} does not map {self.cfgs[-1].Ch} hidden channels onto "
+                                 f"at most {Cc} input channels")
+            if from_step < 0 or (from_step == 0 and not s.has_init_state):
+                raise ValueError("feedback: step 0 can only be fed from a given initial state (from_step = 0 needs a state)")
+            if self._beyond_fused_head(self.layers[-1].Chp, O):
+                raise _lib.NintError(f"feedback: a head of {O} outputs on {self.layers[-1].Chp} padded channels is beyond the "
+                                     "staged head kernels (nint_head_feedback: NINT_E_SHAPE)")
+            ws._fb_keep = (w2, b2)      # the pointers below stay valid as long as the fields name them
+            fb.w, fb.b, fb.O, fb.from_step = ptr(w2), ptr(b2), O, from_step
         self.pack_input(ws, x)
         if h0 is not None:
             self._write_state(h0, c0, self._slot_ptrs(ws, 0), B, ws.g, "0")
         self._set_wave(ws)
-        check(self.lib.nint_seq_fwd(C.byref(ws.seq), stream_ptr()), "nint_seq_fwd")
+        if fb.O > 0:
+            check(self.lib.nint_seq_fwd_closed(C.byref(s), C.byref(fb), stream_ptr()), "nint_seq_fwd_closed")
+        else:
+            check(self.lib.nint_seq_fwd(C.byref(s), stream_ptr()), "nint_seq_fwd")
 
     def _set_wave(self, ws: Workspace):
         """nint_seq.wave: independent launches as one grid (a forward wavefront step; in BPTT the dgrad launches of layers 0 and 1
@@ -754,7 +782,10 @@ class SeqEngine:
         s.accumulate = int(bool(accumulate))
         s.train_from = train_from
         try:
-            if train_from < L:
+            if ws.fb.O > 0:         # the window's forward pass was a closed-loop one: refused unless nothing was fed back
+                check(self.lib.nint_seq_bwd_closed(C.byref(s), C.byref(ws.fb), stream_ptr()), "nint_seq_bwd_closed (the backward "
+                      "pass of a window in which the prediction was fed back is not defined)")
+            elif train_from < L:
                 check(self.lib.nint_seq_bwd(C.byref(s), stream_ptr()), "nint_seq_bwd")
         finally:
             s.bwd_parts = 0

@@ -285,7 +285,8 @@ def evaluate_skill(net, dataset, batch_size: int = 8, halo: Tuple[int, int] = (5
 
 # ------------------------------------------------------------------------------ roll-forward inference with carried state
 @torch.no_grad()
-def predict_stream(net, dataset, lanes: int = 1, halo: Tuple[int, int] = (5, 5), skill: Optional[SkillAccumulator] = None):
+def predict_stream(net, dataset, lanes: int = 1, halo: Tuple[int, int] = (5, 5), skill: Optional[SkillAccumulator] = None,
+                   closed_loop: bool = False, spinup: int = 1):
     """Walk the dataset's period ONCE: non-overlapping chunks of `dataset.seq_len` steps with the state carried on the device
     (`net(X, state, return_state="device")`), the head applied at every step (head_forward_seq) -- where `predict` runs
     every record step seq_len times, once per sliding window it falls into.
@@ -299,8 +300,19 @@ def predict_stream(net, dataset, lanes: int = 1, halo: Tuple[int, int] = (5, 5),
     that fill no full row of lanes are dropped too.
 
     `skill`: a SkillAccumulator (O, Hc, Wc of the dataset's grid) that every chunk's steps are folded into
-    (update_from_pred, time steps as samples, slot 0) against the tracer at the same steps."""
+    (update_from_pred, time steps as samples, slot 0) against the tracer at the same steps.
+
+    `closed_loop` (a ``ConvLSTM(feedback=True)``): the model runs on its own prediction.  The first chunk
+    takes its first `spinup` >= 1 steps from the dataset (the spin-up on analysis data) and feeds the head's output back
+    from step `spinup` on; every later chunk is fed from its step 0, from the head of the carried state -- so the walk
+    equals ONE closed-loop window over the whole period, bit for bit.  With `lanes` > 1 every lane spins up on its own
+    first chunk (the lanes' first chunks are one batch)."""
     from .dataset import stateful_schedule
+    if closed_loop:
+        if not getattr(net, "feedback", False):
+            raise ValueError("predict_stream(closed_loop=True) needs a ConvLSTM built with feedback=True")
+        if isinstance(spinup, bool) or int(spinup) != spinup or spinup < 1:
+            raise ValueError(f"predict_stream: spinup must be an integer >= 1 (step 0 has no prediction to be fed), got {spinup!r}")
     net.eval()
     T = dataset.seq_len
     Hc, Wc = dataset.grid
@@ -321,7 +333,8 @@ def predict_stream(net, dataset, lanes: int = 1, halo: Tuple[int, int] = (5, 5),
             net._pack_weights(eng)
             if state is not None:
                 eng.load_state(ws, state)
-            eng.forward(ws, X)
+            fb = (net.conv.weight, net.conv.bias, int(spinup) if k == 0 else 0) if closed_loop else None
+            eng.forward(ws, X, feedback=fb)
             state = eng.save_state(ws, state)
             seq = eng.head_forward_seq(ws, net.conv.weight, net.conv.bias)             # (B, T*O, H, W), channel t*O + o
         out[:, k * T:(k + 1) * T] = seq.view(B, T, O, H, W)[:, :, :, halo[0]:halo[0] + Hc, halo[1]:halo[1] + Wc]
@@ -347,3 +360,65 @@ def _step_targets(dataset, dv, t0s, T):
     check(_lib.load().nint_preproc_fuse_pad_batch(yptr, ylev, 1, ptr(dv["ymean"]), ptr(dv["ystd"]), tl, B, ptr(y), T, H, W, H, W, 1,
                                                   stream_ptr()), "target z-score")
     return y
+
+
+# ------------------------------------------------------------------------------ closed-loop roll-out skill by lead time
+@torch.no_grad()
+def rollout_skill(net, dataset, starts: Sequence[int], horizon: int, spinup: int, batch_size: int = 8, lat=None,
+                  halo: Optional[Tuple[int, int]] = None) -> SkillAccumulator:
+    """Skill of the free-running model by LEAD TIME.  From every record step in `starts` a window of
+    `spinup + horizon` steps runs closed loop from step `spinup` (``ConvLSTM(feedback=True)``; the first `spinup` steps see
+    the dataset's input, the rest the model's own prediction in the feedback channels).  The prediction made `j` steps into
+    the free run -- the head's output at window step spinup + j, against the tracer of that record step -- is folded into
+    slot j of the returned SkillAccumulator (update_from_pred, targets from the record), so
+    ``acc.report(dataset.y_mean, dataset.y_std, slots=[j])`` is the skill at lead time j, 0 <= j < horizon.
+
+    `starts`: record steps (not dataset indices), each with start + spinup + horizon <= the record's length, and >= 1 for a
+    ``tracer_input`` dataset.  `halo`: the crop's offset inside the model grid (None: centred)."""
+    from .dataset import SlabBatch
+    if not getattr(net, "feedback", False):
+        raise ValueError("rollout_skill needs a ConvLSTM built with feedback=True")
+    horizon, spinup = int(horizon), int(spinup)
+    if horizon < 1 or spinup < 1:
+        raise ValueError(f"rollout_skill: horizon and spinup must be >= 1, got {(horizon, spinup)}")
+    T = spinup + horizon
+    starts = [int(v) for v in starts]
+    n_steps = int(dataset.yraw.shape[0])
+    lo = 1 if getattr(dataset, "tracer_input", False) else 0
+    if not starts or min(starts) < lo or max(starts) + T > n_steps:
+        raise ValueError(f"rollout_skill: every start must lie in [{lo}, {n_steps - T}] for windows of {T} steps in a record of {n_steps}")
+    net.eval()
+    dev = next(net.parameters()).device
+    eng = net._engine(dev)
+    Hc, Wc = dataset.grid
+    O = net.conv.weight.shape[0]
+    if O != dataset.levels:
+        raise ValueError(f"rollout_skill: the head has {O} outputs, the record's tracer {dataset.levels} levels")
+    acc = SkillAccumulator(O, Hc, Wc, nslots=horizon, lat=lat, device=dev, halo=halo)
+    dv = dataset._device_arrays()
+    for s in range(0, len(starts), batch_size):
+        t0s = starts[s:s + batch_size]
+        X = SlabBatch(dataset, np.asarray(t0s), T)
+        B, _, _, H, W = X.shape
+        oy, ox = ((H - Hc) // 2, (W - Wc) // 2) if halo is None else halo
+        with eng.window(B, T, H, W, False, False) as ws:
+            net._pack_weights(eng)
+            eng.forward(ws, X, feedback=(net.conv.weight, net.conv.bias, spinup))
+            seq = eng.head_forward_seq(ws, net.conv.weight, net.conv.bias).view(B, T, O, H, W)
+        y = _step_targets(dataset, dv, t0s, T)                                    # (B, T, L, Hc, Wc)
+        free = seq[:, spinup:].reshape(B * horizon, O, H, W)
+        slots = [j for _ in range(B) for j in range(horizon)]
+        acc.update_from_pred(free, y[:, spinup:].reshape(B * horizon, O, Hc, Wc), (oy, ox), slots)
+    return acc
+
+
+def lead_time_r2(acc: SkillAccumulator) -> np.ndarray:
+    """R2 per slot of an accumulator, every output and grid cell of the slot's samples pooled (rollout_skill: per lead time):
+    1 - sum (y-p)^2 / (sum y^2 - (sum y)^2 / n) from the slot's f64 planes; nan for an empty slot"""
+    pix, counts, _ = acc.sums()
+    out = np.full(acc.nslots, np.nan)
+    for j in range(acc.nslots):
+        n = counts[j] * acc.O * acc.Hc * acc.Wc
+        if n > 0:
+            out[j] = float(_r2(pix[j, 4].sum(), _centred(pix[j, 2].sum(), pix[j, 0].sum(), n)))
+    return out

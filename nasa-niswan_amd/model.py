@@ -116,8 +116,9 @@ class _CallOpts:
     """the non-tensor arguments of _ConvLSTMFn: the device state that comes in (or None), what goes out, the box the outgoing
     device state is handed back in (a Function's outputs are tensors), and the default route's head-backward rule"""
 
-    def __init__(self, state_in=None, return_state=False, seq_always=False):
+    def __init__(self, state_in=None, return_state=False, seq_always=False, free_from=None):
         self.state_in, self.return_state, self.state_out = state_in, return_state, None
+        self.free_from = free_from      # closed loop from this step on (ConvLSTM(feedback=True)); None: open loop
         # The default call (no state in, none out) of a return_sequence module ALWAYS takes the per-step head backward
         # (head_backward_seq + BPTT with seq_grads), also when only `pred` has a cotangent; a call with state does so only
         # when `seq` has one.  Two launch plans and two summation orders of dw_head: kept apart, as they have always been.
@@ -151,7 +152,7 @@ class _ConvLSTMFn(torch.autograd.Function):
         if opts.state_in is not None:
             eng.load_state(ws, opts.state_in)
         h0, c0 = (list(st[0::2]), list(st[1::2])) if st else (None, None)
-        eng.forward(ws, x, h0, c0)
+        eng.forward(ws, x, h0, c0, feedback=None if opts.free_from is None else (head_w, head_b, opts.free_from))
         outs = [eng.head_forward(ws, head_w, head_b)]
         if module.return_sequence:
             outs.append(eng.head_forward_seq(ws, head_w, head_b))       # every step in one launch
@@ -297,9 +298,16 @@ class ConvLSTM(_EngineOwner, nn.Module):
     """reference model.py:234-274"""
 
     def __init__(self, input_channels, hidden_channels, kernel_size, num_layers, *, out_channels=1,
-                 return_sequence=False, compute_dtype="f32", lon_cyclic=False):
+                 return_sequence=False, compute_dtype="f32", lon_cyclic=False, feedback=False):
         super().__init__()
         assert len(hidden_channels) == num_layers, 'The length of hidden_channels must be equal to num_layers.'
+        # closed loop (DESIGN.md 4.18): the last out_channels input channels are FEEDBACK channels, which forward(free_from=s)
+        # fills with the head's own output from step s on.  Not a parameter and not in the state_dict; without free_from the
+        # module is, bit for bit, the module without it.
+        self.feedback = bool(feedback)
+        if self.feedback and not 1 <= out_channels <= input_channels:
+            raise ValueError(f"ConvLSTM(feedback=True): the {out_channels} head outputs are fed back into the last input channels, "
+                             f"so out_channels <= input_channels ({input_channels}) is required")
         self.num_layers = num_layers
         self.layers = nn.ModuleList()
         self.layers.append(ConvLSTMCell(input_channels, hidden_channels[0], kernel_size[0], compute_dtype=compute_dtype))
@@ -326,7 +334,7 @@ class ConvLSTM(_EngineOwner, nn.Module):
         inference loops, which drive the engine themselves, do before a forward pass"""
         eng.pack_weights([c.conv.weight for c in self.layers], [c.conv.bias for c in self.layers])
 
-    def forward(self, x, state=None, *, return_state=False):
+    def forward(self, x, state=None, *, return_state=False, free_from=None):
         """x: (batch_size, sequence_length, channels, height, width)  (model.py:254).
 
         ``state``: None (zeros, model.py:259-262), a list of ``num_layers`` ``(h, c)`` tensor pairs (B, Ch_l, H, W) -- the
@@ -337,14 +345,37 @@ class ConvLSTM(_EngineOwner, nn.Module):
         Tensor states are differentiable both ways: a state that requires grad receives dL/dh0, dL/dc0, and the returned
         tensors carry gradients back into the window, so two chained calls are full BPTT across the boundary.  A
         ``ConvLSTMState`` in or out is DETACHED: chaining calls through it is truncated BPTT.  ``net(x)`` alone takes the
-        path it always took."""
+        path it always took.
+
+        ``free_from = s`` (a ``feedback=True`` module only): CLOSED LOOP from step s -- at every step t >= s the last
+        ``out_channels`` input channels are replaced, on the device, by the head of the top layer's hidden state after step
+        t-1, rounded to the storage type; steps t < s see ``x`` as given (the spin-up).  ``free_from >= T`` feeds nothing
+        back; ``free_from = 0`` needs a ``state``.  Forward only: with anything that requires grad under grad mode and
+        ``free_from < T`` the call raises -- back-propagation through the fed-back prediction is not implemented."""
+        if free_from is not None:                       # every refusal here, before anything is launched (or any device is asked for)
+            if not self.feedback:
+                raise ValueError("free_from needs a ConvLSTM built with feedback=True")
+            if isinstance(free_from, bool) or int(free_from) != free_from or free_from < 0:
+                raise ValueError(f"free_from must be a step index >= 0, got {free_from!r}")
+            free_from = int(free_from)
+            if len(x.shape) != 5:
+                raise ValueError(f"ConvLSTM: x must be (B, T, C, H, W), got {tuple(x.shape)}")
+            if free_from == 0 and state is None:
+                raise ValueError("free_from=0 feeds step 0 from the head of the initial state: pass a state")
+            if free_from < x.shape[1] and torch.is_grad_enabled() and (
+                    x.requires_grad or any(p.requires_grad for p in self.parameters())
+                    or (state is not None and not isinstance(state, ConvLSTMState)
+                        and any(t.requires_grad for pair in state for t in pair))):
+                raise RuntimeError("ConvLSTM: back-propagation through the fed-back prediction (free_from < T under grad mode with "
+                                   "an input, parameter or state that requires grad) is not implemented; run the closed loop "
+                                   "under torch.no_grad(), or train teacher-forced (free_from=None)")
         _require_cuda(x, "ConvLSTM")
         wb = []
         for cell in self.layers:
             wb += [cell.conv.weight, cell.conv.bias]
         st = []
         if state is None and not return_state:          # the default call: nothing to validate, and its own head-backward rule
-            opts = _CallOpts(seq_always=self.return_sequence)
+            opts = _CallOpts(seq_always=self.return_sequence, free_from=free_from)
         else:
             if return_state not in (False, True, "device"):
                 raise ValueError(f"return_state must be False, True or 'device', got {return_state!r}")
@@ -357,7 +388,7 @@ class ConvLSTM(_EngineOwner, nn.Module):
             elif state is not None:
                 hs, cs = eng._state_tensors(state, (B, H, W))
                 st = _interleave(hs, cs)
-            opts = _CallOpts(state if isinstance(state, ConvLSTMState) else None, return_state)
+            opts = _CallOpts(state if isinstance(state, ConvLSTMState) else None, return_state, free_from=free_from)
         out = _ConvLSTMFn.apply(self, torch.is_grad_enabled(), opts, x, self.conv.weight, self.conv.bias, *wb, *st)
         out = list(out) if isinstance(out, tuple) else [out]
         n0 = 2 if self.return_sequence else 1

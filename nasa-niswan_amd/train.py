@@ -129,6 +129,16 @@ def get_arguments(argv=None, MODEL='LSTM-00', SPECIES='bcb', LEARNING_RATE=1.0E-
                         help="the model treats longitude as periodic: column 0 and column W-1 of its grid are neighbours in every "
                              "convolution (ConvLSTM(lon_cyclic=True)), so the input needs no longitude halo and the loss no "
                              "longitude crop.  The width of --input-size must equal the width of --grid")
+    parser.add_argument("--tracer-input", action="store_true",
+                        help="the tracer of the step before joins the input as its last --levels channels (dataset tracer_input; "
+                             "--in-channels counts the other channels, the model gets --in-channels + --levels): teacher-forced "
+                             "training of a model that can run on its own prediction (ConvLSTM(feedback=True)).  Needs a grid "
+                             "without a data halo: --input-size equal to --grid, usually with --cyclic-longitude")
+    parser.add_argument("--test-rollout", type=int, default=0, metavar="HORIZON",
+                        help="with --tracer-input: after the test pass rank 0 runs the model closed loop over the 'test' period "
+                             "(inference.rollout_skill) and prints R2 per lead time 0 .. HORIZON-1")
+    parser.add_argument("--rollout-spinup", type=int, default=None, metavar="K",
+                        help="steps of analysis input before the free run of --test-rollout (default: --sequence-length)")
     parser.add_argument("--reset-optimizer", action="store_true",
                         help="with --use-checkpoint: load the weights of --restore-from only and start the optimizer afresh "
                              "(the fine-tuning entry point; without it an optimizer state of other param groups is an error)")
@@ -140,6 +150,17 @@ def get_arguments(argv=None, MODEL='LSTM-00', SPECIES='bcb', LEARNING_RATE=1.0E-
     if args.cyclic_longitude and int(args.input_size[1]) != int(args.grid[1]):
         parser.error(f"--cyclic-longitude: the model wraps at the edge of its own grid, so --input-size's width "
                      f"({args.input_size[1]}) must be --grid's ({args.grid[1]}): no longitude halo")
+    if args.tracer_input and tuple(int(v) for v in args.input_size) != tuple(int(v) for v in args.grid):
+        parser.error(f"--tracer-input: a fed-back prediction has no value in a data halo, so --input-size {tuple(args.input_size)} "
+                     f"must equal --grid {tuple(args.grid)}; pass --cyclic-longitude for periodic longitude instead of the halo")
+    if args.tracer_input and args.static_channels:
+        parser.error("--tracer-input and --static-channels both claim the last input channels; they are not combined")
+    if args.test_rollout < 0 or (args.test_rollout > 0 and not args.tracer_input):
+        parser.error("--test-rollout takes a horizon >= 1 and needs --tracer-input")
+    if args.rollout_spinup is None:
+        args.rollout_spinup = args.sequence_length
+    if args.test_rollout > 0 and args.rollout_spinup < 1:
+        parser.error("--rollout-spinup must be >= 1")
     if args.spinup_steps < 0:
         parser.error("--spinup-steps must be >= 0")
     if args.spinup_steps > 0 and not args.sequence_loss:
@@ -203,15 +224,16 @@ def main(args):
     if args.model.split('-')[0] != 'LSTM':
         raise SystemExit("only the LSTM family (ConvLSTM) is in scope of this build")
     out_ch = args.levels
-    generator = pkg.ConvLSTM(args.in_channels, list(args.hidden_channels), list(args.kernel_size), args.num_layers,
+    in_ch = args.in_channels + (args.levels if args.tracer_input else 0)      # the tracer of the step before: --levels more channels
+    generator = pkg.ConvLSTM(in_ch, list(args.hidden_channels), list(args.kernel_size), args.num_layers,
                              out_channels=out_ch, compute_dtype=args.dtype,
-                             lon_cyclic=args.cyclic_longitude).to(dev)                      # train.py:48
+                             lon_cyclic=args.cyclic_longitude, feedback=args.tracer_input).to(dev)  # train.py:48
     H, W = (int(v) for v in args.grid)
     if args.input_size[0] < H or args.input_size[1] < W:
         raise SystemExit(f"--input-size {tuple(args.input_size)} is smaller than --grid {(H, W)}: the model runs on the "
                          "grid plus its halo (launcher.sh:24)")
     halo = ((args.input_size[0] - H) // 2, (args.input_size[1] - W) // 2)                    # 5,5 in the reference (train.py:102)
-    ds_kw = dict(species=args.species, padding=tuple(args.input_size), in_channels=args.in_channels,
+    ds_kw = dict(species=args.species, padding=tuple(args.input_size), in_channels=in_ch, tracer_input=args.tracer_input,
                  sequence_length=args.sequence_length, levels=args.levels, n_steps=args.synthetic_steps,
                  grid=(H, W), pad_mode=args.pad_mode, device=dev, static_channels=args.static_channels,
                  sequence_targets=args.sequence_loss)
@@ -301,6 +323,22 @@ def main(args):
             logger['skill'] = report
             print(f"Test period ({len(test_dataset)} windows): mean R2 per window {np.mean(report.r2_temporal):.5f}, "
                   f"mean R2 per grid cell {np.mean(report.r2_spatial):.5f}")
+        if args.test_rollout:
+            # closed loop over the 'test' period: non-overlapping windows of spin-up + horizon steps, skill by lead time
+            from nasa_niswan_amd.inference import lead_time_r2, rollout_skill
+            test_dataset = SyntheticE33OMA_CRNN('test', **dict(ds_kw, sequence_targets=False))
+            span = args.rollout_spinup + args.test_rollout
+            t_lo, t_hi = int(test_dataset.first[0]), int(test_dataset.yraw.shape[0])
+            starts = list(range(t_lo, t_hi - span + 1, span))
+            if not starts:
+                raise SystemExit(f"--test-rollout: the test period ({t_hi - t_lo} steps) holds no window of {span} steps")
+            acc = rollout_skill(generator, test_dataset, starts, args.test_rollout, args.rollout_spinup, args.batch_size,
+                                lat=grid_latitudes(H))
+            r2_lead = [float(v) for v in lead_time_r2(acc)]
+            logger['rollout_r2'] = r2_lead
+            np.save(os.path.join(args.snapshot_dir, "rollout_r2.npy"), np.array(r2_lead))
+            print(f"Closed-loop roll-out, {len(starts)} windows, spin-up {args.rollout_spinup}: R2 per lead time")
+            print("  " + " ".join(f"{j}:{v:.4f}" for j, v in enumerate(r2_lead)))
         time_elapsed = time.time() - since
         print(f'Training complete in {time_elapsed // 60:.0f}m {time_elapsed % 60:.0f}s')
     if world > 1:

@@ -97,6 +97,8 @@ WAVES = [None, 0, 1, 4, 2, 5, 4]            # engine.FORCE_WAVE by case number
 TILE_ROWS = [0, 0, 4, 8]                    # engine.FORCE_TILE_ROWS by case number
 OLD_MODES = ("plain", "trainer", "cell", "dataset")
 NEW_MODES = ("state", "train_opts", "stateful", "finetune")       # (a new mode goes LAST: case_rng keys a stream by position)
+# ... and the modes with a stream per case that have a draw and a run of their own, behind them (positions as above)
+STREAM_MODES = NEW_MODES + ("closed_loop",)
 LIM = {"f32": 1e-3, "bf16": 3e-2}
 LOSS_LIM = {"f32": 2e-6, "bf16": 2e-2}
 
@@ -242,7 +244,7 @@ def check_head_wgrad(tag, dW, dWo, h_stored, h_oracle, dpred, dpred_oracle=None)
 # ---------------------------------------------------------------------------------------------------- the draw (pure)
 def case_rng(seed: int, mode: str, it: int):
     """the generator of one case of a state / options mode: its own stream, so a case replays without the ones before it"""
-    return np.random.default_rng([int(seed), 1 + NEW_MODES.index(mode), int(it)])
+    return np.random.default_rng([int(seed), 1 + STREAM_MODES.index(mode), int(it)])
 
 
 def _halo(rng, H, W):
@@ -254,6 +256,8 @@ def draw_case(rng, it: int, mode: str = "plain", big: bool = False, wide: bool =
     """One case from ``rng``: the shared shape draw, the knobs that rotate with the case number ``it``, then the values of
     ``mode``.  Pure: numpy only.  ``case["draws"]`` lists (name, shape) of the standard-normal tensors the run then draws from
     the same generator, in order (``draw_data``); a replay that skips the case draws and drops them."""
+    if mode == "closed_loop":
+        return draw_closed_loop(rng, it)
     new = mode in NEW_MODES
     L = int(rng.integers(1, 5))
     hidden = [int(rng.choice([4, 8, 16, 24, 32, 48, 64] if new else [4, 8, 16, 24, 32, 48, 64, 64, 128])) for _ in range(L)]
@@ -367,6 +371,31 @@ def draw_case(rng, it: int, mode: str = "plain", big: bool = False, wide: bool =
     return case
 
 
+def draw_closed_loop(rng, it: int) -> dict:
+    """--closed-loop: a stack, a grid, O feedback channels (the last O of C), the first fed step (T: nothing is fed), a tensor
+    state or none (step 0 can only be fed from one), both storage types, cyclic longitude or zero padding, the thin-input fold
+    allowed or off.  Pure."""
+    L = int(rng.integers(1, 4))
+    hidden = [int(rng.choice([4, 8, 16, 24, 32, 64])) for _ in range(L)]
+    ks = [int(rng.choice([1, 3, 3, 5, 5])) for _ in range(L)]
+    C = int(rng.choice([1, 3, 4, 6, 16, 33, 40, 62]))
+    out = min(C, int(rng.choice([1, 1, 2, 3, 20])))
+    B, T = int(rng.integers(1, 4)), int(rng.integers(2, 6))
+    H, W = int(rng.integers(5, 21)), int(rng.integers(9, 41))
+    dtype = "f32" if it % 2 == 0 else "bf16"
+    wave, rows = WAVES[it % 7], TILE_ROWS[it % 4]
+    cyclic, fold, with_state = (bool(rng.integers(0, 2)) for _ in range(3))
+    fb_from = int(rng.integers(0 if with_state else 1, T + 1))
+    draws = [("X", (B, T, C, H, W))]
+    if with_state:
+        for l, ch in enumerate(hidden):
+            draws += [(f"{n}.{l}", (B, ch, H, W)) for n in ("h0", "c0")]
+    return dict(it=it, mode="closed_loop", L=L, hidden=hidden, ks=ks, C=C, out=out, B=B, T=T, H=H, W=W, dtype=dtype, wave=wave,
+                rows=rows, wide=0, cyclic=cyclic, fold=fold, with_state=with_state, fb_from=fb_from, draws=draws,
+                tag=f"#{it} C={C} hidden={hidden} k={ks} out={out} B={B} T={T} {H}x{W} {dtype} wave={wave} rows={rows} "
+                    f"closed loop from {fb_from} cyclic={int(cyclic)} fold={int(fold)} state={int(with_state)}")
+
+
 def draw_data(rng, case) -> dict:
     """the standard-normal tensors of a case, f32, from the generator that drew it"""
     return {name: torch.from_numpy(rng.standard_normal(sh).astype(np.float32)) for name, sh in case["draws"]}
@@ -377,7 +406,7 @@ def draw_cases(seed: int, n: int, mode: str = "plain", big: bool = False, wide: 
     cases = []
     rng = np.random.default_rng(seed)
     for it in range(n):
-        if mode in NEW_MODES:
+        if mode in STREAM_MODES:
             cases.append(draw_case(case_rng(seed, mode, it), it, mode))
         else:
             cases.append(draw_case(rng, it, mode, big, wide))
@@ -1001,6 +1030,7 @@ def parse(argv=None):
     ap.add_argument("--train-opts", action="store_true", help="FusedTrainer.step with drawn bptt_segments, accumulate_steps, loss_weights, max_grad_norm, sequence_loss: losses and the bucket against CPU autograd over the whole window")
     ap.add_argument("--stateful", action="store_true", help="two chunks through FusedTrainer(stateful=True), the second with a drawn reset, each checked from the state and parameters the device held")
     ap.add_argument("--finetune", action="store_true", help="two steps of FusedTrainer with a drawn number of frozen layers (0 ... all), weight decay and per-layer lr scales: loss and trained gradients against CPU autograd, the update against torch.optim.AdamW, the frozen regions untouched")
+    ap.add_argument("--closed-loop", action="store_true", help="ConvLSTM(feedback=True)(x[, state], free_from=s): the per-step predictions of a drawn stack, grid, number of feedback channels, first fed step, state, storage type, boundary condition and input layout against the CPU model tests/closed_loop_model.py, and bit for bit against the open-loop pass over the input with those predictions substituted")
     ap.add_argument("--self-check", action="store_true", help="with --state / --train-opts / --stateful / --finetune: corrupt the reference after the first passing case and require the comparison to fail")
     ap.add_argument("--guarded", action="store_true", help="every mode: the device side of each case allocates through oracle/guarded_alloc.py in poison mode (guards around every buffer, `empty` payloads 0xFF), its inputs and parameters in arenas of their own; the comparison stays what it is and every guard byte is checked after each case.  With --self-check (any mode): one guard byte is flipped after the first passing case and the check has to fail (the reference is then not corrupted)")
     ap.add_argument("--list", action="store_true", help="print the drawn cases as JSON lines and exit (no GPU, the package is not imported)")
@@ -1008,10 +1038,12 @@ def parse(argv=None):
     ap.add_argument("--force-wave", type=int, default=None, help="with --only: nint_seq.wave for the replayed case instead of the rotation's value")
     ap.add_argument("--force-dtype", choices=["f32", "bf16"], default=None, help="with --only: the storage type of the replayed case instead of the alternation's (is the miss the arithmetic's, or the storage type's?)")
     args = ap.parse_args(argv)
-    modes = [m for m in ("dataset", "cell", "trainer", "state", "train_opts", "stateful", "finetune") if getattr(args, m)]
+    modes = [m for m in ("dataset", "cell", "trainer", "state", "train_opts", "stateful", "finetune", "closed_loop") if getattr(args, m)]
     if len(modes) > 1 and not all(m in OLD_MODES for m in modes):
-        ap.error("one of --state / --train-opts / --stateful / --finetune at a time, and none of the other modes with it")
+        ap.error("one of --state / --train-opts / --stateful / --finetune / --closed-loop at a time, and none of the other modes with it")
     args.mode = modes[0] if modes else "plain"          # (--dataset before --cell before --trainer, as ever)
+    if args.mode == "closed_loop" and (args.big or args.wide):
+        ap.error("--closed-loop draws its own shapes: not with --big / --wide")
     if args.self_check and args.mode not in NEW_MODES and not args.guarded:
         ap.error("--self-check needs --state, --train-opts, --stateful or --finetune (or --guarded)")
     # --guarded --self-check is the guard's own self-check; the reference stays what it is
@@ -1206,9 +1238,56 @@ def run_new(case, d, args, worst, tried):
     print(f"ok   {tag}  worst {w:.2e}", flush=True)
 
 
+def closed_loop_run(case, d, args, worst):
+    """--closed-loop: one case on the device against tests/closed_loop_model.py (f64, the fed value rounded to the storage type)"""
+    tdir = os.path.join(ROOT, "tests")
+    if tdir not in sys.path:
+        sys.path.insert(0, tdir)
+    import closed_loop_model as CLM
+    tag, dtype = case["tag"], case["dtype"]
+    C, out, T, s, L = case["C"], case["out"], case["T"], case["fb_from"], case["L"]
+    params = O.synth_params(C, case["hidden"], case["ks"], L, out_channels=out, seed=case["it"])
+    net = pkg.ConvLSTM(C, case["hidden"], case["ks"], L, out_channels=out, compute_dtype=dtype, lon_cyclic=case["cyclic"],
+                       feedback=True, return_sequence=True)
+    net.load_state_dict(params)
+    net = _net(net)
+    old_fold, engine.XFOLD = engine.XFOLD, case["fold"]
+    try:
+        net._engine(torch.device("cuda", torch.cuda.current_device()))
+    finally:
+        engine.XFOLD = old_fold
+    state = [(d[f"h0.{l}"], d[f"c0.{l}"]) for l in range(L)] if case["with_state"] else None
+    dev_state = None if state is None else [(_dev(h), _dev(c)) for h, c in state]
+    X = _dev(d["X"])
+    with torch.no_grad():
+        pred, seq = net(X, dev_state, free_from=s)
+        pred_o, seq_o = net(X, dev_state)
+        # bit contract: the open-loop pass over the input that holds the predictions of the step before in its last channels
+        X2 = X.clone()
+        if s < T:
+            sv = seq.view(case["B"], T, out, case["H"], case["W"])
+            if s == 0:
+                eng = next(iter(net._engines.values()))
+                with eng.window(case["B"], T, case["H"], case["W"], False, True) as ws:
+                    eng.load_state(ws, eng.state_from_tensors(dev_state))
+                    X2[:, 0, C - out:] = eng.head_forward(ws, net.conv.weight, net.conv.bias, slot=0)
+            X2[:, max(s, 1):, C - out:] = sv[:, max(s, 1) - 1:T - 1]
+        pred2, seq2 = net(X2, dev_state)
+    torch.cuda.synchronize()
+    assert torch.equal(seq, seq2) and torch.equal(pred, pred2), (tag, "closed loop differs from the open loop on the substituted input")
+    if s >= T:
+        assert torch.equal(seq, seq_o), (tag, "nothing fed back, yet not the open-loop pass")
+    p64 = {k: v.double() for k, v in params.items()}
+    kw = dict(h0=[h.double() for h, _ in state], c0=[c.double() for _, c in state]) if state is not None else {}
+    ref = CLM.forward(d["X"].double(), p64, free_from=s, cyclic=case["cyclic"], storage=dtype, **kw)
+    w = compare(tag, dtype, dict(pred=pred.cpu(), seq=seq.cpu()), dict(pred=ref["pred"], seq=ref["seq"]), args.only >= 0)
+    worst[dtype] = max(worst[dtype], w)
+    print(f"ok   {tag}  worst {w:.2e}", flush=True)
+
+
 def main(argv=None):
     args = parse(argv)
-    new = args.mode in NEW_MODES
+    new = args.mode in STREAM_MODES
     if args.list:
         for case in draw_cases(args.seed, args.n, args.mode, args.big, args.wide):
             print(json.dumps(case), flush=True)
@@ -1241,7 +1320,9 @@ def main(argv=None):
         try:
             d = draw_data(rng, case)
             with guarded_case(args, case, tried):
-                if new:
+                if args.mode == "closed_loop":
+                    closed_loop_run(case, d, args, worst)
+                elif new:
                     run_new(case, d, args, worst, tried)
                 else:
                     run_old(case, d, args, worst)

@@ -150,7 +150,7 @@ def main():
         alg = B * T * args.C * H * W
         run("preproc_slab", lambda: sb.fill_slab(eng, ws), None, alg * (4 + es))     # 4 B in + ET out per element
         run("preproc_nchw", lambda: ds.device_batch(idx), None, alg * 8)
-    if not only or only & {"head_skill", "skill_plain", "head_fwd", "head_loss", "head_loss_spec", "head_loss_spec3"}:
+    if not only or only & {"head_skill", "skill_plain", "head_fwd", "head_feedback", "head_loss", "head_loss_spec", "head_loss_spec3"}:
         # evaluation: the head on the last step's images + crop + the f64 skill sums in one pass (nint_head_skill_accum), and the
         # same sums from a prediction in memory (nint_skill_accum), one slot, cos-latitude row weights
         O, oy, ox = args.O, 5, 5
@@ -204,6 +204,15 @@ def main():
         part = 2 * nb                                             # the per-wave partial rows, written and read back
         maps = 2 * pix.numel() * 8 + y.numel() * 4 + part         # pix read + written once per call, the targets
         run("head_fwd", head_fwd, None, B * comp_px * (ly.Chp * es + O * 4))
+        if O <= args.C:
+            # closed loop: the head of one step's images, rounded to ET, into the last O input channels of the next step's block
+            # (nint_head_feedback; plain or folded as the engine lays the input out: --C 6 --O 1 is the folded reference stack)
+            l0, kf = eng.layers[0], (cfgs[0].k if eng.cfgs[0].xfold else 0)
+
+            def head_feedback():
+                assert lib.nint_head_feedback(P(ws.h[-1]), B, B, ly.Ch, ly.Chp, O, P(hw), P(hb), P(ws.xs), B, args.C, l0.Cxp,
+                                              args.C - O, kf, int(eng.lon_cyclic), g, eng.dt, st) == 0
+            run("head_feedback", head_feedback, None, B * comp_px * (ly.Chp + max(kf, 1) * O) * es)
         run("head_skill", head_skill, None, B * Hc * Wc * ly.Chp * es + maps)
         run("skill_plain", skill_plain, None, B * O * Hc * Wc * 4 + maps)
     tot = sum(ms * (T if not n.startswith(("wgrad", "pack", "preproc")) else 1) for n, ms in rows
