@@ -227,6 +227,18 @@ typedef struct nint_feedback {
   int32_t from;         /* first fed step */
 } nint_feedback;
 
+/* ROLL-OUT BACKWARD: what nint_seq_bwd_rollout takes beside the nint_seq and the nint_feedback of the window's
+ * closed-loop forward pass.  (Again a structure of its own: nint_seq and nint_feedback keep their layout and size.) */
+typedef struct nint_feedback_grad {
+  float* dpred;         /* f32 [T*B][O][H][W], image t*B + b.  In: l_t, the direct cotangent of p_t = head(h^{L-1} after step t)
+                         * (zeros where the loss has no term).  Out: g_t = l_t + xi_{t+1} for F-1 <= t <= T-2, xi_u being
+                         * d/dx of step u on the feedback channels; the other images stay.  nint_head_bwd_acc(n0 = B, N = T*B,
+                         * dh = NULL) reduces the slab to the head's dw / db.  4-byte aligned. */
+  void* dx_step;        /* ET compact [B][H][W][Cxp0]: where layer 0's dgrad of a fed step stores its x columns when need_dx = 0
+                         * (one step's block, overwritten step after step; not read with need_dx = 1, may be NULL then).
+                         * 16-byte aligned. */
+} nint_feedback_grad;
+
 /* launch kinds for nint_seq.probe_mask / the probe tags */
 enum { NINT_PROBE_CAL = 0, NINT_PROBE_GATE = 1, NINT_PROBE_POINTWISE = 2, NINT_PROBE_DGRAD = 3, NINT_PROBE_FUSED = 4,
        NINT_PROBE_WGRAD = 5, NINT_PROBE_FOLD = 6,
@@ -236,7 +248,8 @@ enum { NINT_PROBE_CAL = 0, NINT_PROBE_GATE = 1, NINT_PROBE_POINTWISE = 2, NINT_P
        NINT_PROBE_BWD_PW = 9,   /* wave = 4 / 5: the top layer's fused step with the bottom layer's pointwise backward: tag layer = the
                                  * fused layer, t = its time step */
        NINT_PROBE_WRAP = 10,    /* nint_seq.lon_cyclic: a halo wrap / clear launch: tag layer = its number of jobs, t = 0 */
-       NINT_PROBE_FEEDBACK = 11 /* nint_seq_fwd_closed: the feedback launch of step t: tag layer = 0, t = the step */ };
+       NINT_PROBE_FEEDBACK = 11, /* nint_seq_fwd_closed: the feedback launch of step t: tag layer = 0, t = the step */
+       NINT_PROBE_FEEDBACK_BWD = 12 /* nint_seq_bwd_rollout: the feedback backward launch of step u: tag layer = 0, t = u */ };
 
 /* ---- library / device ---------------------------------------------------------------- */
 int nint_version(void);
@@ -361,6 +374,26 @@ int nint_seq_bwd(const nint_seq* s /*host*/, void* stream);
 int nint_seq_fwd_closed(const nint_seq* s /*host*/, const nint_feedback* fb /*host*/, void* stream);
 int nint_seq_bwd_closed(const nint_seq* s /*host*/, const nint_feedback* fb /*host*/, void* stream);
 
+/* BPTT THROUGH THE FED-BACK PREDICTION: the backward pass of a window whose forward pass was
+ * nint_seq_fwd_closed(s, fb) with 1 <= F = fb->from < T.  The rounding of the fed value is straight-through (derivative 1).
+ *   for u = T-1 ... 0:  for l = L-1 ... 0: pointwise backward (l, u), then conv backward-data (l, u), each its own launch
+ *                       (the arithmetic of fuse_bwd = 1 with wave = 0, whatever the two fields say: xi_u exists only after
+ *                       layer 0's dgrad of step u and the top layer's pointwise backward of step u-1 needs it);
+ *                       layer 0's dgrad stores its x columns for every u >= F (need_dx: for every u, into dx block u);
+ *                       F <= u <= T-1: nint_head_feedback_bwd -- dpred images of step u-1 += xi_u, dh_seq block u-1 = W^T g_{u-1}
+ *   then the weight / bias gradients as in nint_seq_bwd (layer 0's x source is xs, which holds the fed values).
+ * dh_seq is REQUIRED: on entry block t holds W^T l_t for t < F-1 and t = T-1 (zeros where the loss has no term: the caller
+ * clears or writes them, nint_head_bwd_acc with dw = NULL does); blocks F-1 ... T-2 are overwritten and need no initialisation.
+ * dx (need_dx) receives the chain's d/dx of every step, fed channels of fed steps included: those values are xi, not a gradient of
+ * the caller's x (which the forward pass overwrote there) -- the caller zeroes them.  accumulate: as in nint_seq_bwd.
+ * fb->O == 0 or fb->from >= T: nothing was fed back -- exactly nint_seq_bwd(s), rg is not read.
+ * NINT_E_ARG before any launch (fed windows): fb->from == 0, train_from > 0, bwd_parts != 0, a NULL rg, rg->dpred or dh_seq, a
+ * NULL rg->dx_step with need_dx = 0, and everything nint_seq_bwd and nint_seq_fwd_closed refuse.  NINT_E_ALIGN: rg->dpred not
+ * 4-byte, rg->dx_step / dx not 16-byte aligned.  NINT_E_SHAPE before anything is enqueued: a head nint_head_feedback_bwd
+ * does not hold.  nint_seq_bwd_closed keeps refusing every fed window. */
+int nint_seq_bwd_rollout(const nint_seq* s /*host*/, const nint_feedback* fb /*host*/, const nint_feedback_grad* rg /*host*/,
+                         void* stream);
+
 /* The launch plan of a pass, for tests and tools (host only: nothing is enqueued, no pointer is dereferenced).  Both drivers
  * first PLAN a pass into an ordered list of launches and then enqueue that list; this entry runs the same argument checks and
  * the same planner as nint_seq_fwd (bwd = 0) / nint_seq_bwd (bwd = 1: the BPTT chain, without the weight-gradient
@@ -388,6 +421,9 @@ int nint_debug_seq_plan(const nint_seq* s /*host*/, int bwd, nint_launch_rec* ou
  * `index` counts the feedback launches in between, as it counts the halo wraps of cyclic longitude. */
 int nint_debug_seq_plan_closed(const nint_seq* s /*host*/, const nint_feedback* fb /*host*/, int bwd, nint_launch_rec* out /*host*/,
                                int cap);
+/* ... of nint_seq_bwd_rollout (the BPTT chain; the nint_feedback_grad pointers are made up inside: the plan reads none).  `index`
+ * counts the feedback backward launches in between. */
+int nint_debug_seq_plan_rollout(const nint_seq* s /*host*/, const nint_feedback* fb /*host*/, nint_launch_rec* out /*host*/, int cap);
 /* The merged-grid rule alone, for tests (host arithmetic only): the NINT_K_* kernel that would carry n independent launches of
  * the conv_igemm bodies shapes[5 * i .. 5 * i + 5) = (epi, wn, wk, ntw, mt) as ONE grid, with_pw != 0: together with one
  * pointwise backward pass -- or NINT_E_SHAPE where no merged kernel holds them all (also n outside [1, 4], or a tuple that is
@@ -479,6 +515,23 @@ int nint_head_fwd_seq(const void* h_slab, int B, int T, int Ch, int Chp, int O, 
 int nint_head_feedback(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w, const float* b,
                        void* xs_slab, int x_n0, int Cx, int Cxp, int c0, int xfold_k, int lon_cyclic, const nint_geom* g,
                        int dtype, void* stream);
+/* The adjoint of nint_head_feedback (nint_seq_bwd_rollout), by itself.  dx: ET compact [..][H][W][Cxp], the
+ * gradient of the input slab (plain or folded) of a fed step, images [dx_n0, dx_n0 + N); dpred: f32 [..][O][H][W], images
+ * [p_n0, p_n0 + N), the cotangent of the head outputs that were fed; dh: ET compact [..][H][W][Chp], images [dh_n0, dh_n0 + N).
+ * One thread per pixel, a fixed sequence:
+ *     xi[o]  = dx[pixel][c0 + o]  (plain)  |  sum over kx = 0 .. k-1, in that order from 0.f, of
+ *              dx[pixel x - kx + k/2][kx*Cx + c0 + o], terms outside the row dropped or taken mod W with lon_cyclic (folded:
+ *              the arithmetic of nint_unfold_dx[_cyclic])
+ *     g[o]   = dpred[o] + xi[o]  in f32, stored back into dpred by the one thread that owns the element
+ *     dh[c]  = sum_o w[o][c] * g[o]  with the staged body of nint_head_bwd's dh pass, rounded to ET; the whole Chp record is stored
+ * so dpred and dh equal nint_unpack_compact / nint_unfold_dx[_cyclic] of the fed channels -> f32 add -> nint_head_bwd(dh only)
+ * bit for bit.  No store outside those dpred images and dh images; nothing else of dx is read than the fed channels.
+ * Shapes: exactly nint_head_feedback's (NINT_E_SHAPE beyond).  NINT_E_ARG / NINT_E_ALIGN before any launch: its checks on
+ * (N, O, Ch, Chp, Cx, Cxp, c0, xfold_k, lon_cyclic, g, dtype), a NULL dx / dpred / dh / w, a negative image index; dx or dh
+ * not 16-byte, dpred not 4-byte aligned. */
+int nint_head_feedback_bwd(const void* dx, int dx_n0, float* dpred, int p_n0, void* dh, int dh_n0, int N, int Ch, int Chp, int O,
+                           const float* w, int Cx, int Cxp, int c0, int xfold_k, int lon_cyclic, const nint_geom* g, int dtype,
+                           void* stream);
 /* dseq (B, T*O, H, W) and dpred_last (B, O, H, W: the cotangent of pred = head(h_{T-1}), added to step T-1 inside the
  * kernels); either may be NULL, not both.  dh_seq: compact ET [T*B][H][W][Chp], image t*B+b, padding channels zero
  * (nint_seq.dh_seq; may be NULL: not written); dw (O,Ch), db (O): summed over all T*B images in a fixed order (overwritten;

@@ -56,6 +56,12 @@ class NintFeedback(C.Structure):
     _fields_ = [("w", vp), ("b", vp), ("O", C.c_int32), ("from_step", C.c_int32)]
 
 
+class NintFeedbackGrad(C.Structure):
+    """nint_feedback_grad: what the roll-out backward (nint_seq_bwd_rollout) takes beside them: the f32 slab of the per-step
+    head cotangents (T*B, O, H, W), in l_t and out g_t, and a one-step ET d/dx scratch for need_dx = 0"""
+    _fields_ = [("dpred", vp), ("dx_step", vp)]
+
+
 class NintLaunchRec(C.Structure):
     """nint_launch_rec: one conv / pointwise problem of a planned pass (nint_debug_seq_plan)"""
     _fields_ = [(n, C.c_int32) for n in ("index", "bwd", "op", "layer", "t", "kernel", "dtype", "epi", "wn", "wk", "ntw", "mt",
@@ -98,6 +104,7 @@ _I, _SZ, _F, _D = C.c_int, C.c_size_t, C.c_float, C.c_double
 _PG, _PL, _PS, _PLS = C.POINTER(NintGeom), C.POINTER(NintLayer), C.POINTER(NintSeq), C.POINTER(NintLossSpec)
 _POG = C.POINTER(NintOptGroup)
 _PFB = C.POINTER(NintFeedback)
+_PFG = C.POINTER(NintFeedbackGrad)
 SIGNATURES = {
     "nint_version": (_I, []),
     "nint_error_string": (C.c_char_p, [_I]),
@@ -133,10 +140,13 @@ SIGNATURES = {
     "nint_seq_fwd_closed": (_I, [_PS, _PFB, vp]),
     "nint_seq_bwd_closed": (_I, [_PS, _PFB, vp]),
     "nint_debug_seq_plan_closed": (_I, [_PS, _PFB, _I, C.POINTER(NintLaunchRec), _I]),
+    "nint_seq_bwd_rollout": (_I, [_PS, _PFB, _PFG, vp]),
+    "nint_debug_seq_plan_rollout": (_I, [_PS, _PFB, C.POINTER(NintLaunchRec), _I]),
     "nint_debug_multi_carrier": (_I, [C.POINTER(C.c_int32), _I, _I]),
     "nint_debug_wgrad_plan": (_I, [_PL, _PG, _I, _I, _I, _I, C.POINTER(NintWgradPlanRec)]),
     "nint_head_fwd": (_I, [vp, _I, _I, _I, _I, _I, vp, vp, vp, _PG, _I, vp]),
     "nint_head_feedback": (_I, [vp, _I, _I, _I, _I, _I, vp, vp, vp, _I, _I, _I, _I, _I, _I, _PG, _I, vp]),
+    "nint_head_feedback_bwd": (_I, [vp, _I, vp, _I, vp, _I, _I, _I, _I, _I, vp, _I, _I, _I, _I, _I, _PG, _I, vp]),
     "nint_head_bwd": (_I, [vp, _I, _I, _I, _I, _I, vp, vp, vp, vp, vp, _PG, _I, vp, _SZ, vp]),
     "nint_head_bwd_acc": (_I, [vp, _I, _I, _I, _I, _I, vp, vp, vp, vp, vp, _I, _PG, _I, vp, _SZ, vp]),
     "nint_head_fwd_seq": (_I, [vp, _I, _I, _I, _I, _I, vp, vp, vp, _PG, _I, vp]),

@@ -587,10 +587,13 @@ __global__ __launch_bounds__(256) void head_feedback_kernel(const void* __restri
   }
 }
 
-int nint_internal_feedback_plan(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w, const float* b,
-                                void* xs_slab, int x_n0, int Cx, int Cxp, int c0, int xfold_k, int lon_cyclic, const nint_geom* g,
-                                int dtype, FbPlan* plan) {
-  if (!h_slab || !w || !xs_slab || !g || !plan || N <= 0 || O <= 0 || Ch <= 0 || Cx <= 0 || n0 < 0 || x_n0 < 0) return NINT_E_ARG;
+// what nint_head_feedback and its adjoint check of the numbers they share, in this order: NINT_E_ARG, then (aligned: the caller's
+// pointers) NINT_E_ALIGN, then NINT_E_SHAPE -- the staged head with a row of predictions beside the weights, for both.  (The
+// W * O term is the FORWARD kernel's LDS; the backward launch stages the weights alone and takes the rule only so that it
+// holds exactly the forward's shapes: its own LDS is FbBwdPlan.lds.)
+static int feedback_check(int N, int Ch, int Chp, int O, int Cx, int Cxp, int c0, int xfold_k, int lon_cyclic, const nint_geom* g,
+                          int dtype, bool aligned) {
+  if (!g || N <= 0 || O <= 0 || Ch <= 0 || Cx <= 0) return NINT_E_ARG;
   if (dtype != NINT_BF16 && dtype != NINT_F32) return NINT_E_ARG;
   const int es = dtype == NINT_BF16 ? 2 : 4;
   if (g->H <= 0 || g->W <= 0 || g->P < 0 || g->Hh < g->H + 2 * g->P || g->Wh < g->W + 2 * g->P) return NINT_E_ARG;
@@ -601,10 +604,21 @@ int nint_internal_feedback_plan(const void* h_slab, int n0, int N, int Ch, int C
   if (Cxp < kf * Cx || (Cxp * es) % 16 != 0) return NINT_E_ARG;
   if (lon_cyclic != 0 && lon_cyclic != 1) return NINT_E_ARG;
   if (lon_cyclic && (g->W < g->P || g->W < kf / 2)) return NINT_E_ARG;
-  if (((((uintptr_t)h_slab) | ((uintptr_t)xs_slab)) & 15) != 0) return NINT_E_ALIGN;
+  if (!aligned) return NINT_E_ALIGN;
   if (!head_staged_holds(Chp, O)) return NINT_E_SHAPE;
+  if (((size_t)O * head_chv(Chp) + (size_t)g->W * O) * sizeof(float) > 160 * 1024) return NINT_E_SHAPE;
+  return NINT_OK;
+}
+
+int nint_internal_feedback_plan(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w, const float* b,
+                                void* xs_slab, int x_n0, int Cx, int Cxp, int c0, int xfold_k, int lon_cyclic, const nint_geom* g,
+                                int dtype, FbPlan* plan) {
+  if (!h_slab || !w || !xs_slab || !plan || n0 < 0 || x_n0 < 0) return NINT_E_ARG;
+  const int rc = feedback_check(N, Ch, Chp, O, Cx, Cxp, c0, xfold_k, lon_cyclic, g, dtype,
+                                ((((uintptr_t)h_slab) | ((uintptr_t)xs_slab)) & 15) == 0);
+  if (rc != NINT_OK) return rc;
+  const int es = dtype == NINT_BF16 ? 2 : 4, kf = xfold_k > 1 ? xfold_k : 1;
   const size_t lds = ((size_t)O * head_chv(Chp) + (size_t)g->W * O) * sizeof(float);
-  if (lds > 160 * 1024) return NINT_E_SHAPE;
   const size_t halo_px = (size_t)g->Hh * g->Wh;
   FbPlan p = {};
   p.h = (const char*)h_slab + (size_t)n0 * halo_px * Chp * es; p.w = w; p.b = b;
@@ -635,6 +649,87 @@ extern "C" int nint_head_feedback(const void* h_slab, int n0, int N, int Ch, int
   FbPlan p;
   const int rc = nint_internal_feedback_plan(h_slab, n0, N, Ch, Chp, O, w, b, xs_slab, x_n0, Cx, Cxp, c0, xfold_k, lon_cyclic, g, dtype, &p);
   return rc != NINT_OK ? rc : nint_internal_feedback_enqueue(&p, stream);
+}
+
+// ------------------------------------------------------------------------------ feedback, backward (roll-out training)
+// nint_head_feedback_bwd (nint.h): the adjoint of the launch above for the N images of one fed step u.  It is
+// nint_head_bwd's dh pass -- head_bwd_dh_body, one thread per pixel, the weights staged once per workgroup, the Chp record
+// stored in whole vectors -- over a cotangent that is formed on the way: DpFed hands the body g = dpred + xi and stores it back,
+// each element by the one thread that reads it.  xi, the d/dx of step u on the feedback channels, comes out of the compact
+// dx block by element loads: the fed span starts at any channel c0 (37 of 40: across a 16-byte group), and every 64-byte
+// line it touches is fetched once per pixel either way.  Plain slab: the pixel's own channel, as nint_unpack_compact reads it;
+// folded slab: the k terms of nint_unfold_dx[_cyclic] in its order, from 0.f.
+template <int DT>
+struct DpFed {
+  const void* __restrict__ dx; float* dp; int O, W, Cx, Cxp, c0, kf, cyc; size_t HW;
+  __device__ __forceinline__ float operator()(size_t n, int o, size_t yx) const {
+    const int x = (int)(yx % (size_t)W);
+    const size_t row = n * HW + yx - x;                        // first pixel of the row in the compact block
+    float xi;
+    if (kf == 1) xi = load_elem<DT>(dx, (row + x) * Cxp + c0 + o);
+    else {
+      xi = 0.f;
+      for (int kx = 0; kx < kf; ++kx) {
+        int xs = x - kx + kf / 2;
+        if (cyc) xs = xs < 0 ? xs + W : (xs >= W ? xs - W : xs);
+        if (xs >= 0 && xs < W) xi += load_elem<DT>(dx, (row + xs) * Cxp + kx * Cx + c0 + o);
+      }
+    }
+    float* p = dp + (n * O + o) * HW + yx;
+    const float g = *p + xi;
+    *p = g;
+    return g;
+  }
+};
+
+template <int DT, int CHV>
+__global__ __launch_bounds__(256) void head_feedback_bwd_kernel(const void* __restrict__ dx, float* dpred, const float* __restrict__ w,
+                                                                void* __restrict__ dh, FbBwdPlan a) {
+  extern __shared__ __attribute__((aligned(16))) char smem_fbb[];
+  const DpFed<DT> dp{dx, dpred, a.O, a.W, a.Cx, a.Cxp, a.c0, a.kf, a.cyc, (size_t)a.H * a.W};
+  head_bwd_dh_body<DT, CHV>((float*)smem_fbb, w, dp, dh, a.N, a.Ch, a.Chp, a.O, a.H, a.W);
+}
+
+int nint_internal_feedback_bwd_plan(const void* dx, int dx_n0, float* dpred, int p_n0, void* dh, int dh_n0, int N, int Ch, int Chp,
+                                    int O, const float* w, int Cx, int Cxp, int c0, int xfold_k, int lon_cyclic, const nint_geom* g,
+                                    int dtype, FbBwdPlan* plan) {
+  if (!dx || !dpred || !dh || !w || !plan || dx_n0 < 0 || p_n0 < 0 || dh_n0 < 0) return NINT_E_ARG;
+  const int rc = feedback_check(N, Ch, Chp, O, Cx, Cxp, c0, xfold_k, lon_cyclic, g, dtype,
+                                ((((uintptr_t)dx) | ((uintptr_t)dh)) & 15) == 0 && (((uintptr_t)dpred) & 3) == 0);
+  if (rc != NINT_OK) return rc;
+  const size_t es = dtype == NINT_BF16 ? 2 : 4, comp_px = (size_t)g->H * g->W;
+  FbBwdPlan p = {};
+  p.dx = (const char*)dx + (size_t)dx_n0 * comp_px * Cxp * es; p.dpred = dpred + (size_t)p_n0 * O * comp_px;
+  p.dh = (char*)dh + (size_t)dh_n0 * comp_px * Chp * es; p.w = w;
+  p.N = N; p.Ch = Ch; p.Chp = Chp; p.O = O; p.Cx = Cx; p.Cxp = Cxp; p.c0 = c0; p.kf = xfold_k > 1 ? xfold_k : 1; p.cyc = lon_cyclic;
+  p.dtype = dtype; p.H = g->H; p.W = g->W;
+  p.lds = (size_t)O * head_chv(Chp) * sizeof(float);           // the staged weights [O][CHV], as in nint_head_bwd's dh pass
+  *plan = p;
+  return NINT_OK;
+}
+
+int nint_internal_feedback_bwd_enqueue(const FbBwdPlan* p, void* stream) {
+  const size_t npix = (size_t)p->N * p->H * p->W;
+  const int rc = nint_by_dtype(p->dtype, [&](auto dt) -> int {
+    return head_by_chv(p->Chp, [&](auto chv) -> int {
+      auto kern = head_feedback_bwd_kernel<decltype(dt)::value, decltype(chv)::value>;
+      if (p->lds > 64 * 1024) NINT_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->lds));
+      hipLaunchKernelGGL(kern, dim3((unsigned)((npix + 255) / 256)), dim3(256), p->lds, (hipStream_t)stream, p->dx, p->dpred, p->w, p->dh, *p);
+      return NINT_OK;
+    });
+  });
+  if (rc != NINT_OK) return rc;
+  NINT_LAUNCH_CHECK();
+  return NINT_OK;
+}
+
+extern "C" int nint_head_feedback_bwd(const void* dx, int dx_n0, float* dpred, int p_n0, void* dh, int dh_n0, int N, int Ch, int Chp,
+                                      int O, const float* w, int Cx, int Cxp, int c0, int xfold_k, int lon_cyclic, const nint_geom* g,
+                                      int dtype, void* stream) {
+  FbBwdPlan p;
+  const int rc = nint_internal_feedback_bwd_plan(dx, dx_n0, dpred, p_n0, dh, dh_n0, N, Ch, Chp, O, w, Cx, Cxp, c0, xfold_k, lon_cyclic,
+                                                 g, dtype, &p);
+  return rc != NINT_OK ? rc : nint_internal_feedback_bwd_enqueue(&p, stream);
 }
 
 // SEQ: d loss / d (head output) comes from the sequence tensors (DpSeq: dpred = dseq, dlast, Bs = B, T) instead of dpred alone

@@ -374,6 +374,17 @@ int nint_internal_feedback_plan(const void* h_slab, int n0, int N, int Ch, int C
                                 void* xs_slab, int x_n0, int Cx, int Cxp, int c0, int xfold_k, int lon_cyclic, const nint_geom* g,
                                 int dtype, FbPlan* plan);
 int nint_internal_feedback_enqueue(const FbPlan* plan, void* stream);
+// ... and its adjoint, the feedback step of the roll-out backward (nint_head_feedback_bwd's arguments)
+struct FbBwdPlan {
+  const void* dx; float* dpred; void* dh; const float* w;        // dx, dpred, dh: the FIRST image read / written
+  int N, Ch, Chp, O, Cx, Cxp, c0, kf, cyc, dtype;                // kf: 1 = plain slab, k = folded
+  int H, W;
+  size_t lds;
+};
+int nint_internal_feedback_bwd_plan(const void* dx, int dx_n0, float* dpred, int p_n0, void* dh, int dh_n0, int N, int Ch, int Chp,
+                                    int O, const float* w, int Cx, int Cxp, int c0, int xfold_k, int lon_cyclic, const nint_geom* g,
+                                    int dtype, FbBwdPlan* plan);
+int nint_internal_feedback_bwd_enqueue(const FbBwdPlan* plan, void* stream);
 #define NINT_MULTI_MAX 4  // problems per merged grid (the kernels of NINT_MULTI_KERNELS, csrc/conv_igemm.hip)
 struct CellFwdJob {      // one gate launch (nint_cell_fwd's arguments)
   const nint_layer* ly; const void* x_slab; const void* h_prev; const float* c_prev; void* h_out; float* c_out; void* gates_out;

@@ -151,16 +151,17 @@ static int seq_check(const nint_seq* s, const nint_feedback* fb) {
 
 // A pass is first PLANNED into an ordered list of steps -- host arithmetic only: nothing is enqueued, no stream is touched, no
 // buffer is read -- and then the list is enqueued (run_steps).  nint_debug_seq_plan shows the same list to tests and tools.
-enum { STEP_CONV, STEP_MULTI, STEP_PW, STEP_GATE, STEP_WGRAD, STEP_FOLD, STEP_WRAP, STEP_FEEDBACK };
+enum { STEP_CONV, STEP_MULTI, STEP_PW, STEP_GATE, STEP_WGRAD, STEP_FOLD, STEP_WRAP, STEP_FEEDBACK, STEP_FEEDBACK_BWD };
 struct SeqProb { int op, layer, t; };              // one conv / pointwise problem (NINT_OP_*)
 struct GateCall { CellFwdJob job; nint_layer ly; int carrier; };
 struct SeqStep {
   int kind;        // a planned conv launch | a merged grid | a pointwise backward | a direct nint_cell_fwd call (stencil / dense-K: no planned form)
                    // | one layer's weight-gradient reduction | the fold of a pass's reductions | a halo wrap / clear (cyclic longitude)
                    // | the feedback launch of a closed-loop step (tag_t = the step; no problems, n = 0)
+                   // | its adjoint in the roll-out backward (tag_t = the fed step u; no problems, n = 0)
   int probe, tag_layer, tag_t;       // the NINT_PROBE_* kind and tag it is bracketed with
   int n; SeqProb prob[NINT_MULTI_MAX + 1];         // its problems, in grid order (a reduction / the fold: none, n = 0)
-  union { ConvPlan conv; MultiPlan multi; PwArgs pw; GateCall gate; WgJobPlan wg; WgFoldPlan fold; WrapTable wrap; FbPlan fb; };
+  union { ConvPlan conv; MultiPlan multi; PwArgs pw; GateCall gate; WgJobPlan wg; WgFoldPlan fold; WrapTable wrap; FbPlan fb; FbBwdPlan fbb; };
 };
 typedef std::vector<SeqStep> Steps;
 
@@ -201,6 +202,7 @@ static int run_steps(const nint_seq* s, const Steps& steps, Probe& probe, void* 
       case STEP_FOLD: rc = nint_internal_wgrad_fold_enqueue(&st.fold, stream); break;
       case STEP_WRAP: rc = nint_internal_wrap_enqueue(&st.wrap, stream); break;
       case STEP_FEEDBACK: rc = nint_internal_feedback_enqueue(&st.fb, stream); break;
+      case STEP_FEEDBACK_BWD: rc = nint_internal_feedback_bwd_enqueue(&st.fbb, stream); break;
     }
     probe.stamp(st.probe, st.tag_layer, st.tag_t, 1);
     if (rc != NINT_OK) return rc;
@@ -348,8 +350,14 @@ struct BwdPlanner {
   bool has_d, has_p;
   ConvPlan held_d; int held_u;       // the bottom layer's dgrad of time held_u
   PwArgs held_p; int held_t;         // the bottom layer's pointwise backward of time held_t
+  // ---- ROLL-OUT (nint_seq_bwd_rollout; rg == nullptr: none of it): steps u >= F were fed.  Layer 0's dgrad of a
+  // fed step stores its x columns (without need_dx: into the one-step scratch) and the feedback backward launch follows it.
+  // The caller hands in a nint_seq with fuse_bwd = 1 and wave = 0: every launch by itself, time-major.
+  const nint_feedback* fb; const nint_feedback_grad* rg; int F;
 
-  BwdPlanner(const nint_seq* s_, int n_cu_, Steps& out_) : s(s_), n_cu(n_cu_), out(out_), L(s_->L), T(s_->T), B(s_->B), has_d(false), has_p(false), held_u(0), held_t(0) {
+  BwdPlanner(const nint_seq* s_, int n_cu_, Steps& out_, const nint_feedback* fb_ = nullptr, const nint_feedback_grad* rg_ = nullptr)
+      : s(s_), n_cu(n_cu_), out(out_), L(s_->L), T(s_->T), B(s_->B), has_d(false), has_p(false), held_u(0), held_t(0), fb(fb_), rg(rg_),
+        F(rg_ ? fb_->from : s_->T) {
     es = esize(s->dtype); halo_px = (size_t)s->g.Hh * s->g.Wh; comp_px = (size_t)s->g.H * s->g.W;
     const bool explicit_mask = (s->fuse_bwd & 0x40000000) != 0;
     for (int l = L - 1; l >= 0; --l) {
@@ -414,7 +422,8 @@ struct BwdPlanner {
   // layer l's conv backward-data of time u (pw: with a pointwise backward in its epilogue)
   int dgrad(int l, int u, const DgradPw* pw, ConvPlan* pl) {
     const nint_layer* ly = &s->layer[l];
-    void* dx_dst = (l > 0) ? s->dh[l - 1] : (s->need_dx ? (void*)((char*)s->dx + (size_t)u * B * comp_px * ly->Cxp * es) : nullptr);
+    void* dx_dst = (l > 0) ? s->dh[l - 1] : (s->need_dx ? (void*)((char*)s->dx + (size_t)u * B * comp_px * ly->Cxp * es)
+                                                        : (rg && u >= F ? rg->dx_step : nullptr));
     // the x columns go to the layer below's dh or this time step's dx slab: STORED where nothing else is there (dx; a dh flagged zero at the
     // first step; a FUSED layer below, whose dh buffer only ever carries them), else accumulated onto the h columns a classic layer below stored
     const bool ow = l == 0 ? true : (u == T - 1 ? (((s->zero_dstate >> (2 * (l - 1) + 1)) & 1) != 0) : (fused[l - 1] || (merge_d && l == 1)));
@@ -495,8 +504,18 @@ struct BwdPlanner {
     return NINT_OK;
   }
 
+  // behind layer 0's dgrad of a fed step u: dpred images of step u-1 += xi_u, dh_seq block u-1 = W^T g_{u-1}
+  int feedback_bwd(int u) {
+    const nint_layer* l0 = &s->layer[0];
+    const nint_layer* top = &s->layer[L - 1];
+    SeqStep& st = push(out, STEP_FEEDBACK_BWD, NINT_PROBE_FEEDBACK_BWD, 0, u);
+    return nint_internal_feedback_bwd_plan(s->need_dx ? s->dx : rg->dx_step, s->need_dx ? u * (int)B : 0, rg->dpred, (u - 1) * (int)B,
+                                           (void*)s->dh_seq, (u - 1) * (int)B, (int)B, top->Ch, top->Chp, fb->O, fb->w, l0->Cx, l0->Cxp,
+                                           l0->Cx - fb->O, l0->xfold ? l0->k : 0, s->lon_cyclic, &s->g, s->dtype, &st.fbb);
+  }
+
   int plan() {
-    out.reserve((size_t)(T + L) * L * 2 + L + 1);
+    out.reserve((size_t)(T + L) * L * 2 + L + 1 + (size_t)(T - F));
     for (int so = T - 1; so >= -off[0] && s->bwd_parts != 2; --so) {      // (part 2: the chain ran in the part-1 call)
       for (int l = L - 1; l >= 0; --l) {
         const int u = so + off[l];
@@ -512,6 +531,7 @@ struct BwdPlanner {
           if ((rc = dgrad(l, 0, nullptr, &pl)) == NINT_OK) push_conv(out, pl, NINT_PROBE_DGRAD, NINT_OP_DGRAD, l, 0);
         }
         if (rc != NINT_OK) return rc;
+        if (rg && l == 0 && u >= F && (rc = feedback_bwd(u)) != NINT_OK) return rc;
       }
     }
     flush_p(); flush_d();
@@ -637,6 +657,28 @@ static int plan_chain(const nint_seq* s, const nint_feedback* fb, bool bwd, Step
   return rc2;
 }
 
+// ROLL-OUT BACKWARD (nint_seq_bwd_rollout).  A window in which nothing was fed back is nint_seq_bwd's, record for
+// record.  A fed window is planned by the one BwdPlanner over the caller's nint_seq with fuse_bwd = 1 and wave = 0 -- xi_u
+// exists only after layer 0's dgrad of step u and the top layer's pointwise backward of step u-1 needs it, so no fused step of
+// the top layer and no merged grid -- with the feedback backward launches in between.
+static int plan_rollout(const nint_seq* s, const nint_feedback* fb, const nint_feedback_grad* rg, Steps& steps) {
+  if (!s) return NINT_E_ARG;
+  if (!fb || fb->O == 0 || (fb->from >= s->T && fb->O > 0)) return plan_chain(s, &NO_FB, true, steps);
+  int rc = bwd_check(s, &NO_FB);
+  if (rc == NINT_OK) rc = seq_check(s, fb);
+  if (rc != NINT_OK) return rc;
+  if (fb->from == 0 || s->train_from > 0 || s->bwd_parts != 0 || !rg || !rg->dpred || !s->dh_seq) return NINT_E_ARG;
+  if (!s->need_dx && !rg->dx_step) return NINT_E_ARG;
+  if ((((uintptr_t)rg->dpred) & 3) != 0 || (((uintptr_t)(s->need_dx ? s->dx : rg->dx_step)) & 15) != 0) return NINT_E_ALIGN;
+  nint_seq v = *s;                               // (the plan keeps no pointer into it)
+  v.fuse_bwd = 1; v.wave = 0;
+  return BwdPlanner(&v, nint_internal_n_cu(), steps, fb, rg).plan();
+}
+static int plan_rollout_pass(const nint_seq* s, const nint_feedback* fb, const nint_feedback_grad* rg, Steps& steps) {
+  const int rc = plan_rollout(s, fb, rg, steps);
+  return rc == NINT_OK && s->lon_cyclic ? add_wrap_steps(s, true, steps) : rc;
+}
+
 // ... and, for cyclic longitude only, the wrap launches in between
 static int plan_pass(const nint_seq* s, const nint_feedback* fb, bool bwd, Steps& steps) {
   if (!fb) fb = &NO_FB;
@@ -655,16 +697,35 @@ extern "C" int nint_seq_fwd(const nint_seq* s, void* stream) { return run_pass(s
 extern "C" int nint_seq_bwd(const nint_seq* s, void* stream) { return run_pass(s, nullptr, true, stream); }
 extern "C" int nint_seq_fwd_closed(const nint_seq* s, const nint_feedback* fb, void* stream) { return run_pass(s, fb, false, stream); }
 extern "C" int nint_seq_bwd_closed(const nint_seq* s, const nint_feedback* fb, void* stream) { return run_pass(s, fb, true, stream); }
+extern "C" int nint_seq_bwd_rollout(const nint_seq* s, const nint_feedback* fb, const nint_feedback_grad* rg, void* stream) {
+  Steps steps;
+  const int rc = plan_rollout_pass(s, fb, rg, steps);
+  if (rc != NINT_OK) return rc;
+  Probe probe = make_probe(s, true, stream);
+  return run_steps(s, steps, probe, stream);
+}
 
 // ------------------------------------------------------------------------------ the plan, for tests and tools
 extern "C" int nint_debug_seq_plan(const nint_seq* s, int bwd, nint_launch_rec* out, int cap) {
   return nint_debug_seq_plan_closed(s, nullptr, bwd, out, cap);
 }
 
+static int plan_records(const nint_seq* s, const Steps& steps, int bwd, nint_launch_rec* out, int cap);
 extern "C" int nint_debug_seq_plan_closed(const nint_seq* s, const nint_feedback* fb, int bwd, nint_launch_rec* out, int cap) {
   Steps steps;
   const int rc = plan_pass(s, fb, bwd != 0, steps);
-  if (rc != NINT_OK) return rc;
+  return rc != NINT_OK ? rc : plan_records(s, steps, bwd, out, cap);
+}
+
+extern "C" int nint_debug_seq_plan_rollout(const nint_seq* s, const nint_feedback* fb, nint_launch_rec* out, int cap) {
+  // made-up, aligned, non-NULL: the plan reads no pointer (a NULL dh_seq or dx is still the caller's, and refused)
+  const nint_feedback_grad rg = {(float*)(uintptr_t)64, (void*)(uintptr_t)64};
+  Steps steps;
+  const int rc = plan_rollout_pass(s, fb, &rg, steps);
+  return rc != NINT_OK ? rc : plan_records(s, steps, 1, out, cap);
+}
+
+static int plan_records(const nint_seq* s, const Steps& steps, int bwd, nint_launch_rec* out, int cap) {
   if (cap > 0 && !out) return NINT_E_ARG;
   int n = 0;
   for (size_t i = 0; i < steps.size(); ++i) {

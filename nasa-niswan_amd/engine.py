@@ -11,7 +11,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 
 from . import _lib
-from ._lib import NINT_BF16, NINT_F32, NintFeedback, NintGeom, NintLayer, NintSeq, check, ptr, stream_ptr
+from ._lib import NINT_BF16, NINT_F32, NintFeedback, NintFeedbackGrad, NintGeom, NintLayer, NintSeq, check, ptr, stream_ptr
 
 # 0: the library picks the gate / dgrad pixel-tile height per launch shape; 4 or 8 forces it for every layer of
 # engines built afterwards (nint_layer.tile_rows) -- how the tests run both heights on every shape
@@ -94,6 +94,9 @@ class Workspace:
         # closed loop (nint_feedback): what the last forward pass on this workspace fed back (O = 0: nothing), and the tensors
         # its pointers name
         self.fb, self._fb_keep = NintFeedback(), None
+        # roll-out training: the last forward pass asked for the gradient through what it fed back; the f32 slab
+        # of the per-step head cotangents and the one-step d/dx scratch are allocated when first asked for
+        self.fb_grad, self._rollout_dpred, self._rollout_dx = False, None, None
         self.seq = NintSeq()
         s = self.seq
         s.dtype, s.B, s.T, s.L = eng.dt, B, T, len(eng.cfgs)
@@ -120,6 +123,13 @@ class Workspace:
         if self._dh_seq is None:
             self._dh_seq = torch.empty(self.T * self.B * self.H * self.W * eng.layers[-1].Chp * eng.es, dtype=torch.uint8, device=eng.device)
         return self._dh_seq
+
+    def rollout_dpred(self, eng, O: int) -> torch.Tensor:
+        """f32 (T*B, O, H, W), image t*B + b: the direct cotangent l_t of every step's head output going into the roll-out
+        backward, g_t = l_t + (the gradient that came back through the feedback) coming out (nint_feedback_grad.dpred)"""
+        if self._rollout_dpred is None or self._rollout_dpred.shape[1] != O:
+            self._rollout_dpred = torch.empty(self.T * self.B, O, self.H, self.W, dtype=torch.float32, device=eng.device)
+        return self._rollout_dpred
 
     # byte offsets of slab (t) inside the per-layer stacks
     def h_view(self, eng, l: int, slot: int) -> int:
@@ -482,19 +492,24 @@ class SeqEngine:
 
     # ------------------------------------------------------------------ passes
     def forward(self, ws: Workspace, x: torch.Tensor, h0: Optional[List[torch.Tensor]] = None,
-                c0: Optional[List[torch.Tensor]] = None, feedback=None):
+                c0: Optional[List[torch.Tensor]] = None, feedback=None, feedback_grad: bool = False):
         """x (B,T,C,H,W) f32 on the engine's device, or a dataset.SlabBatch of that shape.  Runs model.py:253-271
         (all layers, all steps).
 
         ``feedback = (w, b, from_step)``: CLOSED LOOP (nint_seq_fwd_closed) -- the head ``w`` (O, Ch_top), ``b`` (O)
         or None, of the top layer's hidden state is rounded to the storage type and written into the last O input channels
         before every step ``t >= from_step``; earlier steps see what ``x`` holds.  The input slab is filled from ``x`` first
-        (tensor or SlabBatch), then the pass writes into it.  from_step = 0 needs a has_init workspace."""
+        (tensor or SlabBatch), then the pass writes into it.  from_step = 0 needs a has_init workspace.
+
+        ``feedback_grad=True`` (with ``feedback``, on a training workspace): the window will be trained THROUGH the fed-back
+        prediction.  It marks the workspace: ``backward(..., rollout=...)`` then runs nint_seq_bwd_rollout.
+        The forward pass is the same one.  Without it a backward pass on a fed window is refused, as ever."""
         B, T, Cc, H, W = x.shape
         assert (B, T, H, W) == (ws.B, ws.T, ws.H, ws.W) and Cc == self.cfgs[0].Cx
         s, fb = ws.seq, ws.fb
         # ws.fb stays as this pass sets it: a backward pass on a fed window is refused by the library (nint_seq_bwd_closed)
         fb.w, fb.b, fb.O, fb.from_step, ws._fb_keep = None, None, 0, 0, None
+        ws.fb_grad = bool(feedback_grad) and feedback is not None
         if feedback is not None:
             w, b, from_step = feedback
             _, _, O, w2, b2 = self._head_args(w, b)
@@ -715,9 +730,40 @@ class SeqEngine:
                                          self.wg_partial.numel() * 4, stream_ptr()), "nint_head_bwd_acc")
         return dw.view(O, Ch, 1, 1), db
 
+    def rollout_cotangents(self, ws: Workspace, w: torch.Tensor, dseq: Optional[torch.Tensor] = None,
+                           dpred: Optional[torch.Tensor] = None, slab_filled: bool = False, dh_written: bool = False) -> torch.Tensor:
+        """What the roll-out backward starts from (nint_seq_bwd_rollout's entry contract), for a workspace whose forward pass
+        was marked ``feedback_grad``: the slab ``ws.rollout_dpred`` filled with l_t -- ``dseq`` (B, T*O, H, W) and / or
+        ``dpred`` (B, O, H, W), which joins step T-1; zeros where there is neither -- and W^T l_t in the blocks of
+        ``ws.dh_seq_slab`` that the chain itself does not write (t < F-1 and t = T-1; nint_head_bwd_acc, dh only).
+        ``slab_filled``: the caller has written l_t into the slab (the fused head / loss passes take it as their dpred);
+        ``dh_written``: ... and every block of dh_seq holds W^T l_t (head_loss_seq_fused).  Returns the slab."""
+        Ch, Chp, O, w2, _ = self._head_args(w, None)
+        B, T, F = ws.B, ws.T, min(int(ws.fb.from_step), ws.T)
+        slab = ws.rollout_dpred(self, O)
+        if not slab_filled:
+            v = slab.view(T, B, O, ws.H, ws.W)
+            if dseq is not None:
+                v.copy_(dseq.detach().reshape(B, T, O, ws.H, ws.W).transpose(0, 1))
+            else:
+                v.zero_()
+            if dpred is not None:
+                v[T - 1] += dpred.detach()
+        if dh_written:
+            return slab
+        dh_seq = ws.dh_seq_slab(self)
+        blk = B * ws.H * ws.W * Chp * self.es
+        for t0, t1 in ((0, max(F - 1, 0)), (T - 1, T)):         # images [t0*B, t1*B) of the slab -> the same blocks of dh_seq
+            if t1 > t0:
+                check(self.lib.nint_head_bwd_acc(ptr(ws.h[-1]), (t0 + 1) * B, (t1 - t0) * B, Ch, Chp, O, ptr(w2), slab[t0 * B:].data_ptr(),
+                                                 dh_seq.data_ptr() + t0 * blk, None, None, 0, C.byref(ws.g), self.dt, None, 0,
+                                                 stream_ptr()), "nint_head_bwd_acc (dh of the unfed steps)")
+        return slab
+
     def backward(self, ws: Workspace, need_dx: bool, zero_state_grads: Sequence[int] = (),
                  dW_out: Optional[Sequence[torch.Tensor]] = None, db_out: Optional[Sequence[torch.Tensor]] = None, parts: int = 0,
-                 seq_grads: bool = False, zero_mask: Optional[int] = None, accumulate: bool = False, train_from: int = 0):
+                 seq_grads: bool = False, zero_mask: Optional[int] = None, accumulate: bool = False, train_from: int = 0,
+                 rollout: Optional[torch.Tensor] = None):
         """BPTT of model.py:253-271.  Precondition: ws.dh[l], ws.dc[l] hold dL/dh_{T-1}, dL/dc_{T-1}
         (layers listed in ``zero_state_grads`` start from zero state gradients instead).  Returns ([dW_l], [db_l], dx or None).
         ``dW_out`` / ``db_out``: f32 contiguous destinations (e.g. views of a flat gradient bucket).
@@ -732,8 +778,18 @@ class SeqEngine:
         gradients: a window runs as segments, last to first, through ONE workspace and sums into one bucket (trainer.py).
         ``train_from`` (nint_seq.train_from): layers below it are frozen -- BPTT stops above them, their ``dW_out`` / ``db_out``
         entries are not touched (they may be None) and their slots of the returned lists hold None.  The workspace must have
-        been acquired with a ``train_from`` no larger.  Not with ``need_dx`` or ``parts``; ``train_from == L``: no library call."""
+        been acquired with a ``train_from`` no larger.  Not with ``need_dx`` or ``parts``; ``train_from == L``: no library call.
+        ``rollout`` (a workspace whose forward pass was marked ``feedback_grad``): the slab that
+        ``rollout_cotangents`` returned.  BPTT then runs through the fed-back prediction (nint_seq_bwd_rollout, ``seq_grads``
+        implied); on return the slab holds g_t, which ``head_backward(images=(B, T*B), write_dh=False)`` reduces to the
+        head's gradients.  The returned dx is zero on the fed channels of the fed steps: the forward pass overwrote them."""
         assert ws.train
+        fed = ws.fb.O > 0 and ws.fb.from_step < ws.T
+        if rollout is not None and not ws.fb_grad:
+            raise ValueError("backward(rollout=...) needs a forward pass with feedback=..., feedback_grad=True on this workspace")
+        if ws.fb_grad and fed and rollout is None:
+            raise ValueError("backward: this window was run with feedback_grad=True: pass rollout=rollout_cotangents(...)")
+        rollout = rollout if fed else None               # (nothing was fed back: the window trains as ever)
         L = len(self.cfgs)
         train_from = int(train_from)
         if not 0 <= train_from <= L:
@@ -778,11 +834,19 @@ class SeqEngine:
             s.dx = dx.data_ptr()
         s.need_dx = int(need_dx)
         s.bwd_parts = int(parts)
-        s.dh_seq = ws.dh_seq_slab(self).data_ptr() if seq_grads else None
+        s.dh_seq = ws.dh_seq_slab(self).data_ptr() if seq_grads or rollout is not None else None
         s.accumulate = int(bool(accumulate))
         s.train_from = train_from
         try:
-            if ws.fb.O > 0:         # the window's forward pass was a closed-loop one: refused unless nothing was fed back
+            if rollout is not None:
+                rg = NintFeedbackGrad()
+                rg.dpred = rollout.data_ptr()
+                if not need_dx:
+                    if ws._rollout_dx is None:
+                        ws._rollout_dx = torch.empty(ws.B * ws.H * ws.W * ws.Cxp0 * self.es, dtype=torch.uint8, device=self.device)
+                    rg.dx_step = ws._rollout_dx.data_ptr()
+                check(self.lib.nint_seq_bwd_rollout(C.byref(s), C.byref(ws.fb), C.byref(rg), stream_ptr()), "nint_seq_bwd_rollout")
+            elif ws.fb.O > 0:       # the window's forward pass was a closed-loop one: refused unless nothing was fed back
                 check(self.lib.nint_seq_bwd_closed(C.byref(s), C.byref(ws.fb), stream_ptr()), "nint_seq_bwd_closed (the backward "
                       "pass of a window in which the prediction was fed back is not defined)")
             elif train_from < L:
@@ -806,6 +870,8 @@ class SeqEngine:
                 check(self.lib.nint_unpack_compact(ptr(dx), ptr(tb), ws.T * ws.B, C0, ws.Cxp0, ws.H, ws.W, self.dt, stream_ptr()),
                       "unpack dx")
             dx_out = tb.view(ws.T, ws.B, C0, ws.H, ws.W).transpose(0, 1).contiguous()
+            if rollout is not None:         # the caller's x never reached those channels
+                dx_out[:, ws.fb.from_step:, C0 - ws.fb.O:] = 0
         return dWs, dbs, dx_out
 
     def state_grads(self, ws: Workspace, l: int):

@@ -116,9 +116,10 @@ class _CallOpts:
     """the non-tensor arguments of _ConvLSTMFn: the device state that comes in (or None), what goes out, the box the outgoing
     device state is handed back in (a Function's outputs are tensors), and the default route's head-backward rule"""
 
-    def __init__(self, state_in=None, return_state=False, seq_always=False, free_from=None):
+    def __init__(self, state_in=None, return_state=False, seq_always=False, free_from=None, feedback_grad=False):
         self.state_in, self.return_state, self.state_out = state_in, return_state, None
         self.free_from = free_from      # closed loop from this step on (ConvLSTM(feedback=True)); None: open loop
+        self.feedback_grad = feedback_grad and free_from is not None    # ... and differentiated through what it feeds back (4.19)
         # The default call (no state in, none out) of a return_sequence module ALWAYS takes the per-step head backward
         # (head_backward_seq + BPTT with seq_grads), also when only `pred` has a cotangent; a call with state does so only
         # when `seq` has one.  Two launch plans and two summation orders of dw_head: kept apart, as they have always been.
@@ -147,12 +148,17 @@ class _ConvLSTMFn(torch.autograd.Function):
         need = ctx.needs_input_grad
         f = train_from_rule(need[3], [any(need[6 + 2 * l:8 + 2 * l]) or (len(st) > 0 and any(need[6 + 2 * L + 2 * l:8 + 2 * L + 2 * l]))
                                       for l in range(L)]) if train else 0
+        # a fed step's input depends on every layer of the step before: the gradient passes through all of them
+        rollout = train and opts.feedback_grad and opts.free_from < T
+        if rollout:
+            f = 0
         ws = eng.acquire(B, T, H, W, train, has_init, f)
         eng.pack_weights(wb[0::2], wb[1::2])
         if opts.state_in is not None:
             eng.load_state(ws, opts.state_in)
         h0, c0 = (list(st[0::2]), list(st[1::2])) if st else (None, None)
-        eng.forward(ws, x, h0, c0, feedback=None if opts.free_from is None else (head_w, head_b, opts.free_from))
+        eng.forward(ws, x, h0, c0, feedback=None if opts.free_from is None else (head_w, head_b, opts.free_from),
+                    feedback_grad=rollout)
         outs = [eng.head_forward(ws, head_w, head_b)]
         if module.return_sequence:
             outs.append(eng.head_forward_seq(ws, head_w, head_b))       # every step in one launch
@@ -167,7 +173,7 @@ class _ConvLSTMFn(torch.autograd.Function):
         ctx.x_needs_grad = ctx.needs_input_grad[3]
         ctx.nwb, ctx.nst = len(wb), len(st)
         ctx.st_needs_grad = any(ctx.needs_input_grad[6 + len(wb):])
-        ctx.train_from = f
+        ctx.train_from, ctx.rollout = f, rollout
         return tuple(outs) if len(outs) > 1 else outs[0]
 
     @staticmethod
@@ -188,13 +194,20 @@ class _ConvLSTMFn(torch.autograd.Function):
         seq_grads = dseq is not None or ctx.seq_always          # (the default route's rule: _CallOpts)
         dh_top = dst[2 * (L - 1)]
         dw_head = db_head = None
-        if seq_grads:
+        slab = None
+        if ctx.rollout:
+            # BPTT through the fed-back prediction: the head's cotangents travel as a slab, which comes back holding what the
+            # feedback added; the head's own gradients are reduced from it afterwards
+            slab, seq_grads = eng.rollout_cotangents(ws, head_w, dseq, dpred), True
+            if dh_top is not None:
+                eng.add_top_dh(ws, dh_top, True)
+        elif seq_grads:
             dw_head, db_head = eng.head_backward_seq(ws, head_w, dseq, dpred)
         elif dpred is not None:
             dw_head, db_head = eng.head_backward(ws, head_w, dpred)
-        if dw_head is None:                     # no head gradient at all: the state's cotangent alone (zeros if there is none)
+        if slab is None and dw_head is None:    # no head gradient at all: the state's cotangent alone (zeros if there is none)
             eng.set_dstate(ws, L - 1, "h", dh_top)
-        elif dh_top is not None:
+        elif slab is None and dh_top is not None:
             eng.add_top_dh(ws, dh_top, seq_grads)
         mask, f = 0, ctx.train_from
         for l in range(f, L):                   # (a frozen layer's returned state feeds nothing that wants a gradient)
@@ -208,7 +221,9 @@ class _ConvLSTMFn(torch.autograd.Function):
                     mask |= 1 << (2 * l + 1)
                 else:
                     eng.set_dstate(ws, l, "h", dh)
-        dWs, dbs, dx = eng.backward(ws, ctx.x_needs_grad, seq_grads=seq_grads, zero_mask=mask, train_from=f)
+        dWs, dbs, dx = eng.backward(ws, ctx.x_needs_grad, seq_grads=seq_grads, zero_mask=mask, train_from=f, rollout=slab)
+        if slab is not None:
+            dw_head, db_head = eng.head_backward(ws, head_w, slab, write_dh=False, images=(ws.B, ws.T * ws.B))
         dstate = []
         if ctx.nst:
             for l in range(L):
@@ -334,7 +349,7 @@ class ConvLSTM(_EngineOwner, nn.Module):
         inference loops, which drive the engine themselves, do before a forward pass"""
         eng.pack_weights([c.conv.weight for c in self.layers], [c.conv.bias for c in self.layers])
 
-    def forward(self, x, state=None, *, return_state=False, free_from=None):
+    def forward(self, x, state=None, *, return_state=False, free_from=None, feedback_grad=False):
         """x: (batch_size, sequence_length, channels, height, width)  (model.py:254).
 
         ``state``: None (zeros, model.py:259-262), a list of ``num_layers`` ``(h, c)`` tensor pairs (B, Ch_l, H, W) -- the
@@ -351,7 +366,13 @@ class ConvLSTM(_EngineOwner, nn.Module):
         ``out_channels`` input channels are replaced, on the device, by the head of the top layer's hidden state after step
         t-1, rounded to the storage type; steps t < s see ``x`` as given (the spin-up).  ``free_from >= T`` feeds nothing
         back; ``free_from = 0`` needs a ``state``.  Forward only: with anything that requires grad under grad mode and
-        ``free_from < T`` the call raises -- back-propagation through the fed-back prediction is not implemented."""
+        ``free_from < T`` the call raises -- unless ``feedback_grad=True``.
+
+        ``feedback_grad=True`` (with ``free_from = s >= 1``): ROLL-OUT TRAINING -- the call is differentiable
+        through the fed-back prediction, the rounding of the fed value taken straight-through.  The forward pass is the same
+        one; the backward pass runs time-major with one extra launch per fed step.  The gradient of ``x`` is zero on the
+        fed channels of the fed steps.  ``free_from = 0`` under grad stays refused (the first fed value comes from the
+        initial state); with ``free_from >= T`` the flag changes nothing."""
         if free_from is not None:                       # every refusal here, before anything is launched (or any device is asked for)
             if not self.feedback:
                 raise ValueError("free_from needs a ConvLSTM built with feedback=True")
@@ -362,7 +383,7 @@ class ConvLSTM(_EngineOwner, nn.Module):
                 raise ValueError(f"ConvLSTM: x must be (B, T, C, H, W), got {tuple(x.shape)}")
             if free_from == 0 and state is None:
                 raise ValueError("free_from=0 feeds step 0 from the head of the initial state: pass a state")
-            if free_from < x.shape[1] and torch.is_grad_enabled() and (
+            if free_from < x.shape[1] and not (feedback_grad and free_from >= 1) and torch.is_grad_enabled() and (
                     x.requires_grad or any(p.requires_grad for p in self.parameters())
                     or (state is not None and not isinstance(state, ConvLSTMState)
                         and any(t.requires_grad for pair in state for t in pair))):
@@ -375,7 +396,7 @@ class ConvLSTM(_EngineOwner, nn.Module):
             wb += [cell.conv.weight, cell.conv.bias]
         st = []
         if state is None and not return_state:          # the default call: nothing to validate, and its own head-backward rule
-            opts = _CallOpts(seq_always=self.return_sequence, free_from=free_from)
+            opts = _CallOpts(seq_always=self.return_sequence, free_from=free_from, feedback_grad=bool(feedback_grad))
         else:
             if return_state not in (False, True, "device"):
                 raise ValueError(f"return_state must be False, True or 'device', got {return_state!r}")
@@ -388,7 +409,8 @@ class ConvLSTM(_EngineOwner, nn.Module):
             elif state is not None:
                 hs, cs = eng._state_tensors(state, (B, H, W))
                 st = _interleave(hs, cs)
-            opts = _CallOpts(state if isinstance(state, ConvLSTMState) else None, return_state, free_from=free_from)
+            opts = _CallOpts(state if isinstance(state, ConvLSTMState) else None, return_state, free_from=free_from,
+                             feedback_grad=bool(feedback_grad))
         out = _ConvLSTMFn.apply(self, torch.is_grad_enabled(), opts, x, self.conv.weight, self.conv.bias, *wb, *st)
         out = list(out) if isinstance(out, tuple) else [out]
         n0 = 2 if self.return_sequence else 1

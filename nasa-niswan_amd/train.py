@@ -7,7 +7,7 @@ stepped once per epoch before validation, checkpoint every 10 epochs); the per-b
 once per epoch.  Added flags: --dtype, --levels, --grid, --synthetic-steps, --pad-mode, --f32-inputs,
 --static-channels, --sequence-loss, --test-skill, --lat-weighted-loss, --loss-weights, --clip-grad-norm,
 --skip-nonfinite-steps, --stateful, --bptt-segments, --accumulate-steps, --loss-mix, --huber-delta, --output-weights,
---spinup-steps.
+--spinup-steps, --rollout-from.
 
 The data path is on the device too: by default every batch is written by ONE launch of the
 fuse / z-score / halo-pad kernel straight into the model's bf16 input slab (dataset.slab_batch);
@@ -139,6 +139,11 @@ def get_arguments(argv=None, MODEL='LSTM-00', SPECIES='bcb', LEARNING_RATE=1.0E-
                              "(inference.rollout_skill) and prints R2 per lead time 0 .. HORIZON-1")
     parser.add_argument("--rollout-spinup", type=int, default=None, metavar="K",
                         help="steps of analysis input before the free run of --test-rollout (default: --sequence-length)")
+    parser.add_argument("--rollout-from", type=int, default=None, metavar="K",
+                        help="with --tracer-input: ROLL-OUT TRAINING -- from step K >= 1 of every training window the model runs on "
+                             "its own prediction (the tracer channels of steps >= K are the head's output of the step before) and "
+                             "the loss is back-propagated through the fed-back prediction (FusedTrainer(rollout_from=K)).  "
+                             "Validation stays teacher-forced.  Not with --stateful, --bptt-segments, --freeze-layers")
     parser.add_argument("--reset-optimizer", action="store_true",
                         help="with --use-checkpoint: load the weights of --restore-from only and start the optimizer afresh "
                              "(the fine-tuning entry point; without it an optimizer state of other param groups is an error)")
@@ -157,6 +162,13 @@ def get_arguments(argv=None, MODEL='LSTM-00', SPECIES='bcb', LEARNING_RATE=1.0E-
         parser.error("--tracer-input and --static-channels both claim the last input channels; they are not combined")
     if args.test_rollout < 0 or (args.test_rollout > 0 and not args.tracer_input):
         parser.error("--test-rollout takes a horizon >= 1 and needs --tracer-input")
+    if args.rollout_from is not None:
+        if not args.tracer_input:
+            parser.error("--rollout-from needs --tracer-input: the model must have feedback channels to run on its own prediction")
+        if args.rollout_from < 1:
+            parser.error("--rollout-from must be >= 1: step 0 has no prediction to be fed")
+        if args.stateful or (args.bptt_segments or 1) > 1 or args.freeze_layers > 0:
+            parser.error("--rollout-from is not combined with --stateful, --bptt-segments or --freeze-layers")
     if args.rollout_spinup is None:
         args.rollout_spinup = args.sequence_length
     if args.test_rollout > 0 and args.rollout_spinup < 1:
@@ -254,7 +266,8 @@ def main(args):
                            sequence_loss=args.sequence_loss, loss_weights=loss_weights,
                            max_grad_norm=args.clip_grad_norm, skip_nonfinite=args.skip_nonfinite_steps, stateful=args.stateful,
                            bptt_segments=args.bptt_segments, accumulate_steps=args.accumulate_steps, loss=build_loss_spec(args),
-                           freeze_layers=args.freeze_layers, weight_decay=args.weight_decay, layer_lr_scale=args.layer_lr_scale)
+                           freeze_layers=args.freeze_layers, weight_decay=args.weight_decay, layer_lr_scale=args.layer_lr_scale,
+                           rollout_from=args.rollout_from)
     if args.stateful:
         # one schedule of world * batch lanes, the same every epoch; each rank takes its own columns and carries its own state
         sched, dropped = stateful_schedule(len(train_dataset), args.sequence_length, world * args.batch_size)

@@ -25,6 +25,10 @@
                                                exchange and the norm run over the trained tail of the bucket, and the optimizer
                                                is AdamW over per-layer groups (nint_adam_flat_groups: ``weight_decay``,
                                                ``layer_lr_scale``).  f = L trains the head alone: no BPTT
+    [rollout_from = s]                      -> ROLL-OUT TRAINING: the closed-loop forward from step s (nint_seq_fwd_closed),
+                                               the same fused head / loss pass with its dpred in the roll-out slab, BPTT through
+                                               the fed-back prediction (nint_seq_bwd_rollout), then the head's gradients from
+                                               the slab (nint_head_bwd_acc over all T*B images)
     [accumulate_steps = k]                  -> k micro-batches add into the bucket (accumulate = 1 from the second on); the
                                                all-reduce and ONE Adam launch with grad_scale = 1/(k world) on the k-th
 
@@ -60,7 +64,22 @@ class FusedTrainer:
                  overlap_allreduce: bool = False, sequence_loss: bool = False, loss_weights=None,
                  max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False, stateful: bool = False,
                  bptt_segments: Optional[int] = None, accumulate_steps: int = 1, loss: Optional[LossSpec] = None,
-                 freeze_layers: int = 0, weight_decay: float = 0.0, layer_lr_scale=None):
+                 freeze_layers: int = 0, weight_decay: float = 0.0, layer_lr_scale=None, rollout_from: Optional[int] = None):
+        # Roll-out training: from step `rollout_from` on the window runs on its own prediction and the loss's gradient flows
+        # back through it.  Checked first: these refusals need no device.
+        if rollout_from is not None:
+            if isinstance(rollout_from, bool) or int(rollout_from) != rollout_from or rollout_from < 1:
+                raise ValueError(f"rollout_from must be a step index >= 1 (the first fed step; step 0 has no prediction to be fed), "
+                                 f"got {rollout_from!r}")
+            if not getattr(model, "feedback", False):
+                raise ValueError("rollout_from needs a ConvLSTM built with feedback=True")
+            for name, on in (("bptt_segments > 1", (bptt_segments or 1) > 1), ("stateful", stateful), ("freeze_layers > 0", freeze_layers),
+                             ("overlap_allreduce", overlap_allreduce)):
+                if on:
+                    raise ValueError(f"rollout_from with {name} is not supported: the roll-out backward runs one whole window from "
+                                     "the zero state, through every layer, in one call")
+            rollout_from = int(rollout_from)
+        self.rollout_from = rollout_from
         dev = next(model.parameters()).device
         if dev.type != "cuda":
             raise _lib.NintError("FusedTrainer needs the model on the MI355X (cuda)")
@@ -259,6 +278,23 @@ class FusedTrainer:
         for v in views:
             v.masked_fill_(bad, 0)
 
+    def _head_pass_rollout(self, eng, ws, yv, B, T, O, H, W, Hc, Wc, wts, spec=None):
+        """_head_pass for a roll-out window: the same fused pass, its d loss / d pred written into the workspace's roll-out slab
+        (zeros where the loss has no term) and W^T of it into the blocks of dh_seq the roll-out backward starts from.  The
+        head's weight gradient waits for the slab to come back from BPTT.  Returns the slab."""
+        m, sq = self.model, self.sequence_loss
+        slab = ws.rollout_dpred(eng, O)
+        sk = {} if spec is None else dict(spec=spec)
+        args = (self.scratch, self.stats, self.halo, Hc, Wc, wts)
+        if sq:
+            fused = eng.head_loss_seq_fused(ws, m.conv.weight, m.conv.bias, yv, slab, *args, **sk)
+        else:
+            slab[:(T - 1) * B].zero_()
+            fused = eng.head_loss_fused(ws, m.conv.weight, m.conv.bias, yv, slab[(T - 1) * B:], *args, **sk)
+        if not fused:       # (a head beyond the fused kernels is beyond the feedback kernel too: the forward pass refuses it first)
+            raise _lib.NintError("rollout_from: the head is beyond the fused head / loss kernels, which write the roll-out slab")
+        return eng.rollout_cotangents(ws, m.conv.weight, slab_filled=True, dh_written=sq)
+
     def _head_pass(self, eng, ws, yv, B, T, O, H, W, Hc, Wc, wts, acc: bool, spec=None):
         """head forward + crop + loss + d loss / d pred + dL/dh + the head's weight gradient on the workspace's last h (every
         h with sequence_loss); `acc`: the head's gradients are added to the bucket (a later micro-batch of a group)"""
@@ -318,15 +354,26 @@ class FusedTrainer:
             m._pack_weights(eng)
             if carried is not None:
                 eng.load_state(ws, carried)          # carried state -> slot 0
-            eng.forward(ws, X)
+            rollout = self.rollout_from is not None and self.rollout_from < T       # (else nothing is fed: the step it was)
+            if rollout:
+                eng.forward(ws, X, feedback=(m.conv.weight, m.conv.bias, self.rollout_from), feedback_grad=True)
+            else:
+                eng.forward(ws, X)
             if carried is not None:
                 eng.save_state(ws, carried)          # slot T -> carried state; BPTT below stops at the chunk start
                 self._drop_nonfinite_lanes(carried)
             mark()
-            self._head_pass(eng, ws, yv, B, T, O, H, W, Hc, Wc, wts, acc, spec)
+            if rollout:
+                slab = self._head_pass_rollout(eng, ws, yv, B, T, O, H, W, Hc, Wc, wts, spec)
+            else:
+                self._head_pass(eng, ws, yv, B, T, O, H, W, Hc, Wc, wts, acc, spec)
             mark()
             bk = dict(zero_state_grads=range(L), dW_out=self._dW, db_out=self._db, seq_grads=sq, accumulate=acc, train_from=f)
-            if last and self.distributed and self.overlap_allreduce and L > 1 and pb is None:
+            if rollout:
+                eng.backward(ws, False, rollout=slab, **bk)
+                eng.head_backward(ws, m.conv.weight, slab, write_dh=False, images=(B, T * B), dw_out=self._dw_head,
+                                  db_out=self._db_head, accumulate=acc)
+            elif last and self.distributed and self.overlap_allreduce and L > 1 and pb is None:
                 # the bucket without layer 0's slice is exchanged under layer 0's weight gradient; _finish exchanges the slice
                 n0 = self.flat.offsets[2]              # layers.0.conv.weight + .bias lead the bucket (module parameter order)
                 eng.backward(ws, False, parts=1, **bk)

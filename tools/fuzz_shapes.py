@@ -99,6 +99,10 @@ OLD_MODES = ("plain", "trainer", "cell", "dataset")
 NEW_MODES = ("state", "train_opts", "stateful", "finetune")       # (a new mode goes LAST: case_rng keys a stream by position)
 # ... and the modes with a stream per case that have a draw and a run of their own, behind them (positions as above)
 STREAM_MODES = NEW_MODES + ("closed_loop",)
+# ... and the modes added since.  STREAM_MODES itself is pinned by the tests of the modes it lists, so a later mode continues the
+# numbering here: ALL_STREAM_MODES is what case_rng indexes, and no earlier mode's position moves.
+LATE_MODES = ("rollout",)
+ALL_STREAM_MODES = STREAM_MODES + LATE_MODES
 LIM = {"f32": 1e-3, "bf16": 3e-2}
 LOSS_LIM = {"f32": 2e-6, "bf16": 2e-2}
 
@@ -244,7 +248,7 @@ def check_head_wgrad(tag, dW, dWo, h_stored, h_oracle, dpred, dpred_oracle=None)
 # ---------------------------------------------------------------------------------------------------- the draw (pure)
 def case_rng(seed: int, mode: str, it: int):
     """the generator of one case of a state / options mode: its own stream, so a case replays without the ones before it"""
-    return np.random.default_rng([int(seed), 1 + STREAM_MODES.index(mode), int(it)])
+    return np.random.default_rng([int(seed), 1 + ALL_STREAM_MODES.index(mode), int(it)])
 
 
 def _halo(rng, H, W):
@@ -258,6 +262,8 @@ def draw_case(rng, it: int, mode: str = "plain", big: bool = False, wide: bool =
     the same generator, in order (``draw_data``); a replay that skips the case draws and drops them."""
     if mode == "closed_loop":
         return draw_closed_loop(rng, it)
+    if mode == "rollout":
+        return draw_rollout(rng, it)
     new = mode in NEW_MODES
     L = int(rng.integers(1, 5))
     hidden = [int(rng.choice([4, 8, 16, 24, 32, 48, 64] if new else [4, 8, 16, 24, 32, 48, 64, 64, 128])) for _ in range(L)]
@@ -396,6 +402,29 @@ def draw_closed_loop(rng, it: int) -> dict:
                     f"closed loop from {fb_from} cyclic={int(cyclic)} fold={int(fold)} state={int(with_state)}")
 
 
+def draw_rollout(rng, it: int) -> dict:
+    """--rollout: a stack, a grid, O feedback channels, the first fed step F >= 1 (1, the middle, T-1, or T: nothing is fed), both
+    storage types, cyclic longitude or zero padding, the thin-input fold allowed or off, and cotangents on the per-step outputs,
+    on the last one, or on both.  Pure."""
+    L = int(rng.integers(1, 4))
+    hidden = [int(rng.choice([4, 8, 16, 24, 32, 64])) for _ in range(L)]
+    ks = [int(rng.choice([1, 3, 3, 5, 5])) for _ in range(L)]
+    C = int(rng.choice([1, 3, 4, 6, 16, 33, 40, 62]))
+    out = min(C, int(rng.choice([1, 1, 2, 3, 20])))
+    B, T = int(rng.integers(1, 4)), int(rng.integers(3, 7))
+    H, W = int(rng.integers(5, 21)), int(rng.integers(9, 41))
+    dtype = "f32" if it % 2 == 0 else "bf16"
+    wave, rows = WAVES[it % 7], TILE_ROWS[it % 4]
+    cyclic, fold = (bool(rng.integers(0, 2)) for _ in range(2))
+    fb_from = [1, T // 2, T - 1, T][int(rng.integers(0, 4))]
+    cot = ["seq", "last", "both"][int(rng.integers(0, 3))]
+    draws = [("X", (B, T, C, H, W)), ("dseq", (B, T * out, H, W)), ("dpred", (B, out, H, W))]
+    return dict(it=it, mode="rollout", L=L, hidden=hidden, ks=ks, C=C, out=out, B=B, T=T, H=H, W=W, dtype=dtype, wave=wave,
+                rows=rows, wide=0, cyclic=cyclic, fold=fold, fb_from=fb_from, cot=cot, draws=draws,
+                tag=f"#{it} C={C} hidden={hidden} k={ks} out={out} B={B} T={T} {H}x{W} {dtype} wave={wave} rows={rows} "
+                    f"roll-out from {fb_from} cyclic={int(cyclic)} fold={int(fold)} cotangents={cot}")
+
+
 def draw_data(rng, case) -> dict:
     """the standard-normal tensors of a case, f32, from the generator that drew it"""
     return {name: torch.from_numpy(rng.standard_normal(sh).astype(np.float32)) for name, sh in case["draws"]}
@@ -406,7 +435,7 @@ def draw_cases(seed: int, n: int, mode: str = "plain", big: bool = False, wide: 
     cases = []
     rng = np.random.default_rng(seed)
     for it in range(n):
-        if mode in STREAM_MODES:
+        if mode in ALL_STREAM_MODES:
             cases.append(draw_case(case_rng(seed, mode, it), it, mode))
         else:
             cases.append(draw_case(rng, it, mode, big, wide))
@@ -1031,6 +1060,7 @@ def parse(argv=None):
     ap.add_argument("--stateful", action="store_true", help="two chunks through FusedTrainer(stateful=True), the second with a drawn reset, each checked from the state and parameters the device held")
     ap.add_argument("--finetune", action="store_true", help="two steps of FusedTrainer with a drawn number of frozen layers (0 ... all), weight decay and per-layer lr scales: loss and trained gradients against CPU autograd, the update against torch.optim.AdamW, the frozen regions untouched")
     ap.add_argument("--closed-loop", action="store_true", help="ConvLSTM(feedback=True)(x[, state], free_from=s): the per-step predictions of a drawn stack, grid, number of feedback channels, first fed step, state, storage type, boundary condition and input layout against the CPU model tests/closed_loop_model.py, and bit for bit against the open-loop pass over the input with those predictions substituted")
+    ap.add_argument("--rollout", action="store_true", help="ConvLSTM(feedback=True)(x, free_from=F, feedback_grad=True): outputs, every parameter gradient and dx of a drawn stack, grid, number of feedback channels, first fed step F >= 1, storage type, boundary condition, input layout and cotangents (per step, last step, both) against the CPU model tests/rollout_model.py under CPU autograd in f64")
     ap.add_argument("--self-check", action="store_true", help="with --state / --train-opts / --stateful / --finetune: corrupt the reference after the first passing case and require the comparison to fail")
     ap.add_argument("--guarded", action="store_true", help="every mode: the device side of each case allocates through oracle/guarded_alloc.py in poison mode (guards around every buffer, `empty` payloads 0xFF), its inputs and parameters in arenas of their own; the comparison stays what it is and every guard byte is checked after each case.  With --self-check (any mode): one guard byte is flipped after the first passing case and the check has to fail (the reference is then not corrupted)")
     ap.add_argument("--list", action="store_true", help="print the drawn cases as JSON lines and exit (no GPU, the package is not imported)")
@@ -1038,12 +1068,12 @@ def parse(argv=None):
     ap.add_argument("--force-wave", type=int, default=None, help="with --only: nint_seq.wave for the replayed case instead of the rotation's value")
     ap.add_argument("--force-dtype", choices=["f32", "bf16"], default=None, help="with --only: the storage type of the replayed case instead of the alternation's (is the miss the arithmetic's, or the storage type's?)")
     args = ap.parse_args(argv)
-    modes = [m for m in ("dataset", "cell", "trainer", "state", "train_opts", "stateful", "finetune", "closed_loop") if getattr(args, m)]
+    modes = [m for m in ("dataset", "cell", "trainer", "state", "train_opts", "stateful", "finetune", "closed_loop", "rollout") if getattr(args, m)]
     if len(modes) > 1 and not all(m in OLD_MODES for m in modes):
-        ap.error("one of --state / --train-opts / --stateful / --finetune / --closed-loop at a time, and none of the other modes with it")
+        ap.error("one of --state / --train-opts / --stateful / --finetune / --closed-loop / --rollout at a time, and none of the other modes with it")
     args.mode = modes[0] if modes else "plain"          # (--dataset before --cell before --trainer, as ever)
-    if args.mode == "closed_loop" and (args.big or args.wide):
-        ap.error("--closed-loop draws its own shapes: not with --big / --wide")
+    if args.mode in ("closed_loop", "rollout") and (args.big or args.wide):
+        ap.error("--closed-loop / --rollout draw their own shapes: not with --big / --wide")
     if args.self_check and args.mode not in NEW_MODES and not args.guarded:
         ap.error("--self-check needs --state, --train-opts, --stateful or --finetune (or --guarded)")
     # --guarded --self-check is the guard's own self-check; the reference stays what it is
@@ -1285,9 +1315,49 @@ def closed_loop_run(case, d, args, worst):
     print(f"ok   {tag}  worst {w:.2e}", flush=True)
 
 
+def rollout_run(case, d, args, worst):
+    """--rollout: one case on the device against tests/rollout_model.py (f64 under CPU autograd, the fed value rounded to f32 and
+    passed straight through)"""
+    tdir = os.path.join(ROOT, "tests")
+    if tdir not in sys.path:
+        sys.path.insert(0, tdir)
+    import rollout_model as RM
+    tag, dtype = case["tag"], case["dtype"]
+    C, out, T, F, L = case["C"], case["out"], case["T"], case["fb_from"], case["L"]
+    params = O.synth_params(C, case["hidden"], case["ks"], L, out_channels=out, seed=case["it"])
+    net = pkg.ConvLSTM(C, case["hidden"], case["ks"], L, out_channels=out, compute_dtype=dtype, lon_cyclic=case["cyclic"],
+                       feedback=True, return_sequence=True)
+    net.load_state_dict(params)
+    net = _net(net)
+    old_fold, engine.XFOLD = engine.XFOLD, case["fold"]
+    try:
+        net._engine(torch.device("cuda", torch.cuda.current_device()))
+    finally:
+        engine.XFOLD = old_fold
+    # (the drawn cotangents get a mean: a bias gradient is the plain sum of what reaches it, and zero-mean cotangents make that
+    # sum a difference of large numbers whose relative error in bf16 measures the draw)
+    dseq = d["dseq"] + 0.5 if case["cot"] in ("seq", "both") else None
+    dpred = d["dpred"] + 0.5 if case["cot"] in ("last", "both") else None
+    X = _dev(d["X"]).requires_grad_(True)
+    pred, seq = net(X, free_from=F, feedback_grad=True)
+    outs, cots = zip(*[(o, _dev(c)) for o, c in ((pred, dpred), (seq, dseq)) if c is not None])
+    torch.autograd.backward(list(outs), list(cots))
+    torch.cuda.synchronize()
+    assert not bool(X.grad[:, F:, C - out:].any()), (tag, "a gradient on the fed channels of a fed step")
+    p64 = {k: v.double() for k, v in params.items()}
+    ref = RM.grads(d["X"].double(), p64, F, case["cyclic"], "f32", dpred, dseq)
+    res = dict(pred=pred.detach().cpu(), seq=seq.detach().cpu(), dx=X.grad.cpu())
+    want = dict(pred=ref["pred"], seq=ref["seq"], dx=ref["dx"])
+    for k, p in net.named_parameters():
+        res["d." + k], want["d." + k] = p.grad.cpu(), ref["params"][k]
+    w = compare(tag, dtype, res, want, args.only >= 0)
+    worst[dtype] = max(worst[dtype], w)
+    print(f"ok   {tag}  worst {w:.2e}", flush=True)
+
+
 def main(argv=None):
     args = parse(argv)
-    new = args.mode in STREAM_MODES
+    new = args.mode in ALL_STREAM_MODES
     if args.list:
         for case in draw_cases(args.seed, args.n, args.mode, args.big, args.wide):
             print(json.dumps(case), flush=True)
@@ -1322,6 +1392,8 @@ def main(argv=None):
             with guarded_case(args, case, tried):
                 if args.mode == "closed_loop":
                     closed_loop_run(case, d, args, worst)
+                elif args.mode == "rollout":
+                    rollout_run(case, d, args, worst)
                 elif new:
                     run_new(case, d, args, worst, tried)
                 else:

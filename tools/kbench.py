@@ -150,7 +150,7 @@ def main():
         alg = B * T * args.C * H * W
         run("preproc_slab", lambda: sb.fill_slab(eng, ws), None, alg * (4 + es))     # 4 B in + ET out per element
         run("preproc_nchw", lambda: ds.device_batch(idx), None, alg * 8)
-    if not only or only & {"head_skill", "skill_plain", "head_fwd", "head_feedback", "head_loss", "head_loss_spec", "head_loss_spec3"}:
+    if not only or only & {"head_skill", "skill_plain", "head_fwd", "head_feedback", "head_feedback_bwd", "head_loss", "head_loss_spec", "head_loss_spec3"}:
         # evaluation: the head on the last step's images + crop + the f64 skill sums in one pass (nint_head_skill_accum), and the
         # same sums from a prediction in memory (nint_skill_accum), one slot, cos-latitude row weights
         O, oy, ox = args.O, 5, 5
@@ -213,6 +213,18 @@ def main():
                 assert lib.nint_head_feedback(P(ws.h[-1]), B, B, ly.Ch, ly.Chp, O, P(hw), P(hb), P(ws.xs), B, args.C, l0.Cxp,
                                               args.C - O, kf, int(eng.lon_cyclic), g, eng.dt, st) == 0
             run("head_feedback", head_feedback, None, B * comp_px * (ly.Chp + max(kf, 1) * O) * es)
+            # ... and its adjoint (nint_head_feedback_bwd): one step's dx block in (whole 64-byte lines: the fed span's lines), the
+            # step's dpred images in and out, one dh block out
+            fdx = torch.randn(B * comp_px * l0.Cxp, device="cuda").to(torch.bfloat16 if es == 2 else torch.float32)
+            fdp = torch.randn(B, O, ws.H, ws.W, device="cuda")
+            fdh = torch.empty(B * comp_px * ly.Chp * es, dtype=torch.uint8, device="cuda")
+            c0 = args.C - O
+            lines = (((max(kf, 1) - 1) * args.C + c0 + O) * es + 63) // 64 - c0 * es // 64      # 64-byte lines of a pixel's fed span
+
+            def head_feedback_bwd():
+                assert lib.nint_head_feedback_bwd(P(fdx), 0, P(fdp), 0, P(fdh), 0, B, ly.Ch, ly.Chp, O, P(hw), args.C, l0.Cxp, c0, kf,
+                                                  int(eng.lon_cyclic), g, eng.dt, st) == 0
+            run("head_feedback_bwd", head_feedback_bwd, None, B * comp_px * (lines * 64 + 2 * O * 4 + ly.Chp * es))
         run("head_skill", head_skill, None, B * Hc * Wc * ly.Chp * es + maps)
         run("skill_plain", skill_plain, None, B * O * Hc * Wc * 4 + maps)
     tot = sum(ms * (T if not n.startswith(("wgrad", "pack", "preproc")) else 1) for n, ms in rows
