@@ -125,7 +125,27 @@ static Probe make_probe(const nint_seq* s, bool bwd, void* stream) {
   return p;
 }
 
-static int seq_check(const nint_seq* s) {
+// ONE PASS VALUE: what a call of the eight entries is -- the window, what it feeds back (never NULL in here: NO_FB is the open
+// loop), the direction and, roll-out only, where the head cotangents travel.  pass_check, plan_pass, run_pass.
+enum { PASS_FWD, PASS_BWD, PASS_ROLLOUT };         // nint_seq_fwd[_closed] | nint_seq_bwd[_closed] | nint_seq_bwd_rollout
+static const nint_feedback NO_FB = {};
+struct Pass {
+  const nint_seq* s; const nint_feedback* fb; const nint_feedback_grad* rg; int dir;
+  bool bwd() const { return dir != PASS_FWD; }
+  bool fed() const { return fb->O > 0 && fb->from < s->T; }          // steps [from, T) run on the fed-back prediction
+  bool rollout() const { return dir == PASS_ROLLOUT && fed(); }      // ... and this pass differentiates through it
+};
+static Pass pass_of(const nint_seq* s, const nint_feedback* fb, const nint_feedback_grad* rg, int dir) {
+  return Pass{s, fb ? fb : &NO_FB, dir == PASS_ROLLOUT ? rg : nullptr, dir};
+}
+
+// THE ONE CHECK; its order decides the code of a doubly wrong call (tests/golden/seq_plan.npy.xz).  KEPT DIFFERENCE between the
+// backward entries: nint_seq_bwd_rollout looks at the feedback only AFTER the backward fields (a misaligned dh_seq is
+// NINT_E_ALIGN there, NINT_E_ARG with nint_seq_bwd_closed) and only where O < 0 or the window is fed: with O > 0 and from >= T
+// (or O = 0 and from < 0) it accepts a head that nint_seq_bwd_closed refuses.
+static int pass_check(const Pass& p) {
+  const nint_seq* s = p.s; const nint_feedback* fb = p.fb;
+  // 1. the window
   if (!s || s->L < 1 || s->L > NINT_MAX_LAYERS || s->B < 1 || s->T < 1) return NINT_E_ARG;
   if (s->dtype != NINT_F32 && s->dtype != NINT_BF16) return NINT_E_ARG;
   if (s->wave < 0 || s->wave > 5) return NINT_E_ARG;          // the modes of nint_seq.wave (nint.h); no other value is a mode
@@ -136,16 +156,28 @@ static int seq_check(const nint_seq* s) {
     if (!s->h[l] || !s->c[l]) return NINT_E_ARG;
     if (l > 0 && s->layer[l].Cxp != s->layer[l - 1].Chp) return NINT_E_ARG;
   }
-  return NINT_OK;
-}
-// ... and of a closed-loop window (struct nint_feedback; fb is never NULL here: NO_FB stands for the open loop)
-static const nint_feedback NO_FB = {};
-static int seq_check(const nint_seq* s, const nint_feedback* fb) {
-  const int rc = seq_check(s);
-  if (rc != NINT_OK) return rc;
-  if (fb->O < 0 || fb->O > s->layer[0].Cx || fb->from < 0) return NINT_E_ARG;
-  // step 0 can only be fed from a state that was handed in
-  if (fb->O > 0 && (!fb->w || (fb->from == 0 && !s->has_init_state))) return NINT_E_ARG;
+  // 2. the feedback; step 0 can only be fed from a state that was handed in
+  const bool fb_ok = fb->O >= 0 && fb->O <= s->layer[0].Cx && fb->from >= 0 && (fb->O == 0 || (fb->w && (fb->from > 0 || s->has_init_state)));
+  if (p.dir != PASS_ROLLOUT && !fb_ok) return NINT_E_ARG;
+  if (!p.bwd()) return NINT_OK;
+  // 3. the backward fields
+  const int f = s->train_from;         // (nint_seq.train_from: nothing of a layer below it is read)
+  if (f < 0 || f > s->L || (f > 0 && (s->need_dx || s->bwd_parts != 0))) return NINT_E_ARG;
+  for (int l = f; l < s->L; ++l)
+    if (!s->gates[l] || !s->dG[l] || !s->dh[l] || !s->dc[l] || !s->dW[l] || !s->db[l]) return NINT_E_ARG;
+  if ((s->need_dx && !s->dx) || (f < s->L && !s->wg_partial)) return NINT_E_ARG;
+  if (s->fuse_bwd < 0 || (s->fuse_bwd > 2 && !(s->fuse_bwd & 0x40000000)) || s->bwd_parts < 0 || s->bwd_parts > 2) return NINT_E_ARG;
+  if (s->accumulate != 0 && s->accumulate != 1) return NINT_E_ARG;     // stored or added (nint.h); no other value is a mode
+  if ((((uintptr_t)s->dh_seq) & 15) != 0) return NINT_E_ALIGN;
+  // 4. a fed window has no backward pass but the roll-out: d/dx of a fed step re-enters the top layer's d/dh of the step before,
+  // which re-plans BPTT (BwdPlanner::feedback_bwd).  A window in which nothing is fed back trains as ever.
+  if (p.dir != PASS_ROLLOUT) return p.fed() ? NINT_E_ARG : NINT_OK;
+  if ((fb->O < 0 || p.fed()) && !fb_ok) return NINT_E_ARG;
+  if (!p.fed()) return NINT_OK;
+  const nint_feedback_grad* rg = p.rg;          // (where the slab and the one-step scratch travel)
+  if (fb->from == 0 || f > 0 || s->bwd_parts != 0 || !rg || !rg->dpred || !s->dh_seq) return NINT_E_ARG;
+  if (!s->need_dx && !rg->dx_step) return NINT_E_ARG;
+  if ((((uintptr_t)rg->dpred) & 3) != 0 || (((uintptr_t)(s->need_dx ? s->dx : rg->dx_step)) & 15) != 0) return NINT_E_ALIGN;
   return NINT_OK;
 }
 
@@ -234,89 +266,61 @@ static int plan_gate(const nint_seq* s, int n_cu, bool rows8, int l, int t, Gate
   return rc;
 }
 
-// the open-loop pass over steps [0, T)
-static int plan_fwd_open(const nint_seq* s, int n_cu, int T, Steps& out) {
-  const int L = s->L;
-  // (t, layer) WAVEFRONT: step w runs gate(l, w - l) of every layer -- each needs gate(l-1, w-l) and gate(l, w-l-1), both of
-  // step w-1 -- as ONE grid (conv_lstm_multi[8]_kernel).  T + L - 1 launches instead of T * L; the same workgroups on the same
-  // data, so the results are those of the time-major order bit for bit.  Else: for t, for layer (model.py:265-267).
-  const bool wavefront = s->wave && L > 1 && L <= NINT_MULTI_MAX;
-  const bool rows8 = wavefront && (s->wave == 2 || s->wave == 3 || s->wave == 4);
+// ... pushed: its planned conv launch, or (no planned form) the direct nint_cell_fwd call
+static void push_gate(Steps& out, const GateCall& gc, const ConvPlan& pl, int l, int t) {
+  if (pl.gx > 0) { push_conv(out, pl, NINT_PROBE_GATE, NINT_OP_GATE, l, t); return; }
+  SeqStep& st = push(out, STEP_GATE, NINT_PROBE_GATE, l, t);
+  st.prob[st.n++] = SeqProb{NINT_OP_GATE, l, t}; st.gate = gc; st.gate.job.ly = nullptr;      // (run_steps passes the step's own copy)
+}
+
+// Steps [t0, t1) of the forward pass.  OPEN LOOP (f == nullptr), (t, layer) WAVEFRONT: step w runs gate(l, w - l) of every layer
+// -- each needs gate(l-1, w-l) and gate(l, w-l-1), both of step w-1 -- as ONE grid (conv_lstm_multi[8]_kernel).  T + L - 1 launches
+// instead of T * L; the same workgroups on the same data, so the results are those of the time-major order bit for bit.  Else:
+// for t, for layer (model.py:265-267).  CLOSED LOOP (f): gate(0, t) needs gate(L-1, t-1) through the feedback, so
+// nothing merges: feedback(t), gate(0, t) ... gate(L-1, t), each gate on the tile_rows the same `wave` gives it in the open-loop
+// pass -- the pass is then that open-loop pass, bit for bit, over an input that already holds the fed values.
+static int plan_fwd_steps(const nint_seq* s, const nint_feedback* f, int n_cu, int t0, int t1, Steps& out) {
+  const int L = s->L, T = t1 - t0;
+  const bool wavefront = !f && s->wave && L > 1 && L <= NINT_MULTI_MAX;
+  const bool rows8 = (s->wave == 2 || s->wave == 3 || s->wave == 4) && L > 1 && L <= NINT_MULTI_MAX;     // the 8-row rule (plan_gate)
   for (int w = 0; w < (wavefront ? T + L - 1 : T * L); ++w) {
     GateCall gc[NINT_MULTI_MAX]; ConvPlan pl[NINT_MULTI_MAX]; SeqProb pr[NINT_MULTI_MAX];
     int n = 0; bool planned = true;
     for (int l = wavefront ? 0 : w % L; l < (wavefront ? L : w % L + 1); ++l) {
-      const int t = wavefront ? w - l : w / L;
-      if (t < 0 || t >= T) continue;
+      const int t = t0 + (wavefront ? w - l : w / L);
+      if (t < t0 || t >= t1) continue;
+      if (f && l == 0) {                         // slab t of the top layer's h -> block t of xs
+        const nint_layer* l0 = &s->layer[0];
+        const nint_layer* top = &s->layer[L - 1];
+        SeqStep& fb = push(out, STEP_FEEDBACK, NINT_PROBE_FEEDBACK, 0, t);
+        const int rc = nint_internal_feedback_plan(s->h[L - 1], t * s->B, s->B, top->Ch, top->Chp, f->O, f->w, f->b, (void*)s->xs, t * s->B,
+                                                   l0->Cx, l0->Cxp, l0->Cx - f->O, l0->xfold ? l0->k : 0, s->lon_cyclic, &s->g, s->dtype, &fb.fb);
+        if (rc != NINT_OK) return rc;
+      }
       const int rc = plan_gate(s, n_cu, rows8, l, t, &gc[n], &pl[n]);
       if (rc != NINT_OK && rc != NINT_E_SHAPE) return rc;
       planned = planned && rc == NINT_OK;
       pr[n++] = SeqProb{NINT_OP_GATE, l, t};
     }
     if (n > 1 && planned && push_grid(out, pl, n, nullptr, NINT_PROBE_WAVE, n, w, pr, n)) continue;
-    for (int q = 0; q < n; ++q) {    // (a single launch, or a shape the merged grid does not hold: one by one)
-      if (pl[q].gx > 0) { push_conv(out, pl[q], NINT_PROBE_GATE, NINT_OP_GATE, pr[q].layer, pr[q].t); continue; }
-      SeqStep& st = push(out, STEP_GATE, NINT_PROBE_GATE, pr[q].layer, pr[q].t);
-      st.prob[st.n++] = pr[q]; st.gate = gc[q]; st.gate.job.ly = nullptr;      // (run_steps passes the step's own copy)
-    }
+    // (a single launch, or a shape the merged grid does not hold: one by one)
+    for (int q = 0; q < n; ++q) push_gate(out, gc[q], pl[q], pr[q].layer, pr[q].t);
   }
   return NINT_OK;
 }
 
-// CLOSED LOOP (struct nint_feedback): steps below F = min(max(from, 0), T) are the open-loop pass of F steps -- same
-// merges, same rows8 pinning, same launches.  From F on gate(0, t) needs gate(L-1, t-1) through the feedback, so nothing merges:
-// feedback(t), gate(0, t) ... gate(L-1, t), each gate on the tile_rows the same `wave` gives it in the open-loop pass -- the pass
-// is then that open-loop pass, bit for bit, over an input that already holds the fed values.
-static int plan_fwd(const nint_seq* s, const nint_feedback* f, int n_cu, Steps& out) {
-  const int L = s->L, T = s->T;
-  out.reserve((size_t)T * (L + 1));
-  if (f->O <= 0) return plan_fwd_open(s, n_cu, T, out);
-  const int F = f->from < T ? f->from : T;                     // (seq_check: from >= 0)
-  int rc = plan_fwd_open(s, n_cu, F, out);
-  if (rc != NINT_OK) return rc;
-  const bool rows8 = L > 1 && L <= NINT_MULTI_MAX && (s->wave == 2 || s->wave == 3 || s->wave == 4);   // plan_fwd_open's rule
-  const nint_layer* l0 = &s->layer[0];
-  const nint_layer* top = &s->layer[L - 1];
-  for (int t = F; t < T; ++t) {
-    SeqStep& fb = push(out, STEP_FEEDBACK, NINT_PROBE_FEEDBACK, 0, t);
-    // slab t of the top layer's h -> block t of xs
-    rc = nint_internal_feedback_plan(s->h[L - 1], t * s->B, s->B, top->Ch, top->Chp, f->O, f->w, f->b, (void*)s->xs, t * s->B,
-                                     l0->Cx, l0->Cxp, l0->Cx - f->O, l0->xfold ? l0->k : 0, s->lon_cyclic, &s->g, s->dtype, &fb.fb);
-    if (rc != NINT_OK) return rc;
-    for (int l = 0; l < L; ++l) {
-      GateCall gc; ConvPlan pl;
-      rc = plan_gate(s, n_cu, rows8, l, t, &gc, &pl);
-      if (rc != NINT_OK && rc != NINT_E_SHAPE) return rc;
-      if (pl.gx > 0) { push_conv(out, pl, NINT_PROBE_GATE, NINT_OP_GATE, l, t); continue; }
-      SeqStep& st = push(out, STEP_GATE, NINT_PROBE_GATE, l, t);
-      st.prob[st.n++] = SeqProb{NINT_OP_GATE, l, t}; st.gate = gc; st.gate.job.ly = nullptr;         // (run_steps passes the step's own copy)
-    }
-  }
-  return NINT_OK;
+// steps below F = min(max(from, 0), T) are the open-loop pass of F steps -- same merges, same rows8 pinning, same launches
+static int plan_fwd(const Pass& p, int n_cu, Steps& out) {
+  const int T = p.s->T, F = p.fed() ? p.fb->from : T;          // (pass_check: from >= 0)
+  out.reserve((size_t)T * (p.s->L + 1));
+  const int rc = plan_fwd_steps(p.s, nullptr, n_cu, 0, F, out);
+  return rc != NINT_OK || F == T ? rc : plan_fwd_steps(p.s, p.fb, n_cu, F, T, out);
 }
-
 
 // default of the "lower layer's pointwise backward on the fused layer's x columns" option: on (962.2 -> 963.6 samples/s, profiles/HISTORY.md)
 #ifndef NINT_AUTO_LO
 #define NINT_AUTO_LO true
 #endif
-
-static int bwd_check(const nint_seq* s, const nint_feedback* fb) {
-  const int rc = seq_check(s, fb);
-  if (rc != NINT_OK) return rc;
-  const int f = s->train_from;         // (nint_seq.train_from: nothing of a layer below it is read)
-  if (f < 0 || f > s->L || (f > 0 && (s->need_dx || s->bwd_parts != 0))) return NINT_E_ARG;
-  for (int l = f; l < s->L; ++l)
-    if (!s->gates[l] || !s->dG[l] || !s->dh[l] || !s->dc[l] || !s->dW[l] || !s->db[l]) return NINT_E_ARG;
-  if ((s->need_dx && !s->dx) || (f < s->L && !s->wg_partial)) return NINT_E_ARG;
-  if (s->fuse_bwd < 0 || (s->fuse_bwd > 2 && !(s->fuse_bwd & 0x40000000)) || s->bwd_parts < 0 || s->bwd_parts > 2) return NINT_E_ARG;
-  if (s->accumulate != 0 && s->accumulate != 1) return NINT_E_ARG;     // stored or added (nint.h); no other value is a mode
-  if ((((uintptr_t)s->dh_seq) & 15) != 0) return NINT_E_ALIGN;
-  // a fed window has no backward pass yet: d/dx of a fed step would re-enter the top layer's d/dh of the step before, which
-  // re-plans BPTT.  A window in which nothing is fed back trains as ever.
-  if (fb->O > 0 && fb->from < s->T) return NINT_E_ARG;
-  return NINT_OK;
-}
 
 // BPTT.  A layer runs either the CLASSIC step (pointwise backward of time u, then conv backward-data of time u) or the
 // FUSED step X[u] = conv backward-data of time u with the pointwise backward of time u-1 in its epilogue
@@ -352,12 +356,12 @@ struct BwdPlanner {
   PwArgs held_p; int held_t;         // the bottom layer's pointwise backward of time held_t
   // ---- ROLL-OUT (nint_seq_bwd_rollout; rg == nullptr: none of it): steps u >= F were fed.  Layer 0's dgrad of a
   // fed step stores its x columns (without need_dx: into the one-step scratch) and the feedback backward launch follows it.
-  // The caller hands in a nint_seq with fuse_bwd = 1 and wave = 0: every launch by itself, time-major.
+  // plan_bwd hands in a nint_seq with fuse_bwd = 1 and wave = 0: every launch by itself, time-major.
   const nint_feedback* fb; const nint_feedback_grad* rg; int F;
 
-  BwdPlanner(const nint_seq* s_, int n_cu_, Steps& out_, const nint_feedback* fb_ = nullptr, const nint_feedback_grad* rg_ = nullptr)
-      : s(s_), n_cu(n_cu_), out(out_), L(s_->L), T(s_->T), B(s_->B), has_d(false), has_p(false), held_u(0), held_t(0), fb(fb_), rg(rg_),
-        F(rg_ ? fb_->from : s_->T) {
+  BwdPlanner(const Pass& p, int n_cu_, Steps& out_)
+      : s(p.s), n_cu(n_cu_), out(out_), L(p.s->L), T(p.s->T), B(p.s->B), has_d(false), has_p(false), held_u(0), held_t(0), fb(p.fb),
+        rg(p.rollout() ? p.rg : nullptr), F(p.rollout() ? p.fb->from : p.s->T) {
     es = esize(s->dtype); halo_px = (size_t)s->g.Hh * s->g.Wh; comp_px = (size_t)s->g.H * s->g.W;
     const bool explicit_mask = (s->fuse_bwd & 0x40000000) != 0;
     for (int l = L - 1; l >= 0; --l) {
@@ -639,92 +643,48 @@ static int add_wrap_steps(const nint_seq* s, bool bwd, Steps& steps) {
   return NINT_OK;
 }
 
-// check, plan (the CU count the launch-shape rules read is looked up once per pass), then the callers execute
-static int plan_chain(const nint_seq* s, const nint_feedback* fb, bool bwd, Steps& steps) {
-  const int rc = bwd ? bwd_check(s, fb) : seq_check(s, fb);
-  if (rc != NINT_OK) return rc;
-  const int n_cu = nint_internal_n_cu();
-  if (!bwd) return plan_fwd(s, fb, n_cu, steps);
+// The backward plan: the one BwdPlanner over the caller's nint_seq or a view of it (frozen layers: sub_stack).  A ROLL-OUT (4.19):
+// xi_u exists only after layer 0's dgrad of step u and the top layer's pointwise backward of step u-1 needs it, so fuse_bwd = 1, wave = 0.
+static int plan_bwd(const Pass& p, int n_cu, Steps& steps) {
+  const nint_seq* s = p.s;
   const int f = s->train_from;
-  if (f == 0) return BwdPlanner(s, n_cu, steps).plan();
   if (f == s->L) return NINT_OK;                 // every layer frozen: nothing to plan
-  const nint_seq sub = sub_stack(s, f);          // (the plan keeps no pointer into it)
-  const int rc2 = BwdPlanner(&sub, n_cu, steps).plan();
+  nint_seq v;                                    // (the plan keeps no pointer into it)
+  Pass q = p;
+  if (p.rollout()) { v = *s; v.fuse_bwd = 1; v.wave = 0; q.s = &v; }       // (pass_check: f == 0)
+  else if (f > 0) { v = sub_stack(s, f); q.s = &v; }
+  const int rc = BwdPlanner(q, n_cu, steps).plan();
   for (SeqStep& st : steps) {                    // the records and probe tags carry the real layer index
-    for (int q = 0; q < st.n; ++q) st.prob[q].layer += f;
+    for (int i = 0; i < st.n; ++i) st.prob[i].layer += f;
     if (st.kind == STEP_CONV || st.kind == STEP_MULTI || st.kind == STEP_PW) st.tag_layer += f;
   }
-  return rc2;
+  return rc;
 }
 
-// ROLL-OUT BACKWARD (nint_seq_bwd_rollout).  A window in which nothing was fed back is nint_seq_bwd's, record for
-// record.  A fed window is planned by the one BwdPlanner over the caller's nint_seq with fuse_bwd = 1 and wave = 0 -- xi_u
-// exists only after layer 0's dgrad of step u and the top layer's pointwise backward of step u-1 needs it, so no fused step of
-// the top layer and no merged grid -- with the feedback backward launches in between.
-static int plan_rollout(const nint_seq* s, const nint_feedback* fb, const nint_feedback_grad* rg, Steps& steps) {
-  if (!s) return NINT_E_ARG;
-  if (!fb || fb->O == 0 || (fb->from >= s->T && fb->O > 0)) return plan_chain(s, &NO_FB, true, steps);
-  int rc = bwd_check(s, &NO_FB);
-  if (rc == NINT_OK) rc = seq_check(s, fb);
+// THE ONE FUNNEL: check, plan (the CU count the launch-shape rules read is looked up once per pass; cyclic longitude: the wrap
+// launches go in between) and, run_pass, enqueue.
+static int plan_pass(const Pass& p, Steps& steps) {
+  int rc = pass_check(p);
   if (rc != NINT_OK) return rc;
-  if (fb->from == 0 || s->train_from > 0 || s->bwd_parts != 0 || !rg || !rg->dpred || !s->dh_seq) return NINT_E_ARG;
-  if (!s->need_dx && !rg->dx_step) return NINT_E_ARG;
-  if ((((uintptr_t)rg->dpred) & 3) != 0 || (((uintptr_t)(s->need_dx ? s->dx : rg->dx_step)) & 15) != 0) return NINT_E_ALIGN;
-  nint_seq v = *s;                               // (the plan keeps no pointer into it)
-  v.fuse_bwd = 1; v.wave = 0;
-  return BwdPlanner(&v, nint_internal_n_cu(), steps, fb, rg).plan();
-}
-static int plan_rollout_pass(const nint_seq* s, const nint_feedback* fb, const nint_feedback_grad* rg, Steps& steps) {
-  const int rc = plan_rollout(s, fb, rg, steps);
-  return rc == NINT_OK && s->lon_cyclic ? add_wrap_steps(s, true, steps) : rc;
+  const int n_cu = nint_internal_n_cu();
+  rc = p.bwd() ? plan_bwd(p, n_cu, steps) : plan_fwd(p, n_cu, steps);
+  return rc == NINT_OK && p.s->lon_cyclic ? add_wrap_steps(p.s, p.bwd(), steps) : rc;
 }
 
-// ... and, for cyclic longitude only, the wrap launches in between
-static int plan_pass(const nint_seq* s, const nint_feedback* fb, bool bwd, Steps& steps) {
-  if (!fb) fb = &NO_FB;
-  const int rc = s ? plan_chain(s, fb, bwd, steps) : (int)NINT_E_ARG;
-  return rc == NINT_OK && s->lon_cyclic ? add_wrap_steps(s, bwd, steps) : rc;
-}
-
-static int run_pass(const nint_seq* s, const nint_feedback* fb, bool bwd, void* stream) {
+static int run_pass(const Pass& p, void* stream) {
   Steps steps;
-  const int rc = plan_pass(s, fb, bwd, steps);
+  const int rc = plan_pass(p, steps);
   if (rc != NINT_OK) return rc;
-  Probe probe = make_probe(s, bwd, stream);
-  return run_steps(s, steps, probe, stream);
+  Probe probe = make_probe(p.s, p.bwd(), stream);
+  return run_steps(p.s, steps, probe, stream);
 }
-extern "C" int nint_seq_fwd(const nint_seq* s, void* stream) { return run_pass(s, nullptr, false, stream); }
-extern "C" int nint_seq_bwd(const nint_seq* s, void* stream) { return run_pass(s, nullptr, true, stream); }
-extern "C" int nint_seq_fwd_closed(const nint_seq* s, const nint_feedback* fb, void* stream) { return run_pass(s, fb, false, stream); }
-extern "C" int nint_seq_bwd_closed(const nint_seq* s, const nint_feedback* fb, void* stream) { return run_pass(s, fb, true, stream); }
-extern "C" int nint_seq_bwd_rollout(const nint_seq* s, const nint_feedback* fb, const nint_feedback_grad* rg, void* stream) {
-  Steps steps;
-  const int rc = plan_rollout_pass(s, fb, rg, steps);
-  if (rc != NINT_OK) return rc;
-  Probe probe = make_probe(s, true, stream);
-  return run_steps(s, steps, probe, stream);
-}
+extern "C" int nint_seq_fwd(const nint_seq* s, void* stream) { return run_pass(pass_of(s, nullptr, nullptr, PASS_FWD), stream); }
+extern "C" int nint_seq_bwd(const nint_seq* s, void* stream) { return run_pass(pass_of(s, nullptr, nullptr, PASS_BWD), stream); }
+extern "C" int nint_seq_fwd_closed(const nint_seq* s, const nint_feedback* fb, void* stream) { return run_pass(pass_of(s, fb, nullptr, PASS_FWD), stream); }
+extern "C" int nint_seq_bwd_closed(const nint_seq* s, const nint_feedback* fb, void* stream) { return run_pass(pass_of(s, fb, nullptr, PASS_BWD), stream); }
+extern "C" int nint_seq_bwd_rollout(const nint_seq* s, const nint_feedback* fb, const nint_feedback_grad* rg, void* stream) { return run_pass(pass_of(s, fb, rg, PASS_ROLLOUT), stream); }
 
 // ------------------------------------------------------------------------------ the plan, for tests and tools
-extern "C" int nint_debug_seq_plan(const nint_seq* s, int bwd, nint_launch_rec* out, int cap) {
-  return nint_debug_seq_plan_closed(s, nullptr, bwd, out, cap);
-}
-
-static int plan_records(const nint_seq* s, const Steps& steps, int bwd, nint_launch_rec* out, int cap);
-extern "C" int nint_debug_seq_plan_closed(const nint_seq* s, const nint_feedback* fb, int bwd, nint_launch_rec* out, int cap) {
-  Steps steps;
-  const int rc = plan_pass(s, fb, bwd != 0, steps);
-  return rc != NINT_OK ? rc : plan_records(s, steps, bwd, out, cap);
-}
-
-extern "C" int nint_debug_seq_plan_rollout(const nint_seq* s, const nint_feedback* fb, nint_launch_rec* out, int cap) {
-  // made-up, aligned, non-NULL: the plan reads no pointer (a NULL dh_seq or dx is still the caller's, and refused)
-  const nint_feedback_grad rg = {(float*)(uintptr_t)64, (void*)(uintptr_t)64};
-  Steps steps;
-  const int rc = plan_rollout_pass(s, fb, &rg, steps);
-  return rc != NINT_OK ? rc : plan_records(s, steps, 1, out, cap);
-}
-
 static int plan_records(const nint_seq* s, const Steps& steps, int bwd, nint_launch_rec* out, int cap) {
   if (cap > 0 && !out) return NINT_E_ARG;
   int n = 0;
@@ -749,4 +709,17 @@ static int plan_records(const nint_seq* s, const Steps& steps, int bwd, nint_lau
     }
   }
   return n;
+}
+
+static int show_pass(const Pass& p, nint_launch_rec* out, int cap) {
+  Steps steps;
+  const int rc = plan_pass(p, steps);
+  return rc != NINT_OK ? rc : plan_records(p.s, steps, p.bwd(), out, cap);
+}
+extern "C" int nint_debug_seq_plan(const nint_seq* s, int bwd, nint_launch_rec* out, int cap) { return show_pass(pass_of(s, nullptr, nullptr, bwd ? PASS_BWD : PASS_FWD), out, cap); }
+extern "C" int nint_debug_seq_plan_closed(const nint_seq* s, const nint_feedback* fb, int bwd, nint_launch_rec* out, int cap) { return show_pass(pass_of(s, fb, nullptr, bwd ? PASS_BWD : PASS_FWD), out, cap); }
+extern "C" int nint_debug_seq_plan_rollout(const nint_seq* s, const nint_feedback* fb, nint_launch_rec* out, int cap) {
+  // made-up, aligned, non-NULL: the plan reads no pointer (a NULL dh_seq or dx is still the caller's, and refused)
+  const nint_feedback_grad rg = {(float*)(uintptr_t)64, (void*)(uintptr_t)64};
+  return show_pass(pass_of(s, fb, &rg, PASS_ROLLOUT), out, cap);
 }

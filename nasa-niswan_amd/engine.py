@@ -54,6 +54,27 @@ class LayerCfg:
         return _rup(self.k * self.Cx if self.xfold else self.Cx, kc), _rup(self.Ch, 16), _rup(self.Ch, kc)
 
 
+class Feedback:
+    """What the last forward pass on a workspace fed back: its nint_feedback (O = 0: nothing), the
+    tensors its pointers name, the ``feedback_grad`` mark (the window will be trained through what it fed) and the roll-out
+    backward's two buffers -- the f32 slab of the per-step head cotangents and the one-step d/dx scratch, None until asked for."""
+
+    def __init__(self, T: int):
+        self.T, self.fb, self.keep, self.grad, self.dpred, self.dx_step = T, NintFeedback(), None, False, None, None
+
+    @staticmethod
+    def steps(from_step: int, T: int) -> range:
+        """the steps [F, T) of a T-step window that a closed loop from ``from_step`` feeds, F clamped into [0, T]"""
+        return range(min(max(int(from_step), 0), T), T)
+
+    fed = property(lambda self: self.steps(self.fb.from_step if self.fb.O > 0 else self.T, self.T),
+                   doc="the steps [F, T) that were fed (empty: the open loop, or a closed loop that starts beyond the window)")
+
+    def set(self, w=None, b=None, O: int = 0, from_step: int = 0, grad: bool = False):
+        self.keep = (w, b)          # the pointers below stay valid as long as the fields name them
+        self.fb.w, self.fb.b, self.fb.O, self.fb.from_step, self.grad = ptr(w), ptr(b), O, from_step, grad
+
+
 class Workspace:
     """All slabs of one (B, T, H, W) problem.  Halo slabs are zero-initialised once; kernels only
     ever write their interior, so the zero padding of nn.Conv2d (model.py:207-211) is physical."""
@@ -91,12 +112,7 @@ class Workspace:
         self.dx = None
         self._dh_seq = None
         self.Cxp0 = Cxp0
-        # closed loop (nint_feedback): what the last forward pass on this workspace fed back (O = 0: nothing), and the tensors
-        # its pointers name
-        self.fb, self._fb_keep = NintFeedback(), None
-        # roll-out training: the last forward pass asked for the gradient through what it fed back; the f32 slab
-        # of the per-step head cotangents and the one-step d/dx scratch are allocated when first asked for
-        self.fb_grad, self._rollout_dpred, self._rollout_dx = False, None, None
+        self.feedback = Feedback(T)     # closed loop, roll-out training: what the last forward pass on this workspace fed back
         self.seq = NintSeq()
         s = self.seq
         s.dtype, s.B, s.T, s.L = eng.dt, B, T, len(eng.cfgs)
@@ -124,12 +140,14 @@ class Workspace:
             self._dh_seq = torch.empty(self.T * self.B * self.H * self.W * eng.layers[-1].Chp * eng.es, dtype=torch.uint8, device=eng.device)
         return self._dh_seq
 
+    fb = property(lambda self: self.feedback.fb)       # the nint_feedback of the last forward pass
+
     def rollout_dpred(self, eng, O: int) -> torch.Tensor:
         """f32 (T*B, O, H, W), image t*B + b: the direct cotangent l_t of every step's head output going into the roll-out
         backward, g_t = l_t + (the gradient that came back through the feedback) coming out (nint_feedback_grad.dpred)"""
-        if self._rollout_dpred is None or self._rollout_dpred.shape[1] != O:
-            self._rollout_dpred = torch.empty(self.T * self.B, O, self.H, self.W, dtype=torch.float32, device=eng.device)
-        return self._rollout_dpred
+        if self.feedback.dpred is None or self.feedback.dpred.shape[1] != O:
+            self.feedback.dpred = torch.empty(self.T * self.B, O, self.H, self.W, dtype=torch.float32, device=eng.device)
+        return self.feedback.dpred
 
     # byte offsets of slab (t) inside the per-layer stacks
     def h_view(self, eng, l: int, slot: int) -> int:
@@ -466,7 +484,7 @@ class SeqEngine:
         return [ws.h_view(self, l, slot) for l in L], [ws.c_view(self, l, slot) for l in L]
 
     def load_state(self, ws: Workspace, state: ConvLSTMState):
-        """state -> slot 0 of a has_init workspace (the initial state nint_seq_fwd starts from): one launch"""
+        """state -> slot 0 of a has_init workspace (the initial state the forward pass starts from): one launch"""
         if not ws.key[5]:
             raise ValueError("load_state needs a workspace acquired with has_init=True (others start from the zero state)")
         self.check_state(state, ws.B, ws.H, ws.W)
@@ -496,20 +514,18 @@ class SeqEngine:
         """x (B,T,C,H,W) f32 on the engine's device, or a dataset.SlabBatch of that shape.  Runs model.py:253-271
         (all layers, all steps).
 
-        ``feedback = (w, b, from_step)``: CLOSED LOOP (nint_seq_fwd_closed) -- the head ``w`` (O, Ch_top), ``b`` (O)
+        ``feedback = (w, b, from_step)``: CLOSED LOOP -- the head ``w`` (O, Ch_top), ``b`` (O)
         or None, of the top layer's hidden state is rounded to the storage type and written into the last O input channels
         before every step ``t >= from_step``; earlier steps see what ``x`` holds.  The input slab is filled from ``x`` first
         (tensor or SlabBatch), then the pass writes into it.  from_step = 0 needs a has_init workspace.
 
         ``feedback_grad=True`` (with ``feedback``, on a training workspace): the window will be trained THROUGH the fed-back
-        prediction.  It marks the workspace: ``backward(..., rollout=...)`` then runs nint_seq_bwd_rollout.
+        prediction.  It marks the workspace: ``backward(..., rollout=...)`` then runs the roll-out backward.
         The forward pass is the same one.  Without it a backward pass on a fed window is refused, as ever."""
         B, T, Cc, H, W = x.shape
         assert (B, T, H, W) == (ws.B, ws.T, ws.H, ws.W) and Cc == self.cfgs[0].Cx
-        s, fb = ws.seq, ws.fb
-        # ws.fb stays as this pass sets it: a backward pass on a fed window is refused by the library (nint_seq_bwd_closed)
-        fb.w, fb.b, fb.O, fb.from_step, ws._fb_keep = None, None, 0, 0, None
-        ws.fb_grad = bool(feedback_grad) and feedback is not None
+        s = ws.seq
+        ws.feedback.set()       # (stays as this pass sets it: a backward pass on a fed window is refused unless marked)
         if feedback is not None:
             w, b, from_step = feedback
             _, _, O, w2, b2 = self._head_args(w, b)
@@ -522,16 +538,26 @@ class SeqEngine:
             if self._beyond_fused_head(self.layers[-1].Chp, O):
                 raise _lib.NintError(f"feedback: a head of {O} outputs on {self.layers[-1].Chp} padded channels is beyond the "
                                      "staged head kernels (nint_head_feedback: NINT_E_SHAPE)")
-            ws._fb_keep = (w2, b2)      # the pointers below stay valid as long as the fields name them
-            fb.w, fb.b, fb.O, fb.from_step = ptr(w2), ptr(b2), O, from_step
+            ws.feedback.set(w2, b2, O, from_step, bool(feedback_grad))
         self.pack_input(ws, x)
         if h0 is not None:
             self._write_state(h0, c0, self._slot_ptrs(ws, 0), B, ws.g, "0")
         self._set_wave(ws)
-        if fb.O > 0:
-            check(self.lib.nint_seq_fwd_closed(C.byref(s), C.byref(fb), stream_ptr()), "nint_seq_fwd_closed")
+        self._seq_pass(ws, False)
+
+    def _seq_pass(self, ws: Workspace, bwd: bool, rg: Optional[NintFeedbackGrad] = None):
+        """Choose and call the C entry of a whole-sequence pass: forward | backward, each open or (the last forward pass ran with
+        a head) closed loop -- whose backward entry refuses every fed window --, and the roll-out backward (``rg``).  The one
+        place in the package that names the five."""
+        s, fb = ws.seq, ws.feedback.fb
+        if rg is not None:
+            name, extra = "nint_seq_bwd_rollout", (C.byref(fb), C.byref(rg))
+        elif fb.O > 0:
+            name, extra = ("nint_seq_bwd_closed" if bwd else "nint_seq_fwd_closed"), (C.byref(fb),)
         else:
-            check(self.lib.nint_seq_fwd(C.byref(s), stream_ptr()), "nint_seq_fwd")
+            name, extra = ("nint_seq_bwd" if bwd else "nint_seq_fwd"), ()
+        what = name + (" (the backward pass of a window in which the prediction was fed back is not defined)" if bwd and extra and rg is None else "")
+        check(getattr(self.lib, name)(C.byref(s), *extra, stream_ptr()), what)
 
     def _set_wave(self, ws: Workspace):
         """nint_seq.wave: independent launches as one grid (a forward wavefront step; in BPTT the dgrad launches of layers 0 and 1
@@ -568,7 +594,7 @@ class SeqEngine:
         if x.dtype != torch.float32 or not x.is_contiguous():
             x = x.float().contiguous()
         st, g = stream_ptr(), C.byref(ws.g)
-        if self.cfgs[0].xfold:       # (cyclic longitude: the fold wraps by itself; a plain slab's halo is nint_seq_fwd's)
+        if self.cfgs[0].xfold:       # (cyclic longitude: the fold wraps by itself; a plain slab's halo is the forward pass's)
             name = "nint_pack_btchw_xfold_cyclic" if self.lon_cyclic else "nint_pack_btchw_xfold"
             check(getattr(self.lib, name)(ptr(x), ptr(ws.xs), B, T, Cc, self.cfgs[0].k, ws.Cxp0, g, self.dt, st), name)
         else:
@@ -732,14 +758,14 @@ class SeqEngine:
 
     def rollout_cotangents(self, ws: Workspace, w: torch.Tensor, dseq: Optional[torch.Tensor] = None,
                            dpred: Optional[torch.Tensor] = None, slab_filled: bool = False, dh_written: bool = False) -> torch.Tensor:
-        """What the roll-out backward starts from (nint_seq_bwd_rollout's entry contract), for a workspace whose forward pass
+        """What the roll-out backward starts from (the roll-out entry's contract, include/nint.h), for a workspace whose forward pass
         was marked ``feedback_grad``: the slab ``ws.rollout_dpred`` filled with l_t -- ``dseq`` (B, T*O, H, W) and / or
         ``dpred`` (B, O, H, W), which joins step T-1; zeros where there is neither -- and W^T l_t in the blocks of
         ``ws.dh_seq_slab`` that the chain itself does not write (t < F-1 and t = T-1; nint_head_bwd_acc, dh only).
         ``slab_filled``: the caller has written l_t into the slab (the fused head / loss passes take it as their dpred);
         ``dh_written``: ... and every block of dh_seq holds W^T l_t (head_loss_seq_fused).  Returns the slab."""
         Ch, Chp, O, w2, _ = self._head_args(w, None)
-        B, T, F = ws.B, ws.T, min(int(ws.fb.from_step), ws.T)
+        B, T, F = ws.B, ws.T, ws.feedback.fed.start
         slab = ws.rollout_dpred(self, O)
         if not slab_filled:
             v = slab.view(T, B, O, ws.H, ws.W)
@@ -780,14 +806,14 @@ class SeqEngine:
         entries are not touched (they may be None) and their slots of the returned lists hold None.  The workspace must have
         been acquired with a ``train_from`` no larger.  Not with ``need_dx`` or ``parts``; ``train_from == L``: no library call.
         ``rollout`` (a workspace whose forward pass was marked ``feedback_grad``): the slab that
-        ``rollout_cotangents`` returned.  BPTT then runs through the fed-back prediction (nint_seq_bwd_rollout, ``seq_grads``
+        ``rollout_cotangents`` returned.  BPTT then runs through the fed-back prediction (the roll-out entry, ``seq_grads``
         implied); on return the slab holds g_t, which ``head_backward(images=(B, T*B), write_dh=False)`` reduces to the
         head's gradients.  The returned dx is zero on the fed channels of the fed steps: the forward pass overwrote them."""
         assert ws.train
-        fed = ws.fb.O > 0 and ws.fb.from_step < ws.T
-        if rollout is not None and not ws.fb_grad:
+        fed = bool(ws.feedback.fed)
+        if rollout is not None and not ws.feedback.grad:
             raise ValueError("backward(rollout=...) needs a forward pass with feedback=..., feedback_grad=True on this workspace")
-        if ws.fb_grad and fed and rollout is None:
+        if ws.feedback.grad and fed and rollout is None:
             raise ValueError("backward: this window was run with feedback_grad=True: pass rollout=rollout_cotangents(...)")
         rollout = rollout if fed else None               # (nothing was fed back: the window trains as ever)
         L = len(self.cfgs)
@@ -828,38 +854,21 @@ class SeqEngine:
                 dbs.append(torch.empty(4 * cfg.Ch, dtype=torch.float32, device=self.device))
             s.dW[l] = dWs[-1].data_ptr()
             s.db[l] = dbs[-1].data_ptr()
-        dx = None
-        if need_dx:
-            dx = torch.empty(ws.T * ws.B * ws.H * ws.W * ws.Cxp0 * self.es, dtype=torch.uint8, device=self.device)   # ET compact
-            s.dx = dx.data_ptr()
-        s.need_dx = int(need_dx)
-        s.bwd_parts = int(parts)
-        s.dh_seq = ws.dh_seq_slab(self).data_ptr() if seq_grads or rollout is not None else None
-        s.accumulate = int(bool(accumulate))
-        s.train_from = train_from
-        try:
-            if rollout is not None:
-                rg = NintFeedbackGrad()
-                rg.dpred = rollout.data_ptr()
-                if not need_dx:
-                    if ws._rollout_dx is None:
-                        ws._rollout_dx = torch.empty(ws.B * ws.H * ws.W * ws.Cxp0 * self.es, dtype=torch.uint8, device=self.device)
-                    rg.dx_step = ws._rollout_dx.data_ptr()
-                check(self.lib.nint_seq_bwd_rollout(C.byref(s), C.byref(ws.fb), C.byref(rg), stream_ptr()), "nint_seq_bwd_rollout")
-            elif ws.fb.O > 0:       # the window's forward pass was a closed-loop one: refused unless nothing was fed back
-                check(self.lib.nint_seq_bwd_closed(C.byref(s), C.byref(ws.fb), stream_ptr()), "nint_seq_bwd_closed (the backward "
-                      "pass of a window in which the prediction was fed back is not defined)")
-            elif train_from < L:
-                check(self.lib.nint_seq_bwd(C.byref(s), stream_ptr()), "nint_seq_bwd")
-        finally:
-            s.bwd_parts = 0
-            s.dh_seq = None
-            s.accumulate = 0
-            s.train_from = 0
-        s.dx = None
+        dx = torch.empty(ws.T * ws.B * ws.H * ws.W * ws.Cxp0 * self.es, dtype=torch.uint8, device=self.device) if need_dx else None
+        rg = None
+        if rollout is not None:
+            rg = NintFeedbackGrad()
+            rg.dpred = rollout.data_ptr()
+            if not need_dx:
+                if ws.feedback.dx_step is None:
+                    ws.feedback.dx_step = torch.empty(ws.B * ws.H * ws.W * ws.Cxp0 * self.es, dtype=torch.uint8, device=self.device)
+                rg.dx_step = ws.feedback.dx_step.data_ptr()
+        dh_seq = ws.dh_seq_slab(self) if seq_grads or rg is not None else None
+        with self._bwd_fields(s, dx, need_dx, parts, dh_seq, accumulate, train_from):
+            if rg is not None or ws.feedback.fb.O > 0 or train_from < L:
+                self._seq_pass(ws, True, rg)
         dx_out = None
-        if need_dx:
-            # compact [T*B][H][W][Cxp0] -> (B,T,C,H,W)
+        if need_dx:                     # compact [T*B][H][W][Cxp0] -> (B,T,C,H,W)
             C0 = self.cfgs[0].Cx
             tb = torch.empty(ws.T * ws.B, C0, ws.H, ws.W, dtype=torch.float32, device=self.device)
             if self.cfgs[0].xfold:     # gradient of the folded input -> gradient of the input
@@ -870,9 +879,28 @@ class SeqEngine:
                 check(self.lib.nint_unpack_compact(ptr(dx), ptr(tb), ws.T * ws.B, C0, ws.Cxp0, ws.H, ws.W, self.dt, stream_ptr()),
                       "unpack dx")
             dx_out = tb.view(ws.T, ws.B, C0, ws.H, ws.W).transpose(0, 1).contiguous()
-            if rollout is not None:         # the caller's x never reached those channels
-                dx_out[:, ws.fb.from_step:, C0 - ws.fb.O:] = 0
+            if rg is not None:              # the caller's x never reached those channels
+                dx_out[:, ws.feedback.fed.start:, C0 - ws.fb.O:] = 0
         return dWs, dbs, dx_out
+
+    @staticmethod
+    @contextlib.contextmanager
+    def _bwd_fields(s: NintSeq, dx, need_dx, parts, dh_seq, accumulate, train_from):
+        """the nint_seq fields of ONE backward call: set for the body; bwd_parts, dh_seq, accumulate and train_from put back
+        whatever happens, dx once the call has returned (need_dx stays: every call sets its own)"""
+        if dx is not None:
+            s.dx = dx.data_ptr()
+        s.need_dx, s.bwd_parts, s.accumulate, s.train_from = int(need_dx), int(parts), int(bool(accumulate)), train_from
+        s.dh_seq = None if dh_seq is None else dh_seq.data_ptr()
+        try:
+            yield
+        finally:
+            s.bwd_parts, s.dh_seq, s.accumulate, s.train_from = 0, None, 0, 0
+        s.dx = None
+
+    def rollout_head_backward(self, ws: Workspace, w: torch.Tensor, slab: torch.Tensor, dw_out=None, db_out=None, accumulate: bool = False):
+        """the end of a roll-out: the slab came back from ``backward(rollout=slab)`` holding g_t; (dw_head, db_head) from it"""
+        return self.head_backward(ws, w, slab, dw_out, db_out, write_dh=False, images=(ws.B, ws.T * ws.B), accumulate=accumulate)
 
     def state_grads(self, ws: Workspace, l: int):
         """dL/dh_init, dL/dc_init of layer l after backward (has_init_state workspaces)."""

@@ -31,7 +31,7 @@ import torch
 import torch.nn as nn
 from torch._C import _functions
 
-from .engine import ConvLSTMState, LayerCfg, SeqEngine, dtype_code
+from .engine import ConvLSTMState, Feedback, LayerCfg, SeqEngine, dtype_code
 
 __all__ = ["ConvLSTMCell", "ConvLSTM", "ConvLSTMState"]
 
@@ -149,7 +149,7 @@ class _ConvLSTMFn(torch.autograd.Function):
         f = train_from_rule(need[3], [any(need[6 + 2 * l:8 + 2 * l]) or (len(st) > 0 and any(need[6 + 2 * L + 2 * l:8 + 2 * L + 2 * l]))
                                       for l in range(L)]) if train else 0
         # a fed step's input depends on every layer of the step before: the gradient passes through all of them
-        rollout = train and opts.feedback_grad and opts.free_from < T
+        rollout = train and opts.feedback_grad and bool(Feedback.steps(opts.free_from, T))
         if rollout:
             f = 0
         ws = eng.acquire(B, T, H, W, train, has_init, f)
@@ -191,23 +191,11 @@ class _ConvLSTMFn(torch.autograd.Function):
             ctx.rel.release()
             return (None,) * nin
         # the top layer: the head's dL/dh_{T-1} (per step with a sequence cotangent) plus the cotangent of the returned h_{T-1}
-        seq_grads = dseq is not None or ctx.seq_always          # (the default route's rule: _CallOpts)
         dh_top = dst[2 * (L - 1)]
-        dw_head = db_head = None
-        slab = None
-        if ctx.rollout:
-            # BPTT through the fed-back prediction: the head's cotangents travel as a slab, which comes back holding what the
-            # feedback added; the head's own gradients are reduced from it afterwards
-            slab, seq_grads = eng.rollout_cotangents(ws, head_w, dseq, dpred), True
-            if dh_top is not None:
-                eng.add_top_dh(ws, dh_top, True)
-        elif seq_grads:
-            dw_head, db_head = eng.head_backward_seq(ws, head_w, dseq, dpred)
-        elif dpred is not None:
-            dw_head, db_head = eng.head_backward(ws, head_w, dpred)
-        if slab is None and dw_head is None:    # no head gradient at all: the state's cotangent alone (zeros if there is none)
+        dw_head, db_head, seq_grads, slab = _head_backward(ctx, eng, ws, head_w, dpred, dseq)
+        if dw_head is None and slab is None:    # no head gradient at all: the state's cotangent alone (zeros if there is none)
             eng.set_dstate(ws, L - 1, "h", dh_top)
-        elif slab is None and dh_top is not None:
+        elif dh_top is not None:
             eng.add_top_dh(ws, dh_top, seq_grads)
         mask, f = 0, ctx.train_from
         for l in range(f, L):                   # (a frozen layer's returned state feeds nothing that wants a gradient)
@@ -223,13 +211,27 @@ class _ConvLSTMFn(torch.autograd.Function):
                     eng.set_dstate(ws, l, "h", dh)
         dWs, dbs, dx = eng.backward(ws, ctx.x_needs_grad, seq_grads=seq_grads, zero_mask=mask, train_from=f, rollout=slab)
         if slab is not None:
-            dw_head, db_head = eng.head_backward(ws, head_w, slab, write_dh=False, images=(ws.B, ws.T * ws.B))
+            dw_head, db_head = eng.rollout_head_backward(ws, head_w, slab)
         dstate = []
         if ctx.nst:
             for l in range(L):
                 dstate += list(eng.state_grads(ws, l)) if ctx.st_needs_grad and l >= f else [None, None]
         ctx.rel.release()
         return (None, None, None, dx, dw_head, db_head, *_interleave(dWs, dbs), *dstate)
+
+
+def _head_backward(ctx, eng, ws, head_w, dpred, dseq):
+    """The head's part of _ConvLSTMFn.backward, ahead of BPTT: (dw_head, db_head, seq_grads, slab).  A roll-out: the head's
+    cotangents travel as a slab, which comes back holding what the feedback added -- the head's own gradients are reduced from
+    it afterwards.  Else the per-step head backward (the default route's rule: _CallOpts), or the last step's, or nothing."""
+    seq_grads = dseq is not None or ctx.seq_always
+    if ctx.rollout:
+        return None, None, True, eng.rollout_cotangents(ws, head_w, dseq, dpred)
+    if seq_grads:
+        return (*eng.head_backward_seq(ws, head_w, dseq, dpred), True, None)
+    if dpred is not None:
+        return (*eng.head_backward(ws, head_w, dpred), False, None)
+    return None, None, False, None
 
 
 class _CellFn(torch.autograd.Function):

@@ -1,13 +1,13 @@
 """One batch of the reference fit loop (train.py:92-114) as a fixed sequence of HIP launches.
 
     X.cuda(), y.cuda()                      -> inputs already on device
-    pred = generator(X)                     -> nint_pack_btchw + nint_seq_fwd + nint_head_fwd
+    pred = generator(X)                     -> nint_pack_btchw + the forward pass (SeqEngine._seq_pass) + nint_head_fwd
     pred[:, :, 5:95, 5:149].squeeze()       -> crop folded into the loss kernel (index math)
     MSELoss(y,pred) + L1Loss(y,pred)        -> nint_loss_mse_l1_crop (also emits d loss/d pred); with ``loss_weights`` the
                                                per-cell weighted means of loss.py (the _weighted entries); with ``loss``
                                                (a loss.LossSpec) the MSE / L1 / Huber mix with output and step weights
                                                (the _spec entries)
-    zero_grad; loss.backward()              -> nint_head_bwd + nint_seq_bwd (grads overwrite the bucket)
+    zero_grad; loss.backward()              -> nint_head_bwd + the backward pass (grads overwrite the bucket)
     [DDP]                                   -> ONE RCCL all-reduce of the flat gradient bucket
     [stateful]                              -> nint_state_copy before the forward pass (carried state -> slot 0) and after it
                                                (slot T -> carried state): truncated BPTT over consecutive chunks of a record;
@@ -18,16 +18,16 @@
     loss.item(); r2_score(...cpu())         -> device-side accumulators, read once per epoch
     [bptt_segments = n]                     -> the window runs as n segments of S = T/n steps through ONE S-step training
                                                workspace: a forward sweep that keeps the state at every segment start, then
-                                               per segment, last to first, recompute + nint_seq_bwd with accumulate = 1 -- the
+                                               per segment, last to first, recompute + the backward pass with accumulate = 1 -- the
                                                full-window gradient at 1/n of the resident slabs
     [freeze_layers = f]                     -> fine-tuning: the first f ConvLSTM layers are frozen.  nint_seq.train_from = f: BPTT
                                                stops above layer f-1, a frozen layer keeps no stash and no gradient slabs, the
                                                exchange and the norm run over the trained tail of the bucket, and the optimizer
                                                is AdamW over per-layer groups (nint_adam_flat_groups: ``weight_decay``,
                                                ``layer_lr_scale``).  f = L trains the head alone: no BPTT
-    [rollout_from = s]                      -> ROLL-OUT TRAINING: the closed-loop forward from step s (nint_seq_fwd_closed),
+    [rollout_from = s]                      -> ROLL-OUT TRAINING: the closed-loop forward from step s,
                                                the same fused head / loss pass with its dpred in the roll-out slab, BPTT through
-                                               the fed-back prediction (nint_seq_bwd_rollout), then the head's gradients from
+                                               the fed-back prediction (the roll-out entry), then the head's gradients from
                                                the slab (nint_head_bwd_acc over all T*B images)
     [accumulate_steps = k]                  -> k micro-batches add into the bucket (accumulate = 1 from the second on); the
                                                all-reduce and ONE Adam launch with grad_scale = 1/(k world) on the k-th
@@ -278,47 +278,59 @@ class FusedTrainer:
         for v in views:
             v.masked_fill_(bad, 0)
 
-    def _head_pass_rollout(self, eng, ws, yv, B, T, O, H, W, Hc, Wc, wts, spec=None):
-        """_head_pass for a roll-out window: the same fused pass, its d loss / d pred written into the workspace's roll-out slab
-        (zeros where the loss has no term) and W^T of it into the blocks of dh_seq the roll-out backward starts from.  The
-        head's weight gradient waits for the slab to come back from BPTT.  Returns the slab."""
-        m, sq = self.model, self.sequence_loss
-        slab = ws.rollout_dpred(eng, O)
-        sk = {} if spec is None else dict(spec=spec)
-        args = (self.scratch, self.stats, self.halo, Hc, Wc, wts)
-        if sq:
-            fused = eng.head_loss_seq_fused(ws, m.conv.weight, m.conv.bias, yv, slab, *args, **sk)
-        else:
-            slab[:(T - 1) * B].zero_()
-            fused = eng.head_loss_fused(ws, m.conv.weight, m.conv.bias, yv, slab[(T - 1) * B:], *args, **sk)
-        if not fused:       # (a head beyond the fused kernels is beyond the feedback kernel too: the forward pass refuses it first)
-            raise _lib.NintError("rollout_from: the head is beyond the fused head / loss kernels, which write the roll-out slab")
-        return eng.rollout_cotangents(ws, m.conv.weight, slab_filled=True, dh_written=sq)
-
-    def _head_pass(self, eng, ws, yv, B, T, O, H, W, Hc, Wc, wts, acc: bool, spec=None):
+    def _head_pass(self, eng, ws, yv, B, T, O, H, W, Hc, Wc, wts, acc: bool, spec=None, slab=None):
         """head forward + crop + loss + d loss / d pred + dL/dh + the head's weight gradient on the workspace's last h (every
-        h with sequence_loss); `acc`: the head's gradients are added to the bucket (a later micro-batch of a group)"""
+        h with sequence_loss); `acc`: the head's gradients are added to the bucket (a later micro-batch of a group).
+        `slab` (a roll-out window's): the fused pass writes d loss / d pred there (zeros where the loss has no term) and W^T of it
+        into the dh_seq blocks the roll-out starts from; the head's weight gradient waits for the slab to come back (_bptt)."""
         m, sq = self.model, self.sequence_loss
-        if self._dpred is None or self._dpred.numel() != B * (T if sq else 1) * O * H * W:
-            self._dpred = torch.empty(B * (T if sq else 1), O, H, W, dtype=torch.float32, device=self.device)
-        dpred = self._dpred
+        if slab is not None:
+            dpred = slab if sq else slab[(T - 1) * B:]
+            if not sq:
+                slab[:(T - 1) * B].zero_()
+        else:
+            if self._dpred is None or self._dpred.numel() != B * (T if sq else 1) * O * H * W:
+                self._dpred = torch.empty(B * (T if sq else 1), O, H, W, dtype=torch.float32, device=self.device)
+            dpred = self._dpred
         hk = dict(dw_out=self._dw_head, db_out=self._db_head, accumulate=acc)
         sk = {} if spec is None else dict(spec=spec)             # (None: today's calls, argument for argument)
-        if sq:
-            # the same over every step: one pass writes the loss, d loss / d pred (image order t*B + b, which the head's
-            # weight-gradient kernels reduce as T*B images) and the per-step dL/dh that BPTT adds at each t
-            fused = eng.head_loss_seq_fused(ws, m.conv.weight, m.conv.bias, yv, dpred, self.scratch, self.stats, self.halo, Hc, Wc, wts, **sk)
-            if fused:
-                eng.head_backward(ws, m.conv.weight, dpred, write_dh=False, images=(B, T * B), **hk)
-            else:
-                self._head_loss_unfused(eng, ws, yv, dpred, B, T, O, H, W, Hc, Wc, wts, spec)
-                eng.head_backward_seq(ws, m.conv.weight, dpred.view(B, T * O, H, W), None, **hk)
+        # one pass: loss, d loss / d pred and dL/dh of the last step (the prediction itself is never materialised) or of every
+        # step (image order t*B + b, which the head's weight-gradient kernels reduce as T*B images; BPTT adds dL/dh at each t)
+        fused = (eng.head_loss_seq_fused if sq else eng.head_loss_fused)(ws, m.conv.weight, m.conv.bias, yv, dpred, self.scratch,
+                                                                         self.stats, self.halo, Hc, Wc, wts, **sk)
+        if slab is not None:
+            if not fused:   # (a head beyond the fused kernels is beyond the feedback kernel too: the forward pass refuses it first)
+                raise _lib.NintError("rollout_from: the head is beyond the fused head / loss kernels, which write the roll-out slab")
+            eng.rollout_cotangents(ws, m.conv.weight, slab_filled=True, dh_written=sq)
+            return
+        if not fused:
+            self._head_loss_unfused(eng, ws, yv, dpred, B, T, O, H, W, Hc, Wc, wts, spec)
+        if sq and fused:
+            eng.head_backward(ws, m.conv.weight, dpred, write_dh=False, images=(B, T * B), **hk)
+        elif sq:
+            eng.head_backward_seq(ws, m.conv.weight, dpred.view(B, T * O, H, W), None, **hk)
         else:
-            # head forward + crop + loss + dpred + dL/dh in one pass; the prediction itself is never materialised
-            fused = eng.head_loss_fused(ws, m.conv.weight, m.conv.bias, yv, dpred, self.scratch, self.stats, self.halo, Hc, Wc, wts, **sk)
-            if not fused:
-                self._head_loss_unfused(eng, ws, yv, dpred, B, T, O, H, W, Hc, Wc, wts, spec)
             eng.head_backward(ws, m.conv.weight, dpred, write_dh=not fused, **hk)
+
+    def _bptt(self, eng, ws, acc: bool, last: bool, slab=None):
+        """BPTT of a resident window into the bucket -- as a roll-out (`slab`: through the fed-back prediction, then the head's
+        gradients from the slab), in two parts around the exchange, or plain.  Returns (pending, n0) for _finish."""
+        m, L = self.model, self.model.num_layers
+        bk = dict(zero_state_grads=range(L), dW_out=self._dW, db_out=self._db, seq_grads=self.sequence_loss, accumulate=acc,
+                  train_from=self.freeze_layers)
+        if slab is not None:
+            eng.backward(ws, False, rollout=slab, **bk)
+            eng.rollout_head_backward(ws, m.conv.weight, slab, self._dw_head, self._db_head, acc)
+        elif last and self.distributed and self.overlap_allreduce and L > 1 and self._probe[0] is None:
+            # the bucket without layer 0's slice is exchanged under layer 0's weight gradient; _finish exchanges the slice
+            n0 = self.flat.offsets[2]              # layers.0.conv.weight + .bias lead the bucket (module parameter order)
+            eng.backward(ws, False, parts=1, **bk)
+            pending = self.dist.all_reduce(self.flat.grad[n0:], op=self.dist.ReduceOp.SUM, group=self.pg, async_op=True)
+            eng.backward(ws, False, parts=2, **bk)
+            return pending, n0
+        else:
+            eng.backward(ws, False, **bk)
+        return None, 0
 
     def step(self, X: torch.Tensor, y: torch.Tensor, reset=None) -> torch.Tensor:
         """One call of the fit loop; returns the loss as a 0-dim DEVICE tensor (no sync).  X: (B,T,C,Hp,Wp) f32 or a
@@ -327,7 +339,6 @@ class FusedTrainer:
         With ``accumulate_steps = k`` the optimizer steps on every k-th call, on the mean gradient of the k calls."""
         m = self.model
         eng = m._engine(self.device)
-        L = m.num_layers
         wts, spec, B, T, H, W, O, Hc, Wc, yv = self._call_facts(X, y)
         if reset is not None and not self.stateful:
             raise ValueError("step(reset=...) needs FusedTrainer(stateful=True)")
@@ -338,15 +349,13 @@ class FusedTrainer:
         else:
             plan = None
         carried = self._carried_state(eng, B, H, W, reset) if self.stateful else None
-        sq = self.sequence_loss
         mark = self._mark
         if plan is not None:
             mark()
             m._pack_weights(eng)
             self._segments(eng, X, yv, plan, carried, acc, wts, spec)
             return self._finish(last)
-        pending, n0, f = None, 0, self.freeze_layers
-        with eng.window(B, T, H, W, True, self.stateful, f) as ws:
+        with eng.window(B, T, H, W, True, self.stateful, self.freeze_layers) as ws:
             pb, pm = self._probe
             ws.seq.probe = pb.data_ptr() if pb is not None else None
             ws.seq.probe_mask, ws.seq.probe_slots = pm, (pb.numel() // 2 if pb is not None else 0)
@@ -354,33 +363,16 @@ class FusedTrainer:
             m._pack_weights(eng)
             if carried is not None:
                 eng.load_state(ws, carried)          # carried state -> slot 0
-            rollout = self.rollout_from is not None and self.rollout_from < T       # (else nothing is fed: the step it was)
-            if rollout:
-                eng.forward(ws, X, feedback=(m.conv.weight, m.conv.bias, self.rollout_from), feedback_grad=True)
-            else:
-                eng.forward(ws, X)
+            fed = self.rollout_from is not None and bool(ws.feedback.steps(self.rollout_from, T))   # (else: the step it was)
+            eng.forward(ws, X, **(dict(feedback=(m.conv.weight, m.conv.bias, self.rollout_from), feedback_grad=True) if fed else {}))
             if carried is not None:
                 eng.save_state(ws, carried)          # slot T -> carried state; BPTT below stops at the chunk start
                 self._drop_nonfinite_lanes(carried)
             mark()
-            if rollout:
-                slab = self._head_pass_rollout(eng, ws, yv, B, T, O, H, W, Hc, Wc, wts, spec)
-            else:
-                self._head_pass(eng, ws, yv, B, T, O, H, W, Hc, Wc, wts, acc, spec)
+            slab = ws.rollout_dpred(eng, O) if ws.feedback.fed else None
+            self._head_pass(eng, ws, yv, B, T, O, H, W, Hc, Wc, wts, acc, spec, slab)
             mark()
-            bk = dict(zero_state_grads=range(L), dW_out=self._dW, db_out=self._db, seq_grads=sq, accumulate=acc, train_from=f)
-            if rollout:
-                eng.backward(ws, False, rollout=slab, **bk)
-                eng.head_backward(ws, m.conv.weight, slab, write_dh=False, images=(B, T * B), dw_out=self._dw_head,
-                                  db_out=self._db_head, accumulate=acc)
-            elif last and self.distributed and self.overlap_allreduce and L > 1 and pb is None:
-                # the bucket without layer 0's slice is exchanged under layer 0's weight gradient; _finish exchanges the slice
-                n0 = self.flat.offsets[2]              # layers.0.conv.weight + .bias lead the bucket (module parameter order)
-                eng.backward(ws, False, parts=1, **bk)
-                pending = self.dist.all_reduce(self.flat.grad[n0:], op=self.dist.ReduceOp.SUM, group=self.pg, async_op=True)
-                eng.backward(ws, False, parts=2, **bk)
-            else:
-                eng.backward(ws, False, **bk)
+            pending, n0 = self._bptt(eng, ws, acc, last, slab)
             mark()
         return self._finish(last, pending, n0)
 
