@@ -239,6 +239,18 @@ typedef struct nint_feedback_grad {
                          * 16-byte aligned. */
 } nint_feedback_grad;
 
+/* SCHEDULED SAMPLING: a per-step, per-image feed mask beside the nint_feedback, for the _sampled entries below.
+ * (A structure of its own once more: nint_seq, nint_feedback and nint_feedback_grad keep their layout and size.)
+ * fed[t*B + b] = 1: image b runs step t on the fed-back prediction -- xs[t*B + b] receives round_ET(p_{t-1}[b]) on the feedback
+ * channels exactly as in nint_feedback's rule; fed[t*B + b] = 0: image t*B + b of xs keeps every byte the caller packed (a
+ * folded slab's k copies and a cyclic slab's halo columns included).  fed[t][b] = (t >= s) IS nint_feedback.from = s, bit for
+ * bit, gradients included.  The bytes are read on the HOST while the pass is planned and reach the kernels by value, one
+ * 64-bit word per feedback launch: the library keeps no copy, and a masked window holds B <= 64.
+ * fed == NULL (or a NULL pointer to the structure): "use fb->from" -- every _sampled entry is then the entry it extends. */
+typedef struct nint_feedback_mask {
+  const uint8_t* fed;   /* HOST bytes, T*B of them, index t*B + b, each 0 or 1; NULL = none */
+} nint_feedback_mask;
+
 /* launch kinds for nint_seq.probe_mask / the probe tags */
 enum { NINT_PROBE_CAL = 0, NINT_PROBE_GATE = 1, NINT_PROBE_POINTWISE = 2, NINT_PROBE_DGRAD = 3, NINT_PROBE_FUSED = 4,
        NINT_PROBE_WGRAD = 5, NINT_PROBE_FOLD = 6,
@@ -394,6 +406,24 @@ int nint_seq_bwd_closed(const nint_seq* s /*host*/, const nint_feedback* fb /*ho
 int nint_seq_bwd_rollout(const nint_seq* s /*host*/, const nint_feedback* fb /*host*/, const nint_feedback_grad* rg /*host*/,
                          void* stream);
 
+/* The closed-loop forward and the roll-out backward under a FEED MASK (struct nint_feedback_mask above).
+ * fm == NULL or fm->fed == NULL, or fb->O == 0: exactly nint_seq_fwd_closed / nint_seq_bwd_rollout.  With a mask fb->from is
+ * ignored and F is the first step with a fed image (T: none -- the open loop).
+ *   forward   steps [0, F) are the open-loop pass of F steps; steps [F, T) go out time-major, and the feedback launch (behind
+ *             it the xs wrap of cyclic longitude with a plain slab) only at steps with a fed image; it writes the fed images only.
+ *   backward  time-major as nint_seq_bwd_rollout; layer 0's dgrad stores its x columns for u >= F, and the feedback backward of
+ *             step u goes out for EVERY u in [F, T-1]: g_{u-1}[b] = l_{u-1}[b] + (xi_u[b] if fed[u][b] else 0), dh_seq block u-1 =
+ *             W^T g_{u-1} -- so dh_seq blocks t < F-1 and T-1 are the caller's and blocks F-1 ... T-2 the chain's, as before.
+ *             dx (need_dx) holds xi on the fed channels of fed (t, b) only -- the caller zeroes those; on an unfed image of a
+ *             step it is the input's gradient.
+ * The mask's checks sit where the feedback's do (step 2 of the one check; the roll-out looks at the feedback
+ * after the backward fields): NINT_E_ARG for a byte other than 0 or 1, a fed image at step 0 without has_init_state and, in
+ * the roll-out, any fed image at step 0; then, with everything else in order, NINT_E_SHAPE for B > 64 -- before any launch. */
+int nint_seq_fwd_sampled(const nint_seq* s /*host*/, const nint_feedback* fb /*host*/, const nint_feedback_mask* fm /*host*/,
+                         void* stream);
+int nint_seq_bwd_rollout_sampled(const nint_seq* s /*host*/, const nint_feedback* fb /*host*/, const nint_feedback_mask* fm /*host*/,
+                                 const nint_feedback_grad* rg /*host*/, void* stream);
+
 /* The launch plan of a pass, for tests and tools (host only: nothing is enqueued, no pointer is dereferenced).  Both drivers
  * first PLAN a pass into an ordered list of launches and then enqueue that list; this entry runs the same argument checks and
  * the same planner as nint_seq_fwd (bwd = 0) / nint_seq_bwd (bwd = 1: the BPTT chain, without the weight-gradient
@@ -424,6 +454,11 @@ int nint_debug_seq_plan_closed(const nint_seq* s /*host*/, const nint_feedback* 
 /* ... of nint_seq_bwd_rollout (the BPTT chain; the nint_feedback_grad pointers are made up inside: the plan reads none).  `index`
  * counts the feedback backward launches in between. */
 int nint_debug_seq_plan_rollout(const nint_seq* s /*host*/, const nint_feedback* fb /*host*/, nint_launch_rec* out /*host*/, int cap);
+/* ... of a pass under a feed mask.  dir: 0 = nint_seq_fwd_sampled, 1 = the plain backward entry (which refuses every fed window,
+ * as nint_seq_bwd_closed does), 2 = nint_seq_bwd_rollout_sampled; any other value: NINT_E_ARG.  A step without a fed image
+ * shows as a missing feedback launch in `index`. */
+int nint_debug_seq_plan_sampled(const nint_seq* s /*host*/, const nint_feedback* fb /*host*/, const nint_feedback_mask* fm /*host*/,
+                                int dir, nint_launch_rec* out /*host*/, int cap);
 /* The merged-grid rule alone, for tests (host arithmetic only): the NINT_K_* kernel that would carry n independent launches of
  * the conv_igemm bodies shapes[5 * i .. 5 * i + 5) = (epi, wn, wk, ntw, mt) as ONE grid, with_pw != 0: together with one
  * pointwise backward pass -- or NINT_E_SHAPE where no merged kernel holds them all (also n outside [1, 4], or a tuple that is
@@ -532,6 +567,21 @@ int nint_head_feedback(const void* h_slab, int n0, int N, int Ch, int Chp, int O
 int nint_head_feedback_bwd(const void* dx, int dx_n0, float* dpred, int p_n0, void* dh, int dh_n0, int N, int Ch, int Chp, int O,
                            const float* w, int Cx, int Cxp, int c0, int xfold_k, int lon_cyclic, const nint_geom* g, int dtype,
                            void* stream);
+/* The two launches above under a FEED MASK (scheduled sampling).  fed: HOST bytes, one per image, each 0 or
+ * 1; it reaches the kernel by value, as one 64-bit word (bit i = image i of the N), so N <= 64.
+ * nint_head_feedback_sel: the workgroups of an unfed image return before they touch anything -- no byte of that xs image
+ *     changes; a fed image receives what nint_head_feedback stores.  No image fed: no launch.
+ * nint_head_feedback_bwd_sel: a fed image behaves as in nint_head_feedback_bwd; for an unfed image xi is 0 without a read of
+ *     dx, dpred is not stored (its bits stay) and dh = W^T dpred is still written as the whole Chp record, which is
+ *     nint_head_bwd(dh only) of that image bit for bit.  A mask of zeros is legal.
+ * Arguments, checks and their order: those of nint_head_feedback / nint_head_feedback_bwd; then NINT_E_ARG for a NULL fed or
+ * a byte other than 0 or 1, then NINT_E_SHAPE for N > 64; all before any launch. */
+int nint_head_feedback_sel(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w, const float* b,
+                           void* xs_slab, int x_n0, int Cx, int Cxp, int c0, int xfold_k, int lon_cyclic,
+                           const uint8_t* fed /*host, N bytes*/, const nint_geom* g, int dtype, void* stream);
+int nint_head_feedback_bwd_sel(const void* dx, int dx_n0, float* dpred, int p_n0, void* dh, int dh_n0, int N, int Ch, int Chp,
+                               int O, const float* w, int Cx, int Cxp, int c0, int xfold_k, int lon_cyclic,
+                               const uint8_t* fed /*host, N bytes*/, const nint_geom* g, int dtype, void* stream);
 /* dseq (B, T*O, H, W) and dpred_last (B, O, H, W: the cotangent of pred = head(h_{T-1}), added to step T-1 inside the
  * kernels); either may be NULL, not both.  dh_seq: compact ET [T*B][H][W][Chp], image t*B+b, padding channels zero
  * (nint_seq.dh_seq; may be NULL: not written); dw (O,Ch), db (O): summed over all T*B images in a fixed order (overwritten;

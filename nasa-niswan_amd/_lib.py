@@ -62,6 +62,12 @@ class NintFeedbackGrad(C.Structure):
     _fields_ = [("dpred", vp), ("dx_step", vp)]
 
 
+class NintFeedbackMask(C.Structure):
+    """nint_feedback_mask: scheduled sampling (the _sampled entries) -- T*B HOST bytes, index t*B + b, 1 = that image runs that
+    step on the fed-back prediction; NULL: use nint_feedback.from"""
+    _fields_ = [("fed", vp)]
+
+
 class NintLaunchRec(C.Structure):
     """nint_launch_rec: one conv / pointwise problem of a planned pass (nint_debug_seq_plan)"""
     _fields_ = [(n, C.c_int32) for n in ("index", "bwd", "op", "layer", "t", "kernel", "dtype", "epi", "wn", "wk", "ntw", "mt",
@@ -105,6 +111,7 @@ _PG, _PL, _PS, _PLS = C.POINTER(NintGeom), C.POINTER(NintLayer), C.POINTER(NintS
 _POG = C.POINTER(NintOptGroup)
 _PFB = C.POINTER(NintFeedback)
 _PFG = C.POINTER(NintFeedbackGrad)
+_PFM = C.POINTER(NintFeedbackMask)
 SIGNATURES = {
     "nint_version": (_I, []),
     "nint_error_string": (C.c_char_p, [_I]),
@@ -142,11 +149,16 @@ SIGNATURES = {
     "nint_debug_seq_plan_closed": (_I, [_PS, _PFB, _I, C.POINTER(NintLaunchRec), _I]),
     "nint_seq_bwd_rollout": (_I, [_PS, _PFB, _PFG, vp]),
     "nint_debug_seq_plan_rollout": (_I, [_PS, _PFB, C.POINTER(NintLaunchRec), _I]),
+    "nint_seq_fwd_sampled": (_I, [_PS, _PFB, _PFM, vp]),
+    "nint_seq_bwd_rollout_sampled": (_I, [_PS, _PFB, _PFM, _PFG, vp]),
+    "nint_debug_seq_plan_sampled": (_I, [_PS, _PFB, _PFM, _I, C.POINTER(NintLaunchRec), _I]),
     "nint_debug_multi_carrier": (_I, [C.POINTER(C.c_int32), _I, _I]),
     "nint_debug_wgrad_plan": (_I, [_PL, _PG, _I, _I, _I, _I, C.POINTER(NintWgradPlanRec)]),
     "nint_head_fwd": (_I, [vp, _I, _I, _I, _I, _I, vp, vp, vp, _PG, _I, vp]),
     "nint_head_feedback": (_I, [vp, _I, _I, _I, _I, _I, vp, vp, vp, _I, _I, _I, _I, _I, _I, _PG, _I, vp]),
     "nint_head_feedback_bwd": (_I, [vp, _I, vp, _I, vp, _I, _I, _I, _I, _I, vp, _I, _I, _I, _I, _I, _PG, _I, vp]),
+    "nint_head_feedback_sel": (_I, [vp, _I, _I, _I, _I, _I, vp, vp, vp, _I, _I, _I, _I, _I, _I, vp, _PG, _I, vp]),
+    "nint_head_feedback_bwd_sel": (_I, [vp, _I, vp, _I, vp, _I, _I, _I, _I, _I, vp, _I, _I, _I, _I, _I, vp, _PG, _I, vp]),
     "nint_head_bwd": (_I, [vp, _I, _I, _I, _I, _I, vp, vp, vp, vp, vp, _PG, _I, vp, _SZ, vp]),
     "nint_head_bwd_acc": (_I, [vp, _I, _I, _I, _I, _I, vp, vp, vp, vp, vp, _I, _PG, _I, vp, _SZ, vp]),
     "nint_head_fwd_seq": (_I, [vp, _I, _I, _I, _I, _I, vp, vp, vp, _PG, _I, vp]),

@@ -538,10 +538,16 @@ extern "C" int nint_head_fwd_seq(const void* h_slab, int B, int T, int Ch, int C
 //       kx*Cx + c of pixel x is channel c of pixel x + kx - k/2 (0 outside the row; cyc: mod W), so the span runs over all k
 //       copies and a dword's elements are stored only where their channel is a fed one -- a whole dword where both are
 //       (bf16), else the one element.  Nothing else of xs is written: no halo pixel, no slack column, no other channel.
-template <int DT, int CHV>
+// SEL (scheduled sampling): the workgroup of an image whose bit of a.mask is clear returns before it touches
+// anything -- a wave-uniform scalar test on a kernel argument; every byte of that image stays the caller's.  The unmasked
+// instantiation is the kernel it was: it has no such test and never reads the word.
+template <int DT, int CHV, bool SEL = false>
 __global__ __launch_bounds__(256) void head_feedback_kernel(const void* __restrict__ h, const float* __restrict__ w,
                                                             const float* __restrict__ b, void* __restrict__ xs, FbPlan a) {
   // (the pointers as __restrict__ arguments of their own, as head_fwd_kernel has them; a is the rest of the plan)
+  if constexpr (SEL) {
+    if (!((a.mask >> (blockIdx.x / a.H)) & 1ull)) return;
+  }
   extern __shared__ __attribute__((aligned(16))) char smem_fb[];
   constexpr int ES = Elem<DT>::ES, EPD = 4 / ES;               // elements per dword
   float* __restrict__ w_s = (float*)smem_fb;                   // [O][CHV]
@@ -632,7 +638,8 @@ int nint_internal_feedback_plan(const void* h_slab, int n0, int N, int Ch, int C
 int nint_internal_feedback_enqueue(const FbPlan* p, void* stream) {
   const int rc = nint_by_dtype(p->dtype, [&](auto dt) -> int {
     return head_by_chv(p->Chp, [&](auto chv) -> int {
-      auto kern = head_feedback_kernel<decltype(dt)::value, decltype(chv)::value>;
+      auto kern = p->sel ? head_feedback_kernel<decltype(dt)::value, decltype(chv)::value, true>
+                         : head_feedback_kernel<decltype(dt)::value, decltype(chv)::value, false>;
       if (p->lds > 64 * 1024) NINT_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->lds));
       hipLaunchKernelGGL(kern, dim3((unsigned)((size_t)p->N * p->H)), dim3(256), p->lds, (hipStream_t)stream, p->h, p->w, p->b, p->xs, *p);
       return NINT_OK;
@@ -651,6 +658,19 @@ extern "C" int nint_head_feedback(const void* h_slab, int n0, int N, int Ch, int
   return rc != NINT_OK ? rc : nint_internal_feedback_enqueue(&p, stream);
 }
 
+// ... for the images of `fed` (HOST bytes, one per image, 0 or 1; N <= 64) alone: nint_head_feedback's checks in its order,
+// then the mask's (nint_internal_mask_word)
+extern "C" int nint_head_feedback_sel(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w, const float* b,
+                                      void* xs_slab, int x_n0, int Cx, int Cxp, int c0, int xfold_k, int lon_cyclic,
+                                      const uint8_t* fed, const nint_geom* g, int dtype, void* stream) {
+  FbPlan p;
+  int rc = nint_internal_feedback_plan(h_slab, n0, N, Ch, Chp, O, w, b, xs_slab, x_n0, Cx, Cxp, c0, xfold_k, lon_cyclic, g, dtype, &p);
+  if (rc == NINT_OK) rc = nint_internal_mask_word(fed, N, &p.mask);
+  if (rc != NINT_OK) return rc;
+  p.sel = 1;
+  return p.mask ? nint_internal_feedback_enqueue(&p, stream) : (int)NINT_OK;       // (no image fed: nothing to launch)
+}
+
 // ------------------------------------------------------------------------------ feedback, backward (roll-out training)
 // nint_head_feedback_bwd (nint.h): the adjoint of the launch above for the N images of one fed step u.  It is
 // nint_head_bwd's dh pass -- head_bwd_dh_body, one thread per pixel, the weights staged once per workgroup, the Chp record
@@ -659,10 +679,16 @@ extern "C" int nint_head_feedback(const void* h_slab, int n0, int N, int Ch, int
 // dx block by element loads: the fed span starts at any channel c0 (37 of 40: across a 16-byte group), and every 64-byte
 // line it touches is fetched once per pixel either way.  Plain slab: the pixel's own channel, as nint_unpack_compact reads it;
 // folded slab: the k terms of nint_unfold_dx[_cyclic] in its order, from 0.f.
-template <int DT>
+// SEL (scheduled sampling): an image whose bit of `mask` is clear was not fed -- xi is 0 without a read of dx,
+// dpred is handed on as it stands and not stored, so the launch is nint_head_bwd's dh pass for that image.  The test is per
+// thread: a 256-thread workgroup straddles image boundaries.
+template <int DT, bool SEL = false>
 struct DpFed {
-  const void* __restrict__ dx; float* dp; int O, W, Cx, Cxp, c0, kf, cyc; size_t HW;
+  const void* __restrict__ dx; float* dp; int O, W, Cx, Cxp, c0, kf, cyc; size_t HW; unsigned long long mask;
   __device__ __forceinline__ float operator()(size_t n, int o, size_t yx) const {
+    if constexpr (SEL) {
+      if (!((mask >> n) & 1ull)) return dp[(n * O + o) * HW + yx];
+    }
     const int x = (int)(yx % (size_t)W);
     const size_t row = n * HW + yx - x;                        // first pixel of the row in the compact block
     float xi;
@@ -682,11 +708,11 @@ struct DpFed {
   }
 };
 
-template <int DT, int CHV>
+template <int DT, int CHV, bool SEL = false>
 __global__ __launch_bounds__(256) void head_feedback_bwd_kernel(const void* __restrict__ dx, float* dpred, const float* __restrict__ w,
                                                                 void* __restrict__ dh, FbBwdPlan a) {
   extern __shared__ __attribute__((aligned(16))) char smem_fbb[];
-  const DpFed<DT> dp{dx, dpred, a.O, a.W, a.Cx, a.Cxp, a.c0, a.kf, a.cyc, (size_t)a.H * a.W};
+  const DpFed<DT, SEL> dp{dx, dpred, a.O, a.W, a.Cx, a.Cxp, a.c0, a.kf, a.cyc, (size_t)a.H * a.W, a.mask};
   head_bwd_dh_body<DT, CHV>((float*)smem_fbb, w, dp, dh, a.N, a.Ch, a.Chp, a.O, a.H, a.W);
 }
 
@@ -712,7 +738,8 @@ int nint_internal_feedback_bwd_enqueue(const FbBwdPlan* p, void* stream) {
   const size_t npix = (size_t)p->N * p->H * p->W;
   const int rc = nint_by_dtype(p->dtype, [&](auto dt) -> int {
     return head_by_chv(p->Chp, [&](auto chv) -> int {
-      auto kern = head_feedback_bwd_kernel<decltype(dt)::value, decltype(chv)::value>;
+      auto kern = p->sel ? head_feedback_bwd_kernel<decltype(dt)::value, decltype(chv)::value, true>
+                         : head_feedback_bwd_kernel<decltype(dt)::value, decltype(chv)::value, false>;
       if (p->lds > 64 * 1024) NINT_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->lds));
       hipLaunchKernelGGL(kern, dim3((unsigned)((npix + 255) / 256)), dim3(256), p->lds, (hipStream_t)stream, p->dx, p->dpred, p->w, p->dh, *p);
       return NINT_OK;
@@ -730,6 +757,20 @@ extern "C" int nint_head_feedback_bwd(const void* dx, int dx_n0, float* dpred, i
   const int rc = nint_internal_feedback_bwd_plan(dx, dx_n0, dpred, p_n0, dh, dh_n0, N, Ch, Chp, O, w, Cx, Cxp, c0, xfold_k, lon_cyclic,
                                                  g, dtype, &p);
   return rc != NINT_OK ? rc : nint_internal_feedback_bwd_enqueue(&p, stream);
+}
+
+// ... with xi taken for the images of `fed` alone (HOST bytes, one per image, 0 or 1; N <= 64): an unfed image keeps its dpred
+// and gets dh = W^T dpred.  A mask of zeros is legal: the plain head backward (dh only) of the N images.
+extern "C" int nint_head_feedback_bwd_sel(const void* dx, int dx_n0, float* dpred, int p_n0, void* dh, int dh_n0, int N, int Ch,
+                                          int Chp, int O, const float* w, int Cx, int Cxp, int c0, int xfold_k, int lon_cyclic,
+                                          const uint8_t* fed, const nint_geom* g, int dtype, void* stream) {
+  FbBwdPlan p;
+  int rc = nint_internal_feedback_bwd_plan(dx, dx_n0, dpred, p_n0, dh, dh_n0, N, Ch, Chp, O, w, Cx, Cxp, c0, xfold_k, lon_cyclic,
+                                           g, dtype, &p);
+  if (rc == NINT_OK) rc = nint_internal_mask_word(fed, N, &p.mask);
+  if (rc != NINT_OK) return rc;
+  p.sel = 1;
+  return nint_internal_feedback_bwd_enqueue(&p, stream);
 }
 
 // SEQ: d loss / d (head output) comes from the sequence tensors (DpSeq: dpred = dseq, dlast, Bs = B, T) instead of dpred alone

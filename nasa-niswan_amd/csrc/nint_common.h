@@ -368,7 +368,23 @@ struct FbPlan {
   int N, Ch, Chp, O, Cx, Cxp, c0, kf, cyc, dtype;                // kf: 1 = plain slab, k = folded
   int H, W, P, Hh, Wh;
   size_t lds;
+  // SCHEDULED SAMPLING.  sel = 1: the masked instantiation, which feeds image i only where bit i of `mask` is set
+  // (N <= 64).  sel = 0, what every plan function below leaves: the unmasked kernels, which never read the word.
+  unsigned long long mask; int sel;
 };
+// The mask word of N images from N HOST bytes, each 0 or 1 (nint_feedback_mask, nint_head_feedback_sel): NINT_E_ARG for a NULL
+// pointer or any other byte, then NINT_E_SHAPE for more images than the word has bits.
+static inline int nint_internal_mask_word(const unsigned char* fed, int N, unsigned long long* word) {
+  if (!fed || N < 0) return NINT_E_ARG;
+  unsigned long long m = 0;
+  for (int i = 0; i < N; ++i) {
+    if (fed[i] > 1) return NINT_E_ARG;
+    if (i < 64 && fed[i]) m |= 1ull << i;
+  }
+  if (N > 64) return NINT_E_SHAPE;
+  *word = m;
+  return NINT_OK;
+}
 // pure: every check of nint_head_feedback (NINT_E_ARG / NINT_E_ALIGN / NINT_E_SHAPE) is made here and *plan filled; nothing is enqueued
 int nint_internal_feedback_plan(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w, const float* b,
                                 void* xs_slab, int x_n0, int Cx, int Cxp, int c0, int xfold_k, int lon_cyclic, const nint_geom* g,
@@ -380,6 +396,7 @@ struct FbBwdPlan {
   int N, Ch, Chp, O, Cx, Cxp, c0, kf, cyc, dtype;                // kf: 1 = plain slab, k = folded
   int H, W;
   size_t lds;
+  unsigned long long mask; int sel;                              // as in FbPlan; per thread here: a workgroup straddles images
 };
 int nint_internal_feedback_bwd_plan(const void* dx, int dx_n0, float* dpred, int p_n0, void* dh, int dh_n0, int N, int Ch, int Chp,
                                     int O, const float* w, int Cx, int Cxp, int c0, int xfold_k, int lon_cyclic, const nint_geom* g,

@@ -129,14 +129,30 @@ static Probe make_probe(const nint_seq* s, bool bwd, void* stream) {
 // loop), the direction and, roll-out only, where the head cotangents travel.  pass_check, plan_pass, run_pass.
 enum { PASS_FWD, PASS_BWD, PASS_ROLLOUT };         // nint_seq_fwd[_closed] | nint_seq_bwd[_closed] | nint_seq_bwd_rollout
 static const nint_feedback NO_FB = {};
+// SCHEDULED SAMPLING: `mask` (T*B host bytes, or nullptr: "use fb->from") says per step and image what is fed.
+// It is read here, on the host, while the pass is checked and planned; a launch gets its step's 64-bit word by value.
 struct Pass {
-  const nint_seq* s; const nint_feedback* fb; const nint_feedback_grad* rg; int dir;
+  const nint_seq* s; const nint_feedback* fb; const nint_feedback_grad* rg; int dir; const uint8_t* mask;
   bool bwd() const { return dir != PASS_FWD; }
-  bool fed() const { return fb->O > 0 && fb->from < s->T; }          // steps [from, T) run on the fed-back prediction
+  // the first step with a fed image (a mask; any non-zero byte counts, so that a bad byte is looked at), else fb->from
+  int first() const {
+    if (!mask) return fb->from;
+    for (int t = 0; t < s->T; ++t) if (word_any(t)) return t;
+    return s->T;
+  }
+  bool word_any(int t) const { for (int b = 0; b < s->B; ++b) if (mask[(size_t)t * s->B + b]) return true; return false; }
+  unsigned long long word(int t) const {                             // (pass_check: B <= 64, bytes 0 / 1)
+    unsigned long long m = 0;
+    for (int b = 0; b < s->B && b < 64; ++b) if (mask[(size_t)t * s->B + b]) m |= 1ull << b;
+    return m;
+  }
+  bool fed() const { return fb->O > 0 && first() < s->T; }           // steps [F, T) run time-major, fed images on the fed-back prediction
   bool rollout() const { return dir == PASS_ROLLOUT && fed(); }      // ... and this pass differentiates through it
 };
-static Pass pass_of(const nint_seq* s, const nint_feedback* fb, const nint_feedback_grad* rg, int dir) {
-  return Pass{s, fb ? fb : &NO_FB, dir == PASS_ROLLOUT ? rg : nullptr, dir};
+static Pass pass_of(const nint_seq* s, const nint_feedback* fb, const nint_feedback_grad* rg, int dir, const nint_feedback_mask* fm = nullptr) {
+  // (a mask beside a head of no outputs says nothing; s is checked before anything reads it: pass_check step 1 comes first)
+  const bool masked = fm && fm->fed && fb && fb->O > 0 && s && s->B >= 1 && s->T >= 1;
+  return Pass{s, fb ? fb : &NO_FB, dir == PASS_ROLLOUT ? rg : nullptr, dir, masked ? fm->fed : nullptr};
 }
 
 // THE ONE CHECK; its order decides the code of a doubly wrong call (tests/golden/seq_plan.npy.xz).  KEPT DIFFERENCE between the
@@ -157,9 +173,15 @@ static int pass_check(const Pass& p) {
     if (l > 0 && s->layer[l].Cxp != s->layer[l - 1].Chp) return NINT_E_ARG;
   }
   // 2. the feedback; step 0 can only be fed from a state that was handed in
-  const bool fb_ok = fb->O >= 0 && fb->O <= s->layer[0].Cx && fb->from >= 0 && (fb->O == 0 || (fb->w && (fb->from > 0 || s->has_init_state)));
+  // A mask (4.21) takes the place of `from`, which is then not read: every byte 0 or 1, and F in the place of from.  Its one
+  // NINT_E_SHAPE -- more images than the mask word has bits -- comes where the feedback has been found in order.
+  bool mask_ok = true;
+  for (size_t i = 0; p.mask && i < (size_t)s->T * s->B; ++i) mask_ok = mask_ok && p.mask[i] <= 1;
+  const int F = p.mask ? p.first() : fb->from;
+  const bool fb_ok = fb->O >= 0 && fb->O <= s->layer[0].Cx && mask_ok && F >= 0 && (fb->O == 0 || (fb->w && (F > 0 || s->has_init_state)));
+  const int mask_rc = p.mask && s->B > 64 ? NINT_E_SHAPE : NINT_OK;
   if (p.dir != PASS_ROLLOUT && !fb_ok) return NINT_E_ARG;
-  if (!p.bwd()) return NINT_OK;
+  if (!p.bwd()) return mask_rc;
   // 3. the backward fields
   const int f = s->train_from;         // (nint_seq.train_from: nothing of a layer below it is read)
   if (f < 0 || f > s->L || (f > 0 && (s->need_dx || s->bwd_parts != 0))) return NINT_E_ARG;
@@ -171,14 +193,14 @@ static int pass_check(const Pass& p) {
   if ((((uintptr_t)s->dh_seq) & 15) != 0) return NINT_E_ALIGN;
   // 4. a fed window has no backward pass but the roll-out: d/dx of a fed step re-enters the top layer's d/dh of the step before,
   // which re-plans BPTT (BwdPlanner::feedback_bwd).  A window in which nothing is fed back trains as ever.
-  if (p.dir != PASS_ROLLOUT) return p.fed() ? NINT_E_ARG : NINT_OK;
+  if (p.dir != PASS_ROLLOUT) return p.fed() ? (int)NINT_E_ARG : mask_rc;
   if ((fb->O < 0 || p.fed()) && !fb_ok) return NINT_E_ARG;
-  if (!p.fed()) return NINT_OK;
+  if (!p.fed()) return mask_rc;
   const nint_feedback_grad* rg = p.rg;          // (where the slab and the one-step scratch travel)
-  if (fb->from == 0 || f > 0 || s->bwd_parts != 0 || !rg || !rg->dpred || !s->dh_seq) return NINT_E_ARG;
+  if (F == 0 || f > 0 || s->bwd_parts != 0 || !rg || !rg->dpred || !s->dh_seq) return NINT_E_ARG;     // (F == 0: a fed image at step 0)
   if (!s->need_dx && !rg->dx_step) return NINT_E_ARG;
   if ((((uintptr_t)rg->dpred) & 3) != 0 || (((uintptr_t)(s->need_dx ? s->dx : rg->dx_step)) & 15) != 0) return NINT_E_ALIGN;
-  return NINT_OK;
+  return mask_rc;
 }
 
 // A pass is first PLANNED into an ordered list of steps -- host arithmetic only: nothing is enqueued, no stream is touched, no
@@ -279,7 +301,9 @@ static void push_gate(Steps& out, const GateCall& gc, const ConvPlan& pl, int l,
 // for t, for layer (model.py:265-267).  CLOSED LOOP (f): gate(0, t) needs gate(L-1, t-1) through the feedback, so
 // nothing merges: feedback(t), gate(0, t) ... gate(L-1, t), each gate on the tile_rows the same `wave` gives it in the open-loop
 // pass -- the pass is then that open-loop pass, bit for bit, over an input that already holds the fed values.
-static int plan_fwd_steps(const nint_seq* s, const nint_feedback* f, int n_cu, int t0, int t1, Steps& out) {
+// UNDER A MASK (m) the feedback launch goes out only at steps with a fed image, as the masked instantiation with
+// the step's word; the gates of the step are planned as in any closed-loop step.
+static int plan_fwd_steps(const nint_seq* s, const nint_feedback* f, int n_cu, int t0, int t1, Steps& out, const Pass* m = nullptr) {
   const int L = s->L, T = t1 - t0;
   const bool wavefront = !f && s->wave && L > 1 && L <= NINT_MULTI_MAX;
   const bool rows8 = (s->wave == 2 || s->wave == 3 || s->wave == 4) && L > 1 && L <= NINT_MULTI_MAX;     // the 8-row rule (plan_gate)
@@ -289,13 +313,15 @@ static int plan_fwd_steps(const nint_seq* s, const nint_feedback* f, int n_cu, i
     for (int l = wavefront ? 0 : w % L; l < (wavefront ? L : w % L + 1); ++l) {
       const int t = t0 + (wavefront ? w - l : w / L);
       if (t < t0 || t >= t1) continue;
-      if (f && l == 0) {                         // slab t of the top layer's h -> block t of xs
+      const unsigned long long word = m ? m->word(t) : ~0ull;
+      if (f && l == 0 && word) {                 // slab t of the top layer's h -> block t of xs
         const nint_layer* l0 = &s->layer[0];
         const nint_layer* top = &s->layer[L - 1];
         SeqStep& fb = push(out, STEP_FEEDBACK, NINT_PROBE_FEEDBACK, 0, t);
         const int rc = nint_internal_feedback_plan(s->h[L - 1], t * s->B, s->B, top->Ch, top->Chp, f->O, f->w, f->b, (void*)s->xs, t * s->B,
                                                    l0->Cx, l0->Cxp, l0->Cx - f->O, l0->xfold ? l0->k : 0, s->lon_cyclic, &s->g, s->dtype, &fb.fb);
         if (rc != NINT_OK) return rc;
+        if (m) { fb.fb.mask = word; fb.fb.sel = 1; }
       }
       const int rc = plan_gate(s, n_cu, rows8, l, t, &gc[n], &pl[n]);
       if (rc != NINT_OK && rc != NINT_E_SHAPE) return rc;
@@ -311,10 +337,10 @@ static int plan_fwd_steps(const nint_seq* s, const nint_feedback* f, int n_cu, i
 
 // steps below F = min(max(from, 0), T) are the open-loop pass of F steps -- same merges, same rows8 pinning, same launches
 static int plan_fwd(const Pass& p, int n_cu, Steps& out) {
-  const int T = p.s->T, F = p.fed() ? p.fb->from : T;          // (pass_check: from >= 0)
+  const int T = p.s->T, F = p.fed() ? p.first() : T;           // (pass_check: from >= 0)
   out.reserve((size_t)T * (p.s->L + 1));
   const int rc = plan_fwd_steps(p.s, nullptr, n_cu, 0, F, out);
-  return rc != NINT_OK || F == T ? rc : plan_fwd_steps(p.s, p.fb, n_cu, F, T, out);
+  return rc != NINT_OK || F == T ? rc : plan_fwd_steps(p.s, p.fb, n_cu, F, T, out, p.mask ? &p : nullptr);
 }
 
 // default of the "lower layer's pointwise backward on the fused layer's x columns" option: on (962.2 -> 963.6 samples/s, profiles/HISTORY.md)
@@ -357,11 +383,13 @@ struct BwdPlanner {
   // ---- ROLL-OUT (nint_seq_bwd_rollout; rg == nullptr: none of it): steps u >= F were fed.  Layer 0's dgrad of a
   // fed step stores its x columns (without need_dx: into the one-step scratch) and the feedback backward launch follows it.
   // plan_bwd hands in a nint_seq with fuse_bwd = 1 and wave = 0: every launch by itself, time-major.
-  const nint_feedback* fb; const nint_feedback_grad* rg; int F;
+  // Under a mask (4.21) F is the first step with a fed image and the launch of EVERY step u >= F goes out, with the step's word:
+  // an all-zero word makes it the plain head backward of block u-1, so the division of dh_seq between caller and chain stays.
+  const nint_feedback* fb; const nint_feedback_grad* rg; int F; const Pass* mp;
 
   BwdPlanner(const Pass& p, int n_cu_, Steps& out_)
       : s(p.s), n_cu(n_cu_), out(out_), L(p.s->L), T(p.s->T), B(p.s->B), has_d(false), has_p(false), held_u(0), held_t(0), fb(p.fb),
-        rg(p.rollout() ? p.rg : nullptr), F(p.rollout() ? p.fb->from : p.s->T) {
+        rg(p.rollout() ? p.rg : nullptr), F(p.rollout() ? p.first() : p.s->T), mp(p.mask ? &p : nullptr) {
     es = esize(s->dtype); halo_px = (size_t)s->g.Hh * s->g.Wh; comp_px = (size_t)s->g.H * s->g.W;
     const bool explicit_mask = (s->fuse_bwd & 0x40000000) != 0;
     for (int l = L - 1; l >= 0; --l) {
@@ -513,9 +541,11 @@ struct BwdPlanner {
     const nint_layer* l0 = &s->layer[0];
     const nint_layer* top = &s->layer[L - 1];
     SeqStep& st = push(out, STEP_FEEDBACK_BWD, NINT_PROBE_FEEDBACK_BWD, 0, u);
-    return nint_internal_feedback_bwd_plan(s->need_dx ? s->dx : rg->dx_step, s->need_dx ? u * (int)B : 0, rg->dpred, (u - 1) * (int)B,
-                                           (void*)s->dh_seq, (u - 1) * (int)B, (int)B, top->Ch, top->Chp, fb->O, fb->w, l0->Cx, l0->Cxp,
-                                           l0->Cx - fb->O, l0->xfold ? l0->k : 0, s->lon_cyclic, &s->g, s->dtype, &st.fbb);
+    const int rc = nint_internal_feedback_bwd_plan(s->need_dx ? s->dx : rg->dx_step, s->need_dx ? u * (int)B : 0, rg->dpred, (u - 1) * (int)B,
+                                                   (void*)s->dh_seq, (u - 1) * (int)B, (int)B, top->Ch, top->Chp, fb->O, fb->w, l0->Cx, l0->Cxp,
+                                                   l0->Cx - fb->O, l0->xfold ? l0->k : 0, s->lon_cyclic, &s->g, s->dtype, &st.fbb);
+    if (mp) { st.fbb.mask = mp->word(u); st.fbb.sel = 1; }       // (the plan function zero-fills both: after it)
+    return rc;
   }
 
   int plan() {
@@ -683,6 +713,8 @@ extern "C" int nint_seq_bwd(const nint_seq* s, void* stream) { return run_pass(p
 extern "C" int nint_seq_fwd_closed(const nint_seq* s, const nint_feedback* fb, void* stream) { return run_pass(pass_of(s, fb, nullptr, PASS_FWD), stream); }
 extern "C" int nint_seq_bwd_closed(const nint_seq* s, const nint_feedback* fb, void* stream) { return run_pass(pass_of(s, fb, nullptr, PASS_BWD), stream); }
 extern "C" int nint_seq_bwd_rollout(const nint_seq* s, const nint_feedback* fb, const nint_feedback_grad* rg, void* stream) { return run_pass(pass_of(s, fb, rg, PASS_ROLLOUT), stream); }
+extern "C" int nint_seq_fwd_sampled(const nint_seq* s, const nint_feedback* fb, const nint_feedback_mask* fm, void* stream) { return run_pass(pass_of(s, fb, nullptr, PASS_FWD, fm), stream); }
+extern "C" int nint_seq_bwd_rollout_sampled(const nint_seq* s, const nint_feedback* fb, const nint_feedback_mask* fm, const nint_feedback_grad* rg, void* stream) { return run_pass(pass_of(s, fb, rg, PASS_ROLLOUT, fm), stream); }
 
 // ------------------------------------------------------------------------------ the plan, for tests and tools
 static int plan_records(const nint_seq* s, const Steps& steps, int bwd, nint_launch_rec* out, int cap) {
@@ -722,4 +754,9 @@ extern "C" int nint_debug_seq_plan_rollout(const nint_seq* s, const nint_feedbac
   // made-up, aligned, non-NULL: the plan reads no pointer (a NULL dh_seq or dx is still the caller's, and refused)
   const nint_feedback_grad rg = {(float*)(uintptr_t)64, (void*)(uintptr_t)64};
   return show_pass(pass_of(s, fb, &rg, PASS_ROLLOUT), out, cap);
+}
+extern "C" int nint_debug_seq_plan_sampled(const nint_seq* s, const nint_feedback* fb, const nint_feedback_mask* fm, int dir, nint_launch_rec* out, int cap) {
+  if (dir != PASS_FWD && dir != PASS_BWD && dir != PASS_ROLLOUT) return NINT_E_ARG;
+  const nint_feedback_grad rg = {(float*)(uintptr_t)64, (void*)(uintptr_t)64};       // (made up, as in nint_debug_seq_plan_rollout)
+  return show_pass(pass_of(s, fb, &rg, dir, fm), out, cap);
 }

@@ -11,7 +11,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 
 from . import _lib
-from ._lib import NINT_BF16, NINT_F32, NintFeedback, NintFeedbackGrad, NintGeom, NintLayer, NintSeq, check, ptr, stream_ptr
+from ._lib import NINT_BF16, NINT_F32, NintFeedback, NintFeedbackGrad, NintFeedbackMask, NintGeom, NintLayer, NintSeq, check, ptr, stream_ptr
 
 # 0: the library picks the gate / dgrad pixel-tile height per launch shape; 4 or 8 forces it for every layer of
 # engines built afterwards (nint_layer.tile_rows) -- how the tests run both heights on every shape
@@ -57,10 +57,14 @@ class LayerCfg:
 class Feedback:
     """What the last forward pass on a workspace fed back: its nint_feedback (O = 0: nothing), the
     tensors its pointers name, the ``feedback_grad`` mark (the window will be trained through what it fed) and the roll-out
-    backward's two buffers -- the f32 slab of the per-step head cotangents and the one-step d/dx scratch, None until asked for."""
+    backward's two buffers -- the f32 slab of the per-step head cotangents and the one-step d/dx scratch, None until asked for.
+    Scheduled sampling: ``mask``, the pinned host uint8 (T, B) array that ``fm`` (nint_feedback_mask) points
+    at, or None; ``fb.from_step`` is then F, the first step with a fed image, so ``fed`` stays the range [F, T)."""
 
-    def __init__(self, T: int):
+    def __init__(self, T: int, B: int = 1):
         self.T, self.fb, self.keep, self.grad, self.dpred, self.dx_step = T, NintFeedback(), None, False, None, None
+        self.B = B
+        self.fm, self.mask, self._pin = NintFeedbackMask(), None, None
 
     @staticmethod
     def steps(from_step: int, T: int) -> range:
@@ -70,8 +74,44 @@ class Feedback:
     fed = property(lambda self: self.steps(self.fb.from_step if self.fb.O > 0 else self.T, self.T),
                    doc="the steps [F, T) that were fed (empty: the open loop, or a closed loop that starts beyond the window)")
 
-    def set(self, w=None, b=None, O: int = 0, from_step: int = 0, grad: bool = False):
+    @staticmethod
+    def mask_bt(mask, B: int, T: int) -> torch.Tensor:
+        """a feed mask as the host layers take it -- a bool / uint8 tensor or array of shape (B, T), every value 0 or 1 -- as a
+        CPU uint8 tensor (B, T); ValueError otherwise.  Pure: no device is asked for."""
+        m = torch.as_tensor(mask).detach().cpu()
+        if m.dtype not in (torch.bool, torch.uint8) or tuple(m.shape) != (B, T):
+            raise ValueError(f"feed mask: a bool / uint8 tensor or array of shape (B, T) = ({B}, {T}) is needed, got "
+                             f"{m.dtype} {tuple(m.shape)}")
+        m = m.to(torch.uint8)
+        if bool((m > 1).any()):
+            raise ValueError("feed mask: every value must be 0 or 1")
+        return m
+
+    @staticmethod
+    def first_fed(m_bt: torch.Tensor) -> int:
+        """F of a (B, T) mask: the first step with a fed image, T if there is none"""
+        any_t = m_bt.bool().any(dim=0)
+        return int(any_t.to(torch.uint8).argmax()) if bool(any_t.any()) else int(m_bt.shape[1])
+
+    @property
+    def fed_mask(self) -> torch.Tensor:
+        """(B, T) bool, CPU: image b ran step t on the fed-back prediction (all False: the open loop)"""
+        if self.mask is not None and self.fb.O > 0:
+            return self.mask.t().bool()
+        return (torch.arange(self.T) >= self.fed.start).expand(self.B, self.T).clone()
+
+    def set(self, w=None, b=None, O: int = 0, from_step: int = 0, grad: bool = False, mask=None):
+        """``mask``: a CPU uint8 (B, T) tensor (``mask_bt``) in the place of ``from_step``"""
         self.keep = (w, b)          # the pointers below stay valid as long as the fields name them
+        self.mask, self.fm.fed = None, None
+        if mask is not None:
+            # one pinned (T, B) buffer per workspace, time-major (index t*B + b), reused pass after pass: the library reads it on
+            # the host while it plans, inside the call, so nothing is in flight from it when the next pass fills it
+            if self._pin is None or tuple(self._pin.shape) != (mask.shape[1], mask.shape[0]):
+                self._pin = torch.empty(mask.shape[1], mask.shape[0], dtype=torch.uint8, pin_memory=True)
+            tb = self._pin
+            tb.copy_(mask.t())
+            self.mask, self.fm.fed, from_step = tb, tb.data_ptr(), self.first_fed(mask)
         self.fb.w, self.fb.b, self.fb.O, self.fb.from_step, self.grad = ptr(w), ptr(b), O, from_step, grad
 
 
@@ -112,7 +152,7 @@ class Workspace:
         self.dx = None
         self._dh_seq = None
         self.Cxp0 = Cxp0
-        self.feedback = Feedback(T)     # closed loop, roll-out training: what the last forward pass on this workspace fed back
+        self.feedback = Feedback(T, B)     # closed loop, roll-out training: what the last forward pass on this workspace fed back
         self.seq = NintSeq()
         s = self.seq
         s.dtype, s.B, s.T, s.L = eng.dt, B, T, len(eng.cfgs)
@@ -518,6 +558,8 @@ class SeqEngine:
         or None, of the top layer's hidden state is rounded to the storage type and written into the last O input channels
         before every step ``t >= from_step``; earlier steps see what ``x`` holds.  The input slab is filled from ``x`` first
         (tensor or SlabBatch), then the pass writes into it.  from_step = 0 needs a has_init workspace.
+        In the place of ``from_step``: a FEED MASK (scheduled sampling), a bool / uint8 tensor or array of
+        shape (B, T) -- image b runs step t on the fed-back prediction where it is set and on ``x`` where it is not; B <= 64.
 
         ``feedback_grad=True`` (with ``feedback``, on a training workspace): the window will be trained THROUGH the fed-back
         prediction.  It marks the workspace: ``backward(..., rollout=...)`` then runs the roll-out backward.
@@ -529,6 +571,12 @@ class SeqEngine:
         if feedback is not None:
             w, b, from_step = feedback
             _, _, O, w2, b2 = self._head_args(w, b)
+            mask = None
+            if not isinstance(from_step, int) and getattr(from_step, "ndim", 0) > 0:         # (a 0-dim value is a step index)
+                mask = Feedback.mask_bt(from_step, B, T)
+                if B > 64:
+                    raise _lib.NintError(f"feedback: a feed mask holds at most 64 images per step, got B = {B} (NINT_E_SHAPE)")
+                from_step = Feedback.first_fed(mask)
             from_step = int(from_step)
             if w2.numel() != O * self.cfgs[-1].Ch or not 1 <= O <= Cc:      # (O, Ch) or the 1x1 conv's (O, Ch, 1, 1)
                 raise ValueError(f"feedback: head weight {tuple(w.shape)} does not map {self.cfgs[-1].Ch} hidden channels onto "
@@ -538,7 +586,7 @@ class SeqEngine:
             if self._beyond_fused_head(self.layers[-1].Chp, O):
                 raise _lib.NintError(f"feedback: a head of {O} outputs on {self.layers[-1].Chp} padded channels is beyond the "
                                      "staged head kernels (nint_head_feedback: NINT_E_SHAPE)")
-            ws.feedback.set(w2, b2, O, from_step, bool(feedback_grad))
+            ws.feedback.set(w2, b2, O, from_step, bool(feedback_grad), mask)
         self.pack_input(ws, x)
         if h0 is not None:
             self._write_state(h0, c0, self._slot_ptrs(ws, 0), B, ws.g, "0")
@@ -547,11 +595,17 @@ class SeqEngine:
 
     def _seq_pass(self, ws: Workspace, bwd: bool, rg: Optional[NintFeedbackGrad] = None):
         """Choose and call the C entry of a whole-sequence pass: forward | backward, each open or (the last forward pass ran with
-        a head) closed loop -- whose backward entry refuses every fed window --, and the roll-out backward (``rg``).  The one
-        place in the package that names the five."""
-        s, fb = ws.seq, ws.feedback.fb
-        if rg is not None:
+        a head) closed loop -- whose backward entry refuses every fed window --, and the roll-out backward (``rg``); the closed
+        forward and the roll-out backward under a feed mask are the _sampled entries.  The one place in the package that names
+        the seven."""
+        s, fb, fm = ws.seq, ws.feedback.fb, ws.feedback.fm
+        masked = ws.feedback.mask is not None and fb.O > 0
+        if rg is not None and masked:
+            name, extra = "nint_seq_bwd_rollout_sampled", (C.byref(fb), C.byref(fm), C.byref(rg))
+        elif rg is not None:
             name, extra = "nint_seq_bwd_rollout", (C.byref(fb), C.byref(rg))
+        elif masked and not bwd:
+            name, extra = "nint_seq_fwd_sampled", (C.byref(fb), C.byref(fm))
         elif fb.O > 0:
             name, extra = ("nint_seq_bwd_closed" if bwd else "nint_seq_fwd_closed"), (C.byref(fb),)
         else:
@@ -808,7 +862,8 @@ class SeqEngine:
         ``rollout`` (a workspace whose forward pass was marked ``feedback_grad``): the slab that
         ``rollout_cotangents`` returned.  BPTT then runs through the fed-back prediction (the roll-out entry, ``seq_grads``
         implied); on return the slab holds g_t, which ``head_backward(images=(B, T*B), write_dh=False)`` reduces to the
-        head's gradients.  The returned dx is zero on the fed channels of the fed steps: the forward pass overwrote them."""
+        head's gradients.  The returned dx is zero on the fed channels of the fed steps (under a feed mask: of the fed images
+        of each step) -- the forward pass overwrote them."""
         assert ws.train
         fed = bool(ws.feedback.fed)
         if rollout is not None and not ws.feedback.grad:
@@ -880,7 +935,11 @@ class SeqEngine:
                       "unpack dx")
             dx_out = tb.view(ws.T, ws.B, C0, ws.H, ws.W).transpose(0, 1).contiguous()
             if rg is not None:              # the caller's x never reached those channels
-                dx_out[:, ws.feedback.fed.start:, C0 - ws.fb.O:] = 0
+                if ws.feedback.mask is not None:
+                    m = ws.feedback.fed_mask.to(self.device)        # (T*B bytes, a plain copy: the pinned buffer is the next pass's)
+                    dx_out[:, :, C0 - ws.fb.O:].masked_fill_(m.view(ws.B, ws.T, 1, 1, 1), 0)
+                else:
+                    dx_out[:, ws.feedback.fed.start:, C0 - ws.fb.O:] = 0
         return dWs, dbs, dx_out
 
     @staticmethod

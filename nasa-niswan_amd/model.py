@@ -112,6 +112,11 @@ def train_from_rule(x_needs: bool, layer_needs: Sequence[bool]) -> int:
     return next((l for l, need in enumerate(layer_needs) if need), len(layer_needs))
 
 
+_NO_FEEDBACK_GRAD = ("ConvLSTM: back-propagation through the fed-back prediction (free_from < T under grad mode with "
+                     "an input, parameter or state that requires grad) is not implemented; run the closed loop "
+                     "under torch.no_grad(), or train teacher-forced (free_from=None)")
+
+
 class _CallOpts:
     """the non-tensor arguments of _ConvLSTMFn: the device state that comes in (or None), what goes out, the box the outgoing
     device state is handed back in (a Function's outputs are tensors), and the default route's head-backward rule"""
@@ -119,6 +124,8 @@ class _CallOpts:
     def __init__(self, state_in=None, return_state=False, seq_always=False, free_from=None, feedback_grad=False):
         self.state_in, self.return_state, self.state_out = state_in, return_state, None
         self.free_from = free_from      # closed loop from this step on (ConvLSTM(feedback=True)); None: open loop
+        # ... or a (B, T) feed mask (scheduled sampling); `first`: the first step that feeds anything
+        self.first = free_from if free_from is None or isinstance(free_from, int) else Feedback.first_fed(free_from)
         self.feedback_grad = feedback_grad and free_from is not None    # ... and differentiated through what it feeds back (4.19)
         # The default call (no state in, none out) of a return_sequence module ALWAYS takes the per-step head backward
         # (head_backward_seq + BPTT with seq_grads), also when only `pred` has a cotangent; a call with state does so only
@@ -149,7 +156,7 @@ class _ConvLSTMFn(torch.autograd.Function):
         f = train_from_rule(need[3], [any(need[6 + 2 * l:8 + 2 * l]) or (len(st) > 0 and any(need[6 + 2 * L + 2 * l:8 + 2 * L + 2 * l]))
                                       for l in range(L)]) if train else 0
         # a fed step's input depends on every layer of the step before: the gradient passes through all of them
-        rollout = train and opts.feedback_grad and bool(Feedback.steps(opts.free_from, T))
+        rollout = train and opts.feedback_grad and bool(Feedback.steps(opts.first, T))
         if rollout:
             f = 0
         ws = eng.acquire(B, T, H, W, train, has_init, f)
@@ -351,7 +358,7 @@ class ConvLSTM(_EngineOwner, nn.Module):
         inference loops, which drive the engine themselves, do before a forward pass"""
         eng.pack_weights([c.conv.weight for c in self.layers], [c.conv.bias for c in self.layers])
 
-    def forward(self, x, state=None, *, return_state=False, free_from=None, feedback_grad=False):
+    def forward(self, x, state=None, *, return_state=False, free_from=None, feedback_grad=False, free_mask=None):
         """x: (batch_size, sequence_length, channels, height, width)  (model.py:254).
 
         ``state``: None (zeros, model.py:259-262), a list of ``num_layers`` ``(h, c)`` tensor pairs (B, Ch_l, H, W) -- the
@@ -374,7 +381,32 @@ class ConvLSTM(_EngineOwner, nn.Module):
         through the fed-back prediction, the rounding of the fed value taken straight-through.  The forward pass is the same
         one; the backward pass runs time-major with one extra launch per fed step.  The gradient of ``x`` is zero on the
         fed channels of the fed steps.  ``free_from = 0`` under grad stays refused (the first fed value comes from the
-        initial state); with ``free_from >= T`` the flag changes nothing."""
+        initial state); with ``free_from >= T`` the flag changes nothing.
+
+        ``free_mask = M`` (in the place of ``free_from``; the two are exclusive): SCHEDULED SAMPLING -- a
+        bool / uint8 tensor or array of shape (B, T); image b runs step t on its own last prediction where ``M[b, t]`` is set
+        and on ``x`` where it is not.  ``M[b, t] = (t >= s)`` is ``free_from = s`` bit for bit; an all-zero mask is the open
+        loop.  What ``free_from`` refuses is refused here by the first column that feeds anything: column 0 set needs a
+        ``state`` and is forward only; under grad the call needs ``feedback_grad=True``.  The gradient of ``x`` is zero on the
+        fed channels of the fed (b, t) only.  At most 64 images per call."""
+        if free_mask is not None:                       # the refusals of free_from, by the first column with a fed image
+            if free_from is not None:
+                raise ValueError("free_mask and free_from are exclusive: the mask says for every step what free_from says for all")
+            if not self.feedback:
+                raise ValueError("free_mask needs a ConvLSTM built with feedback=True")
+            if len(x.shape) != 5:
+                raise ValueError(f"ConvLSTM: x must be (B, T, C, H, W), got {tuple(x.shape)}")
+            mask = Feedback.mask_bt(free_mask, x.shape[0], x.shape[1])
+            first = Feedback.first_fed(mask)
+            if first == 0 and state is None:
+                raise ValueError("free_mask with column 0 set feeds step 0 from the head of the initial state: pass a state")
+            if first < x.shape[1] and not (feedback_grad and first >= 1) and self._wants_grad(x, state):
+                raise RuntimeError(_NO_FEEDBACK_GRAD)
+            if first < x.shape[1] and x.shape[0] > 64:
+                raise ValueError(f"free_mask: a feed mask holds at most 64 images per call, got B = {x.shape[0]}")
+            free_from = mask if first < x.shape[1] else None         # (nothing fed: the open loop, the call it always was)
+            feedback_grad = feedback_grad and free_from is not None
+            return self._forward(x, state, return_state, free_from, feedback_grad)
         if free_from is not None:                       # every refusal here, before anything is launched (or any device is asked for)
             if not self.feedback:
                 raise ValueError("free_from needs a ConvLSTM built with feedback=True")
@@ -385,13 +417,18 @@ class ConvLSTM(_EngineOwner, nn.Module):
                 raise ValueError(f"ConvLSTM: x must be (B, T, C, H, W), got {tuple(x.shape)}")
             if free_from == 0 and state is None:
                 raise ValueError("free_from=0 feeds step 0 from the head of the initial state: pass a state")
-            if free_from < x.shape[1] and not (feedback_grad and free_from >= 1) and torch.is_grad_enabled() and (
-                    x.requires_grad or any(p.requires_grad for p in self.parameters())
-                    or (state is not None and not isinstance(state, ConvLSTMState)
-                        and any(t.requires_grad for pair in state for t in pair))):
-                raise RuntimeError("ConvLSTM: back-propagation through the fed-back prediction (free_from < T under grad mode with "
-                                   "an input, parameter or state that requires grad) is not implemented; run the closed loop "
-                                   "under torch.no_grad(), or train teacher-forced (free_from=None)")
+            if free_from < x.shape[1] and not (feedback_grad and free_from >= 1) and self._wants_grad(x, state):
+                raise RuntimeError(_NO_FEEDBACK_GRAD)
+        return self._forward(x, state, return_state, free_from, feedback_grad)
+
+    def _wants_grad(self, x, state) -> bool:
+        """grad mode is on and an input, a parameter or a tensor state requires grad"""
+        return torch.is_grad_enabled() and (
+            x.requires_grad or any(p.requires_grad for p in self.parameters())
+            or (state is not None and not isinstance(state, ConvLSTMState) and any(t.requires_grad for pair in state for t in pair)))
+
+    def _forward(self, x, state, return_state, free_from, feedback_grad):
+        """forward() behind its refusals; ``free_from``: None, a step index or a (B, T) uint8 feed mask"""
         _require_cuda(x, "ConvLSTM")
         wb = []
         for cell in self.layers:

@@ -7,7 +7,7 @@ stepped once per epoch before validation, checkpoint every 10 epochs); the per-b
 once per epoch.  Added flags: --dtype, --levels, --grid, --synthetic-steps, --pad-mode, --f32-inputs,
 --static-channels, --sequence-loss, --test-skill, --lat-weighted-loss, --loss-weights, --clip-grad-norm,
 --skip-nonfinite-steps, --stateful, --bptt-segments, --accumulate-steps, --loss-mix, --huber-delta, --output-weights,
---spinup-steps, --rollout-from.
+--spinup-steps, --rollout-from, --sampling-prob, --sampling-ramp-epochs, --sampling-seed.
 
 The data path is on the device too: by default every batch is written by ONE launch of the
 fuse / z-score / halo-pad kernel straight into the model's bf16 input slab (dataset.slab_batch);
@@ -144,6 +144,14 @@ def get_arguments(argv=None, MODEL='LSTM-00', SPECIES='bcb', LEARNING_RATE=1.0E-
                              "its own prediction (the tracer channels of steps >= K are the head's output of the step before) and "
                              "the loss is back-propagated through the fed-back prediction (FusedTrainer(rollout_from=K)).  "
                              "Validation stays teacher-forced.  Not with --stateful, --bptt-segments, --freeze-layers")
+    parser.add_argument("--sampling-prob", type=float, default=None, metavar="P",
+                        help="with --rollout-from K: SCHEDULED SAMPLING -- per training step, per sample and per window step >= K a coin "
+                             "of bias P decides whether the sample sees its own last prediction or the analysis "
+                             "(FusedTrainer(sampling_prob=P)).  1 is plain --rollout-from; 0 is teacher forcing")
+    parser.add_argument("--sampling-ramp-epochs", type=int, default=0, metavar="E",
+                        help="with --sampling-prob P: the probability rises linearly from 0 to P over the first E epochs (set once "
+                             "per epoch, printed with the epoch line); 0: P from the first epoch")
+    parser.add_argument("--sampling-seed", type=int, default=0, help="the coin's seed (each rank draws from seed + rank)")
     parser.add_argument("--reset-optimizer", action="store_true",
                         help="with --use-checkpoint: load the weights of --restore-from only and start the optimizer afresh "
                              "(the fine-tuning entry point; without it an optimizer state of other param groups is an error)")
@@ -169,6 +177,13 @@ def get_arguments(argv=None, MODEL='LSTM-00', SPECIES='bcb', LEARNING_RATE=1.0E-
             parser.error("--rollout-from must be >= 1: step 0 has no prediction to be fed")
         if args.stateful or (args.bptt_segments or 1) > 1 or args.freeze_layers > 0:
             parser.error("--rollout-from is not combined with --stateful, --bptt-segments or --freeze-layers")
+    if args.sampling_prob is not None:
+        if args.rollout_from is None:
+            parser.error("--sampling-prob needs --rollout-from: the coin is thrown for the steps from --rollout-from on")
+        if not 0.0 <= args.sampling_prob <= 1.0:
+            parser.error("--sampling-prob must be a probability in [0, 1]")
+    if args.sampling_ramp_epochs < 0 or (args.sampling_ramp_epochs > 0 and args.sampling_prob is None):
+        parser.error("--sampling-ramp-epochs takes a number of epochs >= 0 and needs --sampling-prob")
     if args.rollout_spinup is None:
         args.rollout_spinup = args.sequence_length
     if args.test_rollout > 0 and args.rollout_spinup < 1:
@@ -186,6 +201,14 @@ def get_arguments(argv=None, MODEL='LSTM-00', SPECIES='bcb', LEARNING_RATE=1.0E-
         with open(os.path.join(args.snapshot_dir, 'configurations.json'), "w") as f:     # train.py:221-225
             json.dump(vars(args), f, indent=4)
     return args
+
+
+def sampling_prob_of(epoch: int, P, ramp_epochs: int):
+    """the coin's bias during epoch `epoch` (0-based): linear from 0 to P over the first `ramp_epochs` epochs, P from then on
+    (and from the first epoch without a ramp); None without --sampling-prob"""
+    if P is None:
+        return None
+    return float(P) if ramp_epochs <= 0 else float(P) * min(epoch / ramp_epochs, 1.0)
 
 
 def build_loss_spec(args):
@@ -267,7 +290,7 @@ def main(args):
                            max_grad_norm=args.clip_grad_norm, skip_nonfinite=args.skip_nonfinite_steps, stateful=args.stateful,
                            bptt_segments=args.bptt_segments, accumulate_steps=args.accumulate_steps, loss=build_loss_spec(args),
                            freeze_layers=args.freeze_layers, weight_decay=args.weight_decay, layer_lr_scale=args.layer_lr_scale,
-                           rollout_from=args.rollout_from)
+                           rollout_from=args.rollout_from, sampling_prob=args.sampling_prob, sampling_seed=args.sampling_seed)
     if args.stateful:
         # one schedule of world * batch lanes, the same every epoch; each rank takes its own columns and carries its own state
         sched, dropped = stateful_schedule(len(train_dataset), args.sequence_length, world * args.batch_size)
@@ -286,6 +309,9 @@ def main(args):
     for epoch in range(1, args.num_epochs + 1):                                              # train.py:82
         generator.train()
         trainer.reset_stats()
+        p_epoch = sampling_prob_of(epoch - 1, args.sampling_prob, args.sampling_ramp_epochs)
+        if p_epoch is not None:
+            trainer.set_sampling_prob(p_epoch)                                               # once per epoch
         torch.cuda.synchronize()
         t_epoch, n_epoch = time.time(), 0
         if args.stateful:
@@ -310,7 +336,8 @@ def main(args):
         logger['r2_score_val'].append(trainer.epoch_stats()[1])
         if rank == 0:
             print(f"Epoch: {epoch}, Loss: {logger['MSELoss'][-1]:.5f}, R2T: {logger['r2_score'][-1]:.5f}, "
-                  f"R2V: {logger['r2_score_val'][-1]:.5f}")                                  # train.py:124
+                  f"R2V: {logger['r2_score_val'][-1]:.5f}"                                   # train.py:124
+                  + ("" if p_epoch is None else f", sampling prob: {p_epoch:.3f}"))
             if guarded:
                 print(f"  grad norm: mean {gstats['mean_norm']:.5f}, max {gstats['max_norm']:.5f}, "
                       f"clipped {gstats['clipped']}, skipped {gstats['skipped']} of {gstats['calls']} steps")

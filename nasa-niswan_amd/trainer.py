@@ -29,6 +29,9 @@
                                                the same fused head / loss pass with its dpred in the roll-out slab, BPTT through
                                                the fed-back prediction (the roll-out entry), then the head's gradients from
                                                the slab (nint_head_bwd_acc over all T*B images)
+    [rollout_from = s, sampling_prob = p]   -> SCHEDULED SAMPLING: per step t >= s and per image a coin of
+                                               bias p decides whether the image sees its own last prediction; the same step
+                                               under that feed mask (the _sampled entries).  p = 1: the line above, call for call
     [accumulate_steps = k]                  -> k micro-batches add into the bucket (accumulate = 1 from the second on); the
                                                all-reduce and ONE Adam launch with grad_scale = 1/(k world) on the k-th
 
@@ -64,7 +67,8 @@ class FusedTrainer:
                  overlap_allreduce: bool = False, sequence_loss: bool = False, loss_weights=None,
                  max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False, stateful: bool = False,
                  bptt_segments: Optional[int] = None, accumulate_steps: int = 1, loss: Optional[LossSpec] = None,
-                 freeze_layers: int = 0, weight_decay: float = 0.0, layer_lr_scale=None, rollout_from: Optional[int] = None):
+                 freeze_layers: int = 0, weight_decay: float = 0.0, layer_lr_scale=None, rollout_from: Optional[int] = None,
+                 sampling_prob: Optional[float] = None, sampling_seed: int = 0):
         # Roll-out training: from step `rollout_from` on the window runs on its own prediction and the loss's gradient flows
         # back through it.  Checked first: these refusals need no device.
         if rollout_from is not None:
@@ -80,6 +84,17 @@ class FusedTrainer:
                                      "the zero state, through every layer, in one call")
             rollout_from = int(rollout_from)
         self.rollout_from = rollout_from
+        # Scheduled sampling: with 0 < p < 1 each step draws a (T, B) feed mask, rows below rollout_from forced
+        # to 0.  None or 1: every image is fed from rollout_from on (the roll-out step itself); 0: the teacher-forced step.  The
+        # draw comes from a CPU generator seeded sampling_seed + rank, made on the first draw (the rank is known once the process
+        # group is): reproducible, and different on every rank.
+        if sampling_prob is not None and rollout_from is None:
+            raise ValueError("sampling_prob needs rollout_from: the coin is thrown for the steps from rollout_from on")
+        self.sampling_prob = None
+        self.set_sampling_prob(sampling_prob)
+        self.sampling_seed = int(sampling_seed)
+        self._sampler, self._last_p = None, None
+        self.last_mask = None   # (T, B) bool, CPU: what the last step() fed; None before the first step and without sampling
         dev = next(model.parameters()).device
         if dev.type != "cuda":
             raise _lib.NintError("FusedTrainer needs the model on the MI355X (cuda)")
@@ -278,6 +293,52 @@ class FusedTrainer:
         for v in views:
             v.masked_fill_(bad, 0)
 
+    def set_sampling_prob(self, p: Optional[float]):
+        """the coin's bias for the steps to come (a curriculum sets it once per epoch); None: no sampling"""
+        if p is not None:
+            if self.rollout_from is None:
+                raise ValueError("sampling_prob needs rollout_from: the coin is thrown for the steps from rollout_from on")
+            if isinstance(p, bool) or not 0.0 <= float(p) <= 1.0:
+                raise ValueError(f"sampling_prob must be a probability in [0, 1], got {p!r}")
+            p = float(p)
+        self.sampling_prob = p
+
+    @staticmethod
+    def draw_mask(gen: torch.Generator, T: int, B: int, rollout_from: int, p: float) -> torch.Tensor:
+        """one step's feed mask, (T, B) bool on the CPU: rand((T, B)) < p, rows t < rollout_from forced to 0.  Pure."""
+        m = torch.rand((T, B), generator=gen) < p
+        m[:rollout_from] = False
+        return m
+
+    @staticmethod
+    def sampler(seed: int, rank: int) -> torch.Generator:
+        """the CPU generator of a rank's draws"""
+        return torch.Generator(device="cpu").manual_seed(int(seed) + int(rank))
+
+    def _draw(self, T: int, B: int):
+        """the feed argument of this step's forward pass: None (nothing fed: the teacher-forced step), rollout_from (every image
+        fed from there on: the roll-out step) or a (B, T) mask"""
+        s = self.rollout_from
+        if s is None or not range(min(s, T), T):
+            return None
+        if self.sampling_prob is None:
+            return s
+        if self.sampling_prob >= 1.0 or self.sampling_prob <= 0.0:
+            # no coin to throw (rand is in [0, 1): < 1 always, < 0 never), and no generator state spent: the roll-out step or the
+            # teacher-forced step, call for call.  The mask is still shown.
+            if self.last_mask is None or tuple(self.last_mask.shape) != (T, B) or self._last_p != self.sampling_prob:
+                self.last_mask = (torch.arange(T) >= (s if self.sampling_prob >= 1.0 else T)).view(T, 1).expand(T, B).clone()
+                self._last_p = self.sampling_prob
+            return s if self.sampling_prob >= 1.0 else None
+        self._last_p = None
+        if self._sampler is None:
+            rank = self.dist.get_rank(self.pg) if self.distributed else 0
+            self._sampler = self.sampler(self.sampling_seed, rank)
+        self.last_mask = self.draw_mask(self._sampler, T, B, s, self.sampling_prob)
+        if bool(self.last_mask[s:].all()):          # (p = 1: every image fed from s on -- the roll-out step, call for call)
+            return s
+        return self.last_mask.t().contiguous() if bool(self.last_mask.any()) else None
+
     def _head_pass(self, eng, ws, yv, B, T, O, H, W, Hc, Wc, wts, acc: bool, spec=None, slab=None):
         """head forward + crop + loss + d loss / d pred + dL/dh + the head's weight gradient on the workspace's last h (every
         h with sequence_loss); `acc`: the head's gradients are added to the bucket (a later micro-batch of a group).
@@ -363,8 +424,8 @@ class FusedTrainer:
             m._pack_weights(eng)
             if carried is not None:
                 eng.load_state(ws, carried)          # carried state -> slot 0
-            fed = self.rollout_from is not None and bool(ws.feedback.steps(self.rollout_from, T))   # (else: the step it was)
-            eng.forward(ws, X, **(dict(feedback=(m.conv.weight, m.conv.bias, self.rollout_from), feedback_grad=True) if fed else {}))
+            feed = self._draw(T, B)     # (None: nothing is fed -- the step it was)
+            eng.forward(ws, X, **(dict(feedback=(m.conv.weight, m.conv.bias, feed), feedback_grad=True) if feed is not None else {}))
             if carried is not None:
                 eng.save_state(ws, carried)          # slot T -> carried state; BPTT below stops at the chunk start
                 self._drop_nonfinite_lanes(carried)

@@ -44,6 +44,12 @@ after the shape.
                 and the frozen regions of the gradient bucket, the weights and both moments bit-unchanged.  The L1 kink
                 (below) is not treated here: a case that lands on it shows as a gradient miss in bf16.  --self-check: the
                 reference's AdamW loses its weight decay; the reference trains the frozen layers too.
+  --sampled     ``ConvLSTM(feedback=True)(x[, state], free_mask=M[, feedback_grad=True])`` (scheduled sampling) with
+                a drawn stack, grid, number of feedback channels, storage type, boundary, input layout, state and (B, T) feed
+                mask of a drawn density.  Forward: bit for bit the open-loop pass over the input with the predictions
+                substituted where the mask says, and against tests/sampled_model.py.  Where no image is fed at step 0: outputs,
+                every parameter gradient and dx under drawn cotangents against the model under CPU autograd.  --self-check:
+                the reference of the first case with a mixed step feeds every image from the first fed step on.
   --self-check  (with one of these modes) after the first passing case to which a fault applies, the REFERENCE is corrupted on
                 the host and the same comparison of the same device results must fail: --state: the oracle gets a zero c0
                 for the last layer; --train-opts with n >= 2: the oracle back-propagates the last segment only (truncated
@@ -103,6 +109,10 @@ STREAM_MODES = NEW_MODES + ("closed_loop",)
 # numbering here: ALL_STREAM_MODES is what case_rng indexes, and no earlier mode's position moves.
 LATE_MODES = ("rollout",)
 ALL_STREAM_MODES = STREAM_MODES + LATE_MODES
+# ... and ALL_STREAM_MODES is pinned in turn (tests/test_rollout_cpu.py).  The modes behind it have a tuple and a stream key of their
+# own (case_rng), so that no earlier mode's draws move.
+SAMPLED_MODES = ("sampled",)
+SAMPLED_KEY = 1000              # the stream key of SAMPLED_MODES[i] is SAMPLED_KEY + i
 LIM = {"f32": 1e-3, "bf16": 3e-2}
 LOSS_LIM = {"f32": 2e-6, "bf16": 2e-2}
 
@@ -248,6 +258,8 @@ def check_head_wgrad(tag, dW, dWo, h_stored, h_oracle, dpred, dpred_oracle=None)
 # ---------------------------------------------------------------------------------------------------- the draw (pure)
 def case_rng(seed: int, mode: str, it: int):
     """the generator of one case of a state / options mode: its own stream, so a case replays without the ones before it"""
+    if mode in SAMPLED_MODES:
+        return np.random.default_rng([int(seed), SAMPLED_KEY + SAMPLED_MODES.index(mode), int(it)])
     return np.random.default_rng([int(seed), 1 + ALL_STREAM_MODES.index(mode), int(it)])
 
 
@@ -264,6 +276,8 @@ def draw_case(rng, it: int, mode: str = "plain", big: bool = False, wide: bool =
         return draw_closed_loop(rng, it)
     if mode == "rollout":
         return draw_rollout(rng, it)
+    if mode == "sampled":
+        return draw_sampled(rng, it)
     new = mode in NEW_MODES
     L = int(rng.integers(1, 5))
     hidden = [int(rng.choice([4, 8, 16, 24, 32, 48, 64] if new else [4, 8, 16, 24, 32, 48, 64, 64, 128])) for _ in range(L)]
@@ -425,6 +439,37 @@ def draw_rollout(rng, it: int) -> dict:
                     f"roll-out from {fb_from} cyclic={int(cyclic)} fold={int(fold)} cotangents={cot}")
 
 
+def draw_sampled(rng, it: int) -> dict:
+    """--sampled: a stack, a grid, O feedback channels, both storage types, cyclic longitude or zero padding, the thin-input fold
+    allowed or off, a tensor state or none, a (B, T) feed mask of a drawn density (column 0 only with a state: then the case is
+    checked forward only) and cotangents on the per-step outputs or on the last one.  Pure."""
+    L = int(rng.integers(1, 4))
+    hidden = [int(rng.choice([4, 8, 16, 24, 32, 64])) for _ in range(L)]
+    ks = [int(rng.choice([1, 3, 3, 5, 5])) for _ in range(L)]
+    C = int(rng.choice([1, 3, 4, 6, 16, 33, 40, 62]))
+    out = min(C, int(rng.choice([1, 1, 2, 3, 20])))
+    B, T = int(rng.integers(1, 5)), int(rng.integers(3, 7))
+    H, W = int(rng.integers(5, 21)), int(rng.integers(9, 41))
+    dtype = "f32" if it % 2 == 0 else "bf16"
+    wave, rows = WAVES[it % 7], TILE_ROWS[it % 4]
+    cyclic, fold, with_state = (bool(rng.integers(0, 2)) for _ in range(3))
+    density = float(rng.choice([0.0, 0.25, 0.5, 0.5, 0.5, 0.75, 0.75, 1.0]))
+    mask = (rng.random((B, T)) < density).astype(int)
+    if not with_state:
+        mask[:, 0] = 0
+    cot = ["seq", "last"][int(rng.integers(0, 2))]
+    draws = [("X", (B, T, C, H, W)), ("dseq", (B, T * out, H, W)), ("dpred", (B, out, H, W))]
+    if with_state:
+        for l, ch in enumerate(hidden):
+            draws += [(f"{n}.{l}", (B, ch, H, W)) for n in ("h0", "c0")]
+    rows_ = "/".join("".join(str(int(v)) for v in r) for r in mask)
+    return dict(it=it, mode="sampled", L=L, hidden=hidden, ks=ks, C=C, out=out, B=B, T=T, H=H, W=W, dtype=dtype, wave=wave,
+                rows=rows, wide=0, cyclic=cyclic, fold=fold, with_state=with_state, density=density, mask=mask.tolist(), cot=cot,
+                draws=draws,
+                tag=f"#{it} C={C} hidden={hidden} k={ks} out={out} B={B} T={T} {H}x{W} {dtype} wave={wave} rows={rows} "
+                    f"sampled mask={rows_} cyclic={int(cyclic)} fold={int(fold)} state={int(with_state)} cotangents={cot}")
+
+
 def draw_data(rng, case) -> dict:
     """the standard-normal tensors of a case, f32, from the generator that drew it"""
     return {name: torch.from_numpy(rng.standard_normal(sh).astype(np.float32)) for name, sh in case["draws"]}
@@ -435,7 +480,7 @@ def draw_cases(seed: int, n: int, mode: str = "plain", big: bool = False, wide: 
     cases = []
     rng = np.random.default_rng(seed)
     for it in range(n):
-        if mode in ALL_STREAM_MODES:
+        if mode in ALL_STREAM_MODES + SAMPLED_MODES:
             cases.append(draw_case(case_rng(seed, mode, it), it, mode))
         else:
             cases.append(draw_case(rng, it, mode, big, wide))
@@ -1061,21 +1106,22 @@ def parse(argv=None):
     ap.add_argument("--finetune", action="store_true", help="two steps of FusedTrainer with a drawn number of frozen layers (0 ... all), weight decay and per-layer lr scales: loss and trained gradients against CPU autograd, the update against torch.optim.AdamW, the frozen regions untouched")
     ap.add_argument("--closed-loop", action="store_true", help="ConvLSTM(feedback=True)(x[, state], free_from=s): the per-step predictions of a drawn stack, grid, number of feedback channels, first fed step, state, storage type, boundary condition and input layout against the CPU model tests/closed_loop_model.py, and bit for bit against the open-loop pass over the input with those predictions substituted")
     ap.add_argument("--rollout", action="store_true", help="ConvLSTM(feedback=True)(x, free_from=F, feedback_grad=True): outputs, every parameter gradient and dx of a drawn stack, grid, number of feedback channels, first fed step F >= 1, storage type, boundary condition, input layout and cotangents (per step, last step, both) against the CPU model tests/rollout_model.py under CPU autograd in f64")
-    ap.add_argument("--self-check", action="store_true", help="with --state / --train-opts / --stateful / --finetune: corrupt the reference after the first passing case and require the comparison to fail")
+    ap.add_argument("--sampled", action="store_true", help="ConvLSTM(feedback=True)(x[, state], free_mask=M[, feedback_grad=True]): a drawn stack, grid, number of feedback channels, storage type, boundary condition, input layout, state and (B, T) feed mask of a drawn density.  Forward: the per-step predictions against the CPU model tests/sampled_model.py and bit for bit against the open-loop pass over the input with those predictions substituted where the mask says.  Without a fed image at step 0: outputs, every parameter gradient and dx under drawn cotangents (per step or last step) against the model under CPU autograd in f64.  --self-check: the reference of the first case with a mixed step is computed as if every image were fed from the first fed step on")
+    ap.add_argument("--self-check", action="store_true", help="with --state / --train-opts / --stateful / --finetune / --sampled: corrupt the reference after the first passing case and require the comparison to fail")
     ap.add_argument("--guarded", action="store_true", help="every mode: the device side of each case allocates through oracle/guarded_alloc.py in poison mode (guards around every buffer, `empty` payloads 0xFF), its inputs and parameters in arenas of their own; the comparison stays what it is and every guard byte is checked after each case.  With --self-check (any mode): one guard byte is flipped after the first passing case and the check has to fail (the reference is then not corrupted)")
     ap.add_argument("--list", action="store_true", help="print the drawn cases as JSON lines and exit (no GPU, the package is not imported)")
     ap.add_argument("--only", type=int, default=-1, help="replay the random stream up to this iteration and run it alone, printing every tensor's error")
     ap.add_argument("--force-wave", type=int, default=None, help="with --only: nint_seq.wave for the replayed case instead of the rotation's value")
     ap.add_argument("--force-dtype", choices=["f32", "bf16"], default=None, help="with --only: the storage type of the replayed case instead of the alternation's (is the miss the arithmetic's, or the storage type's?)")
     args = ap.parse_args(argv)
-    modes = [m for m in ("dataset", "cell", "trainer", "state", "train_opts", "stateful", "finetune", "closed_loop", "rollout") if getattr(args, m)]
+    modes = [m for m in ("dataset", "cell", "trainer", "state", "train_opts", "stateful", "finetune", "closed_loop", "rollout", "sampled") if getattr(args, m)]
     if len(modes) > 1 and not all(m in OLD_MODES for m in modes):
-        ap.error("one of --state / --train-opts / --stateful / --finetune / --closed-loop / --rollout at a time, and none of the other modes with it")
+        ap.error("one of --state / --train-opts / --stateful / --finetune / --closed-loop / --rollout / --sampled at a time, and none of the other modes with it")
     args.mode = modes[0] if modes else "plain"          # (--dataset before --cell before --trainer, as ever)
-    if args.mode in ("closed_loop", "rollout") and (args.big or args.wide):
-        ap.error("--closed-loop / --rollout draw their own shapes: not with --big / --wide")
-    if args.self_check and args.mode not in NEW_MODES and not args.guarded:
-        ap.error("--self-check needs --state, --train-opts, --stateful or --finetune (or --guarded)")
+    if args.mode in ("closed_loop", "rollout", "sampled") and (args.big or args.wide):
+        ap.error("--closed-loop / --rollout / --sampled draw their own shapes: not with --big / --wide")
+    if args.self_check and args.mode not in NEW_MODES + SAMPLED_MODES and not args.guarded:
+        ap.error("--self-check needs --state, --train-opts, --stateful, --finetune or --sampled (or --guarded)")
     # --guarded --self-check is the guard's own self-check; the reference stays what it is
     args.guard_self_check = args.self_check and args.guarded
     if args.guard_self_check:
@@ -1355,9 +1401,86 @@ def rollout_run(case, d, args, worst):
     print(f"ok   {tag}  worst {w:.2e}", flush=True)
 
 
+def sampled_run(case, d, args, worst, tried):
+    """--sampled: one case on the device against tests/sampled_model.py.  Forward (always, under no_grad): the fed value rounded
+    to the storage type, and the bit contract.  Gradients (no fed image at step 0): f64 under CPU autograd, the fed value
+    rounded to f32 and passed straight through.  ``tried`` (--self-check): "full_mask" once the fault has been tried."""
+    tdir = os.path.join(ROOT, "tests")
+    if tdir not in sys.path:
+        sys.path.insert(0, tdir)
+    import sampled_model as SM
+    tag, dtype = case["tag"], case["dtype"]
+    C, out, B, T, L, H, W = case["C"], case["out"], case["B"], case["T"], case["L"], case["H"], case["W"]
+    fed = torch.tensor(case["mask"], dtype=torch.bool)
+    params = O.synth_params(C, case["hidden"], case["ks"], L, out_channels=out, seed=case["it"])
+    net = pkg.ConvLSTM(C, case["hidden"], case["ks"], L, out_channels=out, compute_dtype=dtype, lon_cyclic=case["cyclic"],
+                       feedback=True, return_sequence=True)
+    net.load_state_dict(params)
+    net = _net(net)
+    old_fold, engine.XFOLD = engine.XFOLD, case["fold"]
+    try:
+        net._engine(torch.device("cuda", torch.cuda.current_device()))
+    finally:
+        engine.XFOLD = old_fold
+    state = [(d[f"h0.{l}"], d[f"c0.{l}"]) for l in range(L)] if case["with_state"] else None
+    dev_state = None if state is None else [(_dev(h), _dev(c)) for h, c in state]
+    p64 = {k: v.double() for k, v in params.items()}
+    kw = dict(h0=[h.double() for h, _ in state], c0=[c.double() for _, c in state]) if state is not None else {}
+    X = _dev(d["X"])
+    with torch.no_grad():
+        pred, seq = net(X, dev_state, free_mask=fed)
+        # bit contract: the open-loop pass over the input that holds, where the mask says, the predictions of the step before
+        X2 = X.clone()
+        sv = seq.view(B, T, out, H, W)
+        if bool(fed[:, 0].any()):
+            eng = next(iter(net._engines.values()))
+            with eng.window(B, T, H, W, False, True) as ws:
+                eng.load_state(ws, eng.state_from_tensors(dev_state))
+                p0 = eng.head_forward(ws, net.conv.weight, net.conv.bias, slot=0)
+        for b in range(B):
+            for t in range(T):
+                if bool(fed[b, t]):
+                    X2[b, t, C - out:] = sv[b, t - 1] if t > 0 else p0[b]
+        pred2, seq2 = net(X2, dev_state)
+    torch.cuda.synchronize()
+    assert torch.equal(seq, seq2) and torch.equal(pred, pred2), (tag, "the masked pass differs from the open loop on the substituted input")
+    ref = SM.forward(d["X"].double(), p64, fed, cyclic=case["cyclic"], storage=dtype, **kw)
+    w = compare(tag, dtype, dict(pred=pred.cpu(), seq=seq.cpu()), dict(pred=ref["pred"], seq=ref["seq"]), args.only >= 0)
+    if not bool(fed[:, 0].any()):
+        # (the drawn cotangents get a mean, as in --rollout)
+        dseq = d["dseq"] + 0.5 if case["cot"] == "seq" else None
+        dpred = d["dpred"] + 0.5 if case["cot"] == "last" else None
+        Xg = _dev(d["X"]).requires_grad_(True)
+        pred, seq = net(Xg, dev_state, free_mask=fed, feedback_grad=True)
+        outs, cots = zip(*[(o, _dev(c)) for o, c in ((pred, dpred), (seq, dseq)) if c is not None])
+        torch.autograd.backward(list(outs), list(cots))
+        torch.cuda.synchronize()
+        fedc = fed.view(B, T, 1, 1, 1).expand(B, T, out, H, W)
+        assert not bool(Xg.grad.cpu()[:, :, C - out:][fedc].any()), (tag, "a gradient on the fed channels of a fed image")
+        res = dict(pred=pred.detach().cpu(), seq=seq.detach().cpu(), dx=Xg.grad.cpu())
+        for k, p in net.named_parameters():
+            res["d." + k] = p.grad.cpu()
+
+        def against(mask):
+            r = SM.grads(d["X"].double(), p64, mask, case["cyclic"], "f32", dpred, dseq, **kw)
+            want = dict(pred=r["pred"], seq=r["seq"], dx=r["dx"])
+            for k in p64:
+                want["d." + k] = r["params"][k]
+            return compare(tag, dtype, res, want, args.only >= 0)
+        w = max(w, against(fed))
+        any_t = fed.any(dim=0)
+        mixed = bool((any_t & ~fed.all(dim=0)).any())
+        if args.self_check and mixed and not tried.get("full_mask"):
+            first = int(any_t.to(torch.uint8).argmax())
+            expect_failure(tag, "the reference feeds every image from the first fed step on", lambda: against(SM.suffix(B, T, first)))
+            tried["full_mask"] = True
+    worst[dtype] = max(worst[dtype], w)
+    print(f"ok   {tag}  worst {w:.2e}", flush=True)
+
+
 def main(argv=None):
     args = parse(argv)
-    new = args.mode in ALL_STREAM_MODES
+    new = args.mode in ALL_STREAM_MODES + SAMPLED_MODES
     if args.list:
         for case in draw_cases(args.seed, args.n, args.mode, args.big, args.wide):
             print(json.dumps(case), flush=True)
@@ -1394,6 +1517,8 @@ def main(argv=None):
                     closed_loop_run(case, d, args, worst)
                 elif args.mode == "rollout":
                     rollout_run(case, d, args, worst)
+                elif args.mode == "sampled":
+                    sampled_run(case, d, args, worst, tried)
                 elif new:
                     run_new(case, d, args, worst, tried)
                 else:
@@ -1401,7 +1526,8 @@ def main(argv=None):
         finally:
             engine.FORCE_WAVE, engine.FORCE_TILE_ROWS, engine.FORCE_WIDE = None, 0, 0
     if args.self_check:
-        want = {"state": ["zero_c0"], "train_opts": ["truncate", "drop"], "stateful": ["reset"], "finetune": ["no_decay", "unfrozen"]}[args.mode]
+        want = {"state": ["zero_c0"], "train_opts": ["truncate", "drop"], "stateful": ["reset"], "finetune": ["no_decay", "unfrozen"],
+                "sampled": ["full_mask"]}[args.mode]
         missing = [f for f in want if not tried.get(f)]
         if missing:
             raise SystemExit(f"SELF-CHECK INCOMPLETE: no drawn case to try {missing} on (raise --n or change the seed)")

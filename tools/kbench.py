@@ -75,7 +75,7 @@ def main():
             return
         ms = timeit(fn, args.iters)
         extra = f"{flops / ms / 1e9:8.1f} TFLOP/s" if flops else (f"{bytes_ / ms / 1e6:8.1f} GB/s" if bytes_ else "")
-        print(f"{name:12s} {ms * 1e3:9.1f} us  {extra}", flush=True)
+        print(f"{name:22s} {ms * 1e3:9.1f} us  {extra}", flush=True)
         rows.append((name, ms))
 
     for l, cfg in enumerate(cfgs):
@@ -150,7 +150,8 @@ def main():
         alg = B * T * args.C * H * W
         run("preproc_slab", lambda: sb.fill_slab(eng, ws), None, alg * (4 + es))     # 4 B in + ET out per element
         run("preproc_nchw", lambda: ds.device_batch(idx), None, alg * 8)
-    if not only or only & {"head_skill", "skill_plain", "head_fwd", "head_feedback", "head_feedback_bwd", "head_loss", "head_loss_spec", "head_loss_spec3"}:
+    if not only or only & {"head_skill", "skill_plain", "head_fwd", "head_feedback", "head_feedback_bwd", "head_feedback_sel",
+                           "head_feedback_sel1", "head_feedback_bwd_sel", "head_feedback_bwd_sel1", "head_loss", "head_loss_spec", "head_loss_spec3"}:
         # evaluation: the head on the last step's images + crop + the f64 skill sums in one pass (nint_head_skill_accum), and the
         # same sums from a prediction in memory (nint_skill_accum), one slot, cos-latitude row weights
         O, oy, ox = args.O, 5, 5
@@ -224,7 +225,26 @@ def main():
             def head_feedback_bwd():
                 assert lib.nint_head_feedback_bwd(P(fdx), 0, P(fdp), 0, P(fdh), 0, B, ly.Ch, ly.Chp, O, P(hw), args.C, l0.Cxp, c0, kf,
                                                   int(eng.lon_cyclic), g, eng.dt, st) == 0
-            run("head_feedback_bwd", head_feedback_bwd, None, B * comp_px * (lines * 64 + 2 * O * 4 + ly.Chp * es))
+            fbb_bytes = lambda n_fed: comp_px * (n_fed * (lines * 64 + 2 * O * 4) + (B - n_fed) * O * 4 + B * ly.Chp * es)
+            run("head_feedback_bwd", head_feedback_bwd, None, fbb_bytes(B))
+            # scheduled sampling: the masked instantiations under a half-set mask (every other image fed) and,
+            # `1`, under an all-ones mask -- the same work as the unmasked rows above
+            import numpy as np
+            half, ones = np.arange(B, dtype=np.uint8) % 2, np.ones(B, np.uint8)
+            nh = int(half.sum())
+
+            def head_feedback_sel(m=half):
+                assert lib.nint_head_feedback_sel(P(ws.h[-1]), B, B, ly.Ch, ly.Chp, O, P(hw), P(hb), P(ws.xs), B, args.C, l0.Cxp,
+                                                  args.C - O, kf, int(eng.lon_cyclic), m.ctypes.data, g, eng.dt, st) == 0
+
+            def head_feedback_bwd_sel(m=half):
+                assert lib.nint_head_feedback_bwd_sel(P(fdx), 0, P(fdp), 0, P(fdh), 0, B, ly.Ch, ly.Chp, O, P(hw), args.C, l0.Cxp, c0, kf,
+                                                      int(eng.lon_cyclic), m.ctypes.data, g, eng.dt, st) == 0
+            if B <= 64:
+                run("head_feedback_sel", head_feedback_sel, None, nh * comp_px * (ly.Chp + max(kf, 1) * O) * es)
+                run("head_feedback_sel1", lambda: head_feedback_sel(ones), None, B * comp_px * (ly.Chp + max(kf, 1) * O) * es)
+                run("head_feedback_bwd_sel", head_feedback_bwd_sel, None, fbb_bytes(nh))
+                run("head_feedback_bwd_sel1", lambda: head_feedback_bwd_sel(ones), None, fbb_bytes(B))
         run("head_skill", head_skill, None, B * Hc * Wc * ly.Chp * es + maps)
         run("skill_plain", skill_plain, None, B * O * Hc * Wc * 4 + maps)
     tot = sum(ms * (T if not n.startswith(("wgrad", "pack", "preproc")) else 1) for n, ms in rows

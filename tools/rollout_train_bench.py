@@ -8,6 +8,8 @@ hidden 64/32/16, k 5/3/3, 100 x 144 cyclic, T = 12, B = 8, bf16, C = 62 + 20, O 
        prediction, the head's gradients from the slab, Adam
   (b)  the teacher-forced step of the same shape planned as (a)'s BPTT is: time-major, all-classic (FUSE_BWD = 1, FORCE_WAVE = 0)
   (c)  the default teacher-forced step
+  --sampling-prob P [P ...]: (s) FusedTrainer(rollout_from=s, sampling_prob=P).step for every P: a fresh
+       feed mask per step.  P = 1 is (a), call for call
 
 Expectation to check, not a gate: (a) is (b) plus T - s feedback launches forward, T - s backward launches and the x columns
 of layer 0's dgrad at the fed steps.  Every variant is warmed up, then timed with device events over --iters steps; the
@@ -49,6 +51,7 @@ def main():
     ap.add_argument("--ks", default="5,3,3")
     ap.add_argument("--rollout-from", type=int, default=1)
     ap.add_argument("--sequence-loss", action="store_true")
+    ap.add_argument("--sampling-prob", type=float, nargs="*", default=[], help="also time the scheduled-sampling step at these probabilities")
     ap.add_argument("--zero-pad", action="store_true", help="zero padding instead of cyclic longitude")
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--iters", type=int, default=10)
@@ -83,6 +86,9 @@ def main():
 
     variants = [("(a) roll-out step", lambda: tr_a.step(X, y)), ("(b) teacher-forced, time-major all-classic", classic),
                 ("(c) teacher-forced, default plan", lambda: tr_c.step(X, y))]
+    for p in args.sampling_prob:
+        tr_s = trainer(rollout_from=s, sampling_prob=p, sampling_seed=0)
+        variants.append((f"(s) scheduled sampling, p = {p:g}", lambda tr_s=tr_s: tr_s.step(X, y)))
     for _, fn in variants:                         # warm-up: every shape and code object the timed windows use
         for _ in range(3):
             fn()
