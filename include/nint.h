@@ -424,6 +424,24 @@ int nint_seq_fwd_sampled(const nint_seq* s /*host*/, const nint_feedback* fb /*h
 int nint_seq_bwd_rollout_sampled(const nint_seq* s /*host*/, const nint_feedback* fb /*host*/, const nint_feedback_mask* fm /*host*/,
                                  const nint_feedback_grad* rg /*host*/, void* stream);
 
+/* The two _sampled entries for the RESIDUAL HEAD: p_t = x_t[feedback channels] + head(h_t), x_t as the model
+ * saw it -- on a teacher-forced step what the caller packed, on a fed step round_ET(p_{t-1}).  They ARE nint_seq_fwd_sampled
+ * and nint_seq_bwd_rollout_sampled (fm == NULL or fm->fed == NULL: "use fb->from") with the residual feedback launches in the
+ * same places of the same plan: same launch list, same `index` numbering of the debug plans, same wrap launches.
+ *   forward   the feedback launch of step t reads its base from block t-1 of xs (nint_head_feedback_res): the fed value is
+ *             round_ET( head(h after step t-1) + x_{t-1}[feedback channels] ).  So the pass equals, bit for bit, the open-loop
+ *             pass over an input that already holds the fed values, and its per-step outputs are nint_head_fwd_seq_res of it.
+ *   backward  the feedback backward launch of step u (nint_head_feedback_bwd_res) also adds g_u, final in dpred block u:
+ *             g_{u-1}[b] = l_{u-1}[b] + fed[u][b] * (xi_u[b] + g_u[b]), dh_seq block u-1 = W^T g_{u-1}.  dpred comes back
+ *             holding the total cotangent g_t of every p_t; the caller adds it to its d/dx on the feedback channels of
+ *             the unfed (t, b) -- the skip path into its own input -- and zeroes the fed ones, as before.
+ * Additionally refused with NINT_E_ARG, before any launch, where the feedback is looked at: a fed image at step 0 -- p_{-1}
+ * has no base, even with an initial state.  fb->O == 0 or nothing fed: the open-loop entries, as ever. */
+int nint_seq_fwd_residual(const nint_seq* s /*host*/, const nint_feedback* fb /*host*/, const nint_feedback_mask* fm /*host*/,
+                          void* stream);
+int nint_seq_bwd_rollout_residual(const nint_seq* s /*host*/, const nint_feedback* fb /*host*/, const nint_feedback_mask* fm /*host*/,
+                                  const nint_feedback_grad* rg /*host*/, void* stream);
+
 /* The launch plan of a pass, for tests and tools (host only: nothing is enqueued, no pointer is dereferenced).  Both drivers
  * first PLAN a pass into an ordered list of launches and then enqueue that list; this entry runs the same argument checks and
  * the same planner as nint_seq_fwd (bwd = 0) / nint_seq_bwd (bwd = 1: the BPTT chain, without the weight-gradient
@@ -582,6 +600,49 @@ int nint_head_feedback_sel(const void* h_slab, int n0, int N, int Ch, int Chp, i
 int nint_head_feedback_bwd_sel(const void* dx, int dx_n0, float* dpred, int p_n0, void* dh, int dh_n0, int N, int Ch, int Chp,
                                int O, const float* w, int Cx, int Cxp, int c0, int xfold_k, int lon_cyclic,
                                const uint8_t* fed /*host, N bytes*/, const nint_geom* g, int dtype, void* stream);
+/* ---- RESIDUAL HEAD: the head predicts the tracer's tendency ------------------------------------------------
+ * p = fl32( d + base ): d is the staged head's f32 dot product as defined above (accumulator from b[o], same order, same fused /
+ * unfused tail), base the value STORED in the input halo slab xs at the pixel's feedback channel c0 + o, converted to f32 exactly
+ * (a bf16 value is exact in f32).  A horizontally folded slab (nint_layer.xfold) is read at the pixel's own copy, slab channel
+ * (k/2)*Cx + c0 + o.  ONE f32 add behind the dot product; the base never enters the accumulator.  Everything downstream -- the
+ * loss, d loss / d pred, dL/dh, the value fed to the next step -- sees p.  The base is read from interior pixels only: no halo,
+ * no slack, no pad channel, and nothing of xs but the O channels of every pixel the twin's body visits.
+ * Every _res entry below takes its twin's arguments, runs its twin's body (ONE body per kernel: the operand is a template
+ * parameter of it, and the instantiation without a base is the kernel the twin has always launched) and makes its twin's checks
+ * in its twin's order, then the base's: NINT_E_ARG for x_n0 < 0, Cx < 1, c0 < 0 or c0 + O > Cx, xfold_k negative or even, Cxp
+ * below Cx (xfold_k * Cx for a folded slab) or a pixel of Cxp elements that is no multiple of 16 bytes; NINT_E_ALIGN for an xs
+ * that is not 16-byte aligned.  The memory contracts are the twins': no kernel stores anywhere its twin does not.
+ * The twins themselves are the _res entries with a NULL base.
+ * Gradients (straight-through, as in nint_seq_bwd_rollout): d p / d d = 1, so dpred, dh = W^T dpred, dw and db are formed from
+ * the same dpred by the same entries; d p / d base = 1, which is the caller's to add where the base was its own input
+ * (SeqEngine.backward) and nint_head_feedback_bwd_res's where the base was a fed value. */
+typedef struct nint_head_base {   /* host; xs == NULL (or a NULL pointer to the struct): no base -- the twin entry, bit for bit */
+  const void* xs;                 /* ET input halo slab */
+  int32_t x_n0;                   /* image of xs that pairs with the first head image (SEQ entries: image t*B + b pairs with h slot t+1) */
+  int32_t Cx, Cxp, c0, xfold_k;   /* as in nint_head_feedback */
+} nint_head_base;
+/* nint_head_fwd / nint_head_fwd_seq with the base added.  Staged heads only: where the rule above the head entries does not
+ * hold, the generic wide kernels have no residual form and the entry returns NINT_E_SHAPE before any launch (with a base). */
+int nint_head_fwd_res(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w, const float* b, float* pred,
+                      const nint_geom* g, int dtype, const nint_head_base* base /*host*/, void* stream);
+int nint_head_fwd_seq_res(const void* h_slab, int B, int T, int Ch, int Chp, int O, const float* w, const float* b, float* seq,
+                          const nint_geom* g, int dtype, const nint_head_base* base /*host*/, void* stream);
+/* nint_head_feedback[_sel] with the base: image x_n0 + i of xs receives round_ET( dot + base ), the base read from image
+ * base_n0 + i of the same slab (the step before), the same pixel's own channel as above.  base_n0 < 0: no base.  fed (HOST, N
+ * bytes): NULL = every image, else the mask of nint_head_feedback_sel (its checks, its behaviour: N <= 64, an unfed image keeps
+ * every byte, no image fed = no launch).  The base is gathered by the thread that forms the pixel's dot products, in the pass
+ * that loads h: no second sweep over the row.  Checks: nint_head_feedback's, then NINT_E_ARG where the images
+ * [base_n0, base_n0 + N) and [x_n0, x_n0 + N) overlap, then the mask's. */
+int nint_head_feedback_res(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w, const float* b,
+                           void* xs_slab, int x_n0, int Cx, int Cxp, int c0, int xfold_k, int lon_cyclic, int base_n0,
+                           const uint8_t* fed /*host, NULL = every image*/, const nint_geom* g, int dtype, void* stream);
+/* nint_head_feedback_bwd[_sel] with the skip term: on a fed image g = fl32( fl32(dpred + xi) + dpred[pnext_n0 + i] ), stored
+ * back and handed to the dh body; an unfed image as in nint_head_feedback_bwd_sel.  The images [pnext_n0, pnext_n0 + N) of the
+ * dpred slab -- the total cotangent of the fed step's own prediction -- are read, never written, and must lie apart from
+ * [p_n0, p_n0 + N) (else NINT_E_ARG).  pnext_n0 < 0: no such term.  fed: as above (a mask of zeros is legal). */
+int nint_head_feedback_bwd_res(const void* dx, int dx_n0, float* dpred, int p_n0, void* dh, int dh_n0, int N, int Ch, int Chp,
+                               int O, const float* w, int Cx, int Cxp, int c0, int xfold_k, int lon_cyclic, int pnext_n0,
+                               const uint8_t* fed /*host, NULL = every image*/, const nint_geom* g, int dtype, void* stream);
 /* dseq (B, T*O, H, W) and dpred_last (B, O, H, W: the cotangent of pred = head(h_{T-1}), added to step T-1 inside the
  * kernels); either may be NULL, not both.  dh_seq: compact ET [T*B][H][W][Chp], image t*B+b, padding channels zero
  * (nint_seq.dh_seq; may be NULL: not written); dw (O,Ch), db (O): summed over all T*B images in a fixed order (overwritten;
@@ -716,6 +777,19 @@ int nint_head_loss_seq_fused_spec(const void* h_slab, int B, int T, int Ch, int 
                                   const float* y, const float* wgt, double wsum, const nint_loss_spec* spec, float* dpred,
                                   void* dh_seq, float* loss_out, double* stats, const nint_geom* g, int oy, int ox, int Hc,
                                   int Wc, int dtype, void* stream);
+/* The two fused _spec entries for the RESIDUAL HEAD (nint_head_base above): the same pass with p = dot + base in the place of
+ * the dot product -- the loss, d loss / d pred and dL/dh = W^T dpred are formed from it; bit-identical to
+ * nint_head_fwd[_seq]_res -> nint_loss_crop_spec -> nint_head_bwd[_seq].  They keep the optional map and the spec and always
+ * run the general body; the plain and _weighted forms need no residual twin (the default spec reproduces their bits).  Checks:
+ * the _spec entry's in its order, then the base's.  A NULL base (or xs): the _spec entry, which calls these. */
+int nint_head_loss_fused_res(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w, const float* b,
+                             const float* y, const float* wgt, double wsum, const nint_loss_spec* spec, float* dpred, void* dh,
+                             float* loss_out, double* stats, const nint_geom* g, int oy, int ox, int Hc, int Wc, int dtype,
+                             const nint_head_base* base /*host*/, void* stream);
+int nint_head_loss_seq_fused_res(const void* h_slab, int B, int T, int Ch, int Chp, int O, const float* w, const float* b,
+                                 const float* y, const float* wgt, double wsum, const nint_loss_spec* spec, float* dpred,
+                                 void* dh_seq, float* loss_out, double* stats, const nint_geom* g, int oy, int ox, int Hc,
+                                 int Wc, int dtype, const nint_head_base* base /*host*/, void* stream);
 
 /* ---- evaluation: skill sums (test.ipynb:377-385, :462-485, :605, :630, :684-693, :796-803) ------------ */
 /* Everything the analysis notebook derives from the gathered test-period predictions -- one R2 per window, one R2 per grid

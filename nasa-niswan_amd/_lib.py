@@ -68,6 +68,12 @@ class NintFeedbackMask(C.Structure):
     _fields_ = [("fed", vp)]
 
 
+class NintHeadBase(C.Structure):
+    """nint_head_base: the residual head's base operand (the _res head entries) -- the input halo slab, the image that pairs with
+    the first head image, and where the feedback channels lie in a pixel; xs NULL: no base"""
+    _fields_ = [("xs", vp), ("x_n0", C.c_int32), ("Cx", C.c_int32), ("Cxp", C.c_int32), ("c0", C.c_int32), ("xfold_k", C.c_int32)]
+
+
 class NintLaunchRec(C.Structure):
     """nint_launch_rec: one conv / pointwise problem of a planned pass (nint_debug_seq_plan)"""
     _fields_ = [(n, C.c_int32) for n in ("index", "bwd", "op", "layer", "t", "kernel", "dtype", "epi", "wn", "wk", "ntw", "mt",
@@ -112,6 +118,7 @@ _POG = C.POINTER(NintOptGroup)
 _PFB = C.POINTER(NintFeedback)
 _PFG = C.POINTER(NintFeedbackGrad)
 _PFM = C.POINTER(NintFeedbackMask)
+_PHB = C.POINTER(NintHeadBase)
 SIGNATURES = {
     "nint_version": (_I, []),
     "nint_error_string": (C.c_char_p, [_I]),
@@ -151,6 +158,8 @@ SIGNATURES = {
     "nint_debug_seq_plan_rollout": (_I, [_PS, _PFB, C.POINTER(NintLaunchRec), _I]),
     "nint_seq_fwd_sampled": (_I, [_PS, _PFB, _PFM, vp]),
     "nint_seq_bwd_rollout_sampled": (_I, [_PS, _PFB, _PFM, _PFG, vp]),
+    "nint_seq_fwd_residual": (_I, [_PS, _PFB, _PFM, vp]),
+    "nint_seq_bwd_rollout_residual": (_I, [_PS, _PFB, _PFM, _PFG, vp]),
     "nint_debug_seq_plan_sampled": (_I, [_PS, _PFB, _PFM, _I, C.POINTER(NintLaunchRec), _I]),
     "nint_debug_multi_carrier": (_I, [C.POINTER(C.c_int32), _I, _I]),
     "nint_debug_wgrad_plan": (_I, [_PL, _PG, _I, _I, _I, _I, C.POINTER(NintWgradPlanRec)]),
@@ -159,6 +168,10 @@ SIGNATURES = {
     "nint_head_feedback_bwd": (_I, [vp, _I, vp, _I, vp, _I, _I, _I, _I, _I, vp, _I, _I, _I, _I, _I, _PG, _I, vp]),
     "nint_head_feedback_sel": (_I, [vp, _I, _I, _I, _I, _I, vp, vp, vp, _I, _I, _I, _I, _I, _I, vp, _PG, _I, vp]),
     "nint_head_feedback_bwd_sel": (_I, [vp, _I, vp, _I, vp, _I, _I, _I, _I, _I, vp, _I, _I, _I, _I, _I, vp, _PG, _I, vp]),
+    "nint_head_fwd_res": (_I, [vp, _I, _I, _I, _I, _I, vp, vp, vp, _PG, _I, _PHB, vp]),
+    "nint_head_fwd_seq_res": (_I, [vp, _I, _I, _I, _I, _I, vp, vp, vp, _PG, _I, _PHB, vp]),
+    "nint_head_feedback_res": (_I, [vp, _I, _I, _I, _I, _I, vp, vp, vp, _I, _I, _I, _I, _I, _I, _I, vp, _PG, _I, vp]),
+    "nint_head_feedback_bwd_res": (_I, [vp, _I, vp, _I, vp, _I, _I, _I, _I, _I, vp, _I, _I, _I, _I, _I, _I, vp, _PG, _I, vp]),
     "nint_head_bwd": (_I, [vp, _I, _I, _I, _I, _I, vp, vp, vp, vp, vp, _PG, _I, vp, _SZ, vp]),
     "nint_head_bwd_acc": (_I, [vp, _I, _I, _I, _I, _I, vp, vp, vp, vp, vp, _I, _PG, _I, vp, _SZ, vp]),
     "nint_head_fwd_seq": (_I, [vp, _I, _I, _I, _I, _I, vp, vp, vp, _PG, _I, vp]),
@@ -173,6 +186,8 @@ SIGNATURES = {
     "nint_loss_crop_spec": (_I, [vp, vp, vp, _D, _PLS, vp, vp, vp, _I, _I, _I, _I, _I, _I, _I, _I, vp]),
     "nint_head_loss_fused_spec": (_I, [vp, _I, _I, _I, _I, _I, vp, vp, vp, vp, _D, _PLS, vp, vp, vp, vp, _PG, _I, _I, _I, _I, _I, vp]),
     "nint_head_loss_seq_fused_spec": (_I, [vp, _I, _I, _I, _I, _I, vp, vp, vp, vp, _D, _PLS, vp, vp, vp, vp, _PG, _I, _I, _I, _I, _I, vp]),
+    "nint_head_loss_fused_res": (_I, [vp, _I, _I, _I, _I, _I, vp, vp, vp, vp, _D, _PLS, vp, vp, vp, vp, _PG, _I, _I, _I, _I, _I, _PHB, vp]),
+    "nint_head_loss_seq_fused_res": (_I, [vp, _I, _I, _I, _I, _I, vp, vp, vp, vp, _D, _PLS, vp, vp, vp, vp, _PG, _I, _I, _I, _I, _I, _PHB, vp]),
     "nint_skill_scratch_bytes": (_SZ, [_I, _I, _I, _I]),
     "nint_skill_accum": (_I, [vp, vp, C.POINTER(C.c_int32), _I, vp, vp, vp, vp, _SZ, _I, _I, _I, _I, _I, _I, _I, _I, vp]),
     "nint_head_skill_accum": (_I, [vp, _I, _I, _I, _I, _I, vp, vp, vp, C.POINTER(C.c_int32), _I, vp, vp, vp, vp, vp, _SZ, _PG,

@@ -94,10 +94,25 @@ __device__ __forceinline__ size_t head_image(size_t n, int Bs, int T) {
   else return n;
 }
 
-template <int DT, int CHV, bool SEQ>
+// RESIDUAL HEAD (nint_head_base, nint.h): p = fl32(d + base), d the staged dot product above and base the value
+// STORED in the input slab xs at the pixel's feedback channel c0 + o (a folded slab: the pixel's own copy, slab channel
+// (k/2)*Cx + c0 + o), converted to f32 exactly.  One rounded add behind the dot product: the base never enters the accumulator.
+// The bodies below take the operand as a trailing pack `Base...` that is empty (the kernel as it was: same arguments, same
+// instruction stream) or one HeadBaseK; the loss body finds it in its element (LossSpecRes).  The base of a pixel is read where
+// the pixel's h record is: interior pixels only, the O channels from `c`, nothing else of xs.
+struct HeadBaseK { const void* xs; int n0, Cxp, c; };     // image n0 of xs pairs with the body's first image; c: first slab channel read
+__device__ __forceinline__ size_t head_base_at(const HeadBaseK& k, size_t n, int y, int x, int P, int Hh, int Wh) {
+  return ((((size_t)k.n0 + n) * Hh + (y + P)) * Wh + (x + P)) * k.Cxp + k.c;
+}
+__device__ __forceinline__ float head_add_base(float d, float base) {
+#pragma clang fp contract(off)
+  return d + base;
+}
+
+template <int DT, int CHV, bool SEQ, class... Base>
 __device__ __forceinline__ void head_fwd_body(float* w_s, const void* __restrict__ h, int n0, int N, int Ch, int Chp, int O,
                                               const float* __restrict__ w, const float* __restrict__ b,
-                                              float* __restrict__ pred, int H, int W, int P, int Hh, int Wh, int Bs) {
+                                              float* __restrict__ pred, int H, int W, int P, int Hh, int Wh, int Bs, const Base... base) {
   head_stage_weights<CHV>(w_s, w, O, Ch);
   const size_t npix = (size_t)N * H * W;
   const size_t pix = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
@@ -114,15 +129,23 @@ __device__ __forceinline__ void head_fwd_body(float* w_s, const void* __restrict
     hv[c] = v[0]; hv[c + 1] = v[1]; hv[c + 2] = v[2]; hv[c + 3] = v[3];
   }
   float* out = pred + (head_image<SEQ>(n, Bs, N / (SEQ ? Bs : 1)) * O * H + y) * W + x;
-  for (int o = 0; o < O; ++o) out[(size_t)o * H * W] = head_dot<CHV>(b ? b[o] : 0.f, w_s + o * CHV, hv);
+  if constexpr (sizeof...(Base) > 0) {
+    const HeadBaseK k = (base, ...);
+    const size_t xb = head_base_at(k, (size_t)n, y, x, P, Hh, Wh);
+    for (int o = 0; o < O; ++o)
+      out[(size_t)o * H * W] = head_add_base(head_dot<CHV>(b ? b[o] : 0.f, w_s + o * CHV, hv), load_elem<DT>(k.xs, xb + o));
+  } else {
+    for (int o = 0; o < O; ++o) out[(size_t)o * H * W] = head_dot<CHV>(b ? b[o] : 0.f, w_s + o * CHV, hv);
+  }
 }
 
-template <int DT, int CHV, bool SEQ>
+template <int DT, int CHV, bool SEQ, class... Base>
 __global__ __launch_bounds__(256) void head_fwd_kernel(const void* __restrict__ h, int n0, int N, int Ch, int Chp, int O,
                                                        const float* __restrict__ w, const float* __restrict__ b,
-                                                       float* __restrict__ pred, int H, int W, int P, int Hh, int Wh, int Bs) {
+                                                       float* __restrict__ pred, int H, int W, int P, int Hh, int Wh, int Bs,
+                                                       const Base... base) {
   extern __shared__ __attribute__((aligned(16))) char smem_hf[];
-  head_fwd_body<DT, CHV, SEQ>((float*)smem_hf, h, n0, N, Ch, Chp, O, w, b, pred, H, W, P, Hh, Wh, Bs);
+  head_fwd_body<DT, CHV, SEQ>((float*)smem_hf, h, n0, N, Ch, Chp, O, w, b, pred, H, W, P, Hh, Wh, Bs, base...);
 }
 
 // generic widths: one thread per output element
@@ -480,10 +503,28 @@ __global__ void head_bwd_dw_final_kernel(const float* __restrict__ partial, int 
   *dst = acc_out ? *dst + s : s;                  // (nint_head_bwd_acc: stored, or added by the output's only writer)
 }
 
-// SEQ: the sequence entry (n0 = Bs = B, N = T*B, plane blocks b*T + t)
+// The base operand of the _res entries (nint_head_base, nint.h), checked behind the twin's own checks: NINT_OK with *k filled and
+// *on = whether there is a base at all (a NULL structure or a NULL xs: the twin entry).  NINT_E_ARG: a negative x_n0, Cx < 1, the
+// O feedback channels [c0, c0 + O) outside [0, Cx), xfold_k negative or even, Cxp below the (folded) channel count, or a pixel of
+// Cxp elements that is no multiple of 16 bytes; NINT_E_ALIGN: xs not 16-byte aligned.
+static int head_base_check(const nint_head_base* hb, int O, int dtype, HeadBaseK* k, bool* on) {
+  *on = hb && hb->xs;
+  if (!*on) return NINT_OK;
+  const int es = dtype == NINT_BF16 ? 2 : 4;
+  if (hb->x_n0 < 0 || hb->Cx <= 0 || hb->c0 < 0 || (long long)hb->c0 + O > hb->Cx) return NINT_E_ARG;
+  if (hb->xfold_k < 0 || (hb->xfold_k > 0 && !(hb->xfold_k & 1))) return NINT_E_ARG;
+  const int kf = hb->xfold_k > 1 ? hb->xfold_k : 1;
+  if ((long long)hb->Cxp < (long long)kf * hb->Cx || ((long long)hb->Cxp * es) % 16 != 0) return NINT_E_ARG;
+  if ((((uintptr_t)hb->xs) & 15) != 0) return NINT_E_ALIGN;
+  *k = HeadBaseK{hb->xs, hb->x_n0, hb->Cxp, (kf >> 1) * hb->Cx + hb->c0};
+  return NINT_OK;
+}
+
+// SEQ: the sequence entry (n0 = Bs = B, N = T*B, plane blocks b*T + t).  hb: the residual head's base (nullptr: none); the generic
+// wide kernels have no residual form: NINT_E_SHAPE beyond the staged rule.
 template <bool SEQ>
 static int head_fwd_impl(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w, const float* b, float* pred,
-                         const nint_geom* g, int dtype, int Bs, void* stream) {
+                         const nint_geom* g, int dtype, int Bs, void* stream, const HeadBaseK* hb = nullptr) {
   const size_t total = (size_t)N * O * g->H * g->W, npix = (size_t)N * g->H * g->W;
   hipStream_t st = (hipStream_t)stream;
   const dim3 gp((unsigned)((npix + 255) / 256));
@@ -492,11 +533,18 @@ static int head_fwd_impl(const void* h_slab, int n0, int N, int Ch, int Chp, int
     constexpr int DT = decltype(dt)::value;
     if (head_staged_holds(Chp, O))
       return head_by_chv(Chp, [&](auto chv) -> int {
+        if (hb) {
+          auto kern = head_fwd_kernel<DT, decltype(chv)::value, SEQ, HeadBaseK>;
+          if (w_lds > 64 * 1024) NINT_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)w_lds));
+          hipLaunchKernelGGL(kern, gp, dim3(256), w_lds, st, h_slab, n0, N, Ch, Chp, O, w, b, pred, g->H, g->W, g->P, g->Hh, g->Wh, Bs, *hb);
+          return NINT_OK;
+        }
         auto kern = head_fwd_kernel<DT, decltype(chv)::value, SEQ>;
         if (w_lds > 64 * 1024) NINT_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)w_lds));
         hipLaunchKernelGGL(kern, gp, dim3(256), w_lds, st, h_slab, n0, N, Ch, Chp, O, w, b, pred, g->H, g->W, g->P, g->Hh, g->Wh, Bs);
         return NINT_OK;
       });
+    if (hb) return NINT_E_SHAPE;
     hipLaunchKernelGGL((head_fwd_wide_kernel<DT, SEQ>), grid1d(total), dim3(256), 0, st, h_slab, n0, N, Ch, Chp, O, w, b, pred, g->H, g->W, g->P, g->Hh, g->Wh, Bs);
     return NINT_OK;
   });
@@ -505,11 +553,19 @@ static int head_fwd_impl(const void* h_slab, int n0, int N, int Ch, int Chp, int
   return NINT_OK;
 }
 
-extern "C" int nint_head_fwd(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w,
-                             const float* b, float* pred, const nint_geom* g, int dtype, void* stream) {
+extern "C" int nint_head_fwd_res(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w, const float* b,
+                                 float* pred, const nint_geom* g, int dtype, const nint_head_base* base, void* stream) {
   if (!h_slab || !w || !pred || !g || N <= 0 || O <= 0 || Ch <= 0) return NINT_E_ARG;
   if (dtype != NINT_BF16 && dtype != NINT_F32) return NINT_E_ARG;
-  return head_fwd_impl<false>(h_slab, n0, N, Ch, Chp, O, w, b, pred, g, dtype, 0, stream);
+  HeadBaseK k; bool on;
+  const int rc = head_base_check(base, O, dtype, &k, &on);
+  if (rc != NINT_OK) return rc;
+  return head_fwd_impl<false>(h_slab, n0, N, Ch, Chp, O, w, b, pred, g, dtype, 0, stream, on ? &k : nullptr);
+}
+
+extern "C" int nint_head_fwd(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w,
+                             const float* b, float* pred, const nint_geom* g, int dtype, void* stream) {
+  return nint_head_fwd_res(h_slab, n0, N, Ch, Chp, O, w, b, pred, g, dtype, nullptr, stream);
 }
 
 // channel padding of a slab the head reads: KC of the storage type (nint.h), so every 16-byte channel vector stays inside
@@ -520,11 +576,19 @@ static bool head_seq_args_ok(const void* h_slab, int B, int T, int Ch, int Chp, 
   return Chp % (dtype == NINT_BF16 ? 32 : 16) == 0;
 }
 
-extern "C" int nint_head_fwd_seq(const void* h_slab, int B, int T, int Ch, int Chp, int O, const float* w, const float* b,
-                                 float* seq, const nint_geom* g, int dtype, void* stream) {
+extern "C" int nint_head_fwd_seq_res(const void* h_slab, int B, int T, int Ch, int Chp, int O, const float* w, const float* b,
+                                     float* seq, const nint_geom* g, int dtype, const nint_head_base* base, void* stream) {
   if (!seq || !head_seq_args_ok(h_slab, B, T, Ch, Chp, O, w, g, dtype)) return NINT_E_ARG;
   if ((((uintptr_t)h_slab) & 15) != 0) return NINT_E_ALIGN;
-  return head_fwd_impl<true>(h_slab, B, T * B, Ch, Chp, O, w, b, seq, g, dtype, B, stream);     // h_t = slot t + 1: images from B
+  HeadBaseK k; bool on;
+  const int rc = head_base_check(base, O, dtype, &k, &on);
+  if (rc != NINT_OK) return rc;
+  return head_fwd_impl<true>(h_slab, B, T * B, Ch, Chp, O, w, b, seq, g, dtype, B, stream, on ? &k : nullptr);     // h_t = slot t + 1: images from B
+}
+
+extern "C" int nint_head_fwd_seq(const void* h_slab, int B, int T, int Ch, int Chp, int O, const float* w, const float* b,
+                                 float* seq, const nint_geom* g, int dtype, void* stream) {
+  return nint_head_fwd_seq_res(h_slab, B, T, Ch, Chp, O, w, b, seq, g, dtype, nullptr, stream);
 }
 
 // ------------------------------------------------------------------------------ feedback (closed-loop forward)
@@ -541,7 +605,11 @@ extern "C" int nint_head_fwd_seq(const void* h_slab, int B, int T, int Ch, int C
 // SEL (scheduled sampling): the workgroup of an image whose bit of a.mask is clear returns before it touches
 // anything -- a wave-uniform scalar test on a kernel argument; every byte of that image stays the caller's.  The unmasked
 // instantiation is the kernel it was: it has no such test and never reads the word.
-template <int DT, int CHV, bool SEL = false>
+// RES (residual head): the thread that forms a pixel's dot products also reads the pixel's base -- the O stored
+// values from channel (kf/2)*Cx + c0 of the same pixel of image a.xb + n, the step before -- in the pass that loads h, and adds
+// each to its dot product (head_add_base) before the rounding.  The launch writes images from a.xs on and reads images from a.xb
+// on: the plan keeps the two ranges apart.  The instantiation without it never reads the pointer.
+template <int DT, int CHV, bool SEL = false, bool RES = false>
 __global__ __launch_bounds__(256) void head_feedback_kernel(const void* __restrict__ h, const float* __restrict__ w,
                                                             const float* __restrict__ b, void* __restrict__ xs, FbPlan a) {
   // (the pointers as __restrict__ arguments of their own, as head_fwd_kernel has them; a is the rest of the plan)
@@ -564,7 +632,8 @@ __global__ __launch_bounds__(256) void head_feedback_kernel(const void* __restri
       hv[c] = v[0]; hv[c + 1] = v[1]; hv[c + 2] = v[2]; hv[c + 3] = v[3];
     }
     for (int o = 0; o < a.O; ++o) {
-      const float p = head_dot<CHV>(b ? b[o] : 0.f, w_s + o * CHV, hv);
+      float p = head_dot<CHV>(b ? b[o] : 0.f, w_s + o * CHV, hv);
+      if constexpr (RES) p = head_add_base(p, load_elem<DT>(a.xb, (row + x) * a.Cxp + (size_t)((a.kf >> 1) * a.Cx + a.c0 + o)));
       p_s[x * a.O + o] = DT == NINT_BF16 ? bf2f(f2bf(p)) : p;
     }
   }
@@ -638,8 +707,9 @@ int nint_internal_feedback_plan(const void* h_slab, int n0, int N, int Ch, int C
 int nint_internal_feedback_enqueue(const FbPlan* p, void* stream) {
   const int rc = nint_by_dtype(p->dtype, [&](auto dt) -> int {
     return head_by_chv(p->Chp, [&](auto chv) -> int {
-      auto kern = p->sel ? head_feedback_kernel<decltype(dt)::value, decltype(chv)::value, true>
-                         : head_feedback_kernel<decltype(dt)::value, decltype(chv)::value, false>;
+      constexpr int DT = decltype(dt)::value, CHV = decltype(chv)::value;
+      auto kern = p->res ? (p->sel ? head_feedback_kernel<DT, CHV, true, true> : head_feedback_kernel<DT, CHV, false, true>)
+                         : (p->sel ? head_feedback_kernel<DT, CHV, true, false> : head_feedback_kernel<DT, CHV, false, false>);
       if (p->lds > 64 * 1024) NINT_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->lds));
       hipLaunchKernelGGL(kern, dim3((unsigned)((size_t)p->N * p->H)), dim3(256), p->lds, (hipStream_t)stream, p->h, p->w, p->b, p->xs, *p);
       return NINT_OK;
@@ -671,6 +741,29 @@ extern "C" int nint_head_feedback_sel(const void* h_slab, int n0, int N, int Ch,
   return p.mask ? nint_internal_feedback_enqueue(&p, stream) : (int)NINT_OK;       // (no image fed: nothing to launch)
 }
 
+// The base of a residual feedback launch (FbPlan.xb / .res): images [base_n0, base_n0 + N) of the slab the launch writes images
+// [x_n0, x_n0 + N) of -- the two ranges apart, else NINT_E_ARG.  Called behind nint_internal_feedback_plan, whose checks cover the slab.
+int nint_internal_feedback_base(FbPlan* p, const void* xs_slab, int x_n0, int base_n0, int N) {
+  if (base_n0 < 0 || (base_n0 < x_n0 + N && x_n0 < base_n0 + N)) return NINT_E_ARG;
+  const size_t es = p->dtype == NINT_BF16 ? 2 : 4;
+  p->xb = (const char*)xs_slab + (size_t)base_n0 * p->Hh * p->Wh * p->Cxp * es;
+  p->res = 1;
+  return NINT_OK;
+}
+
+// ... with the residual head's base: p = dot + the value stored in the feedback channels of image base_n0 + i,
+// rounded and stored into image x_n0 + i.  base_n0 < 0: no base; fed == NULL: every image -- with both, nint_head_feedback.
+extern "C" int nint_head_feedback_res(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w, const float* b,
+                                      void* xs_slab, int x_n0, int Cx, int Cxp, int c0, int xfold_k, int lon_cyclic, int base_n0,
+                                      const uint8_t* fed, const nint_geom* g, int dtype, void* stream) {
+  FbPlan p;
+  int rc = nint_internal_feedback_plan(h_slab, n0, N, Ch, Chp, O, w, b, xs_slab, x_n0, Cx, Cxp, c0, xfold_k, lon_cyclic, g, dtype, &p);
+  if (rc == NINT_OK && base_n0 >= 0) rc = nint_internal_feedback_base(&p, xs_slab, x_n0, base_n0, N);
+  if (rc == NINT_OK && fed) { rc = nint_internal_mask_word(fed, N, &p.mask); p.sel = 1; }
+  if (rc != NINT_OK) return rc;
+  return !p.sel || p.mask ? nint_internal_feedback_enqueue(&p, stream) : (int)NINT_OK;
+}
+
 // ------------------------------------------------------------------------------ feedback, backward (roll-out training)
 // nint_head_feedback_bwd (nint.h): the adjoint of the launch above for the N images of one fed step u.  It is
 // nint_head_bwd's dh pass -- head_bwd_dh_body, one thread per pixel, the weights staged once per workgroup, the Chp record
@@ -682,9 +775,12 @@ extern "C" int nint_head_feedback_sel(const void* h_slab, int n0, int N, int Ch,
 // SEL (scheduled sampling): an image whose bit of `mask` is clear was not fed -- xi is 0 without a read of dx,
 // dpred is handed on as it stands and not stored, so the launch is nint_head_bwd's dh pass for that image.  The test is per
 // thread: a 256-thread workgroup straddles image boundaries.
-template <int DT, bool SEL = false>
+// RES (residual head): the base of step u is the fed value itself, so the total cotangent g_u of p_u comes back
+// beside xi_u: g = fl32(fl32(dpred + xi) + dpn), dpn the same element of the dpred image of step u (final: the plan is time-major,
+// descending), which this launch does not write.  An unfed image takes neither.
+template <int DT, bool SEL = false, bool RES = false>
 struct DpFed {
-  const void* __restrict__ dx; float* dp; int O, W, Cx, Cxp, c0, kf, cyc; size_t HW; unsigned long long mask;
+  const void* __restrict__ dx; float* dp; int O, W, Cx, Cxp, c0, kf, cyc; size_t HW; unsigned long long mask; const float* dpn;
   __device__ __forceinline__ float operator()(size_t n, int o, size_t yx) const {
     if constexpr (SEL) {
       if (!((mask >> n) & 1ull)) return dp[(n * O + o) * HW + yx];
@@ -702,17 +798,18 @@ struct DpFed {
       }
     }
     float* p = dp + (n * O + o) * HW + yx;
-    const float g = *p + xi;
+    float g = *p + xi;
+    if constexpr (RES) g = g + dpn[(n * O + o) * HW + yx];
     *p = g;
     return g;
   }
 };
 
-template <int DT, int CHV, bool SEL = false>
+template <int DT, int CHV, bool SEL = false, bool RES = false>
 __global__ __launch_bounds__(256) void head_feedback_bwd_kernel(const void* __restrict__ dx, float* dpred, const float* __restrict__ w,
                                                                 void* __restrict__ dh, FbBwdPlan a) {
   extern __shared__ __attribute__((aligned(16))) char smem_fbb[];
-  const DpFed<DT, SEL> dp{dx, dpred, a.O, a.W, a.Cx, a.Cxp, a.c0, a.kf, a.cyc, (size_t)a.H * a.W, a.mask};
+  const DpFed<DT, SEL, RES> dp{dx, dpred, a.O, a.W, a.Cx, a.Cxp, a.c0, a.kf, a.cyc, (size_t)a.H * a.W, a.mask, RES ? a.pnext : nullptr};
   head_bwd_dh_body<DT, CHV>((float*)smem_fbb, w, dp, dh, a.N, a.Ch, a.Chp, a.O, a.H, a.W);
 }
 
@@ -738,8 +835,9 @@ int nint_internal_feedback_bwd_enqueue(const FbBwdPlan* p, void* stream) {
   const size_t npix = (size_t)p->N * p->H * p->W;
   const int rc = nint_by_dtype(p->dtype, [&](auto dt) -> int {
     return head_by_chv(p->Chp, [&](auto chv) -> int {
-      auto kern = p->sel ? head_feedback_bwd_kernel<decltype(dt)::value, decltype(chv)::value, true>
-                         : head_feedback_bwd_kernel<decltype(dt)::value, decltype(chv)::value, false>;
+      constexpr int DT = decltype(dt)::value, CHV = decltype(chv)::value;
+      auto kern = p->res ? (p->sel ? head_feedback_bwd_kernel<DT, CHV, true, true> : head_feedback_bwd_kernel<DT, CHV, false, true>)
+                         : (p->sel ? head_feedback_bwd_kernel<DT, CHV, true, false> : head_feedback_bwd_kernel<DT, CHV, false, false>);
       if (p->lds > 64 * 1024) NINT_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->lds));
       hipLaunchKernelGGL(kern, dim3((unsigned)((npix + 255) / 256)), dim3(256), p->lds, (hipStream_t)stream, p->dx, p->dpred, p->w, p->dh, *p);
       return NINT_OK;
@@ -770,6 +868,24 @@ extern "C" int nint_head_feedback_bwd_sel(const void* dx, int dx_n0, float* dpre
   if (rc == NINT_OK) rc = nint_internal_mask_word(fed, N, &p.mask);
   if (rc != NINT_OK) return rc;
   p.sel = 1;
+  return nint_internal_feedback_bwd_enqueue(&p, stream);
+}
+
+// ... with the residual head's skip term: g = (dpred + xi) + dpred image pnext_n0 + i on a fed image.
+// pnext_n0 < 0: no such term; fed == NULL: every image -- with both, nint_head_feedback_bwd.  The images [pnext_n0, pnext_n0 + N)
+// are only read: they must lie apart from [p_n0, p_n0 + N), else NINT_E_ARG.
+extern "C" int nint_head_feedback_bwd_res(const void* dx, int dx_n0, float* dpred, int p_n0, void* dh, int dh_n0, int N, int Ch,
+                                          int Chp, int O, const float* w, int Cx, int Cxp, int c0, int xfold_k, int lon_cyclic,
+                                          int pnext_n0, const uint8_t* fed, const nint_geom* g, int dtype, void* stream) {
+  FbBwdPlan p;
+  int rc = nint_internal_feedback_bwd_plan(dx, dx_n0, dpred, p_n0, dh, dh_n0, N, Ch, Chp, O, w, Cx, Cxp, c0, xfold_k, lon_cyclic,
+                                           g, dtype, &p);
+  if (rc == NINT_OK && pnext_n0 >= 0) {
+    if (pnext_n0 < p_n0 + N && p_n0 < pnext_n0 + N) rc = NINT_E_ARG;
+    else { p.pnext = dpred + (size_t)pnext_n0 * O * g->H * g->W; p.res = 1; }
+  }
+  if (rc == NINT_OK && fed) { rc = nint_internal_mask_word(fed, N, &p.mask); p.sel = 1; }
+  if (rc != NINT_OK) return rc;
   return nint_internal_feedback_bwd_enqueue(&p, stream);
 }
 
@@ -897,6 +1013,7 @@ extern "C" int nint_head_bwd_seq(const void* h_slab, int B, int T, int Ch, int C
 struct LossMseL1 {                               // what LossPlain and LossMap share
   static constexpr int NS = 4;
   static constexpr bool OW = false;
+  static constexpr bool BASE = false;            // no residual form: the default spec reproduces their bits (LossSpecRes)
   static constexpr bool HEAD_DOT = false;        // the fused pass keeps the loop it had: head_dot there costs the default step a wave per SIMD
   using Mix = LossMseL1;
   struct Sums { double s2, s1, sy, syy; };      // (an aggregate, zeroed by `= {}`: a constructor call would stand between the kernel and its early passes)
@@ -996,7 +1113,7 @@ __device__ __forceinline__ float loss_spec_grad(const LossSpecK& sp, float df, d
 
 struct LossSpec {
   static constexpr int NS = 5;
-  static constexpr bool CELL = true, OW = true, HEAD_DOT = true;
+  static constexpr bool CELL = true, OW = true, HEAD_DOT = true, BASE = false;
   using Mix = LossSpecK;
   using Sums = LossSpecSums;
   const float* wgt; double cnt; LossSpecK k;     // wgt may be nullptr; cnt = images * (osum or O) * (wsum or Hc * Wc)
@@ -1007,6 +1124,15 @@ struct LossSpec {
   __device__ __forceinline__ double weight(double wd, float q) const { return (double)q * wd; }
   __device__ __forceinline__ Sums add(Sums s, double Wd, float d, float t) const { s.add(Wd, d, t, loss_spec_huber(k, d)); return s; }
   __device__ __forceinline__ float grad(float d, double inv_n, double Wd) const { return loss_spec_grad(k, d, inv_n, Wd); }
+};
+
+// LossSpec for the RESIDUAL HEAD (the _res fused entries): the same element; the fused pass adds the base it
+// carries to every dot product (head_add_base), so the loss, d loss / d pred and dL/dh see p = d + base.  Built from the kernel's
+// arguments (wgt, cnt, LossSpecK, HeadBaseK); the closing fold is LossSpec's and takes the LossSpecK alone.
+struct LossSpecRes : LossSpec {
+  static constexpr bool BASE = true;
+  HeadBaseK base;
+  __device__ __forceinline__ LossSpecRes(const float* wgt_, double cnt_, const LossSpecK& k_, const HeadBaseK& b_) : LossSpec(wgt_, cnt_, k_), base(b_) {}
 };
 
 // The fold of a workgroup's NQ running sums, red[q][thread] -> red[q][0]: a fixed-order tree from `half` threads down.
@@ -1223,6 +1349,8 @@ __device__ __forceinline__ void head_loss_body(char* smem_hl, const void* __rest
     const size_t step = SEQ ? n / Bs : 0;        // of the pixel's image n = t*B + b: the row of the (step, output) weights
     float* dp = dpred + ((size_t)n * O * H + yy) * W + x;
     const float* yp = y + (head_image<SEQ>(n, Bs, N / (SEQ ? Bs : 1)) * O * Hc + cy) * Wc + cx;
+    size_t xb = 0;                               // residual head: the pixel's base, fetched with the targets of the outputs that count
+    if constexpr (Elem::BASE) xb = head_base_at(e.base, (size_t)n, yy, x, P, Hh, Wh);
     float acc[CQ];
 #pragma unroll
     for (int c = 0; c < CQ; ++c) acc[c] = 0.f;
@@ -1240,6 +1368,11 @@ __device__ __forceinline__ void head_loss_body(char* smem_hl, const void* __rest
         for (int u = 0; u < OU; ++u) qq[u] = (in && o0 + u < oe) ? (Elem::OW ? e.out(step, O, o0 + u) : 1.f) : 0.f;
 #pragma unroll
         for (int u = 0; u < OU; ++u) tq[u] = (Elem::OW ? qq[u] != 0.f : in && o0 + u < oe) ? yp[(size_t)(o0 + u) * Hc * Wc] : 0.f;
+        [[maybe_unused]] float bq[OU];
+        if constexpr (Elem::BASE) {
+#pragma unroll
+          for (int u = 0; u < OU; ++u) bq[u] = qq[u] != 0.f ? load_elem<DT>(e.base.xs, xb + (o0 + u)) : 0.f;
+        }
 #pragma unroll
         for (int u = 0; u < OU; ++u) {
           const int o = o0 + u;
@@ -1247,6 +1380,7 @@ __device__ __forceinline__ void head_loss_body(char* smem_hl, const void* __rest
           float p = b ? b[o] : 0.f;
           if constexpr (Elem::HEAD_DOT) {
             p = head_dot<CHV>(p, w_s + o * CHV, hv);
+            if constexpr (Elem::BASE) p = head_add_base(p, bq[u]);
           } else {                               // head_dot's chain as the optimiser forms it from this loop (see head_dot)
             const f32x4_t* wr = (const f32x4_t*)(w_s + o * CHV);
 #pragma unroll
@@ -1311,6 +1445,17 @@ __global__ __launch_bounds__(256) void head_loss_kernel(const void* __restrict__
   head_loss_body<DT, CHV, SEQ>(smem_hl, h, n0, N, Ch, Chp, O, w, b, y, dpred, dh, partial, H, W, P, Hh, Wh, oy, ox, Hc, Wc, Bs, Elem(wgt, cnt, sp...));
 }
 
+// the closing fold of a fused pass: loss_final_kernel<Mix> with the first of the pass's coefficient arguments, if any (LossSpecRes
+// carries its base behind the LossSpecK, which the fold has no use for)
+template <class Mix>
+static void loss_final_first(hipStream_t st, double* partial, int nblk, float* loss_out, double* stats, double cnt) {
+  hipLaunchKernelGGL((loss_final_kernel<Mix>), dim3(1), dim3(256), 0, st, partial, nblk, loss_out, stats, cnt);
+}
+template <class Mix, class K0, class... Rest>
+static void loss_final_first(hipStream_t st, double* partial, int nblk, float* loss_out, double* stats, double cnt, const K0& k0, const Rest&...) {
+  hipLaunchKernelGGL((loss_final_kernel<Mix, K0>), dim3(1), dim3(256), 0, st, partial, nblk, loss_out, stats, cnt, k0);
+}
+
 // The fused pass.  SEQ: the sequence entry (n0 = Bs = B, N = T*B).  cnt: the n of the loss; k: the LossSpecK of LossSpec
 template <bool SEQ, class Elem, class... Coef>
 static int head_loss_launch(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w, const float* b,
@@ -1331,7 +1476,7 @@ static int head_loss_launch(const void* h_slab, int n0, int N, int Ch, int Chp, 
     return NINT_OK; }); });
   if (rc != NINT_OK) return rc;
   NINT_LAUNCH_CHECK();
-  hipLaunchKernelGGL((loss_final_kernel<typename Elem::Mix, Coef...>), dim3(1), dim3(256), 0, st, partial, nblk, loss_out, stats, cnt, k...);
+  loss_final_first<typename Elem::Mix>(st, partial, nblk, loss_out, stats, cnt, k...);
   NINT_LAUNCH_CHECK();
   return NINT_OK;
 }
@@ -1367,18 +1512,33 @@ extern "C" int nint_head_loss_fused_weighted(const void* h_slab, int n0, int N, 
                                           oy, ox, Hc, Wc, dtype, 0, stream);
 }
 
+// (the _spec entries are their _res twins without a base: the twin's checks in the twin's order, then the base's)
+extern "C" int nint_head_loss_fused_res(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w, const float* b,
+                                        const float* y, const float* wgt, double wsum, const nint_loss_spec* spec, float* dpred,
+                                        void* dh, float* loss_out, double* stats, const nint_geom* g, int oy, int ox, int Hc,
+                                        int Wc, int dtype, const nint_head_base* base, void* stream) {
+  if (!y || !dpred || !dh || !loss_out || !head_loss_args_ok(h_slab, N, Ch, O, w, g, dtype)) return NINT_E_ARG;
+  if (!loss_crop_ok(g->H, g->W, oy, ox, Hc, Wc, true)) return NINT_E_ARG;
+  int rc = loss_spec_check(spec, O, wgt, wsum);
+  if (rc != NINT_OK) return rc;
+  if (Chp > 128 || Chp % 4) return NINT_E_SHAPE;
+  if (!loss_aligned(loss_out, wgt, spec->ow)) return NINT_E_ALIGN;
+  HeadBaseK k; bool on;
+  if ((rc = head_base_check(base, O, dtype, &k, &on)) != NINT_OK) return rc;
+  const double cnt = loss_spec_cnt(spec, N, O, wgt, wsum, Hc, Wc);
+  if (on)
+    return head_loss_launch<false, LossSpecRes>(h_slab, n0, N, Ch, Chp, O, w, b, y, wgt, cnt, dpred, dh, loss_out, stats, g, oy, ox, Hc, Wc,
+                                                dtype, 0, stream, loss_spec_k(spec), k);
+  return head_loss_launch<false, LossSpec>(h_slab, n0, N, Ch, Chp, O, w, b, y, wgt, cnt, dpred, dh,
+                                           loss_out, stats, g, oy, ox, Hc, Wc, dtype, 0, stream, loss_spec_k(spec));
+}
+
 extern "C" int nint_head_loss_fused_spec(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w, const float* b,
                                          const float* y, const float* wgt, double wsum, const nint_loss_spec* spec, float* dpred,
                                          void* dh, float* loss_out, double* stats, const nint_geom* g, int oy, int ox, int Hc,
                                          int Wc, int dtype, void* stream) {
-  if (!y || !dpred || !dh || !loss_out || !head_loss_args_ok(h_slab, N, Ch, O, w, g, dtype)) return NINT_E_ARG;
-  if (!loss_crop_ok(g->H, g->W, oy, ox, Hc, Wc, true)) return NINT_E_ARG;
-  const int rc = loss_spec_check(spec, O, wgt, wsum);
-  if (rc != NINT_OK) return rc;
-  if (Chp > 128 || Chp % 4) return NINT_E_SHAPE;
-  if (!loss_aligned(loss_out, wgt, spec->ow)) return NINT_E_ALIGN;
-  return head_loss_launch<false, LossSpec>(h_slab, n0, N, Ch, Chp, O, w, b, y, wgt, loss_spec_cnt(spec, N, O, wgt, wsum, Hc, Wc), dpred, dh,
-                                           loss_out, stats, g, oy, ox, Hc, Wc, dtype, 0, stream, loss_spec_k(spec));
+  return nint_head_loss_fused_res(h_slab, n0, N, Ch, Chp, O, w, b, y, wgt, wsum, spec, dpred, dh, loss_out, stats, g, oy, ox, Hc, Wc, dtype,
+                                  nullptr, stream);
 }
 
 extern "C" int nint_head_loss_seq_fused(const void* h_slab, int B, int T, int Ch, int Chp, int O, const float* w, const float* b,
@@ -1404,20 +1564,33 @@ extern "C" int nint_head_loss_seq_fused_weighted(const void* h_slab, int B, int 
                                          stats, g, oy, ox, Hc, Wc, dtype, B, stream);
 }
 
+extern "C" int nint_head_loss_seq_fused_res(const void* h_slab, int B, int T, int Ch, int Chp, int O, const float* w, const float* b,
+                                            const float* y, const float* wgt, double wsum, const nint_loss_spec* spec, float* dpred,
+                                            void* dh_seq, float* loss_out, double* stats, const nint_geom* g, int oy, int ox,
+                                            int Hc, int Wc, int dtype, const nint_head_base* base, void* stream) {
+  if (!y || !dpred || !dh_seq || !loss_out || !head_seq_args_ok(h_slab, B, T, Ch, Chp, O, w, g, dtype)) return NINT_E_ARG;
+  if (!loss_crop_ok(g->H, g->W, oy, ox, Hc, Wc, true) || (long long)T * O > INT_MAX) return NINT_E_ARG;
+  int rc = loss_spec_check(spec, T * O, wgt, wsum);
+  if (rc != NINT_OK) return rc;
+  if (Chp > 128) return NINT_E_SHAPE;
+  if (!loss_aligned(loss_out, wgt, spec->ow) || !head_seq_aligned(h_slab, dh_seq)) return NINT_E_ALIGN;
+  HeadBaseK k; bool on;
+  if ((rc = head_base_check(base, O, dtype, &k, &on)) != NINT_OK) return rc;
+  // with ow the weights run over (step, output): cnt = B * osum * wsum; without, the twin's (T*B) * O * wsum
+  const double cnt = loss_spec_cnt(spec, spec->ow ? B : T * B, O, wgt, wsum, Hc, Wc);
+  if (on)
+    return head_loss_launch<true, LossSpecRes>(h_slab, B, T * B, Ch, Chp, O, w, b, y, wgt, cnt, dpred, dh_seq, loss_out, stats, g, oy, ox, Hc,
+                                               Wc, dtype, B, stream, loss_spec_k(spec), k);
+  return head_loss_launch<true, LossSpec>(h_slab, B, T * B, Ch, Chp, O, w, b, y, wgt, cnt, dpred, dh_seq, loss_out, stats, g, oy, ox, Hc, Wc,
+                                          dtype, B, stream, loss_spec_k(spec));
+}
+
 extern "C" int nint_head_loss_seq_fused_spec(const void* h_slab, int B, int T, int Ch, int Chp, int O, const float* w, const float* b,
                                              const float* y, const float* wgt, double wsum, const nint_loss_spec* spec, float* dpred,
                                              void* dh_seq, float* loss_out, double* stats, const nint_geom* g, int oy, int ox,
                                              int Hc, int Wc, int dtype, void* stream) {
-  if (!y || !dpred || !dh_seq || !loss_out || !head_seq_args_ok(h_slab, B, T, Ch, Chp, O, w, g, dtype)) return NINT_E_ARG;
-  if (!loss_crop_ok(g->H, g->W, oy, ox, Hc, Wc, true) || (long long)T * O > INT_MAX) return NINT_E_ARG;
-  const int rc = loss_spec_check(spec, T * O, wgt, wsum);
-  if (rc != NINT_OK) return rc;
-  if (Chp > 128) return NINT_E_SHAPE;
-  if (!loss_aligned(loss_out, wgt, spec->ow) || !head_seq_aligned(h_slab, dh_seq)) return NINT_E_ALIGN;
-  // with ow the weights run over (step, output): cnt = B * osum * wsum; without, the twin's (T*B) * O * wsum
-  const double cnt = loss_spec_cnt(spec, spec->ow ? B : T * B, O, wgt, wsum, Hc, Wc);
-  return head_loss_launch<true, LossSpec>(h_slab, B, T * B, Ch, Chp, O, w, b, y, wgt, cnt, dpred, dh_seq, loss_out, stats, g, oy, ox, Hc, Wc,
-                                          dtype, B, stream, loss_spec_k(spec));
+  return nint_head_loss_seq_fused_res(h_slab, B, T, Ch, Chp, O, w, b, y, wgt, wsum, spec, dpred, dh_seq, loss_out, stats, g, oy, ox, Hc, Wc,
+                                      dtype, nullptr, stream);
 }
 
 // ------------------------------------------------------------------------------ evaluation: skill sums (test.ipynb)

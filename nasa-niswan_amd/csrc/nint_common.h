@@ -371,6 +371,10 @@ struct FbPlan {
   // SCHEDULED SAMPLING.  sel = 1: the masked instantiation, which feeds image i only where bit i of `mask` is set
   // (N <= 64).  sel = 0, what every plan function below leaves: the unmasked kernels, which never read the word.
   unsigned long long mask; int sel;
+  // RESIDUAL HEAD.  res = 1: the instantiation that adds the base -- the value stored in the feedback channels of
+  // the images from xb on, the pixel's own copy in a folded slab -- to the dot product before the rounding.  res = 0, what every
+  // plan function below leaves: the kernels without it, which never read the pointer.
+  const void* xb; int res;
 };
 // The mask word of N images from N HOST bytes, each 0 or 1 (nint_feedback_mask, nint_head_feedback_sel): NINT_E_ARG for a NULL
 // pointer or any other byte, then NINT_E_SHAPE for more images than the word has bits.
@@ -390,6 +394,8 @@ int nint_internal_feedback_plan(const void* h_slab, int n0, int N, int Ch, int C
                                 void* xs_slab, int x_n0, int Cx, int Cxp, int c0, int xfold_k, int lon_cyclic, const nint_geom* g,
                                 int dtype, FbPlan* plan);
 int nint_internal_feedback_enqueue(const FbPlan* plan, void* stream);
+// residual head: the planned launch reads its base from images [base_n0, base_n0 + N) of the slab it writes [x_n0, x_n0 + N) of
+int nint_internal_feedback_base(FbPlan* plan, const void* xs_slab, int x_n0, int base_n0, int N);
 // ... and its adjoint, the feedback step of the roll-out backward (nint_head_feedback_bwd's arguments)
 struct FbBwdPlan {
   const void* dx; float* dpred; void* dh; const float* w;        // dx, dpred, dh: the FIRST image read / written
@@ -397,6 +403,7 @@ struct FbBwdPlan {
   int H, W;
   size_t lds;
   unsigned long long mask; int sel;                              // as in FbPlan; per thread here: a workgroup straddles images
+  const float* pnext; int res;                                   // residual head: g += dpred of the fed step itself, images from pnext on (res = 1)
 };
 int nint_internal_feedback_bwd_plan(const void* dx, int dx_n0, float* dpred, int p_n0, void* dh, int dh_n0, int N, int Ch, int Chp,
                                     int O, const float* w, int Cx, int Cxp, int c0, int xfold_k, int lon_cyclic, const nint_geom* g,

@@ -133,6 +133,7 @@ static const nint_feedback NO_FB = {};
 // It is read here, on the host, while the pass is checked and planned; a launch gets its step's 64-bit word by value.
 struct Pass {
   const nint_seq* s; const nint_feedback* fb; const nint_feedback_grad* rg; int dir; const uint8_t* mask;
+  bool res;                                        // RESIDUAL HEAD: the feedback launches of the plan are the _res ones
   bool bwd() const { return dir != PASS_FWD; }
   // the first step with a fed image (a mask; any non-zero byte counts, so that a bad byte is looked at), else fb->from
   int first() const {
@@ -149,10 +150,11 @@ struct Pass {
   bool fed() const { return fb->O > 0 && first() < s->T; }           // steps [F, T) run time-major, fed images on the fed-back prediction
   bool rollout() const { return dir == PASS_ROLLOUT && fed(); }      // ... and this pass differentiates through it
 };
-static Pass pass_of(const nint_seq* s, const nint_feedback* fb, const nint_feedback_grad* rg, int dir, const nint_feedback_mask* fm = nullptr) {
+static Pass pass_of(const nint_seq* s, const nint_feedback* fb, const nint_feedback_grad* rg, int dir, const nint_feedback_mask* fm = nullptr,
+                    bool res = false) {
   // (a mask beside a head of no outputs says nothing; s is checked before anything reads it: pass_check step 1 comes first)
   const bool masked = fm && fm->fed && fb && fb->O > 0 && s && s->B >= 1 && s->T >= 1;
-  return Pass{s, fb ? fb : &NO_FB, dir == PASS_ROLLOUT ? rg : nullptr, dir, masked ? fm->fed : nullptr};
+  return Pass{s, fb ? fb : &NO_FB, dir == PASS_ROLLOUT ? rg : nullptr, dir, masked ? fm->fed : nullptr, res};
 }
 
 // THE ONE CHECK; its order decides the code of a doubly wrong call (tests/golden/seq_plan.npy.xz).  KEPT DIFFERENCE between the
@@ -181,6 +183,8 @@ static int pass_check(const Pass& p) {
   const bool fb_ok = fb->O >= 0 && fb->O <= s->layer[0].Cx && mask_ok && F >= 0 && (fb->O == 0 || (fb->w && (F > 0 || s->has_init_state)));
   const int mask_rc = p.mask && s->B > 64 ? NINT_E_SHAPE : NINT_OK;
   if (p.dir != PASS_ROLLOUT && !fb_ok) return NINT_E_ARG;
+  // (residual head, 4.22: the fed value of step 0 would need p_{-1}'s base; the roll-out refuses F == 0 anyway, below)
+  if (p.res && p.dir == PASS_FWD && fb->O > 0 && F == 0) return NINT_E_ARG;
   if (!p.bwd()) return mask_rc;
   // 3. the backward fields
   const int f = s->train_from;         // (nint_seq.train_from: nothing of a layer below it is read)
@@ -303,7 +307,9 @@ static void push_gate(Steps& out, const GateCall& gc, const ConvPlan& pl, int l,
 // pass -- the pass is then that open-loop pass, bit for bit, over an input that already holds the fed values.
 // UNDER A MASK (m) the feedback launch goes out only at steps with a fed image, as the masked instantiation with
 // the step's word; the gates of the step are planned as in any closed-loop step.
-static int plan_fwd_steps(const nint_seq* s, const nint_feedback* f, int n_cu, int t0, int t1, Steps& out, const Pass* m = nullptr) {
+// RESIDUAL HEAD (res): the same launch in the same place with its base in block t-1 of xs (pass_check: t >= 1).
+static int plan_fwd_steps(const nint_seq* s, const nint_feedback* f, int n_cu, int t0, int t1, Steps& out, const Pass* m = nullptr,
+                          bool res = false) {
   const int L = s->L, T = t1 - t0;
   const bool wavefront = !f && s->wave && L > 1 && L <= NINT_MULTI_MAX;
   const bool rows8 = (s->wave == 2 || s->wave == 3 || s->wave == 4) && L > 1 && L <= NINT_MULTI_MAX;     // the 8-row rule (plan_gate)
@@ -321,7 +327,9 @@ static int plan_fwd_steps(const nint_seq* s, const nint_feedback* f, int n_cu, i
         const int rc = nint_internal_feedback_plan(s->h[L - 1], t * s->B, s->B, top->Ch, top->Chp, f->O, f->w, f->b, (void*)s->xs, t * s->B,
                                                    l0->Cx, l0->Cxp, l0->Cx - f->O, l0->xfold ? l0->k : 0, s->lon_cyclic, &s->g, s->dtype, &fb.fb);
         if (rc != NINT_OK) return rc;
+        int rc2 = NINT_OK;
         if (m) { fb.fb.mask = word; fb.fb.sel = 1; }
+        if (res && (rc2 = nint_internal_feedback_base(&fb.fb, s->xs, t * s->B, (t - 1) * s->B, s->B)) != NINT_OK) return rc2;
       }
       const int rc = plan_gate(s, n_cu, rows8, l, t, &gc[n], &pl[n]);
       if (rc != NINT_OK && rc != NINT_E_SHAPE) return rc;
@@ -340,7 +348,7 @@ static int plan_fwd(const Pass& p, int n_cu, Steps& out) {
   const int T = p.s->T, F = p.fed() ? p.first() : T;           // (pass_check: from >= 0)
   out.reserve((size_t)T * (p.s->L + 1));
   const int rc = plan_fwd_steps(p.s, nullptr, n_cu, 0, F, out);
-  return rc != NINT_OK || F == T ? rc : plan_fwd_steps(p.s, p.fb, n_cu, F, T, out, p.mask ? &p : nullptr);
+  return rc != NINT_OK || F == T ? rc : plan_fwd_steps(p.s, p.fb, n_cu, F, T, out, p.mask ? &p : nullptr, p.res);
 }
 
 // default of the "lower layer's pointwise backward on the fused layer's x columns" option: on (962.2 -> 963.6 samples/s, profiles/HISTORY.md)
@@ -385,11 +393,12 @@ struct BwdPlanner {
   // plan_bwd hands in a nint_seq with fuse_bwd = 1 and wave = 0: every launch by itself, time-major.
   // Under a mask (4.21) F is the first step with a fed image and the launch of EVERY step u >= F goes out, with the step's word:
   // an all-zero word makes it the plain head backward of block u-1, so the division of dh_seq between caller and chain stays.
-  const nint_feedback* fb; const nint_feedback_grad* rg; int F; const Pass* mp;
+  // Residual head (4.22): the launch of step u also adds dpred block u, which is final by then (`res`).
+  const nint_feedback* fb; const nint_feedback_grad* rg; int F; const Pass* mp; bool res;
 
   BwdPlanner(const Pass& p, int n_cu_, Steps& out_)
       : s(p.s), n_cu(n_cu_), out(out_), L(p.s->L), T(p.s->T), B(p.s->B), has_d(false), has_p(false), held_u(0), held_t(0), fb(p.fb),
-        rg(p.rollout() ? p.rg : nullptr), F(p.rollout() ? p.first() : p.s->T), mp(p.mask ? &p : nullptr) {
+        rg(p.rollout() ? p.rg : nullptr), F(p.rollout() ? p.first() : p.s->T), mp(p.mask ? &p : nullptr), res(p.res) {
     es = esize(s->dtype); halo_px = (size_t)s->g.Hh * s->g.Wh; comp_px = (size_t)s->g.H * s->g.W;
     const bool explicit_mask = (s->fuse_bwd & 0x40000000) != 0;
     for (int l = L - 1; l >= 0; --l) {
@@ -545,6 +554,7 @@ struct BwdPlanner {
                                                    (void*)s->dh_seq, (u - 1) * (int)B, (int)B, top->Ch, top->Chp, fb->O, fb->w, l0->Cx, l0->Cxp,
                                                    l0->Cx - fb->O, l0->xfold ? l0->k : 0, s->lon_cyclic, &s->g, s->dtype, &st.fbb);
     if (mp) { st.fbb.mask = mp->word(u); st.fbb.sel = 1; }       // (the plan function zero-fills both: after it)
+    if (res) { st.fbb.pnext = rg->dpred + (size_t)u * B * fb->O * comp_px; st.fbb.res = 1; }
     return rc;
   }
 
@@ -715,6 +725,8 @@ extern "C" int nint_seq_bwd_closed(const nint_seq* s, const nint_feedback* fb, v
 extern "C" int nint_seq_bwd_rollout(const nint_seq* s, const nint_feedback* fb, const nint_feedback_grad* rg, void* stream) { return run_pass(pass_of(s, fb, rg, PASS_ROLLOUT), stream); }
 extern "C" int nint_seq_fwd_sampled(const nint_seq* s, const nint_feedback* fb, const nint_feedback_mask* fm, void* stream) { return run_pass(pass_of(s, fb, nullptr, PASS_FWD, fm), stream); }
 extern "C" int nint_seq_bwd_rollout_sampled(const nint_seq* s, const nint_feedback* fb, const nint_feedback_mask* fm, const nint_feedback_grad* rg, void* stream) { return run_pass(pass_of(s, fb, rg, PASS_ROLLOUT, fm), stream); }
+extern "C" int nint_seq_fwd_residual(const nint_seq* s, const nint_feedback* fb, const nint_feedback_mask* fm, void* stream) { return run_pass(pass_of(s, fb, nullptr, PASS_FWD, fm, true), stream); }
+extern "C" int nint_seq_bwd_rollout_residual(const nint_seq* s, const nint_feedback* fb, const nint_feedback_mask* fm, const nint_feedback_grad* rg, void* stream) { return run_pass(pass_of(s, fb, rg, PASS_ROLLOUT, fm, true), stream); }
 
 // ------------------------------------------------------------------------------ the plan, for tests and tools
 static int plan_records(const nint_seq* s, const Steps& steps, int bwd, nint_launch_rec* out, int cap) {

@@ -11,7 +11,8 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 
 from . import _lib
-from ._lib import NINT_BF16, NINT_F32, NintFeedback, NintFeedbackGrad, NintFeedbackMask, NintGeom, NintLayer, NintSeq, check, ptr, stream_ptr
+from ._lib import (NINT_BF16, NINT_F32, NintFeedback, NintFeedbackGrad, NintFeedbackMask, NintGeom, NintHeadBase, NintLayer, NintLossSpec,
+                   NintSeq, check, ptr, stream_ptr)
 
 # 0: the library picks the gate / dgrad pixel-tile height per launch shape; 4 or 8 forces it for every layer of
 # engines built afterwards (nint_layer.tile_rows) -- how the tests run both heights on every shape
@@ -27,6 +28,10 @@ FORCE_WIDE = 0
 FORCE_WAVE = None        # merged grids (nint_seq.wave): None = by batch size (SeqEngine._set_wave), 0 = never, 1 = forward wavefront + backward pair, 2 = forward wavefront only (8-row tiles), 4 = 2 + the BPTT pairs (dgrad 0 + dgrad 1, pointwise 0 + the top layer's fused step), 5 = the forward pass of 1 + the BPTT pairs of 4
 WAVE_TILES_PER_CU = 1.5   # ... wave = 5 (the layers' own tiles) while 2 * (8-row pixel tiles of the batch) < WAVE_TILES_PER_CU * CUs: B = 1 at 100 x 154; wave = 4 above
 FUSE_BWD = 0          # nint_seq.fuse_bwd of new workspaces: 0 = per layer, 1 = never fused, 2 = every layer fused (tests run all three)
+
+RESIDUAL_STEP0 = ("residual head: step 0 cannot be fed -- the fed value is the prediction of the step before, p_{-1} = x_{-1}[feedback "
+                  "channels] + head(h_{-1}), and no input precedes the window, even with an initial state; feed from step 1 on "
+                  "(free_from >= 1, or a mask whose column 0 is clear)")
 
 DTYPES = {"f32": NINT_F32, "fp32": NINT_F32, "float32": NINT_F32, "bf16": NINT_BF16, "bfloat16": NINT_BF16}
 
@@ -59,11 +64,13 @@ class Feedback:
     tensors its pointers name, the ``feedback_grad`` mark (the window will be trained through what it fed) and the roll-out
     backward's two buffers -- the f32 slab of the per-step head cotangents and the one-step d/dx scratch, None until asked for.
     Scheduled sampling: ``mask``, the pinned host uint8 (T, B) array that ``fm`` (nint_feedback_mask) points
-    at, or None; ``fb.from_step`` is then F, the first step with a fed image, so ``fed`` stays the range [F, T)."""
+    at, or None; ``fb.from_step`` is then F, the first step with a fed image, so ``fed`` stays the range [F, T).
+    Residual head: ``res`` -- the pass ran for a head that predicts the increment, p_t = x_t[feedback channels] +
+    head(h_t); every head call on the workspace then adds that base, fed or not (``fb.O`` may be 0: a teacher-forced window)."""
 
     def __init__(self, T: int, B: int = 1):
         self.T, self.fb, self.keep, self.grad, self.dpred, self.dx_step = T, NintFeedback(), None, False, None, None
-        self.B = B
+        self.B, self.res = B, False
         self.fm, self.mask, self._pin = NintFeedbackMask(), None, None
 
     @staticmethod
@@ -100,9 +107,10 @@ class Feedback:
             return self.mask.t().bool()
         return (torch.arange(self.T) >= self.fed.start).expand(self.B, self.T).clone()
 
-    def set(self, w=None, b=None, O: int = 0, from_step: int = 0, grad: bool = False, mask=None):
+    def set(self, w=None, b=None, O: int = 0, from_step: int = 0, grad: bool = False, mask=None, res: bool = False):
         """``mask``: a CPU uint8 (B, T) tensor (``mask_bt``) in the place of ``from_step``"""
         self.keep = (w, b)          # the pointers below stay valid as long as the fields name them
+        self.res = bool(res)
         self.mask, self.fm.fed = None, None
         if mask is not None:
             # one pinned (T, B) buffer per workspace, time-major (index t*B + b), reused pass after pass: the library reads it on
@@ -550,7 +558,7 @@ class SeqEngine:
 
     # ------------------------------------------------------------------ passes
     def forward(self, ws: Workspace, x: torch.Tensor, h0: Optional[List[torch.Tensor]] = None,
-                c0: Optional[List[torch.Tensor]] = None, feedback=None, feedback_grad: bool = False):
+                c0: Optional[List[torch.Tensor]] = None, feedback=None, feedback_grad: bool = False, residual=False):
         """x (B,T,C,H,W) f32 on the engine's device, or a dataset.SlabBatch of that shape.  Runs model.py:253-271
         (all layers, all steps).
 
@@ -563,11 +571,21 @@ class SeqEngine:
 
         ``feedback_grad=True`` (with ``feedback``, on a training workspace): the window will be trained THROUGH the fed-back
         prediction.  It marks the workspace: ``backward(..., rollout=...)`` then runs the roll-out backward.
-        The forward pass is the same one.  Without it a backward pass on a fed window is refused, as ever."""
+        The forward pass is the same one.  Without it a backward pass on a fed window is refused, as ever.
+
+        ``residual``: False, or the number O of head outputs of a RESIDUAL HEAD -- the head predicts the
+        increment, p_t = x_t[last O channels] + head(h_t) with x_t as the model saw it.  It marks the workspace: every head
+        call on it (head_forward[_seq], the fused head / loss passes, the skill pass) then adds that base, and with
+        ``feedback`` the fed value is round_ET(p_{t-1}) of that p (the _residual entries).  A fed image at step 0 is refused:
+        p_{-1} has no base, even with a state."""
         B, T, Cc, H, W = x.shape
         assert (B, T, H, W) == (ws.B, ws.T, ws.H, ws.W) and Cc == self.cfgs[0].Cx
         s = ws.seq
-        ws.feedback.set()       # (stays as this pass sets it: a backward pass on a fed window is refused unless marked)
+        res_O = 0 if residual is False or residual is None else int(residual)
+        if res_O and (not 1 <= res_O <= Cc or self._beyond_fused_head(self.layers[-1].Chp, res_O)):
+            raise _lib.NintError(f"residual head: {res_O} outputs on {self.layers[-1].Chp} padded channels over {Cc} input channels is "
+                                 "beyond the staged head kernels, which alone add the base (NINT_E_SHAPE), or has no feedback channels")
+        ws.feedback.set(res=bool(res_O))       # (stays as this pass sets it: a backward pass on a fed window is refused unless marked)
         if feedback is not None:
             w, b, from_step = feedback
             _, _, O, w2, b2 = self._head_args(w, b)
@@ -583,10 +601,14 @@ class SeqEngine:
                                  f"at most {Cc} input channels")
             if from_step < 0 or (from_step == 0 and not s.has_init_state):
                 raise ValueError("feedback: step 0 can only be fed from a given initial state (from_step = 0 needs a state)")
+            if res_O and from_step == 0:
+                raise ValueError(RESIDUAL_STEP0)
+            if res_O and res_O != O:
+                raise ValueError(f"residual head: residual = {res_O} outputs, the fed-back head has {O}")
             if self._beyond_fused_head(self.layers[-1].Chp, O):
                 raise _lib.NintError(f"feedback: a head of {O} outputs on {self.layers[-1].Chp} padded channels is beyond the "
                                      "staged head kernels (nint_head_feedback: NINT_E_SHAPE)")
-            ws.feedback.set(w2, b2, O, from_step, bool(feedback_grad), mask)
+            ws.feedback.set(w2, b2, O, from_step, bool(feedback_grad), mask, bool(res_O))
         self.pack_input(ws, x)
         if h0 is not None:
             self._write_state(h0, c0, self._slot_ptrs(ws, 0), B, ws.g, "0")
@@ -600,7 +622,10 @@ class SeqEngine:
         the seven."""
         s, fb, fm = ws.seq, ws.feedback.fb, ws.feedback.fm
         masked = ws.feedback.mask is not None and fb.O > 0
-        if rg is not None and masked:
+        if ws.feedback.res and fb.O > 0 and (rg is not None or not bwd):    # residual head (4.22): the _sampled entries' twins
+            name = "nint_seq_bwd_rollout_residual" if rg is not None else "nint_seq_fwd_residual"
+            extra = (C.byref(fb), C.byref(fm)) + ((C.byref(rg),) if rg is not None else ())
+        elif rg is not None and masked:
             name, extra = "nint_seq_bwd_rollout_sampled", (C.byref(fb), C.byref(fm), C.byref(rg))
         elif rg is not None:
             name, extra = "nint_seq_bwd_rollout", (C.byref(fb), C.byref(rg))
@@ -611,6 +636,7 @@ class SeqEngine:
         else:
             name, extra = ("nint_seq_bwd" if bwd else "nint_seq_fwd"), ()
         what = name + (" (the backward pass of a window in which the prediction was fed back is not defined)" if bwd and extra and rg is None else "")
+        # (seven names, and the residual head's two)
         check(getattr(self.lib, name)(C.byref(s), *extra, stream_ptr()), what)
 
     def _set_wave(self, ws: Workspace):
@@ -665,9 +691,38 @@ class SeqEngine:
         Ch, Chp, O, w2, b2 = self._head_args(w, b)
         slot = ws.T if slot is None else slot
         pred = torch.empty(ws.B, O, ws.H, ws.W, dtype=torch.float32, device=self.device)
+        if ws.feedback.res:             # residual head: + the feedback channels of the step's input, block slot - 1 of xs
+            if slot < 1:
+                raise ValueError("residual head: slot 0 is the initial state, which no input step pairs with")
+            base = self._head_base(ws, O, (slot - 1) * ws.B)
+            check(self.lib.nint_head_fwd_res(ptr(ws.h[-1]), slot * ws.B, ws.B, Ch, Chp, O, ptr(w2), ptr(b2), ptr(pred),
+                                             C.byref(ws.g), self.dt, C.byref(base), stream_ptr()), "nint_head_fwd_res")
+            return pred
         check(self.lib.nint_head_fwd(ptr(ws.h[-1]), slot * ws.B, ws.B, Ch, Chp, O, ptr(w2), ptr(b2), ptr(pred),
                                      C.byref(ws.g), self.dt, stream_ptr()), "nint_head_fwd")
         return pred
+
+    def _head_base(self, ws: Workspace, O: int, x_n0: int) -> NintHeadBase:
+        """nint_head_base of a workspace's input slab: image ``x_n0`` pairs with the head call's first image; the feedback
+        channels are the last O of layer 0's input"""
+        cfg = self.cfgs[0]
+        if not 1 <= O <= cfg.Cx:
+            raise ValueError(f"residual head: {O} outputs do not fit the {cfg.Cx} input channels")
+        hb = NintHeadBase()
+        hb.xs, hb.x_n0, hb.Cx, hb.Cxp, hb.c0, hb.xfold_k = ws.xs.data_ptr(), int(x_n0), cfg.Cx, ws.Cxp0, cfg.Cx - O, cfg.k if cfg.xfold else 0
+        return hb
+
+    _DEFAULT_SPEC = None
+
+    @classmethod
+    def _default_spec(cls) -> NintLossSpec:
+        """the spec (1, 1, 0) without output weights: the bits of the plain and _weighted loss entries (include/nint.h), for
+        the residual fused passes, which exist as twins of the _spec entries only"""
+        if cls._DEFAULT_SPEC is None:
+            c = NintLossSpec()
+            c.mse, c.l1, c.huber, c.delta, c.ow, c.now, c.osum = 1.0, 1.0, 0.0, 1.0, None, 0, 0.0
+            cls._DEFAULT_SPEC = c
+        return cls._DEFAULT_SPEC
 
     def _head_args(self, w: torch.Tensor, b: Optional[torch.Tensor]):
         cfg = self.cfgs[-1]
@@ -689,6 +744,11 @@ class SeqEngine:
         t*O + o -- torch.cat of the per-step outputs (model.py:264,272,274 commented code)."""
         Ch, Chp, O, w2, b2 = self._head_args(w, b)
         seq = torch.empty(ws.B, ws.T * O, ws.H, ws.W, dtype=torch.float32, device=self.device)
+        if ws.feedback.res:             # residual head: step t's output + the feedback channels of block t of xs
+            base = self._head_base(ws, O, 0)
+            check(self.lib.nint_head_fwd_seq_res(ptr(ws.h[-1]), ws.B, ws.T, Ch, Chp, O, ptr(w2), ptr(b2), ptr(seq), C.byref(ws.g),
+                                                 self.dt, C.byref(base), stream_ptr()), "nint_head_fwd_seq_res")
+            return seq
         check(self.lib.nint_head_fwd_seq(ptr(ws.h[-1]), ws.B, ws.T, Ch, Chp, O, ptr(w2), ptr(b2), ptr(seq), C.byref(ws.g),
                                          self.dt, stream_ptr()), "nint_head_fwd_seq")
         return seq
@@ -726,8 +786,21 @@ class SeqEngine:
         Ch, Chp, O, w2, b2 = self._head_args(w, b)
         if self._beyond_fused_head(Chp, O):
             return False
-        fn, name, extra = self._loss_entry(seq, weights, spec)
         n0, N, dh = (ws.B, ws.T, ws.dh_seq_slab(self)) if seq else (ws.T * ws.B, ws.B, ws.dh[-1])
+        if ws.feedback.res:
+            # residual head: the _res twin of the _spec entry (the default spec gives the plain / weighted entries' bits);
+            # `scratch` holds NINT_LOSS_SPEC_SCRATCH_FLOATS floats then
+            if scratch.numel() < _lib.NINT_LOSS_SPEC_SCRATCH_FLOATS:
+                raise ValueError("residual head: the fused head / loss pass needs a scratch of NINT_LOSS_SPEC_SCRATCH_FLOATS floats")
+            name = "nint_head_loss_seq_fused_res" if seq else "nint_head_loss_fused_res"
+            wgt, wsum = weights if weights is not None else (None, 0.0)
+            sp = spec if spec is not None else self._default_spec()
+            base = self._head_base(ws, O, 0 if seq else (ws.T - 1) * ws.B)
+            check(getattr(self.lib, name)(ptr(ws.h[-1]), n0, N, Ch, Chp, O, ptr(w2), ptr(b2), ptr(y), ptr(wgt), wsum, C.byref(sp),
+                                          ptr(dpred), ptr(dh), ptr(scratch), ptr(stats), C.byref(ws.g), halo[0], halo[1], Hc, Wc,
+                                          self.dt, C.byref(base), stream_ptr()), name)
+            return True
+        fn, name, extra = self._loss_entry(seq, weights, spec)
         check(fn(ptr(ws.h[-1]), n0, N, Ch, Chp, O, ptr(w2), ptr(b2), ptr(y), *extra, ptr(dpred), ptr(dh),
                  ptr(scratch), ptr(stats), C.byref(ws.g), halo[0], halo[1], Hc, Wc, self.dt, stream_ptr()), name)
         return True
@@ -765,7 +838,7 @@ class SeqEngine:
         sl = None if slots is None else (C.c_int32 * B)(*[int(v) for v in slots])
         sample = torch.empty(B, O, _lib.NINT_SKILL_SAMPLE, dtype=torch.float64, device=self.device)
         scratch = acc.scratch_for(B)
-        if self._beyond_fused_head(Chp, O):
+        if self._beyond_fused_head(Chp, O) or ws.feedback.res:       # (residual head: nint_head_fwd_res + nint_skill_accum, no fused twin)
             pred = self.head_forward(ws, w, b)
             check(self.lib.nint_skill_accum(ptr(pred), ptr(yv), sl, acc.nslots, ptr(acc.row_w), ptr(acc.pix), ptr(sample),
                                             ptr(scratch), scratch.numel() * 8, B, O, ws.H, ws.W, oy, ox, Hc, Wc, stream_ptr()),
@@ -863,7 +936,9 @@ class SeqEngine:
         ``rollout_cotangents`` returned.  BPTT then runs through the fed-back prediction (the roll-out entry, ``seq_grads``
         implied); on return the slab holds g_t, which ``head_backward(images=(B, T*B), write_dh=False)`` reduces to the
         head's gradients.  The returned dx is zero on the fed channels of the fed steps (under a feed mask: of the fed images
-        of each step) -- the forward pass overwrote them."""
+        of each step) -- the forward pass overwrote them.  On a residual-head workspace the roll-out entry is
+        the _residual one, and the returned dx carries + g_t on the feedback channels of every unfed (t, b): d p_t / d x_t = 1
+        there.  (A residual window in which nothing was fed has no slab: its caller adds the head cotangents, add_skip_dx.)"""
         assert ws.train
         fed = bool(ws.feedback.fed)
         if rollout is not None and not ws.feedback.grad:
@@ -934,6 +1009,8 @@ class SeqEngine:
                 check(self.lib.nint_unpack_compact(ptr(dx), ptr(tb), ws.T * ws.B, C0, ws.Cxp0, ws.H, ws.W, self.dt, stream_ptr()),
                       "unpack dx")
             dx_out = tb.view(ws.T, ws.B, C0, ws.H, ws.W).transpose(0, 1).contiguous()
+            if rg is not None and ws.feedback.res:      # residual head: the skip path into the input, g_t from the slab
+                self.add_skip_dx(dx_out, ws.fb.O, slab=rollout)
             if rg is not None:              # the caller's x never reached those channels
                 if ws.feedback.mask is not None:
                     m = ws.feedback.fed_mask.to(self.device)        # (T*B bytes, a plain copy: the pinned buffer is the next pass's)
@@ -941,6 +1018,22 @@ class SeqEngine:
                 else:
                     dx_out[:, ws.feedback.fed.start:, C0 - ws.fb.O:] = 0
         return dWs, dbs, dx_out
+
+    @staticmethod
+    def add_skip_dx(dx: torch.Tensor, O: int, slab: Optional[torch.Tensor] = None, dseq: Optional[torch.Tensor] = None,
+                    dpred: Optional[torch.Tensor] = None):
+        """Residual head: d p_t / d x_t[feedback channels] = 1, so the input gradient ``dx`` (B, T, C, H, W) gains the total
+        cotangent of p_t on its last O channels -- from the roll-out slab (T*B, O, H, W), image t*B + b, which came back
+        holding g_t, or from the cotangents of a window in which nothing was fed: ``dseq`` (B, T*O, H, W) and / or ``dpred``
+        (B, O, H, W), which joins step T-1.  A boundary operation on the result, in place; the caller zeroes the fed (t, b)."""
+        B, T, C0, H, W = dx.shape
+        fbc = dx[:, :, C0 - O:]
+        if slab is not None:
+            fbc += slab.view(T, B, O, H, W).transpose(0, 1)
+        if dseq is not None:
+            fbc += dseq.detach().reshape(B, T, O, H, W)
+        if dpred is not None:
+            fbc[:, T - 1] += dpred.detach().reshape(B, O, H, W)
 
     @staticmethod
     @contextlib.contextmanager

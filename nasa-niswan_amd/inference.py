@@ -278,7 +278,7 @@ def evaluate_skill(net, dataset, batch_size: int = 8, halo: Tuple[int, int] = (5
         B, T, _, H, W = X.shape
         with eng.window(B, T, H, W, False, False) as ws:
             net._pack_weights(eng)
-            eng.forward(ws, X)
+            eng.forward(ws, X, residual=_residual(net))
             acc.update(eng, ws, net.conv.weight, net.conv.bias, y, slots_all[s:s + B], pred_out=None if preds is None else preds[s:s + B])
     return (acc, preds) if return_predictions else acc
 
@@ -305,7 +305,9 @@ def predict_stream(net, dataset, lanes: int = 1, halo: Tuple[int, int] = (5, 5),
     `closed_loop` (a ``ConvLSTM(feedback=True)``): the model runs on its own prediction.  The first chunk
     takes its first `spinup` >= 1 steps from the dataset (the spin-up on analysis data) and feeds the head's output back
     from step `spinup` on; every later chunk is fed from its step 0, from the head of the carried state -- so the walk
-    equals ONE closed-loop window over the whole period, bit for bit.  With `lanes` > 1 every lane spins up on its own
+    equals ONE closed-loop window over the whole period, bit for bit.  (A residual head, DESIGN.md 4.22: a later chunk's
+    step 0 receives the previous chunk's last prediction through the pack instead, and is fed from its step 1 -- the same
+    bits: the pack rounds as the feedback launch does.)  With `lanes` > 1 every lane spins up on its own
     first chunk (the lanes' first chunks are one batch)."""
     from .dataset import stateful_schedule
     if closed_loop:
@@ -325,7 +327,7 @@ def predict_stream(net, dataset, lanes: int = 1, halo: Tuple[int, int] = (5, 5),
     eng = net._engine(dev)
     out = torch.empty(B, K * T, O, Hc, Wc, dtype=torch.float32, device=dev)
     dv = dataset._device_arrays() if skill is not None else None
-    state = None
+    state, last, res = None, None, _residual(net)
     for k in range(K):
         X, _ = dataset.slab_batch(sched[k])
         _, _, _, H, W = X.shape
@@ -334,9 +336,18 @@ def predict_stream(net, dataset, lanes: int = 1, halo: Tuple[int, int] = (5, 5),
             if state is not None:
                 eng.load_state(ws, state)
             fb = (net.conv.weight, net.conv.bias, int(spinup) if k == 0 else 0) if closed_loop else None
-            eng.forward(ws, X, feedback=fb)
+            if fb is not None and k > 0 and res:
+                # residual head: a chunk cannot be fed at its step 0 (the base of that value lies in the chunk before), so the
+                # previous chunk's last prediction is packed into the feedback channels of step 0 -- the pack rounds exactly
+                # as the feedback kernel does -- and the chunk is fed from step 1.  The chunk travels as an f32 tensor for that
+                # (device_batch: the same values the slab fill writes, through the pack kernel).
+                X, _ = dataset.device_batch(sched[k])
+                X[:, 0, X.shape[2] - O:] = last
+                fb = (net.conv.weight, net.conv.bias, 1)
+            eng.forward(ws, X, feedback=fb, residual=res)
             state = eng.save_state(ws, state)
             seq = eng.head_forward_seq(ws, net.conv.weight, net.conv.bias)             # (B, T*O, H, W), channel t*O + o
+            last = seq[:, (T - 1) * O:]                 # p_{T-1} on the whole grid: what the next chunk's step 0 is fed
         out[:, k * T:(k + 1) * T] = seq.view(B, T, O, H, W)[:, :, :, halo[0]:halo[0] + Hc, halo[1]:halo[1] + Wc]
         if skill is not None:
             t0s = [int(dataset.first[int(i)]) for i in sched[k]]
@@ -345,6 +356,11 @@ def predict_stream(net, dataset, lanes: int = 1, halo: Tuple[int, int] = (5, 5),
     first = int(dataset.first[0])
     steps = np.concatenate([first + int(sched[0, b]) + np.arange(K * T, dtype=np.int64) for b in range(B)])
     return out.view(B * K * T, O, Hc, Wc), steps, dropped
+
+
+def _residual(net):
+    """SeqEngine.forward's ``residual`` argument for a model: its number of head outputs if it has a residual head, else False"""
+    return net.conv.weight.shape[0] if getattr(net, "residual", False) else False
 
 
 def _step_targets(dataset, dv, t0s, T):
@@ -403,7 +419,7 @@ def rollout_skill(net, dataset, starts: Sequence[int], horizon: int, spinup: int
         oy, ox = ((H - Hc) // 2, (W - Wc) // 2) if halo is None else halo
         with eng.window(B, T, H, W, False, False) as ws:
             net._pack_weights(eng)
-            eng.forward(ws, X, feedback=(net.conv.weight, net.conv.bias, spinup))
+            eng.forward(ws, X, feedback=(net.conv.weight, net.conv.bias, spinup), residual=_residual(net))
             seq = eng.head_forward_seq(ws, net.conv.weight, net.conv.bias).view(B, T, O, H, W)
         y = _step_targets(dataset, dv, t0s, T)                                    # (B, T, L, Hc, Wc)
         free = seq[:, spinup:].reshape(B * horizon, O, H, W)

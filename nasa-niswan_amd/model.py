@@ -31,7 +31,7 @@ import torch
 import torch.nn as nn
 from torch._C import _functions
 
-from .engine import ConvLSTMState, Feedback, LayerCfg, SeqEngine, dtype_code
+from .engine import RESIDUAL_STEP0, ConvLSTMState, Feedback, LayerCfg, SeqEngine, dtype_code
 
 __all__ = ["ConvLSTMCell", "ConvLSTM", "ConvLSTMState"]
 
@@ -121,9 +121,10 @@ class _CallOpts:
     """the non-tensor arguments of _ConvLSTMFn: the device state that comes in (or None), what goes out, the box the outgoing
     device state is handed back in (a Function's outputs are tensors), and the default route's head-backward rule"""
 
-    def __init__(self, state_in=None, return_state=False, seq_always=False, free_from=None, feedback_grad=False):
+    def __init__(self, state_in=None, return_state=False, seq_always=False, free_from=None, feedback_grad=False, residual=False):
         self.state_in, self.return_state, self.state_out = state_in, return_state, None
         self.free_from = free_from      # closed loop from this step on (ConvLSTM(feedback=True)); None: open loop
+        self.residual = residual        # the module's head predicts the increment (ConvLSTM(residual=True), DESIGN.md 4.22)
         # ... or a (B, T) feed mask (scheduled sampling, DESIGN.md 4.21); `first`: the first step that feeds anything
         self.first = free_from if free_from is None or isinstance(free_from, int) else Feedback.first_fed(free_from)
         self.feedback_grad = feedback_grad and free_from is not None    # ... and differentiated through what it feeds back (4.19)
@@ -165,7 +166,7 @@ class _ConvLSTMFn(torch.autograd.Function):
             eng.load_state(ws, opts.state_in)
         h0, c0 = (list(st[0::2]), list(st[1::2])) if st else (None, None)
         eng.forward(ws, x, h0, c0, feedback=None if opts.free_from is None else (head_w, head_b, opts.free_from),
-                    feedback_grad=rollout)
+                    feedback_grad=rollout, residual=head_w.shape[0] if opts.residual else False)
         outs = [eng.head_forward(ws, head_w, head_b)]
         if module.return_sequence:
             outs.append(eng.head_forward_seq(ws, head_w, head_b))       # every step in one launch
@@ -219,6 +220,8 @@ class _ConvLSTMFn(torch.autograd.Function):
         dWs, dbs, dx = eng.backward(ws, ctx.x_needs_grad, seq_grads=seq_grads, zero_mask=mask, train_from=f, rollout=slab)
         if slab is not None:
             dw_head, db_head = eng.rollout_head_backward(ws, head_w, slab)
+        elif dx is not None and ws.feedback.res:        # residual head, nothing fed: the skip path into x is the head cotangent
+            eng.add_skip_dx(dx, head_w.shape[0], dseq=dseq, dpred=dpred)
         dstate = []
         if ctx.nst:
             for l in range(L):
@@ -322,7 +325,7 @@ class ConvLSTM(_EngineOwner, nn.Module):
     """reference model.py:234-274"""
 
     def __init__(self, input_channels, hidden_channels, kernel_size, num_layers, *, out_channels=1,
-                 return_sequence=False, compute_dtype="f32", lon_cyclic=False, feedback=False):
+                 return_sequence=False, compute_dtype="f32", lon_cyclic=False, feedback=False, residual=False):
         super().__init__()
         assert len(hidden_channels) == num_layers, 'The length of hidden_channels must be equal to num_layers.'
         # closed loop (DESIGN.md 4.18): the last out_channels input channels are FEEDBACK channels, which forward(free_from=s)
@@ -332,6 +335,12 @@ class ConvLSTM(_EngineOwner, nn.Module):
         if self.feedback and not 1 <= out_channels <= input_channels:
             raise ValueError(f"ConvLSTM(feedback=True): the {out_channels} head outputs are fed back into the last input channels, "
                              f"so out_channels <= input_channels ({input_channels}) is required")
+        # residual head: the head predicts the tracer's tendency, p_t = x_t[feedback channels] + head(h_t), x_t
+        # as the model saw it.  Like `feedback`: not a parameter, not in the state_dict.
+        self.residual = bool(residual)
+        if self.residual and not self.feedback:
+            raise ValueError("ConvLSTM(residual=True) needs feedback=True: the increment is added to the feedback channels, the last "
+                             "out_channels input channels")
         self.num_layers = num_layers
         self.layers = nn.ModuleList()
         self.layers.append(ConvLSTMCell(input_channels, hidden_channels[0], kernel_size[0], compute_dtype=compute_dtype))
@@ -388,7 +397,13 @@ class ConvLSTM(_EngineOwner, nn.Module):
         and on ``x`` where it is not.  ``M[b, t] = (t >= s)`` is ``free_from = s`` bit for bit; an all-zero mask is the open
         loop.  What ``free_from`` refuses is refused here by the first column that feeds anything: column 0 set needs a
         ``state`` and is forward only; under grad the call needs ``feedback_grad=True``.  The gradient of ``x`` is zero on the
-        fed channels of the fed (b, t) only.  At most 64 images per call."""
+        fed channels of the fed (b, t) only.  At most 64 images per call.
+
+        A ``residual=True`` module honours all of it with p_t = x_t[feedback channels] + head(h_t): ``pred``,
+        ``seq`` and the fed value are that p; the gradient of ``x`` gains the cotangent of p_t on the feedback channels of
+        every step that saw ``x`` (zero on the fed ones, as above).  ``free_from = 0`` and a mask with column 0 set are
+        refused, state or not: the value fed at step 0 would be the prediction of a step before the window, which has no
+        input to be added to."""
         if free_mask is not None:                       # the refusals of free_from, by the first column with a fed image
             if free_from is not None:
                 raise ValueError("free_mask and free_from are exclusive: the mask says for every step what free_from says for all")
@@ -398,6 +413,8 @@ class ConvLSTM(_EngineOwner, nn.Module):
                 raise ValueError(f"ConvLSTM: x must be (B, T, C, H, W), got {tuple(x.shape)}")
             mask = Feedback.mask_bt(free_mask, x.shape[0], x.shape[1])
             first = Feedback.first_fed(mask)
+            if first == 0 and self.residual:
+                raise ValueError(RESIDUAL_STEP0)
             if first == 0 and state is None:
                 raise ValueError("free_mask with column 0 set feeds step 0 from the head of the initial state: pass a state")
             if first < x.shape[1] and not (feedback_grad and first >= 1) and self._wants_grad(x, state):
@@ -415,6 +432,8 @@ class ConvLSTM(_EngineOwner, nn.Module):
             free_from = int(free_from)
             if len(x.shape) != 5:
                 raise ValueError(f"ConvLSTM: x must be (B, T, C, H, W), got {tuple(x.shape)}")
+            if free_from == 0 and self.residual:
+                raise ValueError(RESIDUAL_STEP0)
             if free_from == 0 and state is None:
                 raise ValueError("free_from=0 feeds step 0 from the head of the initial state: pass a state")
             if free_from < x.shape[1] and not (feedback_grad and free_from >= 1) and self._wants_grad(x, state):
@@ -435,7 +454,8 @@ class ConvLSTM(_EngineOwner, nn.Module):
             wb += [cell.conv.weight, cell.conv.bias]
         st = []
         if state is None and not return_state:          # the default call: nothing to validate, and its own head-backward rule
-            opts = _CallOpts(seq_always=self.return_sequence, free_from=free_from, feedback_grad=bool(feedback_grad))
+            opts = _CallOpts(seq_always=self.return_sequence, free_from=free_from, feedback_grad=bool(feedback_grad),
+                             residual=self.residual)
         else:
             if return_state not in (False, True, "device"):
                 raise ValueError(f"return_state must be False, True or 'device', got {return_state!r}")
@@ -449,7 +469,7 @@ class ConvLSTM(_EngineOwner, nn.Module):
                 hs, cs = eng._state_tensors(state, (B, H, W))
                 st = _interleave(hs, cs)
             opts = _CallOpts(state if isinstance(state, ConvLSTMState) else None, return_state, free_from=free_from,
-                             feedback_grad=bool(feedback_grad))
+                             feedback_grad=bool(feedback_grad), residual=self.residual)
         out = _ConvLSTMFn.apply(self, torch.is_grad_enabled(), opts, x, self.conv.weight, self.conv.bias, *wb, *st)
         out = list(out) if isinstance(out, tuple) else [out]
         n0 = 2 if self.return_sequence else 1

@@ -7,7 +7,7 @@ stepped once per epoch before validation, checkpoint every 10 epochs); the per-b
 once per epoch.  Added flags: --dtype, --levels, --grid, --synthetic-steps, --pad-mode, --f32-inputs,
 --static-channels, --sequence-loss, --test-skill, --lat-weighted-loss, --loss-weights, --clip-grad-norm,
 --skip-nonfinite-steps, --stateful, --bptt-segments, --accumulate-steps, --loss-mix, --huber-delta, --output-weights,
---spinup-steps, --rollout-from, --sampling-prob, --sampling-ramp-epochs, --sampling-seed.
+--spinup-steps, --rollout-from, --sampling-prob, --sampling-ramp-epochs, --sampling-seed, --residual-head.
 
 The data path is on the device too: by default every batch is written by ONE launch of the
 fuse / z-score / halo-pad kernel straight into the model's bf16 input slab (dataset.slab_batch);
@@ -152,6 +152,11 @@ def get_arguments(argv=None, MODEL='LSTM-00', SPECIES='bcb', LEARNING_RATE=1.0E-
                         help="with --sampling-prob P: the probability rises linearly from 0 to P over the first E epochs (set once "
                              "per epoch, printed with the epoch line); 0: P from the first epoch")
     parser.add_argument("--sampling-seed", type=int, default=0, help="the coin's seed (each rank draws from seed + rank)")
+    parser.add_argument("--residual-head", action="store_true",
+                        help="with --tracer-input: the head predicts the tracer's TENDENCY -- every step's prediction is the tracer "
+                             "the step was given (its last --levels input channels) plus the head's output "
+                             "(ConvLSTM(residual=True)); stored with the snapshot's arguments.  Resuming a checkpoint that was "
+                             "trained without it is refused unless --reset-optimizer asks for fine-tuning")
     parser.add_argument("--reset-optimizer", action="store_true",
                         help="with --use-checkpoint: load the weights of --restore-from only and start the optimizer afresh "
                              "(the fine-tuning entry point; without it an optimizer state of other param groups is an error)")
@@ -177,6 +182,15 @@ def get_arguments(argv=None, MODEL='LSTM-00', SPECIES='bcb', LEARNING_RATE=1.0E-
             parser.error("--rollout-from must be >= 1: step 0 has no prediction to be fed")
         if args.stateful or (args.bptt_segments or 1) > 1 or args.freeze_layers > 0:
             parser.error("--rollout-from is not combined with --stateful, --bptt-segments or --freeze-layers")
+    if args.residual_head and not args.tracer_input:
+        parser.error("--residual-head needs --tracer-input: the increment is added to the tracer of the step before, the model's "
+                     "feedback channels")
+    if args.residual_head and args.use_checkpoint and not args.reset_optimizer:
+        was = checkpoint_residual_head(args.restore_from)
+        if was is False:
+            parser.error(f"--residual-head: the checkpoint under {args.restore_from} was trained without it (its head predicts the "
+                         "state, not the increment, and its optimizer moments belong to that head); pass --reset-optimizer to "
+                         "fine-tune its weights as a residual model")
     if args.sampling_prob is not None:
         if args.rollout_from is None:
             parser.error("--sampling-prob needs --rollout-from: the coin is thrown for the steps from --rollout-from on")
@@ -201,6 +215,18 @@ def get_arguments(argv=None, MODEL='LSTM-00', SPECIES='bcb', LEARNING_RATE=1.0E-
         with open(os.path.join(args.snapshot_dir, 'configurations.json'), "w") as f:     # train.py:221-225
             json.dump(vars(args), f, indent=4)
     return args
+
+
+def checkpoint_residual_head(restore_from: str):
+    """Whether the run that wrote the checkpoint directory ``restore_from`` had --residual-head, from the configurations.json
+    stored with the snapshot (in the directory itself or the one above it: checkpoints lie in epoch-NNN below --snapshot-dir);
+    None where no such file is found.  A run from before the flag existed was trained without it."""
+    for d in (restore_from, os.path.dirname(os.path.abspath(restore_from))):
+        path = os.path.join(d, 'configurations.json')
+        if os.path.isfile(path):
+            with open(path) as f:
+                return bool(json.load(f).get('residual_head', False))
+    return None
 
 
 def sampling_prob_of(epoch: int, P, ramp_epochs: int):
@@ -262,7 +288,8 @@ def main(args):
     in_ch = args.in_channels + (args.levels if args.tracer_input else 0)      # the tracer of the step before: --levels more channels
     generator = pkg.ConvLSTM(in_ch, list(args.hidden_channels), list(args.kernel_size), args.num_layers,
                              out_channels=out_ch, compute_dtype=args.dtype,
-                             lon_cyclic=args.cyclic_longitude, feedback=args.tracer_input).to(dev)  # train.py:48
+                             lon_cyclic=args.cyclic_longitude, feedback=args.tracer_input,
+                             residual=args.residual_head).to(dev)                                   # train.py:48
     H, W = (int(v) for v in args.grid)
     if args.input_size[0] < H or args.input_size[1] < W:
         raise SystemExit(f"--input-size {tuple(args.input_size)} is smaller than --grid {(H, W)}: the model runs on the "

@@ -32,6 +32,11 @@
     [rollout_from = s, sampling_prob = p]   -> SCHEDULED SAMPLING: per step t >= s and per image a coin of
                                                bias p decides whether the image sees its own last prediction; the same step
                                                under that feed mask (the _sampled entries).  p = 1: the line above, call for call
+    [ConvLSTM(residual=True)]               -> RESIDUAL HEAD: every head / loss pass adds the feedback channels of the
+                                               step's own input to the head's output (the _res entries); with rollout_from the
+                                               closed loop and its backward are the _residual entries.  Every other option
+                                               composes: the base of a step is that step's input, so no segment, chunk or
+                                               micro-batch boundary is crossed
     [accumulate_steps = k]                  -> k micro-batches add into the bucket (accumulate = 1 from the second on); the
                                                all-reduce and ONE Adam launch with grad_scale = 1/(k world) on the k-th
 
@@ -248,7 +253,7 @@ class FusedTrainer:
         wts, spec, B, T, H, W, O, Hc, Wc, yv = self._call_facts(X, y)
         ws = eng.acquire(B, T, H, W, train, False)          # (handed to the caller still acquired: no `with eng.window`)
         m._pack_weights(eng)
-        eng.forward(ws, X)
+        eng.forward(ws, X, **self._res_kw())
         dpred = None
         if train:
             shape = (B, T * O if self.sequence_loss else O, H, W)
@@ -257,6 +262,12 @@ class FusedTrainer:
             dpred = self._dpred
         pred = self._head_loss_unfused(eng, ws, yv, dpred, B, T, O, H, W, Hc, Wc, wts, spec)
         return eng, ws, pred, dpred
+
+    def _res_kw(self) -> dict:
+        """the ``residual`` argument of every forward pass of a residual-head model, nothing otherwise: the
+        calls of any other model are, argument for argument, what they were.  The base of step t is the input of step t itself,
+        so segments (bptt_segments) and carried state (stateful) need nothing more: no base crosses a boundary."""
+        return dict(residual=self.model.conv.weight.shape[0]) if getattr(self.model, "residual", False) else {}
 
     def reset_state(self):
         """stateful: the next step() starts every lane from the zero state (a new epoch, a new record)"""
@@ -425,7 +436,8 @@ class FusedTrainer:
             if carried is not None:
                 eng.load_state(ws, carried)          # carried state -> slot 0
             feed = self._draw(T, B)     # (None: nothing is fed -- the step it was)
-            eng.forward(ws, X, **(dict(feedback=(m.conv.weight, m.conv.bias, feed), feedback_grad=True) if feed is not None else {}))
+            eng.forward(ws, X, **(dict(feedback=(m.conv.weight, m.conv.bias, feed), feedback_grad=True) if feed is not None else {}),
+                        **self._res_kw())
             if carried is not None:
                 eng.save_state(ws, carried)          # slot T -> carried state; BPTT below stops at the chunk start
                 self._drop_nonfinite_lanes(carried)
@@ -480,11 +492,11 @@ class FusedTrainer:
             for t0, _ in plan[:-1]:
                 eng.load_state(wf, states[-1])
                 eng.zero_start(wf, carried is None and t0 == 0)
-                eng.forward(wf, seg(t0))
+                eng.forward(wf, seg(t0), **self._res_kw())
                 states.append(eng.save_state(wf))        # slot S -> a new state: the start of the next segment
         with eng.window(B, S, H, W, True, True, f) as ws:
             eng.load_state(ws, states[-1])
-            eng.forward(ws, seg(plan[-1][0]))
+            eng.forward(ws, seg(plan[-1][0]), **self._res_kw())
             if carried is not None:
                 self.state = eng.save_state(ws)          # (a new object: the chunk's start state above stays what it was)
                 self._drop_nonfinite_lanes(self.state)
@@ -496,7 +508,7 @@ class FusedTrainer:
             for j in range(n - 2, -1, -1) if f < L else ():      # (the head alone: its gradient is the last segment's)
                 eng.load_state(ws, states[j])
                 eng.zero_start(ws, carried is None and j == 0)
-                eng.forward(ws, seg(plan[j][0]))
+                eng.forward(ws, seg(plan[j][0]), **self._res_kw())
                 eng.backward(ws, False, zero_state_grads=(), dW_out=self._dW, db_out=self._db, accumulate=True, train_from=f)
             mark()
 

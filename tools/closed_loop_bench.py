@@ -46,6 +46,7 @@ def main():
     ap.add_argument("--ks", default="5,3,3")
     ap.add_argument("--free-from", type=int, default=1)
     ap.add_argument("--zero-pad", action="store_true", help="zero padding instead of cyclic longitude")
+    ap.add_argument("--residual", action="store_true", help="the residual head (DESIGN.md 4.22): the closed-loop passes of (a) feed round(x + head)")
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--iters", type=int, default=20)
     args = ap.parse_args()
@@ -64,10 +65,10 @@ def main():
     out = {}
 
     def closed():
-        eng.forward(ws, X, feedback=(w, b, s))
+        eng.forward(ws, X, feedback=(w, b, s), **({"residual": O} if args.residual else {}))
 
     def closed_seq():
-        eng.forward(ws, X, feedback=(w, b, s))
+        eng.forward(ws, X, feedback=(w, b, s), **({"residual": O} if args.residual else {}))
         out["closed"] = eng.head_forward_seq(ws, w, b)
 
     def open_(wave):

@@ -50,6 +50,14 @@ after the shape.
                 substituted where the mask says, and against tests/sampled_model.py.  Where no image is fed at step 0: outputs,
                 every parameter gradient and dx under drawn cotangents against the model under CPU autograd.  --self-check:
                 the reference of the first case with a mixed step feeds every image from the first fed step on.
+  --residual    ``ConvLSTM(feedback=True, residual=True)(x[, state], free_from=F | free_mask=M[, feedback_grad=True])`` (the residual
+                head, DESIGN.md 4.22: p_t = x_t[feedback channels] + head(h_t)) with a drawn stack, grid, number of feedback
+                channels, storage type, boundary, input layout, state, and either a first fed step F >= 1 (T: nothing fed) or a
+                (B, T) feed mask with column 0 clear.  Forward: bit for bit the residual open-loop pass over the input with the
+                predictions substituted where fed, and against tests/residual_model.py.  Then outputs, every parameter gradient
+                and dx (the skip add on the unfed feedback channels, zeros on the fed ones) under drawn cotangents against the
+                model under CPU autograd.  --self-check: the reference of the first case loses the base (the non-residual
+                model, tests/sampled_model.py).
   --self-check  (with one of these modes) after the first passing case to which a fault applies, the REFERENCE is corrupted on
                 the host and the same comparison of the same device results must fail: --state: the oracle gets a zero c0
                 for the last layer; --train-opts with n >= 2: the oracle back-propagates the last segment only (truncated
@@ -113,6 +121,9 @@ ALL_STREAM_MODES = STREAM_MODES + LATE_MODES
 # own (case_rng), so that no earlier mode's draws move.
 SAMPLED_MODES = ("sampled",)
 SAMPLED_KEY = 1000              # the stream key of SAMPLED_MODES[i] is SAMPLED_KEY + i
+# ... and SAMPLED_MODES is pinned too (tests/test_sampled_cpu.py): the residual head's mode has its own tuple and key
+RESIDUAL_MODES = ("residual",)
+RESIDUAL_KEY = 2000             # the stream key of RESIDUAL_MODES[i] is RESIDUAL_KEY + i
 LIM = {"f32": 1e-3, "bf16": 3e-2}
 LOSS_LIM = {"f32": 2e-6, "bf16": 2e-2}
 
@@ -260,6 +271,8 @@ def case_rng(seed: int, mode: str, it: int):
     """the generator of one case of a state / options mode: its own stream, so a case replays without the ones before it"""
     if mode in SAMPLED_MODES:
         return np.random.default_rng([int(seed), SAMPLED_KEY + SAMPLED_MODES.index(mode), int(it)])
+    if mode in RESIDUAL_MODES:
+        return np.random.default_rng([int(seed), RESIDUAL_KEY + RESIDUAL_MODES.index(mode), int(it)])
     return np.random.default_rng([int(seed), 1 + ALL_STREAM_MODES.index(mode), int(it)])
 
 
@@ -278,6 +291,8 @@ def draw_case(rng, it: int, mode: str = "plain", big: bool = False, wide: bool =
         return draw_rollout(rng, it)
     if mode == "sampled":
         return draw_sampled(rng, it)
+    if mode == "residual":
+        return draw_residual(rng, it)
     new = mode in NEW_MODES
     L = int(rng.integers(1, 5))
     hidden = [int(rng.choice([4, 8, 16, 24, 32, 48, 64] if new else [4, 8, 16, 24, 32, 48, 64, 64, 128])) for _ in range(L)]
@@ -470,6 +485,38 @@ def draw_sampled(rng, it: int) -> dict:
                     f"sampled mask={rows_} cyclic={int(cyclic)} fold={int(fold)} state={int(with_state)} cotangents={cot}")
 
 
+def draw_residual(rng, it: int) -> dict:
+    """--residual: a stack, a grid, O feedback channels, both storage types, cyclic longitude or zero padding, the thin-input fold
+    allowed or off, a tensor state or none, and what is fed -- a first fed step F in {1, the middle, T-1, T: nothing} or a (B, T)
+    feed mask of a drawn density with column 0 clear (a residual head is never fed at step 0) -- and cotangents on the per-step
+    outputs, on the last one, or on both.  Pure."""
+    L = int(rng.integers(1, 4))
+    hidden = [int(rng.choice([4, 8, 16, 24, 32, 64])) for _ in range(L)]
+    ks = [int(rng.choice([1, 3, 3, 5, 5])) for _ in range(L)]
+    C = int(rng.choice([1, 3, 4, 6, 16, 33, 40, 62]))
+    out = min(C, int(rng.choice([1, 1, 2, 3, 20])))
+    B, T = int(rng.integers(1, 5)), int(rng.integers(3, 7))
+    H, W = int(rng.integers(5, 21)), int(rng.integers(9, 41))
+    dtype = "f32" if it % 2 == 0 else "bf16"
+    wave, rows = WAVES[it % 7], TILE_ROWS[it % 4]
+    cyclic, fold, with_state, masked = (bool(rng.integers(0, 2)) for _ in range(4))
+    fb_from = [1, max(T // 2, 1), T - 1, T][int(rng.integers(0, 4))]
+    density = float(rng.choice([0.25, 0.5, 0.5, 0.75, 1.0]))
+    mask = (rng.random((B, T)) < density).astype(int)
+    mask[:, 0] = 0
+    cot = ["seq", "last", "both"][int(rng.integers(0, 3))]
+    draws = [("X", (B, T, C, H, W)), ("dseq", (B, T * out, H, W)), ("dpred", (B, out, H, W))]
+    if with_state:
+        for l, ch in enumerate(hidden):
+            draws += [(f"{n}.{l}", (B, ch, H, W)) for n in ("h0", "c0")]
+    what = "mask=" + "/".join("".join(str(int(v)) for v in r) for r in mask) if masked else f"from {fb_from}"
+    return dict(it=it, mode="residual", L=L, hidden=hidden, ks=ks, C=C, out=out, B=B, T=T, H=H, W=W, dtype=dtype, wave=wave,
+                rows=rows, wide=0, cyclic=cyclic, fold=fold, with_state=with_state, fb_from=fb_from,
+                mask=mask.tolist() if masked else None, cot=cot, draws=draws,
+                tag=f"#{it} C={C} hidden={hidden} k={ks} out={out} B={B} T={T} {H}x{W} {dtype} wave={wave} rows={rows} "
+                    f"residual {what} cyclic={int(cyclic)} fold={int(fold)} state={int(with_state)} cotangents={cot}")
+
+
 def draw_data(rng, case) -> dict:
     """the standard-normal tensors of a case, f32, from the generator that drew it"""
     return {name: torch.from_numpy(rng.standard_normal(sh).astype(np.float32)) for name, sh in case["draws"]}
@@ -480,7 +527,7 @@ def draw_cases(seed: int, n: int, mode: str = "plain", big: bool = False, wide: 
     cases = []
     rng = np.random.default_rng(seed)
     for it in range(n):
-        if mode in ALL_STREAM_MODES + SAMPLED_MODES:
+        if mode in ALL_STREAM_MODES + SAMPLED_MODES + RESIDUAL_MODES:
             cases.append(draw_case(case_rng(seed, mode, it), it, mode))
         else:
             cases.append(draw_case(rng, it, mode, big, wide))
@@ -1107,21 +1154,23 @@ def parse(argv=None):
     ap.add_argument("--closed-loop", action="store_true", help="ConvLSTM(feedback=True)(x[, state], free_from=s): the per-step predictions of a drawn stack, grid, number of feedback channels, first fed step, state, storage type, boundary condition and input layout against the CPU model tests/closed_loop_model.py, and bit for bit against the open-loop pass over the input with those predictions substituted")
     ap.add_argument("--rollout", action="store_true", help="ConvLSTM(feedback=True)(x, free_from=F, feedback_grad=True): outputs, every parameter gradient and dx of a drawn stack, grid, number of feedback channels, first fed step F >= 1, storage type, boundary condition, input layout and cotangents (per step, last step, both) against the CPU model tests/rollout_model.py under CPU autograd in f64")
     ap.add_argument("--sampled", action="store_true", help="ConvLSTM(feedback=True)(x[, state], free_mask=M[, feedback_grad=True]): a drawn stack, grid, number of feedback channels, storage type, boundary condition, input layout, state and (B, T) feed mask of a drawn density.  Forward: the per-step predictions against the CPU model tests/sampled_model.py and bit for bit against the open-loop pass over the input with those predictions substituted where the mask says.  Without a fed image at step 0: outputs, every parameter gradient and dx under drawn cotangents (per step or last step) against the model under CPU autograd in f64.  --self-check: the reference of the first case with a mixed step is computed as if every image were fed from the first fed step on")
-    ap.add_argument("--self-check", action="store_true", help="with --state / --train-opts / --stateful / --finetune / --sampled: corrupt the reference after the first passing case and require the comparison to fail")
+    ap.add_argument("--residual", action="store_true", help="ConvLSTM(feedback=True, residual=True)(x[, state], free_from=F | free_mask=M[, feedback_grad=True]): a drawn stack, grid, number of feedback channels, storage type, boundary condition, input layout, state and first fed step F >= 1 or (B, T) feed mask with column 0 clear.  Forward: the per-step predictions p_t = x_t[feedback channels] + head(h_t) against the CPU model tests/residual_model.py and bit for bit against the residual open-loop pass over the input with those predictions substituted where fed.  Then outputs, every parameter gradient and dx under drawn cotangents against the model under CPU autograd in f64.  --self-check: the reference of the first case is the non-residual model (the base dropped)")
+    ap.add_argument("--self-check", action="store_true", help="with --state / --train-opts / --stateful / --finetune / --sampled / --residual: corrupt the reference after the first passing case and require the comparison to fail")
     ap.add_argument("--guarded", action="store_true", help="every mode: the device side of each case allocates through oracle/guarded_alloc.py in poison mode (guards around every buffer, `empty` payloads 0xFF), its inputs and parameters in arenas of their own; the comparison stays what it is and every guard byte is checked after each case.  With --self-check (any mode): one guard byte is flipped after the first passing case and the check has to fail (the reference is then not corrupted)")
     ap.add_argument("--list", action="store_true", help="print the drawn cases as JSON lines and exit (no GPU, the package is not imported)")
     ap.add_argument("--only", type=int, default=-1, help="replay the random stream up to this iteration and run it alone, printing every tensor's error")
     ap.add_argument("--force-wave", type=int, default=None, help="with --only: nint_seq.wave for the replayed case instead of the rotation's value")
     ap.add_argument("--force-dtype", choices=["f32", "bf16"], default=None, help="with --only: the storage type of the replayed case instead of the alternation's (is the miss the arithmetic's, or the storage type's?)")
     args = ap.parse_args(argv)
-    modes = [m for m in ("dataset", "cell", "trainer", "state", "train_opts", "stateful", "finetune", "closed_loop", "rollout", "sampled") if getattr(args, m)]
+    modes = [m for m in ("dataset", "cell", "trainer", "state", "train_opts", "stateful", "finetune", "closed_loop", "rollout", "sampled",
+                         "residual") if getattr(args, m)]
     if len(modes) > 1 and not all(m in OLD_MODES for m in modes):
-        ap.error("one of --state / --train-opts / --stateful / --finetune / --closed-loop / --rollout / --sampled at a time, and none of the other modes with it")
+        ap.error("one of --state / --train-opts / --stateful / --finetune / --closed-loop / --rollout / --sampled / --residual at a time, and none of the other modes with it")
     args.mode = modes[0] if modes else "plain"          # (--dataset before --cell before --trainer, as ever)
-    if args.mode in ("closed_loop", "rollout", "sampled") and (args.big or args.wide):
-        ap.error("--closed-loop / --rollout / --sampled draw their own shapes: not with --big / --wide")
-    if args.self_check and args.mode not in NEW_MODES + SAMPLED_MODES and not args.guarded:
-        ap.error("--self-check needs --state, --train-opts, --stateful, --finetune or --sampled (or --guarded)")
+    if args.mode in ("closed_loop", "rollout", "sampled", "residual") and (args.big or args.wide):
+        ap.error("--closed-loop / --rollout / --sampled / --residual draw their own shapes: not with --big / --wide")
+    if args.self_check and args.mode not in NEW_MODES + SAMPLED_MODES + RESIDUAL_MODES and not args.guarded:
+        ap.error("--self-check needs --state, --train-opts, --stateful, --finetune, --sampled or --residual (or --guarded)")
     # --guarded --self-check is the guard's own self-check; the reference stays what it is
     args.guard_self_check = args.self_check and args.guarded
     if args.guard_self_check:
@@ -1478,9 +1527,79 @@ def sampled_run(case, d, args, worst, tried):
     print(f"ok   {tag}  worst {w:.2e}", flush=True)
 
 
+def residual_run(case, d, args, worst, tried):
+    """--residual: one case on the device against tests/residual_model.py.  Forward (under no_grad): the fed value rounded to the
+    storage type, and the bit contract.  Gradients: f64 under CPU autograd, the fed value rounded to f32 and passed straight
+    through.  ``tried`` (--self-check): "no_base" once the fault has been tried."""
+    tdir = os.path.join(ROOT, "tests")
+    if tdir not in sys.path:
+        sys.path.insert(0, tdir)
+    import residual_model as RES
+    import sampled_model as SM
+    tag, dtype = case["tag"], case["dtype"]
+    C, out, B, T, L, H, W = case["C"], case["out"], case["B"], case["T"], case["L"], case["H"], case["W"]
+    fed = torch.tensor(case["mask"], dtype=torch.bool) if case["mask"] is not None else SM.suffix(B, T, case["fb_from"])
+    feed = dict(free_mask=fed) if case["mask"] is not None else dict(free_from=case["fb_from"])
+    params = O.synth_params(C, case["hidden"], case["ks"], L, out_channels=out, seed=case["it"])
+    net = pkg.ConvLSTM(C, case["hidden"], case["ks"], L, out_channels=out, compute_dtype=dtype, lon_cyclic=case["cyclic"],
+                       feedback=True, residual=True, return_sequence=True)
+    net.load_state_dict(params)
+    net = _net(net)
+    old_fold, engine.XFOLD = engine.XFOLD, case["fold"]
+    try:
+        net._engine(torch.device("cuda", torch.cuda.current_device()))
+    finally:
+        engine.XFOLD = old_fold
+    state = [(d[f"h0.{l}"], d[f"c0.{l}"]) for l in range(L)] if case["with_state"] else None
+    dev_state = None if state is None else [(_dev(h), _dev(c)) for h, c in state]
+    p64 = {k: v.double() for k, v in params.items()}
+    kw = dict(h0=[h.double() for h, _ in state], c0=[c.double() for _, c in state]) if state is not None else {}
+    X = _dev(d["X"])
+    with torch.no_grad():
+        pred, seq = net(X, dev_state, **feed)
+        # bit contract: the residual open-loop pass over the input that holds, where fed, the predictions of the step before
+        X2 = X.clone()
+        sv = seq.view(B, T, out, H, W)
+        for b in range(B):
+            for t in range(1, T):
+                if bool(fed[b, t]):
+                    X2[b, t, C - out:] = sv[b, t - 1]
+        pred2, seq2 = net(X2, dev_state)
+    torch.cuda.synchronize()
+    assert torch.equal(seq, seq2) and torch.equal(pred, pred2), (tag, "the residual closed loop differs from the open loop on the substituted input")
+    ref = RES.forward(d["X"].double(), p64, fed, cyclic=case["cyclic"], storage=dtype, **kw)
+    w = compare(tag, dtype, dict(pred=pred.cpu(), seq=seq.cpu()), dict(pred=ref["pred"], seq=ref["seq"]), args.only >= 0)
+    # (the drawn cotangents get a mean, as in --rollout)
+    dseq = d["dseq"] + 0.5 if case["cot"] in ("seq", "both") else None
+    dpred = d["dpred"] + 0.5 if case["cot"] in ("last", "both") else None
+    Xg = _dev(d["X"]).requires_grad_(True)
+    pred, seq = net(Xg, dev_state, feedback_grad=True, **feed)
+    outs, cots = zip(*[(o, _dev(c)) for o, c in ((pred, dpred), (seq, dseq)) if c is not None])
+    torch.autograd.backward(list(outs), list(cots))
+    torch.cuda.synchronize()
+    fedc = fed.view(B, T, 1, 1, 1).expand(B, T, out, H, W)
+    assert not bool(Xg.grad.cpu()[:, :, C - out:][fedc].any()), (tag, "a gradient on the fed channels of a fed image")
+    res = dict(pred=pred.detach().cpu(), seq=seq.detach().cpu(), dx=Xg.grad.cpu())
+    for k, p in net.named_parameters():
+        res["d." + k] = p.grad.cpu()
+
+    def against(model):
+        r = model.grads(d["X"].double(), p64, fed, case["cyclic"], "f32", dpred, dseq, **kw)
+        want = dict(pred=r["pred"], seq=r["seq"], dx=r["dx"])
+        for k in p64:
+            want["d." + k] = r["params"][k]
+        return compare(tag, dtype, res, want, args.only >= 0)
+    w = max(w, against(RES))
+    if args.self_check and not tried.get("no_base"):
+        expect_failure(tag, "the reference has no base (the non-residual model)", lambda: against(SM))
+        tried["no_base"] = True
+    worst[dtype] = max(worst[dtype], w)
+    print(f"ok   {tag}  worst {w:.2e}", flush=True)
+
+
 def main(argv=None):
     args = parse(argv)
-    new = args.mode in ALL_STREAM_MODES + SAMPLED_MODES
+    new = args.mode in ALL_STREAM_MODES + SAMPLED_MODES + RESIDUAL_MODES
     if args.list:
         for case in draw_cases(args.seed, args.n, args.mode, args.big, args.wide):
             print(json.dumps(case), flush=True)
@@ -1519,6 +1638,8 @@ def main(argv=None):
                     rollout_run(case, d, args, worst)
                 elif args.mode == "sampled":
                     sampled_run(case, d, args, worst, tried)
+                elif args.mode == "residual":
+                    residual_run(case, d, args, worst, tried)
                 elif new:
                     run_new(case, d, args, worst, tried)
                 else:
@@ -1527,7 +1648,7 @@ def main(argv=None):
             engine.FORCE_WAVE, engine.FORCE_TILE_ROWS, engine.FORCE_WIDE = None, 0, 0
     if args.self_check:
         want = {"state": ["zero_c0"], "train_opts": ["truncate", "drop"], "stateful": ["reset"], "finetune": ["no_decay", "unfrozen"],
-                "sampled": ["full_mask"]}[args.mode]
+                "sampled": ["full_mask"], "residual": ["no_base"]}[args.mode]
         missing = [f for f in want if not tried.get(f)]
         if missing:
             raise SystemExit(f"SELF-CHECK INCOMPLETE: no drawn case to try {missing} on (raise --n or change the seed)")

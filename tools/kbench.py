@@ -150,7 +150,7 @@ def main():
         alg = B * T * args.C * H * W
         run("preproc_slab", lambda: sb.fill_slab(eng, ws), None, alg * (4 + es))     # 4 B in + ET out per element
         run("preproc_nchw", lambda: ds.device_batch(idx), None, alg * 8)
-    if not only or only & {"head_skill", "skill_plain", "head_fwd", "head_feedback", "head_feedback_bwd", "head_feedback_sel",
+    if not only or only & {"head_skill", "skill_plain", "head_fwd", "head_feedback", "head_feedback_bwd", "head_feedback_res", "head_feedback_bwd_res", "head_feedback_sel",
                            "head_feedback_sel1", "head_feedback_bwd_sel", "head_feedback_bwd_sel1", "head_loss", "head_loss_spec", "head_loss_spec3"}:
         # evaluation: the head on the last step's images + crop + the f64 skill sums in one pass (nint_head_skill_accum), and the
         # same sums from a prediction in memory (nint_skill_accum), one slot, cos-latitude row weights
@@ -227,6 +227,20 @@ def main():
                                                   int(eng.lon_cyclic), g, eng.dt, st) == 0
             fbb_bytes = lambda n_fed: comp_px * (n_fed * (lines * 64 + 2 * O * 4) + (B - n_fed) * O * 4 + B * ly.Chp * es)
             run("head_feedback_bwd", head_feedback_bwd, None, fbb_bytes(B))
+            # the residual head: the same launches with the base (O more stored values per pixel, read from the
+            # block before) and with the skip term (one more dpred image per fed image, read only)
+            if hasattr(lib, "nint_head_feedback_res") and ws.T >= 2:
+                fdp2 = torch.randn(2 * B, O, ws.H, ws.W, device="cuda")
+
+                def head_feedback_res():
+                    assert lib.nint_head_feedback_res(P(ws.h[-1]), B, B, ly.Ch, ly.Chp, O, P(hw), P(hb), P(ws.xs), B, args.C, l0.Cxp,
+                                                      args.C - O, kf, int(eng.lon_cyclic), 0, None, g, eng.dt, st) == 0
+
+                def head_feedback_bwd_res():
+                    assert lib.nint_head_feedback_bwd_res(P(fdx), 0, P(fdp2), 0, P(fdh), 0, B, ly.Ch, ly.Chp, O, P(hw), args.C, l0.Cxp, c0,
+                                                          kf, int(eng.lon_cyclic), B, None, g, eng.dt, st) == 0
+                run("head_feedback_res", head_feedback_res, None, B * comp_px * ((ly.Chp + max(kf, 1) * O) * es + O * es))
+                run("head_feedback_bwd_res", head_feedback_bwd_res, None, fbb_bytes(B) + B * comp_px * O * 4)
             # scheduled sampling: the masked instantiations under a half-set mask (every other image fed) and,
             # `1`, under an all-ones mask -- the same work as the unmasked rows above
             import numpy as np

@@ -53,6 +53,7 @@ def main():
     ap.add_argument("--sequence-loss", action="store_true")
     ap.add_argument("--sampling-prob", type=float, nargs="*", default=[], help="also time the scheduled-sampling step at these probabilities")
     ap.add_argument("--zero-pad", action="store_true", help="zero padding instead of cyclic longitude")
+    ap.add_argument("--residual", action="store_true", help="the residual head (DESIGN.md 4.22): ConvLSTM(residual=True) in every variant")
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--iters", type=int, default=10)
     args = ap.parse_args()
@@ -68,7 +69,7 @@ def main():
     def trainer(**kw):
         # (one model each: a step moves the weights; a tiny learning rate keeps the three on the same data path all run long)
         net = pkg.ConvLSTM(C_, hidden, ks, len(hidden), out_channels=O, compute_dtype=args.dtype, lon_cyclic=not args.zero_pad,
-                           feedback=True).cuda()
+                           feedback=True, **({"residual": True} if args.residual else {})).cuda()
         return FusedTrainer(net, lr=1e-6, halo=(0, 0), sequence_loss=sq, **kw)
     tr_a, tr_b, tr_c = trainer(rollout_from=s), trainer(), trainer()
 
@@ -98,7 +99,7 @@ def main():
         order = variants if r % 2 == 0 else variants[::-1]
         for name, fn in order:
             times[name].append(timed(fn, args.iters))
-    print(f"{args.dtype} B={B} T={T} C={C_} O={O} {H}x{W} hidden={hidden} k={ks} rollout_from={s} "
+    print(f"{args.dtype} B={B} T={T} C={C_} O={O} {H}x{W} hidden={hidden} k={ks} rollout_from={s} {'RESIDUAL head ' if args.residual else ''}"
           f"{'sequence loss' if sq else 'last-step loss'} {'zero padding' if args.zero_pad else 'cyclic longitude'}; "
           f"{args.rounds} rounds x {args.iters} steps; loss (a) {float(tr_a.step(X, y)):.5f} (c) {float(tr_c.step(X, y)):.5f}")
     print(f"{'variant':48s} {'min':>9s} {'median':>9s} {'max':>9s}  ms per step")
