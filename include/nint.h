@@ -655,6 +655,50 @@ int nint_head_bwd_seq_acc(const void* h_slab, int B, int T, int Ch, int Chp, int
                           const float* dpred_last, void* dh_seq, float* dw, float* db, int accumulate, const nint_geom* g,
                           int dtype, float* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- INPUT NOISE: seeded Gaussian noise on a span of the input's channels, drawn on the device ---------------
+ * THE RULE.  For the noise span, channels [c0, c0 + n) of the model's input, the element at channel offset o in [0, n), pixel
+ * (y, x) of the H x W model grid, window step t and batch lane b draws from one Philox4x32-10 block (Salmon et al., SC'11):
+ *     ctr = (y*W + x,  o / 4,  step0 + t,  lane0 + b)      key = (seed, draw)        all u32, sums mod 2^32
+ *     (w0, w1, w2, w3) = philox4x32_10(ctr, key)
+ *     pair A = (w0, w1) serves o % 4 = 0, 1;   pair B = (w2, w3) serves o % 4 = 2, 3;   (wa, wb) the pair's words
+ *     u  = (float(wa >> 9) + 0.5f) * 2^-23          in [2^-24, 1 - 2^-24]: never 0, exact in f32
+ *     a  = float(wb >> 8) * 2^-23                   in [0, 2), exact
+ *     r  = sqrtf(-2.f * logf(u));  (s, c) = sincospif(a)        the precise forms, never the fast-math ones
+ *     z  = r * c  (even o)   |   r * s  (odd o)                 |z| <= 5.77
+ *     stored' = round_ET( __fadd_rn( f32(stored), __fmul_rn(sigma[o], z) ) )
+ * The product and the sum are two f32 operations, never one FMA: given z, a float32 model reproduces the update bit for bit.
+ * round_ET is the pack entries' round-to-nearest-even to the storage type (the identity in f32).  A channel with sigma[o] == 0
+ * is SKIPPED, not multiplied: its bytes stay, -0.0 included.  The noise of an element is a pure function of (seed, draw, lane,
+ * step, o, pixel): whatever launch produces it -- the sweep or the recompute of a segmented window, a plain or a folded slab,
+ * any batch split over ranks -- it is the same number.
+ *
+ * nint_input_noise applies the rule to images [x_n0, x_n0 + T*B) of an input halo slab, image order t*B + b (Cx channels
+ * padded to Cxp per pixel, sigma: n DEVICE floats).  It writes exactly the bytes nint_head_feedback may write:
+ *   xfold_k = 0   plain slab: channels [c0, c0 + n) of the INTERIOR pixels and nothing else -- no halo pixel, no slack column,
+ *                 no pad channel, no other channel.  (Cyclic longitude: the halo columns are refreshed by the wrap launch that
+ *                 heads nint_seq_fwd.)  lon_cyclic is only checked.
+ *   xfold_k = k   folded slab: slab channel kx*Cx + c0 + o of pixel x holds pixel x' = x + kx - k/2 and receives THAT pixel's
+ *                 noisy value, keyed by x' (x' mod W with lon_cyclic); where x' lies outside the row of a zero-padded slab the
+ *                 copy stays 0.  Each copy reads its own stored value: the k copies of a pixel held the same bits before, so they
+ *                 hold the same bits after.
+ *   bf16          every dword is read, merged and stored whole by ONE lane, also a dword that holds one span element and one
+ *                 foreign one (an odd first channel, an odd n): no two lanes write halves of one dword.
+ * One Philox block feeds four channels of a pixel; a workgroup forms a row's addends once, stages them in LDS, and every fold
+ * copy gathers its own.  Plain vector loads and stores only.
+ * NINT_E_ARG before any launch, in nint_head_feedback's order: a NULL xs_slab / sigma / g, x_n0 < 0; B, T, n, Cx < 1; a bad dtype
+ * or geometry; c0 < 0 or c0 + n > Cx; xfold_k negative or even; Cxp < Cx (xfold_k * Cx folded) or a pixel that is no multiple
+ * of 16 bytes; lon_cyclic not 0 / 1, or 1 with g->W < g->P or g->W < xfold_k / 2.  NINT_E_ALIGN: a slab that is not 16-byte
+ * or a sigma that is not 4-byte aligned.  No shape limit on n, W, Cx (a span or a row too long for one staged window is cut
+ * into workgroups and, in whole Philox blocks, into launches); NINT_E_SHAPE only for xfold_k > 4095. */
+int nint_input_noise(void* xs_slab, int x_n0, int B, int T, int Cx, int Cxp, int c0, int n, const float* sigma /*device, n*/,
+                     int xfold_k, int lon_cyclic, uint32_t seed, uint32_t draw, uint32_t step0, uint32_t lane0,
+                     const nint_geom* g, int dtype, void* stream);
+/* z alone, f32 [T*B][n][H][W], through the device function the slab kernel inlines: the hook that separates the generator from
+ * the layout, and an ensemble caller's source of perturbations.  Only g->H and g->W are used.  NINT_E_ARG: a NULL out / g, B,
+ * T, n < 1, a bad geometry; NINT_E_ALIGN: out not 4-byte aligned. */
+int nint_noise_normal(float* out, int B, int T, int n, uint32_t seed, uint32_t draw, uint32_t step0, uint32_t lane0,
+                      const nint_geom* g, void* stream);
+
 /* ---- loss (train.py:102,105) ------------------------------------------------------------------ */
 /* pred (N,O,H,W) f32, y (N,O,Hc,Wc) f32; crop window [oy,oy+Hc) x [ox,ox+Wc).
  * loss_out: NINT_LOSS_SCRATCH_FLOATS floats, 8-byte aligned; [0] = mean((y-p)^2) + mean(|y-p|), the

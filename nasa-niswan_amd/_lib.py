@@ -112,7 +112,7 @@ class NintLossSpec(C.Structure):
 
 
 # every symbol include/nint.h declares: name -> (restype, argtypes)
-_I, _SZ, _F, _D = C.c_int, C.c_size_t, C.c_float, C.c_double
+_I, _SZ, _F, _D, _U = C.c_int, C.c_size_t, C.c_float, C.c_double, C.c_uint32
 _PG, _PL, _PS, _PLS = C.POINTER(NintGeom), C.POINTER(NintLayer), C.POINTER(NintSeq), C.POINTER(NintLossSpec)
 _POG = C.POINTER(NintOptGroup)
 _PFB = C.POINTER(NintFeedback)
@@ -172,6 +172,8 @@ SIGNATURES = {
     "nint_head_fwd_seq_res": (_I, [vp, _I, _I, _I, _I, _I, vp, vp, vp, _PG, _I, _PHB, vp]),
     "nint_head_feedback_res": (_I, [vp, _I, _I, _I, _I, _I, vp, vp, vp, _I, _I, _I, _I, _I, _I, _I, vp, _PG, _I, vp]),
     "nint_head_feedback_bwd_res": (_I, [vp, _I, vp, _I, vp, _I, _I, _I, _I, _I, vp, _I, _I, _I, _I, _I, _I, vp, _PG, _I, vp]),
+    "nint_input_noise": (_I, [vp, _I, _I, _I, _I, _I, _I, _I, vp, _I, _I, _U, _U, _U, _U, _PG, _I, vp]),
+    "nint_noise_normal": (_I, [vp, _I, _I, _I, _U, _U, _U, _U, _PG, vp]),
     "nint_head_bwd": (_I, [vp, _I, _I, _I, _I, _I, vp, vp, vp, vp, vp, _PG, _I, vp, _SZ, vp]),
     "nint_head_bwd_acc": (_I, [vp, _I, _I, _I, _I, _I, vp, vp, vp, vp, vp, _I, _PG, _I, vp, _SZ, vp]),
     "nint_head_fwd_seq": (_I, [vp, _I, _I, _I, _I, _I, vp, vp, vp, _PG, _I, vp]),

@@ -123,6 +123,63 @@ class Feedback:
         self.fb.w, self.fb.b, self.fb.O, self.fb.from_step, self.grad = ptr(w), ptr(b), O, from_step, grad
 
 
+@dataclass(frozen=True)
+class InputNoise:
+    """Seeded Gaussian noise on a span of the input's channels, drawn on the device (include/nint.h: THE RULE).
+    ``std``: one float or n floats, in the units of the stored (z-scored) input; ``channels = (c0, n)``, None: the feedback
+    channels of the module that takes it (the last out_channels).  The noise of an element is a pure function of (seed, draw,
+    lane0 + b, step0 + t, channel offset, pixel): ``draw`` tells one pass from the next, ``step0`` places a segment in its
+    window, ``lane0`` a rank's batch in the global one.  A negative or non-finite ``std`` is refused here."""
+    std: object
+    channels: Optional[Tuple[int, int]] = None
+    seed: int = 0
+    draw: int = 0
+    step0: int = 0
+    lane0: int = 0
+
+    def __post_init__(self):
+        std = self.std
+        try:
+            vals = tuple(float(v) for v in std) if hasattr(std, "__iter__") else (float(std),)
+        except (TypeError, ValueError):
+            raise ValueError(f"InputNoise: std must be a float or a sequence of floats, got {std!r}") from None
+        if not vals or any(not (v >= 0.0) or v == float("inf") for v in vals):
+            raise ValueError(f"InputNoise: std must be finite and >= 0, got {std!r}")
+        object.__setattr__(self, "std", vals if hasattr(std, "__iter__") else vals[0])
+        if self.channels is not None:
+            ch = tuple(self.channels)
+            if len(ch) != 2 or any(isinstance(v, bool) or int(v) != v for v in ch):
+                raise ValueError(f"InputNoise: channels must be (c0, n), got {self.channels!r}")
+            object.__setattr__(self, "channels", (int(ch[0]), int(ch[1])))
+        for name in ("seed", "draw", "step0", "lane0"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or int(v) != v or v < 0:
+                raise ValueError(f"InputNoise: {name} must be an integer >= 0, got {v!r}")
+            object.__setattr__(self, name, int(v) & 0xffffffff)
+
+    @property
+    def active(self) -> bool:
+        """False: an all-zero std -- no launch, no allocation, the bits of a pass without noise"""
+        return any(v != 0.0 for v in (self.std if isinstance(self.std, tuple) else (self.std,)))
+
+    def span(self, C: int, feedback_O: Optional[int] = None) -> Tuple[int, int, Tuple[float, ...]]:
+        """(c0, n, the n sigmas) on an input of C channels; ValueError for a span outside [0, C), a std whose length is not n,
+        or channels=None where there are no feedback channels"""
+        if self.channels is None:
+            if not feedback_O:
+                raise ValueError("InputNoise(channels=None) means the feedback channels, and this module was built without "
+                                 "feedback=True: give channels=(c0, n)")
+            c0, n = C - int(feedback_O), int(feedback_O)
+        else:
+            c0, n = self.channels
+        if n < 1 or c0 < 0 or c0 + n > C:
+            raise ValueError(f"InputNoise: channels [{c0}, {c0 + n}) lie outside the input's [0, {C})")
+        sig = self.std if isinstance(self.std, tuple) else (self.std,) * n
+        if len(sig) != n:
+            raise ValueError(f"InputNoise: {len(sig)} std values for {n} channels")
+        return c0, n, sig
+
+
 class Workspace:
     """All slabs of one (B, T, H, W) problem.  Halo slabs are zero-initialised once; kernels only
     ever write their interior, so the zero padding of nn.Conv2d (model.py:207-211) is physical."""
@@ -322,6 +379,7 @@ class SeqEngine:
         self.train_unsupported = self.untrainable_layers(self.cfgs, self.dt, self.n_cu)
         self._wg_bytes = wg_bytes
         self._wg_partial = None
+        self._noise_sigma: Dict[tuple, torch.Tensor] = {}      # InputNoise's sigmas on the device, by value
         self.pool: Dict[tuple, List[Workspace]] = {}
 
     @property
@@ -558,7 +616,8 @@ class SeqEngine:
 
     # ------------------------------------------------------------------ passes
     def forward(self, ws: Workspace, x: torch.Tensor, h0: Optional[List[torch.Tensor]] = None,
-                c0: Optional[List[torch.Tensor]] = None, feedback=None, feedback_grad: bool = False, residual=False):
+                c0: Optional[List[torch.Tensor]] = None, feedback=None, feedback_grad: bool = False, residual=False,
+                noise: Optional[InputNoise] = None):
         """x (B,T,C,H,W) f32 on the engine's device, or a dataset.SlabBatch of that shape.  Runs model.py:253-271
         (all layers, all steps).
 
@@ -610,10 +669,24 @@ class SeqEngine:
                                      "staged head kernels (nint_head_feedback: NINT_E_SHAPE)")
             ws.feedback.set(w2, b2, O, from_step, bool(feedback_grad), mask, bool(res_O))
         self.pack_input(ws, x)
+        if noise is not None and noise.active:
+            self.input_noise(ws, noise, ws.feedback.fb.O or res_O or None)
         if h0 is not None:
             self._write_state(h0, c0, self._slot_ptrs(ws, 0), B, ws.g, "0")
         self._set_wave(ws)
         self._seq_pass(ws, False)
+
+    def input_noise(self, ws: Workspace, noise: InputNoise, feedback_O: Optional[int] = None):
+        """One launch of nint_input_noise on the whole input slab of ``ws``: after the slab is filled, before
+        the pass reads it.  The n sigmas live on the device, one small tensor per distinct value tuple for the engine's life."""
+        cfg = self.cfgs[0]
+        c0, n, sig = noise.span(cfg.Cx, feedback_O)
+        sd = self._noise_sigma.get(sig)
+        if sd is None:
+            sd = self._noise_sigma[sig] = torch.tensor(sig, dtype=torch.float32, device=self.device)
+        check(self.lib.nint_input_noise(ptr(ws.xs), 0, ws.B, ws.T, cfg.Cx, ws.Cxp0, c0, n, ptr(sd), cfg.k if cfg.xfold else 0,
+                                        int(self.lon_cyclic), noise.seed, noise.draw, noise.step0, noise.lane0, C.byref(ws.g),
+                                        self.dt, stream_ptr()), "nint_input_noise")
 
     def _seq_pass(self, ws: Workspace, bwd: bool, rg: Optional[NintFeedbackGrad] = None):
         """Choose and call the C entry of a whole-sequence pass: forward | backward, each open or (the last forward pass ran with

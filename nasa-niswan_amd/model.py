@@ -31,9 +31,9 @@ import torch
 import torch.nn as nn
 from torch._C import _functions
 
-from .engine import RESIDUAL_STEP0, ConvLSTMState, Feedback, LayerCfg, SeqEngine, dtype_code
+from .engine import RESIDUAL_STEP0, ConvLSTMState, Feedback, InputNoise, LayerCfg, SeqEngine, dtype_code
 
-__all__ = ["ConvLSTMCell", "ConvLSTM", "ConvLSTMState"]
+__all__ = ["ConvLSTMCell", "ConvLSTM", "ConvLSTMState", "InputNoise"]
 
 
 def _require_cuda(t: torch.Tensor, who: str):
@@ -121,8 +121,10 @@ class _CallOpts:
     """the non-tensor arguments of _ConvLSTMFn: the device state that comes in (or None), what goes out, the box the outgoing
     device state is handed back in (a Function's outputs are tensors), and the default route's head-backward rule"""
 
-    def __init__(self, state_in=None, return_state=False, seq_always=False, free_from=None, feedback_grad=False, residual=False):
+    def __init__(self, state_in=None, return_state=False, seq_always=False, free_from=None, feedback_grad=False, residual=False,
+                 noise=None):
         self.state_in, self.return_state, self.state_out = state_in, return_state, None
+        self.noise = noise              # an InputNoise with its span resolved, or None (DESIGN.md 4.23)
         self.free_from = free_from      # closed loop from this step on (ConvLSTM(feedback=True)); None: open loop
         self.residual = residual        # the module's head predicts the increment (ConvLSTM(residual=True), DESIGN.md 4.22)
         # ... or a (B, T) feed mask (scheduled sampling, DESIGN.md 4.21); `first`: the first step that feeds anything
@@ -166,7 +168,7 @@ class _ConvLSTMFn(torch.autograd.Function):
             eng.load_state(ws, opts.state_in)
         h0, c0 = (list(st[0::2]), list(st[1::2])) if st else (None, None)
         eng.forward(ws, x, h0, c0, feedback=None if opts.free_from is None else (head_w, head_b, opts.free_from),
-                    feedback_grad=rollout, residual=head_w.shape[0] if opts.residual else False)
+                    feedback_grad=rollout, residual=head_w.shape[0] if opts.residual else False, noise=opts.noise)
         outs = [eng.head_forward(ws, head_w, head_b)]
         if module.return_sequence:
             outs.append(eng.head_forward_seq(ws, head_w, head_b))       # every step in one launch
@@ -367,7 +369,7 @@ class ConvLSTM(_EngineOwner, nn.Module):
         inference loops, which drive the engine themselves, do before a forward pass"""
         eng.pack_weights([c.conv.weight for c in self.layers], [c.conv.bias for c in self.layers])
 
-    def forward(self, x, state=None, *, return_state=False, free_from=None, feedback_grad=False, free_mask=None):
+    def forward(self, x, state=None, *, return_state=False, free_from=None, feedback_grad=False, free_mask=None, input_noise=None):
         """x: (batch_size, sequence_length, channels, height, width)  (model.py:254).
 
         ``state``: None (zeros, model.py:259-262), a list of ``num_layers`` ``(h, c)`` tensor pairs (B, Ch_l, H, W) -- the
@@ -403,7 +405,15 @@ class ConvLSTM(_EngineOwner, nn.Module):
         ``seq`` and the fed value are that p; the gradient of ``x`` gains the cotangent of p_t on the feedback channels of
         every step that saw ``x`` (zero on the fed ones, as above).  ``free_from = 0`` and a mask with column 0 set are
         refused, state or not: the value fed at step 0 would be the prediction of a step before the window, which has no
-        input to be added to."""
+        input to be added to.
+
+        ``input_noise = InputNoise(std, channels=None, seed, draw, step0, lane0)``: seeded Gaussian noise is
+        added, on the device, to channels ``[c0, c0 + n)`` of the input the model is shown (None: the feedback channels),
+        rounded to the storage type.  The noise is a constant: the gradient of ``x`` is what it was, the rounding taken
+        straight-through.  Everything above composes with it: a fed step overwrites its fed channels afterwards, an unfed
+        step of a ``residual=True`` module takes the NOISY stored value as its base.  None, or an all-zero ``std``: no launch,
+        the bits of the call without it."""
+        noise = self._check_noise(x, input_noise)
         if free_mask is not None:                       # the refusals of free_from, by the first column with a fed image
             if free_from is not None:
                 raise ValueError("free_mask and free_from are exclusive: the mask says for every step what free_from says for all")
@@ -423,7 +433,7 @@ class ConvLSTM(_EngineOwner, nn.Module):
                 raise ValueError(f"free_mask: a feed mask holds at most 64 images per call, got B = {x.shape[0]}")
             free_from = mask if first < x.shape[1] else None         # (nothing fed: the open loop, the call it always was)
             feedback_grad = feedback_grad and free_from is not None
-            return self._forward(x, state, return_state, free_from, feedback_grad)
+            return self._forward(x, state, return_state, free_from, feedback_grad, noise)
         if free_from is not None:                       # every refusal here, before anything is launched (or any device is asked for)
             if not self.feedback:
                 raise ValueError("free_from needs a ConvLSTM built with feedback=True")
@@ -438,7 +448,20 @@ class ConvLSTM(_EngineOwner, nn.Module):
                 raise ValueError("free_from=0 feeds step 0 from the head of the initial state: pass a state")
             if free_from < x.shape[1] and not (feedback_grad and free_from >= 1) and self._wants_grad(x, state):
                 raise RuntimeError(_NO_FEEDBACK_GRAD)
-        return self._forward(x, state, return_state, free_from, feedback_grad)
+        return self._forward(x, state, return_state, free_from, feedback_grad, noise)
+
+    def _check_noise(self, x, input_noise):
+        """the refusals of ``input_noise``, before anything is launched; the InputNoise the engine takes (span resolved), or None"""
+        if input_noise is None:
+            return None
+        if not isinstance(input_noise, InputNoise):
+            raise ValueError(f"input_noise must be an InputNoise or None, got {type(input_noise).__name__}")
+        if len(x.shape) != 5:
+            raise ValueError(f"ConvLSTM: x must be (B, T, C, H, W), got {tuple(x.shape)}")
+        c0, n, _ = input_noise.span(self.layers[0].input_channels, self.conv.out_channels if self.feedback else None)
+        if not input_noise.active:
+            return None
+        return InputNoise(input_noise.std, (c0, n), input_noise.seed, input_noise.draw, input_noise.step0, input_noise.lane0)
 
     def _wants_grad(self, x, state) -> bool:
         """grad mode is on and an input, a parameter or a tensor state requires grad"""
@@ -446,8 +469,9 @@ class ConvLSTM(_EngineOwner, nn.Module):
             x.requires_grad or any(p.requires_grad for p in self.parameters())
             or (state is not None and not isinstance(state, ConvLSTMState) and any(t.requires_grad for pair in state for t in pair)))
 
-    def _forward(self, x, state, return_state, free_from, feedback_grad):
-        """forward() behind its refusals; ``free_from``: None, a step index or a (B, T) uint8 feed mask"""
+    def _forward(self, x, state, return_state, free_from, feedback_grad, noise=None):
+        """forward() behind its refusals; ``free_from``: None, a step index or a (B, T) uint8 feed mask; ``noise``: None or an
+        InputNoise with its span resolved"""
         _require_cuda(x, "ConvLSTM")
         wb = []
         for cell in self.layers:
@@ -455,7 +479,7 @@ class ConvLSTM(_EngineOwner, nn.Module):
         st = []
         if state is None and not return_state:          # the default call: nothing to validate, and its own head-backward rule
             opts = _CallOpts(seq_always=self.return_sequence, free_from=free_from, feedback_grad=bool(feedback_grad),
-                             residual=self.residual)
+                             residual=self.residual, noise=noise)
         else:
             if return_state not in (False, True, "device"):
                 raise ValueError(f"return_state must be False, True or 'device', got {return_state!r}")
@@ -469,7 +493,7 @@ class ConvLSTM(_EngineOwner, nn.Module):
                 hs, cs = eng._state_tensors(state, (B, H, W))
                 st = _interleave(hs, cs)
             opts = _CallOpts(state if isinstance(state, ConvLSTMState) else None, return_state, free_from=free_from,
-                             feedback_grad=bool(feedback_grad), residual=self.residual)
+                             feedback_grad=bool(feedback_grad), residual=self.residual, noise=noise)
         out = _ConvLSTMFn.apply(self, torch.is_grad_enabled(), opts, x, self.conv.weight, self.conv.bias, *wb, *st)
         out = list(out) if isinstance(out, tuple) else [out]
         n0 = 2 if self.return_sequence else 1

@@ -7,7 +7,8 @@ stepped once per epoch before validation, checkpoint every 10 epochs); the per-b
 once per epoch.  Added flags: --dtype, --levels, --grid, --synthetic-steps, --pad-mode, --f32-inputs,
 --static-channels, --sequence-loss, --test-skill, --lat-weighted-loss, --loss-weights, --clip-grad-norm,
 --skip-nonfinite-steps, --stateful, --bptt-segments, --accumulate-steps, --loss-mix, --huber-delta, --output-weights,
---spinup-steps, --rollout-from, --sampling-prob, --sampling-ramp-epochs, --sampling-seed, --residual-head.
+--spinup-steps, --rollout-from, --sampling-prob, --sampling-ramp-epochs, --sampling-seed, --residual-head,
+--tracer-noise, --noise-seed.
 
 The data path is on the device too: by default every batch is written by ONE launch of the
 fuse / z-score / halo-pad kernel straight into the model's bf16 input slab (dataset.slab_batch);
@@ -157,6 +158,11 @@ def get_arguments(argv=None, MODEL='LSTM-00', SPECIES='bcb', LEARNING_RATE=1.0E-
                              "the step was given (its last --levels input channels) plus the head's output "
                              "(ConvLSTM(residual=True)); stored with the snapshot's arguments.  Resuming a checkpoint that was "
                              "trained without it is refused unless --reset-optimizer asks for fine-tuning")
+    parser.add_argument("--tracer-noise", type=float, default=None, metavar="STD",
+                        help="with --tracer-input: every training step shows the model its tracer channels with Gaussian noise of "
+                             "this standard deviation (z-score units) added, drawn on the device (FusedTrainer(input_noise=STD)); "
+                             "validation and test see clean inputs.  A resumed run restarts the draw counter at 0")
+    parser.add_argument("--noise-seed", type=int, default=0, help="the seed of --tracer-noise (the same on every rank)")
     parser.add_argument("--reset-optimizer", action="store_true",
                         help="with --use-checkpoint: load the weights of --restore-from only and start the optimizer afresh "
                              "(the fine-tuning entry point; without it an optimizer state of other param groups is an error)")
@@ -191,6 +197,13 @@ def get_arguments(argv=None, MODEL='LSTM-00', SPECIES='bcb', LEARNING_RATE=1.0E-
             parser.error(f"--residual-head: the checkpoint under {args.restore_from} was trained without it (its head predicts the "
                          "state, not the increment, and its optimizer moments belong to that head); pass --reset-optimizer to "
                          "fine-tune its weights as a residual model")
+    if args.tracer_noise is not None:
+        if not args.tracer_input:
+            parser.error("--tracer-noise needs --tracer-input: the noise is added to the tracer channels of the input")
+        if not 0.0 <= args.tracer_noise < float("inf"):
+            parser.error("--tracer-noise must be a finite standard deviation >= 0")
+    if args.noise_seed < 0:
+        parser.error("--noise-seed must be >= 0")
     if args.sampling_prob is not None:
         if args.rollout_from is None:
             parser.error("--sampling-prob needs --rollout-from: the coin is thrown for the steps from --rollout-from on")
@@ -317,7 +330,8 @@ def main(args):
                            max_grad_norm=args.clip_grad_norm, skip_nonfinite=args.skip_nonfinite_steps, stateful=args.stateful,
                            bptt_segments=args.bptt_segments, accumulate_steps=args.accumulate_steps, loss=build_loss_spec(args),
                            freeze_layers=args.freeze_layers, weight_decay=args.weight_decay, layer_lr_scale=args.layer_lr_scale,
-                           rollout_from=args.rollout_from, sampling_prob=args.sampling_prob, sampling_seed=args.sampling_seed)
+                           rollout_from=args.rollout_from, sampling_prob=args.sampling_prob, sampling_seed=args.sampling_seed,
+                           input_noise=args.tracer_noise, noise_seed=args.noise_seed)
     if args.stateful:
         # one schedule of world * batch lanes, the same every epoch; each rank takes its own columns and carries its own state
         sched, dropped = stateful_schedule(len(train_dataset), args.sequence_length, world * args.batch_size)

@@ -37,6 +37,10 @@
                                                closed loop and its backward are the _residual entries.  Every other option
                                                composes: the base of a step is that step's input, so no segment, chunk or
                                                micro-batch boundary is crossed
+    [input_noise = sigma]                   -> INPUT NOISE: one nint_input_noise launch behind every filling of an
+                                               input slab of step() -- seeded Gaussian noise on the tracer channels, keyed by
+                                               (noise_seed, the count of step() calls, rank * B + b, the step's place in the
+                                               window), so the sweep and the recompute of a segment see the same input
     [accumulate_steps = k]                  -> k micro-batches add into the bucket (accumulate = 1 from the second on); the
                                                all-reduce and ONE Adam launch with grad_scale = 1/(k world) on the k-th
 
@@ -49,6 +53,7 @@ import torch
 
 from . import _lib
 from ._lib import NINT_LOSS_SPEC_SCRATCH_FLOATS, NINT_LOSS_STATS
+from .engine import InputNoise
 from .model import ConvLSTM
 from .loss import DeviceWeights, LossSpec, crop_loss_launch
 from .optim import FlatParams, FusedAdam
@@ -73,7 +78,16 @@ class FusedTrainer:
                  max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False, stateful: bool = False,
                  bptt_segments: Optional[int] = None, accumulate_steps: int = 1, loss: Optional[LossSpec] = None,
                  freeze_layers: int = 0, weight_decay: float = 0.0, layer_lr_scale=None, rollout_from: Optional[int] = None,
-                 sampling_prob: Optional[float] = None, sampling_seed: int = 0):
+                 sampling_prob: Optional[float] = None, sampling_seed: int = 0, input_noise=None, noise_channels=None,
+                 noise_seed: int = 0):
+        # Input noise: every step() shows the model its input with N(0, input_noise^2) added to the noise
+        # channels (None: the feedback channels), drawn on the device.  `draw` is the count of step() calls (micro-batches
+        # included), `lane0` = rank * B with the SAME seed on every rank, `step0` a segment's start in its window.  evaluate()
+        # and forward_loss() never add noise.  Checked first: these refusals need no device.
+        self._noise_channels, self.noise_seed = noise_channels, noise_seed
+        self._noise_model = (model.layers[0].input_channels, model.conv.weight.shape[0] if getattr(model, "feedback", False) else None)
+        self._noise, self._draws = None, 0
+        self.set_input_noise(input_noise)
         # Roll-out training: from step `rollout_from` on the window runs on its own prediction and the loss's gradient flows
         # back through it.  Checked first: these refusals need no device.
         if rollout_from is not None:
@@ -304,6 +318,25 @@ class FusedTrainer:
         for v in views:
             v.masked_fill_(bad, 0)
 
+    def set_input_noise(self, std):
+        """the noise level of the steps to come (a curriculum sets it once per epoch): a float or one per noise channel, in the
+        units of the stored input; None or 0: no noise, the step it was.  ValueError for a negative or non-finite value, for a
+        span outside the input's channels, or -- without ``noise_channels`` -- a model built without feedback=True."""
+        if std is None:
+            self._noise = None
+            return
+        nz = InputNoise(std, self._noise_channels, self.noise_seed)
+        c0, n, _ = nz.span(*self._noise_model)
+        self._noise = InputNoise(nz.std, (c0, n), nz.seed) if nz.active else None
+
+    def _noise_kw(self, draw: int, B: int, step0: int = 0) -> dict:
+        """the ``noise`` argument of a forward pass of step(), nothing without noise: the calls are then, argument for argument,
+        what they were.  ``draw``: this step()'s number; ``step0``: where the pass's first step lies in the window."""
+        if self._noise is None:
+            return {}
+        rank = self.dist.get_rank(self.pg) if self.distributed else 0
+        return dict(noise=InputNoise(self._noise.std, self._noise.channels, self._noise.seed, draw, step0, rank * B))
+
     def set_sampling_prob(self, p: Optional[float]):
         """the coin's bias for the steps to come (a curriculum sets it once per epoch); None: no sampling"""
         if p is not None:
@@ -416,6 +449,7 @@ class FusedTrainer:
             raise ValueError("step(reset=...) needs FusedTrainer(stateful=True)")
         k = self.accumulate_steps
         acc, last = self._micro > 0, self._micro == k - 1       # add to the bucket; exchange and step after this call
+        draw, self._draws = self._draws, self._draws + 1        # (input noise: one draw per call, micro-batches included)
         if (self.bptt_segments or 1) > 1:
             plan = segment_plan(T, self.bptt_segments)          # (before anything is acquired)
         else:
@@ -425,7 +459,7 @@ class FusedTrainer:
         if plan is not None:
             mark()
             m._pack_weights(eng)
-            self._segments(eng, X, yv, plan, carried, acc, wts, spec)
+            self._segments(eng, X, yv, plan, carried, acc, wts, spec, draw)
             return self._finish(last)
         with eng.window(B, T, H, W, True, self.stateful, self.freeze_layers) as ws:
             pb, pm = self._probe
@@ -437,7 +471,7 @@ class FusedTrainer:
                 eng.load_state(ws, carried)          # carried state -> slot 0
             feed = self._draw(T, B)     # (None: nothing is fed -- the step it was)
             eng.forward(ws, X, **(dict(feedback=(m.conv.weight, m.conv.bias, feed), feedback_grad=True) if feed is not None else {}),
-                        **self._res_kw())
+                        **self._res_kw(), **self._noise_kw(draw, B))
             if carried is not None:
                 eng.save_state(ws, carried)          # slot T -> carried state; BPTT below stops at the chunk start
                 self._drop_nonfinite_lanes(carried)
@@ -468,7 +502,7 @@ class FusedTrainer:
         self._mark()
         return self.scratch[0]
 
-    def _segments(self, eng, X, yv, plan, carried, acc: bool, wts, spec=None):
+    def _segments(self, eng, X, yv, plan, carried, acc: bool, wts, spec=None, draw: int = 0):
         """Checkpointed BPTT of one window: the gradients of the whole window into the bucket, with S = T / n
         steps resident instead of T.
           1. forward sweep: segments 0 .. n-2 in an S-step inference workspace (no stash, no dG), each from the state the one
@@ -480,7 +514,8 @@ class FusedTrainer:
         Segment 0 starts from the zero state, or from the carried one (stateful: gradients still stop at the chunk start, and
         the carried state becomes the one segment n-1 ended in).  A zero-state segment 0 runs as the whole window's first
         steps do (SeqEngine.zero_start: the h half of K skipped at t = 0), so every segment's forward pass has the whole
-        window's bits and so has the loss."""
+        window's bits and so has the loss.  Input noise (``draw``): every pass over a segment carries the segment's start as step0,
+        so the sweep and the recompute add the same noise, the whole window's."""
         m, L, mark = self.model, self.model.num_layers, self._mark
         B, T, _, H, W = X.shape
         n, S, f = len(plan), plan[0][1], self.freeze_layers
@@ -492,11 +527,11 @@ class FusedTrainer:
             for t0, _ in plan[:-1]:
                 eng.load_state(wf, states[-1])
                 eng.zero_start(wf, carried is None and t0 == 0)
-                eng.forward(wf, seg(t0), **self._res_kw())
+                eng.forward(wf, seg(t0), **self._res_kw(), **self._noise_kw(draw, B, t0))
                 states.append(eng.save_state(wf))        # slot S -> a new state: the start of the next segment
         with eng.window(B, S, H, W, True, True, f) as ws:
             eng.load_state(ws, states[-1])
-            eng.forward(ws, seg(plan[-1][0]), **self._res_kw())
+            eng.forward(ws, seg(plan[-1][0]), **self._res_kw(), **self._noise_kw(draw, B, plan[-1][0]))
             if carried is not None:
                 self.state = eng.save_state(ws)          # (a new object: the chunk's start state above stays what it was)
                 self._drop_nonfinite_lanes(self.state)
@@ -508,7 +543,7 @@ class FusedTrainer:
             for j in range(n - 2, -1, -1) if f < L else ():      # (the head alone: its gradient is the last segment's)
                 eng.load_state(ws, states[j])
                 eng.zero_start(ws, carried is None and j == 0)
-                eng.forward(ws, seg(plan[j][0]), **self._res_kw())
+                eng.forward(ws, seg(plan[j][0]), **self._res_kw(), **self._noise_kw(draw, B, plan[j][0]))
                 eng.backward(ws, False, zero_state_grads=(), dW_out=self._dW, db_out=self._db, accumulate=True, train_from=f)
             mark()
 

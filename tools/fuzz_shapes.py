@@ -58,6 +58,12 @@ after the shape.
                 and dx (the skip add on the unfed feedback channels, zeros on the fed ones) under drawn cotangents against the
                 model under CPU autograd.  --self-check: the reference of the first case loses the base (the non-residual
                 model, tests/sampled_model.py).
+  --noise       ``ConvLSTM(x, input_noise=InputNoise(std, channels=(c0, n), seed, draw, step0, lane0))`` (the input noise, DESIGN.md
+                4.23) with a drawn stack, grid, noise span, sigma per channel (one may be 0), storage type, boundary, input
+                layout and generator key.  Outputs, every parameter gradient and dx under drawn cotangents against the CPU
+                oracle under autograd on the PRE-NOISED input, built on the host by tests/noise_model.py from its own Philox;
+                an all-zero std is the pass without the argument, bit for bit.  --self-check: the reference of the first
+                case sees the clean input.
   --self-check  (with one of these modes) after the first passing case to which a fault applies, the REFERENCE is corrupted on
                 the host and the same comparison of the same device results must fail: --state: the oracle gets a zero c0
                 for the last layer; --train-opts with n >= 2: the oracle back-propagates the last segment only (truncated
@@ -124,6 +130,9 @@ SAMPLED_KEY = 1000              # the stream key of SAMPLED_MODES[i] is SAMPLED_
 # ... and SAMPLED_MODES is pinned too (tests/test_sampled_cpu.py): the residual head's mode has its own tuple and key
 RESIDUAL_MODES = ("residual",)
 RESIDUAL_KEY = 2000             # the stream key of RESIDUAL_MODES[i] is RESIDUAL_KEY + i
+# ... and RESIDUAL_MODES is pinned in turn (tests/test_residual_cpu.py): the input noise's mode continues the same way
+NOISE_MODES = ("noise",)
+NOISE_KEY = 3000                # the stream key of NOISE_MODES[i] is NOISE_KEY + i
 LIM = {"f32": 1e-3, "bf16": 3e-2}
 LOSS_LIM = {"f32": 2e-6, "bf16": 2e-2}
 
@@ -273,6 +282,8 @@ def case_rng(seed: int, mode: str, it: int):
         return np.random.default_rng([int(seed), SAMPLED_KEY + SAMPLED_MODES.index(mode), int(it)])
     if mode in RESIDUAL_MODES:
         return np.random.default_rng([int(seed), RESIDUAL_KEY + RESIDUAL_MODES.index(mode), int(it)])
+    if mode in NOISE_MODES:
+        return np.random.default_rng([int(seed), NOISE_KEY + NOISE_MODES.index(mode), int(it)])
     return np.random.default_rng([int(seed), 1 + ALL_STREAM_MODES.index(mode), int(it)])
 
 
@@ -293,6 +304,8 @@ def draw_case(rng, it: int, mode: str = "plain", big: bool = False, wide: bool =
         return draw_sampled(rng, it)
     if mode == "residual":
         return draw_residual(rng, it)
+    if mode == "noise":
+        return draw_noise(rng, it)
     new = mode in NEW_MODES
     L = int(rng.integers(1, 5))
     hidden = [int(rng.choice([4, 8, 16, 24, 32, 48, 64] if new else [4, 8, 16, 24, 32, 48, 64, 64, 128])) for _ in range(L)]
@@ -517,6 +530,34 @@ def draw_residual(rng, it: int) -> dict:
                     f"residual {what} cyclic={int(cyclic)} fold={int(fold)} state={int(with_state)} cotangents={cot}")
 
 
+def draw_noise(rng, it: int) -> dict:
+    """--noise: a stack, a grid, a noise span [c0, c0 + n) anywhere in the input's channels with a sigma per channel (one of them
+    may be 0), both storage types, cyclic longitude or zero padding, the thin-input fold allowed or off, the generator's key
+    (seed, draw, step0, lane0 -- step0 near 2^32 now and then), and cotangents on the per-step outputs and the last one.  Pure."""
+    L = int(rng.integers(1, 4))
+    hidden = [int(rng.choice([4, 8, 16, 24, 32, 64])) for _ in range(L)]
+    ks = [int(rng.choice([1, 3, 3, 5, 5])) for _ in range(L)]
+    C = int(rng.choice([1, 3, 4, 6, 16, 33, 40, 62]))
+    out = min(C, int(rng.choice([1, 2, 3])))            # (the CPU model of the stack is the closed-loop one: O <= C)
+    n = int(rng.integers(1, C + 1))
+    c0 = int(rng.integers(0, C - n + 1))
+    B, T = int(rng.integers(1, 5)), int(rng.integers(2, 6))
+    H, W = int(rng.integers(5, 21)), int(rng.integers(9, 41))
+    dtype = "f32" if it % 2 == 0 else "bf16"
+    wave, rows = WAVES[it % 7], TILE_ROWS[it % 4]
+    cyclic, fold = (bool(rng.integers(0, 2)) for _ in range(2))
+    sigma = [float(v) for v in rng.choice([0.03125, 0.0625, 0.125, 0.25], size=n)]
+    if n > 1 and bool(rng.integers(0, 2)):
+        sigma[int(rng.integers(0, n))] = 0.0
+    key = dict(seed=int(rng.integers(0, 1 << 32)), draw=int(rng.integers(0, 1 << 16)),
+               step0=[0, 3, (1 << 32) - 1][int(rng.integers(0, 3))], lane0=int(rng.integers(0, 64)))
+    draws = [("X", (B, T, C, H, W)), ("dseq", (B, T * out, H, W)), ("dpred", (B, out, H, W))]
+    return dict(it=it, mode="noise", L=L, hidden=hidden, ks=ks, C=C, out=out, B=B, T=T, H=H, W=W, dtype=dtype, wave=wave,
+                rows=rows, wide=0, cyclic=cyclic, fold=fold, c0=c0, n=n, sigma=sigma, key=key, draws=draws,
+                tag=f"#{it} C={C} hidden={hidden} k={ks} out={out} B={B} T={T} {H}x{W} {dtype} wave={wave} rows={rows} "
+                    f"noise span=[{c0},{c0 + n}) zero-sigma={int(0.0 in sigma)} step0={key['step0']} cyclic={int(cyclic)} fold={int(fold)}")
+
+
 def draw_data(rng, case) -> dict:
     """the standard-normal tensors of a case, f32, from the generator that drew it"""
     return {name: torch.from_numpy(rng.standard_normal(sh).astype(np.float32)) for name, sh in case["draws"]}
@@ -527,7 +568,7 @@ def draw_cases(seed: int, n: int, mode: str = "plain", big: bool = False, wide: 
     cases = []
     rng = np.random.default_rng(seed)
     for it in range(n):
-        if mode in ALL_STREAM_MODES + SAMPLED_MODES + RESIDUAL_MODES:
+        if mode in ALL_STREAM_MODES + SAMPLED_MODES + RESIDUAL_MODES + NOISE_MODES:
             cases.append(draw_case(case_rng(seed, mode, it), it, mode))
         else:
             cases.append(draw_case(rng, it, mode, big, wide))
@@ -1155,6 +1196,7 @@ def parse(argv=None):
     ap.add_argument("--rollout", action="store_true", help="ConvLSTM(feedback=True)(x, free_from=F, feedback_grad=True): outputs, every parameter gradient and dx of a drawn stack, grid, number of feedback channels, first fed step F >= 1, storage type, boundary condition, input layout and cotangents (per step, last step, both) against the CPU model tests/rollout_model.py under CPU autograd in f64")
     ap.add_argument("--sampled", action="store_true", help="ConvLSTM(feedback=True)(x[, state], free_mask=M[, feedback_grad=True]): a drawn stack, grid, number of feedback channels, storage type, boundary condition, input layout, state and (B, T) feed mask of a drawn density.  Forward: the per-step predictions against the CPU model tests/sampled_model.py and bit for bit against the open-loop pass over the input with those predictions substituted where the mask says.  Without a fed image at step 0: outputs, every parameter gradient and dx under drawn cotangents (per step or last step) against the model under CPU autograd in f64.  --self-check: the reference of the first case with a mixed step is computed as if every image were fed from the first fed step on")
     ap.add_argument("--residual", action="store_true", help="ConvLSTM(feedback=True, residual=True)(x[, state], free_from=F | free_mask=M[, feedback_grad=True]): a drawn stack, grid, number of feedback channels, storage type, boundary condition, input layout, state and first fed step F >= 1 or (B, T) feed mask with column 0 clear.  Forward: the per-step predictions p_t = x_t[feedback channels] + head(h_t) against the CPU model tests/residual_model.py and bit for bit against the residual open-loop pass over the input with those predictions substituted where fed.  Then outputs, every parameter gradient and dx under drawn cotangents against the model under CPU autograd in f64.  --self-check: the reference of the first case is the non-residual model (the base dropped)")
+    ap.add_argument("--noise", action="store_true", help="ConvLSTM(x, input_noise=InputNoise(std, channels=(c0, n), seed, draw, step0, lane0)): a drawn stack, grid, noise span, sigma per channel (one may be 0), storage type, boundary condition, input layout and generator key.  The noisy pass -- outputs, every parameter gradient and dx under drawn cotangents -- against the CPU oracle under autograd in f64 on the PRE-NOISED input, which tests/noise_model.py builds on the host from its own Philox and normals; a pass with an all-zero std is the pass without the argument, bit for bit.  --self-check: the reference of the first case is the clean input")
     ap.add_argument("--self-check", action="store_true", help="with --state / --train-opts / --stateful / --finetune / --sampled / --residual: corrupt the reference after the first passing case and require the comparison to fail")
     ap.add_argument("--guarded", action="store_true", help="every mode: the device side of each case allocates through oracle/guarded_alloc.py in poison mode (guards around every buffer, `empty` payloads 0xFF), its inputs and parameters in arenas of their own; the comparison stays what it is and every guard byte is checked after each case.  With --self-check (any mode): one guard byte is flipped after the first passing case and the check has to fail (the reference is then not corrupted)")
     ap.add_argument("--list", action="store_true", help="print the drawn cases as JSON lines and exit (no GPU, the package is not imported)")
@@ -1163,14 +1205,14 @@ def parse(argv=None):
     ap.add_argument("--force-dtype", choices=["f32", "bf16"], default=None, help="with --only: the storage type of the replayed case instead of the alternation's (is the miss the arithmetic's, or the storage type's?)")
     args = ap.parse_args(argv)
     modes = [m for m in ("dataset", "cell", "trainer", "state", "train_opts", "stateful", "finetune", "closed_loop", "rollout", "sampled",
-                         "residual") if getattr(args, m)]
+                         "residual", "noise") if getattr(args, m)]
     if len(modes) > 1 and not all(m in OLD_MODES for m in modes):
         ap.error("one of --state / --train-opts / --stateful / --finetune / --closed-loop / --rollout / --sampled / --residual at a time, and none of the other modes with it")
     args.mode = modes[0] if modes else "plain"          # (--dataset before --cell before --trainer, as ever)
-    if args.mode in ("closed_loop", "rollout", "sampled", "residual") and (args.big or args.wide):
-        ap.error("--closed-loop / --rollout / --sampled / --residual draw their own shapes: not with --big / --wide")
-    if args.self_check and args.mode not in NEW_MODES + SAMPLED_MODES + RESIDUAL_MODES and not args.guarded:
-        ap.error("--self-check needs --state, --train-opts, --stateful, --finetune, --sampled or --residual (or --guarded)")
+    if args.mode in ("closed_loop", "rollout", "sampled", "residual", "noise") and (args.big or args.wide):
+        ap.error("--closed-loop / --rollout / --sampled / --residual / --noise draw their own shapes: not with --big / --wide")
+    if args.self_check and args.mode not in NEW_MODES + SAMPLED_MODES + RESIDUAL_MODES + NOISE_MODES and not args.guarded:
+        ap.error("--self-check needs --state, --train-opts, --stateful, --finetune, --sampled, --residual or --noise (or --guarded)")
     # --guarded --self-check is the guard's own self-check; the reference stays what it is
     args.guard_self_check = args.self_check and args.guarded
     if args.guard_self_check:
@@ -1597,9 +1639,66 @@ def residual_run(case, d, args, worst, tried):
     print(f"ok   {tag}  worst {w:.2e}", flush=True)
 
 
+def noise_run(case, d, args, worst, tried):
+    """--noise: one case on the device against the CPU oracle on the pre-noised input.  The reference input is built on the host
+    by tests/noise_model.py (its own Philox, f64 normals rounded to f32, the float32 update, the storage rounding); the model
+    then runs in f64 under CPU autograd (tests/rollout_model.py with nothing fed: the oracle's open loop).  ``tried``
+    (--self-check): "clean" once the fault has been tried."""
+    tdir = os.path.join(ROOT, "tests")
+    if tdir not in sys.path:
+        sys.path.insert(0, tdir)
+    import noise_model as NM
+    import rollout_model as RM
+    from nasa_niswan_amd.engine import InputNoise
+    tag, dtype = case["tag"], case["dtype"]
+    C, out, B, T, L, H, W = case["C"], case["out"], case["B"], case["T"], case["L"], case["H"], case["W"]
+    c0, n, sigma, key = case["c0"], case["n"], case["sigma"], case["key"]
+    params = O.synth_params(C, case["hidden"], case["ks"], L, out_channels=out, seed=case["it"])
+    net = pkg.ConvLSTM(C, case["hidden"], case["ks"], L, out_channels=out, compute_dtype=dtype, lon_cyclic=case["cyclic"],
+                       return_sequence=True)
+    net.load_state_dict(params)
+    net = _net(net)
+    old_fold, engine.XFOLD = engine.XFOLD, case["fold"]
+    try:
+        net._engine(torch.device("cuda", torch.cuda.current_device()))
+    finally:
+        engine.XFOLD = old_fold
+    N = InputNoise(tuple(sigma), channels=(c0, n), **key)
+    with torch.no_grad():
+        X = _dev(d["X"])
+        clean = net(X)
+        zero = net(X, input_noise=InputNoise((0.0,) * n, channels=(c0, n), **key))
+    assert all(torch.equal(a, b) for a, b in zip(clean, zero)), (tag, "an all-zero std is not the pass without noise")
+    dseq, dpred = d["dseq"] + 0.5, d["dpred"] + 0.5
+    Xg = _dev(d["X"]).requires_grad_(True)
+    pred, seq = net(Xg, input_noise=N)
+    torch.autograd.backward([pred, seq], [_dev(dpred), _dev(dseq)])
+    torch.cuda.synchronize()
+    res = dict(pred=pred.detach().cpu(), seq=seq.detach().cpu(), dx=Xg.grad.cpu())
+    for k, p in net.named_parameters():
+        res["d." + k] = p.grad.cpu()
+    assert any(v != 0 for v in sigma) and not torch.equal(res["pred"], clean[0].cpu()), (tag, "the noise changed nothing")
+    p64 = {k: v.double() for k, v in params.items()}
+    z = NM.z_images(B, T, n, H, W, **key).astype(np.float32)
+    Xn = torch.from_numpy(NM.noisy_input(d["X"].numpy(), z, c0, sigma, dtype == "bf16"))
+
+    def against(x):
+        r = RM.grads(x.double(), p64, None, case["cyclic"], "f32", dpred, dseq)
+        want = dict(pred=r["pred"], seq=r["seq"], dx=r["dx"])
+        for k in p64:
+            want["d." + k] = r["params"][k]
+        return compare(tag, dtype, res, want, args.only >= 0)
+    w = against(Xn)
+    if args.self_check and not tried.get("clean"):
+        expect_failure(tag, "the reference saw the clean input", lambda: against(d["X"]))
+        tried["clean"] = True
+    worst[dtype] = max(worst[dtype], w)
+    print(f"ok   {tag}  worst {w:.2e}", flush=True)
+
+
 def main(argv=None):
     args = parse(argv)
-    new = args.mode in ALL_STREAM_MODES + SAMPLED_MODES + RESIDUAL_MODES
+    new = args.mode in ALL_STREAM_MODES + SAMPLED_MODES + RESIDUAL_MODES + NOISE_MODES
     if args.list:
         for case in draw_cases(args.seed, args.n, args.mode, args.big, args.wide):
             print(json.dumps(case), flush=True)
@@ -1640,6 +1739,8 @@ def main(argv=None):
                     sampled_run(case, d, args, worst, tried)
                 elif args.mode == "residual":
                     residual_run(case, d, args, worst, tried)
+                elif args.mode == "noise":
+                    noise_run(case, d, args, worst, tried)
                 elif new:
                     run_new(case, d, args, worst, tried)
                 else:
@@ -1648,7 +1749,7 @@ def main(argv=None):
             engine.FORCE_WAVE, engine.FORCE_TILE_ROWS, engine.FORCE_WIDE = None, 0, 0
     if args.self_check:
         want = {"state": ["zero_c0"], "train_opts": ["truncate", "drop"], "stateful": ["reset"], "finetune": ["no_decay", "unfrozen"],
-                "sampled": ["full_mask"], "residual": ["no_base"]}[args.mode]
+                "sampled": ["full_mask"], "residual": ["no_base"], "noise": ["clean"]}[args.mode]
         missing = [f for f in want if not tried.get(f)]
         if missing:
             raise SystemExit(f"SELF-CHECK INCOMPLETE: no drawn case to try {missing} on (raise --n or change the seed)")

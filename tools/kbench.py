@@ -151,7 +151,8 @@ def main():
         run("preproc_slab", lambda: sb.fill_slab(eng, ws), None, alg * (4 + es))     # 4 B in + ET out per element
         run("preproc_nchw", lambda: ds.device_batch(idx), None, alg * 8)
     if not only or only & {"head_skill", "skill_plain", "head_fwd", "head_feedback", "head_feedback_bwd", "head_feedback_res", "head_feedback_bwd_res", "head_feedback_sel",
-                           "head_feedback_sel1", "head_feedback_bwd_sel", "head_feedback_bwd_sel1", "head_loss", "head_loss_spec", "head_loss_spec3"}:
+                           "head_feedback_sel1", "head_feedback_bwd_sel", "head_feedback_bwd_sel1", "head_loss", "head_loss_spec", "head_loss_spec3",
+                           "input_noise", "noise_normal"}:
         # evaluation: the head on the last step's images + crop + the f64 skill sums in one pass (nint_head_skill_accum), and the
         # same sums from a prediction in memory (nint_skill_accum), one slot, cos-latitude row weights
         O, oy, ox = args.O, 5, 5
@@ -214,6 +215,19 @@ def main():
                 assert lib.nint_head_feedback(P(ws.h[-1]), B, B, ly.Ch, ly.Chp, O, P(hw), P(hb), P(ws.xs), B, args.C, l0.Cxp,
                                               args.C - O, kf, int(eng.lon_cyclic), g, eng.dt, st) == 0
             run("head_feedback", head_feedback, None, B * comp_px * (ly.Chp + max(kf, 1) * O) * es)
+            # input noise on the same O channels of ALL T*B images of the slab: every fold copy of the span read and
+            # written once; and the normals alone, f32 out
+            nsig = torch.full((O,), 0.05, device="cuda")
+            nz = torch.empty(T * B * O * ws.H * ws.W, device="cuda")
+
+            def input_noise():
+                assert lib.nint_input_noise(P(ws.xs), 0, B, T, args.C, l0.Cxp, args.C - O, O, P(nsig), kf, int(eng.lon_cyclic), 1, 2, 0, 0,
+                                            g, eng.dt, st) == 0
+
+            def noise_normal():
+                assert lib.nint_noise_normal(P(nz), B, T, O, 1, 2, 0, 0, g, st) == 0
+            run("input_noise", input_noise, None, 2 * T * B * comp_px * max(kf, 1) * O * es)
+            run("noise_normal", noise_normal, None, nz.numel() * 4)
             # ... and its adjoint (nint_head_feedback_bwd): one step's dx block in (whole 64-byte lines: the fed span's lines), the
             # step's dpred images in and out, one dh block out
             fdx = torch.randn(B * comp_px * l0.Cxp, device="cuda").to(torch.bfloat16 if es == 2 else torch.float32)
@@ -262,7 +276,7 @@ def main():
         run("head_skill", head_skill, None, B * Hc * Wc * ly.Chp * es + maps)
         run("skill_plain", skill_plain, None, B * O * Hc * Wc * 4 + maps)
     tot = sum(ms * (T if not n.startswith(("wgrad", "pack", "preproc")) else 1) for n, ms in rows
-              if n != "preproc_nchw" and not n.startswith(("head_", "skill_")))      # (the evaluation rows are no part of a training step)
+              if n != "preproc_nchw" and not n.startswith(("head_", "skill_", "input_noise", "noise_")))      # (the evaluation and noise rows are no part of the default training step)
     print(f"sum over a step (T x per-step kernels + wgrad + pack): {tot:.2f} ms")
 
 

@@ -10,6 +10,7 @@ hidden 64/32/16, k 5/3/3, 100 x 144 cyclic, T = 12, B = 8, bf16, C = 62 + 20, O 
   (c)  the default teacher-forced step
   --sampling-prob P [P ...]: (s) FusedTrainer(rollout_from=s, sampling_prob=P).step for every P: a fresh
        feed mask per step.  P = 1 is (a), call for call
+  --input-noise STD: (n) (c) with FusedTrainer(input_noise=STD): one nint_input_noise launch more per step
 
 Expectation to check, not a gate: (a) is (b) plus T - s feedback launches forward, T - s backward launches and the x columns
 of layer 0's dgrad at the fed steps.  Every variant is warmed up, then timed with device events over --iters steps; the
@@ -52,6 +53,7 @@ def main():
     ap.add_argument("--rollout-from", type=int, default=1)
     ap.add_argument("--sequence-loss", action="store_true")
     ap.add_argument("--sampling-prob", type=float, nargs="*", default=[], help="also time the scheduled-sampling step at these probabilities")
+    ap.add_argument("--input-noise", type=float, default=None, metavar="STD", help="also time the teacher-forced default step with this input noise on the feedback channels")
     ap.add_argument("--zero-pad", action="store_true", help="zero padding instead of cyclic longitude")
     ap.add_argument("--residual", action="store_true", help="the residual head (DESIGN.md 4.22): ConvLSTM(residual=True) in every variant")
     ap.add_argument("--rounds", type=int, default=7)
@@ -90,6 +92,9 @@ def main():
     for p in args.sampling_prob:
         tr_s = trainer(rollout_from=s, sampling_prob=p, sampling_seed=0)
         variants.append((f"(s) scheduled sampling, p = {p:g}", lambda tr_s=tr_s: tr_s.step(X, y)))
+    if args.input_noise is not None:
+        tr_n = trainer(input_noise=args.input_noise)
+        variants.append((f"(n) teacher-forced, default plan, noise {args.input_noise:g}", lambda: tr_n.step(X, y)))
     for _, fn in variants:                         # warm-up: every shape and code object the timed windows use
         for _ in range(3):
             fn()
