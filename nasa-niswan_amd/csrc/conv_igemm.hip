@@ -597,7 +597,17 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, char* smem, c
     // With lo_gates set the x columns get the same treatment: they are the LAST contribution to d/dh of the layer BELOW at
     // this launch's own time step (that layer's h columns of the next time step are already in out0), so its pointwise
     // backward runs here too and its stand-alone launch disappears.
+    // bf16 (WIDE): the gate stash and dG go as 16-byte vectors, the mirror image of the forward's stash store.  Even lane rows load
+    // gates i and f of their pair's 8 channels, odd rows g and o, each as ONE vector; v_permlane16_swap between lane rows 2r / 2r+1
+    // (channel quads 8r..8r+3 and 8r+4..8r+7 of the same pixel) hands every lane the i, f, g, o of its own quad, and after
+    // lstm_bwd_elem the four dG quads are traded back: 2 + 2 accesses of 16 bytes per column tile instead of 4 + 4 of 8.  The swaps
+    // need every lane, so they stand outside the `okp` blocks (both lanes of a pair hold the same pixel; tile kinds are wave-uniform).
     typedef Pk4<DT> PK;
+    // (the 8-row bodies of 4 column tiles per wave spill already and would spill more, one of them inside its K loop: they keep
+    // the 8-byte form -- tools/regs.py, profiles/bwd_wide_access_asm.txt)
+    constexpr bool WIDE = DT == NINT_BF16 && !(NTW == 4 && MT == 8);
+    typedef __attribute__((ext_vector_type(2))) unsigned u2_t;
+    const int wo = (lane >> 5) * 8 + ((lane >> 4) & 1) * 32;     // WIDE: this lane's 8 channels of gate i (even row) / g (odd row); + 16: f / o
     constexpr int RB0 = NTW >= 4 ? 1 : 4 / NTW;                  // rows per batch: about 4 column tiles (88 registers) in flight
     constexpr int RB = RB0 >= Q ? Q : (Q % RB0 == 0 ? RB0 : 1);
     // per column tile (wave-uniform): 0 = x columns stored / accumulated, 1 = pointwise backward of this layer (h columns),
@@ -614,7 +624,8 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, char* smem, c
     };
 #pragma unroll
     for (int ib = 0; ib < Q; ib += RB) {
-      typename PK::T gq[RB][NTW][4], oldv[RB][NTW];
+      typename PK::T gq[WIDE ? 1 : RB][WIDE ? 1 : NTW][4], oldv[RB][NTW];
+      u32x4_t gw[WIDE ? RB : 1][WIDE ? NTW : 1][2];
       f32x4_t cpq[RB][NTW], cnq[RB][NTW], dcq[RB][NTW];
 #pragma unroll
       for (int ii = 0; ii < RB; ++ii) {
@@ -624,8 +635,12 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, char* smem, c
         for (int j = 0; j < NTW; ++j) {
           int ch0;
           const int kind = tile_kind(j, ch0);
+          if constexpr (WIDE) {
+            gw[ii][j][0] = gw[ii][j][1] = (u32x4_t){0u, 0u, 0u, 0u};
+          } else {
 #pragma unroll
-          for (int q = 0; q < 4; ++q) gq[ii][j][q] = PK::zero();
+            for (int q = 0; q < 4; ++q) gq[ii][j][q] = PK::zero();
+          }
           oldv[ii][j] = PK::zero();
           cpq[ii][j] = cnq[ii][j] = dcq[ii][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
           if (!okp || kind < 0) continue;
@@ -645,9 +660,15 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, char* smem, c
           const float* cpp = lo ? a.lo_c_prev : a.pw_c_prev;
           const float* cnp = lo ? a.lo_c_new : a.pw_c_new;
           const float* dcp_ = lo ? (a.lo_dc_zero ? nullptr : a.lo_dc) : a.pw_dc;
-          const size_t gb = pix * Gc + (size_t)(ch0 >> 4) * 64 + c4;
+          if constexpr (WIDE) {
+            const uint16_t* g8 = (const uint16_t*)gp + pix * Gc + (size_t)(ch0 >> 4) * 64 + wo;
+            gw[ii][j][0] = *(const u32x4_t*)g8;
+            gw[ii][j][1] = *(const u32x4_t*)(g8 + 16);
+          } else {
+            const size_t gb = pix * Gc + (size_t)(ch0 >> 4) * 64 + c4;
 #pragma unroll
-          for (int q = 0; q < 4; ++q) gq[ii][j][q] = PK::ld(gp, gb + 16 * q);
+            for (int q = 0; q < 4; ++q) gq[ii][j][q] = PK::ld(gp, gb + 16 * q);
+          }
           const size_t ci = pix * Cp + ch0 + c4;
           if (cpp) cpq[ii][j] = *(const f32x4_t*)(cpp + ci);
           cnq[ii][j] = *(const f32x4_t*)(cnp + ci);
@@ -663,7 +684,11 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, char* smem, c
         for (int j = 0; j < NTW; ++j) {
           int ch0;
           const int kind = tile_kind(j, ch0);
-          if (!okp || kind < 0) continue;
+          if constexpr (WIDE) {
+            if (kind < 0 || (kind != 1 && kind != 2 && !okp)) continue;        // (kinds 1 and 2 swap: every lane goes on)
+          } else {
+            if (!okp || kind < 0) continue;
+          }
           const f32x4_t dhv = acc[i][j] + PK::up(oldv[ii][j]);
           // kinds 0 and 3: the stores of the EPI_DGRAD epilogue below (twins; shared helpers cost 14 kernels their allocation)
           if (kind == 0) {
@@ -676,7 +701,20 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, char* smem, c
           }
           const bool lo = kind == 2;
           const int Gc = 4 * (lo ? a.lo_Ch16 : a.Ch16), Cp = lo ? a.C0p : a.Chp;
-          const f32x4_t gi = PK::up(gq[ii][j][0]), gf = PK::up(gq[ii][j][1]), gg = PK::up(gq[ii][j][2]), go = PK::up(gq[ii][j][3]);
+          f32x4_t gi, gf, gg, go;
+          if constexpr (WIDE) {
+            // swap(v, s): the odd row's v and the even row's s change places.  Even row: own words 0, 1 are its quad of i (f), the
+            // partner's words 0, 1 its quad of g (o); odd row: the partner's words 2, 3 are its i (f), own words 2, 3 its g (o).
+            const u32x4_t A = gw[ii][j][0], B = gw[ii][j][1];
+            const u2_t a0 = __builtin_amdgcn_permlane16_swap(A[0], A[2], false, false);
+            const u2_t a1 = __builtin_amdgcn_permlane16_swap(A[1], A[3], false, false);
+            const u2_t b0 = __builtin_amdgcn_permlane16_swap(B[0], B[2], false, false);
+            const u2_t b1 = __builtin_amdgcn_permlane16_swap(B[1], B[3], false, false);
+            gi = PK::up((typename PK::T){a0[0], a1[0]}); gg = PK::up((typename PK::T){a0[1], a1[1]});
+            gf = PK::up((typename PK::T){b0[0], b1[0]}); go = PK::up((typename PK::T){b0[1], b1[1]});
+          } else {
+            gi = PK::up(gq[ii][j][0]); gf = PK::up(gq[ii][j][1]); gg = PK::up(gq[ii][j][2]); go = PK::up(gq[ii][j][3]);
+          }
           const f32x4_t cp = cpq[ii][j], cn = cnq[ii][j], dcv = dcq[ii][j];
           f32x4_t o_i, o_f, o_g, o_o, dcp;
 #pragma unroll
@@ -685,12 +723,26 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, char* smem, c
             o_i[e] = b.d_i; o_f[e] = b.d_f; o_g[e] = b.d_g; o_o[e] = b.d_o; dcp[e] = b.dc_prev;
           }
           char* grow = (lo ? a.lo_dG : a.pw_dG) + ((((size_t)img * a.Hh) + (y + a.P)) * a.Wh + (xo + a.P)) * Gc * Elem<DT>::ES;
-          const unsigned ob = (unsigned)(x * Gc + (ch0 >> 4) * 64 + c4);
-          store_vec4<DT>(grow, ob, o_i);
-          store_vec4<DT>(grow, ob + 16, o_f);
-          store_vec4<DT>(grow, ob + 32, o_g);
-          store_vec4<DT>(grow, ob + 48, o_o);
-          *(f32x4_t*)((lo ? a.lo_dc : a.pw_dc) + (rowpix + x) * Cp + ch0 + c4) = dcp;
+          if constexpr (WIDE) {
+            // even row: (own, partner) of the first operand = d/d gate i / f; odd row: (partner, own) of the second = g / o
+            const u2_t ig0 = __builtin_amdgcn_permlane16_swap(pack_bf16x2(o_i[0], o_i[1]), pack_bf16x2(o_g[0], o_g[1]), false, false);
+            const u2_t ig1 = __builtin_amdgcn_permlane16_swap(pack_bf16x2(o_i[2], o_i[3]), pack_bf16x2(o_g[2], o_g[3]), false, false);
+            const u2_t fo0 = __builtin_amdgcn_permlane16_swap(pack_bf16x2(o_f[0], o_f[1]), pack_bf16x2(o_o[0], o_o[1]), false, false);
+            const u2_t fo1 = __builtin_amdgcn_permlane16_swap(pack_bf16x2(o_f[2], o_f[3]), pack_bf16x2(o_o[2], o_o[3]), false, false);
+            if (okp) {
+              uint16_t* g8 = (uint16_t*)grow + (unsigned)(x * Gc + (ch0 >> 4) * 64 + wo);
+              *(u32x4_t*)g8 = (u32x4_t){ig0[0], ig1[0], ig0[1], ig1[1]};
+              *(u32x4_t*)(g8 + 16) = (u32x4_t){fo0[0], fo1[0], fo0[1], fo1[1]};
+              *(f32x4_t*)((lo ? a.lo_dc : a.pw_dc) + (rowpix + x) * Cp + ch0 + c4) = dcp;
+            }
+          } else {
+            const unsigned ob = (unsigned)(x * Gc + (ch0 >> 4) * 64 + c4);
+            store_vec4<DT>(grow, ob, o_i);
+            store_vec4<DT>(grow, ob + 16, o_f);
+            store_vec4<DT>(grow, ob + 32, o_g);
+            store_vec4<DT>(grow, ob + 48, o_o);
+            *(f32x4_t*)((lo ? a.lo_dc : a.pw_dc) + (rowpix + x) * Cp + ch0 + c4) = dcp;
+          }
         }
       }
     }
