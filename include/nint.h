@@ -251,6 +251,21 @@ typedef struct nint_feedback_mask {
   const uint8_t* fed;   /* HOST bytes, T*B of them, index t*B + b, each 0 or 1; NULL = none */
 } nint_feedback_mask;
 
+/* NOISE ON THE FED-BACK VALUE, beside the nint_feedback, for nint_seq_fwd_stochastic and
+ * nint_head_feedback_noise.  (A structure of its own again: the structures above keep their layout and size.)  The value a fed
+ * step t stores for (image b, output o, pixel) becomes
+ *     round_ET( __fadd_rn( p, __fmul_rn(sigma[o], z) ) )
+ * p: the f32 prediction the launch forms without it (a residual head: after the base has been added); z: the normal of
+ * nint_input_noise's rule for (pixel y*W + x, channel offset o, step step0 + t, lane lane0 + b) under the key (seed, draw) --
+ * the same device function, the number nint_noise_normal returns.  The product and the sum are two f32 operations.  A channel
+ * with sigma[o] == 0 stores what it stores without the structure; a folded slab's k copies receive one value, keyed by the
+ * source pixel; under a mask only fed images draw.  sigma == NULL (or a NULL pointer to the structure): off -- the entry is then
+ * the entry it extends: same plan, same launches, same bits. */
+typedef struct nint_feedback_noise {
+  const float* sigma;   /* DEVICE f32 [O]; NULL = off */
+  uint32_t seed, draw, step0, lane0;
+} nint_feedback_noise;
+
 /* launch kinds for nint_seq.probe_mask / the probe tags */
 enum { NINT_PROBE_CAL = 0, NINT_PROBE_GATE = 1, NINT_PROBE_POINTWISE = 2, NINT_PROBE_DGRAD = 3, NINT_PROBE_FUSED = 4,
        NINT_PROBE_WGRAD = 5, NINT_PROBE_FOLD = 6,
@@ -441,6 +456,15 @@ int nint_seq_fwd_residual(const nint_seq* s /*host*/, const nint_feedback* fb /*
                           void* stream);
 int nint_seq_bwd_rollout_residual(const nint_seq* s /*host*/, const nint_feedback* fb /*host*/, const nint_feedback_mask* fm /*host*/,
                                   const nint_feedback_grad* rg /*host*/, void* stream);
+
+/* The closed-loop forward with noise on the fed-back value (nint_feedback_noise above; forward only: there is no backward
+ * entry).  It IS nint_seq_fwd_sampled (residual == 0) / nint_seq_fwd_residual (residual == 1) with the feedback launch of step t
+ * drawing its noise for step step0 + t, lanes lane0 + b: no launch is added, and fn == NULL or fn->sigma == NULL gives that
+ * entry's plan, launches and bits.  The closed-loop contract carries over: the pass equals, bit for bit, the open-loop pass over
+ * an input that already holds the stored values.  Additionally refused before any launch: residual not 0 / 1 (NINT_E_ARG), a
+ * sigma that is not 4-byte aligned (NINT_E_ALIGN, where the feedback is looked at). */
+int nint_seq_fwd_stochastic(const nint_seq* s /*host*/, const nint_feedback* fb /*host*/, const nint_feedback_mask* fm /*host*/,
+                            int residual, const nint_feedback_noise* fn /*host*/, void* stream);
 
 /* The launch plan of a pass, for tests and tools (host only: nothing is enqueued, no pointer is dereferenced).  Both drivers
  * first PLAN a pass into an ordered list of launches and then enqueue that list; this entry runs the same argument checks and
@@ -636,6 +660,13 @@ int nint_head_fwd_seq_res(const void* h_slab, int B, int T, int Ch, int Chp, int
 int nint_head_feedback_res(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w, const float* b,
                            void* xs_slab, int x_n0, int Cx, int Cxp, int c0, int xfold_k, int lon_cyclic, int base_n0,
                            const uint8_t* fed /*host, NULL = every image*/, const nint_geom* g, int dtype, void* stream);
+/* nint_head_feedback_res with noise on the stored value (nint_feedback_noise): image x_n0 + i draws for (step, lane0 + i).
+ * fn == NULL or fn->sigma == NULL: nint_head_feedback_res.  Checks: its checks, then NINT_E_ALIGN for a sigma that is not
+ * 4-byte aligned. */
+int nint_head_feedback_noise(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w, const float* b,
+                             void* xs_slab, int x_n0, int Cx, int Cxp, int c0, int xfold_k, int lon_cyclic, int base_n0,
+                             const uint8_t* fed /*host, NULL = every image*/, const nint_geom* g, int dtype, void* stream,
+                             const nint_feedback_noise* fn /*host*/, uint32_t step);
 /* nint_head_feedback_bwd[_sel] with the skip term: on a fed image g = fl32( fl32(dpred + xi) + dpred[pnext_n0 + i] ), stored
  * back and handed to the dh body; an unfed image as in nint_head_feedback_bwd_sel.  The images [pnext_n0, pnext_n0 + N) of the
  * dpred slab -- the total cotangent of the fed step's own prediction -- are read, never written, and must lie apart from
@@ -872,6 +903,44 @@ int nint_head_skill_accum(const void* h_slab, int n0, int N, int Ch, int Chp, in
                           const float* y, const int32_t* slot /*host*/, int nslots, const double* row_w, double* pix,
                           double* sample, float* pred_out, double* scratch, size_t scratch_bytes, const nint_geom* g,
                           int oy, int ox, int Hc, int Wc, int dtype, void* stream);
+
+/* ---- evaluation: ensemble sums -------------------------------------------------------- */
+/* M member predictions of each sample against one target, in one pass over the members where they lie.  Member i of sample
+ * n is an (O, H, W) f32 image at pred + sample_off[n] + i * member_stride (elements; the offsets need be neither ordered nor
+ * disjoint, so the (lanes, T, O, H, W) head output of a roll-out whose lanes are start * M + member is read in place: sample
+ * (start, lead j) at ((start * M) * T + spinup + j) * O*H*W, member stride T * O*H*W).  y (N,O,Hc,Wc), the crop window, slot,
+ * nslots and row_w are nint_skill_accum's.
+ * Per cell (sample, output, crop pixel), in f64, every product and every sum its own operation, NO division:
+ *   x_i = (double)member i, t = (double)y, dM = (double)M;   S = x_0 + ... + x_{M-1} in that order;   E = S - dM*t;
+ *   A = sum_i |x_i - t| and V = sum_i (dM*x_i - S)^2, i ascending;   D = sum_{i<j} |x_i - x_j|, (i, j) in lexicographic order.
+ *   pix       [nslots][NINT_ENS_PIX][O][Hc][Wc] f64, ACCUMULATED: sum E^2, sum V, sum A, sum D, sum E, sum t, sum t^2 over
+ *             the slot's samples; one thread owns a cell for the whole call and adds the call's samples in ascending n, so
+ *             pix is bit-identical run to run and under any split of the samples into consecutive calls.
+ *   sample    [N][O][NINT_ENS_SAMPLE] f64, OVERWRITTEN: sum E^2, sum V, sum A, sum D, sum row_w*E^2, sum row_w*V,
+ *             sum row_w*A, sum row_w*D over the crop; the reduction tree depends on (O, Hc, Wc) only.
+ *   rank_hist [nslots][O][M + 2] int64, ACCUMULATED: bin r = #{i : x_i < t} (ties go low) counts the cells of the samples
+ *             with slot >= 0; bin M + 1 counts instead the cells whose target or any member is NaN (such a cell still adds
+ *             what the arithmetic gives to the f64 sums: masking is the caller's, through slot = -1).  Integer atomics.
+ *   mean_out  (N,O,Hc,Wc) f32 or NULL: (float)(S / dM), the one division, outside every sum.
+ *   scratch   nint_ens_scratch_bytes(N, M, O, Hc, Wc) bytes, 8-byte aligned.  Memory contract: exactly that
+ *             many suffice (N beyond NINT_ENS_MAX_N included), no store goes outside the named extents and no result depends
+ *             on a byte the library did not write.
+ * The host derives the ensemble mean's MSE (sum E^2 / M^2 / n), the mean variance (sum V / (M^2 (M-1)) / n), the CRPS
+ * (fair: A/M - D/(M(M-1)); plain: A/M - D/M^2), the bias and R2 (inference.ensemble_from_sums).  The sums are additive: a
+ * data-parallel reduction adds the ranks' pix and rank_hist.
+ * NINT_E_ARG: a NULL pred / sample_off / y / pix / sample / rank_hist / scratch, M outside [2, NINT_ENS_MAX_M], N or O < 1,
+ * a negative offset or stride, nslots < 1, a slot outside [-1, nslots), a crop outside the grid, a scratch that is too
+ * small; then NINT_E_ALIGN: pix / sample / rank_hist / scratch / row_w not 8-byte, pred / y / mean_out not 4-byte aligned --
+ * all before any launch. */
+#define NINT_ENS_MAX_M 64
+#define NINT_ENS_MAX_N 64     /* samples per launch; larger N is split internally, as NINT_SKILL_MAX_N is */
+#define NINT_ENS_PIX 7        /* f64 planes per slot: sum E^2, sum V, sum A, sum D, sum E, sum t, sum t^2 */
+#define NINT_ENS_SAMPLE 8     /* f64 per (sample, output) */
+size_t nint_ens_scratch_bytes(int N, int M, int O, int Hc, int Wc);       /* host arithmetic only */
+int nint_ens_accum(const float* pred, const int64_t* sample_off /*host, N*/, int64_t member_stride, int M, const float* y,
+                   const int32_t* slot /*host, N, or NULL = all 0*/, int nslots, const double* row_w /*device [Hc] or NULL = 1*/,
+                   double* pix, double* sample, int64_t* rank_hist, float* mean_out /*(N,O,Hc,Wc) or NULL*/, double* scratch,
+                   size_t scratch_bytes, int N, int O, int H, int W, int oy, int ox, int Hc, int Wc, void* stream);
 
 /* ---- optimiser (train.py:71,110) ---------------------------------------------------------------- */
 /* torch.optim.Adam (eps 1e-8, no weight decay / amsgrad) on one flat f32 buffer.

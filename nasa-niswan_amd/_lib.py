@@ -18,6 +18,7 @@ NINT_LOSS_SCRATCH_FLOATS = 8194
 NINT_LOSS_SPEC_SCRATCH_FLOATS = 10242     # the _spec loss entries: five doubles per workgroup
 NINT_LOSS_STATS = 8
 NINT_SKILL_PIX, NINT_SKILL_SAMPLE, NINT_SKILL_MAX_N = 5, 8, 64
+NINT_ENS_PIX, NINT_ENS_SAMPLE, NINT_ENS_MAX_N, NINT_ENS_MAX_M = 7, 8, 64, 64
 NINT_GRAD_NORM_BLOCKS = 256
 NINT_OPT_STATE = 16
 NINT_MAX_OPT_GROUPS = 2 * NINT_MAX_LAYERS + 2
@@ -66,6 +67,12 @@ class NintFeedbackMask(C.Structure):
     """nint_feedback_mask: scheduled sampling (the _sampled entries) -- T*B HOST bytes, index t*B + b, 1 = that image runs that
     step on the fed-back prediction; NULL: use nint_feedback.from"""
     _fields_ = [("fed", vp)]
+
+
+class NintFeedbackNoise(C.Structure):
+    """nint_feedback_noise: noise on the fed-back value (nint_seq_fwd_stochastic, nint_head_feedback_noise) -- O DEVICE sigmas
+    (NULL: off) and the generator's key and offsets, as nint_input_noise takes them"""
+    _fields_ = [("sigma", vp), ("seed", C.c_uint32), ("draw", C.c_uint32), ("step0", C.c_uint32), ("lane0", C.c_uint32)]
 
 
 class NintHeadBase(C.Structure):
@@ -119,6 +126,7 @@ _PFB = C.POINTER(NintFeedback)
 _PFG = C.POINTER(NintFeedbackGrad)
 _PFM = C.POINTER(NintFeedbackMask)
 _PHB = C.POINTER(NintHeadBase)
+_PFN = C.POINTER(NintFeedbackNoise)
 SIGNATURES = {
     "nint_version": (_I, []),
     "nint_error_string": (C.c_char_p, [_I]),
@@ -160,6 +168,7 @@ SIGNATURES = {
     "nint_seq_bwd_rollout_sampled": (_I, [_PS, _PFB, _PFM, _PFG, vp]),
     "nint_seq_fwd_residual": (_I, [_PS, _PFB, _PFM, vp]),
     "nint_seq_bwd_rollout_residual": (_I, [_PS, _PFB, _PFM, _PFG, vp]),
+    "nint_seq_fwd_stochastic": (_I, [_PS, _PFB, _PFM, _I, _PFN, vp]),
     "nint_debug_seq_plan_sampled": (_I, [_PS, _PFB, _PFM, _I, C.POINTER(NintLaunchRec), _I]),
     "nint_debug_multi_carrier": (_I, [C.POINTER(C.c_int32), _I, _I]),
     "nint_debug_wgrad_plan": (_I, [_PL, _PG, _I, _I, _I, _I, C.POINTER(NintWgradPlanRec)]),
@@ -171,6 +180,7 @@ SIGNATURES = {
     "nint_head_fwd_res": (_I, [vp, _I, _I, _I, _I, _I, vp, vp, vp, _PG, _I, _PHB, vp]),
     "nint_head_fwd_seq_res": (_I, [vp, _I, _I, _I, _I, _I, vp, vp, vp, _PG, _I, _PHB, vp]),
     "nint_head_feedback_res": (_I, [vp, _I, _I, _I, _I, _I, vp, vp, vp, _I, _I, _I, _I, _I, _I, _I, vp, _PG, _I, vp]),
+    "nint_head_feedback_noise": (_I, [vp, _I, _I, _I, _I, _I, vp, vp, vp, _I, _I, _I, _I, _I, _I, _I, vp, _PG, _I, vp, _PFN, _U]),
     "nint_head_feedback_bwd_res": (_I, [vp, _I, vp, _I, vp, _I, _I, _I, _I, _I, vp, _I, _I, _I, _I, _I, _I, vp, _PG, _I, vp]),
     "nint_input_noise": (_I, [vp, _I, _I, _I, _I, _I, _I, _I, vp, _I, _I, _U, _U, _U, _U, _PG, _I, vp]),
     "nint_noise_normal": (_I, [vp, _I, _I, _I, _U, _U, _U, _U, _PG, vp]),
@@ -194,6 +204,9 @@ SIGNATURES = {
     "nint_skill_accum": (_I, [vp, vp, C.POINTER(C.c_int32), _I, vp, vp, vp, vp, _SZ, _I, _I, _I, _I, _I, _I, _I, _I, vp]),
     "nint_head_skill_accum": (_I, [vp, _I, _I, _I, _I, _I, vp, vp, vp, C.POINTER(C.c_int32), _I, vp, vp, vp, vp, vp, _SZ, _PG,
                                    _I, _I, _I, _I, _I, vp]),
+    "nint_ens_scratch_bytes": (_SZ, [_I, _I, _I, _I, _I]),
+    "nint_ens_accum": (_I, [vp, C.POINTER(C.c_int64), C.c_int64, _I, vp, C.POINTER(C.c_int32), _I, vp, vp, vp, vp, vp, vp, _SZ,
+                            _I, _I, _I, _I, _I, _I, _I, _I, vp]),
     "nint_adam_flat": (_I, [vp, vp, vp, vp, _SZ, C.c_double, C.c_double, C.c_double, C.c_double, _I, _F, vp]),
     "nint_grad_norm_scratch_bytes": (_SZ, []),
     "nint_grad_norm_flat": (_I, [vp, _SZ, _F, vp, vp, _SZ, vp]),

@@ -609,9 +609,15 @@ extern "C" int nint_head_fwd_seq(const void* h_slab, int B, int T, int Ch, int C
 // values from channel (kf/2)*Cx + c0 of the same pixel of image a.xb + n, the step before -- in the pass that loads h, and adds
 // each to its dot product (head_add_base) before the rounding.  The launch writes images from a.xs on and reads images from a.xb
 // on: the plan keeps the two ranges apart.  The instantiation without it never reads the pointer.
-template <int DT, int CHV, bool SEL = false, bool RES = false>
+// NZ (noise on the fed-back value): the same thread adds __fmul_rn(sigma[o], z) to the f32 value -- after the base --
+// before the rounding: two f32 operations, never one FMA.  z is nint_input_noise's normal of (pixel y*W + x, o, a.nz_step,
+// a.nz_lane0 + image): one Philox block (noise_quad, nint_common.h) per four outputs.  A channel with sigma[o] == 0 is left as the
+// launch without NZ forms it.  What is staged in p_s is the stored value, so a folded slab's copies and a cyclic wrap gather one
+// number per source pixel, as before.  The instantiations without it take the plan without the fields (FbPlan, as ever).
+template <int DT, int CHV, bool SEL = false, bool RES = false, bool NZ = false>
 __global__ __launch_bounds__(256) void head_feedback_kernel(const void* __restrict__ h, const float* __restrict__ w,
-                                                            const float* __restrict__ b, void* __restrict__ xs, FbPlan a) {
+                                                            const float* __restrict__ b, void* __restrict__ xs,
+                                                            std::conditional_t<NZ, FbPlanNz, FbPlan> a) {
   // (the pointers as __restrict__ arguments of their own, as head_fwd_kernel has them; a is the rest of the plan)
   if constexpr (SEL) {
     if (!((a.mask >> (blockIdx.x / a.H)) & 1ull)) return;
@@ -631,9 +637,21 @@ __global__ __launch_bounds__(256) void head_feedback_kernel(const void* __restri
       const f32x4_t v = (c < a.Chp) ? load_vec4<DT>(h, hb + c) : (f32x4_t){0.f, 0.f, 0.f, 0.f};
       hv[c] = v[0]; hv[c + 1] = v[1]; hv[c + 2] = v[2]; hv[c + 3] = v[3];
     }
+    f32x4_t z = {0.f, 0.f, 0.f, 0.f};
     for (int o = 0; o < a.O; ++o) {
       float p = head_dot<CHV>(b ? b[o] : 0.f, w_s + o * CHV, hv);
       if constexpr (RES) p = head_add_base(p, load_elem<DT>(a.xb, (row + x) * a.Cxp + (size_t)((a.kf >> 1) * a.Cx + a.c0 + o)));
+      if constexpr (NZ) {
+        if ((o & 3) == 0) z = noise_quad((uint32_t)(y * a.W + x), (uint32_t)(o >> 2), a.nz_step, a.nz_lane0 + (uint32_t)n, a.nz_seed, a.nz_draw);
+        const float sg = a.nz_sigma[o];
+        if (sg != 0.f) {
+          // (the rule's __fmul_rn and __fadd_rn: HIP defines both as the plain operators, which the compiler contracts into one FMA
+          // wherever it may -- so they are written as operators under contraction off)
+#pragma clang fp contract(off)
+          const float add = sg * z[o & 3];
+          p = p + add;
+        }
+      }
       p_s[x * a.O + o] = DT == NINT_BF16 ? bf2f(f2bf(p)) : p;
     }
   }
@@ -704,14 +722,22 @@ int nint_internal_feedback_plan(const void* h_slab, int n0, int N, int Ch, int C
   return NINT_OK;
 }
 
-int nint_internal_feedback_enqueue(const FbPlan* p, void* stream) {
+int nint_internal_feedback_enqueue(const FbPlanNz* p, void* stream) {
   const int rc = nint_by_dtype(p->dtype, [&](auto dt) -> int {
     return head_by_chv(p->Chp, [&](auto chv) -> int {
       constexpr int DT = decltype(dt)::value, CHV = decltype(chv)::value;
+      const dim3 grid((unsigned)((size_t)p->N * p->H));
+      if (p->nz) {                                 // (the instantiations with the noise take the whole plan, the others the FbPlan in it)
+        auto kern = p->res ? (p->sel ? head_feedback_kernel<DT, CHV, true, true, true> : head_feedback_kernel<DT, CHV, false, true, true>)
+                           : (p->sel ? head_feedback_kernel<DT, CHV, true, false, true> : head_feedback_kernel<DT, CHV, false, false, true>);
+        if (p->lds > 64 * 1024) NINT_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->lds));
+        hipLaunchKernelGGL(kern, grid, dim3(256), p->lds, (hipStream_t)stream, p->h, p->w, p->b, p->xs, *p);
+        return NINT_OK;
+      }
       auto kern = p->res ? (p->sel ? head_feedback_kernel<DT, CHV, true, true> : head_feedback_kernel<DT, CHV, false, true>)
                          : (p->sel ? head_feedback_kernel<DT, CHV, true, false> : head_feedback_kernel<DT, CHV, false, false>);
       if (p->lds > 64 * 1024) NINT_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->lds));
-      hipLaunchKernelGGL(kern, dim3((unsigned)((size_t)p->N * p->H)), dim3(256), p->lds, (hipStream_t)stream, p->h, p->w, p->b, p->xs, *p);
+      hipLaunchKernelGGL(kern, grid, dim3(256), p->lds, (hipStream_t)stream, p->h, p->w, p->b, p->xs, (const FbPlan&)*p);
       return NINT_OK;
     });
   });
@@ -723,7 +749,7 @@ int nint_internal_feedback_enqueue(const FbPlan* p, void* stream) {
 extern "C" int nint_head_feedback(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w, const float* b,
                                   void* xs_slab, int x_n0, int Cx, int Cxp, int c0, int xfold_k, int lon_cyclic,
                                   const nint_geom* g, int dtype, void* stream) {
-  FbPlan p;
+  FbPlanNz p = {};
   const int rc = nint_internal_feedback_plan(h_slab, n0, N, Ch, Chp, O, w, b, xs_slab, x_n0, Cx, Cxp, c0, xfold_k, lon_cyclic, g, dtype, &p);
   return rc != NINT_OK ? rc : nint_internal_feedback_enqueue(&p, stream);
 }
@@ -733,7 +759,7 @@ extern "C" int nint_head_feedback(const void* h_slab, int n0, int N, int Ch, int
 extern "C" int nint_head_feedback_sel(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w, const float* b,
                                       void* xs_slab, int x_n0, int Cx, int Cxp, int c0, int xfold_k, int lon_cyclic,
                                       const uint8_t* fed, const nint_geom* g, int dtype, void* stream) {
-  FbPlan p;
+  FbPlanNz p = {};
   int rc = nint_internal_feedback_plan(h_slab, n0, N, Ch, Chp, O, w, b, xs_slab, x_n0, Cx, Cxp, c0, xfold_k, lon_cyclic, g, dtype, &p);
   if (rc == NINT_OK) rc = nint_internal_mask_word(fed, N, &p.mask);
   if (rc != NINT_OK) return rc;
@@ -756,10 +782,31 @@ int nint_internal_feedback_base(FbPlan* p, const void* xs_slab, int x_n0, int ba
 extern "C" int nint_head_feedback_res(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w, const float* b,
                                       void* xs_slab, int x_n0, int Cx, int Cxp, int c0, int xfold_k, int lon_cyclic, int base_n0,
                                       const uint8_t* fed, const nint_geom* g, int dtype, void* stream) {
-  FbPlan p;
+  return nint_head_feedback_noise(h_slab, n0, N, Ch, Chp, O, w, b, xs_slab, x_n0, Cx, Cxp, c0, xfold_k, lon_cyclic, base_n0, fed, g, dtype,
+                                  stream, nullptr, 0);
+}
+
+// The noise of a feedback launch (FbPlanNz.nz*): called behind nint_internal_feedback_plan, which fills the FbPlan in it alone.  This
+// function owns the noise's fields and sets every one of them: off (fn or its sigma NULL) is nz = 0, whatever the plan held.
+int nint_internal_feedback_noise(FbPlanNz* p, const nint_feedback_noise* fn, uint32_t step) {
+  p->nz_sigma = nullptr; p->nz_seed = p->nz_draw = p->nz_step = p->nz_lane0 = 0; p->nz = 0;
+  if (!fn || !fn->sigma) return NINT_OK;
+  if ((((uintptr_t)fn->sigma) & 3) != 0) return NINT_E_ALIGN;
+  p->nz_sigma = fn->sigma; p->nz_seed = fn->seed; p->nz_draw = fn->draw; p->nz_step = step; p->nz_lane0 = fn->lane0;
+  p->nz = 1;
+  return NINT_OK;
+}
+
+// ... and with noise on the stored value: nint_head_feedback_res's checks in its order, then the noise's
+extern "C" int nint_head_feedback_noise(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w, const float* b,
+                                        void* xs_slab, int x_n0, int Cx, int Cxp, int c0, int xfold_k, int lon_cyclic, int base_n0,
+                                        const uint8_t* fed, const nint_geom* g, int dtype, void* stream,
+                                        const nint_feedback_noise* fn, uint32_t step) {
+  FbPlanNz p = {};
   int rc = nint_internal_feedback_plan(h_slab, n0, N, Ch, Chp, O, w, b, xs_slab, x_n0, Cx, Cxp, c0, xfold_k, lon_cyclic, g, dtype, &p);
   if (rc == NINT_OK && base_n0 >= 0) rc = nint_internal_feedback_base(&p, xs_slab, x_n0, base_n0, N);
   if (rc == NINT_OK && fed) { rc = nint_internal_mask_word(fed, N, &p.mask); p.sel = 1; }
+  if (rc == NINT_OK) rc = nint_internal_feedback_noise(&p, fn, step);
   if (rc != NINT_OK) return rc;
   return !p.sel || p.mask ? nint_internal_feedback_enqueue(&p, stream) : (int)NINT_OK;
 }
@@ -1612,21 +1659,7 @@ extern "C" int nint_head_loss_seq_fused_spec(const void* h_slab, int B, int T, i
 #define SKILL_OG 4
 struct SkillPlan { int32_t slot[NINT_SKILL_MAX_N]; uint8_t idx[NINT_SKILL_MAX_N]; };   // the call's samples in slot order
 
-// Sum of v[k] over the wave's 64 lanes for k = 0..7 at once: three halving exchanges (each lane keeps half of its values and
-// takes the partner's for them), then three plain ones.  Lane 8*k ends with the total of v[k] (every lane of 8k..8k+7 does).
-__device__ __forceinline__ double skill_wave_fold(const double (&v)[8], int lane) {
-  const bool b5 = lane & 32, b4 = lane & 16, b3 = lane & 8;
-  double a[4], c[2];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) a[j] = (b5 ? v[j + 4] : v[j]) + __shfl_xor(b5 ? v[j] : v[j + 4], 32);
-#pragma unroll
-  for (int j = 0; j < 2; ++j) c[j] = (b4 ? a[j + 2] : a[j]) + __shfl_xor(b4 ? a[j] : a[j + 2], 16);
-  double s = (b3 ? c[1] : c[0]) + __shfl_xor(b3 ? c[0] : c[1], 8);   // the value k = lane >> 3 over the 8 lanes that share lane & 7
-  s += __shfl_xor(s, 4);
-  s += __shfl_xor(s, 2);
-  s += __shfl_xor(s, 1);
-  return s;
-}
+// (skill_wave_fold, the per-wave sum of eight values at once: nint_common.h -- ensemble.hip forms its sample rows with it too)
 
 // the prediction of (sample n, output o0 + u) at the thread's pixel, from memory ...
 struct SkillPredPlain {
@@ -1765,6 +1798,12 @@ __global__ __launch_bounds__(256) void skill_fold_kernel(const double* __restric
   if (j == 0) sample[(size_t)pair * NINT_SKILL_SAMPLE + k] = t;
 }
 
+int nint_internal_skill_fold_enqueue(const double* part, double* sample, int npair, int NP, void* stream) {
+  hipLaunchKernelGGL(skill_fold_kernel, dim3(nint_cdiv(npair, 4)), dim3(256), 0, (hipStream_t)stream, part, sample, npair, NP);
+  NINT_LAUNCH_CHECK();
+  return NINT_OK;
+}
+
 static inline size_t skill_pix_blocks(int Hc, int Wc) { return ((size_t)Hc * Wc + 255) / 256; }
 
 extern "C" size_t nint_skill_scratch_bytes(int N, int O, int Hc, int Wc) {
@@ -1802,9 +1841,8 @@ static int skill_run(const int32_t* slot, double* sample, double* scratch, int N
     }
     launch(c0, nc, plan);
     NINT_LAUNCH_CHECK();
-    hipLaunchKernelGGL(skill_fold_kernel, dim3(nint_cdiv(nc * O, 4)), dim3(256), 0, st, scratch,
-                       sample + (size_t)c0 * O * NINT_SKILL_SAMPLE, nc * O, NP);
-    NINT_LAUNCH_CHECK();
+    const int rc = nint_internal_skill_fold_enqueue(scratch, sample + (size_t)c0 * O * NINT_SKILL_SAMPLE, nc * O, NP, st);
+    if (rc != NINT_OK) return rc;
   }
   return NINT_OK;
 }

@@ -218,6 +218,58 @@ __device__ __forceinline__ void lstm_bwd_pointwise_body(const PwArgs& a, size_t 
   }
 }
 
+// Sum of v[k] over the wave's 64 lanes for k = 0..7 at once: three halving exchanges (each lane keeps half of its values and
+// takes the partner's for them), then three plain ones.  Lane 8*k ends with the total of v[k] (every lane of 8k..8k+7 does).
+// (head.hip: the skill sums' sample rows; ensemble.hip: the ensemble sums'.)
+__device__ __forceinline__ double skill_wave_fold(const double (&v)[8], int lane) {
+  const bool b5 = lane & 32, b4 = lane & 16, b3 = lane & 8;
+  double a[4], c[2];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) a[j] = (b5 ? v[j + 4] : v[j]) + __shfl_xor(b5 ? v[j] : v[j + 4], 32);
+#pragma unroll
+  for (int j = 0; j < 2; ++j) c[j] = (b4 ? a[j + 2] : a[j]) + __shfl_xor(b4 ? a[j] : a[j + 2], 16);
+  double s = (b3 ? c[1] : c[0]) + __shfl_xor(b3 ? c[0] : c[1], 8);   // the value k = lane >> 3 over the 8 lanes that share lane & 7
+  s += __shfl_xor(s, 4);
+  s += __shfl_xor(s, 2);
+  s += __shfl_xor(s, 1);
+  return s;
+}
+
+// ---- the noise generator: noise.hip (nint_input_noise, nint_noise_normal) and head.hip (the noise on the
+// fed-back value, nint_feedback_noise) inline these, so a value is the same number whichever kernel draws it
+// Philox4x32-10 (Salmon et al., SC'11; the Random123 constants)
+__device__ __forceinline__ u32x4_t philox4x32_10(u32x4_t c, uint32_t k0, uint32_t k1) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint32_t h0 = __umulhi(0xD2511F53u, c[0]), l0 = 0xD2511F53u * c[0];
+    const uint32_t h1 = __umulhi(0xCD9E8D57u, c[2]), l1 = 0xCD9E8D57u * c[2];
+    c = (u32x4_t){h1 ^ c[1] ^ k0, l1, h0 ^ c[3] ^ k1, l0};
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  return c;
+}
+
+// one word pair -> two normals (Box-Muller): u in [2^-24, 1 - 2^-24] and a in [0, 2) are exact in f32; precise logf / sqrtf /
+// sincospif (no file of the library is built with fast-math forms)
+__device__ __forceinline__ void noise_pair(uint32_t wa, uint32_t wb, float& z0, float& z1) {
+  const float u = ((float)(wa >> 9) + 0.5f) * 0x1p-23f;
+  const float a = (float)(wb >> 8) * 0x1p-23f;
+  const float r = sqrtf(-2.f * logf(u));
+  float s, c;
+  sincospif(a, &s, &c);
+  z0 = r * c; z1 = r * s;
+}
+
+// THE device function every kernel inlines: the four normals of channel offsets 4q .. 4q + 3 of one pixel
+__device__ __forceinline__ f32x4_t noise_quad(uint32_t pix, uint32_t q, uint32_t step, uint32_t lane, uint32_t seed, uint32_t draw) {
+  const u32x4_t w = philox4x32_10((u32x4_t){pix, q, step, lane}, seed, draw);
+  f32x4_t z;
+  float z0, z1;
+  noise_pair(w[0], w[1], z0, z1); z[0] = z0; z[1] = z1;
+  noise_pair(w[2], w[3], z0, z1); z[2] = z0; z[3] = z1;
+  return z;
+}
+
 // launcher-side descriptors -----------------------------------------------------------------
 struct ConvArgs {
   const char* src0;      // halo slab (x for fwd, dG for dgrad)
@@ -376,6 +428,13 @@ struct FbPlan {
   // plan function below leaves: the kernels without it, which never read the pointer.
   const void* xb; int res;
 };
+// NOISE ON THE FED-BACK VALUE: the plan with the noise's fields behind it.  nz = 1: the instantiation that adds
+// __fmul_rn(sigma[o], z) to the f32 value before the rounding, z = noise_quad's normal of (pixel, o, nz_step, nz_lane0 + image), and
+// takes this whole structure.  nz = 0, what every plan function below leaves: the kernels without it, whose argument stays the FbPlan
+// above -- so they are, byte for byte, the kernels they were.
+struct FbPlanNz : FbPlan {
+  const float* nz_sigma; uint32_t nz_seed, nz_draw, nz_step, nz_lane0; int nz;
+};
 // The mask word of N images from N HOST bytes, each 0 or 1 (nint_feedback_mask, nint_head_feedback_sel): NINT_E_ARG for a NULL
 // pointer or any other byte, then NINT_E_SHAPE for more images than the word has bits.
 static inline int nint_internal_mask_word(const unsigned char* fed, int N, unsigned long long* word) {
@@ -393,9 +452,11 @@ static inline int nint_internal_mask_word(const unsigned char* fed, int N, unsig
 int nint_internal_feedback_plan(const void* h_slab, int n0, int N, int Ch, int Chp, int O, const float* w, const float* b,
                                 void* xs_slab, int x_n0, int Cx, int Cxp, int c0, int xfold_k, int lon_cyclic, const nint_geom* g,
                                 int dtype, FbPlan* plan);
-int nint_internal_feedback_enqueue(const FbPlan* plan, void* stream);
+int nint_internal_feedback_enqueue(const FbPlanNz* plan, void* stream);
 // residual head: the planned launch reads its base from images [base_n0, base_n0 + N) of the slab it writes [x_n0, x_n0 + N) of
 int nint_internal_feedback_base(FbPlan* plan, const void* xs_slab, int x_n0, int base_n0, int N);
+// noise on the stored value: the planned launch draws for step `step`; fn == nullptr or fn->sigma == nullptr leaves the plan as it is
+int nint_internal_feedback_noise(FbPlanNz* plan, const nint_feedback_noise* fn, uint32_t step);
 // ... and its adjoint, the feedback step of the roll-out backward (nint_head_feedback_bwd's arguments)
 struct FbBwdPlan {
   const void* dx; float* dpred; void* dh; const float* w;        // dx, dpred, dh: the FIRST image read / written
@@ -409,6 +470,9 @@ int nint_internal_feedback_bwd_plan(const void* dx, int dx_n0, float* dpred, int
                                     int O, const float* w, int Cx, int Cxp, int c0, int xfold_k, int lon_cyclic, const nint_geom* g,
                                     int dtype, FbBwdPlan* plan);
 int nint_internal_feedback_bwd_enqueue(const FbBwdPlan* plan, void* stream);
+// head.hip: skill_fold_kernel, the fixed-order fold of NP partial rows of eight f64 per pair into sample[pair][8] -- the second
+// launch of nint_skill_accum / nint_head_skill_accum and of nint_ens_accum (ensemble.hip)
+int nint_internal_skill_fold_enqueue(const double* part, double* sample, int npair, int NP, void* stream);
 #define NINT_MULTI_MAX 4  // problems per merged grid (the kernels of NINT_MULTI_KERNELS, csrc/conv_igemm.hip)
 struct CellFwdJob {      // one gate launch (nint_cell_fwd's arguments)
   const nint_layer* ly; const void* x_slab; const void* h_prev; const float* c_prev; void* h_out; float* c_out; void* gates_out;

@@ -4,39 +4,8 @@
 // produces it: the sweep and the recompute of a segmented window, a plain and a folded slab, one rank or many see the same values.
 #include "nint_common.h"
 
-// ------------------------------------------------------------------------------ the generator
-// Philox4x32-10 (Salmon et al., SC'11; the Random123 constants)
-__device__ __forceinline__ u32x4_t philox4x32_10(u32x4_t c, uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t h0 = __umulhi(0xD2511F53u, c[0]), l0 = 0xD2511F53u * c[0];
-    const uint32_t h1 = __umulhi(0xCD9E8D57u, c[2]), l1 = 0xCD9E8D57u * c[2];
-    c = (u32x4_t){h1 ^ c[1] ^ k0, l1, h0 ^ c[3] ^ k1, l0};
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  return c;
-}
-
-// one word pair -> two normals (Box-Muller): u in [2^-24, 1 - 2^-24] and a in [0, 2) are exact in f32; precise logf / sqrtf /
-// sincospif (this file is never built with fast-math forms)
-__device__ __forceinline__ void noise_pair(uint32_t wa, uint32_t wb, float& z0, float& z1) {
-  const float u = ((float)(wa >> 9) + 0.5f) * 0x1p-23f;
-  const float a = (float)(wb >> 8) * 0x1p-23f;
-  const float r = sqrtf(-2.f * logf(u));
-  float s, c;
-  sincospif(a, &s, &c);
-  z0 = r * c; z1 = r * s;
-}
-
-// THE device function both kernels inline: the four normals of channel offsets 4q .. 4q + 3 of one pixel
-__device__ __forceinline__ f32x4_t noise_quad(uint32_t pix, uint32_t q, uint32_t step, uint32_t lane, uint32_t seed, uint32_t draw) {
-  const u32x4_t w = philox4x32_10((u32x4_t){pix, q, step, lane}, seed, draw);
-  f32x4_t z;
-  float z0, z1;
-  noise_pair(w[0], w[1], z0, z1); z[0] = z0; z[1] = z1;
-  noise_pair(w[2], w[3], z0, z1); z[2] = z0; z[3] = z1;
-  return z;
-}
+// (the generator -- philox4x32_10, noise_pair, noise_quad -- lives in nint_common.h: head.hip inlines it too, for the noise on the
+// fed-back value)
 
 // ------------------------------------------------------------------------------ z alone (nint_noise_normal)
 struct NormalPlan {

@@ -134,6 +134,7 @@ static const nint_feedback NO_FB = {};
 struct Pass {
   const nint_seq* s; const nint_feedback* fb; const nint_feedback_grad* rg; int dir; const uint8_t* mask;
   bool res;                                        // RESIDUAL HEAD: the feedback launches of the plan are the _res ones
+  const nint_feedback_noise* fn;                   // NOISE ON THE FED-BACK VALUE (forward only), or nullptr: none
   bool bwd() const { return dir != PASS_FWD; }
   // the first step with a fed image (a mask; any non-zero byte counts, so that a bad byte is looked at), else fb->from
   int first() const {
@@ -151,10 +152,11 @@ struct Pass {
   bool rollout() const { return dir == PASS_ROLLOUT && fed(); }      // ... and this pass differentiates through it
 };
 static Pass pass_of(const nint_seq* s, const nint_feedback* fb, const nint_feedback_grad* rg, int dir, const nint_feedback_mask* fm = nullptr,
-                    bool res = false) {
+                    bool res = false, const nint_feedback_noise* fn = nullptr) {
   // (a mask beside a head of no outputs says nothing; s is checked before anything reads it: pass_check step 1 comes first)
   const bool masked = fm && fm->fed && fb && fb->O > 0 && s && s->B >= 1 && s->T >= 1;
-  return Pass{s, fb ? fb : &NO_FB, dir == PASS_ROLLOUT ? rg : nullptr, dir, masked ? fm->fed : nullptr, res};
+  return Pass{s, fb ? fb : &NO_FB, dir == PASS_ROLLOUT ? rg : nullptr, dir, masked ? fm->fed : nullptr, res,
+              dir == PASS_FWD && fn && fn->sigma ? fn : nullptr};
 }
 
 // THE ONE CHECK; its order decides the code of a doubly wrong call (tests/golden/seq_plan.npy.xz).  KEPT DIFFERENCE between the
@@ -219,7 +221,7 @@ struct SeqStep {
                    // | its adjoint in the roll-out backward (tag_t = the fed step u; no problems, n = 0)
   int probe, tag_layer, tag_t;       // the NINT_PROBE_* kind and tag it is bracketed with
   int n; SeqProb prob[NINT_MULTI_MAX + 1];         // its problems, in grid order (a reduction / the fold: none, n = 0)
-  union { ConvPlan conv; MultiPlan multi; PwArgs pw; GateCall gate; WgJobPlan wg; WgFoldPlan fold; WrapTable wrap; FbPlan fb; FbBwdPlan fbb; };
+  union { ConvPlan conv; MultiPlan multi; PwArgs pw; GateCall gate; WgJobPlan wg; WgFoldPlan fold; WrapTable wrap; FbPlanNz fb; FbBwdPlan fbb; };
 };
 typedef std::vector<SeqStep> Steps;
 
@@ -308,8 +310,9 @@ static void push_gate(Steps& out, const GateCall& gc, const ConvPlan& pl, int l,
 // UNDER A MASK (m) the feedback launch goes out only at steps with a fed image, as the masked instantiation with
 // the step's word; the gates of the step are planned as in any closed-loop step.
 // RESIDUAL HEAD (res): the same launch in the same place with its base in block t-1 of xs (pass_check: t >= 1).
+// NOISE (fn): the same launch in the same place, drawing for step fn->step0 + t.
 static int plan_fwd_steps(const nint_seq* s, const nint_feedback* f, int n_cu, int t0, int t1, Steps& out, const Pass* m = nullptr,
-                          bool res = false) {
+                          bool res = false, const nint_feedback_noise* fn = nullptr) {
   const int L = s->L, T = t1 - t0;
   const bool wavefront = !f && s->wave && L > 1 && L <= NINT_MULTI_MAX;
   const bool rows8 = (s->wave == 2 || s->wave == 3 || s->wave == 4) && L > 1 && L <= NINT_MULTI_MAX;     // the 8-row rule (plan_gate)
@@ -330,6 +333,7 @@ static int plan_fwd_steps(const nint_seq* s, const nint_feedback* f, int n_cu, i
         int rc2 = NINT_OK;
         if (m) { fb.fb.mask = word; fb.fb.sel = 1; }
         if (res && (rc2 = nint_internal_feedback_base(&fb.fb, s->xs, t * s->B, (t - 1) * s->B, s->B)) != NINT_OK) return rc2;
+        if ((rc2 = nint_internal_feedback_noise(&fb.fb, fn, fn ? fn->step0 + (uint32_t)t : 0)) != NINT_OK) return rc2;     // (fn == nullptr: nz = 0, set here)
       }
       const int rc = plan_gate(s, n_cu, rows8, l, t, &gc[n], &pl[n]);
       if (rc != NINT_OK && rc != NINT_E_SHAPE) return rc;
@@ -348,7 +352,7 @@ static int plan_fwd(const Pass& p, int n_cu, Steps& out) {
   const int T = p.s->T, F = p.fed() ? p.first() : T;           // (pass_check: from >= 0)
   out.reserve((size_t)T * (p.s->L + 1));
   const int rc = plan_fwd_steps(p.s, nullptr, n_cu, 0, F, out);
-  return rc != NINT_OK || F == T ? rc : plan_fwd_steps(p.s, p.fb, n_cu, F, T, out, p.mask ? &p : nullptr, p.res);
+  return rc != NINT_OK || F == T ? rc : plan_fwd_steps(p.s, p.fb, n_cu, F, T, out, p.mask ? &p : nullptr, p.res, p.fn);
 }
 
 // default of the "lower layer's pointwise backward on the fused layer's x columns" option: on (962.2 -> 963.6 samples/s, profiles/HISTORY.md)
@@ -726,6 +730,10 @@ extern "C" int nint_seq_bwd_rollout(const nint_seq* s, const nint_feedback* fb, 
 extern "C" int nint_seq_fwd_sampled(const nint_seq* s, const nint_feedback* fb, const nint_feedback_mask* fm, void* stream) { return run_pass(pass_of(s, fb, nullptr, PASS_FWD, fm), stream); }
 extern "C" int nint_seq_bwd_rollout_sampled(const nint_seq* s, const nint_feedback* fb, const nint_feedback_mask* fm, const nint_feedback_grad* rg, void* stream) { return run_pass(pass_of(s, fb, rg, PASS_ROLLOUT, fm), stream); }
 extern "C" int nint_seq_fwd_residual(const nint_seq* s, const nint_feedback* fb, const nint_feedback_mask* fm, void* stream) { return run_pass(pass_of(s, fb, nullptr, PASS_FWD, fm, true), stream); }
+extern "C" int nint_seq_fwd_stochastic(const nint_seq* s, const nint_feedback* fb, const nint_feedback_mask* fm, int residual, const nint_feedback_noise* fn, void* stream) {
+  if (residual != 0 && residual != 1) return NINT_E_ARG;
+  return run_pass(pass_of(s, fb, nullptr, PASS_FWD, fm, residual == 1, fn), stream);
+}
 extern "C" int nint_seq_bwd_rollout_residual(const nint_seq* s, const nint_feedback* fb, const nint_feedback_mask* fm, const nint_feedback_grad* rg, void* stream) { return run_pass(pass_of(s, fb, rg, PASS_ROLLOUT, fm, true), stream); }
 
 // ------------------------------------------------------------------------------ the plan, for tests and tools

@@ -11,7 +11,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 
 from . import _lib
-from ._lib import (NINT_BF16, NINT_F32, NintFeedback, NintFeedbackGrad, NintFeedbackMask, NintGeom, NintHeadBase, NintLayer, NintLossSpec,
+from ._lib import (NINT_BF16, NINT_F32, NintFeedback, NintFeedbackGrad, NintFeedbackMask, NintFeedbackNoise, NintGeom, NintHeadBase, NintLayer, NintLossSpec,
                    NintSeq, check, ptr, stream_ptr)
 
 # 0: the library picks the gate / dgrad pixel-tile height per launch shape; 4 or 8 forces it for every layer of
@@ -71,6 +71,7 @@ class Feedback:
     def __init__(self, T: int, B: int = 1):
         self.T, self.fb, self.keep, self.grad, self.dpred, self.dx_step = T, NintFeedback(), None, False, None, None
         self.B, self.res = B, False
+        self.noise = None               # the nint_feedback_noise of the last forward pass, or None
         self.fm, self.mask, self._pin = NintFeedbackMask(), None, None
 
     @staticmethod
@@ -617,7 +618,7 @@ class SeqEngine:
     # ------------------------------------------------------------------ passes
     def forward(self, ws: Workspace, x: torch.Tensor, h0: Optional[List[torch.Tensor]] = None,
                 c0: Optional[List[torch.Tensor]] = None, feedback=None, feedback_grad: bool = False, residual=False,
-                noise: Optional[InputNoise] = None):
+                noise: Optional[InputNoise] = None, feedback_noise: Optional[InputNoise] = None):
         """x (B,T,C,H,W) f32 on the engine's device, or a dataset.SlabBatch of that shape.  Runs model.py:253-271
         (all layers, all steps).
 
@@ -636,7 +637,12 @@ class SeqEngine:
         increment, p_t = x_t[last O channels] + head(h_t) with x_t as the model saw it.  It marks the workspace: every head
         call on it (head_forward[_seq], the fused head / loss passes, the skill pass) then adds that base, and with
         ``feedback`` the fed value is round_ET(p_{t-1}) of that p (the _residual entries).  A fed image at step 0 is refused:
-        p_{-1} has no base, even with a state."""
+        p_{-1} has no base, even with a state.
+
+        ``feedback_noise`` (with ``feedback``, forward only): an InputNoise whose ``std`` is one float or O floats
+        -- every fed step stores round_ET(p + std[o] * z), z the input noise's normal of (pixel, o, step0 + t, lane0 + b).  It is
+        one more field of the same feedback launches (nint_seq_fwd_stochastic).  None, all zeros or nothing fed: the entries and
+        bits of the pass without it."""
         B, T, Cc, H, W = x.shape
         assert (B, T, H, W) == (ws.B, ws.T, ws.H, ws.W) and Cc == self.cfgs[0].Cx
         s = ws.seq
@@ -644,6 +650,7 @@ class SeqEngine:
         if res_O and (not 1 <= res_O <= Cc or self._beyond_fused_head(self.layers[-1].Chp, res_O)):
             raise _lib.NintError(f"residual head: {res_O} outputs on {self.layers[-1].Chp} padded channels over {Cc} input channels is "
                                  "beyond the staged head kernels, which alone add the base (NINT_E_SHAPE), or has no feedback channels")
+        ws.feedback.noise = None
         ws.feedback.set(res=bool(res_O))       # (stays as this pass sets it: a backward pass on a fed window is refused unless marked)
         if feedback is not None:
             w, b, from_step = feedback
@@ -668,6 +675,15 @@ class SeqEngine:
                 raise _lib.NintError(f"feedback: a head of {O} outputs on {self.layers[-1].Chp} padded channels is beyond the "
                                      "staged head kernels (nint_head_feedback: NINT_E_SHAPE)")
             ws.feedback.set(w2, b2, O, from_step, bool(feedback_grad), mask, bool(res_O))
+        if feedback_noise is not None and feedback_noise.active and feedback is not None:      # (nothing fed back: nothing to put it on)
+            if feedback_grad or feedback_noise.channels is not None:
+                raise ValueError("feedback_noise: the noise goes onto the fed-back value of a forward-only closed loop -- it is refused "
+                                 "together with feedback_grad=True, and its channels must be None (the feedback channels)")
+            _, _, sig = feedback_noise.span(ws.feedback.fb.O, ws.feedback.fb.O)
+            fn = NintFeedbackNoise()
+            fn.sigma = self._sigma_tensor(sig).data_ptr()
+            fn.seed, fn.draw, fn.step0, fn.lane0 = feedback_noise.seed, feedback_noise.draw, feedback_noise.step0, feedback_noise.lane0
+            ws.feedback.noise = fn
         self.pack_input(ws, x)
         if noise is not None and noise.active:
             self.input_noise(ws, noise, ws.feedback.fb.O or res_O or None)
@@ -681,12 +697,17 @@ class SeqEngine:
         the pass reads it.  The n sigmas live on the device, one small tensor per distinct value tuple for the engine's life."""
         cfg = self.cfgs[0]
         c0, n, sig = noise.span(cfg.Cx, feedback_O)
-        sd = self._noise_sigma.get(sig)
-        if sd is None:
-            sd = self._noise_sigma[sig] = torch.tensor(sig, dtype=torch.float32, device=self.device)
+        sd = self._sigma_tensor(sig)
         check(self.lib.nint_input_noise(ptr(ws.xs), 0, ws.B, ws.T, cfg.Cx, ws.Cxp0, c0, n, ptr(sd), cfg.k if cfg.xfold else 0,
                                         int(self.lon_cyclic), noise.seed, noise.draw, noise.step0, noise.lane0, C.byref(ws.g),
                                         self.dt, stream_ptr()), "nint_input_noise")
+
+    def _sigma_tensor(self, sig: Tuple[float, ...]) -> torch.Tensor:
+        """the sigmas of a noise launch on the device: one small tensor per distinct value tuple for the engine's life"""
+        sd = self._noise_sigma.get(sig)
+        if sd is None:
+            sd = self._noise_sigma[sig] = torch.tensor(sig, dtype=torch.float32, device=self.device)
+        return sd
 
     def _seq_pass(self, ws: Workspace, bwd: bool, rg: Optional[NintFeedbackGrad] = None):
         """Choose and call the C entry of a whole-sequence pass: forward | backward, each open or (the last forward pass ran with
@@ -695,7 +716,9 @@ class SeqEngine:
         the seven."""
         s, fb, fm = ws.seq, ws.feedback.fb, ws.feedback.fm
         masked = ws.feedback.mask is not None and fb.O > 0
-        if ws.feedback.res and fb.O > 0 and (rg is not None or not bwd):    # residual head (4.22): the _sampled entries' twins
+        if ws.feedback.noise is not None and fb.O > 0 and not bwd:          # noise on the fed-back value (4.24): one entry, forward only
+            name, extra = "nint_seq_fwd_stochastic", (C.byref(fb), C.byref(fm), int(ws.feedback.res), C.byref(ws.feedback.noise))
+        elif ws.feedback.res and fb.O > 0 and (rg is not None or not bwd):    # residual head (4.22): the _sampled entries' twins
             name = "nint_seq_bwd_rollout_residual" if rg is not None else "nint_seq_fwd_residual"
             extra = (C.byref(fb), C.byref(fm)) + ((C.byref(rg),) if rg is not None else ())
         elif rg is not None and masked:
@@ -709,7 +732,7 @@ class SeqEngine:
         else:
             name, extra = ("nint_seq_bwd" if bwd else "nint_seq_fwd"), ()
         what = name + (" (the backward pass of a window in which the prediction was fed back is not defined)" if bwd and extra and rg is None else "")
-        # (seven names, and the residual head's two)
+        # (seven names, the residual head's two and the stochastic forward)
         check(getattr(self.lib, name)(C.byref(s), *extra, stream_ptr()), what)
 
     def _set_wave(self, ws: Workspace):

@@ -13,7 +13,7 @@ from typing import Callable, Optional, Sequence, Tuple, Union
 import numpy as np
 import torch
 
-from ._lib import NINT_SKILL_PIX, NINT_SKILL_SAMPLE
+from ._lib import NINT_ENS_MAX_M, NINT_ENS_PIX, NINT_ENS_SAMPLE, NINT_SKILL_PIX, NINT_SKILL_SAMPLE
 
 
 @torch.no_grad()
@@ -438,3 +438,262 @@ def lead_time_r2(acc: SkillAccumulator) -> np.ndarray:
         if n > 0:
             out[j] = float(_r2(pix[j, 4].sum(), _centred(pix[j, 2].sum(), pix[j, 0].sum(), n)))
     return out
+
+
+# ------------------------------------------------------------------------------ ensemble statistics from device-side sums
+@dataclass
+class EnsembleReport:
+    """Ensemble verification from the sums of nint_ens_accum, in z-score units; the `_phys` fields are the
+    same figures times `scale` (y_std), where a scale applies -- ratios, R2 and the histogram have none.  Scalars pool every
+    sample, output and grid cell of the chosen slots; maps are (O, Hc, Wc); the cos-latitude means are one row per sample
+    of those slots, (n, O), in the order the samples were folded in."""
+    rmse_mean: float                     # sqrt(mean (ensemble mean - y)^2)
+    spread: float                        # sqrt(mean unbiased member variance)
+    spread_skill: float                  # sqrt((M+1)/M) * spread / rmse_mean: 1 for a reliable ensemble
+    crps_fair: float                     # mean over cells of A / M - D / (M (M - 1)): the fair CRPS (unbiased in the ensemble size)
+    crps: float                          # the plain form: A/M - D/M^2
+    bias: float                          # mean (ensemble mean - y)
+    r2_mean: float                       # R2 of the ensemble mean
+    rmse_mean_map: np.ndarray
+    spread_map: np.ndarray
+    spread_skill_map: np.ndarray
+    crps_fair_map: np.ndarray
+    coslat_mse_mean: np.ndarray          # row-weighted (cos latitude) means over the grid, per sample and output
+    coslat_variance: np.ndarray
+    coslat_crps_fair: np.ndarray
+    coslat_crps: np.ndarray
+    rank_hist: np.ndarray                # (O, M + 2) int64: bins 0..M the target's rank, bin M + 1 the NaN cells
+    rmse_mean_phys: float
+    spread_phys: float
+    crps_fair_phys: float
+    crps_phys: float
+    bias_phys: float
+    members: int
+    count: float                         # samples behind the maps
+    scale: float
+
+    def arrays(self) -> dict:
+        return {f.name: np.asarray(getattr(self, f.name)) for f in fields(self)}
+
+
+def ensemble_from_sums(pix, counts, sample, rank_hist, M: int, row_w=None, y_mean: float = 0.0, y_std: float = 1.0,
+                       slots: Optional[Sequence[int]] = None, sample_slots: Optional[Sequence[int]] = None) -> EnsembleReport:
+    """The sums of nint_ens_accum -> an EnsembleReport.  Pure numpy f64; needs no GPU.
+
+    pix (nslots, 7, O, Hc, Wc): per slot and cell sum E^2, sum V, sum A, sum D, sum E, sum t, sum t^2, where per sample
+    S = sum_i x_i, E = S - M t, V = sum_i (M x_i - S)^2, A = sum_i |x_i - t|, D = sum_{i<j} |x_i - x_j|; counts (nslots):
+    samples per slot; sample (N, O, 8): sum E^2, V, A, D over the grid, then the same weighted by row_w (Hc; None: 1);
+    rank_hist (nslots, O, M + 2).  Every division the kernel left out happens here, over n values:
+      MSE of the ensemble mean = sum E^2 / M^2 / n          mean variance = sum V / (M^2 (M - 1)) / n   (1/(M-1) sum (x_i - mean)^2)
+      fair CRPS = (sum A / M - sum D / (M (M - 1))) / n     plain CRPS    = (sum A / M - sum D / M^2) / n
+      bias = sum E / M / n                                  R2 = 1 - (sum E^2 / M^2) / (sum t^2 - (sum t)^2 / n)
+    `slots`: the union of slots behind the maps and scalars (None: all); `sample_slots` (N): the slot of each sample row,
+    which restricts the cos-latitude rows to that union (None: every row).  y_mean shifts no figure reported here."""
+    pix, counts, sample = np.asarray(pix, np.float64), np.asarray(counts, np.float64), np.asarray(sample, np.float64)
+    rank_hist = np.asarray(rank_hist, np.int64)
+    M = int(M)
+    nslots, npl, O, Hc, Wc = pix.shape
+    if not 2 <= M <= NINT_ENS_MAX_M:
+        raise ValueError(f"ensemble_from_sums: members must lie in [2, {NINT_ENS_MAX_M}], got {M}")
+    assert npl == NINT_ENS_PIX and counts.shape == (nslots,) and sample.shape[1:] == (O, NINT_ENS_SAMPLE)
+    assert rank_hist.shape == (nslots, O, M + 2)
+    sel = list(range(nslots)) if slots is None else [int(v) for v in slots]
+    see, sv, sa, sd, se, st, stt = pix[sel].sum(axis=0)
+    n = float(counts[sel].sum())
+    m2, m2m1, mm1 = float(M * M), float(M * M * (M - 1)), float(M * (M - 1))
+    kappa = np.sqrt((M + 1.0) / M)
+    sig = float(y_std)
+
+    def figures(see, sv, sa, sd, cnt):
+        """(rmse, spread, ratio, fair CRPS, plain CRPS) of sums over cnt values; arrays or scalars"""
+        with np.errstate(divide="ignore", invalid="ignore"):
+            inv = 1.0 / cnt if cnt > 0 else np.nan
+            rmse, spread = np.sqrt(see / m2 * inv), np.sqrt(sv / m2m1 * inv)
+            return rmse, spread, kappa * spread / rmse, (sa / M - sd / mm1) * inv, (sa / M - sd / m2) * inv
+
+    rmse_map, spread_map, ratio_map, fair_map, _ = figures(see, sv, sa, sd, n)
+    ncell = n * O * Hc * Wc
+    rmse, spread, ratio, fair, plain = (float(v) for v in figures(see.sum(), sv.sum(), sa.sum(), sd.sum(), ncell))
+    bias = float(se.sum() / M / ncell) if ncell > 0 else float("nan")
+    r2 = float(_r2(see.sum() / m2, _centred(stt.sum(), st.sum(), ncell))) if ncell > 0 else float("nan")
+    rows = sample if sample_slots is None else sample[[i for i, s in enumerate(sample_slots) if int(s) in sel]]
+    wsum = Wc * (float(Hc) if row_w is None else float(np.asarray(row_w, dtype=np.float64).sum()))
+    return EnsembleReport(
+        rmse_mean=rmse, spread=spread, spread_skill=ratio, crps_fair=fair, crps=plain, bias=bias, r2_mean=r2,
+        rmse_mean_map=rmse_map, spread_map=spread_map, spread_skill_map=ratio_map, crps_fair_map=fair_map,
+        coslat_mse_mean=rows[..., 4] / m2 / wsum, coslat_variance=rows[..., 5] / m2m1 / wsum,
+        coslat_crps_fair=(rows[..., 6] / M - rows[..., 7] / mm1) / wsum, coslat_crps=(rows[..., 6] / M - rows[..., 7] / m2) / wsum,
+        rank_hist=rank_hist[sel].sum(axis=0), rmse_mean_phys=sig * rmse, spread_phys=sig * spread, crps_fair_phys=sig * fair,
+        crps_phys=sig * plain, bias_phys=sig * bias, members=M, count=n, scale=sig)
+
+
+class EnsembleAccumulator:
+    """Device-side accumulators of one ensemble evaluation (nint_ens_accum): `pix` (nslots, 7, O, Hc, Wc) f64, `rank_hist`
+    (nslots, O, M + 2) int64, the per-sample sums of every batch seen (a growing (n_samples, O, 8) table) and the kernel's
+    scratch.  `lat`, `halo`: as SkillAccumulator's.  The sums are additive: a data-parallel reduction adds the ranks' `pix`,
+    `rank_hist` and `counts`."""
+
+    def __init__(self, O: int, Hc: int, Wc: int, M: int, nslots: int = 1, lat=None, device="cuda", halo: Optional[Tuple[int, int]] = None):
+        from . import _lib
+        self.O, self.Hc, self.Wc, self.M, self.nslots = int(O), int(Hc), int(Wc), int(M), int(nslots)
+        if self.nslots < 1:
+            raise ValueError("nslots must be >= 1")
+        if not 2 <= self.M <= NINT_ENS_MAX_M:
+            raise ValueError(f"EnsembleAccumulator: members must lie in [2, {NINT_ENS_MAX_M}], got {self.M}")
+        self.lib = _lib.load()
+        self.device = torch.device(device)
+        self.halo = None if halo is None else (int(halo[0]), int(halo[1]))
+        self.row_w_host = None
+        self.row_w = None
+        if lat is not None:
+            lat = np.asarray(lat, dtype=np.float64)
+            if lat.shape != (self.Hc,):
+                raise ValueError(f"lat: expected {self.Hc} latitudes, got {lat.shape}")
+            self.row_w_host = np.cos(np.deg2rad(lat))
+            self.row_w = torch.from_numpy(self.row_w_host).to(self.device)
+        self.pix = torch.zeros(self.nslots, NINT_ENS_PIX, self.O, self.Hc, self.Wc, dtype=torch.float64, device=self.device)
+        self.rank_hist = torch.zeros(self.nslots, self.O, self.M + 2, dtype=torch.int64, device=self.device)
+        self._counts = np.zeros(self.nslots, dtype=np.float64)
+        self._rows, self._row_slots = [], []
+        self._scratch = None
+
+    @property
+    def counts(self) -> torch.Tensor:
+        return torch.from_numpy(self._counts.copy()).to(self.device)
+
+    @property
+    def n_samples(self) -> int:
+        return len(self._row_slots)
+
+    def scratch_for(self, N: int) -> torch.Tensor:
+        need = self.lib.nint_ens_scratch_bytes(int(N), self.M, self.O, self.Hc, self.Wc) // 8
+        if self._scratch is None or self._scratch.numel() < need:
+            self._scratch = torch.empty(need, dtype=torch.float64, device=self.device)
+        return self._scratch
+
+    def update(self, pred: torch.Tensor, sample_off: Sequence[int], member_stride: int, y: torch.Tensor, slots=None,
+               mean_out: Optional[torch.Tensor] = None):
+        """Fold one batch in.  `pred`: a contiguous f32 device tensor whose last three dimensions are (O, H, W); member i of
+        sample n is the image at element sample_off[n] + i * member_stride of it, read in place.  `y` (N, O, Hc, Wc) f32."""
+        from ._lib import check, ptr, stream_ptr
+        if pred.dtype != torch.float32 or not pred.is_contiguous() or pred.dim() < 3 or pred.shape[-3] != self.O:
+            raise ValueError(f"EnsembleAccumulator.update: pred must be a contiguous f32 tensor (..., {self.O}, H, W)")
+        H, W = int(pred.shape[-2]), int(pred.shape[-1])
+        off = [int(v) for v in sample_off]
+        N, stride = len(off), int(member_stride)
+        if N < 1 or stride < 0 or min(off) < 0 or max(off) + (self.M - 1) * stride + self.O * H * W > pred.numel():
+            raise ValueError("EnsembleAccumulator.update: a member image lies outside pred")
+        oy, ox = ((H - self.Hc) // 2, (W - self.Wc) // 2) if self.halo is None else self.halo
+        yv = y.detach().float().contiguous()
+        if yv.numel() != N * self.O * self.Hc * self.Wc:
+            raise ValueError("EnsembleAccumulator.update: target must be (N, O, Hc, Wc)")
+        sl = [0] * N if slots is None else [int(v) for v in slots]
+        if len(sl) != N or any(v < -1 or v >= self.nslots for v in sl):
+            raise ValueError(f"slots: {N} values in [-1, {self.nslots}) expected")
+        if mean_out is not None and (mean_out.dtype != torch.float32 or not mean_out.is_contiguous()
+                                     or mean_out.numel() != yv.numel()):
+            raise ValueError("EnsembleAccumulator.update: mean_out must be a contiguous f32 (N, O, Hc, Wc)")
+        sample = torch.empty(N, self.O, NINT_ENS_SAMPLE, dtype=torch.float64, device=self.device)
+        scratch = self.scratch_for(N)
+        check(self.lib.nint_ens_accum(ptr(pred), (C.c_int64 * N)(*off), stride, self.M, ptr(yv), (C.c_int32 * N)(*sl), self.nslots,
+                                      ptr(self.row_w), ptr(self.pix), ptr(sample), ptr(self.rank_hist), ptr(mean_out), ptr(scratch),
+                                      scratch.numel() * 8, N, self.O, H, W, int(oy), int(ox), self.Hc, self.Wc, stream_ptr()),
+              "nint_ens_accum")
+        self._rows.append(sample)
+        self._row_slots += sl
+        for v in sl:
+            if v >= 0:
+                self._counts[v] += 1.0
+
+    def sums(self):
+        """(pix, counts, sample, rank_hist) as numpy: ONE device-to-host read (the int64 counts travel as their bits)"""
+        rows = torch.cat(self._rows) if self._rows else torch.empty(0, self.O, NINT_ENS_SAMPLE, dtype=torch.float64, device=self.device)
+        flat = torch.cat([self.pix.reshape(-1), rows.reshape(-1), self.rank_hist.reshape(-1).view(torch.float64)]).cpu().numpy()
+        a, b = self.pix.numel(), self.pix.numel() + rows.numel()
+        return (flat[:a].reshape(tuple(self.pix.shape)), self._counts.copy(), flat[a:b].reshape(-1, self.O, NINT_ENS_SAMPLE),
+                flat[b:].view(np.int64).reshape(tuple(self.rank_hist.shape)).copy())
+
+    def report(self, y_mean: float = 0.0, y_std: float = 1.0, slots: Optional[Sequence[int]] = None) -> EnsembleReport:
+        pix, counts, sample, hist = self.sums()
+        return ensemble_from_sums(pix, counts, sample, hist, self.M, self.row_w_host, y_mean, y_std, slots, self._row_slots)
+
+
+LEAD_TIME_COLUMNS = ("rmse_mean", "spread", "spread_skill", "crps_fair", "crps", "bias", "r2_mean")
+
+
+def lead_time_table(acc: EnsembleAccumulator) -> np.ndarray:
+    """The scalars of EnsembleReport per slot of an accumulator (rollout_ensemble: per lead time), z-score units:
+    (nslots, 7) in the order of LEAD_TIME_COLUMNS; nan for an empty slot.  One device-to-host read."""
+    pix, counts, sample, hist = acc.sums()
+    out = np.full((acc.nslots, len(LEAD_TIME_COLUMNS)), np.nan)
+    for j in range(acc.nslots):
+        if counts[j] > 0:
+            rep = ensemble_from_sums(pix, counts, sample, hist, acc.M, acc.row_w_host, slots=[j], sample_slots=acc._row_slots)
+            out[j] = [getattr(rep, k) for k in LEAD_TIME_COLUMNS]
+    return out
+
+
+# ------------------------------------------------------------------------------ ensemble roll-outs by lead time
+@torch.no_grad()
+def rollout_ensemble(net, dataset, starts: Sequence[int], horizon: int, spinup: int, members: int, ic_noise=0.05,
+                     feedback_noise=0.0, seed: int = 0, batch_size: int = 8, lat=None, halo: Optional[Tuple[int, int]] = None,
+                     _allow_no_noise: bool = False) -> EnsembleAccumulator:
+    """Ensemble verification of the free-running model by LEAD TIME.  From every record step in `starts`,
+    `members` copies of the window of `spinup + horizon` steps run closed loop from step `spinup` as lanes of one batch --
+    lane start_index * members + m -- and differ by their noise alone:
+      * `ic_noise` (std, z-score units): the input noise on the tracer channels with draw = 0.  The fed steps
+        overwrite it, so it perturbs the spin-up -- the members' initial condition -- only;
+      * `feedback_noise`: noise on every fed-back value (``net(..., feedback_noise=)``) with draw = 1.
+    Both use `seed` and lane0 = start_index * members with the GLOBAL start index, so the noise of (start, member) does not
+    depend on `batch_size`; a batch holds max(1, batch_size // members) starts.  The head runs at every step
+    (head_forward_seq), the targets come from the record, and the statistics kernel (nint_ens_accum) reads the members where
+    they lie; the prediction made `j` steps into the free run goes to slot j of the returned EnsembleAccumulator:
+    ``lead_time_table(acc)``, ``acc.report(dataset.y_mean, dataset.y_std, slots=[j])``.
+
+    Refused: what rollout_skill refuses, `members` outside [2, 64], a negative or non-finite std, and both noises zero --
+    the members would be identical and the ensemble would have no spread."""
+    from .dataset import SlabBatch
+    from .engine import InputNoise
+    if not getattr(net, "feedback", False):
+        raise ValueError("rollout_ensemble needs a ConvLSTM built with feedback=True")
+    horizon, spinup = int(horizon), int(spinup)
+    if horizon < 1 or spinup < 1:
+        raise ValueError(f"rollout_ensemble: horizon and spinup must be >= 1, got {(horizon, spinup)}")
+    if isinstance(members, bool) or int(members) != members or not 2 <= members <= NINT_ENS_MAX_M:
+        raise ValueError(f"rollout_ensemble: members must be an integer in [2, {NINT_ENS_MAX_M}], got {members!r}")
+    M, T = int(members), spinup + horizon
+    starts = [int(v) for v in starts]
+    n_steps = int(dataset.yraw.shape[0])
+    lo = 1 if getattr(dataset, "tracer_input", False) else 0
+    if not starts or min(starts) < lo or max(starts) + T > n_steps:
+        raise ValueError(f"rollout_ensemble: every start must lie in [{lo}, {n_steps - T}] for windows of {T} steps in a record of {n_steps}")
+    ic, fbn = InputNoise(ic_noise, seed=seed, draw=0), InputNoise(feedback_noise, seed=seed, draw=1)      # (a bad std or seed: ValueError)
+    if not (ic.active or fbn.active or _allow_no_noise):
+        raise ValueError("rollout_ensemble: ic_noise and feedback_noise are both zero -- the members would be identical and the "
+                         "ensemble would have no spread; give at least one a positive std")
+    O = net.conv.weight.shape[0]
+    if O != dataset.levels:
+        raise ValueError(f"rollout_ensemble: the head has {O} outputs, the record's tracer {dataset.levels} levels")
+    net.eval()
+    dev = next(net.parameters()).device
+    eng = net._engine(dev)
+    Hc, Wc = dataset.grid
+    acc = EnsembleAccumulator(O, Hc, Wc, M, nslots=horizon, lat=lat, device=dev, halo=halo)
+    dv = dataset._device_arrays()
+    per = max(1, int(batch_size) // M)
+    for s in range(0, len(starts), per):
+        t0s = starts[s:s + per]
+        X = SlabBatch(dataset, np.asarray([t for t in t0s for _ in range(M)]), T)
+        B, _, _, H, W = X.shape
+        lane = dict(seed=ic.seed, lane0=s * M)
+        with eng.window(B, T, H, W, False, False) as ws:
+            net._pack_weights(eng)
+            eng.forward(ws, X, feedback=(net.conv.weight, net.conv.bias, spinup), residual=_residual(net),
+                        noise=InputNoise(ic.std, draw=0, **lane), feedback_noise=InputNoise(fbn.std, draw=1, **lane))
+            seq = eng.head_forward_seq(ws, net.conv.weight, net.conv.bias).view(B, T, O, H, W)
+        y = _step_targets(dataset, dv, t0s, T)                                    # (starts, T, L, Hc, Wc)
+        img = O * H * W
+        off = [((i * M) * T + spinup + j) * img for i in range(len(t0s)) for j in range(horizon)]
+        acc.update(seq, off, T * img, y[:, spinup:].reshape(len(t0s) * horizon, O, Hc, Wc),
+                   [j for _ in t0s for j in range(horizon)])
+    return acc

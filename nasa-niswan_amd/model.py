@@ -122,9 +122,10 @@ class _CallOpts:
     device state is handed back in (a Function's outputs are tensors), and the default route's head-backward rule"""
 
     def __init__(self, state_in=None, return_state=False, seq_always=False, free_from=None, feedback_grad=False, residual=False,
-                 noise=None):
+                 noise=None, fnoise=None):
         self.state_in, self.return_state, self.state_out = state_in, return_state, None
         self.noise = noise              # an InputNoise with its span resolved, or None (DESIGN.md 4.23)
+        self.fnoise = fnoise            # the noise on the fed-back value: an InputNoise with O sigmas, or None (DESIGN.md 4.24)
         self.free_from = free_from      # closed loop from this step on (ConvLSTM(feedback=True)); None: open loop
         self.residual = residual        # the module's head predicts the increment (ConvLSTM(residual=True), DESIGN.md 4.22)
         # ... or a (B, T) feed mask (scheduled sampling, DESIGN.md 4.21); `first`: the first step that feeds anything
@@ -168,7 +169,8 @@ class _ConvLSTMFn(torch.autograd.Function):
             eng.load_state(ws, opts.state_in)
         h0, c0 = (list(st[0::2]), list(st[1::2])) if st else (None, None)
         eng.forward(ws, x, h0, c0, feedback=None if opts.free_from is None else (head_w, head_b, opts.free_from),
-                    feedback_grad=rollout, residual=head_w.shape[0] if opts.residual else False, noise=opts.noise)
+                    feedback_grad=rollout, residual=head_w.shape[0] if opts.residual else False, noise=opts.noise,
+                    feedback_noise=opts.fnoise)
         outs = [eng.head_forward(ws, head_w, head_b)]
         if module.return_sequence:
             outs.append(eng.head_forward_seq(ws, head_w, head_b))       # every step in one launch
@@ -369,7 +371,8 @@ class ConvLSTM(_EngineOwner, nn.Module):
         inference loops, which drive the engine themselves, do before a forward pass"""
         eng.pack_weights([c.conv.weight for c in self.layers], [c.conv.bias for c in self.layers])
 
-    def forward(self, x, state=None, *, return_state=False, free_from=None, feedback_grad=False, free_mask=None, input_noise=None):
+    def forward(self, x, state=None, *, return_state=False, free_from=None, feedback_grad=False, free_mask=None, input_noise=None,
+                feedback_noise=None):
         """x: (batch_size, sequence_length, channels, height, width)  (model.py:254).
 
         ``state``: None (zeros, model.py:259-262), a list of ``num_layers`` ``(h, c)`` tensor pairs (B, Ch_l, H, W) -- the
@@ -412,8 +415,15 @@ class ConvLSTM(_EngineOwner, nn.Module):
         rounded to the storage type.  The noise is a constant: the gradient of ``x`` is what it was, the rounding taken
         straight-through.  Everything above composes with it: a fed step overwrites its fed channels afterwards, an unfed
         step of a ``residual=True`` module takes the NOISY stored value as its base.  None, or an all-zero ``std``: no launch,
-        the bits of the call without it."""
+        the bits of the call without it.
+
+        ``feedback_noise = InputNoise(std, seed=, draw=, step0=, lane0=)`` (``channels`` must be None: the
+        feedback channels): the value every fed step stores becomes round(p + std[o] * z), z the normal of ``input_noise``'s
+        rule for (pixel, output o, step0 + t, lane0 + b) -- an ensemble member's perturbation of the free run.  ``std``: one
+        float or out_channels floats.  Forward only: refused together with ``feedback_grad=True``, and on a module without
+        ``feedback=True``.  None, an all-zero ``std`` or a call that feeds nothing: the launches and bits of the call without it."""
         noise = self._check_noise(x, input_noise)
+        fnoise = self._check_feedback_noise(feedback_noise, feedback_grad)
         if free_mask is not None:                       # the refusals of free_from, by the first column with a fed image
             if free_from is not None:
                 raise ValueError("free_mask and free_from are exclusive: the mask says for every step what free_from says for all")
@@ -433,7 +443,7 @@ class ConvLSTM(_EngineOwner, nn.Module):
                 raise ValueError(f"free_mask: a feed mask holds at most 64 images per call, got B = {x.shape[0]}")
             free_from = mask if first < x.shape[1] else None         # (nothing fed: the open loop, the call it always was)
             feedback_grad = feedback_grad and free_from is not None
-            return self._forward(x, state, return_state, free_from, feedback_grad, noise)
+            return self._forward(x, state, return_state, free_from, feedback_grad, noise, fnoise if free_from is not None else None)
         if free_from is not None:                       # every refusal here, before anything is launched (or any device is asked for)
             if not self.feedback:
                 raise ValueError("free_from needs a ConvLSTM built with feedback=True")
@@ -448,7 +458,27 @@ class ConvLSTM(_EngineOwner, nn.Module):
                 raise ValueError("free_from=0 feeds step 0 from the head of the initial state: pass a state")
             if free_from < x.shape[1] and not (feedback_grad and free_from >= 1) and self._wants_grad(x, state):
                 raise RuntimeError(_NO_FEEDBACK_GRAD)
-        return self._forward(x, state, return_state, free_from, feedback_grad, noise)
+        # (a call that feeds nothing has no value to put the noise on: the call without the argument)
+        return self._forward(x, state, return_state, free_from, feedback_grad, noise, fnoise if free_from is not None else None)
+
+    def _check_feedback_noise(self, feedback_noise, feedback_grad):
+        """the refusals of ``feedback_noise``, before anything is launched; an InputNoise with out_channels sigmas, or None"""
+        if feedback_noise is None:
+            return None
+        if not isinstance(feedback_noise, InputNoise):
+            raise ValueError(f"feedback_noise must be an InputNoise or None, got {type(feedback_noise).__name__}")
+        if not self.feedback:
+            raise ValueError("feedback_noise needs a ConvLSTM built with feedback=True")
+        if feedback_noise.channels is not None:
+            raise ValueError("feedback_noise: channels must be None -- the noise goes onto the fed-back value, the feedback channels")
+        if feedback_grad:
+            raise ValueError("feedback_noise is forward only: it is refused together with feedback_grad=True (roll-out training "
+                             "through the stochastic feedback is not built)")
+        O = self.conv.out_channels
+        _, _, sig = feedback_noise.span(O, O)                      # one std for all, or one per output
+        if not feedback_noise.active:
+            return None
+        return InputNoise(sig, None, feedback_noise.seed, feedback_noise.draw, feedback_noise.step0, feedback_noise.lane0)
 
     def _check_noise(self, x, input_noise):
         """the refusals of ``input_noise``, before anything is launched; the InputNoise the engine takes (span resolved), or None"""
@@ -469,7 +499,7 @@ class ConvLSTM(_EngineOwner, nn.Module):
             x.requires_grad or any(p.requires_grad for p in self.parameters())
             or (state is not None and not isinstance(state, ConvLSTMState) and any(t.requires_grad for pair in state for t in pair)))
 
-    def _forward(self, x, state, return_state, free_from, feedback_grad, noise=None):
+    def _forward(self, x, state, return_state, free_from, feedback_grad, noise=None, fnoise=None):
         """forward() behind its refusals; ``free_from``: None, a step index or a (B, T) uint8 feed mask; ``noise``: None or an
         InputNoise with its span resolved"""
         _require_cuda(x, "ConvLSTM")
@@ -479,7 +509,7 @@ class ConvLSTM(_EngineOwner, nn.Module):
         st = []
         if state is None and not return_state:          # the default call: nothing to validate, and its own head-backward rule
             opts = _CallOpts(seq_always=self.return_sequence, free_from=free_from, feedback_grad=bool(feedback_grad),
-                             residual=self.residual, noise=noise)
+                             residual=self.residual, noise=noise, fnoise=fnoise)
         else:
             if return_state not in (False, True, "device"):
                 raise ValueError(f"return_state must be False, True or 'device', got {return_state!r}")
@@ -493,7 +523,7 @@ class ConvLSTM(_EngineOwner, nn.Module):
                 hs, cs = eng._state_tensors(state, (B, H, W))
                 st = _interleave(hs, cs)
             opts = _CallOpts(state if isinstance(state, ConvLSTMState) else None, return_state, free_from=free_from,
-                             feedback_grad=bool(feedback_grad), residual=self.residual, noise=noise)
+                             feedback_grad=bool(feedback_grad), residual=self.residual, noise=noise, fnoise=fnoise)
         out = _ConvLSTMFn.apply(self, torch.is_grad_enabled(), opts, x, self.conv.weight, self.conv.bias, *wb, *st)
         out = list(out) if isinstance(out, tuple) else [out]
         n0 = 2 if self.return_sequence else 1

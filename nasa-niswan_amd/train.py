@@ -138,6 +138,16 @@ def get_arguments(argv=None, MODEL='LSTM-00', SPECIES='bcb', LEARNING_RATE=1.0E-
     parser.add_argument("--test-rollout", type=int, default=0, metavar="HORIZON",
                         help="with --tracer-input: after the test pass rank 0 runs the model closed loop over the 'test' period "
                              "(inference.rollout_skill) and prints R2 per lead time 0 .. HORIZON-1")
+    parser.add_argument("--ensemble-members", type=int, default=None, metavar="M",
+                        help="with --test-rollout: also run every roll-out window as an ensemble of M members in [2, 64] "
+                             "(inference.rollout_ensemble) and print RMSE of the ensemble mean, spread, their ratio, CRPS, bias "
+                             "and R2 per lead time")
+    parser.add_argument("--ensemble-noise", type=float, default=None, metavar="S",
+                        help="with --ensemble-members: std of the members' initial-condition noise on the tracer channels of the "
+                             "spin-up, z-score units (default 0.05)")
+    parser.add_argument("--ensemble-feedback-noise", type=float, default=None, metavar="S",
+                        help="with --ensemble-members: std of the noise added to every fed-back value (default 0)")
+    parser.add_argument("--ensemble-seed", type=int, default=None, metavar="K", help="with --ensemble-members: the noise seed (default 0)")
     parser.add_argument("--rollout-spinup", type=int, default=None, metavar="K",
                         help="steps of analysis input before the free run of --test-rollout (default: --sequence-length)")
     parser.add_argument("--rollout-from", type=int, default=None, metavar="K",
@@ -213,6 +223,26 @@ def get_arguments(argv=None, MODEL='LSTM-00', SPECIES='bcb', LEARNING_RATE=1.0E-
         parser.error("--sampling-ramp-epochs takes a number of epochs >= 0 and needs --sampling-prob")
     if args.rollout_spinup is None:
         args.rollout_spinup = args.sequence_length
+    ens = {"--ensemble-members": args.ensemble_members, "--ensemble-noise": args.ensemble_noise,
+           "--ensemble-feedback-noise": args.ensemble_feedback_noise, "--ensemble-seed": args.ensemble_seed}
+    given = [k for k, v in ens.items() if v is not None]
+    if given and not args.test_rollout:
+        parser.error(f"{given[0]} needs --test-rollout: the ensemble runs the roll-out's windows")
+    if given and args.ensemble_members is None:
+        parser.error(f"{given[0]} needs --ensemble-members")
+    if args.ensemble_members is not None:
+        if not 2 <= args.ensemble_members <= 64:
+            parser.error("--ensemble-members must be in [2, 64]")
+        args.ensemble_noise = 0.05 if args.ensemble_noise is None else args.ensemble_noise
+        args.ensemble_feedback_noise = 0.0 if args.ensemble_feedback_noise is None else args.ensemble_feedback_noise
+        args.ensemble_seed = 0 if args.ensemble_seed is None else args.ensemble_seed
+        for name, v in (("--ensemble-noise", args.ensemble_noise), ("--ensemble-feedback-noise", args.ensemble_feedback_noise)):
+            if not 0.0 <= v < float("inf"):
+                parser.error(f"{name} must be a finite standard deviation >= 0")
+        if args.ensemble_noise == 0.0 and args.ensemble_feedback_noise == 0.0:
+            parser.error("--ensemble-noise and --ensemble-feedback-noise are both 0: the ensemble would have no spread")
+        if args.ensemble_seed < 0:
+            parser.error("--ensemble-seed must be >= 0")
     if args.test_rollout > 0 and args.rollout_spinup < 1:
         parser.error("--rollout-spinup must be >= 1")
     if args.spinup_steps < 0:
@@ -420,6 +450,19 @@ def main(args):
             np.save(os.path.join(args.snapshot_dir, "rollout_r2.npy"), np.array(r2_lead))
             print(f"Closed-loop roll-out, {len(starts)} windows, spin-up {args.rollout_spinup}: R2 per lead time")
             print("  " + " ".join(f"{j}:{v:.4f}" for j, v in enumerate(r2_lead)))
+            if args.ensemble_members:
+                from nasa_niswan_amd.inference import LEAD_TIME_COLUMNS, lead_time_table, rollout_ensemble
+                ens = rollout_ensemble(generator, test_dataset, starts, args.test_rollout, args.rollout_spinup, args.ensemble_members,
+                                       ic_noise=args.ensemble_noise, feedback_noise=args.ensemble_feedback_noise,
+                                       seed=args.ensemble_seed, batch_size=args.batch_size, lat=grid_latitudes(H))
+                table = lead_time_table(ens)
+                logger['rollout_ensemble'] = table
+                np.save(os.path.join(args.snapshot_dir, "rollout_ensemble_table.npy"), table)
+                np.savez(os.path.join(args.snapshot_dir, "rollout_ensemble.npz"),
+                         **ens.report(test_dataset.y_mean, test_dataset.y_std).arrays())
+                print(f"Ensemble roll-out, {args.ensemble_members} members (z-score units): lead " + " ".join(LEAD_TIME_COLUMNS))
+                for j, row in enumerate(table):
+                    print(f"  {j}: " + " ".join(f"{v:.4f}" for v in row))
         time_elapsed = time.time() - since
         print(f'Training complete in {time_elapsed // 60:.0f}m {time_elapsed % 60:.0f}s')
     if world > 1:

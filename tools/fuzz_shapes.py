@@ -133,6 +133,9 @@ RESIDUAL_KEY = 2000             # the stream key of RESIDUAL_MODES[i] is RESIDUA
 # ... and RESIDUAL_MODES is pinned in turn (tests/test_residual_cpu.py): the input noise's mode continues the same way
 NOISE_MODES = ("noise",)
 NOISE_KEY = 3000                # the stream key of NOISE_MODES[i] is NOISE_KEY + i
+# ... and NOISE_MODES is pinned as well (tests/test_gpu_fuzz_noise.py): the ensemble statistics' mode continues the same way
+ENSEMBLE_MODES = ("ensemble",)
+ENSEMBLE_KEY = 4000             # the stream key of ENSEMBLE_MODES[i] is ENSEMBLE_KEY + i
 LIM = {"f32": 1e-3, "bf16": 3e-2}
 LOSS_LIM = {"f32": 2e-6, "bf16": 2e-2}
 
@@ -284,6 +287,8 @@ def case_rng(seed: int, mode: str, it: int):
         return np.random.default_rng([int(seed), RESIDUAL_KEY + RESIDUAL_MODES.index(mode), int(it)])
     if mode in NOISE_MODES:
         return np.random.default_rng([int(seed), NOISE_KEY + NOISE_MODES.index(mode), int(it)])
+    if mode in ENSEMBLE_MODES:
+        return np.random.default_rng([int(seed), ENSEMBLE_KEY + ENSEMBLE_MODES.index(mode), int(it)])
     return np.random.default_rng([int(seed), 1 + ALL_STREAM_MODES.index(mode), int(it)])
 
 
@@ -306,6 +311,8 @@ def draw_case(rng, it: int, mode: str = "plain", big: bool = False, wide: bool =
         return draw_residual(rng, it)
     if mode == "noise":
         return draw_noise(rng, it)
+    if mode == "ensemble":
+        return draw_ensemble(rng, it)
     new = mode in NEW_MODES
     L = int(rng.integers(1, 5))
     hidden = [int(rng.choice([4, 8, 16, 24, 32, 48, 64] if new else [4, 8, 16, 24, 32, 48, 64, 64, 128])) for _ in range(L)]
@@ -558,6 +565,29 @@ def draw_noise(rng, it: int) -> dict:
                     f"noise span=[{c0},{c0 + n}) zero-sigma={int(0.0 in sigma)} step0={key['step0']} cyclic={int(cyclic)} fold={int(fold)}")
 
 
+def draw_ensemble(rng, it: int) -> dict:
+    """--ensemble: nint_ens_accum alone -- members M, samples N (now and then beyond one launch's 64), outputs, a grid and a crop
+    window in it, slots with -1 among them and one slot that no sample names, and where the members lie: contiguous, or a
+    roll-out's (lanes, T, O, H, W) buffer read in place, the samples in shuffled order and one of them twice.  Pure."""
+    M = int(rng.choice([2, 3, 4, 5, 8, 16, 33, 64]))
+    N = int(rng.choice([1, 2, 3, 5, 8, 70])) if M <= 8 else int(rng.integers(1, 5))
+    O = int(rng.choice([1, 2, 4, 5, 9]))
+    H, W = int(rng.integers(3, 25)), int(rng.integers(3, 45))
+    Hc, Wc = int(rng.integers(1, H + 1)), int(rng.integers(1, W + 1))
+    oy, ox = int(rng.integers(0, H - Hc + 1)), int(rng.integers(0, W - Wc + 1))
+    used = int(rng.integers(1, 4))
+    slots = [int(v) for v in rng.integers(-1, used, size=N)]
+    layout = "contiguous" if it % 2 == 0 else "rollout"
+    T, spinup = int(rng.integers(2, 5)), 1
+    order = [int(v) for v in rng.permutation(N)]
+    if layout == "rollout" and N > 1:
+        order[-1] = order[0]                                      # one sample twice: overlapping reads
+    return dict(it=it, mode="ensemble", M=M, N=N, O=O, H=H, W=W, oy=oy, ox=ox, Hc=Hc, Wc=Wc, slots=slots, nslots=used + 1,
+                layout=layout, T=T, spinup=spinup, order=order, row_w=bool(rng.integers(0, 2)), integer=bool(it % 3 == 0),
+                draws=[], tag=f"#{it} ensemble M={M} N={N} O={O} {H}x{W} crop {Hc}x{Wc}@({oy},{ox}) slots={used}+1 {layout} "
+                               f"{'integer' if it % 3 == 0 else 'normal'} data")
+
+
 def draw_data(rng, case) -> dict:
     """the standard-normal tensors of a case, f32, from the generator that drew it"""
     return {name: torch.from_numpy(rng.standard_normal(sh).astype(np.float32)) for name, sh in case["draws"]}
@@ -568,7 +598,7 @@ def draw_cases(seed: int, n: int, mode: str = "plain", big: bool = False, wide: 
     cases = []
     rng = np.random.default_rng(seed)
     for it in range(n):
-        if mode in ALL_STREAM_MODES + SAMPLED_MODES + RESIDUAL_MODES + NOISE_MODES:
+        if mode in ALL_STREAM_MODES + SAMPLED_MODES + RESIDUAL_MODES + NOISE_MODES + ENSEMBLE_MODES:
             cases.append(draw_case(case_rng(seed, mode, it), it, mode))
         else:
             cases.append(draw_case(rng, it, mode, big, wide))
@@ -1197,6 +1227,7 @@ def parse(argv=None):
     ap.add_argument("--sampled", action="store_true", help="ConvLSTM(feedback=True)(x[, state], free_mask=M[, feedback_grad=True]): a drawn stack, grid, number of feedback channels, storage type, boundary condition, input layout, state and (B, T) feed mask of a drawn density.  Forward: the per-step predictions against the CPU model tests/sampled_model.py and bit for bit against the open-loop pass over the input with those predictions substituted where the mask says.  Without a fed image at step 0: outputs, every parameter gradient and dx under drawn cotangents (per step or last step) against the model under CPU autograd in f64.  --self-check: the reference of the first case with a mixed step is computed as if every image were fed from the first fed step on")
     ap.add_argument("--residual", action="store_true", help="ConvLSTM(feedback=True, residual=True)(x[, state], free_from=F | free_mask=M[, feedback_grad=True]): a drawn stack, grid, number of feedback channels, storage type, boundary condition, input layout, state and first fed step F >= 1 or (B, T) feed mask with column 0 clear.  Forward: the per-step predictions p_t = x_t[feedback channels] + head(h_t) against the CPU model tests/residual_model.py and bit for bit against the residual open-loop pass over the input with those predictions substituted where fed.  Then outputs, every parameter gradient and dx under drawn cotangents against the model under CPU autograd in f64.  --self-check: the reference of the first case is the non-residual model (the base dropped)")
     ap.add_argument("--noise", action="store_true", help="ConvLSTM(x, input_noise=InputNoise(std, channels=(c0, n), seed, draw, step0, lane0)): a drawn stack, grid, noise span, sigma per channel (one may be 0), storage type, boundary condition, input layout and generator key.  The noisy pass -- outputs, every parameter gradient and dx under drawn cotangents -- against the CPU oracle under autograd in f64 on the PRE-NOISED input, which tests/noise_model.py builds on the host from its own Philox and normals; a pass with an all-zero std is the pass without the argument, bit for bit.  --self-check: the reference of the first case is the clean input")
+    ap.add_argument("--ensemble", action="store_true", help="nint_ens_accum alone: drawn members, samples (beyond one launch's 64 too), outputs, grid, crop window, slots with -1 and an empty slot, and the members contiguous or read in place from a roll-out's (lanes, T, O, H, W) buffer with shuffled, overlapping sample offsets.  Integer data: every plane, sample column and bin bit for bit against the numpy model tests/ensemble_model.py; normal data: the maps and bins bit for bit, the sample rows within the any-order bound of their f64 addends")
     ap.add_argument("--self-check", action="store_true", help="with --state / --train-opts / --stateful / --finetune / --sampled / --residual: corrupt the reference after the first passing case and require the comparison to fail")
     ap.add_argument("--guarded", action="store_true", help="every mode: the device side of each case allocates through oracle/guarded_alloc.py in poison mode (guards around every buffer, `empty` payloads 0xFF), its inputs and parameters in arenas of their own; the comparison stays what it is and every guard byte is checked after each case.  With --self-check (any mode): one guard byte is flipped after the first passing case and the check has to fail (the reference is then not corrupted)")
     ap.add_argument("--list", action="store_true", help="print the drawn cases as JSON lines and exit (no GPU, the package is not imported)")
@@ -1205,11 +1236,13 @@ def parse(argv=None):
     ap.add_argument("--force-dtype", choices=["f32", "bf16"], default=None, help="with --only: the storage type of the replayed case instead of the alternation's (is the miss the arithmetic's, or the storage type's?)")
     args = ap.parse_args(argv)
     modes = [m for m in ("dataset", "cell", "trainer", "state", "train_opts", "stateful", "finetune", "closed_loop", "rollout", "sampled",
-                         "residual", "noise") if getattr(args, m)]
+                         "residual", "noise", "ensemble") if getattr(args, m)]
     if len(modes) > 1 and not all(m in OLD_MODES for m in modes):
         ap.error("one of --state / --train-opts / --stateful / --finetune / --closed-loop / --rollout / --sampled / --residual at a time, and none of the other modes with it")
     args.mode = modes[0] if modes else "plain"          # (--dataset before --cell before --trainer, as ever)
-    if args.mode in ("closed_loop", "rollout", "sampled", "residual", "noise") and (args.big or args.wide):
+    if args.mode == "ensemble" and (args.self_check or args.guarded):
+        ap.error("--ensemble has no reference to corrupt and allocates its own buffers: not with --self-check / --guarded")
+    if args.mode in ("closed_loop", "rollout", "sampled", "residual", "noise", "ensemble") and (args.big or args.wide):
         ap.error("--closed-loop / --rollout / --sampled / --residual / --noise draw their own shapes: not with --big / --wide")
     if args.self_check and args.mode not in NEW_MODES + SAMPLED_MODES + RESIDUAL_MODES + NOISE_MODES and not args.guarded:
         ap.error("--self-check needs --state, --train-opts, --stateful, --finetune, --sampled, --residual or --noise (or --guarded)")
@@ -1696,6 +1729,91 @@ def noise_run(case, d, args, worst, tried):
     print(f"ok   {tag}  worst {w:.2e}", flush=True)
 
 
+def ensemble_run(case, lib):
+    """one drawn case of nint_ens_accum against tests/ensemble_model.py; returns the worst sample-row error / bound"""
+    import ctypes as C
+    import math
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    try:
+        import ensemble_model as EM
+    finally:
+        sys.path.pop(0)
+    from oracle import small_audit as SM
+    M, N, O, H, W, oy, ox, Hc, Wc = (case[k] for k in ("M", "N", "O", "H", "W", "oy", "ox", "Hc", "Wc"))
+    rng = np.random.default_rng([case["it"], M, N])
+    if case["integer"]:
+        x = rng.integers(-8, 9, (N, M, O, Hc, Wc)).astype(np.float32)
+        y = rng.integers(-8, 9, (N, O, Hc, Wc)).astype(np.float32)
+        row_w = EM.dyadic_rows(Hc) if case["row_w"] else None
+    else:
+        x = rng.standard_normal((N, M, O, Hc, Wc)).astype(np.float32)
+        y = rng.standard_normal((N, O, Hc, Wc)).astype(np.float32)
+        row_w = 0.25 + rng.random(Hc) if case["row_w"] else None
+    img = O * H * W
+    if case["layout"] == "contiguous":
+        buf = np.full((N, M, O, H, W), np.nan, np.float32)
+        buf[:, :, :, oy:oy + Hc, ox:ox + Wc] = x
+        off, stride = [n * M * img for n in range(N)], img
+    else:                                     # sample n = (start n, lead 0) of a roll-out buffer, listed in case["order"]
+        T, sp = case["T"], case["spinup"]
+        buf = np.full((N * M, T, O, H, W), np.nan, np.float32)
+        for n in range(N):
+            buf[n * M:(n + 1) * M, sp, :, oy:oy + Hc, ox:ox + Wc] = x[n]
+        order = case["order"]
+        off, stride = [((n * M) * T + sp) * img for n in order], T * img
+        x = x[order]
+    nslots, slots = case["nslots"], case["slots"]
+    pix0 = rng.integers(-4, 5, (nslots, EM.PIX, O, Hc, Wc)).astype(np.float64)
+    hist0 = rng.integers(0, 9, (nslots, O, M + 2)).astype(np.int64)
+    ref = EM.sums(x, y, slots, nslots, row_w, pix0, hist0)
+    dev = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    P = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+    bd, yd, rw, pix, hist = dev(buf), dev(y), dev(row_w), dev(pix0), dev(hist0)
+    nb = lib.nint_ens_scratch_bytes(N, M, O, Hc, Wc)
+    sample = torch.full((N, O, EM.SAMPLE), float("nan"), dtype=torch.float64, device="cuda")
+    scratch = torch.full((nb // 8,), float("nan"), dtype=torch.float64, device="cuda")
+    mean = torch.full((N, O, Hc, Wc), float("nan"), device="cuda")
+    rc = lib.nint_ens_accum(P(bd), (C.c_int64 * N)(*off), stride, M, P(yd), (C.c_int32 * N)(*slots), nslots, P(rw), P(pix), P(sample),
+                            P(hist), P(mean), P(scratch), nb, N, O, H, W, oy, ox, Hc, Wc, None)
+    assert rc == 0, (case["tag"], rc)
+    torch.cuda.synchronize()
+    SM.check_equal(pix.cpu().numpy(), ref["pix"], case["tag"] + ": pix")
+    SM.check_equal(hist.cpu().numpy(), ref["rank_hist"], case["tag"] + ": rank_hist")
+    SM.check_equal(mean.cpu().numpy(), ref["mean"], case["tag"] + ": mean_out")
+    got = sample.cpu().numpy()
+    if case["integer"]:
+        SM.check_equal(got, ref["sample"], case["tag"] + ": sample")
+        return 0.0
+    # a row is a tree over the crop's f64 addends (the model's own terms, bit for bit the kernel's): any order of Hc * Wc terms
+    st, worst = ref["sample_terms"], 0.0
+    g = SM.gamma(max(Hc * Wc - 1, 0), SM.U64)
+    for n in range(N):
+        for o in range(O):
+            for k in range(EM.SAMPLE):
+                terms = st[k, n, o].reshape(-1).tolist()
+                err, bound = abs(math.fsum(terms + [-float(got[n, o, k])])), g * math.fsum(abs(v) for v in terms)
+                assert math.isfinite(got[n, o, k]) and err <= bound, (case["tag"], (n, o, k), got[n, o, k], err, bound)
+                worst = max(worst, err / bound if bound > 0 else 0.0)
+    return worst
+
+
+def ensemble_main(args):
+    if ROOT not in sys.path:
+        sys.path.insert(0, ROOT)
+    import nasa_niswan_amd as pkg_
+    lib = pkg_.load_library()
+    t_start, worst = time.time(), 0.0
+    for it in range(args.n):
+        if args.only >= 0 and it != args.only:           # (a stream per case: the replayed case needs none of the others)
+            continue
+        case = draw_case(case_rng(args.seed, "ensemble", it), it, "ensemble")
+        w = ensemble_run(case, lib)
+        worst = max(worst, w)
+        print(f"ok   {case['tag']}  rows {w:.2e} of the bound", flush=True)
+    print(f"wall {time.time() - t_start:.1f} s")
+    print(f"{args.n} shapes ok; worst sample-row error {worst:.2e} of the any-order bound")
+
+
 def main(argv=None):
     args = parse(argv)
     new = args.mode in ALL_STREAM_MODES + SAMPLED_MODES + RESIDUAL_MODES + NOISE_MODES
@@ -1703,6 +1821,8 @@ def main(argv=None):
         for case in draw_cases(args.seed, args.n, args.mode, args.big, args.wide):
             print(json.dumps(case), flush=True)
         return
+    if args.mode == "ensemble":
+        return ensemble_main(args)
     _load()
     t_start = time.time()
     rng = np.random.default_rng(args.seed)
