@@ -942,6 +942,61 @@ int nint_ens_accum(const float* pred, const int64_t* sample_off /*host, N*/, int
                    double* pix, double* sample, int64_t* rank_hist, float* mean_out /*(N,O,Hc,Wc) or NULL*/, double* scratch,
                    size_t scratch_bytes, int N, int O, int H, int W, int oy, int ox, int Hc, int Wc, void* stream);
 
+/* ---- training: the almost-fair CRPS of an ensemble's member lanes --------------------------------------- */
+/* The loss that couples the M members of a sample, d loss / d pred of every member and the epoch statistics, in one pass over
+ * the members where they lie.  Addressing is nint_ens_accum's, once for reading and once for writing: member i of sample n is
+ * the (O, H, W) f32 image at pred + pred_off[n] + i * pred_stride, its gradient image is written at dpred + dpred_off[n] +
+ * i * dpred_stride (elements; host arrays of N offsets, read at the call).  So the (lanes, T, O, H, W) output of
+ * nint_head_fwd_seq with lanes n*M + m is read in place -- sample (n, t) at ((n*M)*T + t) * O*H*W, member stride T * O*H*W --
+ * and the roll-out slab (T*B, O, H, W) of nint_feedback_grad is written in place -- sample (n, t) at (t*B + n*M) * O*H*W,
+ * member stride O*H*W.  y (N, O, Hc, Wc) f32 and the crop window as in every loss entry.
+ * Weights, with nint_loss_crop_spec's conventions: wgt, the optional cell map [Hc][Wc] with its f64 sum wsum (not read
+ * without a map); spec->ow, an optional DEVICE table [nrows][O] of output weights of which spec->ow_row[n] (HOST, N entries;
+ * NULL: row 0) picks the row of sample n -- step weights and spin-up discounts arrive as one row per step.
+ *   w = wgt[cy][cx] or 1, q = ow[ow_row[n]][o] or 1, Wd = (double)q * (double)w.
+ *   spec->cnt, formed by the caller in f64: the sum of q AS STORED over the listed samples and outputs, times wsum (N * O
+ *   without a table, Hc * Wc without a map).
+ *   Wd == 0: the element is skipped -- its target is not read (a NaN target is harmless), it enters no sum, dpred = +0 for
+ *   all M members.
+ * Per cell, all in f64, every operation rounded once (no contraction); x_i = (double)member i, t = (double)y, dM = (double)M:
+ *   A = sum_i |x_i - t| (i ascending);  D = sum_{i<j} |x_i - x_j| ((i, j) lexicographic);  S = x_0 + ... + x_{M-1};
+ *   V = sum_i (dM*x_i - S)^2;  m = S / dM (the one division, for the statistics only);
+ *   sgn(d) = d > 0 ? 1 : (d < 0 ? -1 : d): sgn(0) = 0, a NaN stays NaN;   R_i = sum_{j != i} sgn(x_i - x_j), j ascending
+ *   kp = (M - 1 + alpha) / (M^2 (M - 1)), formed on the host in f64 from spec->alpha in [0, 1]: alpha = 1 the fair CRPS
+ *   (kp = 1 / (M (M - 1))), alpha = 0 the plain one (1 / M^2), in between the "almost fair" mix.
+ *   Over the cells of the call: SA = sum Wd*A, SD = sum Wd*D, SV = sum Wd*V, S2 = sum Wd*(m-t)^2, S1 = sum Wd*|m-t|,
+ *   Sy = sum Wd*t, Syy = sum Wd*t^2 -- a fixed-order reduction without floating-point atomics: a tree per (sample, output) that
+ *   depends on (H, W) only, then the (sample, output) rows in ascending order; bit-identical run to run and under any
+ *   internal cut (N beyond NINT_ENS_MAX_N runs in pieces).
+ *   loss    = (SA / dM - kp * SD) / cnt, left to right; loss_out[0] = (float)loss, on the device.
+ *   dpred_i = (float)(((sgn(x_i - t) / dM - kp * R_i) * (1.0 / cnt)) * Wd), left to right, rounded to f32 once; +0 at every
+ *             pixel outside the crop.  Whole (O, H, W) images of the M members of the listed samples are written; images of
+ *             samples that are not listed are the caller's to zero.
+ *   stats   : NINT_LOSS_STATS doubles, ACCUMULATED, with the ENSEMBLE MEAN m as the prediction: [0..4] += S2, S1, Sy, Syy, cnt;
+ *             [5] += loss; [6] += the weighted R2 of the mean (the _spec entries' expression); [7] += 1.
+ *   ens_out : NINT_ENS_LOSS_OUT doubles, ACCUMULATED: += SA, SD, SV, cnt.  Mean CRPS (SA/M - kp SD) / cnt, spread
+ *             sqrt(SV / (M^2 (M-1)) / cnt), RMSE of the mean sqrt(stats[0] / stats[4]).
+ *   scratch : nint_ens_loss_scratch_bytes(N, M, O, H, W) bytes, 8-byte aligned.  Memory contract: exactly that
+ *             many suffice, no store goes outside the named extents and no result depends on a byte the library did not write.
+ * NINT_E_ARG before any launch: a NULL pred / pred_off / dpred / dpred_off / y / spec / loss_out / stats / ens_out / scratch; M
+ * outside [2, NINT_ENS_MAX_M]; N or O < 1; a negative offset or stride; alpha outside [0, 1] or not finite; !(cnt > 0) or a
+ * non-finite cnt; a map with !(wsum > 0) or a non-finite wsum; ow_row (or nrows != 0) without ow, ow with nrows < 1, a row
+ * outside the table; a crop outside the grid; a scratch that is too small.  Then NINT_E_ALIGN: stats / ens_out / scratch not
+ * 8-byte, pred / dpred / y / wgt / ow / loss_out not 4-byte aligned. */
+#define NINT_ENS_LOSS_OUT 4
+typedef struct nint_ens_loss_spec {
+  double alpha;           /* 1 = fair CRPS, 0 = plain, between: almost fair */
+  double cnt;             /* the normaliser (above) */
+  const float* ow;        /* device f32 [nrows][O], 4-byte aligned, finite and >= 0 (the caller validates); NULL = 1 */
+  const int32_t* ow_row;  /* host, N entries in [0, nrows); NULL = row 0 */
+  int32_t nrows;          /* rows of ow; 0 with ow == NULL */
+} nint_ens_loss_spec;
+size_t nint_ens_loss_scratch_bytes(int N, int M, int O, int H, int W);    /* host arithmetic only */
+int nint_ens_loss(const float* pred, const int64_t* pred_off /*host, N*/, int64_t pred_stride, float* dpred,
+                  const int64_t* dpred_off /*host, N*/, int64_t dpred_stride, int M, const float* y, const float* wgt, double wsum,
+                  const nint_ens_loss_spec* spec, float* loss_out, double* stats, double* ens_out, double* scratch,
+                  size_t scratch_bytes, int N, int O, int H, int W, int oy, int ox, int Hc, int Wc, void* stream);
+
 /* ---- optimiser (train.py:71,110) ---------------------------------------------------------------- */
 /* torch.optim.Adam (eps 1e-8, no weight decay / amsgrad) on one flat f32 buffer.
  * grad_scale multiplies g first (1/world_size after the RCCL all-reduce). step is 1-based. */

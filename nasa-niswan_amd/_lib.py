@@ -19,6 +19,7 @@ NINT_LOSS_SPEC_SCRATCH_FLOATS = 10242     # the _spec loss entries: five doubles
 NINT_LOSS_STATS = 8
 NINT_SKILL_PIX, NINT_SKILL_SAMPLE, NINT_SKILL_MAX_N = 5, 8, 64
 NINT_ENS_PIX, NINT_ENS_SAMPLE, NINT_ENS_MAX_N, NINT_ENS_MAX_M = 7, 8, 64, 64
+NINT_ENS_LOSS_OUT = 4     # nint_ens_loss's ens_out: SA, SD, SV, cnt
 NINT_GRAD_NORM_BLOCKS = 256
 NINT_OPT_STATE = 16
 NINT_MAX_OPT_GROUPS = 2 * NINT_MAX_LAYERS + 2
@@ -118,6 +119,12 @@ class NintLossSpec(C.Structure):
                 ("now", C.c_int32), ("osum", C.c_double)]
 
 
+class NintEnsLossSpec(C.Structure):
+    """nint_ens_loss_spec: the almost-fair CRPS of nint_ens_loss (alpha, the normaliser, the output-weight table and the HOST
+    array that picks each sample's row)"""
+    _fields_ = [("alpha", C.c_double), ("cnt", C.c_double), ("ow", vp), ("ow_row", C.POINTER(C.c_int32)), ("nrows", C.c_int32)]
+
+
 # every symbol include/nint.h declares: name -> (restype, argtypes)
 _I, _SZ, _F, _D, _U = C.c_int, C.c_size_t, C.c_float, C.c_double, C.c_uint32
 _PG, _PL, _PS, _PLS = C.POINTER(NintGeom), C.POINTER(NintLayer), C.POINTER(NintSeq), C.POINTER(NintLossSpec)
@@ -207,6 +214,9 @@ SIGNATURES = {
     "nint_ens_scratch_bytes": (_SZ, [_I, _I, _I, _I, _I]),
     "nint_ens_accum": (_I, [vp, C.POINTER(C.c_int64), C.c_int64, _I, vp, C.POINTER(C.c_int32), _I, vp, vp, vp, vp, vp, vp, _SZ,
                             _I, _I, _I, _I, _I, _I, _I, _I, vp]),
+    "nint_ens_loss_scratch_bytes": (_SZ, [_I, _I, _I, _I, _I]),
+    "nint_ens_loss": (_I, [vp, C.POINTER(C.c_int64), C.c_int64, vp, C.POINTER(C.c_int64), C.c_int64, _I, vp, vp, _D,
+                           C.POINTER(NintEnsLossSpec), vp, vp, vp, vp, _SZ, _I, _I, _I, _I, _I, _I, _I, _I, vp]),
     "nint_adam_flat": (_I, [vp, vp, vp, vp, _SZ, C.c_double, C.c_double, C.c_double, C.c_double, _I, _F, vp]),
     "nint_grad_norm_scratch_bytes": (_SZ, []),
     "nint_grad_norm_flat": (_I, [vp, _SZ, _F, vp, vp, _SZ, vp]),

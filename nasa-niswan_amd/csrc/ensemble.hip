@@ -22,6 +22,7 @@
 // integer atomics into hist_s[M + 2] and adds the non-zero bins to rank_hist with vector global 64-bit atomics when the slot
 // changes and after the last sample.
 #include <algorithm>
+#include <cfloat>
 #include <climits>
 #include "nint_common.h"
 
@@ -166,5 +167,175 @@ extern "C" int nint_ens_accum(const float* pred, const int64_t* sample_off, int6
     const int rc = nint_internal_skill_fold_enqueue(scratch, sample + (size_t)c0 * O * NINT_ENS_SAMPLE, nc * O, NP, st);
     if (rc != NINT_OK) return rc;
   }
+  return NINT_OK;
+}
+
+// ------------------------------------------------------------------------------ the training loss
+// nint_ens_loss: the almost-fair CRPS of M member lanes, d loss / d pred of every member and the epoch statistics in one pass
+// over the members where they lie (include/nint.h carries the rule).
+// Mapping: nothing accumulates per pixel here, so the samples go on the grid: grid = (256-pixel blocks of the FULL H x W image,
+// groups of ENS_OG outputs, samples of the piece).  A thread owns one pixel of every member image of its (sample, output): outside
+// the crop (or under a zero weight) it stores M zeros; inside it reads the M members once into its own LDS column
+// x_s[i][thread] (no bank conflict, no barrier), runs the pair loop from there and stores M gradients.  Consecutive lanes touch
+// consecutive pixels in every load and store.  The seven sums of a (sample, output): skill_wave_fold per wave, the workgroup's
+// four waves joined in wave order through LDS (the kernel's one barrier), one partial row per (sample, output, workgroup),
+// skill_fold_kernel over the workgroups, and ens_loss_final_kernel over the (sample, output) rows in ascending order: no
+// floating-point atomics, and no figure depends on how the samples are cut into launches.
+struct EnsLossPlan { int64_t poff[NINT_ENS_MAX_N]; int64_t doff[NINT_ENS_MAX_N]; int32_t row[NINT_ENS_MAX_N]; };
+
+// sgn with sgn(0) = 0 that keeps a NaN (comparisons, as C(d) of the spec loss)
+__device__ __forceinline__ double ens_sgn(double d) { return d > 0.0 ? 1.0 : (d < 0.0 ? -1.0 : d); }
+
+__global__ __launch_bounds__(256) void ens_loss_kernel(const float* __restrict__ pred, int64_t pstride, float* __restrict__ dpred,
+                                                       int64_t dstride, int M, const float* __restrict__ y,
+                                                       const float* __restrict__ wgt, const float* __restrict__ ow, double kp,
+                                                       double cnt, double* __restrict__ part, const EnsLossPlan plan, int O, int H,
+                                                       int W, int oy, int ox, int Hc, int Wc) {
+#pragma clang fp contract(off)
+  extern __shared__ float x_s[];                                       // [M][256]: the thread's members of one cell
+  __shared__ double red_s[ENS_OG][4][NINT_ENS_SAMPLE];                 // the four waves' sums of each output of the group
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = blockIdx.z;
+  const size_t HW = (size_t)H * W, HWc = (size_t)Hc * Wc, p = (size_t)blockIdx.x * 256 + tid;
+  const bool in_img = p < HW;
+  const int py = (int)(p / W), px = (int)(p - (size_t)py * W), cy = py - oy, cx = px - ox;
+  const bool in_crop = in_img && cy >= 0 && cy < Hc && cx >= 0 && cx < Wc;
+  const size_t cyx = in_crop ? (size_t)cy * Wc + cx : 0;
+  const float cw = in_crop ? (wgt ? wgt[cyx] : 1.f) : 0.f;
+  const int o0 = blockIdx.y * ENS_OG, on = min(ENS_OG, O - o0);
+  const double dM = (double)M, inv_n = 1.0 / cnt;
+  const float* owr = ow ? ow + (size_t)plan.row[n] * O : nullptr;
+  float* xc = x_s + tid;
+  for (int u = 0; u < on; ++u) {                                       // (block-uniform)
+    const int o = o0 + u;
+    const float q = owr ? owr[o] : 1.f;
+    float* dp = dpred + plan.doff[n] + (size_t)o * HW + p;
+    double v[NINT_ENS_SAMPLE] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (in_crop && cw != 0.f && q != 0.f) {                            // Wd != 0: two non-zero f32 have a non-zero f64 product
+      const double Wd = (double)q * (double)cw;
+      const double t = (double)y[((size_t)n * O + o) * HWc + cyx];
+      const float* pm = pred + plan.poff[n] + (size_t)o * HW + p;
+      double S = 0.0, A = 0.0;
+#pragma unroll 4
+      for (int i = 0; i < M; ++i) {
+        const float xf = pm[(size_t)i * pstride];
+        xc[i * 256] = xf;
+        const double x = (double)xf;
+        S += x;
+        A += fabs(x - t);
+      }
+      const double m = S / dM;                                         // the one division of the cell: the statistics' mean
+      double V = 0.0, D = 0.0;
+      for (int i = 0; i < M; ++i) {
+        const double xi = (double)xc[i * 256];
+        const double dv = dM * xi - S;
+        V += dv * dv;
+        double R = 0.0;
+        for (int j = 0; j < M; ++j) {
+          if (j == i) continue;
+          const double d = xi - (double)xc[j * 256];
+          R += ens_sgn(d);
+          if (j > i) D += fabs(d);
+        }
+        dp[(size_t)i * dstride] = (float)(((ens_sgn(xi - t) / dM - kp * R) * inv_n) * Wd);
+      }
+      const double e = m - t;
+      v[0] = Wd * A; v[1] = Wd * D; v[2] = Wd * V; v[3] = Wd * (e * e); v[4] = Wd * fabs(e); v[5] = Wd * t; v[6] = Wd * (t * t);
+    } else if (in_img) {
+      for (int i = 0; i < M; ++i) dp[(size_t)i * dstride] = 0.f;
+    }
+    const double tot = skill_wave_fold(v, lane);
+    if ((lane & 7) == 0) red_s[u][wave][lane >> 3] = tot;
+  }
+  __syncthreads();
+  if (tid < on * NINT_ENS_SAMPLE) {
+    const int u = tid >> 3, k = tid & 7;
+    const double s = ((red_s[u][0][k] + red_s[u][1][k]) + red_s[u][2][k]) + red_s[u][3][k];
+    part[(((size_t)n * O + o0 + u) * gridDim.x + blockIdx.x) * NINT_ENS_SAMPLE + k] = s;
+  }
+}
+
+// rows [nrows][NINT_ENS_SAMPLE]: SA, SD, SV, S2, S1, Sy, Syy of every (sample, output), added in ascending row order by one
+// thread per sum; then the loss, the statistics of the ensemble mean and the ensemble sums (include/nint.h)
+__global__ __launch_bounds__(64) void ens_loss_final_kernel(const double* __restrict__ rows, int nrows, double dM, double kp, double cnt,
+                                                           float* __restrict__ loss_out, double* __restrict__ stats,
+                                                           double* __restrict__ ens_out) {
+#pragma clang fp contract(off)
+  __shared__ double tot_s[NINT_ENS_SAMPLE];
+  const int k = threadIdx.x;
+  if (k < NINT_ENS_SAMPLE) {
+    double s = 0.0;
+#pragma unroll 8
+    for (int r = 0; r < nrows; ++r) s += rows[(size_t)r * NINT_ENS_SAMPLE + k];
+    tot_s[k] = s;
+  }
+  __syncthreads();
+  if (k == 0) {
+    const double SA = tot_s[0], SD = tot_s[1], SV = tot_s[2], S2 = tot_s[3], S1 = tot_s[4], Sy = tot_s[5], Syy = tot_s[6];
+    const double loss = (SA / dM - kp * SD) / cnt;
+    loss_out[0] = (float)loss;
+    stats[0] += S2; stats[1] += S1; stats[2] += Sy; stats[3] += Syy; stats[4] += cnt;
+    const double ss_tot = Syy - Sy * Sy / cnt;
+    const double r2 = ss_tot > 0.0 ? 1.0 - S2 / ss_tot : (S2 == 0.0 ? 1.0 : 0.0);   // the loss entries' constant-target convention
+    stats[5] += loss; stats[6] += r2; stats[7] += 1.0;
+    ens_out[0] += SA; ens_out[1] += SD; ens_out[2] += SV; ens_out[3] += cnt;
+  }
+}
+
+static inline size_t ens_loss_blocks(int H, int W) { return ((size_t)H * W + 255) / 256; }
+
+// scratch: the workgroups' partial rows of one piece, then the (sample, output) rows of the whole call
+extern "C" size_t nint_ens_loss_scratch_bytes(int N, int M, int O, int H, int W) {
+  if (N <= 0 || M <= 0 || O <= 0 || H <= 0 || W <= 0) return 0;
+  const size_t nc = N < NINT_ENS_MAX_N ? N : NINT_ENS_MAX_N;
+  return (nc * O * ens_loss_blocks(H, W) + (size_t)N * O) * NINT_ENS_SAMPLE * sizeof(double);
+}
+
+extern "C" int nint_ens_loss(const float* pred, const int64_t* pred_off, int64_t pred_stride, float* dpred, const int64_t* dpred_off,
+                             int64_t dpred_stride, int M, const float* y, const float* wgt, double wsum,
+                             const nint_ens_loss_spec* spec, float* loss_out, double* stats, double* ens_out, double* scratch,
+                             size_t scratch_bytes, int N, int O, int H, int W, int oy, int ox, int Hc, int Wc, void* stream) {
+  if (!pred || !pred_off || !dpred || !dpred_off || !y || !spec || !loss_out || !stats || !ens_out || !scratch) return NINT_E_ARG;
+  if (M < 2 || M > NINT_ENS_MAX_M || N < 1 || O < 1 || pred_stride < 0 || dpred_stride < 0) return NINT_E_ARG;
+  for (int n = 0; n < N; ++n)
+    if (pred_off[n] < 0 || dpred_off[n] < 0) return NINT_E_ARG;
+  if (!(spec->alpha >= 0.0) || !(spec->alpha <= 1.0)) return NINT_E_ARG;
+  if (!(spec->cnt > 0.0) || spec->cnt > DBL_MAX) return NINT_E_ARG;
+  if (wgt && (!(wsum > 0.0) || wsum > DBL_MAX)) return NINT_E_ARG;
+  if (spec->ow) {
+    if (spec->nrows < 1) return NINT_E_ARG;
+    for (int n = 0; spec->ow_row && n < N; ++n)
+      if (spec->ow_row[n] < 0 || spec->ow_row[n] >= spec->nrows) return NINT_E_ARG;
+  } else if (spec->ow_row || spec->nrows != 0) {
+    return NINT_E_ARG;
+  }
+  if (Hc < 1 || Wc < 1 || oy < 0 || ox < 0 || oy + Hc > H || ox + Wc > W) return NINT_E_ARG;
+  if (scratch_bytes < nint_ens_loss_scratch_bytes(N, M, O, H, W)) return NINT_E_ARG;
+  if (((((uintptr_t)stats) | ((uintptr_t)ens_out) | ((uintptr_t)scratch)) & 7) != 0) return NINT_E_ALIGN;
+  if (((((uintptr_t)pred) | ((uintptr_t)dpred) | ((uintptr_t)y) | ((uintptr_t)wgt) | ((uintptr_t)spec->ow) | ((uintptr_t)loss_out)) & 3) != 0)
+    return NINT_E_ALIGN;
+  hipStream_t st = (hipStream_t)stream;
+  const double dM = (double)M;
+  const double kp = (dM - 1.0 + spec->alpha) / (dM * dM * (dM - 1.0));   // (M^2 (M - 1) <= 2^18: exact)
+  const int NP = (int)ens_loss_blocks(H, W);
+  const size_t HWc = (size_t)Hc * Wc;
+  const size_t ncmax = N < NINT_ENS_MAX_N ? N : NINT_ENS_MAX_N;
+  double* rows = scratch + ncmax * O * NP * NINT_ENS_SAMPLE;
+  for (int c0 = 0; c0 < N; c0 += NINT_ENS_MAX_N) {                     // pieces of at most NINT_ENS_MAX_N samples
+    const int nc = N - c0 < NINT_ENS_MAX_N ? N - c0 : NINT_ENS_MAX_N;
+    EnsLossPlan plan = {};
+    for (int i = 0; i < nc; ++i) {
+      plan.poff[i] = pred_off[c0 + i];
+      plan.doff[i] = dpred_off[c0 + i];
+      plan.row[i] = spec->ow_row ? spec->ow_row[c0 + i] : 0;
+    }
+    const dim3 grid((unsigned)NP, (unsigned)nint_cdiv(O, ENS_OG), (unsigned)nc);
+    hipLaunchKernelGGL(ens_loss_kernel, grid, dim3(256), (size_t)M * 256 * sizeof(float), st, pred, pred_stride, dpred, dpred_stride,
+                       M, y + (size_t)c0 * O * HWc, wgt, spec->ow, kp, spec->cnt, scratch, plan, O, H, W, oy, ox, Hc, Wc);
+    NINT_LAUNCH_CHECK();
+    const int rc = nint_internal_skill_fold_enqueue(scratch, rows + (size_t)c0 * O * NINT_ENS_SAMPLE, nc * O, NP, st);
+    if (rc != NINT_OK) return rc;
+  }
+  hipLaunchKernelGGL(ens_loss_final_kernel, dim3(1), dim3(64), 0, st, rows, N * O, dM, kp, spec->cnt, loss_out, stats, ens_out);
+  NINT_LAUNCH_CHECK();
   return NINT_OK;
 }

@@ -639,10 +639,12 @@ class SeqEngine:
         ``feedback`` the fed value is round_ET(p_{t-1}) of that p (the _residual entries).  A fed image at step 0 is refused:
         p_{-1} has no base, even with a state.
 
-        ``feedback_noise`` (with ``feedback``, forward only): an InputNoise whose ``std`` is one float or O floats
+        ``feedback_noise`` (with ``feedback``): an InputNoise whose ``std`` is one float or O floats
         -- every fed step stores round_ET(p + std[o] * z), z the input noise's normal of (pixel, o, step0 + t, lane0 + b).  It is
         one more field of the same feedback launches (nint_seq_fwd_stochastic).  None, all zeros or nothing fed: the entries and
-        bits of the pass without it."""
+        bits of the pass without it.  With ``feedback_grad=True`` the window is trained through the noisy
+        feedback: z is a constant, so under the straight-through rule the roll-out backward of the noise-free window is its
+        adjoint and runs as it stands."""
         B, T, Cc, H, W = x.shape
         assert (B, T, H, W) == (ws.B, ws.T, ws.H, ws.W) and Cc == self.cfgs[0].Cx
         s = ws.seq
@@ -676,9 +678,9 @@ class SeqEngine:
                                      "staged head kernels (nint_head_feedback: NINT_E_SHAPE)")
             ws.feedback.set(w2, b2, O, from_step, bool(feedback_grad), mask, bool(res_O))
         if feedback_noise is not None and feedback_noise.active and feedback is not None:      # (nothing fed back: nothing to put it on)
-            if feedback_grad or feedback_noise.channels is not None:
-                raise ValueError("feedback_noise: the noise goes onto the fed-back value of a forward-only closed loop -- it is refused "
-                                 "together with feedback_grad=True, and its channels must be None (the feedback channels)")
+            if feedback_noise.channels is not None:
+                raise ValueError("feedback_noise: the noise goes onto the fed-back value of the closed loop -- its channels must be "
+                                 "None (the feedback channels)")
             _, _, sig = feedback_noise.span(ws.feedback.fb.O, ws.feedback.fb.O)
             fn = NintFeedbackNoise()
             fn.sigma = self._sigma_tensor(sig).data_ptr()
@@ -1008,6 +1010,54 @@ class SeqEngine:
                                                  dh_seq.data_ptr() + t0 * blk, None, None, 0, C.byref(ws.g), self.dt, None, 0,
                                                  stream_ptr()), "nint_head_bwd_acc (dh of the unfed steps)")
         return slab
+
+    def ens_loss(self, ws: Workspace, seq: torch.Tensor, y: torch.Tensor, slab: torch.Tensor, M: int, spec, weights, scratch: torch.Tensor,
+                 loss_out: torch.Tensor, stats: torch.Tensor, ens_out: torch.Tensor, halo, Hc: int, Wc: int, every_step: bool = False):
+        """The almost-fair CRPS over the member lanes of a roll-out window (nint_ens_loss): ``seq`` is
+        head_forward_seq's (B, T*O, H, W) with lanes n*M + m, read in place; d loss / d pred of every member goes into the
+        roll-out slab ``slab`` (T*B, O, H, W), image t*B + n*M + m, in place.  ``y``: (N, O, Hc, Wc), the last step's targets, or
+        with ``every_step`` (N, T, O, Hc, Wc) -- sample (n, t) then takes row t of the output-weight table.  ``spec``
+        (loss.EnsembleLoss.on): ``alpha``, and ``ow`` (device f32 (rows, O)) with its host copy ``ow_host`` (numpy f32, the same
+        values: cnt is formed from it here), or both None: all ones.  ``weights`` = (wgt, wsum) as in head_loss_fused, or None.  Without ``every_step`` the images of the steps before the last are NOT
+        written: the caller zeroes them.  ``scratch``: f64, at least ens_loss_scratch(...) elements.  No host sync."""
+        B, T, H, W = ws.B, ws.T, ws.H, ws.W
+        O = slab.shape[1]
+        if M < 2 or B % M:
+            raise ValueError(f"ens_loss: {B} lanes do not hold whole ensembles of {M} members")
+        N, img = B // M, O * H * W
+        steps = range(T) if every_step else (T - 1,)
+        pairs = [(n, t) for n in range(N) for t in steps]               # y's own order: (N, [T,] O, Hc, Wc) is read in place
+        ns = len(pairs)
+        assert y.dtype == torch.float32 and y.is_contiguous() and y.numel() == ns * O * Hc * Wc
+        assert seq.dtype == torch.float32 and seq.is_contiguous() and seq.numel() == B * T * img and slab.numel() == T * B * img
+        poff = (C.c_int64 * ns)(*[((n * M) * T + t) * img for n, t in pairs])
+        doff = (C.c_int64 * ns)(*[(t * B + n * M) * img for n, t in pairs])
+        wgt, wsum = weights if weights is not None else (None, 0.0)
+        sp = _lib.NintEnsLossSpec()
+        sp.alpha = float(spec.alpha)
+        ow, ow_host, rows = spec.ow, spec.ow_host, None
+        if ow is not None:
+            nrows = ow.shape[0]
+            if every_step and nrows != T or not every_step and nrows != 1:
+                raise ValueError(f"ens_loss: {nrows} rows of output weights for {'a window of %d steps' % T if every_step else 'the last step'}")
+            rows = (C.c_int32 * ns)(*[t if every_step else 0 for _, t in pairs])
+            q64 = ow_host.astype("float64")
+            qsum = float(sum(float(q64[r].sum()) for r in rows))
+            sp.ow, sp.ow_row, sp.nrows = ow.data_ptr(), rows, nrows
+        else:
+            qsum = float(ns) * float(O)
+            sp.ow, sp.ow_row, sp.nrows = None, None, 0
+        sp.cnt = qsum * (wsum if weights is not None else float(Hc) * float(Wc))
+        nb = self.lib.nint_ens_loss_scratch_bytes(ns, M, O, H, W)
+        if scratch.dtype != torch.float64 or scratch.numel() * 8 < nb:
+            raise ValueError("ens_loss: the scratch is smaller than nint_ens_loss_scratch_bytes")
+        check(self.lib.nint_ens_loss(ptr(seq), poff, T * img, ptr(slab), doff, img, M, ptr(y), ptr(wgt), wsum, C.byref(sp), ptr(loss_out),
+                                     ptr(stats), ptr(ens_out), ptr(scratch), nb, ns, O, H, W, halo[0], halo[1], Hc, Wc, stream_ptr()),
+              "nint_ens_loss")
+
+    def ens_loss_scratch(self, N: int, M: int, O: int, H: int, W: int) -> int:
+        """f64 elements of nint_ens_loss's scratch for N samples (host arithmetic)"""
+        return self.lib.nint_ens_loss_scratch_bytes(N, M, O, H, W) // 8
 
     def backward(self, ws: Workspace, need_dx: bool, zero_state_grads: Sequence[int] = (),
                  dW_out: Optional[Sequence[torch.Tensor]] = None, db_out: Optional[Sequence[torch.Tensor]] = None, parts: int = 0,

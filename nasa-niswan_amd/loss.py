@@ -26,7 +26,7 @@ arithmetic.  Ways in: ``FusedTrainer(loss=LossSpec(...))``, ``CropLoss`` and ``t
 given the same one (``train.py`` builds it from the command line on every rank)."""
 from __future__ import annotations
 
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import ctypes as C
 import math
@@ -37,7 +37,7 @@ import torch
 from . import _lib
 from ._lib import NINT_LOSS_SCRATCH_FLOATS, NINT_LOSS_SPEC_SCRATCH_FLOATS, check, ptr, stream_ptr
 
-__all__ = ["grid_latitudes", "cos_latitude_weights", "validate_loss_weights", "CropMSEL1Loss", "LossSpec", "CropLoss"]
+__all__ = ["grid_latitudes", "cos_latitude_weights", "validate_loss_weights", "CropMSEL1Loss", "LossSpec", "CropLoss", "EnsembleLoss"]
 
 
 def grid_latitudes(H: int) -> np.ndarray:
@@ -273,3 +273,50 @@ class CropLoss(torch.nn.Module):
             raise _lib.NintError("CropLoss needs the uncropped prediction (B, O, H, W) on the MI355X (cuda)")
         wgt, wsum = (None, 0.0) if self._weights is None else self._weights.on(pred.device, y.shape[-2], y.shape[-1])
         return _CropLoss.apply(pred, y, wgt, wsum, self.spec.on(pred.device, pred.shape[1]), self.halo[0], self.halo[1])
+
+
+class EnsSpecOn(NamedTuple):
+    """EnsembleLoss.on: what SeqEngine.ens_loss takes -- alpha, the (rows, O) output-weight table on the device and its host copy"""
+    alpha: float
+    ow: Optional[torch.Tensor]
+    ow_host: Optional[np.ndarray]
+
+
+class EnsembleLoss:
+    """The training loss of an ensemble (``nint_ens_loss``): the almost-fair CRPS over the M member lanes of a
+    sample,
+
+        loss = mean_w( (1/M) sum_i |x_i - y|  -  (M - 1 + alpha) / (M^2 (M - 1)) sum_{i<j} |x_i - x_j| )
+
+    ``alpha = 1`` is the fair CRPS (unbiased in M), ``alpha = 0`` the plain one, in between the "almost fair" mix that keeps a
+    member from drifting freely.  ``output_weights`` (O,) and, with the sequence loss, ``step_weights`` (T,) weight the terms as
+    in ``LossSpec``: the device table is ``f32(step[t]) * f32(out[o])`` rounded to f32, one row per step.  Validated here on the
+    host (ValueError: alpha outside [0, 1] or not finite; weights negative, non-finite or all zero); the lengths at the first
+    call that knows O and T.  Not broadcast between data-parallel ranks."""
+
+    def __init__(self, alpha: float = 1.0, output_weights=None, step_weights=None):
+        self.alpha = float(alpha)
+        if not (math.isfinite(self.alpha) and 0.0 <= self.alpha <= 1.0):
+            raise ValueError(f"EnsembleLoss: alpha = {alpha!r} must lie in [0, 1]")
+        self.output_weights = None if output_weights is None else _weight_vector(output_weights, "output weights")
+        self.step_weights = None if step_weights is None else _weight_vector(step_weights, "step weights")
+        self._key, self._on = None, None
+
+    def host_table(self, O: int, T: Optional[int] = None) -> Optional[np.ndarray]:
+        """the f32 table the device reads: (1, O) for the last-step loss (``T`` None), (T, O) for the sequence loss; None when
+        no weight is set.  Checks the lengths (LossSpec.host_vector's rules)."""
+        vec = LossSpec(output_weights=self.output_weights, step_weights=self.step_weights).host_vector(O, T)
+        return None if vec is None else np.ascontiguousarray(vec.reshape(1 if T is None else T, O))
+
+    def on(self, device, O: int, T: Optional[int] = None) -> EnsSpecOn:
+        key = (str(device), int(O), None if T is None else int(T))
+        if self._key != key:
+            tab = self.host_table(int(O), None if T is None else int(T))
+            self._on = EnsSpecOn(self.alpha, None if tab is None else torch.from_numpy(tab).to(device), tab)
+            self._key = key
+        return self._on
+
+    def __repr__(self):
+        return (f"EnsembleLoss(alpha={self.alpha}, "
+                f"output_weights={None if self.output_weights is None else self.output_weights.tolist()}, "
+                f"step_weights={None if self.step_weights is None else self.step_weights.tolist()})")

@@ -8,7 +8,7 @@ once per epoch.  Added flags: --dtype, --levels, --grid, --synthetic-steps, --pa
 --static-channels, --sequence-loss, --test-skill, --lat-weighted-loss, --loss-weights, --clip-grad-norm,
 --skip-nonfinite-steps, --stateful, --bptt-segments, --accumulate-steps, --loss-mix, --huber-delta, --output-weights,
 --spinup-steps, --rollout-from, --sampling-prob, --sampling-ramp-epochs, --sampling-seed, --residual-head,
---tracer-noise, --noise-seed.
+--tracer-noise, --noise-seed, --train-ensemble, --train-feedback-noise, --crps-alpha.
 
 The data path is on the device too: by default every batch is written by ONE launch of the
 fuse / z-score / halo-pad kernel straight into the model's bf16 input slab (dataset.slab_batch);
@@ -173,6 +173,17 @@ def get_arguments(argv=None, MODEL='LSTM-00', SPECIES='bcb', LEARNING_RATE=1.0E-
                              "this standard deviation (z-score units) added, drawn on the device (FusedTrainer(input_noise=STD)); "
                              "validation and test see clean inputs.  A resumed run restarts the draw counter at 0")
     parser.add_argument("--noise-seed", type=int, default=0, help="the seed of --tracer-noise (the same on every rank)")
+    parser.add_argument("--train-ensemble", type=int, default=None, metavar="M",
+                        help="with --rollout-from: ENSEMBLE TRAINING -- every sample runs as M member lanes in [2, 64] that differ by "
+                             "the seeded noise alone (--tracer-noise on the input, --train-feedback-noise on every fed-back value), "
+                             "and the loss is the almost-fair CRPS over the members (FusedTrainer(ensemble_members=M)).  "
+                             "--batch-size counts samples: a step runs batch * M lanes.  --output-weights and --spinup-steps "
+                             "weight it; --loss-mix / --huber-delta are refused with it")
+    parser.add_argument("--train-feedback-noise", type=float, default=None, metavar="S",
+                        help="with --train-ensemble: std (z-score units) of the noise added to every fed-back value in training "
+                             "(default 0.05 when --tracer-noise is not given, else 0)")
+    parser.add_argument("--crps-alpha", type=float, default=None, metavar="A",
+                        help="with --train-ensemble: 1 the fair CRPS, 0 the plain one, between them the almost-fair mix (default 0.95)")
     parser.add_argument("--reset-optimizer", action="store_true",
                         help="with --use-checkpoint: load the weights of --restore-from only and start the optimizer afresh "
                              "(the fine-tuning entry point; without it an optimizer state of other param groups is an error)")
@@ -223,6 +234,28 @@ def get_arguments(argv=None, MODEL='LSTM-00', SPECIES='bcb', LEARNING_RATE=1.0E-
         parser.error("--sampling-ramp-epochs takes a number of epochs >= 0 and needs --sampling-prob")
     if args.rollout_spinup is None:
         args.rollout_spinup = args.sequence_length
+    if args.train_ensemble is None:
+        for name, v in (("--train-feedback-noise", args.train_feedback_noise), ("--crps-alpha", args.crps_alpha)):
+            if v is not None:
+                parser.error(f"{name} needs --train-ensemble")
+    else:
+        if args.rollout_from is None:
+            parser.error("--train-ensemble needs --rollout-from: the members differ through the closed loop")
+        if not 2 <= args.train_ensemble <= 64:
+            parser.error("--train-ensemble must be in [2, 64]")
+        if args.sampling_prob is not None:
+            parser.error("--train-ensemble is not combined with --sampling-prob")
+        if tuple(float(v) for v in args.loss_mix) != (1.0, 1.0, 0.0):
+            parser.error("--train-ensemble trains the CRPS: --loss-mix is refused with it")
+        if args.train_feedback_noise is None:
+            args.train_feedback_noise = 0.0 if args.tracer_noise else 0.05
+        if not 0.0 <= args.train_feedback_noise < float("inf"):
+            parser.error("--train-feedback-noise must be a finite standard deviation >= 0")
+        if args.train_feedback_noise == 0.0 and not args.tracer_noise:
+            parser.error("--train-feedback-noise and --tracer-noise are both 0: the members would be identical")
+        args.crps_alpha = 0.95 if args.crps_alpha is None else args.crps_alpha
+        if not 0.0 <= args.crps_alpha <= 1.0:
+            parser.error("--crps-alpha must lie in [0, 1]")
     ens = {"--ensemble-members": args.ensemble_members, "--ensemble-noise": args.ensemble_noise,
            "--ensemble-feedback-noise": args.ensemble_feedback_noise, "--ensemble-seed": args.ensemble_seed}
     given = [k for k, v in ens.items() if v is not None]
@@ -284,9 +317,9 @@ def build_loss_spec(args):
     """The loss.LossSpec of the loss flags, or None when none of them changes the reference's MSE + L1 (the trainer then runs
     the entries it has always run).  Built the same way on every rank: a spec is not broadcast."""
     mix = tuple(float(v) for v in args.loss_mix)
-    if mix == (1.0, 1.0, 0.0) and not args.output_weights and not args.spinup_steps:
+    if mix == (1.0, 1.0, 0.0) and not args.output_weights and not args.spinup_steps and not args.train_ensemble:
         return None
-    from nasa_niswan_amd.loss import LossSpec
+    from nasa_niswan_amd.loss import EnsembleLoss, LossSpec
     ow = None
     if args.output_weights:
         ow = np.load(args.output_weights)
@@ -297,6 +330,8 @@ def build_loss_spec(args):
         sw = np.ones(args.sequence_length, np.float32)
         sw[:args.spinup_steps] = 0.0
     try:
+        if args.train_ensemble:          # the same weights on the CRPS (FusedTrainer(ensemble_loss=...))
+            return EnsembleLoss(args.crps_alpha, output_weights=ow, step_weights=sw)
         return LossSpec(mix[0], mix[1], mix[2], args.huber_delta, output_weights=ow, step_weights=sw)
     except ValueError as e:
         raise SystemExit(f"loss flags: {e}")
@@ -358,7 +393,9 @@ def main(args):
     trainer = FusedTrainer(generator, lr=args.learning_rate, betas=tuple(args.betas), halo=halo,        # train.py:71
                            sequence_loss=args.sequence_loss, loss_weights=loss_weights,
                            max_grad_norm=args.clip_grad_norm, skip_nonfinite=args.skip_nonfinite_steps, stateful=args.stateful,
-                           bptt_segments=args.bptt_segments, accumulate_steps=args.accumulate_steps, loss=build_loss_spec(args),
+                           bptt_segments=args.bptt_segments, accumulate_steps=args.accumulate_steps,
+                           **(dict(ensemble_members=args.train_ensemble, feedback_noise=args.train_feedback_noise,
+                                   ensemble_loss=build_loss_spec(args)) if args.train_ensemble else dict(loss=build_loss_spec(args))),
                            freeze_layers=args.freeze_layers, weight_decay=args.weight_decay, layer_lr_scale=args.layer_lr_scale,
                            rollout_from=args.rollout_from, sampling_prob=args.sampling_prob, sampling_seed=args.sampling_seed,
                            input_noise=args.tracer_noise, noise_seed=args.noise_seed)
@@ -377,6 +414,9 @@ def main(args):
         load_checkpoint(f'{args.restore_from}/generator.pth.tar', generator, optimizer, args.learning_rate,
                         map_location=dev, reset_optimizer=args.reset_optimizer)             # train.py:77-78
     logger = {'MSELoss': [], 'r2_score': [], 'r2_score_val': [], 'first_step_loss': None, 'train_samples_per_s': []}
+    M_ens = args.train_ensemble or 0
+    if M_ens:
+        logger['crps'], logger['spread_skill'] = [], []
     for epoch in range(1, args.num_epochs + 1):                                              # train.py:82
         generator.train()
         trainer.reset_stats()
@@ -389,13 +429,21 @@ def main(args):
             trainer.reset_state()                                                            # every lane starts the record anew
         batches = sched if args.stateful else shard_indices(len(train_dataset), epoch, rank, world, args.batch_size)   # train.py:89
         for idx in batches:
-            X, y = get_batch(train_dataset, idx)                                             # preproc on device
+            if M_ens:                    # every index M times: lane n*M + m; the target of a sample is taken once
+                X, y = get_batch(train_dataset, np.repeat(np.asarray(idx), M_ens))
+                y = y[::M_ens].contiguous()
+            else:
+                X, y = get_batch(train_dataset, idx)                                         # preproc on device
             loss = trainer.step(X, y)                                                        # train.py:96-110
             n_epoch += len(idx)
             if logger['first_step_loss'] is None:
                 logger['first_step_loss'] = float(loss)
         loss_e, r2_e = trainer.epoch_stats()                                                 # one host read per epoch (syncs)
         gstats = trainer.grad_stats(reset=True) if guarded else None                         # (and one more with the guard on)
+        estats = trainer.ensemble_stats(reset=True) if M_ens else None                       # (before evaluate() adds to the stats)
+        if M_ens:
+            logger['crps'].append(estats['crps'])
+            logger['spread_skill'].append(estats['spread_skill'])
         logger['train_samples_per_s'].append(world * n_epoch / max(time.time() - t_epoch, 1e-9))   # data path included
         logger['MSELoss'].append(loss_e)                                                     # (MSE+L1, as in train.py:116)
         logger['r2_score'].append(r2_e)
@@ -408,7 +456,8 @@ def main(args):
         if rank == 0:
             print(f"Epoch: {epoch}, Loss: {logger['MSELoss'][-1]:.5f}, R2T: {logger['r2_score'][-1]:.5f}, "
                   f"R2V: {logger['r2_score_val'][-1]:.5f}"                                   # train.py:124
-                  + ("" if p_epoch is None else f", sampling prob: {p_epoch:.3f}"))
+                  + ("" if p_epoch is None else f", sampling prob: {p_epoch:.3f}")
+                  + ("" if not M_ens else f", crps: {estats['crps']:.5f}, spread/skill: {estats['spread_skill']:.3f}"))
             if guarded:
                 print(f"  grad norm: mean {gstats['mean_norm']:.5f}, max {gstats['max_norm']:.5f}, "
                       f"clipped {gstats['clipped']}, skipped {gstats['skipped']} of {gstats['calls']} steps")

@@ -41,6 +41,12 @@
                                                input slab of step() -- seeded Gaussian noise on the tracer channels, keyed by
                                                (noise_seed, the count of step() calls, rank * B + b, the step's place in the
                                                window), so the sweep and the recompute of a segment see the same input
+    [rollout_from = s, ensemble_members = M]-> ENSEMBLE TRAINING: the B lanes are N samples x M members (lane
+                                               n*M + m); the closed loop runs with seeded noise on every fed-back value
+                                               (nint_seq_fwd_stochastic, training stash on), nint_head_fwd_seq materialises
+                                               the members' predictions, nint_ens_loss forms the almost-fair CRPS over the
+                                               member lanes and writes every member's d loss / d pred into the roll-out slab,
+                                               and the roll-out backward runs as it stands (the noise is a constant)
     [accumulate_steps = k]                  -> k micro-batches add into the bucket (accumulate = 1 from the second on); the
                                                all-reduce and ONE Adam launch with grad_scale = 1/(k world) on the k-th
 
@@ -55,7 +61,7 @@ from . import _lib
 from ._lib import NINT_LOSS_SPEC_SCRATCH_FLOATS, NINT_LOSS_STATS
 from .engine import InputNoise
 from .model import ConvLSTM
-from .loss import DeviceWeights, LossSpec, crop_loss_launch
+from .loss import DeviceWeights, EnsembleLoss, LossSpec, crop_loss_launch
 from .optim import FlatParams, FusedAdam
 
 
@@ -79,7 +85,8 @@ class FusedTrainer:
                  bptt_segments: Optional[int] = None, accumulate_steps: int = 1, loss: Optional[LossSpec] = None,
                  freeze_layers: int = 0, weight_decay: float = 0.0, layer_lr_scale=None, rollout_from: Optional[int] = None,
                  sampling_prob: Optional[float] = None, sampling_seed: int = 0, input_noise=None, noise_channels=None,
-                 noise_seed: int = 0):
+                 noise_seed: int = 0, ensemble_members: Optional[int] = None, feedback_noise=None,
+                 ensemble_loss: Optional[EnsembleLoss] = None):
         # Input noise: every step() shows the model its input with N(0, input_noise^2) added to the noise
         # channels (None: the feedback channels), drawn on the device.  `draw` is the count of step() calls (micro-batches
         # included), `lane0` = rank * B with the SAME seed on every rank, `step0` a segment's start in its window.  evaluate()
@@ -114,6 +121,32 @@ class FusedTrainer:
         self.sampling_seed = int(sampling_seed)
         self._sampler, self._last_p = None, None
         self.last_mask = None   # (T, B) bool, CPU: what the last step() fed; None before the first step and without sampling
+        # Ensemble training: step() takes B = N * M lanes (lane n*M + m: the caller replicates the indices M
+        # times) and y of N samples; the members differ by the seeded noise alone -- on the input (``input_noise``, keyed as
+        # ever) and on every fed-back value (``feedback_noise``, the same seed and lanes, draw = 0x80000000 | the call count, so
+        # the two never share a key) -- and the loss is the almost-fair CRPS over the member lanes (``ensemble_loss``).  All
+        # lanes of a sample live on ONE rank: under data parallelism every rank holds whole ensembles and the bucket is reduced
+        # as ever; ens_out is not reduced.  Checked here: these refusals need no device.
+        self.ensemble_members, self._fb_noise, self._ens_spec = None, None, None
+        if ensemble_members is None:
+            if feedback_noise is not None or ensemble_loss is not None:
+                raise ValueError("feedback_noise / ensemble_loss need ensemble_members: they belong to the ensemble training step")
+        else:
+            if rollout_from is None:
+                raise ValueError("ensemble_members needs rollout_from: the members differ through the closed loop")
+            if isinstance(ensemble_members, bool) or int(ensemble_members) != ensemble_members or not 2 <= ensemble_members <= _lib.NINT_ENS_MAX_M:
+                raise ValueError(f"ensemble_members must be an integer in [2, {_lib.NINT_ENS_MAX_M}], got {ensemble_members!r}")
+            if loss is not None:
+                raise ValueError("ensemble_members trains the CRPS (ensemble_loss=EnsembleLoss(...)): a LossSpec (loss=) is refused with it")
+            if sampling_prob is not None:
+                raise ValueError("ensemble_members with sampling_prob is not supported: scheduled sampling over member lanes is not built")
+            if ensemble_loss is not None and not isinstance(ensemble_loss, EnsembleLoss):
+                raise TypeError("ensemble_loss must be a loss.EnsembleLoss or None")
+            self._ens_spec = ensemble_loss if ensemble_loss is not None else EnsembleLoss()
+            if self._ens_spec.step_weights is not None and not sequence_loss:
+                raise ValueError("step_weights need FusedTrainer(sequence_loss=True): the last-step loss has one step")
+            self.ensemble_members = int(ensemble_members)
+            self.set_feedback_noise(feedback_noise)
         dev = next(model.parameters()).device
         if dev.type != "cuda":
             raise _lib.NintError("FusedTrainer needs the model on the MI355X (cuda)")
@@ -160,6 +193,9 @@ class FusedTrainer:
         # [0..4] pooled: sum d^2, sum |d|, sum y, sum y^2, n; [5..7] per call: sum loss, sum r2_score, calls
         self.stats = torch.zeros(NINT_LOSS_STATS, dtype=torch.float64, device=dev)
         self._dpred = None
+        # ensemble training: nint_ens_loss's four sums (SA, SD, SV, cnt), accumulated like `stats`, and its scratch
+        self.ens_out = torch.zeros(_lib.NINT_ENS_LOSS_OUT, dtype=torch.float64, device=dev) if self.ensemble_members else None
+        self._ens_scratch = None
         self._probe = (None, 0)
         self._marks = None      # diagnostic: a list that step() fills with HIP events (start, after forward, after head/loss, after BPTT, end)
         import torch.distributed as dist
@@ -337,6 +373,29 @@ class FusedTrainer:
         rank = self.dist.get_rank(self.pg) if self.distributed else 0
         return dict(noise=InputNoise(self._noise.std, self._noise.channels, self._noise.seed, draw, step0, rank * B))
 
+    def set_feedback_noise(self, std):
+        """ensemble training: the noise level on the fed-back value for the steps to come (a curriculum sets it beside
+        set_input_noise): a float or one per output, in the units of the stored input.  ValueError without
+        ``ensemble_members``, for a negative or non-finite value, and where it leaves both noises zero -- identical members
+        make the pair term of the CRPS vanish."""
+        if self.ensemble_members is None:
+            raise ValueError("set_feedback_noise needs FusedTrainer(ensemble_members=M)")
+        nz = None if std is None else InputNoise(std, None, self.noise_seed)
+        if nz is not None:
+            nz.span(self._noise_model[1] or 0, self._noise_model[1])       # (one value or O values)
+        if (nz is None or not nz.active) and self._noise is None:
+            raise ValueError("ensemble_members needs noise: input_noise and feedback_noise are both zero, so the members would "
+                             "be identical and the CRPS's pair term would vanish")
+        self._fb_noise = nz if nz is not None and nz.active else None
+
+    def _fb_noise_kw(self, draw: int, B: int) -> dict:
+        """the ``feedback_noise`` argument of the ensemble step's forward pass: the input noise's seed and lanes, and a draw
+        with the top bit set, so that no (seed, draw) key is shared with the input noise of any step"""
+        if self._fb_noise is None:
+            return {}
+        rank = self.dist.get_rank(self.pg) if self.distributed else 0
+        return dict(feedback_noise=InputNoise(self._fb_noise.std, None, self._fb_noise.seed, 0x80000000 | (draw & 0x7fffffff), 0, rank * B))
+
     def set_sampling_prob(self, p: Optional[float]):
         """the coin's bias for the steps to come (a curriculum sets it once per epoch); None: no sampling"""
         if p is not None:
@@ -442,6 +501,8 @@ class FusedTrainer:
         dataset.SlabBatch.  y: (B,[O,]Hc,Wc), or (B,T,[O,]Hc,Wc) with ``sequence_loss``.
         ``reset`` (stateful trainers only): True, or one boolean per lane -- those lanes start this chunk from the zero state.
         With ``accumulate_steps = k`` the optimizer steps on every k-th call, on the mean gradient of the k calls."""
+        if self.ensemble_members is not None:
+            return self._ens_step(X, y, reset)
         m = self.model
         eng = m._engine(self.device)
         wts, spec, B, T, H, W, O, Hc, Wc, yv = self._call_facts(X, y)
@@ -482,6 +543,77 @@ class FusedTrainer:
             pending, n0 = self._bptt(eng, ws, acc, last, slab)
             mark()
         return self._finish(last, pending, n0)
+
+    def _ens_step(self, X, y, reset=None) -> torch.Tensor:
+        """step() of an ensemble trainer.  X carries B = N * M lanes, lane n*M + m (the caller replicates the
+        indices, as rollout_ensemble does); y is (N, [T,] [O,] Hc, Wc), never replicated.  One step, no host sync: the noisy
+        closed-loop training forward, head_forward_seq, nint_ens_loss into the roll-out slab (the last step alone without
+        ``sequence_loss``, the other images zeroed), the cotangents of the unfed steps, the roll-out BPTT and the optimizer.
+        All lanes of a sample live on one rank."""
+        m, M, sq = self.model, self.ensemble_members, self.sequence_loss
+        B, T, _, H, W = X.shape
+        O, Hc, Wc = m.conv.weight.shape[0], y.shape[-2], y.shape[-1]
+        if B % M:
+            raise ValueError(f"ensemble step: {B} lanes do not hold whole ensembles of {M} members (lane n*M + m)")
+        N = B // M
+        if y.shape[0] != N or y.numel() != N * (T if sq else 1) * O * Hc * Wc:
+            raise ValueError(f"ensemble step: the target must be ({N}, {'T, ' if sq else ''}[O,] Hc, Wc) for {B} lanes of {M} members -- "
+                             f"one per sample, never replicated -- got {tuple(y.shape)}")
+        if reset is not None:
+            raise ValueError("step(reset=...) needs FusedTrainer(stateful=True)")
+        feed = self._draw(T, B)
+        if feed is None:
+            raise ValueError(f"ensemble step: rollout_from = {self.rollout_from} lies beyond the window of {T} steps: nothing is fed back")
+        eng = m._engine(self.device)
+        wts = self._loss_weights(Hc, Wc)
+        spec = self._ens_spec.on(self.device, O, T if sq else None)
+        yv = y.detach().float().contiguous()
+        k = self.accumulate_steps
+        acc, last = self._micro > 0, self._micro == k - 1
+        draw, self._draws = self._draws, self._draws + 1
+        need = eng.ens_loss_scratch(N * (T if sq else 1), M, O, H, W)
+        if self._ens_scratch is None or self._ens_scratch.numel() < need:
+            self._ens_scratch = torch.empty(need, dtype=torch.float64, device=self.device)
+        mark = self._mark
+        with eng.window(B, T, H, W, True, False, 0) as ws:
+            pb, pm = self._probe
+            ws.seq.probe = pb.data_ptr() if pb is not None else None
+            ws.seq.probe_mask, ws.seq.probe_slots = pm, (pb.numel() // 2 if pb is not None else 0)
+            mark()
+            m._pack_weights(eng)
+            eng.forward(ws, X, feedback=(m.conv.weight, m.conv.bias, feed), feedback_grad=True, **self._res_kw(),
+                        **self._noise_kw(draw, B), **self._fb_noise_kw(draw, B))
+            mark()
+            slab = ws.rollout_dpred(eng, O)
+            seq = eng.head_forward_seq(ws, m.conv.weight, m.conv.bias)
+            if not sq:
+                slab[:(T - 1) * B].zero_()
+            eng.ens_loss(ws, seq, yv, slab, M, spec, wts, self._ens_scratch, self.scratch, self.stats, self.ens_out, self.halo,
+                         Hc, Wc, every_step=sq)
+            eng.rollout_cotangents(ws, m.conv.weight, slab_filled=True, dh_written=False)
+            mark()
+            pending, n0 = self._bptt(eng, ws, acc, last, slab)
+            mark()
+        return self._finish(last, pending, n0)
+
+    def ensemble_stats(self, reset: bool = False) -> dict:
+        """One device->host read: from nint_ens_loss's sums since the last reset -- ``crps`` (the mean of the trained score),
+        ``rmse_mean`` (of the ensemble mean), ``spread`` (sqrt of the mean unbiased member variance) and ``spread_skill``
+        (with the sqrt((M + 1) / M) factor of inference.lead_time_table).  Not reduced between ranks."""
+        if self.ens_out is None:
+            raise ValueError("ensemble_stats needs FusedTrainer(ensemble_members=M)")
+        v = torch.cat([self.ens_out, self.stats[:5]]).cpu().tolist()
+        if reset:
+            self.ens_out.zero_()
+        SA, SD, SV, cnt, S2, n = v[0], v[1], v[2], v[3], v[4], v[8]
+        M = float(self.ensemble_members)
+        if not cnt > 0:
+            return dict(crps=float("nan"), rmse_mean=float("nan"), spread=float("nan"), spread_skill=float("nan"))
+        kp = (M - 1.0 + self._ens_spec.alpha) / (M * M * (M - 1.0))
+        rmse = (S2 / n) ** 0.5 if n > 0 else float("nan")
+        spread = (SV / (M * M * (M - 1.0)) / cnt) ** 0.5
+        return dict(crps=(SA / M - kp * SD) / cnt, rmse_mean=rmse, spread=spread,
+                    spread_skill=((M + 1.0) / M) ** 0.5 * spread / rmse if rmse > 0 else float("nan"))
 
     def _finish(self, last: bool, pending=None, n0: int = 0) -> torch.Tensor:
         """The end of every call: on the last one of a group the all-reduce of the bucket -- ONE, or with `pending` (the
