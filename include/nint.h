@@ -997,6 +997,50 @@ int nint_ens_loss(const float* pred, const int64_t* pred_off /*host, N*/, int64_
                   const nint_ens_loss_spec* spec, float* loss_out, double* stats, double* ens_out, double* scratch,
                   size_t scratch_bytes, int N, int O, int H, int W, int oy, int ox, int Hc, int Wc, void* stream);
 
+/* ---- evaluation: zonal power spectra --------------------------------------------------------------------- */
+/* The along-longitude power spectrum of M member predictions and of the target, their cross spectrum and the spectrum of the
+ * member sum, per slot (lead time), output and wavenumber, in one pass over the members where they lie.  pred, sample_off,
+ * member_stride, y (N,O,Hc,Wc), the crop window, slot, nslots and row_w are nint_ens_accum's; M lies in [1, NINT_ENS_MAX_M]
+ * (M = 1: a deterministic roll-out).  K = Wc / 2 + 1 wavenumbers (integer division: an odd width has no Nyquist line).
+ * The transform uses the CALLER'S table tw [Wc][2] f64 on the device -- the kernel computes no sine: for a crop row f[0..Wc)
+ * converted to f64,   F_k = sum_x f[x] * (tw[j][0] + i tw[j][1]),  j = (k x) mod Wc,  0 <= k < K.
+ * nint_spec_twiddles (host arithmetic only) writes tw[j] = (cos(2 pi j / Wc), -sin(2 pi j / Wc)) into a HOST array, every
+ * component within 1 ulp, exactly 0 and +-1 at whole quarter turns, tw[Wc - j] = conj(tw[j]) bit for bit, no negative zero;
+ * the caller uploads it once.  Any other table makes the kernel that other linear map (an integer table: exact integers).
+ * With Y_k the transform of target row r, P_{i,k} that of member i, S_k = sum_i P_{i,k} and w = row_w[r] (1 without a table),
+ * every row of every sample with slot s >= 0 adds to
+ *   spec [nslots][NINT_SPEC_PLANES][O][K] f64, ACCUMULATED, entry (s, plane, o, k):
+ *     YY: w |Y_k|^2     PP: w sum_i |P_{i,k}|^2     CR: w Re(S_k conj Y_k)     CI: w Im(S_k conj Y_k)     SS: w |S_k|^2
+ * No division and no normalisation (inference.spectrum_from_sums has them).  The error power follows: sum_i |P_i - Y|^2 =
+ * PP + M YY - 2 CR; of the ensemble mean: SS / M^2 + YY - 2 CR / M.  A NaN goes where the arithmetic takes it (masking is the
+ * caller's: slot = -1, such a sample adds nothing and is not read).
+ * THE ORDER, a function of (M, O, Hc, Wc) only; f64 throughout, contraction off except where a fused multiply-add is named:
+ *   F_k: re = fma(f[x], tw[j][0], re), im = fma(f[x], tw[j][1], im), x = 0 .. Wc-1 ascending from 0.0 -- Wc roundings each;
+ *   S = (0.0 + P_0) + P_1 + ..., pp = (0.0 + (Pr_0^2 + Pi_0^2)) + ..., i ascending (every product and sum one operation);
+ *   the row's terms  w * (Yr Yr + Yi Yi),  w * pp,  w * (Sr Yr + Si Yi),  w * (Si Yr - Sr Yi),  w * (Sr Sr + Si Si);
+ *   rows: with Kt = min(K, 256) and R = min(Hc, max(1, 256 / Kt)), the rows r = rl, rl + R, rl + 2R, ... are added in that
+ *   order from 0.0 for each rl < R, then the R sums in ascending rl: the value of (sample, output, plane, k), kept in scratch;
+ *   samples: one owner per (slot, plane, o, k) adds the call's samples of the slot to the stored value in ascending n.
+ *   So an entry carries at most 2 Wc + 2 M + 3 roundings inside a row term, ceil(Hc / R) + R - 1 <= Hc additions over the
+ *   rows and one per sample.  No floating-point atomics: spec is bit-identical run to run, under any split of the samples
+ *   into consecutive calls, and for N beyond NINT_SPEC_MAX_N (run in pieces).
+ *   scratch   nint_spec_scratch_bytes(N, M, O, Hc, Wc) = min(N, NINT_SPEC_MAX_N) * O * NINT_SPEC_PLANES * K * 8 bytes, 8-byte
+ *             aligned.  Memory contract: exactly that many suffice, no store goes outside spec and scratch,
+ *             and no result depends on a byte the library did not write, nor on a pixel outside the crop.
+ * Before any launch -- NINT_E_ARG: a NULL pred / sample_off / y / tw / spec / scratch, M outside [1, NINT_ENS_MAX_M], N, O or
+ * nslots < 1, a negative offset or stride, a slot outside [-1, nslots), a crop outside the grid, Wc < 2, a scratch that is too
+ * small; NINT_E_SHAPE: Wc > NINT_SPEC_MAX_W; then NINT_E_ALIGN: spec / scratch / row_w / tw not 8-byte, pred / y not 4-byte
+ * aligned.  nint_spec_twiddles: NINT_E_ARG for a NULL table or Wc < 2, NINT_E_SHAPE for Wc > NINT_SPEC_MAX_W. */
+#define NINT_SPEC_PLANES 5    /* per (slot, output, wavenumber): YY, PP, CR, CI, SS */
+#define NINT_SPEC_MAX_W  512  /* crop width; NINT_E_SHAPE beyond */
+#define NINT_SPEC_MAX_N  64   /* samples per launch; larger N split internally, as NINT_ENS_MAX_N is */
+size_t nint_spec_scratch_bytes(int N, int M, int O, int Hc, int Wc);      /* host arithmetic only */
+int nint_spec_twiddles(int Wc, double* tw /*HOST [Wc][2]*/);              /* host arithmetic only */
+int nint_spec_accum(const float* pred, const int64_t* sample_off /*host, N*/, int64_t member_stride, int M, const float* y,
+                    const int32_t* slot /*host, N, or NULL = all 0*/, int nslots, const double* row_w /*device [Hc] or NULL = 1*/,
+                    const double* tw /*device [Wc][2]*/, double* spec, double* scratch, size_t scratch_bytes, int N, int O, int H,
+                    int W, int oy, int ox, int Hc, int Wc, void* stream);
+
 /* ---- optimiser (train.py:71,110) ---------------------------------------------------------------- */
 /* torch.optim.Adam (eps 1e-8, no weight decay / amsgrad) on one flat f32 buffer.
  * grad_scale multiplies g first (1/world_size after the RCCL all-reduce). step is 1-based. */

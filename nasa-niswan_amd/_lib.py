@@ -20,6 +20,7 @@ NINT_LOSS_STATS = 8
 NINT_SKILL_PIX, NINT_SKILL_SAMPLE, NINT_SKILL_MAX_N = 5, 8, 64
 NINT_ENS_PIX, NINT_ENS_SAMPLE, NINT_ENS_MAX_N, NINT_ENS_MAX_M = 7, 8, 64, 64
 NINT_ENS_LOSS_OUT = 4     # nint_ens_loss's ens_out: SA, SD, SV, cnt
+NINT_SPEC_PLANES, NINT_SPEC_MAX_W, NINT_SPEC_MAX_N = 5, 512, 64     # nint_spec_accum: YY, PP, CR, CI, SS per (slot, output, k)
 NINT_GRAD_NORM_BLOCKS = 256
 NINT_OPT_STATE = 16
 NINT_MAX_OPT_GROUPS = 2 * NINT_MAX_LAYERS + 2
@@ -217,6 +218,10 @@ SIGNATURES = {
     "nint_ens_loss_scratch_bytes": (_SZ, [_I, _I, _I, _I, _I]),
     "nint_ens_loss": (_I, [vp, C.POINTER(C.c_int64), C.c_int64, vp, C.POINTER(C.c_int64), C.c_int64, _I, vp, vp, _D,
                            C.POINTER(NintEnsLossSpec), vp, vp, vp, vp, _SZ, _I, _I, _I, _I, _I, _I, _I, _I, vp]),
+    "nint_spec_scratch_bytes": (_SZ, [_I, _I, _I, _I, _I]),
+    "nint_spec_twiddles": (_I, [_I, C.POINTER(C.c_double)]),
+    "nint_spec_accum": (_I, [vp, C.POINTER(C.c_int64), C.c_int64, _I, vp, C.POINTER(C.c_int32), _I, vp, vp, vp, vp, _SZ,
+                             _I, _I, _I, _I, _I, _I, _I, _I, vp]),
     "nint_adam_flat": (_I, [vp, vp, vp, vp, _SZ, C.c_double, C.c_double, C.c_double, C.c_double, _I, _F, vp]),
     "nint_grad_norm_scratch_bytes": (_SZ, []),
     "nint_grad_norm_flat": (_I, [vp, _SZ, _F, vp, vp, _SZ, vp]),

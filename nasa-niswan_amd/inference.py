@@ -13,7 +13,7 @@ from typing import Callable, Optional, Sequence, Tuple, Union
 import numpy as np
 import torch
 
-from ._lib import NINT_ENS_MAX_M, NINT_ENS_PIX, NINT_ENS_SAMPLE, NINT_SKILL_PIX, NINT_SKILL_SAMPLE
+from ._lib import NINT_ENS_MAX_M, NINT_ENS_PIX, NINT_ENS_SAMPLE, NINT_SKILL_PIX, NINT_SKILL_SAMPLE, NINT_SPEC_MAX_W, NINT_SPEC_PLANES
 
 
 @torch.no_grad()
@@ -381,7 +381,7 @@ def _step_targets(dataset, dv, t0s, T):
 # ------------------------------------------------------------------------------ closed-loop roll-out skill by lead time
 @torch.no_grad()
 def rollout_skill(net, dataset, starts: Sequence[int], horizon: int, spinup: int, batch_size: int = 8, lat=None,
-                  halo: Optional[Tuple[int, int]] = None) -> SkillAccumulator:
+                  halo: Optional[Tuple[int, int]] = None, spectrum: Optional["SpectrumAccumulator"] = None) -> SkillAccumulator:
     """Skill of the free-running model by LEAD TIME.  From every record step in `starts` a window of
     `spinup + horizon` steps runs closed loop from step `spinup` (``ConvLSTM(feedback=True)``; the first `spinup` steps see
     the dataset's input, the rest the model's own prediction in the feedback channels).  The prediction made `j` steps into
@@ -390,7 +390,9 @@ def rollout_skill(net, dataset, starts: Sequence[int], horizon: int, spinup: int
     ``acc.report(dataset.y_mean, dataset.y_std, slots=[j])`` is the skill at lead time j, 0 <= j < horizon.
 
     `starts`: record steps (not dataset indices), each with start + spinup + horizon <= the record's length, and >= 1 for a
-    ``tracer_input`` dataset.  `halo`: the crop's offset inside the model grid (None: centred)."""
+    ``tracer_input`` dataset.  `halo`: the crop's offset inside the model grid (None: centred).
+    `spectrum`: a SpectrumAccumulator(O, Hc, Wc, M=1, nslots=horizon, halo=halo) that is filled from the same per-step head
+    output, slot j = lead time j; a mismatch is a ValueError before any device work.  None: nothing changes."""
     from .dataset import SlabBatch
     if not getattr(net, "feedback", False):
         raise ValueError("rollout_skill needs a ConvLSTM built with feedback=True")
@@ -403,6 +405,8 @@ def rollout_skill(net, dataset, starts: Sequence[int], horizon: int, spinup: int
     lo = 1 if getattr(dataset, "tracer_input", False) else 0
     if not starts or min(starts) < lo or max(starts) + T > n_steps:
         raise ValueError(f"rollout_skill: every start must lie in [{lo}, {n_steps - T}] for windows of {T} steps in a record of {n_steps}")
+    if spectrum is not None:
+        spectrum._check_rollout("rollout_skill", net.conv.weight.shape[0], dataset.grid[0], dataset.grid[1], 1, horizon, halo)
     net.eval()
     dev = next(net.parameters()).device
     eng = net._engine(dev)
@@ -425,6 +429,8 @@ def rollout_skill(net, dataset, starts: Sequence[int], horizon: int, spinup: int
         free = seq[:, spinup:].reshape(B * horizon, O, H, W)
         slots = [j for _ in range(B) for j in range(horizon)]
         acc.update_from_pred(free, y[:, spinup:].reshape(B * horizon, O, Hc, Wc), (oy, ox), slots)
+        if spectrum is not None:
+            spectrum.update_from_pred(free, y[:, spinup:].reshape(B * horizon, O, Hc, Wc), (oy, ox), slots)
     return acc
 
 
@@ -633,11 +639,213 @@ def lead_time_table(acc: EnsembleAccumulator) -> np.ndarray:
     return out
 
 
+# ------------------------------------------------------------------------------ zonal power spectra from device-side sums
+@dataclass
+class SpectrumReport:
+    """Zonal (along-longitude) power spectra from the sums of nint_spec_accum, z-score units, per output and
+    wavenumber: (O, K) arrays, K = Wc // 2 + 1.  The densities are one-sided (the factor 2 for 0 < k < Wc / 2) and normalised
+    by Wc^2, the sum of the row weights and the sample count, so a density summed over k is the weighted mean square of the
+    field (Parseval).  nan where nothing was folded in."""
+    wavenumber: np.ndarray               # (K,) 0 .. Wc // 2
+    power_target: np.ndarray             # of the target
+    power_member: np.ndarray             # mean over the members of each member's power
+    power_mean: np.ndarray               # of the ensemble mean (the prediction for M = 1)
+    power_error: np.ndarray              # of (ensemble mean - target)
+    ratio_member: np.ndarray             # power_member / power_target: 1 where the members are as sharp as the analysis
+    ratio_mean: np.ndarray               # power_mean / power_target: below ratio_member where the members disagree
+    coherence: np.ndarray                # |sum S conj Y|^2 / (sum |S|^2 sum |Y|^2), in [0, 1]
+    members: int
+    width: int
+    count: float                         # samples behind the figures
+
+    def arrays(self) -> dict:
+        return {f.name: np.asarray(getattr(self, f.name)) for f in fields(self)}
+
+
+def _one_sided(Wc: int) -> np.ndarray:
+    """the weight of each of the K = Wc // 2 + 1 lines in a one-sided spectrum: 1 for k = 0 and the Nyquist line, else 2"""
+    c = np.full(Wc // 2 + 1, 2.0)
+    c[0] = 1.0
+    if Wc % 2 == 0:
+        c[-1] = 1.0
+    return c
+
+
+def spectrum_from_sums(spec, counts, M: int, Wc: int, row_w_sum: float, slots: Optional[Sequence[int]] = None) -> SpectrumReport:
+    """The sums of nint_spec_accum -> a SpectrumReport.  Pure numpy f64; needs no GPU.
+
+    spec (nslots, 5, O, K): per slot, output and wavenumber the sums over samples and rows of w |Y|^2 (YY), w sum_i |P_i|^2
+    (PP), w Re(S conj Y) (CR), w Im(S conj Y) (CI), w |S|^2 (SS) with S = sum_i P_i; counts (nslots): samples per slot;
+    row_w_sum: the sum of the row weights (Hc without a table).  With c_k the one-sided factor and
+    Z = Wc^2 * row_w_sum * n:  power_target = c YY / Z, power_member = c PP / M / Z, power_mean = c SS / M^2 / Z,
+    power_error = c (SS / M^2 + YY - 2 CR / M) / Z, coherence = (CR^2 + CI^2) / (SS YY).  `slots`: the union of slots (None: all)."""
+    spec, counts = np.asarray(spec, np.float64), np.asarray(counts, np.float64)
+    M, Wc = int(M), int(Wc)
+    if not 1 <= M <= NINT_ENS_MAX_M:
+        raise ValueError(f"spectrum_from_sums: members must lie in [1, {NINT_ENS_MAX_M}], got {M}")
+    if Wc < 2:
+        raise ValueError(f"spectrum_from_sums: the width must be >= 2, got {Wc}")
+    K = Wc // 2 + 1
+    if spec.ndim != 4 or spec.shape[1] != NINT_SPEC_PLANES or spec.shape[3] != K or counts.shape != (spec.shape[0],):
+        raise ValueError(f"spectrum_from_sums: spec must be (nslots, {NINT_SPEC_PLANES}, O, {K}) and counts (nslots,), got "
+                         f"{spec.shape} and {counts.shape}")
+    sel = list(range(spec.shape[0])) if slots is None else [int(v) for v in slots]
+    yy, pp, cr, ci, ss = spec[sel].sum(axis=0)
+    n = float(counts[sel].sum())
+    with np.errstate(divide="ignore", invalid="ignore"):
+        norm = _one_sided(Wc) / (float(Wc) * Wc * float(row_w_sum) * n) if n > 0 else np.full(K, np.nan)
+        pt, pm, pe = yy * norm, pp / M * norm, ss / (M * M) * norm
+        err = (ss / (M * M) + yy - 2.0 * cr / M) * norm
+        coh = (cr * cr + ci * ci) / (ss * yy)
+        return SpectrumReport(wavenumber=np.arange(K), power_target=pt, power_member=pm, power_mean=pe, power_error=err,
+                              ratio_member=pm / pt, ratio_mean=pe / pt, coherence=coh, members=M, width=Wc, count=n)
+
+
+class SpectrumAccumulator:
+    """Device-side accumulator of zonal power spectra (nint_spec_accum): `spec` (nslots, 5, O, K) f64, the uploaded twiddle
+    table (nint_spec_twiddles), `row_w` = cos(lat) and the kernel's scratch.  M = 1: a deterministic prediction.  `lat`,
+    `halo`: as SkillAccumulator's.  The sums are additive: a data-parallel reduction adds the ranks' `spec` and `counts`."""
+
+    def __init__(self, O: int, Hc: int, Wc: int, M: int = 1, nslots: int = 1, lat=None, device="cuda",
+                 halo: Optional[Tuple[int, int]] = None):
+        from . import _lib
+        self.O, self.Hc, self.Wc, self.M, self.nslots = int(O), int(Hc), int(Wc), int(M), int(nslots)
+        if self.nslots < 1:
+            raise ValueError("nslots must be >= 1")
+        if self.O < 1 or self.Hc < 1:
+            raise ValueError(f"SpectrumAccumulator: O and Hc must be >= 1, got {(self.O, self.Hc)}")
+        if not 1 <= self.M <= NINT_ENS_MAX_M:
+            raise ValueError(f"SpectrumAccumulator: members must lie in [1, {NINT_ENS_MAX_M}], got {self.M}")
+        if not 2 <= self.Wc <= NINT_SPEC_MAX_W:
+            raise ValueError(f"SpectrumAccumulator: the crop width must lie in [2, {NINT_SPEC_MAX_W}], got {self.Wc}")
+        self.K = self.Wc // 2 + 1
+        self.row_w_host = None
+        if lat is not None:
+            lat = np.asarray(lat, dtype=np.float64)
+            if lat.shape != (self.Hc,):
+                raise ValueError(f"lat: expected {self.Hc} latitudes, got {lat.shape}")
+            self.row_w_host = np.cos(np.deg2rad(lat))
+        self.halo = None if halo is None else (int(halo[0]), int(halo[1]))
+        self.lib = _lib.load()
+        self.tw_host = np.empty((self.Wc, 2), dtype=np.float64)
+        _lib.check(self.lib.nint_spec_twiddles(self.Wc, self.tw_host.ctypes.data_as(C.POINTER(C.c_double))), "nint_spec_twiddles")
+        self.device = torch.device(device)
+        self.tw = torch.from_numpy(self.tw_host).to(self.device)
+        self.row_w = None if self.row_w_host is None else torch.from_numpy(self.row_w_host).to(self.device)
+        self.spec = torch.zeros(self.nslots, NINT_SPEC_PLANES, self.O, self.K, dtype=torch.float64, device=self.device)
+        self._counts = np.zeros(self.nslots, dtype=np.float64)
+        self._scratch = None
+
+    @property
+    def counts(self) -> torch.Tensor:
+        return torch.from_numpy(self._counts.copy()).to(self.device)
+
+    @property
+    def row_w_sum(self) -> float:
+        return float(self.Hc) if self.row_w_host is None else float(self.row_w_host.sum())
+
+    def scratch_for(self, N: int) -> torch.Tensor:
+        need = self.lib.nint_spec_scratch_bytes(int(N), self.M, self.O, self.Hc, self.Wc) // 8
+        if self._scratch is None or self._scratch.numel() < need:
+            self._scratch = torch.empty(need, dtype=torch.float64, device=self.device)
+        return self._scratch
+
+    def update(self, pred: torch.Tensor, sample_off: Sequence[int], member_stride: int, y: torch.Tensor, slots=None,
+               halo: Optional[Tuple[int, int]] = None):
+        """Fold one batch in.  `pred`, `sample_off`, `member_stride`, `y`, `slots`: EnsembleAccumulator.update's -- member i of
+        sample n is the (O, H, W) image at element sample_off[n] + i * member_stride of the contiguous f32 tensor `pred`,
+        read in place.  `halo`: the crop's offset for this call (None: the accumulator's)."""
+        from ._lib import check, ptr, stream_ptr
+        if pred.dtype != torch.float32 or not pred.is_contiguous() or pred.dim() < 3 or pred.shape[-3] != self.O:
+            raise ValueError(f"SpectrumAccumulator.update: pred must be a contiguous f32 tensor (..., {self.O}, H, W)")
+        H, W = int(pred.shape[-2]), int(pred.shape[-1])
+        off = [int(v) for v in sample_off]
+        N, stride = len(off), int(member_stride)
+        if N < 1 or stride < 0 or min(off) < 0 or max(off) + (self.M - 1) * stride + self.O * H * W > pred.numel():
+            raise ValueError("SpectrumAccumulator.update: a member image lies outside pred")
+        at = self.halo if halo is None else (int(halo[0]), int(halo[1]))
+        oy, ox = ((H - self.Hc) // 2, (W - self.Wc) // 2) if at is None else at
+        yv = y.detach().float().contiguous()
+        if yv.numel() != N * self.O * self.Hc * self.Wc:
+            raise ValueError("SpectrumAccumulator.update: target must be (N, O, Hc, Wc)")
+        sl = [0] * N if slots is None else [int(v) for v in slots]
+        if len(sl) != N or any(v < -1 or v >= self.nslots for v in sl):
+            raise ValueError(f"slots: {N} values in [-1, {self.nslots}) expected")
+        scratch = self.scratch_for(N)
+        check(self.lib.nint_spec_accum(ptr(pred), (C.c_int64 * N)(*off), stride, self.M, ptr(yv), (C.c_int32 * N)(*sl), self.nslots,
+                                       ptr(self.row_w), ptr(self.tw), ptr(self.spec), ptr(scratch), scratch.numel() * 8, N, self.O,
+                                       H, W, int(oy), int(ox), self.Hc, self.Wc, stream_ptr()), "nint_spec_accum")
+        for v in sl:
+            if v >= 0:
+                self._counts[v] += 1.0
+
+    def update_from_pred(self, pred: torch.Tensor, y: torch.Tensor, halo: Optional[Tuple[int, int]] = None, slots=None):
+        """One batch of deterministic predictions (N, O, H, W) that are already in memory (M = 1)."""
+        if self.M != 1:
+            raise ValueError(f"SpectrumAccumulator.update_from_pred is for M = 1; this accumulator has {self.M} members")
+        pv = pred.detach().float().contiguous()
+        if pv.dim() != 4 or pv.shape[1] != self.O:
+            raise ValueError(f"SpectrumAccumulator.update_from_pred: pred must be (N, {self.O}, H, W)")
+        img = int(pv.shape[1] * pv.shape[2] * pv.shape[3])
+        self.update(pv, [n * img for n in range(pv.shape[0])], 0, y, slots, halo)
+
+    def sums(self):
+        """(spec, counts) as numpy: ONE device-to-host read"""
+        return self.spec.cpu().numpy(), self._counts.copy()
+
+    def report(self, slots: Optional[Sequence[int]] = None) -> SpectrumReport:
+        spec, counts = self.sums()
+        return spectrum_from_sums(spec, counts, self.M, self.Wc, self.row_w_sum, slots)
+
+    def _check_rollout(self, who: str, O: int, Hc: int, Wc: int, M: int, horizon: int, halo):
+        """a roll-out fills this accumulator only if its shapes are the roll-out's; refused before any device work"""
+        want = (int(O), int(Hc), int(Wc), int(M), int(horizon), None if halo is None else (int(halo[0]), int(halo[1])))
+        have = (self.O, self.Hc, self.Wc, self.M, self.nslots, self.halo)
+        if want != have:
+            raise ValueError(f"{who}: spectrum must be a SpectrumAccumulator with (O, Hc, Wc, M, nslots, halo) = {want}, got {have}")
+
+
+LEAD_SPECTRUM_COLUMNS = ("small_scale_ratio_member", "small_scale_ratio_mean", "coherence_cut", "error_small_scale_frac")
+
+
+def lead_spectrum_from_sums(spec, counts, M: int, Wc: int, kmin: Optional[int] = None) -> np.ndarray:
+    """lead_time_spectrum on the raw sums (numpy f64, no device): (nslots, 4) in the order of LEAD_SPECTRUM_COLUMNS"""
+    spec, counts = np.asarray(spec, np.float64), np.asarray(counts, np.float64)
+    M, Wc = int(M), int(Wc)
+    K = Wc // 2 + 1
+    kmin = Wc // 8 if kmin is None else int(kmin)
+    if not 0 <= kmin < K:
+        raise ValueError(f"lead_time_spectrum: kmin must lie in [0, {K}), got {kmin}")
+    c = _one_sided(Wc)
+    out = np.full((spec.shape[0], len(LEAD_SPECTRUM_COLUMNS)), np.nan)
+    for j in range(spec.shape[0]):
+        if counts[j] <= 0:
+            continue
+        yy, pp, cr, ci, ss = spec[j].sum(axis=1)                                  # outputs pooled: (K,)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            err = c * (ss / (M * M) + yy - 2.0 * cr / M)
+            small_y = (c * yy)[kmin:].sum()
+            coh = (cr * cr + ci * ci) / (ss * yy)
+            below = np.nonzero(coh < 0.5)[0]
+            out[j] = [(c * pp)[kmin:].sum() / M / small_y, (c * ss)[kmin:].sum() / (M * M) / small_y,
+                      float(below[0]) if below.size else float(K), err[kmin:].sum() / err.sum()]
+    return out
+
+
+def lead_time_spectrum(acc: SpectrumAccumulator, kmin: Optional[int] = None) -> np.ndarray:
+    """Small-scale figures per slot of a SpectrumAccumulator (a roll-out: per lead time), outputs pooled: (nslots, 4) in the
+    order of LEAD_SPECTRUM_COLUMNS -- the power of the members and of the ensemble mean at k >= kmin (default Wc // 8) over the
+    target's, the smallest k whose pooled coherence falls under 0.5 (K if none), and the share of the mean's error power at
+    k >= kmin; nan for an empty slot.  One device-to-host read."""
+    spec, counts = acc.sums()
+    return lead_spectrum_from_sums(spec, counts, acc.M, acc.Wc, kmin)
+
+
 # ------------------------------------------------------------------------------ ensemble roll-outs by lead time
 @torch.no_grad()
 def rollout_ensemble(net, dataset, starts: Sequence[int], horizon: int, spinup: int, members: int, ic_noise=0.05,
                      feedback_noise=0.0, seed: int = 0, batch_size: int = 8, lat=None, halo: Optional[Tuple[int, int]] = None,
-                     _allow_no_noise: bool = False) -> EnsembleAccumulator:
+                     _allow_no_noise: bool = False, spectrum: Optional[SpectrumAccumulator] = None) -> EnsembleAccumulator:
     """Ensemble verification of the free-running model by LEAD TIME.  From every record step in `starts`,
     `members` copies of the window of `spinup + horizon` steps run closed loop from step `spinup` as lanes of one batch --
     lane start_index * members + m -- and differ by their noise alone:
@@ -649,6 +857,9 @@ def rollout_ensemble(net, dataset, starts: Sequence[int], horizon: int, spinup: 
     (head_forward_seq), the targets come from the record, and the statistics kernel (nint_ens_accum) reads the members where
     they lie; the prediction made `j` steps into the free run goes to slot j of the returned EnsembleAccumulator:
     ``lead_time_table(acc)``, ``acc.report(dataset.y_mean, dataset.y_std, slots=[j])``.
+
+    `spectrum`: a SpectrumAccumulator(O, Hc, Wc, M=members, nslots=horizon, halo=halo) that is filled from the same members with
+    the same offsets; a mismatch is a ValueError before any device work.  None: nothing changes.
 
     Refused: what rollout_skill refuses, `members` outside [2, 64], a negative or non-finite std, and both noises zero --
     the members would be identical and the ensemble would have no spread."""
@@ -674,6 +885,8 @@ def rollout_ensemble(net, dataset, starts: Sequence[int], horizon: int, spinup: 
     O = net.conv.weight.shape[0]
     if O != dataset.levels:
         raise ValueError(f"rollout_ensemble: the head has {O} outputs, the record's tracer {dataset.levels} levels")
+    if spectrum is not None:
+        spectrum._check_rollout("rollout_ensemble", O, dataset.grid[0], dataset.grid[1], M, horizon, halo)
     net.eval()
     dev = next(net.parameters()).device
     eng = net._engine(dev)
@@ -696,4 +909,7 @@ def rollout_ensemble(net, dataset, starts: Sequence[int], horizon: int, spinup: 
         off = [((i * M) * T + spinup + j) * img for i in range(len(t0s)) for j in range(horizon)]
         acc.update(seq, off, T * img, y[:, spinup:].reshape(len(t0s) * horizon, O, Hc, Wc),
                    [j for _ in t0s for j in range(horizon)])
+        if spectrum is not None:
+            spectrum.update(seq, off, T * img, y[:, spinup:].reshape(len(t0s) * horizon, O, Hc, Wc),
+                            [j for _ in t0s for j in range(horizon)])
     return acc

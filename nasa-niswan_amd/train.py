@@ -8,7 +8,7 @@ once per epoch.  Added flags: --dtype, --levels, --grid, --synthetic-steps, --pa
 --static-channels, --sequence-loss, --test-skill, --lat-weighted-loss, --loss-weights, --clip-grad-norm,
 --skip-nonfinite-steps, --stateful, --bptt-segments, --accumulate-steps, --loss-mix, --huber-delta, --output-weights,
 --spinup-steps, --rollout-from, --sampling-prob, --sampling-ramp-epochs, --sampling-seed, --residual-head,
---tracer-noise, --noise-seed, --train-ensemble, --train-feedback-noise, --crps-alpha.
+--tracer-noise, --noise-seed, --train-ensemble, --train-feedback-noise, --crps-alpha, --test-spectrum.
 
 The data path is on the device too: by default every batch is written by ONE launch of the
 fuse / z-score / halo-pad kernel straight into the model's bf16 input slab (dataset.slab_batch);
@@ -148,6 +148,10 @@ def get_arguments(argv=None, MODEL='LSTM-00', SPECIES='bcb', LEARNING_RATE=1.0E-
     parser.add_argument("--ensemble-feedback-noise", type=float, default=None, metavar="S",
                         help="with --ensemble-members: std of the noise added to every fed-back value (default 0)")
     parser.add_argument("--ensemble-seed", type=int, default=None, metavar="K", help="with --ensemble-members: the noise seed (default 0)")
+    parser.add_argument("--test-spectrum", action="store_true",
+                        help="with --test-rollout: also accumulate the zonal power spectra of the roll-out (and, with "
+                             "--ensemble-members, of the ensemble) against the target's per lead time on the device "
+                             "(inference.SpectrumAccumulator), print the small-scale table and write rollout_spectrum.npz")
     parser.add_argument("--rollout-spinup", type=int, default=None, metavar="K",
                         help="steps of analysis input before the free run of --test-rollout (default: --sequence-length)")
     parser.add_argument("--rollout-from", type=int, default=None, metavar="K",
@@ -276,6 +280,8 @@ def get_arguments(argv=None, MODEL='LSTM-00', SPECIES='bcb', LEARNING_RATE=1.0E-
             parser.error("--ensemble-noise and --ensemble-feedback-noise are both 0: the ensemble would have no spread")
         if args.ensemble_seed < 0:
             parser.error("--ensemble-seed must be >= 0")
+    if args.test_spectrum and not args.test_rollout:
+        parser.error("--test-spectrum needs --test-rollout: the spectra are those of the roll-out's windows")
     if args.test_rollout > 0 and args.rollout_spinup < 1:
         parser.error("--rollout-spinup must be >= 1")
     if args.spinup_steps < 0:
@@ -492,8 +498,15 @@ def main(args):
             starts = list(range(t_lo, t_hi - span + 1, span))
             if not starts:
                 raise SystemExit(f"--test-rollout: the test period ({t_hi - t_lo} steps) holds no window of {span} steps")
+            spectra = {}
+            if args.test_spectrum:
+                from nasa_niswan_amd.inference import SpectrumAccumulator
+                for name, members in (("rollout", 1), ("ensemble", args.ensemble_members)):
+                    if members:
+                        spectra[name] = SpectrumAccumulator(test_dataset.levels, H, W, M=members, nslots=args.test_rollout,
+                                                            lat=grid_latitudes(H), device=dev)
             acc = rollout_skill(generator, test_dataset, starts, args.test_rollout, args.rollout_spinup, args.batch_size,
-                                lat=grid_latitudes(H))
+                                lat=grid_latitudes(H), spectrum=spectra.get("rollout"))
             r2_lead = [float(v) for v in lead_time_r2(acc)]
             logger['rollout_r2'] = r2_lead
             np.save(os.path.join(args.snapshot_dir, "rollout_r2.npy"), np.array(r2_lead))
@@ -503,7 +516,8 @@ def main(args):
                 from nasa_niswan_amd.inference import LEAD_TIME_COLUMNS, lead_time_table, rollout_ensemble
                 ens = rollout_ensemble(generator, test_dataset, starts, args.test_rollout, args.rollout_spinup, args.ensemble_members,
                                        ic_noise=args.ensemble_noise, feedback_noise=args.ensemble_feedback_noise,
-                                       seed=args.ensemble_seed, batch_size=args.batch_size, lat=grid_latitudes(H))
+                                       seed=args.ensemble_seed, batch_size=args.batch_size, lat=grid_latitudes(H),
+                                       spectrum=spectra.get("ensemble"))
                 table = lead_time_table(ens)
                 logger['rollout_ensemble'] = table
                 np.save(os.path.join(args.snapshot_dir, "rollout_ensemble_table.npy"), table)
@@ -512,6 +526,20 @@ def main(args):
                 print(f"Ensemble roll-out, {args.ensemble_members} members (z-score units): lead " + " ".join(LEAD_TIME_COLUMNS))
                 for j, row in enumerate(table):
                     print(f"  {j}: " + " ".join(f"{v:.4f}" for v in row))
+            if spectra:
+                from nasa_niswan_amd.inference import LEAD_SPECTRUM_COLUMNS, lead_time_spectrum
+                out, tables = {}, {}
+                for name, sp in spectra.items():
+                    spec, counts = sp.sums()
+                    tables[name] = lead_time_spectrum(sp)
+                    out.update({f"{name}_spec": spec, f"{name}_counts": counts, f"{name}_table": tables[name], f"{name}_members": sp.M})
+                    out.update({f"{name}_{k}": v for k, v in sp.report().arrays().items()})
+                    print(f"Zonal spectra of the {name}, {sp.M} member(s), k >= {sp.Wc // 8} as the small scales: lead "
+                          + " ".join(LEAD_SPECTRUM_COLUMNS))
+                    for j, row in enumerate(tables[name]):
+                        print(f"  {j}: " + " ".join(f"{v:.4f}" for v in row))
+                logger['rollout_spectrum'] = tables
+                np.savez(os.path.join(args.snapshot_dir, "rollout_spectrum.npz"), columns=np.array(LEAD_SPECTRUM_COLUMNS), **out)
         time_elapsed = time.time() - since
         print(f'Training complete in {time_elapsed // 60:.0f}m {time_elapsed % 60:.0f}s')
     if world > 1:
